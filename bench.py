@@ -10,12 +10,19 @@ Workload at N GPUs: BASELINE.json configs[1] per GPU (LineMOD obj_01, batch 16, 
 
 `value` is the launch form the PRODUCT ships by default: infer.GraphedPipeline captures the step as a hipGraph in two forms (one
 stream; pyramid / mesh branch / point branch forked onto side streams) and keeps the forked one only if it is bit-identical to the
-single-stream eager step on the box at hand -- the bench times whatever that logic kept (`config.launch`), and reports the other
-forms and the eager loop beside it (`launch_forms`).  Top-level extras on a 1-GPU run: `value_b32` (batch 32), `value_exact_f32`
-(strict fp32 products everywhere), `value_from_host` (PCIe-inclusive: every step's batch copied from pinned host memory first -- never
-the metric), `rooflines` (one entry per kernel family that dominates the step), `cpu_baseline`.
+single-stream eager step on the box at hand -- the bench times whatever that logic kept (`config.launch`).  A form whose timed
+replays are no longer bit-identical to the eager step is not the headline: the next form is timed instead (single-stream, then eager).
+
+A plain run does only that: set up, warm up, capture, time `--steps` steps of the headline form, write the last step's outputs
+(`--dump-outputs DIR`) and print the line.  `--full` adds everything else, as before: all launch forms and the eager loop timed
+beside the headline (`launch_forms`), the stage breakdown (`stage_ms`), the graph checks with an eager-vs-eager control, and on a
+1-GPU run the top-level extras `value_b32` (batch 32), `value_exact_f32` (strict fp32 products everywhere), `value_from_host`
+(PCIe-inclusive: every step's batch copied from pinned host memory first -- never the metric), `rooflines` (one entry per kernel
+family that dominates the step), `cpu_baseline` and the legs after the line (DGCNN variant, training step).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # DIR/<name>.npy: the last timed step's outputs
     python bench.py --gpus N ...            # starts N ranks itself (torch.distributed.run, one process per GPU, RCCL)
     python bench.py --group-of-one          # one rank INSIDE an RCCL group: the N-rank code path rehearsed on a 1-GPU box
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
@@ -64,7 +71,16 @@ def parse(argv=None):
                          "all run exactly as they do with N ranks")
     ap.add_argument("--probe-ranks", action="store_true",
                     help="launcher self-test: every rank joins the process group, all-reduces a 1 and rank 0 prints the count; no GPU work")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other launch forms and the eager loop, the stage breakdown, the extras, rooflines and CPU "
+                         "baseline (a plain run times the headline form only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: larger outputs are written as a fixed seeded sample)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args, argv, run=None):
@@ -588,6 +604,136 @@ def probe_ranks(args):
                           "torch_cuda_initialised": bool(torch.cuda.is_initialized())}), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of a step's output dict as out_dir/<name>.npy.  Floating arrays are written as float32 (float64
+    stays float64), boolean arrays as float32 and integer arrays as float64 (exact).  If the whole set exceeds `limit` bytes, the largest arrays are
+    replaced by a fixed sample of their flattened elements (RandomState(0), sorted positions: the same positions for the same
+    shapes) so that the set fits; the others are written whole.  Returns {name: [shape written, source shape, dtype written]}."""
+    import numpy as np
+    import torch
+    arrs = {}
+    for k in sorted(outs):
+        v = outs[k]
+        if not torch.is_tensor(v):
+            continue
+        a = v.detach().cpu()
+        if a.is_floating_point():
+            a = a.double() if a.dtype == torch.float64 else a.float()
+        else:
+            a = a.float() if a.dtype == torch.bool else a.double()
+        arrs[k] = a.numpy()
+    budget = limit - 256 * len(arrs)                        # room for the .npy headers
+    order = sorted(arrs, key=lambda k: arrs[k].nbytes)
+    written = {}
+    for i, k in enumerate(order):
+        a = arrs[k]
+        share = budget // (len(order) - i)                  # what is left, split evenly over this and the larger arrays
+        shape = list(a.shape)
+        if a.nbytes > share:
+            n = max(1, share // a.itemsize)
+            pos = np.sort(np.random.RandomState(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[pos]
+        budget -= a.nbytes
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        written[k] = [list(a.shape), shape, str(a.dtype)]
+    return written
+
+
+def plain_run(torch, dist, args, model, inputs, prec_name, rank, world, grouped):
+    """The plain run's timing: warm-up, the product's capture (infer.GraphedPipeline, both forms kept), then `args.steps` steps of the
+    headline form only.  The headline form is picked as the --full run picks it: forked if every rank's product logic kept it, else the
+    single-stream capture if bit-identical to the eager step on every rank, else the eager loop; a form whose timed replays are not
+    bit-identical to the eager step afterwards (on any rank) is dropped and the next one timed.  Returns (seconds for the timed steps,
+    max over ranks; form; outputs of the last timed step; graph check of the timed form; product check; a rank outside tolerance)."""
+    from geometric_aware_dense_matching_amd import infer, ops
+    step_pool = ops.BufferPool()
+    dev = inputs["rgb"].device
+
+    def step():
+        with ops.buffer_pool(step_pool):
+            return infer.pipeline_step(model, inputs, precision=prec_name, with_pose=False, keep_pyramid=True)
+
+    def sync_all():
+        torch.cuda.synchronize()
+        if grouped:
+            dist.barrier()
+            torch.cuda.synchronize()
+
+    def any_rank(flags):
+        """Element-wise OR of a list of booleans over the ranks."""
+        if not grouped:
+            return [bool(f) for f in flags]
+        t = torch.tensor([1.0 if f else 0.0 for f in flags], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return [v > 0 for v in t.tolist()]
+
+    gp, ref, product_check = None, None, None
+    with torch.no_grad():
+        if world > 1 and rank != 0:
+            dist.barrier()
+        for _ in range(max(args.warmup, 1)):
+            step()
+        torch.cuda.synchronize()
+        if world > 1 and rank == 0:
+            dist.barrier()
+        sync_all()
+        if not args.eager:
+            ref = {k: v.clone() for k, v in step().items() if torch.is_tensor(v)}
+            torch.cuda.synchronize()
+            try:
+                gp = infer.GraphedPipeline(model, inputs, precision=prec_name, with_pose=False, keep_pyramid=True,
+                                           forked=False if args.no_forked else "auto", keep_both=True,
+                                           capture_error_mode="thread_local" if grouped else None)
+                product_check = dict(gp.check, form=gp.form)
+            except Exception as e:                             # noqa: BLE001
+                product_check = {"error": "%s: %s" % (type(e).__name__, str(e).splitlines()[0] if str(e) else "")}
+                gp = None
+                torch.cuda.synchronize()
+        sync_all()
+        valid = {"forked": gp is not None and gp.form == "forked" and "forked" in gp.graphs,
+                 "single": gp is not None and "single" in gp.graphs and bool(gp.check.get("single", {}).get("bit_identical"))}
+        bad = any_rank([not valid["forked"], not valid["single"]])
+        candidates = [f for f, b in zip(("forked", "single"), bad) if not b] + ["eager"]
+        nwarm = max(3, min(args.warmup, 10))
+        check, outside = None, False
+        for form in candidates:
+            if form == "eager":
+                for _ in range(nwarm):
+                    step()
+                sync_all()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    out = step()
+                sync_all()
+                dt = time.perf_counter() - t0
+                check = None
+            else:
+                g = gp.graphs[form]
+                for _ in range(nwarm):
+                    g.replay()
+                sync_all()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    g.replay()
+                sync_all()
+                dt = time.perf_counter() - t0
+                out = gp.outs[form]
+                check = graph_check(torch, ref, out)           # the timed replays against the eager step
+                outside = outside or not check.get("ok")
+                if any_rank([not check.get("bit_identical")])[0]:
+                    continue                                   # a form whose timed replays drifted is not the headline
+            break
+        if grouped:
+            t = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        outside = any_rank([outside])[0]
+    return dt, form, out, check, product_check, outside
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
@@ -659,6 +805,44 @@ def main(argv=None):
     inputs = {k: torch.from_numpy(batch[k]).to(dev) for k in ("rgb", "cld_rgb_nrm", "choose", "dpt_xyz")}
     prec_name = "bf16x3" if args.precision == "bf16x3" else "f32"
     prec = ops.MATCH_BF16X3 if args.precision == "bf16x3" else ops.MATCH_F32
+    workload = ("LineMOD obj_01 batch=%d/GPU, N=%d scene pts x M=%d model kps, crop 256x256, geoMatch "
+                "(CNN+RandLA+SplineCNN) fwd-only + kNN pyramid + matching" % (B, N, M))
+    arithmetic = ("exact f32" if args.exact_f32 else
+                  "split-bf16 MFMA x3 (fp32 accumulate) for matching, trunk convolutions and 1x1 mixes; f32 elsewhere")
+    launch_text = {
+        "forked": "infer.GraphedPipeline default: hipGraph replay, FORKED form (pyramid / mesh branch / point branch on side streams), kept because bit-identical to the single-stream eager step before and after the timed replays",
+        "single": "infer.GraphedPipeline: hipGraph replay, single-stream form (the forked form was not offered or failed its bit-identity check on some rank)",
+        "eager": "eager loop of infer.pipeline_step (one host call per kernel; no valid hipGraph capture, or --eager)"}
+
+    if not args.full:
+        dt, form, outs, check, product_check, outside = plain_run(torch, dist, args, model, inputs, prec_name, rank, world, grouped)
+        value = world * B * args.steps / dt
+        line = {
+            "metric": "rgbd_crops_per_sec_geomatch_fwd", "value": round(value, 2), "unit": "crops/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32" if args.exact_f32 else "bf16x3/f32acc", "data": "synthetic", "full": False,
+            "config": {"workload": workload, "batch_per_gpu": B, "global_batch": B * world, "n_points": N, "n_model": M,
+                       "match_precision": args.precision, "product_arithmetic": arithmetic,
+                       "launch": launch_text[form], "side_streams": form == "forked",
+                       "mesh_cached": bool(args.cache_mesh), "parallelism": "dp%d" % world},
+            "value_default_form": round(value, 2),
+            "n_ranks_seen": n_ranks_seen, "gpus_flag": args.gpus, "process_group": backend_info,
+            "graph_check": check, "product_check": product_check, "ranks_outside_tolerance": int(outside),
+            "build": _lib.build_record(),
+        }
+        if args.exact_f32:
+            line["value_exact_f32"] = line["value"]
+        if rank == 0:
+            if args.dump_outputs:
+                os.makedirs(args.dump_outputs, exist_ok=True)
+                line["dumped_outputs"] = len(dump_outputs(outs, args.dump_outputs))
+            print(json.dumps(line), flush=True)
+        if grouped:
+            dist.destroy_process_group()
+        if args.strict and outside:
+            sys.exit(3)
+        return
 
     step_pool = ops.BufferPool()               # the eager step's scratch buffers (each captured form owns its own)
 
@@ -767,10 +951,12 @@ def main(argv=None):
         sync_all()
         t1 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            eager_last = step()
         dt_enqueue = time.perf_counter() - t1                      # host time to issue the eager steps (no wait for the GPU)
         sync_all()
         dt_eager = time.perf_counter() - t1
+        if args.dump_outputs:                                      # the step pool's buffers are reused by the staged steps below
+            eager_last = snap(eager_last)
         # stage breakdown from a few more, instrumented, eager steps OUTSIDE the timed region
         for _ in range(min(args.steps, 5)):
             staged_step()
@@ -786,9 +972,10 @@ def main(argv=None):
     # capture, else (no valid capture anywhere, or --eager) the eager loop.  It is NOT "whichever was fastest".
     which = 0 if forms[0] < INF else (1 if forms[1] < INF else 2)
     dt = forms[which]
-    launch = ("infer.GraphedPipeline default: hipGraph replay, FORKED form (pyramid / mesh branch / point branch on side streams), kept because bit-identical to the single-stream eager step before and after the timed replays",
-              "infer.GraphedPipeline: hipGraph replay, single-stream form (the forked form was not offered or failed its bit-identity check on some rank)",
-              "eager loop of infer.pipeline_step (one host call per kernel; no valid hipGraph capture, or --eager)")[which]
+    launch = launch_text[("forked", "single", "eager")[which]]
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = len(dump_outputs(gp.outs[("forked", "single")[which]] if which < 2 else eager_last, args.dump_outputs))
     if grouped:
         # every rank's check rides along: one rank outside tolerance is reported, it does not stop the others
         bad = 0.0 if all((c is None or c.get("ok")) for c in checks.values()) else 1.0
@@ -808,13 +995,11 @@ def main(argv=None):
         "metric": "rgbd_crops_per_sec_geomatch_fwd", "value": round(value, 2), "unit": "crops/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" if args.exact_f32 else "bf16x3/f32acc", "data": "synthetic",
-        "config": {"workload": "LineMOD obj_01 batch=%d/GPU, N=%d scene pts x M=%d model kps, crop 256x256, geoMatch "
-                               "(CNN+RandLA+SplineCNN) fwd-only + kNN pyramid + matching" % (B, N, M),
+        "dtype": "f32" if args.exact_f32 else "bf16x3/f32acc", "data": "synthetic", "full": True,
+        "config": {"workload": workload,
                    "batch_per_gpu": B, "global_batch": B * world, "n_points": N, "n_model": M,
                    "match_precision": args.precision,
-                   "product_arithmetic": "exact f32" if args.exact_f32 else
-                   "split-bf16 MFMA x3 (fp32 accumulate) for matching, trunk convolutions and 1x1 mixes; f32 elsewhere",
+                   "product_arithmetic": arithmetic,
                    "launch": launch, "side_streams": which == 0,
                    "mesh_cached": bool(args.cache_mesh), "parallelism": "dp%d" % world},
         "value_default_form": round(value, 2),           # = value: what a caller of infer.GraphedPipeline gets under its defaults
@@ -833,6 +1018,8 @@ def main(argv=None):
         "roofline": None, "roofline_fused": None, "rooflines": None, "cpu_baseline": None, "extras": None,
         "build": _lib.build_record(),
     }
+    if rank == 0 and args.dump_outputs:
+        line["dumped_outputs"] = dumped
     printed = []
 
     def emit():

@@ -135,3 +135,38 @@ def test_exact_f32_flag_covers_every_split_bf16_switch():
     assert len(envs) == len(settings.SPLIT_BF16_SWITCHES) and "GDM_OWN_STEM" in envs
     for name, env in zip(settings.SPLIT_BF16_SWITCHES, envs):
         assert env == "GDM_" + name[len("USE_"):], (name, env)
+
+
+def test_bench_flags_and_output_dump(tmp_path):
+    """A plain bench run times the headline form only (`--full` adds the rest); `--dump-outputs DIR` writes every output array of the
+    last timed step as DIR/<name>.npy in float32 / float64 (integers exactly), and a set above the size limit as a fixed sample."""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    g = torch.Generator().manual_seed(0)
+    outs = {"rgbd": torch.randn(4, 128, 512, generator=g), "best_idx": torch.randint(0, 1 << 20, (4, 512), dtype=torch.int32, generator=g),
+            "mask": torch.rand(4, 512, generator=g) > 0.5, "sim64": torch.randn(9, dtype=torch.float64, generator=g), "n": 3}
+    whole = tmp_path / "whole"
+    whole.mkdir()
+    w = bench.dump_outputs(outs, str(whole))
+    assert sorted(w) == ["best_idx", "mask", "rgbd", "sim64"]
+    for k in w:
+        got = np.load(str(whole / (k + ".npy")))
+        assert got.dtype in (np.float32, np.float64) and got.shape == tuple(outs[k].shape)
+        assert np.array_equal(got, outs[k].numpy().astype(got.dtype))
+    assert np.load(str(whole / "best_idx.npy")).dtype == np.float64
+    limit = 256 << 10
+    parts = [tmp_path / "s1", tmp_path / "s2"]
+    for p in parts:
+        p.mkdir()
+        bench.dump_outputs(outs, str(p), limit=limit)
+        assert sum(f.stat().st_size for f in p.iterdir()) <= limit
+    s1, s2 = (np.load(str(p / "rgbd.npy")) for p in parts)
+    assert s1.size < outs["rgbd"].numel() and np.array_equal(s1, s2)
+    assert np.isin(s1, outs["rgbd"].numpy()).all()

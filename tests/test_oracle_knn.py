@@ -61,13 +61,18 @@ def test_duplicate_points_same_distances_as_reference():
     assert np.array_equal(np.sort(a, axis=1), np.sort(b, axis=1))
 
 
-@pytest.mark.skipif(not oknn.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("S,Q,K", [(2048, 2048, 16), (512, 4096, 1), (4096, 512, 16), (32, 32, 16), (8, 1024, 1)])
 def test_oracle_equals_compiled_reference(S, Q, K):
+    """Against the compiled reference's recorded answer (tests/golden/make_golden_knn_ref.py), and against the compiled
+    reference itself when oracle/_ref is present."""
     rs = np.random.RandomState(S + Q + K)
     sup = rs.rand(2, S, 3).astype(np.float32)
     qry = rs.rand(2, Q, 3).astype(np.float32)
-    assert np.array_equal(oknn.knn_batch(sup, qry, K), oknn.ref_knn_batch(sup, qry, K))
+    got = oknn.knn_batch(sup, qry, K)
+    want = np.load(os.path.join(G, "knn_ref_cases.npz"))["oracle_S%d_Q%d_K%d" % (S, Q, K)]
+    assert np.array_equal(got, want.astype(np.int64))
+    if oknn.have_ref():
+        assert np.array_equal(got, oknn.ref_knn_batch(sup, qry, K))
 
 
 def test_k_larger_than_support_leaves_zero_slots():

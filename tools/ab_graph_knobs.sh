@@ -5,7 +5,7 @@ out=$1; shift; mkdir -p $out
 i=0
 for kv in "" "$@"; do
   i=$((i+1))
-  env $kv python bench.py --no-cpu-baseline --no-extras --steps 40 --warmup 5 > $out/run_$i.json 2> $out/run_$i.err
+  env $kv python bench.py --full --no-cpu-baseline --no-extras --steps 40 --warmup 5 > $out/run_$i.json 2> $out/run_$i.err
   rc=$?
   python - $out/run_$i.json "$kv" $rc <<'P'
 import json, sys

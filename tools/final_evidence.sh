@@ -3,10 +3,10 @@
 # `bench.py --gpus 2` itself.  Everything lands under gpurun_out/fin; copy what is to be judged into profiles/.
 set -o pipefail
 out=gpurun_out/fin; mkdir -p $out/prof $out/pmc_f $out/pmc_w $out/proft
-python bench.py > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
+python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
 cp gpurun_out/bench_extras.json $out/bench_extras.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o b -- python3 bench.py --no-cpu-baseline --no-extras --steps 10 --warmup 3 > $out/bench_prof.json 2> $out/bench_prof.err || exit 2
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o b -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 10 --warmup 3 > $out/bench_prof.json 2> $out/bench_prof.err || exit 2
 T=$(find $out/prof -name "*kernel_trace.csv" | head -1); S=$(find $out/prof -name "*kernel_stats.csv" | head -1)
 python tools/summarize_trace.py $T --steps 10 > $out/steady_state_b16.csv
 python tools/step_sequence.py $T > $out/step_sequence.txt
@@ -25,6 +25,6 @@ TT=$(find $out/proft -name "*kernel_trace.csv" | head -1)
 python tools/summarize_trace.py $TT --steps 5 --periodic > $out/train_steady_b24.csv
 find $out/proft -name "*.csv" -delete; find $out/proft -name "*.db" -delete
 echo "train profile done"
-python bench.py --gpus 2 --backend gloo --steps 10 --warmup 3 --no-heavy-extras > $out/two_rank.json 2> $out/two_rank.err || exit 3
-python bench.py --group-of-one --backend nccl --no-cpu-baseline --no-extras --steps 20 --warmup 3 > $out/rccl_group_of_one.json 2> $out/rccl_group_of_one.err || exit 8
+python bench.py --full --gpus 2 --backend gloo --steps 10 --warmup 3 --no-heavy-extras > $out/two_rank.json 2> $out/two_rank.err || exit 3
+python bench.py --full --group-of-one --backend nccl --no-cpu-baseline --no-extras --steps 20 --warmup 3 > $out/rccl_group_of_one.json 2> $out/rccl_group_of_one.err || exit 8
 head -c 300 $out/bench_n1.json; echo; head -1 $out/steady_state_b16.csv; tail -1 $out/step_sequence.txt; tail -1 $out/forked_replay_queues.txt; head -1 $out/train_steady_b24.csv; head -c 200 $out/two_rank.json
