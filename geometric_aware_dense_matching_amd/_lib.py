@@ -24,110 +24,6 @@ class KnnJob(ctypes.Structure):
                 ("S", ctypes.c_int32), ("Q", ctypes.c_int32), ("K", ctypes.c_int32), ("grid_w", ctypes.c_int32)]
 
 
-# name -> (restype, argtypes); must list every symbol include/gdm.h declares
-SIGNATURES = {
-    "gdm_last_error": (ctypes.c_char_p, []),
-    "gdm_version": (_i, []),
-    "gdm_knn_batch": (None, [_vp, _sz, _sz, _sz, _vp, _sz, _sz, _vp]),
-    "gdm_knn_batch_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_knn_jobs_hip": (_i, [ctypes.POINTER(KnnJob), _i, _i, _vp]),
-    "gdm_knn_jobs_workspace_bytes": (_sz, [ctypes.POINTER(KnnJob), _i, _i]),
-    "gdm_knn_jobs_ws_hip": (_i, [ctypes.POINTER(KnnJob), _i, _i, _vp, _sz, _vp]),
-    "gdm_ballquery_hip": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
-    "gdm_furthestsampling_hip": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
-    "gdm_interpolation_forward_hip": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_interpolation_backward_hip": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_labelstat_ballrange_hip": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_labelstat_idx_hip": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "gdm_group_gather_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_group_gather_bwd_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_group_gather_bwd2_hip": (_i, [_vp, ctypes.c_long, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_gather_max_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_gather_max_bwd_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_gather_nn_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_gather_nn_bwd_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_rel_pos_enc_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "gdm_att_pool_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_att_pool_bwd_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_match_workspace_bytes": (_sz, [_i, _i, _i]),
-    "gdm_match_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "gdm_match_rows_bytes": (_sz, [_i]),
-    "gdm_match_partial_bytes": (_sz, [_i, _i]),
-    "gdm_match_pack_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_match_pack2_hip": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
-    "gdm_match_packed_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "gdm_seg_mask_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "gdm_upsample_bilinear_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_upsample_bilinear_bwd_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_topk_rows_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp]),
-    "gdm_topk_negdist_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "gdm_affine_act_maxk_hip": (_i, [_vp, _vp, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _i, _f, _vp, _vp]),
-    "gdm_edge_feature_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_edge_feature_bwd_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_circle_rows_fwd_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "gdm_circle_rows_bwd_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_circle_match_rows_bytes": (_sz, [_i]),
-    "gdm_circle_match_tp_bytes": (_sz, [_i]),
-    "gdm_circle_match_pack_hip": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
-    "gdm_circle_match_nbr_hip": (_i, [_vp, _i, _f, _vp, _vp]),
-    "gdm_circle_match_visbits_hip": (_i, [_vp, _i, _i, _vp, _vp]),
-    "gdm_circle_match_fwd_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]),
-    "gdm_circle_match_bwd_parts": (_i, [_i, _i]),
-    "gdm_circle_match_bwd_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_kabsch_stats_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "gdm_kabsch_solve_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "gdm_lfa_stage_hip": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "gdm_affine_act_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _f, _vp, _vp]),
-    "gdm_prelu1_hip": (_i, [_vp, _vp, ctypes.c_long, _vp, _vp]),
-    "gdm_prelu1_bwd_hip": (_i, [_vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp]),
-    "gdm_upconv3x3_gather_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "gdm_upconv3x3_gather2_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
-    "gdm_upconv3x3_gather_bwd_hip": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_upconv_fused64_weight_bytes": (_sz, []),
-    "gdm_upconv_fused64_pack_weight_hip": (_i, [_vp, _vp, _vp]),
-    "gdm_upconv_fused64_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "gdm_psp_combine_hip": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_psp_combine2_hip": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_gather_add_affine_act_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "gdm_conv1x1_gather_add_act_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_long, _i, _f, _vp, _vp]),
-    "gdm_conv1x1_gather_add_act2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_long, _i, _f, _i, _vp, _vp]),
-    "gdm_pack_rows64_hip": (_i, [_vp, _i, _vp, _vp]),
-    "gdm_conv64_gather_add_act_mfma_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _i, _i, _vp, _vp]),
-    "gdm_conv64_gather_add_act_mfma2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _i, _i, _vp, _vp, _i, _vp]),
-    "gdm_point_heads_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
-    "gdm_point_heads2_hip": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
-    "gdm_upconv_final_points_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_conv3x3_act_bytes": (_sz, [_i, _i, _i, _i]),
-    "gdm_conv3x3_weight_bytes": (_sz, [_i, _i]),
-    "gdm_conv3x3_pack_weight_hip": (_i, [_vp, _i, _i, _vp, _vp]),
-    "gdm_conv3x3_pack_act_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_conv3x3_packed_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_conv3x3_packed2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_conv3x3_strided_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_conv1x1_strided_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_affine_relu_maxpool_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_conv1x1_logsoftmax_hip": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_long, _vp, _vp]),
-    "gdm_psp_pools_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_bn_sums_len": (ctypes.c_long, [_i, _i, ctypes.c_long]),
-    "gdm_bn_stats_hip": (_i, [_vp, _i, _i, ctypes.c_long, _vp, _vp]),
-    "gdm_bn_fwd_apply_hip": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_long, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_bn_bwd_reduce_hip": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _vp, _vp]),
-    "gdm_bn_bwd_apply_hip": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _vp, _vp, _vp, _vp]),
-    "gdm_psp_pools_bwd_hip": (_i, [_vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _vp, _vp]),
-    "gdm_conv1x1_weight_bytes": (_sz, [_i, _i]),
-    "gdm_conv1x1_pack_weight_hip": (_i, [_vp, _i, _i, _vp, _vp]),
-    "gdm_conv_pack_weight_dgrad_hip": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "gdm_conv1x1_packed_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_depth_to_xyz_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_spline_aggregate_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_spline_aggregate_bwd_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "gdm_spline_direct_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_gemm_grouped_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_spline_pairs_aggregate_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-}
-
-
-
 class PwSeg(ctypes.Structure):
     """gdm_pw_seg (include/gdm.h)."""
     _fields_ = [("x", _vp), ("idx", _vp), ("C", ctypes.c_int32), ("n_src", ctypes.c_int32)]
@@ -144,32 +40,116 @@ class CopyJob(ctypes.Structure):
                 ("B", ctypes.c_int32), ("R1", ctypes.c_int32), ("R2", ctypes.c_int32), ("E", ctypes.c_int32)]
 
 
-SIGNATURES["gdm_circle_match_nbr_items_hip"] = (_i, [_vp, _i, _vp, _i, _vp, _vp])
-SIGNATURES["gdm_circle_match_fwd2_hip"] = (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp])
-SIGNATURES["gdm_circle_match_bwd2_hip"] = (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp])
-SIGNATURES["gdm_stem_weight_bytes"] = (_sz, [])
-SIGNATURES["gdm_stem_pack_weight_hip"] = (_i, [_vp, _vp, _vp])
-SIGNATURES["gdm_stem_hip"] = (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp])
-SIGNATURES["gdm_wgrad_x_bytes"] = (_sz, [_i, _i, _i, _i])
-SIGNATURES["gdm_wgrad_go_bytes"] = (_sz, [_i, _i, _i, _i])
-SIGNATURES["gdm_wgrad_pack_x_hip"] = (_i, [_vp, _i, _i, _i, _i, _vp, _vp])
-SIGNATURES["gdm_wgrad_pack_go_hip"] = (_i, [_vp, _i, _i, _i, _i, _vp, _vp])
-SIGNATURES["gdm_conv1x1_packed_wb_hip"] = (_i, [_vp, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _vp])
-SIGNATURES["gdm_gather_add_affine_act2_hip"] = (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp])
-SIGNATURES["gdm_spline_direct3_hip"] = (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-SIGNATURES["gdm_spline_pairs_aggregate3_hip"] = (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp])
-SIGNATURES["gdm_spline_direct2_hip"] = (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp])
-SIGNATURES["gdm_spline_pairs_aggregate2_hip"] = (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp])
-SIGNATURES["gdm_wgrad_x1_bytes"] = (_sz, [_i, _i, _i])
-SIGNATURES["gdm_wgrad_pack_x1_hip"] = (_i, [_vp, _i, _i, _i, _vp, _vp])
-SIGNATURES["gdm_wgrad_direct_hip"] = (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _vp, _vp])
-SIGNATURES["gdm_mfma_probe_hip"] = (_i, [_i, _i, _i, _vp, _vp])
-SIGNATURES["gdm_mfma_probe_lds_hip"] = (_i, [_i, _i, _i, _vp, _vp])
-SIGNATURES["gdm_copy_jobs_hip"] = (_i, [ctypes.POINTER(CopyJob), _i, _vp])
-SIGNATURES["gdm_pointwise_chain2_hip"] = (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp])
-SIGNATURES["gdm_pointwise_jobs_hip"] = (_i, [ctypes.POINTER(PwJob), _i, _i, _i, _i, _vp])
-SIGNATURES["gdm_pointwise2_hip"] = (_i, [ctypes.POINTER(PwSeg), _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _i, _vp])
-SIGNATURES["gdm_pointwise_hip"] = (_i, [ctypes.POINTER(PwSeg), _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _i, _vp])
+# name -> (restype, argtypes) of every symbol include/gdm.h declares, in its order
+SIGNATURES = {
+    "gdm_last_error": (ctypes.c_char_p, []),
+    "gdm_version": (_i, []),
+    "gdm_knn_batch": (None, [_vp, _sz, _sz, _sz, _vp, _sz, _sz, _vp]),
+    "gdm_knn_batch_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_knn_jobs_workspace_bytes": (_sz, [ctypes.POINTER(KnnJob), _i, _i]),
+    "gdm_knn_jobs_ws_hip": (_i, [ctypes.POINTER(KnnJob), _i, _i, _vp, _sz, _vp]),
+    "gdm_ballquery_hip": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "gdm_furthestsampling_hip": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gdm_interpolation_forward_hip": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_interpolation_backward_hip": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_labelstat_ballrange_hip": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_labelstat_idx_hip": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gdm_group_gather_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_group_gather_bwd2_hip": (_i, [_vp, ctypes.c_long, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_gather_max_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_gather_max_bwd_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_rel_pos_enc_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "gdm_att_pool_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_att_pool_bwd_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_match_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gdm_match_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdm_match_rows_bytes": (_sz, [_i]),
+    "gdm_match_partial_bytes": (_sz, [_i, _i]),
+    "gdm_match_pack_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_match_pack2_hip": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "gdm_match_packed_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdm_seg_mask_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "gdm_spline_aggregate_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_spline_aggregate_bwd_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "gdm_spline_direct3_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gdm_gemm_grouped_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_spline_pairs_aggregate3_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gdm_upsample_bilinear_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_upsample_bilinear_bwd_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_topk_rows_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp]),
+    "gdm_topk_negdist_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "gdm_edge_feature_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_edge_feature_bwd_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_circle_rows_fwd_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "gdm_circle_rows_bwd_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_circle_match_rows_bytes": (_sz, [_i]),
+    "gdm_circle_match_tp_bytes": (_sz, [_i]),
+    "gdm_circle_match_pack_hip": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "gdm_circle_match_nbr_hip": (_i, [_vp, _i, _f, _vp, _vp]),
+    "gdm_circle_match_visbits_hip": (_i, [_vp, _i, _i, _vp, _vp]),
+    "gdm_circle_match_nbr_items_hip": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "gdm_circle_match_fwd2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp]),
+    "gdm_circle_match_bwd2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_circle_match_bwd_parts": (_i, [_i, _i]),
+    "gdm_lfa_stage_hip": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "gdm_kabsch_stats_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "gdm_kabsch_solve_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "gdm_affine_act_maxk_hip": (_i, [_vp, _vp, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _i, _f, _vp, _vp]),
+    "gdm_prelu1_hip": (_i, [_vp, _vp, ctypes.c_long, _vp, _vp]),
+    "gdm_prelu1_bwd_hip": (_i, [_vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp]),
+    "gdm_affine_act_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _f, _vp, _vp]),
+    "gdm_upconv3x3_gather_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "gdm_upconv3x3_gather2_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "gdm_upconv3x3_gather_bwd_hip": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_upconv_fused64_weight_bytes": (_sz, []),
+    "gdm_upconv_fused64_pack_weight_hip": (_i, [_vp, _vp, _vp]),
+    "gdm_upconv_fused64_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "gdm_psp_combine2_hip": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_gather_add_affine_act2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    "gdm_conv1x1_gather_add_act2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_long, _i, _f, _i, _vp, _vp]),
+    "gdm_conv64_gather_add_act_mfma2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _i, _i, _vp, _vp, _i, _vp]),
+    "gdm_conv3x3_act_bytes": (_sz, [_i, _i, _i, _i]),
+    "gdm_conv3x3_weight_bytes": (_sz, [_i, _i]),
+    "gdm_conv3x3_pack_weight_hip": (_i, [_vp, _i, _i, _vp, _vp]),
+    "gdm_conv3x3_pack_act_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_conv3x3_packed_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_conv3x3_strided_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_conv1x1_strided_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_affine_relu_maxpool_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_conv1x1_logsoftmax_hip": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_long, _vp, _vp]),
+    "gdm_pack_rows64_hip": (_i, [_vp, _i, _vp, _vp]),
+    "gdm_upconv_final_points_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_psp_pools_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_psp_pools_bwd_hip": (_i, [_vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _vp, _vp]),
+    "gdm_conv1x1_weight_bytes": (_sz, [_i, _i]),
+    "gdm_conv1x1_pack_weight_hip": (_i, [_vp, _i, _i, _vp, _vp]),
+    "gdm_conv_pack_weight_dgrad_hip": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "gdm_conv1x1_packed_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_depth_to_xyz_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_bn_sums_len": (ctypes.c_long, [_i, _i, ctypes.c_long]),
+    "gdm_bn_stats_hip": (_i, [_vp, _i, _i, ctypes.c_long, _vp, _vp]),
+    "gdm_bn_fwd_apply_hip": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_long, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_bn_bwd_reduce_hip": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _vp, _vp]),
+    "gdm_bn_bwd_apply_hip": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _vp, _vp, _vp, _vp]),
+    "gdm_point_heads2_hip": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "gdm_pointwise2_hip": (_i, [ctypes.POINTER(PwSeg), _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _i, _vp]),
+    "gdm_pointwise_jobs_hip": (_i, [ctypes.POINTER(PwJob), _i, _i, _i, _i, _vp]),
+    "gdm_pointwise_chain2_hip": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_stem_weight_bytes": (_sz, []),
+    "gdm_stem_pack_weight_hip": (_i, [_vp, _vp, _vp]),
+    "gdm_stem_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_wgrad_x_bytes": (_sz, [_i, _i, _i, _i]),
+    "gdm_wgrad_go_bytes": (_sz, [_i, _i, _i, _i]),
+    "gdm_wgrad_pack_x_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_wgrad_pack_go_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_wgrad_x1_bytes": (_sz, [_i, _i, _i]),
+    "gdm_wgrad_pack_x1_hip": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "gdm_mfma_probe_hip": (_i, [_i, _i, _i, _vp, _vp]),
+    "gdm_mfma_probe_lds_hip": (_i, [_i, _i, _i, _vp, _vp]),
+    "gdm_wgrad_direct_hip": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_conv1x1_packed_wb_hip": (_i, [_vp, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_copy_jobs_hip": (_i, [ctypes.POINTER(CopyJob), _i, _vp]),
+}
 
 _lib = None
 

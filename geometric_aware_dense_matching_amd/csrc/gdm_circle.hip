@@ -479,21 +479,13 @@ extern "C" int gdm_circle_match_fwd2_hip(const void* xrows, const void* xtp, con
                                          float* lse_p, float* lse_n, float* loss, void* stream)
 {
     CmArgs a;
-    int rc = fill_args(a, xrows, xtp, xpad, yrows, ytp, R, M, g, c2, item, nbr, visb, gamma, m, "gdm_circle_match_fwd_hip");
+    int rc = fill_args(a, xrows, xtp, xpad, yrows, ytp, R, M, g, c2, item, nbr, visb, gamma, m, "gdm_circle_match_fwd2_hip");
     if (rc) return rc;
-    GDM_CHECK_ARG(lse_p && lse_n && loss, "gdm_circle_match_fwd_hip: NULL output");
+    GDM_CHECK_ARG(lse_p && lse_n && loss, "gdm_circle_match_fwd2_hip: NULL output");
     a.lse_p = lse_p; a.lse_n = lse_n; a.loss = loss;
     a.nbr_istride = nbr_per_item ? (long)M * a.W : 0;
     a.pad_e0 = pad_e0 ? 1 : 0;
     return launch_mode<0>(a, c2 != nullptr, (hipStream_t)stream);
-}
-
-extern "C" int gdm_circle_match_fwd_hip(const void* xrows, const void* xtp, const float* xsum, const void* yrows, const void* ytp,
-                                        int R, int M, const int32_t* g, const int32_t* c2, const int32_t* item,
-                                        const uint32_t* nbr, const uint32_t* visb, float gamma, float m,
-                                        float* lse_p, float* lse_n, float* loss, void* stream)
-{
-    return gdm_circle_match_fwd2_hip(xrows, xtp, xsum, yrows, ytp, R, M, g, c2, item, nbr, 0, visb, 0, gamma, m, lse_p, lse_n, loss, stream);
 }
 
 extern "C" int gdm_circle_match_bwd_parts(int R, int M)
@@ -509,28 +501,14 @@ extern "C" int gdm_circle_match_bwd_parts(int R, int M)
 extern "C" int gdm_circle_match_bwd2_hip(const void* xrows, const void* xtp, const float* xpad, const void* yrows, const void* ytp,
                                          int R, int M, const int32_t* g, const int32_t* c2, const int32_t* item,
                                          const uint32_t* nbr, int nbr_per_item, const uint32_t* visb, int pad_e0, float gamma, float m,
-                                         const float* lse_p, const float* lse_n, const float* coef, float* gx, float* gy_part, void* stream);
-
-extern "C" int gdm_circle_match_bwd_hip(const void* xrows, const void* xtp, const float* xsum, const void* yrows, const void* ytp,
-                                        int R, int M, const int32_t* g, const int32_t* c2, const int32_t* item,
-                                        const uint32_t* nbr, const uint32_t* visb, float gamma, float m,
-                                        const float* lse_p, const float* lse_n, const float* coef, float* gx, float* gy_part, void* stream)
-{
-    return gdm_circle_match_bwd2_hip(xrows, xtp, xsum, yrows, ytp, R, M, g, c2, item, nbr, 0, visb, 0, gamma, m, lse_p, lse_n, coef, gx, gy_part,
-                                     stream);
-}
-
-extern "C" int gdm_circle_match_bwd2_hip(const void* xrows, const void* xtp, const float* xsum, const void* yrows, const void* ytp,
-                                         int R, int M, const int32_t* g, const int32_t* c2, const int32_t* item,
-                                         const uint32_t* nbr, int nbr_per_item, const uint32_t* visb, int pad_e0, float gamma, float m,
                                          const float* lse_p, const float* lse_n, const float* coef, float* gx, float* gy_part, void* stream)
 {
     CmArgs a;
-    int rc = fill_args(a, xrows, xtp, xsum, yrows, ytp, R, M, g, c2, item, nbr, visb, gamma, m, "gdm_circle_match_bwd_hip");
+    int rc = fill_args(a, xrows, xtp, xpad, yrows, ytp, R, M, g, c2, item, nbr, visb, gamma, m, "gdm_circle_match_bwd2_hip");
     if (rc) return rc;
     a.nbr_istride = nbr_per_item ? (long)M * a.W : 0;
     a.pad_e0 = pad_e0 ? 1 : 0;
-    GDM_CHECK_ARG(lse_p && lse_n && coef && gx && gy_part, "gdm_circle_match_bwd_hip: NULL pointer");
+    GDM_CHECK_ARG(lse_p && lse_n && coef && gx && gy_part, "gdm_circle_match_bwd2_hip: NULL pointer");
     a.lse_p = const_cast<float*>(lse_p); a.lse_n = const_cast<float*>(lse_n); a.coef = coef;
     a.gout = gx;
     if ((rc = launch_mode<1>(a, c2 != nullptr, (hipStream_t)stream))) return rc;

@@ -610,32 +610,34 @@ extern "C" int gdm_conv3x3_pack_act_hip(const float* x, int B, int Cin, int H, i
 // out (fp32 NCHW) and / or outpk (the packed operand of the next convolution over [B, Cout, H, W]; zero-filled once by the caller, only
 // interior pixels are written) -- at least one of them.
 static int conv3x3_launch(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
-                          int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream);
+                          int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream,
+                          const char* who);
 
-extern "C" int gdm_conv3x3_packed2_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
-                                       int B, int Cin, int Cout, int H, int W, int act, float* out, void* outpk, void* stream)
+extern "C" int gdm_conv3x3_packed_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
+                                      int B, int Cin, int Cout, int H, int W, int act, float* out, void* stream)
 {
-    return conv3x3_launch(xpk, wpk, scale, shift, res, B, Cin, Cout, H, W, 1, act, out, outpk, stream);
+    return conv3x3_launch(xpk, wpk, scale, shift, res, B, Cin, Cout, H, W, 1, act, out, nullptr, stream, "gdm_conv3x3_packed_hip");
 }
 
 // H, W = OUTPUT size; xpk = the (H stride) x (W stride) input packed by gdm_conv3x3_pack_act_hip; stride 1 or 2
 extern "C" int gdm_conv3x3_strided_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
                                        int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream)
 {
-    return conv3x3_launch(xpk, wpk, scale, shift, res, B, Cin, Cout, H, W, stride, act, out, outpk, stream);
+    return conv3x3_launch(xpk, wpk, scale, shift, res, B, Cin, Cout, H, W, stride, act, out, outpk, stream, "gdm_conv3x3_strided_hip");
 }
 
 static int conv3x3_launch(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
-                          int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream)
+                          int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream,
+                          const char* who)
 {
-    GDM_CHECK_ARG(stride == 1 || stride == 2, "gdm_conv3x3: stride=%d (1 or 2)", stride);
-    GDM_CHECK_ARG(xpk && wpk && (out || outpk), "gdm_conv3x3_packed_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cout >= 1, "gdm_conv3x3_packed_hip: Cin=%d Cout=%d (Cin a multiple of 128, or 64)", Cin, Cout);
+    GDM_CHECK_ARG(stride == 1 || stride == 2, "%s: stride=%d (1 or 2)", who, stride);
+    GDM_CHECK_ARG(xpk && wpk && (out || outpk), "%s: NULL pointer", who);
+    GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cout >= 1, "%s: Cin=%d Cout=%d (Cin a multiple of 128, or 64)", who, Cin, Cout);
     GDM_CHECK_ARG(W % 32 == 0 && H >= 1 && (H * W) % CONV_WPIX == 0,
-                  "gdm_conv3x3_packed_hip: W=%d must be a multiple of 32 and H*W=%d of %d", W, H * W, CONV_WPIX);
-    GDM_CHECK_ARG(act == 0 || act == 1, "gdm_conv3x3_packed_hip: act=%d", act);
+                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, CONV_WPIX);
+    GDM_CHECK_ARG(act == 0 || act == 1, "%s: act=%d", who, act);
     GDM_CHECK_ARG(!outpk || (Cout % 8 == 0 && ((long)B * H * W) % CV_PIX == 0),
-                  "gdm_conv3x3_packed_hip: packed output needs Cout %% 8 == 0 and B*H*W %% 256 == 0 (got Cout=%d, B*H*W=%ld)", Cout, (long)B * H * W);
+                  "%s: packed output needs Cout %% 8 == 0 and B*H*W %% 256 == 0 (got Cout=%d, B*H*W=%ld)", who, Cout, (long)B * H * W);
     const long ptot = (long)B * H * W;
     dim3 grid(gdm_cdiv(ptot, CV_PIX), gdm_cdiv(Cout, CV_CO));
     hipStream_t s = (hipStream_t)stream;
@@ -703,12 +705,6 @@ static int conv3x3_launch(const void* xpk, const void* wpk, const float* scale, 
     return gdm_launch_status("conv_mfma16_kernel (3x3)");
 }
 
-extern "C" int gdm_conv3x3_packed_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
-                                      int B, int Cin, int Cout, int H, int W, int act, float* out, void* stream)
-{
-    return gdm_conv3x3_packed2_hip(xpk, wpk, scale, shift, res, B, Cin, Cout, H, W, act, out, nullptr, stream);
-}
-
 // Grouped, gathered GEMM on the same kernel: Y[r, 0:128] = Wpk[tile_co0[r / 256] + 0:128, :] . X[rowidx[r], :] for R rows (R % 256 == 0),
 // X packed by gdm_conv3x3_pack_act_hip(x, 1, Cin, 1, M), weights packed by gdm_conv1x1_pack_weight_hip(Cout_total, Cin).
 extern "C" int gdm_gemm_grouped_hip(const void* xpk, const void* wpk, const int32_t* rowidx, const int32_t* tile_co0, int R, int M,
@@ -732,12 +728,13 @@ extern "C" int gdm_gemm_grouped_hip(const void* xpk, const void* wpk, const int3
 // 1x1 convolution / GEMM on the same kernel (one tap): out = act(scale * (W x) + shift), x packed by gdm_conv3x3_pack_act_hip.
 // pixel_major != 0 writes out[B*H*W, Cout] (row per pixel) instead of NCHW.
 static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, const float* shift,
-                          int B, int Cin, int Cout, int H, int W, int stride, int act, int pixel_major, float* out, void* stream);
+                          int B, int Cin, int Cout, int H, int W, int stride, int act, int pixel_major, float* out, void* stream,
+                          const char* who);
 
 extern "C" int gdm_conv1x1_packed_hip(const void* xpk, const void* wpk, const float* scale, const float* shift,
                                       int B, int Cin, int Cout, int H, int W, int act, int pixel_major, float* out, void* stream)
 {
-    return conv1x1_launch(xpk, wpk, scale, shift, B, Cin, Cout, H, W, 1, act, pixel_major, out, stream);
+    return conv1x1_launch(xpk, wpk, scale, shift, B, Cin, Cout, H, W, 1, act, pixel_major, out, stream, "gdm_conv1x1_packed_hip");
 }
 
 // the same GEMM with one weight set PER IMAGE (include/gdm.h: the split-K parts of the weight-gradient GEMM): H*W % 256 == 0
@@ -766,19 +763,20 @@ extern "C" int gdm_conv1x1_packed_wb_hip(const void* xpk, const void* wpk, long 
 extern "C" int gdm_conv1x1_strided_hip(const void* xpk, const void* wpk, const float* scale, const float* shift,
                                        int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* stream)
 {
-    return conv1x1_launch(xpk, wpk, scale, shift, B, Cin, Cout, H, W, stride, act, 0, out, stream);
+    return conv1x1_launch(xpk, wpk, scale, shift, B, Cin, Cout, H, W, stride, act, 0, out, stream, "gdm_conv1x1_strided_hip");
 }
 
 static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, const float* shift,
-                          int B, int Cin, int Cout, int H, int W, int stride, int act, int pixel_major, float* out, void* stream)
+                          int B, int Cin, int Cout, int H, int W, int stride, int act, int pixel_major, float* out, void* stream,
+                          const char* who)
 {
-    GDM_CHECK_ARG(stride == 1 || stride == 2, "gdm_conv1x1: stride=%d (1 or 2)", stride);
-    GDM_CHECK_ARG(xpk && wpk && out, "gdm_conv1x1_packed_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cout >= 1, "gdm_conv1x1_packed_hip: Cin=%d Cout=%d (Cin a multiple of 128, or 64)", Cin, Cout);
-    GDM_CHECK_ARG(Cin != 64 || !pixel_major, "gdm_conv1x1_packed_hip: Cin=64 is built for the NCHW output only");
+    GDM_CHECK_ARG(stride == 1 || stride == 2, "%s: stride=%d (1 or 2)", who, stride);
+    GDM_CHECK_ARG(xpk && wpk && out, "%s: NULL pointer", who);
+    GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cout >= 1, "%s: Cin=%d Cout=%d (Cin a multiple of 128, or 64)", who, Cin, Cout);
+    GDM_CHECK_ARG(Cin != 64 || !pixel_major, "%s: Cin=64 is built for the NCHW output only", who);
     GDM_CHECK_ARG(W % 32 == 0 && H >= 1 && (H * W) % CONV_WPIX == 0,
-                  "gdm_conv1x1_packed_hip: W=%d must be a multiple of 32 and H*W=%d of %d", W, H * W, CONV_WPIX);
-    GDM_CHECK_ARG(act == 0 || act == 1, "gdm_conv1x1_packed_hip: act=%d", act);
+                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, CONV_WPIX);
+    GDM_CHECK_ARG(act == 0 || act == 1, "%s: act=%d", who, act);
     const long ptot = (long)B * H * W;
     const unsigned ptiles = gdm_cdiv(ptot, CV_PIX);
     // 144-channel tiles (nine 16-channel blocks) where they divide Cout and fill the chip's rounds better than 128-channel ones: the

@@ -451,23 +451,14 @@ extern "C" int gdm_group_gather_hip(const float* feat, const int32_t* idx, int B
     return gdm_launch_status("group_gather_kernel");
 }
 
-extern "C" int gdm_group_gather_bwd2_hip(const float* go, long go_bstride, const int32_t* idx, int B, int C, int n, int m, int K,
-                                         float* gfeat, void* stream);
-
-extern "C" int gdm_group_gather_bwd_hip(const float* go, const int32_t* idx, int B, int C, int n, int m, int K,
-                                        float* gfeat, void* stream)
-{
-    return gdm_group_gather_bwd2_hip(go, (long)C * m * K, idx, B, C, n, m, K, gfeat, stream);
-}
-
 // go_bstride: floats between two batch items of go (rows of m * K floats, channel stride m * K): a channel slice of a concatenation's
 // gradient is read in place
 extern "C" int gdm_group_gather_bwd2_hip(const float* go, long go_bstride, const int32_t* idx, int B, int C, int n, int m, int K,
                                          float* gfeat, void* stream)
 {
-    GDM_CHECK_ARG(go && idx && gfeat, "gdm_group_gather_bwd_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && C >= 1 && n >= 1 && m >= 1 && K >= 1, "gdm_group_gather_bwd_hip: bad shape");
-    GDM_CHECK_ARG(go_bstride >= (long)C * m * K, "gdm_group_gather_bwd_hip: batch stride %ld below C*m*K", go_bstride);
+    GDM_CHECK_ARG(go && idx && gfeat, "gdm_group_gather_bwd2_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && C >= 1 && n >= 1 && m >= 1 && K >= 1, "gdm_group_gather_bwd2_hip: bad shape");
+    GDM_CHECK_ARG(go_bstride >= (long)C * m * K, "gdm_group_gather_bwd2_hip: batch stride %ld below C*m*K", go_bstride);
     const long gbs = go_bstride;
     const long mk = (long)m * K;
     if ((size_t)n * LCH * sizeof(float) <= 64 * 1024 && mk >= 4L * n && gdm_cdiv(C, LCH) <= 65535 && B <= 65535) {
@@ -487,19 +478,9 @@ extern "C" int gdm_group_gather_bwd2_hip(const float* go, long go_bstride, const
         return gdm_launch_status("group_gather_bwd_lds_kernel");
     }
     dim3 grid(gdm_cdiv(mk, GB), gdm_cdiv(C, CCHUNK), B);
-    GDM_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "gdm_group_gather_bwd_hip: grid too large");
+    GDM_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "gdm_group_gather_bwd2_hip: grid too large");
     hipLaunchKernelGGL(group_gather_bwd_kernel, grid, dim3(GB), 0, STREAM(stream), go, idx, C, n, mk, gfeat, gbs);
     return gdm_launch_status("group_gather_bwd_kernel");
-}
-
-extern "C" int gdm_gather_nn_hip(const float* feat, const int32_t* idx, int B, int C, int n, int m, float* out, void* stream)
-{
-    return gdm_group_gather_hip(feat, idx, B, C, n, m, 1, out, stream);
-}
-
-extern "C" int gdm_gather_nn_bwd_hip(const float* go, const int32_t* idx, int B, int C, int n, int m, float* gfeat, void* stream)
-{
-    return gdm_group_gather_bwd_hip(go, idx, B, C, n, m, 1, gfeat, stream);
 }
 
 extern "C" int gdm_gather_max_hip(const float* feat, const int32_t* idx, int B, int C, int n, int m, int K,

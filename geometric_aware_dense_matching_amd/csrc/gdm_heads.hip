@@ -193,21 +193,6 @@ __global__ __launch_bounds__(256, 2) void point_heads_kernel(HeadArgs A)
 extern "C" int gdm_point_heads2_hip(const float* a, const float* b, int Ca, const float* ra, const float* rb, int rCa, int B, int N, int nlayer,
                                     const void* const* w, const float* const* scale, const float* const* shift, const int* act, int feat_layer,
                                     int res_layer, const void* w_last, const float* shift_last, int c_last, float* out_feat, float* out_last,
-                                    void* stream);
-
-extern "C" int gdm_point_heads_hip(const float* a, const float* b, int Ca, int B, int N, int nlayer, const void* const* w,
-                                   const float* const* scale, const float* const* shift, const int* act, int feat_layer, int res_layer,
-                                   const void* w_last, const float* shift_last, int c_last, float* out_feat, float* out_last, void* stream)
-{
-    GDM_CHECK_ARG(w_last && out_feat && out_last && c_last >= 1, "gdm_point_heads_hip: NULL pointer / c_last=%d", c_last);
-    return gdm_point_heads2_hip(a, b, Ca, a, b, Ca, B, N, nlayer, w, scale, shift, act, feat_layer, res_layer, w_last, shift_last, c_last,
-                                out_feat, out_last, stream);
-}
-
-/* see include/gdm.h */
-extern "C" int gdm_point_heads2_hip(const float* a, const float* b, int Ca, const float* ra, const float* rb, int rCa, int B, int N, int nlayer,
-                                    const void* const* w, const float* const* scale, const float* const* shift, const int* act, int feat_layer,
-                                    int res_layer, const void* w_last, const float* shift_last, int c_last, float* out_feat, float* out_last,
                                     void* stream)
 {
     GDM_CHECK_ARG(a && w && scale && shift && act, "gdm_point_heads2_hip: NULL pointer");

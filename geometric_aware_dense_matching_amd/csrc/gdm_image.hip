@@ -1243,22 +1243,12 @@ extern "C" int gdm_upconv3x3_gather_bwd_hip(const float* grad_out, int B, int Co
 
 extern "C" int gdm_psp_combine2_hip(const float* g, const float* y1, int s1, const float* y2, int s2, const float* y3, int s3,
                                     const float* y4, int s4, const float* bias, int B, int C, int H, int W, float* out, void* outpk,
-                                    void* stream);
-
-extern "C" int gdm_psp_combine_hip(const float* g, const float* y1, int s1, const float* y2, int s2, const float* y3, int s3,
-                                   const float* y4, int s4, const float* bias, int B, int C, int H, int W, float* out, void* stream)
-{
-    return gdm_psp_combine2_hip(g, y1, s1, y2, s2, y3, s3, y4, s4, bias, B, C, H, W, out, nullptr, stream);
-}
-
-extern "C" int gdm_psp_combine2_hip(const float* g, const float* y1, int s1, const float* y2, int s2, const float* y3, int s3,
-                                    const float* y4, int s4, const float* bias, int B, int C, int H, int W, float* out, void* outpk,
                                     void* stream)
 {
-    GDM_CHECK_ARG(g && y1 && y2 && y3 && y4 && out, "gdm_psp_combine_hip: NULL pointer");
+    GDM_CHECK_ARG(g && y1 && y2 && y3 && y4 && out, "gdm_psp_combine2_hip: NULL pointer");
     GDM_CHECK_ARG(B >= 1 && C >= 1 && (long)B * C <= 65535 && H >= 1 && W >= 1 && s1 >= 1 && s2 >= 1 && s3 >= 1 && s4 >= 1,
-                  "gdm_psp_combine_hip: bad shape");
-    GDM_CHECK_ARG(s1 <= 8 && s2 <= 8 && s3 <= 8 && s4 <= 8, "gdm_psp_combine_hip: prior maps up to 8x8 (the reference uses 1, 2, 3, 6)");
+                  "gdm_psp_combine2_hip: bad shape");
+    GDM_CHECK_ARG(s1 <= 8 && s2 <= 8 && s3 <= 8 && s4 <= 8, "gdm_psp_combine2_hip: prior maps up to 8x8 (the reference uses 1, 2, 3, 6)");
     PspMaps maps;
     maps.y[0] = y1; maps.y[1] = y2; maps.y[2] = y3; maps.y[3] = y4;
     maps.s[0] = s1; maps.s[1] = s2; maps.s[2] = s3; maps.s[3] = s4;
@@ -1266,7 +1256,7 @@ extern "C" int gdm_psp_combine2_hip(const float* g, const float* y1, int s1, con
         maps.sy[k] = H > 1 ? (float)(maps.s[k] - 1) / (float)(H - 1) : 0.f;
         maps.sx[k] = W > 1 ? (float)(maps.s[k] - 1) / (float)(W - 1) : 0.f;
     }
-    GDM_CHECK_ARG(((long)H * W) % 4 == 0 && (((uintptr_t)g | (uintptr_t)out) & 15) == 0, "gdm_psp_combine_hip: H*W must be a multiple of 4 and the maps 16-byte aligned");
+    GDM_CHECK_ARG(((long)H * W) % 4 == 0 && (((uintptr_t)g | (uintptr_t)out) & 15) == 0, "gdm_psp_combine2_hip: H*W must be a multiple of 4 and the maps 16-byte aligned");
     int gx = gdm_cdiv((long)H * W, 1024);
     if (gx > 16) gx = 16;
     if (outpk) {
@@ -1280,18 +1270,12 @@ extern "C" int gdm_psp_combine2_hip(const float* g, const float* y1, int s1, con
     return gdm_launch_status("psp_combine_kernel");
 }
 
-extern "C" int gdm_gather_add_affine_act_hip(const float* x, const float* t, const int32_t* idx, const float* scale, const float* shift,
-                                             int B, int C, int n, int m, int act, float slope, float* y, void* stream)
-{
-    return gdm_gather_add_affine_act2_hip(x, t, idx, scale, shift, B, C, n, m, act, slope, y, nullptr, 0, stream);
-}
-
 extern "C" int gdm_gather_add_affine_act2_hip(const float* x, const float* t, const int32_t* idx, const float* scale, const float* shift,
                                               int B, int C, int n, int m, int act, float slope, float* y, void* y_packed, int W, void* stream)
 {
     unsigned char* ypk = (unsigned char*)y_packed;
-    GDM_CHECK_ARG(x && t && idx && scale && shift && y, "gdm_gather_add_affine_act_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && n >= 1 && m >= 1 && act >= 0 && act <= 2, "gdm_gather_add_affine_act_hip: bad shape");
+    GDM_CHECK_ARG(x && t && idx && scale && shift && y, "gdm_gather_add_affine_act2_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && n >= 1 && m >= 1 && act >= 0 && act <= 2, "gdm_gather_add_affine_act2_hip: bad shape");
     GDM_CHECK_ARG(!ypk || (W >= 1 && m % W == 0 && C % 8 == 0 && (C == 64 || C % 128 == 0) && ((uintptr_t)ypk & 15) == 0),
                   "gdm_gather_add_affine_act2_hip: packed output needs m %% W == 0, C = 64 or a multiple of 128, a 16-byte aligned buffer");
     dim3 grid(gdm_cdiv(m, 256), gdm_cdiv(C, 8), B);
@@ -1306,9 +1290,9 @@ extern "C" int gdm_conv1x1_gather_add_act2_hip(const float* x, const float* wt, 
                                                const float* shift, int B, int C, int n, long m, int act, float slope, int pixel_major,
                                                float* y, void* stream)
 {
-    GDM_CHECK_ARG(x && wt && t && idx && scale && shift && y, "gdm_conv1x1_gather_add_act_hip: NULL pointer");
-    GDM_CHECK_ARG(C == 64, "gdm_conv1x1_gather_add_act_hip: C=%d, only the 64-channel fusion levels are built", C);
-    GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && act >= 0 && act <= 2, "gdm_conv1x1_gather_add_act_hip: bad shape");
+    GDM_CHECK_ARG(x && wt && t && idx && scale && shift && y, "gdm_conv1x1_gather_add_act2_hip: NULL pointer");
+    GDM_CHECK_ARG(C == 64, "gdm_conv1x1_gather_add_act2_hip: C=%d, only the 64-channel fusion levels are built", C);
+    GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && act >= 0 && act <= 2, "gdm_conv1x1_gather_add_act2_hip: bad shape");
     dim3 grid(gdm_cdiv(m, 256), B);
     hipStream_t s = (hipStream_t)stream;
 #define CGA(A, P) hipLaunchKernelGGL((conv1x1_gather_add_act_kernel<64, A, P>), grid, dim3(256), 0, s, x, wt, t, idx, scale, shift, n, m, slope, y)
@@ -1316,12 +1300,6 @@ extern "C" int gdm_conv1x1_gather_add_act2_hip(const float* x, const float* wt, 
     else { if (act == 0) CGA(0, false); else if (act == 1) CGA(1, false); else CGA(2, false); }
 #undef CGA
     return gdm_launch_status("conv1x1_gather_add_act_kernel");
-}
-
-extern "C" int gdm_conv1x1_gather_add_act_hip(const float* x, const float* wt, const float* t, const int32_t* idx, const float* scale,
-                                              const float* shift, int B, int C, int n, long m, int act, float slope, float* y, void* stream)
-{
-    return gdm_conv1x1_gather_add_act2_hip(x, wt, t, idx, scale, shift, B, C, n, m, act, slope, 0, y, stream);
 }
 
 // ResNet stem tail: BatchNorm (folded) + ReLU + MaxPool2d(3, stride 2, padding 1) in one pass over the 7x7 convolution's output

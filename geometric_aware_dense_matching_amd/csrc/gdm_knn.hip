@@ -1226,21 +1226,20 @@ extern "C" size_t gdm_knn_jobs_workspace_bytes(const gdm_knn_job* jobs, int njob
     return total;
 }
 
-extern "C" int gdm_knn_jobs_ws_hip(const gdm_knn_job* jobs, int njobs, int B, void* workspace, size_t workspace_bytes, void* stream_)
+static int run_jobs(const gdm_knn_job* jobs, int njobs, int B, void* workspace, size_t workspace_bytes, hipStream_t stream, const char* who)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     int rc;
-    if ((rc = check_jobs(jobs, njobs, B, "gdm_knn_jobs_ws_hip"))) return rc;
-    GDM_CHECK_ARG(workspace || workspace_bytes == 0, "gdm_knn_jobs_ws_hip: NULL workspace with workspace_bytes=%zu", workspace_bytes);
-    GDM_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "gdm_knn_jobs_ws_hip: workspace must be 16-byte aligned");
+    if ((rc = check_jobs(jobs, njobs, B, who))) return rc;
+    GDM_CHECK_ARG(workspace || workspace_bytes == 0, "%s: NULL workspace with workspace_bytes=%zu", who, workspace_bytes);
+    GDM_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
     if ((rc = launch_k1(jobs, njobs, B, stream))) return rc;
     if ((rc = launch_wave(jobs, njobs, B, workspace, workspace_bytes, stream))) return rc;
     return 0;
 }
 
-extern "C" int gdm_knn_jobs_hip(const gdm_knn_job* jobs, int njobs, int B, void* stream_)
+extern "C" int gdm_knn_jobs_ws_hip(const gdm_knn_job* jobs, int njobs, int B, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return gdm_knn_jobs_ws_hip(jobs, njobs, B, nullptr, 0, stream_);
+    return run_jobs(jobs, njobs, B, workspace, workspace_bytes, (hipStream_t)stream, "gdm_knn_jobs_ws_hip");
 }
 
 extern "C" int gdm_knn_batch_hip(const float* support, const float* query, int B, int S, int Q, int K,
@@ -1257,7 +1256,7 @@ extern "C" int gdm_knn_batch_hip(const float* support, const float* query, int B
     j.Q = Q;
     j.K = K;
     j.grid_w = 0;
-    return gdm_knn_jobs_hip(&j, 1, B, stream);
+    return run_jobs(&j, 1, B, nullptr, 0, (hipStream_t)stream, "gdm_knn_batch_hip");
 }
 
 // Host-pointer drop-in with the reference's exact argument list (knn_.h:17-19).

@@ -602,35 +602,28 @@ bool seg_ok(const gdm_pw_seg& s, int n)
 
 } // namespace
 
-extern "C" int gdm_pointwise_hip(const gdm_pw_seg* segs, int nseg, const float* wt, const float* scale, const float* shift,
-                                 int B, int n, int Cout, int act, float slope, float* out, int out_C, int out_c0, int point_major,
-                                 void* stream)
-{
-    return gdm_pointwise2_hip(segs, nseg, wt, 0, scale, shift, B, n, Cout, act, slope, out, out_C, out_c0, point_major, stream);
-}
-
 extern "C" int gdm_pointwise2_hip(const gdm_pw_seg* segs, int nseg, const float* wt, int w_rowmajor, const float* scale, const float* shift,
                                   int B, int n, int Cout, int act, float slope, float* out, int out_C, int out_c0, int point_major,
                                   void* stream)
 {
-    GDM_CHECK_ARG(segs && wt && out, "gdm_pointwise_hip: NULL pointer");
-    GDM_CHECK_ARG(nseg >= 1 && nseg <= MAXSEG, "gdm_pointwise_hip: nseg=%d not in [1,%d]", nseg, MAXSEG);
-    GDM_CHECK_ARG(B >= 1 && n >= 1 && Cout >= 1, "gdm_pointwise_hip: bad shape B=%d n=%d Cout=%d", B, n, Cout);
-    GDM_CHECK_ARG(out_c0 >= 0 && out_c0 + Cout <= out_C, "gdm_pointwise_hip: channels [%d, %d) outside the output's %d", out_c0,
+    GDM_CHECK_ARG(segs && wt && out, "gdm_pointwise2_hip: NULL pointer");
+    GDM_CHECK_ARG(nseg >= 1 && nseg <= MAXSEG, "gdm_pointwise2_hip: nseg=%d not in [1,%d]", nseg, MAXSEG);
+    GDM_CHECK_ARG(B >= 1 && n >= 1 && Cout >= 1, "gdm_pointwise2_hip: bad shape B=%d n=%d Cout=%d", B, n, Cout);
+    GDM_CHECK_ARG(out_c0 >= 0 && out_c0 + Cout <= out_C, "gdm_pointwise2_hip: channels [%d, %d) outside the output's %d", out_c0,
                   out_c0 + Cout, out_C);
-    GDM_CHECK_ARG(act >= 0 && act <= 2, "gdm_pointwise_hip: act=%d", act);
+    GDM_CHECK_ARG(act >= 0 && act <= 2, "gdm_pointwise2_hip: act=%d", act);
     PwArgs a;
     a.K = 0;
     for (int s = 0; s < MAXSEG; ++s) {
         if (s < nseg) {
-            GDM_CHECK_ARG(seg_ok(segs[s], n), "gdm_pointwise_hip: segment %d: NULL / empty, or n_src=%d != n=%d without an index", s,
+            GDM_CHECK_ARG(seg_ok(segs[s], n), "gdm_pointwise2_hip: segment %d: NULL / empty, or n_src=%d != n=%d without an index", s,
                           segs[s].n_src, n);
             a.seg[s] = PwSegDev{segs[s].x, segs[s].idx, segs[s].C, segs[s].n_src};
             a.K += segs[s].C;
         } else
             a.seg[s] = PwSegDev{nullptr, nullptr, 0, 0};
     }
-    GDM_CHECK_ARG(((uintptr_t)out & 15) == 0, "gdm_pointwise_hip: out must be 16-byte aligned");
+    GDM_CHECK_ARG(((uintptr_t)out & 15) == 0, "gdm_pointwise2_hip: out must be 16-byte aligned");
     a.nseg = nseg;
     a.wt = wt;
     a.wks = w_rowmajor ? 1 : Cout;
@@ -647,7 +640,7 @@ extern "C" int gdm_pointwise2_hip(const gdm_pw_seg* segs, int nseg, const float*
     a.slope = slope;
     a.total = (long)B * n;
     const long tiles = (a.total + PT - 1) / PT;
-    GDM_CHECK_ARG(tiles <= 0x7fffffffL, "gdm_pointwise_hip: grid too large");
+    GDM_CHECK_ARG(tiles <= 0x7fffffffL, "gdm_pointwise2_hip: grid too large");
     hipStream_t st = (hipStream_t)stream;
     bool vec = (n % 4 == 0) && (Cout % 4 == 0) && (((uintptr_t)wt & 15) == 0) && !w_rowmajor;      // (the FMA form's 16-byte weight loads run along Cout)
     for (int s = 0; s < nseg; ++s) vec = vec && !segs[s].idx && (((uintptr_t)segs[s].x & 15) == 0);
@@ -687,7 +680,7 @@ extern "C" int gdm_pointwise2_hip(const gdm_pw_seg* segs, int nseg, const float*
         return gdm_launch_status("pointwise_mfma_kernel");
     }
     // K < 32 (or more than 2^20 output channels): the FMA form, four waves per 64 x 64 tile, no K split
-    GDM_CHECK_ARG(nseg <= 3, "gdm_pointwise_hip: four segments need K >= 32 (the MFMA form)");
+    GDM_CHECK_ARG(nseg <= 3, "gdm_pointwise2_hip: four segments need K >= 32 (the MFMA form)");
     GDM_PW_LAUNCH(4, 1, 64);
 #undef GDM_PW_LAUNCH
     return gdm_launch_status("pointwise_kernel");
@@ -697,7 +690,7 @@ extern "C" int gdm_pointwise_jobs_hip(const gdm_pw_job* jobs, int njobs, int B, 
 {
     GDM_CHECK_ARG(jobs && njobs >= 1 && njobs <= 4, "gdm_pointwise_jobs_hip: njobs=%d not in [1,4]", njobs);
     GDM_CHECK_ARG(B >= 1 && K >= 32 && Cout >= 1 && gdm_cdiv(Cout, 16) <= 65535, "gdm_pointwise_jobs_hip: bad shape B=%d K=%d Cout=%d", B, K, Cout);
-    // the K split of gdm_pointwise_hip is chosen PER JOB there (from its own grid size); a job launched here must agree with its separate
+    // the K split of gdm_pointwise2_hip is chosen PER JOB there (from its own grid size); a job launched here must agree with its separate
     // launch bit for bit, so jobs are launched together only with the jobs that take the same split: one launch per distinct split
     // (the pyramid-pooling products at batch 16: all four take eight parts -> one launch; at batch 32 the 36-bin job takes four -> two)
     int kjob[4] = {0, 0, 0, 0};

@@ -348,9 +348,9 @@ extern "C" int gdm_spline_pairs_aggregate3_hip(const float* Y, const int32_t* ro
                                                void* out_packed, void* stream)
 {
     unsigned char* out_pk = (unsigned char*)out_packed;
-    GDM_CHECK_ARG(Y && rowptr && pos && basis && (out || out_t), "gdm_spline_pairs_aggregate_hip: NULL pointer");
+    GDM_CHECK_ARG(Y && rowptr && pos && basis && (out || out_t), "gdm_spline_pairs_aggregate3_hip: NULL pointer");
     GDM_CHECK_ARG(!out_pk || (C % 128 == 0 && C <= 512), "gdm_spline_pairs_aggregate3_hip: the packed output needs C = 128, 256 or 512");
-    GDM_CHECK_ARG(M >= 1 && C >= 1, "gdm_spline_pairs_aggregate_hip: bad shape");
+    GDM_CHECK_ARG(M >= 1 && C >= 1, "gdm_spline_pairs_aggregate3_hip: bad shape");
     if (C % 4 == 0 && C <= 512 && 512 % C == 0 && ((uintptr_t)Y & 15) == 0 && ((uintptr_t)out & 15) == 0 && (!root || ((uintptr_t)root & 15) == 0) &&
         (!bias || ((uintptr_t)bias & 15) == 0)) {
         const dim3 grid(gdm_cdiv(M, 128 / (C / 4)));
@@ -360,7 +360,7 @@ extern "C" int gdm_spline_pairs_aggregate3_hip(const float* Y, const int32_t* ro
             hipLaunchKernelGGL(spline_pairs_aggregate_vec_kernel<false>, grid, dim3(128), 0, (hipStream_t)stream, Y, rowptr, pos, basis, root, bias, M, C, out, out_t, out_pk);
         return gdm_launch_status("spline_pairs_aggregate_vec_kernel");
     }
-    GDM_CHECK_ARG(out && !out_t && !out_pk, "gdm_spline_pairs_aggregate2_hip: the channel-major / packed outputs need C %% 4 == 0, 512 %% C == 0 and 16-byte aligned buffers");
+    GDM_CHECK_ARG(out && !out_t && !out_pk, "gdm_spline_pairs_aggregate3_hip: the channel-major / packed outputs need C %% 4 == 0, 512 %% C == 0 and 16-byte aligned buffers");
     if (relu)
         hipLaunchKernelGGL(spline_pairs_aggregate_kernel<true>, dim3(M), dim3(128), 0, (hipStream_t)stream, Y, rowptr, pos, basis, root, bias, C, out);
     else
@@ -368,48 +368,14 @@ extern "C" int gdm_spline_pairs_aggregate3_hip(const float* Y, const int32_t* ro
     return gdm_launch_status("spline_pairs_aggregate_kernel");
 }
 
-extern "C" int gdm_spline_pairs_aggregate2_hip(const float* Y, const int32_t* rowptr, const int32_t* pos, const float* basis,
-                                               const float* root, const float* bias, int M, int C, int relu, float* out, float* out_t,
-                                               void* stream)
-{
-    return gdm_spline_pairs_aggregate3_hip(Y, rowptr, pos, basis, root, bias, M, C, relu, out, out_t, nullptr, stream);
-}
-
-extern "C" int gdm_spline_pairs_aggregate_hip(const float* Y, const int32_t* rowptr, const int32_t* pos, const float* basis,
-                                              const float* root, const float* bias, int M, int C, int relu, float* out, void* stream)
-{
-    return gdm_spline_pairs_aggregate2_hip(Y, rowptr, pos, basis, root, bias, M, C, relu, out, nullptr, stream);
-}
-
-extern "C" int gdm_spline_direct2_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
-                                     const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
-                                     float* out, float* out_t, void* stream);
-extern "C" int gdm_spline_direct3_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
-                                     const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
-                                     float* out, float* out_t, void* out_packed, void* stream);
-
-extern "C" int gdm_spline_direct_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
-                                     const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
-                                     float* out, void* stream)
-{
-    return gdm_spline_direct2_hip(x, weight, rowptr, src, attr, root_t, bias, M, Cin, C, kernel_size, relu, out, nullptr, stream);
-}
-
-extern "C" int gdm_spline_direct2_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
-                                     const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
-                                     float* out, float* out_t, void* stream)
-{
-    return gdm_spline_direct3_hip(x, weight, rowptr, src, attr, root_t, bias, M, Cin, C, kernel_size, relu, out, out_t, nullptr, stream);
-}
-
 extern "C" int gdm_spline_direct3_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
                                      const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
                                      float* out, float* out_t, void* out_packed, void* stream)
 {
     unsigned char* out_pk = (unsigned char*)out_packed;
-    GDM_CHECK_ARG(x && weight && rowptr && src && attr && (out || out_t), "gdm_spline_direct_hip: NULL pointer");
+    GDM_CHECK_ARG(x && weight && rowptr && src && attr && (out || out_t), "gdm_spline_direct3_hip: NULL pointer");
     GDM_CHECK_ARG(!out_pk || (C % 128 == 0 && C <= 512), "gdm_spline_direct3_hip: the packed output needs C = 128, 256 or 512");
-    GDM_CHECK_ARG(M >= 1 && C >= 1 && kernel_size >= 2 && Cin >= 1 && Cin <= 16, "gdm_spline_direct_hip: bad shape M=%d Cin=%d (<= 16) C=%d ks=%d", M, Cin, C, kernel_size);
+    GDM_CHECK_ARG(M >= 1 && C >= 1 && kernel_size >= 2 && Cin >= 1 && Cin <= 16, "gdm_spline_direct3_hip: bad shape M=%d Cin=%d (<= 16) C=%d ks=%d", M, Cin, C, kernel_size);
     const bool vec = C % 4 == 0 && C <= 512 && 512 % C == 0 && ((uintptr_t)weight & 15) == 0 && ((uintptr_t)out & 15) == 0 &&
                      (!root_t || ((uintptr_t)root_t & 15) == 0) && (!bias || ((uintptr_t)bias & 15) == 0);
     if (vec) {
@@ -423,7 +389,7 @@ extern "C" int gdm_spline_direct3_hip(const float* x, const float* weight, const
                                bias, M, Cin, C, kernel_size, out, out_t, out_pk);
         return gdm_launch_status("spline_direct_vec_kernel");
     }
-    GDM_CHECK_ARG(out && !out_t && !out_pk, "gdm_spline_direct2_hip: the channel-major / packed outputs need C %% 4 == 0, 512 %% C == 0 and 16-byte aligned buffers");
+    GDM_CHECK_ARG(out && !out_t && !out_pk, "gdm_spline_direct3_hip: the channel-major / packed outputs need C %% 4 == 0, 512 %% C == 0 and 16-byte aligned buffers");
     if (relu)
         hipLaunchKernelGGL((spline_direct_kernel<true, 16>), dim3(M), dim3(128), 0, (hipStream_t)stream, x, weight, rowptr, src, attr, root_t, bias, Cin, C, kernel_size, out);
     else

@@ -626,21 +626,10 @@ extern "C" int gdm_upconv_final_points_hip(const float* xpm, const int32_t* choo
 
 extern "C" int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
                                                    const float* shift, int B, int n, long m, int act, float slope, int pixel_major,
-                                                   int t_point_major, float* y, void* ypk, int W, void* stream);
-
-extern "C" int gdm_conv64_gather_add_act_mfma_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
-                                                  const float* shift, int B, int n, long m, int act, float slope, int pixel_major,
-                                                  int t_point_major, float* y, void* stream)
-{
-    return gdm_conv64_gather_add_act_mfma2_hip(x, wpk, t, idx, scale, shift, B, n, m, act, slope, pixel_major, t_point_major, y, nullptr, 0, stream);
-}
-
-extern "C" int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
-                                                   const float* shift, int B, int n, long m, int act, float slope, int pixel_major,
                                                    int t_point_major, float* y, void* ypk, int W, void* stream)
 {
-    GDM_CHECK_ARG(x && wpk && t && idx && scale && shift && y, "gdm_conv64_gather_add_act_mfma_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && m <= 0x7fffffffL && act >= 0 && act <= 2, "gdm_conv64_gather_add_act_mfma_hip: bad shape");
+    GDM_CHECK_ARG(x && wpk && t && idx && scale && shift && y, "gdm_conv64_gather_add_act_mfma2_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && m <= 0x7fffffffL && act >= 0 && act <= 2, "gdm_conv64_gather_add_act_mfma2_hip: bad shape");
     GDM_CHECK_ARG(!ypk || (!pixel_major && W >= 1 && m % W == 0 && ((uintptr_t)ypk & 15) == 0),
                   "gdm_conv64_gather_add_act_mfma2_hip: packed output goes with the NCHW form of an [m / W, W] map (m=%ld W=%d)", m, W);
     unsigned char* ypk8 = (unsigned char*)ypk;

@@ -275,7 +275,7 @@ class _GroupGather(torch.autograd.Function):
             go = go.contiguous()
         g = torch.zeros((B, C, ctx.n), dtype=torch.float32, device=go.device)
         check(_lib.lib().gdm_group_gather_bwd2_hip(go.data_ptr(), go.stride(0), idx.data_ptr(), B, C, ctx.n, m, K, g.data_ptr(), _stream()),
-              "gdm_group_gather_bwd_hip")
+              "gdm_group_gather_bwd2_hip")
         return g, None
 
 
@@ -554,7 +554,7 @@ class _CircleMatch(torch.autograd.Function):
                                                    gp.data_ptr(), c2p.data_ptr() if c2p is not None else None, ip.data_ptr(),
                                                    nbr.data_ptr() if nbr is not None else None, int(per_item),
                                                    visb.data_ptr() if visb is not None else None, int(bool(pad_e0)),
-                                                   gamma, m, lp.data_ptr(), ln.data_ptr(), loss.data_ptr(), _stream()), "gdm_circle_match_fwd_hip")
+                                                   gamma, m, lp.data_ptr(), ln.data_ptr(), loss.data_ptr(), _stream()), "gdm_circle_match_fwd2_hip")
         ctx.save_for_backward(xr, xt, xs, yr, yt, gp, ip, lp, ln)
         ctx.extra = (c2p, nbr, visb, gamma, m, R, M, per_item, bool(pad_e0))
         return loss[:R]
@@ -577,7 +577,7 @@ class _CircleMatch(torch.autograd.Function):
                                           nbr.data_ptr() if nbr is not None else None, int(per_item),
                                           visb.data_ptr() if visb is not None else None, int(pad_e0),
                                           gamma, m, lp.data_ptr(), ln.data_ptr(), coef.data_ptr(), gx.data_ptr(), gyp.data_ptr(), _stream()),
-              "gdm_circle_match_bwd_hip")
+              "gdm_circle_match_bwd2_hip")
         return gx[:R], gyp.sum(dim=0)[:M], None, None, None, None, None, None, None, None
 
 
@@ -647,7 +647,7 @@ def _pw_seg(spec, B, name):
 
 
 def pointwise(segs, wt, scale=None, shift=None, act=ACT_NONE, slope=0.0, point_major=False, out=None, out_c0=0, w_rowmajor=False):
-    """One per-point (1x1) layer in one launch (include/gdm.h gdm_pointwise_hip), inference only:
+    """One per-point (1x1) layer in one launch (include/gdm.h gdm_pointwise2_hip), inference only:
         y[b,:,i] = act(scale * (W . cat(segs)[b,:,i]) + shift)
     segs: a list of one to three of  x f32[B,C,n(,1)]  or  (x f32[B,C,n_src(,1)], idx int[B,n(,1)])  -- the concat along channels
     is never formed, an indexed segment is read through its index (nearest-neighbour interpolation folded into the load).
@@ -689,7 +689,7 @@ def pointwise(segs, wt, scale=None, shift=None, act=ACT_NONE, slope=0.0, point_m
             raise ValueError("pointwise: out must be a contiguous f32 [B,%s] tensor" % ("n,outC" if point_major else "outC,n"))
     check(_lib.lib().gdm_pointwise2_hip(arr, len(segs), wt.data_ptr(), 1 if w_rowmajor else 0, scale.data_ptr() if scale is not None else None,
                                         shift.data_ptr() if shift is not None else None, B, n, Cout, int(act), float(slope),
-                                        out.data_ptr(), outC, int(out_c0), 1 if point_major else 0, _stream()), "gdm_pointwise_hip")
+                                        out.data_ptr(), outC, int(out_c0), 1 if point_major else 0, _stream()), "gdm_pointwise2_hip")
     return out
 
 
@@ -1230,7 +1230,7 @@ def conv1x1_gather_add_act(x, wt, t, idx, scale, shift, act=ACT_NONE, slope=0.0,
     y = torch.empty((B, m, C), dtype=torch.float32, device=x.device) if pixel_major else torch.empty_like(x)
     check(_lib.lib().gdm_conv1x1_gather_add_act2_hip(x.data_ptr(), wt.data_ptr(), t.data_ptr(), idx.data_ptr(), scale.data_ptr(),
                                                      shift.data_ptr(), B, C, t.shape[2], m, act, float(slope), int(bool(pixel_major)),
-                                                     y.data_ptr(), _stream()), "gdm_conv1x1_gather_add_act_hip")
+                                                     y.data_ptr(), _stream()), "gdm_conv1x1_gather_add_act2_hip")
     return y
 
 
@@ -1420,10 +1420,10 @@ class _PspCombine(torch.autograd.Function):
         ys = [_dev(y, torch.float32, "y") for y in (y1, y2, y3, y4)]
         B, C, H, W = g.shape
         out = torch.empty_like(g)
-        check(_lib.lib().gdm_psp_combine_hip(g.data_ptr(), ys[0].data_ptr(), ys[0].shape[2], ys[1].data_ptr(), ys[1].shape[2],
-                                             ys[2].data_ptr(), ys[2].shape[2], ys[3].data_ptr(), ys[3].shape[2],
-                                             bias.data_ptr() if bias is not None else None, B, C, H, W, out.data_ptr(), _stream()),
-              "gdm_psp_combine_hip")
+        check(_lib.lib().gdm_psp_combine2_hip(g.data_ptr(), ys[0].data_ptr(), ys[0].shape[2], ys[1].data_ptr(), ys[1].shape[2],
+                                              ys[2].data_ptr(), ys[2].shape[2], ys[3].data_ptr(), ys[3].shape[2],
+                                              bias.data_ptr() if bias is not None else None, B, C, H, W, out.data_ptr(), None, _stream()),
+              "gdm_psp_combine2_hip")
         ctx.save_for_backward(out)
         ctx.sizes = [y.shape[2] for y in ys]
         ctx.has_bias = bias is not None

@@ -134,9 +134,9 @@ class SplineConv(nn.Module):
                 self.__dict__["_gdm_root_t"] = cache
             out = torch.empty((M, self.cout), dtype=torch.float32, device=x.device)
             xc = x.contiguous()
-            check(_lib.lib().gdm_spline_direct_hip(xc.data_ptr(), self.weight.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
-                                                   cache[1].data_ptr(), self.bias.data_ptr(), M, self.cin, self.cout, KERNEL_SIZE, int(relu),
-                                                   out.data_ptr(), ops._stream()), "gdm_spline_direct_hip")
+            check(_lib.lib().gdm_spline_direct3_hip(xc.data_ptr(), self.weight.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
+                                                    cache[1].data_ptr(), self.bias.data_ptr(), M, self.cin, self.cout, KERNEL_SIZE, int(relu),
+                                                    out.data_ptr(), None, None, ops._stream()), "gdm_spline_direct3_hip")
             return out
         if (settings.USE_MFMA_GEMM and settings.USE_GROUPED_SPLINE and pairs is not None and not torch.is_grad_enabled() and x.is_cuda
                 and self.cin % 128 == 0 and self.cout == 128):
@@ -157,9 +157,9 @@ class SplineConv(nn.Module):
             else:
                 root = self.lin(x)
             out = torch.empty((M, self.cout), dtype=torch.float32, device=x.device)
-            check(_lib.lib().gdm_spline_pairs_aggregate_hip(Y.data_ptr(), rowptr.data_ptr(), pairs["pos"].data_ptr(), pairs["basis"].data_ptr(),
-                                                            root.data_ptr(), self.bias.data_ptr(), M, self.cout, int(relu), out.data_ptr(),
-                                                            ops._stream()), "gdm_spline_pairs_aggregate_hip")
+            check(_lib.lib().gdm_spline_pairs_aggregate3_hip(Y.data_ptr(), rowptr.data_ptr(), pairs["pos"].data_ptr(), pairs["basis"].data_ptr(),
+                                                             root.data_ptr(), self.bias.data_ptr(), M, self.cout, int(relu), out.data_ptr(),
+                                                             None, None, ops._stream()), "gdm_spline_pairs_aggregate3_hip")
             return out
         if (settings.USE_MFMA_GEMM and not torch.is_grad_enabled() and x.is_cuda
                 and ops.gemm_supported(self.cin, nk * self.cout, M)):

@@ -65,12 +65,11 @@ typedef struct gdm_knn_job {
                                * results are identical with and without it, for any data                                            */
 } gdm_knn_job;
 #define GDM_KNN_MAX_JOBS 32
-int gdm_knn_jobs_hip(const gdm_knn_job* jobs /* host array */, int njobs, int B, void* stream);
-/* Same, with a device workspace (16-byte aligned, >= gdm_knn_jobs_workspace_bytes) in which every distinct support set of the
- * K > 1 jobs is re-laid out once: small unorganised supports as hashed float4 tiles that the search blocks stream with coalesced
- * loads, unorganised supports of >= 1024 points as (x, y) cell lists (a counting sort per crop; a query then visits cells ring by
- * ring instead of every point), organised supports (grid_w) as per-column / per-row ratio ranges; without it (gdm_knn_jobs_hip)
- * each block gathers its tiles from the [S,3] array.  Results are identical in every form, for any data.                       */
+/* jobs is a HOST array.  workspace: device memory (16-byte aligned, >= gdm_knn_jobs_workspace_bytes) in which every distinct support
+ * set of the K > 1 jobs is re-laid out once: small unorganised supports as hashed float4 tiles that the search blocks stream with
+ * coalesced loads, unorganised supports of >= 1024 points as (x, y) cell lists (a counting sort per crop; a query then visits cells
+ * ring by ring instead of every point), organised supports (grid_w) as per-column / per-row ratio ranges.  workspace NULL with
+ * workspace_bytes 0: each block gathers its tiles from the [S,3] array.  Results are identical in every form, for any data.      */
 size_t gdm_knn_jobs_workspace_bytes(const gdm_knn_job* jobs, int njobs, int B);
 int gdm_knn_jobs_ws_hip(const gdm_knn_job* jobs, int njobs, int B, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -105,14 +104,14 @@ int gdm_labelstat_idx_hip(int B, int n, int m, int nsample, int nclass, const in
 
 /* out[b,c,j,k] = feat[b,c,idx[b,j,k]]   feat f32[B,C,n], idx i32[B,m,K] -> f32[B,C,m,K]
  * replaces Building_block.gather_neighbour + permute (models/RandLA/RandLANet.py:729-738,
- * 704-716) and pointops grouping_forward_cuda (pointops.py:151-176).                     */
+ * 704-716) and pointops grouping_forward_cuda (pointops.py:151-176); with K == 1 also
+ * FFB6DEmb.nearest_interpolation (models/ffb6d.py:148-163), the `choose` gather
+ * (ffb6d.py:278-281) and pointops gathering_forward_cuda (pointops.py:61-82).              */
 int gdm_group_gather_hip(const float* feat, const int32_t* idx, int B, int C, int n, int m, int K,
                          float* out, void* stream);
-/* grad_feat[b,c,idx[b,j,k]] += grad_out[b,c,j,k]; grad_feat must be zeroed by the caller. */
-int gdm_group_gather_bwd_hip(const float* grad_out, const int32_t* idx, int B, int C, int n, int m, int K,
-                             float* grad_feat, void* stream);
-/* the same with grad_out read in place from a wider tensor: go_bstride = floats between two batch items (rows of m*K floats, channel
- * stride m*K; >= C*m*K) -- the gradient slice a torch.cat backward hands to nearest_interpolation (models/ffb6d.py:148-163) */
+/* grad_feat[b,c,idx[b,j,k]] += grad_out[b,c,j,k]; grad_feat must be zeroed by the caller.  grad_out may be read in place from a
+ * wider tensor: go_bstride = floats between two batch items (rows of m*K floats, channel stride m*K; >= C*m*K, C*m*K when dense)
+ * -- the gradient slice a torch.cat backward hands to nearest_interpolation (models/ffb6d.py:148-163) */
 int gdm_group_gather_bwd2_hip(const float* grad_out, long go_bstride, const int32_t* idx, int B, int C, int n, int m, int K,
                               float* grad_feat, void* stream);
 
@@ -123,15 +122,6 @@ int gdm_gather_max_hip(const float* feat, const int32_t* idx, int B, int C, int 
 /* grad_feat[b,c,arg[b,c,j]] += grad_out[b,c,j]; grad_feat zeroed by the caller.          */
 int gdm_gather_max_bwd_hip(const float* grad_out, const int32_t* arg, int B, int C, int n, int m,
                            float* grad_feat, void* stream);
-
-/* out[b,c,j] = feat[b,c,idx[b,j]]      (K == 1)
- * replaces FFB6DEmb.nearest_interpolation (models/ffb6d.py:148-163), the `choose` gather
- * (ffb6d.py:278-281) and pointops gathering_forward_cuda (pointops.py:61-82).
- * idx_bstride = elements between batch items of idx (0 broadcasts one index row).        */
-int gdm_gather_nn_hip(const float* feat, const int32_t* idx, int B, int C, int n, int m,
-                      float* out, void* stream);
-int gdm_gather_nn_bwd_hip(const float* grad_out, const int32_t* idx, int B, int C, int n, int m,
-                          float* grad_feat, void* stream);
 
 /* Relative position encoding (RandLANet.py:720-727 + the permute of :701-702):
  * xyz f32[B,n,3], idx i32[B,n,K] -> out f32[B,10,n,K] with channels
@@ -199,33 +189,24 @@ int gdm_spline_aggregate_bwd_hip(const float* grad_out, const int32_t* rowptr, c
                                  int M, int C, int kernel_size, float* grad_xw, void* stream);
 /* The same layer for few input channels (Cin <= 16; the first mesh layer, 9 -> 128) without the [M, 125*C] table:
  * out_i = mean_e sum_s b_s (x_j . W[wi_s]) + x_i . W_root + bias; x f32[M,Cin], weight f32[ks^3,Cin,C] (SplineConv.weight as stored),
- * root_t f32[Cin,C] (lin.weight transposed, may be NULL), bias f32[C] (may be NULL). */
-int gdm_spline_direct_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
-                          const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
-                          float* out, void* stream);
+ * root_t f32[Cin,C] (lin.weight transposed, may be NULL), bias f32[C] (may be NULL).
+ * This kernel and gdm_spline_pairs_aggregate3_hip write up to three forms of the result: out f32[M,C]; out_t f32[C,M] (channel-major:
+ * what the next layer's grouped GEMM, its root product and the final linear read as gdm_pointwise2_hip segments); out_packed, the
+ * split-bf16 operand planes of the next layer's grouped GEMM (gdm_conv3x3_act_bytes(1, C, 1, M) bytes, the layout
+ * gdm_conv3x3_pack_act_hip(x_cm, 1, C, 1, M) writes; zero border in place, C = 128, 256 or 512), so that the pack launch between two
+ * SplineConv layers (SplineCNN.py:238-239) is not needed.  Each may be NULL, but not both out and out_t; out_t and out_packed need
+ * C % 4 == 0, 512 % C == 0 and 16-byte aligned buffers. */
+int gdm_spline_direct3_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
+                           const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
+                           float* out, float* out_t, void* out_packed, void* stream);
 /* Edge-grouped form of the 128-channel layers: only the (source vertex, kernel index) pairs that some edge needs are multiplied,
  * 4x fewer FLOPs than the dense form and no [M, 125*C] table.  gdm_gemm_grouped_hip: Y[r, 0:128] = Wpk[tile_co0[r/256] + 0:128, :] .
  * X[rowidx[r], :] for R % 256 == 0 rows (pairs sorted by kernel index, groups padded to 256 rows with rowidx = 0), X packed by
  * gdm_conv3x3_pack_act_hip(x^T, 1, Cin, 1, M), weights by gdm_conv1x1_pack_weight_hip (125*C rows, row = wi*C + co).
- * gdm_spline_pairs_aggregate_hip: out_i = mean_e sum_s basis[e,s] * Y[pos[e,s]] + root_i + bias. */
+ * gdm_spline_pairs_aggregate3_hip: out_i = mean_e sum_s basis[e,s] * Y[pos[e,s]] + root_i + bias; root f32[M,C] and bias f32[C] may
+ * be NULL. */
 int gdm_gemm_grouped_hip(const void* xpk, const void* wpk, const int32_t* rowidx, const int32_t* tile_co0, int R, int M,
                          int Cin, int Cout_total, float* out, void* stream);
-int gdm_spline_pairs_aggregate_hip(const float* Y, const int32_t* rowptr, const int32_t* pos, const float* basis,
-                                   const float* root, const float* bias, int M, int C, int relu, float* out, void* stream);
-/* The two kernels above with an optional second output out_t f32[C, M] (channel-major: what the next layer's grouped GEMM, its root
- * product and the final linear read as gdm_pointwise_hip segments), out and out_t may each be NULL but not both; out_t needs
- * C % 4 == 0 and 512 % C == 0. */
-int gdm_spline_direct2_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
-                           const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
-                           float* out, float* out_t, void* stream);
-int gdm_spline_pairs_aggregate2_hip(const float* Y, const int32_t* rowptr, const int32_t* pos, const float* basis,
-                                    const float* root, const float* bias, int M, int C, int relu, float* out, float* out_t, void* stream);
-/* ... and with an optional THIRD output out_packed: the result as the split-bf16 operand planes of the next layer's grouped GEMM
- * (gdm_conv3x3_act_bytes(1, C, 1, M) bytes, the layout gdm_conv3x3_pack_act_hip(x_cm, 1, C, 1, M) writes; zero border in place, C = 128,
- * 256 or 512): the pack launch between two SplineConv layers (SplineCNN.py:238-239) is then not needed. */
-int gdm_spline_direct3_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
-                           const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
-                           float* out, float* out_t, void* out_packed, void* stream);
 int gdm_spline_pairs_aggregate3_hip(const float* Y, const int32_t* rowptr, const int32_t* pos, const float* basis,
                                     const float* root, const float* bias, int M, int C, int relu, float* out, float* out_t,
                                     void* out_packed, void* stream);
@@ -270,23 +251,20 @@ int gdm_circle_rows_bwd_hip(const float* sim, int R, int Mp, const int32_t* matc
  *   pack      x -> split-bf16 rows + d-major tiles + row sums (sizes from the two *_bytes functions, rows padded to 128)
  *   nbr       bit table [M][ceil(M/32)] of vertices within `radius` of each vertex (basic_utils.py:86-89 arithmetic); once per model
  *   visbits   visible_flag u8[B,M] -> bits [B][ceil(M/32)]
- *   fwd       per-row lse_p, lse_n, loss f32[Rp]; g i32[Rp] = ground-truth vertex (M = none), item i32[Rp]; symmetric objects:
+ *   fwd2      per-row lse_p, lse_n, loss f32[Rp]; g i32[Rp] = ground-truth vertex (M = none), item i32[Rp]; symmetric objects:
  *             g / c2 = the two positive columns of the row (geoMatch.py:91-95), nbr / visb unused
- *   bwd       coef f32[Rp] = upstream gradient x sigmoid(lse_p + lse_n) (0 for padding rows and empty positive sets) ->
- *             gx f32[Rp,128], gy_part f32[P][Mp,128] with P = gdm_circle_match_bwd_parts (sum over P = gradient w.r.t. y)    */
+ *   bwd2      coef f32[Rp] = upstream gradient x sigmoid(lse_p + lse_n) (0 for padding rows and empty positive sets) ->
+ *             gx f32[Rp,128], gy_part f32[P][Mp,128] with P = gdm_circle_match_bwd_parts (sum over P = gradient w.r.t. y)
+ * fwd2 / bwd2 options: nbr_per_item = 0 -- `nbr` is the one table of gdm_circle_match_nbr_hip; != 0 -- `nbr` holds one neighbour
+ * table PER BATCH ITEM, u32[B][M][ceil(M/32)], made by gdm_circle_match_nbr_items_hip from a per-item, per-vertex radius (the
+ * geoMatch_DGCNN variant, /root/reference/models/geoMatch_DGCNN.py:52-135; positive_r / 1000 * z of the posed vertex, :66-67).
+ * pad_e0 = 0 -- `xpad` holds the row sums that pack wrote; != 0 -- the padding column is the unit vector e0 (geoMatch_DGCNN.py:96-99)
+ * and `xpad` holds x[r][0].                                                                                                       */
 size_t gdm_circle_match_rows_bytes(int n);
 size_t gdm_circle_match_tp_bytes(int n);
 int gdm_circle_match_pack_hip(const float* x, int n, void* rows, void* tp, float* rowsum, void* stream);
 int gdm_circle_match_nbr_hip(const float* xyz, int M, float radius, uint32_t* nbr, void* stream);
 int gdm_circle_match_visbits_hip(const uint8_t* vis, int B, int M, uint32_t* bits, void* stream);
-int gdm_circle_match_fwd_hip(const void* xrows, const void* xtp, const float* xsum, const void* yrows, const void* ytp,
-                             int R, int M, const int32_t* g, const int32_t* c2, const int32_t* item,
-                             const uint32_t* nbr, const uint32_t* visb, float gamma, float m,
-                             float* lse_p, float* lse_n, float* loss, void* stream);
-/* The same two kernels for the geoMatch_DGCNN variant (/root/reference/models/geoMatch_DGCNN.py:52-135): nbr_per_item != 0 -- `nbr` holds one
- * neighbour table PER BATCH ITEM, u32[B][M][ceil(M/32)] made by gdm_circle_match_nbr_items_hip from a per-item, per-vertex radius
- * (positive_r / 1000 * z of the posed vertex, :66-67); pad_e0 != 0 -- the padding column is the unit vector e0 (:96-99) and `xpad`
- * holds x[r][0] instead of the row sums.  (0, 0) = gdm_circle_match_fwd_hip / _bwd_hip.                                            */
 int gdm_circle_match_nbr_items_hip(const float* xyz, int M, const float* rad /* f32[B,M] */, int B, uint32_t* nbr, void* stream);
 int gdm_circle_match_fwd2_hip(const void* xrows, const void* xtp, const float* xpad, const void* yrows, const void* ytp,
                               int R, int M, const int32_t* g, const int32_t* c2, const int32_t* item,
@@ -297,10 +275,6 @@ int gdm_circle_match_bwd2_hip(const void* xrows, const void* xtp, const float* x
                               const uint32_t* nbr, int nbr_per_item, const uint32_t* visb, int pad_e0, float gamma, float m,
                               const float* lse_p, const float* lse_n, const float* coef, float* gx, float* gy_part, void* stream);
 int gdm_circle_match_bwd_parts(int R, int M);
-int gdm_circle_match_bwd_hip(const void* xrows, const void* xtp, const float* xsum, const void* yrows, const void* ytp,
-                             int R, int M, const int32_t* g, const int32_t* c2, const int32_t* item,
-                             const uint32_t* nbr, const uint32_t* visb, float gamma, float m,
-                             const float* lse_p, const float* lse_n, const float* coef, float* gx, float* gy_part, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * One attentive-pooling stage of RandLA-Net's local feature aggregation in a single launch (inference):
@@ -372,40 +346,32 @@ int gdm_upconv_fused64_hip(const float* x, const void* wpk, const float* scale, 
                            int OH, int OW, int act, float slope, float* out, void* stream);
 
 /* Pyramid-pooling bottleneck tail (pspnet.py:24-31) after splitting the 1x1 convolution over the concat:
- * out = relu(g + bias[c] + sum_k bilinear_align_corners(y_k)), g f32[B,C,H,W] = W_f . feats, y_k f32[B,C,s_k,s_k] = W_k . prior_k. */
-int gdm_psp_combine_hip(const float* g, const float* y1, int s1, const float* y2, int s2, const float* y3, int s3,
-                        const float* y4, int s4, const float* bias, int B, int C, int H, int W, float* out, void* stream);
-/* The same, also writing the result as the packed split-bf16 operand (gdm_conv3x3_pack_act_hip's layout, gdm_conv3x3_act_bytes bytes, zero
- * border kept by the caller) of the next GEMM over the map: C = 64 or a multiple of 128, W % 4 == 0.  outpk NULL = gdm_psp_combine_hip. */
+ * out = relu(g + bias[c] + sum_k bilinear_align_corners(y_k)), g f32[B,C,H,W] = W_f . feats, y_k f32[B,C,s_k,s_k] = W_k . prior_k.
+ * outpk (may be NULL): the result also as the packed split-bf16 operand (gdm_conv3x3_pack_act_hip's layout, gdm_conv3x3_act_bytes
+ * bytes, zero border kept by the caller) of the next GEMM over the map: C = 64 or a multiple of 128, W % 4 == 0. */
 int gdm_psp_combine2_hip(const float* g, const float* y1, int s1, const float* y2, int s2, const float* y3, int s3,
                          const float* y4, int s4, const float* bias, int B, int C, int H, int W, float* out, void* outpk, void* stream);
 /* Point->pixel fusion tail (ffb6d.py:216-222,252-258): y[b,c,j] = act(scale[c]*(x[b,c,j] + t[b,c,idx[b,j]]) + shift[c]),
- * x f32[B,C,m] (pixel half of the 1x1 conv), t f32[B,C,n] (point half, computed at the points), idx i32[B,m]. May run in place. */
-int gdm_gather_add_affine_act_hip(const float* x, const float* t, const int32_t* idx, const float* scale, const float* shift,
-                                  int B, int C, int n, int m, int act, float slope, float* y, void* stream);
-/* ... and, with y_packed != NULL, the result ALSO as the packed split-bf16 operand of the next convolution / GEMM over the
- * [B, C, m/W, W] map (gdm_conv3x3_act_bytes(B, C, m/W, W) bytes, zero border in place): no pack launch in front of that layer. */
+ * x f32[B,C,m] (pixel half of the 1x1 conv), t f32[B,C,n] (point half, computed at the points), idx i32[B,m]. May run in place.
+ * With y_packed != NULL the result is ALSO written as the packed split-bf16 operand of the next convolution / GEMM over the
+ * [B, C, m/W, W] map (gdm_conv3x3_act_bytes(B, C, m/W, W) bytes, zero border in place; C = 64 or a multiple of 128): no pack launch
+ * in front of that layer.  W is read only with y_packed. */
 int gdm_gather_add_affine_act2_hip(const float* x, const float* t, const int32_t* idx, const float* scale, const float* shift,
                                    int B, int C, int n, int m, int act, float slope, float* y, void* y_packed, int W, void* stream);
 /* The same tail with the pixel half of the 1x1 convolution inside, for the 64-channel levels (C == 64):
- * y[b,co,j] = act(scale[co]*(sum_ci W[co,ci] x[b,ci,j] + t[b,co,idx[b,j]]) + shift[co]); wt f32[C,C] = W transposed ([ci][co]). */
-int gdm_conv1x1_gather_add_act_hip(const float* x, const float* wt, const float* t, const int32_t* idx, const float* scale,
-                                   const float* shift, int B, int C, int n, long m, int act, float slope, float* y, void* stream);
-/* The same fusion with the K = 64 channel mix on the matrix cores (split-bf16 x3, fp32 accumulate): wpk = the 64 x 64 weight (row =
- * output channel) packed by gdm_pack_rows64_hip; t_point_major != 0: t is f32[B, n, 64] (the gathered term is then one contiguous
- * 256-byte row per pixel instead of 64 scattered floats); other arguments as above. */
-int gdm_conv64_gather_add_act_mfma_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
-                                       const float* shift, int B, int n, long m, int act, float slope, int pixel_major, int t_point_major,
-                                       float* y, void* stream);
-/* The same (NCHW form) also writing the result as the packed split-bf16 operand of the next convolution over the [B, 64, m / W, W] map
- * (gdm_conv3x3_act_bytes(B, 64, m / W, W) bytes, zero border kept by the caller).  ypk NULL = gdm_conv64_gather_add_act_mfma_hip. */
-int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
-                                        const float* shift, int B, int n, long m, int act, float slope, int pixel_major,
-                                        int t_point_major, float* y, void* ypk, int W, void* stream);
-/* The same with the output layout selectable: pixel_major != 0 writes y f32[B, m, C] (one 256-byte row per pixel). */
+ * y[b,co,j] = act(scale[co]*(sum_ci W[co,ci] x[b,ci,j] + t[b,co,idx[b,j]]) + shift[co]); wt f32[C,C] = W transposed ([ci][co]).
+ * pixel_major = 0 writes y f32[B, C, m]; != 0 writes y f32[B, m, C] (one 256-byte row per pixel). */
 int gdm_conv1x1_gather_add_act2_hip(const float* x, const float* wt, const float* t, const int32_t* idx, const float* scale,
                                     const float* shift, int B, int C, int n, long m, int act, float slope, int pixel_major,
                                     float* y, void* stream);
+/* The same fusion with the K = 64 channel mix on the matrix cores (split-bf16 x3, fp32 accumulate): wpk = the 64 x 64 weight (row =
+ * output channel) packed by gdm_pack_rows64_hip; t_point_major != 0: t is f32[B, n, 64] (the gathered term is then one contiguous
+ * 256-byte row per pixel instead of 64 scattered floats); pixel_major and the other arguments as above.  With ypk != NULL (NCHW form
+ * only) the result is ALSO written as the packed split-bf16 operand of the next convolution over the [B, 64, m / W, W] map
+ * (gdm_conv3x3_act_bytes(B, 64, m / W, W) bytes, zero border kept by the caller).  W is read only with ypk. */
+int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
+                                        const float* shift, int B, int n, long m, int act, float slope, int pixel_major,
+                                        int t_point_major, float* y, void* ypk, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * 3x3 / stride 1 / pad 1 convolution as an implicit GEMM on split-bf16 MFMA (hi*hi + hi*lo + lo*hi, fp32 accumulate),
@@ -421,13 +387,11 @@ int gdm_conv3x3_pack_weight_hip(const float* w, int Cout, int Cin, void* wpk, vo
 int gdm_conv3x3_pack_act_hip(const float* x, int B, int Cin, int H, int W, void* xpk, void* stream);
 int gdm_conv3x3_packed_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
                            int B, int Cin, int Cout, int H, int W, int act, float* out, void* stream);
-/* The same convolution with the result ALSO (or only: out == NULL) written as the packed operand of the next convolution
- * (outpk: gdm_conv3x3_act_bytes(B, Cout, H, W) bytes, zero-filled once by the caller), which then needs no pack launch.  */
-int gdm_conv3x3_packed2_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
-                            int B, int Cin, int Cout, int H, int W, int act, float* out, void* outpk, void* stream);
 /* Strided forms (stride 1 or 2; the first block of ResNet-18 layer2, extractors.py:151-177): H, W are the OUTPUT size, xpk is the
  * (H*stride) x (W*stride) input packed by gdm_conv3x3_pack_act_hip; gdm_conv1x1_strided_hip is the block's 1x1 downsample branch
- * on the same packed input (NCHW output). */
+ * on the same packed input (NCHW output).  gdm_conv3x3_strided_hip writes its result to out, to outpk as the packed operand of the
+ * next convolution (gdm_conv3x3_act_bytes(B, Cout, H, W) bytes, zero-filled once by the caller; Cout % 8 == 0, B*H*W % 256 == 0),
+ * which then needs no pack launch, or to both; either may be NULL, not both. */
 int gdm_conv3x3_strided_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
                             int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream);
 int gdm_conv1x1_strided_hip(const void* xpk, const void* wpk, const float* scale, const float* shift,
@@ -497,18 +461,15 @@ int gdm_bn_bwd_apply_hip(const float* x, const float* grad_out, const double* su
  * The per-point heads of GeoMatch.forward in one kernel (inference; /root/reference/models/geoMatch.py:159-200: feature_encoding_layer,
  * normalize_feature_layer, the residual add and seg_layer -- nine 1x1 convolutions per scene point).  Input x0 = channels of a
  * f32[B,Ca,N] followed by b f32[B,128-Ca,N] (b may be NULL when Ca == 128).  `nlayer` hidden layers 128 -> 128:
- *   x_{l+1} = act_l(scale_l * (W_l x_l) + shift_l)  [+ x0 after layer res_layer];  out_feat f32[B,128,N] = the affine output of layer
+ *   x_{l+1} = act_l(scale_l * (W_l x_l) + shift_l)  [+ r after layer res_layer];  out_feat f32[B,128,N] = the affine output of layer
  *   feat_layer (before the residual);  then out_last f32[B,c_last,N] = W_last x_nlayer + shift_last (c_last <= 16).
+ * The residual r is given as the input is, by (ra, rb, rCa); NULL ra = the input x0.
  * w[l], w_last: weights packed by gdm_conv1x1_pack_weight_hip(Cout, 128) (rows padded to 128); scale[l] / shift[l] may be NULL (1 / 0);
  * act[l]: 0 none, 1 ReLU; feat_layer / res_layer: -1 = none.  w, scale, shift, act are HOST arrays of nlayer entries.
+ * c_last = 0 ends the chain with its hidden layers (w_last / out_last unused); out_feat may be NULL with feat_layer < 0.
+ * GeoMatch.forward runs the chain in two pieces, the four feature layers first and the normalise / segmentation layers second, so that
+ * the matching kernel -- which reads the features only -- runs beside the second piece.
  * Split-bf16 products (hi*hi + hi*lo + lo*hi), fp32 accumulate, as the convolution kernels. */
-int gdm_point_heads_hip(const float* a, const float* b, int Ca, int B, int N, int nlayer, const void* const* w,
-                        const float* const* scale, const float* const* shift, const int* act, int feat_layer, int res_layer,
-                        const void* w_last, const float* shift_last, int c_last, float* out_feat, float* out_last, void* stream);
-/* The same chain in pieces: the tensor added at res_layer comes from (ra, rb, rCa) instead of the input (NULL ra = the input), c_last = 0
- * ends the chain with its hidden layers (w_last / out_last unused), out_feat may be NULL with feat_layer < 0.  GeoMatch.forward launches
- * the four feature layers first and the normalise / segmentation layers second, so that the matching kernel -- which reads the features
- * only -- runs beside the second piece. */
 int gdm_point_heads2_hip(const float* a, const float* b, int Ca, const float* ra, const float* rb, int rCa, int B, int N, int nlayer,
                          const void* const* w, const float* const* scale, const float* const* shift, const int* act, int feat_layer,
                          int res_layer, const void* w_last, const float* shift_last, int c_last, float* out_feat, float* out_last,
@@ -524,7 +485,10 @@ int gdm_point_heads2_hip(const float* a, const float* b, int Ca, const float* ra
  * X = the channels of segs[0], segs[1], ... in order (the concat, never formed; nseg in [1,4], four only when K >= 32).  A segment is f32[B,C,n_src]
  * channel-major, read at column i (n_src == n) or at idx[b*n + i] (i32, any n_src).  A residual branch
  * s1*(W1 . x1) + b1 + s2*(W2 . x2) + b2 is the two-segment layer with wt = [s1*W1^T ; s2*W2^T], shift = b1 + b2 (the caller folds).
- * wt f32[K,Cout] TRANSPOSED weight, K = sum of the segments' C; scale / shift f32[Cout] or NULL (1 / 0).
+ * wt f32[K,Cout] TRANSPOSED weight (w_rowmajor = 0), K = sum of the segments' C; or, with w_rowmajor != 0, wt f32[Cout,K] as the
+ * module holds it (nn.Conv1d / nn.Conv2d 1x1 weight), so that the TRAINING forward W . x and input gradient W^T . go (wt = the same
+ * tensor read as [K' = Cout][Cout' = K], w_rowmajor = 0) of /root/reference/models/pytorch_utils.py:70-124 need no transposed copy of
+ * a weight that changes every step.  scale / shift f32[Cout] or NULL (1 / 0).
  * act: 0 none, 1 ReLU, 2 leaky ReLU (slope).  out f32[B,out_C,n] (point_major 0) or f32[B*n,out_C] (1), 16-byte aligned;
  * channels [out_c0, out_c0 + Cout) of it are written.  fp32 FMAs; the K axis may be summed as up to four partial sums added in
  * fixed order (deterministic; no atomics). */
@@ -533,18 +497,13 @@ typedef struct {
     const int32_t* idx;
     int32_t C, n_src;
 } gdm_pw_seg;
-int gdm_pointwise_hip(const gdm_pw_seg* segs, int nseg, const float* wt, const float* scale, const float* shift,
-                      int B, int n, int Cout, int act, float slope, float* out, int out_C, int out_c0, int point_major, void* stream);
-/* The same layer with the weight as the module holds it when w_rowmajor != 0: wt f32[Cout,K] (nn.Conv1d / nn.Conv2d 1x1 weight), so
- * the TRAINING forward W . x and input gradient W^T . go (wt = the same tensor read as [K' = Cout][Cout' = K], w_rowmajor = 0) of
- * /root/reference/models/pytorch_utils.py:70-124 need no transposed copy of a weight that changes every step. */
 int gdm_pointwise2_hip(const gdm_pw_seg* segs, int nseg, const float* wt, int w_rowmajor, const float* scale, const float* shift,
                        int B, int n, int Cout, int act, float slope, float* out, int out_C, int out_c0, int point_major, void* stream);
 /* Up to four independent plain layers out_j f32[B,Cout,n_j] = W_j^T . x_j (x_j f32[B,K,n_j], wt_j f32[K,Cout]; no scale / shift /
  * activation) of equal K >= 32 and Cout in ONE launch: the four prior products of the pyramid-pooling module
  * (/root/reference/models/cnn/pspnet.py:17-31, `stage(feats)` of the 1 / 2 / 3 / 6-bin pools folded with the bottleneck's slices).
- * Bit-identical to njobs calls of gdm_pointwise_hip: jobs that would take different K splits alone (gdm_pointwise_hip picks the split
- * from a job's own grid size) are launched apart, one launch per distinct split. */
+ * Bit-identical to njobs calls of gdm_pointwise2_hip (w_rowmajor = 0): jobs that would take different K splits alone (gdm_pointwise2_hip
+ * picks the split from a job's own grid size) are launched apart, one launch per distinct split. */
 typedef struct {
     const float* x;
     const float* wt;
@@ -555,7 +514,7 @@ int gdm_pointwise_jobs_hip(const gdm_pw_job* jobs, int njobs, int B, int K, int 
 /* Two chained narrow per-point layers in one launch, both results written: y0 = act0(s0 (W0 x) + b0) f32[B,C1,n],
  * y1 = act1(s1 (W1 y0) + b1) f32[B,C2,n]; x f32[B,C0,n], w0t f32[C0,C1], w1t f32[C1,C2] (weights transposed), s / b folded
  * BatchNorm or NULL, act 0 none / 1 ReLU / 2 LeakyReLU(slope); C0, C1 <= 16, C2 <= 32.  The RandLA stem fc0 and the first block's
- * mlp1 (/root/reference/models/RandLA/RandLANet.py:19,683-684).  Bit-identical to two gdm_pointwise_hip launches. */
+ * mlp1 (/root/reference/models/RandLA/RandLANet.py:19,683-684).  Bit-identical to two gdm_pointwise2_hip launches. */
 int gdm_pointwise_chain2_hip(const float* x, const float* w0t, const float* s0, const float* b0, int act0, float slope0,
                              const float* w1t, const float* s1, const float* b1, int act1, float slope1,
                              int B, int n, int C0, int C1, int C2, float* y0, float* y1, void* stream);

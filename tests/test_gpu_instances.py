@@ -211,8 +211,8 @@ def test_spline_layers_without_relu(ops):
     pos = torch.randint(0, R, (E, 8), generator=g).int().cuda()
     basis = torch.rand(E, 8, generator=g).cuda()
     out = torch.empty(M, C, device="cuda")
-    assert _lib.lib().gdm_spline_pairs_aggregate_hip(Y.data_ptr(), rowptr.data_ptr(), pos.data_ptr(), basis.data_ptr(), None, None, M, C, 0,
-                                                     out.data_ptr(), None) == 0
+    assert _lib.lib().gdm_spline_pairs_aggregate3_hip(Y.data_ptr(), rowptr.data_ptr(), pos.data_ptr(), basis.data_ptr(), None, None, M, C, 0,
+                                                      out.data_ptr(), None, None, None) == 0
     msg = (basis.double().unsqueeze(2) * Y.double()[pos.long()]).sum(1)
     tgt = torch.repeat_interleave(torch.arange(M, device="cuda"), (rowptr[1:] - rowptr[:-1]).long())
     want = torch.zeros(M, C, dtype=torch.float64, device="cuda").index_add_(0, tgt, msg) / (rowptr[1:] - rowptr[:-1]).double().clamp(min=1).unsqueeze(1)

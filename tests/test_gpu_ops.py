@@ -625,7 +625,7 @@ def test_upconv3x3_gather_train_forward_backward_any_scale(ops, B, C, H, W, OH, 
 
 def test_spline_scalar_kernels_for_odd_channel_counts(ops):
     """SplineConv with a channel count that is not a multiple of 4 takes the one-channel-per-thread kernels (the 16-byte forms need
-    C % 4 == 0 and 512 % C == 0): the direct first layer against the dense form, and gdm_spline_pairs_aggregate_hip against its
+    C % 4 == 0 and 512 % C == 0): the direct first layer against the dense form, and gdm_spline_pairs_aggregate3_hip against its
     definition out_i = mean_e sum_s basis[e,s] Y[pos[e,s]] + root_i + bias."""
     from geometric_aware_dense_matching_amd import _lib, splinecnn
     torch.manual_seed(4)
@@ -653,8 +653,8 @@ def test_spline_scalar_kernels_for_odd_channel_counts(ops):
     basis = torch.rand(E, 8, generator=g).cuda()
     root = torch.randn(M, C, generator=g).cuda()
     out = torch.empty(M, C, device="cuda")
-    rc = _lib.lib().gdm_spline_pairs_aggregate_hip(Y.data_ptr(), rowptr.data_ptr(), pos.data_ptr(), basis.data_ptr(), root.data_ptr(),
-                                                   conv.bias.data_ptr(), M, C, 1, out.data_ptr(), None)
+    rc = _lib.lib().gdm_spline_pairs_aggregate3_hip(Y.data_ptr(), rowptr.data_ptr(), pos.data_ptr(), basis.data_ptr(), root.data_ptr(),
+                                                    conv.bias.data_ptr(), M, C, 1, out.data_ptr(), None, None, None)
     assert rc == 0
     msg = (basis.double().unsqueeze(2) * Y.double()[pos.long()]).sum(1)                   # [E, C]
     tgt = torch.repeat_interleave(torch.arange(M, device="cuda"), (rowptr[1:] - rowptr[:-1]).long())
@@ -962,7 +962,7 @@ def test_affine_relu_maxpool_equals_modules(ops, B, C, H, W):
     (2, 65536, (16, 16), 80, 4096, False),            # ... an indexed segment, 80 = 64 + 16 channels
 ])
 def test_pointwise_layer_vs_torch(ops, B, n, cs, cout, n_src, pm):
-    """ops.pointwise (gdm_pointwise_hip) == cat -> 1x1 conv -> affine (folded BN) -> activation in fp64 torch, to fp32 rounding
+    """ops.pointwise (gdm_pointwise2_hip) == cat -> 1x1 conv -> affine (folded BN) -> activation in fp64 torch, to fp32 rounding
     of a K-term dot product (1e-5 relative to the output scale); an indexed segment = nearest interpolation of its source."""
     g = torch.Generator(device="cpu").manual_seed(B * 1000 + n)
     xs, segs = [], []
@@ -1048,7 +1048,7 @@ def test_pointwise_rejects_bad_arguments(ops):
 @pytest.mark.parametrize("B,K,Cout,ns", [(16, 512, 1024, (1, 4, 9, 36)), (32, 512, 1024, (1, 4, 9, 36)), (2, 512, 1024, (1, 4, 9, 36)), (3, 64, 40, (5, 64)), (1, 128, 16, (7,))])
 def test_pointwise_jobs_equal_separate_launches_bit_for_bit(ops, B, K, Cout, ns):
     """gdm_pointwise_jobs_hip (the four prior products of the pyramid-pooling module, pspnet.py:17-31, in one launch) == one
-    gdm_pointwise_hip launch per job, bit for bit (same tile function, same K split), and == the fp64 product at fp32 accuracy."""
+    gdm_pointwise2_hip launch per job, bit for bit (same tile function, same K split), and == the fp64 product at fp32 accuracy."""
     g = torch.Generator(device="cpu").manual_seed(K + Cout + len(ns))
     xs = [torch.randn(B, K, n, generator=g).cuda() for n in ns]
     wts = [(torch.randn(K, Cout, generator=g) / K ** 0.5).cuda() for _ in ns]
@@ -1073,7 +1073,7 @@ def test_match_pack2_equals_two_pack_launches(ops, prec, R1, n1, n2):
 
 @pytest.mark.parametrize("B,n,C0,C1,C2,acts", [(16, 2048, 9, 8, 16, (2, 2)), (3, 77, 16, 16, 32, (1, 0)), (1, 5, 1, 3, 2, (0, 2))])
 def test_pointwise_chain2_equals_two_launches_bit_for_bit(ops, B, n, C0, C1, C2, acts):
-    """gdm_pointwise_chain2_hip (RandLA stem fc0 + the first block's mlp1, RandLANet.py:19,683) == two gdm_pointwise_hip launches."""
+    """gdm_pointwise_chain2_hip (RandLA stem fc0 + the first block's mlp1, RandLANet.py:19,683) == two gdm_pointwise2_hip launches."""
     g = torch.Generator(device="cpu").manual_seed(B + n + C2)
     x = torch.randn(B, C0, n, generator=g).cuda()
     mk = lambda k, c: ((torch.randn(k, c, generator=g) / k ** 0.5).cuda(), (torch.rand(c, generator=g) + 0.5).cuda(), torch.randn(c, generator=g).cuda())

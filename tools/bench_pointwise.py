@@ -1,4 +1,4 @@
-"""Per-shape timing of the per-point 1x1 layer kernel (gdm_pointwise_hip) at the shapes of the eval step (batch 16, N = 2048):
+"""Per-shape timing of the per-point 1x1 layer kernel (gdm_pointwise2_hip) at the shapes of the eval step (batch 16, N = 2048):
     python tools/bench_pointwise.py"""
 import os
 import sys
