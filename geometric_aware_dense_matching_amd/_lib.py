@@ -16,6 +16,8 @@ _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
 
+GDM_RANSAC_MAX_H = 4096                # include/gdm.h
+
 
 class KnnJob(ctypes.Structure):
     """struct gdm_knn_job (include/gdm.h)."""
@@ -94,6 +96,12 @@ SIGNATURES = {
     "gdm_lfa_stage_hip": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _f, _vp, _vp]),
     "gdm_kabsch_stats_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "gdm_kabsch_solve_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "gdm_ransac_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gdm_ransac_pose_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, ctypes.c_double, ctypes.c_uint32, _i,
+                                 _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_icp_transform_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "gdm_icp_update_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, ctypes.c_double, _i, _vp, _vp, _vp, _vp,
+                                _vp]),
     "gdm_affine_act_maxk_hip": (_i, [_vp, _vp, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _i, _f, _vp, _vp]),
     "gdm_prelu1_hip": (_i, [_vp, _vp, ctypes.c_long, _vp, _vp]),
     "gdm_prelu1_bwd_hip": (_i, [_vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp]),

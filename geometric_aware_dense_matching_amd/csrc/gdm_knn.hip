@@ -1191,7 +1191,8 @@ static int check_jobs(const gdm_knn_job* jobs, int njobs, int B, const char* who
         GDM_CHECK_ARG(j.support && j.query && j.idx, "%s: job %d has a NULL pointer", who, i);
         GDM_CHECK_ARG(j.S >= 1 && j.Q >= 1, "%s: job %d S=%d Q=%d", who, i, j.S, j.Q);
         GDM_CHECK_ARG(j.K >= 1 && j.K <= 32, "%s: job %d K=%d not in [1,32]", who, i, j.K);
-        GDM_CHECK_ARG(j.support_bstride >= (int64_t)j.S * 3 || B == 1, "%s: job %d support_bstride too small", who, i);
+        GDM_CHECK_ARG(j.support_bstride >= (int64_t)j.S * 3 || j.support_bstride == 0 || B == 1, "%s: job %d support_bstride too small",
+                      who, i);
         GDM_CHECK_ARG(j.query_bstride >= (int64_t)j.Q * 3 || B == 1, "%s: job %d query_bstride too small", who, i);
     }
     return 0;

@@ -1,0 +1,396 @@
+// Robust pose fitting on the device, gfx950: batched RANSAC over the dense correspondences and point-to-point ICP refinement.
+//
+// RANSAC restates the reference's sequential loop (utils/pvn3d_eval_utils_kpls.py:79-124 best_fit_transform_with_RANSAC) for a
+// whole batch with every hypothesis at once:
+//   ransac_compact_kernel  one workgroup per crop: the selected correspondences (mask != 0) in point order, as six fp32 planes
+//                          (A = matched model vertex, B = scene point) -- the reference's A = mdl[idx], B = cld[cls_msk]
+//   ransac_hyp_kernel      one lane per (crop, hypothesis): h = 0 is the Kabsch fit of all selected pairs (the statistics of
+//                          gdm_kabsch_stats_hip), h >= 1 the Kabsch fit of 4 pairs drawn by the counter-based hash of gdm.h
+//   ransac_score_kernel    one wave per 4 hypotheses of a crop: integer inlier counts (ballot + popcount, no float atomics)
+//   ransac_select_kernel   one workgroup per crop: the reference's selection rule on the counts, and the fp64 refit on the inliers
+// ICP (pvn3d_eval_utils_kpls.py:126-212 icp) runs scene -> model: icp_transform_kernel maps the selected scene points into the model
+// frame, the exact kNN (K = 1) finds the nearest vertex, icp_update_kernel refits the absolute pose from (model[nn], scene) in fp64
+// and applies the reference's convergence rule per crop, freezing a crop on the device once it stops.
+#include "gdm_common.h"
+
+namespace {
+
+constexpr int SCORE_HYP_PER_WAVE = 4;
+constexpr int SCORE_HYP_PER_BLOCK = 4 * SCORE_HYP_PER_WAVE;        // 256 threads = 4 waves
+
+__device__ __forceinline__ void sentinel_pose(float* o)
+{
+    o[0] = 1.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
+    o[4] = 0.f; o[5] = 1.f; o[6] = 0.f; o[7] = 0.f;
+    o[8] = 0.f; o[9] = 0.f; o[10] = 1.f; o[11] = -1000.f;
+}
+
+// [R | t] from the 16 statistics { n, sum A, sum B, sum A_i B_j }, n >= 1 (the same math as kabsch_solve_kernel).
+__device__ __forceinline__ void kabsch_fit(const double* st, float* o)
+{
+    const double n = st[0];
+#include "gdm_kabsch_fit.inc"
+}
+
+// lowbias32 (include/gdm.h, GDM_RANSAC sampling)
+__device__ __forceinline__ uint32_t mix32(uint32_t x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+
+// Squared residual |R a + t - b|^2 in fp32, evaluated in one fixed order (scoring and refit must agree on every inlier).
+__device__ __forceinline__ float residual2(const float* rt, float ax, float ay, float az, float bx, float by, float bz)
+{
+    const float ex = rt[0] * ax + rt[1] * ay + rt[2] * az + rt[3] - bx;
+    const float ey = rt[4] * ax + rt[5] * ay + rt[6] * az + rt[7] - by;
+    const float ez = rt[8] * ax + rt[9] * ay + rt[10] * az + rt[11] - bz;
+    return ex * ex + ey * ey + ez * ez;
+}
+
+__device__ __forceinline__ void acc_pair(double* acc, double ax, double ay, double az, double bx, double by, double bz)
+{
+    acc[0] += 1.0;
+    acc[1] += ax; acc[2] += ay; acc[3] += az;
+    acc[4] += bx; acc[5] += by; acc[6] += bz;
+    acc[7] += ax * bx; acc[8] += ax * by; acc[9] += ax * bz;
+    acc[10] += ay * bx; acc[11] += ay * by; acc[12] += ay * bz;
+    acc[13] += az * bx; acc[14] += az * by; acc[15] += az * bz;
+}
+
+// Sum of NA per-thread accumulators over a 256-thread block in a fixed order (butterfly in each wave, then waves 0..3);
+// every thread gets the totals in tot[].
+template <int NA>
+__device__ __forceinline__ void block_sum(double* acc, double (*red)[NA], double* tot)
+{
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        double v = acc[i];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        acc[i] = v;
+    }
+    if ((threadIdx.x & 63) == 0)
+        for (int i = 0; i < NA; ++i) red[threadIdx.x >> 6][i] = acc[i];
+    __syncthreads();
+    for (int i = 0; i < NA; ++i) tot[i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
+}
+
+// pts f32[B][6][N]: planes ax, ay, az, bx, by, bz of the selected pairs in point order; nsel i32[B] their number.
+__global__ __launch_bounds__(256) void ransac_compact_kernel(const float* __restrict__ scene_xyz, long scene_bstride, int pt_stride,
+                                                             int ch_stride, const float* __restrict__ model_xyz,
+                                                             const int32_t* __restrict__ best_idx, const uint8_t* __restrict__ mask,
+                                                             int N, int M, float* __restrict__ pts, int32_t* __restrict__ nsel)
+{
+    __shared__ int wtot[4];
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* sp = scene_xyz + (long)b * scene_bstride;
+    float* P = pts + (long)b * 6 * N;
+    int run = 0;
+    for (int c0 = 0; c0 < N; c0 += 256) {
+        const int i = c0 + threadIdx.x;
+        const bool sel = i < N && mask[(long)b * N + i];
+        const unsigned long long bal = __ballot(sel);
+        const int below = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wtot[wave] = __popcll(bal);
+        __syncthreads();
+        int off = run;
+        for (int w = 0; w < wave; ++w) off += wtot[w];
+        if (sel) {
+            int j = best_idx[(long)b * N + i];
+            j = min(max(j, 0), M - 1);
+            const int k = off + below;
+            P[k] = model_xyz[3 * j];
+            P[N + k] = model_xyz[3 * j + 1];
+            P[2 * N + k] = model_xyz[3 * j + 2];
+            P[3 * N + k] = sp[(long)i * pt_stride];
+            P[4 * N + k] = sp[(long)i * pt_stride + ch_stride];
+            P[5 * N + k] = sp[(long)i * pt_stride + 2 * ch_stride];
+        }
+        run += wtot[0] + wtot[1] + wtot[2] + wtot[3];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) nsel[b] = run;
+}
+
+// hyp f32[B][H][12]: hypothesis poses.  Crops with n < min_points get the identity (never scored).
+__global__ __launch_bounds__(64) void ransac_hyp_kernel(const float* __restrict__ pts, const int32_t* __restrict__ nsel,
+                                                        const double* __restrict__ stats, int N, int H, int min_points, uint32_t seed,
+                                                        float* __restrict__ hyp)
+{
+    const int b = blockIdx.y;
+    const int h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= H) return;
+    float* o = hyp + ((long)b * H + h) * 12;
+    const int n = nsel[b];
+    if (n < min_points) {
+        o[0] = 1.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
+        o[4] = 0.f; o[5] = 1.f; o[6] = 0.f; o[7] = 0.f;
+        o[8] = 0.f; o[9] = 0.f; o[10] = 1.f; o[11] = 0.f;
+        return;
+    }
+    if (h == 0) {                                                   // pvn3d_eval_utils_kpls.py:95 curr_RT = best_fit_transform(A, B)
+        kabsch_fit(stats + (long)b * 16, o);
+        return;
+    }
+    const float* P = pts + (long)b * 6 * N;
+    const uint32_t hb = mix32(mix32(seed ^ 0x9e3779b9u) ^ (uint32_t)b);
+    double st[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) st[i] = 0.0;
+    for (int s = 0; s < 4; ++s) {                                   // :115-118 np.random.randint(0, ptsnum, 4), with replacement
+        const uint32_t r = mix32(hb ^ (uint32_t)(4 * h + s));
+        const int k = (int)(((unsigned long long)r * (unsigned long long)n) >> 32);
+        acc_pair(st, P[k], P[N + k], P[2 * N + k], P[3 * N + k], P[4 * N + k], P[5 * N + k]);
+    }
+    kabsch_fit(st, o);
+}
+
+// counts i32[B][H]: the inliers of every hypothesis, |R a + t - b| <= match_err (:104-106).
+__global__ __launch_bounds__(256) void ransac_score_kernel(const float* __restrict__ pts, const int32_t* __restrict__ nsel,
+                                                           const float* __restrict__ hyp, int N, int H, int min_points, float thr2,
+                                                           int32_t* __restrict__ counts)
+{
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h0 = blockIdx.x * SCORE_HYP_PER_BLOCK + wave * SCORE_HYP_PER_WAVE;
+    if (h0 >= H) return;                                            // wave-uniform: no barrier below
+    const int n = nsel[b];
+    float rt[SCORE_HYP_PER_WAVE][12];
+#pragma unroll
+    for (int k = 0; k < SCORE_HYP_PER_WAVE; ++k) {
+        const float* src = hyp + ((long)b * H + min(h0 + k, H - 1)) * 12;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) rt[k][e] = src[e];
+    }
+    int c[SCORE_HYP_PER_WAVE] = {0, 0, 0, 0};
+    if (n >= min_points) {
+        const float* P = pts + (long)b * 6 * N;
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const bool in = i < n;
+            const int k = in ? i : 0;
+            const float ax = P[k], ay = P[N + k], az = P[2 * N + k], bx = P[3 * N + k], by = P[4 * N + k], bz = P[5 * N + k];
+#pragma unroll
+            for (int q = 0; q < SCORE_HYP_PER_WAVE; ++q)
+                c[q] += __popcll(__ballot(in && residual2(rt[q], ax, ay, az, bx, by, bz) <= thr2));
+        }
+    }
+    if (lane == 0)
+        for (int q = 0; q < SCORE_HYP_PER_WAVE; ++q)
+            if (h0 + q < H) counts[(long)b * H + h0 + q] = c[q];
+}
+
+// The reference's sequential rule on the counts (:102-110): the FIRST h with c_h > fix_percent * n wins and is refit on its inliers;
+// otherwise the largest c_h (lowest h on ties) wins without a refit.  No inlier at all -> the sentinel (the reference returns zeros).
+__global__ __launch_bounds__(256) void ransac_select_kernel(const float* __restrict__ pts, const int32_t* __restrict__ nsel,
+                                                            const float* __restrict__ hyp, const int32_t* __restrict__ counts, int N,
+                                                            int H, int min_points, float thr2, double fix_percent,
+                                                            float* __restrict__ RT, uint8_t* __restrict__ valid,
+                                                            int32_t* __restrict__ winner)
+{
+    __shared__ int s_first[4], s_bc[4], s_bh[4];
+    __shared__ double red[4][16];
+    __shared__ float s_rt[12];
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = nsel[b];
+    float* o = RT + (long)b * 12;
+    if (n < min_points) {                                           // evaluator.py:94-96
+        if (threadIdx.x == 0) { sentinel_pose(o); valid[b] = 0; winner[b] = -1; }
+        return;
+    }
+    const double lim = fix_percent * (double)n;
+    int first = 0x7fffffff, bc = -1, bh = 0x7fffffff;
+    for (int h = threadIdx.x; h < H; h += 256) {
+        const int c = counts[(long)b * H + h];
+        if ((double)c > lim && h < first) first = h;
+        if (c > bc || (c == bc && h < bh)) { bc = c; bh = h; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        first = min(first, __shfl_xor(first, off, 64));
+        const int oc = __shfl_xor(bc, off, 64), oh = __shfl_xor(bh, off, 64);
+        if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
+    }
+    if (lane == 0) { s_first[wave] = first; s_bc[wave] = bc; s_bh[wave] = bh; }
+    __syncthreads();
+    first = s_first[0]; bc = s_bc[0]; bh = s_bh[0];
+    for (int w = 1; w < 4; ++w) {
+        first = min(first, s_first[w]);
+        if (s_bc[w] > bc || (s_bc[w] == bc && s_bh[w] < bh)) { bc = s_bc[w]; bh = s_bh[w]; }
+    }
+    if (first == 0x7fffffff) {                                      // no early exit: the best hypothesis as it is
+        if (threadIdx.x == 0) {
+            if (bc <= 0) { sentinel_pose(o); valid[b] = 0; winner[b] = -1; }
+            else {
+                const float* src = hyp + ((long)b * H + bh) * 12;
+                for (int e = 0; e < 12; ++e) o[e] = src[e];
+                valid[b] = 1; winner[b] = bh;
+            }
+        }
+        return;
+    }
+    if (threadIdx.x < 12) s_rt[threadIdx.x] = hyp[((long)b * H + first) * 12 + threadIdx.x];
+    __syncthreads();
+    float rt[12];
+    for (int e = 0; e < 12; ++e) rt[e] = s_rt[e];
+    const float* P = pts + (long)b * 6 * N;
+    double acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {                    // :108 best_fit_transform(A[match_idx], B[match_idx])
+        const float ax = P[i], ay = P[N + i], az = P[2 * N + i], bx = P[3 * N + i], by = P[4 * N + i], bz = P[5 * N + i];
+        if (residual2(rt, ax, ay, az, bx, by, bz) <= thr2) acc_pair(acc, ax, ay, az, bx, by, bz);
+    }
+    double tot[16];
+    block_sum<16>(acc, red, tot);
+    if (threadIdx.x == 0) {
+        kabsch_fit(tot, o);
+        valid[b] = 1;
+        winner[b] = first;
+    }
+}
+
+// query f32[B,N,3] = R^T (b - t): the scene points in the model frame of the current pose.
+__global__ __launch_bounds__(256) void icp_transform_kernel(const float* __restrict__ scene_xyz, long scene_bstride, int pt_stride,
+                                                            int ch_stride, const float* __restrict__ RT, int N,
+                                                            float* __restrict__ query)
+{
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const float* r = RT + (long)b * 12;
+    const float* sp = scene_xyz + (long)b * scene_bstride + (long)i * pt_stride;
+    const float dx = sp[0] - r[3], dy = sp[ch_stride] - r[7], dz = sp[2 * ch_stride] - r[11];
+    float* q = query + ((long)b * N + i) * 3;
+    q[0] = r[0] * dx + r[4] * dy + r[8] * dz;
+    q[1] = r[1] * dx + r[5] * dy + r[9] * dz;
+    q[2] = r[2] * dx + r[6] * dy + r[10] * dz;
+}
+
+// One ICP iteration of every active crop (:191-207): pairs (model[nn], scene) of the selected points (minus those farther than
+// reject_dist when it is >= 0) -> fp64 statistics -> the absolute pose.  mean = mean pair distance before the update; the update is
+// applied, then |err - mean| < tolerance stops the crop; err <- mean.  Fewer than min_points pairs: the crop stops unchanged.
+__global__ __launch_bounds__(256) void icp_update_kernel(const float* __restrict__ scene_xyz, long scene_bstride, int pt_stride,
+                                                         int ch_stride, const float* __restrict__ model_xyz, const int32_t* __restrict__ nn,
+                                                         const float* __restrict__ d2, const uint8_t* __restrict__ mask, int N, int M,
+                                                         float reject2, double tolerance, int min_points, float* __restrict__ RT,
+                                                         uint8_t* __restrict__ active, int32_t* __restrict__ iters,
+                                                         double* __restrict__ err)
+{
+    __shared__ double red[4][17];
+    const int b = blockIdx.x;
+    if (!active[b]) return;                                         // block-uniform
+    const float* sp = scene_xyz + (long)b * scene_bstride;
+    double acc[17];
+#pragma unroll
+    for (int i = 0; i < 17; ++i) acc[i] = 0.0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        if (!mask[(long)b * N + i]) continue;
+        const float dd = fmaxf(d2[(long)b * N + i], 0.f);
+        if (reject2 >= 0.f && !(dd <= reject2)) continue;
+        int j = nn[(long)b * N + i];
+        j = min(max(j, 0), M - 1);
+        acc_pair(acc, model_xyz[3 * j], model_xyz[3 * j + 1], model_xyz[3 * j + 2], sp[(long)i * pt_stride],
+                 sp[(long)i * pt_stride + ch_stride], sp[(long)i * pt_stride + 2 * ch_stride]);
+        acc[16] += sqrt((double)dd);
+    }
+    double tot[17];
+    block_sum<17>(acc, red, tot);
+    if (threadIdx.x != 0) return;
+    if (!(tot[0] >= (double)min_points)) { active[b] = 0; return; }
+    kabsch_fit(tot, RT + (long)b * 12);
+    iters[b] += 1;
+    const double mean = tot[16] / tot[0];
+    if (fabs(err[b] - mean) < tolerance) active[b] = 0;
+    err[b] = mean;
+}
+
+struct RansacWs {
+    float* pts;
+    float* hyp;
+    int32_t* nsel;
+    size_t bytes;
+};
+
+RansacWs ransac_ws(void* base, int B, int N, int H)
+{
+    RansacWs w;
+    const size_t pts = ((size_t)B * 6 * N * sizeof(float) + 255) & ~(size_t)255;
+    const size_t hyp = ((size_t)B * H * 12 * sizeof(float) + 255) & ~(size_t)255;
+    const size_t nsel = ((size_t)B * sizeof(int32_t) + 255) & ~(size_t)255;
+    char* p = (char*)base;
+    w.pts = (float*)p;
+    w.hyp = (float*)(p + pts);
+    w.nsel = (int32_t*)(p + pts + hyp);
+    w.bytes = pts + hyp + nsel;
+    return w;
+}
+
+} // namespace
+
+extern "C" size_t gdm_ransac_workspace_bytes(int B, int N, int H)
+{
+    if (B < 1 || N < 1 || H < 1 || H > GDM_RANSAC_MAX_H) return 0;
+    return ransac_ws(nullptr, B, N, H).bytes;
+}
+
+extern "C" int gdm_ransac_pose_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* model_xyz,
+                                   const int32_t* best_idx, const uint8_t* mask, const double* stats, int B, int N, int M, int H,
+                                   float match_err, double fix_percent, uint32_t seed, int min_points, void* workspace,
+                                   size_t workspace_bytes, float* RT, uint8_t* valid, int32_t* counts, int32_t* winner, void* stream)
+{
+    GDM_CHECK_ARG(scene_xyz && model_xyz && best_idx && mask && stats && workspace && RT && valid && counts && winner,
+                  "gdm_ransac_pose_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_ransac_pose_hip: bad shape B=%d N=%d M=%d", B, N, M);
+    GDM_CHECK_ARG(pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0, "gdm_ransac_pose_hip: bad scene strides");
+    GDM_CHECK_ARG(B <= 65535, "gdm_ransac_pose_hip: B=%d > 65535", B);
+    GDM_CHECK_ARG(H >= 1 && H <= GDM_RANSAC_MAX_H, "gdm_ransac_pose_hip: H=%d not in [1,%d]", H, GDM_RANSAC_MAX_H);
+    GDM_CHECK_ARG(match_err > 0.f && match_err < 1e18f, "gdm_ransac_pose_hip: match_err=%g must be > 0", (double)match_err);
+    GDM_CHECK_ARG(fix_percent > 0.0 && fix_percent <= 1.0, "gdm_ransac_pose_hip: fix_percent=%g not in (0, 1]", fix_percent);
+    GDM_CHECK_ARG(min_points >= 1, "gdm_ransac_pose_hip: min_points=%d must be >= 1", min_points);
+    const RansacWs w = ransac_ws(workspace, B, N, H);
+    GDM_CHECK_ARG(workspace_bytes >= w.bytes, "gdm_ransac_pose_hip: workspace of %zu bytes, %zu needed", workspace_bytes, w.bytes);
+    GDM_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "gdm_ransac_pose_hip: workspace must be 16-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    const float thr2 = match_err * match_err;
+    hipLaunchKernelGGL(ransac_compact_kernel, dim3(B), dim3(256), 0, s, scene_xyz, scene_bstride, pt_stride, ch_stride, model_xyz,
+                       best_idx, mask, N, M, w.pts, w.nsel);
+    int rc = gdm_launch_status("ransac_compact_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ransac_hyp_kernel, dim3(gdm_cdiv(H, 64), B), dim3(64), 0, s, w.pts, w.nsel, stats, N, H, min_points, seed, w.hyp);
+    if ((rc = gdm_launch_status("ransac_hyp_kernel"))) return rc;
+    hipLaunchKernelGGL(ransac_score_kernel, dim3(gdm_cdiv(H, SCORE_HYP_PER_BLOCK), B), dim3(256), 0, s, w.pts, w.nsel, w.hyp, N, H,
+                       min_points, thr2, counts);
+    if ((rc = gdm_launch_status("ransac_score_kernel"))) return rc;
+    hipLaunchKernelGGL(ransac_select_kernel, dim3(B), dim3(256), 0, s, w.pts, w.nsel, w.hyp, counts, N, H, min_points, thr2, fix_percent,
+                       RT, valid, winner);
+    return gdm_launch_status("ransac_select_kernel");
+}
+
+extern "C" int gdm_icp_transform_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* RT, int B,
+                                     int N, float* query, void* stream)
+{
+    GDM_CHECK_ARG(scene_xyz && RT && query, "gdm_icp_transform_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && N >= 1, "gdm_icp_transform_hip: bad shape B=%d N=%d", B, N);
+    GDM_CHECK_ARG(pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0, "gdm_icp_transform_hip: bad scene strides");
+    GDM_CHECK_ARG(B <= 65535, "gdm_icp_transform_hip: B=%d > 65535", B);
+    hipLaunchKernelGGL(icp_transform_kernel, dim3(gdm_cdiv(N, 256), B), dim3(256), 0, (hipStream_t)stream, scene_xyz, scene_bstride,
+                       pt_stride, ch_stride, RT, N, query);
+    return gdm_launch_status("icp_transform_kernel");
+}
+
+extern "C" int gdm_icp_update_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* model_xyz,
+                                  const int32_t* nn, const float* d2, const uint8_t* mask, int B, int N, int M, float reject_dist,
+                                  double tolerance, int min_points, float* RT, uint8_t* active, int32_t* iters, double* err, void* stream)
+{
+    GDM_CHECK_ARG(scene_xyz && model_xyz && nn && d2 && mask && RT && active && iters && err, "gdm_icp_update_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_icp_update_hip: bad shape B=%d N=%d M=%d", B, N, M);
+    GDM_CHECK_ARG(pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0, "gdm_icp_update_hip: bad scene strides");
+    GDM_CHECK_ARG(tolerance >= 0.0, "gdm_icp_update_hip: tolerance=%g must be >= 0", tolerance);
+    GDM_CHECK_ARG(min_points >= 1, "gdm_icp_update_hip: min_points=%d must be >= 1", min_points);
+    const float reject2 = reject_dist >= 0.f ? reject_dist * reject_dist : -1.f;
+    hipLaunchKernelGGL(icp_update_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scene_xyz, scene_bstride, pt_stride, ch_stride,
+                       model_xyz, nn, d2, mask, N, M, reject2, tolerance, min_points, RT, active, iters, err);
+    return gdm_launch_status("icp_update_kernel");
+}

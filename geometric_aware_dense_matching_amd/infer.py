@@ -12,10 +12,11 @@ from . import matching, ops, pose, pyramid, settings
 _PREC = {"bf16x3": ops.MATCH_BF16X3, "f32": ops.MATCH_F32, 0: 0, 1: 1}
 
 
-def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf16x3"):
+def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf16x3", pose_fit="kabsch", icp_iters=0, pose_opts=None):
     """model_dict: {cls_id: GeoMatch (eval, on the GPU)}; inputs: dict of batched device tensors (loader keys, plus
-    `dpt_xyz` when the neighbour pyramid is not already in it); cls_ids: int tensor/list [bs].
-    Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, RT, valid])."""
+    `dpt_xyz` when the neighbour pyramid is not already in it); cls_ids: int tensor/list [bs].  pose_fit / icp_iters / pose_opts:
+    pose.estimate_poses (the defaults are the plain Kabsch fit).
+    Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, RT, valid[, icp_iters, icp_resid]])."""
     cls = torch.as_tensor(cls_ids).cpu().tolist()
     bs = len(cls)
     out = {}
@@ -33,7 +34,7 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
             part = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"].expand(len(sel), -1, -1), mask=res["mask"],
                         best_idx=res["best_idx"], best_sim=res["best_sim"])
             if with_pose:
-                part["RT"], part["valid"] = pose.solve_poses(res, sub["cld_rgb_nrm"], model.model_emb.xyz)
+                part.update(pose.estimate_poses(res, sub["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts))
             for k, v in part.items():
                 out.setdefault(k, []).append(v)
             order += sel
@@ -43,12 +44,13 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
     return {k: torch.cat(v, dim=0).index_select(0, inv) for k, v in out.items()}
 
 
-def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyramid=False):
+def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyramid=False, pose_fit="kabsch", icp_iters=0, pose_opts=None):
     """ONE pass of the hot path over a batch of crops resident on the device: neighbour pyramid (unless `inputs` already carries the
     loader's index arrays) -> GeoMatch.forward (eval) -> seg mask + descriptor packs + N x M arg-max (evaluator.py:78-93) [-> pose].
     Everything is enqueued on the current stream (and, with settings.USE_SIDE_STREAMS, on side streams forked from and joined back to
     it) with no host synchronisation, so the call captures in a hipGraph as it is.  Returns dict(seg, rgbd, mesh, mask, count,
-    best_idx, best_sim[, RT, valid]) plus the 30 pyramid arrays when keep_pyramid."""
+    best_idx, best_sim[, RT, valid[, icp_iters, icp_resid]]) plus the 30 pyramid arrays when keep_pyramid.  The pose stage is
+    pose.estimate_poses(pose_fit, icp_iters, pose_opts): RANSAC and ICP run on the device too, with no host branching."""
     prec = _PREC[precision]
     d = dict(inputs)
     pyr = None
@@ -61,7 +63,7 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
     mask, count, bi, bs = matching.match_tail(ep, B, N, M, prec)
     out = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=mask, count=count, best_idx=bi, best_sim=bs)
     if with_pose:
-        out["RT"], out["valid"] = pose.solve_poses(out, d["cld_rgb_nrm"], model.model_emb.xyz)
+        out.update(pose.estimate_poses(out, d["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts))
     if keep_pyramid and pyr is not None:
         out.update((k, v) for k, v in pyr.items() if torch.is_tensor(v))
     return out
@@ -92,9 +94,10 @@ class GraphedPipeline:
     freed after the decision (keep_both=True keeps both: `replay(form)`)."""
 
     def __init__(self, model, example_inputs, precision="bf16x3", with_pose=True, warmup=3, forked="auto", burst=8,
-                 keep_pyramid=False, capture_error_mode=None, keep_both=False):
+                 keep_pyramid=False, capture_error_mode=None, keep_both=False, pose_fit="kabsch", icp_iters=0, pose_opts=None):
         self.model = model.eval()
         self.precision, self.with_pose, self.keep_pyramid = precision, with_pose, keep_pyramid
+        self.pose_fit, self.icp_iters, self.pose_opts = pose_fit, icp_iters, dict(pose_opts or {})
         self.static_in = {k: v.clone() for k, v in example_inputs.items() if torch.is_tensor(v)}
         self.graphs, self.outs, self.pools, self.check = {}, {}, {}, {}
         self._cap_kw = {"capture_error_mode": capture_error_mode} if capture_error_mode else {}
@@ -137,7 +140,8 @@ class GraphedPipeline:
 
     # -- construction helpers ---------------------------------------------------------------------------------------------
     def _step(self):
-        return pipeline_step(self.model, self.static_in, self.precision, self.with_pose, self.keep_pyramid)
+        return pipeline_step(self.model, self.static_in, self.precision, self.with_pose, self.keep_pyramid, self.pose_fit, self.icp_iters,
+                             self.pose_opts)
 
     def _eager_reference(self, warmup):
         """Eager single-stream steps on the example inputs (they also fill the per-module caches); the last one's outputs, cloned."""

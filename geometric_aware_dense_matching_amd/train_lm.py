@@ -77,6 +77,15 @@ def build_parser():
                    help="test: directory for the evaluator's files -- BOP result csv, error / recall / precision pickles, table text")
     p.add_argument("--graph-batch1", action="store_true",
                    help="test: per-object hipGraph replay for single-instance groups (a batch-1 eager step is launch-bound)")
+    p.add_argument("--pose-fit", dest="pose_fit", type=str, default="kabsch", choices=["kabsch", "ransac"],
+                   help="test: pose fit from the correspondences -- least squares over all of them (evaluator.py:97) or the reference's "
+                        "RANSAC (pvn3d_eval_utils_kpls.py:79-124), both on the GPU")
+    p.add_argument("--ransac-iters", dest="ransac_iters", type=int, default=20, help="test: RANSAC hypotheses per crop (max_iter)")
+    p.add_argument("--ransac-inlier-dist", dest="ransac_inlier_dist", type=float, default=0.015,
+                   help="test: RANSAC inlier distance in metres (match_err)")
+    p.add_argument("--icp-iters", dest="icp_iters", type=int, default=0,
+                   help="test: point-to-point ICP iterations after the fit (pvn3d_eval_utils_kpls.py:126-212); 0 = none")
+    p.add_argument("--icp-tolerance", dest="icp_tolerance", type=float, default=0.001, help="test: ICP convergence tolerance (m)")
     p.add_argument("--objects-across-gpus", action="store_true",
                    help="train: the dataset's objects are independent jobs (train_ycb.sh:3-9 runs them one after the other): rank r of a "
                         "torch.distributed.run launch trains objects r, r + world, ... on its own GPU as single-process jobs -- no process "
@@ -350,6 +359,9 @@ def test(args):
     loader = torch.utils.data.DataLoader(make_dataset(args, "test", cls_ids=ids), batch_size=batch_size, shuffle=False, num_workers=2)
     graphs = {}
     results = []
+    pose_kw = dict(pose_fit=args.pose_fit, icp_iters=args.icp_iters,
+                   pose_opts=dict(ransac_iters=args.ransac_iters, ransac_inlier_dist=args.ransac_inlier_dist,
+                                  icp_tolerance=args.icp_tolerance))
     # evaluator.py:308-463: when the loader carries ground-truth poses (`RT`), every instance's ADD(-S) / re / te / re-projection error
     # is computed on the device per object group and the reference's recall table is printed at the end
     from . import evaluation
@@ -368,10 +380,10 @@ def test(args):
                 cid = cls[0]
                 one = {k: cu[k] for k in ("rgb", "cld_rgb_nrm", "choose", "dpt_xyz")}
                 if cid not in graphs:
-                    graphs[cid] = infer.GraphedPipeline(model_dict[cid], one)
+                    graphs[cid] = infer.GraphedPipeline(model_dict[cid], one, **pose_kw)
                 out = {k: v.clone() for k, v in graphs[cid](one).items()}
             else:
-                out = infer.run_multi_object(model_dict, cu, cls)
+                out = infer.run_multi_object(model_dict, cu, cls, **pose_kw)
             torch.cuda.synchronize()
             results.append(dict(time=time.perf_counter() - t0, cls_id=cls, count=out["mask"].sum(dim=1).cpu(), best_idx=out["best_idx"].cpu(),
                                 best_sim=out["best_sim"].cpu(), mask=out["mask"].cpu(), RT=out["RT"].cpu(), valid=out["valid"].cpu()))

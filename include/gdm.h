@@ -57,7 +57,7 @@ typedef struct gdm_knn_job {
     const float* query;       /* f32[B,Q,3], batch item b at query + b*query_bstride     */
     int32_t* idx;             /* i32[B,Q,K] dense */
     float* d2;                /* f32[B,Q,K] dense, or NULL */
-    int64_t support_bstride;  /* in floats; S*3 when dense. A prefix slice cld[:, :S] of a  */
+    int64_t support_bstride;  /* in floats; S*3 when dense (0: one support shared by all). A prefix slice cld[:, :S] of a  */
     int64_t query_bstride;    /* [B,N,3] array keeps bstride N*3 (linemod_pbr.py:538)     */
     int32_t S, Q, K;
     int32_t grid_w;           /* 0, or: the support is an ORGANISED map (e.g. the xyz of a depth crop) of S / grid_w rows x grid_w columns
@@ -304,6 +304,46 @@ int gdm_kabsch_stats_hip(const float* scene_xyz, long scene_bstride, int pt_stri
  * reference's sentinel pose [I | (0,0,-1000)] (evaluator.py:94-96).  The optimal proper rotation is obtained as Horn's unit
  * quaternion (largest eigenvector of a symmetric 4x4, cyclic Jacobi, f64) -- the same R as SVD + reflection fix. */
 int gdm_kabsch_solve_hip(const double* stats, int B, int min_points, float* RT, uint8_t* valid, void* stream);
+
+/* Robust fit: the reference's RANSAC (utils/pvn3d_eval_utils_kpls.py:79-124 best_fit_transform_with_RANSAC, used next to
+ * best_fit_transform by evaluator.py:21) for a whole batch, every hypothesis evaluated at once.  Same correspondences as
+ * gdm_kabsch_stats_hip (same arguments), plus `stats` = its output for them.  H = max_iter hypotheses per crop:
+ *   h = 0      the Kabsch fit of all n selected pairs (what gdm_kabsch_solve_hip returns);
+ *   h >= 1     the Kabsch fit of 4 pairs drawn with replacement from the selected pairs in point order (np.random.randint(0, n, 4)
+ *              indexing A[cls_msk]; the reference's draw of iteration i is hypothesis i + 1, its last draw is never scored).
+ *              Sampling is a stateless counter-based hash (no host RNG; eager, graph and forked-graph runs are bit-identical):
+ *                mix(x) = lowbias32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *                r      = mix(mix(mix(seed ^ 0x9e3779b9) ^ b) ^ (4 h + s)),  s = 0..3
+ *                index  = (uint64(r) * n) >> 32
+ *              (restated in Python as pose.ransac_sample_indices).
+ * counts i32[B,H]: c_h = #{selected pairs with |R a + t - b|^2 <= match_err^2}, fp32, integer counts (no float atomics).
+ * Selection (the reference's sequential rule): the FIRST h with c_h > fix_percent * n (fp64) wins and RT is the Kabsch refit on its
+ * inliers; otherwise the largest c_h wins (lowest h on ties) and RT is that hypothesis, without a refit.  winner i32[B] = that h.
+ * n < min_points -> the sentinel [I | (0,0,-1000)], valid = 0, winner = -1.  Every c_h == 0 -> the same sentinel, valid = 0,
+ * winner = -1 (the one deliberate deviation: the reference returns an all-zero matrix there).
+ * 1 <= H <= GDM_RANSAC_MAX_H, match_err > 0, 0 < fix_percent <= 1, B <= 65535.  workspace: device memory, 16-byte aligned, of at
+ * least gdm_ransac_workspace_bytes(B, N, H) bytes (the compacted pairs and the H hypothesis poses of every crop). */
+#define GDM_RANSAC_MAX_H 4096
+size_t gdm_ransac_workspace_bytes(int B, int N, int H);
+int gdm_ransac_pose_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* model_xyz,
+                        const int32_t* best_idx, const uint8_t* mask, const double* stats, int B, int N, int M, int H,
+                        float match_err, double fix_percent, uint32_t seed, int min_points, void* workspace, size_t workspace_bytes,
+                        float* RT, uint8_t* valid, int32_t* counts, int32_t* winner, void* stream);
+
+/* Point-to-point ICP refinement, scene -> model (utils/pvn3d_eval_utils_kpls.py:126-212 icp, run as icp(scene, model, RT^-1)).
+ * One iteration = gdm_icp_transform_hip, an exact K = 1 search of the query among the model vertices (gdm_knn_jobs_ws_hip, support
+ * batch stride 0, with d2), gdm_icp_update_hip.
+ * gdm_icp_transform_hip: query f32[B,N,3] = R^T (b - t) for every scene point b (same addressing as gdm_kabsch_stats_hip), RT f32[B,3,4].
+ * gdm_icp_update_hip: for every crop with active != 0, the pairs (model_xyz[nn], b) of the points with mask != 0 (and, when
+ * reject_dist >= 0, d2 <= reject_dist^2) -> fp64 statistics -> RT is refit (absolute pose), iters += 1, mean = mean pair distance
+ * (before the update, as :193-204); |err - mean| < tolerance sets active = 0; err = mean.  err starts at 0 (prev_error = 0, :189).
+ * Fewer than min_points pairs: active = 0 and the crop is left unchanged.  nn i32[B,N], d2 f32[B,N] (the K = 1 search),
+ * active u8[B], iters i32[B], err f64[B] are read and written: a fixed number of iterations runs without host synchronisation. */
+int gdm_icp_transform_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* RT, int B, int N,
+                          float* query, void* stream);
+int gdm_icp_update_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* model_xyz,
+                       const int32_t* nn, const float* d2, const uint8_t* mask, int B, int N, int M, float reject_dist,
+                       double tolerance, int min_points, float* RT, uint8_t* active, int32_t* iters, double* err, void* stream);
 
 /* Eval-mode BatchNorm + activation + max over the K neighbours (DGCNN edge convolutions, dgcnn.py:104-117) in one pass:
  * out[plane,i] = max_k act(scale[c]*x[plane,i,k] + shift[c]), c = plane % C; x f32[planes,n,K], K % 4 == 0, planes <= 65535. */
