@@ -35,9 +35,11 @@ def sample_valid_pixels(xyz, n_points, generator=None):
     return torch.gather(order, 1, j).to(torch.int32).unsqueeze(1)
 
 
-def make_inputs(rgb_norm, depth, normals, K, origin, S, n_points, generator=None):
+def make_inputs(rgb_norm, depth, normals, K, origin, S, n_points, generator=None, mask=None):
     """rgb_norm f32[B,3,H,W] (already colour-normalised), depth f32[B,H,W], normals f32[B,3,H,W], K f32[B,3,3],
-    origin i32[B,2] -> the model's input dict incl. the neighbour pyramid, all on the device."""
+    origin i32[B,2] -> the model's input dict incl. the neighbour pyramid, all on the device.  With the object mask [B,H,W]
+    (any dtype) the dict also holds origin_labels [B,N]: the mask at the chosen points, 255 mapped to 1 (linemod_pbr.py:470,
+    :501-502), the labels targets.pose_gt_info takes."""
     B = depth.shape[0]
     xyz = depth_to_xyz(depth, K, origin, S)                                          # [B,S,S,3]
     ys = (origin[:, 1:2].long() + torch.arange(S, device=depth.device)[None]).clamp(0, depth.shape[1] - 1)
@@ -52,5 +54,9 @@ def make_inputs(rgb_norm, depth, normals, K, origin, S, n_points, generator=None
     nrm_pt = torch.gather(nrm_c.reshape(B, 3, S * S), 2, ch[:, None, :].expand(-1, 3, -1))
     inputs = dict(rgb=rgb_c, cld_rgb_nrm=torch.cat([cld.transpose(1, 2), rgb_pt, nrm_pt], dim=1).contiguous(), choose=choose,
                   dpt_xyz=xyz)
+    if mask is not None:
+        msk = mask[bidx, ys[:, :, None], xs[:, None, :]].reshape(B, S * S)                  # [B,S*S], the crop of the mask
+        lab = torch.gather(msk, 1, ch)
+        inputs["origin_labels"] = torch.where(lab == 255, torch.ones_like(lab), lab)
     inputs.update(pyramid.build_pyramid(cld.contiguous(), xyz))
     return inputs

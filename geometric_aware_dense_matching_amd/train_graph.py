@@ -44,7 +44,7 @@ class GraphedTrainStep:
     optimiser steps whichever path ran them.
     """
 
-    def __init__(self, model, optimizer, device, warmup=3):
+    def __init__(self, model, optimizer, device, warmup=3, gt_targets="loader"):
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep captures a single-process step; multi-rank training runs the eager loop")
         self.model, self.optimizer, self.device = model, make_capturable(optimizer), device
@@ -57,12 +57,17 @@ class GraphedTrainStep:
         self.captures = 0
         self.stream = torch.cuda.Stream(device)
         self.pool = ops.BufferPool()               # scratch buffers of the captured iteration (ops.buffer_pool)
+        self.gt_targets = gt_targets               # "device": the targets are computed inside the captured iteration
+        self.replaced = torch.zeros(2, dtype=torch.int64, device=device) if gt_targets == "device" else None
+        self.static_targets = None                 # device mode: the iteration's labels / match_idx / visible_flag (after replacement)
 
     # ---- one eager iteration on static buffers (what the capture records) -------------------------------------------------------
     def _iteration(self):
         with ops.buffer_pool(self.pool):
-            out, _ = train_lm.model_fn_dec(self.model, dict(self.static_in), self.device)
+            out, cu = train_lm.model_fn_dec(self.model, dict(self.static_in), self.device, self.gt_targets, self.replaced)
             out["loss"].backward()
+        if self.gt_targets == "device":
+            self.static_targets = {k: cu[k] for k in ("labels", "match_idx", "visible_flag")}
         self.optimizer.step()
         return {k: torch.as_tensor(out[k], device=self.device).detach().float() for k in ("loss", "seg_loss", "match_loss")}
 

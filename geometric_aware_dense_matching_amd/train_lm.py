@@ -40,6 +40,9 @@ bnm_clip = 1e-2
 DEFAULT_DATASET = "lmo"                     # train_ycb.py sets "ycbv" (train_ycb.py:70)
 
 
+GT_TARGETS = ("loader", "device")
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Arg parser")
     p.add_argument("-weight_decay", type=float, default=0)
@@ -92,6 +95,10 @@ def build_parser():
                         "group, no collective")
     p.add_argument("--graph-train", action="store_true",
                    help="train: capture one iteration (forward + losses + backward + Adam) as a hipGraph and replay it (single process)")
+    p.add_argument("--gt-targets", dest="gt_targets", type=str, default="loader", choices=GT_TARGETS,
+                   help="train: 'loader' = labels / match_idx / visible_flag come with the items; 'device' = computed on the GPU from the "
+                        "items' RT and origin_labels (get_pose_gt_info, linemod_pbr.py:602-655; targets.pose_gt_info), invalid items "
+                        "replaced by the batch's first valid one")
     return p
 
 
@@ -119,15 +126,19 @@ class SyntheticCrops(torch.utils.data.Dataset):
     """Generated items with the loader's keys (datasets/lm/linemod_pbr.py:572-599): model inputs + labels,
     match_idx (index of the corresponding model vertex, M = 'no correspondence'), visible_flag, RT."""
 
-    def __init__(self, n_items, n_points, n_mesh, seed=0, cls_ids=None, with_ids=True):
+    def __init__(self, n_items, n_points, n_mesh, seed=0, cls_ids=None, with_ids=True, *, model_xyz=None):
         self.n_items, self.n_points, self.n_mesh, self.seed = n_items, n_points, n_mesh, seed
         self.cls_ids = list(cls_ids) if cls_ids else None          # test split: item i is an instance of cls_ids[i % len]
         self.with_ids = with_ids                                    # scene_id / im_id as a BOP test split carries them (evaluator.py:366-367)
+        # --gt-targets device: the object model f32[M,3] (m); items then carry a ground-truth pose and points on the posed model
+        self.model_xyz = None if model_xyz is None else np.asarray(model_xyz, dtype=np.float32)
 
     def __len__(self):
         return self.n_items
 
     def __getitem__(self, i):
+        if self.model_xyz is not None:
+            return self._posed_item(i)
         it = synthetic.make_crop(self.seed * 100003 + i, self.n_points)
         rs = np.random.RandomState(self.seed * 7 + i)
         labels = it["labels"].astype(np.int32)
@@ -135,6 +146,36 @@ class SyntheticCrops(torch.utils.data.Dataset):
         match[rs.rand(self.n_points) < 0.1] = self.n_mesh
         it.update(labels=labels, origin_labels=labels.copy(), match_idx=match, visible_flag=(rs.rand(self.n_mesh) < 0.6).astype(np.uint8),
                   RT=np.eye(4, dtype=np.float32)[:3])
+        if self.cls_ids:
+            it["cls_id"] = np.int32(self.cls_ids[i % len(self.cls_ids)])
+        if self.with_ids:
+            it["scene_id"], it["im_id"] = np.int32(1 + self.seed), np.int32(i)
+        return it
+
+    def _posed_item(self, i):
+        """An item for --gt-targets device: a pose RT (model -> camera, 0.5-1.2 m away) and labelled points on the posed model --
+        camera-facing vertices plus 1-2 mm noise, about 10 % pushed 1.5-3 cm outwards -- written over the crop's labelled points.
+        Ships RT and origin_labels; labels / match_idx / visible_flag are computed on the device."""
+        it = synthetic.make_crop(self.seed * 100003 + i, self.n_points)
+        rs = np.random.RandomState(self.seed * 7 + i + 7919)
+        q, _ = np.linalg.qr(rs.randn(3, 3))
+        q *= np.sign(np.linalg.det(q))
+        t = np.array([rs.uniform(-0.1, 0.1), rs.uniform(-0.1, 0.1), rs.uniform(0.5, 1.2)])
+        RT = np.concatenate([q, t[:, None]], axis=1).astype(np.float32)
+        posed = self.model_xyz @ RT[:, :3].T + RT[:, 3]
+        front = np.where(posed[:, 2] < np.median(posed[:, 2]))[0]
+        lab = np.where(it["labels"] > 0)[0]
+        pick = rs.choice(front, size=len(lab))
+        d = rs.randn(len(lab), 3)
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        off = rs.uniform(0.001, 0.002, size=(len(lab), 1))
+        far = rs.rand(len(lab)) < 0.1
+        out = posed[pick[far]] - posed.mean(0)
+        d[far] = out / np.linalg.norm(out, axis=1, keepdims=True)
+        off[far, 0] = rs.uniform(0.015, 0.03, size=int(far.sum()))
+        it["cld_rgb_nrm"][:3, lab] = (posed[pick] + d * off).T.astype(np.float32)
+        labels = it.pop("labels").astype(np.int32)
+        it.update(origin_labels=labels, RT=RT)
         if self.cls_ids:
             it["cls_id"] = np.int32(self.cls_ids[i % len(self.cls_ids)])
         if self.with_ids:
@@ -160,8 +201,39 @@ def to_device(data, device):
     return out
 
 
-def model_fn_dec(model, data, device):
+def device_targets(model, cu, counter=None):
+    """--gt-targets device: labels / match_idx / visible_flag of every item from its RT and origin_labels and the model's own
+    vertices (targets.pose_gt_info, get_pose_gt_info of linemod_pbr.py:602-655), in the loader's dtypes.  The reference draws another
+    item for an invalid one (:509-510, :663-668); a batch has a fixed shape here, so every invalid item is replaced by the batch's
+    first valid item (a device gather over every batch tensor), and a batch without any valid item is left as it is.  counter i64[2]
+    (device, optional) += (items replaced, items of batches without a valid item).  No host synchronisation."""
+    from . import targets
+    emb = getattr(model, "module", model).model_emb
+    B = cu["RT"].shape[0]
+    gt = targets.pose_gt_info(cu["cld_rgb_nrm"], cu["origin_labels"], cu["RT"], emb.xyz.contiguous())
+    cu["labels"] = gt["labels"].to(torch.int32)
+    cu["match_idx"] = gt["match_idx"]
+    cu["visible_flag"] = gt["visible_flag"].float()
+    valid = gt["valid"]
+    ar = torch.arange(B, device=valid.device)
+    any_valid = valid.any()
+    first = torch.argmax(valid.to(torch.float32))                    # lowest index of a valid item (0 when there is none)
+    src = torch.where(valid | ~any_valid, ar, first)
+    for k, v in list(cu.items()):
+        if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B:
+            cu[k] = v.index_select(0, src)
+    if counter is not None:
+        n_bad = (~valid).sum()
+        counter += torch.stack([torch.where(any_valid, n_bad, 0), torch.where(any_valid, 0, n_bad)]).to(counter.dtype)
+    return cu
+
+
+def model_fn_dec(model, data, device, gt_targets="loader", counter=None):
     cu = to_device(data, device)
+    if gt_targets == "device":
+        cu = device_targets(model, cu, counter)
+    elif gt_targets != "loader":
+        raise ValueError("gt_targets must be one of %s, got %r" % (GT_TARGETS, gt_targets))
     needs_pyramid = getattr(getattr(model, "module", model), "needs_pyramid", True)       # the DGCNN variant builds its own graphs
     if needs_pyramid and "cld_nei_idx0" not in cu:            # pyramid on the GPU (two launches per batch)
         cu.update(pyramid.build_pyramid(pyramid.cloud_from_inputs(cu["cld_rgb_nrm"]), cu["dpt_xyz"]))
@@ -173,8 +245,11 @@ class Trainer:
     """train_lm.py:178-296."""
 
     def __init__(self, model, optimizer, checkpoint_dir, obj_name, lr_scheduler=None, bnm_scheduler=None, device=None,
-                 local_rank=0, save_every=10, log_every=100, graphed_step=None):
+                 local_rank=0, save_every=10, log_every=100, graphed_step=None, gt_targets="loader"):
         self.model, self.optimizer = model, optimizer
+        self.gt_targets = gt_targets
+        # --gt-targets device: (items replaced, items of batches without a valid item), on the device, read with the loss sums
+        self.replaced = torch.zeros(2, dtype=torch.int64, device=device) if gt_targets == "device" else None
         self.graphed_step = graphed_step                     # train_graph.GraphedTrainStep: the iteration as one hipGraph launch
         self.lr_scheduler, self.bnm_scheduler = lr_scheduler, bnm_scheduler
         self.checkpoint_dir, self.obj_name = checkpoint_dir, obj_name
@@ -197,7 +272,7 @@ class Trainer:
                     if self.graphed_step is not None:
                         out = self.graphed_step.step(batch)      # forward, backward and optimizer.step() in one launch
                     else:
-                        out, _ = model_fn_dec(self.model, batch, self.device)
+                        out, _ = model_fn_dec(self.model, batch, self.device, self.gt_targets, self.replaced)
                     loss = out["loss"]
                     vals = torch.stack([loss.detach().float(), out["seg_loss"].detach().float(),
                                         torch.as_tensor(out["match_loss"], device=loss.device).detach().float()])
@@ -205,7 +280,12 @@ class Trainer:
                     dev_hist.append(vals)
                     if (it + 1) % self.log_every == 0:
                         self._flush_history(dev_hist)            # the one host read of this log window; frees the per-iteration scalars
-                        if self.local_rank == 0:
+                        if self.local_rank == 0 and self.replaced is not None:
+                            rd = self._replaced_counter()
+                            vals = torch.cat([sums / self.log_every, rd.to(sums.dtype)]).tolist()     # one read: sums and counter
+                            print("avg_loss:{:.4f} seg: {:.4f} match: {:.4f}  invalid items replaced: {:.0f} unreplaced: {:.0f}  "
+                                  "time cost:{:.1f} s".format(*vals, time.time() - t0))
+                        elif self.local_rank == 0:
                             print("avg_loss:{:.4f} seg: {:.4f} match: {:.4f}  time cost:{:.1f} s".format(
                                 *(sums / self.log_every).tolist(), time.time() - t0))
                         sums = None
@@ -227,6 +307,12 @@ class Trainer:
         finally:
             self._flush_history(dev_hist)
 
+    def _replaced_counter(self):
+        """The device counter of invalid items (eager loop's, or the graphed step's own)."""
+        if self.graphed_step is not None and self.graphed_step.replaced is not None:
+            return self.graphed_step.replaced
+        return self.replaced
+
     HISTORY_CAP = 100000          # `history` keeps the most recent iterations' (loss, seg, match) triples
 
     def _flush_history(self, dev_hist):
@@ -241,7 +327,12 @@ def make_dataset(args, split, cls_ids=None):
     if args.dataset_factory:
         mod, fn = args.dataset_factory.split(":")
         return getattr(importlib.import_module(mod), fn)(args, split)
-    return SyntheticCrops(args.synthetic_items, args.n_points, args.n_mesh, seed=0 if split == "train" else 1, cls_ids=cls_ids)
+    model_xyz = None
+    if split == "train" and getattr(args, "gt_targets", "loader") == "device":
+        ds = dataset_config(args.dataset_name)
+        model_xyz = _model_points(args, ds, args.cls_id)[:, :3] / 1000.0           # the model_emb.xyz of build_model (metres)
+    return SyntheticCrops(args.synthetic_items, args.n_points, args.n_mesh, seed=0 if split == "train" else 1, cls_ids=cls_ids,
+                          model_xyz=model_xyz)
 
 
 def _model_points(args, ds, cls_id):
@@ -326,7 +417,8 @@ def train(args):
         if world > 1:
             raise SystemExit("--graph-train captures a single-process iteration; run multi-rank training without it")
         from .train_graph import GraphedTrainStep
-        graphed = GraphedTrainStep(model, optimizer, device)      # before the schedulers: they then drive the device-side lr
+        graphed = GraphedTrainStep(model, optimizer, device,      # before the schedulers: they then drive the device-side lr
+                                   gt_targets=getattr(args, "gt_targets", "loader"))
     steps = max(1, args.epochs * len(train_ds) // batch_size // 6 // max(world, 1))
     lr_scheduler = torch.optim.lr_scheduler.CyclicLR(optimizer, base_lr=1e-6, max_lr=1e-3, cycle_momentum=False,
                                                      step_size_up=steps, step_size_down=steps, mode="triangular")
@@ -334,7 +426,7 @@ def train(args):
                                                    bnm_clip), last_epoch=it)
     trainer = Trainer(model, optimizer, log_dir, obj_name, lr_scheduler, bnm, device,
                       0 if getattr(args, "_single_process", False) else local_rank,     # an objects-across-gpus rank logs / saves its own objects
-                      args.save_every, args.log_every, graphed_step=graphed)
+                      args.save_every, args.log_every, graphed_step=graphed, gt_targets=getattr(args, "gt_targets", "loader"))
     trainer.train(start_epoch, args.epochs, loader, sampler, max_iters=args.max_iters)
     return trainer
 

@@ -345,6 +345,41 @@ int gdm_icp_update_hip(const float* scene_xyz, long scene_bstride, int pt_stride
                        const int32_t* nn, const float* d2, const uint8_t* mask, int B, int N, int M, float reject_dist,
                        double tolerance, int min_points, float* RT, uint8_t* active, int32_t* iters, double* err, void* stream);
 
+/* Ground-truth correspondence targets: the reference loader's get_pose_gt_info (datasets/lm/linemod_pbr.py:602-655) for a batch.
+ * workspace: device memory, 16-byte aligned, of at least gdm_targets_workspace_bytes(B, N, M) bytes (any N >= 1 for
+ * gdm_hpr_visible_hip alone); 0 for a bad shape.  M >= GDM_TARGETS_MIN_M, B <= 65535.
+ * Model addressing: vertex (b, j) at model_xyz[b*model_bstride + 3*j] (f32 xyz, metres); model_bstride = 0 shares one cloud.
+ *
+ * gdm_hpr_visible_hip -- hidden-point removal (utils/compute_visibility.py:26-47 sphericalFlip / convexHull, :128-134 VisiblePoints):
+ *   camera centre c f32[3]: cam_center[b] when cam_center != NULL, else fp32(-R^T t) evaluated in fp64 as
+ *     c_k = -((R_0k t_0 + R_1k t_1) + R_2k t_2)
+ *     (a deviation: the reference inverts the fp32 4x4 [R t; 0 1] with LAPACK, :617-623, whose rounding can differ by an ulp);
+ *   p = v - c (fp32), n = sqrt((p_x^2 + p_y^2) + p_z^2) (fp32), Rad = fp64(max_j n_j) * 10^pi (10^pi = 1385.4557313670107),
+ *   flipped f64[B,M,3] = (2 ((Rad - n) p)) / n + p in fp64 -- bit-equal to sphericalFlip for the same centre.
+ *   visible u8[B,M] = 1 for the hull vertices of {f} U {origin}, then the reference's vertices[:-1]: when the origin is not a vertex
+ *   of that hull the highest-index visible vertex is dropped as well.  Vertex test: f_i is a vertex iff no point of the set lies
+ *   in conv(the others), decided per (crop, vertex) as a 2-D LP feasibility problem in fp64 (directions d = f_i/|f_i| + a e1 + b e2,
+ *   |a|, |b| <= 1e6) with Seidel's incremental algorithm in a fixed hashed order; exact for points in general position (no four
+ *   coplanar hull points through f_i), which is where Qhull's answer is defined.  Among exactly coincident flipped points only the
+ *   lowest index can be visible.  The camera centre must not coincide with a vertex (n = 0).
+ *
+ * gdm_pose_targets_hip -- the targets from that visibility (:632-655):
+ *   the visible vertices are posed in fp32 as ((r_0 x + r_1 y) + r_2 z) + t; for every point with labels != 0 (cld addressing as
+ *   gdm_kabsch_stats_hip) the nearest posed visible vertex by fp64 ((dx^2 + dy^2) + dz^2) from the fp32 coordinates, ties to the
+ *   lowest model index (sklearn NearestNeighbors, utils/icp.py:50-64); sqrt(d^2) > dist_thresh -> match M and label 0.
+ *   labels_out u8[B,N] (may alias labels), match_idx i32[B,N] (M where unmatched or unlabelled), visible_flag u8[B,M], valid u8[B]:
+ *     no labelled point             -> labels unchanged, match_idx all M, visible_flag all 0, valid 0 (:626-630);
+ *     every labelled point too far  -> labels unchanged, match_idx all M, visible_flag = visible, valid 0 (:644-646);
+ *     otherwise                     -> as above, valid 1. */
+#define GDM_TARGETS_MIN_M 4
+size_t gdm_targets_workspace_bytes(int B, int N, int M);
+int gdm_hpr_visible_hip(const float* model_xyz, long model_bstride, const float* RT, const float* cam_center, int B, int M,
+                        void* workspace, size_t workspace_bytes, double* flipped, uint8_t* visible, void* stream);
+int gdm_pose_targets_hip(const float* cld, long cld_bstride, int pt_stride, int ch_stride, const uint8_t* labels, const float* RT,
+                         const float* model_xyz, long model_bstride, const uint8_t* visible, int B, int N, int M, double dist_thresh,
+                         void* workspace, size_t workspace_bytes, uint8_t* labels_out, int32_t* match_idx, uint8_t* visible_flag,
+                         uint8_t* valid, void* stream);
+
 /* Eval-mode BatchNorm + activation + max over the K neighbours (DGCNN edge convolutions, dgcnn.py:104-117) in one pass:
  * out[plane,i] = max_k act(scale[c]*x[plane,i,k] + shift[c]), c = plane % C; x f32[planes,n,K], K % 4 == 0, planes <= 65535. */
 int gdm_affine_act_maxk_hip(const float* x, const float* scale, const float* shift, long planes, int C, long n, int K, int act,
