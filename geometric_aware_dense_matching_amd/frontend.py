@@ -1,9 +1,20 @@
 """GPU-side front end: from a device-resident RGB-D frame and a detection box to the model's input dict, so that the
 DataLoader only ships the frame.  Mirrors the geometric part of the reference loader
-(/root/reference/datasets/lm/linemod_pbr.py): depth -> xyz (`dpt_2_pcld` :398-411), the S x S crop (:468-473; integer crops
-only -- the reference's warpAffine resampling with a zoom is host-side preprocessing and stays out of scope), valid-pixel
-sampling of N points with wrap-around padding (:476-496), `cld_rgb_nrm` / `choose` assembly (:498-513) and the neighbour
-pyramid (:515-569)."""
+(/root/reference/datasets/lm/linemod_pbr.py): depth -> xyz (`dpt_2_pcld` :398-411), the surface normals from the depth image
+(:460-463), the padded / jittered detection box (`aug_bbox_DZI` :99-120), the S x S crop resampled around it (:468-473), valid-pixel
+sampling of N points with wrap-around padding (:476-496), `cld_rgb_nrm` / `choose` assembly (:498-513) and the neighbour pyramid
+(:515-569).
+
+  make_inputs             integer S x S crops of a frame whose rgb is normalised and whose normals are given
+  depth_normals           depth -> normal map (csrc/gdm_frontend.hip; the definition is in include/gdm.h)
+  dzi_boxes               box -> centre and scale (torch, on the boxes' device)
+  crop_from_boxes         the resampling crop: rgb, normals, dpt_xyz, depth, mask from one launch
+  make_inputs_from_boxes  raw uint8 rgb + depth + K + box (+ mask) -> the input dict, no host step and no host synchronisation
+
+`depth_normals_numpy` and `crop_from_boxes_numpy` restate the two kernels' definitions on the CPU (as targets.spherical_flip does
+for the flip); the device results equal them value for value.  Parity with normalSpeed and with a given cv2 build is unpinned
+(DESIGN.md 6d)."""
+import numpy as np
 import torch
 
 from . import _lib, ops, pyramid
@@ -57,6 +68,232 @@ def make_inputs(rgb_norm, depth, normals, K, origin, S, n_points, generator=None
     if mask is not None:
         msk = mask[bidx, ys[:, :, None], xs[:, None, :]].reshape(B, S * S)                  # [B,S*S], the crop of the mask
         lab = torch.gather(msk, 1, ch)
+        inputs["origin_labels"] = torch.where(lab == 255, torch.ones_like(lab), lab)
+    inputs.update(pyramid.build_pyramid(cld.contiguous(), xyz))
+    return inputs
+
+
+# --------------------------------------------------------------------------------------
+# detection boxes: normals from depth, the resampling crop, the whole item
+# --------------------------------------------------------------------------------------
+COLOR_MEAN = (0.485, 0.456, 0.406)                  # normalize_color (/root/reference/utils/ply.py:502-509), as csrc/gdm_frontend.hip
+COLOR_STD_CROP = (0.229, 0.224, 0.224)
+NORMALS_MAX_K = 64                                  # include/gdm.h GDM_NORMALS_MAX_K
+
+
+def _depth_mm(depth):
+    """(uint16) trunc(fp32(depth) * 1000.0f) as int64; negative and NaN -> 0, 65.535 m and beyond -> 65535."""
+    v = np.asarray(depth, dtype=np.float32) * np.float32(1000.0)
+    with np.errstate(invalid="ignore"):
+        return np.where(v >= 65535.0, 65535.0, np.where(v >= 0.0, np.trunc(v), 0.0)).astype(np.int64)
+
+
+def depth_normals_numpy(depth, K, k_size=5, distance_threshold=2000, difference_threshold=20):
+    """The definition of `depth_normals` (include/gdm.h gdm_depth_normals_hip) restated on the CPU: depth f32[B,H,W] (m),
+    K f32[B,3,3] -> normals f32[B,3,H,W]."""
+    depth = np.asarray(depth, dtype=np.float32)
+    K = np.asarray(K, dtype=np.float32)
+    B, H, W = depth.shape
+    r = int(k_size)
+    d = _depth_mm(depth)
+    out = np.zeros((B, 3, H, W), np.float32)
+    if H <= 2 * r or W <= 2 * r:
+        return out
+    c = d[:, r:H - r, r:W - r]
+    A0, A1, A3, b0, b1 = (np.zeros(c.shape, np.int64) for _ in range(5))
+    for j in (-r, 0, r):
+        for i in (-r, 0, r):
+            if i == 0 and j == 0:
+                continue
+            delta = d[:, r + j:H - r + j, r + i:W - r + i] - c
+            f = (np.abs(delta) < int(difference_threshold)).astype(np.int64)
+            A0 += f * (i * i)
+            A1 += f * (i * j)
+            A3 += f * (j * j)
+            b0 += f * i * delta
+            b1 += f * j * delta
+    det = A0 * A3 - A1 * A1
+    ddx = A3 * b0 - A1 * b1
+    ddy = -A1 * b0 + A0 * b1
+    nx = K[:, 0, 0][:, None, None] * ddx.astype(np.float32)
+    ny = K[:, 1, 1][:, None, None] * ddy.astype(np.float32)
+    nz = (-(det * c)).astype(np.float32)
+    s = np.sqrt((nx * nx + ny * ny) + nz * nz)
+    ok = (s > 0) & (c < int(distance_threshold))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        n = np.stack([nx / s, ny / s, nz / s], axis=1)
+    out[:, :, r:H - r, r:W - r] = np.where(ok[:, None], n, np.float32(0.0))
+    return out
+
+
+def _fix10(v):
+    """round-half-even(v * 1024) as int64 (v float64); NaN and anything beyond +-1e15 land on +-1e15."""
+    with np.errstate(invalid="ignore"):
+        w = np.asarray(v, dtype=np.float64) * 1024.0
+        w = np.where(w > -1e15, w, -1e15)                          # NaN -> -1e15, as fmax(NaN, -1e15) on the device
+        return np.rint(np.minimum(w, 1e15)).astype(np.int64)
+
+
+def crop_from_boxes_numpy(rgb_u8, depth, normals, K, center, scale, S, mask=None):
+    """The definition of `crop_from_boxes` (include/gdm.h gdm_warp_crop_hip) restated on the CPU, numpy arrays in and out:
+    -> dict(rgb f32[B,3,S,S], normals f32[B,3,S,S], dpt_xyz f32[B,S,S,3], depth f32[B,S,S], mask u8[B,S,S] with a mask)."""
+    rgb_u8 = np.asarray(rgb_u8, dtype=np.uint8)
+    depth = np.asarray(depth, dtype=np.float32)
+    normals = np.asarray(normals, dtype=np.float32)
+    K = np.asarray(K, dtype=np.float32)
+    center = np.asarray(center, dtype=np.float32).astype(np.float64)
+    scale = np.asarray(scale, dtype=np.float32).astype(np.float64)
+    B, H, W = depth.shape
+    f32 = np.float32
+    out = dict(rgb=np.zeros((B, 3, S, S), f32), normals=np.zeros((B, 3, S, S), f32), dpt_xyz=np.zeros((B, S, S, 3), f32),
+               depth=np.zeros((B, S, S), f32))
+    if mask is not None:
+        mask = np.asarray(mask, dtype=np.uint8)
+        out["mask"] = np.zeros((B, S, S), np.uint8)
+    g = np.arange(S, dtype=np.float64)
+    mean, std = np.array(COLOR_MEAN, f32), np.array(COLOR_STD_CROP, f32)
+    for b in range(B):
+        a = scale[b] / float(S)
+        half = (a * float(S)) / 2.0
+        bx, by = center[b, 0] - half, center[b, 1] - half
+        rx = (_fix10(a * g) + _fix10(bx))[None, :]                 # [1,S]
+        ry = _fix10(a * g + by)[:, None]                           # [S,1]
+        X, Y = np.broadcast_arrays((rx + 512) >> 10, (ry + 512) >> 10)
+        X5, Y5 = (rx + 16) >> 5, (ry + 16) >> 5
+        sx, al, sy, be = X5 >> 5, X5 & 31, Y5 >> 5, Y5 & 31
+
+        def taps(img):                                             # img [H,W,...] -> the four taps, 0 outside the frame
+            res = []
+            for dy, dx in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                yy, xx = np.broadcast_arrays(sy + dy, sx + dx)
+                ok = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+                v = img[np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)]
+                res.append(np.where(ok.reshape(ok.shape + (1,) * (v.ndim - 2)), v, 0))
+            return res
+
+        wi = [32 * (32 - be) * (32 - al), 32 * (32 - be) * al, 32 * be * (32 - al), 32 * be * al]
+        t = taps(rgb_u8[b].astype(np.int64))
+        acc = sum(w[..., None] * v for w, v in zip(wi, t))
+        c = ((acc + 16384) >> 15).astype(f32) / f32(255.0)
+        c = c - mean
+        c = c / std
+        out["rgb"][b] = c.transpose(2, 0, 1)
+        fb, fa = be.astype(f32) / f32(32.0), al.astype(f32) / f32(32.0)
+        one = f32(1.0)
+        wf = [((one - fb) * (one - fa))[..., None], ((one - fb) * fa)[..., None], (fb * (one - fa))[..., None], (fb * fa)[..., None]]
+        t = [v.astype(f32) for v in taps(normals[b].transpose(1, 2, 0))]
+        n = ((t[0] * wf[0] + t[1] * wf[1]) + t[2] * wf[2]) + t[3] * wf[3]
+        out["normals"][b] = n.transpose(2, 0, 1)
+        ok = (Y >= 0) & (Y < H) & (X >= 0) & (X < W)
+        Yc, Xc = np.clip(Y, 0, H - 1), np.clip(X, 0, W - 1)
+        d = np.where(ok, depth[b][Yc, Xc], f32(0.0)).astype(f32)
+        out["depth"][b] = d
+        if mask is not None:
+            out["mask"][b] = np.where(ok, mask[b][Yc, Xc], 0)
+        d64 = d.astype(np.float64)
+        m = (d > f32(1e-8)).astype(np.float64)
+        k = K[b].astype(np.float64)
+        out["dpt_xyz"][b] = np.stack([(X.astype(np.float64) - k[0, 2]) * d64 / k[0, 0] * m,
+                                      (Y.astype(np.float64) - k[1, 2]) * d64 / k[1, 1] * m, d64 * m], axis=2).astype(f32)
+    return out
+
+
+def depth_normals(depth, K, k_size=5, distance_threshold=2000, difference_threshold=20):
+    """Surface normals from the depth image, the loader's normalSpeed.depth_normal(dpt_mm, fx, fy, 5, 2000, 20, False)
+    (linemod_pbr.py:460-463): depth f32[B,H,W] (m), K f32[B,3,3] -> normals f32[B,3,H,W], unit vectors towards the camera
+    (nz <= 0), zero on the k_size border, beyond distance_threshold (mm) and where no gradient can be fitted.  One launch."""
+    depth = ops._dev(depth, torch.float32, "depth")
+    K = ops._dev(K, torch.float32, "K")
+    if depth.dim() != 3 or tuple(K.shape) != (depth.shape[0], 3, 3):
+        raise ValueError("depth must be [B,H,W] and K [B,3,3], got %s and %s" % (tuple(depth.shape), tuple(K.shape)))
+    B, H, W = depth.shape
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=depth.device)
+    check(_lib.lib().gdm_depth_normals_hip(depth.data_ptr(), K.data_ptr(), B, H, W, int(k_size), int(distance_threshold),
+                                           int(difference_threshold), out.data_ptr(), ops._stream()), "gdm_depth_normals_hip")
+    return out
+
+
+def dzi_boxes(bbox_xyxy, im_hw, pad_ratio=1.5, scale_ratio=0.25, shift_ratio=0.25, train=False, generator=None):
+    """`aug_bbox_DZI` (linemod_pbr.py:99-120) for a batch, in torch on the boxes' device: bbox_xyxy f32[B,4] = (x1,y1,x2,y2) ->
+    center f32[B,2] = (cx,cy), scale f32[B], the side of the square source window.  The box is padded by pad_ratio; with `train`
+    its side is scaled by 1 + scale_ratio * U(-1,1) and its centre shifted by shift_ratio * U(-1,1) of the box's width / height,
+    the three draws per box from `generator`.  scale <= max(H, W)."""
+    if not isinstance(bbox_xyxy, torch.Tensor) or bbox_xyxy.dim() != 2 or bbox_xyxy.shape[1] != 4:
+        raise ValueError("bbox_xyxy must be a tensor [B,4]")
+    box = bbox_xyxy.to(torch.float32)
+    x1, y1, x2, y2 = box.unbind(1)
+    bw, bh = x2 - x1, y2 - y1
+    cx, cy = 0.5 * (x1 + x2), 0.5 * (y1 + y2)
+    if train:
+        u = 2.0 * torch.rand((box.shape[0], 3), device=box.device, generator=generator) - 1.0
+        cx = cx + bw * (shift_ratio * u[:, 1])
+        cy = cy + bh * (shift_ratio * u[:, 2])
+        scale = torch.maximum(bh, bw) * (1.0 + scale_ratio * u[:, 0]) * pad_ratio
+    else:
+        scale = torch.maximum(bh, bw) * pad_ratio
+    scale = scale.clamp(max=float(max(im_hw)))
+    return torch.stack([cx, cy], dim=1), scale
+
+
+def crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=None):
+    """The loader's six crop_resize_by_warp_affine calls (linemod_pbr.py:468-473) in one launch: rgb_u8 u8[B,H,W,3],
+    depth f32[B,H,W], normals f32[B,3,H,W], K f32[B,3,3], center f32[B,2], scale f32[B] (source pixels), mask u8[B,H,W] or None ->
+    dict(rgb f32[B,3,S,S] colour-normalised, normals f32[B,3,S,S], dpt_xyz f32[B,S,S,3], depth f32[B,S,S], mask u8[B,S,S] with a
+    mask).  Bilinear for rgb and normals, nearest for the rest, zeros outside the frame; with scale == S and
+    center = (x0 + S/2, y0 + S/2) it is the integer crop at (x0, y0)."""
+    rgb_u8 = ops._dev(rgb_u8, torch.uint8, "rgb_u8")
+    depth = ops._dev(depth, torch.float32, "depth")
+    normals = ops._dev(normals, torch.float32, "normals")
+    K = ops._dev(K, torch.float32, "K")
+    center = ops._dev(center, torch.float32, "center")
+    scale = ops._dev(scale, torch.float32, "scale")
+    if depth.dim() != 3:
+        raise ValueError("depth must be [B,H,W], got %s" % (tuple(depth.shape),))
+    B, H, W = depth.shape
+    for t, shape, name in ((rgb_u8, (B, H, W, 3), "rgb_u8"), (normals, (B, 3, H, W), "normals"), (K, (B, 3, 3), "K"),
+                           (center, (B, 2), "center"), (scale, (B,), "scale")):
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, list(shape), tuple(t.shape)))
+    dev = depth.device
+    out = dict(rgb=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
+               normals=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
+               dpt_xyz=torch.empty((B, S, S, 3), dtype=torch.float32, device=dev),
+               depth=torch.empty((B, S, S), dtype=torch.float32, device=dev))
+    mp = op = None
+    if mask is not None:
+        mask = ops._dev(mask, torch.uint8, "mask")
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError("mask must be [B=%d,H=%d,W=%d], got %s" % (B, H, W, tuple(mask.shape)))
+        out["mask"] = torch.empty((B, S, S), dtype=torch.uint8, device=dev)
+        mp, op = mask.data_ptr(), out["mask"].data_ptr()
+    check(_lib.lib().gdm_warp_crop_hip(rgb_u8.data_ptr(), depth.data_ptr(), normals.data_ptr(), K.data_ptr(), mp, center.data_ptr(),
+                                       scale.data_ptr(), B, H, W, int(S), out["rgb"].data_ptr(), out["normals"].data_ptr(),
+                                       out["dpt_xyz"].data_ptr(), out["depth"].data_ptr(), op, ops._stream()), "gdm_warp_crop_hip")
+    return out
+
+
+def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, train=False, generator=None, normals=None):
+    """The whole item from the raw frame: rgb_u8 u8[B,H,W,3], depth f32[B,H,W] (m), K f32[B,3,3], bbox_xyxy f32[B,4], mask
+    u8[B,H,W] or None -> the dict of `make_inputs` (rgb, cld_rgb_nrm, choose, dpt_xyz, origin_labels with a mask, the neighbour
+    pyramid) plus n_valid i32[B], the number of depth > 1e-6 pixels of each crop (the loader drops a training item below 200,
+    linemod_pbr.py:479), and the center f32[B,2] / scale f32[B] it cropped at.  depth_normals (unless `normals` f32[B,3,H,W] is
+    given) -> dzi_boxes -> crop_from_boxes -> sample_valid_pixels -> assembly -> pyramid.build_pyramid, all on
+    the device without a host synchronisation."""
+    B, H, W = depth.shape
+    if normals is None:
+        normals = depth_normals(depth, K)
+    center, scale = dzi_boxes(bbox_xyxy, (H, W), train=train, generator=generator)
+    crop = crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=mask)
+    xyz = crop["dpt_xyz"]
+    choose = sample_valid_pixels(xyz, n_points, generator)                           # [B,1,N]
+    ch = choose[:, 0].long()
+    cld = torch.gather(xyz.reshape(B, S * S, 3), 1, ch[:, :, None].expand(-1, -1, 3))
+    rgb_pt = torch.gather(crop["rgb"].reshape(B, 3, S * S), 2, ch[:, None, :].expand(-1, 3, -1))
+    nrm_pt = torch.gather(crop["normals"].reshape(B, 3, S * S), 2, ch[:, None, :].expand(-1, 3, -1))
+    inputs = dict(rgb=crop["rgb"], cld_rgb_nrm=torch.cat([cld.transpose(1, 2), rgb_pt, nrm_pt], dim=1).contiguous(), choose=choose,
+                  dpt_xyz=xyz, n_valid=(crop["depth"].reshape(B, S * S) > 1e-6).sum(dim=1).to(torch.int32), center=center, scale=scale)
+    if mask is not None:
+        lab = torch.gather(crop["mask"].reshape(B, S * S), 1, ch)
         inputs["origin_labels"] = torch.where(lab == 255, torch.ones_like(lab), lab)
     inputs.update(pyramid.build_pyramid(cld.contiguous(), xyz))
     return inputs

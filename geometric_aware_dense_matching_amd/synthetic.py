@@ -50,6 +50,17 @@ def make_frame(rs, hole_frac=0.05):
     return depth, rgb, nrm.astype(np.float32)
 
 
+def make_box_mask(rs, H=480, W=640, radius=(40.0, 110.0)):
+    """A detection for a frame: the object mask u8[H,W] (255 on a disc, as the loader's mask images) and its tight box
+    f32[4] = (x1, y1, x2, y2), the `bbox` of an annotation.  The disc's centre lies inside the frame, its radius in `radius`."""
+    rad = rs.uniform(*radius)
+    cx, cy = rs.uniform(0.25 * W, 0.75 * W), rs.uniform(0.25 * H, 0.75 * H)
+    v, u = np.mgrid[:H, :W]
+    mask = np.where((u - cx) ** 2 + (v - cy) ** 2 <= rad * rad, 255, 0).astype(np.uint8)
+    ys, xs = np.nonzero(mask)
+    return np.array([xs.min(), ys.min(), xs.max() + 1, ys.max() + 1], dtype=np.float32), mask
+
+
 def depth_to_xyz(depth, K=LM_K):
     """`dpt_2_pcld` arithmetic (linemod_pbr.py:398-411): integer pixel maps minus a float32 intrinsic promote to
     float64, so the reference forms x, y in double from the float32 depth and rounds to float32 once, at the end."""

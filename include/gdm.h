@@ -513,6 +513,39 @@ int gdm_conv1x1_packed_hip(const void* xpk, const void* wpk, const float* scale,
 int gdm_depth_to_xyz_hip(const float* depth, const float* K, const int32_t* origin, int B, int H, int W, int S,
                          float* out, void* stream);
 
+/* Front end, surface normals from the depth image (the loader's normalSpeed.depth_normal(dpt_mm, fx, fy, 5, 2000, 20, False),
+ * datasets/lm/linemod_pbr.py:460-463): depth (m) f32[B,H,W], K f32[B,3,3] -> normals f32[B,3,H,W], unit or zero, towards the camera
+ * (nz <= 0).  The LINEMOD least-squares depth gradient, defined here operation by operation:
+ *   d = (uint16) trunc(fp32(depth) * 1000.0f)   (negative and NaN -> 0; 65.535 m and beyond -> 65535)
+ *   r = k_size; pixels with x < r, x >= W-r, y < r or y >= H-r -> (0,0,0);  c = d[y,x]; !(c < distance_threshold) -> (0,0,0)
+ *   over the 8 offsets (i,j) in {-r,0,r}^2 \ (0,0), in integers:  delta = d[y+j,x+i] - c;  f = |delta| < difference_threshold;
+ *     A0 += f i i; A1 += f i j; A3 += f j j; b0 += f i delta; b1 += f j delta
+ *   det = A0 A3 - A1 A1; ddx = A3 b0 - A1 b1; ddy = -A1 b0 + A0 b1   (64-bit)
+ *   nx = fp32(fx) * fp32(ddx); ny = fp32(fy) * fp32(ddy); nz = fp32(-(det c));  fx = K[0][0], fy = K[1][1]
+ *   s = sqrtf((nx nx + ny ny) + nz nz);  s > 0 ? (nx/s, ny/s, nz/s) : (0,0,0)   (fp32, no contraction)
+ * 1 <= k_size <= GDM_NORMALS_MAX_K and both thresholds in [0, 65536], which keeps every integer above inside its type. */
+#define GDM_NORMALS_MAX_K 64
+int gdm_depth_normals_hip(const float* depth, const float* K, int B, int H, int W, int k_size, int distance_threshold,
+                          int difference_threshold, float* normals, void* stream);
+
+/* Front end, the resampling crop around a detection box (the loader's six crop_resize_by_warp_affine calls, linemod_pbr.py:468-473):
+ * rgb u8[B,H,W,3], depth f32[B,H,W], normals f32[B,3,H,W], K f32[B,3,3], mask u8[B,H,W] or NULL, center f32[B,2] = (cx,cy) and
+ * scale f32[B] in source pixels -> out_rgb f32[B,3,S,S] (bilinear on uint8, then normalize_color: / 255, - mean, / std with std
+ * .229/.224/.224), out_normals f32[B,3,S,S] (bilinear), out_xyz f32[B,S,S,3] (dpt_2_pcld of the nearest source pixel, the arithmetic
+ * of gdm_depth_to_xyz_hip), out_depth f32[B,S,S] and out_mask u8[B,S,S] (nearest; out_mask NULL exactly when mask is).
+ * OpenCV's fixed-point warpAffine with BORDER_CONSTANT 0 for a pure scale + shift:
+ *   a = fp64(scale)/S; bx = fp64(cx) - (a S)/2; by = fp64(cy) - (a S)/2;  R(v) = round-half-even(v * 1024) as an integer
+ *   nearest: X = (R(a x) + R(bx) + 512) >> 10;  Y = (R(a y + by) + 512) >> 10
+ *   linear:  X5 = (R(a x) + R(bx) + 16) >> 5;  Y5 = (R(a y + by) + 16) >> 5;  sx = X5 >> 5, al = X5 & 31;  sy = Y5 >> 5, be = Y5 & 31
+ *            taps (sy,sx) (sy,sx+1) (sy+1,sx) (sy+1,sx+1); a tap outside the frame contributes 0
+ *     uint8: w = 32 {(32-be)(32-al), (32-be) al, be (32-al), be al};  out = (sum w_k v_k + 16384) >> 15
+ *     float: w = {(1-be/32)(1-al/32), (1-be/32)(al/32), (be/32)(1-al/32), (be/32)(al/32)} in fp32;
+ *            out = ((v0 w0 + v1 w1) + v2 w2) + v3 w3   (fp32, no contraction)
+ * With scale == S and center = (x0 + S/2, y0 + S/2) this is the integer crop at (x0, y0). */
+int gdm_warp_crop_hip(const uint8_t* rgb, const float* depth, const float* normals, const float* K, const uint8_t* mask,
+                      const float* center, const float* scale, int B, int H, int W, int S, float* out_rgb, float* out_normals,
+                      float* out_xyz, float* out_depth, uint8_t* out_mask, void* stream);
+
 /* ---- training-mode BatchNorm (+ ReLU / LeakyReLU), forward and backward -------------------------------------------------------
  * Replaces the conv -> nn.BatchNorm{1,2}d -> activation chains of the embedding network in the training step
  * (models/pytorch_utils.py:70-124, models/RandLA/pytorch_utils.py:34-105, models/cnn/extractors.py:36-58; train_lm.py:171-225).
