@@ -120,6 +120,7 @@ SIGNATURES = {
     "gdm_gather_add_affine_act2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     "gdm_conv1x1_gather_add_act2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_long, _i, _f, _i, _vp, _vp]),
     "gdm_conv64_gather_add_act_mfma2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _i, _i, _vp, _vp, _i, _vp]),
+    "gdm_conv64_gather_add_final_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _vp, _vp, _vp, _vp]),
     "gdm_conv3x3_act_bytes": (_sz, [_i, _i, _i, _i]),
     "gdm_conv3x3_weight_bytes": (_sz, [_i, _i]),
     "gdm_conv3x3_pack_weight_hip": (_i, [_vp, _i, _i, _vp, _vp]),

@@ -285,8 +285,24 @@ class PSPUpsample(nn.Module):
             self.__dict__["_gdm_wt"] = cache
         return cache[1]
 
+    def reads_packed_only(self, shape):
+        """True when forward() on a GPU map of this shape takes the tap GEMM on the map's packed operand (`gemm_bf16x3_map`) and reads
+        nothing else of it: its producer may then hand over the ops.PackedAct alone.  Mirrors the branch conditions of forward()."""
+        conv = self.conv[1]
+        Bx, Cin, Hx, Wx = shape
+        if self.training or torch.is_grad_enabled() or act_code(self.conv[3]) is None or Cin != conv.in_channels:
+            return False
+        if not (Bx * conv.out_channels <= 65535 and conv.in_channels >= settings.UPCONV_MIN_CIN):
+            return False
+        if settings.USE_FUSED_UPCONV and Cin == 64 and conv.out_channels == 64 and Hx >= 2 and Wx >= 2 and Bx <= 65535:
+            return False
+        return settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, 9 * conv.out_channels, Hx * Wx) and Wx % 32 == 0
+
     def forward(self, x):
-        if fused_eval(x, self):
+        packed_in = isinstance(x, ops.PackedAct)
+        if packed_in and not self.reads_packed_only(x.shape):
+            raise RuntimeError("PSPUpsample: a packed-only map of shape %s does not fit the path this stage takes" % (x.shape,))
+        if packed_in or fused_eval(x, self):
             code = act_code(self.conv[3])
             conv = self.conv[1]
             if code is not None and x.shape[0] * conv.out_channels <= 65535 and conv.in_channels >= settings.UPCONV_MIN_CIN:

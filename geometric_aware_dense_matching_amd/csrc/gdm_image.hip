@@ -836,7 +836,8 @@ __global__ __launch_bounds__(256) void psp_combine8_kernel(const float* __restri
 // y[b,c,j] = act(scale[c] * (x[b,c,j] + t[b,c,idx[b,j]]) + shift[c]) : the point->pixel fusion layers
 // conv1x1(cat(rgb, nearest_interp(p))) + BN + ReLU (ffb6d.py:216-222,252-258) with the point half of the
 // convolution done at the (few) points and gathered afterwards (a 1x1 convolution commutes with a gather).
-template <int ACT>
+// F32 = false: only the packed operand is written (the next reader is a GEMM on it): no fp32 store, x stays as it was.
+template <int ACT, bool F32 = true>
 __global__ __launch_bounds__(256) void gather_add_affine_act_kernel(const float* __restrict__ x, const float* __restrict__ t,
                                                                     const int32_t* __restrict__ idx, const float* __restrict__ scale,
                                                                     const float* __restrict__ shift, int C, int n, int m, float slope,
@@ -865,7 +866,7 @@ __global__ __launch_bounds__(256) void gather_add_affine_act_kernel(const float*
         float o = scale[c] * (x[row * m + j] + t[row * n + src]) + shift[c];
         if (ACT == 1) o = fmaxf(o, 0.f);
         if (ACT == 2) o = o > 0.f ? o : o * slope;
-        y[row * m + j] = o;
+        if (F32) y[row * m + j] = o;
         v[i] = o;
     }
     if (ypk) {
@@ -1274,15 +1275,16 @@ extern "C" int gdm_gather_add_affine_act2_hip(const float* x, const float* t, co
                                               int B, int C, int n, int m, int act, float slope, float* y, void* y_packed, int W, void* stream)
 {
     unsigned char* ypk = (unsigned char*)y_packed;
-    GDM_CHECK_ARG(x && t && idx && scale && shift && y, "gdm_gather_add_affine_act2_hip: NULL pointer");
+    GDM_CHECK_ARG(x && t && idx && scale && shift && (y || ypk), "gdm_gather_add_affine_act2_hip: NULL pointer");
     GDM_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && n >= 1 && m >= 1 && act >= 0 && act <= 2, "gdm_gather_add_affine_act2_hip: bad shape");
     GDM_CHECK_ARG(!ypk || (W >= 1 && m % W == 0 && C % 8 == 0 && (C == 64 || C % 128 == 0) && ((uintptr_t)ypk & 15) == 0),
                   "gdm_gather_add_affine_act2_hip: packed output needs m %% W == 0, C = 64 or a multiple of 128, a 16-byte aligned buffer");
     dim3 grid(gdm_cdiv(m, 256), gdm_cdiv(C, 8), B);
     hipStream_t s = (hipStream_t)stream;
-    if (act == 0) hipLaunchKernelGGL(gather_add_affine_act_kernel<0>, grid, dim3(256), 0, s, x, t, idx, scale, shift, C, n, m, slope, y, ypk, W);
-    else if (act == 1) hipLaunchKernelGGL(gather_add_affine_act_kernel<1>, grid, dim3(256), 0, s, x, t, idx, scale, shift, C, n, m, slope, y, ypk, W);
-    else hipLaunchKernelGGL(gather_add_affine_act_kernel<2>, grid, dim3(256), 0, s, x, t, idx, scale, shift, C, n, m, slope, y, ypk, W);
+#define GAA(A, F) hipLaunchKernelGGL((gather_add_affine_act_kernel<A, F>), grid, dim3(256), 0, s, x, t, idx, scale, shift, C, n, m, slope, y, ypk, W)
+    if (y) { if (act == 0) GAA(0, true); else if (act == 1) GAA(1, true); else GAA(2, true); }
+    else { if (act == 0) GAA(0, false); else if (act == 1) GAA(1, false); else GAA(2, false); }
+#undef GAA
     return gdm_launch_status("gather_add_affine_act_kernel");
 }
 

@@ -547,6 +547,149 @@ __global__ __launch_bounds__(256, 4) void conv64_gather_add_act_mfma_kernel(cons
     }
 }
 
+// The last 64-channel fusion of the image branch and `final` behind it (ffb6d.py:252-258 at 128 x 128, then pspnet.py:108-112) in one
+// launch: out[b,:,j] = log_softmax_c(Wf . f[b,:,j] + bf), f = the value conv64_gather_add_act_mfma_kernel<ACT, false, true> writes.
+// Only `final` reads that fused map, and both are per-pixel functions of the 64 channels of one pixel, so the map (a 67 MB write
+// and a 67 MB read at batch 16) and one launch go.  Same expressions in the same order as the two kernels, so the same bits:
+// the fusion half is the code above up to its stores; the fused values then cross from the accumulator layout (lane = pixel,
+// registers = 4 channels) through LDS to `final`'s layout, wave = 16 output channels, lane = pixel (W^T rows stay wave-uniform scalar
+// loads, one per FMA as in conv1x1_logsoftmax_kernel); y = bias then fmaf over ci ascending; the maximum crosses the waves through LDS
+// (order-free); the sum of exponentials runs co = 0 .. 63 as ONE chain handed from wave to wave.
+constexpr int CF_XS = 68;                // row stride (floats) of the fused tile in LDS: channel rows 4 apart land 16 banks apart
+template <int ACT>
+__global__ __launch_bounds__(256, 4) void conv64_gather_add_final_kernel(const float* __restrict__ x, const unsigned char* __restrict__ wpk,
+                                                                       const float* __restrict__ t, const int32_t* __restrict__ idx,
+                                                                       const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                       int n, int m, float slope, const float* __restrict__ wft,
+                                                                       const float* __restrict__ fbias, float* __restrict__ out)
+{
+    // the operand rows (16 KiB) during the products, the fused tile f32[64 channels][CF_XS] afterwards
+    __shared__ __attribute__((aligned(16))) unsigned char smem[UF_C * CF_XS * 4];
+    __shared__ float redm[4][CG_P];
+    __shared__ float reds[CG_P];
+    static_assert(UF_C * CF_XS * 4 >= CG_P * UF_ROWB, "the fused tile reuses the operand rows");
+    unsigned char* rows = smem;
+    float* xs = reinterpret_cast<float*>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l16 = lane & 15, kg = lane >> 4;
+    const int b = blockIdx.y, j0 = blockIdx.x * CG_P;
+    const float* xb = x + (long)b * UF_C * m;
+    u32x4 wh[2], wl[2];
+    {
+        const unsigned char* r = wpk + (long)(16 * wave + l16) * UF_ROWB;
+#pragma unroll
+        for (int S = 0; S < 2; ++S) {
+            wh[S] = *reinterpret_cast<const u32x4*>(r + (4 * S + kg) * 16);
+            wl[S] = *reinterpret_cast<const u32x4*>(r + (8 + 4 * S + kg) * 16);
+        }
+    }
+    {
+        float raw[2][8];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int item = i * 256 + tid;
+            const int p = item & (CG_P - 1), grp = item >> 6;
+            const int pp = min(j0 + p, m - 1);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) raw[i][c] = xb[(long)(grp * 8 + c) * m + pp];
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int item = i * 256 + tid;
+            const int p = item & (CG_P - 1), grp = item >> 6;
+            unsigned hi[4], lo[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) gdm_split2(raw[i][2 * c], raw[i][2 * c + 1], hi[c], lo[c]);
+            *reinterpret_cast<u32x4*>(rows + uf_off(p, grp)) = u32x4{hi[0], hi[1], hi[2], hi[3]};
+            *reinterpret_cast<u32x4*>(rows + uf_off(p, 8 + grp)) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        }
+    }
+    const int c0 = 16 * wave + 4 * kg;
+    float tv[4][4];
+#pragma unroll
+    for (int pb = 0; pb < 4; ++pb) {
+        const int j = min(j0 + 16 * pb + l16, m - 1);
+        int src = idx[(long)b * m + j];
+        src = min(max(src, 0), n - 1);
+        const float4 q = *reinterpret_cast<const float4*>(t + ((long)b * n + src) * UF_C + c0);
+        tv[pb][0] = q.x; tv[pb][1] = q.y; tv[pb][2] = q.z; tv[pb][3] = q.w;
+    }
+    float sc[4], sh[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        sc[r] = scale[c0 + r];
+        sh[r] = shift[c0 + r];
+    }
+    __syncthreads();
+    typedef __attribute__((ext_vector_type(4))) float f32x4w;
+    f32x4w acc[4];
+#pragma unroll
+    for (int pb = 0; pb < 4; ++pb) {
+        acc[pb] = f32x4w{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int S = 0; S < 2; ++S) {
+            const bf16x8 xh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rows + uf_off(16 * pb + l16, 4 * S + kg)));
+            const bf16x8 xl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rows + uf_off(16 * pb + l16, 8 + 4 * S + kg)));
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, wh[S]);
+            const bf16x8 al = __builtin_bit_cast(bf16x8, wl[S]);
+            acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl, acc[pb], 0, 0, 0);
+            acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, acc[pb], 0, 0, 0);
+            acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, acc[pb], 0, 0, 0);
+        }
+    }
+    __syncthreads();                                   // every wave has read its operand rows: the tile may take their place
+#pragma unroll
+    for (int pb = 0; pb < 4; ++pb) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float v = sc[r] * (acc[pb][r] + tv[pb][r]) + sh[r];
+            if (ACT == 1) v = fmaxf(v, 0.f);
+            if (ACT == 2) v = v > 0.f ? v : v * slope;
+            xs[(c0 + r) * CF_XS + 16 * pb + l16] = v;
+        }
+    }
+    __syncthreads();
+    // `final`: this wave's 16 output channels of pixel j0 + lane
+    const int cb = __builtin_amdgcn_readfirstlane(16 * wave);
+    float y[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) y[k] = fbias ? fbias[cb + k] : 0.f;
+    const float* wr = wft + cb;
+#pragma unroll 4
+    for (int ci = 0; ci < UF_C; ++ci) {
+        const float xv = xs[ci * CF_XS + lane];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) y[k] = fmaf(wr[ci * UF_C + k], xv, y[k]);
+    }
+    float mx = y[0];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) mx = fmaxf(mx, y[k]);
+    redm[wave][lane] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(redm[0][lane], redm[1][lane]), fmaxf(redm[2][lane], redm[3][lane]));
+    float e[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) e[k] = __expf(y[k] - mx);
+    // ssum = ((0 + e_0) + e_1) + .. + e_63: wave w continues the chain where wave w - 1 left it
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+            float ssum = w == 0 ? 0.f : reds[lane];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) ssum += e[k];
+            reds[lane] = ssum;
+        }
+        __syncthreads();
+    }
+    const float lse = mx + logf(reds[lane]);
+    const int j = j0 + lane;
+    if (j < m) {
+        float* ob = out + ((long)b * UF_C + cb) * m + j;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) ob[(long)k * m] = y[k] - lse;
+    }
+}
+
 // w f32[R, 64] -> R rows of 256 B: 64 bf16 hi | 64 bf16 lo
 __global__ __launch_bounds__(256) void pack_rows64_kernel(const float* __restrict__ w, int R, unsigned char* __restrict__ out)
 {
@@ -642,4 +785,18 @@ extern "C" int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* w
 #undef CGA
 #undef CGM
     return gdm_launch_status("conv64_gather_add_act_mfma_kernel");
+}
+
+extern "C" int gdm_conv64_gather_add_final_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
+                                               const float* shift, int B, int n, long m, int act, float slope, const float* wft,
+                                               const float* fbias, float* out, void* stream)
+{
+    GDM_CHECK_ARG(x && wpk && t && idx && scale && shift && wft && out, "gdm_conv64_gather_add_final_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && m <= 0x7fffffffL && act >= 0 && act <= 2, "gdm_conv64_gather_add_final_hip: bad shape");
+    dim3 grid(gdm_cdiv(m, CG_P), B);
+    hipStream_t s = (hipStream_t)stream;
+#define CGF(A) hipLaunchKernelGGL(conv64_gather_add_final_kernel<A>, grid, dim3(256), 0, s, x, (const unsigned char*)wpk, t, idx, scale, shift, n, (int)m, slope, wft, fbias, out)
+    if (act == 0) CGF(0); else if (act == 1) CGF(1); else CGF(2);
+#undef CGF
+    return gdm_launch_status("conv64_gather_add_final_kernel");
 }

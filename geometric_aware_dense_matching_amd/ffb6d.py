@@ -133,10 +133,14 @@ class FFB6DEmb(nn.Module):
             return ops.pointwise([pp], self._fuse_weight_t(fuse_layer, wb, "b"), point_major=True)       # [B, n', 64]
         return ops.pointwise([pp], self._fuse_weight_t(fuse_layer, wb, "b"))                             # [B, Cout, n']
 
-    def _p2r_fuse(self, pre_layer, fuse_layer, rgb_emb0, p_emb0, idx, pixel_major=False, point_term=None, want_packed=False):
+    def _p2r_fuse(self, pre_layer, fuse_layer, rgb_emb0, p_emb0, idx, pixel_major=False, point_term=None, want_packed=False,
+                  packed_only=False, final=None):
         """fuse(cat(rgb_emb0, nearest_interp(pre(p_emb0)))) (ffb6d.py:216-222,252-258).  Eval: the point half of the
         1x1 fuse convolution runs at the points (a 1x1 conv commutes with the gather), the pixel half is a GEMM with half
-        the K, and gather + add + BN + ReLU is one HIP launch; no concat, no full-resolution point features."""
+        the K, and gather + add + BN + ReLU is one HIP launch; no concat, no full-resolution point features.
+        packed_only (the caller's promise, _packed_only_consumer): the next image stage reads the packed operand and nothing else, so
+        the generic path returns the ops.PackedAct alone and the fp32 map is never stored.  final (_fused_final_stage): the FinalStage
+        that is the fused map's only reader; the 64-channel path then returns final(fused map) from one launch, the map never stored."""
         bs, c, hr, wr = rgb_emb0.shape
         if fused_eval(rgb_emb0, self):
             code = act_code(getattr(fuse_layer, "activation", None))
@@ -159,6 +163,10 @@ class FFB6DEmb(nn.Module):
                     if cache is None or cache[0] is not wa:
                         cache = (wa, ops.pack_rows64(wa))
                         fuse_layer.__dict__["_gdm_wa_pk"] = cache
+                    if final is not None:
+                        fconv = final[0]
+                        return ops.conv64_gather_add_final(rgb_emb0.reshape(bs, c, hr * wr), cache[1], t_pm, idx.reshape(bs, -1), scale, shift,
+                                                           code[0], code[1], fconv.weight, fconv.bias).view(bs, -1, hr, wr)
                     y = ops.conv64_gather_add_act_mfma(rgb_emb0.reshape(bs, c, hr * wr), cache[1], t_pm, idx.reshape(bs, -1), scale, shift,
                                                        code[0], code[1], pixel_major=pixel_major, t_point_major=True,
                                                        hw=(hr, wr) if (want_packed and settings.USE_PACKED_PRODUCERS and not pixel_major) else None)
@@ -190,6 +198,8 @@ class FFB6DEmb(nn.Module):
                 else:
                     x = ops.wx(wa, rgb_emb0.reshape(bs, c, hr * wr))                    # [B,Cout,HW]
                 scale, shift = folded_bn(fuse_layer.normlayer.bn)
+                if packed_only and ops.packed_out_supported(bs, x.shape[1], hr, wr):
+                    return ops.gather_add_affine_act(x, t, idx.reshape(bs, -1), scale, shift, code[0], code[1], hw=(hr, wr), f32_out=False)
                 y, ypk = ops.gather_add_affine_act(x, t, idx.reshape(bs, -1), scale, shift, code[0], code[1], hw=(hr, wr))
                 y = y.view(bs, -1, hr, wr)
                 if ypk is not None:
@@ -199,6 +209,38 @@ class FFB6DEmb(nn.Module):
             raise RuntimeError("pixel-major fusion output is the eval kernel's; _sparse_final_ok() guards the caller")
         p2r_emb = self.nearest_interpolation(pre_layer(p_emb0), idx).view(bs, -1, hr, wr)
         return fuse_layer(torch.cat((rgb_emb0, p2r_emb), dim=1))
+
+    def _packed_only_consumer(self, stage, shape):
+        """True when image stage `stage`, given a GPU map of this shape, reads its packed operand and nothing else: Sequential(PSPUpsample,
+        dropout) in eval (the dropout is the identity) whose up-sampling stage takes its tap GEMM on the packed operand."""
+        from .cnn import PSPUpsample
+        return (isinstance(stage, nn.Sequential) and len(stage) == 2 and isinstance(stage[0], PSPUpsample)
+                and isinstance(stage[1], (nn.Dropout, nn.Dropout2d)) and not stage[1].training and stage[0].reads_packed_only(shape))
+
+    @staticmethod
+    def _image_stage(stage, x):
+        """stage(x); a packed-only map (see _packed_only_consumer) goes straight to the up-sampling stage, past the identity dropout."""
+        return stage[0](x) if isinstance(x, ops.PackedAct) else stage(x)
+
+    def _fused_final_stage(self, i_up, rgb_emb0, pixel_major):
+        """The FinalStage that _p2r_fuse of up stage i_up may apply in the same launch, or None: the fusion takes the 64-channel MFMA
+        kernel (the conditions of _p2r_fuse) in NCHW form, and the next image stage is `final` alone, 64 -> 64, so the fused map has
+        no other reader (the r2p gather of that stage reads rgb_emb0, the following stage reads final's output)."""
+        from .cnn import FinalStage
+        if pixel_major or i_up + 1 >= len(self.rndla_up_stages) - 1 or not fused_eval(rgb_emb0, self):
+            return None
+        fuse = self.up_fuse_p2r_fuse_layers[i_up]
+        w = fuse.conv.weight
+        if not (act_code(getattr(fuse, "activation", None)) is not None and settings.USE_MFMA_GEMM and rgb_emb0.shape[1] == 64
+                and w.shape[0] == 64 and w.shape[1] == 128 and rgb_emb0.shape[0] <= 65535):
+            return None
+        nxt = self.cnn_up_stages[i_up + 1]
+        if not (isinstance(nxt, nn.Sequential) and len(nxt) == 1 and isinstance(nxt[0], FinalStage) and not nxt[0].training):
+            return None
+        fconv = nxt[0][0]
+        if not (isinstance(fconv, nn.Conv2d) and fconv.in_channels == 64 and fconv.out_channels == 64 and fconv.kernel_size == (1, 1)):
+            return None
+        return nxt[0]
 
     def forward(self, inputs, end_points=None, parts=False):
         """-> f32[B,128,N] (ffb6d.py:285: cat of the 64 image channels at the chosen pixels and the 64 point channels); parts=True
@@ -264,7 +306,8 @@ class FFB6DEmb(nn.Module):
                 ds_emb.append(f_encoder_i)
 
             rgb_emb = self._p2r_fuse(self.ds_fuse_p2r_pre_layers[i_ds], self.ds_fuse_p2r_fuse_layers[i_ds], rgb_emb0, p_emb0,
-                                     inputs["p2r_ds_nei_idx%d" % i_ds], want_packed=True)
+                                     inputs["p2r_ds_nei_idx%d" % i_ds], want_packed=True,
+                                     packed_only=i_ds == 3 and self._packed_only_consumer(self.cnn_up_stages[0], rgb_emb0.shape))
 
             r2p_emb = self.random_sample(rgb_emb0.reshape(bs, c, hr * wr), inputs["r2p_ds_nei_idx%d" % i_ds])
             r2p_emb = self.ds_fuse_r2p_pre_layers[i_ds](r2p_emb)
@@ -273,15 +316,20 @@ class FFB6DEmb(nn.Module):
 
         n_up = len(self.rndla_up_stages)
         sparse_final = self._sparse_final_ok(inputs["rgb"])
+        final_done = False
         for i_up in range(n_up - 1):
-            rgb_emb0 = self.cnn_up_stages[i_up](rgb_emb)
+            rgb_emb0 = rgb_emb if final_done else self._image_stage(self.cnn_up_stages[i_up], rgb_emb)   # `final` ran inside the last fusion
             bs, c, hr, wr = rgb_emb0.size()
+            pm = sparse_final and i_up == n_up - 2
+            final = self._fused_final_stage(i_up, rgb_emb0, pm)
+            final_done = final is not None
 
             # decoder layer over cat(skip, nearest_interpolation(p_emb)): the interpolation is the second segment's index
             p_emb0 = self.rndla_up_stages[i_up].forward_segs([ds_emb[-i_up - 2], (p_emb, inputs["cld_interp_idx%d" % (n_up - i_up - 1)])])
 
             rgb_emb = self._p2r_fuse(self.up_fuse_p2r_pre_layers[i_up], self.up_fuse_p2r_fuse_layers[i_up], rgb_emb0, p_emb0,
-                                     inputs["p2r_up_nei_idx%d" % i_up], pixel_major=sparse_final and i_up == n_up - 2)
+                                     inputs["p2r_up_nei_idx%d" % i_up], pixel_major=pm, final=final,
+                                     packed_only=i_up + 1 < n_up - 1 and self._packed_only_consumer(self.cnn_up_stages[i_up + 1], rgb_emb0.shape))
 
             r2p_emb = self.random_sample(rgb_emb0.reshape(bs, c, hr * wr), inputs["r2p_up_nei_idx%d" % i_up])
             r2p_emb = self.up_fuse_r2p_pre_layers[i_up](r2p_emb)
@@ -376,13 +424,18 @@ class FFB6DEmb(nn.Module):
             M.wait_event(ev_p0)
             to(M, p_emb0, pt)
             rgb_emb = self._p2r_fuse(self.ds_fuse_p2r_pre_layers[i_ds], self.ds_fuse_p2r_fuse_layers[i_ds], rgb_emb0, p_emb0,
-                                     inputs["p2r_ds_nei_idx%d" % i_ds], point_term=pt, want_packed=True)
+                                     inputs["p2r_ds_nei_idx%d" % i_ds], point_term=pt, want_packed=True,
+                                     packed_only=i_ds == 3 and self._packed_only_consumer(self.cnn_up_stages[0], rgb_emb0.shape))
         n_up = len(self.rndla_up_stages)
         sparse_final = self._sparse_final_ok(inputs["rgb"])
+        final_done = False
         for i_up in range(n_up - 1):
-            rgb_emb0 = self.cnn_up_stages[i_up](rgb_emb)
+            rgb_emb0 = rgb_emb if final_done else self._image_stage(self.cnn_up_stages[i_up], rgb_emb)   # `final` ran inside the last fusion
             ev_rgb0 = event(M)
             bs, c, hr, wr = rgb_emb0.size()
+            pm = sparse_final and i_up == n_up - 2
+            final = self._fused_final_stage(i_up, rgb_emb0, pm)
+            final_done = final is not None
             with torch.cuda.stream(S):
                 p_emb0 = self.rndla_up_stages[i_up].forward_segs([ds_emb[-i_up - 2], (p_emb, inputs["cld_interp_idx%d" % (n_up - i_up - 1)])])
                 pt = self._p2r_point_term(self.up_fuse_p2r_pre_layers[i_up], self.up_fuse_p2r_fuse_layers[i_up], c, p_emb0)
@@ -395,7 +448,8 @@ class FFB6DEmb(nn.Module):
             M.wait_event(ev_p0)
             to(M, p_emb0, pt)
             rgb_emb = self._p2r_fuse(self.up_fuse_p2r_pre_layers[i_up], self.up_fuse_p2r_fuse_layers[i_up], rgb_emb0, p_emb0,
-                                     inputs["p2r_up_nei_idx%d" % i_up], pixel_major=sparse_final and i_up == n_up - 2, point_term=pt)
+                                     inputs["p2r_up_nei_idx%d" % i_up], pixel_major=pm, point_term=pt, final=final,
+                                     packed_only=i_up + 1 < n_up - 1 and self._packed_only_consumer(self.cnn_up_stages[i_up + 1], rgb_emb0.shape))
         with torch.cuda.stream(S):
             p_emb = self.rndla_up_stages[n_up - 1].forward_segs([ds_emb[0], (p_emb, inputs["cld_interp_idx0"])]).squeeze(-1)
         if sparse_final:

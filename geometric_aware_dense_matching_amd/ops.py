@@ -1151,22 +1151,34 @@ def psp_combine(g, ys, bias, packed=False):
     return g
 
 
-def gather_add_affine_act(x, t, idx, scale, shift, act=ACT_NONE, slope=0.0, hw=None):
+def packed_out_supported(B, C, H, W):
+    """The shapes for which gather_add_affine_act writes the packed operand of the [B,C,H,W] map."""
+    return (C == 64 or C % 128 == 0) and W % 32 == 0 and (B * H * W) % 256 == 0
+
+
+def gather_add_affine_act(x, t, idx, scale, shift, act=ACT_NONE, slope=0.0, hw=None, f32_out=True):
     """y[b,c,j] = act(scale[c]*(x[b,c,j] + t[b,c,idx[b,j]]) + shift[c]); x f32[B,C,m], t f32[B,C,n], idx int[B,m(,1)].
     Inference only, in place on x.  With hw = (H, W) of the pixel map (m = H*W) the kernel also writes the packed split-bf16 operand
-    of the next convolution / GEMM over it; the caller hangs the returned PackedAct on the map it hands on (`_gdm_packed`)."""
+    of the next convolution / GEMM over it; the caller hangs the returned PackedAct on the map it hands on (`_gdm_packed`).
+    f32_out=False (needs hw and packed_out_supported): the PackedAct is the only output and the only return value -- no fp32 store,
+    x is left as it was -- for a map whose only reader is a GEMM on the packed operand."""
     x = _dev(x, torch.float32, "x")
     t = _dev(t, torch.float32, "t")
     idx = _idx32(idx, "idx")
     B, C, m = x.shape
     n = t.shape[2]
     opk = None
-    if hw is not None and hw[0] * hw[1] == m and (C == 64 or C % 128 == 0) and hw[1] % 32 == 0 and (B * m) % 256 == 0:
+    if hw is not None and hw[0] * hw[1] == m and packed_out_supported(B, C, hw[0], hw[1]):
         opk = PackedAct(_packed_buffer(B, C, hw[0], hw[1], x.device), (B, C, hw[0], hw[1]))
+    if not f32_out and opk is None:
+        raise ValueError("gather_add_affine_act: f32_out=False needs a map the packed operand is built for, got x %s hw %s" % (tuple(x.shape), hw))
     check(_lib.lib().gdm_gather_add_affine_act2_hip(x.data_ptr(), t.data_ptr(), idx.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                    B, C, n, m, act, float(slope), x.data_ptr(), opk.buf.data_ptr() if opk is not None else None,
+                                                    B, C, n, m, act, float(slope), x.data_ptr() if f32_out else None,
+                                                    opk.buf.data_ptr() if opk is not None else None,
                                                     hw[1] if opk is not None else 0, _stream()),
           "gdm_gather_add_affine_act2_hip")
+    if not f32_out:
+        return opk
     return (x, opk) if hw is not None else x
 
 
@@ -1348,22 +1360,47 @@ def affine_relu_maxpool(x, scale, shift):
     return y
 
 
+def _final_weight_t(weight):
+    """W^T of the 64 -> 64 `final` weight (the kernels read 64 contiguous scalars per ci), cached ON the weight tensor: it lives and
+    dies with it.  (A module-level dict keyed by id(weight) served a NEW tensor that got a dead one's id, address and version the old
+    one's transpose: wrong output, found by a test that builds several weights in a row.)"""
+    key = (weight._version, weight.data_ptr())
+    cache = getattr(weight, "_gdm_final_wt", None)
+    if cache is None or cache[0] != key:
+        C = weight.shape[0]
+        cache = (key, weight.detach().reshape(C, C).t().contiguous())
+        weight._gdm_final_wt = cache
+    return cache[1]
+
+
 def conv1x1_logsoftmax(x, weight, bias):
     """log_softmax over channels of a 64->64 1x1 convolution, one pass (the `final` stage, pspnet.py:108-112). Inference only."""
     x = _dev(x, torch.float32, "x")
     B, C, H, W = x.shape
-    # W^T (the kernel reads 64 contiguous scalars per ci), cached ON the weight tensor: it lives and dies with it.  (A module-level dict
-    # keyed by id(weight) served a NEW tensor that got a dead one's id, address and version the old one's transpose: wrong output, found
-    # by a test that builds several weights in a row.)
-    key = (weight._version, weight.data_ptr())
-    cache = getattr(weight, "_gdm_final_wt", None)
-    if cache is None or cache[0] != key:
-        cache = (key, weight.detach().reshape(C, C).t().contiguous())
-        weight._gdm_final_wt = cache
-    w = cache[1]
+    w = _final_weight_t(weight)
     out = torch.empty_like(x)
     check(_lib.lib().gdm_conv1x1_logsoftmax_hip(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None,
                                                 B, C, H * W, out.data_ptr(), _stream()), "gdm_conv1x1_logsoftmax_hip")
+    return out
+
+
+def conv64_gather_add_final(x, wpk, t, idx, scale, shift, act, slope, final_weight, final_bias):
+    """conv1x1_logsoftmax(conv64_gather_add_act_mfma(x, wpk, t, idx, scale, shift, act, slope, t_point_major=True), final_weight,
+    final_bias) in one launch, bit for bit, without the fused map between the two (nobody else reads it).  x f32[B,64,m],
+    t f32[B,n,64] point-major, final_weight [64,64(,1,1)] -> f32[B,64,m].  Inference only."""
+    x = _dev(x, torch.float32, "x")
+    t = _dev(t, torch.float32, "t")
+    idx = _idx32(idx, "idx")
+    B, C, m = x.shape
+    if C != 64 or t.dim() != 3 or t.shape[2] != 64 or wpk.numel() != 64 * 256 or final_weight.numel() != 64 * 64:
+        raise ValueError("conv64_gather_add_final: built for 64 -> 64 -> 64 channels, got x %s t %s final %s"
+                         % (tuple(x.shape), tuple(t.shape), tuple(final_weight.shape)))
+    wft = _final_weight_t(final_weight)
+    out = torch.empty_like(x)
+    check(_lib.lib().gdm_conv64_gather_add_final_hip(x.data_ptr(), wpk.data_ptr(), t.data_ptr(), idx.data_ptr(), scale.data_ptr(),
+                                                     shift.data_ptr(), B, t.shape[1], m, act, float(slope), wft.data_ptr(),
+                                                     final_bias.data_ptr() if final_bias is not None else None, out.data_ptr(),
+                                                     _stream()), "gdm_conv64_gather_add_final_hip")
     return out
 
 
@@ -1641,8 +1678,13 @@ def conv3x3_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, res=None,
 
 def gemm_bf16x3_map(x, wpk, cout):
     """W @ x over the channels of a map x f32[B,Cin,H,W] -> f32[B,cout,H,W] on split-bf16 MFMA.  If x carries the packed operand its
-    producer wrote (`_gdm_packed`, the trunk's residual blocks), the GEMM reads that and no pack launch is needed."""
+    producer wrote (`_gdm_packed`, the trunk's residual blocks), or is that PackedAct itself, the GEMM reads that and no pack launch
+    is needed."""
     B, Cin, H, W = x.shape
+    if isinstance(x, PackedAct):                     # a map that exists as the packed operand only
+        if W % 32 != 0:
+            raise ValueError("gemm_bf16x3_map: a packed-only map needs W %% 32 == 0, got %s" % (x.shape,))
+        return conv1x1_packed2d(x, wpk, cout)
     xp = getattr(x, "_gdm_packed", None)
     if isinstance(xp, PackedAct) and xp.shape == (B, Cin, H, W) and W % 32 == 0:
         return conv1x1_packed2d(xp, wpk, cout)

@@ -430,7 +430,8 @@ int gdm_psp_combine2_hip(const float* g, const float* y1, int s1, const float* y
  * x f32[B,C,m] (pixel half of the 1x1 conv), t f32[B,C,n] (point half, computed at the points), idx i32[B,m]. May run in place.
  * With y_packed != NULL the result is ALSO written as the packed split-bf16 operand of the next convolution / GEMM over the
  * [B, C, m/W, W] map (gdm_conv3x3_act_bytes(B, C, m/W, W) bytes, zero border in place; C = 64 or a multiple of 128): no pack launch
- * in front of that layer.  W is read only with y_packed. */
+ * in front of that layer.  W is read only with y_packed.  y may be NULL when y_packed is given: the packed operand is then the only
+ * output (no fp32 store, x is left untouched), for a map whose only reader is a GEMM on the packed operand. */
 int gdm_gather_add_affine_act2_hip(const float* x, const float* t, const int32_t* idx, const float* scale, const float* shift,
                                    int B, int C, int n, int m, int act, float slope, float* y, void* y_packed, int W, void* stream);
 /* The same tail with the pixel half of the 1x1 convolution inside, for the 64-channel levels (C == 64):
@@ -447,6 +448,13 @@ int gdm_conv1x1_gather_add_act2_hip(const float* x, const float* wt, const float
 int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
                                         const float* shift, int B, int n, long m, int act, float slope, int pixel_major,
                                         int t_point_major, float* y, void* ypk, int W, void* stream);
+/* That fusion (NCHW form, point-major t f32[B, n, 64]) and the `final` stage behind it in one launch, for a fused map only `final`
+ * reads: out f32[B, 64, m] = log_softmax_c(Wf . y + fbias) with y the map gdm_conv64_gather_add_act_mfma2_hip would write; the same
+ * bits as that call followed by gdm_conv1x1_logsoftmax_hip, without the map between them.  wft f32[64, 64] = the `final` weight
+ * transposed ([ci][co]), fbias f32[64] or NULL. */
+int gdm_conv64_gather_add_final_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
+                                    const float* shift, int B, int n, long m, int act, float slope, const float* wft,
+                                    const float* fbias, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * 3x3 / stride 1 / pad 1 convolution as an implicit GEMM on split-bf16 MFMA (hi*hi + hi*lo + lo*hi, fp32 accumulate),
