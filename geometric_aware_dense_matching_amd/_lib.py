@@ -141,6 +141,8 @@ SIGNATURES = {
     "gdm_depth_to_xyz_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "gdm_depth_normals_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "gdm_warp_crop_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_fill_depth_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gdm_fill_depth_hip": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _sz, _vp, _vp, _vp]),
     "gdm_bn_sums_len": (ctypes.c_long, [_i, _i, ctypes.c_long]),
     "gdm_bn_stats_hip": (_i, [_vp, _i, _i, ctypes.c_long, _vp, _vp]),
     "gdm_bn_fwd_apply_hip": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_long, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp]),

@@ -124,15 +124,17 @@ __global__ __launch_bounds__(256) void warp_crop_kernel(const uint8_t* __restric
     }
 
     // normals: ((v0 w0 + v1 w1) + v2 w2) + v3 w3 in fp32, a tap outside the frame is 0
-    const float* nrm_b = normals + (long)b * 3 * plane;
-    const float fb = (float)be / 32.0f, fa = (float)al / 32.0f;
-    const float wf[4] = {(1.0f - fb) * (1.0f - fa), (1.0f - fb) * fa, fb * (1.0f - fa), fb * fa};
+    if (o_nrm) {                                                           // uniform: the YCB-V item takes its normals from the crop
+        const float* nrm_b = normals + (long)b * 3 * plane;
+        const float fb = (float)be / 32.0f, fa = (float)al / 32.0f;
+        const float wf[4] = {(1.0f - fb) * (1.0f - fa), (1.0f - fb) * fa, fb * (1.0f - fa), fb * fa};
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float* s = nrm_b + ch * plane;
-        const float v0 = in[0] ? s[off[0]] : 0.f, v1 = in[1] ? s[off[1]] : 0.f;
-        const float v2 = in[2] ? s[off[2]] : 0.f, v3 = in[3] ? s[off[3]] : 0.f;
-        o_nrm[((long)b * 3 + ch) * oplane + t] = ((v0 * wf[0] + v1 * wf[1]) + v2 * wf[2]) + v3 * wf[3];
+        for (int ch = 0; ch < 3; ++ch) {
+            const float* s = nrm_b + ch * plane;
+            const float v0 = in[0] ? s[off[0]] : 0.f, v1 = in[1] ? s[off[1]] : 0.f;
+            const float v2 = in[2] ? s[off[2]] : 0.f, v3 = in[3] ? s[off[3]] : 0.f;
+            o_nrm[((long)b * 3 + ch) * oplane + t] = ((v0 * wf[0] + v1 * wf[1]) + v2 * wf[2]) + v3 * wf[3];
+        }
     }
 
     // nearest: depth, mask, and dpt_2_pcld of the source pixel (the arithmetic of depth_to_xyz_kernel)
@@ -172,8 +174,9 @@ extern "C" int gdm_warp_crop_hip(const uint8_t* rgb, const float* depth, const f
                                  const float* center, const float* scale, int B, int H, int W, int S, float* out_rgb,
                                  float* out_normals, float* out_xyz, float* out_depth, uint8_t* out_mask, void* stream)
 {
-    GDM_CHECK_ARG(rgb && depth && normals && K && center && scale && out_rgb && out_normals && out_xyz && out_depth,
-                  "gdm_warp_crop_hip: NULL pointer");
+    GDM_CHECK_ARG(rgb && depth && K && center && scale && out_rgb && out_xyz && out_depth, "gdm_warp_crop_hip: NULL pointer");
+    GDM_CHECK_ARG((normals == nullptr) == (out_normals == nullptr),
+                  "gdm_warp_crop_hip: normals and out_normals go together (both or neither)");
     GDM_CHECK_ARG((mask == nullptr) == (out_mask == nullptr), "gdm_warp_crop_hip: mask and out_mask go together (both or neither)");
     GDM_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "gdm_warp_crop_hip: bad shape B=%d H=%d W=%d",
                   B, H, W);

@@ -9,11 +9,15 @@ sampling of N points with wrap-around padding (:476-496), `cld_rgb_nrm` / `choos
   depth_normals           depth -> normal map (csrc/gdm_frontend.hip; the definition is in include/gdm.h)
   dzi_boxes               box -> centre and scale (torch, on the boxes' device)
   crop_from_boxes         the resampling crop: rgb, normals, dpt_xyz, depth, mask from one launch
-  make_inputs_from_boxes  raw uint8 rgb + depth + K + box (+ mask) -> the input dict, no host step and no host synchronisation
+  fill_depth              depth completion of the crop (csrc/gdm_depthfill.hip), the step the YCB-V item adds
+  make_inputs_from_boxes  raw uint8 rgb + depth + K + box (+ mask) -> the input dict, no host step and no host synchronisation;
+                          depth_fill=None is the LineMOD item, "multiscale" / "fast" the YCB-V item
+                          (/root/reference/datasets/ycbv/ycbv_pbr.py:458-509)
 
-`depth_normals_numpy` and `crop_from_boxes_numpy` restate the two kernels' definitions on the CPU (as targets.spherical_flip does
-for the flip); the device results equal them value for value.  Parity with normalSpeed and with a given cv2 build is unpinned
-(DESIGN.md 6d)."""
+`depth_normals_numpy`, `crop_from_boxes_numpy` and `fill_depth_numpy` restate the kernels' definitions on the CPU (as
+targets.spherical_flip does for the flip); the device results equal them value for value, up to the fp32 rounding of the bilateral
+filter's exponentials in the last stage of the fill.  Parity with normalSpeed and with a given cv2 build is unpinned (DESIGN.md 6d,
+6e)."""
 import numpy as np
 import torch
 
@@ -33,11 +37,17 @@ def depth_to_xyz(depth, K, origin, S):
     return out
 
 
-def sample_valid_pixels(xyz, n_points, generator=None):
-    """Choose n_points valid pixels (z > 1e-6) per crop uniformly without replacement, in random order; crops with fewer valid
-    pixels wrap around (np.pad(..., 'wrap'), linemod_pbr.py:492).  xyz f32[B,S,S,3] -> choose i32[B,1,N]."""
+def sample_valid_pixels(xyz, n_points, generator=None, valid=None):
+    """Choose n_points valid pixels (z > 1e-6, or where `valid` bool[B,S,S] is set when it is given) per crop uniformly without
+    replacement, in random order; crops with fewer valid pixels wrap around (np.pad(..., 'wrap'), linemod_pbr.py:492).
+    xyz f32[B,S,S,3] -> choose i32[B,1,N]."""
     B, S = xyz.shape[0], xyz.shape[1]
-    valid = xyz[..., 2].reshape(B, S * S) > 1e-6
+    if valid is None:
+        valid = xyz[..., 2].reshape(B, S * S) > 1e-6
+    else:
+        if valid.dtype != torch.bool or tuple(valid.shape) != (B, S, S):
+            raise ValueError("valid must be bool[B=%d,S=%d,S=%d], got %s %s" % (B, S, S, valid.dtype, tuple(valid.shape)))
+        valid = valid.reshape(B, S * S)
     key = torch.rand((B, S * S), device=xyz.device, generator=generator)
     key = torch.where(valid, key, key + 2.0)                       # invalid pixels sort last
     order = torch.argsort(key, dim=1)                              # random permutation of the valid pixels first
@@ -198,6 +208,166 @@ def crop_from_boxes_numpy(rgb_u8, depth, normals, K, center, scale, S, mask=None
     return out
 
 
+# the structuring elements of depth completion (include/gdm.h gdm_fill_depth_hip), as (dy, dx) tap lists
+def _full(n):
+    r = n // 2
+    return [(dy, dx) for dy in range(-r, r + 1) for dx in range(-r, r + 1)]
+
+
+def _cross(n):
+    r = n // 2
+    return [(dy, dx) for dy, dx in _full(n) if dy == 0 or dx == 0]
+
+
+_DIAMOND_5 = [(dy, dx) for dy, dx in _full(5) if abs(dy) + abs(dx) <= 2]
+FILL_MODES = {"multiscale": 0, "fast": 1}                      # include/gdm.h GDM_FILL_MULTISCALE / GDM_FILL_FAST
+FILL_STAGES = 7                                                # include/gdm.h GDM_FILL_STAGES
+_FILL_STAGE_NAMES = ("s1_inverted_depths", "s2_dilated_depths", "s3_closed_depths", "s4_blurred_depths", "s5_combined_depths",
+                     "s7_before_bilateral", "s7_blurred_depths")
+
+
+def _morph(a, taps, op):
+    """max (op = np.maximum) or min over the taps; a tap outside the image is ignored.  a f32[B,H,W]."""
+    B, H, W = a.shape
+    r = max(max(abs(dy), abs(dx)) for dy, dx in taps)
+    pad = np.pad(a, ((0, 0), (r, r), (r, r)), constant_values=-np.inf if op is np.maximum else np.inf)
+    out = a.copy()
+    for dy, dx in taps:
+        out = op(out, pad[:, r + dy:r + dy + H, r + dx:r + dx + W])
+    return out
+
+
+def _median5(a):
+    """The 13th smallest of the 5 x 5 window, replicated border."""
+    B, H, W = a.shape
+    pad = np.pad(a, ((0, 0), (2, 2), (2, 2)), mode="edge")
+    win = np.stack([pad[:, 2 + dy:2 + dy + H, 2 + dx:2 + dx + W] for dy, dx in _full(5)], axis=0)
+    return np.sort(win, axis=0)[12]
+
+
+def _reflect101(n):
+    """Source index of positions -2 .. n+1: reflected (-1 -> 1, n -> n-2), then clamped to the image."""
+    p = np.abs(np.arange(-2, n + 2))
+    p = np.where(p >= n, 2 * n - 2 - p, p)
+    return np.clip(p, 0, n - 1)
+
+
+def _bilateral(a, sigma_color, sigma_space):
+    """The bilateral filter of the definition: 13 taps in row-major order, fp32, one rounding per operation."""
+    f32 = np.float32
+    B, H, W = a.shape
+    pad = a[:, _reflect101(H)[:, None], _reflect101(W)[None, :]]
+    cc = f32(-0.5 / (sigma_color * sigma_color))
+    g = -0.5 / (sigma_space * sigma_space)
+    num, den = np.zeros_like(a), np.zeros_like(a)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for dy, dx in _full(5):
+            r2 = dx * dx + dy * dy
+            if r2 > 4:
+                continue
+            v = pad[:, 2 + dy:2 + dy + H, 2 + dx:2 + dx + W]
+            dv = v - a
+            e = (dv * dv) * cc
+            w = f32(np.exp(float(r2) * g)) * np.exp(e)
+            num = num + w * v
+            den = den + w
+        return num / den
+
+
+def _column_top_mask(valid):
+    """top[y,x] = y >= the first valid row of column x; a column without one has first row 0 (np.argmax of all-False)."""
+    H = valid.shape[1]
+    return np.arange(H)[None, :, None] >= np.argmax(valid, axis=1)[:, None, :]
+
+
+def fill_depth_numpy(depth, mode="multiscale", max_depth=100.0, return_stages=False, extrapolate=False, blur_type="bilateral"):
+    """The definition of `fill_depth` (include/gdm.h gdm_fill_depth_hip) restated on the CPU: depth f32[B,H,W] (m) -> f32[B,H,W],
+    IP-Basic's fill_in_multiscale / fill_in_fast with the defaults the YCB-V loader uses (/root/reference/utils/ip_basic/
+    depth_map_utils.py:133-286, :66-130).  With return_stages also a dict of the intermediate images under the reference's
+    process_dict names (s1_inverted_depths ... s8_inverted_depths; s6_extended_depths is s5_combined_depths without extrapolation)
+    plus s7_before_bilateral, the image the bilateral filter reads; the fast mode has no s4 and no s6."""
+    if mode not in FILL_MODES:
+        raise ValueError("mode must be 'multiscale' or 'fast', got %r" % (mode,))
+    if extrapolate or blur_type != "bilateral":
+        raise ValueError("only extrapolate=False and blur_type='bilateral' are defined (the loader passes nothing else)")
+    f32 = np.float32
+    d = np.asarray(depth, dtype=f32)
+    if d.ndim != 3:
+        raise ValueError("depth must be [B,H,W], got %s" % (d.shape,))
+    with np.errstate(invalid="ignore"):
+        d = np.where(d > 0, d, f32(0.0))
+    md, t = f32(max_depth), f32(0.1)
+
+    def inv(a):
+        return np.where(a > t, md - a, a)
+
+    st = {}
+    s1 = inv(d)
+    if mode == "multiscale":
+        near, med, far = (d > t) & (d <= f32(15.0)), (d > f32(15.0)) & (d <= f32(30.0)), d > f32(30.0)
+        s2 = s1
+        for sel, taps in ((far, _cross(3)), (med, _cross(5)), (near, _cross(7))):
+            dil = _morph(np.where(sel, s1, f32(0.0)), taps, np.maximum)
+            s2 = np.where(dil > t, dil, s2)
+        s3 = _morph(_morph(s2, _full(5), np.maximum), _full(5), np.minimum)
+        s4 = np.where(s3 > t, _median5(s3), s3)
+        s5 = np.where(~(s4 > t) & _column_top_mask(s4 > t), _morph(s4, _full(9), np.maximum), s4)
+        top = _column_top_mask(s5 > t)
+        s7 = s5
+        for _ in range(6):
+            s7 = np.where((s7 < t) & top, _morph(s7, _full(5), np.maximum), s7)
+        valid = (s7 > t) & top
+        m = np.where(valid, _median5(s7), s7)
+        f = np.where(valid, _bilateral(m, 0.5, 2.0), m)
+        st.update(s4_blurred_depths=s4, s6_extended_depths=s5)
+    else:
+        s2 = _morph(s1, _DIAMOND_5, np.maximum)
+        s3 = _morph(_morph(s2, _full(5), np.maximum), _full(5), np.minimum)
+        s5 = np.where(s3 < t, _morph(s3, _full(7), np.maximum), s3)
+        m = _median5(s5)
+        f = _bilateral(m, 1.5, 2.0)
+    out = inv(f).astype(f32)
+    if not return_stages:
+        return out
+    st.update(s1_inverted_depths=s1, s2_dilated_depths=s2, s3_closed_depths=s3, s5_combined_depths=s5, s7_before_bilateral=m,
+              s7_blurred_depths=f, s8_inverted_depths=out)
+    return out, {k: st[k] for k in sorted(st)}
+
+
+_fill_workspace = {}                                           # device -> the grow-only workspace of fill_depth
+
+
+def fill_depth(depth, mode="multiscale", max_depth=100.0, return_stages=False, extrapolate=False, blur_type="bilateral"):
+    """Depth completion of cropped depth images, the YCB-V loader's `fill_missing(dpt, 1, 1)` (ycbv_pbr.py:477): depth f32[B,H,W]
+    (m, any H, W >= 1) -> f32[B,H,W], the definition `fill_depth_numpy` restates.  mode "multiscale" (a memset and three launches) or
+    "fast" (one launch), whatever B.  With return_stages also the dict of intermediate images `fill_depth_numpy` returns."""
+    if mode not in FILL_MODES:
+        raise ValueError("mode must be 'multiscale' or 'fast', got %r" % (mode,))
+    if extrapolate or blur_type != "bilateral":
+        raise ValueError("only extrapolate=False and blur_type='bilateral' are defined (the loader passes nothing else)")
+    depth = ops._dev(depth, torch.float32, "depth")
+    if depth.dim() != 3:
+        raise ValueError("depth must be [B,H,W], got %s" % (tuple(depth.shape),))
+    B, H, W = depth.shape
+    lib, m = _lib.lib(), FILL_MODES[mode]
+    need = lib.gdm_fill_depth_workspace_bytes(B, H, W, m)
+    ws = _fill_workspace.get(depth.device)
+    if need and (ws is None or ws.numel() < need):
+        ws = _fill_workspace[depth.device] = torch.empty(need, dtype=torch.uint8, device=depth.device)
+    out = torch.empty_like(depth)
+    stages = torch.empty((FILL_STAGES, B, H, W), dtype=torch.float32, device=depth.device) if return_stages else None
+    check(lib.gdm_fill_depth_hip(depth.data_ptr(), B, H, W, m, float(max_depth), ws.data_ptr() if need else None,
+                                 ws.numel() if need else 0, out.data_ptr(), stages.data_ptr() if return_stages else None,
+                                 ops._stream()), "gdm_fill_depth_hip")
+    if not return_stages:
+        return out
+    st = {name: stages[i] for i, name in enumerate(_FILL_STAGE_NAMES) if not (mode == "fast" and i == 3)}
+    if mode == "multiscale":
+        st["s6_extended_depths"] = st["s5_combined_depths"]
+    st["s8_inverted_depths"] = out
+    return out, {k: st[k] for k in sorted(st)}
+
+
 def depth_normals(depth, K, k_size=5, distance_threshold=2000, difference_threshold=20):
     """Surface normals from the depth image, the loader's normalSpeed.depth_normal(dpt_mm, fx, fy, 5, 2000, 20, False)
     (linemod_pbr.py:460-463): depth f32[B,H,W] (m), K f32[B,3,3] -> normals f32[B,3,H,W], unit vectors towards the camera
@@ -240,10 +410,11 @@ def crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=None):
     depth f32[B,H,W], normals f32[B,3,H,W], K f32[B,3,3], center f32[B,2], scale f32[B] (source pixels), mask u8[B,H,W] or None ->
     dict(rgb f32[B,3,S,S] colour-normalised, normals f32[B,3,S,S], dpt_xyz f32[B,S,S,3], depth f32[B,S,S], mask u8[B,S,S] with a
     mask).  Bilinear for rgb and normals, nearest for the rest, zeros outside the frame; with scale == S and
-    center = (x0 + S/2, y0 + S/2) it is the integer crop at (x0, y0)."""
+    center = (x0 + S/2, y0 + S/2) it is the integer crop at (x0, y0).  normals=None crops no normals (no "normals" in the dict)."""
     rgb_u8 = ops._dev(rgb_u8, torch.uint8, "rgb_u8")
     depth = ops._dev(depth, torch.float32, "depth")
-    normals = ops._dev(normals, torch.float32, "normals")
+    if normals is not None:
+        normals = ops._dev(normals, torch.float32, "normals")
     K = ops._dev(K, torch.float32, "K")
     center = ops._dev(center, torch.float32, "center")
     scale = ops._dev(scale, torch.float32, "scale")
@@ -252,46 +423,68 @@ def crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=None):
     B, H, W = depth.shape
     for t, shape, name in ((rgb_u8, (B, H, W, 3), "rgb_u8"), (normals, (B, 3, H, W), "normals"), (K, (B, 3, 3), "K"),
                            (center, (B, 2), "center"), (scale, (B,), "scale")):
-        if tuple(t.shape) != shape:
+        if t is not None and tuple(t.shape) != shape:
             raise ValueError("%s must be %s, got %s" % (name, list(shape), tuple(t.shape)))
     dev = depth.device
     out = dict(rgb=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
-               normals=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
                dpt_xyz=torch.empty((B, S, S, 3), dtype=torch.float32, device=dev),
                depth=torch.empty((B, S, S), dtype=torch.float32, device=dev))
-    mp = op = None
+    mp = op = np_ = on = None
+    if normals is not None:
+        out["normals"] = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+        np_, on = normals.data_ptr(), out["normals"].data_ptr()
     if mask is not None:
         mask = ops._dev(mask, torch.uint8, "mask")
         if tuple(mask.shape) != (B, H, W):
             raise ValueError("mask must be [B=%d,H=%d,W=%d], got %s" % (B, H, W, tuple(mask.shape)))
         out["mask"] = torch.empty((B, S, S), dtype=torch.uint8, device=dev)
         mp, op = mask.data_ptr(), out["mask"].data_ptr()
-    check(_lib.lib().gdm_warp_crop_hip(rgb_u8.data_ptr(), depth.data_ptr(), normals.data_ptr(), K.data_ptr(), mp, center.data_ptr(),
-                                       scale.data_ptr(), B, H, W, int(S), out["rgb"].data_ptr(), out["normals"].data_ptr(),
+    check(_lib.lib().gdm_warp_crop_hip(rgb_u8.data_ptr(), depth.data_ptr(), np_, K.data_ptr(), mp, center.data_ptr(),
+                                       scale.data_ptr(), B, H, W, int(S), out["rgb"].data_ptr(), on,
                                        out["dpt_xyz"].data_ptr(), out["depth"].data_ptr(), op, ops._stream()), "gdm_warp_crop_hip")
     return out
 
 
-def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, train=False, generator=None, normals=None):
+def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, train=False, generator=None, normals=None,
+                           depth_fill=None):
     """The whole item from the raw frame: rgb_u8 u8[B,H,W,3], depth f32[B,H,W] (m), K f32[B,3,3], bbox_xyxy f32[B,4], mask
     u8[B,H,W] or None -> the dict of `make_inputs` (rgb, cld_rgb_nrm, choose, dpt_xyz, origin_labels with a mask, the neighbour
     pyramid) plus n_valid i32[B], the number of depth > 1e-6 pixels of each crop (the loader drops a training item below 200,
-    linemod_pbr.py:479), and the center f32[B,2] / scale f32[B] it cropped at.  depth_normals (unless `normals` f32[B,3,H,W] is
-    given) -> dzi_boxes -> crop_from_boxes -> sample_valid_pixels -> assembly -> pyramid.build_pyramid, all on
-    the device without a host synchronisation."""
+    linemod_pbr.py:479), and the center f32[B,2] / scale f32[B] it cropped at.  All on the device without a host synchronisation.
+
+    depth_fill=None, the LineMOD item: depth_normals on the frame (unless `normals` f32[B,3,H,W] is given) -> dzi_boxes ->
+    crop_from_boxes -> sample_valid_pixels -> assembly -> pyramid.build_pyramid.
+
+    depth_fill="multiscale" / "fast", the YCB-V item (ycbv_pbr.py:458-509): dzi_boxes -> crop_from_boxes without normals ->
+    fill_depth on the cropped depth -> depth_normals of the filled crop with the frame's own K (the reference passes fx, fy unchanged)
+    -> sample_valid_pixels among the FILLED pixels (filled > 1e-6, which n_valid then counts) -> assembly -> pyramid.  The dict also
+    holds depth_filled f32[B,S,S].  As in the reference (:506), cld is gathered from the crop's UNFILLED dpt_xyz, so a point chosen
+    inside a filled hole has xyz = (0,0,0) while its normal comes from the filled surface; `normals` is not taken here."""
     B, H, W = depth.shape
-    if normals is None:
-        normals = depth_normals(depth, K)
     center, scale = dzi_boxes(bbox_xyxy, (H, W), train=train, generator=generator)
-    crop = crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=mask)
-    xyz = crop["dpt_xyz"]
-    choose = sample_valid_pixels(xyz, n_points, generator)                           # [B,1,N]
+    extra = {}
+    if depth_fill is None:
+        if normals is None:
+            normals = depth_normals(depth, K)
+        crop = crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=mask)
+        xyz, nrm = crop["dpt_xyz"], crop["normals"]
+        valid = crop["depth"] > 1e-6
+        choose = sample_valid_pixels(xyz, n_points, generator)                       # [B,1,N]
+    else:
+        if normals is not None:
+            raise ValueError("normals= goes with depth_fill=None: the YCB-V item takes its normals from the filled crop")
+        crop = crop_from_boxes(rgb_u8, depth, None, K, center, scale, S, mask=mask)
+        filled = fill_depth(crop["depth"], mode=depth_fill)
+        xyz, nrm = crop["dpt_xyz"], depth_normals(filled, K)
+        valid = filled > 1e-6
+        choose = sample_valid_pixels(xyz, n_points, generator, valid=valid)
+        extra["depth_filled"] = filled
     ch = choose[:, 0].long()
     cld = torch.gather(xyz.reshape(B, S * S, 3), 1, ch[:, :, None].expand(-1, -1, 3))
     rgb_pt = torch.gather(crop["rgb"].reshape(B, 3, S * S), 2, ch[:, None, :].expand(-1, 3, -1))
-    nrm_pt = torch.gather(crop["normals"].reshape(B, 3, S * S), 2, ch[:, None, :].expand(-1, 3, -1))
+    nrm_pt = torch.gather(nrm.reshape(B, 3, S * S), 2, ch[:, None, :].expand(-1, 3, -1))
     inputs = dict(rgb=crop["rgb"], cld_rgb_nrm=torch.cat([cld.transpose(1, 2), rgb_pt, nrm_pt], dim=1).contiguous(), choose=choose,
-                  dpt_xyz=xyz, n_valid=(crop["depth"].reshape(B, S * S) > 1e-6).sum(dim=1).to(torch.int32), center=center, scale=scale)
+                  dpt_xyz=xyz, n_valid=valid.reshape(B, S * S).sum(dim=1).to(torch.int32), center=center, scale=scale, **extra)
     if mask is not None:
         lab = torch.gather(crop["mask"].reshape(B, S * S), 1, ch)
         inputs["origin_labels"] = torch.where(lab == 255, torch.ones_like(lab), lab)

@@ -50,6 +50,29 @@ def make_frame(rs, hole_frac=0.05):
     return depth, rgb, nrm.astype(np.float32)
 
 
+def make_fill_crops():
+    """Named depth images f32[H,W] for depth completion (frontend.fill_depth), chosen so that every stage of the operator decides
+    something: `A` a 256 x 256 crop of a frame with a hole the fill cannot close, an empty top band and empty columns; `B` the same
+    with its right half scaled into the medium and far depth bins; `zero`; two odd sizes; an isolated pixel and a 3 x 3 block in an
+    empty 64 x 64 crop (the block tells the two treatments of an empty column apart); a crop with 90 % holes; a whole frame with
+    30 % holes."""
+    a = make_frame(np.random.RandomState(3))[0][100:356, 200:456].copy()
+    a[40:90, 60:130] = 0
+    a[:30, 200:] = 0
+    a[:, 10:14] = 0
+    b = a.copy()
+    b[:, 128:192] *= np.float32(20.0)
+    b[:, 192:256] *= np.float32(35.0)
+    pixel = np.zeros((64, 64), np.float32)
+    pixel[31, 31] = 0.8
+    block = np.zeros((64, 64), np.float32)
+    block[30:33, 30:33] = 0.8
+    return dict(A=a, B=b, zero=np.zeros((256, 256), np.float32), odd=np.ascontiguousarray(b[5:42, 100:153]),
+                small=np.ascontiguousarray(a[20:84, 170:234]), pixel=pixel, block=block,
+                sparse=np.ascontiguousarray(make_frame(np.random.RandomState(4), hole_frac=0.9)[0][100:356, 200:456]),
+                frame=make_frame(np.random.RandomState(5), hole_frac=0.3)[0])
+
+
 def make_box_mask(rs, H=480, W=640, radius=(40.0, 110.0)):
     """A detection for a frame: the object mask u8[H,W] (255 on a disc, as the loader's mask images) and its tight box
     f32[4] = (x1, y1, x2, y2), the `bbox` of an annotation.  The disc's centre lies inside the frame, its radius in `radius`."""

@@ -540,7 +540,8 @@ int gdm_depth_normals_hip(const float* depth, const float* K, int B, int H, int 
  * rgb u8[B,H,W,3], depth f32[B,H,W], normals f32[B,3,H,W], K f32[B,3,3], mask u8[B,H,W] or NULL, center f32[B,2] = (cx,cy) and
  * scale f32[B] in source pixels -> out_rgb f32[B,3,S,S] (bilinear on uint8, then normalize_color: / 255, - mean, / std with std
  * .229/.224/.224), out_normals f32[B,3,S,S] (bilinear), out_xyz f32[B,S,S,3] (dpt_2_pcld of the nearest source pixel, the arithmetic
- * of gdm_depth_to_xyz_hip), out_depth f32[B,S,S] and out_mask u8[B,S,S] (nearest; out_mask NULL exactly when mask is).
+ * of gdm_depth_to_xyz_hip), out_depth f32[B,S,S] and out_mask u8[B,S,S] (nearest; out_mask NULL exactly when mask is).  normals and
+ * out_normals may both be NULL: no normals are cropped (the YCB-V item computes them on the filled crop instead).
  * OpenCV's fixed-point warpAffine with BORDER_CONSTANT 0 for a pure scale + shift:
  *   a = fp64(scale)/S; bx = fp64(cx) - (a S)/2; by = fp64(cy) - (a S)/2;  R(v) = round-half-even(v * 1024) as an integer
  *   nearest: X = (R(a x) + R(bx) + 512) >> 10;  Y = (R(a y + by) + 512) >> 10
@@ -553,6 +554,42 @@ int gdm_depth_normals_hip(const float* depth, const float* K, int B, int H, int 
 int gdm_warp_crop_hip(const uint8_t* rgb, const float* depth, const float* normals, const float* K, const uint8_t* mask,
                       const float* center, const float* scale, int B, int H, int W, int S, float* out_rgb, float* out_normals,
                       float* out_xyz, float* out_depth, uint8_t* out_mask, void* stream);
+
+/* Front end, depth completion of a cropped depth image (the YCB-V loader's `fill_missing(dpt, 1, 1)`, datasets/ycbv/ycbv_pbr.py:477:
+ * IP-Basic's fill_in_multiscale, or fill_in_fast, with their defaults, utils/ip_basic/depth_map_utils.py): depth (m) f32[B,H,W] ->
+ * out f32[B,H,W].  Defined here operation by operation, in fp32, from the documented meaning of the cv2 calls the reference makes
+ * (equality with a given cv2 build is unpinned):
+ *   in = depth > 0 ? depth : 0   (negative and NaN -> 0);  the thresholds are fp32(0.1), fp32(15), fp32(30)
+ *   inv(d) = d > 0.1 ? max_depth - d : d   (one fp32 subtraction)
+ *   dilate(a, k)[y,x] = max of a[y+dy,x+dx] over the nonzero (dy,dx) of k, anchored at its centre, taps outside the image ignored;
+ *     erode = min under the same rule;  close(a, k) = erode(dilate(a, k), k)
+ *     FULL_n: all of n x n;  CROSS_n: the centre row and the centre column of n x n;  DIAMOND_5: |dy| + |dx| <= 2
+ *   median5(a)[y,x] = the 13th smallest of the 5 x 5 window, coordinates clamped to the image (replicated border)
+ *   bilateral(a, sc, ss)[y,x]: the 13 taps with dx^2 + dy^2 <= 4 in row-major order (dy outer, from -2), coordinates reflected
+ *     (-1 -> 1, n -> n-2) and then clamped to the image;  cc = fp32(-0.5 / (sc sc)), ws(r2) = fp32(exp(-0.5 r2 / (ss ss))) (fp64 inside);
+ *     per tap v:  dv = v - a[y,x];  e = (dv dv) cc;  w = ws(dx^2+dy^2) expf(e);  num = num + w v;  den = den + w;   out = num / den
+ *     (no contraction; cv2 interpolates a table whose range depends on the image -- the formula is defined, not the table)
+ * mode GDM_FILL_MULTISCALE (extrapolate=False, blur_type='bilateral'):
+ *   near = 0.1 < in <= 15; med = 15 < in <= 30; far = in > 30;   s1 = inv(in)
+ *   s2 = s1, then overwritten where D > 0.1 by D = dilate(far ? s1 : 0, CROSS_3), then by dilate(med ? s1 : 0, CROSS_5), then by
+ *     dilate(near ? s1 : 0, CROSS_7)
+ *   s3 = close(s2, FULL_5);   s4 = s3 > 0.1 ? median5(s3) : s3
+ *   r0[x] = the first row y with s4[y,x] > 0.1, and 0 for a column without one;  top[y,x] = y >= r0[x]
+ *   s5 = (!(s4 > 0.1) && top) ? dilate(s4, FULL_9) : s4;   r0, top recomputed from s5
+ *   s7 = s5; six times: s7 = (s7 < 0.1 && top) ? dilate(s7, FULL_5) : s7
+ *   valid = s7 > 0.1 && top;  m = valid ? median5(s7) : s7;   f = valid ? bilateral(m, 0.5, 2.0) : m;   out = inv(f)
+ * mode GDM_FILL_FAST (DIAMOND_5, extrapolate=False, blur_type='bilateral'):
+ *   s1 = inv(in); s2 = dilate(s1, DIAMOND_5); s3 = close(s2, FULL_5); s5 = s3 < 0.1 ? dilate(s3, FULL_7) : s3;
+ *   m = median5(s5); f = bilateral(m, 1.5, 2.0); out = inv(f)
+ * stages (or NULL): f32[GDM_FILL_STAGES,B,H,W] = s1 | s2 | s3 | s4 | s5 | m | f; plane 3 is not written in the fast mode.
+ * workspace: gdm_fill_depth_workspace_bytes(B, H, W, mode) bytes (0 for the fast mode, where it may be NULL).  One memset node and
+ * three kernels (multiscale) or one kernel (fast), whatever B; no allocation, no host synchronisation. */
+#define GDM_FILL_MULTISCALE 0
+#define GDM_FILL_FAST 1
+#define GDM_FILL_STAGES 7
+size_t gdm_fill_depth_workspace_bytes(int B, int H, int W, int mode);
+int gdm_fill_depth_hip(const float* depth, int B, int H, int W, int mode, float max_depth, void* workspace, size_t workspace_bytes,
+                       float* out, float* stages, void* stream);
 
 /* ---- training-mode BatchNorm (+ ReLU / LeakyReLU), forward and backward -------------------------------------------------------
  * Replaces the conv -> nn.BatchNorm{1,2}d -> activation chains of the embedding network in the training step
