@@ -1,5 +1,6 @@
 """CPU: the robust pose fits' host side -- the sample hash restated in Python against the golden's recorded draws, argument checking
-of the new C entry points (no GPU needed: every check comes before any HIP call) and the command-line defaults."""
+of the new C entry points (no GPU needed: every check comes before any HIP call), the command-line defaults, and the numpy
+restatements of the reference's RANSAC and ICP (oracle/pose_ref.py) against the golden the real reference made."""
 import ctypes
 import os
 
@@ -113,3 +114,53 @@ def test_pose_options_are_checked_on_the_host():
         pose.solve_poses({"mask": None, "best_idx": None}, None, None, method="lmeds")
     with pytest.raises(ValueError, match="pose_opts"):
         pose.estimate_poses({}, None, None, pose_opts={"ransac_iter": 3})
+
+
+def test_oracle_ransac_restatement_matches_reference_golden():
+    """oracle/pose_ref.ransac (what the GPU tests at product shapes compare with) against the real reference's recorded run."""
+    from oracle import pose_ref
+    g = np.load(os.path.join(G, "pose_robust.npz"))
+    H = int(g["H"])
+    for b in range(g["r_mask"].shape[0]):
+        sel = g["r_mask"][b] != 0
+        if sel.sum() < 5:                                              # the evaluator's sentinel, before any fit
+            assert g["r_winner"][b] == -1 and g["r_valid"][b] == 0
+            continue
+        A = g["r_model"][g["r_idx"][b][sel]].astype(np.float64)
+        Bp = g["r_cld"][b, :3][:, sel].T.astype(np.float64)
+        r = pose_ref.ransac(A, Bp, g["r_samples"][b], float(g["match_err"]), float(g["fix_percent"]))
+        assert np.array_equal(r["counts"], g["r_counts"][b]) and np.array_equal(r["near"], g["r_near"][b])
+        assert r["winner"] == g["r_winner"][b] and (r["winner"] >= 0) == bool(g["r_valid"][b])
+        assert not r["degenerate"][1:].any()                           # the golden script rejected such data
+        assert len(r["poses"]) == H
+        if r["winner"] >= 0:
+            assert np.abs(r["RT"] - g["r_RT"][b]).max() <= 1e-9
+        else:
+            assert r["RT"] is None
+
+
+def test_oracle_icp_restatement_matches_reference_golden():
+    from oracle import pose_ref
+    g = np.load(os.path.join(G, "pose_robust.npz"))
+    for b in range(g["i_RT0"].shape[0]):
+        r = pose_ref.icp(g["i_cld"][b, :3].T, g["i_model"], g["i_RT0"][b], None, int(g["i_max_iters"]), float(g["i_tol"]))
+        assert r["iters"] == g["i_iters"][b]
+        assert np.abs(r["RT"] - g["i_RT"][b]).max() <= 1e-9
+        assert abs(r["resid"][-1] - g["i_resid"][b]) <= 1e-9
+        assert not r["starved"] and all(len(t) == 0 for t in r["ties"])
+
+
+def test_oracle_ransac_rule_and_pinning():
+    """The decision rule and the 'pinned' predicate the GPU test leans on, on hand-made count tables."""
+    from oracle import pose_cases, pose_ref
+    z = np.zeros(4, bool)
+    assert pose_ref.ransac_decide([3, 8, 8, 2], 10, 0.7) == (1, True)
+    assert pose_ref.ransac_decide([3, 7, 7, 2], 10, 0.7) == (1, False)          # 7 > 7.0 is false: best count, earliest on ties
+    assert pose_ref.ransac_decide([0, 0, 0, 0], 10, 0.7) == (-1, False)
+    assert pose_cases.decision_pinned([3, 8, 8, 2], [0, 0, 5, 5], z, 10, 0.7)
+    assert not pose_cases.decision_pinned([3, 8, 8, 2], [0, 1, 0, 0], z, 10, 0.7)     # the winner could drop to 7
+    assert not pose_cases.decision_pinned([6, 8, 8, 2], [2, 0, 0, 0], z, 10, 0.7)     # an earlier one could rise to 8
+    assert pose_cases.decision_pinned([6, 8, 8, 2], [2, 0, 0, 0], np.array([1, 0, 0, 0], bool), 10, 0.7)
+    assert pose_cases.decision_pinned([3, 7, 6, 2], [0, 0, 1, 0], z, 10, 0.7)          # a later tie still loses to the earlier h
+    assert not pose_cases.decision_pinned([6, 7, 3, 2], [1, 0, 0, 0], z, 10, 0.7)     # an earlier tie would win
+    assert not pose_cases.decision_pinned([0, 0, 0, 0], [0, 1, 0, 0], z, 10, 0.7)
