@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, settings
+from .derived import derived
 from .layers import act_code, cached_gemm_weight, folded_bn, fused_eval
 
 
@@ -51,13 +52,7 @@ class BasicBlock(nn.Module):
 
     @staticmethod
     def _packed_weight(conv):
-        w = conv.weight
-        key = (w._version, w.data_ptr())
-        cache = conv.__dict__.get("_gdm_wpk")
-        if cache is None or cache[0] != key:
-            cache = (key, ops.conv3x3_pack_weight(w))
-            conv.__dict__["_gdm_wpk"] = cache
-        return cache[1]
+        return derived(conv, "wpk", (conv.weight,), lambda: ops.conv3x3_pack_weight(conv.weight))
 
     @staticmethod
     def _train_conv(conv, x):
@@ -177,26 +172,17 @@ class PSPModule(nn.Module):
         M_k = W[:, kF:(k+1)F] @ V_k (so W_k . up(V_k pool_k f) = up(M_k pool_k f)), W_f = W[:, 4F:].  Cached."""
         w = self.bottleneck.weight
         vs = [st[1].weight for st in self.stages]
-        key = tuple((t._version, t.data_ptr()) for t in [w] + vs)
-        cache = self.__dict__.get("_gdm_split")
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                F_ = vs[0].shape[0]
-                w2 = w.view(w.shape[0], -1)
-                ms = [(w2[:, k * F_:(k + 1) * F_] @ v.view(F_, F_)).contiguous() for k, v in enumerate(vs)]
-                wf = w2[:, len(vs) * F_:].contiguous()
-            cache = (key, ms, wf)
-            self.__dict__["_gdm_split"] = cache
-        return cache[1], cache[2]
+
+        def make():
+            F_ = vs[0].shape[0]
+            w2 = w.view(w.shape[0], -1)
+            ms = [(w2[:, k * F_:(k + 1) * F_] @ v.view(F_, F_)).contiguous() for k, v in enumerate(vs)]
+            return ms, w2[:, len(vs) * F_:].contiguous()
+        return derived(self, "split", [w] + vs, make)
 
     def _split_weights_t(self, ms):
         """The folded prior matrices transposed ([Cin, Cout], the per-point kernel's weight layout), cached beside them."""
-        cache = self.__dict__.get("_gdm_split_t")
-        if cache is None or cache[0] is not ms:
-            with torch.no_grad():
-                cache = (ms, [m.t().contiguous() for m in ms])
-            self.__dict__["_gdm_split_t"] = cache
-        return cache[1]
+        return derived(self, "split_t", ms, lambda: [m.t().contiguous() for m in ms])
 
     def forward(self, feats):
         h, w = feats.size(2), feats.size(3)
@@ -276,14 +262,7 @@ class PSPUpsample(nn.Module):
     def _tap_major_weight(self):
         """[Cout,Cin,3,3] -> [9*Cout,Cin], row = tap*Cout + co; cached until the weight changes."""
         w = self.conv[1].weight
-        key = (w._version, w.data_ptr())
-        cache = self.__dict__.get("_gdm_wt")
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                wt = w.permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1]).contiguous()
-            cache = (key, wt)
-            self.__dict__["_gdm_wt"] = cache
-        return cache[1]
+        return derived(self, "wt", (w,), lambda: w.permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1]).contiguous())
 
     def reads_packed_only(self, shape):
         """True when forward() on a GPU map of this shape takes the tap GEMM on the map's packed operand (`gemm_bf16x3_map`) and reads
@@ -311,14 +290,9 @@ class PSPUpsample(nn.Module):
                 Bx, Cin, Hx, Wx = x.shape
                 if settings.USE_FUSED_UPCONV and Cin == 64 and conv.out_channels == 64 and Hx >= 2 and Wx >= 2 and Bx <= 65535:
                     # 64 -> 64 (last up stage): channel mix on the matrix cores into LDS + gather in ONE kernel, no 9*64-channel tensor
-                    w = conv.weight
-                    key = (w._version, w.data_ptr())
-                    cache = self.__dict__.get("_gdm_fused64")
-                    if cache is None or cache[0] != key:
-                        cache = (key, ops.upconv_fused64_pack_weight(w))
-                        self.__dict__["_gdm_fused64"] = cache
+                    wpk = derived(self, "fused64", (conv.weight,), lambda: ops.upconv_fused64_pack_weight(conv.weight))
                     scale, shift = folded_bn(self.conv[2], conv.bias)
-                    return ops.upconv_fused64(x, cache[1], scale, shift, (Hx * 2, Wx * 2), code[0], code[1])
+                    return ops.upconv_fused64(x, wpk, scale, shift, (Hx * 2, Wx * 2), code[0], code[1])
                 if settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, 9 * conv.out_channels, Hx * Wx):
                     wpk, c9 = cached_gemm_weight(self, "tap", self._tap_major_weight, (conv.weight,))
                     z = ops.gemm_bf16x3_map(x, wpk, c9)            # split-bf16 MFMA; reads the packed operand its producer wrote, if any

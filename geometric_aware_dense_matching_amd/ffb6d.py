@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from . import ops, settings
 from .cnn import PSPNet, bn_act
+from .derived import derived
 from .layers import act_code, cached_gemm_weight, folded_bn, fused_eval, pt_conv2d, rl_conv1d, rl_conv2d
 from .randla import DilatedResBlock
 
@@ -101,24 +102,16 @@ class FFB6DEmb(nn.Module):
     def _split_fuse_weight(layer, c_first):
         """1x1 fuse conv over cat(a, b): W = [W_a | W_b] split at channel c_first (contiguous copies, cached)."""
         w = layer.conv.weight
-        key = (w._version, w.data_ptr(), c_first)
-        cache = layer.__dict__.get("_gdm_split")
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                w2 = w.view(w.shape[0], -1)
-                cache = (key, w2[:, :c_first].contiguous(), w2[:, c_first:].contiguous())
-            layer.__dict__["_gdm_split"] = cache
-        return cache[1], cache[2]
+
+        def make():
+            w2 = w.view(w.shape[0], -1)
+            return w2[:, :c_first].contiguous(), w2[:, c_first:].contiguous()
+        return derived(layer, "split", (w,), make, extra=(c_first,))
 
     @staticmethod
     def _fuse_weight_t(layer, wa, tag="a"):
         """wa transposed ([ci][co], contiguous), cached beside the split weights."""
-        slot = "_gdm_w%s_t" % tag
-        cache = layer.__dict__.get(slot)
-        if cache is None or cache[0] is not wa:
-            cache = (wa, wa.t().contiguous())
-            layer.__dict__[slot] = cache
-        return cache[1]
+        return derived(layer, "w%s_t" % tag, (wa,), lambda: wa.t().contiguous())
 
     def _p2r_point_term(self, pre_layer, fuse_layer, c, p_emb0):
         """The point half of the p2r fusion, W_b . pre(p_emb0), at the points -- exactly what _p2r_fuse computes first (same branch
@@ -159,15 +152,12 @@ class FFB6DEmb(nn.Module):
                             t_pm = ops.pointwise([pp], self._fuse_weight_t(fuse_layer, wb, "b"), point_major=True)   # [B, n', 64]
                         else:
                             t_pm = torch.matmul(pp.transpose(1, 2), wb.t())
-                    cache = fuse_layer.__dict__.get("_gdm_wa_pk")
-                    if cache is None or cache[0] is not wa:
-                        cache = (wa, ops.pack_rows64(wa))
-                        fuse_layer.__dict__["_gdm_wa_pk"] = cache
+                    wa_pk = derived(fuse_layer, "wa_pk", (wa,), lambda: ops.pack_rows64(wa))
                     if final is not None:
                         fconv = final[0]
-                        return ops.conv64_gather_add_final(rgb_emb0.reshape(bs, c, hr * wr), cache[1], t_pm, idx.reshape(bs, -1), scale, shift,
+                        return ops.conv64_gather_add_final(rgb_emb0.reshape(bs, c, hr * wr), wa_pk, t_pm, idx.reshape(bs, -1), scale, shift,
                                                            code[0], code[1], fconv.weight, fconv.bias).view(bs, -1, hr, wr)
-                    y = ops.conv64_gather_add_act_mfma(rgb_emb0.reshape(bs, c, hr * wr), cache[1], t_pm, idx.reshape(bs, -1), scale, shift,
+                    y = ops.conv64_gather_add_act_mfma(rgb_emb0.reshape(bs, c, hr * wr), wa_pk, t_pm, idx.reshape(bs, -1), scale, shift,
                                                        code[0], code[1], pixel_major=pixel_major, t_point_major=True,
                                                        hw=(hr, wr) if (want_packed and settings.USE_PACKED_PRODUCERS and not pixel_major) else None)
                     if pixel_major:
@@ -256,12 +246,7 @@ class FFB6DEmb(nn.Module):
                     and tuple(conv.stride) == (2, 2) and tuple(conv.padding) == (3, 3) and tuple(conv.dilation) == (1, 1)
                     and inputs["rgb"].shape[0] <= 65535):
                 # the whole stem in one own launch (split-bf16 MFMA implicit GEMM, pooled in LDS): no library kernel is left in the step
-                key = (conv.weight._version, conv.weight.data_ptr())
-                cache = conv.__dict__.get("_gdm_stem_pk")
-                if cache is None or cache[0] != key:
-                    cache = (key, ops.stem_pack_weight(conv.weight))
-                    conv.__dict__["_gdm_stem_pk"] = cache
-                rgb_emb = ops.stem(inputs["rgb"], cache[1], s0, b0)
+                rgb_emb = ops.stem(inputs["rgb"], derived(conv, "stem_pk", (conv.weight,), lambda: ops.stem_pack_weight(conv.weight)), s0, b0)
             else:
                 y0 = conv(inputs["rgb"])
                 if plain_pool and y0.shape[0] * y0.shape[1] <= 65535:
@@ -490,12 +475,9 @@ class FFB6DEmb(nn.Module):
         last = self.cnn_up_stages[len(self.rndla_up_stages) - 1]
         up, fin = last[0], last[1]
         conv, fconv = up.conv[1], fin[0]
-        key = (conv.weight._version, conv.weight.data_ptr(), fconv.weight._version, fconv.weight.data_ptr())
-        cache = self.__dict__.get("_gdm_final_pk")
-        if cache is None or cache[0] != key:
-            cache = (key, ops.upconv_fused64_pack_weight(conv.weight), ops.pack_rows64(fconv.weight.reshape(64, 64)))
-            self.__dict__["_gdm_final_pk"] = cache
+        wpk, fpk = derived(self, "final_pk", (conv.weight, fconv.weight),
+                           lambda: (ops.upconv_fused64_pack_weight(conv.weight), ops.pack_rows64(fconv.weight.reshape(64, 64))))
         scale, shift = _fbn(up.conv[2], conv.bias)
         code = act_code(up.conv[3])
-        return ops.upconv_final_points(x_pm, hw, choose, cache[1], scale, shift, code[0], code[1], cache[2], fconv.bias,
+        return ops.upconv_final_points(x_pm, hw, choose, wpk, scale, shift, code[0], code[1], fpk, fconv.bias,
                                        (hw[0] * 2, hw[1] * 2))

@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, settings
+from .derived import derived
 from .ffb6d import FFB6DEmb
 from .layers import PtSeq, pt_conv1d
 from .loss import AutomaticWeightedLoss, CircleLoss, FocalLoss
@@ -46,15 +47,11 @@ class GeoMatch(nn.Module):
         self._mesh_cache = None
 
     # ------------------------------------------------------------------ training matching (geoMatch.py:55-157)
-    def _positive_tables(self, mesh_xyz):
+    def _positive_tables(self):
         """Radius-test bit table of the model (depends on xyz and positive_r only): built once, rebuilt if either changes."""
-        from . import ops
-        key = (mesh_xyz.data_ptr(), mesh_xyz._version, float(self.positive_r), mesh_xyz.device)
-        cache = self.__dict__.get("_gdm_nbr")
-        if cache is None or cache[0] != key:
-            cache = (key, ops.circle_nbr_table(mesh_xyz, self.positive_r))
-            self.__dict__["_gdm_nbr"] = cache
-        return cache[1]
+        xyz = self.model_emb.xyz
+        return derived(self, "nbr", (xyz,), lambda: ops.circle_nbr_table(xyz.contiguous(), self.positive_r),
+                       extra=(float(self.positive_r), xyz.device))
 
     def pointwise_feature_matching(self, rgbd_feature, mesh_feature, x):
         """geoMatch.py:102-157 for the whole batch at once: value and gradients of the reference's per-item loop (mean over the
@@ -104,7 +101,7 @@ class GeoMatch(nn.Module):
             if symmetric:
                 lrow = ops.circle_match(rows, mesh_rows, c1, bi, c2=c2, gamma=16.0, m=0.2)
             else:
-                lrow = ops.circle_match(rows, mesh_rows, c1, bi, nbr=self._positive_tables(self.model_emb.xyz.contiguous()),
+                lrow = ops.circle_match(rows, mesh_rows, c1, bi, nbr=self._positive_tables(),
                                         visb=ops.circle_visbits(x["visible_flag"]), gamma=16.0, m=0.2)
         else:
             padding = -torch.ones((self.feat_dim, 1), dtype=torch.float32, device=mesh.device)
@@ -139,42 +136,27 @@ class GeoMatch(nn.Module):
     def _fused_heads(self, rgb):
         """Packed weights + folded BatchNorms of the per-point heads for ops.point_heads, or None when the fused kernel does not apply
         (training / autograd, a non-default head structure, split-bf16 GEMMs switched off).  Cached until a parameter changes."""
-        from .layers import act_code, fused_eval, folded_bn, _PtConv
+        from .layers import act_code, fused_eval, layer_deps, scale_shift, _PtConv
         if not (settings.USE_FUSED_HEADS and settings.USE_MFMA_GEMM and fused_eval(rgb, self)):
             return None
         chain = list(self.feature_encoding_layer) + [self.normalize_feature_layer] + list(self.seg_layer)
         if len(chain) != 9 or not all(isinstance(m, _PtConv) and isinstance(m.conv, nn.Conv1d) for m in chain):
             return None
-        deps = []
-        for m in chain:
-            deps += [m.conv.weight] + ([m.conv.bias] if m.conv.bias is not None else [])
-            if hasattr(m, "normlayer"):
-                bn = m.normlayer.bn
-                deps += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        key = tuple((t._version, t.data_ptr()) for t in deps)
-        cache = self.__dict__.get("_gdm_heads")
-        if cache is not None and cache[0] == key:
-            return cache[1]
-        hidden, last = chain[:-1], chain[-1]
-        ok = (all(m.conv.in_channels == 128 and m.conv.out_channels == 128 for m in hidden) and last.conv.in_channels == 128
-              and last.conv.out_channels <= 16 and not hasattr(last, "normlayer") and getattr(last, "activation", None) is None)
-        codes = [act_code(getattr(m, "activation", None)) for m in hidden]
-        ok = ok and all(c is not None and c[0] in (ops.ACT_NONE, ops.ACT_RELU) for c in codes)
-        value = None
-        if ok:
-            with torch.no_grad():
-                layers = []
-                for m, c in zip(hidden, codes):
-                    if hasattr(m, "normlayer"):
-                        scale, shift = folded_bn(m.normlayer.bn, m.conv.bias)
-                    else:
-                        scale, shift = None, (m.conv.bias.detach().contiguous() if m.conv.bias is not None else None)
-                    layers.append((ops.gemm_pack_weight(m.conv.weight.reshape(128, 128)), scale, shift, c[0]))
-                cl = last.conv.out_channels
-                value = (layers, (ops.gemm_pack_weight(last.conv.weight.reshape(cl, 128)),
-                                  last.conv.bias.detach().contiguous() if last.conv.bias is not None else None, cl))
-        self.__dict__["_gdm_heads"] = (key, value)
-        return value
+
+        def bn_of(m):
+            return m.normlayer.bn if hasattr(m, "normlayer") else None
+
+        def make():
+            hidden, last = chain[:-1], chain[-1]
+            ok = (all(m.conv.in_channels == 128 and m.conv.out_channels == 128 for m in hidden) and last.conv.in_channels == 128
+                  and last.conv.out_channels <= 16 and not hasattr(last, "normlayer") and getattr(last, "activation", None) is None)
+            codes = [act_code(getattr(m, "activation", None)) for m in hidden]
+            if not (ok and all(c is not None and c[0] in (ops.ACT_NONE, ops.ACT_RELU) for c in codes)):
+                return None
+            layers = [(ops.gemm_pack_weight(m.conv.weight.reshape(128, 128)),) + scale_shift(m.conv, bn_of(m)) + (c[0],) for m, c in zip(hidden, codes)]
+            cl = last.conv.out_channels
+            return layers, (ops.gemm_pack_weight(last.conv.weight.reshape(cl, 128)), scale_shift(last.conv)[1], cl)
+        return derived(self, "heads", sum((layer_deps(m.conv, bn_of(m)) for m in chain), []), make)
 
     def forward(self, inputs, end_points=None, defer_seg=False):
         """defer_seg: accepted for callers of earlier rounds (a split of the fused heads onto a side stream was measured without gain and

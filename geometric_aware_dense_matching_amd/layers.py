@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, settings
+from .derived import derived
 
 
 def fused_eval(x, module):
@@ -19,37 +20,37 @@ def fused_eval(x, module):
     return (not module.training) and x.is_cuda and not torch.is_grad_enabled()
 
 
+def layer_deps(conv=None, bn=None):
+    """The tensors the derived values of a conv(+BN) layer depend on: weight, bias when there is one, the BN's four."""
+    ts = ([conv.weight, conv.bias] if conv is not None else []) + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+    return [t for t in ts if t is not None]
+
+
 def folded_bn(bn, conv_bias=None):
-    """(scale, shift) of an eval-mode BatchNorm, with an optional preceding conv bias folded in; cached on the
-    module and recomputed when any of its tensors changed (version counters / storage)."""
-    ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var) + ((conv_bias,) if conv_bias is not None else ())
-    key = tuple((t._version, t.data_ptr()) for t in ts)
-    cache = bn.__dict__.get("_gdm_fold")
-    if cache is None or cache[0] != key:
-        with torch.no_grad():
-            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-            shift = bn.bias - bn.running_mean * scale
-            if conv_bias is not None:
-                shift = shift + conv_bias * scale
-        cache = (key, scale.contiguous(), shift.contiguous())
-        bn.__dict__["_gdm_fold"] = cache
-    return cache[1], cache[2]
+    """(scale, shift) of an eval-mode BatchNorm, with an optional preceding conv bias folded in; cached on the module."""
+    def make():
+        scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+        shift = bn.bias - bn.running_mean * scale
+        if conv_bias is not None:
+            shift = shift + conv_bias * scale
+        return scale.contiguous(), shift.contiguous()
+    return derived(bn, "fold", layer_deps(bn=bn) + ([conv_bias] if conv_bias is not None else []), make)
+
+
+def scale_shift(conv, bn=None):
+    """(scale, shift) behind `conv`: its BatchNorm folded together with the bias, or (None, bias) when there is no BatchNorm."""
+    if bn is not None:
+        return folded_bn(bn, conv.bias)
+    return None, (conv.bias.detach().contiguous() if conv.bias is not None else None)
 
 
 def cached_gemm_weight(owner, tag, weight2d, deps):
     """Packed split-bf16 GEMM weight of `weight2d` (a [Cout,Cin] tensor, or a callable producing it), cached on `owner`
     under `tag` until any tensor in `deps` changes."""
-    key = tuple((t._version, t.data_ptr()) for t in deps)
-    slot = "_gdm_gemm_" + tag
-    cache = owner.__dict__.get(slot)
-    if cache is None or cache[0] != key:
-        with torch.no_grad():
-            w = weight2d() if callable(weight2d) else weight2d
-            cache = (key, ops.gemm_pack_weight(w.contiguous()), w.shape[0])
-        owner.__dict__[slot] = cache
-    return cache[1], cache[2]
-
-
+    def make():
+        w = weight2d() if callable(weight2d) else weight2d
+        return ops.gemm_pack_weight(w.contiguous()), w.shape[0]
+    return derived(owner, "gemm_" + tag, deps, make)
 
 
 def act_code(act):
@@ -61,12 +62,7 @@ def act_code(act):
     if isinstance(act, nn.LeakyReLU):
         return ops.ACT_LEAKY, float(act.negative_slope)
     if isinstance(act, nn.PReLU) and act.weight.numel() == 1:
-        key = (act.weight._version, act.weight.data_ptr())
-        cache = act.__dict__.get("_gdm_slope")
-        if cache is None or cache[0] != key:
-            cache = (key, float(act.weight.detach().item()))          # one host sync per weight change
-            act.__dict__["_gdm_slope"] = cache
-        return ops.ACT_LEAKY, cache[1]
+        return ops.ACT_LEAKY, derived(act, "slope", (act.weight,), lambda: float(act.weight.item()))   # one host sync per weight change
     return None
 
 
@@ -94,21 +90,11 @@ class _FusedConvMixin:
         if code is None:
             return None
         bnw = getattr(self, self._bn_name, None)
-        deps = [conv.weight] + ([conv.bias] if conv.bias is not None else [])
-        if bnw is not None:
-            deps += [bnw.bn.weight, bnw.bn.bias, bnw.bn.running_mean, bnw.bn.running_var]
-        key = tuple((t._version, t.data_ptr()) for t in deps)
-        cache = self.__dict__.get("_gdm_pw")
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                wt = conv.weight.reshape(conv.weight.shape[0], -1).t().contiguous()
-                if bnw is not None:
-                    scale, shift = folded_bn(bnw.bn, conv.bias)
-                else:
-                    scale, shift = None, (conv.bias.detach().contiguous() if conv.bias is not None else None)
-            cache = (key, wt, scale, shift)
-            self.__dict__["_gdm_pw"] = cache
-        return cache[1], cache[2], cache[3], code[0], code[1]
+        bn = bnw.bn if bnw is not None else None
+
+        def make():
+            return (conv.weight.reshape(conv.weight.shape[0], -1).t().contiguous(),) + scale_shift(conv, bn)
+        return derived(self, "pw", layer_deps(conv, bn), make) + code
 
     def _residual_params(self, other):
         """This layer + `other` (both without activation) as ONE layer over cat(own input, other's input):
@@ -116,17 +102,14 @@ class _FusedConvMixin:
         a, b = self._pointwise_params(), other._pointwise_params()
         if a is None or b is None or a[3] != ops.ACT_NONE or b[3] != ops.ACT_NONE:
             return None
-        cache = self.__dict__.get("_gdm_pw_res")
-        if cache is None or cache[0] is not a[0] or cache[1] is not b[0] or cache[2] is not a[1] or cache[3] is not b[1]:
-            with torch.no_grad():
-                def scaled(w, sc):
-                    return w if sc is None else w * sc.view(1, -1)
-                wt = torch.cat([scaled(a[0], a[1]), scaled(b[0], b[1])], dim=0).contiguous()
-                sh = [t for t in (a[2], b[2]) if t is not None]
-                shift = (sh[0] + sh[1]) if len(sh) == 2 else (sh[0] if sh else None)
-            cache = (a[0], b[0], a[1], b[1], wt, shift)
-            self.__dict__["_gdm_pw_res"] = cache
-        return cache[4], cache[5]
+
+        def make():
+            def scaled(w, sc):
+                return w if sc is None else w * sc.view(1, -1)
+            wt = torch.cat([scaled(a[0], a[1]), scaled(b[0], b[1])], dim=0).contiguous()
+            sh = [t for t in (a[2], b[2]) if t is not None]
+            return wt, (sh[0] + sh[1]) if len(sh) == 2 else (sh[0] if sh else None)
+        return derived(self, "pw_res", [t for t in a[:3] + b[:3] if t is not None], make)
 
     def forward_segs(self, segs, res=None, act=None):
         """The layer over cat(segs, dim=1) WITHOUT forming the concat (eval: one ops.pointwise launch).  segs: list of

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib, settings
 from ._lib import KnnJob, check
+from .derived import derived
 
 MATCH_BF16X3 = 0
 MATCH_F32 = 1
@@ -1364,13 +1365,8 @@ def _final_weight_t(weight):
     """W^T of the 64 -> 64 `final` weight (the kernels read 64 contiguous scalars per ci), cached ON the weight tensor: it lives and
     dies with it.  (A module-level dict keyed by id(weight) served a NEW tensor that got a dead one's id, address and version the old
     one's transpose: wrong output, found by a test that builds several weights in a row.)"""
-    key = (weight._version, weight.data_ptr())
-    cache = getattr(weight, "_gdm_final_wt", None)
-    if cache is None or cache[0] != key:
-        C = weight.shape[0]
-        cache = (key, weight.detach().reshape(C, C).t().contiguous())
-        weight._gdm_final_wt = cache
-    return cache[1]
+    C = weight.shape[0]
+    return derived(weight, "final_wt", (weight,), lambda: weight.reshape(C, C).t().contiguous())
 
 
 def conv1x1_logsoftmax(x, weight, bias):

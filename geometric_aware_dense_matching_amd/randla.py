@@ -17,7 +17,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, settings
-from .layers import folded_bn, fused_eval, rl_conv2d
+from .derived import derived
+from .layers import folded_bn, fused_eval, layer_deps, rl_conv2d
 
 
 
@@ -47,24 +48,19 @@ class BuildingBlock(nn.Module):
     def _fused_weights(self):
         """Transposed weights + folded BatchNorms of both stages, cached until any parameter changes."""
         convs = (self.mlp1, self.mlp2, self.att_pooling_1.mlp, self.att_pooling_2.mlp)
-        deps = [m.conv.weight for m in convs] + [self.att_pooling_1.fc.weight, self.att_pooling_2.fc.weight]
-        for m in convs:
-            deps += [m.bn.bn.weight, m.bn.bn.bias, m.bn.bn.running_mean, m.bn.bn.running_var]
-        key = tuple((t._version, t.data_ptr()) for t in deps)
-        cache = self.__dict__.get("_gdm_lfa")
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                def wt(conv):
-                    return conv.weight.view(conv.weight.shape[0], -1).t().contiguous()
-                w = dict(w1t=wt(self.mlp1.conv), w2t=wt(self.mlp2.conv), wf1=wt(self.att_pooling_1.fc), wf2=wt(self.att_pooling_2.fc),
-                         wm1=wt(self.att_pooling_1.mlp.conv), wm2=wt(self.att_pooling_2.mlp.conv))
-                w["s1"], w["b1"] = folded_bn(self.mlp1.bn.bn)
-                w["s2"], w["b2"] = folded_bn(self.mlp2.bn.bn)
-                w["sm1"], w["bm1"] = folded_bn(self.att_pooling_1.mlp.bn.bn)
-                w["sm2"], w["bm2"] = folded_bn(self.att_pooling_2.mlp.bn.bn)
-            cache = (key, w)
-            self.__dict__["_gdm_lfa"] = cache
-        return cache[1]
+        deps = sum((layer_deps(m.conv, m.bn.bn) for m in convs), [self.att_pooling_1.fc.weight, self.att_pooling_2.fc.weight])
+
+        def make():
+            def wt(conv):
+                return conv.weight.view(conv.weight.shape[0], -1).t().contiguous()
+            w = dict(w1t=wt(self.mlp1.conv), w2t=wt(self.mlp2.conv), wf1=wt(self.att_pooling_1.fc), wf2=wt(self.att_pooling_2.fc),
+                     wm1=wt(self.att_pooling_1.mlp.conv), wm2=wt(self.att_pooling_2.mlp.conv))
+            w["s1"], w["b1"] = folded_bn(self.mlp1.bn.bn)
+            w["s2"], w["b2"] = folded_bn(self.mlp2.bn.bn)
+            w["sm1"], w["bm1"] = folded_bn(self.att_pooling_1.mlp.bn.bn)
+            w["sm2"], w["bm2"] = folded_bn(self.att_pooling_2.mlp.bn.bn)
+            return w
+        return derived(self, "lfa", deps, make)
 
     def _fusable(self, feature, neigh_idx):
         acts = (self.mlp1, self.mlp2, self.att_pooling_1.mlp, self.att_pooling_2.mlp)

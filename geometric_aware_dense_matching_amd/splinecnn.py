@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops, settings
 from ._lib import check
+from .derived import derived
 from .layers import cached_gemm_weight
 from .synthetic import COLOR_MEAN, COLOR_STD_MESH
 
@@ -79,13 +80,7 @@ class SplineConv(nn.Module):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def _root_t(self):
-        w = self.lin.weight
-        key = (w._version, w.data_ptr())
-        cache = self.__dict__.get("_gdm_root_t")
-        if cache is None or cache[0] != key:
-            cache = (key, w.detach().t().contiguous())
-            self.__dict__["_gdm_root_t"] = cache
-        return cache[1]
+        return derived(self, "root_t", (self.lin.weight,), lambda: self.lin.weight.t().contiguous())
 
     def forward_direct_cm(self, x, rowptr, src, attr, relu):
         """First layer (cin <= 16), result CHANNEL-major f32[1, cout, M]: what the next layer's grouped GEMM / root product and the
@@ -126,16 +121,10 @@ class SplineConv(nn.Module):
         nk = KERNEL_SIZE ** 3
         if self.cin <= 16 and x.is_cuda and not torch.is_grad_enabled():
             # few input channels (first layer, 9 -> 128): messages formed directly, no [M, 125*out] table (524 MB at M = 8192)
-            w = self.lin.weight
-            key = (w._version, w.data_ptr())
-            cache = self.__dict__.get("_gdm_root_t")
-            if cache is None or cache[0] != key:
-                cache = (key, w.detach().t().contiguous())
-                self.__dict__["_gdm_root_t"] = cache
             out = torch.empty((M, self.cout), dtype=torch.float32, device=x.device)
             xc = x.contiguous()
             check(_lib.lib().gdm_spline_direct3_hip(xc.data_ptr(), self.weight.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
-                                                    cache[1].data_ptr(), self.bias.data_ptr(), M, self.cin, self.cout, KERNEL_SIZE, int(relu),
+                                                    self._root_t().data_ptr(), self.bias.data_ptr(), M, self.cin, self.cout, KERNEL_SIZE, int(relu),
                                                     out.data_ptr(), None, None, ops._stream()), "gdm_spline_direct3_hip")
             return out
         if (settings.USE_MFMA_GEMM and settings.USE_GROUPED_SPLINE and pairs is not None and not torch.is_grad_enabled() and x.is_cuda
@@ -147,13 +136,7 @@ class SplineConv(nn.Module):
             xt = x.t().contiguous().unsqueeze(0)                     # [1, cin, M] channel-major: the GEMM's and the root layer's operand
             Y = ops.gemm_grouped(xt, wpk, pairs["rowidx"], pairs["tile_co0"], nk * self.cout)
             if settings.USE_POINTWISE and self.lin.bias is None:
-                w = self.lin.weight
-                key = (w._version, w.data_ptr())
-                cache = self.__dict__.get("_gdm_root_t")
-                if cache is None or cache[0] != key:
-                    cache = (key, w.detach().t().contiguous())
-                    self.__dict__["_gdm_root_t"] = cache
-                root = ops.pointwise([xt], cache[1], point_major=True).view(M, self.cout)      # x @ W_root^T on the own kernel
+                root = ops.pointwise([xt], self._root_t(), point_major=True).view(M, self.cout)      # x @ W_root^T on the own kernel
             else:
                 root = self.lin(x)
             out = torch.empty((M, self.cout), dtype=torch.float32, device=x.device)
@@ -344,12 +327,7 @@ class SplineCNN_Mesh(nn.Module):
         product read and what the final linear reads as concat-free segments -- no transposing copies, no torch.cat, no library GEMM;
         the result f32[128, M] is the layout GeoMatch.forward returns."""
         x0 = self.mesh_graph_x
-        key = (x0._version, x0.data_ptr())
-        cache = self.__dict__.get("_gdm_x0_t")
-        if cache is None or cache[0] != key:
-            cache = (key, x0.detach().t().contiguous().unsqueeze(0))       # [1, 9, M], constant per object
-            self.__dict__["_gdm_x0_t"] = cache
-        segs = [cache[1]]
+        segs = [derived(self, "x0_t", (x0,), lambda: x0.t().contiguous().unsqueeze(0))]       # [1, 9, M], constant per object
         convs = list(self.mesh_convs)
         # each layer's kernel also writes the packed operand of the NEXT layer's grouped GEMM (settings.USE_PACKED_PRODUCERS)
         packed = settings.USE_PACKED_PRODUCERS
@@ -359,12 +337,7 @@ class SplineCNN_Mesh(nn.Module):
             out_t, pk = conv.forward_grouped_cm(segs[-1], rowptr, self._pairs, True, xpk=pk, want_packed=packed and li + 2 < len(convs))
             segs.append(out_t)
         w = self.mesh_final.weight
-        key = (w._version, w.data_ptr())
-        cache = self.mesh_final.__dict__.get("_gdm_wt")
-        if cache is None or cache[0] != key:
-            cache = (key, w.detach().t().contiguous())
-            self.mesh_final.__dict__["_gdm_wt"] = cache
-        out = ops.pointwise(segs, cache[1], None, self.mesh_final.bias)     # [1, 128, M]; eval: dropout is the identity
+        out = ops.pointwise(segs, derived(self.mesh_final, "wt", (w,), lambda: w.t().contiguous()), None, self.mesh_final.bias)     # [1, 128, M]; eval: dropout is the identity
         return out[0]
 
     def forward(self):

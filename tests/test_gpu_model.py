@@ -660,3 +660,57 @@ def test_every_runtime_switch_off_gives_the_same_eval_forward(golden_model):
     finally:
         for n, v in saved.items():
             setattr(settings, n, v)
+
+
+def test_derived_parameter_cache_follows_in_place_updates_and_invalidate():
+    """Every derived tensor (folded BatchNorms, packed / split / transposed weights, the fused heads) is rebuilt when its parameters
+    change: a warm model whose every parameter and BatchNorm statistic was changed in place, and then again after writes through
+    `.data` followed by derived.invalidate(), gives bit for bit what a cold twin loaded from its state_dict gives (own kernels without
+    float atomics: two forwards of one model are equal, asserted here too)."""
+    from geometric_aware_dense_matching_amd import derived, pyramid
+    from geometric_aware_dense_matching_amd.geoMatch import GeoMatch
+    M = 512
+    keys = json.load(open(os.path.join(G, "geomatch_state.json")))
+
+    def cold(state):
+        m = GeoMatch(make_model_cfg(n_mesh_node=M), 1, model_points=synthetic.make_model_points(1, M))
+        missing, unexpected = m.load_state_dict(state, strict=False)
+        assert not unexpected and all(k.startswith("model_emb.") for k in missing)
+        return m.cuda().eval()
+
+    model = cold(synthetic.synthetic_state_dict({k: torch.zeros(v) for k, v in keys.items()}, seed=0))
+    batch = synthetic.make_batch(seed=5, batch=2, n_points=1024)
+    d = _dev_inputs(batch)
+    d.update(pyramid.build_pyramid(pyramid.cloud_from_inputs(d["cld_rgb_nrm"]), d["dpt_xyz"]))
+
+    def forward(m):
+        with torch.no_grad():
+            ep = m(dict(d))
+        return {k: ep[k].clone() for k in ("rgbd", "seg", "mesh")}
+
+    def same(a, b):
+        return {k: torch.equal(a[k], b[k]) for k in a}
+
+    first = forward(model)                                                   # every cache warm
+    g = torch.Generator(device="cuda").manual_seed(0)
+    with torch.no_grad():
+        for name, t in list(model.named_parameters()) + list(model.named_buffers()):
+            if name.endswith("running_var"):
+                t.mul_(1.1)
+            elif name.endswith("running_mean") or isinstance(t, torch.nn.Parameter):
+                t.add_(0.01 * torch.randn(t.shape, generator=g, device="cuda"))
+    second = forward(model)
+    twin = cold(model.state_dict())
+    want = forward(twin)
+    assert same(want, forward(twin)) == dict(rgbd=True, seg=True, mesh=True)
+    assert same(second, want) == dict(rgbd=True, seg=True, mesh=True)
+    assert same(second, first) == dict(rgbd=False, seg=False, mesh=False)
+
+    emb = model.pcd_emb
+    for w in (emb.cnn_ds_stages[0][0].conv1.weight, emb.rndla_ds_stages[0].lfa.mlp1.conv.weight, model.model_emb.mesh_convs[1].weight,
+              model.seg_layer[0].conv.weight, model.feature_encoding_layer[0].conv.weight):
+        w.data.mul_(1.05)                                                    # image trunk, point branch, mesh branch, both heads
+    derived.invalidate(model)
+    third = forward(model)
+    assert same(third, forward(cold(model.state_dict()))) == dict(rgbd=True, seg=True, mesh=True)
+    assert same(third, second) == dict(rgbd=False, seg=False, mesh=False)
