@@ -6,6 +6,10 @@ Sequentials, `conv9`, buffer `mesh`).  The dynamic graph (dgcnn.py:21-56) is reb
 forward: dense negative squared distances by one GEMM (same formula as the reference), row-wise top-k by a
 HIP kernel, edge features cat(x_j - x_i, x_i) by a HIP kernel; the reference's hard-coded
 `torch.device('cuda')` (:39) is gone.
+
+Inference has a second, fused path (`forward(..., fused=True)`, `_DgcnnTrunk._embed_fused`): graphs by `knn_fused` (ops.feature_knn:
+Gram tile and selection in one kernel, no [B,n,n] matrix), every edge stage by one per-point layer + ops.edge_block (no [B,2C,n,k]
+tensor), conv6 .. conv9 by ops.pointwise over segments.  It has no backward and raises in training mode.
 """
 import os
 
@@ -14,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .derived import derived
 from .layers import folded_bn, fused_eval
 from .synthetic import COLOR_MEAN, COLOR_STD_MESH
 
@@ -24,6 +29,12 @@ def knn(x, k):
     xx = torch.sum(x ** 2, dim=1)
     # pairwise_distance = -xx - (-2 * gram) - xx^T is formed inside the top-k kernel (same operations, same order)
     return ops.topk_negdist(gram, xx, k)
+
+
+def knn_fused(feat, k):
+    """The graph of the fused inference path: feat f32[B,C,n] -> idx i32[B,n,k], the same ranking as `knn` with the Gram tile and the
+    selection in one kernel (ops.feature_knn): no [B,n,n] matrix.  The one seam the fused trunk builds its graphs through."""
+    return ops.feature_knn(feat, k)
 
 
 def get_graph_feature(x, k=20, idx=None, dim9=False):
@@ -87,6 +98,56 @@ class _DgcnnTrunk(nn.Module):
         x = self._cba(self.conv8, self._cba(self.conv7, x))
         return self.conv9(self.dp1(x))
 
+    # -- fused inference path: HIP operators only, neither [B,n,n] distances nor [B,2C,n,k] edge tensors --------------------------
+    @staticmethod
+    def _wt(conv):
+        """The weight of a 1x1 convolution transposed to [Cin,Cout], as ops.pointwise reads it."""
+        return derived(conv, "wt", (conv.weight,), lambda: conv.weight.reshape(conv.weight.shape[0], -1).t().contiguous())
+
+    @staticmethod
+    def _edge_wt(conv):
+        """The first convolution of an edge stage, W = [W_a | W_b] over cat(x_j - x_i, x_i), split per point:
+        W cat(x_j - x_i, x_i) = W_a x_j + (W_b - W_a) x_i  ->  the stacked weight [W_a ; W_b - W_a] transposed to [C,128]."""
+        def make():
+            w = conv.weight.reshape(conv.weight.shape[0], -1)
+            c = w.shape[1] // 2
+            return torch.cat((w[:, :c], w[:, c:] - w[:, :c]), dim=0).t().contiguous()
+        return derived(conv, "edge_wt", (conv.weight,), make)
+
+    def _edge_stage(self, x, idx, seq1, seq2, out):
+        """conv (+ conv) of one edge stage and the max over the neighbours -> out f32[B,64,n]; x f32[B,C,n], idx i32[B,n,k]."""
+        pq = ops.pointwise([x], self._edge_wt(seq1[0]), point_major=True)          # [B,n,128]: both halves of the split, one launch
+        s1, t1 = folded_bn(seq1[1])
+        w2 = s2 = t2 = None
+        if seq2 is not None:
+            w2 = seq2[0].weight
+            s2, t2 = folded_bn(seq2[1])
+        return ops.edge_block(pq, idx, s1, t1, w2, s2, t2, float(seq1[2].negative_slope), out=out)
+
+    def _pw(self, seq, segs):
+        scale, shift = folded_bn(seq[1])
+        return ops.pointwise(segs, self._wt(seq[0]), scale, shift, ops.ACT_LEAKY, float(seq[2].negative_slope))
+
+    def _embed_fused(self, x):
+        """`_embed` in eval mode on HIP operators alone (the max over the points excepted): graphs by `knn_fused`, every edge stage by
+        one per-point layer + ops.edge_block, conv6 .. conv9 by ops.pointwise over segments (no cat, no repeat).  No backward."""
+        if self.training:
+            raise RuntimeError("the fused DGCNN path is inference only (it has no backward): call .eval() or pass fused=False")
+        if not x.is_cuda:
+            raise RuntimeError("the fused DGCNN path runs on the GPU (HIP kernels); there is no CPU fallback")
+        x = x.contiguous()
+        B, _, n = x.shape
+        # x1, x2, x3: three contiguous [B,64,n] slices of one allocation, read as segments by conv6 / conv7 (cat(x1, x2, x3) is never formed)
+        x1, x2, x3 = torch.empty((3, B, 64, n), dtype=torch.float32, device=x.device).unbind(0)
+        self._edge_stage(x, knn_fused(x[:, :3], self.k), self.conv1, self.conv2, x1)       # the graph from xyz, the features from all 9 channels
+        self._edge_stage(x1, knn_fused(x1, self.k), self.conv3, self.conv4, x2)
+        self._edge_stage(x2, knn_fused(x2, self.k), self.conv5, None, x3)
+        g = self._pw(self.conv6, [x1, x2, x3]).max(dim=-1, keepdim=True)[0]                 # [B,embed,1]
+        # the global feature is read by every point through an all-zero index: a constant of the shape, made once per trunk
+        everywhere = derived(self, "zero_idx", (), lambda: torch.zeros((B, n), dtype=torch.int32, device=x.device), extra=(B, n, str(x.device)))
+        y = self._pw(self.conv8, [self._pw(self.conv7, [(g, everywhere), x1, x2, x3])])
+        return ops.pointwise([y], self._wt(self.conv9))                                     # dropout is the identity in eval
+
 
 class DgcnnPcdEmb(_DgcnnTrunk):
     def __init__(self, args):
@@ -98,8 +159,8 @@ class DgcnnPcdEmb(_DgcnnTrunk):
         self.dropout = args.get("dropout", 0.1)
         self._build(self.embed_dim, self.feat_dim, self.dropout)
 
-    def forward(self, x):
-        return self._embed(x)
+    def forward(self, x, fused=False):
+        return self._embed_fused(x) if fused else self._embed(x)
 
 
 class DgcnnMeshEmb(_DgcnnTrunk):
@@ -133,5 +194,8 @@ class DgcnnMeshEmb(_DgcnnTrunk):
     def xyz(self):
         return self.mesh[0, :3].t()
 
-    def forward(self):
+    def forward(self, fused=False):
+        if fused:
+            # the buffer is a transposed view of the loaded rows: its channel-major copy is made once, not per step
+            return self._embed_fused(derived(self, "mesh_cm", (self.mesh,), lambda: self.mesh.contiguous()))
         return self._embed(self.mesh)

@@ -6,6 +6,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import ops, settings
 from .dgcnn import DgcnnMeshEmb, DgcnnPcdEmb
 from .layers import PtSeq, pt_conv1d
 from .loss import AutomaticWeightedLoss, CircleLoss, FocalLoss
@@ -38,7 +39,6 @@ class GeoMatch(nn.Module):
             pdist(g, v) < positive_r / 1000 * z_i(v), z_i(v) = depth of v posed by the item's RT (:62-67): the radius depends on the
             item AND the vertex, so the positive tables are built per item (ops.circle_nbr_items, one launch for the batch) and the
             fused kernels index them by (item, g) -- ops.circle_match(..., pad="e0")."""
-        from . import ops
         if not rgbd_feature.is_cuda:
             raise RuntimeError("GeoMatch (DGCNN) training matching loss runs on the GPU (HIP kernels); there is no CPU fallback")
         B, D, N = rgbd_feature.shape
@@ -64,11 +64,21 @@ class GeoMatch(nn.Module):
         per_item = per_item[item_ok] / counts[item_ok].to(torch.float32)
         return per_item.mean()
 
-    def forward(self, inputs, end_points=None):
+    def forward(self, inputs, end_points=None, fused=False, defer_seg=False):
+        """fused: both trunks on the fused inference path (dgcnn._DgcnnTrunk._embed_fused; eval only).  defer_seg is accepted and
+        ignored, as in geoMatch.GeoMatch: infer.pipeline_step passes it to every model."""
         if not end_points:
             end_points = {}
-        rgbd_emb = self.pcd_emb(inputs["cld_rgb_nrm"])
-        mesh_features = self.model_emb()
+        x = inputs["cld_rgb_nrm"]
+        if fused and settings.USE_SIDE_STREAMS and "mesh" in settings.SIDE_PARTS and (not self.training) and x.is_cuda and not torch.is_grad_enabled():
+            # the mesh trunk depends on nothing in `inputs`: it runs on a side stream beside the cloud trunk
+            with ops.fork(x.device, 1) as f:                 # reads module buffers / parameters only (never freed mid-step)
+                mesh_features = self.model_emb(fused=True)
+            rgbd_emb = self.pcd_emb(x, fused=True)
+            f.join(mesh_features)
+        else:
+            rgbd_emb = self.pcd_emb(x, fused=fused)
+            mesh_features = self.model_emb(fused=fused)
         rgbd_features = self.feature_encoding_layer(rgbd_emb)
         rgbd_normalized = self.normalize_feature_layer(rgbd_features)
         rgbd_emb = rgbd_emb + rgbd_normalized

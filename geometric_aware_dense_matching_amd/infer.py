@@ -54,10 +54,13 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
     prec = _PREC[precision]
     d = dict(inputs)
     pyr = None
-    if "cld_nei_idx0" not in d:
-        pyr = pyramid.build_pyramid(pyramid.cloud_view(d["cld_rgb_nrm"]), d["dpt_xyz"], overlap=True)
-        d.update(pyr)
-    ep = model(d, defer_seg=True)
+    if not getattr(model, "needs_pyramid", True):
+        ep = model(d, fused=True, defer_seg=True)          # the DGCNN variant builds its graphs inside the trunks: no pyramid
+    else:
+        if "cld_nei_idx0" not in d:
+            pyr = pyramid.build_pyramid(pyramid.cloud_view(d["cld_rgb_nrm"]), d["dpt_xyz"], overlap=True)
+            d.update(pyr)
+        ep = model(d, defer_seg=True)
     B, _, N = ep["rgbd"].shape
     M = ep["mesh"].shape[-1]
     mask, count, bi, bs = matching.match_tail(ep, B, N, M, prec)

@@ -397,6 +397,63 @@ def topk_negdist(gram, xx, k):
     return idx
 
 
+def feature_knn(x, k, return_values=False, splits=0):
+    """x f32[B,C,n] channel-major -> idx i32[B,n,k] (and val f32[B,n,k]) of the k largest dgcnn.py:22-25 scores per row, Gram tile and
+    selection in one kernel (include/gdm.h gdm_feature_knn_hip): no [B,n,n] matrix, the only workspace is O(B n).  Score
+    descending, ties by ascending column, short rows filled with index 0.  A channel slice `t[:, :c]` of a contiguous tensor is read
+    in place (its batch stride is passed on).  splits (1, 2, 4; 0 = chosen from the shape): how many waves share a row group's columns --
+    a launch parameter only, the result does not depend on it.  Inference only."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("x must be a CUDA (HIP) tensor: the geoMatch ops have no CPU fallback")
+    if x.dtype != torch.float32 or x.dim() != 3:
+        raise TypeError("x must be f32[B,C,n], got %s %s" % (x.dtype, tuple(x.shape)))
+    B, C, n = x.shape
+    if not 1 <= k <= 32:
+        raise ValueError("feature_knn: k=%d not in [1, 32]" % k)
+    if x.stride(2) != 1 or x.stride(1) != n or (B > 1 and x.stride(0) < C * n):
+        x = x.contiguous()
+    bstride = x.stride(0) if B > 1 else C * n
+    nbytes = _lib.lib().gdm_feature_knn_workspace_bytes(B, n)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)          # xx f32[B,n] + one flag per 32 rows
+    idx = torch.empty((B, n, k), dtype=torch.int32, device=x.device)
+    val = torch.empty((B, n, k), dtype=torch.float32, device=x.device) if return_values else None
+    check(_lib.lib().gdm_feature_knn_hip(x.data_ptr(), bstride, B, C, n, k, int(splits), ws.data_ptr(), nbytes, idx.data_ptr(),
+                                         val.data_ptr() if return_values else None, _stream()), "gdm_feature_knn_hip")
+    return (idx, val) if return_values else idx
+
+
+def edge_block(pq, idx, scale1, shift1, w2=None, scale2=None, shift2=None, slope=0.2, out=None, out_c0=0):
+    """One edge-convolution stage without the edge tensor (include/gdm.h gdm_edge_block_hip), inference only.
+    pq f32[B,n,128] point-major: the stage's first convolution applied per point, [W_a ; W_b - W_a] x; idx int[B,n,K], K <= 32;
+    scale1 / shift1 f32[64]: the first folded BatchNorm; w2 f32[64,64(,1,1)], scale2 / shift2: the second convolution and its
+    BatchNorm, or None for a single-convolution stage.  Returns f32[B,64,n] = max over the neighbours of the last activation, or
+    writes channels [out_c0, out_c0 + 64) of `out` f32[B,outC,n] and returns it."""
+    pq = _dev(pq, torch.float32, "pq")
+    idx = _idx32(idx, "idx")
+    B, n, c2 = pq.shape
+    if c2 != 128 or idx.dim() != 3 or tuple(idx.shape[:2]) != (B, n):
+        raise ValueError("edge_block: pq must be [B,n,128] and idx [B,n,K], got %s and %s" % (tuple(pq.shape), tuple(idx.shape)))
+    K = idx.shape[2]
+    scale1, shift1 = _dev(scale1, torch.float32, "scale1"), _dev(shift1, torch.float32, "shift1")
+    if (w2 is None) != (scale2 is None) or (w2 is None) != (shift2 is None):
+        raise ValueError("edge_block: w2, scale2 and shift2 go together")
+    if w2 is not None:
+        w2, scale2, shift2 = _dev(w2, torch.float32, "w2"), _dev(scale2, torch.float32, "scale2"), _dev(shift2, torch.float32, "shift2")
+        if w2.numel() != 64 * 64 or scale2.numel() != 64 or shift2.numel() != 64:
+            raise ValueError("edge_block: the second convolution is 64 -> 64")
+    if scale1.numel() != 64 or shift1.numel() != 64:
+        raise ValueError("edge_block: scale1 / shift1 must hold 64 channels")
+    if out is None:
+        out = torch.empty((B, 64, n), dtype=torch.float32, device=pq.device)
+    elif (not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 3 or out.shape[0] != B
+          or out.shape[2] != n):
+        raise ValueError("edge_block: out must be a contiguous f32 [B,outC,%d] tensor" % n)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    check(_lib.lib().gdm_edge_block_hip(pq.data_ptr(), idx.data_ptr(), scale1.data_ptr(), shift1.data_ptr(), ptr(w2), ptr(scale2), ptr(shift2),
+                                        float(slope), B, n, K, out.data_ptr(), out.shape[1], int(out_c0), _stream()), "gdm_edge_block_hip")
+    return out
+
+
 def affine_act_maxk(x, scale, shift, act=0, slope=0.0):
     """max over the last (neighbour) dimension of act(scale[c]*x + shift[c]); x f32[B,C,n,K] -> f32[B,C,n].  Inference only."""
     x = _dev(x, torch.float32, "x")
@@ -650,7 +707,7 @@ def _pw_seg(spec, B, name):
 def pointwise(segs, wt, scale=None, shift=None, act=ACT_NONE, slope=0.0, point_major=False, out=None, out_c0=0, w_rowmajor=False):
     """One per-point (1x1) layer in one launch (include/gdm.h gdm_pointwise2_hip), inference only:
         y[b,:,i] = act(scale * (W . cat(segs)[b,:,i]) + shift)
-    segs: a list of one to three of  x f32[B,C,n(,1)]  or  (x f32[B,C,n_src(,1)], idx int[B,n(,1)])  -- the concat along channels
+    segs: a list of one to four (three when the layer has fewer than 32 input channels) of  x f32[B,C,n(,1)]  or  (x f32[B,C,n_src(,1)], idx int[B,n(,1)])  -- the concat along channels
     is never formed, an indexed segment is read through its index (nearest-neighbour interpolation folded into the load).
     wt f32[K,Cout]: the layer's weight TRANSPOSED (K = total input channels); w_rowmajor: wt is f32[Cout,K] instead, the weight as an
     nn.Conv1d / nn.Conv2d holds it (the training path: no transposed copy of a weight that changes every step).

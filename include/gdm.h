@@ -229,6 +229,27 @@ int gdm_topk_rows_hip(const float* score, long rows, int n, int K, int32_t* idx,
 int gdm_topk_negdist_hip(const float* gram, const float* xx, int B, int n, int K, int32_t* idx, void* stream);
 int gdm_edge_feature_hip(const float* x, const int32_t* idx, int B, int C, int n, int K, float* out, void* stream);
 int gdm_edge_feature_bwd_hip(const float* grad_out, const int32_t* idx, int B, int C, int n, int K, float* grad_x, void* stream);
+/* The fused inference path of the variant: neither the [B,n,n] distances nor the [B,2C,n,K] edge tensor exist.
+ * feature_knn (dgcnn.py:21-27 as ONE operator): x f32[B,C,n] channel-major (item b at x + b * x_bstride, rows contiguous) ->
+ * idx i32[B,n,K], val f32[B,n,K] or NULL, of the K largest  ((-xx[c]) - (-2 g[r][c])) - xx[r]  per row r, g = x^T x with exact fp32
+ * products accumulated in fp32 (fp32 MFMA), xx[c] = sum_ch x[ch][c]^2.  Descending score, ties by ascending column, a row with fewer
+ * than K candidates is filled with index 0.  The only workspace is O(B n): xx and one flag per 32 rows (gdm_feature_knn_workspace_bytes);
+ * Gram tiles live in registers.  1 <= K <= 32, C <= 128 (a workgroup keeps all channels of its rows in LDS), C * n < 2^29.
+ * splits: over how many waves a row group's columns are divided (1, 2 or 4; their lists are merged through LDS), 0 = chosen from
+ * the number of workgroups so that one large item still fills the chip.  The result does not depend on it.
+ * Deterministic (no atomics on floats; the result does not depend on scheduling). */
+size_t gdm_feature_knn_workspace_bytes(int B, int n);
+int gdm_feature_knn_hip(const float* x, long x_bstride, int B, int C, int n, int K, int splits, void* ws, size_t ws_bytes, int32_t* idx,
+                        float* val, void* stream);
+/* edge_block: one edge-convolution stage (dgcnn.py:108-120: get_graph_feature -> conv -> BN -> LeakyReLU [-> conv -> BN -> LeakyReLU]
+ * -> max over the neighbours) from the per-point products of its first convolution: pq f32[B,n,128] point-major, columns 0..63 =
+ * W_a x, 64..127 = (W_b - W_a) x for W = [W_a | W_b] (W cat(x_j - x_i, x_i) = W_a x_j + (W_b - W_a) x_i).  Per point i:
+ *   out[b, out_c0 + c, i] = max_k act2(act1(scale1 (pq[idx[b,i,k], 0:64] + pq[i, 64:128]) + shift1)),   act = LeakyReLU(slope),
+ *   act2(h) = LeakyReLU(scale2 (w2 h) + shift2) with w2 f32[64,64] as the convolution holds it, or the identity when w2, scale2 and
+ * shift2 are NULL (the single-convolution stage).  out f32[B,out_C,n]; only channels [out_c0, out_c0 + 64) are written.
+ * idx i32[B,n,K], clamped to [0, n); 1 <= K <= 32.  pq, scale1, shift1 and w2 must be 16-byte aligned. */
+int gdm_edge_block_hip(const float* pq, const int32_t* idx, const float* scale1, const float* shift1, const float* w2, const float* scale2,
+                       const float* shift2, float slope, int B, int n, int K, float* out, int out_C, int out_c0, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Fused circle loss rows for the training matching (models/geoMatch.py:55-83 matching_loss,
