@@ -85,6 +85,11 @@ SIGNATURES = {
     "gdm_feature_knn_workspace_bytes": (_sz, [_i, _i]),
     "gdm_feature_knn_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "gdm_edge_block_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _i, _i, _vp]),
+    "gdm_edge_train_groups": (ctypes.c_long, [_i, _i]),
+    "gdm_edge_stats_hip": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp]),
+    "gdm_edge_bwd_reduce_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gdm_edge_bwd_mid_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_edge_bwd_scatter_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gdm_circle_rows_fwd_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "gdm_circle_rows_bwd_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "gdm_circle_match_rows_bytes": (_sz, [_i]),

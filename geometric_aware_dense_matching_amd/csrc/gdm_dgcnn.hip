@@ -658,6 +658,412 @@ __global__ __launch_bounds__(256) void edge_block2_kernel(const float* __restric
     eb_store_tile(outs, out, b, out_C, out_c0, n, i0);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// edge_block in TRAINING mode: batch statistics over all B n K edges and a full backward, every pass recomputing its edges from pq, idx
+// and per-channel numbers -- no buffer of O(B n K C) in either direction.  st f32[4][64] per BatchNorm = (scale = gamma rstd |
+// shift = beta - mean scale | mean | rstd), cf f32[2][64] = (dbeta / E | dgamma / E).  Per-channel sums leave a workgroup as one fp64
+// pair per channel (part[wg][64][2]); the caller folds the workgroups in fp64.
+//   one convolution   edge_train1_kernel   lane = channel, a wave per point
+//   two convolutions  edge_train2_kernel   the MFMA layout of edge_block2_kernel: a wave takes four points, 16 edges per tile
+// Backward of the second convolution, per 16-edge tile of a wave: y1 and dy2 go through a 16 x 64 LDS tile each, because every product
+// wants them in the other MFMA role than the one they were produced in (dy2: C/D of the forward product -> A of dh1 = dy2 W2;
+// y1: A of the forward product -> the C/D positions, where it is the B operand of dW2 += dy2^T h1 and the mask / y_hat of dz1).
+constexpr int ET_LD = 68;                   // 16-byte aligned rows, four banks apart
+enum { ET_STATS = 0, ET_REDUCE = 1, ET_MID = 2, ET_SCATTER = 3 };
+
+// the workgroup's 64 channels x 64 points of go[b, c, i0 + pt] into LDS (rows along the points: coalesced)
+__device__ __forceinline__ void et_load_tile(float* gs, const float* __restrict__ go, int b, int n, int i0)
+{
+    const int pt = threadIdx.x & 63, cq = threadIdx.x >> 6;
+    for (int c = cq; c < 64; c += 4) gs[c * EB_LDO + pt] = i0 + pt < n ? go[((long)b * 64 + c) * n + i0 + pt] : 0.f;
+}
+
+// red[wave][channel][2] -> part[wg][channel][2]
+__device__ __forceinline__ void et_store_partials(double (*red)[64][2], double* __restrict__ part)
+{
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const long wg = (long)blockIdx.y * gridDim.x + blockIdx.x;
+        const int c = threadIdx.x;
+        part[(wg * 64 + c) * 2] = (red[0][c][0] + red[1][c][0]) + (red[2][c][0] + red[3][c][0]);
+        part[(wg * 64 + c) * 2 + 1] = (red[0][c][1] + red[1][c][1]) + (red[2][c][1] + red[3][c][1]);
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void edge_train1_kernel(const float* __restrict__ pq, const int32_t* __restrict__ idx, const float* __restrict__ st1,
+                                                          const float* __restrict__ cf1, float slope, int n, int K, const float* __restrict__ go,
+                                                          uint8_t* __restrict__ amax, double* __restrict__ part, float* __restrict__ dpq)
+{
+    __shared__ float gs[64 * EB_LDO];
+    __shared__ double red[4][64][2];
+    const int b = blockIdx.y, i0 = blockIdx.x * EB_PTS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;             // lane = channel
+    float sc = 1.f, sh = 0.f, mu = 0.f, rs = 1.f, c0 = 0.f, c1 = 0.f;
+    if (MODE != ET_STATS) {
+        sc = st1[lane], sh = st1[64 + lane], mu = st1[128 + lane], rs = st1[192 + lane];
+        et_load_tile(gs, go, b, n, i0);
+        __syncthreads();
+    }
+    if (MODE == ET_SCATTER) c0 = cf1[lane], c1 = cf1[64 + lane];
+    const float* pqb = pq + (long)b * n * 128;
+    const int32_t* ib = idx + (long)b * n * K;
+    double d0 = 0.0, d1 = 0.0;
+    for (int p = 0; p < 16; ++p) {
+        const int pl = wave * 16 + p, i = i0 + pl;
+        if (i >= n) break;                                                  // uniform over the wave
+        const float q = pqb[(long)i * 128 + 64 + lane];
+        if (MODE == ET_STATS) {
+            float s0 = 0.f, s1 = 0.f;                                       // fp32 over the K edges of a point, fp64 above
+            for (int k = 0; k < K; ++k) {
+                const int j = min(max(ib[(long)i * K + k], 0), n - 1);
+                const float y = pqb[(long)j * 128 + lane] + q;
+                s0 += y;
+                s1 = fmaf(y, y, s1);
+            }
+            d0 += (double)s0;
+            d1 += (double)s1;
+        } else if (MODE == ET_REDUCE) {
+            float hb = -INFINITY, yb = 0.f;
+            int kb = 0;
+            for (int k = 0; k < K; ++k) {
+                const int j = min(max(ib[(long)i * K + k], 0), n - 1);
+                const float y = pqb[(long)j * 128 + lane] + q;
+                const float h = eb_lrelu(sc * y + sh, slope);
+                if (h > hb) hb = h, yb = y, kb = k;                         // strict: the first arg-max
+            }
+            const float dz = gs[lane * EB_LDO + pl] * (sc * yb + sh > 0.f ? 1.f : slope);
+            d0 += (double)dz;
+            d1 += (double)(dz * ((yb - mu) * rs));
+            amax[((long)b * n + i) * 64 + lane] = (uint8_t)kb;
+        } else {
+            const int a = amax[((long)b * n + i) * 64 + lane];
+            const float g = gs[lane * EB_LDO + pl];
+            float qs = 0.f;
+            for (int k = 0; k < K; ++k) {
+                const int j = min(max(ib[(long)i * K + k], 0), n - 1);
+                const float y = pqb[(long)j * 128 + lane] + q;
+                const float dz = k == a ? g * (sc * y + sh > 0.f ? 1.f : slope) : 0.f;
+                const float dy = sc * (dz - c0 - (y - mu) * rs * c1);
+                atomicAdd(&dpq[((long)b * n + j) * 128 + lane], dy);        // a neighbour's row: 256 contiguous bytes per wave
+                qs += dy;
+            }
+            dpq[((long)b * n + i) * 128 + 64 + lane] = qs;
+        }
+    }
+    if (MODE != ET_SCATTER) {
+        red[wave][lane][0] = d0;
+        red[wave][lane][1] = d1;
+        et_store_partials(red, part);
+    }
+}
+
+__device__ __forceinline__ void et_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void edge_train2_kernel(const float* __restrict__ pq, const int32_t* __restrict__ idx, const float* __restrict__ st1,
+                                                          const float* __restrict__ w2, const float* __restrict__ st2, const float* __restrict__ cf1,
+                                                          const float* __restrict__ cf2, float slope, int n, int K, const float* __restrict__ go,
+                                                          uint8_t* __restrict__ amax, double* __restrict__ part, float* __restrict__ dwslab,
+                                                          float* __restrict__ dpq)
+{
+    constexpr bool BWD = MODE == ET_MID || MODE == ET_SCATTER;
+    __shared__ float gs[MODE == ET_STATS ? 1 : 64 * EB_LDO];
+    __shared__ __attribute__((aligned(16))) float tiles[BWD ? 4 * 2 * 16 * ET_LD : 4];
+    __shared__ double red[4][64][2];
+    const int b = blockIdx.y, i0 = blockIdx.x * EB_PTS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lq = lane >> 4, lr = lane & 15;
+    float wf[4][16], sc1[16], sh1[16], sc2[4], sh2[4], mu2[4], rs2[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const float4 a = *reinterpret_cast<const float4*>(st1 + 16 * lq + 4 * m);
+        const float4 c = *reinterpret_cast<const float4*>(st1 + 64 + 16 * lq + 4 * m);
+        sc1[4 * m] = a.x, sc1[4 * m + 1] = a.y, sc1[4 * m + 2] = a.z, sc1[4 * m + 3] = a.w;
+        sh1[4 * m] = c.x, sh1[4 * m + 1] = c.y, sh1[4 * m + 2] = c.z, sh1[4 * m + 3] = c.w;
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        const int c = 16 * jj + lr;
+        sc2[jj] = MODE == ET_STATS ? 1.f : st2[c];
+        sh2[jj] = MODE == ET_STATS ? 0.f : st2[64 + c];
+        mu2[jj] = MODE == ET_STATS ? 0.f : st2[128 + c];
+        rs2[jj] = MODE == ET_STATS ? 1.f : st2[192 + c];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const float4 w = *reinterpret_cast<const float4*>(w2 + c * 64 + 16 * lq + 4 * m);                   // W2[out 16 jj + lr][in 16 lq + 4 m ..]
+            wf[jj][4 * m] = w.x, wf[jj][4 * m + 1] = w.y, wf[jj][4 * m + 2] = w.z, wf[jj][4 * m + 3] = w.w;
+        }
+    }
+    // backward only: W2 in the B role of dh1 = dy2 W2 (step s contracts output channel 16 lq + s), the first BatchNorm and the
+    // coefficients at the C/D channels 16 jj + lr
+    float wtf[BWD ? 4 : 1][16], sc1c[4], sh1c[4], mu1c[4], rs1c[4], c20[4], c21[4], c10[4], c11[4];
+    if (BWD) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const int c = 16 * jj + lr;
+            sc1c[jj] = st1[c], sh1c[jj] = st1[64 + c], mu1c[jj] = st1[128 + c], rs1c[jj] = st1[192 + c];
+            c20[jj] = cf2[c], c21[jj] = cf2[64 + c];
+            c10[jj] = MODE == ET_SCATTER ? cf1[c] : 0.f;
+            c11[jj] = MODE == ET_SCATTER ? cf1[64 + c] : 0.f;
+#pragma unroll
+            for (int s = 0; s < 16; ++s) wtf[jj][s] = w2[(16 * lq + s) * 64 + c];
+        }
+    }
+    if (MODE != ET_STATS) {
+        et_load_tile(gs, go, b, n, i0);
+        __syncthreads();
+    }
+    float* ys = tiles + wave * (2 * 16 * ET_LD);                            // this wave's y1 tile, then its dy2 (later dy1) tile
+    float* ds = ys + 16 * ET_LD;
+    fk_f32x4 dwacc[MODE == ET_MID ? 4 : 1][MODE == ET_MID ? 4 : 1];
+    if (MODE == ET_MID) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int bb = 0; bb < 4; ++bb) dwacc[a][bb] = fk_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    double d0[4] = {0.0, 0.0, 0.0, 0.0}, d1[4] = {0.0, 0.0, 0.0, 0.0};
+    const float* pqb = pq + (long)b * n * 128;
+    const int32_t* ib = idx + (long)b * n * K;
+    for (int t = 0; t < 4; ++t) {
+        const int pbase = wave * 16 + 4 * t, ibase = i0 + pbase;
+        const int np = min(4, n - ibase);                                   // uniform over the wave
+        if (np <= 0) break;
+        const int E = np * K;
+        // per point P and C/D channel jj: the incoming gradient and the arg-max (backward), or the running arg-max (ET_REDUCE)
+        float gP[4][4], hb[4][4], yb[4][4];
+        int aP[4][4];
+        if (MODE != ET_STATS) {
+#pragma unroll
+            for (int P = 0; P < 4; ++P)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    gP[P][jj] = gs[(16 * jj + lr) * EB_LDO + pbase + P];
+                    hb[P][jj] = -INFINITY, yb[P][jj] = 0.f;
+                    aP[P][jj] = (BWD && P < np) ? (int)amax[((long)b * n + ibase + P) * 64 + 16 * jj + lr] : 0;
+                }
+        }
+        float qs[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int e0 = 0; e0 < E; e0 += 16) {
+            const int eg = e0 + lr;
+            const bool ev = eg < E;                                         // rows past the last edge contribute zeros and are masked below
+            const int egc = ev ? eg : 0;
+            const int p = egc / K, k = egc - p * K;
+            const long i = ibase + p;
+            const int j = min(max(ib[i * K + k], 0), n - 1);
+            const float4* pr = reinterpret_cast<const float4*>(pqb + (long)j * 128 + 16 * lq);
+            const float4* qr = reinterpret_cast<const float4*>(pqb + i * 128 + 64 + 16 * lq);
+            float h[16];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const float4 pv = pr[m], qv = qr[m];
+                const float y0 = pv.x + qv.x, y1 = pv.y + qv.y, y2 = pv.z + qv.z, y3 = pv.w + qv.w;
+                h[4 * m] = ev ? eb_lrelu(sc1[4 * m] * y0 + sh1[4 * m], slope) : 0.f;
+                h[4 * m + 1] = ev ? eb_lrelu(sc1[4 * m + 1] * y1 + sh1[4 * m + 1], slope) : 0.f;
+                h[4 * m + 2] = ev ? eb_lrelu(sc1[4 * m + 2] * y2 + sh1[4 * m + 2], slope) : 0.f;
+                h[4 * m + 3] = ev ? eb_lrelu(sc1[4 * m + 3] * y3 + sh1[4 * m + 3], slope) : 0.f;
+                if (BWD) *reinterpret_cast<float4*>(ys + lr * ET_LD + 16 * lq + 4 * m) = make_float4(y0, y1, y2, y3);
+            }
+            fk_f32x4 acc[4];
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) acc[jj] = fk_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) acc[jj] = __builtin_amdgcn_mfma_f32_16x16x4f32(h[s], wf[jj][s], acc[jj], 0, 0, 0);
+            // C/D layout: acc[jj][r] = edge e0 + 4 lq + r, channel 16 jj + lr
+            if (MODE == ET_STATS) {
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (e0 + 4 * lq + r < E) {
+                            s0 += acc[jj][r];
+                            s1 = fmaf(acc[jj][r], acc[jj][r], s1);
+                        }
+                    d0[jj] += (double)s0;
+                    d1[jj] += (double)s1;
+                }
+            } else if (MODE == ET_REDUCE) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ed = e0 + 4 * lq + r;
+                    const int pp = ed < E ? (ed >= K) + (ed >= 2 * K) + (ed >= 3 * K) : -1;
+                    const int kk = ed - pp * K;
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        const float v = eb_lrelu(sc2[jj] * acc[jj][r] + sh2[jj], slope);
+#pragma unroll
+                        for (int P = 0; P < 4; ++P) {
+                            const bool up = pp == P && v > hb[P][jj];       // edges ascend within a lane: strict keeps the first
+                            hb[P][jj] = up ? v : hb[P][jj];
+                            yb[P][jj] = up ? acc[jj][r] : yb[P][jj];
+                            aP[P][jj] = up ? kk : aP[P][jj];
+                        }
+                    }
+                }
+            } else {
+                et_wave_sync();                                             // (the previous tile's reads of ds are done)
+                float dy2[4][4];                                            // [jj][r]
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ed = e0 + 4 * lq + r;
+                    const int pp = ed < E ? (ed >= K) + (ed >= 2 * K) + (ed >= 3 * K) : -1;
+                    const int kk = ed - pp * K;
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        float g = 0.f;
+                        int a = -1;
+#pragma unroll
+                        for (int P = 0; P < 4; ++P) {
+                            g = pp == P ? gP[P][jj] : g;
+                            a = pp == P ? aP[P][jj] : a;
+                        }
+                        const float y2v = acc[jj][r];
+                        const float dz2 = kk == a ? g * (sc2[jj] * y2v + sh2[jj] > 0.f ? 1.f : slope) : 0.f;
+                        dy2[jj][r] = pp >= 0 ? sc2[jj] * (dz2 - c20[jj] - (y2v - mu2[jj]) * rs2[jj] * c21[jj]) : 0.f;
+                        ds[(4 * lq + r) * ET_LD + 16 * jj + lr] = dy2[jj][r];
+                    }
+                }
+                et_wave_sync();
+                // y1 at the C/D positions, dy2 in the A role
+                float yc[4][4], dsa[16];
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) yc[jj][r] = ys[(4 * lq + r) * ET_LD + 16 * jj + lr];
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const float4 v = *reinterpret_cast<const float4*>(ds + lr * ET_LD + 16 * lq + 4 * m);
+                    dsa[4 * m] = v.x, dsa[4 * m + 1] = v.y, dsa[4 * m + 2] = v.z, dsa[4 * m + 3] = v.w;
+                }
+                if (MODE == ET_MID) {
+                    // dW2[out][in] += dy2[e][out] h1[e][in], the four edges 4 lq + r (lq = 0..3) of step r as the contraction
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float hc[4];
+#pragma unroll
+                        for (int bb = 0; bb < 4; ++bb) hc[bb] = eb_lrelu(sc1c[bb] * yc[bb][r] + sh1c[bb], slope);
+#pragma unroll
+                        for (int a = 0; a < 4; ++a)
+#pragma unroll
+                            for (int bb = 0; bb < 4; ++bb)
+                                dwacc[a][bb] = __builtin_amdgcn_mfma_f32_16x16x4f32(dy2[a][r], hc[bb], dwacc[a][bb], 0, 0, 0);
+                    }
+                }
+                fk_f32x4 dh[4];
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) dh[jj] = fk_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < 16; ++s)
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) dh[jj] = __builtin_amdgcn_mfma_f32_16x16x4f32(dsa[s], wtf[jj][s], dh[jj], 0, 0, 0);
+                // dh[jj][r] = edge e0 + 4 lq + r, input channel 16 jj + lr
+                if (MODE == ET_SCATTER) et_wave_sync();                     // every lane has read dy2: the tile takes dy1
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const bool valid = e0 + 4 * lq + r < E;
+                        const float y = yc[jj][r];
+                        const float dz1 = valid ? dh[jj][r] * (sc1c[jj] * y + sh1c[jj] > 0.f ? 1.f : slope) : 0.f;
+                        const float yh = (y - mu1c[jj]) * rs1c[jj];
+                        if (MODE == ET_MID) {
+                            s0 += dz1;
+                            s1 = fmaf(dz1, yh, s1);
+                        } else {
+                            ds[(4 * lq + r) * ET_LD + 16 * jj + lr] = valid ? sc1c[jj] * (dz1 - c10[jj] - yh * c11[jj]) : 0.f;
+                        }
+                    }
+                    d0[jj] += (double)s0;
+                    d1[jj] += (double)s1;
+                }
+                if (MODE == ET_SCATTER) {
+                    et_wave_sync();
+                    // lane = channel: a neighbour's row takes one 256-byte atomic per edge, dQ of the wave's own points is summed here
+                    const int ne = min(16, E - e0);
+                    for (int e = 0; e < ne; ++e) {
+                        const int je = __shfl(j, e, 64);                    // lane e (lq = 0, lr = e) holds the edge's neighbour
+                        const float v = ds[e * ET_LD + lane];
+                        atomicAdd(&dpq[((long)b * n + je) * 128 + lane], v);
+                        const int ed = e0 + e;
+                        const int pp = (ed >= K) + (ed >= 2 * K) + (ed >= 3 * K);
+#pragma unroll
+                        for (int P = 0; P < 4; ++P) qs[P] += pp == P ? v : 0.f;
+                    }
+                }
+            }
+        }
+        if (MODE == ET_REDUCE) {
+#pragma unroll
+            for (int P = 0; P < 4; ++P)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    float hv = hb[P][jj], yv = yb[P][jj];
+                    int kv = aP[P][jj];
+#pragma unroll
+                    for (int m = 16; m <= 32; m <<= 1) {
+                        const float ho = __shfl_xor(hv, m, 64), yo = __shfl_xor(yv, m, 64);
+                        const int ko = __shfl_xor(kv, m, 64);
+                        if (ho > hv || (ho == hv && ko < kv)) hv = ho, yv = yo, kv = ko;
+                    }
+                    if (lq == 0 && P < np) {
+                        const float dz = gP[P][jj] * (sc2[jj] * yv + sh2[jj] > 0.f ? 1.f : slope);
+                        d0[jj] += (double)dz;
+                        d1[jj] += (double)(dz * ((yv - mu2[jj]) * rs2[jj]));
+                        amax[((long)b * n + ibase + P) * 64 + 16 * jj + lr] = (uint8_t)kv;
+                    }
+                }
+        }
+        if (MODE == ET_SCATTER) {
+#pragma unroll
+            for (int P = 0; P < 4; ++P)
+                if (P < np) dpq[((long)b * n + ibase + P) * 128 + 64 + lane] = qs[P];
+        }
+    }
+    if (MODE != ET_SCATTER) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            double a = d0[jj], c = d1[jj];
+            a += __shfl_xor(a, 16, 64), c += __shfl_xor(c, 16, 64);
+            a += __shfl_xor(a, 32, 64), c += __shfl_xor(c, 32, 64);
+            if (lq == 0) {
+                red[wave][16 * jj + lr][0] = a;
+                red[wave][16 * jj + lr][1] = c;
+            }
+        }
+        et_store_partials(red, part);
+    }
+    if (MODE == ET_MID) {
+        // the four waves' dW2 tiles are added in wave order through LDS (over the edge tiles, which no wave reads any more) and leave as
+        // one 64 x 64 slab per workgroup: dwacc[a][bb][r] = output channel 16 a + 4 lq + r, input channel 16 bb + lr
+        __syncthreads();
+        for (int w = 0; w < 4; ++w) {
+            if (wave == w) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float* slot = tiles + (16 * a + 4 * lq + r) * 64 + 16 * bb + lr;
+                            *slot = w == 0 ? dwacc[a][bb][r] : *slot + dwacc[a][bb][r];
+                        }
+            }
+            __syncthreads();
+        }
+        const long wg = (long)blockIdx.y * gridDim.x + blockIdx.x;
+        for (int e = threadIdx.x; e < 64 * 64; e += 256) dwslab[wg * 4096 + e] = tiles[e];
+    }
+}
+
 } // namespace
 
 extern "C" int gdm_topk_rows_hip(const float* score, long rows, int n, int K, int32_t* idx, float* val, void* stream)
@@ -772,4 +1178,87 @@ extern "C" int gdm_edge_block_hip(const float* pq, const int32_t* idx, const flo
     else
         hipLaunchKernelGGL(edge_block1_kernel, grid, dim3(256), 0, s, pq, idx, scale1, shift1, slope, n, K, out, out_C, out_c0);
     return gdm_launch_status("edge_block_kernel");
+}
+
+namespace {
+bool et_shape_ok(int B, int n, int K) { return B >= 1 && B <= 65535 && n >= 1 && K >= 1 && K <= 32 && (long)B * n * 128 < (1L << 40); }
+bool et_aligned(const void* a, const void* b, const void* c) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0; }
+} // namespace
+
+extern "C" long gdm_edge_train_groups(int B, int n)
+{
+    if (B < 1 || n < 1) return 0;
+    return (long)B * gdm_cdiv(n, EB_PTS);
+}
+
+extern "C" int gdm_edge_stats_hip(const float* pq, const int32_t* idx, const float* st1, const float* w2, float slope, int B, int n, int K, double* part,
+                                  void* stream)
+{
+    GDM_CHECK_ARG(pq && idx && part, "gdm_edge_stats_hip: NULL pointer");
+    GDM_CHECK_ARG((w2 != nullptr) == (st1 != nullptr), "gdm_edge_stats_hip: the second convolution's statistics need st1 and w2 together");
+    GDM_CHECK_ARG(et_shape_ok(B, n, K), "gdm_edge_stats_hip: bad shape B=%d n=%d K=%d", B, n, K);
+    GDM_CHECK_ARG(et_aligned(pq, st1, w2), "gdm_edge_stats_hip: pq, st1 and w2 must be 16-byte aligned");
+    const dim3 grid(gdm_cdiv(n, EB_PTS), B);
+    hipStream_t s = (hipStream_t)stream;
+    const float* nof = nullptr;
+    uint8_t* nob = nullptr;
+    float* now = nullptr;
+    if (w2)
+        hipLaunchKernelGGL(edge_train2_kernel<ET_STATS>, grid, dim3(256), 0, s, pq, idx, st1, w2, nof, nof, nof, slope, n, K, nof, nob, part, now, now);
+    else
+        hipLaunchKernelGGL(edge_train1_kernel<ET_STATS>, grid, dim3(256), 0, s, pq, idx, nof, nof, slope, n, K, nof, nob, part, now);
+    return gdm_launch_status("edge_stats_kernel");
+}
+
+extern "C" int gdm_edge_bwd_reduce_hip(const float* pq, const int32_t* idx, const float* st1, const float* w2, const float* st2, float slope, int B, int n,
+                                       int K, const float* grad_out, uint8_t* amax, double* part, void* stream)
+{
+    GDM_CHECK_ARG(pq && idx && st1 && grad_out && amax && part, "gdm_edge_bwd_reduce_hip: NULL pointer");
+    GDM_CHECK_ARG((w2 != nullptr) == (st2 != nullptr), "gdm_edge_bwd_reduce_hip: the second convolution needs w2 and st2 together");
+    GDM_CHECK_ARG(et_shape_ok(B, n, K), "gdm_edge_bwd_reduce_hip: bad shape B=%d n=%d K=%d", B, n, K);
+    GDM_CHECK_ARG(et_aligned(pq, st1, w2), "gdm_edge_bwd_reduce_hip: pq, st1 and w2 must be 16-byte aligned");
+    const dim3 grid(gdm_cdiv(n, EB_PTS), B);
+    hipStream_t s = (hipStream_t)stream;
+    const float* nof = nullptr;
+    float* now = nullptr;
+    if (w2)
+        hipLaunchKernelGGL(edge_train2_kernel<ET_REDUCE>, grid, dim3(256), 0, s, pq, idx, st1, w2, st2, nof, nof, slope, n, K, grad_out, amax, part, now, now);
+    else
+        hipLaunchKernelGGL(edge_train1_kernel<ET_REDUCE>, grid, dim3(256), 0, s, pq, idx, st1, nof, slope, n, K, grad_out, amax, part, now);
+    return gdm_launch_status("edge_bwd_reduce_kernel");
+}
+
+extern "C" int gdm_edge_bwd_mid_hip(const float* pq, const int32_t* idx, const float* st1, const float* w2, const float* st2, const float* cf2, float slope,
+                                    int B, int n, int K, const float* grad_out, const uint8_t* amax, double* part, float* dw_slabs, void* stream)
+{
+    GDM_CHECK_ARG(pq && idx && st1 && w2 && st2 && cf2 && grad_out && amax && part && dw_slabs, "gdm_edge_bwd_mid_hip: NULL pointer");
+    GDM_CHECK_ARG(et_shape_ok(B, n, K), "gdm_edge_bwd_mid_hip: bad shape B=%d n=%d K=%d", B, n, K);
+    GDM_CHECK_ARG(et_aligned(pq, st1, w2), "gdm_edge_bwd_mid_hip: pq, st1 and w2 must be 16-byte aligned");
+    const dim3 grid(gdm_cdiv(n, EB_PTS), B);
+    const float* nof = nullptr;
+    float* now = nullptr;
+    hipLaunchKernelGGL(edge_train2_kernel<ET_MID>, grid, dim3(256), 0, (hipStream_t)stream, pq, idx, st1, w2, st2, nof, cf2, slope, n, K, grad_out,
+                       const_cast<uint8_t*>(amax), part, dw_slabs, now);
+    return gdm_launch_status("edge_bwd_mid_kernel");
+}
+
+extern "C" int gdm_edge_bwd_scatter_hip(const float* pq, const int32_t* idx, const float* st1, const float* cf1, const float* w2, const float* st2,
+                                        const float* cf2, float slope, int B, int n, int K, const float* grad_out, const uint8_t* amax, float* grad_pq,
+                                        void* stream)
+{
+    GDM_CHECK_ARG(pq && idx && st1 && cf1 && grad_out && amax && grad_pq, "gdm_edge_bwd_scatter_hip: NULL pointer");
+    GDM_CHECK_ARG((w2 != nullptr) == (st2 != nullptr) && (w2 != nullptr) == (cf2 != nullptr),
+                  "gdm_edge_bwd_scatter_hip: the second convolution needs w2, st2 and cf2 together");
+    GDM_CHECK_ARG(et_shape_ok(B, n, K), "gdm_edge_bwd_scatter_hip: bad shape B=%d n=%d K=%d", B, n, K);
+    GDM_CHECK_ARG(et_aligned(pq, st1, w2), "gdm_edge_bwd_scatter_hip: pq, st1 and w2 must be 16-byte aligned");
+    const dim3 grid(gdm_cdiv(n, EB_PTS), B);
+    hipStream_t s = (hipStream_t)stream;
+    double* nod = nullptr;
+    float* now = nullptr;
+    uint8_t* am = const_cast<uint8_t*>(amax);
+    if (w2)
+        hipLaunchKernelGGL(edge_train2_kernel<ET_SCATTER>, grid, dim3(256), 0, s, pq, idx, st1, w2, st2, cf1, cf2, slope, n, K, grad_out, am, nod, now, grad_pq);
+    else
+        hipLaunchKernelGGL(edge_train1_kernel<ET_SCATTER>, grid, dim3(256), 0, s, pq, idx, st1, cf1, slope, n, K, grad_out, am, nod, grad_pq);
+    return gdm_launch_status("edge_bwd_scatter_kernel");
 }

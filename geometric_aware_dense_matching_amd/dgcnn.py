@@ -9,7 +9,12 @@ HIP kernel, edge features cat(x_j - x_i, x_i) by a HIP kernel; the reference's h
 
 Inference has a second, fused path (`forward(..., fused=True)`, `_DgcnnTrunk._embed_fused`): graphs by `knn_fused` (ops.feature_knn:
 Gram tile and selection in one kernel, no [B,n,n] matrix), every edge stage by one per-point layer + ops.edge_block (no [B,2C,n,k]
-tensor), conv6 .. conv9 by ops.pointwise over segments.  It has no backward and raises in training mode.
+tensor), conv6 .. conv9 by ops.pointwise over segments.  It folds the running statistics, so it raises in training mode.
+
+Training has its own fused path (`forward(..., train_fused=True)`, `_DgcnnTrunk._embed_train_fused`; selected by
+`geoMatch_DGCNN.GeoMatch.train_path = "fused"`): the same graphs and the same split of each stage's first convolution, with
+ops.edge_block_train (train-mode BatchNorm over all edges, full backward, every pass recomputing its edges) in place of the edge
+tensors, and a tail that never repeats the global feature.  Same parameters and state-dict names as the module path.
 """
 import os
 
@@ -130,7 +135,8 @@ class _DgcnnTrunk(nn.Module):
 
     def _embed_fused(self, x):
         """`_embed` in eval mode on HIP operators alone (the max over the points excepted): graphs by `knn_fused`, every edge stage by
-        one per-point layer + ops.edge_block, conv6 .. conv9 by ops.pointwise over segments (no cat, no repeat).  No backward."""
+        one per-point layer + ops.edge_block, conv6 .. conv9 by ops.pointwise over segments (no cat, no repeat).  No backward: training
+        has `_embed_train_fused`."""
         if self.training:
             raise RuntimeError("the fused DGCNN path is inference only (it has no backward): call .eval() or pass fused=False")
         if not x.is_cuda:
@@ -148,6 +154,51 @@ class _DgcnnTrunk(nn.Module):
         y = self._pw(self.conv8, [self._pw(self.conv7, [(g, everywhere), x1, x2, x3])])
         return ops.pointwise([y], self._wt(self.conv9))                                     # dropout is the identity in eval
 
+    # -- fused TRAINING path: the same structure under autograd ---------------------------------------------------------------------
+    def _edge_stage_train(self, x, idx, seq1, seq2):
+        """One edge stage in training mode -> f32[B,64,n].  The split weight [W_a ; W_b - W_a] is built with torch operations, so autograd
+        reaches conv.weight; the per-point layer's two gradient products are small batched GEMMs (ops.pointwise_pm_train)."""
+        w = seq1[0].weight.reshape(seq1[0].weight.shape[0], -1)
+        c = w.shape[1] // 2
+        pq = ops.pointwise_pm_train(x, torch.cat((w[:, :c], w[:, c:] - w[:, :c]), dim=0))   # [B,n,128]
+        if seq2 is None:
+            return ops.edge_block_train(pq, idx, seq1[1], slope=float(seq1[2].negative_slope))
+        return ops.edge_block_train(pq, idx, seq1[1], seq2[0].weight, seq2[1], slope=float(seq1[2].negative_slope))
+
+    @staticmethod
+    def _bn_act_train(seq, y):
+        if ops.bn_train_supported(y, seq[1]):
+            return ops.batch_norm_act_train(y, seq[1], ops.ACT_LEAKY, float(seq[2].negative_slope))
+        return seq[2](seq[1](y))
+
+    def _embed_train_fused(self, x):
+        """`_embed` in training mode without [B,n,n] distances, [B,2C,n,k] edge tensors or the repeated global feature.  Graphs by
+        `knn_fused` (no gradient flows through indices, as in `_embed`); stages by `_edge_stage_train`; conv6 .. conv9 by the
+        differentiable per-point operators; conv7(cat(g_rep, x123)) = W7[:, :embed] g + W7[:, embed:] x123 with the first term
+        [B,512,1] broadcast.  Dropout is self.dp1, called once per trunk as in `_embed`."""
+        if not self.training:
+            raise RuntimeError("the fused DGCNN training path needs training mode (batch statistics): call .train(), or use fused=True for inference")
+        if not x.is_cuda:
+            raise RuntimeError("the fused DGCNN path runs on the GPU (HIP kernels); there is no CPU fallback")
+        x = x.contiguous()
+        with torch.no_grad():
+            idx = knn_fused(x[:, :3], self.k)
+        x1 = self._edge_stage_train(x, idx, self.conv1, self.conv2)
+        with torch.no_grad():
+            idx = knn_fused(x1.detach(), self.k)
+        x2 = self._edge_stage_train(x1, idx, self.conv3, self.conv4)
+        with torch.no_grad():
+            idx = knn_fused(x2.detach(), self.k)
+        x3 = self._edge_stage_train(x2, idx, self.conv5, None)
+        x123 = torch.cat((x1, x2, x3), dim=1)                                                # [B,192,n]
+        g = self._bn_act_train(self.conv6, ops.conv1x1_train(self.conv6[0], x123)).max(dim=-1, keepdim=True)[0]      # [B,embed,1]
+        w7 = self.conv7[0].weight.reshape(self.conv7[0].weight.shape[0], -1)
+        e = g.shape[1]
+        y = ops.conv1x1_train_w(x123, w7[:, e:].contiguous()) + torch.matmul(w7[:, :e], g)   # the global term is one column per item
+        y = self._bn_act_train(self.conv7, y)
+        y = self._bn_act_train(self.conv8, ops.conv1x1_train(self.conv8[0], y))
+        return ops.conv1x1_train(self.conv9, self.dp1(y))
+
 
 class DgcnnPcdEmb(_DgcnnTrunk):
     def __init__(self, args):
@@ -159,8 +210,10 @@ class DgcnnPcdEmb(_DgcnnTrunk):
         self.dropout = args.get("dropout", 0.1)
         self._build(self.embed_dim, self.feat_dim, self.dropout)
 
-    def forward(self, x, fused=False):
-        return self._embed_fused(x) if fused else self._embed(x)
+    def forward(self, x, fused=False, train_fused=False):
+        if fused:
+            return self._embed_fused(x)
+        return self._embed_train_fused(x) if train_fused else self._embed(x)
 
 
 class DgcnnMeshEmb(_DgcnnTrunk):
@@ -194,8 +247,9 @@ class DgcnnMeshEmb(_DgcnnTrunk):
     def xyz(self):
         return self.mesh[0, :3].t()
 
-    def forward(self, fused=False):
-        if fused:
+    def forward(self, fused=False, train_fused=False):
+        if fused or train_fused:
             # the buffer is a transposed view of the loaded rows: its channel-major copy is made once, not per step
-            return self._embed_fused(derived(self, "mesh_cm", (self.mesh,), lambda: self.mesh.contiguous()))
+            mesh = derived(self, "mesh_cm", (self.mesh,), lambda: self.mesh.contiguous())
+            return self._embed_fused(mesh) if fused else self._embed_train_fused(mesh)
         return self._embed(self.mesh)

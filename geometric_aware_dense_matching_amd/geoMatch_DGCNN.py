@@ -14,6 +14,8 @@ from .loss import AutomaticWeightedLoss, CircleLoss, FocalLoss
 
 class GeoMatch(nn.Module):
     needs_pyramid = False            # dynamic graphs are built inside the trunks; no neighbour pyramid in the inputs
+    train_path = "modules"           # "modules" | "fused": how both trunks run in TRAINING mode (dgcnn._DgcnnTrunk._embed /
+                                     # ._embed_train_fused); not part of the state dict, read only when self.training
 
     def __init__(self, cfg, cls_id, model_points=None):
         super().__init__()
@@ -65,7 +67,8 @@ class GeoMatch(nn.Module):
         return per_item.mean()
 
     def forward(self, inputs, end_points=None, fused=False, defer_seg=False):
-        """fused: both trunks on the fused inference path (dgcnn._DgcnnTrunk._embed_fused; eval only).  defer_seg is accepted and
+        """fused: both trunks on the fused inference path (dgcnn._DgcnnTrunk._embed_fused; eval only; raises in training mode).  In
+        training mode `self.train_path == "fused"` sends both trunks through dgcnn._DgcnnTrunk._embed_train_fused.  defer_seg is accepted and
         ignored, as in geoMatch.GeoMatch: infer.pipeline_step passes it to every model."""
         if not end_points:
             end_points = {}
@@ -77,8 +80,11 @@ class GeoMatch(nn.Module):
             rgbd_emb = self.pcd_emb(x, fused=True)
             f.join(mesh_features)
         else:
-            rgbd_emb = self.pcd_emb(x, fused=fused)
-            mesh_features = self.model_emb(fused=fused)
+            if self.train_path not in ("modules", "fused"):
+                raise ValueError("train_path must be 'modules' or 'fused', got %r" % (self.train_path,))
+            train_fused = self.training and not fused and self.train_path == "fused"
+            rgbd_emb = self.pcd_emb(x, fused=fused, train_fused=train_fused)          # cloud first, then mesh: the dropout masks of a
+            mesh_features = self.model_emb(fused=fused, train_fused=train_fused)      # seed do not depend on the path
         rgbd_features = self.feature_encoding_layer(rgbd_emb)
         rgbd_normalized = self.normalize_feature_layer(rgbd_features)
         rgbd_emb = rgbd_emb + rgbd_normalized

@@ -402,7 +402,8 @@ def feature_knn(x, k, return_values=False, splits=0):
     selection in one kernel (include/gdm.h gdm_feature_knn_hip): no [B,n,n] matrix, the only workspace is O(B n).  Score
     descending, ties by ascending column, short rows filled with index 0.  A channel slice `t[:, :c]` of a contiguous tensor is read
     in place (its batch stride is passed on).  splits (1, 2, 4; 0 = chosen from the shape): how many waves share a row group's columns --
-    a launch parameter only, the result does not depend on it.  Inference only."""
+    a launch parameter only, the result does not depend on it.  No gradient flows through indices (both the inference and the training
+    path of the variant build their graphs here)."""
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise RuntimeError("x must be a CUDA (HIP) tensor: the geoMatch ops have no CPU fallback")
     if x.dtype != torch.float32 or x.dim() != 3:
@@ -423,7 +424,8 @@ def feature_knn(x, k, return_values=False, splits=0):
 
 
 def edge_block(pq, idx, scale1, shift1, w2=None, scale2=None, shift2=None, slope=0.2, out=None, out_c0=0):
-    """One edge-convolution stage without the edge tensor (include/gdm.h gdm_edge_block_hip), inference only.
+    """One edge-convolution stage without the edge tensor (include/gdm.h gdm_edge_block_hip), on folded (eval) BatchNorm: no autograd.
+    Training goes through `edge_block_train`, which runs this kernel on the batch statistics and has a backward.
     pq f32[B,n,128] point-major: the stage's first convolution applied per point, [W_a ; W_b - W_a] x; idx int[B,n,K], K <= 32;
     scale1 / shift1 f32[64]: the first folded BatchNorm; w2 f32[64,64(,1,1)], scale2 / shift2: the second convolution and its
     BatchNorm, or None for a single-convolution stage.  Returns f32[B,64,n] = max over the neighbours of the last activation, or
@@ -451,6 +453,142 @@ def edge_block(pq, idx, scale1, shift1, w2=None, scale2=None, shift2=None, slope
     ptr = lambda t: t.data_ptr() if t is not None else None
     check(_lib.lib().gdm_edge_block_hip(pq.data_ptr(), idx.data_ptr(), scale1.data_ptr(), shift1.data_ptr(), ptr(w2), ptr(scale2), ptr(shift2),
                                         float(slope), B, n, K, out.data_ptr(), out.shape[1], int(out_c0), _stream()), "gdm_edge_block_hip")
+    return out
+
+
+def _edge_sums_buffer(B, n, K, device):
+    """f64[groups * 128 + 2] in the layout `_fold_and_all_reduce` reads: one (sum, sum) pair per workgroup and channel, then the local
+    edge count and the number of workgroups."""
+    groups = _lib.lib().gdm_edge_train_groups(B, n)
+    buf = torch.empty(groups * 128 + 2, dtype=torch.float64, device=device)
+    buf[-2:] = float(B * n * K)                               # only the count is read
+    return buf
+
+
+def _edge_fold(buf, group):
+    """-> (local sums f64[64,2], sums over the ranks of `group` f64[64,2], edge count over the ranks: a number, or a 0-dim tensor when
+    it came through the all-reduce -- no host synchronisation either way).  Workgroup partials are added in fp64 in a fixed order."""
+    local = buf[:-2].view(-1, 128).sum(0).view(64, 2)
+    if group is None:
+        return local, local, None
+    compact = _fold_and_all_reduce(buf, 64, group)
+    return local, compact[:128].view(64, 2), compact[128]
+
+
+def _edge_bn_fold(sums, E, bn_w, bn_b, eps, momentum, running_mean, running_var):
+    """Batch moments from (sum y, sum y^2) over E edges in fp64 -> st f32[4,64] = (gamma rstd | beta - mean gamma rstd | mean | rstd);
+    updates the running statistics as the module does (unbiased variance)."""
+    mean = sums[:, 0] / E
+    var = (sums[:, 1] / E - mean * mean).clamp_min(0.0)
+    rstd = torch.rsqrt(var + eps)
+    sc = bn_w.detach().double() * rstd
+    st = torch.stack((sc, bn_b.detach().double() - mean * sc, mean, rstd)).float()
+    if running_mean is not None:
+        running_mean.copy_((1.0 - momentum) * running_mean.double() + momentum * mean)
+        running_var.copy_((1.0 - momentum) * running_var.double() + momentum * (var * (E / (E - 1.0))))
+    return st
+
+
+class _EdgeBlockTrain(torch.autograd.Function):
+    """ops.edge_block_train: forward = two statistics passes + the inference kernel on the folded batch statistics; backward = arg-max /
+    last sums, (dW2 and the first layer's sums,) scatter -- every pass recomputes its edges (include/gdm.h gdm_edge_stats_hip ...)."""
+
+    @staticmethod
+    def forward(ctx, pq, idx, w1, b1, w2, g2, b2, slope, bn1_args, bn2_args, group):
+        L = _lib.lib()
+        B, n, _ = pq.shape
+        K = idx.shape[2]
+        two = w2 is not None
+        count = float(B * n * K)
+        buf = _edge_sums_buffer(B, n, K, pq.device)
+        check(L.gdm_edge_stats_hip(pq.data_ptr(), idx.data_ptr(), None, None, float(slope), B, n, K, buf.data_ptr(), _stream()), "gdm_edge_stats_hip")
+        _, tot, E = _edge_fold(buf, group)
+        E = count if E is None else E
+        st1 = _edge_bn_fold(tot, E, w1, b1, *bn1_args)
+        st2 = None
+        if two:
+            ctx.w2_shape = w2.shape
+            w2 = _dev(w2.detach().reshape(64, 64), torch.float32, "w2")
+            check(L.gdm_edge_stats_hip(pq.data_ptr(), idx.data_ptr(), st1.data_ptr(), w2.data_ptr(), float(slope), B, n, K, buf.data_ptr(), _stream()),
+                  "gdm_edge_stats_hip")
+            _, tot, _ = _edge_fold(buf, group)
+            st2 = _edge_bn_fold(tot, E, g2, b2, *bn2_args)
+        out = edge_block(pq, idx, st1[0], st1[1], w2, st2[0] if two else None, st2[1] if two else None, slope)
+        ctx.save_for_backward(pq, idx, st1, w2, st2, E if torch.is_tensor(E) else None)
+        ctx.count, ctx.slope, ctx.group = count, float(slope), group
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        pq, idx, st1, w2, st2, E = ctx.saved_tensors
+        E = ctx.count if E is None else E
+        go = _dev(go, torch.float32, "grad")
+        L = _lib.lib()
+        B, n, _ = pq.shape
+        K = idx.shape[2]
+        two = w2 is not None
+        slope, group = ctx.slope, ctx.group
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        amax = torch.empty((B, n, 64), dtype=torch.uint8, device=pq.device)
+        buf = _edge_sums_buffer(B, n, K, pq.device)
+        check(L.gdm_edge_bwd_reduce_hip(pq.data_ptr(), idx.data_ptr(), st1.data_ptr(), ptr(w2), ptr(st2), slope, B, n, K, go.data_ptr(), amax.data_ptr(),
+                                        buf.data_ptr(), _stream()), "gdm_edge_bwd_reduce_hip")
+        # grad gamma / beta (and dW2) stay LOCAL sums, as in _BatchNormAct: DDP averages parameter gradients over the ranks
+        local, tot, _ = _edge_fold(buf, group)
+        cf_last = (tot / E).t().contiguous().float()                        # [2,64] = dbeta / E | dgamma / E
+        gw2 = gg2 = gb2 = cf2 = None
+        if two:
+            gb2, gg2, cf2 = local[:, 0].float(), local[:, 1].float(), cf_last
+            slabs = torch.empty((buf.numel() - 2) // 128, 64, 64, dtype=torch.float32, device=pq.device)
+            check(L.gdm_edge_bwd_mid_hip(pq.data_ptr(), idx.data_ptr(), st1.data_ptr(), w2.data_ptr(), st2.data_ptr(), cf2.data_ptr(), slope, B, n, K,
+                                         go.data_ptr(), amax.data_ptr(), buf.data_ptr(), slabs.data_ptr(), _stream()), "gdm_edge_bwd_mid_hip")
+            gw2 = slabs.sum(0).reshape(ctx.w2_shape)
+            local, tot, _ = _edge_fold(buf, group)
+            cf1 = (tot / E).t().contiguous().float()
+        else:
+            cf1 = cf_last
+        gb1, gg1 = local[:, 0].float(), local[:, 1].float()
+        gpq = torch.zeros_like(pq)                                          # the P half is accumulated by atomicAdd
+        check(L.gdm_edge_bwd_scatter_hip(pq.data_ptr(), idx.data_ptr(), st1.data_ptr(), cf1.data_ptr(), ptr(w2), ptr(st2), ptr(cf2), slope, B, n, K,
+                                         go.data_ptr(), amax.data_ptr(), gpq.data_ptr(), _stream()), "gdm_edge_bwd_scatter_hip")
+        return gpq, None, gg1, gb1, gw2, gg2, gb2, None, None, None, None
+
+
+def _edge_bn_check(bn, name):
+    if not (bn.training and bn.affine and bn.momentum is not None and bn.weight.numel() == 64):
+        raise ValueError("edge_block_train: %s must be an affine 64-channel BatchNorm in training mode with a numeric momentum" % name)
+    return (float(bn.eps), float(bn.momentum), bn.running_mean if bn.track_running_stats else None,
+            bn.running_var if bn.track_running_stats else None)
+
+
+def edge_block_train(pq, idx, bn1, w2=None, bn2=None, slope=0.2):
+    """`edge_block` in training mode, differentiable: one edge-convolution stage with train-mode BatchNorm over all B n K edges (over all
+    ranks for a SyncBatchNorm that spans several) and no [B,C,n,K] tensor, forward or backward.
+    pq f32[B,n,128] point-major (the stage's first convolution per point, as for edge_block); idx int[B,n,K], clamped to [0, n);
+    bn1: the first BatchNorm MODULE (weight, bias, eps and momentum are read at call time, running statistics and
+    num_batches_tracked are updated as the module does); w2 f32[64,64(,1,1)] and bn2: the second convolution and its BatchNorm, or
+    None.  Returns f32[B,64,n].  Gradients reach pq, bn1.weight / bias, w2 and bn2.weight / bias; none flows through idx.
+    grad pq's neighbour half is accumulated by float atomics: it is not bitwise reproducible from run to run."""
+    pq = _dev(pq, torch.float32, "pq")
+    idx = _idx32(idx, "idx")
+    if pq.dim() != 3 or pq.shape[2] != 128 or idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(pq.shape[:2]):
+        raise ValueError("edge_block_train: pq must be [B,n,128] and idx [B,n,K], got %s and %s" % (tuple(pq.shape), tuple(idx.shape)))
+    if not 1 <= idx.shape[2] <= 32:
+        raise ValueError("edge_block_train: K=%d not in [1, 32]" % idx.shape[2])
+    if (w2 is None) != (bn2 is None):
+        raise ValueError("edge_block_train: w2 and bn2 go together")
+    if w2 is not None and w2.numel() != 64 * 64:
+        raise ValueError("edge_block_train: the second convolution is 64 -> 64")
+    a1 = _edge_bn_check(bn1, "bn1")
+    a2 = _edge_bn_check(bn2, "bn2") if bn2 is not None else None
+    out = _EdgeBlockTrain.apply(pq, idx, bn1.weight, bn1.bias, w2, bn2.weight if bn2 is not None else None,
+                                bn2.bias if bn2 is not None else None, float(slope), a1, a2, _sync_group(bn1))
+    for bn in (bn1, bn2):
+        if bn is not None and bn.num_batches_tracked is not None:
+            if _bn_counters is not None:
+                _bn_counters.append(bn.num_batches_tracked)
+            else:
+                bn.num_batches_tracked.add_(1)
     return out
 
 
@@ -1183,6 +1321,32 @@ def conv1x1_train(conv, x):
             y = y + conv.bias.view(1, -1, 1)
         return y.view(B, Cout, *x.shape[2:])
     return _Conv1x1Train.apply(x.contiguous(), w.reshape(w.shape[0], w.shape[1]), conv.bias)
+
+
+def conv1x1_train_w(x, w2, bias=None):
+    """`conv1x1_train` for a weight TENSOR f32[Cout,Cin] (a slice of a module's weight, say) instead of a module: x f32[B,Cin,n]."""
+    return _Conv1x1Train.apply(x.contiguous(), w2, bias)
+
+
+class _PointwisePmTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x, w)
+        return pointwise([x], w.t().contiguous(), point_major=True)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g = g.contiguous()
+        gx = torch.matmul(g, w).transpose(1, 2).contiguous() if ctx.needs_input_grad[0] else None      # [B,n,C] -> [B,C,n]
+        gw = torch.bmm(x, g).sum(0).t() if ctx.needs_input_grad[1] else None                           # sum_b x[b] g[b] = [C,Cout]
+        return gx, gw
+
+
+def pointwise_pm_train(x, w):
+    """Differentiable per-point layer with a POINT-MAJOR result: x f32[B,C,n], w f32[Cout,C] -> f32[B,n,Cout] = (W x)^T, the forward on
+    the exact-fp32 MFMA kernel of `pointwise`, the two gradient products (2 B n C Cout flops each) as batched GEMMs."""
+    return _PointwisePmTrain.apply(_dev(x, torch.float32, "x"), w)
 
 
 def upconv_train_supported(B, cout):

@@ -95,6 +95,10 @@ def build_parser():
                         "group, no collective")
     p.add_argument("--graph-train", action="store_true",
                    help="train: capture one iteration (forward + losses + backward + Adam) as a hipGraph and replay it (single process)")
+    p.add_argument("--dgcnn-train-path", dest="dgcnn_train_path", type=str, default="modules", choices=["modules", "fused"],
+                   help="train, --model-variant dgcnn: 'modules' = dense distances and library convolutions on edge tensors; 'fused' = "
+                        "feature-space kNN with no N x N matrix and ops.edge_block_train stages with no edge tensor (same parameters, "
+                        "interchangeable checkpoints)")
     p.add_argument("--gt-targets", dest="gt_targets", type=str, default="loader", choices=GT_TARGETS,
                    help="train: 'loader' = labels / match_idx / visible_flag come with the items; 'device' = computed on the GPU from the "
                         "items' RT and origin_labels (get_pose_gt_info, linemod_pbr.py:602-655; targets.pose_gt_info), invalid items "
@@ -350,7 +354,9 @@ def build_model(args, cls_id, cache_mesh_in_eval=False):
     pts = _model_points(args, ds, cls_id)
     if args.model_variant == "dgcnn":
         from .geoMatch_DGCNN import GeoMatch as GeoMatchDGCNN
-        return GeoMatchDGCNN(make_dgcnn_cfg(n_mesh_node=args.n_mesh, dataset=args.dataset_name), cls_id, model_points=pts)
+        model = GeoMatchDGCNN(make_dgcnn_cfg(n_mesh_node=args.n_mesh, dataset=args.dataset_name), cls_id, model_points=pts)
+        model.train_path = getattr(args, "dgcnn_train_path", "modules")
+        return model
     cfg = make_model_cfg(n_mesh_node=args.n_mesh, num_points=args.n_points, dataset=args.dataset_name)
     return GeoMatch(cfg, cls_id, model_points=pts, cache_mesh_in_eval=cache_mesh_in_eval)
 

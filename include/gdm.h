@@ -250,6 +250,31 @@ int gdm_feature_knn_hip(const float* x, long x_bstride, int B, int C, int n, int
  * idx i32[B,n,K], clamped to [0, n); 1 <= K <= 32.  pq, scale1, shift1 and w2 must be 16-byte aligned. */
 int gdm_edge_block_hip(const float* pq, const int32_t* idx, const float* scale1, const float* shift1, const float* w2, const float* scale2,
                        const float* shift2, float slope, int B, int n, int K, float* out, int out_C, int out_c0, void* stream);
+/* edge_block in training mode (train-mode BatchNorm over all E = B n K edges, differentiable): the passes around gdm_edge_block_hip.
+ * Every pass recomputes its edges from pq, idx and per-channel numbers; none allocates O(B n K C).  With y1 = pq[idx[b,i,k], 0:64] +
+ * pq[i, 64:128], h1 = act(scale1 y1 + shift1), y2 = w2 h1:
+ *   st  f32[4][64] per BatchNorm: scale = gamma rstd | shift = beta - mean scale | mean | rstd (of the batch)
+ *   cf  f32[2][64] per BatchNorm: dbeta / E | dgamma / E
+ *   part f64[gdm_edge_train_groups(B, n)][64][2]: one pair of per-channel sums per workgroup, to be added by the caller (in fp64, in a
+ *        fixed order: the sums do not depend on scheduling)
+ * gdm_edge_stats_hip       pair = (sum y1, sum y1^2) with st1 = w2 = NULL, else (sum y2, sum y2^2)
+ * gdm_edge_bwd_reduce_hip  the last layer's first arg-max over k per (point, channel) -> amax u8[B,n,64], and pair = (dbeta, dgamma) of
+ *                          the last BatchNorm (w2 = st2 = NULL: the single-convolution stage); grad_out f32[B,64,n]
+ * gdm_edge_bwd_mid_hip     two convolutions: dy2 = scale2 (dz2 - cf2[0] - y2_hat cf2[1]); dw_slabs f32[groups][64][64] = the workgroup's
+ *                          sum over its edges of dy2 (x) h1 (fp32 MFMA with the edges as the contraction), pair = (dbeta1, dgamma1)
+ * gdm_edge_bwd_scatter_hip dy1 = scale1 (dz1 - cf1[0] - y1_hat cf1[1]) -> grad_pq f32[B,n,128]: columns 0..63 of row idx[b,i,k] by
+ *                          atomicAdd (ZEROED by the caller; one 256-byte row per edge), columns 64..127 of row i stored
+ * idx is clamped to [0, n) as gdm_edge_block_hip clamps; 1 <= K <= 32; pq, st1 and w2 16-byte aligned. */
+long gdm_edge_train_groups(int B, int n);
+int gdm_edge_stats_hip(const float* pq, const int32_t* idx, const float* st1, const float* w2, float slope, int B, int n, int K, double* part,
+                       void* stream);
+int gdm_edge_bwd_reduce_hip(const float* pq, const int32_t* idx, const float* st1, const float* w2, const float* st2, float slope, int B, int n,
+                            int K, const float* grad_out, uint8_t* amax, double* part, void* stream);
+int gdm_edge_bwd_mid_hip(const float* pq, const int32_t* idx, const float* st1, const float* w2, const float* st2, const float* cf2, float slope,
+                         int B, int n, int K, const float* grad_out, const uint8_t* amax, double* part, float* dw_slabs, void* stream);
+int gdm_edge_bwd_scatter_hip(const float* pq, const int32_t* idx, const float* st1, const float* cf1, const float* w2, const float* st2,
+                             const float* cf2, float slope, int B, int n, int K, const float* grad_out, const uint8_t* amax, float* grad_pq,
+                             void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Fused circle loss rows for the training matching (models/geoMatch.py:55-83 matching_loss,
