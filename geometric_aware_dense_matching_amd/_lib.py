@@ -136,6 +136,7 @@ SIGNATURES = {
     "gdm_conv3x3_packed_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "gdm_conv3x3_strided_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gdm_conv1x1_strided_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gdm_conv1x1_gather_add_hip": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gdm_affine_relu_maxpool_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "gdm_conv1x1_logsoftmax_hip": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_long, _vp, _vp]),
     "gdm_pack_rows64_hip": (_i, [_vp, _i, _vp, _vp]),

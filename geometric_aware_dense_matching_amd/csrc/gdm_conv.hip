@@ -153,7 +153,10 @@ constexpr int MF_SMEM = 2 * CV_PANEL > CV_PIX * MF_TSTRIDE * 4 ? 2 * CV_PANEL : 
 // tiling leaves half the chip idle -- layer1-3 of the trunk at batch 16 -- and no zero-padded weight rows for 64-channel layers)
 // WV = waves per workgroup: 8 (256 pixels), or 4 (128 pixels: the 128 -> 128 layers at 32 x 32 have 128 workgroups of the 256-pixel, 64-channel
 // tiling on 256 CUs -- half tiles put one on every CU)
-template <int ACT, bool HAS_RES, int TAPS = 9, bool PIXMAJOR = false, int NKS = 8, int NCB = 8, int WV = MF_WAVES>
+// GADD (NCHW / packed epilogue only): the point-to-pixel fusion tail in the epilogue -- the GEMM result x takes the gathered point term
+// and the folded BatchNorm, out = act(scale[co] * (x + gt[b, co, clamp(gidx[b, pixel])]) + shift[co]), with the bits of the GEMM
+// followed by gather_add_affine_act_kernel (gdm_image.hip) and without the fp32 map between them
+template <int ACT, bool HAS_RES, int TAPS = 9, bool PIXMAJOR = false, int NKS = 8, int NCB = 8, int WV = MF_WAVES, bool GADD = false>
 __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned char* __restrict__ xpk, const unsigned char* __restrict__ wpk,
                                                                  const float* __restrict__ scale, const float* __restrict__ shift,
                                                                  const float* __restrict__ res, int B, int Cin, int Cout, int H, int W,
@@ -162,7 +165,14 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
                                                                  unsigned char* __restrict__ outpk = nullptr, int stride = 1,
                                                                  // per-image weights (the weight-gradient GEMM: image b of a workgroup's 256 pixels --
                                                                  // H*W % 256 == 0 -- reads its rows at wpk + b * wbstride); 0 = shared weights
-                                                                 long wbstride = 0)
+                                                                 long wbstride = 0,
+                                                                 // GADD: gidx int32[B, H*W] (per pixel), gt f32[B, Cout, gn] (channel-major)
+                                                                 const int32_t* __restrict__ gidx = nullptr,
+                                                                 const float* __restrict__ gt = nullptr, int gn = 0,
+                                                                 // byte offset in LDS (behind the panels and the output tile) where the
+                                                                 // workgroup stages its rows of gt, gn + 1 floats apart; 0: the lanes
+                                                                 // gather from global memory.  Needs one image per workgroup (hw % 256 == 0)
+                                                                 int gt_lds = 0)
 {
     // H, W: OUTPUT map; the packed input is the (H stride) x (W stride) map (stride 2: layer2's first block, extractors.py:151-177)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // 2 x CV_PANEL
@@ -392,21 +402,83 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
         }
         return;
     }
+    // GADD: what the epilogue reads from memory -- the four pixels' indices per ph, the folded BN pair per 16-channel block, the gathered
+    // values -- is requested here, in front of the barrier, without a branch in between (rows beyond Cout read row Cout - 1 and are masked
+    // below).  The gathered values are NCB * 4 NPH scattered 4-byte loads per lane; a scattered load costs the vector memory pipe a
+    // cycle per lane whatever the cache holds (measured: 12 us per workgroup on top of the GEMM, the same with every index 0), so with
+    // gt_lds the workgroup copies its NCB * 16 rows of gt (contiguous in memory: coalesced loads) to LDS and gathers there.
+    float gtv[GADD ? NPH : 1][GADD ? NCB : 1][4], gsc[GADD ? NCB : 1], gsh[GADD ? NCB : 1];
+    int gsrc[GADD ? NPH : 1][4];
+    if constexpr (GADD) {
+#pragma unroll
+        for (int ph = 0; ph < NPH; ++ph) {                           // one 16-byte load (hw % 32 == 0, prem % 32 == 0: aligned)
+            const int4 i4 = *reinterpret_cast<const int4*>(gidx + (long)b * hw + prem + 16 * ph + 4 * kg);
+            gsrc[ph][0] = min(max(i4.x, 0), gn - 1);
+            gsrc[ph][1] = min(max(i4.y, 0), gn - 1);
+            gsrc[ph][2] = min(max(i4.z, 0), gn - 1);
+            gsrc[ph][3] = min(max(i4.w, 0), gn - 1);
+        }
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) {
+            const int cl = min(co0 + cb * 16 + l16, Cout - 1);
+            gsc[cb] = scale[cl];
+            gsh[cb] = shift[cl];
+        }
+        if (gt_lds) {
+            float* ts = reinterpret_cast<float*>(smem + gt_lds);
+            for (int r = wave; r < NCB * 16; r += WV) {              // a row per wave and turn: gn consecutive floats
+                const float* tp = gt + ((long)b * Cout + min(co0 + r, Cout - 1)) * gn;
+                for (int c = lane; c < gn; c += 64) ts[r * (gn + 1) + c] = tp[c];
+            }
+        } else {
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) {
+                const float* tp = gt + ((long)b * Cout + min(co0 + cb * 16 + l16, Cout - 1)) * gn;
+#pragma unroll
+                for (int ph = 0; ph < NPH; ++ph)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) gtv[ph][cb][j] = tp[gsrc[ph][j]];
+            }
+        }
+    }
     float* tl = reinterpret_cast<float*>(smem) + wave * MF_WPIX * TST;
-    if (outpk) __syncthreads();                                      // every wave has finished reading the last weight panel
+    if (outpk || (GADD && gt_lds)) __syncthreads();                  // every wave has finished reading the last weight panel
+    if constexpr (GADD) {
+        if (gt_lds) {                                                // (the barrier above: the staged rows are complete)
+            const float* ts = reinterpret_cast<const float*>(smem + gt_lds);
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+                for (int ph = 0; ph < NPH; ++ph)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) gtv[ph][cb][j] = ts[(cb * 16 + l16) * (gn + 1) + gsrc[ph][j]];
+        }
+    }
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
         const int co = co0 + cb * 16 + l16;
         const bool live = co < Cout;
-        const float sc = (live && scale) ? scale[co] : 1.f, sh = (live && shift) ? shift[co] : 0.f;
+        float sc, sh;
+        if constexpr (GADD) { sc = gsc[cb]; sh = gsh[cb]; }
+        else { sc = (live && scale) ? scale[co] : 1.f; sh = (live && shift) ? shift[co] : 0.f; }
         float* op = out ? out + ((long)b * Cout + (live ? co : 0)) * hw + prem : nullptr;
         const float* rp = (HAS_RES && live) ? res + ((long)b * Cout + co) * hw + prem : nullptr;
 #pragma unroll
         for (int ph = 0; ph < NPH; ++ph) {
             const int poff = 16 * ph + 4 * kg;
             float v[4];
+            if constexpr (GADD) {
+                // the two-launch form's arithmetic, step by step (-ffp-contract=off: the source order is the bit pattern): the GEMM's
+                // identity scale / shift (x * 1 + 0: -0 becomes +0), then scale * (x + t) + shift
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = acc[ph][cb][j] * sc + sh;
+                for (int j = 0; j < 4; ++j) {
+                    const float x = acc[ph][cb][j] * 1.f + 0.f;
+                    v[j] = (x + gtv[ph][cb][j]) * sc + sh;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = acc[ph][cb][j] * sc + sh;
+            }
             if (HAS_RES && live) {
                 const float4 r4 = *reinterpret_cast<const float4*>(rp + poff);
                 v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w;
@@ -841,4 +913,59 @@ static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, 
     else { if (pixel_major) C1(1, true); else C1(1, false); }
 #undef C1
     return gdm_launch_status("conv1x1_bf16x3_kernel");
+}
+
+// The point-to-pixel fusion as ONE launch: the 1x1 GEMM above (stride 1, NCHW) whose epilogue adds the gathered point term and applies
+// the folded BatchNorm and the activation (conv_mfma16_kernel, GADD) -- what gdm_conv1x1_strided_hip followed by
+// gdm_gather_add_affine_act2_hip computes, bit for bit, without the fp32 map [B, Cout, H*W] written and read back between them.
+// out (fp32 NCHW) and / or outpk (the packed operand of the next convolution / GEMM, as gdm_conv3x3_strided_hip writes it).
+extern "C" int gdm_conv1x1_gather_add_hip(const void* xpk, const void* wpk, const int32_t* gidx, const float* gt, int gn, const float* scale,
+                                          const float* shift, int B, int Cin, int Cout, int H, int W, int act, float* out, void* outpk,
+                                          void* stream)
+{
+    const char* who = "gdm_conv1x1_gather_add_hip";
+    GDM_CHECK_ARG(xpk && wpk && gidx && gt && scale && shift && (out || outpk), "%s: NULL pointer", who);
+    GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cin != 64 && Cout >= 1, "%s: Cin=%d Cout=%d (Cin a multiple of 128)", who, Cin, Cout);
+    GDM_CHECK_ARG(W >= 32 && W % 32 == 0 && H >= 1 && (H * W) % CONV_WPIX == 0,
+                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, CONV_WPIX);
+    GDM_CHECK_ARG(gn >= 1, "%s: gn=%d (the gathered term needs at least one column)", who, gn);
+    GDM_CHECK_ARG(act == 0 || act == 1, "%s: act=%d (none or ReLU)", who, act);
+    GDM_CHECK_ARG(!outpk || (Cout % 8 == 0 && ((long)B * H * W) % CV_PIX == 0),
+                  "%s: packed output needs Cout %% 8 == 0 and B*H*W %% 256 == 0 (got Cout=%d, B*H*W=%ld)", who, Cout, (long)B * H * W);
+    // the kernel addresses the packed activations and the packed weights through buffer descriptors with 32-bit byte offsets
+    const long xbytes = (long)B * (H + 2) * (W + 2) * ((Cin + 127) / 128) * ROWB;
+    const long wbytes = (long)((Cin + 127) / 128) * ((Cout + 127) & ~127) * ROWB;
+    GDM_CHECK_ARG(xbytes < (1L << 31) && wbytes < (1L << 31),
+                  "%s: packed operands must stay below 2 GiB (activations %ld bytes, weights %ld bytes)", who, xbytes, wbytes);
+    GDM_CHECK_ARG(((uintptr_t)gidx & 15) == 0, "%s: gidx must be 16-byte aligned (the epilogue loads four indices at once)", who);
+    const long ptot = (long)B * H * W;
+    const unsigned ptiles = gdm_cdiv(ptot, CV_PIX);
+    const bool narrow = narrow_tiles(ptiles, Cout);                 // the tile width conv1x1_launch takes for this shape
+    const dim3 grid(ptiles, gdm_cdiv(Cout, narrow ? 64 : CV_CO));
+    hipStream_t s = (hipStream_t)stream;
+    // weight panels, or (packed output) the waves' output tiles where those are larger
+    constexpr int SMEM8 = CONV_SMEM;
+    constexpr int SMEM4 = 2 * 64 * ROWB > CV_PIX * 68 * 4 ? 2 * 64 * ROWB : CV_PIX * 68 * 4;
+    // behind them the workgroup's rows of gt, gn + 1 floats apart (conflict-free across the 16 channels of a fragment), where a workgroup
+    // lies inside one image and the rows fit the CU's 160 KiB; 64-channel tiles stay at two workgroups per CU unless the grid has no
+    // second workgroup for a CU anyway.  Otherwise the lanes gather from global memory.
+    constexpr int LDS_MAX = 160 * 1024;
+    const long trows = (long)(narrow ? 64 : CV_CO) * (gn + 1) * 4;
+    const long smem = (narrow ? SMEM4 : SMEM8) + trows;
+    const bool stage_t = (H * W) % CV_PIX == 0 && smem <= (narrow && (long)grid.x * grid.y > 256 ? LDS_MAX / 2 : LDS_MAX);
+    const int gt_lds = stage_t ? (narrow ? SMEM4 : SMEM8) : 0;
+    const int SM = stage_t ? (int)smem : (narrow ? SMEM4 : SMEM8);
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false, 8, 8, MF_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, false, 8, 8, MF_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false, 8, 4, MF_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, false, 8, 4, MF_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        attr = true;
+    }
+#define C1G(A, N) hipLaunchKernelGGL((CONV_KERNEL<A, false, 1, false, 8, N, MF_WAVES, true>), grid, dim3(CONV_THREADS), SM, s, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, (const float*)nullptr, B, Cin, Cout, H, W, out, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned char*)outpk, 1, 0L, gidx, gt, gn, gt_lds)
+    if (narrow) { if (act == 0) C1G(0, 4); else C1G(1, 4); }
+    else { if (act == 0) C1G(0, 8); else C1G(1, 8); }
+#undef C1G
+    return gdm_launch_status(narrow ? "conv1x1_gather_add_kernel (64-channel tiles)" : "conv1x1_gather_add_kernel");
 }

@@ -184,7 +184,13 @@ class FFB6DEmb(nn.Module):
                     raise RuntimeError("pixel-major fusion output is the 64-channel kernel's; _sparse_final_ok() guards the caller")
                 if settings.USE_MFMA_GEMM and ops.gemm_supported(c, wa.shape[0], hr * wr):
                     wpk, co = cached_gemm_weight(fuse_layer, "wa", wa, (fuse_layer.conv.weight,))
-                    x = ops.gemm_bf16x3_map(rgb_emb0, wpk, co).view(bs, co, hr * wr)   # split-bf16 MFMA; reads the stage's packed output
+                    only = packed_only and ops.packed_out_supported(bs, co, hr, wr)
+                    if ops.conv1x1_gather_add_supported(rgb_emb0, co, code[0], f32_out=not only):
+                        # the GEMM runs inside gather_add_affine_act's launch (ops.conv1x1_packed_gather_add_act): gather, add, BN and
+                        # activation are its epilogue, the fp32 map between the two is never written
+                        x = ops.GemmMap(rgb_emb0, wpk, co)
+                    else:
+                        x = ops.gemm_bf16x3_map(rgb_emb0, wpk, co).view(bs, co, hr * wr)   # split-bf16 MFMA; reads the stage's packed output
                 else:
                     x = ops.wx(wa, rgb_emb0.reshape(bs, c, hr * wr))                    # [B,Cout,HW]
                 scale, shift = folded_bn(fuse_layer.normlayer.bn)

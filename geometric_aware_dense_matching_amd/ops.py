@@ -1383,7 +1383,13 @@ def gather_add_affine_act(x, t, idx, scale, shift, act=ACT_NONE, slope=0.0, hw=N
     Inference only, in place on x.  With hw = (H, W) of the pixel map (m = H*W) the kernel also writes the packed split-bf16 operand
     of the next convolution / GEMM over it; the caller hangs the returned PackedAct on the map it hands on (`_gdm_packed`).
     f32_out=False (needs hw and packed_out_supported): the PackedAct is the only output and the only return value -- no fp32 store,
-    x is left as it was -- for a map whose only reader is a GEMM on the packed operand."""
+    x is left as it was -- for a map whose only reader is a GEMM on the packed operand.
+    x may be a GemmMap (the 1x1 GEMM that would produce x, not yet run): the whole call is then that GEMM with this tail as its
+    epilogue, conv1x1_packed_gather_add_act -- one launch, same bits, x never stored."""
+    if isinstance(x, GemmMap):
+        if hw is None:
+            raise ValueError("gather_add_affine_act: a GemmMap needs hw")
+        return conv1x1_packed_gather_add_act(x.x, x.wpk, x.cout, t, idx, scale, shift, act, hw=hw, f32_out=f32_out)
     x = _dev(x, torch.float32, "x")
     t = _dev(t, torch.float32, "t")
     idx = _idx32(idx, "idx")
@@ -1906,6 +1912,71 @@ def gemm_bf16x3_map(x, wpk, cout):
     if isinstance(xp, PackedAct) and xp.shape == (B, Cin, H, W) and W % 32 == 0:
         return conv1x1_packed2d(xp, wpk, cout)
     return gemm_bf16x3(x.reshape(B, Cin, H * W), wpk, cout).view(B, cout, H, W)
+
+
+def _packed_operand(x):
+    """The packed operand gemm_bf16x3_map would read for the map x (a PackedAct, or a tensor that carries its producer's `_gdm_packed`),
+    or None where it would pack x itself."""
+    if isinstance(x, PackedAct):
+        return x if x.shape[3] % 32 == 0 else None
+    xp = getattr(x, "_gdm_packed", None)
+    if isinstance(xp, PackedAct) and len(x.shape) == 4 and xp.shape == tuple(x.shape) and x.shape[3] % 32 == 0:
+        return xp
+    return None
+
+
+def conv1x1_gather_add_supported(x, cout, act, f32_out=True):
+    """True when conv1x1_packed_gather_add_act(x, ...) replaces gemm_bf16x3_map + gather_add_affine_act: the map exists as a packed
+    operand, the GEMM is one gemm_supported takes (K in whole 128-channel chunks), the activation is none or ReLU, and the pair would
+    give the same outputs -- the packed operand where packed_out_supported, which f32_out=False needs."""
+    xp = _packed_operand(x)
+    if xp is None or act not in (ACT_NONE, ACT_RELU):
+        return False
+    B, cin, H, W = xp.shape
+    if cin % 128 != 0 or not gemm_supported(cin, cout, H * W) or cout % 8 != 0 or (B * H * W) % 256 != 0:
+        return False
+    return bool(f32_out) or packed_out_supported(B, cout, H, W)
+
+
+class GemmMap:
+    """gemm_bf16x3_map(x, wpk, cout) not yet run: what _p2r_fuse hands to gather_add_affine_act in place of the fp32 map where
+    conv1x1_gather_add_supported, so that the GEMM and the fusion tail are one launch."""
+    __slots__ = ("x", "wpk", "cout", "shape")
+
+    def __init__(self, x, wpk, cout):
+        B, _, H, W = x.shape
+        self.x, self.wpk, self.cout, self.shape = x, wpk, cout, (B, cout, H * W)
+
+
+def conv1x1_packed_gather_add_act(x, wpk, cout, t, idx, scale, shift, act=ACT_NONE, hw=None, f32_out=True):
+    """act(scale[c] * ((W @ x)[b,c,j] + t[b,c,idx[b,j]]) + shift[c]) in ONE launch: gemm_bf16x3_map(x, wpk, cout) followed by
+    gather_add_affine_act(., t, idx, scale, shift, act, hw=hw, f32_out=f32_out), bit for bit, with the gather, the folded BatchNorm and
+    the activation in the GEMM's epilogue -- the fp32 map between the two launches is never written.  x: a PackedAct or a map that
+    carries one (conv1x1_gather_add_supported); t f32[B,cout,n]; idx int[B,H*W(,1)]; hw = (H, W) of the map.  Returns what
+    gather_add_affine_act returns: (y f32[B,cout,H*W], PackedAct or None), or the PackedAct alone with f32_out=False.  Inference only."""
+    if not conv1x1_gather_add_supported(x, cout, act, f32_out):
+        raise ValueError("conv1x1_packed_gather_add_act: not built for x %s -> %d channels, act %r, f32_out %r"
+                         % (tuple(x.shape), cout, act, f32_out))
+    xp = _packed_operand(x)
+    B, Cin, H, W = xp.shape
+    if hw is not None and tuple(hw) != (H, W):
+        raise ValueError("conv1x1_packed_gather_add_act: hw %s of a %dx%d map" % (tuple(hw), H, W))
+    t = _dev(t, torch.float32, "t")
+    idx = _idx32(idx, "idx")
+    if tuple(t.shape[:2]) != (B, cout) or idx.numel() != B * H * W:
+        raise ValueError("conv1x1_packed_gather_add_act: t %s idx %s for a [%d,%d,%d,%d] result" % (tuple(t.shape), tuple(idx.shape), B, cout, H, W))
+    if idx.data_ptr() % 16:
+        idx = idx.clone()                            # the epilogue loads four indices at once
+    dev = xp.buf.device
+    y = torch.empty((B, cout, H * W), dtype=torch.float32, device=dev) if f32_out else None
+    opk = None
+    if packed_out_supported(B, cout, H, W):
+        opk = PackedAct(_packed_buffer(B, cout, H, W, dev, avoid=xp.buf), (B, cout, H, W))
+    check(_lib.lib().gdm_conv1x1_gather_add_hip(xp.buf.data_ptr(), wpk.data_ptr(), idx.data_ptr(), t.data_ptr(), t.shape[2],
+                                                scale.data_ptr(), shift.data_ptr(), B, Cin, cout, H, W, act,
+                                                y.data_ptr() if y is not None else None,
+                                                opk.buf.data_ptr() if opk is not None else None, _stream()), "gdm_conv1x1_gather_add_hip")
+    return (y, opk) if f32_out else opk
 
 
 def conv1x1_packed2d(xp, wpk, cout, scale=None, shift=None, act=ACT_NONE, stride=1):

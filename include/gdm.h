@@ -525,6 +525,14 @@ int gdm_conv3x3_strided_hip(const void* xpk, const void* wpk, const float* scale
                             int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream);
 int gdm_conv1x1_strided_hip(const void* xpk, const void* wpk, const float* scale, const float* shift,
                             int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* stream);
+/* The point-to-pixel fusion in one launch: gdm_conv1x1_strided_hip (stride 1, no scale / shift) followed by
+ * gdm_gather_add_affine_act2_hip, bit for bit, with the gather, the folded BatchNorm and the activation in the GEMM's epilogue:
+ * out[b,co,j] = act(scale[co] * (sum_ci W[co,ci] x[b,ci,j] + gt[b,co,clamp(gidx[b,j], 0, gn-1)]) + shift[co]).
+ * gidx int32[B,H*W] (16-byte aligned), gt f32[B,Cout,gn], gn >= 1; Cin a multiple of 128; act 0 (none) or 1 (ReLU).  out f32[B,Cout,H,W]
+ * and / or outpk (the packed operand of the next convolution, as gdm_conv3x3_strided_hip writes it: Cout % 8 == 0, B*H*W % 256 == 0);
+ * either may be NULL, not both.  The packed activations and the packed weights must each stay below 2 GiB. */
+int gdm_conv1x1_gather_add_hip(const void* xpk, const void* wpk, const int32_t* gidx, const float* gt, int gn, const float* scale,
+                               const float* shift, int B, int Cin, int Cout, int H, int W, int act, float* out, void* outpk, void* stream);
 
 /* `final` stage of the image branch (pspnet.py:108-112): out = log_softmax_c(W x + b), x,out f32[B,64,hw], W f32[64,64]. */
 /* ResNet stem tail in one pass (extractors.py:128-131 after conv1): y = MaxPool2d(3, stride 2, padding 1)(relu(scale[c] * x + shift[c])),
