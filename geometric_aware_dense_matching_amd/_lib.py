@@ -76,6 +76,9 @@ SIGNATURES = {
     "gdm_spline_direct3_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gdm_gemm_grouped_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "gdm_spline_pairs_aggregate3_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gdm_spline_pairs_grad_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "gdm_spline_segment_sum_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "gdm_spline_wgrad_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gdm_upsample_bilinear_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _vp, _vp]),
     "gdm_upsample_bilinear_bwd_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _vp, _vp]),
     "gdm_topk_rows_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp]),

@@ -341,7 +341,190 @@ __global__ __launch_bounds__(128) void spline_pairs_aggregate_vec_kernel(const f
     if (out_pk) spline_store_packed(out_pk, M, i, o, r);
 }
 
+// ---- training on the edge-grouped form (SplineCNN_Mesh.train_path = "grouped"): the backward of gemm_grouped + pairs_aggregate without
+// the [M, 125*C] table.  Static inverse maps from splinecnn.build_spline_pairs.
+//
+// Pair gradient, gather form: gY[r, :] = sum over the (edge, corner) uses of pair row r of basis[e,s] * inv_deg[tgt(e)] * g[tgt(e), :],
+// g = go * (out > 0) where the layer has ReLU (out_mask = the layer's output, else NULL).  Every row is written (padding rows have empty
+// lists: zeros), in ascending (edge, corner) order: no atomics, no pre-zeroing, the same bits every run.  Written row-major f32[R, C]
+// (the weight-gradient kernel's operand) and, gy_pk, as the packed split-bf16 operand of the input-gradient grouped GEMM (a [1, C, 1, R]
+// map), so that no pack launch follows.  32 threads x 4 channels per row at C = 128.
+template <bool RELU>
+__global__ __launch_bounds__(128) void spline_pairs_grad_kernel(const float* __restrict__ go, const float* __restrict__ out_mask,
+                                                                const int32_t* __restrict__ pair_ptr, const int32_t* __restrict__ pair_ec,
+                                                                const float* __restrict__ basis, const int32_t* __restrict__ tgt,
+                                                                const float* __restrict__ inv_deg, int R, int C, float* __restrict__ gy,
+                                                                unsigned char* __restrict__ gy_pk)
+{
+    const int tpv = C / 4;
+    const int r = blockIdx.x * (128 / tpv) + threadIdx.x / tpv;
+    const int o = (threadIdx.x % tpv) * 4;
+    if (r >= R) return;
+    const int q0 = pair_ptr[r], q1 = pair_ptr[r + 1];
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = q0; q < q1; ++q) {
+        const int ec = pair_ec[q];
+        const int t = tgt[ec >> 3];
+        const float b = basis[ec] * inv_deg[t];
+        float4 g = *reinterpret_cast<const float4*>(go + (long)t * C + o);
+        if (RELU) {
+            const float4 m = *reinterpret_cast<const float4*>(out_mask + (long)t * C + o);
+            g.x = m.x > 0.f ? g.x : 0.f; g.y = m.y > 0.f ? g.y : 0.f; g.z = m.z > 0.f ? g.z : 0.f; g.w = m.w > 0.f ? g.w : 0.f;
+        }
+        acc.x = fmaf(b, g.x, acc.x); acc.y = fmaf(b, g.y, acc.y); acc.z = fmaf(b, g.z, acc.z); acc.w = fmaf(b, g.w, acc.w);
+    }
+    *reinterpret_cast<float4*>(gy + (long)r * C + o) = acc;
+    if (gy_pk) spline_store_packed(gy_pk, R, r, o, acc);
+}
+
+// Input gradient, second half: dX[j, :] = add[j, :] + sum of Z[r, :] over the pair rows r whose source is j (src_ptr / src_rows, ascending
+// row order: a fixed order).  Z f32[R, C] = gY . W[k(r)]^T from gdm_gemm_grouped_hip; add (may be NULL) carries the root term go . W_root.
+__global__ __launch_bounds__(128) void spline_segment_sum_kernel(const float* __restrict__ z, const int32_t* __restrict__ src_ptr,
+                                                                 const int32_t* __restrict__ src_rows, const float* __restrict__ add,
+                                                                 int M, int C, float* __restrict__ dx)
+{
+    const int tpv = C / 4;
+    const int j = blockIdx.x * (128 / tpv) + threadIdx.x / tpv;
+    const int o = (threadIdx.x % tpv) * 4;
+    if (j >= M) return;
+    float4 acc = add ? *reinterpret_cast<const float4*>(add + (long)j * C + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int q0 = src_ptr[j], q1 = src_ptr[j + 1];
+    for (int q = q0; q < q1; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(z + (long)src_rows[q] * C + o);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    *reinterpret_cast<float4*>(dx + (long)j * C + o) = acc;
+}
+
+// Grouped weight gradient: dW[k] (Cin x 128) = sum over the rows r of kernel index k's block of X[rowidx[r], :]^T . gY[r, :], all kernel
+// indices in one launch, on v_mfma_f32_32x32x2_f32 (exact fp32: a row-ordered fmaf chain, so the weight gradient keeps fp32 accuracy and
+// the same bits every run).  The contraction axis is the block's rows; one MFMA takes two of them, and its operands are what a lane
+// loads straight from memory: lane l holds A[i = l & 31][k = l >> 5] = X[rowidx[r + (l >> 5)], ci0 + (l & 31)] and B[k][j = l & 31] =
+// gY[r + (l >> 5), co0 + (l & 31)] -- each half wave reads 128 contiguous bytes of one row, no LDS, no transposition.
+// The blocks are very uneven (at M = 4096 the central kernel index holds 3987 of 76791 pairs, the mean is 614), and a workgroup that
+// walks a whole block is bound by the latency of its gathered loads.  So the unit of work is one 256-row TILE of the pair rows (a tile
+// belongs to one kernel index: the blocks are padded to whole tiles): workgroup (t, h) writes the partial product of tile t to
+// part[t], and spline_wgrad_reduce_kernel adds the partials of every kernel index in ascending tile order -- a fixed order.
+// 4 waves: Cin = 128 -> grid (tiles, 2), wave w the Cin tile w and two 32-column tiles of its half of the 128 outputs (two independent
+// accumulators); Cin <= 32 (the first layer, rows beyond Cin zero inside the kernel) -> grid (tiles, 1), wave w the column tile w.
+typedef __attribute__((ext_vector_type(16))) float spl_f32x16;
+
+template <int CI_TILES, int NACC>
+__global__ __launch_bounds__(256) void spline_wgrad_kernel(const float* __restrict__ x, const int32_t* __restrict__ rowidx,
+                                                           const float* __restrict__ gy, const int32_t* __restrict__ tile_co0,
+                                                           const int32_t* __restrict__ blk_start, const int32_t* __restrict__ blk_rows,
+                                                           int nk, int Cin, float* __restrict__ part)
+{
+    constexpr int C = 128, U = 16, TILE = 256;                     // U row pairs in flight per iteration
+    const int t = blockIdx.x;
+    const int k = tile_co0[t] / C;
+    if (k < 0 || k >= nk) return;                                  // not a tile of these blocks: its partial is never read
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int half = lane >> 5, l31 = lane & 31;
+    const int ci_t = (wave % CI_TILES) * 32;
+    const int co0 = (blockIdx.y * (4 / CI_TILES) + wave / CI_TILES) * NACC * 32;
+    const long r0 = (long)t * TILE;
+    const int n = min(TILE, blk_start[k] + blk_rows[k] - (int)r0);  // real rows of this tile (<= 0: a tile of padding only)
+    const bool ci_ok = ci_t + l31 < Cin;
+    spl_f32x16 acc[NACC];
+#pragma unroll
+    for (int q = 0; q < NACC; ++q)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[q][v] = 0.f;
+    for (int base = 0; base < n; base += 2 * U) {
+        float a[U], b[U][NACC];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int rr = base + 2 * u + half;
+            a[u] = 0.f;
+#pragma unroll
+            for (int q = 0; q < NACC; ++q) b[u][q] = 0.f;
+            if (rr < n) {
+                const long r = r0 + rr;
+                const int j = rowidx[r];
+                if (ci_ok) a[u] = x[(long)j * Cin + ci_t + l31];
+#pragma unroll
+                for (int q = 0; q < NACC; ++q) b[u][q] = gy[r * C + co0 + 32 * q + l31];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int q = 0; q < NACC; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u][q], acc[q], 0, 0, 0);
+    }
+#pragma unroll
+    for (int q = 0; q < NACC; ++q)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const int ci = ci_t + (v & 3) + 8 * (v >> 2) + 4 * half;      // C/D map of the 32x32 forms: row on the register, column on the lane
+            if (ci < Cin) part[((long)t * Cin + ci) * C + co0 + 32 * q + l31] = acc[q][v];
+        }
+}
+
+// dW[k] = the partials of kernel index k's tiles, added in ascending tile order; a kernel index without rows is written as zeros.
+__global__ __launch_bounds__(256) void spline_wgrad_reduce_kernel(const float* __restrict__ part, const int32_t* __restrict__ blk_start,
+                                                                  const int32_t* __restrict__ blk_rows, int per_k, float* __restrict__ dw)
+{
+    const int k = blockIdx.x;
+    const int i = (blockIdx.y * 256 + threadIdx.x) * 4;
+    if (i >= per_k) return;
+    const int t0 = blk_start[k] / 256, nt = (blk_rows[k] + 255) / 256;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int t = t0; t < t0 + nt; ++t) {
+        const float4 v = *reinterpret_cast<const float4*>(part + (long)t * per_k + i);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    *reinterpret_cast<float4*>(dw + (long)k * per_k + i) = acc;
+}
+
 } // namespace
+
+extern "C" int gdm_spline_pairs_grad_hip(const float* grad_out, const float* out_mask, const int32_t* pair_ptr, const int32_t* pair_ec,
+                                         const float* basis, const int32_t* tgt, const float* inv_deg, int R, int C, float* gy,
+                                         void* gy_packed, void* stream)
+{
+    GDM_CHECK_ARG(grad_out && pair_ptr && pair_ec && basis && tgt && inv_deg && gy, "gdm_spline_pairs_grad_hip: NULL pointer");
+    GDM_CHECK_ARG(R >= 1 && C >= 4 && C % 4 == 0 && C <= 512 && 512 % C == 0, "gdm_spline_pairs_grad_hip: bad shape R=%d C=%d (C %% 4 == 0, 512 %% C == 0)", R, C);
+    GDM_CHECK_ARG(!gy_packed || C % 128 == 0, "gdm_spline_pairs_grad_hip: the packed output needs C = 128, 256 or 512");
+    GDM_CHECK_ARG((((uintptr_t)grad_out | (uintptr_t)out_mask | (uintptr_t)gy) & 15) == 0, "gdm_spline_pairs_grad_hip: buffers must be 16-byte aligned");
+    const dim3 grid(gdm_cdiv(R, 128 / (C / 4)));
+    if (out_mask)
+        hipLaunchKernelGGL(spline_pairs_grad_kernel<true>, grid, dim3(128), 0, (hipStream_t)stream, grad_out, out_mask, pair_ptr, pair_ec, basis,
+                           tgt, inv_deg, R, C, gy, (unsigned char*)gy_packed);
+    else
+        hipLaunchKernelGGL(spline_pairs_grad_kernel<false>, grid, dim3(128), 0, (hipStream_t)stream, grad_out, out_mask, pair_ptr, pair_ec, basis,
+                           tgt, inv_deg, R, C, gy, (unsigned char*)gy_packed);
+    return gdm_launch_status("spline_pairs_grad_kernel");
+}
+
+extern "C" int gdm_spline_segment_sum_hip(const float* z, const int32_t* src_ptr, const int32_t* src_rows, const float* add, int M, int C,
+                                          float* dx, void* stream)
+{
+    GDM_CHECK_ARG(z && src_ptr && src_rows && dx, "gdm_spline_segment_sum_hip: NULL pointer");
+    GDM_CHECK_ARG(M >= 1 && C >= 4 && C % 4 == 0 && C <= 512 && 512 % C == 0, "gdm_spline_segment_sum_hip: bad shape M=%d C=%d (C %% 4 == 0, 512 %% C == 0)", M, C);
+    GDM_CHECK_ARG((((uintptr_t)z | (uintptr_t)add | (uintptr_t)dx) & 15) == 0, "gdm_spline_segment_sum_hip: buffers must be 16-byte aligned");
+    hipLaunchKernelGGL(spline_segment_sum_kernel, dim3(gdm_cdiv(M, 128 / (C / 4))), dim3(128), 0, (hipStream_t)stream, z, src_ptr, src_rows, add, M, C, dx);
+    return gdm_launch_status("spline_segment_sum_kernel");
+}
+
+extern "C" int gdm_spline_wgrad_hip(const float* x, const int32_t* rowidx, const float* gy, const int32_t* tile_co0, const int32_t* blk_start,
+                                    const int32_t* blk_rows, int nk, int R, int Cin, int C, float* part, float* dw, void* stream)
+{
+    GDM_CHECK_ARG(x && rowidx && gy && tile_co0 && blk_start && blk_rows && part && dw, "gdm_spline_wgrad_hip: NULL pointer");
+    GDM_CHECK_ARG(nk >= 1 && R >= 256 && R % 256 == 0 && C == 128 && ((Cin >= 1 && Cin <= 32) || Cin == 128),
+                  "gdm_spline_wgrad_hip: nk=%d R=%d (multiple of 256) Cin=%d (<= 32 or 128) C=%d (128)", nk, R, Cin, C);
+    GDM_CHECK_ARG((((uintptr_t)part | (uintptr_t)dw) & 15) == 0, "gdm_spline_wgrad_hip: part and dw must be 16-byte aligned");
+    const int tiles = R / 256;
+    if (Cin == 128)
+        hipLaunchKernelGGL((spline_wgrad_kernel<4, 2>), dim3(tiles, 2), dim3(256), 0, (hipStream_t)stream, x, rowidx, gy, tile_co0, blk_start, blk_rows, nk, Cin, part);
+    else
+        hipLaunchKernelGGL((spline_wgrad_kernel<1, 1>), dim3(tiles, 1), dim3(256), 0, (hipStream_t)stream, x, rowidx, gy, tile_co0, blk_start, blk_rows, nk, Cin, part);
+    const int rc = gdm_launch_status("spline_wgrad_kernel");
+    if (rc != 0) return rc;
+    const int per_k = Cin * C;                                      // a multiple of 128
+    hipLaunchKernelGGL(spline_wgrad_reduce_kernel, dim3(nk, gdm_cdiv(per_k, 1024)), dim3(256), 0, (hipStream_t)stream, part, blk_start, blk_rows, per_k, dw);
+    return gdm_launch_status("spline_wgrad_reduce_kernel");
+}
 
 extern "C" int gdm_spline_pairs_aggregate3_hip(const float* Y, const int32_t* rowptr, const int32_t* pos, const float* basis,
                                                const float* root, const float* bias, int M, int C, int relu, float* out, float* out_t,

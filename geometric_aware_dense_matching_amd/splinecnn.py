@@ -11,6 +11,8 @@ published definitions (see csrc/gdm_spline.hip and DESIGN.md: parity unpinned fo
 MI355X formulation: the dense part of SplineConv is one GEMM X @ [W_0|...|W_124]
 (hipBLASLt through torch.matmul), the sparse part (basis, 8-row gather, mean, root, bias, ReLU) is
 one HIP kernel over CSR edges (ops below).  The graph's kNN runs on the HIP kNN kernel.
+Inference runs the edge-grouped form instead (only the (source, kernel index) pairs some edge needs are multiplied, no table), and so
+does training with `SplineCNN_Mesh.train_path = "grouped"`, whose backward gathers through the inverse maps of build_spline_pairs.
 
 The embedding is input independent (`forward()` takes no arguments, SplineCNN.py:234); the
 reference nevertheless recomputes it on every GeoMatch.forward (geoMatch.py:179).  `forward`
@@ -22,6 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib, ops, settings
 from ._lib import check
@@ -57,6 +60,131 @@ class _SplineAggregate(torch.autograd.Function):
                                                       M, C, KERNEL_SIZE, gxw.data_ptr(), ops._stream()),
               "gdm_spline_aggregate_bwd_hip")
         return gxw, go, go.sum(dim=0), None, None, None, None
+
+
+def _pairs_grad(go, out, pairs, relu, want_packed):
+    """gY f32[R,C] of the pair rows (gdm_spline_pairs_grad_hip: gather form, ReLU mask inside), and its packed operand if wanted."""
+    M, C = go.shape
+    R = pairs["rowidx"].shape[0]
+    gy = torch.empty((R, C), dtype=torch.float32, device=go.device)
+    pk = ops.spline_packed_buffer(C, R, go.device) if want_packed else None
+    check(_lib.lib().gdm_spline_pairs_grad_hip(go.data_ptr(), out.data_ptr() if relu else None, pairs["pair_ptr"].data_ptr(),
+                                               pairs["pair_ec"].data_ptr(), pairs["basis"].data_ptr(), pairs["tgt"].data_ptr(),
+                                               pairs["inv_deg"].data_ptr(), R, C, gy.data_ptr(), pk.data_ptr() if pk is not None else None,
+                                               ops._stream()), "gdm_spline_pairs_grad_hip")
+    return gy, pk
+
+
+def _spline_wgrad(x, gy, pairs, cin, cout):
+    """dW f32[125,cin,cout] = per kernel index X[rowidx]^T gY over its block of pair rows (gdm_spline_wgrad_hip, exact-fp32 MFMA:
+    per-tile partial products, then their sum in ascending tile order)."""
+    nk = KERNEL_SIZE ** 3
+    R = pairs["rowidx"].shape[0]
+    dw = torch.empty((nk, cin, cout), dtype=torch.float32, device=x.device)
+    part = torch.empty((R // 256, cin, cout), dtype=torch.float32, device=x.device)          # per-tile partial products
+    check(_lib.lib().gdm_spline_wgrad_hip(x.data_ptr(), pairs["rowidx"].data_ptr(), gy.data_ptr(), pairs["tile_co0"].data_ptr(),
+                                          pairs["blk_start"].data_ptr(), pairs["blk_rows"].data_ptr(), nk, R, cin, cout, part.data_ptr(),
+                                          dw.data_ptr(), ops._stream()), "gdm_spline_wgrad_hip")
+    return dw
+
+
+def _train_gemm_weight(conv, tag, w, make):
+    """Packed split-bf16 GEMM weight made from the tensor `w` the Function was given (or saved), cached on `conv` under `tag` until
+    `w` changes.  While a hipGraph is being captured the pack runs (and is captured) every time: a cache hit there would leave the
+    pack out of the graph, and replays after an optimizer step would multiply by stale weights."""
+    if torch.cuda.is_current_stream_capturing():
+        with torch.no_grad():
+            return ops.gemm_pack_weight(make(w).contiguous())
+    return cached_gemm_weight(conv, tag, lambda: make(w), (w,))[0]
+
+
+def _train_root_t(conv, lin_weight):
+    """lin_weight^T (the slot SplineConv._root_t fills) from the tensor the Function was given; recomputed (and captured) while a
+    hipGraph is being captured, as _train_gemm_weight."""
+    if torch.cuda.is_current_stream_capturing():
+        with torch.no_grad():
+            return lin_weight.t().contiguous()
+    return derived(conv, "root_t", (lin_weight,), lambda: lin_weight.t().contiguous())
+
+
+class _SplineDirectTrain(torch.autograd.Function):
+    """First layer (cin <= 16, input without gradient) in training: the forward is gdm_spline_direct3_hip as in inference; the backward
+    gathers the pair gradient gY and forms dW on the grouped weight-gradient kernel.  Saved: x, out and the static maps -- no table."""
+
+    @staticmethod
+    def forward(ctx, x, weight, lin_weight, bias, conv, rowptr, src, attr, pairs, relu):
+        M = x.shape[0]
+        out = torch.empty((M, conv.cout), dtype=torch.float32, device=x.device)
+        root_t = _train_root_t(conv, lin_weight)
+        check(_lib.lib().gdm_spline_direct3_hip(x.data_ptr(), weight.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
+                                                root_t.data_ptr(), bias.data_ptr(), M, conv.cin, conv.cout, KERNEL_SIZE, int(relu),
+                                                out.data_ptr(), None, None, ops._stream()), "gdm_spline_direct3_hip")
+        ctx.save_for_backward(x, out)
+        ctx.pairs, ctx.relu, ctx.dims = pairs, relu, (conv.cin, conv.cout)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, go):
+        x, out = ctx.saved_tensors
+        go = go.contiguous()
+        cin, cout = ctx.dims
+        gy, _ = _pairs_grad(go, out, ctx.pairs, ctx.relu, False)
+        dw = _spline_wgrad(x, gy, ctx.pairs, cin, cout)
+        g = go * (out > 0).to(go.dtype) if ctx.relu else go
+        return None, dw, g.t() @ x, g.sum(dim=0), None, None, None, None, None, None
+
+
+class _SplineGroupedTrain(torch.autograd.Function):
+    """128 -> 128 layer in training on the edge-grouped form.  Forward: the launches of the inference path (pack, gdm_gemm_grouped_hip,
+    root product, gdm_spline_pairs_aggregate3_hip).  Backward: gY by gather over the pair -> (edge, corner) lists; dX = segment sum
+    over the source -> pair-row lists of Z = gY . W[k]^T (the same grouped GEMM, identity gather) + g . W_root; dW on the grouped
+    weight-gradient kernel.  Saved: x, out and the static maps; Y is not kept."""
+
+    @staticmethod
+    def forward(ctx, x, weight, lin_weight, bias, conv, rowptr, pairs, relu):
+        M = x.shape[0]
+        nk = KERNEL_SIZE ** 3
+        wpk = _train_gemm_weight(conv, "dense", weight, lambda w: w.permute(0, 2, 1).reshape(nk * conv.cout, conv.cin))
+        xt = x.t().contiguous().unsqueeze(0)
+        Y = ops.gemm_grouped(xt, wpk, pairs["rowidx"], pairs["tile_co0"], nk * conv.cout)
+        if settings.USE_POINTWISE:
+            root = ops.pointwise([xt], _train_root_t(conv, lin_weight), point_major=True).view(M, conv.cout)
+        else:
+            root = x @ lin_weight.t()
+        out = torch.empty((M, conv.cout), dtype=torch.float32, device=x.device)
+        check(_lib.lib().gdm_spline_pairs_aggregate3_hip(Y.data_ptr(), rowptr.data_ptr(), pairs["pos"].data_ptr(), pairs["basis"].data_ptr(),
+                                                         root.data_ptr(), bias.data_ptr(), M, conv.cout, int(relu), out.data_ptr(),
+                                                         None, None, ops._stream()), "gdm_spline_pairs_aggregate3_hip")
+        ctx.save_for_backward(x, out, weight, lin_weight)
+        ctx.conv, ctx.pairs, ctx.relu = conv, pairs, relu
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, go):
+        x, out, weight, lin_weight = ctx.saved_tensors          # the saved weights: an in-place update since the forward raises here
+        conv, pairs = ctx.conv, ctx.pairs
+        go = go.contiguous()
+        M = x.shape[0]
+        nk = KERNEL_SIZE ** 3
+        R = pairs["rowidx"].shape[0]
+        gy, pk = _pairs_grad(go, out, pairs, ctx.relu, ctx.needs_input_grad[0])
+        g = go * (out > 0).to(go.dtype) if ctx.relu else go
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # Z[r, :] = gY[r, :] . W[k(r)]^T: rows of weight.reshape(125*cin, cout) are (k, ci); cin == cout, so tile_co0 = k*cin as it stands
+            wpk = _train_gemm_weight(conv, "dgrad", weight, lambda w: w.reshape(nk * conv.cin, conv.cout))
+            Z = torch.empty((R, conv.cin), dtype=torch.float32, device=x.device)
+            L = _lib.lib()
+            check(L.gdm_gemm_grouped_hip(pk.data_ptr(), wpk.data_ptr(), pairs["rowid"].data_ptr(), pairs["tile_co0"].data_ptr(), R, R, conv.cout,
+                                         nk * conv.cin, Z.data_ptr(), ops._stream()), "gdm_gemm_grouped_hip")
+            add = g @ lin_weight
+            dx = torch.empty((M, conv.cin), dtype=torch.float32, device=x.device)
+            check(L.gdm_spline_segment_sum_hip(Z.data_ptr(), pairs["src_ptr"].data_ptr(), pairs["src_rows"].data_ptr(), add.data_ptr(), M,
+                                               conv.cin, dx.data_ptr(), ops._stream()), "gdm_spline_segment_sum_hip")
+        dw = _spline_wgrad(x, gy, pairs, conv.cin, conv.cout)
+        return dx, dw, g.t() @ x, g.sum(dim=0), None, None, None, None
 
 
 class SplineConv(nn.Module):
@@ -115,6 +243,23 @@ class SplineConv(nn.Module):
                                                          out_t.data_ptr(), pk.data_ptr() if pk is not None else None, ops._stream()),
               "gdm_spline_pairs_aggregate3_hip")
         return out_t, pk
+
+    def train_grouped_ok(self, x, pairs):
+        """Whether forward_train_grouped serves this layer: a first layer (cin <= 16, input without gradient) or a 128 -> 128 layer,
+        on the GPU, with the pairs' inverse maps."""
+        if not (x.is_cuda and pairs is not None and "inv_deg" in pairs and self.cout == 128 and self.lin.bias is None):
+            return False
+        if self.cin <= 16:
+            return not x.requires_grad
+        return self.cin == 128 and settings.USE_MFMA_GEMM and settings.USE_GROUPED_SPLINE
+
+    def forward_train_grouped(self, x, rowptr, src, attr, relu, pairs):
+        """Differentiable layer without the [M, 125*cout] table (SplineCNN_Mesh.train_path = "grouped"): same launches as inference
+        forward, gather-form backward (_SplineDirectTrain / _SplineGroupedTrain)."""
+        x = x.contiguous()
+        if self.cin <= 16:
+            return _SplineDirectTrain.apply(x, self.weight, self.lin.weight, self.bias, self, rowptr, src, attr, pairs, relu)
+        return _SplineGroupedTrain.apply(x, self.weight, self.lin.weight, self.bias, self, rowptr, pairs, relu)
 
     def forward(self, x, rowptr, src, attr, relu=False, pairs=None):
         M = x.shape[0]
@@ -184,10 +329,18 @@ def build_mesh_graph(pos, k=4):
     return torch.stack([row, col], dim=0), cart
 
 
-def build_spline_pairs(src, attr, M, cout=128):
+def build_spline_pairs(src, attr, M, cout=128, rowptr=None):
     """Static bookkeeping of the edge-grouped SplineConv: the unique (source vertex, kernel index) pairs the edges need, sorted by
     kernel index and padded per kernel index to whole 256-row tiles.  src i32[E] / attr f32[E,3] in CSR (target-sorted) order.
-    -> dict(rowidx i32[R], tile_co0 i32[R/256], pos i32[E,8], basis f32[E,8]).  Same fp32 arithmetic as spline_aggregate_kernel."""
+    -> dict(rowidx i32[R], tile_co0 i32[R/256], pos i32[E,8], basis f32[E,8]).  Same fp32 arithmetic as spline_aggregate_kernel.
+
+    Given rowptr i32[M+1] (the CSR the edges are sorted by), also the inverse maps the training path (SplineCNN_Mesh.train_path =
+    "grouped") reads, built with torch ops that run on CPU tensors too (SplineCNN_Mesh builds them the first time that path is taken):
+      pair_ptr i32[R+1], pair_ec i32[8E]   pair row -> its (edge, corner) uses e*8+s, ascending; padding rows have empty lists
+      src_ptr i32[M+1], src_rows i32[U]    source vertex -> its pair rows, ascending; the U real pairs only, never a padding row
+      blk_start, blk_rows i32[125]         first row and row count of every kernel index' block, padding excluded
+      rowid i32[R]                         0..R-1: the identity gather of the input-gradient GEMM
+      tgt i32[E], inv_deg f32[M]           target vertex of every edge; 1 / in-degree (0 for a vertex without incoming edges)"""
     ks = KERNEL_SIZE
     v = attr * float(ks - 1)
     f = torch.floor(v)
@@ -217,11 +370,39 @@ def build_spline_pairs(src, attr, M, cout=128):
     tile_k = torch.repeat_interleave(torch.arange(ks ** 3, device=src.device), padded // 256)
     tile_co0 = torch.zeros(R // 256, dtype=torch.int32, device=src.device)
     tile_co0[: tile_k.shape[0]] = (tile_k * cout).to(torch.int32)
-    return dict(rowidx=rowidx.contiguous(), tile_co0=tile_co0.contiguous(), pos=row[inv].view(E, 8).to(torch.int32).contiguous(),
-                basis=basis.contiguous())
+    pairs = dict(rowidx=rowidx.contiguous(), tile_co0=tile_co0.contiguous(), pos=row[inv].view(E, 8).to(torch.int32).contiguous(),
+                 basis=basis.contiguous())
+    if rowptr is None:
+        return pairs
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    ptr = lambda counts_: torch.cat((counts_.new_zeros(1), torch.cumsum(counts_, 0)))
+    pos_flat = row[inv]                                                # pair row of every (edge, corner), flat index e*8+s
+    pairs["pair_ptr"] = i32(ptr(torch.bincount(pos_flat, minlength=R)))
+    pairs["pair_ec"] = i32(torch.argsort(pos_flat, stable=True))       # stable: ascending (edge, corner) inside a row
+    pair_src = uniq % M                                                # `row` ascends with the unique-pair id
+    pairs["src_ptr"] = i32(ptr(torch.bincount(pair_src, minlength=M)))
+    pairs["src_rows"] = i32(row[torch.argsort(pair_src, stable=True)])
+    pairs["blk_start"] = i32(start)
+    pairs["blk_rows"] = i32(counts)
+    pairs["rowid"] = torch.arange(R, dtype=torch.int32, device=src.device)
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
+    pairs["tgt"] = i32(torch.repeat_interleave(torch.arange(M, device=src.device), deg))
+    pairs["inv_deg"] = torch.where(deg > 0, 1.0 / deg.clamp(min=1).to(torch.float32), torch.zeros((), device=src.device)).contiguous()
+    return pairs
 
 
 class SplineCNN_Mesh(nn.Module):
+    """The mesh branch.  `train_path` selects how the SplineConv layers run when autograd records them:
+      "dense"    (default) X @ [W_0|...|W_124] into an [M, 125*C] table on the library GEMM, kept for the backward, whose gradient
+                 table is filled with atomics (SplineConv.forward's last branch);
+      "grouped"  the edge-grouped launches of inference with a gather-form backward (SplineConv.forward_train_grouped): no table, no
+                 atomics, the same gradient bits every run.
+    "grouped" is taken when ALL of these hold, and the dense path silently otherwise (as the eval predicates do): the module is in
+    training mode with grad enabled, on the GPU, `self._pairs` exists (out_channels == 128), the first layer has cin <= 16 and an input
+    that does not require grad, every later layer is 128 -> 128, and settings.USE_MFMA_GEMM / USE_GROUPED_SPLINE are on.  torch.cat,
+    F.dropout and mesh_final are torch modules on both paths, so both draw the same dropout mask from the same seed."""
+    train_path = "dense"
+
     def __init__(self, cfg, idx, mesh_in_channels=9, out_channels=128, mesh_coord_dim=3, num_mesh_layers=3,
                  cat=True, lin=True, dropout=0.1, model_points=None):
         """cfg keys as the reference (SplineCNN.py:108-110): model_pth, n_mesh_node, model_name.
@@ -340,12 +521,29 @@ class SplineCNN_Mesh(nn.Module):
         out = ops.pointwise(segs, derived(self.mesh_final, "wt", (w,), lambda: w.t().contiguous()), None, self.mesh_final.bias)     # [1, 128, M]; eval: dropout is the identity
         return out[0]
 
+    def _train_grouped_ok(self):
+        convs = list(self.mesh_convs)
+        if (self.train_path == "grouped" and self.training and torch.is_grad_enabled() and self._pairs is not None
+                and "inv_deg" not in self._pairs):
+            # the inverse maps of the backward: built the first time the path is asked for, never for inference or the dense path
+            self._pairs = build_spline_pairs(self._csr[1], self._csr[2], self.xyz.shape[0], self.out_channels, rowptr=self._csr[0])
+        return (self.train_path == "grouped" and self.training and torch.is_grad_enabled() and self.xyz.is_cuda and self._pairs is not None
+                and settings.USE_MFMA_GEMM and settings.USE_GROUPED_SPLINE and len(convs) >= 1
+                and convs[0].cin <= 16 and not self.mesh_graph_x.requires_grad and convs[0].train_grouped_ok(self.mesh_graph_x, self._pairs)
+                and all(c.cin == 128 and c.cout == 128 and c.lin.bias is None for c in convs[1:]))
+
     def forward(self):
+        if self.train_path not in ("dense", "grouped"):
+            raise ValueError("train_path must be 'dense' or 'grouped', got %r" % (self.train_path,))
         rowptr, src, attr = self._ensure_graph()
         if self._channel_major_ok():
             return self._forward_channel_major(rowptr, src, attr)
+        grouped = self._train_grouped_ok()
         feats = [self.mesh_graph_x]
         for conv in self.mesh_convs:
+            if grouped:
+                feats.append(conv.forward_train_grouped(feats[-1], rowptr, src, attr, True, self._pairs))
+                continue
             feats.append(conv(feats[-1], rowptr, src, attr, relu=True, pairs=self._pairs))   # F.relu(conv(...)) (SplineCNN.py:238-239)
         out = torch.cat(feats, dim=-1) if self.cat else feats[-1]
         out = F.dropout(out, p=self.dropout, training=self.training)

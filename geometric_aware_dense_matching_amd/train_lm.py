@@ -99,6 +99,10 @@ def build_parser():
                    help="train, --model-variant dgcnn: 'modules' = dense distances and library convolutions on edge tensors; 'fused' = "
                         "feature-space kNN with no N x N matrix and ops.edge_block_train stages with no edge tensor (same parameters, "
                         "interchangeable checkpoints)")
+    p.add_argument("--mesh-train-path", dest="mesh_train_path", type=str, default="dense", choices=["dense", "grouped"],
+                   help="train: how the SplineConv layers of the mesh branch run (splinecnn.SplineCNN_Mesh.train_path): 'dense' = the "
+                        "[M, 125*C] table on the library GEMM with an atomic backward; 'grouped' = the edge-grouped launches of inference "
+                        "with a gather-form backward, no table, reproducible gradients (same parameters, interchangeable checkpoints)")
     p.add_argument("--gt-targets", dest="gt_targets", type=str, default="loader", choices=GT_TARGETS,
                    help="train: 'loader' = labels / match_idx / visible_flag come with the items; 'device' = computed on the GPU from the "
                         "items' RT and origin_labels (get_pose_gt_info, linemod_pbr.py:602-655; targets.pose_gt_info), invalid items "
@@ -356,9 +360,18 @@ def build_model(args, cls_id, cache_mesh_in_eval=False):
         from .geoMatch_DGCNN import GeoMatch as GeoMatchDGCNN
         model = GeoMatchDGCNN(make_dgcnn_cfg(n_mesh_node=args.n_mesh, dataset=args.dataset_name), cls_id, model_points=pts)
         model.train_path = getattr(args, "dgcnn_train_path", "modules")
-        return model
+        return _set_mesh_train_path(model, args)
     cfg = make_model_cfg(n_mesh_node=args.n_mesh, num_points=args.n_points, dataset=args.dataset_name)
-    return GeoMatch(cfg, cls_id, model_points=pts, cache_mesh_in_eval=cache_mesh_in_eval)
+    return _set_mesh_train_path(GeoMatch(cfg, cls_id, model_points=pts, cache_mesh_in_eval=cache_mesh_in_eval), args)
+
+
+def _set_mesh_train_path(model, args):
+    """--mesh-train-path onto the model's SplineCNN mesh branch, where the variant has one."""
+    from .splinecnn import SplineCNN_Mesh
+    emb = getattr(model, "model_emb", None)
+    if isinstance(emb, SplineCNN_Mesh):
+        emb.train_path = getattr(args, "mesh_train_path", "dense")
+    return model
 
 
 def obj_name_of(ds, cls_id):

@@ -210,6 +210,28 @@ int gdm_gemm_grouped_hip(const void* xpk, const void* wpk, const int32_t* rowidx
 int gdm_spline_pairs_aggregate3_hip(const float* Y, const int32_t* rowptr, const int32_t* pos, const float* basis,
                                     const float* root, const float* bias, int M, int C, int relu, float* out, float* out_t,
                                     void* out_packed, void* stream);
+/* Training on the edge-grouped form: the backward of gdm_gemm_grouped_hip + gdm_spline_pairs_aggregate3_hip, no [M, 125*C] table, no
+ * atomics (every sum in a fixed order).  Static inverse maps of the pairs: pair_ptr i32[R+1] / pair_ec i32[8E] (the (edge, corner) uses
+ * e*8+s of every pair row, ascending; padding rows empty), tgt i32[E] (target vertex of every edge), inv_deg f32[M] (1 / in-degree),
+ * src_ptr i32[M+1] / src_rows i32[U] (the pair rows of every source vertex, ascending), blk_start / blk_rows i32[nk] (first row and
+ * row count of every kernel index' block, padding excluded).
+ * gdm_spline_pairs_grad_hip: gy[r, :] = sum_{(e,s) in pair r} basis[e,s] * inv_deg[tgt e] * g[tgt e, :], g = grad_out masked by
+ *   out_mask > 0 (the layer's output f32[M,C], ReLU layers) or grad_out itself (out_mask NULL); every one of the R rows is written.
+ *   gy f32[R,C]; gy_packed (may be NULL): the same as the packed split-bf16 operand of a [1,C,1,R] map (gdm_conv3x3_act_bytes bytes, zero
+ *   border kept by the caller) for the input-gradient GEMM  Z = gdm_gemm_grouped_hip(gy_packed, W packed from weight.reshape(nk*Cin, C),
+ *   rowidx = 0..R-1, tile_co0 = k*Cin).
+ * gdm_spline_segment_sum_hip: dx[j, :] = add[j, :] (add may be NULL) + sum_{r in src_rows[src_ptr[j] : src_ptr[j+1]]} z[r, :].
+ * gdm_spline_wgrad_hip: dw[k] f32[Cin,C] = sum_{r in block k} x[rowidx[r], :]^T gy[r, :] for all nk kernel indices on the exact-fp32
+ *   MFMA (v_mfma_f32_32x32x2_f32): one launch forms the partial product of every 256-row tile (tile_co0 i32[R/256] = k*C names its
+ *   kernel index) in part f32[R/256, Cin, C] (workspace, no initialisation needed), a second adds each kernel index' partials in
+ *   ascending tile order.  x f32[M,Cin], Cin = 128 or <= 32, C = 128; empty blocks are written as zeros. */
+int gdm_spline_pairs_grad_hip(const float* grad_out, const float* out_mask, const int32_t* pair_ptr, const int32_t* pair_ec,
+                              const float* basis, const int32_t* tgt, const float* inv_deg, int R, int C, float* gy,
+                              void* gy_packed, void* stream);
+int gdm_spline_segment_sum_hip(const float* z, const int32_t* src_ptr, const int32_t* src_rows, const float* add, int M, int C,
+                               float* dx, void* stream);
+int gdm_spline_wgrad_hip(const float* x, const int32_t* rowidx, const float* gy, const int32_t* tile_co0, const int32_t* blk_start,
+                         const int32_t* blk_rows, int nk, int R, int Cin, int C, float* part, float* dw, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Bilinear resize, align_corners=True, NCHW fp32 (models/cnn/pspnet.py:26-29,38).
