@@ -13,8 +13,10 @@ sampling of N points with wrap-around padding (:476-496), `cld_rgb_nrm` / `choos
   make_inputs_from_boxes  raw uint8 rgb + depth + K + box (+ mask) -> the input dict, no host step and no host synchronisation;
                           depth_fill=None is the LineMOD item, "multiscale" / "fast" the YCB-V item
                           (/root/reference/datasets/ycbv/ycbv_pbr.py:458-509)
+                          sampler="hash": the N points by the written rule of include/gdm.h and the assembly in one launch
+                          (ops.sample_assemble, csrc/gdm_sample.hip) instead of sample_valid_pixels and the torch gathers
 
-`depth_normals_numpy`, `crop_from_boxes_numpy` and `fill_depth_numpy` restate the kernels' definitions on the CPU (as
+`depth_normals_numpy`, `crop_from_boxes_numpy`, `fill_depth_numpy` and `sample_assemble_numpy` restate the kernels' definitions on the CPU (as
 targets.spherical_flip does for the flip); the device results equal them value for value, up to the fp32 rounding of the bilateral
 filter's exponentials in the last stage of the fill.  Parity with normalSpeed and with a given cv2 build is unpinned (DESIGN.md 6d,
 6e)."""
@@ -334,6 +336,53 @@ def fill_depth_numpy(depth, mode="multiscale", max_depth=100.0, return_stages=Fa
     return out, {k: st[k] for k in sorted(st)}
 
 
+def _mix32(x):
+    """lowbias32 on uint32 arrays (include/gdm.h; the same function as pose._mix32)."""
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def sample_keys(B, P, seed=0):
+    """key(p) of include/gdm.h gdm_sample_assemble_hip for every crop and pixel: u32[B,P]."""
+    with np.errstate(over="ignore"):
+        hb = _mix32(_mix32(np.uint32(int(seed) & 0xffffffff) ^ np.uint32(0x9e3779b9)) ^ np.arange(B, dtype=np.uint32))
+        return _mix32(hb[:, None] ^ np.arange(P, dtype=np.uint32)[None, :])
+
+
+def sample_assemble_numpy(valid_depth, dpt_xyz, rgb, normals, mask, N, seed=0):
+    """The definition of `ops.sample_assemble` (include/gdm.h gdm_sample_assemble_hip) restated on the CPU: valid_depth f32[B,S,S]
+    (or [B,P]), dpt_xyz f32[B,S,S,3], rgb f32[B,3,S,S], normals f32[B,3,S,S], mask u8[B,S,S] or None -> choose i32[B,N],
+    cld_rgb_nrm f32[B,9,N], labels u8[B,N] (None without a mask), n_valid i32[B]."""
+    vd = np.asarray(valid_depth, dtype=np.float32)
+    B = vd.shape[0]
+    vd = vd.reshape(B, -1)
+    P = vd.shape[1]
+    xyz = np.asarray(dpt_xyz, dtype=np.float32).reshape(B, P, 3)
+    rgb = np.asarray(rgb, dtype=np.float32).reshape(B, 3, P)
+    nrm = np.asarray(normals, dtype=np.float32).reshape(B, 3, P)
+    with np.errstate(invalid="ignore"):
+        valid = vd > np.float32(1e-6)                              # NaN and negative depth compare false
+    keys = sample_keys(B, P, seed)
+    choose = np.zeros((B, N), np.int32)
+    n_valid = valid.sum(axis=1).astype(np.int32)
+    for b in range(B):
+        pix = np.nonzero(valid[b])[0]
+        if pix.size:
+            order = pix[np.argsort(keys[b, pix], kind="stable")]   # the keys of a crop are distinct: no tie to break
+            choose[b] = order[np.arange(N) % pix.size]
+    ch3 = np.repeat(choose[:, None, :], 3, axis=1).astype(np.int64)                    # [B,3,N]
+    cld_rgb_nrm = np.concatenate([np.take_along_axis(xyz.transpose(0, 2, 1), ch3, axis=2), np.take_along_axis(rgb, ch3, axis=2),
+                                  np.take_along_axis(nrm, ch3, axis=2)], axis=1).astype(np.float32)
+    labels = None
+    if mask is not None:
+        lab = np.take_along_axis(np.asarray(mask, dtype=np.uint8).reshape(B, P), choose.astype(np.int64), axis=1)
+        labels = np.where(lab == 255, np.uint8(1), lab).astype(np.uint8)
+    return choose, cld_rgb_nrm, labels, n_valid
+
+
 _fill_workspace = {}                                           # device -> the grow-only workspace of fill_depth
 
 
@@ -351,9 +400,12 @@ def fill_depth(depth, mode="multiscale", max_depth=100.0, return_stages=False, e
     B, H, W = depth.shape
     lib, m = _lib.lib(), FILL_MODES[mode]
     need = lib.gdm_fill_depth_workspace_bytes(B, H, W, m)
-    ws = _fill_workspace.get(depth.device)
-    if need and (ws is None or ws.numel() < need):
-        ws = _fill_workspace[depth.device] = torch.empty(need, dtype=torch.uint8, device=depth.device)
+    if need and ops._pool is not ops._default_pool:                # inside a BufferPool scope (a captured step): the owner's scratch buffer,
+        ws = ops._workspace(need, depth.device)                    # which no later, larger call can replace under the graph
+    else:
+        ws = _fill_workspace.get(depth.device)
+        if need and (ws is None or ws.numel() < need):
+            ws = _fill_workspace[depth.device] = torch.empty(need, dtype=torch.uint8, device=depth.device)
     out = torch.empty_like(depth)
     stages = torch.empty((FILL_STAGES, B, H, W), dtype=torch.float32, device=depth.device) if return_stages else None
     check(lib.gdm_fill_depth_hip(depth.data_ptr(), B, H, W, m, float(max_depth), ws.data_ptr() if need else None,
@@ -446,7 +498,7 @@ def crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=None):
 
 
 def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, train=False, generator=None, normals=None,
-                           depth_fill=None):
+                           depth_fill=None, sampler="torch", seed=0, build_pyramid=True):
     """The whole item from the raw frame: rgb_u8 u8[B,H,W,3], depth f32[B,H,W] (m), K f32[B,3,3], bbox_xyxy f32[B,4], mask
     u8[B,H,W] or None -> the dict of `make_inputs` (rgb, cld_rgb_nrm, choose, dpt_xyz, origin_labels with a mask, the neighbour
     pyramid) plus n_valid i32[B], the number of depth > 1e-6 pixels of each crop (the loader drops a training item below 200,
@@ -459,7 +511,15 @@ def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, 
     fill_depth on the cropped depth -> depth_normals of the filled crop with the frame's own K (the reference passes fx, fy unchanged)
     -> sample_valid_pixels among the FILLED pixels (filled > 1e-6, which n_valid then counts) -> assembly -> pyramid.  The dict also
     holds depth_filled f32[B,S,S].  As in the reference (:506), cld is gathered from the crop's UNFILLED dpt_xyz, so a point chosen
-    inside a filled hole has xyz = (0,0,0) while its normal comes from the filled surface; `normals` is not taken here."""
+    inside a filled hole has xyz = (0,0,0) while its normal comes from the filled surface; `normals` is not taken here.
+
+    sampler="torch" (the default) draws the points with sample_valid_pixels from `generator`.  sampler="hash" replaces
+    sample_valid_pixels and the assembly on either leg with ONE launch, ops.sample_assemble: the points follow the written rule of
+    include/gdm.h (restated as sample_assemble_numpy) from `seed`, an int or a one-element int32 device tensor; `generator` then only
+    feeds the box jitter of train=True.  build_pyramid=False leaves the neighbour pyramid to the caller (infer.pipeline_step builds it
+    when the dict lacks it)."""
+    if sampler not in ("torch", "hash"):
+        raise ValueError("sampler must be 'torch' or 'hash', got %r" % (sampler,))
     B, H, W = depth.shape
     center, scale = dzi_boxes(bbox_xyxy, (H, W), train=train, generator=generator)
     extra = {}
@@ -468,17 +528,30 @@ def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, 
             normals = depth_normals(depth, K)
         crop = crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=mask)
         xyz, nrm = crop["dpt_xyz"], crop["normals"]
-        valid = crop["depth"] > 1e-6
-        choose = sample_valid_pixels(xyz, n_points, generator)                       # [B,1,N]
+        valid_depth = crop["depth"]
+        if sampler == "torch":
+            choose = sample_valid_pixels(xyz, n_points, generator)                   # [B,1,N]
     else:
         if normals is not None:
             raise ValueError("normals= goes with depth_fill=None: the YCB-V item takes its normals from the filled crop")
         crop = crop_from_boxes(rgb_u8, depth, None, K, center, scale, S, mask=mask)
         filled = fill_depth(crop["depth"], mode=depth_fill)
         xyz, nrm = crop["dpt_xyz"], depth_normals(filled, K)
-        valid = filled > 1e-6
-        choose = sample_valid_pixels(xyz, n_points, generator, valid=valid)
+        valid_depth = filled
+        if sampler == "torch":
+            choose = sample_valid_pixels(xyz, n_points, generator, valid=filled > 1e-6)
         extra["depth_filled"] = filled
+    if sampler == "hash":
+        ch, cld_rgb_nrm, labels, n_valid = ops.sample_assemble(valid_depth, xyz, crop["rgb"], nrm, n_points, mask=crop.get("mask"),
+                                                               seed=seed)
+        inputs = dict(rgb=crop["rgb"], cld_rgb_nrm=cld_rgb_nrm, choose=ch.unsqueeze(1), dpt_xyz=xyz, n_valid=n_valid, center=center,
+                      scale=scale, **extra)
+        if mask is not None:
+            inputs["origin_labels"] = labels
+        if build_pyramid:
+            inputs.update(pyramid.build_pyramid(pyramid.cloud_from_inputs(cld_rgb_nrm), xyz))
+        return inputs
+    valid = valid_depth > 1e-6
     ch = choose[:, 0].long()
     cld = torch.gather(xyz.reshape(B, S * S, 3), 1, ch[:, :, None].expand(-1, -1, 3))
     rgb_pt = torch.gather(crop["rgb"].reshape(B, 3, S * S), 2, ch[:, None, :].expand(-1, 3, -1))
@@ -488,5 +561,6 @@ def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, 
     if mask is not None:
         lab = torch.gather(crop["mask"].reshape(B, S * S), 1, ch)
         inputs["origin_labels"] = torch.where(lab == 255, torch.ones_like(lab), lab)
-    inputs.update(pyramid.build_pyramid(cld.contiguous(), xyz))
+    if build_pyramid:
+        inputs.update(pyramid.build_pyramid(cld.contiguous(), xyz))
     return inputs

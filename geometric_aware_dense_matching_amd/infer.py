@@ -7,7 +7,7 @@ results come back in the original instance order with the reference's concatenat
 (`seg [bs,2,N]`, `rgbd [bs,128,N]`, `mesh [bs,128,M]`)."""
 import torch
 
-from . import matching, ops, pose, pyramid, settings
+from . import frontend, matching, ops, pose, pyramid, settings
 
 _PREC = {"bf16x3": ops.MATCH_BF16X3, "f32": ops.MATCH_F32, 0: 0, 1: 1}
 
@@ -69,6 +69,24 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
         out.update(pose.estimate_poses(out, d["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts))
     if keep_pyramid and pyr is not None:
         out.update((k, v) for k, v in pyr.items() if torch.is_tensor(v))
+    return out
+
+
+FRAME_KEYS = ("rgb_u8", "depth", "K", "bbox_xyxy", "mask")           # what a `frames` dict holds; the mask is optional
+
+
+def frame_step(model, frames, S, n_points, seed=0, depth_fill=None, precision="bf16x3", with_pose=False, keep_pyramid=False,
+               pose_fit="kabsch", icp_iters=0, pose_opts=None):
+    """From raw frames and detection boxes to the step's outputs: frames = dict(rgb_u8 u8[B,H,W,3], depth f32[B,H,W], K f32[B,3,3],
+    bbox_xyxy f32[B,4][, mask u8[B,H,W]]) -> frontend.make_inputs_from_boxes(sampler="hash", build_pyramid=False, train=False) ->
+    pipeline_step (which builds the pyramid a model needs).  seed: an int or a one-element int32 device tensor (ops.sample_assemble).
+    Returns pipeline_step's dict plus choose, cld_rgb_nrm, n_valid, center, scale (and origin_labels with a mask).  Like
+    pipeline_step, no host synchronisation: the call captures in a hipGraph as it is."""
+    item = frontend.make_inputs_from_boxes(frames["rgb_u8"], frames["depth"], frames["K"], frames["bbox_xyxy"], S, n_points,
+                                           mask=frames.get("mask"), train=False, depth_fill=depth_fill, sampler="hash", seed=seed,
+                                           build_pyramid=False)
+    out = pipeline_step(model, item, precision, with_pose, keep_pyramid, pose_fit, icp_iters, pose_opts)
+    out.update((k, item[k]) for k in ("choose", "cld_rgb_nrm", "n_valid", "center", "scale", "origin_labels") if k in item)
     return out
 
 
@@ -199,3 +217,33 @@ class GraphedPipeline:
         form = form or self.form
         self.graphs[form].replay()
         return self.outs[form]
+
+
+class GraphedFramePipeline(GraphedPipeline):
+    """Frames to poses in one hipGraph replay: GraphedPipeline whose step is `frame_step`, so the front end (depth normals or depth
+    completion, the box crop, the hash-sampled item) is captured in front of the model, the matching and the pose fit.  The static
+    inputs are the frame buffers (rgb_u8, depth, K, bbox_xyxy[, mask]) and a one-word seed tensor the sampling kernel reads on every
+    replay: `__call__(frames, seed=None)` copies both in.  The single / forked decision and its bit-identity check against the eager
+    step are GraphedPipeline's.  Works for the FFB6D model and for the DGCNN variant (needs_pyramid = False)."""
+
+    def __init__(self, model, example_frames, S, n_points, depth_fill=None, seed=0, **kw):
+        self.S, self.n_points, self.depth_fill = int(S), int(n_points), depth_fill
+        dev = example_frames["depth"].device
+        self.seed = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._set_seed(seed)
+        super().__init__(model, {k: example_frames[k] for k in FRAME_KEYS if example_frames.get(k) is not None}, **kw)
+
+    def _set_seed(self, seed):
+        s = int(seed) & 0xffffffff
+        self.seed.fill_(s - (1 << 32) if s >= (1 << 31) else s)         # the 32-bit word, as the int32 the tensor holds
+
+    def _step(self):
+        return frame_step(self.model, self.static_in, self.S, self.n_points, self.seed, self.depth_fill, self.precision, self.with_pose,
+                          self.keep_pyramid, self.pose_fit, self.icp_iters, self.pose_opts)
+
+    def __call__(self, frames, seed=None):
+        """Copies `frames` (and, when given, the seed) into the static buffers, replays the graph, returns the static outputs (valid
+        until the next call)."""
+        if seed is not None:
+            self._set_seed(seed)
+        return super().__call__(frames)

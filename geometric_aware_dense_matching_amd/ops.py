@@ -2220,3 +2220,53 @@ def seg_mask(seg):
     check(_lib.lib().gdm_seg_mask_hip(seg.data_ptr(), B, N, mask.data_ptr(), count.data_ptr(), _stream()),
           "gdm_seg_mask_hip")
     return mask, count
+
+
+# --------------------------------------------------------------------------------------
+# front end: hash-sampled points and the assembled item (gdm_sample.hip)
+# --------------------------------------------------------------------------------------
+def sample_assemble(valid_depth, dpt_xyz, rgb, normals, n_points, mask=None, seed=0):
+    """The N points of every crop by the counter-based rule of include/gdm.h (gdm_sample_assemble_hip) and the assembled item, one
+    launch: valid_depth f32[B,S,S] (a pixel is valid where it is > 1e-6), dpt_xyz f32[B,S,S,3], rgb f32[B,3,S,S], normals
+    f32[B,3,S,S], mask u8[B,S,S] or None -> choose i32[B,N], cld_rgb_nrm f32[B,9,N], labels u8[B,N] (None without a mask),
+    n_valid i32[B].  seed: an int (its low 32 bits), or a one-element int32 device tensor whose word the kernel reads when it runs
+    (a captured graph then draws differently on every replay).  The scratch buffer comes from the current BufferPool."""
+    valid_depth = _dev(valid_depth, torch.float32, "valid_depth")
+    dpt_xyz = _dev(dpt_xyz, torch.float32, "dpt_xyz")
+    rgb = _dev(rgb, torch.float32, "rgb")
+    normals = _dev(normals, torch.float32, "normals")
+    if valid_depth.dim() != 3 or valid_depth.shape[1] != valid_depth.shape[2]:
+        raise ValueError("valid_depth must be [B,S,S], got %s" % (tuple(valid_depth.shape),))
+    B, S, N = valid_depth.shape[0], valid_depth.shape[1], int(n_points)
+    for t, shape, name in ((dpt_xyz, (B, S, S, 3), "dpt_xyz"), (rgb, (B, 3, S, S), "rgb"), (normals, (B, 3, S, S), "normals")):
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, list(shape), tuple(t.shape)))
+    if not 1 <= N <= _lib.GDM_SAMPLE_MAX_N:
+        raise ValueError("n_points=%d not in [1, %d]" % (N, _lib.GDM_SAMPLE_MAX_N))
+    dev = valid_depth.device
+    seed_ptr, seed_val = None, 0
+    if torch.is_tensor(seed):
+        if not seed.is_cuda or seed.dtype != torch.int32 or seed.numel() != 1:
+            raise ValueError("a tensor seed must be a one-element int32 device tensor")
+        seed_ptr = seed.data_ptr()
+    else:
+        seed_val = int(seed) & 0xffffffff
+    labels = mp = lp = None
+    if mask is not None:
+        mask = _dev(mask, torch.uint8, "mask")
+        if tuple(mask.shape) != (B, S, S):
+            raise ValueError("mask must be [B=%d,S=%d,S=%d], got %s" % (B, S, S, tuple(mask.shape)))
+        labels = torch.empty((B, N), dtype=torch.uint8, device=dev)
+        mp, lp = mask.data_ptr(), labels.data_ptr()
+    L = _lib.lib()
+    need = L.gdm_sample_assemble_workspace_bytes(B, S)
+    if need == 0:
+        raise ValueError("sample_assemble: unsupported shape B=%d S=%d" % (B, S))
+    ws = _workspace(need, dev)
+    choose = torch.empty((B, N), dtype=torch.int32, device=dev)
+    cld_rgb_nrm = torch.empty((B, 9, N), dtype=torch.float32, device=dev)
+    n_valid = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(L.gdm_sample_assemble_hip(valid_depth.data_ptr(), dpt_xyz.data_ptr(), rgb.data_ptr(), normals.data_ptr(), mp, B, S, N,
+                                    seed_val, seed_ptr, choose.data_ptr(), cld_rgb_nrm.data_ptr(), lp, n_valid.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream()), "gdm_sample_assemble_hip")
+    return choose, cld_rgb_nrm, labels, n_valid

@@ -667,6 +667,34 @@ size_t gdm_fill_depth_workspace_bytes(int B, int H, int W, int mode);
 int gdm_fill_depth_hip(const float* depth, int B, int H, int W, int mode, float max_depth, void* workspace, size_t workspace_bytes,
                        float* out, float* stages, void* stream);
 
+/* Front end, the N points of a crop and the assembled item (the loader's choose / cld_rgb_nrm / labels, datasets/lm/linemod_pbr.py:
+ * 476-513, datasets/ycbv/ycbv_pbr.py:492-509) in one launch.  valid_depth f32[B,P], dpt_xyz f32[B,P,3], rgb f32[B,3,P], normals
+ * f32[B,3,P], mask u8[B,P] or NULL, P = S S -> choose i32[B,N], cld_rgb_nrm f32[B,9,N], labels u8[B,N] (NULL exactly when mask is),
+ * n_valid i32[B].  Which pixels are drawn is DEFINED here (no generator state, no library sort; eager, graph and forked-graph runs
+ * and every build give the same points).  For crop b, pixel p in [0, P) and the 32-bit seed:
+ *   valid(p)  = valid_depth[b,p] > 1e-6f                        (NaN and negative depth are invalid)
+ *   key(p)    = mix(mix(mix(seed ^ 0x9e3779b9) ^ b) ^ p)        (mix = lowbias32, as for GDM_RANSAC sampling above; mix is a bijection
+ *                                                                of 32-bit words, so the keys of one crop are pairwise distinct: no ties)
+ *   n_valid[b] = #{p : valid(p)};   order = the valid pixels by ascending key
+ *   choose[b,j] = order[j mod n_valid[b]], j < N                (a uniform subset in uniform random order when n_valid > N, the
+ *                                                                wrap-around padding of np.pad(..., 'wrap') otherwise)
+ *   n_valid[b] == 0:  choose[b,:] = 0                           (the reference's choose = [0], linemod_pbr.py:481-483)
+ *   cld_rgb_nrm[b,0:3,j] = dpt_xyz[b,c,:], [b,3:6,j] = rgb[b,:,c], [b,6:9,j] = normals[b,:,c] with c = choose[b,j]
+ *   labels[b,j] = mask[b,c] == 255 ? 1 : mask[b,c]
+ * valid_depth is separate from dpt_xyz because the YCB-V item samples among the FILLED pixels and gathers the UNFILLED xyz.
+ * seed_dev (or NULL): a device pointer to one word that replaces `seed` when the kernel runs, so that a captured graph can draw
+ * differently on every replay.  (Restated in Python as frontend.sample_assemble_numpy.)
+ * 1 <= B <= 65535, 1 <= S <= GDM_SAMPLE_MAX_S, 1 <= N <= GDM_SAMPLE_MAX_N.  workspace: device memory, 8-byte aligned, of at least
+ * gdm_sample_assemble_workspace_bytes(B, S) bytes (one bit per pixel; 0 for a bad shape).  One kernel, one workgroup per crop: exact
+ * selection by radix select on integer LDS histograms, no sort of all P keys, no global atomics, no allocation, no host read. */
+#define GDM_SAMPLE_MAX_N 4096
+#define GDM_SAMPLE_MAX_S 4096
+size_t gdm_sample_assemble_workspace_bytes(int B, int S);
+int gdm_sample_assemble_hip(const float* valid_depth, const float* dpt_xyz, const float* rgb, const float* normals,
+                            const uint8_t* mask, int B, int S, int N, uint32_t seed, const uint32_t* seed_dev, int32_t* choose,
+                            float* cld_rgb_nrm, uint8_t* labels, int32_t* n_valid, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 /* ---- training-mode BatchNorm (+ ReLU / LeakyReLU), forward and backward -------------------------------------------------------
  * Replaces the conv -> nn.BatchNorm{1,2}d -> activation chains of the embedding network in the training step
  * (models/pytorch_utils.py:70-124, models/RandLA/pytorch_utils.py:34-105, models/cnn/extractors.py:36-58; train_lm.py:171-225).
