@@ -182,6 +182,10 @@ SIGNATURES = {
     "gdm_wgrad_direct_hip": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gdm_conv1x1_packed_wb_hip": (_i, [_vp, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _vp]),
     "gdm_copy_jobs_hip": (_i, [ctypes.POINTER(CopyJob), _i, _vp]),
+    "gdm_mssd_mspd_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gdm_render_depth_hip": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_double, _i, _vp, _vp]),
+    "gdm_vsd_counts_hip": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, ctypes.c_double, ctypes.POINTER(ctypes.c_double), _i,
+                                ctypes.c_double, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

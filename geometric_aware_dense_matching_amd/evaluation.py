@@ -192,3 +192,425 @@ class BopCsv:
         with open(path, "w") as f:
             f.write("\n".join(self.lines))                             # no trailing newline, as the reference (:430-431)
         return path
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# BOP pose errors: MSSD, MSPD, VSD (lib/pysixd/pose_error.py:22-179) with the symmetry sets of lib/pysixd/misc.py:206-254 and the
+# visibility masks of lib/pysixd/visibility.py.  The device paths are gdm_bop.hip (ops.mssd_mspd / render_depth / vsd_counts); the
+# *_numpy functions restate them in fp64 on the host, operation for operation where a result is decided.
+
+BOP_THETAS = np.round(np.arange(1, 11) * 0.05, 2)                   # BOP-2019: correct when e < theta (x diameter for MSSD, VSD as is)
+BOP_MSPD_THETAS = np.arange(1, 11) * 5.0                            # pixels at a 640 px wide image
+BOP_VSD_TAUS = np.round(np.arange(1, 11) * 0.05, 2)                 # misalignment tolerances, fractions of the diameter
+BOP_VSD_DELTA = 0.015                                               # 15 mm, in metres: multiply by the caller's units per metre
+
+
+def load_models_info(path):
+    """models_info.json of a BOP dataset -> {obj_id (int): info dict}."""
+    import json
+    with open(path) as f:
+        return {int(k): v for k, v in json.load(f).items()}
+
+
+def _axis_rotation(angle, axis):
+    """lib/pysixd/transform.py:295-335 (rotation_matrix) without the point: 3x3."""
+    sina, cosa = np.sin(angle), np.cos(angle)
+    d = np.asarray(axis, dtype=np.float64)[:3]
+    d = d / np.sqrt(np.dot(d, d))
+    R = np.diag([cosa, cosa, cosa]) + np.outer(d, d) * (1.0 - cosa)
+    d = d * sina
+    return R + np.array([[0.0, -d[2], d[1]], [d[2], 0.0, -d[0]], [-d[1], d[0], 0.0]])
+
+
+def symmetry_transformations(model_info, max_sym_disc_step=0.01, scale=1.0):
+    """misc.get_symmetry_transformations (misc.py:206-254) -> R f64[S,3,3], t f64[S,3].  The discrete list is the identity first, then the
+    flat 4x4 lists of `symmetries_discrete`; every continuous symmetry is discretised into ceil(pi / step) steps about `axis` through
+    `offset` (the zero rotation left out); with continuous symmetries the set is, for each discrete one, all continuous ones composed
+    in front of it -- the reference's order, which then holds no identity.  t stays in the model
+    file's unit (mm in BOP) times `scale` (0.001 for this project's metres)."""
+    disc = [(np.eye(3), np.zeros(3))]
+    for sym in model_info.get("symmetries_discrete", ()):
+        m = np.reshape(np.asarray(sym, dtype=np.float64), (4, 4))
+        disc.append((m[:3, :3], m[:3, 3]))
+    cont = []
+    for sym in model_info.get("symmetries_continuous", ()):
+        offset = np.asarray(sym["offset"], dtype=np.float64).reshape(3)
+        steps = int(np.ceil(np.pi / max_sym_disc_step))
+        step = 2.0 * np.pi / steps
+        for i in range(1, steps):
+            R = _axis_rotation(i * step, sym["axis"])
+            cont.append((R, -R.dot(offset) + offset))
+    out = []
+    for Rd, td in disc:
+        if cont:
+            out += [(Rc.dot(Rd), Rc.dot(td) + tc) for Rc, tc in cont]
+        else:
+            out.append((Rd, td))
+    return np.stack([r for r, _ in out]).astype(np.float64), np.stack([t for _, t in out]).astype(np.float64) * float(scale)
+
+
+def _np64(x):
+    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.float64)
+
+
+def mssd_mspd_numpy(RT_est, RT_gt, pts, sym_R, sym_t, K):
+    """pose_error.py:131-179 in fp64 numpy, one instance and one symmetry at a time as the reference walks them: the same outputs as
+    mssd_mspd (numpy arrays).  The first minimum wins a tie (the reference's min())."""
+    RT_est, RT_gt, pts, sym_R, sym_t, K = (_np64(a) for a in (RT_est, RT_gt, pts, sym_R, sym_t, K))
+    n = RT_est.shape[0]
+    K = np.broadcast_to(K, (n, 3, 3))
+    pts_h = np.hstack([pts, np.ones((pts.shape[0], 1))])
+
+    def project(Kb, R, t):                                          # misc.project_pts (misc.py:511-525)
+        im = Kb.dot(np.hstack([R, t.reshape(3, 1)])).dot(pts_h.T)
+        return (im[:2] / im[2]).T
+
+    mssd, mspd = np.zeros(n), np.zeros(n)
+    b3, b2 = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for i in range(n):
+        Re, te, Rg, tg = RT_est[i, :, :3], RT_est[i, :, 3], RT_gt[i, :, :3], RT_gt[i, :, 3]
+        pe, ue = pts.dot(Re.T) + te, project(K[i], Re, te)
+        e3, e2 = [], []
+        for Rs, ts in zip(sym_R, sym_t):
+            Rgs, tgs = Rg.dot(Rs), Rg.dot(ts) + tg
+            e3.append(np.linalg.norm(pe - (pts.dot(Rgs.T) + tgs), axis=1).max())
+            e2.append(np.linalg.norm(ue - project(K[i], Rgs, tgs), axis=1).max())
+        b3[i], b2[i] = int(np.argmin(e3)), int(np.argmin(e2))
+        mssd[i], mspd[i] = e3[b3[i]], e2[b2[i]]
+    return mssd, mspd, b3, b2
+
+
+def _f64dev(x, device):
+    return torch.as_tensor(x).to(device=device, dtype=torch.float64)
+
+
+def mssd_mspd(RT_est, RT_gt, pts, sym_R, sym_t, K):
+    """MSSD and MSPD (pose_error.py:131-179) of n pose pairs of ONE object in one kernel: RT_est (a device tensor) and RT_gt [n,3,4],
+    pts [M,3], sym_R [S,3,3] / sym_t [S,3] (symmetry_transformations; t in the unit of pts), K [3,3] or [n,3,3] -> mssd f64[n] (unit
+    of pts), mspd f64[n] (pixels), best_sym_mssd i32[n], best_sym_mspd i32[n] on the device.  Inputs of any float dtype are widened to
+    fp64 there; no [n,S,M] array exists at any point (the largest temporary is [2,n,S])."""
+    from . import ops
+    dev = RT_est.device
+    return ops.mssd_mspd(_f64dev(RT_est, dev), _f64dev(RT_gt, dev)[:, :3], _f64dev(pts, dev), _f64dev(sym_R, dev), _f64dev(sym_t, dev),
+                         _f64dev(K, dev))
+
+
+def render_depth_numpy(verts, faces, RT, K, H, W, near):
+    """The pixel rule of include/gdm.h (gdm_render_depth_hip) on the host, the definition the kernel is tested against:
+    fp64 vertex transform ((R_i0 x + R_i1 y) + R_i2 z) + t_i, u = fx (X / Z) + cx (skew ignored, pixel centres at integers), snapping
+    to 1/256 px, int64 edge functions with the top-left rule on the winding normalised by the sign of the area, perspective-correct
+    depth, minimum over the triangles -> f32[n,H,W], 0 where nothing is drawn."""
+    verts, RT, K = _np64(verts), _np64(RT), _np64(K)
+    faces = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)).astype(np.int64)
+    n = RT.shape[0]
+    K = np.broadcast_to(K, (n, 3, 3))
+    out = np.full((n, H, W), np.inf, dtype=np.float32)
+    x, y, z = verts[:, 0], verts[:, 1], verts[:, 2]
+    for b in range(n):
+        R, t = RT[b, :, :3], RT[b, :, 3]
+        X = ((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0]
+        Y = ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1]
+        Z = ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]
+        with np.errstate(all="ignore"):
+            u = K[b, 0, 0] * (X / Z) + K[b, 0, 2]
+            v = K[b, 1, 1] * (Y / Z) + K[b, 1, 2]
+            ok = (Z > near) & (np.abs(u) <= 65536.0) & (np.abs(v) <= 65536.0)
+            xs = np.floor(np.where(ok, u, 0.0) * 256.0 + 0.5).astype(np.int64)
+            ys = np.floor(np.where(ok, v, 0.0) * 256.0 + 0.5).astype(np.int64)
+            iz = 1.0 / Z
+        for f in faces:
+            if not ok[f].all():
+                continue
+            i0, i1, i2 = f
+            A2 = (xs[i1] - xs[i0]) * (ys[i2] - ys[i0]) - (xs[i2] - xs[i0]) * (ys[i1] - ys[i0])
+            if A2 == 0:
+                continue
+            if A2 < 0:
+                i1, i2 = i2, i1
+            px0, px1 = max((min(xs[i0], xs[i1], xs[i2]) + 255) >> 8, 0), min(max(xs[i0], xs[i1], xs[i2]) >> 8, W - 1)
+            py0, py1 = max((min(ys[i0], ys[i1], ys[i2]) + 255) >> 8, 0), min(max(ys[i0], ys[i1], ys[i2]) >> 8, H - 1)
+            if px0 > px1 or py0 > py1:
+                continue
+            PX, PY = np.meshgrid(np.arange(px0, px1 + 1, dtype=np.int64) * 256, np.arange(py0, py1 + 1, dtype=np.int64) * 256)
+            inside, w = np.ones(PX.shape, dtype=bool), []
+            for a, c in ((i1, i2), (i2, i0), (i0, i1)):                # the edge opposite vertex 0, 1, 2
+                dx, dy = xs[c] - xs[a], ys[c] - ys[a]
+                e = dx * (PY - ys[a]) - dy * (PX - xs[a])
+                inside &= (e > 0) | ((e == 0) & bool(dy < 0 or (dy == 0 and dx > 0)))
+                w.append(e)
+            if not inside.any():
+                continue
+            A = ((w[0] + w[1]) + w[2]).astype(np.float64)
+            izp = ((w[0].astype(np.float64) * iz[i0] + w[1].astype(np.float64) * iz[i1]) + w[2].astype(np.float64) * iz[i2]) / A
+            d = (1.0 / izp).astype(np.float32)
+            tile = out[b, py0:py1 + 1, px0:px1 + 1]
+            tile[inside] = np.minimum(tile[inside], d[inside])
+    out[np.isinf(out)] = 0.0
+    return out
+
+
+def render_depth(verts, faces, RT, K, H, W, near, keep_inf=False):
+    """Depth images of a triangle mesh in n poses on the device (ops.render_depth): verts f32|f64[V,3] and faces i32[F,3] (device
+    tensors or arrays), RT [n,3,4] a device tensor, K [3,3] or [n,3,3] -> f32[n,H,W], 0 where nothing is drawn.  The image is defined
+    by the written pixel rule (render_depth_numpy restates it; only fx, fy, cx, cy of K are used: skew is ignored) and is reproducible
+    bit for bit.  Parity with BOP's OpenGL renderers is NOT pinned."""
+    from . import ops
+    dev = RT.device
+    verts = torch.as_tensor(verts).to(dev)
+    if verts.dtype not in (torch.float32, torch.float64):
+        verts = verts.double()
+    return ops.render_depth(verts, torch.as_tensor(faces).to(device=dev, dtype=torch.int32), _f64dev(RT, dev)[:, :3], _f64dev(K, dev),
+                            H, W, near, keep_inf=keep_inf)
+
+
+def _vsd_masks_numpy(depth_est, depth_gt, depth_test, K, delta):
+    """One instance: the fp64 distance images (misc.py:571-590) and the bop19 visibility masks (visibility.py:34-36, 72-73)."""
+    H, W = depth_test.shape
+    pre_x = (np.arange(W, dtype=np.float64)[None, :] - K[0, 2]) / np.float64(K[0, 0])
+    pre_y = (np.arange(H, dtype=np.float64)[:, None] - K[1, 2]) / np.float64(K[1, 1])
+
+    def dist(d):
+        return np.sqrt(np.multiply(pre_x, d) ** 2 + np.multiply(pre_y, d) ** 2 + d.astype(np.float64) ** 2)
+
+    dist_t, dist_g, dist_e = dist(depth_test), dist(depth_gt), dist(depth_est)
+    t32, no_test = dist_t.astype(np.float32), dist_t == 0
+
+    def visible(d_model):
+        return ((d_model.astype(np.float32) - t32 <= np.float32(delta)) | no_test) & (d_model > 0)
+
+    vis_g = visible(dist_g)
+    vis_e = visible(dist_e) | (vis_g & (dist_e > 0))
+    return dist_t, dist_g, dist_e, vis_g, vis_e
+
+
+def vsd_numpy(depth_est, depth_gt, depth_test, K, delta, taus, diameter=None, cost_type="step", return_counts=False):
+    """pose_error.py:84-126 on given depth images in fp64 numpy, the arithmetic of gdm_vsd_counts_hip operation for operation:
+    depth_est / depth_gt f32[n,H,W], depth_test f32[H,W] or [n,H,W], K [3,3] or [n,3,3] -> errors f64[n,T]; with return_counts also
+    union i64[n], inter i64[n], cost i64[n,T] (cost_type "step")."""
+    as32 = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float32)  # noqa: E731
+    depth_est, depth_gt, depth_test, K = as32(depth_est), as32(depth_gt), as32(depth_test), _np64(K)
+    n = depth_est.shape[0]
+    K = np.broadcast_to(K, (n, 3, 3))
+    taus = [float(t) for t in taus]
+    errors = np.ones((n, len(taus)))
+    union, inter, cost = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros((n, len(taus)), np.int64)
+    for b in range(n):
+        _, dist_g, dist_e, vis_g, vis_e = _vsd_masks_numpy(depth_est[b], depth_gt[b], depth_test if depth_test.ndim == 2 else depth_test[b],
+                                                           K[b], delta)
+        both = vis_g & vis_e
+        union[b], inter[b] = (vis_g | vis_e).sum(), both.sum()
+        dists = np.abs(dist_g[both] - dist_e[both])
+        if diameter:
+            dists = dists / float(diameter)
+        for j, tau in enumerate(taus):
+            if cost_type == "step":
+                cost[b, j] = c = (dists >= tau).sum()
+            elif cost_type == "tlinear":
+                c = np.minimum(dists / tau, 1.0).sum()
+            else:
+                raise ValueError("Unknown pixel matching cost.")
+            if union[b] > 0:
+                errors[b, j] = (c + (union[b] - inter[b])) / float(union[b])
+    return (errors, union, inter, cost) if return_counts else errors
+
+
+def _vsd_errors(counts, cost_type):
+    if cost_type == "step":
+        union, inter, cost = counts
+        c = cost.double()
+    elif cost_type == "tlinear":
+        union, inter, _, c = counts
+    else:
+        raise ValueError("Unknown pixel matching cost.")
+    u = union.double()[:, None]
+    e = (c + (union - inter).double()[:, None]) / u
+    return torch.where(u > 0, e, torch.ones_like(e))                # an empty union: 1.0 (pose_error.py:110-111)
+
+
+def vsd(depth_est, depth_gt, depth_test, K, delta, taus, diameter=None, cost_type="step"):
+    """The visible surface discrepancy (pose_error.py:84-126, visib_mode bop19) of n instances on given depth images, one kernel:
+    depth_est / depth_gt f32[n,H,W] device tensors, depth_test f32[H,W] (shared) or [n,H,W], K [3,3] or [n,3,3]; delta and the pixel
+    distances in the depth images' unit; the distances are divided by `diameter` when one is given (taus are then fractions of it)
+    -> errors f64[n,T] on the device.  cost_type "step" is exact integer counting; "tlinear" sums in fp64."""
+    from . import ops
+    dev = depth_est.device
+    counts = ops.vsd_counts(depth_est, depth_gt.to(dev), torch.as_tensor(depth_test).to(dev), _f64dev(K, dev), delta, taus, diameter,
+                            tlinear=cost_type == "tlinear")
+    return _vsd_errors(counts, cost_type)
+
+
+def vsd_from_poses(verts, faces, RT_est, RT_gt, depth_test, K, delta, taus, diameter=None, cost_type="step", near=0.0,
+                   return_counts=False):
+    """VSD from poses: both poses of every instance are rendered in ONE rasteriser call (render_depth's pixel rule) and scored by
+    the VSD kernel, which also reads the cleared z-buffer as empty; no depth image visits the host.  verts / faces: the object's mesh
+    (load_ply); RT_est, RT_gt [n,3,4]; depth_test f32[H,W] or [n,H,W] on the device; K [3,3] or [n,3,3] -> errors f64[n,T] (with
+    return_counts also the ops-level counts)."""
+    from . import ops
+    dev = RT_est.device
+    depth_test = torch.as_tensor(depth_test).to(dev)
+    H, W = depth_test.shape[-2:]
+    n = RT_est.shape[0]
+    K = _f64dev(K, dev)
+    RT = torch.cat([_f64dev(RT_est, dev)[:, :3], _f64dev(RT_gt, dev)[:, :3]], dim=0)
+    d = render_depth(verts, faces, RT, torch.cat([K, K], dim=0) if K.dim() == 3 else K, H, W, near, keep_inf=True)
+    counts = ops.vsd_counts(d[:n], d[n:], depth_test, K, delta, taus, diameter, tlinear=cost_type == "tlinear", inf_is_empty=True)
+    errors = _vsd_errors(counts, cost_type)
+    return (errors, counts) if return_counts else errors
+
+
+def load_ply(path):
+    """The triangle meshes BOP ships, in pure numpy: ascii or binary_little_endian PLY with a `vertex` element whose properties include
+    x, y, z (further ones -- normals, colours, texture coordinates -- are skipped) and a `face` element that is one list property of
+    uchar / int (or uint) triples -> verts f64[V,3] (the file's unit: mm in BOP), faces i32[F,3]."""
+    np_type = {"char": "i1", "uchar": "u1", "short": "i2", "ushort": "u2", "int": "i4", "uint": "u4", "float": "f4", "double": "f8",
+               "int8": "i1", "uint8": "u1", "int16": "i2", "uint16": "u2", "int32": "i4", "uint32": "u4", "float32": "f4", "float64": "f8"}
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s is not a PLY file" % path)
+        fmt, elements = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: PLY header without end_header" % path)
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                elements[-1][2].append(tuple(tok[1:]))
+            elif tok[0] == "end_header":
+                break
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise ValueError("%s: PLY format %r is not supported (ascii, binary_little_endian)" % (path, fmt))
+        verts = faces = None
+        for name, count, props in elements:
+            is_list = [p[0] == "list" for p in props]
+            if any(is_list) and (name != "face" or len(props) != 1):
+                raise ValueError("%s: element %r with list properties is not supported" % (path, name))
+            if name == "face":
+                ct, it = np_type[props[0][1]], np_type[props[0][2]]
+                if fmt == "ascii":
+                    rows = np.array([f.readline().split() for _ in range(count)], dtype=np.int64).reshape(count, -1)
+                    cnt, idx = rows[:, 0], rows[:, 1:4]
+                    if rows.shape[1] != 4:
+                        raise ValueError("%s: faces must be triangles" % path)
+                else:
+                    rec = np.frombuffer(f.read(count * (np.dtype(ct).itemsize + 3 * np.dtype(it).itemsize)),
+                                        dtype=np.dtype([("n", "<" + ct), ("v", "<" + it, (3,))]), count=count)
+                    cnt, idx = rec["n"], rec["v"]
+                if count and not (cnt == 3).all():
+                    raise ValueError("%s: faces must be triangles" % path)
+                faces = np.ascontiguousarray(idx).astype(np.int32).reshape(count, 3)
+            else:
+                names = [p[1] for p in props]
+                if fmt == "ascii":
+                    rows = np.array([f.readline().split() for _ in range(count)], dtype=np.float64).reshape(count, len(props))
+                    cols = {nm: rows[:, i] for i, nm in enumerate(names)}
+                else:
+                    dt = np.dtype([(nm, "<" + np_type[p[0]]) for nm, p in zip(names, props)])
+                    rec = np.frombuffer(f.read(count * dt.itemsize), dtype=dt, count=count)
+                    cols = {nm: rec[nm] for nm in names}
+                if name == "vertex":
+                    verts = np.stack([cols["x"], cols["y"], cols["z"]], axis=1).astype(np.float64)
+    if verts is None or faces is None:
+        raise ValueError("%s: PLY without a vertex and a face element" % path)
+    return verts, faces
+
+
+class BopScores:
+    """The BOP-2019 scores beside RecallTable: for every object the recall of MSSD (correct when e < theta x diameter, theta = 0.05
+    ... 0.5), MSPD (e < theta x width / 640 px, theta = 5 ... 50) and VSD (e < theta for the same ten theta as MSSD, over the ten
+    misalignment tolerances tau = 0.05 ... 0.5 of the diameter the errors were computed at, BOP_VSD_TAUS, with delta = BOP_VSD_DELTA),
+    AR_x = the mean recall over the thresholds of error x and AR = the mean of the three (of the two when no VSD was given).
+
+    update() takes the errors of a batch of instances of one object, missing() records ground truths without an estimate (every
+    recall 0).  There is ONE estimate per ground-truth instance, as everywhere in this evaluator: the toolkit's matching of several
+    estimates to the instances of an image (eval_calc_scores.py) is not restated."""
+
+    def __init__(self):
+        self.correct = OrderedDict()                                # obj -> {"mssd": [bool[10]], "mspd": [bool[10]], "vsd": [bool[10, T]]}
+        self.errors = OrderedDict()
+
+    def _slot(self, obj_name):
+        if obj_name not in self.correct:
+            self.correct[obj_name] = OrderedDict((e, []) for e in ("mssd", "mspd", "vsd"))
+            self.errors[obj_name] = OrderedDict((e, []) for e in ("mssd", "mspd", "vsd"))
+        return self.correct[obj_name], self.errors[obj_name]
+
+    def update(self, obj_name, mssd, mspd, vsd=None, diameter=1.0, width=640):
+        """mssd f[n] (unit of `diameter`), mspd f[n] (pixels), vsd f[n,T] or None (errors at the T tolerances), tensors or arrays."""
+        cor, err = self._slot(obj_name)
+        mssd, mspd = _np64(mssd).reshape(-1), _np64(mspd).reshape(-1)
+        err["mssd"] += mssd.tolist()
+        err["mspd"] += mspd.tolist()
+        cor["mssd"] += list(mssd[:, None] < BOP_THETAS[None, :] * float(diameter))
+        cor["mspd"] += list(mspd[:, None] < BOP_MSPD_THETAS[None, :] * (float(width) / 640.0))
+        if vsd is not None:
+            vsd = _np64(vsd).reshape(len(mssd), -1)
+            err["vsd"] += vsd.tolist()
+            cor["vsd"] += list(vsd[:, None, :] < BOP_THETAS[None, :, None])
+
+    def missing(self, obj_name, count=1, vsd_taus=None):
+        """Ground truths without an estimate: every threshold missed.  vsd_taus: how many tolerances the VSD entries carry (None:
+        as many as the object's other entries, or no VSD entry when it has none)."""
+        cor, _ = self._slot(obj_name)
+        for e in ("mssd", "mspd"):
+            cor[e] += [np.zeros(10, dtype=bool)] * count
+        T = vsd_taus if vsd_taus is not None else (cor["vsd"][0].shape[1] if cor["vsd"] else 0)
+        if T:
+            cor["vsd"] += [np.zeros((10, T), dtype=bool)] * count
+
+    def recalls(self, obj_name):
+        """{"mssd": f[10], "mspd": f[10], "vsd": f[10] (mean over tau) or None, "AR_mssd", "AR_mspd", "AR_vsd" (or None), "AR"}."""
+        cor = self.correct[obj_name]
+        out = {}
+        for e in ("mssd", "mspd", "vsd"):
+            if cor[e]:
+                a = np.stack(cor[e]).astype(np.float64)             # [instances, 10(, T)]
+                out[e] = a.reshape(a.shape[0], 10, -1).mean(axis=(0, 2))
+                out["AR_" + e] = float(a.mean())
+            else:
+                out[e], out["AR_" + e] = None, None
+        ars = [out["AR_" + e] for e in ("mssd", "mspd", "vsd") if out["AR_" + e] is not None]
+        out["AR"] = float(np.mean(ars)) if ars else 0.0
+        return out
+
+    def table(self):
+        obj_names = sorted(self.correct.keys())
+        rec = {o: self.recalls(o) for o in obj_names}
+        errs = [e for e in ("mssd", "mspd", "vsd") if any(rec[o][e] is not None for o in obj_names)]
+        rows = []
+        for e in errs:
+            thetas = BOP_MSPD_THETAS if e == "mspd" else BOP_THETAS
+            rows += [("%s_%g" % (e, th), [None if rec[o][e] is None else rec[o][e][i] for o in obj_names]) for i, th in enumerate(thetas)]
+            rows.append(("AR_" + e, [rec[o]["AR_" + e] for o in obj_names]))
+        rows.append(("AR", [rec[o]["AR"] for o in obj_names]))
+        tab = [["objects"] + obj_names + ["Avg(%d)" % len(obj_names)]]
+        for name, vals in rows:
+            have = [v for v in vals if v is not None]
+            line = [name] + ["%.2f" % (100 * v) if v is not None else "-" for v in vals]
+            if obj_names:
+                line.append("%.2f" % (100 * np.mean(have)) if have else "-")
+            tab.append(line)
+        return tab
+
+    def format(self):
+        tab = [[str(c) for c in row] for row in self.table()]
+        width = [max(len(r[i]) for r in tab if i < len(r)) for i in range(max(len(r) for r in tab))]
+        return "\n".join("  ".join(c.ljust(width[i]) for i, c in enumerate(r)).rstrip() for r in tab)
+
+    def dump(self, output_dir, dataset_name, method_name=""):
+        """`{method}_{dataset}_bop_errors.pkl` (the per-instance errors) and `{method}_{dataset}_bop_tab.txt` beside RecallTable's."""
+        import os
+        import pickle
+        os.makedirs(output_dir, exist_ok=True)
+        stem = os.path.join(output_dir, "%s_%s" % (method_name, dataset_name))
+        paths = (stem + "_bop_errors.pkl", stem + "_bop_tab.txt")
+        with open(paths[0], "wb") as f:
+            pickle.dump(self.errors, f)
+        with open(paths[1], "w") as f:
+            f.write("%s\n" % self.format())
+        return paths

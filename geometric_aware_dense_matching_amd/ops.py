@@ -2270,3 +2270,109 @@ def sample_assemble(valid_depth, dpt_xyz, rgb, normals, n_points, mask=None, see
                                     seed_val, seed_ptr, choose.data_ptr(), cld_rgb_nrm.data_ptr(), lp, n_valid.data_ptr(),
                                     ws.data_ptr(), ws.numel(), _stream()), "gdm_sample_assemble_hip")
     return choose, cld_rgb_nrm, labels, n_valid
+
+
+# --------------------------------------------------------------------------------------
+# BOP pose errors (lib/pysixd/pose_error.py:22-179): gdm_bop.hip
+
+
+def _k64(K, n, name):
+    """K f64[3,3] or f64[n,3,3] on the device -> (tensor, k_per_instance)."""
+    K = _dev(K, torch.float64, name)
+    if tuple(K.shape) == (3, 3):
+        return K, 0
+    if tuple(K.shape) == (n, 3, 3):
+        return K, 1
+    raise ValueError("%s must be [3,3] or [n=%d,3,3], got %s" % (name, n, tuple(K.shape)))
+
+
+def mssd_mspd(RT_est, RT_gt, pts, sym_R, sym_t, K):
+    """MSSD / MSPD of n pose pairs of one object (gdm_mssd_mspd_hip): RT_est, RT_gt f64[n,3,4], pts f64[M,3], sym_R f64[S,3,3],
+    sym_t f64[S,3], K f64[3,3] or f64[n,3,3] -> mssd f64[n], mspd f64[n], best_sym_mssd i32[n], best_sym_mspd i32[n].  The largest
+    temporary is the per-symmetry maxima f64[2,n,S]."""
+    RT_est = _dev(RT_est, torch.float64, "RT_est")
+    RT_gt = _dev(RT_gt, torch.float64, "RT_gt")
+    pts = _dev(pts, torch.float64, "pts")
+    sym_R = _dev(sym_R, torch.float64, "sym_R")
+    sym_t = _dev(sym_t, torch.float64, "sym_t")
+    if RT_est.dim() != 3 or tuple(RT_est.shape[1:]) != (3, 4) or RT_est.shape[0] < 1:
+        raise ValueError("RT_est must be [n,3,4], got %s" % (tuple(RT_est.shape),))
+    n = RT_est.shape[0]
+    if tuple(RT_gt.shape) != (n, 3, 4):
+        raise ValueError("RT_gt must be [n=%d,3,4], got %s" % (n, tuple(RT_gt.shape)))
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError("pts must be [M,3], got %s" % (tuple(pts.shape),))
+    if sym_R.dim() != 3 or tuple(sym_R.shape[1:]) != (3, 3) or sym_R.shape[0] < 1:
+        raise ValueError("sym_R must be [S,3,3], got %s" % (tuple(sym_R.shape),))
+    S = sym_R.shape[0]
+    if tuple(sym_t.shape) != (S, 3):
+        raise ValueError("sym_t must be [S=%d,3], got %s" % (S, tuple(sym_t.shape)))
+    K, kpi = _k64(K, n, "K")
+    dev = RT_est.device
+    err = torch.empty((2, n, S), dtype=torch.float64, device=dev)
+    out = torch.empty((2, n), dtype=torch.float64, device=dev)
+    best = torch.empty((2, n), dtype=torch.int32, device=dev)
+    check(_lib.lib().gdm_mssd_mspd_hip(RT_est.data_ptr(), RT_gt.data_ptr(), pts.data_ptr(), sym_R.data_ptr(), sym_t.data_ptr(),
+                                       K.data_ptr(), kpi, n, pts.shape[0], S, err.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                       best[0].data_ptr(), best[1].data_ptr(), _stream()), "gdm_mssd_mspd_hip")
+    return out[0], out[1], best[0], best[1]
+
+
+def render_depth(verts, faces, RT, K, H, W, near, keep_inf=False):
+    """Depth images of one mesh in n poses by the pixel rule of include/gdm.h (gdm_render_depth_hip): verts f32|f64[V,3], faces
+    i32[F,3], RT f64[n,3,4], K f64[3,3] or f64[n,3,3] -> f32[n,H,W], 0 where nothing is drawn (+inf with keep_inf, for
+    vsd_counts(inf_is_empty=True))."""
+    if not isinstance(verts, torch.Tensor) or verts.dtype not in (torch.float32, torch.float64):
+        _dev(verts, torch.float32, "verts")
+        raise TypeError("verts must be float32 or float64")
+    verts = _dev(verts, verts.dtype, "verts")
+    faces = _dev(faces, torch.int32, "faces")
+    RT = _dev(RT, torch.float64, "RT")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError("verts must be [V,3], got %s" % (tuple(verts.shape),))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError("faces must be [F,3], got %s" % (tuple(faces.shape),))
+    if RT.dim() != 3 or tuple(RT.shape[1:]) != (3, 4) or RT.shape[0] < 1:
+        raise ValueError("RT must be [n,3,4], got %s" % (tuple(RT.shape),))
+    n, H, W = RT.shape[0], int(H), int(W)
+    K, kpi = _k64(K, n, "K")
+    depth = torch.empty((n, H, W), dtype=torch.float32, device=RT.device)
+    check(_lib.lib().gdm_render_depth_hip(verts.data_ptr(), int(verts.dtype == torch.float64), faces.data_ptr(), RT.data_ptr(),
+                                          K.data_ptr(), kpi, n, verts.shape[0], faces.shape[0], H, W, float(near), int(bool(keep_inf)),
+                                          depth.data_ptr(), _stream()), "gdm_render_depth_hip")
+    return depth
+
+
+def vsd_counts(depth_est, depth_gt, depth_test, K, delta, taus, diameter=None, tlinear=False, inf_is_empty=False):
+    """The integer counts of the VSD error (gdm_vsd_counts_hip): depth_est, depth_gt f32[n,H,W], depth_test f32[H,W] or f32[n,H,W],
+    K f64[3,3] or f64[n,3,3], taus a sequence of at most 16 floats -> union i32[n], inter i32[n], cost i32[n,T] (and, with tlinear,
+    the truncated-linear cost sums f64[n,T])."""
+    depth_est = _dev(depth_est, torch.float32, "depth_est")
+    depth_gt = _dev(depth_gt, torch.float32, "depth_gt")
+    depth_test = _dev(depth_test, torch.float32, "depth_test")
+    if depth_est.dim() != 3 or depth_est.shape[0] < 1:
+        raise ValueError("depth_est must be [n,H,W], got %s" % (tuple(depth_est.shape),))
+    n, H, W = depth_est.shape
+    if tuple(depth_gt.shape) != (n, H, W):
+        raise ValueError("depth_gt must be %s, got %s" % ([n, H, W], tuple(depth_gt.shape)))
+    if tuple(depth_test.shape) == (H, W):
+        tpi = 0
+    elif tuple(depth_test.shape) == (n, H, W):
+        tpi = 1
+    else:
+        raise ValueError("depth_test must be [H,W] or %s, got %s" % ([n, H, W], tuple(depth_test.shape)))
+    K, kpi = _k64(K, n, "K")
+    taus = [float(t) for t in taus]
+    T = len(taus)
+    if not 1 <= T <= 16:
+        raise ValueError("vsd_counts takes 1 to 16 taus, got %d" % T)
+    dev = depth_est.device
+    counts = torch.empty((n, 2 + T), dtype=torch.int32, device=dev)
+    tl = torch.empty((n, T), dtype=torch.float64, device=dev) if tlinear else None
+    check(_lib.lib().gdm_vsd_counts_hip(depth_est.data_ptr(), depth_gt.data_ptr(), depth_test.data_ptr(), tpi, K.data_ptr(), kpi, n, H, W,
+                                        float(delta), (ctypes.c_double * T)(*taus), T, float(diameter) if diameter else 0.0,
+                                        int(bool(inf_is_empty)), counts.data_ptr(), tl.data_ptr() if tlinear else None, _stream()),
+          "gdm_vsd_counts_hip")
+    if tlinear:
+        return counts[:, 0], counts[:, 1], counts[:, 2:], tl
+    return counts[:, 0], counts[:, 1], counts[:, 2:]

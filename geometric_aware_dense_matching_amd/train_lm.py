@@ -78,6 +78,10 @@ def build_parser():
     p.add_argument("--single-object", action="store_true", help="test: only -cls_id instead of every object of the dataset")
     p.add_argument("--eval-output", dest="eval_output", type=str, default=None,
                    help="test: directory for the evaluator's files -- BOP result csv, error / recall / precision pickles, table text")
+    p.add_argument("--bop-scores", dest="bop_scores", action="store_true",
+                   help="test: also score MSSD / MSPD (BOP-2019 thresholds, AR lines) per object; written beside the recall table")
+    p.add_argument("--models-info", dest="models_info", type=str, default=None,
+                   help="test, with --bop-scores: the dataset's models_info.json (object symmetries); without it only the identity")
     p.add_argument("--graph-batch1", action="store_true",
                    help="test: per-object hipGraph replay for single-instance groups (a batch-1 eager step is launch-bound)")
     p.add_argument("--pose-fit", dest="pose_fit", type=str, default="kabsch", choices=["kabsch", "ransac"],
@@ -479,6 +483,19 @@ def test(args):
     table = evaluation.RecallTable()
     prec_table = evaluation.RecallTable(precision=True)      # evaluator.py:466-660, written beside the recall table with --eval_output
     bop = evaluation.BopCsv()                                # evaluator.py:341,365-373: one line per predicted instance
+    # --bop-scores: MSSD / MSPD (pose_error.py:131-179) over the model points the run already has, against every symmetric copy of
+    # the ground truth (misc.py:206-254; models_info.json is in millimetres, the poses in metres).  VSD needs the whole depth frame
+    # and the mesh faces, which these batches do not carry: it stays with the Python API (evaluation.vsd_from_poses).
+    bop_scores = evaluation.BopScores() if getattr(args, "bop_scores", False) else None
+    syms = {}
+    if bop_scores is not None:
+        info = evaluation.load_models_info(args.models_info) if getattr(args, "models_info", None) else {}
+        if not info:
+            import warnings
+            warnings.warn("train_lm test --bop-scores without --models-info: no object symmetries, MSSD / MSPD against the identity only")
+        for cid in ids:
+            R, t = evaluation.symmetry_transformations(info.get(cid, {}), scale=0.001)
+            syms[cid] = (torch.from_numpy(R).to(device), torch.from_numpy(t).to(device))
     n_seen = 0
     bop_ids_seen = True                                      # every batch so far carried scene_id / im_id
     sym_names = set(ds.get("sym_objs", ()))                 # config/*_cfg.py SYM_OBJS: object NAMES
@@ -507,6 +524,11 @@ def test(args):
                                                  sym_rots=getattr(model_dict[cid].model_emb, "sym_rots", None))
                     table.update(obj_name_of(ds, cid), err, ds["diameters"][cid] / 1000.0)
                     prec_table.update(obj_name_of(ds, cid), err, ds["diameters"][cid] / 1000.0)
+                    if bop_scores is not None:
+                        mssd, mspd, _, _ = evaluation.mssd_mspd(out["RT"][rows], cu["RT"][rows][:, :3], model_dict[cid].model_emb.xyz,
+                                                                syms[cid][0], syms[cid][1], Kcam[rows] if Kcam.dim() == 3 else Kcam)
+                        bop_scores.update(obj_name_of(ds, cid), mssd, mspd, None, ds["diameters"][cid] / 1000.0,
+                                          int(ds.get("image_width", 640)))
             # The reference walks the GROUND-TRUTH annotations (evaluator.py:340-373): a csv line is appended only for a prediction that
             # has a ground-truth entry, keyed by the real "scene/.../im_id" (:366-367), and a ground truth without a prediction counts as a
             # miss in the recall table (:355-363).  So: lines only where the loader supplied RT AND scene_id / im_id (ids invented here
@@ -525,11 +547,17 @@ def test(args):
                     if miss > 0:
                         table.missing(obj_name_of(ds, cid), miss)
                         prec_table.missing(obj_name_of(ds, cid), miss)      # (the precision variant ignores them: evaluator.py:549-551)
+                        if bop_scores is not None:
+                            bop_scores.missing(obj_name_of(ds, cid), miss)
             n_seen += len(cls)
     if table.recalls:
         test.last_table = table
         if args.local_rank == 0:
             print(table.format())
+    if bop_scores is not None and bop_scores.correct:
+        test.last_bop_scores = bop_scores
+        if args.local_rank == 0:
+            print(bop_scores.format())
     if getattr(args, "eval_output", None) and args.local_rank == 0:
         # what the reference's evaluator leaves behind: the BOP result csv (:429-431) and, when ground truth was there, the error /
         # recall pickles and the table text of both variants (:449-455, :647-660)
@@ -543,6 +571,8 @@ def test(args):
         if table.recalls:
             written += list(table.dump(args.eval_output, args.dataset_name + "_test"))
             written += list(prec_table.dump(args.eval_output, args.dataset_name + "_test", method_name=args.model_variant))
+        if bop_scores is not None and bop_scores.correct:
+            written += list(bop_scores.dump(args.eval_output, args.dataset_name + "_test", method_name=args.model_variant))
         test.last_outputs = written
     return results
 

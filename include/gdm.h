@@ -839,6 +839,46 @@ typedef struct gdm_copy_job {
 #define GDM_COPY_MAX_JOBS 16
 int gdm_copy_jobs_hip(const gdm_copy_job* jobs /* host array */, int njobs, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * BOP pose errors (/root/reference/lib/pysixd/pose_error.py:22-179 with misc.py:206-254,511-525,571-590 and visibility.py:9-74).
+ * All arithmetic that decides a result is fp64; lengths are in the caller's unit.  K is f64[3,3] (k_per_instance 0) or f64[n,3,3] (1).
+ *
+ * MSSD and MSPD (pose_error.py:131-179) of n pose pairs of one object: for symmetry s the ground truth is (R_gt S_R[s],
+ * R_gt S_t[s] + t_gt); mssd[i] = min_s max_p |P_est p - P_gt,s p|, mspd[i] = min_s max_p |proj(P_est p) - proj(P_gt,s p)| with
+ * proj(X) = (K X)[:2] / (K X)[2] (misc.project_pts); best_sym_* i32[n] = the minimising s, the first one on a tie.
+ * RT_est, RT_gt f64[n,3,4]; pts f64[M,3]; sym_R f64[S,3,3]; sym_t f64[S,3]; err f64[2,n,S] = the per-symmetry maxima (MSSD rows
+ * first), the only temporary: no [n,S,M] array is formed. */
+int gdm_mssd_mspd_hip(const double* RT_est, const double* RT_gt, const double* pts, const double* sym_R, const double* sym_t,
+                      const double* K, int k_per_instance, int n, int M, int S, double* err, double* mssd, double* mspd,
+                      int32_t* best_sym_mssd, int32_t* best_sym_mspd, void* stream);
+/* Depth images of one triangle mesh in n poses (what pose_error.py:59-64 asks of its `renderer`): depth f32[n,H,W], 0 where nothing
+ * is drawn.  verts f32[V,3] (verts_f64 0) or f64[V,3] (1); faces i32[F,3]; RT f64[n,3,4].  THE PIXEL RULE (evaluation.render_depth_numpy
+ * restates it):
+ *   vertex      P = R v + t in fp64, each component ((R_i0 x + R_i1 y) + R_i2 z) + t_i
+ *   projection  u = fx (X / Z) + cx, v = fy (Y / Z) + cy with fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]; skew is ignored.
+ *               Pixel centres sit at integer coordinates.
+ *   discard     the whole triangle when a vertex has Z <= near, or |u| or |v| above 2^16, or its snapped area is 0
+ *   snapping    Xs = (int64) floor(u * 256 + 0.5), Ys likewise
+ *   coverage    int64 edge functions at (256 px, 256 py), the winding normalised by the sign of the area (no culling); a pixel is
+ *               covered when all three are >= 0, a zero counting only on a top or left edge (dy < 0, or dy == 0 and dx > 0, of the
+ *               normalised winding); the pixel range is the snapped bounding box clamped to the image
+ *   depth       iz = ((w0 (1/z0) + w1 (1/z1)) + w2 (1/z2)) / A, w_i the edge value opposite vertex i, A their sum; d = (float)(1 / iz)
+ *   z-buffer    the minimum over the triangles (unsigned atomicMin on the fp32 bit pattern: reproducible), cleared to +inf;
+ *               untouched pixels become 0 at the end -- or stay +inf with keep_inf != 0, for gdm_vsd_counts_hip(inf_is_empty = 1). */
+int gdm_render_depth_hip(const void* verts, int verts_f64, const int32_t* faces, const double* RT, const double* K, int k_per_instance,
+                         int n, int V, int F, int H, int W, double near, int keep_inf, float* depth, void* stream);
+/* The integer counts the VSD errors are made of (pose_error.py:84-126, visib_mode "bop19"): counts i32[n, 2 + T] = (union, inter,
+ * cost_0 .. cost_{T-1}) with cost_j = #{inter pixels with |dist_gt - dist_est| (/ diameter when diameter > 0) >= taus[j]}; the error is
+ * (cost_j + union - inter) / union, 1 for an empty union.  depth_est, depth_gt f32[n,H,W]; depth_test f32[H,W] (test_per_instance 0)
+ * or f32[n,H,W] (1); distance images fp64 sqrt((px d)^2 + (py d)^2 + d^2), px = (col - cx) / fx; the visibility test is the fp32
+ * difference of the fp32-cast distances <= (float) delta, or a missing test depth.  taus: HOST array f64[T], T <= GDM_VSD_MAX_TAUS.
+ * tl_sums f64[n,T] or NULL: the sums of min(dist / tau, 1) of cost_type "tlinear" (fp64 atomic adds of per-workgroup sums: the last
+ * bits depend on their order; the counts are exact).  inf_is_empty != 0: +inf in depth_est / depth_gt reads as 0. */
+#define GDM_VSD_MAX_TAUS 16
+int gdm_vsd_counts_hip(const float* depth_est, const float* depth_gt, const float* depth_test, int test_per_instance, const double* K,
+                       int k_per_instance, int n, int H, int W, double delta, const double* taus /* host array */, int T,
+                       double diameter, int inf_is_empty, int32_t* counts, double* tl_sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

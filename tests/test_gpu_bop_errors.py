@@ -1,0 +1,307 @@
+"""GPU: the BOP pose errors of gdm_bop.hip -- the depth rasteriser against the written pixel rule (evaluation.render_depth_numpy), the
+VSD counts against evaluation.vsd_numpy and the REAL reference's vsd (tests/golden/bop_errors.npz), MSSD / MSPD against the fp64
+restatement and the reference's values, their memory shape, and hipGraph capture of both."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+sys.path.insert(0, G)
+import bop_inputs as bi  # noqa: E402
+
+from geometric_aware_dense_matching_amd import evaluation as ev  # noqa: E402
+from geometric_aware_dense_matching_amd import ops  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def dev(a, dtype=None):
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return dict(np.load(os.path.join(G, "bop_errors.npz")))
+
+
+@pytest.fixture(scope="module")
+def scene(gold):
+    """The mesh, the poses and the restatement's images (the fixture's: tests/test_bop_errors_cpu.py pins them to the rule)."""
+    verts, faces = bi.mesh()
+    est, gt = bi.poses()
+    return dict(verts=verts, faces=faces, est=est, gt=gt, d_est=gold["vsd_depth_est"], d_gt=gold["vsd_depth_gt"],
+                d_test=gold["vsd_depth_test"], diameter=float(gold["vsd_diameter"]), errors=gold["vsd_errors"])
+
+
+def ulp_distance(a, b):
+    """Distance in fp32 ulps between positive floats (their bit patterns are ordered)."""
+    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
+
+
+def check_image(got, want, what):
+    got = got.cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == want.shape
+    assert np.array_equal(got > 0, want > 0), "%s: coverage differs at %d pixels" % (what, ((got > 0) != (want > 0)).sum())
+    m = want > 0
+    worst = int(ulp_distance(got[m], want[m]).max()) if m.any() else 0
+    print("%s: %d covered pixels, largest depth difference %d ulp%s" % (what, m.sum(), worst, " (bit-equal)" if worst == 0 else ""))
+    assert worst <= 1
+    assert not got[~m].any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# rasteriser
+
+@pytest.mark.parametrize("vdtype", [torch.float64, torch.float32])
+def test_render_depth_follows_the_pixel_rule(scene, vdtype):
+    verts = dev(scene["verts"], vdtype)
+    ref_verts = verts.cpu().numpy().astype(np.float64)
+    faces = dev(scene["faces"])
+    one = ev.render_depth(verts, faces, dev(scene["gt"][:1]), bi.K, bi.H, bi.W, bi.NEAR)
+    want_one = scene["d_gt"][:1] if vdtype == torch.float64 else ev.render_depth_numpy(ref_verts, scene["faces"], scene["gt"][:1], bi.K,
+                                                                                        bi.H, bi.W, bi.NEAR)
+    check_image(one, want_one, "n = 1")
+    three = ev.render_depth(verts, faces, dev(scene["est"]), bi.K, bi.H, bi.W, bi.NEAR)                 # three poses, one call
+    want = scene["d_est"] if vdtype == torch.float64 else ev.render_depth_numpy(ref_verts, scene["faces"], scene["est"], bi.K, bi.H, bi.W,
+                                                                                bi.NEAR)
+    check_image(three, want, "n = 3")
+    assert (want[2] > 0).sum() < 0.7 * (want[0] > 0).sum()                                               # the clipped pose leaves the image
+    again = ev.render_depth(verts, faces, dev(scene["est"]), bi.K, bi.H, bi.W, bi.NEAR)
+    assert torch.equal(three.view(torch.int32), again.view(torch.int32))                                  # reproducible bit for bit
+    Kn = np.stack([bi.K, bi.K + np.array([[3.0, 0, 1.5], [0, -2.0, -0.75], [0, 0, 0]]), bi.K])            # K per instance
+    check_image(ev.render_depth(verts, faces, dev(scene["est"]), Kn, bi.H, bi.W, bi.NEAR),
+                ev.render_depth_numpy(ref_verts, scene["faces"], scene["est"], Kn, bi.H, bi.W, bi.NEAR), "K per instance")
+
+
+def test_render_depth_large_triangles_take_the_cooperative_path():
+    verts, faces = bi.full_quad(z=0.5)
+    got = ev.render_depth(verts, faces, dev(bi.identity_pose()), bi.K, bi.H, bi.W, bi.NEAR)
+    assert (got == 0.5).all()                                                                             # every pixel, that depth
+    check_image(got, ev.render_depth_numpy(verts, faces, bi.identity_pose(), bi.K, bi.H, bi.W, bi.NEAR), "full-image quad")
+    # a tilted quad: the depth varies over the box, both triangles are larger than the per-thread limit
+    RT = np.hstack([bi.rot(0.5, (1, 1, 0)), np.array([[0.0], [0.0], [0.25]])])[None]
+    check_image(ev.render_depth(verts, faces, dev(RT), bi.K, bi.H, bi.W, bi.NEAR),
+                ev.render_depth_numpy(verts, faces, RT, bi.K, bi.H, bi.W, bi.NEAR), "tilted quad")
+    one = ev.render_depth(verts, faces[:1], dev(RT), bi.K, bi.H, bi.W, bi.NEAR)                           # F = 1
+    check_image(one, ev.render_depth_numpy(verts, faces[:1], RT, bi.K, bi.H, bi.W, bi.NEAR), "F = 1")
+
+
+def test_render_depth_discards(scene):
+    verts = np.array([[-0.05, -0.05, 0.3], [0.05, -0.05, 0.3], [0.0, 0.05, 0.005]])
+    tri = np.array([[0, 1, 2]], dtype=np.int32)
+    assert not ev.render_depth(verts, tri, dev(bi.identity_pose()), bi.K, bi.H, bi.W, 0.01).any()        # one vertex behind near
+    flipped = ev.render_depth(scene["verts"], scene["faces"][:, ::-1].copy(), dev(scene["gt"][:1]), bi.K, bi.H, bi.W, bi.NEAR)
+    check_image(flipped, scene["d_gt"][:1], "flipped windings")
+    raw = ev.render_depth(scene["verts"], scene["faces"], dev(scene["gt"][:1]), bi.K, bi.H, bi.W, bi.NEAR, keep_inf=True)
+    assert torch.equal(torch.isinf(raw), flipped == 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# VSD
+
+@pytest.mark.parametrize("per_instance", [False, True])
+def test_vsd_counts_equal_the_restatement_and_the_reference(scene, per_instance):
+    d_test = np.stack([scene["d_test"]] * 3) if per_instance else scene["d_test"]
+    want_err, want_union, want_inter, want_cost = ev.vsd_numpy(scene["d_est"], scene["d_gt"], d_test, bi.K, bi.DELTA, bi.TAUS,
+                                                               diameter=scene["diameter"], return_counts=True)
+    union, inter, cost = ops.vsd_counts(dev(scene["d_est"]), dev(scene["d_gt"]), dev(d_test), dev(bi.K), bi.DELTA, bi.TAUS,
+                                        scene["diameter"])
+    print("union %s inter %s" % (union.tolist(), inter.tolist()))
+    assert np.array_equal(union.cpu().numpy(), want_union) and np.array_equal(inter.cpu().numpy(), want_inter)
+    assert np.array_equal(cost.cpu().numpy(), want_cost)
+    err = ev.vsd(dev(scene["d_est"]), dev(scene["d_gt"]), dev(d_test), bi.K, bi.DELTA, bi.TAUS, diameter=scene["diameter"])
+    assert err.dtype == torch.float64 and np.array_equal(err.cpu().numpy(), want_err)
+    assert np.array_equal(err.cpu().numpy(), scene["errors"])                                             # the reference's own vsd
+    assert (err[2] == 1.0).all()
+
+
+def test_vsd_without_diameter_empty_union_and_tlinear(scene):
+    taus_m = [t * scene["diameter"] for t in bi.TAUS]                                                     # the same tolerances in metres
+    a = ev.vsd(dev(scene["d_est"]), dev(scene["d_gt"]), dev(scene["d_test"]), bi.K, bi.DELTA, taus_m)
+    assert np.array_equal(a.cpu().numpy(), ev.vsd_numpy(scene["d_est"], scene["d_gt"], scene["d_test"], bi.K, bi.DELTA, taus_m))
+    z = torch.zeros((2, bi.H, bi.W), device=DEV)
+    assert (ev.vsd(z, z, dev(scene["d_test"]), bi.K, bi.DELTA, bi.TAUS) == 1.0).all()
+    t = ev.vsd(dev(scene["d_est"]), dev(scene["d_gt"]), dev(scene["d_test"]), bi.K, bi.DELTA, bi.TAUS, diameter=scene["diameter"],
+               cost_type="tlinear")
+    want = ev.vsd_numpy(scene["d_est"], scene["d_gt"], scene["d_test"], bi.K, bi.DELTA, bi.TAUS, diameter=scene["diameter"],
+                        cost_type="tlinear")
+    # a sum of at most H x W = 2745 terms in [0, 1], each rounded once, in another order: 2745 x 2^-53 x 2745 / union at the very most
+    assert np.abs(t.cpu().numpy() - want).max() <= 1e-9
+
+
+def test_vsd_from_poses_end_to_end(scene):
+    """The kernel's images may differ from the restatement's by 1 fp32 ulp (test_render_depth_*).  First, from the restatement alone:
+    no pixel is within 16 fp32 ulps of the largest rendered depth of the visibility tolerance delta, and no scored pixel within that
+    (over the diameter) of a misalignment tolerance tau -- so an ulp cannot move a count, and the counts must then be EQUAL."""
+    d_est, d_gt, d_test, diam = scene["d_est"], scene["d_gt"], scene["d_test"], scene["diameter"]
+    allowance = 16 * float(np.spacing(np.float32(max(d_est.max(), d_gt.max()))))
+    m_delta, m_tau = np.inf, np.inf
+    for i in range(3):
+        dist_t, dist_g, dist_e, vis_g, vis_e = ev._vsd_masks_numpy(d_est[i], d_gt[i], d_test, bi.K, bi.DELTA)
+        for dm in (dist_g, dist_e):
+            m = (dm > 0) & (dist_t > 0)
+            diff = dm.astype(np.float32)[m].astype(np.float64) - dist_t.astype(np.float32)[m].astype(np.float64)
+            m_delta = min(m_delta, np.abs(diff - np.float64(np.float32(bi.DELTA))).min())
+        both = vis_g & vis_e
+        if both.any():
+            cost = np.abs(dist_g[both] - dist_e[both]) / diam
+            m_tau = min(m_tau, np.abs(cost[:, None] - np.asarray(bi.TAUS)[None, :]).min())
+    print("smallest margin to delta %.3g m (allowance %.3g m), to a tau %.3g of the diameter (allowance %.3g)" %
+          (m_delta, allowance, m_tau, allowance / diam))
+    assert m_delta > allowance and m_tau > allowance / diam
+
+    want_err, want_union, want_inter, want_cost = ev.vsd_numpy(d_est, d_gt, d_test, bi.K, bi.DELTA, bi.TAUS, diameter=diam,
+                                                               return_counts=True)
+    err, (union, inter, cost) = ev.vsd_from_poses(dev(scene["verts"]), dev(scene["faces"]), dev(scene["est"]), dev(scene["gt"]),
+                                                  dev(d_test), bi.K, bi.DELTA, bi.TAUS, diameter=diam, near=bi.NEAR, return_counts=True)
+    print("gt pixels %d, union %s, inter %s" % ((d_gt[0] > 0).sum(), union.tolist(), inter.tolist()))
+    assert np.array_equal(union.cpu().numpy(), want_union) and np.array_equal(inter.cpu().numpy(), want_inter)
+    assert np.array_equal(cost.cpu().numpy(), want_cost)
+    assert np.array_equal(err.cpu().numpy(), want_err)
+    assert (err[2] == 1.0).all()                                                                          # clipped: exactly 1 for every tau
+    assert 0 < float(err[0, 0]) < float(err[1, 0]) < 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# MSSD / MSPD
+
+@pytest.mark.parametrize("case", bi.SYM_CASES)                                                            # S = 1, 2, 314, 628
+def test_mssd_mspd_equal_the_restatement_and_the_reference(gold, case):
+    R, t = ev.symmetry_transformations(bi.MODEL_INFOS[case], 0.01, scale=0.001)
+    pts, RT_est, RT_gt = gold["ms_pts"], gold["ms_RT_est"], gold["ms_RT_gt"]
+    want = ev.mssd_mspd_numpy(RT_est, RT_gt, pts, R, t, bi.LM_K)
+    args = [dev(a) for a in (RT_est, RT_gt, pts, R, t, bi.LM_K)]
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    mssd, mspd, b3, b2 = ops.mssd_mspd(*args)
+    torch.cuda.synchronize()
+    extra = torch.cuda.max_memory_allocated() - base
+    n, S = RT_est.shape[0], R.shape[0]
+    print("S = %d: %d bytes above the inputs (an [n,S,M] fp64 array would be %d)" % (S, extra, n * S * pts.shape[0] * 8))
+    assert extra <= n * S * 8 + (1 << 20)
+    for got, ref, name in ((mssd, want[0], "mssd"), (mspd, want[1], "mspd")):
+        got = got.cpu().numpy()
+        assert got.dtype == np.float64
+        assert np.abs(got / ref - 1).max() <= 1e-9, name
+        assert np.abs(got / gold["%s_%s" % (name, case)] - 1).max() <= 1e-9, name
+    assert b3.dtype == torch.int32 and np.array_equal(b3.cpu().numpy(), want[2]) and np.array_equal(b2.cpu().numpy(), want[3])
+    # float32 poses and points, K per instance, through the evaluation-level entry
+    Kn = np.stack([bi.LM_K] * n)
+    f = ev.mssd_mspd(dev(RT_est, torch.float32), RT_gt.astype(np.float32), pts.astype(np.float32), R, t, Kn)
+    w32 = ev.mssd_mspd_numpy(RT_est.astype(np.float32), RT_gt.astype(np.float32), pts.astype(np.float32), R, t, Kn)
+    assert np.abs(f[0].cpu().numpy() / w32[0] - 1).max() <= 1e-9 and np.abs(f[1].cpu().numpy() / w32[1] - 1).max() <= 1e-9
+
+
+def test_mssd_mspd_many_points_and_ties():
+    pts, RT_est, RT_gt = bi.mssd_inputs(M=8192, n=5, seed=5)                                              # sixteen point tiles per instance
+    R, t = ev.symmetry_transformations(bi.MODEL_INFOS["continuous"], 0.01, scale=0.001)
+    want = ev.mssd_mspd_numpy(RT_est, RT_gt, pts, R, t, bi.LM_K)
+    got = ev.mssd_mspd(dev(RT_est), RT_gt, pts, R, t, bi.LM_K)
+    assert np.abs(got[0].cpu().numpy() / want[0] - 1).max() <= 1e-9 and np.abs(got[1].cpu().numpy() / want[1] - 1).max() <= 1e-9
+    assert np.array_equal(got[2].cpu().numpy(), want[2]) and np.array_equal(got[3].cpu().numpy(), want[3])
+    odd = ev.mssd_mspd(dev(RT_est), RT_gt, pts[:1027], R[:65], t[:65], bi.LM_K)                           # a ragged tile, a ragged symmetry chunk
+    w = ev.mssd_mspd_numpy(RT_est, RT_gt, pts[:1027], R[:65], t[:65], bi.LM_K)
+    assert np.abs(odd[0].cpu().numpy() / w[0] - 1).max() <= 1e-9 and np.array_equal(odd[2].cpu().numpy(), w[2])
+    same = np.stack([np.eye(3)] * 70)                                                                      # 70 equal symmetries: the first wins
+    tie = ev.mssd_mspd(dev(RT_est), RT_gt, pts[:100], same, np.zeros((70, 3)), bi.LM_K)
+    assert not tie[2].any() and not tie[3].any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# capture
+
+def _capture(fn, static):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()                                                                                               # warm-up outside the capture
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = fn()
+    return g, out
+
+
+def test_vsd_from_poses_captures_and_replays(scene):
+    verts, faces, d_test = dev(scene["verts"]), dev(scene["faces"]), dev(scene["d_test"])
+    K = dev(bi.K)
+    est, gt = dev(scene["est"]), dev(scene["gt"])
+
+    def run():
+        return ev.vsd_from_poses(verts, faces, est, gt, d_test, K, bi.DELTA, bi.TAUS, diameter=scene["diameter"], near=bi.NEAR)
+    g, out = _capture(run, None)
+    for shift in (0.003, -0.007):
+        new_est = scene["est"].copy()
+        new_est[:, 0, 3] += shift
+        est.copy_(dev(new_est))
+        g.replay()
+        torch.cuda.synchronize()
+        replayed = out.clone()
+        assert torch.equal(replayed.view(torch.int64), run().view(torch.int64))
+
+
+def test_mssd_mspd_captures_and_replays(gold):
+    R, t = ev.symmetry_transformations(bi.MODEL_INFOS["continuous"], 0.01, scale=0.001)
+    est, gt, pts, Rd, td, K = (dev(a) for a in (gold["ms_RT_est"], gold["ms_RT_gt"], gold["ms_pts"], R, t, bi.LM_K))
+
+    def run():
+        return ev.mssd_mspd(est, gt, pts, Rd, td, K)
+    g, out = _capture(run, None)
+    for shift in (0.004, -0.002):
+        new_est = gold["ms_RT_est"].copy()
+        new_est[:, 1, 3] += shift
+        est.copy_(dev(new_est))
+        g.replay()
+        torch.cuda.synchronize()
+        replayed = [o.clone() for o in out]
+        eager = run()
+        assert torch.equal(replayed[0].view(torch.int64), eager[0].view(torch.int64))
+        assert torch.equal(replayed[1].view(torch.int64), eager[1].view(torch.int64))
+        assert torch.equal(replayed[2], eager[2]) and torch.equal(replayed[3], eager[3])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# command line
+
+def test_train_lm_bop_scores_switch(tmp_path, monkeypatch):
+    """`-state=test --bop-scores --models-info PATH`: MSSD / MSPD of every instance against the symmetries of models_info.json, their
+    table printed and written beside the recall table; without the switch nothing of it appears."""
+    import json
+    from geometric_aware_dense_matching_amd import train_lm
+    info = tmp_path / "models_info.json"
+    info.write_text(json.dumps({"1": bi.MODEL_INFOS["discrete"], "5": bi.MODEL_INFOS["none"]}))
+    calls = []
+    real = ev.mssd_mspd
+
+    def recording(*a):
+        out = real(*a)
+        calls.append(([x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x) for x in a], [o.cpu().numpy() for o in out]))
+        return out
+    monkeypatch.setattr(ev, "mssd_mspd", recording)
+    base = ("--gpus=0 -state=test -cls_id=1 --single-object --batch-size 2 --n-points 1024 --n-mesh 512 --synthetic-items 4 "
+            "--eval-output %s" % tmp_path)
+    args = train_lm.build_parser().parse_args((base + " --bop-scores --models-info %s" % info).split())
+    train_lm.test(args)
+    assert len(calls) == 2                                                                                # two batches of one object
+    got3, got2 = [], []
+    for a, o in calls:
+        assert a[3].shape == (2, 3, 3) and np.array_equal(a[4][1], np.array([3.0, -2.0, 0.0]) * 0.001)   # the file's symmetry, in metres
+        want = ev.mssd_mspd_numpy(a[0], a[1][:, :3], a[2], a[3], a[4], a[5])
+        assert np.abs(o[0] / want[0] - 1).max() <= 1e-9 and np.abs(o[1] / want[1] - 1).max() <= 1e-9
+        got3 += o[0].tolist()
+        got2 += o[1].tolist()
+    scores = train_lm.test.last_bop_scores
+    (name, errs), = scores.errors.items()
+    assert errs["mssd"] == got3 and errs["mspd"] == got2 and errs["vsd"] == []
+    written = [os.path.basename(p) for p in train_lm.test.last_outputs]
+    assert written[-2:] == ["ffb6d_lmo_test_bop_errors.pkl", "ffb6d_lmo_test_bop_tab.txt"]
+    tab = open(train_lm.test.last_outputs[-1]).read()
+    assert "AR_mssd" in tab and "AR_mspd" in tab and "AR_vsd" not in tab and tab.strip() == scores.format()
+    train_lm.test(train_lm.build_parser().parse_args(base.split()))
+    assert len(calls) == 2 and not any("bop_" in os.path.basename(p) for p in train_lm.test.last_outputs)
