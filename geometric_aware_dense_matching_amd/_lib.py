@@ -19,6 +19,8 @@ _sz = ctypes.c_size_t
 GDM_RANSAC_MAX_H = 4096                # include/gdm.h
 GDM_SAMPLE_MAX_N = 4096
 GDM_SAMPLE_MAX_S = 4096
+GDM_AUG_MIN_S = 32
+GDM_AUG_MAX_S = 4096
 
 
 class KnnJob(ctypes.Structure):
@@ -159,6 +161,10 @@ SIGNATURES = {
     "gdm_fill_depth_hip": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _sz, _vp, _vp, _vp]),
     "gdm_sample_assemble_workspace_bytes": (_sz, [_i, _i]),
     "gdm_sample_assemble_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdm_augment_workspace_bytes": (_sz, [_i, _i]),
+    "gdm_augment_crops_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdm_augment_force_all_stages": (None, [_i]),
+    "gdm_dzi_boxes_hip": (_i, [_vp, _i, _f, _f, _f, _f, _i, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "gdm_bn_sums_len": (ctypes.c_long, [_i, _i, ctypes.c_long]),
     "gdm_bn_stats_hip": (_i, [_vp, _i, _i, ctypes.c_long, _vp, _vp]),
     "gdm_bn_fwd_apply_hip": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_long, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp]),

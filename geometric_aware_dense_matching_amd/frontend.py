@@ -7,16 +7,18 @@ sampling of N points with wrap-around padding (:476-496), `cld_rgb_nrm` / `choos
 
   make_inputs             integer S x S crops of a frame whose rgb is normalised and whose normals are given
   depth_normals           depth -> normal map (csrc/gdm_frontend.hip; the definition is in include/gdm.h)
-  dzi_boxes               box -> centre and scale (torch, on the boxes' device)
+  dzi_boxes               box -> centre and scale (torch, on the boxes' device; jitter="hash": one launch, counter-based draws)
   crop_from_boxes         the resampling crop: rgb, normals, dpt_xyz, depth, mask from one launch
   fill_depth              depth completion of the crop (csrc/gdm_depthfill.hip), the step the YCB-V item adds
+  augment_crops           the YCB-V training item's colour / noise / background augmentation of the crop (csrc/gdm_augment.hip)
   make_inputs_from_boxes  raw uint8 rgb + depth + K + box (+ mask) -> the input dict, no host step and no host synchronisation;
                           depth_fill=None is the LineMOD item, "multiscale" / "fast" the YCB-V item
                           (/root/reference/datasets/ycbv/ycbv_pbr.py:458-509)
                           sampler="hash": the N points by the written rule of include/gdm.h and the assembly in one launch
                           (ops.sample_assemble, csrc/gdm_sample.hip) instead of sample_valid_pixels and the torch gathers
 
-`depth_normals_numpy`, `crop_from_boxes_numpy`, `fill_depth_numpy` and `sample_assemble_numpy` restate the kernels' definitions on the CPU (as
+`depth_normals_numpy`, `crop_from_boxes_numpy`, `fill_depth_numpy`, `augment_crops_numpy`, `dzi_boxes_numpy` and
+`sample_assemble_numpy` restate the kernels' definitions on the CPU (as
 targets.spherical_flip does for the flip); the device results equal them value for value, up to the fp32 rounding of the bilateral
 filter's exponentials in the last stage of the fill.  Parity with normalSpeed and with a given cv2 build is unpinned (DESIGN.md 6d,
 6e)."""
@@ -383,6 +385,249 @@ def sample_assemble_numpy(valid_depth, dpt_xyz, rgb, normals, mask, N, seed=0):
     return choose, cld_rgb_nrm, labels, n_valid
 
 
+# --------------------------------------------------------------------------------------
+# the YCB-V training item's augmentation of the crop (include/gdm.h gdm_augment_crops_hip)
+# --------------------------------------------------------------------------------------
+AUG_C = 0x85ebca6b                                             # the constant of the augmentation's draws (the sampler's is 0x9e3779b9)
+DZI_C = 0xc2b2ae35                                             # the constant of the hash-drawn box jitter
+AUG_MIN_S = _lib.GDM_AUG_MIN_S
+_P20, _P80 = 0xcccccccc, 0x33333333                            # word > _P20: probability 0.2; word > _P80: probability 0.8
+_aug_tab = {}
+
+
+def aug_tables():
+    """The integer tables of csrc/gdm_augment_tables.h (tools/make_aug_tables.py writes them): gdm_aug_cos_q14 [360],
+    gdm_aug_gauss3 [256,2], gdm_aug_gauss5 [256,3], read from the header the kernel is compiled with."""
+    if not _aug_tab:
+        import os
+        import re
+        txt = open(os.path.join(_lib.CSRC, "gdm_augment_tables.h")).read()
+        for name, dims, body in re.findall(r"GDM_AUG_TABLE short (\w+)((?:\[\d+\])+) = \{(.*?)\};", txt, flags=re.S):
+            shape = [int(d) for d in re.findall(r"\d+", dims)]
+            _aug_tab[name] = np.array([int(v) for v in re.findall(r"-?\d+", body)], np.int64).reshape(shape)
+    return _aug_tab
+
+
+def _mix1(x):
+    """lowbias32 on one Python int."""
+    x &= 0xffffffff
+    x ^= x >> 16
+    x = (x * 0x7feb352d) & 0xffffffff
+    x ^= x >> 15
+    x = (x * 0x846ca68b) & 0xffffffff
+    return x ^ (x >> 16)
+
+
+def _below(w, n):
+    return (w * n) >> 32
+
+
+def motion_taps(angle, length):
+    """The taps of linear_motion_blur's a x a kernel by the written rule: (a, [(dy, dx), ...]); a <= 0 -> (a, None), the image as it is."""
+    cos = aug_tables()["gdm_aug_cos_q14"]
+    cs, sn = int(cos[angle % 360]), int(cos[(angle + 270) % 360])
+    a = (max(abs(cs), abs(sn)) * length * 2) >> 14
+    if a <= 0:
+        return a, None
+
+    def trunc(v):
+        return v // 16384 if v >= 0 else -((-v) // 16384)
+
+    cx = a // 2
+    ex, ey = cx + trunc(cs * length), cx + trunc(sn * length)
+    dx, sx = abs(ex - cx), (1 if ex > cx else -1)
+    dy, sy = -abs(ey - cx), (1 if ey > cx else -1)
+    err, x, y, taps = dx + dy, cx, cx, []
+    while True:
+        if 0 <= x < a and 0 <= y < a:
+            taps.append((y - cx, x - cx))
+        if x == ex and y == ey:
+            break
+        e2 = 2 * err
+        if e2 >= dy:
+            err += dy
+            x += sx
+        if e2 <= dx:
+            err += dx
+            y += sy
+    return a, taps
+
+
+def _draw_pass(hb, q):
+    D = lambda j: _mix1(hb ^ (16 * q + j))                     # noqa: E731
+    t = aug_tables()
+    p = dict(ks=320 + _below(D(0), 52), kv=294 + _below(D(1), 52), sharpen=D(2) > _P20, sharpen_u=D(3) >> 24, motion=D(4) > _P20,
+             angle=_below(D(5), 360), length=_below(D(6), 15) + 1, gauss=D(7) > _P20, gauss_k=3 if D(8) > _P80 else 5,
+             gauss_level=D(9) >> 24, sigma=_below(D(11), 15 if D(10) > _P80 else 25), extra=D(12) > _P20,
+             hs=(_mix1(hb ^ (256 + 2 * q)), _mix1(hb ^ (256 + 2 * q + 1))))
+    p["a"], p["taps"] = motion_taps(p["angle"], p["length"])
+    p["gauss_w"] = [int(v) for v in (t["gdm_aug_gauss3"] if p["gauss_k"] == 3 else t["gdm_aug_gauss5"])[p["gauss_level"]]]
+    reach_m = max(max(abs(dy), abs(dx)) for dy, dx in p["taps"]) if p["motion"] and p["taps"] else 0
+    p["halo"] = (1 if p["sharpen"] else 0) + reach_m + (p["gauss_k"] // 2 if p["gauss"] else 0)
+    return p
+
+
+def augment_draws_numpy(B, seed, S=None, bank_shape=None):
+    """Every per-crop decision of `augment_crops` for crops 0 .. B-1 and an int seed, as a list of dicts: passes = [pass 0, pass 1], each
+    with the gains ks, kv (1/256), sharpen / sharpen_u, motion / angle / length / a (the kernel's side) / taps [(dy, dx)], gauss /
+    gauss_k / gauss_level / gauss_w, sigma, extra, halo (the pixels a tile of that pass reads beyond itself) and the hashes hs of its
+    two noise streams; second: whether pass 1 is applied; bank_words: the three words of the paste, and with S and
+    bank_shape = (Nb, Hb, Wb) also bank, wy, wx."""
+    out = []
+    for b in range(B):
+        hb = _mix1(_mix1((int(seed) & 0xffffffff) ^ AUG_C) ^ b)
+        d = dict(hb=hb, passes=[_draw_pass(hb, 0), _draw_pass(hb, 1)], second=_mix1(hb ^ 32) > _P20,
+                 bank_words=(_mix1(hb ^ 33), _mix1(hb ^ 34), _mix1(hb ^ 35)))
+        if bank_shape is not None:
+            Nb, Hb, Wb = bank_shape
+            w = d["bank_words"]
+            d.update(bank=w[0] % Nb, wy=w[1] % (Hb - S - 1), wx=w[2] % (Wb - S - 1))
+        out.append(d)
+    return out
+
+
+def aug_levels(x):
+    """The uint8 levels of a normalised crop x f32[...,3,S,S] (include/gdm.h): int64, NaN -> 0."""
+    f32 = np.float32
+    x = np.asarray(x, dtype=f32)
+    mean, std = np.array(COLOR_MEAN, f32).reshape(3, 1, 1), np.array(COLOR_STD_CROP, f32).reshape(3, 1, 1)
+    with np.errstate(invalid="ignore"):
+        f = ((x * std) + mean) * f32(255.0)
+        f = np.where(f > 0, f, f32(0.0))
+        return np.rint(np.minimum(f, f32(255.0))).astype(np.int64)
+
+
+def aug_normalise(v):
+    """normalize_color as csrc/gdm_frontend.hip does it: levels int[...,3,S,S] -> f32."""
+    f32 = np.float32
+    mean, std = np.array(COLOR_MEAN, f32).reshape(3, 1, 1), np.array(COLOR_STD_CROP, f32).reshape(3, 1, 1)
+    c = np.asarray(v).astype(f32) / f32(255.0)
+    c = c - mean
+    return (c / std).astype(f32)
+
+
+def _pad101(img, r):
+    """img [H,W,...] extended by r pixels a side, BORDER_REFLECT_101."""
+    def idx(n):
+        i = np.abs(np.arange(-r, n + r))
+        return np.where(i >= n, 2 * n - 2 - i, i)
+    return img[idx(img.shape[0])[:, None], idx(img.shape[1])[None, :]]
+
+
+def aug_hsv_gain(img, ks, kv):
+    """Step 1: img int64[H,W,3] -> int64[H,W,3]."""
+    M, m = img.max(axis=2), img.min(axis=2)
+    d = M - m
+    M2 = np.minimum(255, (M * kv) >> 8)
+    s = np.where(M > 0, (255 * d + (M >> 1)) // np.maximum(M, 1), 0)
+    s2 = np.minimum(255, (s * ks) >> 8)
+    m2 = M2 - (M2 * s2 + 127) // 255
+    out = m2[..., None] + ((img - m[..., None]) * (M2 - m2)[..., None] + (d >> 1)[..., None]) // np.maximum(d, 1)[..., None]
+    return np.where((d > 0)[..., None], out, M2[..., None])
+
+
+def aug_sharpen(img, u):
+    H, W = img.shape[:2]
+    pad = _pad101(img, 1)
+    s8 = sum(pad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W] for dy in (-1, 0, 1) for dx in (-1, 0, 1) if dy or dx)
+    c256, q = 2304 + 3 * u, 256 + 3 * u
+    return np.clip((2 * (c256 * img - 256 * s8) + q) // (2 * q), 0, 255)
+
+
+def aug_motion(img, taps):
+    if not taps:
+        return img
+    H, W = img.shape[:2]
+    r = max(max(abs(dy), abs(dx)) for dy, dx in taps)
+    pad = _pad101(img, r)
+    n = len(taps)
+    return (sum(pad[r + dy:r + dy + H, r + dx:r + dx + W] for dy, dx in taps) + (n >> 1)) // n
+
+
+def aug_gauss(img, w):
+    H, W = img.shape[:2]
+    r = len(w) - 1
+    pad = _pad101(img, r)
+    acc = sum(w[abs(dy)] * w[abs(dx)] * pad[r + dy:r + dy + H, r + dx:r + dx + W] for dy in range(-r, r + 1) for dx in range(-r, r + 1))
+    return (acc + 32768) >> 16
+
+
+def aug_noise(img, sigma, hs):
+    """v + ((z sigma 443 + 32768) >> 16), clipped; the word of pixel p = y W + x (a square image: W = S), channel c is mix(hs ^ (3 p + c))."""
+    H, W = img.shape[:2]
+    with np.errstate(over="ignore"):
+        w = _mix32(np.uint32(hs) ^ np.arange(3 * H * W, dtype=np.uint32)).reshape(H, W, 3).astype(np.int64)
+    z = (w & 255) + ((w >> 8) & 255) + ((w >> 16) & 255) + (w >> 24) - 510
+    return np.clip(img + ((z * sigma * 443 + 32768) >> 16), 0, 255)
+
+
+def aug_pass(img, p):
+    """One pass of rgb_add_noise with the draws p (an entry of augment_draws_numpy's passes): img int64[S,S,3] -> int64[S,S,3]."""
+    img = aug_hsv_gain(img, p["ks"], p["kv"])
+    if p["sharpen"]:
+        img = aug_sharpen(img, p["sharpen_u"])
+    if p["motion"]:
+        img = aug_motion(img, p["taps"])
+    if p["gauss"]:
+        img = aug_gauss(img, p["gauss_w"])
+    img = aug_noise(img, p["sigma"], p["hs"][0])
+    if p["extra"]:
+        img = aug_noise(img, 7, p["hs"][1])
+    return img
+
+
+def aug_paste(img, depth, mask, bg_rgb, bg_depth, bg_mask, n, wy, wx):
+    """add_real_back on one crop: img int[S,S,3], depth f32[S,S], mask u8[S,S] and the S x S window at (wy, wx) of the bank's frame n ->
+    (img, depth): the object's pixels (mask > 0) and the valid depths (> 1e-6) stay, the rest is the window where bg_mask < 255, else 0."""
+    S = depth.shape[0]
+    ys, xs = slice(wy, wy + S), slice(wx, wx + S)
+    keep = bg_mask[n, ys, xs] < 255
+    back = np.where(keep[..., None], bg_rgb[n, ys, xs].astype(np.int64), 0)
+    with np.errstate(invalid="ignore"):
+        d = np.where(depth > np.float32(1e-6), depth, np.where(keep, bg_depth[n, ys, xs], np.float32(0.0))).astype(np.float32)
+    return np.where((mask > 0)[..., None], img, back), d
+
+
+def augment_crops_numpy(rgb, depth, mask=None, background=None, enable=None, seed=0):
+    """The definition of `augment_crops` (include/gdm.h gdm_augment_crops_hip) restated on the CPU, numpy arrays in and out:
+    rgb f32[B,3,S,S], depth f32[B,S,S], mask u8[B,S,S], background = (bg_rgb u8[Nb,Hb,Wb,3], bg_depth f32[Nb,Hb,Wb], bg_mask
+    u8[Nb,Hb,Wb]) or None, enable u8[B] or None, an int seed -> (rgb f32[B,3,S,S], depth f32[B,S,S])."""
+    rgb = np.asarray(rgb, dtype=np.float32)
+    depth = np.asarray(depth, dtype=np.float32)
+    B, S = depth.shape[0], depth.shape[1]
+    if rgb.shape != (B, 3, S, S) or depth.shape != (B, S, S):
+        raise ValueError("rgb must be [B,3,S,S] and depth [B,S,S], got %s and %s" % (rgb.shape, depth.shape))
+    if S < AUG_MIN_S:
+        raise ValueError("S=%d is below %d (a blur reaches 15 pixels)" % (S, AUG_MIN_S))
+    bank_shape = None
+    if background is not None:
+        if mask is None:
+            raise ValueError("the background paste needs the crop's mask")
+        bg_rgb, bg_depth, bg_mask = (np.asarray(background[0], np.uint8), np.asarray(background[1], np.float32),
+                                     np.asarray(background[2], np.uint8))
+        bank_shape = bg_rgb.shape[:3]
+        if bank_shape[1] < S + 2 or bank_shape[2] < S + 2:
+            raise ValueError("the bank's frames must be at least S + 2 a side")
+    draws = augment_draws_numpy(B, seed, S, bank_shape)
+    out_rgb, out_depth = rgb.copy(), depth.copy()
+    for b, d in enumerate(draws):
+        if enable is not None and not np.asarray(enable)[b]:
+            continue
+        img = aug_pass(aug_levels(rgb[b]).transpose(1, 2, 0), d["passes"][0])
+        if background is not None:
+            img, out_depth[b] = aug_paste(img, depth[b], np.asarray(mask)[b], bg_rgb, bg_depth, bg_mask, d["bank"], d["wy"], d["wx"])
+        if d["second"]:
+            img = aug_pass(img, d["passes"][1])
+        out_rgb[b] = aug_normalise(img.transpose(2, 0, 1))
+    return out_rgb, out_depth
+
+
+def augment_crops(rgb, depth, mask=None, background=None, enable=None, seed=0):
+    """`ops.augment_crops`: the augmentation of the YCB-V training crop on the device (ycbv_pbr.py:468-477), the definition
+    `augment_crops_numpy` restates -> (rgb, depth).  `augment_draws_numpy(B, seed)` tells what an int seed applies to every crop."""
+    return ops.augment_crops(rgb, depth, mask=mask, background=background, enable=enable, seed=seed)
+
+
 _fill_workspace = {}                                           # device -> the grow-only workspace of fill_depth
 
 
@@ -435,19 +680,12 @@ def depth_normals(depth, K, k_size=5, distance_threshold=2000, difference_thresh
     return out
 
 
-def dzi_boxes(bbox_xyxy, im_hw, pad_ratio=1.5, scale_ratio=0.25, shift_ratio=0.25, train=False, generator=None):
-    """`aug_bbox_DZI` (linemod_pbr.py:99-120) for a batch, in torch on the boxes' device: bbox_xyxy f32[B,4] = (x1,y1,x2,y2) ->
-    center f32[B,2] = (cx,cy), scale f32[B], the side of the square source window.  The box is padded by pad_ratio; with `train`
-    its side is scaled by 1 + scale_ratio * U(-1,1) and its centre shifted by shift_ratio * U(-1,1) of the box's width / height,
-    the three draws per box from `generator`.  scale <= max(H, W)."""
-    if not isinstance(bbox_xyxy, torch.Tensor) or bbox_xyxy.dim() != 2 or bbox_xyxy.shape[1] != 4:
-        raise ValueError("bbox_xyxy must be a tensor [B,4]")
-    box = bbox_xyxy.to(torch.float32)
+def _dzi_torch(box, im_hw, pad_ratio, scale_ratio, shift_ratio, u):
+    """The arithmetic of `dzi_boxes` on box f32[B,4] and the draws u f32[B,3] in [-1, 1) (None: no jitter)."""
     x1, y1, x2, y2 = box.unbind(1)
     bw, bh = x2 - x1, y2 - y1
     cx, cy = 0.5 * (x1 + x2), 0.5 * (y1 + y2)
-    if train:
-        u = 2.0 * torch.rand((box.shape[0], 3), device=box.device, generator=generator) - 1.0
+    if u is not None:
         cx = cx + bw * (shift_ratio * u[:, 1])
         cy = cy + bh * (shift_ratio * u[:, 2])
         scale = torch.maximum(bh, bw) * (1.0 + scale_ratio * u[:, 0]) * pad_ratio
@@ -455,6 +693,63 @@ def dzi_boxes(bbox_xyxy, im_hw, pad_ratio=1.5, scale_ratio=0.25, shift_ratio=0.2
         scale = torch.maximum(bh, bw) * pad_ratio
     scale = scale.clamp(max=float(max(im_hw)))
     return torch.stack([cx, cy], dim=1), scale
+
+
+def dzi_draws_numpy(B, seed):
+    """The three U(-1,1) of every box under jitter="hash" (include/gdm.h gdm_dzi_boxes_hip): f32[B,3], each 2 (w >> 8) 2^-24 - 1."""
+    with np.errstate(over="ignore"):
+        hb = _mix32(_mix32(np.uint32(int(seed) & 0xffffffff) ^ np.uint32(DZI_C)) ^ np.arange(B, dtype=np.uint32))
+        w = _mix32(hb[:, None] ^ np.arange(3, dtype=np.uint32)[None, :])
+    return np.float32(2.0) * ((w >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)) - np.float32(1.0)
+
+
+def dzi_boxes_numpy(bbox_xyxy, im_hw, pad_ratio=1.5, scale_ratio=0.25, shift_ratio=0.25, train=False, seed=0, u=None):
+    """The definition of `dzi_boxes(jitter="hash")` (include/gdm.h gdm_dzi_boxes_hip) restated on the CPU in fp32, one rounding per
+    operation: bbox f32[B,4] -> center f32[B,2], scale f32[B].  `u` f32[B,3] replaces the hash draws of `seed` (to compare with the
+    torch arithmetic on given numbers)."""
+    f32 = np.float32
+    box = np.asarray(bbox_xyxy, dtype=f32)
+    x1, y1, x2, y2 = box[:, 0], box[:, 1], box[:, 2], box[:, 3]
+    bw, bh = x2 - x1, y2 - y1
+    cx, cy = f32(0.5) * (x1 + x2), f32(0.5) * (y1 + y2)
+    with np.errstate(invalid="ignore"):
+        m = np.where((bh > bw) | np.isnan(bh), bh, bw)
+        if train:
+            u = dzi_draws_numpy(box.shape[0], seed) if u is None else np.asarray(u, dtype=f32)
+            cx = cx + bw * (f32(shift_ratio) * u[:, 1])
+            cy = cy + bh * (f32(shift_ratio) * u[:, 2])
+            scale = (m * (f32(1.0) + f32(scale_ratio) * u[:, 0])) * f32(pad_ratio)
+        else:
+            scale = m * f32(pad_ratio)
+        scale = np.where(scale > f32(max(im_hw)), f32(max(im_hw)), scale)
+    return np.stack([cx, cy], axis=1).astype(f32), scale.astype(f32)
+
+
+def dzi_boxes(bbox_xyxy, im_hw, pad_ratio=1.5, scale_ratio=0.25, shift_ratio=0.25, train=False, generator=None, jitter="torch", seed=0):
+    """`aug_bbox_DZI` (linemod_pbr.py:99-120) for a batch, on the boxes' device: bbox_xyxy f32[B,4] = (x1,y1,x2,y2) ->
+    center f32[B,2] = (cx,cy), scale f32[B], the side of the square source window.  The box is padded by pad_ratio; with `train`
+    its side is scaled by 1 + scale_ratio * U(-1,1) and its centre shifted by shift_ratio * U(-1,1) of the box's width / height.
+    scale <= max(H, W).  jitter="torch" (the default): torch arithmetic, the three draws per box from `generator`.  jitter="hash": one
+    launch of gdm_dzi_boxes_hip, the same arithmetic on the counter-based draws of include/gdm.h from `seed`, an int or a
+    one-element int32 device tensor read when the kernel runs (no generator state: the call captures in a graph and a replay draws
+    from the word the tensor then holds); `dzi_boxes_numpy` restates it."""
+    if jitter not in ("torch", "hash"):
+        raise ValueError("jitter must be 'torch' or 'hash', got %r" % (jitter,))
+    if not isinstance(bbox_xyxy, torch.Tensor) or bbox_xyxy.dim() != 2 or bbox_xyxy.shape[1] != 4:
+        raise ValueError("bbox_xyxy must be a tensor [B,4]")
+    box = bbox_xyxy.to(torch.float32)
+    if jitter == "hash":
+        box = ops._dev(box, torch.float32, "bbox_xyxy")
+        B = box.shape[0]
+        seed_val, seed_ptr = ops._seed_args(seed)
+        center = torch.empty((B, 2), dtype=torch.float32, device=box.device)
+        scale = torch.empty((B,), dtype=torch.float32, device=box.device)
+        check(_lib.lib().gdm_dzi_boxes_hip(box.data_ptr(), B, float(max(im_hw)), float(pad_ratio), float(scale_ratio), float(shift_ratio),
+                                           1 if train else 0, seed_val, seed_ptr, center.data_ptr(), scale.data_ptr(), ops._stream()),
+              "gdm_dzi_boxes_hip")
+        return center, scale
+    u = 2.0 * torch.rand((box.shape[0], 3), device=box.device, generator=generator) - 1.0 if train else None
+    return _dzi_torch(box, im_hw, pad_ratio, scale_ratio, shift_ratio, u)
 
 
 def crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=None):
@@ -498,7 +793,7 @@ def crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=None):
 
 
 def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, train=False, generator=None, normals=None,
-                           depth_fill=None, sampler="torch", seed=0, build_pyramid=True):
+                           depth_fill=None, sampler="torch", seed=0, build_pyramid=True, augment=None, jitter="torch"):
     """The whole item from the raw frame: rgb_u8 u8[B,H,W,3], depth f32[B,H,W] (m), K f32[B,3,3], bbox_xyxy f32[B,4], mask
     u8[B,H,W] or None -> the dict of `make_inputs` (rgb, cld_rgb_nrm, choose, dpt_xyz, origin_labels with a mask, the neighbour
     pyramid) plus n_valid i32[B], the number of depth > 1e-6 pixels of each crop (the loader drops a training item below 200,
@@ -517,11 +812,24 @@ def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, 
     sample_valid_pixels and the assembly on either leg with ONE launch, ops.sample_assemble: the points follow the written rule of
     include/gdm.h (restated as sample_assemble_numpy) from `seed`, an int or a one-element int32 device tensor; `generator` then only
     feeds the box jitter of train=True.  build_pyramid=False leaves the neighbour pyramid to the caller (infer.pipeline_step builds it
-    when the dict lacks it)."""
+    when the dict lacks it).
+
+    jitter="hash" draws the box jitter of train=True from `seed` as well (dzi_boxes(jitter="hash")).  augment=dict(background=(bg_rgb,
+    bg_depth, bg_mask) or None, enable=u8[B] or None) is the YCB-V TRAINING item (ycbv_pbr.py:468-477; the LineMOD item applies none):
+    it needs depth_fill and a mask, draws from `seed`, and runs augment_crops on the crop before the fill, so the order is crop ->
+    augment -> fill_depth of the augmented depth -> normals, sampling and assembly from the result.  The dict's rgb is then the
+    augmented crop and depth_aug f32[B,S,S] the depth the fill read.  dpt_xyz stays the unaugmented crop's, as in the reference, whose
+    cld is gathered from dpt_xyz_clip: a point chosen on the pasted background has xyz = (0,0,0), like one inside a filled hole.  With
+    train=True, jitter="hash", sampler="hash" and a device seed word the whole item captures in torch.cuda.graph."""
     if sampler not in ("torch", "hash"):
         raise ValueError("sampler must be 'torch' or 'hash', got %r" % (sampler,))
+    if augment is not None:
+        if depth_fill is None or mask is None:
+            raise ValueError("augment= is the YCB-V training item: it needs depth_fill and a mask")
+        if set(augment) - {"background", "enable"}:
+            raise ValueError("augment takes the keys 'background' and 'enable', got %s" % sorted(augment))
     B, H, W = depth.shape
-    center, scale = dzi_boxes(bbox_xyxy, (H, W), train=train, generator=generator)
+    center, scale = dzi_boxes(bbox_xyxy, (H, W), train=train, generator=generator, jitter=jitter, seed=seed)
     extra = {}
     if depth_fill is None:
         if normals is None:
@@ -535,6 +843,10 @@ def make_inputs_from_boxes(rgb_u8, depth, K, bbox_xyxy, S, n_points, mask=None, 
         if normals is not None:
             raise ValueError("normals= goes with depth_fill=None: the YCB-V item takes its normals from the filled crop")
         crop = crop_from_boxes(rgb_u8, depth, None, K, center, scale, S, mask=mask)
+        if augment is not None:
+            crop["rgb"], crop["depth"] = augment_crops(crop["rgb"], crop["depth"], mask=crop["mask"], background=augment.get("background"),
+                                                       enable=augment.get("enable"), seed=seed)
+            extra["depth_aug"] = crop["depth"]
         filled = fill_depth(crop["depth"], mode=depth_fill)
         xyz, nrm = crop["dpt_xyz"], depth_normals(filled, K)
         valid_depth = filled

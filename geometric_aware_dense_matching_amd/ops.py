@@ -2272,6 +2272,66 @@ def sample_assemble(valid_depth, dpt_xyz, rgb, normals, n_points, mask=None, see
     return choose, cld_rgb_nrm, labels, n_valid
 
 
+def _seed_args(seed):
+    """seed -> (value, device pointer or None): an int (its low 32 bits) or a one-element int32 device tensor read when the kernel runs."""
+    if torch.is_tensor(seed):
+        if not seed.is_cuda or seed.dtype != torch.int32 or seed.numel() != 1:
+            raise ValueError("a tensor seed must be a one-element int32 device tensor")
+        return 0, seed.data_ptr()
+    return int(seed) & 0xffffffff, None
+
+
+def augment_crops(rgb, depth, mask=None, background=None, enable=None, seed=0):
+    """The YCB-V training item's colour, noise and background augmentation of the crop by the integer rule of include/gdm.h
+    (gdm_augment_crops_hip), two launches whatever B: rgb f32[B,3,S,S] as crop_from_boxes wrote it, depth f32[B,S,S], mask u8[B,S,S]
+    (needed with a background), background = (bg_rgb u8[Nb,Hb,Wb,3], bg_depth f32[Nb,Hb,Wb], bg_mask u8[Nb,Hb,Wb]) or None,
+    enable u8[B] or None (0 = the crop is copied bit for bit) -> (rgb f32[B,3,S,S], depth f32[B,S,S]).  seed as for sample_assemble.
+    The uint8 image between the passes lives in the current BufferPool's scratch buffer."""
+    rgb = _dev(rgb, torch.float32, "rgb")
+    depth = _dev(depth, torch.float32, "depth")
+    if depth.dim() != 3 or depth.shape[1] != depth.shape[2]:
+        raise ValueError("depth must be [B,S,S], got %s" % (tuple(depth.shape),))
+    B, S = depth.shape[0], depth.shape[1]
+    if tuple(rgb.shape) != (B, 3, S, S):
+        raise ValueError("rgb must be %s, got %s" % ([B, 3, S, S], tuple(rgb.shape)))
+    if not _lib.GDM_AUG_MIN_S <= S <= _lib.GDM_AUG_MAX_S:
+        raise ValueError("augment_crops: S=%d not in [%d, %d] (a blur reaches 15 pixels)" % (S, _lib.GDM_AUG_MIN_S, _lib.GDM_AUG_MAX_S))
+    mp = ep = None
+    if mask is not None:
+        mask = _dev(mask, torch.uint8, "mask")
+        if tuple(mask.shape) != (B, S, S):
+            raise ValueError("mask must be [B=%d,S=%d,S=%d], got %s" % (B, S, S, tuple(mask.shape)))
+        mp = mask.data_ptr()
+    if enable is not None:
+        enable = _dev(enable, torch.uint8, "enable")
+        if tuple(enable.shape) != (B,):
+            raise ValueError("enable must be [B=%d], got %s" % (B, tuple(enable.shape)))
+        ep = enable.data_ptr()
+    bp, Nb, Hb, Wb = (None, None, None), 0, 0, 0
+    if background is not None:
+        if mask is None:
+            raise ValueError("augment_crops: the background paste needs the crop's mask")
+        bg_rgb = _dev(background[0], torch.uint8, "bg_rgb")
+        bg_depth = _dev(background[1], torch.float32, "bg_depth")
+        bg_mask = _dev(background[2], torch.uint8, "bg_mask")
+        if bg_rgb.dim() != 4 or bg_rgb.shape[3] != 3:
+            raise ValueError("bg_rgb must be [Nb,Hb,Wb,3], got %s" % (tuple(bg_rgb.shape),))
+        Nb, Hb, Wb = bg_rgb.shape[:3]
+        if tuple(bg_depth.shape) != (Nb, Hb, Wb) or tuple(bg_mask.shape) != (Nb, Hb, Wb):
+            raise ValueError("bg_depth and bg_mask must be %s, got %s and %s" % ([Nb, Hb, Wb], tuple(bg_depth.shape), tuple(bg_mask.shape)))
+        if Nb < 1 or Hb < S + 2 or Wb < S + 2:
+            raise ValueError("the bank's frames must be at least S + 2 = %d a side, got %d x %d (Nb = %d)" % (S + 2, Hb, Wb, Nb))
+        bp = (bg_rgb.data_ptr(), bg_depth.data_ptr(), bg_mask.data_ptr())
+    seed_val, seed_ptr = _seed_args(seed)
+    L = _lib.lib()
+    ws = _workspace(L.gdm_augment_workspace_bytes(B, S), rgb.device)
+    out_rgb, out_depth = torch.empty_like(rgb), torch.empty_like(depth)
+    check(L.gdm_augment_crops_hip(rgb.data_ptr(), depth.data_ptr(), mp, bp[0], bp[1], bp[2], ep, B, S, Nb, Hb, Wb, seed_val, seed_ptr,
+                                  out_rgb.data_ptr(), out_depth.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "gdm_augment_crops_hip")
+    return out_rgb, out_depth
+
+
 # --------------------------------------------------------------------------------------
 # BOP pose errors (lib/pysixd/pose_error.py:22-179): gdm_bop.hip
 

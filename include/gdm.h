@@ -695,6 +695,80 @@ int gdm_sample_assemble_hip(const float* valid_depth, const float* dpt_xyz, cons
                             float* cld_rgb_nrm, uint8_t* labels, int32_t* n_valid, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* Front end, the YCB-V training item's augmentation of the CROP (datasets/ycbv/ycbv_pbr.py:468-477: rgb_add_noise, add_real_back,
+ * with probability 0.2 rgb_add_noise again, normalize_color), between gdm_warp_crop_hip and gdm_fill_depth_hip.  rgb f32[B,3,S,S]
+ * as gdm_warp_crop_hip wrote it, depth f32[B,S,S], mask u8[B,S,S] -> out_rgb f32[B,3,S,S], out_depth f32[B,S,S] (neither may alias
+ * an input).  Everything between the first and the last line below is integer arithmetic on uint8 levels and is DEFINED here
+ * operation by operation (frontend.augment_crops_numpy restates it; the kernel equals it bit for bit; parity with a cv2 build or
+ * with np.random streams is not claimed).  `/` is the quotient of non-negative integers, `>>` the arithmetic shift
+ * (a floor), clip(v) = min(255, max(0, v)).
+ *   levels    v_c = (int) rintf(min(255, max(0, ((x_c std_c) + mean_c) 255.0f)))    (NaN -> 0; exact for a crop: 1.5e-5 from an integer)
+ *   normalise x_c = (((float) v_c / 255.0f) - mean_c) / std_c                      (the three fp32 operations of gdm_warp_crop_hip,
+ *                                                                                   mean .485 .456 .406, std .229 .224 .224)
+ * DRAWS.  mix = lowbias32 as above;  hb = mix(mix(seed ^ 0x85ebca6b) ^ b);  decision word D(k) = mix(hb ^ k), k < 256;
+ *   below(w, n) = ((uint64) w n) >> 32;  "with probability 0.2" = w > 0xcccccccc;  "with probability 0.8" = w > 0x33333333
+ *   pixel word of pass q, noise stream e, pixel p = y S + x, channel c:  mix(mix(hb ^ (256 + 2 q + e)) ^ (3 p + c))
+ *   pass q in {0, 1} uses k = 16 q + j:
+ *     j 0  ks = 320 + below(D, 52)          saturation gain in 1/256 (1.25 .. 1.45)
+ *       1  kv = 294 + below(D, 52)          value gain in 1/256 (1.15 .. 1.35)
+ *       2  sharpen with probability 0.2;    3  u = D >> 24: the centre weight is c = 9 + 3 u / 256
+ *       4  motion blur with probability 0.2;  5  angle = below(D, 360) degrees;  6  length L = below(D, 15) + 1
+ *       7  Gaussian blur with probability 0.2;  8  3 x 3 with probability 0.8, else 5 x 5;  9  sigma level l = D >> 24
+ *       10 noise range n = 15 with probability 0.8, else 25;  11 sigma = below(D, n);  12 further noise of sigma 7 with probability 0.2
+ *   k = 32: a second pass with probability 0.2;  33: bank frame n = D mod Nb;  34: wy = D mod (Hb - S - 1);  35: wx = D mod (Wb - S - 1)
+ * ONE PASS, in this order, every stage on all three channels of the whole S x S image (a tap outside it reads the pixel reflected
+ * about the border pixel, BORDER_REFLECT_101: -i -> i, S - 1 + i -> S - 1 - i):
+ *   1 gain     M = max_c v_c, m = min_c v_c, d = M - m;  M' = min(255, (M kv) >> 8);  s = M > 0 ? (255 d + (M >> 1)) / M : 0;
+ *              s' = min(255, (s ks) >> 8);  m' = M' - (M' s' + 127) / 255;
+ *              v_c' = d > 0 ? m' + ((v_c - m) (M' - m') + (d >> 1)) / d : M'     (the hue, i.e. the ratio of the middle channel, is kept:
+ *              cv2 would quantise it to 0 .. 180; S and V are symmetric in the channels, so the loader's BGR/RGB mix-up is immaterial)
+ *   2 sharpen  c256 = 2304 + 3 u, q = 256 + 3 u (= c256 - 2048);  t = 2 (c256 v - 256 (sum of the 8 neighbours)) + q;
+ *              v' = t < 0 ? 0 : min(255, t / (2 q))                               (round to nearest, saturate)
+ *   3 motion   cs = gdm_aug_cos_q14[angle], sn = gdm_aug_cos_q14[(angle + 270) mod 360] (csrc/gdm_augment_tables.h, rint(16384 cos));
+ *              a = (max(|cs|, |sn|) L 2) >> 14 (1 <= a <= 30; a <= 0 would leave the image as it is);  cx = a / 2;
+ *              ex = cx + trunc(cs L / 16384), ey = cx + trunc(sn L / 16384) (trunc towards zero);  the taps are the points of the
+ *              integer Bresenham line from (cx, cx) to (ex, ey) that lie inside [0, a)^2 (what cv2.line draws into the a x a kernel):
+ *                dx = |ex - cx|, sx = sign, dy = -|ey - cx|, sy = sign, err = dx + dy;  repeat { plot (x, y); stop at (ex, ey);
+ *                e2 = 2 err;  if (e2 >= dy) { err += dy; x += sx; }  if (e2 <= dx) { err += dx; y += sy; } }
+ *              a tap (x, y) reads pixel (row + y - cx, column + x - cx);  n taps (1 <= n <= 16):  v' = (sum + (n >> 1)) / n
+ *   4 Gaussian w = gdm_aug_gauss3[l] or gdm_aug_gauss5[l] (weights w_|i| summing to 256 over a row);
+ *              v' = (sum_{i,j} w_|i| w_|j| v[y+i, x+j] + 32768) >> 16
+ *   5 noise    z(word) = (sum of its four bytes) - 510 (Irwin-Hall, standard deviation 147.8, tails end at 3.45 sigma);
+ *              v' = clip(v + ((z(word of stream 0) sigma 443 + 32768) >> 16));  with further noise then
+ *              v'' = clip(v' + ((z(word of stream 1) 7 443 + 32768) >> 16))
+ * PASTE (add_real_back; only with a bank: bg_rgb u8[Nb,Hb,Wb,3], bg_depth f32[Nb,Hb,Wb] in metres, bg_mask u8[Nb,Hb,Wb], all three
+ * or none, Hb, Wb >= S + 2): keep = bg_mask[n, wy+y, wx+x] < 255;
+ *   rgb   = mask[b,y,x] > 0 ? rgb : (keep ? bg_rgb[n, wy+y, wx+x, :] : 0)
+ *   depth = depth[b,y,x] > 1e-6f ? depth : (keep ? bg_depth[n, wy+y, wx+x] : 0.0f)        (without a bank out_depth = depth)
+ * THE CALL: levels, pass 0, paste, with probability 0.2 pass 1, normalise.  enable u8[B] or NULL: a crop with enable[b] == 0 is
+ * copied bit for bit (the loader's img_typ == 'synt' condition).  seed_dev as for gdm_sample_assemble_hip.  dpt_xyz is no argument:
+ * the loader gathers cld from the unaugmented crop.
+ * 1 <= B <= 65535, GDM_AUG_MIN_S <= S <= GDM_AUG_MAX_S (a blur reaches 15 pixels: one reflection needs S >= 32).  workspace: the uint8
+ * image between the passes, gdm_augment_workspace_bytes(B, S) bytes (0 for a bad shape), 4-byte aligned.  Two launches whatever B: one
+ * workgroup per (crop, 32 x 32 tile) keeps the tile and the halo its crop's drawn stages need (0 .. 18 pixels) in LDS and recomputes
+ * the halo; no allocation, no host read, no atomics. */
+#define GDM_AUG_MIN_S 32
+#define GDM_AUG_MAX_S 4096
+size_t gdm_augment_workspace_bytes(int B, int S);
+int gdm_augment_crops_hip(const float* rgb, const float* depth, const uint8_t* mask, const uint8_t* bg_rgb, const float* bg_depth,
+                          const uint8_t* bg_mask, const uint8_t* enable, int B, int S, int Nb, int Hb, int Wb, uint32_t seed,
+                          const uint32_t* seed_dev, float* out_rgb, float* out_depth, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* Measurement aid (tools/augment_profile.py): while on != 0, later gdm_augment_crops_hip calls of this process apply sharpen, motion
+ * blur, Gaussian blur and the second pass to EVERY crop, their parameters drawn as usual -- the cost of the heaviest item, not a result
+ * the rule above defines.  Off by default. */
+void gdm_augment_force_all_stages(int on);
+/* The loader's aug_bbox_DZI (datasets/lm/linemod_pbr.py:99-120) with counter-based draws: bbox f32[B,4] = (x1,y1,x2,y2) ->
+ * center f32[B,2], scale f32[B].  fp32, one rounding per operation, in this order:
+ *   bw = x2 - x1, bh = y2 - y1, cx = 0.5 (x1 + x2), cy = 0.5 (y1 + y2), m = bh > bw or bh is NaN ? bh : bw
+ *   train == 0:  scale = m pad_ratio
+ *   train != 0:  u_k = 2 ((float) (w_k >> 8) 2^-24) - 1 (exact), w_k = mix(mix(mix(seed ^ 0xc2b2ae35) ^ b) ^ k), k = 0, 1, 2;
+ *                cx = cx + bw (shift_ratio u_1), cy = cy + bh (shift_ratio u_2), scale = (m (1 + scale_ratio u_0)) pad_ratio
+ *   scale = scale > max_side ? max_side : scale
+ * (frontend.dzi_boxes_numpy restates it; frontend.dzi_boxes(jitter="torch") is the same arithmetic on torch.rand draws.) */
+int gdm_dzi_boxes_hip(const float* bbox, int B, float max_side, float pad_ratio, float scale_ratio, float shift_ratio, int train,
+                      uint32_t seed, const uint32_t* seed_dev, float* center, float* scale, void* stream);
+
 /* ---- training-mode BatchNorm (+ ReLU / LeakyReLU), forward and backward -------------------------------------------------------
  * Replaces the conv -> nn.BatchNorm{1,2}d -> activation chains of the embedding network in the training step
  * (models/pytorch_utils.py:70-124, models/RandLA/pytorch_utils.py:34-105, models/cnn/extractors.py:36-58; train_lm.py:171-225).
