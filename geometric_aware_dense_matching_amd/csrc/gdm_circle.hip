@@ -33,9 +33,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int ROWB = 512;                       // packed row: 128 bf16 hi | 128 bf16 lo
 constexpr int CM_THREADS = 256;                 // 4 waves
@@ -56,7 +53,7 @@ __device__ __forceinline__ unsigned pack2(float a, float b)
 }
 __device__ __forceinline__ float hi_of(float a) { return (float)(__bf16)a; }
 
-__device__ __forceinline__ void split8(const float* v, u32x4& hi, u32x4& lo)
+__device__ __forceinline__ void split8(const float* v, gdm_u32x4& hi, gdm_u32x4& lo)
 {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -64,8 +61,6 @@ __device__ __forceinline__ void split8(const float* v, u32x4& hi, u32x4& lo)
         lo[j] = pack2(v[2 * j] - hi_of(v[2 * j]), v[2 * j + 1] - hi_of(v[2 * j + 1]));
     }
 }
-
-__device__ __forceinline__ int swz(int row, int ch) { return row * ROWB + (((ch & 16) | ((ch ^ row) & 15)) << 4); }
 
 // accumulator register q (0..7) of k-step ks, lane half h  ->  streamed index inside a 32-item sub-tile
 __host__ __device__ __forceinline__ int acc_row(int ks, int h, int q) { return (q & 3) + 8 * (2 * ks + (q >> 2)) + 4 * h; }
@@ -89,11 +84,11 @@ __global__ __launch_bounds__(256) void cm_pack_kernel(const float* __restrict__ 
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = t[r][ch * 8 + j];
-        u32x4 hi, lo;
+        gdm_u32x4 hi, lo;
         split8(v, hi, lo);
         unsigned char* o = rows + ((long)tile * 32 + r) * ROWB;
-        *reinterpret_cast<u32x4*>(o + ch * 16) = hi;
-        *reinterpret_cast<u32x4*>(o + 256 + ch * 16) = lo;
+        *reinterpret_cast<gdm_u32x4*>(o + ch * 16) = hi;
+        *reinterpret_cast<gdm_u32x4*>(o + 256 + ch * 16) = lo;
     }
     for (int e = tid; e < 512; e += 256) {                       // d-major: (d, piece = 2 ks + h)
         const int d = e >> 2, pc = e & 3;
@@ -101,11 +96,11 @@ __global__ __launch_bounds__(256) void cm_pack_kernel(const float* __restrict__ 
         float v[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = t[acc_row(ks, h, q)][d];
-        u32x4 hi, lo;
+        gdm_u32x4 hi, lo;
         split8(v, hi, lo);
         unsigned char* o = tp + (long)tile * 2 * TP_G + d * 64 + pc * 16;
-        *reinterpret_cast<u32x4*>(o) = hi;
-        *reinterpret_cast<u32x4*>(o + TP_G) = lo;
+        *reinterpret_cast<gdm_u32x4*>(o) = hi;
+        *reinterpret_cast<gdm_u32x4*>(o + TP_G) = lo;
     }
     if (tid < 32) {
         float s = 0.f;
@@ -230,13 +225,13 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
     const int nstage = (own_is_x ? a.Mp : a.Rp) / CM_ST;
 
     // owner operand: 8 k-steps x (hi, lo)
-    u32x4 ohi[8], olo[8];
+    gdm_u32x4 ohi[8], olo[8];
     {
         const unsigned char* r = orows + (long)(own0 + j) * ROWB + h * 16;
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            ohi[s] = *reinterpret_cast<const u32x4*>(r + s * 32);
-            olo[s] = *reinterpret_cast<const u32x4*>(r + 256 + s * 32);
+            ohi[s] = *reinterpret_cast<const gdm_u32x4*>(r + s * 32);
+            olo[s] = *reinterpret_cast<const gdm_u32x4*>(r + 256 + s * 32);
         }
     }
     // per-lane constants of the owner row (MODE 0 / 1)
@@ -255,7 +250,7 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
     const float gam = a.gamma, mm = a.m;
     float sum_p = 0.f, sum_n = 0.f;
 
-    f32x16 outacc[4];
+    gdm_f32x16 outacc[4];
     if (MODE != 0) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -270,7 +265,7 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int gch = i * CM_THREADS + tid;               // 2048 chunks of 16 B
-                *reinterpret_cast<u32x4*>(lrows + swz(gch >> 5, gch & 31)) = *reinterpret_cast<const u32x4*>(src + (long)gch * 16);
+                *reinterpret_cast<gdm_u32x4*>(lrows + gdm_swz<ROWB>(gch >> 5, gch & 31)) = *reinterpret_cast<const gdm_u32x4*>(src + (long)gch * 16);
             }
             if (MODE != 0) {
                 const unsigned char* tsrc = stp + (long)st * (CM_ST / 32) * 2 * TP_G;
@@ -278,7 +273,7 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
                 for (int i = 0; i < 8; ++i) {
                     const int gch = i * CM_THREADS + tid;           // (sub*2 + plane) * 512 + d * 4 + piece
                     const int sp = gch >> 9, d = (gch >> 2) & 127, pc = gch & 3;
-                    *reinterpret_cast<u32x4*>(ltp + sp * TP_L + d * TP_LSTRIDE + pc * 16) = *reinterpret_cast<const u32x4*>(tsrc + (long)gch * 16);
+                    *reinterpret_cast<gdm_u32x4*>(ltp + sp * TP_L + d * TP_LSTRIDE + pc * 16) = *reinterpret_cast<const gdm_u32x4*>(tsrc + (long)gch * 16);
                 }
             }
             if (MODE == 2) {                                        // per streamed scene row: lse_p, lse_n, coef, positives word
@@ -295,16 +290,16 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
             unsigned word = 0;
             if (own_is_x) word = pos_word<SYM>(a, rg, rc2, ritem, t32);
             // ---- S tile: acc[i][j] = <stream_i, owner_j> ----
-            f32x16 acc;
+            gdm_f32x16 acc;
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                const bf16x8 sh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lrows + swz(sub * 32 + j, 2 * s + h)));
-                const bf16x8 sl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lrows + swz(sub * 32 + j, 16 + 2 * s + h)));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sh, __builtin_bit_cast(bf16x8, olo[s]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sl, __builtin_bit_cast(bf16x8, ohi[s]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sh, __builtin_bit_cast(bf16x8, ohi[s]), acc, 0, 0, 0);
+                const gdm_bf16x8 sh = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(lrows + gdm_swz<ROWB>(sub * 32 + j, 2 * s + h)));
+                const gdm_bf16x8 sl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(lrows + gdm_swz<ROWB>(sub * 32 + j, 16 + 2 * s + h)));
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sh, __builtin_bit_cast(gdm_bf16x8, olo[s]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sl, __builtin_bit_cast(gdm_bf16x8, ohi[s]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sh, __builtin_bit_cast(gdm_bf16x8, ohi[s]), acc, 0, 0, 0);
             }
             // ---- element-wise: register r <-> streamed item i = acc_row(r >> 3, h, r & 7), lane <-> owner item j ----
             const int cbase = t32 * 32;                             // MODE 0/1: first vertex of the sub-tile
@@ -341,14 +336,14 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
             // ---- out^T[d][j] += sum_i stream^T[d][i] G[i][j]: G from the accumulator registers as the B operand ----
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                u32x4 gh, gl;
+                gdm_u32x4 gh, gl;
                 split8(&G[8 * ks], gh, gl);
-                const bf16x8 bgh = __builtin_bit_cast(bf16x8, gh), bgl = __builtin_bit_cast(bf16x8, gl);
+                const gdm_bf16x8 bgh = __builtin_bit_cast(gdm_bf16x8, gh), bgl = __builtin_bit_cast(gdm_bf16x8, gl);
 #pragma unroll
                 for (int db = 0; db < 4; ++db) {
                     const unsigned char* p = ltp + (sub * 2) * TP_L + (db * 32 + j) * TP_LSTRIDE + (ks * 2 + h) * 16;
-                    const bf16x8 th = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p));
-                    const bf16x8 tl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p + TP_L));
+                    const gdm_bf16x8 th = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(p));
+                    const gdm_bf16x8 tl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(p + TP_L));
                     outacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(th, bgl, outacc[db], 0, 0, 0);
                     outacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tl, bgh, outacc[db], 0, 0, 0);
                     outacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(th, bgh, outacc[db], 0, 0, 0);

@@ -21,22 +21,12 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
 constexpr int ROWB = 512;                 // bytes per packed row (128 channels, hi | lo)
 constexpr int CV_PIX = 256;               // pixels per workgroup (32 per wave)
 constexpr int CV_CO = 128;                // output channels per workgroup
 constexpr int CV_PANEL = CV_CO * ROWB;    // 64 KiB
-#ifndef GDM_CONV_TAP_INNER
-#define GDM_CONV_TAP_INNER 1             // 1: panels chunk-major (nine taps of a chunk back to back); 0: tap-major (rounds 1-3)
-#endif
 #ifndef GDM_CONV16_PF
 #define GDM_CONV16_PF 2
-#endif
-#ifndef GDM_CONV_GLDS
-#define GDM_CONV_GLDS 1                  // 1: weight panels of the 16x16x32 kernel by LDS-DMA (eight-wave workgroups); 0: through registers
 #endif
 
 __device__ __forceinline__ void split8(const float* v, unsigned (&hi)[4], unsigned (&lo)[4])
@@ -112,8 +102,6 @@ __global__ __launch_bounds__(256) void conv_pack_w_kernel(const float* __restric
     *reinterpret_cast<uint4*>(r + 256 + ch * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
 }
 
-__device__ __forceinline__ int swz(int col, int ch) { return col * ROWB + (((ch & 16) | ((ch ^ col) & 15)) << 4); }
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // The same kernel on v_mfma_f32_16x16x32_bf16.  Same workgroup tile (256 pixels x 128 output channels), same panels, same LDS
 // image, same operand bytes per MFMA cycle (a wave's 32 x 128 tile is 2 x 8 tiles of 16 x 16; a k-step is 32 channels: two
@@ -124,30 +112,33 @@ __device__ __forceinline__ int swz(int col, int ch) { return col * ROWB + (((ch 
 //   B fragment (S, cb): lane l -> output channel 16 cb + (l & 15), same channel group            = 16-B chunk 4 S + (l >> 4) of its row
 //   accumulator (ph, cb): lane l -> channel 16 cb + (l & 15), pixels 16 ph + 4 (l >> 4) + 0..3   = one 16-byte store
 // ---------------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 // pixel fragments (16 pixels each) per wave: 2 = eight waves of 32 pixels (two waves per SIMD), 4 = four waves of 64 pixels (one
 // wave per SIMD, 512 registers): every B fragment read from LDS then feeds twice the MFMAs and no partner wave competes for the
 // matrix pipe; the per-panel barrier joins four waves instead of eight.
 #ifndef GDM_CONV_NPH
 #define GDM_CONV_NPH 2
 #endif
-// 1: the MFMAs of a unit are issued product-major (no MFMA directly behind the one whose accumulator it reads); 0: accumulator-major.
-// Measured equal (512 -> 512: 191 vs 188 us on two boxes; the register-only probe gdm_mfma_probe_hip sustains 2.25 PF/s with independent and
-// 2.40 PF/s with back-to-back dependent MFMAs at two waves per SIMD): dependent issue is not what idles the pipe.  0 ships.
+// The MFMAs of a unit are issued accumulator-major.  Product-major issue (no MFMA directly behind the one whose accumulator it reads) was
+// measured equal (512 -> 512: 191 vs 188 us on two boxes; the register-only probe gdm_mfma_probe_hip sustained 2.25 PF/s with independent and
+// 2.40 PF/s with back-to-back dependent MFMAs at two waves per SIMD): dependent issue was not what idled the pipe.
 // k-steps (of the 4 of a 128-channel panel) whose operand reload is deferred to the top of the next panel
 #ifndef GDM_CONV16_LATE
 #define GDM_CONV16_LATE 1
-#endif
-#ifndef GDM_CONV_MFMA_ORDER
-#define GDM_CONV_MFMA_ORDER 0
 #endif
 constexpr int MF_NPH = GDM_CONV_NPH;
 constexpr int MF_WPIX = 16 * MF_NPH;                  // pixels per wave
 constexpr int MF_WAVES = CV_PIX / MF_WPIX;
 constexpr int MF_THREADS = MF_WAVES * 64;
-constexpr int MF_TSTRIDE = 132;                       // floats per pixel row of a wave's output tile in LDS (128 + 4: conflict-free reads)
-constexpr int MF_SMEM = 2 * CV_PANEL > CV_PIX * MF_TSTRIDE * 4 ? 2 * CV_PANEL : CV_PIX * MF_TSTRIDE * 4;
+// Dynamic LDS of a workgroup with NCB 16-channel output blocks: two weight panels, or (packed output) the waves' output tiles of
+// NCB * 16 + 4 floats per pixel row (conflict-free reads) where those are larger.  Also the bound every non-GADD instance is allowed.
+constexpr int conv_lds_bytes(int NCB)
+{
+    const int panels = 2 * NCB * 16 * ROWB, tiles = CV_PIX * (NCB * 16 + 4) * 4;
+    return panels > tiles ? panels : tiles;
+}
+constexpr int LDS_MAX = 160 * 1024;                   // a CU's LDS: the bound of the GADD instances, which stage their rows of gt behind the tiles
+static_assert(conv_lds_bytes(8) == 135168 && conv_lds_bytes(4) == 69632 && conv_lds_bytes(9) == 151552 && conv_lds_bytes(8) >= 2 * CV_PANEL,
+              "at least what every launch site passes");
 
 // NCB = 16-channel output blocks per workgroup: 8 (128 channels) or 4 (64 channels: twice the workgroups for the layers whose 128-channel
 // tiling leaves half the chip idle -- layer1-3 of the trunk at batch 16 -- and no zero-padded weight rows for 64-channel layers)
@@ -215,17 +206,13 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
         avoff[ph] = (int)(((long)kg * plane + pixbase) * 16);
     }
 
-    u32x4 ahi[NS][NPH], alo[NS][NPH];                               // fragments of k-step S, pixel fragment ph
+    gdm_u32x4 ahi[NS][NPH], alo[NS][NPH];                               // fragments of k-step S, pixel fragment ph
     // Panel bookkeeping in scalar registers, advanced by counters (no division in the loop): panel = (chunk, ky, kx), chunk-major
-    // (GDM_CONV_TAP_INNER) or tap-major.  pan_a / pan_w: byte offsets of a panel's operand rows / weight rows.
+    // (the nine taps of a chunk back to back).  pan_a / pan_w: byte offsets of a panel's operand rows / weight rows.
     struct Pan { int chunk, ky, kx; };
     auto pan_next = [&](Pan p) -> Pan {
         if (TAPS == 1) { ++p.chunk; return p; }
-        if (GDM_CONV_TAP_INNER) {
-            if (++p.kx == 3) { p.kx = 0; if (++p.ky == 3) { p.ky = 0; ++p.chunk; } }
-        } else {
-            if (++p.chunk == nchunk) { p.chunk = 0; if (++p.kx == 3) { p.kx = 0; ++p.ky; } }
-        }
+        if (++p.kx == 3) { p.kx = 0; if (++p.ky == 3) { p.ky = 0; ++p.chunk; } }
         return p;
     };
     const int a_base = (int)(((long)(rowidx ? 0 : b) * nchunk * 32) * plane * 16);
@@ -236,14 +223,14 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
     auto load_a = [&](int r, int S) {
 #pragma unroll
         for (int ph = 0; ph < NPH; ++ph) {
-            ahi[S][ph] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, avoff[ph], r + S * sstride, 0));
-            alo[S][ph] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, avoff[ph], r + S * sstride + lostride, 0));
+            ahi[S][ph] = __builtin_bit_cast(gdm_u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, avoff[ph], r + S * sstride, 0));
+            alo[S][ph] = __builtin_bit_cast(gdm_u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, avoff[ph], r + S * sstride + lostride, 0));
         }
     };
     // a weight panel is staged in two halves (global -> registers -> LDS), each half in flight for half a panel: 16 registers
     constexpr int THREADS = WV * 64, WGPIX = WV * MF_WPIX;
     constexpr int HS = (NCB * 512 / THREADS) / 2;
-    u32x4 stage[HS];
+    gdm_u32x4 stage[HS];
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(wpk), (short)0, 0x7ffffff0, 0x00020000);
     const int w_base = (wbstride ? (int)(((long)bx * WGPIX / hw) * wbstride) : 0) + co0 * ROWB;
     const int w_panel = ((Cout + 127) & ~127) * ROWB;               // the packed weights are (tap, chunk, co) rows
@@ -251,22 +238,22 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
     auto stage_load = [&](int src, int half) {
 #pragma unroll
         for (int i = 0; i < HS; ++i)
-            stage[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wr, tid * 16, src + (half * HS + i) * THREADS * 16, 0));
+            stage[i] = __builtin_bit_cast(gdm_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wr, tid * 16, src + (half * HS + i) * THREADS * 16, 0));
     };
     auto stage_store = [&](int buf, int half) {
         unsigned char* base = smem + buf * PANEL;
 #pragma unroll
         for (int i = 0; i < HS; ++i) {
             const int g = (half * HS + i) * THREADS + tid;
-            *reinterpret_cast<u32x4*>(base + swz(g >> 5, g & 31)) = stage[i];
+            *reinterpret_cast<gdm_u32x4*>(base + gdm_swz<ROWB>(g >> 5, g & 31)) = stage[i];
         }
     };
-    // GLDS (eight-wave workgroups): the weight panel goes global -> LDS by LDS-DMA (buffer_load ... lds), no staging registers and no
+    // GLDS (eight-wave workgroups; the four-wave half tiles stage through registers, above): the weight panel goes global -> LDS by LDS-DMA (buffer_load ... lds), no staging registers and no
     // ds_write pass.  A wave instruction fills 1 KiB = two 512-byte rows LINEARLY (LDS address = M0 base + lane * 16), so the XOR
     // swizzle of the LDS image sits on the per-lane SOURCE offset: lane p of piece j = 8 i + wave writes slot p & 31 of row
-    // col = 2 j + (p >> 5), which must hold chunk ch = (s & 16) | ((s ^ col) & 15) of that row (swz is an involution); 2 j = 16 i + 2 wave,
+    // col = 2 j + (p >> 5), which must hold chunk ch = (s & 16) | ((s ^ col) & 15) of that row (gdm_swz is an involution); 2 j = 16 i + 2 wave,
     // so col & 15 -- and with it the lane's source offset -- is the same for every piece of a wave.
-    constexpr bool GLDS = GDM_CONV_GLDS && WV == 8;
+    constexpr bool GLDS = WV == 8;
     constexpr int NPIECE = PANEL / 1024 / 8;                        // LDS-DMA instructions per wave and panel
     int glds_voff = 0;
     if (GLDS) {
@@ -281,7 +268,7 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void_ptr)(smem + buf * PANEL + (i * 8 + wave) * 1024), 16, glds_voff, src + i * 8192, 0, 0);
     };
 
-    f32x4 acc[NPH][NCB];
+    gdm_f32x4 acc[NPH][NCB];
 #pragma unroll
     for (int ph = 0; ph < NPH; ++ph)
 #pragma unroll
@@ -311,14 +298,14 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
         // units of (k-step S, UG 16-channel output blocks): 3 UG NPH MFMAs of 16 cycles on 2 UG B fragments; PF units' reads in flight
         constexpr int PF = GDM_CONV16_PF;
         constexpr int NU = NPR * NS;
-        u32x4 fh[PF + 1][UG], fl[PF + 1][UG];
+        gdm_u32x4 fh[PF + 1][UG], fl[PF + 1][UG];
         auto frag_load = [&](int un) {
             const int S = un / NPR, pr = un % NPR, slot = un % (PF + 1);
 #pragma unroll
             for (int j = 0; j < UG; ++j) {
                 const int col = (UG * pr + j) * 16 + l16;
-                fh[slot][j] = *reinterpret_cast<const u32x4*>(base + swz(col, 4 * S + kg));
-                fl[slot][j] = *reinterpret_cast<const u32x4*>(base + swz(col, 16 + 4 * S + kg));
+                fh[slot][j] = *reinterpret_cast<const gdm_u32x4*>(base + gdm_swz<ROWB>(col, 4 * S + kg));
+                fl[slot][j] = *reinterpret_cast<const gdm_u32x4*>(base + gdm_swz<ROWB>(col, 16 + 4 * S + kg));
             }
         };
 #pragma unroll
@@ -327,34 +314,19 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
         for (int u = 0; u < NU; ++u) {
             const int S = u / NPR, pr = u % NPR, slot = u % (PF + 1);
             if (u + PF < NU) frag_load(u + PF);
-#if GDM_CONV_MFMA_ORDER == 0
 #pragma unroll
             for (int ph = 0; ph < NPH; ++ph) {
-                const bf16x8 ah = __builtin_bit_cast(bf16x8, ahi[S][ph]);
-                const bf16x8 al = __builtin_bit_cast(bf16x8, alo[S][ph]);
+                const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, ahi[S][ph]);
+                const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, alo[S][ph]);
 #pragma unroll
                 for (int j = 0; j < UG; ++j) {
-                    f32x4 c = acc[ph][UG * pr + j];
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, fl[slot][j]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, __builtin_bit_cast(bf16x8, fh[slot][j]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, fh[slot][j]), c, 0, 0, 0);
+                    gdm_f32x4 c = acc[ph][UG * pr + j];
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(gdm_bf16x8, fl[slot][j]), c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, __builtin_bit_cast(gdm_bf16x8, fh[slot][j]), c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(gdm_bf16x8, fh[slot][j]), c, 0, 0, 0);
                     acc[ph][UG * pr + j] = c;
                 }
             }
-#else
-            // product-major: the unit's 2 NPH accumulators take hi.lo, then lo.hi, then hi.hi -- the same three terms in the same order per
-            // accumulator (bit-identical sums), but an MFMA never waits for its predecessor's result (2 NPH - 1 others in between)
-#pragma unroll
-            for (int prod = 0; prod < 3; ++prod)
-#pragma unroll
-                for (int ph = 0; ph < NPH; ++ph)
-#pragma unroll
-                    for (int j = 0; j < UG; ++j) {
-                        const bf16x8 av = __builtin_bit_cast(bf16x8, prod == 1 ? alo[S][ph] : ahi[S][ph]);
-                        const bf16x8 bv = __builtin_bit_cast(bf16x8, prod == 0 ? fl[slot][j] : fh[slot][j]);
-                        acc[ph][UG * pr + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[ph][UG * pr + j], 0, 0, 0);
-                    }
-#endif
             if (pr == NPR - 1 && S < NS - LATE) load_a(rnext, S);         // this k-step's registers are dead: next panel's data
             if (!GLDS && u == NU / 2 && more) {                     // the other buffer's readers finished at this panel's barrier
                 stage_store((it + 1) & 1, 0);
@@ -522,9 +494,32 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
     }
 }
 
-// (the v_mfma_f32_32x32x16_bf16 form of rounds 1-3, `conv3x3_bf16x3_kernel`, was removed in round 4: compiled, never launched)
-#define CONV_KERNEL conv_mfma16_kernel
-constexpr int CONV_THREADS = MF_THREADS, CONV_WPIX = MF_WPIX, CONV_SMEM = MF_SMEM;
+// What conv_mfma16_kernel takes, by name and in its order (host side only: conv_launch expands it into the kernel's positional parameters).
+struct ConvArgs {
+    const void *xpk = nullptr, *wpk = nullptr;
+    const float *scale = nullptr, *shift = nullptr, *res = nullptr;
+    int B = 0, Cin = 0, Cout = 0, H = 0, W = 0;
+    float* out = nullptr;
+    const int32_t *rowidx = nullptr, *tile_co0 = nullptr;
+    void* outpk = nullptr;
+    int stride = 1;
+    long wbstride = 0;
+    const int32_t* gidx = nullptr;
+    const float* gt = nullptr;
+    int gn = 0, gt_lds = 0;
+};
+
+// The one place conv_mfma16_kernel is launched from.  smem is what the SITE wants (it decides how many workgroups share a CU); what the
+// instance is allowed is set here, once, so an instance cannot be launched without it.
+template <int ACT, bool RES, int TAPS, bool PM, int NKS, int NCB, int WV, bool GADD>
+void conv_launch(dim3 grid, int smem, hipStream_t s, const ConvArgs& a)
+{
+    constexpr auto kernel = conv_mfma16_kernel<ACT, RES, TAPS, PM, NKS, NCB, WV, GADD>;
+    gdm_allow_lds<kernel>(GADD ? LDS_MAX : conv_lds_bytes(NCB));
+    hipLaunchKernelGGL(kernel, grid, dim3(WV * 64), smem, s, (const unsigned char*)a.xpk, (const unsigned char*)a.wpk, a.scale, a.shift, a.res,
+                       a.B, a.Cin, a.Cout, a.H, a.W, a.out, a.rowidx, a.tile_co0, (unsigned char*)a.outpk, a.stride, a.wbstride, a.gidx, a.gt,
+                       a.gn, a.gt_lds);
+}
 
 } // namespace
 
@@ -536,15 +531,13 @@ namespace {
 template <int CHAIN>
 __global__ __launch_bounds__(512) void mfma_probe_kernel(int iters, float* __restrict__ sink)
 {
-    typedef __attribute__((ext_vector_type(8))) __bf16 pb_bf16x8;
-    typedef __attribute__((ext_vector_type(4))) float pb_f32x4;
     const int lane = threadIdx.x & 63;
-    pb_f32x4 acc[8];
+    gdm_f32x4 acc[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] = pb_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 8; ++i) acc[i] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
     const unsigned seed = 0x3f803f80u + (unsigned)lane;             // bf16 pairs near 1.0
-    u32x4 av = {seed, seed ^ 1u, seed ^ 2u, seed ^ 3u}, bv = {seed ^ 4u, seed ^ 5u, seed ^ 6u, seed ^ 7u};
-    const pb_bf16x8 a = __builtin_bit_cast(pb_bf16x8, av), b = __builtin_bit_cast(pb_bf16x8, bv);
+    gdm_u32x4 av = {seed, seed ^ 1u, seed ^ 2u, seed ^ 3u}, bv = {seed ^ 4u, seed ^ 5u, seed ^ 6u, seed ^ 7u};
+    const gdm_bf16x8 a = __builtin_bit_cast(gdm_bf16x8, av), b = __builtin_bit_cast(gdm_bf16x8, bv);
     // CHAIN consecutive MFMAs into the same accumulator before moving to the next one (1: every MFMA independent of its predecessor;
     // 3: the hi.lo / lo.hi / hi.hi triple of a split-bf16 product issued back to back)
     for (int it = 0; it < iters; it += CHAIN) {
@@ -563,29 +556,27 @@ __global__ __launch_bounds__(512) void mfma_probe_kernel(int iters, float* __res
 template <int RPU>
 __global__ __launch_bounds__(512) void mfma_probe_lds_kernel(int iters, float* __restrict__ sink)
 {
-    typedef __attribute__((ext_vector_type(8))) __bf16 pb_bf16x8;
-    typedef __attribute__((ext_vector_type(4))) float pb_f32x4;
     extern __shared__ __attribute__((aligned(16))) unsigned char pl[];          // 64 KiB
     const int tid = threadIdx.x, lane = tid & 63;
-    for (int i = tid; i < 4096; i += 512) reinterpret_cast<u32x4*>(pl)[i] = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u + (unsigned)i};
+    for (int i = tid; i < 4096; i += 512) reinterpret_cast<gdm_u32x4*>(pl)[i] = gdm_u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u + (unsigned)i};
     __syncthreads();
-    pb_f32x4 acc[4];
+    gdm_f32x4 acc[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = pb_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 4; ++i) acc[i] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
     const unsigned seed = 0x3f803f80u + (unsigned)lane;
-    u32x4 a0 = {seed, seed ^ 1u, seed ^ 2u, seed ^ 3u}, a1 = {seed ^ 4u, seed ^ 5u, seed ^ 6u, seed ^ 7u};
-    u32x4 f[4] = {a0, a1, a0, a1};
+    gdm_u32x4 a0 = {seed, seed ^ 1u, seed ^ 2u, seed ^ 3u}, a1 = {seed ^ 4u, seed ^ 5u, seed ^ 6u, seed ^ 7u};
+    gdm_u32x4 f[4] = {a0, a1, a0, a1};
     int off = lane * 16;
     for (int it = 0; it < iters; ++it) {
 #pragma unroll
-        for (int r = 0; r < RPU; ++r) f[r] = *reinterpret_cast<const u32x4*>(pl + ((off + r * 1024) & 0xffff));
+        for (int r = 0; r < RPU; ++r) f[r] = *reinterpret_cast<const gdm_u32x4*>(pl + ((off + r * 1024) & 0xffff));
         off += 4096;
 #pragma unroll
         for (int prod = 0; prod < 3; ++prod)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(pb_bf16x8, prod == 1 ? a1 : a0),
-                                                                 __builtin_bit_cast(pb_bf16x8, f[(i + prod) & 3]), acc[i], 0, 0, 0);
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gdm_bf16x8, prod == 1 ? a1 : a0),
+                                                                 __builtin_bit_cast(gdm_bf16x8, f[(i + prod) & 3]), acc[i], 0, 0, 0);
     }
     float t = 0.f;
 #pragma unroll
@@ -683,7 +674,42 @@ extern "C" int gdm_conv3x3_pack_act_hip(const float* x, int B, int Cin, int H, i
 // interior pixels are written) -- at least one of them.
 static int conv3x3_launch(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
                           int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream,
-                          const char* who);
+                          const char* who)
+{
+    GDM_CHECK_ARG(stride == 1 || stride == 2, "%s: stride=%d (1 or 2)", who, stride);
+    GDM_CHECK_ARG(xpk && wpk && (out || outpk), "%s: NULL pointer", who);
+    GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cout >= 1, "%s: Cin=%d Cout=%d (Cin a multiple of 128, or 64)", who, Cin, Cout);
+    GDM_CHECK_ARG(W % 32 == 0 && H >= 1 && (H * W) % MF_WPIX == 0,
+                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, MF_WPIX);
+    GDM_CHECK_ARG(act == 0 || act == 1, "%s: act=%d", who, act);
+    GDM_CHECK_ARG(!outpk || (Cout % 8 == 0 && ((long)B * H * W) % CV_PIX == 0),
+                  "%s: packed output needs Cout %% 8 == 0 and B*H*W %% 256 == 0 (got Cout=%d, B*H*W=%ld)", who, Cout, (long)B * H * W);
+    const long ptot = (long)B * H * W;
+    const dim3 grid(gdm_cdiv(ptot, CV_PIX), gdm_cdiv(Cout, CV_CO));
+    // 64-channel tiles where 128-channel ones leave the chip half empty (or pad a 64-channel layer with zero rows): twice the workgroups
+    const bool narrow = narrow_tiles(grid.x, Cout);
+    const dim3 grid4(grid.x, gdm_cdiv(Cout, 64));
+    // still fewer workgroups than CUs (128 -> 128 at 32 x 32, batch 16: 64 x 2): 128-pixel workgroups of four waves
+    const bool half = narrow && Cin != 64 && (long)grid4.x * grid4.y < 256 && ptot % (CV_PIX / 2) == 0;
+    const dim3 grid4h(gdm_cdiv(ptot, CV_PIX / 2), grid4.y);
+    hipStream_t s = (hipStream_t)stream;
+    ConvArgs a{xpk, wpk, scale, shift, res, B, Cin, Cout, H, W, out};
+    a.outpk = outpk; a.stride = stride;
+    gdm_dispatch_int<2>(act, [&](auto A) {
+        gdm_dispatch_bool(res != nullptr, [&](auto R) {
+            constexpr int ACT = decltype(A)::value;
+            constexpr bool RES = decltype(R)::value;
+            if (half) return conv_launch<ACT, RES, 9, false, 8, 4, MF_WAVES / 2, false>(grid4h, conv_lds_bytes(4), s, a);
+            gdm_dispatch_bool(Cin == 64, [&](auto K4) {         // one half-filled chunk: only its four non-zero k-steps are run
+                constexpr int NKS = decltype(K4)::value ? 4 : 8;
+                if (narrow) conv_launch<ACT, RES, 9, false, NKS, 4, MF_WAVES, false>(grid4, conv_lds_bytes(4), s, a);
+                else conv_launch<ACT, RES, 9, false, NKS, 8, MF_WAVES, false>(grid, conv_lds_bytes(8), s, a);
+            });
+        });
+    });
+    return gdm_launch_status(half ? "conv_mfma16_kernel (3x3, 64-channel tiles, 128 pixels)"
+                             : narrow ? "conv_mfma16_kernel (3x3, 64-channel tiles)" : "conv_mfma16_kernel (3x3)");
+}
 
 extern "C" int gdm_conv3x3_packed_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
                                       int B, int Cin, int Cout, int H, int W, int act, float* out, void* stream)
@@ -698,85 +724,6 @@ extern "C" int gdm_conv3x3_strided_hip(const void* xpk, const void* wpk, const f
     return conv3x3_launch(xpk, wpk, scale, shift, res, B, Cin, Cout, H, W, stride, act, out, outpk, stream, "gdm_conv3x3_strided_hip");
 }
 
-static int conv3x3_launch(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
-                          int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* outpk, void* stream,
-                          const char* who)
-{
-    GDM_CHECK_ARG(stride == 1 || stride == 2, "%s: stride=%d (1 or 2)", who, stride);
-    GDM_CHECK_ARG(xpk && wpk && (out || outpk), "%s: NULL pointer", who);
-    GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cout >= 1, "%s: Cin=%d Cout=%d (Cin a multiple of 128, or 64)", who, Cin, Cout);
-    GDM_CHECK_ARG(W % 32 == 0 && H >= 1 && (H * W) % CONV_WPIX == 0,
-                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, CONV_WPIX);
-    GDM_CHECK_ARG(act == 0 || act == 1, "%s: act=%d", who, act);
-    GDM_CHECK_ARG(!outpk || (Cout % 8 == 0 && ((long)B * H * W) % CV_PIX == 0),
-                  "%s: packed output needs Cout %% 8 == 0 and B*H*W %% 256 == 0 (got Cout=%d, B*H*W=%ld)", who, Cout, (long)B * H * W);
-    const long ptot = (long)B * H * W;
-    dim3 grid(gdm_cdiv(ptot, CV_PIX), gdm_cdiv(Cout, CV_CO));
-    hipStream_t s = (hipStream_t)stream;
-    constexpr int SMEM = CONV_SMEM;                                 // weight panels, or the waves' output tiles
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 9, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 9, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, true, 9, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, true, 9, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        attr = true;
-    }
-#define CV(A, R, NK) hipLaunchKernelGGL((CONV_KERNEL<A, R, 9, false, NK>), grid, dim3(CONV_THREADS), SMEM, s, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, res, B, Cin, Cout, H, W, out, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned char*)outpk, stride)
-    // 64-channel tiles where 128-channel ones leave the chip half empty (or pad a 64-channel layer with zero rows): twice the workgroups
-    if (narrow_tiles(grid.x, Cout)) {
-        constexpr int SMEM4 = 2 * 64 * ROWB > CV_PIX * 68 * 4 ? 2 * 64 * ROWB : CV_PIX * 68 * 4;
-        const dim3 grid4(grid.x, gdm_cdiv(Cout, 64));
-        static bool attr4 = false;
-#define CV4(A, R, NK) hipLaunchKernelGGL((CONV_KERNEL<A, R, 9, false, NK, 4>), grid4, dim3(CONV_THREADS), SMEM4, s, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, res, B, Cin, Cout, H, W, out, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned char*)outpk, stride)
-#define AT4(A, R, NK) (void)hipFuncSetAttribute((const void*)CONV_KERNEL<A, R, 9, false, NK, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM4)
-        if (!attr4) {
-            AT4(0, false, 4); AT4(1, false, 4); AT4(0, true, 4); AT4(1, true, 4);
-            AT4(0, false, 8); AT4(1, false, 8); AT4(0, true, 8); AT4(1, true, 8);
-            attr4 = true;
-        }
-        // still fewer workgroups than CUs (128 -> 128 at 32 x 32, batch 16: 64 x 2): 128-pixel workgroups of four waves
-        if (Cin != 64 && (long)grid4.x * grid4.y < 256 && ptot % (CV_PIX / 2) == 0) {
-            const dim3 grid4h(gdm_cdiv(ptot, CV_PIX / 2), grid4.y);
-            static bool attr4h = false;
-#define CV4H(A, R) hipLaunchKernelGGL((CONV_KERNEL<A, R, 9, false, 8, 4, MF_WAVES / 2>), grid4h, dim3(CONV_THREADS / 2), SMEM4, s, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, res, B, Cin, Cout, H, W, out, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned char*)outpk, stride)
-#define AT4H(A, R) (void)hipFuncSetAttribute((const void*)CONV_KERNEL<A, R, 9, false, 8, 4, MF_WAVES / 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM4)
-            if (!attr4h) {
-                AT4H(0, false); AT4H(1, false); AT4H(0, true); AT4H(1, true);
-                attr4h = true;
-            }
-            if (act == 0) { if (res) CV4H(0, true); else CV4H(0, false); }
-            else { if (res) CV4H(1, true); else CV4H(1, false); }
-#undef CV4H
-#undef AT4H
-            return gdm_launch_status("conv_mfma16_kernel (3x3, 64-channel tiles, 128 pixels)");
-        }
-        if (Cin == 64) {
-            if (act == 0) { if (res) CV4(0, true, 4); else CV4(0, false, 4); }
-            else { if (res) CV4(1, true, 4); else CV4(1, false, 4); }
-        } else {
-            if (act == 0) { if (res) CV4(0, true, 8); else CV4(0, false, 8); }
-            else { if (res) CV4(1, true, 8); else CV4(1, false, 8); }
-        }
-#undef CV4
-#undef AT4
-        return gdm_launch_status("conv_mfma16_kernel (3x3, 64-channel tiles)");
-    }
-    if (Cin == 64) {                                             // one half-filled chunk: only its four non-zero k-steps are run
-        if (act == 0) { if (res) CV(0, true, 4); else CV(0, false, 4); }
-        else { if (res) CV(1, true, 4); else CV(1, false, 4); }
-    } else {
-        if (act == 0) { if (res) CV(0, true, 8); else CV(0, false, 8); }
-        else { if (res) CV(1, true, 8); else CV(1, false, 8); }
-    }
-#undef CV
-    return gdm_launch_status("conv_mfma16_kernel (3x3)");
-}
-
 // Grouped, gathered GEMM on the same kernel: Y[r, 0:128] = Wpk[tile_co0[r / 256] + 0:128, :] . X[rowidx[r], :] for R rows (R % 256 == 0),
 // X packed by gdm_conv3x3_pack_act_hip(x, 1, Cin, 1, M), weights packed by gdm_conv1x1_pack_weight_hip(Cout_total, Cin).
 extern "C" int gdm_gemm_grouped_hip(const void* xpk, const void* wpk, const int32_t* rowidx, const int32_t* tile_co0, int R, int M,
@@ -785,31 +732,14 @@ extern "C" int gdm_gemm_grouped_hip(const void* xpk, const void* wpk, const int3
     GDM_CHECK_ARG(xpk && wpk && rowidx && tile_co0 && out, "gdm_gemm_grouped_hip: NULL pointer");
     GDM_CHECK_ARG(R >= 256 && R % 256 == 0 && M >= 1 && Cin >= 128 && Cin % 128 == 0 && Cout_total >= 128 && Cout_total % 128 == 0,
                   "gdm_gemm_grouped_hip: R=%d (multiple of 256) M=%d Cin=%d Cout_total=%d (multiples of 128)", R, M, Cin, Cout_total);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CV_PANEL);
-        attr = true;
-    }
     // the kernel sees B = R "pixels" of a 1 x 1 map for the row bookkeeping and H = 1, W = M for the packed source
-    hipLaunchKernelGGL((CONV_KERNEL<0, false, 1, true>), dim3(R / CV_PIX, 1), dim3(CONV_THREADS), 2 * CV_PANEL, (hipStream_t)stream,
-                       (const unsigned char*)xpk, (const unsigned char*)wpk, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                       R, Cin, Cout_total, 1, M, out, rowidx, tile_co0);
+    ConvArgs a{xpk, wpk, nullptr, nullptr, nullptr, R, Cin, Cout_total, 1, M, out, rowidx, tile_co0};
+    // 2 * CV_PANEL, below conv_lds_bytes(8): no packed output, so the waves' output tiles are never in LDS
+    conv_launch<0, false, 1, true, 8, 8, MF_WAVES, false>(dim3(R / CV_PIX, 1), 2 * CV_PANEL, (hipStream_t)stream, a);
     return gdm_launch_status("gemm_grouped_kernel");
 }
 
-// 1x1 convolution / GEMM on the same kernel (one tap): out = act(scale * (W x) + shift), x packed by gdm_conv3x3_pack_act_hip.
-// pixel_major != 0 writes out[B*H*W, Cout] (row per pixel) instead of NCHW.
-static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, const float* shift,
-                          int B, int Cin, int Cout, int H, int W, int stride, int act, int pixel_major, float* out, void* stream,
-                          const char* who);
-
-extern "C" int gdm_conv1x1_packed_hip(const void* xpk, const void* wpk, const float* scale, const float* shift,
-                                      int B, int Cin, int Cout, int H, int W, int act, int pixel_major, float* out, void* stream)
-{
-    return conv1x1_launch(xpk, wpk, scale, shift, B, Cin, Cout, H, W, 1, act, pixel_major, out, stream, "gdm_conv1x1_packed_hip");
-}
-
-// the same GEMM with one weight set PER IMAGE (include/gdm.h: the split-K parts of the weight-gradient GEMM): H*W % 256 == 0
+// the 1x1 GEMM below with one weight set PER IMAGE (include/gdm.h: the split-K parts of the weight-gradient GEMM): H*W % 256 == 0
 extern "C" int gdm_conv1x1_packed_wb_hip(const void* xpk, const void* wpk, long w_bstride, int B, int Cin, int Cout, int H, int W, float* out,
                                          void* stream)
 {
@@ -819,25 +749,15 @@ extern "C" int gdm_conv1x1_packed_wb_hip(const void* xpk, const void* wpk, long 
                   W, H * W, CV_PIX);
     GDM_CHECK_ARG(w_bstride >= 0 && w_bstride % 16 == 0, "gdm_conv1x1_packed_wb_hip: w_bstride=%ld", w_bstride);
     const long ptot = (long)B * H * W;
-    dim3 grid(gdm_cdiv(ptot, CV_PIX), gdm_cdiv(Cout, CV_CO));
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CV_PANEL);
-        attr = true;
-    }
-    hipLaunchKernelGGL((CONV_KERNEL<0, false, 1, false>), grid, dim3(CONV_THREADS), 2 * CV_PANEL, (hipStream_t)stream, (const unsigned char*)xpk,
-                       (const unsigned char*)wpk, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, B, Cin, Cout, H, W, out,
-                       (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned char*)nullptr, 1, w_bstride);
+    const dim3 grid(gdm_cdiv(ptot, CV_PIX), gdm_cdiv(Cout, CV_CO));
+    ConvArgs a{xpk, wpk, nullptr, nullptr, nullptr, B, Cin, Cout, H, W, out};
+    a.wbstride = w_bstride;
+    conv_launch<0, false, 1, false, 8, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, (hipStream_t)stream, a);     // no packed output: panels only
     return gdm_launch_status("conv1x1_bf16x3_kernel (per-image weights)");
 }
 
-// H, W = OUTPUT size; xpk = the (H stride) x (W stride) input (the downsample branch of a strided residual block reads every other pixel)
-extern "C" int gdm_conv1x1_strided_hip(const void* xpk, const void* wpk, const float* scale, const float* shift,
-                                       int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* stream)
-{
-    return conv1x1_launch(xpk, wpk, scale, shift, B, Cin, Cout, H, W, stride, act, 0, out, stream, "gdm_conv1x1_strided_hip");
-}
-
+// 1x1 convolution / GEMM on the same kernel (one tap): out = act(scale * (W x) + shift), x packed by gdm_conv3x3_pack_act_hip.
+// pixel_major != 0 writes out[B*H*W, Cout] (row per pixel) instead of NCHW.
 static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, const float* shift,
                           int B, int Cin, int Cout, int H, int W, int stride, int act, int pixel_major, float* out, void* stream,
                           const char* who)
@@ -846,29 +766,24 @@ static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, 
     GDM_CHECK_ARG(xpk && wpk && out, "%s: NULL pointer", who);
     GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cout >= 1, "%s: Cin=%d Cout=%d (Cin a multiple of 128, or 64)", who, Cin, Cout);
     GDM_CHECK_ARG(Cin != 64 || !pixel_major, "%s: Cin=64 is built for the NCHW output only", who);
-    GDM_CHECK_ARG(W % 32 == 0 && H >= 1 && (H * W) % CONV_WPIX == 0,
-                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, CONV_WPIX);
+    GDM_CHECK_ARG(W % 32 == 0 && H >= 1 && (H * W) % MF_WPIX == 0,
+                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, MF_WPIX);
     GDM_CHECK_ARG(act == 0 || act == 1, "%s: act=%d", who, act);
     const long ptot = (long)B * H * W;
     const unsigned ptiles = gdm_cdiv(ptot, CV_PIX);
+    hipStream_t s = (hipStream_t)stream;
+    ConvArgs a{xpk, wpk, scale, shift, nullptr, B, Cin, Cout, H, W, out};
+    a.stride = stride;
     // 144-channel tiles (nine 16-channel blocks) where they divide Cout and fill the chip's rounds better than 128-channel ones: the
     // tap GEMMs of PSPUpsample have 9 * Cout' outputs -- 2304 at 64 pixel tiles = 1152 tiles of 128 (4.5 rounds of 256 CUs, paid as
     // 5) or 1024 tiles of 144 (4 rounds); 576 at 256 pixel tiles = 1280 tiles of 128, the last of every five half empty, or 1024 of 144
-    if (Cin != 64 && !pixel_major && stride == 1 && Cout % 144 == 0 && GDM_CONV_GLDS) {
+    if (Cin != 64 && !pixel_major && stride == 1 && Cout % 144 == 0) {
         const long r128 = gdm_cdiv((long)ptiles * gdm_cdiv(Cout, 128), 256) * 128, r144 = gdm_cdiv((long)ptiles * (Cout / 144), 256) * 144;
         if (r144 < r128) {
-            constexpr int PANEL9 = 9 * 16 * ROWB, TILE9 = CV_PIX * (9 * 16 + 4) * 4;
-            constexpr int SMEM9 = 2 * PANEL9 > TILE9 ? 2 * PANEL9 : TILE9;
-            static bool attr9 = false;
-            if (!attr9) {
-                (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false, 8, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM9);
-                (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, false, 8, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM9);
-                attr9 = true;
-            }
             const dim3 grid9(ptiles, Cout / 144);
-#define C19(A) hipLaunchKernelGGL((CONV_KERNEL<A, false, 1, false, 8, 9>), grid9, dim3(CONV_THREADS), SMEM9, (hipStream_t)stream, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, (const float*)nullptr, B, Cin, Cout, H, W, out, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned char*)nullptr, stride)
-            if (act == 0) C19(0); else C19(1);
-#undef C19
+            gdm_dispatch_int<2>(act, [&](auto A) {
+                conv_launch<decltype(A)::value, false, 1, false, 8, 9, MF_WAVES, false>(grid9, conv_lds_bytes(9), s, a);
+            });
             return gdm_launch_status("conv1x1_bf16x3_kernel (144-channel tiles)");
         }
     }
@@ -877,42 +792,33 @@ static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, 
     // pixel tiles are the fast grid axis: workgroups that share a pixel tile land on one XCD.  (Channel tiles fastest was measured on the
     // 1024 -> 2304 tap GEMM in round 3: same time, 903 MB instead of 573 MB of fabric traffic -- each XCD then streams every weight panel.)
     const dim3 grid(ptiles, ctiles);
-    hipStream_t s = (hipStream_t)stream;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CV_PANEL);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CV_PANEL);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CV_PANEL);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CV_PANEL);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CV_PANEL);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CV_PANEL);
-        attr = true;
-    }
-    if (Cin == 64) {                                            // one half-filled chunk: only its four non-zero k-steps are run
-#define C1TAIL , (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned char*)nullptr, stride
-#define C1H(A) hipLaunchKernelGGL((CONV_KERNEL<A, false, 1, false, 4>), grid, dim3(CONV_THREADS), 2 * CV_PANEL, s, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, (const float*)nullptr, B, Cin, Cout, H, W, out C1TAIL)
-        if (act == 0) C1H(0); else C1H(1);
-#undef C1H
-        return gdm_launch_status("conv1x1_bf16x3_kernel");
-    }
-    if (narrow) {
-        const dim3 grid4 = grid;
-        static bool attr4 = false;
-        if (!attr4) {
-            (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * ROWB);
-            (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, false, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * ROWB);
-            attr4 = true;
-        }
-#define C14(A) hipLaunchKernelGGL((CONV_KERNEL<A, false, 1, false, 8, 4>), grid4, dim3(CONV_THREADS), 2 * 64 * ROWB, s, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, (const float*)nullptr, B, Cin, Cout, H, W, out C1TAIL)
-        if (act == 0) C14(0); else C14(1);
-#undef C14
-        return gdm_launch_status("conv1x1_bf16x3_kernel (64-channel tiles)");
-    }
-#define C1(A, P) hipLaunchKernelGGL((CONV_KERNEL<A, false, 1, P>), grid, dim3(CONV_THREADS), 2 * CV_PANEL, s, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, (const float*)nullptr, B, Cin, Cout, H, W, out C1TAIL)
-    if (act == 0) { if (pixel_major) C1(0, true); else C1(0, false); }
-    else { if (pixel_major) C1(1, true); else C1(1, false); }
-#undef C1
-    return gdm_launch_status("conv1x1_bf16x3_kernel");
+    // No packed output on this path, so the waves' output tiles are never in LDS: every launch below passes its two weight panels only,
+    // which is below conv_lds_bytes(NCB) -- at 64-channel tiles 64 KiB, so that two workgroups share a CU.
+    gdm_dispatch_int<2>(act, [&](auto A) {
+        constexpr int ACT = decltype(A)::value;
+        if (Cin == 64)                                              // one half-filled chunk: only its four non-zero k-steps are run
+            conv_launch<ACT, false, 1, false, 4, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, s, a);
+        else if (narrow)
+            conv_launch<ACT, false, 1, false, 8, 4, MF_WAVES, false>(grid, 2 * 64 * ROWB, s, a);
+        else
+            gdm_dispatch_bool(pixel_major != 0, [&](auto P) {
+                conv_launch<ACT, false, 1, decltype(P)::value, 8, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, s, a);
+            });
+    });
+    return gdm_launch_status(narrow ? "conv1x1_bf16x3_kernel (64-channel tiles)" : "conv1x1_bf16x3_kernel");
+}
+
+extern "C" int gdm_conv1x1_packed_hip(const void* xpk, const void* wpk, const float* scale, const float* shift,
+                                      int B, int Cin, int Cout, int H, int W, int act, int pixel_major, float* out, void* stream)
+{
+    return conv1x1_launch(xpk, wpk, scale, shift, B, Cin, Cout, H, W, 1, act, pixel_major, out, stream, "gdm_conv1x1_packed_hip");
+}
+
+// H, W = OUTPUT size; xpk = the (H stride) x (W stride) input (the downsample branch of a strided residual block reads every other pixel)
+extern "C" int gdm_conv1x1_strided_hip(const void* xpk, const void* wpk, const float* scale, const float* shift,
+                                       int B, int Cin, int Cout, int H, int W, int stride, int act, float* out, void* stream)
+{
+    return conv1x1_launch(xpk, wpk, scale, shift, B, Cin, Cout, H, W, stride, act, 0, out, stream, "gdm_conv1x1_strided_hip");
 }
 
 // The point-to-pixel fusion as ONE launch: the 1x1 GEMM above (stride 1, NCHW) whose epilogue adds the gathered point term and applies
@@ -926,8 +832,8 @@ extern "C" int gdm_conv1x1_gather_add_hip(const void* xpk, const void* wpk, cons
     const char* who = "gdm_conv1x1_gather_add_hip";
     GDM_CHECK_ARG(xpk && wpk && gidx && gt && scale && shift && (out || outpk), "%s: NULL pointer", who);
     GDM_CHECK_ARG(B >= 1 && cin_ok(Cin) && Cin != 64 && Cout >= 1, "%s: Cin=%d Cout=%d (Cin a multiple of 128)", who, Cin, Cout);
-    GDM_CHECK_ARG(W >= 32 && W % 32 == 0 && H >= 1 && (H * W) % CONV_WPIX == 0,
-                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, CONV_WPIX);
+    GDM_CHECK_ARG(W >= 32 && W % 32 == 0 && H >= 1 && (H * W) % MF_WPIX == 0,
+                  "%s: W=%d must be a multiple of 32 and H*W=%d of %d", who, W, H * W, MF_WPIX);
     GDM_CHECK_ARG(gn >= 1, "%s: gn=%d (the gathered term needs at least one column)", who, gn);
     GDM_CHECK_ARG(act == 0 || act == 1, "%s: act=%d (none or ReLU)", who, act);
     GDM_CHECK_ARG(!outpk || (Cout % 8 == 0 && ((long)B * H * W) % CV_PIX == 0),
@@ -942,30 +848,21 @@ extern "C" int gdm_conv1x1_gather_add_hip(const void* xpk, const void* wpk, cons
     const unsigned ptiles = gdm_cdiv(ptot, CV_PIX);
     const bool narrow = narrow_tiles(ptiles, Cout);                 // the tile width conv1x1_launch takes for this shape
     const dim3 grid(ptiles, gdm_cdiv(Cout, narrow ? 64 : CV_CO));
-    hipStream_t s = (hipStream_t)stream;
     // weight panels, or (packed output) the waves' output tiles where those are larger
-    constexpr int SMEM8 = CONV_SMEM;
-    constexpr int SMEM4 = 2 * 64 * ROWB > CV_PIX * 68 * 4 ? 2 * 64 * ROWB : CV_PIX * 68 * 4;
+    const int tiles = conv_lds_bytes(narrow ? 4 : 8);
     // behind them the workgroup's rows of gt, gn + 1 floats apart (conflict-free across the 16 channels of a fragment), where a workgroup
     // lies inside one image and the rows fit the CU's 160 KiB; 64-channel tiles stay at two workgroups per CU unless the grid has no
     // second workgroup for a CU anyway.  Otherwise the lanes gather from global memory.
-    constexpr int LDS_MAX = 160 * 1024;
     const long trows = (long)(narrow ? 64 : CV_CO) * (gn + 1) * 4;
-    const long smem = (narrow ? SMEM4 : SMEM8) + trows;
+    const long smem = tiles + trows;
     const bool stage_t = (H * W) % CV_PIX == 0 && smem <= (narrow && (long)grid.x * grid.y > 256 ? LDS_MAX / 2 : LDS_MAX);
-    const int gt_lds = stage_t ? (narrow ? SMEM4 : SMEM8) : 0;
-    const int SM = stage_t ? (int)smem : (narrow ? SMEM4 : SMEM8);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false, 8, 8, MF_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, false, 8, 8, MF_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<0, false, 1, false, 8, 4, MF_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)CONV_KERNEL<1, false, 1, false, 8, 4, MF_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-        attr = true;
-    }
-#define C1G(A, N) hipLaunchKernelGGL((CONV_KERNEL<A, false, 1, false, 8, N, MF_WAVES, true>), grid, dim3(CONV_THREADS), SM, s, (const unsigned char*)xpk, (const unsigned char*)wpk, scale, shift, (const float*)nullptr, B, Cin, Cout, H, W, out, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned char*)outpk, 1, 0L, gidx, gt, gn, gt_lds)
-    if (narrow) { if (act == 0) C1G(0, 4); else C1G(1, 4); }
-    else { if (act == 0) C1G(0, 8); else C1G(1, 8); }
-#undef C1G
+    ConvArgs a{xpk, wpk, scale, shift, nullptr, B, Cin, Cout, H, W, out};
+    a.outpk = outpk; a.gidx = gidx; a.gt = gt; a.gn = gn; a.gt_lds = stage_t ? tiles : 0;
+    const int SM = stage_t ? (int)smem : tiles;
+    gdm_dispatch_int<2>(act, [&](auto A) {
+        gdm_dispatch_bool(narrow, [&](auto N4) {
+            conv_launch<decltype(A)::value, false, 1, false, 8, decltype(N4)::value ? 4 : 8, MF_WAVES, true>(grid, SM, (hipStream_t)stream, a);
+        });
+    });
     return gdm_launch_status(narrow ? "conv1x1_gather_add_kernel (64-channel tiles)" : "conv1x1_gather_add_kernel");
 }

@@ -166,7 +166,6 @@ __global__ __launch_bounds__(256) void edge_feature_bwd_kernel(const float* __re
 // per row behind a bound on the row's K-th key, the 16 lists are merged by K rounds of a 16-lane arg-min, the S merged lists of a row
 // are merged through LDS, and a row is exact iff no lane's 8th entry is at least as good as the row's final K-th.  Otherwise the
 // workgroup is flagged and a second kernel sweeps it again with full-length lists (rare on unordered data).
-typedef float fk_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int FK_ROWS = 32;                 // rows per workgroup: two row groups
 constexpr int FK_SMAX = 4;                  // column splits per workgroup: 1, 2 or 4 (the launcher picks by the number of workgroups)
 constexpr int FK_COLS = 64;
@@ -240,7 +239,7 @@ __device__ __forceinline__ float fk_row_max(float t)
     return fmaxf(t, __int_as_float(fk_dpp<0x140>(__float_as_int(t))));
 }
 
-__device__ __forceinline__ float fk_pick(const fk_f32x4& v, int i) { return i == 0 ? v[0] : (i == 1 ? v[1] : (i == 2 ? v[2] : v[3])); }
+__device__ __forceinline__ float fk_pick(const gdm_f32x4& v, int i) { return i == 0 ? v[0] : (i == 1 ? v[1] : (i == 2 ? v[2] : v[3])); }
 
 // One sweep over all columns for accumulator rows i0 .. i0 + NR - 1 of every wave, with private lists of KP.  Writes the rows'
 // results and returns the mask (bit i) of the accumulator rows of this lane that may be inexact (always 0 unless may_fail).
@@ -269,7 +268,7 @@ __device__ __forceinline__ unsigned fk_sweep(const float* __restrict__ xb, const
             const unsigned cc = (unsigned)min(c, n - 4);
 #pragma unroll
             for (int u = 0; u < FK_PB / 4; ++u) {
-                const fk_f32x4 v = *reinterpret_cast<const fk_f32x4*>(xb + ((unsigned)(min(q * FK_CK + bq + 8 * u, C - 1) * n) + cc));
+                const gdm_f32x4 v = *reinterpret_cast<const gdm_f32x4*>(xb + ((unsigned)(min(q * FK_CK + bq + 8 * u, C - 1) * n) + cc));
                 pb[4 * u] = v[0], pb[4 * u + 1] = v[1], pb[4 * u + 2] = v[2], pb[4 * u + 3] = v[3];
             }
         } else {
@@ -311,7 +310,7 @@ __device__ __forceinline__ unsigned fk_sweep(const float* __restrict__ xb, const
     }
     // staging roles within the 128 threads of a split.  Scalar: column t7 & 63, channels (t7 >> 6) + 2 u.  16-byte (n % 4 == 0, aligned
     // base): column quad t7 & 15, channels (t7 >> 4) + 8 u.  Column 16 j + lr of the tile goes to position 4 lr + j of its LDS row.
-    fk_f32x4 acc[4];
+    gdm_f32x4 acc[4];
     float xc[4];
     for (int it = 0; it < total; ++it) {
         const int itile = it / nchunk, q = it - itile * nchunk;
@@ -345,14 +344,14 @@ __device__ __forceinline__ unsigned fk_sweep(const float* __restrict__ xb, const
         if (q == 0) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                acc[j] = fk_f32x4{0.f, 0.f, 0.f, 0.f};
+                acc[j] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
                 xc[j] = xxb[min(tile * FK_COLS + 16 * j + lr, n - 1)];      // (columns past n get an infinite key below)
             }
         }
         const int steps = min(FK_CK, Cpad - q * FK_CK) >> 2;
         const float* ap = As + (q * FK_CK + lq) * FK_LDA + rg * 16 + lr;        // A[row lr][k lq], B[k lq][col lr]
         const float* bp = Bs + lq * FK_LDB + 4 * lr;        // the lane's four columns 16 j + lr are adjacent in LDS: one 16-byte read
-        auto mfma_step = [&](float a, const fk_f32x4& b) {
+        auto mfma_step = [&](float a, const gdm_f32x4& b) {
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[0], acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[1], acc[1], 0, 0, 0);
             acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[2], acc[2], 0, 0, 0);
@@ -360,18 +359,18 @@ __device__ __forceinline__ unsigned fk_sweep(const float* __restrict__ xb, const
         };
         if (steps == FK_CK / 4) {                            // a whole chunk (uniform): fixed trip count, the next step's operands are
             float a = ap[0];                                 // read from LDS before this step's MFMAs are issued
-            fk_f32x4 b = *reinterpret_cast<const fk_f32x4*>(bp);
+            gdm_f32x4 b = *reinterpret_cast<const gdm_f32x4*>(bp);
 #pragma unroll
             for (int s = 0; s < FK_CK / 4; ++s) {
                 const int sn = s + 1 < FK_CK / 4 ? s + 1 : s;
                 const float an = ap[4 * sn * FK_LDA];
-                const fk_f32x4 bn = *reinterpret_cast<const fk_f32x4*>(bp + 4 * sn * FK_LDB);
+                const gdm_f32x4 bn = *reinterpret_cast<const gdm_f32x4*>(bp + 4 * sn * FK_LDB);
                 mfma_step(a, b);
                 a = an;
                 b = bn;
             }
         } else {
-            for (int s = 0; s < steps; ++s) mfma_step(ap[4 * s * FK_LDA], *reinterpret_cast<const fk_f32x4*>(bp + 4 * s * FK_LDB));
+            for (int s = 0; s < steps; ++s) mfma_step(ap[4 * s * FK_LDA], *reinterpret_cast<const gdm_f32x4*>(bp + 4 * s * FK_LDB));
         }
         if (q == nchunk - 1) {
             // C/D layout: acc[j][i] = row 4 lq + i, column 16 j + lr of the tile
@@ -624,9 +623,9 @@ __global__ __launch_bounds__(256) void edge_block2_kernel(const float* __restric
                 h[4 * m + 2] = ev ? eb_lrelu(sc1[4 * m + 2] * (pv.z + qv.z) + sh1[4 * m + 2], slope) : 0.f;
                 h[4 * m + 3] = ev ? eb_lrelu(sc1[4 * m + 3] * (pv.w + qv.w) + sh1[4 * m + 3], slope) : 0.f;
             }
-            fk_f32x4 acc[4];
+            gdm_f32x4 acc[4];
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) acc[jj] = fk_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int jj = 0; jj < 4; ++jj) acc[jj] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 16; ++s)
 #pragma unroll
@@ -820,12 +819,12 @@ __global__ __launch_bounds__(256) void edge_train2_kernel(const float* __restric
     }
     float* ys = tiles + wave * (2 * 16 * ET_LD);                            // this wave's y1 tile, then its dy2 (later dy1) tile
     float* ds = ys + 16 * ET_LD;
-    fk_f32x4 dwacc[MODE == ET_MID ? 4 : 1][MODE == ET_MID ? 4 : 1];
+    gdm_f32x4 dwacc[MODE == ET_MID ? 4 : 1][MODE == ET_MID ? 4 : 1];
     if (MODE == ET_MID) {
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int bb = 0; bb < 4; ++bb) dwacc[a][bb] = fk_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int bb = 0; bb < 4; ++bb) dwacc[a][bb] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
     }
     double d0[4] = {0.0, 0.0, 0.0, 0.0}, d1[4] = {0.0, 0.0, 0.0, 0.0};
     const float* pqb = pq + (long)b * n * 128;
@@ -869,9 +868,9 @@ __global__ __launch_bounds__(256) void edge_train2_kernel(const float* __restric
                 h[4 * m + 3] = ev ? eb_lrelu(sc1[4 * m + 3] * y3 + sh1[4 * m + 3], slope) : 0.f;
                 if (BWD) *reinterpret_cast<float4*>(ys + lr * ET_LD + 16 * lq + 4 * m) = make_float4(y0, y1, y2, y3);
             }
-            fk_f32x4 acc[4];
+            gdm_f32x4 acc[4];
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) acc[jj] = fk_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int jj = 0; jj < 4; ++jj) acc[jj] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 16; ++s)
 #pragma unroll
@@ -957,9 +956,9 @@ __global__ __launch_bounds__(256) void edge_train2_kernel(const float* __restric
                                 dwacc[a][bb] = __builtin_amdgcn_mfma_f32_16x16x4f32(dy2[a][r], hc[bb], dwacc[a][bb], 0, 0, 0);
                     }
                 }
-                fk_f32x4 dh[4];
+                gdm_f32x4 dh[4];
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) dh[jj] = fk_f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int jj = 0; jj < 4; ++jj) dh[jj] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int s = 0; s < 16; ++s)
 #pragma unroll

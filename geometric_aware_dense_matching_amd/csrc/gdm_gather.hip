@@ -506,12 +506,8 @@ extern "C" int gdm_gather_max_hip(const float* feat, const int32_t* idx, int B, 
         return gdm_launch_status("gather_max_flat_kernel");
     }
     if (rowlds && n >= 1024 && n <= 16384 && (long)m * K >= 2048 && C <= 65535) {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)gather_max_rowlds_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-            (void)hipFuncSetAttribute((const void*)gather_max_rowlds_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-            attr = true;
-        }
+        gdm_allow_lds<gather_max_rowlds_kernel<16>>(65536);
+        gdm_allow_lds<gather_max_rowlds_kernel<32>>(65536);
         dim3 g2(C, B);
         const size_t lds = (size_t)((n + 3) & ~3) * 4;
         if (K <= 16)

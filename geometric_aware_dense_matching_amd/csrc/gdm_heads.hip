@@ -14,9 +14,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int HD_C = 128;                 // channels of every hidden layer
 constexpr int HD_P = 64;                  // points per workgroup
@@ -24,8 +21,7 @@ constexpr int HD_ROWB = 512;              // operand row: 128 bf16 hi | 128 bf16
 constexpr int HD_BUF = HD_P * HD_ROWB;    // 32 KiB
 constexpr int HD_MAXL = 12;
 
-// 16-byte chunk `ch` (0-15 hi, 16-31 lo) of row r, XOR-swizzled: 16 consecutive rows' same chunk land in 16 different bank groups
-__device__ __forceinline__ int hd_off(int r, int ch) { return r * HD_ROWB + (((ch & 16) | ((ch ^ r) & 15)) << 4); }
+// (rows in LDS are XOR-swizzled by gdm_swz<HD_ROWB>: 16 consecutive rows' same chunk land in 16 different bank groups)
 
 struct HeadArgs {
     const float* a;                       // f32[B, Ca, N]  first Ca input channels
@@ -77,12 +73,12 @@ __global__ __launch_bounds__(256, 2) void point_heads_kernel(HeadArgs A)
         unsigned hi[4], lo[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) gdm_split2(x0_at(grp * 8 + 2 * j, p), x0_at(grp * 8 + 2 * j + 1, p), hi[j], lo[j]);
-        *reinterpret_cast<u32x4*>(rows + hd_off(p, grp)) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-        *reinterpret_cast<u32x4*>(rows + hd_off(p, 16 + grp)) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        *reinterpret_cast<gdm_u32x4*>(rows + gdm_swz<HD_ROWB>(p, grp)) = gdm_u32x4{hi[0], hi[1], hi[2], hi[3]};
+        *reinterpret_cast<gdm_u32x4*>(rows + gdm_swz<HD_ROWB>(p, 16 + grp)) = gdm_u32x4{lo[0], lo[1], lo[2], lo[3]};
     }
 
     // ---- a layer: the wave owns output channels [32 wave, 32 wave + 32) (two 16-row blocks) x the 64 points (four 16-column blocks) ----
-    u32x4 wh[2][4], wl[2][4];                                     // A fragments: lane (row l16, k-group kg), k-step S = channels 32 S + 8 kg ..
+    gdm_u32x4 wh[2][4], wl[2][4];                                     // A fragments: lane (row l16, k-group kg), k-step S = channels 32 S + 8 kg ..
     auto weights_load = [&](const unsigned char* w, int nblk) {
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
@@ -90,28 +86,28 @@ __global__ __launch_bounds__(256, 2) void point_heads_kernel(HeadArgs A)
             const unsigned char* r = w + (long)(32 * wave + 16 * cb + l16) * HD_ROWB;
 #pragma unroll
             for (int S = 0; S < 4; ++S) {
-                wh[cb][S] = *reinterpret_cast<const u32x4*>(r + (4 * S + kg) * 16);
-                wl[cb][S] = *reinterpret_cast<const u32x4*>(r + 256 + (4 * S + kg) * 16);
+                wh[cb][S] = *reinterpret_cast<const gdm_u32x4*>(r + (4 * S + kg) * 16);
+                wl[cb][S] = *reinterpret_cast<const gdm_u32x4*>(r + 256 + (4 * S + kg) * 16);
             }
         }
     };
-    f32x4 acc[2][4];
+    gdm_f32x4 acc[2][4];
     auto mma = [&](const unsigned char* src, int nblk) {
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-            for (int pb = 0; pb < 4; ++pb) acc[cb][pb] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int pb = 0; pb < 4; ++pb) acc[cb][pb] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int S = 0; S < 4; ++S)
 #pragma unroll
             for (int pb = 0; pb < 4; ++pb) {
-                const bf16x8 xh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(src + hd_off(16 * pb + l16, 4 * S + kg)));
-                const bf16x8 xl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(src + hd_off(16 * pb + l16, 16 + 4 * S + kg)));
+                const gdm_bf16x8 xh = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(src + gdm_swz<HD_ROWB>(16 * pb + l16, 4 * S + kg)));
+                const gdm_bf16x8 xl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(src + gdm_swz<HD_ROWB>(16 * pb + l16, 16 + 4 * S + kg)));
 #pragma unroll
                 for (int cb = 0; cb < 2; ++cb) {
                     if (cb >= nblk) break;
-                    const bf16x8 ah = __builtin_bit_cast(bf16x8, wh[cb][S]);
-                    const bf16x8 al = __builtin_bit_cast(bf16x8, wl[cb][S]);
+                    const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, wh[cb][S]);
+                    const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, wl[cb][S]);
                     acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl, acc[cb][pb], 0, 0, 0);
                     acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, acc[cb][pb], 0, 0, 0);
                     acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, acc[cb][pb], 0, 0, 0);
@@ -164,8 +160,8 @@ __global__ __launch_bounds__(256, 2) void point_heads_kernel(HeadArgs A)
                 gdm_split2(v[2], v[3], h1, l1);
                 // channels c0 .. c0+3: chunk c0 / 8, bytes 8 (kg & 1) .. of it
                 const int ch = (32 * wave + 16 * cb) / 8 + (kg >> 1);
-                *reinterpret_cast<uint2*>(dst + hd_off(p, ch) + 8 * (kg & 1)) = make_uint2(h0, h1);
-                *reinterpret_cast<uint2*>(dst + hd_off(p, 16 + ch) + 8 * (kg & 1)) = make_uint2(l0, l1);
+                *reinterpret_cast<uint2*>(dst + gdm_swz<HD_ROWB>(p, ch) + 8 * (kg & 1)) = make_uint2(h0, h1);
+                *reinterpret_cast<uint2*>(dst + gdm_swz<HD_ROWB>(p, 16 + ch) + 8 * (kg & 1)) = make_uint2(l0, l1);
             }
         }
     }
@@ -216,11 +212,7 @@ extern "C" int gdm_point_heads2_hip(const float* a, const float* b, int Ca, cons
         GDM_CHECK_ARG(l >= nlayer || (w[l] && act[l] >= 0 && act[l] <= 1), "gdm_point_heads2_hip: layer %d: NULL weights or act=%d", l, l < nlayer ? act[l] : 0);
     }
     A.w_last = (const unsigned char*)w_last; A.shift_last = shift_last; A.c_last = c_last; A.out_feat = out_feat; A.out_last = out_last;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)point_heads_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HD_BUF);
-        attr = true;
-    }
+    gdm_allow_lds<point_heads_kernel>(2 * HD_BUF);
     hipLaunchKernelGGL(point_heads_kernel, dim3(gdm_cdiv(N, HD_P), B), dim3(256), 2 * HD_BUF, (hipStream_t)stream, A);
     return gdm_launch_status("point_heads_kernel");
 }

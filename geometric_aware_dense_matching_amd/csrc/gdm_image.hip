@@ -1129,9 +1129,9 @@ extern "C" int gdm_affine_act_maxk_hip(const float* x, const float* scale, const
     GDM_CHECK_ARG(((uintptr_t)x & 15) == 0, "gdm_affine_act_maxk_hip: x must be 16-byte aligned");
     dim3 grid(gdm_cdiv(n, 256), (unsigned)planes);
     hipStream_t s = (hipStream_t)stream;
-    if (act == 0) hipLaunchKernelGGL(affine_act_maxk_kernel<0>, grid, dim3(256), 0, s, x, scale, shift, C, n, K / 4, slope, out);
-    else if (act == 1) hipLaunchKernelGGL(affine_act_maxk_kernel<1>, grid, dim3(256), 0, s, x, scale, shift, C, n, K / 4, slope, out);
-    else hipLaunchKernelGGL(affine_act_maxk_kernel<2>, grid, dim3(256), 0, s, x, scale, shift, C, n, K / 4, slope, out);
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        hipLaunchKernelGGL(affine_act_maxk_kernel<decltype(A)::value>, grid, dim3(256), 0, s, x, scale, shift, C, n, K / 4, slope, out);
+    });
     return gdm_launch_status("affine_act_maxk_kernel");
 }
 
@@ -1168,12 +1168,14 @@ extern "C" int gdm_affine_act_hip(const float* x, const float* scale, const floa
     if (gx > 64) gx = 64;
     dim3 grid(gx, (unsigned)planes);
     hipStream_t s = (hipStream_t)stream;
-#define AA(A, H, R) hipLaunchKernelGGL((affine_act_kernel<A, H, R>), grid, dim3(256), 0, s, x, scale, shift, res, res_scale, res_shift, C, inner4, slope, y)
     const bool has = res != nullptr, aff = res_scale != nullptr && res_shift != nullptr;
-    if (act == 0) { if (!has) AA(0, false, false); else if (aff) AA(0, true, true); else AA(0, true, false); }
-    else if (act == 1) { if (!has) AA(1, false, false); else if (aff) AA(1, true, true); else AA(1, true, false); }
-    else { if (!has) AA(2, false, false); else if (aff) AA(2, true, true); else AA(2, true, false); }
-#undef AA
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        gdm_dispatch_int<3>(!has ? 0 : aff ? 2 : 1, [&](auto R) {       // no residual / residual / residual with its own affine
+            constexpr int RM = decltype(R)::value;
+            hipLaunchKernelGGL((affine_act_kernel<decltype(A)::value, RM != 0, RM == 2>), grid, dim3(256), 0, s, x, scale, shift, res, res_scale,
+                               res_shift, C, inner4, slope, y);
+        });
+    });
     return gdm_launch_status("affine_act_kernel");
 }
 
@@ -1190,9 +1192,10 @@ extern "C" int gdm_upconv3x3_gather2_hip(const float* z, const float* scale, con
                   "gdm_upconv3x3_gather2_hip: scale factors %g x %g too large for the LDS tile (the x2 stages of PSPUpsample fit)", rh, rw);
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(gdm_cdiv(OW, U8_W), gdm_cdiv(OH, U8_H), B * (Cout / 8));
-    if (act == 0) hipLaunchKernelGGL(upconv3x3_gather8_kernel<0>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out, (unsigned char*)outpk);
-    else if (act == 1) hipLaunchKernelGGL(upconv3x3_gather8_kernel<1>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out, (unsigned char*)outpk);
-    else hipLaunchKernelGGL(upconv3x3_gather8_kernel<2>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out, (unsigned char*)outpk);
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        hipLaunchKernelGGL(upconv3x3_gather8_kernel<decltype(A)::value>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out,
+                           (unsigned char*)outpk);
+    });
     return gdm_launch_status("upconv3x3_gather8_kernel");
 }
 
@@ -1209,9 +1212,9 @@ extern "C" int gdm_upconv3x3_gather_hip(const float* z, const float* scale, cons
     const bool lds_ok = (int)(rh * (UT_H + 1)) + 3 <= UP_PH && (int)(rw * (UT_W + 1)) + 3 <= UP_PW && (long)B * Cout <= 65535;
     if (lds_ok) {
         dim3 grid(gdm_cdiv(OW, UT_W), gdm_cdiv(OH, UT_H), B * Cout);
-        if (act == 0) hipLaunchKernelGGL(upconv3x3_gather_lds_kernel<0>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out);
-        else if (act == 1) hipLaunchKernelGGL(upconv3x3_gather_lds_kernel<1>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out);
-        else hipLaunchKernelGGL(upconv3x3_gather_lds_kernel<2>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out);
+        gdm_dispatch_int<3>(act, [&](auto A) {
+            hipLaunchKernelGGL(upconv3x3_gather_lds_kernel<decltype(A)::value>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out);
+        });
         return gdm_launch_status("upconv3x3_gather_lds_kernel");
     }
     // any other scale factor: the direct form (reads its taps from global memory).  (The three launch lines below were lost when the
@@ -1219,9 +1222,9 @@ extern "C" int gdm_upconv3x3_gather_hip(const float* z, const float* scale, cons
     // stages all upsample x2, but wrong for a caller of the C entry point.  tests/test_gpu_ops.py covers a 16 -> 20 stage now.)
     const int quads = ((OW + 3) / 4) * OH;
     dim3 grid(gdm_cdiv(quads, 256), B * Cout);
-    if (act == 0) hipLaunchKernelGGL(upconv3x3_gather_kernel<0>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out);
-    else if (act == 1) hipLaunchKernelGGL(upconv3x3_gather_kernel<1>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out);
-    else hipLaunchKernelGGL(upconv3x3_gather_kernel<2>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out);
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        hipLaunchKernelGGL(upconv3x3_gather_kernel<decltype(A)::value>, grid, dim3(256), 0, s, z, scale, shift, Cout, H, W, OH, OW, rh, rw, slope, out);
+    });
     return gdm_launch_status("upconv3x3_gather_kernel");
 }
 
@@ -1281,10 +1284,12 @@ extern "C" int gdm_gather_add_affine_act2_hip(const float* x, const float* t, co
                   "gdm_gather_add_affine_act2_hip: packed output needs m %% W == 0, C = 64 or a multiple of 128, a 16-byte aligned buffer");
     dim3 grid(gdm_cdiv(m, 256), gdm_cdiv(C, 8), B);
     hipStream_t s = (hipStream_t)stream;
-#define GAA(A, F) hipLaunchKernelGGL((gather_add_affine_act_kernel<A, F>), grid, dim3(256), 0, s, x, t, idx, scale, shift, C, n, m, slope, y, ypk, W)
-    if (y) { if (act == 0) GAA(0, true); else if (act == 1) GAA(1, true); else GAA(2, true); }
-    else { if (act == 0) GAA(0, false); else if (act == 1) GAA(1, false); else GAA(2, false); }
-#undef GAA
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        gdm_dispatch_bool(y != nullptr, [&](auto F) {
+            hipLaunchKernelGGL((gather_add_affine_act_kernel<decltype(A)::value, decltype(F)::value>), grid, dim3(256), 0, s, x, t, idx, scale, shift,
+                               C, n, m, slope, y, ypk, W);
+        });
+    });
     return gdm_launch_status("gather_add_affine_act_kernel");
 }
 
@@ -1297,10 +1302,12 @@ extern "C" int gdm_conv1x1_gather_add_act2_hip(const float* x, const float* wt, 
     GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && act >= 0 && act <= 2, "gdm_conv1x1_gather_add_act2_hip: bad shape");
     dim3 grid(gdm_cdiv(m, 256), B);
     hipStream_t s = (hipStream_t)stream;
-#define CGA(A, P) hipLaunchKernelGGL((conv1x1_gather_add_act_kernel<64, A, P>), grid, dim3(256), 0, s, x, wt, t, idx, scale, shift, n, m, slope, y)
-    if (pixel_major) { if (act == 0) CGA(0, true); else if (act == 1) CGA(1, true); else CGA(2, true); }
-    else { if (act == 0) CGA(0, false); else if (act == 1) CGA(1, false); else CGA(2, false); }
-#undef CGA
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        gdm_dispatch_bool(pixel_major != 0, [&](auto P) {
+            hipLaunchKernelGGL((conv1x1_gather_add_act_kernel<64, decltype(A)::value, decltype(P)::value>), grid, dim3(256), 0, s, x, wt, t, idx,
+                               scale, shift, n, m, slope, y);
+        });
+    });
     return gdm_launch_status("conv1x1_gather_add_act_kernel");
 }
 

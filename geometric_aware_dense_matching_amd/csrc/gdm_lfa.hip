@@ -59,7 +59,6 @@ __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? 
 // A workgroup owns P = 512 / D points (phases 1, 2 and 5 as above with two points per thread group); its 4 waves tile (channel tiles) x
 // (points).  One LDS dword read + one global dword load per 1024 products instead of 64 bytes of LDS per 16.
 // ---------------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) float lfa_f32x4;
 
 // all-reduce over the four lanes l, l ^ 16, l ^ 32, l ^ 48 (same l & 15), in one fixed order for every lane
 __device__ __forceinline__ float quadrow_max(float v)
@@ -80,7 +79,7 @@ __device__ __forceinline__ float quadrow_sum(float v, int kq)
 // acc[i][j] += W^T[:, row tile rt0 + WR i]^T . block of point pt0 + WP j, over KD input rows; src = LDS blocks [P][KD rows][16], wt = [KD][ROWS]
 template <int ROWS, int KD, int NRT, int NPT, int WR, int WP>
 __device__ __forceinline__ void lfa_tiles(const float* __restrict__ wt, const float* src, int src_pstride, int rt0, int pt0, int l16, int kq,
-                                          lfa_f32x4 (&acc)[NRT][NPT])
+                                          gdm_f32x4 (&acc)[NRT][NPT])
 {
 #pragma unroll
     for (int i = 0; i < NRT; ++i)
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(256) void lfa_stage_mfma_kernel(const LfaArgs a)
         constexpr int RT = H / 16, WR = RT < 4 ? RT : 4, WP = 4 / WR, NRT = RT / WR, NPT = P / WP;
         static_assert(RT >= 1 && NRT * WR == RT && NPT * WP == P, "mlp2 tiling");
         const int wr = wave % WR, wp = wave / WR;
-        lfa_f32x4 acc[NRT][NPT];
+        gdm_f32x4 acc[NRT][NPT];
         lfa_tiles<H, H, NRT, NPT, WR, WP>(a.w2t, &fx1[0][0][0], H * LK, wr, wp, l16, kq, acc);
 #pragma unroll
         for (int i = 0; i < NRT; ++i) {
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(256) void lfa_stage_mfma_kernel(const LfaArgs a)
         constexpr int RT = D / 16, WR = RT < 4 ? RT : 4, WP = 4 / WR, NRT = RT / WR, NPT = P / WP;
         static_assert(NRT * WR == RT && NPT * WP == P, "attention tiling");
         const int wr = wave % WR, wp = wave / WR;
-        lfa_f32x4 acc[NRT][NPT];
+        gdm_f32x4 acc[NRT][NPT];
         lfa_tiles<D, D, NRT, NPT, WR, WP>(a.wft, &fcat[0][0][0], D * LK, wr, wp, l16, kq, acc);
 #pragma unroll
         for (int i = 0; i < NRT; ++i) {
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(256) void lfa_stage_mfma_kernel(const LfaArgs a)
 #pragma unroll
             for (int j = 0; j < NPT; ++j) {
                 const int p = wp + WP * j;
-                const lfa_f32x4 t = acc[i][j];
+                const gdm_f32x4 t = acc[i][j];
                 const float mx = quadrow_max(fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3])));
                 const float e0 = __expf(t[0] - mx), e1 = __expf(t[1] - mx), e2 = __expf(t[2] - mx), e3 = __expf(t[3] - mx);
                 const float den = quadrow_sum((e0 + e1) + (e2 + e3), kq);

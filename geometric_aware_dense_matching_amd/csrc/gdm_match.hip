@@ -30,10 +30,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int D = 128;                 // descriptor length (config/lmo_cfg.py:125 feat_dim)
 constexpr int ROW_BYTES = 512;         // one packed row
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
     const int ntiles = (col_end - col_begin + MT_COLS - 1) / MT_COLS;
 
     // ---- A operand: this lane's 16 chunks, resident for the whole kernel ----
-    u32x4 areg[16];
+    gdm_u32x4 areg[16];
     {
         const unsigned char* arow = apk + (long)min(row0 + lr, R - 1) * ROW_BYTES;
 #pragma unroll
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
             int ch;
             if (PREC == GDM_MATCH_BF16X3) ch = (i < 8) ? (2 * i + h) : (16 + 2 * (i - 8) + h);   // hi[0..7], lo[0..7]
             else ch = 16 * h + i;                                                                // k = 64h + 4i..4i+3
-            areg[i] = *reinterpret_cast<const u32x4*>(arow + ch * 16);
+            areg[i] = *reinterpret_cast<const gdm_u32x4*>(arow + ch * 16);
         }
     }
 
@@ -169,7 +165,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
     }
 
     // ---- tile staging: 2048 chunks per tile, 8 per thread ----
-    u32x4 stage[8];
+    gdm_u32x4 stage[8];
     auto stage_load = [&](int tile) {
         const int c0 = col_begin + tile * MT_COLS;
 #pragma unroll
@@ -177,7 +173,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
             const int g = i * 256 + tid;
             const int col = g >> 5, ch = g & 31;
             const int gc = min(c0 + col, M - 1);
-            stage[i] = *reinterpret_cast<const u32x4*>(bpk + (long)gc * ROW_BYTES + ch * 16);
+            stage[i] = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)gc * ROW_BYTES + ch * 16);
         }
     };
     auto stage_store = [&](int buf) {
@@ -186,7 +182,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
         for (int i = 0; i < 8; ++i) {
             const int g = i * 256 + tid;
             const int col = g >> 5, ch = g & 31;
-            *reinterpret_cast<u32x4*>(base + lds_chunk_off(col, ch)) = stage[i];
+            *reinterpret_cast<gdm_u32x4*>(base + lds_chunk_off(col, ch)) = stage[i];
         }
     };
 
@@ -206,19 +202,19 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
 
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
-            f32x16 acc;
+            gdm_f32x16 acc;
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[i] = 0.f;
             const int col = cb * 32 + lr;
             if (PREC == GDM_MATCH_BF16X3) {
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
-                    const u32x4 bh = *reinterpret_cast<const u32x4*>(base + lds_chunk_off(col, 2 * s + h));
-                    const u32x4 bl = *reinterpret_cast<const u32x4*>(base + lds_chunk_off(col, 16 + 2 * s + h));
-                    const bf16x8 ah = __builtin_bit_cast(bf16x8, areg[s]);
-                    const bf16x8 al = __builtin_bit_cast(bf16x8, areg[8 + s]);
-                    const bf16x8 vbh = __builtin_bit_cast(bf16x8, bh);
-                    const bf16x8 vbl = __builtin_bit_cast(bf16x8, bl);
+                    const gdm_u32x4 bh = *reinterpret_cast<const gdm_u32x4*>(base + lds_chunk_off(col, 2 * s + h));
+                    const gdm_u32x4 bl = *reinterpret_cast<const gdm_u32x4*>(base + lds_chunk_off(col, 16 + 2 * s + h));
+                    const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
+                    const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
+                    const gdm_bf16x8 vbh = __builtin_bit_cast(gdm_bf16x8, bh);
+                    const gdm_bf16x8 vbl = __builtin_bit_cast(gdm_bf16x8, bl);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, vbl, acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, vbh, acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, vbh, acc, 0, 0, 0);
@@ -226,7 +222,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
             } else {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const u32x4 bv = *reinterpret_cast<const u32x4*>(base + lds_chunk_off(col, 16 * h + i));
+                    const gdm_u32x4 bv = *reinterpret_cast<const gdm_u32x4*>(base + lds_chunk_off(col, 16 * h + i));
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(bv.x), acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(bv.y), acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].z), __uint_as_float(bv.z), acc, 0, 0, 0);
@@ -295,7 +291,7 @@ constexpr int V2_THREADS = 512;
 constexpr int V2_ROWS = 256;                            // scene rows per workgroup iteration
 
 template <int PREC>
-__device__ __forceinline__ void load_a_rows(const unsigned char* __restrict__ apk, int row, int R, int h, u32x4 (&a)[16])
+__device__ __forceinline__ void load_a_rows(const unsigned char* __restrict__ apk, int row, int R, int h, gdm_u32x4 (&a)[16])
 {
     const unsigned char* arow = apk + (long)min(row, R - 1) * ROW_BYTES;
 #pragma unroll
@@ -303,7 +299,7 @@ __device__ __forceinline__ void load_a_rows(const unsigned char* __restrict__ ap
         int ch;
         if (PREC == GDM_MATCH_BF16X3) ch = (i < 8) ? (2 * i + h) : (16 + 2 * (i - 8) + h);
         else ch = 16 * h + i;
-        a[i] = *reinterpret_cast<const u32x4*>(arow + ch * 16);
+        a[i] = *reinterpret_cast<const gdm_u32x4*>(arow + ch * 16);
     }
 }
 
@@ -333,17 +329,17 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_kernel(const unsigned 
         const int gi = i * V2_THREADS + tid;
         const int col = gi >> 5, ch = gi & 31;
         const int gc = min(col0 + col, M - 1);
-        const u32x4 v = *reinterpret_cast<const u32x4*>(bpk + (long)gc * ROW_BYTES + ch * 16);
-        *reinterpret_cast<u32x4*>(smem + lds_chunk_off(col, ch)) = v;
+        const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)gc * ROW_BYTES + ch * 16);
+        *reinterpret_cast<gdm_u32x4*>(smem + lds_chunk_off(col, ch)) = v;
     }
     __syncthreads();
 
     const int nrb = (R + V2_ROWS - 1) / V2_ROWS;
-    u32x4 anext[16];
+    gdm_u32x4 anext[16];
     if (g < nrb) load_a_rows<PREC>(apk, g * V2_ROWS + wave * 32 + lr, R, h, anext);
 
     for (int rb = g; rb < nrb; rb += G) {
-        u32x4 areg[16];
+        gdm_u32x4 areg[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) areg[i] = anext[i];
         if (rb + G < nrb) load_a_rows<PREC>(apk, (rb + G) * V2_ROWS + wave * 32 + lr, R, h, anext);
@@ -359,7 +355,7 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_kernel(const unsigned 
 
 #pragma unroll 1
         for (int cp = 0; cp < PANEL_COLS / 64; ++cp) {
-            f32x16 acc0, acc1;
+            gdm_f32x16 acc0, acc1;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 acc0[i] = 0.f;
@@ -369,12 +365,12 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_kernel(const unsigned 
             if (PREC == GDM_MATCH_BF16X3) {
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
-                    const bf16x8 bh0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c0, 2 * s + h)));
-                    const bf16x8 bl0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c0, 16 + 2 * s + h)));
-                    const bf16x8 bh1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c1, 2 * s + h)));
-                    const bf16x8 bl1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c1, 16 + 2 * s + h)));
-                    const bf16x8 ah = __builtin_bit_cast(bf16x8, areg[s]);
-                    const bf16x8 al = __builtin_bit_cast(bf16x8, areg[8 + s]);
+                    const gdm_bf16x8 bh0 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 2 * s + h)));
+                    const gdm_bf16x8 bl0 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 + 2 * s + h)));
+                    const gdm_bf16x8 bh1 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 2 * s + h)));
+                    const gdm_bf16x8 bl1 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 16 + 2 * s + h)));
+                    const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
+                    const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
                     acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl0, acc0, 0, 0, 0);
                     acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl1, acc1, 0, 0, 0);
                     acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh0, acc0, 0, 0, 0);
@@ -385,8 +381,8 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_kernel(const unsigned 
             } else {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const u32x4 b0 = *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c0, 16 * h + i));
-                    const u32x4 b1 = *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c1, 16 * h + i));
+                    const gdm_u32x4 b0 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 * h + i));
+                    const gdm_u32x4 b1 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 16 * h + i));
                     acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(b0.x), acc0, 0, 0, 0);
                     acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(b1.x), acc1, 0, 0, 0);
                     acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(b0.y), acc0, 0, 0, 0);
@@ -522,29 +518,29 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_kernel(const unsigned 
 //     that row block's stores in vmcnt order (loads issued behind ~100 stores wait for all of them).
 // Requires R % 256 == 0 and M % 256 == 0 (no per-lane predication, so every step is one basic block); other shapes run v2.
 // Same products, same accumulation order as v2: bit-identical results.
-struct BFrag { u32x4 h0, l0, h1, l1; };
+struct BFrag { gdm_u32x4 h0, l0, h1, l1; };
 
 __device__ __forceinline__ BFrag read_bfrag(const unsigned char* smem, int c0, int s, int h)
 {
     BFrag f;
-    f.h0 = *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c0, 2 * s + h));
-    f.l0 = *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c0, 16 + 2 * s + h));
-    f.h1 = *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c0 + 32, 2 * s + h));
-    f.l1 = *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c0 + 32, 16 + 2 * s + h));
+    f.h0 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 2 * s + h));
+    f.l0 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 + 2 * s + h));
+    f.h1 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0 + 32, 2 * s + h));
+    f.l1 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0 + 32, 16 + 2 * s + h));
     return f;
 }
 
 // (max, first arg-max) of the 32 values a lane holds for its row in one 64-column block, as a tournament: codes are
 // compile-time constants at the leaves, every node takes its right child only if strictly greater (lower column wins ties).
 // code = 16*acc + reg; column within the block = (reg&3) + 8*(reg>>2) + 32*acc (+ 4*h), ascending in code for a fixed lane.
-__device__ __forceinline__ void block_argmax(const f32x16& p0, const f32x16& p1, float& bm, int& bc)
+__device__ __forceinline__ void block_argmax(const gdm_f32x16& p0, const gdm_f32x16& p1, float& bm, int& bc)
 {
     // four independent scan chains over ascending code ranges (8 values each), merged left to right
     float m[4];
     int c[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const f32x16& p = (j < 2) ? p0 : p1;
+        const gdm_f32x16& p = (j < 2) ? p0 : p1;
         const int r0 = (j & 1) * 8;
         m[j] = p[r0];
         c[j] = j * 8;
@@ -572,8 +568,8 @@ __device__ __forceinline__ void block_argmax(const f32x16& p0, const f32x16& p1,
 //   DRAIN     : false only for the very first step of a workgroup (nothing to drain yet)
 // acc[reg] of lane (lr, h) = sim[row lr][column (reg&3) + 8*(reg>>2) + 4*h of the 32-column block]
 template <int CP, int PCP, bool PREFETCH, bool DRAIN>
-__device__ __forceinline__ void pipe_step(const unsigned char* smem, int lr, int h, u32x4 (&areg)[16],
-                                          BFrag& fr, f32x16& n0, f32x16& n1, const f32x16& p0, const f32x16& p1,
+__device__ __forceinline__ void pipe_step(const unsigned char* smem, int lr, int h, gdm_u32x4 (&areg)[16],
+                                          BFrag& fr, gdm_f32x16& n0, gdm_f32x16& n1, const gdm_f32x16& p0, const gdm_f32x16& p1,
                                           float& best, int& bcode, const unsigned char* __restrict__ arow_next)
 {
 #pragma unroll
@@ -586,10 +582,10 @@ __device__ __forceinline__ void pipe_step(const unsigned char* smem, int lr, int
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const BFrag nx = (s < 7) ? read_bfrag(smem, c0, s + 1, h) : read_bfrag(smem, c0n, 0, h);
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, areg[s]);
-        const bf16x8 al = __builtin_bit_cast(bf16x8, areg[8 + s]);
-        const bf16x8 bh0 = __builtin_bit_cast(bf16x8, fr.h0), bl0 = __builtin_bit_cast(bf16x8, fr.l0);
-        const bf16x8 bh1 = __builtin_bit_cast(bf16x8, fr.h1), bl1 = __builtin_bit_cast(bf16x8, fr.l1);
+        const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
+        const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
+        const gdm_bf16x8 bh0 = __builtin_bit_cast(gdm_bf16x8, fr.h0), bl0 = __builtin_bit_cast(gdm_bf16x8, fr.l0);
+        const gdm_bf16x8 bh1 = __builtin_bit_cast(gdm_bf16x8, fr.h1), bl1 = __builtin_bit_cast(gdm_bf16x8, fr.l1);
         n0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl0, ah, n0, 0, 0, 0);
         n1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl1, ah, n1, 0, 0, 0);
         n0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh0, al, n0, 0, 0, 0);
@@ -597,8 +593,8 @@ __device__ __forceinline__ void pipe_step(const unsigned char* smem, int lr, int
         n0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh0, ah, n0, 0, 0, 0);
         n1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh1, ah, n1, 0, 0, 0);
         if (PREFETCH) {
-            areg[s] = *reinterpret_cast<const u32x4*>(arow_next + (2 * s + h) * 16);
-            areg[8 + s] = *reinterpret_cast<const u32x4*>(arow_next + (16 + 2 * s + h) * 16);
+            areg[s] = *reinterpret_cast<const gdm_u32x4*>(arow_next + (2 * s + h) * 16);
+            areg[8 + s] = *reinterpret_cast<const gdm_u32x4*>(arow_next + (16 + 2 * s + h) * 16);
         }
         fr = nx;
     }
@@ -643,25 +639,25 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_kernel(const unsigned c
     for (int i = 0; i < 16; ++i) {
         const int gi = i * V2_THREADS + tid;
         const int col = gi >> 5, ch = gi & 31;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(bpk + (long)(col0 + col) * ROW_BYTES + ch * 16);
-        *reinterpret_cast<u32x4*>(smem + lds_chunk_off(col, ch)) = v;
+        const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)(col0 + col) * ROW_BYTES + ch * 16);
+        *reinterpret_cast<gdm_u32x4*>(smem + lds_chunk_off(col, ch)) = v;
     }
     __syncthreads();
 
     const int nrb = R / V2_ROWS;
     if (g >= nrb) return;
-    u32x4 areg[16];
+    gdm_u32x4 areg[16];
     {
         const unsigned char* arow = apk + (long)(g * V2_ROWS + wave * 32 + lr) * ROW_BYTES;
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            areg[s] = *reinterpret_cast<const u32x4*>(arow + (2 * s + h) * 16);
-            areg[8 + s] = *reinterpret_cast<const u32x4*>(arow + (16 + 2 * s + h) * 16);
+            areg[s] = *reinterpret_cast<const gdm_u32x4*>(arow + (2 * s + h) * 16);
+            areg[8 + s] = *reinterpret_cast<const gdm_u32x4*>(arow + (16 + 2 * s + h) * 16);
         }
     }
     float best = -INFINITY;
     int bcode = 0;
-    f32x16 a0, a1, b0, b1;
+    gdm_f32x16 a0, a1, b0, b1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         b0[i] = 0.f;
@@ -795,22 +791,19 @@ __device__ __forceinline__ void finalize_rows(const float (&best)[16], const int
 // 2 rows x 128 contiguous bytes and may stay non-temporal; the swapped layout's 16-byte pieces need write-back merging in L2
 // and lose under load (347 vs 256 us).  Running (max, arg) per register, v2's butterfly per row block.
 // Steps of 32 columns (one accumulator in flight, one draining): 24 MFMAs | 16 values drained per step.
-#ifndef GDM_MATCH_EXP
-#define GDM_MATCH_EXP 0     // development: 1 = no operand reload, 2 = no matrix stores (wrong results)
-#endif
-struct BFrag1 { u32x4 h, l; };
+struct BFrag1 { gdm_u32x4 h, l; };
 
 __device__ __forceinline__ BFrag1 read_bfrag1(const unsigned char* smem, int c, int s, int h)
 {
     BFrag1 f;
-    f.h = *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c, 2 * s + h));
-    f.l = *reinterpret_cast<const u32x4*>(smem + lds_chunk_off(c, 16 + 2 * s + h));
+    f.h = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c, 2 * s + h));
+    f.l = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c, 16 + 2 * s + h));
     return f;
 }
 
 template <int CP, int PCP, bool RELOAD, bool DRAIN>
-__device__ __forceinline__ void pipe_step_sim(const unsigned char* smem, int lr, int h, u32x4 (&areg)[16], BFrag1& fr,
-                                              f32x16& n, const f32x16& p, float (&best)[16], int (&bidx)[16], int pgc,
+__device__ __forceinline__ void pipe_step_sim(const unsigned char* smem, int lr, int h, gdm_u32x4 (&areg)[16], BFrag1& fr,
+                                              gdm_f32x16& n, const gdm_f32x16& p, float (&best)[16], int (&bidx)[16], int pgc,
                                               float* __restrict__ pbase, unsigned pvoff, long M,
                                               const unsigned char* __restrict__ arow_next)
 {
@@ -821,15 +814,15 @@ __device__ __forceinline__ void pipe_step_sim(const unsigned char* smem, int lr,
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const BFrag1 nx = (s < 7) ? read_bfrag1(smem, c, s + 1, h) : read_bfrag1(smem, cn, 0, h);
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, areg[s]);
-        const bf16x8 al = __builtin_bit_cast(bf16x8, areg[8 + s]);
-        const bf16x8 bh = __builtin_bit_cast(bf16x8, fr.h), bl = __builtin_bit_cast(bf16x8, fr.l);
+        const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
+        const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
+        const gdm_bf16x8 bh = __builtin_bit_cast(gdm_bf16x8, fr.h), bl = __builtin_bit_cast(gdm_bf16x8, fr.l);
         n = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, n, 0, 0, 0);
         n = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, n, 0, 0, 0);
         n = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, n, 0, 0, 0);
-        if (RELOAD && !(GDM_MATCH_EXP & 1)) {
-            areg[s] = *reinterpret_cast<const u32x4*>(arow_next + (2 * s + h) * 16);
-            areg[8 + s] = *reinterpret_cast<const u32x4*>(arow_next + (16 + 2 * s + h) * 16);
+        if (RELOAD) {
+            areg[s] = *reinterpret_cast<const gdm_u32x4*>(arow_next + (2 * s + h) * 16);
+            areg[8 + s] = *reinterpret_cast<const gdm_u32x4*>(arow_next + (16 + 2 * s + h) * 16);
         }
         fr = nx;
     }
@@ -841,7 +834,7 @@ __device__ __forceinline__ void pipe_step_sim(const unsigned char* smem, int lr,
             best[reg] = t ? v : best[reg];
             bidx[reg] = t ? pgc : bidx[reg];
             float* o = pbase + (long)((reg & 3) + 8 * (reg >> 2)) * M + PCP * 32;     // uniform row base, per-lane 32-bit offset
-            if (!(GDM_MATCH_EXP & 2)) __builtin_nontemporal_store(v, o + pvoff);
+            __builtin_nontemporal_store(v, o + pvoff);
         }
     }
 #pragma unroll
@@ -876,20 +869,20 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_sim_kernel(const unsign
     for (int i = 0; i < 16; ++i) {
         const int gi = i * V2_THREADS + tid;
         const int col = gi >> 5, ch = gi & 31;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(bpk + (long)(col0 + col) * ROW_BYTES + ch * 16);
-        *reinterpret_cast<u32x4*>(smem + lds_chunk_off(col, ch)) = v;
+        const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)(col0 + col) * ROW_BYTES + ch * 16);
+        *reinterpret_cast<gdm_u32x4*>(smem + lds_chunk_off(col, ch)) = v;
     }
     __syncthreads();
 
     const int nrb = R / V2_ROWS;
     if (g >= nrb) return;
-    u32x4 areg[16];
+    gdm_u32x4 areg[16];
     {
         const unsigned char* arow = apk + (long)(g * V2_ROWS + wave * 32 + lr) * ROW_BYTES;
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            areg[s] = *reinterpret_cast<const u32x4*>(arow + (2 * s + h) * 16);
-            areg[8 + s] = *reinterpret_cast<const u32x4*>(arow + (16 + 2 * s + h) * 16);
+            areg[s] = *reinterpret_cast<const gdm_u32x4*>(arow + (2 * s + h) * 16);
+            areg[8 + s] = *reinterpret_cast<const gdm_u32x4*>(arow + (16 + 2 * s + h) * 16);
         }
     }
     float best[16];
@@ -899,7 +892,7 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_sim_kernel(const unsign
         best[i] = -INFINITY;
         bidx[i] = 0;
     }
-    f32x16 a, b;
+    gdm_f32x16 a, b;
 #pragma unroll
     for (int i = 0; i < 16; ++i) b[i] = 0.f;
     BFrag1 fr = read_bfrag1(smem, lr, 0, h);
@@ -1077,26 +1070,16 @@ extern "C" int gdm_match_packed_hip(const void* scene_rows, const void* model_ro
         dim3 grid(panels * G);
         float* ov = nsplit == 1 ? best_sim : pval;
         int32_t* oi = nsplit == 1 ? best_idx : pidx;
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)match_panel_kernel<GDM_MATCH_BF16X3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_BYTES);
-            (void)hipFuncSetAttribute((const void*)match_panel_kernel<GDM_MATCH_BF16X3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_BYTES);
-            (void)hipFuncSetAttribute((const void*)match_panel_kernel<GDM_MATCH_F32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_BYTES);
-            (void)hipFuncSetAttribute((const void*)match_panel_kernel<GDM_MATCH_F32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_BYTES);
-            (void)hipFuncSetAttribute((const void*)match_pipe_sim_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_BYTES);
-            (void)hipFuncSetAttribute((const void*)match_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_BYTES);
-            attr_set = true;
-        }
-#define LAUNCH2(P, W) hipLaunchKernelGGL((match_panel_kernel<P, W>), grid, dim3(V2_THREADS), PANEL_BYTES, stream, apk, bpk, R, M, G, sim, ov, oi)
-        if (pipe) {
-            if (ws_sim) hipLaunchKernelGGL(match_pipe_sim_kernel, grid, dim3(V2_THREADS), PANEL_BYTES, stream, apk, bpk, R, M, G, sim, ov, oi);
-            else hipLaunchKernelGGL(match_pipe_kernel, grid, dim3(V2_THREADS), PANEL_BYTES, stream, apk, bpk, R, M, G, sim, ov, oi);
-        } else if (precision == GDM_MATCH_BF16X3) {
-            if (ws_sim) LAUNCH2(GDM_MATCH_BF16X3, true); else LAUNCH2(GDM_MATCH_BF16X3, false);
-        } else {
-            if (ws_sim) LAUNCH2(GDM_MATCH_F32, true); else LAUNCH2(GDM_MATCH_F32, false);
-        }
-#undef LAUNCH2
+        static_assert(GDM_MATCH_BF16X3 == 0 && GDM_MATCH_F32 == 1, "the precision is dispatched as an index");
+        gdm_dispatch_bool(ws_sim, [&](auto WS) {
+            gdm_dispatch_int<3>(pipe ? 2 : precision, [&](auto K) {            // the panel kernel at either precision, or the pipelined pair
+                constexpr bool W = decltype(WS)::value;
+                constexpr int k = decltype(K)::value;
+                constexpr auto kernel = k < 2 ? match_panel_kernel<k & 1, W> : W ? match_pipe_sim_kernel : match_pipe_kernel;
+                gdm_allow_lds<kernel>(PANEL_BYTES);
+                hipLaunchKernelGGL(kernel, grid, dim3(V2_THREADS), PANEL_BYTES, stream, apk, bpk, R, M, G, sim, ov, oi);
+            });
+        });
         rc = gdm_launch_status("match_panel_kernel");
         if (rc) return rc;
     } else {
@@ -1107,13 +1090,11 @@ extern "C" int gdm_match_packed_hip(const void* scene_rows, const void* model_ro
         float* ov = nsplit == 1 ? best_sim : pval;
         int32_t* oi = nsplit == 1 ? best_idx : pidx;
         const size_t lds = 2 * TILE_BYTES;
-#define LAUNCH(P, W) hipLaunchKernelGGL((match_kernel<P, W>), grid, dim3(256), lds, stream, apk, bpk, R, M, cps, sim, ov, oi)
-        if (precision == GDM_MATCH_BF16X3) {
-            if (ws_sim) LAUNCH(GDM_MATCH_BF16X3, true); else LAUNCH(GDM_MATCH_BF16X3, false);
-        } else {
-            if (ws_sim) LAUNCH(GDM_MATCH_F32, true); else LAUNCH(GDM_MATCH_F32, false);
-        }
-#undef LAUNCH
+        gdm_dispatch_int<2>(precision, [&](auto P) {                // GDM_MATCH_BF16X3 = 0, GDM_MATCH_F32 = 1 (asserted above)
+            gdm_dispatch_bool(ws_sim, [&](auto WS) {
+                hipLaunchKernelGGL((match_kernel<decltype(P)::value, decltype(WS)::value>), grid, dim3(256), lds, stream, apk, bpk, R, M, cps, sim, ov, oi);
+            });
+        });
         rc = gdm_launch_status("match_kernel");
         if (rc) return rc;
     }

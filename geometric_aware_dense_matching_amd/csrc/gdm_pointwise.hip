@@ -278,7 +278,6 @@ __global__ __launch_bounds__(NW * 64) void pointwise_kernel(const PwArgs a)
 // A workgroup = KS waves = the KS parts of the K axis of ONE tile of 64 points x 16 channels; partial sums are added through LDS in
 // fixed order.  Each wave walks its K range segment by segment (pointer increments only), four K rows per MFMA step.
 // ---------------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) float pw_f32x4;
 
 // VEC (no indexed segment, n % 4 == 0, 16-byte aligned operands): accumulator block g owns the points p0 + 4 (l & 15) + g instead of
 // p0 + 16 g + (l & 15), so ONE 16-byte load per lane fetches a K row's values for all four blocks (a wave-wide dword load costs the
@@ -315,7 +314,7 @@ __device__ __forceinline__ void pw_mfma_tile(const PwArgs& a, const long p0, con
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) wcoff[cb] = (long)min(c0 + 16 * cb + l16, Cout - 1) * a.wcs;
 
-    pw_f32x4 acc[CB][4];
+    gdm_f32x4 acc[CB][4];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
@@ -644,12 +643,6 @@ extern "C" int gdm_pointwise2_hip(const gdm_pw_seg* segs, int nseg, const float*
     hipStream_t st = (hipStream_t)stream;
     bool vec = (n % 4 == 0) && (Cout % 4 == 0) && (((uintptr_t)wt & 15) == 0) && !w_rowmajor;      // (the FMA form's 16-byte weight loads run along Cout)
     for (int s = 0; s < nseg; ++s) vec = vec && !segs[s].idx && (((uintptr_t)segs[s].x & 15) == 0);
-#define GDM_PW_LAUNCH(NW, KS, COUT_PER_WG)                                                                                          \
-    do {                                                                                                                            \
-        const dim3 grid((unsigned)tiles, gdm_cdiv(Cout, COUT_PER_WG));                                                              \
-        if (vec) hipLaunchKernelGGL((pointwise_kernel<NW, KS, true>), grid, dim3(NW * 64), 0, st, a);                               \
-        else hipLaunchKernelGGL((pointwise_kernel<NW, KS, false>), grid, dim3(NW * 64), 0, st, a);                                  \
-    } while (0)
     if (a.K >= 32 && gdm_cdiv(Cout, 16) <= 65535) {
         // K parts per tile: as many as leave each wave >= 16 rows, at most 8 (= waves of the workgroup)
         int ks = 1;
@@ -657,11 +650,6 @@ extern "C" int gdm_pointwise2_hip(const gdm_pw_seg* segs, int nseg, const float*
         const dim3 grid((unsigned)tiles, gdm_cdiv(Cout, 16));
         bool mvec = (n % 4 == 0);
         for (int sgi = 0; sgi < nseg; ++sgi) mvec = mvec && !segs[sgi].idx && (((uintptr_t)segs[sgi].x & 15) == 0) && segs[sgi].n_src % 4 == 0;
-#define GDM_PWM(KSV)                                                                                                    \
-        do {                                                                                                             \
-            if (mvec) hipLaunchKernelGGL((pointwise_mfma_kernel<KSV, true>), grid, dim3(KSV * 64), 0, st, a);            \
-            else hipLaunchKernelGGL((pointwise_mfma_kernel<KSV, false>), grid, dim3(KSV * 64), 0, st, a);                \
-        } while (0)
         // no K split and still >= 2048 workgroups with four (two) channel blocks per wave: each x row is then fetched Cout / 64 (/ 32)
         // times instead of Cout / 16
         if (ks == 1 && Cout >= 32 && tiles >= 1024) {
@@ -672,17 +660,19 @@ extern "C" int gdm_pointwise2_hip(const gdm_pw_seg* segs, int nseg, const float*
             else hipLaunchKernelGGL((pointwise_mfma_cw_kernel<false, 1>), gridc, dim3(256), 0, st, a);
             return gdm_launch_status("pointwise_mfma_cw_kernel");
         }
-        if (ks == 1) GDM_PWM(1);
-        else if (ks == 2) GDM_PWM(2);
-        else if (ks == 4) GDM_PWM(4);
-        else GDM_PWM(8);
-#undef GDM_PWM
+        gdm_dispatch_int<4>(__builtin_ctz(ks), [&](auto L) {       // ks = 1, 2, 4 or 8
+            constexpr int KSV = 1 << decltype(L)::value;
+            gdm_dispatch_bool(mvec, [&](auto V) {
+                hipLaunchKernelGGL((pointwise_mfma_kernel<KSV, decltype(V)::value>), grid, dim3(KSV * 64), 0, st, a);
+            });
+        });
         return gdm_launch_status("pointwise_mfma_kernel");
     }
     // K < 32 (or more than 2^20 output channels): the FMA form, four waves per 64 x 64 tile, no K split
     GDM_CHECK_ARG(nseg <= 3, "gdm_pointwise2_hip: four segments need K >= 32 (the MFMA form)");
-    GDM_PW_LAUNCH(4, 1, 64);
-#undef GDM_PW_LAUNCH
+    const dim3 grid((unsigned)tiles, gdm_cdiv(Cout, 64));
+    if (vec) hipLaunchKernelGGL((pointwise_kernel<4, 1, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pointwise_kernel<4, 1, false>), grid, dim3(256), 0, st, a);
     return gdm_launch_status("pointwise_kernel");
 }
 
@@ -745,12 +735,10 @@ extern "C" int gdm_pointwise_jobs_hip(const gdm_pw_job* jobs, int njobs, int B, 
         (void)last;
         GDM_CHECK_ARG(tiles <= 0x7fffffffL, "gdm_pointwise_jobs_hip: grid too large");
         const dim3 grid((unsigned)tiles, gdm_cdiv(Cout, 16));
-#define GDM_PWJ(KSV) hipLaunchKernelGGL((pointwise_mfma_jobs_kernel<KSV>), grid, dim3(KSV * 64), 0, st, a[0], a[1], a[2], a[3], ends[0], ends[1], ends[2], vecmask)
-        if (ks == 1) GDM_PWJ(1);
-        else if (ks == 2) GDM_PWJ(2);
-        else if (ks == 4) GDM_PWJ(4);
-        else GDM_PWJ(8);
-#undef GDM_PWJ
+        gdm_dispatch_int<4>(__builtin_ctz(ks), [&](auto L) {       // ks = 1, 2, 4 or 8
+            constexpr int KSV = 1 << decltype(L)::value;
+            hipLaunchKernelGGL((pointwise_mfma_jobs_kernel<KSV>), grid, dim3(KSV * 64), 0, st, a[0], a[1], a[2], a[3], ends[0], ends[1], ends[2], vecmask);
+        });
         const int rc = gdm_launch_status("pointwise_mfma_jobs_kernel");
         if (rc) return rc;
     }

@@ -407,7 +407,6 @@ __global__ __launch_bounds__(128) void spline_segment_sum_kernel(const float* __
 // part[t], and spline_wgrad_reduce_kernel adds the partials of every kernel index in ascending tile order -- a fixed order.
 // 4 waves: Cin = 128 -> grid (tiles, 2), wave w the Cin tile w and two 32-column tiles of its half of the 128 outputs (two independent
 // accumulators); Cin <= 32 (the first layer, rows beyond Cin zero inside the kernel) -> grid (tiles, 1), wave w the column tile w.
-typedef __attribute__((ext_vector_type(16))) float spl_f32x16;
 
 template <int CI_TILES, int NACC>
 __global__ __launch_bounds__(256) void spline_wgrad_kernel(const float* __restrict__ x, const int32_t* __restrict__ rowidx,
@@ -426,7 +425,7 @@ __global__ __launch_bounds__(256) void spline_wgrad_kernel(const float* __restri
     const long r0 = (long)t * TILE;
     const int n = min(TILE, blk_start[k] + blk_rows[k] - (int)r0);  // real rows of this tile (<= 0: a tile of padding only)
     const bool ci_ok = ci_t + l31 < Cin;
-    spl_f32x16 acc[NACC];
+    gdm_f32x16 acc[NACC];
 #pragma unroll
     for (int q = 0; q < NACC; ++q)
 #pragma unroll

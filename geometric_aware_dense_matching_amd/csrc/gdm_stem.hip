@@ -14,15 +14,7 @@
 // order by stem_pack_w_kernel: 48 KB) come straight from global memory / L2 into registers, one k-step ahead.
 #include "gdm_common.h"
 
-#ifndef GDM_STEM_ABL
-#define GDM_STEM_ABL 0
-#endif
-
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int SP_H = 4, SP_W = 16;                 // pooled tile
 constexpr int SC_H = 2 * SP_H + 1, SC_W = 2 * SP_W + 1;   // convolution pixels under it: 9 x 33
@@ -92,18 +84,15 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
             if (e < 3 * SI_H * SI_W) (&patch[0][0][0])[e] = v[i];
         }
     }
-#if GDM_STEM_ABL & 8
-    return;
-#endif
 
     // ---- B fragments of k-step 0 (registers), the wave's A-fragment coordinates ----
-    u32x4 bh[4], bl[4], nbh[4], nbl[4];
-    auto load_b = [&](int step, u32x4 (&h)[4], u32x4 (&l)[4]) {
+    gdm_u32x4 bh[4], bl[4], nbh[4], nbl[4];
+    auto load_b = [&](int step, gdm_u32x4 (&h)[4], gdm_u32x4 (&l)[4]) {
 #pragma unroll
         for (int nf = 0; nf < 4; ++nf) {
             const unsigned char* p = wpk + ((long)((step * 4 + nf) * 2) * 64 + lane) * 16;
-            h[nf] = *reinterpret_cast<const u32x4*>(p);
-            l[nf] = *reinterpret_cast<const u32x4*>(p + 64 * 16);
+            h[nf] = *reinterpret_cast<const gdm_u32x4*>(p);
+            l[nf] = *reinterpret_cast<const gdm_u32x4*>(p + 64 * 16);
         }
     };
     load_b(0, bh, bl);
@@ -115,7 +104,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
         const int cy = p / SC_W, cx = p - cy * SC_W;
         aoff[j] = (2 * cy) * SI_W + 2 * cx;
     }
-    f32x4 acc[MPW][4];
+    gdm_f32x4 acc[MPW][4];
 #pragma unroll
     for (int j = 0; j < MPW; ++j)
 #pragma unroll
@@ -146,16 +135,14 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
             unsigned hi[4], lo[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) gdm_split2(v[2 * q], v[2 * q + 1], hi[q], lo[q]);
-            const u32x4 ahv = {hi[0], hi[1], hi[2], hi[3]}, alv = {lo[0], lo[1], lo[2], lo[3]};
-            const bf16x8 ah = __builtin_bit_cast(bf16x8, ahv), al = __builtin_bit_cast(bf16x8, alv);
+            const gdm_u32x4 ahv = {hi[0], hi[1], hi[2], hi[3]}, alv = {lo[0], lo[1], lo[2], lo[3]};
+            const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, ahv), al = __builtin_bit_cast(gdm_bf16x8, alv);
 #pragma unroll
             for (int nf = 0; nf < 4; ++nf) {
-                f32x4 cacc = acc[j][nf];
-#if !(GDM_STEM_ABL & 1)
-                cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, bl[nf]), cacc, 0, 0, 0);
-                cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, __builtin_bit_cast(bf16x8, bh[nf]), cacc, 0, 0, 0);
-#endif
-                cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, bh[nf]), cacc, 0, 0, 0);
+                gdm_f32x4 cacc = acc[j][nf];
+                cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(gdm_bf16x8, bl[nf]), cacc, 0, 0, 0);
+                cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, __builtin_bit_cast(gdm_bf16x8, bh[nf]), cacc, 0, 0, 0);
+                cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(gdm_bf16x8, bh[nf]), cacc, 0, 0, 0);
                 acc[j][nf] = cacc;
             }
         }
@@ -170,9 +157,6 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
 
     // ---- BN + ReLU, convolution pixels outside the map -> 0 (below every ReLU output a pool window also holds), into LDS; then the
     // max-pool 3x3 / 2 / pad 1 with thread = pooled pixel (tid & 63) x 8 channels (wave); two passes of 32 channels ----
-#if GDM_STEM_ABL & 4
-    if (acc[0][0][0] != 12345.678f) return;
-#endif
     const int pxl = tid & 15, pyl = (tid >> 4) & 3;
     const int py = py0 + pyl, px = px0 + pxl;
     const bool store = py < PH && px < PW;

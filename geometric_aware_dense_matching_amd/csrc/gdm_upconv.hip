@@ -9,9 +9,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int UF_C = 64;                 // channels in and out
 constexpr int UF_ROWB = 256;             // packed row: 64 bf16 hi | 64 bf16 lo
@@ -82,18 +79,18 @@ __global__ __launch_bounds__(256, 2) void upconv_tile64_kernel(const float* __re
     const int xs1 = min((int)(rw * (float)min(ox_t + UT_TX, OW - 1)) + 1, W - 1);
     const int pw = xs1 - xs0 + 1;                                  // <= UT_PW
 
-    u32x4 stage[4];
+    gdm_u32x4 stage[4];
     auto stage_load = [&](int tap) {
         const unsigned char* src = wpk + (long)tap * UT_WBUF;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) stage[i] = *reinterpret_cast<const u32x4*>(src + (long)(i * 256 + tid) * 16);
+        for (int i = 0; i < 4; ++i) stage[i] = *reinterpret_cast<const gdm_u32x4*>(src + (long)(i * 256 + tid) * 16);
     };
     auto stage_store = [&](int buf) {
         unsigned char* dst = ws + buf * UT_WBUF;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int g = i * 256 + tid;
-            *reinterpret_cast<u32x4*>(dst + uf_off(g >> 4, g & 15)) = stage[i];
+            *reinterpret_cast<gdm_u32x4*>(dst + uf_off(g >> 4, g & 15)) = stage[i];
         }
     };
     // source window of a tile (ring and the +1 bilinear neighbour included): first row and row count
@@ -155,15 +152,15 @@ __global__ __launch_bounds__(256, 2) void upconv_tile64_kernel(const float* __re
 #pragma unroll
                 for (int j = 0; j < 4; ++j) gdm_split2(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
             }
-            *reinterpret_cast<u32x4*>(tile + uf_off(px, grp)) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-            *reinterpret_cast<u32x4*>(tile + uf_off(px, 8 + grp)) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+            *reinterpret_cast<gdm_u32x4*>(tile + uf_off(px, grp)) = gdm_u32x4{hi[0], hi[1], hi[2], hi[3]};
+            *reinterpret_cast<gdm_u32x4*>(tile + uf_off(px, 8 + grp)) = gdm_u32x4{lo[0], lo[1], lo[2], lo[3]};
         }
         __syncthreads();                                           // tile complete, patch dead
         stage_store(0);                                            // tap 0's weights (loaded before the loop / during the last tap)
         __syncthreads();
 
         // ---- C: nine taps x K = 64 for 32 pixels x 64 output channels per wave ----
-        f32x16 acc[2];
+        gdm_f32x16 acc[2];
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -174,21 +171,21 @@ __global__ __launch_bounds__(256, 2) void upconv_tile64_kernel(const float* __re
             const int ky = tap / 3, kx = tap - 3 * ky;
             const int R = (prow + ky) * UT_HW + pcol + kx;
             const unsigned char* wb = ws + (tap & 1) * UT_WBUF;
-            u32x4 bh[4], bl[4];
+            gdm_u32x4 bh[4], bl[4];
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                bh[s] = *reinterpret_cast<const u32x4*>(tile + uf_off(R, 2 * s + h));
-                bl[s] = *reinterpret_cast<const u32x4*>(tile + uf_off(R, 8 + 2 * s + h));
+                bh[s] = *reinterpret_cast<const gdm_u32x4*>(tile + uf_off(R, 2 * s + h));
+                bl[s] = *reinterpret_cast<const gdm_u32x4*>(tile + uf_off(R, 8 + 2 * s + h));
             }
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
                 const int n = cb * 32 + lr;
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    const bf16x8 wh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(wb + uf_off(n, 2 * s + h)));
-                    const bf16x8 wl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(wb + uf_off(n, 8 + 2 * s + h)));
-                    const bf16x8 xh = __builtin_bit_cast(bf16x8, bh[s]);
-                    const bf16x8 xl = __builtin_bit_cast(bf16x8, bl[s]);
+                    const gdm_bf16x8 wh = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(wb + uf_off(n, 2 * s + h)));
+                    const gdm_bf16x8 wl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(wb + uf_off(n, 8 + 2 * s + h)));
+                    const gdm_bf16x8 xh = __builtin_bit_cast(gdm_bf16x8, bh[s]);
+                    const gdm_bf16x8 xl = __builtin_bit_cast(gdm_bf16x8, bl[s]);
                     acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc[cb], 0, 0, 0);
                     acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh, acc[cb], 0, 0, 0);
                     acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc[cb], 0, 0, 0);
@@ -228,7 +225,6 @@ __global__ __launch_bounds__(256, 2) void upconv_tile64_kernel(const float* __re
 // (two lane shuffles + one exchange through LDS).  Same products and summation structure as the dense kernels, 1/32 of the work.
 constexpr int FP_P = 32;                              // chosen pixels per workgroup
 constexpr int FP_ABUF = FP_P * UF_ROWB;               // one tap's operand rows: 8 KiB
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
 
 __device__ __forceinline__ int fp_chunk(int row, int ch) { return uf_off(row, ch); }
 
@@ -255,7 +251,7 @@ __global__ __launch_bounds__(256, 4) void upconv_final_points_kernel(const float
         ox = ch - oy * OW;
     }
     const float* xb = xpm + (long)b * H * W * UF_C + grp * 8;
-    f32x4v raw[8];                                              // 4 corners x 8 channels of the tap being built
+    gdm_f32x4 raw[8];                                              // 4 corners x 8 channels of the tap being built
     float ly1, lx1;
     bool inside;
     auto corners_load = [&](int tap) {
@@ -270,14 +266,14 @@ __global__ __launch_bounds__(256, 4) void upconv_final_points_kernel(const float
         const float* p01 = p00 + xp * UF_C;
         const float* p10 = p00 + (long)yp * W * UF_C;
         const float* p11 = p10 + xp * UF_C;
-        raw[0] = *reinterpret_cast<const f32x4v*>(p00);
-        raw[1] = *reinterpret_cast<const f32x4v*>(p00 + 4);
-        raw[2] = *reinterpret_cast<const f32x4v*>(p01);
-        raw[3] = *reinterpret_cast<const f32x4v*>(p01 + 4);
-        raw[4] = *reinterpret_cast<const f32x4v*>(p10);
-        raw[5] = *reinterpret_cast<const f32x4v*>(p10 + 4);
-        raw[6] = *reinterpret_cast<const f32x4v*>(p11);
-        raw[7] = *reinterpret_cast<const f32x4v*>(p11 + 4);
+        raw[0] = *reinterpret_cast<const gdm_f32x4*>(p00);
+        raw[1] = *reinterpret_cast<const gdm_f32x4*>(p00 + 4);
+        raw[2] = *reinterpret_cast<const gdm_f32x4*>(p01);
+        raw[3] = *reinterpret_cast<const gdm_f32x4*>(p01 + 4);
+        raw[4] = *reinterpret_cast<const gdm_f32x4*>(p10);
+        raw[5] = *reinterpret_cast<const gdm_f32x4*>(p10 + 4);
+        raw[6] = *reinterpret_cast<const gdm_f32x4*>(p11);
+        raw[7] = *reinterpret_cast<const gdm_f32x4*>(p11 + 4);
     };
     auto rows_store = [&](int buf) {                              // up(x) as upsample_bilinear2d forms it, split, one 16-B chunk hi + lo
         const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
@@ -294,39 +290,39 @@ __global__ __launch_bounds__(256, 4) void upconv_final_points_kernel(const float
             gdm_split2(v[0], v[1], hi[j], lo[j]);
         }
         unsigned char* dst = abuf + buf * FP_ABUF;
-        *reinterpret_cast<u32x4*>(dst + fp_chunk(bp, grp)) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-        *reinterpret_cast<u32x4*>(dst + fp_chunk(bp, 8 + grp)) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        *reinterpret_cast<gdm_u32x4*>(dst + fp_chunk(bp, grp)) = gdm_u32x4{hi[0], hi[1], hi[2], hi[3]};
+        *reinterpret_cast<gdm_u32x4*>(dst + fp_chunk(bp, 8 + grp)) = gdm_u32x4{lo[0], lo[1], lo[2], lo[3]};
     };
 
     // ---- matrix role: wave = 16 output channels x the 32 pixels (two 16-column blocks), 16x16x32 products ----
     // A fragment (weights): lane (row l16 = channel 16 wave + l16, k-group kg): 8 input channels 32 S + 8 kg .. of k-step S
-    u32x4 wh[2], wl[2];
+    gdm_u32x4 wh[2], wl[2];
     auto weights_load = [&](const unsigned char* rows) {           // rows: 64 packed rows of 256 B (64 bf16 hi | 64 bf16 lo)
         const unsigned char* r = rows + (long)(16 * wave + l16) * UF_ROWB;
 #pragma unroll
         for (int S = 0; S < 2; ++S) {
-            wh[S] = *reinterpret_cast<const u32x4*>(r + (4 * S + kg) * 16);
-            wl[S] = *reinterpret_cast<const u32x4*>(r + (8 + 4 * S + kg) * 16);
+            wh[S] = *reinterpret_cast<const gdm_u32x4*>(r + (4 * S + kg) * 16);
+            wl[S] = *reinterpret_cast<const gdm_u32x4*>(r + (8 + 4 * S + kg) * 16);
         }
     };
-    f32x4v acc[2];
+    gdm_f32x4 acc[2];
     auto mma = [&](int buf) {
         const unsigned char* src = abuf + buf * FP_ABUF;
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
             for (int S = 0; S < 2; ++S) {
-                const bf16x8 xh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(src + fp_chunk(16 * pb + l16, 4 * S + kg)));
-                const bf16x8 xl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(src + fp_chunk(16 * pb + l16, 8 + 4 * S + kg)));
-                const bf16x8 ah = __builtin_bit_cast(bf16x8, wh[S]);
-                const bf16x8 al = __builtin_bit_cast(bf16x8, wl[S]);
+                const gdm_bf16x8 xh = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(src + fp_chunk(16 * pb + l16, 4 * S + kg)));
+                const gdm_bf16x8 xl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(src + fp_chunk(16 * pb + l16, 8 + 4 * S + kg)));
+                const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, wh[S]);
+                const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, wl[S]);
                 acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl, acc[pb], 0, 0, 0);
                 acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, acc[pb], 0, 0, 0);
                 acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, acc[pb], 0, 0, 0);
             }
     };
 #pragma unroll
-    for (int pb = 0; pb < 2; ++pb) acc[pb] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int pb = 0; pb < 2; ++pb) acc[pb] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
 
     corners_load(0);
     rows_store(0);
@@ -345,8 +341,8 @@ __global__ __launch_bounds__(256, 4) void upconv_final_points_kernel(const float
     // accumulator: lane column l16 = pixel 16 pb + l16, registers r = output channels 16 wave + 4 kg + r
     {
         const int c0 = 16 * wave + 4 * kg;
-        const f32x4v sc = f32x4v{scale[c0], scale[c0 + 1], scale[c0 + 2], scale[c0 + 3]};
-        const f32x4v sh = f32x4v{shift[c0], shift[c0 + 1], shift[c0 + 2], shift[c0 + 3]};
+        const gdm_f32x4 sc = gdm_f32x4{scale[c0], scale[c0 + 1], scale[c0 + 2], scale[c0 + 3]};
+        const gdm_f32x4 sh = gdm_f32x4{shift[c0], shift[c0 + 1], shift[c0 + 2], shift[c0 + 3]};
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
             float v[4];
@@ -365,7 +361,7 @@ __global__ __launch_bounds__(256, 4) void upconv_final_points_kernel(const float
             *reinterpret_cast<uint2*>(row) = make_uint2(h0, h1);
             unsigned char* rowl = abuf + fp_chunk(16 * pb + l16, 8 + 2 * wave + (kg >> 1)) + 8 * (kg & 1);
             *reinterpret_cast<uint2*>(rowl) = make_uint2(l0, l1);
-            acc[pb] = f32x4v{0.f, 0.f, 0.f, 0.f};
+            acc[pb] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
     __syncthreads();
@@ -374,8 +370,8 @@ __global__ __launch_bounds__(256, 4) void upconv_final_points_kernel(const float
     // ---- + bias, log-softmax over the 64 channels of a pixel: 4 registers x 4 k-groups (lanes l16 + 16 kg) x 4 waves ----
     {
         const int c0 = 16 * wave + 4 * kg;
-        f32x4v bq = f32x4v{0.f, 0.f, 0.f, 0.f};
-        if (fbias) bq = f32x4v{fbias[c0], fbias[c0 + 1], fbias[c0 + 2], fbias[c0 + 3]};
+        gdm_f32x4 bq = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
+        if (fbias) bq = gdm_f32x4{fbias[c0], fbias[c0 + 1], fbias[c0 + 2], fbias[c0 + 3]};
         float y[2][4], m[2];
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
@@ -438,13 +434,13 @@ __global__ __launch_bounds__(256, 4) void conv64_gather_add_act_mfma_kernel(cons
     const int b = blockIdx.y, j0 = blockIdx.x * CG_P;
     const float* xb = x + (long)b * UF_C * m;
     // A fragments (weights): rows 16 wave + l16, k-step S: channels 32 S + 8 kg ..
-    u32x4 wh[2], wl[2];
+    gdm_u32x4 wh[2], wl[2];
     {
         const unsigned char* r = wpk + (long)(16 * wave + l16) * UF_ROWB;
 #pragma unroll
         for (int S = 0; S < 2; ++S) {
-            wh[S] = *reinterpret_cast<const u32x4*>(r + (4 * S + kg) * 16);
-            wl[S] = *reinterpret_cast<const u32x4*>(r + (8 + 4 * S + kg) * 16);
+            wh[S] = *reinterpret_cast<const gdm_u32x4*>(r + (4 * S + kg) * 16);
+            wl[S] = *reinterpret_cast<const gdm_u32x4*>(r + (8 + 4 * S + kg) * 16);
         }
     }
     // operand rows: thread = (pixel, 8-channel group), lanes = consecutive pixels; loads without control flow
@@ -465,8 +461,8 @@ __global__ __launch_bounds__(256, 4) void conv64_gather_add_act_mfma_kernel(cons
             unsigned hi[4], lo[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) gdm_split2(raw[i][2 * c], raw[i][2 * c + 1], hi[c], lo[c]);
-            *reinterpret_cast<u32x4*>(rows + uf_off(p, grp)) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-            *reinterpret_cast<u32x4*>(rows + uf_off(p, 8 + grp)) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+            *reinterpret_cast<gdm_u32x4*>(rows + uf_off(p, grp)) = gdm_u32x4{hi[0], hi[1], hi[2], hi[3]};
+            *reinterpret_cast<gdm_u32x4*>(rows + uf_off(p, 8 + grp)) = gdm_u32x4{lo[0], lo[1], lo[2], lo[3]};
         }
     }
     // the gathered point term of this lane's pixels and channels, in flight during the products
@@ -492,17 +488,16 @@ __global__ __launch_bounds__(256, 4) void conv64_gather_add_act_mfma_kernel(cons
         sh[r] = shift[c0 + r];
     }
     __syncthreads();
-    typedef __attribute__((ext_vector_type(4))) float f32x4w;
-    f32x4w acc[4];
+    gdm_f32x4 acc[4];
 #pragma unroll
     for (int pb = 0; pb < 4; ++pb) {
-        acc[pb] = f32x4w{0.f, 0.f, 0.f, 0.f};
+        acc[pb] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int S = 0; S < 2; ++S) {
-            const bf16x8 xh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rows + uf_off(16 * pb + l16, 4 * S + kg)));
-            const bf16x8 xl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rows + uf_off(16 * pb + l16, 8 + 4 * S + kg)));
-            const bf16x8 ah = __builtin_bit_cast(bf16x8, wh[S]);
-            const bf16x8 al = __builtin_bit_cast(bf16x8, wl[S]);
+            const gdm_bf16x8 xh = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(rows + uf_off(16 * pb + l16, 4 * S + kg)));
+            const gdm_bf16x8 xl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(rows + uf_off(16 * pb + l16, 8 + 4 * S + kg)));
+            const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, wh[S]);
+            const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, wl[S]);
             acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl, acc[pb], 0, 0, 0);
             acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, acc[pb], 0, 0, 0);
             acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, acc[pb], 0, 0, 0);
@@ -574,13 +569,13 @@ __global__ __launch_bounds__(256, 4) void conv64_gather_add_final_kernel(const f
     const int l16 = lane & 15, kg = lane >> 4;
     const int b = blockIdx.y, j0 = blockIdx.x * CG_P;
     const float* xb = x + (long)b * UF_C * m;
-    u32x4 wh[2], wl[2];
+    gdm_u32x4 wh[2], wl[2];
     {
         const unsigned char* r = wpk + (long)(16 * wave + l16) * UF_ROWB;
 #pragma unroll
         for (int S = 0; S < 2; ++S) {
-            wh[S] = *reinterpret_cast<const u32x4*>(r + (4 * S + kg) * 16);
-            wl[S] = *reinterpret_cast<const u32x4*>(r + (8 + 4 * S + kg) * 16);
+            wh[S] = *reinterpret_cast<const gdm_u32x4*>(r + (4 * S + kg) * 16);
+            wl[S] = *reinterpret_cast<const gdm_u32x4*>(r + (8 + 4 * S + kg) * 16);
         }
     }
     {
@@ -600,8 +595,8 @@ __global__ __launch_bounds__(256, 4) void conv64_gather_add_final_kernel(const f
             unsigned hi[4], lo[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) gdm_split2(raw[i][2 * c], raw[i][2 * c + 1], hi[c], lo[c]);
-            *reinterpret_cast<u32x4*>(rows + uf_off(p, grp)) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-            *reinterpret_cast<u32x4*>(rows + uf_off(p, 8 + grp)) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+            *reinterpret_cast<gdm_u32x4*>(rows + uf_off(p, grp)) = gdm_u32x4{hi[0], hi[1], hi[2], hi[3]};
+            *reinterpret_cast<gdm_u32x4*>(rows + uf_off(p, 8 + grp)) = gdm_u32x4{lo[0], lo[1], lo[2], lo[3]};
         }
     }
     const int c0 = 16 * wave + 4 * kg;
@@ -621,17 +616,16 @@ __global__ __launch_bounds__(256, 4) void conv64_gather_add_final_kernel(const f
         sh[r] = shift[c0 + r];
     }
     __syncthreads();
-    typedef __attribute__((ext_vector_type(4))) float f32x4w;
-    f32x4w acc[4];
+    gdm_f32x4 acc[4];
 #pragma unroll
     for (int pb = 0; pb < 4; ++pb) {
-        acc[pb] = f32x4w{0.f, 0.f, 0.f, 0.f};
+        acc[pb] = gdm_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int S = 0; S < 2; ++S) {
-            const bf16x8 xh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rows + uf_off(16 * pb + l16, 4 * S + kg)));
-            const bf16x8 xl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rows + uf_off(16 * pb + l16, 8 + 4 * S + kg)));
-            const bf16x8 ah = __builtin_bit_cast(bf16x8, wh[S]);
-            const bf16x8 al = __builtin_bit_cast(bf16x8, wl[S]);
+            const gdm_bf16x8 xh = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(rows + uf_off(16 * pb + l16, 4 * S + kg)));
+            const gdm_bf16x8 xl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(rows + uf_off(16 * pb + l16, 8 + 4 * S + kg)));
+            const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, wh[S]);
+            const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, wl[S]);
             acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl, acc[pb], 0, 0, 0);
             acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh, acc[pb], 0, 0, 0);
             acc[pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh, acc[pb], 0, 0, 0);
@@ -728,18 +722,13 @@ extern "C" int gdm_upconv_fused64_hip(const float* x, const void* wpk, const flo
         // worst-case source window of a tile edge: (edge + 1) output steps of size r, + the +1 neighbour, + rounding
         GDM_CHECK_ARG((int)(rh * (UT_TY + 1)) + 3 <= UT_PH && (int)(rw * (UT_TX + 1)) + 3 <= UT_PWV,
                       "gdm_upconv_fused64_hip: scale factors %g x %g need a source patch larger than %dx%d", rh, rw, UT_PH, UT_PWV);
-        static bool attr_t = false;
-        if (!attr_t) {
-            (void)hipFuncSetAttribute((const void*)upconv_tile64_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, UT_LDS);
-            (void)hipFuncSetAttribute((const void*)upconv_tile64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, UT_LDS);
-            (void)hipFuncSetAttribute((const void*)upconv_tile64_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, UT_LDS);
-            attr_t = true;
-        }
         dim3 gt(gdm_cdiv(OW, UT_TX), gdm_cdiv(OH, UT_TY * UT_NT), B);
         GDM_CHECK_ARG(gt.y <= 65535, "gdm_upconv_fused64_hip: OH=%d too large", OH);
-        if (act == 0) hipLaunchKernelGGL(upconv_tile64_kernel<0>, gt, dim3(256), UT_LDS, s, x, (const unsigned char*)wpk, scale, shift, H, W, OH, OW, rh, rw, slope, out);
-        else if (act == 1) hipLaunchKernelGGL(upconv_tile64_kernel<1>, gt, dim3(256), UT_LDS, s, x, (const unsigned char*)wpk, scale, shift, H, W, OH, OW, rh, rw, slope, out);
-        else hipLaunchKernelGGL(upconv_tile64_kernel<2>, gt, dim3(256), UT_LDS, s, x, (const unsigned char*)wpk, scale, shift, H, W, OH, OW, rh, rw, slope, out);
+        gdm_dispatch_int<3>(act, [&](auto A) {
+            constexpr auto kernel = upconv_tile64_kernel<decltype(A)::value>;
+            gdm_allow_lds<kernel>(UT_LDS);
+            hipLaunchKernelGGL(kernel, gt, dim3(256), UT_LDS, s, x, (const unsigned char*)wpk, scale, shift, H, W, OH, OW, rh, rw, slope, out);
+        });
         return gdm_launch_status("upconv_tile64_kernel");
     }
 }
@@ -761,9 +750,10 @@ extern "C" int gdm_upconv_final_points_hip(const float* xpm, const int32_t* choo
     const float rh = uf_scale_ac(H, OH), rw = uf_scale_ac(W, OW);
     dim3 grid(gdm_cdiv(N, FP_P), B);
     hipStream_t s = (hipStream_t)stream;
-#define FPK(A) hipLaunchKernelGGL(upconv_final_points_kernel<A>, grid, dim3(256), 0, s, xpm, choose, (const unsigned char*)wpk, scale, shift, (const unsigned char*)wfpk, fbias, H, W, OH, OW, N, rh, rw, slope, out)
-    if (act == 0) FPK(0); else if (act == 1) FPK(1); else FPK(2);
-#undef FPK
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        hipLaunchKernelGGL(upconv_final_points_kernel<decltype(A)::value>, grid, dim3(256), 0, s, xpm, choose, (const unsigned char*)wpk, scale, shift,
+                           (const unsigned char*)wfpk, fbias, H, W, OH, OW, N, rh, rw, slope, out);
+    });
     return gdm_launch_status("upconv_final_points_kernel");
 }
 
@@ -778,12 +768,14 @@ extern "C" int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* w
     unsigned char* ypk8 = (unsigned char*)ypk;
     dim3 grid(gdm_cdiv(m, CG_P), B);
     hipStream_t s = (hipStream_t)stream;
-#define CGM(A, P, T) hipLaunchKernelGGL((conv64_gather_add_act_mfma_kernel<A, P, T>), grid, dim3(256), 0, s, x, (const unsigned char*)wpk, t, idx, scale, shift, n, (int)m, slope, y, ypk8, W)
-#define CGA(A) do { if (pixel_major) { if (t_point_major) CGM(A, true, true); else CGM(A, true, false); } \
-                    else { if (t_point_major) CGM(A, false, true); else CGM(A, false, false); } } while (0)
-    if (act == 0) CGA(0); else if (act == 1) CGA(1); else CGA(2);
-#undef CGA
-#undef CGM
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        gdm_dispatch_bool(pixel_major != 0, [&](auto P) {
+            gdm_dispatch_bool(t_point_major != 0, [&](auto T) {
+                hipLaunchKernelGGL((conv64_gather_add_act_mfma_kernel<decltype(A)::value, decltype(P)::value, decltype(T)::value>), grid, dim3(256), 0, s,
+                                   x, (const unsigned char*)wpk, t, idx, scale, shift, n, (int)m, slope, y, ypk8, W);
+            });
+        });
+    });
     return gdm_launch_status("conv64_gather_add_act_mfma_kernel");
 }
 
@@ -795,8 +787,9 @@ extern "C" int gdm_conv64_gather_add_final_hip(const float* x, const void* wpk, 
     GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && m <= 0x7fffffffL && act >= 0 && act <= 2, "gdm_conv64_gather_add_final_hip: bad shape");
     dim3 grid(gdm_cdiv(m, CG_P), B);
     hipStream_t s = (hipStream_t)stream;
-#define CGF(A) hipLaunchKernelGGL(conv64_gather_add_final_kernel<A>, grid, dim3(256), 0, s, x, (const unsigned char*)wpk, t, idx, scale, shift, n, (int)m, slope, wft, fbias, out)
-    if (act == 0) CGF(0); else if (act == 1) CGF(1); else CGF(2);
-#undef CGF
+    gdm_dispatch_int<3>(act, [&](auto A) {
+        hipLaunchKernelGGL(conv64_gather_add_final_kernel<decltype(A)::value>, grid, dim3(256), 0, s, x, (const unsigned char*)wpk, t, idx, scale, shift,
+                           n, (int)m, slope, wft, fbias, out);
+    });
     return gdm_launch_status("conv64_gather_add_final_kernel");
 }

@@ -124,9 +124,6 @@ __global__ __launch_bounds__(256) void wgrad_pack_x1_kernel(const float* __restr
 // TM x TN tiles of 16 x 16.  A workgroup = 4 waves = 4 interleaved pixel slices of one (K split, tile block); the waves' tiles are
 // added through LDS in a fixed order and written as one partial product [split][Cout][Cin] (the caller adds the splits).
 // bias (optional) = row sums of go, from the same loads: partial [split][Cout], written by the workgroups of tile column 0.
-typedef __attribute__((ext_vector_type(8))) __bf16 wg_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float wg_f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned wg_u32x4;
 
 // TM x TN = 16 x 16 tiles per wave (<= 2 x 2: 110 registers, four waves per SIMD -- the kernel lives on bytes in flight), WM x WN = waves
 // side by side on the workgroup's (16 TM WM) x (16 TN WN) block of dW, the remaining 4 / (WM WN) waves = interleaved pixel slices.
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(const float* __restri
     for (int m = 0; m < TM; ++m) rowa[m] = min((tm0 + m) * 16 + l16, Cout - 1);
 #pragma unroll
     for (int n = 0; n < TN; ++n) rowb[n] = min((tn0 + n) * 16 + l16, Cin - 1);
-    wg_f32x4 acc[TM][TN];
+    gdm_f32x4 acc[TM][TN];
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -181,13 +178,13 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(const float* __restri
             f.b[n][0] = r[0]; f.b[n][1] = r[1];
         }
     };
-    auto split8 = [](const float4& a, const float4& b, wg_u32x4& hi, wg_u32x4& lo) {
+    auto split8 = [](const float4& a, const float4& b, gdm_u32x4& hi, gdm_u32x4& lo) {
         unsigned h0, h1, h2, h3, l0, l1, l2, l3;
         gdm_split2(a.x, a.y, h0, l0); gdm_split2(a.z, a.w, h1, l1); gdm_split2(b.x, b.y, h2, l2); gdm_split2(b.z, b.w, h3, l3);
-        hi = wg_u32x4{h0, h1, h2, h3}; lo = wg_u32x4{l0, l1, l2, l3};
+        hi = gdm_u32x4{h0, h1, h2, h3}; lo = gdm_u32x4{l0, l1, l2, l3};
     };
     auto compute = [&](const Frags& f) {
-        wg_u32x4 ah[TM], al[TM], bh[TN], bl[TN];
+        gdm_u32x4 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
         for (int m = 0; m < TM; ++m) {
             split8(f.a[m][0], f.a[m][1], ah[m], al[m]);
@@ -200,10 +197,10 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(const float* __restri
         for (int m = 0; m < TM; ++m)
 #pragma unroll
             for (int n = 0; n < TN; ++n) {
-                wg_f32x4 c = acc[m][n];
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wg_bf16x8, ah[m]), __builtin_bit_cast(wg_bf16x8, bl[n]), c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wg_bf16x8, al[m]), __builtin_bit_cast(wg_bf16x8, bh[n]), c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wg_bf16x8, ah[m]), __builtin_bit_cast(wg_bf16x8, bh[n]), c, 0, 0, 0);
+                gdm_f32x4 c = acc[m][n];
+                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gdm_bf16x8, ah[m]), __builtin_bit_cast(gdm_bf16x8, bl[n]), c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gdm_bf16x8, al[m]), __builtin_bit_cast(gdm_bf16x8, bh[n]), c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gdm_bf16x8, ah[m]), __builtin_bit_cast(gdm_bf16x8, bh[n]), c, 0, 0, 0);
                 acc[m][n] = c;
             }
     };
