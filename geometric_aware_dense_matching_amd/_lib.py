@@ -74,6 +74,9 @@ SIGNATURES = {
     "gdm_match_pack_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "gdm_match_pack2_hip": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "gdm_match_packed_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdm_match_soft_partial_bytes": (_sz, [_i, _i]),
+    "gdm_match_soft_packed_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdm_match_score_hip": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "gdm_seg_mask_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "gdm_spline_aggregate_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "gdm_spline_aggregate_bwd_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -111,6 +114,8 @@ SIGNATURES = {
     "gdm_lfa_stage_hip": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _f, _vp, _vp]),
     "gdm_kabsch_stats_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "gdm_kabsch_solve_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "gdm_kabsch_stats_w_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gdm_kabsch_solve_w_hip": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "gdm_ransac_workspace_bytes": (_sz, [_i, _i, _i]),
     "gdm_ransac_pose_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, ctypes.c_double, ctypes.c_uint32, _i,
                                  _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

@@ -706,6 +706,8 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_kernel(const unsigned c
     }
 }
 
+// GUARD: rows past R are not written (the pipelined kernels run only with R a multiple of the row block and need no guard)
+template <bool GUARD = false>
 __device__ __forceinline__ void finalize_rows(const float (&best)[16], const int (&bidx)[16], int lane, int h, int row0, int R,
                                               int panel, float* __restrict__ pval, int32_t* __restrict__ pidx)
 {
@@ -782,6 +784,7 @@ __device__ __forceinline__ void finalize_rows(const float (&best)[16], const int
     if ((lane & 16) == 0) {
         const int reg = ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3);
         const int grow = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        if (GUARD && grow >= R) return;
         pval[(long)panel * R + grow] = v1;
         pidx[(long)panel * R + grow] = i1;
     }
@@ -937,6 +940,218 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_sim_kernel(const unsign
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// soft assignment: v2's panel kernel with log-sum-exp and expected-coordinate accumulation in the epilogue
+// ------------------------------------------------------------------------------------------
+// Per scene row i, over the M real columns j (include/gdm.h gdm_match_soft_packed_hip):
+//   Z_i = sum_j exp(gamma (sim_ij - 1)),  S_i = sum_j exp(gamma (sim_ij - 1)) xyz_j;   lse = gamma + log Z, soft_xyz = S / Z.
+// Cosines are <= 1 and gamma <= 40, so with the fixed shift 1 every term lies in [e^-80, ~1]: no running maximum, no rescaling, and
+// the partial sums of the panels merge by addition.  Same operand loads, same MFMA sequence and same arg-max scan as
+// match_panel_kernel, so best_idx / best_sim are the hard path's bit for bit; that kernel's code is deliberately left untouched (its
+// instances compile to the same instructions as before), so the product block is restated here.
+// Layout as v2: lane = column, 16 rows per lane.  The four accumulators take 64 VGPRs per lane; they are paid for with v2's
+// next-row-block operand prefetch (64 VGPRs), whose latency the SIMD's partner wave covers.  The panel's xyz (3 KiB) sits in LDS
+// behind the descriptor panel.  Per row block a wave sums its 16 x 4 accumulators across the 32 lanes of each half-wave by the
+// same halving butterfly as the arg-max (a fixed order: two launches are bit-identical) and writes one (Z, Sx, Sy, Sz) per
+// (panel, row); soft_merge_kernel adds the panels in ascending order.  No atomics.
+constexpr int SOFT_LDS_BYTES = PANEL_BYTES + PANEL_COLS * 3 * (int)sizeof(float);
+
+// Packed fp32 arithmetic must not read a register in the two wait states behind the wait that retires its LDS read (ADVICE.md
+// item 1, tools/scan_lds_pk_hazard.py): retire the reads and spend the two states here, once per 64-column block / butterfly step.
+#define GDM_LDS_SETTLE(...) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 1" : __VA_ARGS__)
+
+// one halving step of the row butterfly for sums: the lane keeps the upper (up) or lower n of its 2n rows and adds the partner's
+template <int n>
+__device__ __forceinline__ void halve_sum(const float (&in)[2 * n], float (&out)[n], bool up, int mask)
+{
+    float ov[n];
+#pragma unroll
+    for (int i = 0; i < n; ++i) ov[i] = __shfl_xor(up ? in[i] : in[i + n], mask, 64);
+    if constexpr (n == 8) GDM_LDS_SETTLE("+v"(ov[0]), "+v"(ov[1]), "+v"(ov[2]), "+v"(ov[3]), "+v"(ov[4]), "+v"(ov[5]), "+v"(ov[6]), "+v"(ov[7]));
+    else if constexpr (n == 4) GDM_LDS_SETTLE("+v"(ov[0]), "+v"(ov[1]), "+v"(ov[2]), "+v"(ov[3]));
+    else if constexpr (n == 2) GDM_LDS_SETTLE("+v"(ov[0]), "+v"(ov[1]));
+    else GDM_LDS_SETTLE("+v"(ov[0]));
+#pragma unroll
+    for (int i = 0; i < n; ++i) out[i] = (up ? in[i + n] : in[i]) + ov[i];
+}
+
+// sum over the 32 lanes of a half-wave of each of the lane's 16 rows; lanes with (lane & 16) == 0 return row
+// reg = 8*b0 + 4*b1 + 2*b2 + b3 of their lane bits (the row finalize_rows leaves there)
+__device__ __forceinline__ float row_sum16(const float (&a)[16], int lane)
+{
+    float a8[8], a4[4], a2[2], a1[1];
+    halve_sum<8>(a, a8, lane & 1, 1);
+    halve_sum<4>(a8, a4, lane & 2, 2);
+    halve_sum<2>(a4, a2, lane & 4, 4);
+    halve_sum<1>(a2, a1, lane & 8, 8);
+    float o = __shfl_xor(a1[0], 16, 64);
+    GDM_LDS_SETTLE("+v"(o));
+    return a1[0] + o;
+}
+
+template <int PREC>
+__global__ __launch_bounds__(V2_THREADS) void match_panel_soft_kernel(const unsigned char* __restrict__ apk,
+                                                                       const unsigned char* __restrict__ bpk,
+                                                                       const float* __restrict__ xyz,     // [M, 3]
+                                                                       int R, int M, int G, float k2,     // k2 = gamma log2(e)
+                                                                       float* __restrict__ pval,          // [panels, R]
+                                                                       int32_t* __restrict__ pidx,
+                                                                       float4* __restrict__ psum)         // [panels, R] (Z, Sx, Sy, Sz)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // SOFT_LDS_BYTES
+    float* xs = reinterpret_cast<float*>(smem + PANEL_BYTES);              // [PANEL_COLS][3]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int lr = lane & 31;
+    const int h = lane >> 5;
+    const int g = blockIdx.x % G;
+    const int panel = blockIdx.x / G;
+    const int col0 = panel * PANEL_COLS;
+    const int ncols = min(PANEL_COLS, M - col0);
+
+#pragma unroll 4
+    for (int i = 0; i < 16; ++i) {
+        const int gi = i * V2_THREADS + tid;
+        const int col = gi >> 5, ch = gi & 31;
+        const int gc = min(col0 + col, M - 1);
+        const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)gc * ROW_BYTES + ch * 16);
+        *reinterpret_cast<gdm_u32x4*>(smem + lds_chunk_off(col, ch)) = v;
+    }
+    for (int i = tid; i < 3 * PANEL_COLS; i += V2_THREADS) {
+        const int col = i / 3;
+        xs[i] = xyz[(long)min(col0 + col, M - 1) * 3 + (i - 3 * col)];
+    }
+    __syncthreads();
+
+    const int nrb = (R + V2_ROWS - 1) / V2_ROWS;
+    for (int rb = g; rb < nrb; rb += G) {
+        gdm_u32x4 areg[16];
+        const int row0 = rb * V2_ROWS + wave * 32;
+        load_a_rows<PREC>(apk, row0 + lr, R, h, areg);
+
+        float best[16], z[16], sx[16], sy[16], sz[16];
+        int bidx[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            best[i] = -INFINITY;
+            bidx[i] = 0;
+            z[i] = sx[i] = sy[i] = sz[i] = 0.f;
+        }
+
+#pragma unroll 1
+        for (int cp = 0; cp < PANEL_COLS / 64; ++cp) {
+            gdm_f32x16 acc0, acc1;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                acc0[i] = 0.f;
+                acc1[i] = 0.f;
+            }
+            const int c0 = cp * 64 + lr, c1 = c0 + 32;
+            if (PREC == GDM_MATCH_BF16X3) {
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const gdm_bf16x8 bh0 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 2 * s + h)));
+                    const gdm_bf16x8 bl0 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 + 2 * s + h)));
+                    const gdm_bf16x8 bh1 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 2 * s + h)));
+                    const gdm_bf16x8 bl1 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 16 + 2 * s + h)));
+                    const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
+                    const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
+                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl0, acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl1, acc1, 0, 0, 0);
+                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh0, acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh1, acc1, 0, 0, 0);
+                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh0, acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh1, acc1, 0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const gdm_u32x4 b0 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 * h + i));
+                    const gdm_u32x4 b1 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 16 * h + i));
+                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(b0.x), acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(b1.x), acc1, 0, 0, 0);
+                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(b0.y), acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(b1.y), acc1, 0, 0, 0);
+                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].z), __uint_as_float(b0.z), acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].z), __uint_as_float(b1.z), acc1, 0, 0, 0);
+                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].w), __uint_as_float(b0.w), acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].w), __uint_as_float(b1.w), acc1, 0, 0, 0);
+                }
+            }
+            const int gc0 = col0 + c0, gc1 = col0 + c1;
+            const bool ok0 = c0 < ncols, ok1 = c1 < ncols;
+            float x0 = xs[3 * c0], y0 = xs[3 * c0 + 1], z0 = xs[3 * c0 + 2];
+            float x1 = xs[3 * c1], y1 = xs[3 * c1 + 1], z1 = xs[3 * c1 + 2];
+            GDM_LDS_SETTLE("+v"(x0), "+v"(y0), "+v"(z0), "+v"(x1), "+v"(y1), "+v"(z1));
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const float v0 = acc0[reg], v1 = acc1[reg];
+                if (ok0 && v0 > best[reg]) {
+                    best[reg] = v0;
+                    bidx[reg] = gc0;
+                }
+                if (ok1 && v1 > best[reg]) {
+                    best[reg] = v1;
+                    bidx[reg] = gc1;
+                }
+                // a padding column of the last panel weighs nothing
+                const float w0 = ok0 ? __builtin_amdgcn_exp2f(__builtin_fmaf(v0, k2, -k2)) : 0.f;
+                const float w1 = ok1 ? __builtin_amdgcn_exp2f(__builtin_fmaf(v1, k2, -k2)) : 0.f;
+                z[reg] = (z[reg] + w0) + w1;
+                sx[reg] = __builtin_fmaf(w1, x1, __builtin_fmaf(w0, x0, sx[reg]));
+                sy[reg] = __builtin_fmaf(w1, y1, __builtin_fmaf(w0, y0, sy[reg]));
+                sz[reg] = __builtin_fmaf(w1, z1, __builtin_fmaf(w0, z0, sz[reg]));
+            }
+        }
+
+        finalize_rows<true>(best, bidx, lane, h, row0, R, panel, pval, pidx);
+        const float rz = row_sum16(z, lane), rx = row_sum16(sx, lane), ry = row_sum16(sy, lane), rw = row_sum16(sz, lane);
+        if ((lane & 16) == 0) {
+            const int reg = ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3);
+            const int grow = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            if (grow < R) psum[(long)panel * R + grow] = make_float4(rz, rx, ry, rw);
+        }
+    }
+}
+
+// panels in ascending order: (max, first arg-max) as merge_splits_kernel; Z and S by addition; then the three outputs, with the
+// logarithm and the divisions in fp64 so that they add nothing to the error of the fp32 sums.  The numerator of conf is the best
+// column's own term of Z, recomputed by the same two instructions from the same bits: every fp32 addition of non-negative terms
+// is monotone, so Z >= that term (>= twice it when the column has an exact duplicate) and conf stays in (0, 1] (<= 0.5)
+__global__ __launch_bounds__(256) void soft_merge_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
+                                                         const float4* __restrict__ psum, int panels, int R, float gamma, float k2,
+                                                         float* __restrict__ oval, int32_t* __restrict__ oidx, float* __restrict__ lse,
+                                                         float* __restrict__ conf, float* __restrict__ soft)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    float v = pval[r];
+    int ix = pidx[r];
+    float4 s = psum[r];
+    for (int p = 1; p < panels; ++p) {
+        const float ov = pval[(long)p * R + r];
+        if (ov > v) {
+            v = ov;
+            ix = pidx[(long)p * R + r];
+        }
+        const float4 o = psum[(long)p * R + r];
+        s.x += o.x;
+        s.y += o.y;
+        s.z += o.z;
+        s.w += o.w;
+    }
+    oval[r] = v;
+    oidx[r] = ix;
+    const double Z = (double)s.x, gm = (double)gamma;
+    lse[r] = (float)(gm + log(Z));
+    conf[r] = (float)((double)__builtin_amdgcn_exp2f(__builtin_fmaf(v, k2, -k2)) / Z);
+    soft[3L * r] = (float)((double)s.y / Z);
+    soft[3L * r + 1] = (float)((double)s.z / Z);
+    soft[3L * r + 2] = (float)((double)s.w / Z);
+}
+
 __global__ __launch_bounds__(256) void merge_splits_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
                                                            int splits, int R, float* __restrict__ oval, int32_t* __restrict__ oidx)
 {
@@ -978,6 +1193,35 @@ int match_kernel_version()
     if (e && e[0] == '1') return 1;
     if (e && e[0] == '2') return 2;
     return 3;
+}
+
+// score[b] = mean of conf over the points with mask != 0 (0 where there is none): one workgroup per crop, fp64, fixed order
+__global__ __launch_bounds__(256) void match_score_kernel(const float* __restrict__ conf, const uint8_t* __restrict__ mask, int N,
+                                                          float* __restrict__ score)
+{
+    __shared__ double red[4];
+    __shared__ int cred[4];
+    const int b = blockIdx.x;
+    double s = 0.0;
+    int c = 0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        if (!mask[(long)b * N + i]) continue;
+        s += (double)conf[(long)b * N + i];
+        c += 1;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, 64);
+        c += __shfl_xor(c, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = s;
+        cred[threadIdx.x >> 6] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int n = cred[0] + cred[1] + cred[2] + cred[3];
+        score[b] = n > 0 ? (float)(((red[0] + red[1]) + (red[2] + red[3])) / (double)n) : 0.f;
+    }
 }
 
 } // namespace
@@ -1103,6 +1347,63 @@ extern "C" int gdm_match_packed_hip(const void* scene_rows, const void* model_ro
         rc = gdm_launch_status("merge_splits_kernel");
     }
     return rc;
+}
+
+extern "C" size_t gdm_match_soft_partial_bytes(int B, int N)
+{
+    if (B < 1 || N < 1) return 0;
+    return gdm_match_partial_bytes(B, N) + align256(64 * (size_t)B * N * sizeof(float4));
+}
+
+extern "C" int gdm_match_soft_packed_hip(const void* scene_rows, const void* model_rows, const float* model_xyz, int R, int M,
+                                         int precision, float gamma, int32_t* best_idx, float* best_sim, float* lse, float* conf,
+                                         float* soft_xyz, void* partial, size_t partial_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    GDM_CHECK_ARG(scene_rows && model_rows && model_xyz && best_idx && best_sim && lse && conf && soft_xyz && partial,
+                  "gdm_match_soft_packed_hip: NULL pointer");
+    GDM_CHECK_ARG(R >= 1 && M >= 1, "gdm_match_soft_packed_hip: bad shape R=%d M=%d", R, M);
+    GDM_CHECK_ARG(M <= GDM_MATCH_SOFT_MAX_M, "gdm_match_soft_packed_hip: M=%d, the soft kernel covers M <= %d", M, GDM_MATCH_SOFT_MAX_M);
+    GDM_CHECK_ARG(precision == GDM_MATCH_BF16X3 || precision == GDM_MATCH_F32, "gdm_match_soft_packed_hip: precision=%d", precision);
+    GDM_CHECK_ARG(gamma > 0.f && gamma <= GDM_MATCH_SOFT_MAX_GAMMA, "gdm_match_soft_packed_hip: gamma=%g not in (0, %g]", (double)gamma,
+                  (double)GDM_MATCH_SOFT_MAX_GAMMA);                       // a NaN fails both comparisons
+    GDM_CHECK_ARG(((uintptr_t)partial & 15) == 0, "gdm_match_soft_packed_hip: partial must be 16-byte aligned");
+    const size_t half = align256(64 * (size_t)R * sizeof(float));
+    const size_t need = 2 * half + align256(64 * (size_t)R * sizeof(float4));
+    if (partial_bytes < need) {
+        gdm_set_error("gdm_match_soft_packed_hip: partial workspace %zu < %zu bytes", partial_bytes, need);
+        return GDM_ENOMEM;
+    }
+    static_assert(GDM_MATCH_SOFT_MAX_M == 64 * PANEL_COLS, "the partial workspace holds 64 panels");
+    float* pval = (float*)partial;
+    int32_t* pidx = (int32_t*)((unsigned char*)partial + half);
+    float4* psum = (float4*)((unsigned char*)partial + 2 * half);
+    const int panels = gdm_cdiv(M, PANEL_COLS);
+    const int nrb = gdm_cdiv(R, V2_ROWS);
+    int G = 512 / panels;                                       // as v2: one workgroup per CU, two rounds
+    if (G < 1) G = 1;
+    if (G > nrb) G = nrb;
+    if (G >= 8) G &= ~7;
+    const float k2 = gamma * 1.44269504088896340736f;
+    gdm_dispatch_int<2>(precision, [&](auto P) {
+        constexpr auto kernel = match_panel_soft_kernel<decltype(P)::value>;
+        gdm_allow_lds<kernel>(SOFT_LDS_BYTES);
+        hipLaunchKernelGGL(kernel, dim3(panels * G), dim3(V2_THREADS), SOFT_LDS_BYTES, stream, (const unsigned char*)scene_rows,
+                           (const unsigned char*)model_rows, model_xyz, R, M, G, k2, pval, pidx, psum);
+    });
+    int rc = gdm_launch_status("match_panel_soft_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(soft_merge_kernel, dim3(gdm_cdiv(R, 256)), dim3(256), 0, stream, pval, pidx, psum, panels, R, gamma, k2, best_sim,
+                       best_idx, lse, conf, soft_xyz);
+    return gdm_launch_status("soft_merge_kernel");
+}
+
+extern "C" int gdm_match_score_hip(const float* conf, const uint8_t* mask, int B, int N, float* score, void* stream)
+{
+    GDM_CHECK_ARG(conf && mask && score, "gdm_match_score_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && N >= 1, "gdm_match_score_hip: bad shape B=%d N=%d", B, N);
+    hipLaunchKernelGGL(match_score_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, conf, mask, N, score);
+    return gdm_launch_status("match_score_kernel");
 }
 
 extern "C" int gdm_match_hip(const float* scene, const float* model, int B, int Dd, int N, int M, int precision,

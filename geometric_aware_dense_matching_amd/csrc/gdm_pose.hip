@@ -68,6 +68,82 @@ __global__ __launch_bounds__(64) void kabsch_solve_kernel(const double* __restri
     valid[b] = 1;
 }
 
+// Weighted statistics: [0] = sum w, sum w A, sum w B, sum w A B^T over the points with mask != 0 and a finite weight > 0 (others are
+// skipped); count = the number of such points.  A = target[b, i] when `target` is given, else model_xyz[best_idx].
+__global__ __launch_bounds__(256) void kabsch_stats_w_kernel(const float* __restrict__ scene_xyz, long scene_bstride, int pt_stride,
+                                                             int ch_stride, const float* __restrict__ model_xyz,
+                                                             const int32_t* __restrict__ best_idx, const float* __restrict__ target,
+                                                             const float* __restrict__ weight, const uint8_t* __restrict__ mask,
+                                                             int N, int M, double* __restrict__ out, int32_t* __restrict__ count)
+{
+    __shared__ double red[4][16];
+    __shared__ int cred[4];
+    const int b = blockIdx.x;
+    double acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0;
+    int cnt = 0;
+    const float* sp = scene_xyz + (long)b * scene_bstride;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        if (!mask[(long)b * N + i]) continue;
+        const float wf = weight[(long)b * N + i];
+        if (!(wf > 0.f) || !(wf <= 3.402823466e38f)) continue;          // NaN, inf, zero and negative weights are skipped
+        const double w = wf;
+        double ax, ay, az;
+        if (target) {
+            const float* t = target + ((long)b * N + i) * 3;
+            ax = t[0]; ay = t[1]; az = t[2];
+        } else {
+            int j = best_idx[(long)b * N + i];
+            j = min(max(j, 0), M - 1);
+            ax = model_xyz[3 * j]; ay = model_xyz[3 * j + 1]; az = model_xyz[3 * j + 2];
+        }
+        const double bx = sp[(long)i * pt_stride], by = sp[(long)i * pt_stride + ch_stride], bz = sp[(long)i * pt_stride + 2 * ch_stride];
+        const double wax = w * ax, way = w * ay, waz = w * az;
+        cnt += 1;
+        acc[0] += w;
+        acc[1] += wax; acc[2] += way; acc[3] += waz;
+        acc[4] += w * bx; acc[5] += w * by; acc[6] += w * bz;
+        acc[7] += wax * bx; acc[8] += wax * by; acc[9] += wax * bz;
+        acc[10] += way * bx; acc[11] += way * by; acc[12] += way * bz;
+        acc[13] += waz * bx; acc[14] += waz * by; acc[15] += waz * bz;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        double v = acc[i];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        acc[i] = v;
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) {
+        for (int i = 0; i < 16; ++i) red[threadIdx.x >> 6][i] = acc[i];
+        cred[threadIdx.x >> 6] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) out[(long)b * 16 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if (threadIdx.x == 16) count[b] = cred[0] + cred[1] + cred[2] + cred[3];
+}
+
+// The same fit with n = sum w (the fragment is scale-free in n); valid iff count >= min_points and sum w > 0.
+__global__ __launch_bounds__(64) void kabsch_solve_w_kernel(const double* __restrict__ stats, const int32_t* __restrict__ count, int B,
+                                                            int min_points, float* __restrict__ RT, uint8_t* __restrict__ valid)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const double* st = stats + (long)b * 16;
+    const double n = st[0];
+    float* o = RT + (long)b * 12;
+    if (!(count[b] >= min_points) || !(n > 0.0)) {
+        o[0] = 1.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
+        o[4] = 0.f; o[5] = 1.f; o[6] = 0.f; o[7] = 0.f;
+        o[8] = 0.f; o[9] = 0.f; o[10] = 1.f; o[11] = -1000.f;
+        valid[b] = 0;
+        return;
+    }
+#include "gdm_kabsch_fit.inc"
+    valid[b] = 1;
+}
+
 } // namespace
 
 extern "C" int gdm_kabsch_solve_hip(const double* stats, int B, int min_points, float* RT, uint8_t* valid, void* stream)
@@ -86,4 +162,25 @@ extern "C" int gdm_kabsch_stats_hip(const float* scene_xyz, long scene_bstride, 
     hipLaunchKernelGGL(kabsch_stats_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scene_xyz, scene_bstride, pt_stride, ch_stride,
                        model_xyz, best_idx, mask, N, M, out);
     return gdm_launch_status("kabsch_stats_kernel");
+}
+
+extern "C" int gdm_kabsch_stats_w_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* model_xyz,
+                                      const int32_t* best_idx, const float* target, const float* weight, const uint8_t* mask, int B,
+                                      int N, int M, double* out, int32_t* count, void* stream)
+{
+    GDM_CHECK_ARG(scene_xyz && weight && mask && out && count, "gdm_kabsch_stats_w_hip: NULL pointer");
+    GDM_CHECK_ARG(target || (model_xyz && best_idx), "gdm_kabsch_stats_w_hip: NULL pointer (neither target nor model_xyz + best_idx)");
+    GDM_CHECK_ARG(B >= 1 && N >= 1 && (target || M >= 1), "gdm_kabsch_stats_w_hip: bad shape");
+    hipLaunchKernelGGL(kabsch_stats_w_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scene_xyz, scene_bstride, pt_stride, ch_stride,
+                       model_xyz, best_idx, target, weight, mask, N, M, out, count);
+    return gdm_launch_status("kabsch_stats_w_kernel");
+}
+
+extern "C" int gdm_kabsch_solve_w_hip(const double* stats, const int32_t* count, int B, int min_points, float* RT, uint8_t* valid,
+                                      void* stream)
+{
+    GDM_CHECK_ARG(stats && count && RT && valid, "gdm_kabsch_solve_w_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1, "gdm_kabsch_solve_w_hip: bad shape");
+    hipLaunchKernelGGL(kabsch_solve_w_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, stats, count, B, min_points, RT, valid);
+    return gdm_launch_status("kabsch_solve_w_kernel");
 }

@@ -163,7 +163,7 @@ class RecallTable:
 class BopCsv:
     """The BOP-toolkit result file the reference writes while it walks the predictions (evaluator.py:341,365-373,429-431): header
     `scene_id,im_id,obj_id,score,R,t,time`, one line per predicted instance with R row-major and t in MILLIMETRES, both space
-    separated, score and time -1.  `file_name` is the reference's prediction key "scene/…/im_id" (:366-367)."""
+    separated, time -1 and score -1 unless one is given.  `file_name` is the reference's prediction key "scene/…/im_id" (:366-367)."""
 
     HEADER = "scene_id,im_id,obj_id,score,R,t,time"
 
@@ -178,11 +178,19 @@ class BopCsv:
             scene_id=int(parts[0]), im_id=parts[-1], obj_id=int(obj_id), score=score,
             R=" ".join(map(str, R.flatten().tolist())), t=" ".join(map(str, (t * 1000).flatten().tolist())), time=time))
 
-    def add_batch(self, file_names, obj_id, RT):
-        """RT [n,3,4] (pose.solve_poses / infer.run_multi_object output), metres."""
+    def add_batch(self, file_names, obj_id, RT, scores=None):
+        """RT [n,3,4] (pose.solve_poses / infer.run_multi_object output), metres; scores [n] (the step's `score` with soft matching)
+        are written when given, -1 otherwise."""
         RT = RT.detach().cpu().double().numpy() if torch.is_tensor(RT) else np.asarray(RT, dtype=np.float64)
-        for name, rt in zip(file_names, RT):
-            self.add(name, obj_id, rt[:, :3], rt[:, 3])
+        if scores is None:
+            for name, rt in zip(file_names, RT):
+                self.add(name, obj_id, rt[:, :3], rt[:, 3])
+            return
+        scores = scores.detach().cpu().double().numpy() if torch.is_tensor(scores) else np.asarray(scores, dtype=np.float64)
+        if scores.shape != (len(RT),):
+            raise ValueError("BopCsv.add_batch: %d poses, scores of shape %s" % (len(RT), scores.shape))
+        for name, rt, sc in zip(file_names, RT, scores):
+            self.add(name, obj_id, rt[:, :3], rt[:, 3], score=float(sc))
 
     def write(self, path):
         import os

@@ -12,11 +12,12 @@ from . import frontend, matching, ops, pose, pyramid, settings
 _PREC = {"bf16x3": ops.MATCH_BF16X3, "f32": ops.MATCH_F32, 0: 0, 1: 1}
 
 
-def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf16x3", pose_fit="kabsch", icp_iters=0, pose_opts=None):
+def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf16x3", pose_fit="kabsch", icp_iters=0, pose_opts=None,
+                     match_gamma=None):
     """model_dict: {cls_id: GeoMatch (eval, on the GPU)}; inputs: dict of batched device tensors (loader keys, plus
     `dpt_xyz` when the neighbour pyramid is not already in it); cls_ids: int tensor/list [bs].  pose_fit / icp_iters / pose_opts:
-    pose.estimate_poses (the defaults are the plain Kabsch fit).
-    Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, RT, valid[, icp_iters, icp_resid]])."""
+    pose.estimate_poses (the defaults are the plain Kabsch fit).  match_gamma: soft matching at that temperature (pipeline_step).
+    Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, lse, conf, soft_xyz, score][, RT, valid[, icp_iters, icp_resid]])."""
     cls = torch.as_tensor(cls_ids).cpu().tolist()
     bs = len(cls)
     out = {}
@@ -30,9 +31,12 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
             if getattr(model, "needs_pyramid", True) and "cld_nei_idx0" not in sub:
                 sub.update(pyramid.build_pyramid(pyramid.cloud_from_inputs(sub["cld_rgb_nrm"]), sub["dpt_xyz"]))
             ep = model(sub)
-            res = matching.match_frames(ep, precision=precision)
+            soft = None if match_gamma is None else dict(gamma=match_gamma, model_xyz=model.model_emb.xyz)
+            res = matching.match_frames(ep, precision=precision, soft=soft)
             part = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"].expand(len(sel), -1, -1), mask=res["mask"],
                         best_idx=res["best_idx"], best_sim=res["best_sim"])
+            if soft is not None:
+                part.update(lse=res["lse"], conf=res["conf"], soft_xyz=res["soft_xyz"], score=ops.match_score(res["conf"], res["mask"]))
             if with_pose:
                 part.update(pose.estimate_poses(res, sub["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts))
             for k, v in part.items():
@@ -44,13 +48,17 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
     return {k: torch.cat(v, dim=0).index_select(0, inv) for k, v in out.items()}
 
 
-def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyramid=False, pose_fit="kabsch", icp_iters=0, pose_opts=None):
+def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyramid=False, pose_fit="kabsch", icp_iters=0, pose_opts=None,
+                  match_gamma=None):
     """ONE pass of the hot path over a batch of crops resident on the device: neighbour pyramid (unless `inputs` already carries the
     loader's index arrays) -> GeoMatch.forward (eval) -> seg mask + descriptor packs + N x M arg-max (evaluator.py:78-93) [-> pose].
     Everything is enqueued on the current stream (and, with settings.USE_SIDE_STREAMS, on side streams forked from and joined back to
     it) with no host synchronisation, so the call captures in a hipGraph as it is.  Returns dict(seg, rgbd, mesh, mask, count,
     best_idx, best_sim[, RT, valid[, icp_iters, icp_resid]]) plus the 30 pyramid arrays when keep_pyramid.  The pose stage is
-    pose.estimate_poses(pose_fit, icp_iters, pose_opts): RANSAC and ICP run on the device too, with no host branching."""
+    pose.estimate_poses(pose_fit, icp_iters, pose_opts): RANSAC and ICP run on the device too, with no host branching.
+    match_gamma = None: the arg-max kernel, as ever.  With a temperature the soft kernel takes its place (same best_idx / best_sim)
+    and the outputs gain lse, conf, soft_xyz (include/gdm.h gdm_match_soft_packed_hip) and score f32[B] = the mean of conf over the
+    masked points (0 where none); pose_opts' weights / targets can then use them."""
     prec = _PREC[precision]
     d = dict(inputs)
     pyr = None
@@ -63,8 +71,14 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
         ep = model(d, defer_seg=True)
     B, _, N = ep["rgbd"].shape
     M = ep["mesh"].shape[-1]
-    mask, count, bi, bs = matching.match_tail(ep, B, N, M, prec)
-    out = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=mask, count=count, best_idx=bi, best_sim=bs)
+    if match_gamma is None:
+        mask, count, bi, bs = matching.match_tail(ep, B, N, M, prec)
+        out = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=mask, count=count, best_idx=bi, best_sim=bs)
+    else:
+        mask, count, bi, bs, lse, conf, sxyz = matching.match_tail(ep, B, N, M, prec, soft=dict(gamma=match_gamma,
+                                                                                                  model_xyz=model.model_emb.xyz))
+        out = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=mask, count=count, best_idx=bi, best_sim=bs, lse=lse,
+                   conf=conf, soft_xyz=sxyz, score=ops.match_score(conf, mask))
     if with_pose:
         out.update(pose.estimate_poses(out, d["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts))
     if keep_pyramid and pyr is not None:
@@ -76,7 +90,7 @@ FRAME_KEYS = ("rgb_u8", "depth", "K", "bbox_xyxy", "mask")           # what a `f
 
 
 def frame_step(model, frames, S, n_points, seed=0, depth_fill=None, precision="bf16x3", with_pose=False, keep_pyramid=False,
-               pose_fit="kabsch", icp_iters=0, pose_opts=None):
+               pose_fit="kabsch", icp_iters=0, pose_opts=None, match_gamma=None):
     """From raw frames and detection boxes to the step's outputs: frames = dict(rgb_u8 u8[B,H,W,3], depth f32[B,H,W], K f32[B,3,3],
     bbox_xyxy f32[B,4][, mask u8[B,H,W]]) -> frontend.make_inputs_from_boxes(sampler="hash", build_pyramid=False, train=False) ->
     pipeline_step (which builds the pyramid a model needs).  seed: an int or a one-element int32 device tensor (ops.sample_assemble).
@@ -85,7 +99,7 @@ def frame_step(model, frames, S, n_points, seed=0, depth_fill=None, precision="b
     item = frontend.make_inputs_from_boxes(frames["rgb_u8"], frames["depth"], frames["K"], frames["bbox_xyxy"], S, n_points,
                                            mask=frames.get("mask"), train=False, depth_fill=depth_fill, sampler="hash", seed=seed,
                                            build_pyramid=False)
-    out = pipeline_step(model, item, precision, with_pose, keep_pyramid, pose_fit, icp_iters, pose_opts)
+    out = pipeline_step(model, item, precision, with_pose, keep_pyramid, pose_fit, icp_iters, pose_opts, match_gamma)
     out.update((k, item[k]) for k in ("choose", "cld_rgb_nrm", "n_valid", "center", "scale", "origin_labels") if k in item)
     return out
 
@@ -115,8 +129,10 @@ class GraphedPipeline:
     freed after the decision (keep_both=True keeps both: `replay(form)`)."""
 
     def __init__(self, model, example_inputs, precision="bf16x3", with_pose=True, warmup=3, forked="auto", burst=8,
-                 keep_pyramid=False, capture_error_mode=None, keep_both=False, pose_fit="kabsch", icp_iters=0, pose_opts=None):
+                 keep_pyramid=False, capture_error_mode=None, keep_both=False, pose_fit="kabsch", icp_iters=0, pose_opts=None,
+                 match_gamma=None):
         self.model = model.eval()
+        self.match_gamma = match_gamma
         self.precision, self.with_pose, self.keep_pyramid = precision, with_pose, keep_pyramid
         self.pose_fit, self.icp_iters, self.pose_opts = pose_fit, icp_iters, dict(pose_opts or {})
         self.static_in = {k: v.clone() for k, v in example_inputs.items() if torch.is_tensor(v)}
@@ -162,7 +178,7 @@ class GraphedPipeline:
     # -- construction helpers ---------------------------------------------------------------------------------------------
     def _step(self):
         return pipeline_step(self.model, self.static_in, self.precision, self.with_pose, self.keep_pyramid, self.pose_fit, self.icp_iters,
-                             self.pose_opts)
+                             self.pose_opts, self.match_gamma)
 
     def _eager_reference(self, warmup):
         """Eager single-stream steps on the example inputs (they also fill the per-module caches); the last one's outputs, cloned."""
@@ -239,7 +255,7 @@ class GraphedFramePipeline(GraphedPipeline):
 
     def _step(self):
         return frame_step(self.model, self.static_in, self.S, self.n_points, self.seed, self.depth_fill, self.precision, self.with_pose,
-                          self.keep_pyramid, self.pose_fit, self.icp_iters, self.pose_opts)
+                          self.keep_pyramid, self.pose_fit, self.icp_iters, self.pose_opts, self.match_gamma)
 
     def __call__(self, frames, seed=None):
         """Copies `frames` (and, when given, the seed) into the static buffers, replays the graph, returns the static outputs (valid

@@ -10,6 +10,7 @@ the whole batch is ONE fused HIP launch sequence (normalise+pack, MFMA similarit
 row arg-max, optional split merge) that never writes the matrix; rows of unselected points are
 computed too (the mask is data dependent) and simply ignored by `selected`.
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -17,25 +18,51 @@ from . import ops
 _PREC = {"bf16x3": ops.MATCH_BF16X3, "f32": ops.MATCH_F32, 0: 0, 1: 1}
 
 
-def match_frames(end_points, precision="bf16x3", return_sim=False):
+def _soft_args(soft, who):
+    """soft = None | dict(gamma=..., model_xyz=f32[M,3]) -> (gamma, model_xyz) or None."""
+    if soft is None:
+        return None
+    if set(soft) != {"gamma", "model_xyz"}:
+        raise ValueError("%s: soft must be dict(gamma=..., model_xyz=...), got keys %s" % (who, sorted(soft)))
+    return float(soft["gamma"]), soft["model_xyz"]
+
+
+def match_frames(end_points, precision="bf16x3", return_sim=False, soft=None):
     """end_points: GeoMatch.forward output (seg [B,2,N], rgbd [B,128,N], mesh [1,128,M]).
-    Returns dict(mask u8[B,N], count i32[B], best_idx i32[B,N], best_sim f32[B,N] [, sim f32[B,N,M]])."""
+    Returns dict(mask u8[B,N], count i32[B], best_idx i32[B,N], best_sim f32[B,N] [, sim f32[B,N,M]]).
+    soft = dict(gamma=..., model_xyz=f32[M,3]) takes the soft kernel instead (ops.match_soft: the same best_idx / best_sim) and adds
+    lse f32[B,N], conf f32[B,N], soft_xyz f32[B,N,3]."""
     seg, rgbd, mesh = end_points["seg"], end_points["rgbd"], end_points["mesh"]
+    sa = _soft_args(soft, "match_frames")
     mask, count = ops.seg_mask(seg)
-    out = ops.match(rgbd, mesh[0] if mesh.dim() == 3 else mesh, precision=_PREC[precision], return_sim=return_sim)
-    res = dict(mask=mask, count=count, best_idx=out[0], best_sim=out[1])
+    mesh = mesh[0] if mesh.dim() == 3 else mesh
+    if sa is None:
+        out = ops.match(rgbd, mesh, precision=_PREC[precision], return_sim=return_sim)
+        res = dict(mask=mask, count=count, best_idx=out[0], best_sim=out[1])
+        if return_sim:
+            res["sim"] = out[2]
+        return res
     if return_sim:
-        res["sim"] = out[2]
-    return res
+        raise ValueError("match_frames: return_sim and soft exclude each other (the soft kernel writes no matrix)")
+    bi, bs, lse, conf, sxyz = ops.match_soft(rgbd, mesh, sa[1], _PREC[precision], sa[0])
+    return dict(mask=mask, count=count, best_idx=bi, best_sim=bs, lse=lse, conf=conf, soft_xyz=sxyz)
 
 
-def match_tail(end_points, B, N, M, precision=ops.MATCH_BF16X3):
+def match_tail(end_points, B, N, M, precision=ops.MATCH_BF16X3, soft=None):
     """The step's tail on packed rows (evaluator.py:78-93): seg mask, descriptor packs, N x M arg-max -> (mask, count, best_idx, best_sim).
     With settings.USE_SIDE_STREAMS the mask -- which the arg-max does not read -- is formed on a side stream beside the matching
     kernel, and the model's descriptor rows are taken from `end_points["mesh_rows"]` when GeoMatch.forward packed them inside its
-    mesh fork (same kernels, same operands: same bits)."""
+    mesh fork (same kernels, same operands: same bits).  soft = dict(gamma=..., model_xyz=...): the soft kernel in place of the
+    arg-max kernel, and (lse, conf, soft_xyz) appended to the result."""
     from . import settings
     seg, rgbd, mesh = end_points["seg"], end_points["rgbd"], end_points["mesh"]
+    sa = _soft_args(soft, "match_tail")
+
+    def run(srows, mrows):
+        if sa is None:
+            return ops.match_packed(srows, mrows, B, N, M, precision)
+        return ops.match_soft_packed(srows, mrows, sa[1], B, N, M, precision, sa[0])
+
     forked = settings.USE_SIDE_STREAMS and seg.is_cuda and not torch.is_grad_enabled()
     mrows = end_points.get("mesh_rows") if precision == ops.MATCH_BF16X3 else None
     if mrows is None:
@@ -46,12 +73,35 @@ def match_tail(end_points, B, N, M, precision=ops.MATCH_BF16X3):
         with ops.fork(seg.device, 0) as f:                   # side stream 0: behind the segmentation layers, if they are pending there
             f.use(seg)
             mask, count = ops.seg_mask(seg)
-        bi, bs = ops.match_packed(srows, mrows, B, N, M, precision)
+        m = run(srows, mrows)
         f.join(mask, count, seg)
     else:
         mask, count = ops.seg_mask(seg)
-        bi, bs = ops.match_packed(srows, mrows, B, N, M, precision)
-    return mask, count, bi, bs
+        m = run(srows, mrows)
+    return (mask, count) + tuple(m)
+
+
+def match_soft_numpy(scene, model, model_xyz, gamma):
+    """The soft assignment restated in fp64 (numpy).  scene f32[N,128] raw descriptors (one per row) and model f32[128,M] -- or, in
+    place of the descriptors, scene = a similarity matrix [N,M] and model = None.  From descriptors: rows and columns are normalised
+    (x / max(|x|, 1e-12)) and sim = rows @ columns.  -> dict(best_idx i64[N] (first maximum on ties), best_sim, lse = log sum_j
+    exp(gamma sim_ij), conf = exp(gamma best_sim - lse), soft_xyz [N,3] = softmax(gamma sim) @ model_xyz), all f64."""
+    if model is None:
+        sim = np.asarray(scene, dtype=np.float64)
+    else:
+        a = np.asarray(scene, dtype=np.float64)
+        b = np.asarray(model, dtype=np.float64)
+        a = a / np.maximum(np.linalg.norm(a, axis=1, keepdims=True), 1e-12)
+        b = b / np.maximum(np.linalg.norm(b, axis=0, keepdims=True), 1e-12)
+        sim = a @ b
+    xyz = np.asarray(model_xyz, dtype=np.float64)
+    g = float(gamma)
+    best_idx = sim.argmax(axis=1)                             # numpy returns the first maximum
+    best_sim = sim[np.arange(sim.shape[0]), best_idx]
+    e = np.exp(g * (sim - best_sim[:, None]))                 # <= 1
+    Z = e.sum(axis=1)
+    lse = g * best_sim + np.log(Z)
+    return dict(best_idx=best_idx, best_sim=best_sim, lse=lse, conf=1.0 / Z, soft_xyz=(e @ xyz) / Z[:, None])
 
 
 def selected(res, b):

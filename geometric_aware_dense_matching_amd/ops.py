@@ -2210,6 +2210,55 @@ def match_packed(scene_rows, model_rows, B, N, M, precision=MATCH_BF16X3, return
     return (best_idx, best_sim, sim) if return_sim else (best_idx, best_sim)
 
 
+MATCH_SOFT_MAX_GAMMA = 40.0            # include/gdm.h GDM_MATCH_SOFT_MAX_GAMMA
+MATCH_SOFT_MAX_M = 16384               # include/gdm.h GDM_MATCH_SOFT_MAX_M
+
+
+def match_soft_packed(scene_rows, model_rows, model_xyz, B, N, M, precision=MATCH_BF16X3, gamma=16.0):
+    """match_packed plus the soft assignment at temperature gamma (include/gdm.h gdm_match_soft_packed_hip): model_xyz f32[M,3] ->
+    best_idx i32[B,N], best_sim f32[B,N] (the bits of match_packed), lse f32[B,N], conf f32[B,N], soft_xyz f32[B,N,3].  No [N, M]
+    tensor; 0 < gamma <= 40 and M <= 16384, refused otherwise."""
+    L = _lib.lib()
+    model_xyz = _dev(model_xyz, torch.float32, "model_xyz")
+    if tuple(model_xyz.shape) != (M, 3):
+        raise ValueError("match_soft_packed: model_xyz is %s, expected (%d, 3)" % (tuple(model_xyz.shape), M))
+    dev = scene_rows.device
+    part = _workspace(L.gdm_match_soft_partial_bytes(B, N), dev)
+    best_idx = torch.empty((B, N), dtype=torch.int32, device=dev)
+    best_sim = torch.empty((B, N), dtype=torch.float32, device=dev)
+    lse = torch.empty((B, N), dtype=torch.float32, device=dev)
+    conf = torch.empty((B, N), dtype=torch.float32, device=dev)
+    soft_xyz = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    check(L.gdm_match_soft_packed_hip(scene_rows.data_ptr(), model_rows.data_ptr(), model_xyz.data_ptr(), B * N, M, precision,
+                                      float(gamma), best_idx.data_ptr(), best_sim.data_ptr(), lse.data_ptr(), conf.data_ptr(),
+                                      soft_xyz.data_ptr(), part.data_ptr(), part.numel(), _stream()), "gdm_match_soft_packed_hip")
+    return best_idx, best_sim, lse, conf, soft_xyz
+
+
+def match_soft(scene, model, model_xyz, precision=MATCH_BF16X3, gamma=16.0):
+    """scene f32[B,128,N], model f32[128,M], model_xyz f32[M,3] -> (best_idx, best_sim, lse, conf, soft_xyz): both packs, then
+    match_soft_packed."""
+    scene = _dev(scene, torch.float32, "scene")
+    model = _dev(model, torch.float32, "model")
+    if model.dim() == 3:
+        assert model.shape[0] == 1
+        model = model[0]
+    B, D, N = scene.shape
+    assert model.shape[0] == D
+    srows, mrows = match_pack2(scene, model, precision)
+    return match_soft_packed(srows, mrows, model_xyz, B, N, model.shape[1], precision, gamma)
+
+
+def match_score(conf, mask):
+    """conf f32[B,N], mask u8[B,N] -> score f32[B]: the mean confidence of the masked points, 0 for a crop with none."""
+    conf = _dev(conf, torch.float32, "conf")
+    mask = _dev(mask, torch.uint8, "mask")
+    B, N = conf.shape
+    score = torch.empty((B,), dtype=torch.float32, device=conf.device)
+    check(_lib.lib().gdm_match_score_hip(conf.data_ptr(), mask.data_ptr(), B, N, score.data_ptr(), _stream()), "gdm_match_score_hip")
+    return score
+
+
 def seg_mask(seg):
     """seg f32[B,2,N] -> (mask u8[B,N] = argmax==1, count i32[B])."""
     seg = _dev(seg, torch.float32, "seg")

@@ -31,15 +31,29 @@ def kabsch_stats(res, cld_rgb_nrm, model_xyz):
 
 
 def solve_poses(res, cld_rgb_nrm, model_xyz, min_points=5, method="kabsch", ransac_iters=20, inlier_dist=0.015, fix_percent=0.7,
-                seed=0):
+                seed=0, weights="none", targets="vertex"):
     """-> RT f32[B,3,4] mapping model coordinates to the camera frame, valid bool[B].  Two launches (statistics, fit), no
     host synchronisation.  method="ransac": the reference's RANSAC (ransac_poses) with max_iter = ransac_iters hypotheses,
-    match_err = inlier_dist (m) and fix_percent; `seed` selects the hashed samples."""
+    match_err = inlier_dist (m) and fix_percent; `seed` selects the hashed samples.
+    method="kabsch" only: weights="conf" weighs every pair by res["conf"], targets="soft" pairs the scene point with
+    res["soft_xyz"] instead of its arg-max vertex (both from soft matching, matching.match_frames(soft=...)); either takes the
+    weighted entries (solve_poses_weighted).  The defaults are the unweighted launches."""
+    if weights not in ("none", "conf") or targets not in ("vertex", "soft"):
+        raise ValueError("solve_poses: weights must be 'none' or 'conf' and targets 'vertex' or 'soft', got %r, %r" % (weights, targets))
+    soft = weights != "none" or targets != "vertex"
     if method == "ransac":
+        if soft:
+            raise ValueError("solve_poses: weights=%r / targets=%r are for method='kabsch'; RANSAC keeps the hard pairs" % (weights, targets))
         RT, valid, _, _ = ransac_poses(res, cld_rgb_nrm, model_xyz, ransac_iters, inlier_dist, fix_percent, seed, min_points)
         return RT, valid
     if method != "kabsch":
         raise ValueError("solve_poses: method must be 'kabsch' or 'ransac', got %r" % (method,))
+    if soft:
+        need = [k for k, on in (("conf", weights == "conf"), ("soft_xyz", targets == "soft")) if on and k not in res]
+        if need:
+            raise ValueError("solve_poses: weights=%r / targets=%r need the soft matching outputs %s in res" % (weights, targets, need))
+        w = res["conf"] if weights == "conf" else torch.ones(res["mask"].shape, dtype=torch.float32, device=res["mask"].device)
+        return solve_poses_weighted(res, cld_rgb_nrm, model_xyz, w, res["soft_xyz"] if targets == "soft" else None, min_points)
     st = kabsch_stats(res, cld_rgb_nrm, model_xyz)
     B = st.shape[0]
     RT = torch.empty((B, 3, 4), dtype=torch.float32, device=st.device)
@@ -47,6 +61,61 @@ def solve_poses(res, cld_rgb_nrm, model_xyz, min_points=5, method="kabsch", rans
     check(_lib.lib().gdm_kabsch_solve_hip(st.data_ptr(), B, int(min_points), RT.data_ptr(), valid.data_ptr(), ops._stream()),
           "gdm_kabsch_solve_hip")
     return RT, valid.bool()
+
+
+def kabsch_stats_weighted(res, cld_rgb_nrm, model_xyz, weight, target=None):
+    """The 16 weighted statistics (include/gdm.h gdm_kabsch_stats_w_hip): weight f32[B,N]; the model-side point of a pair is
+    target[b, i] (f32[B,N,3]) when given, else model_xyz[best_idx].  -> stats f64[B,16], count i32[B] (masked points with a finite
+    weight > 0; the others are skipped)."""
+    mask, best_idx = res["mask"], res["best_idx"]
+    B, N = mask.shape
+    cld = ops._dev(cld_rgb_nrm, torch.float32, "cld_rgb_nrm")
+    model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
+    weight = ops._dev(weight, torch.float32, "weight")
+    if tuple(weight.shape) != (B, N):
+        raise ValueError("kabsch_stats_weighted: weight is %s, expected %s" % (tuple(weight.shape), (B, N)))
+    if target is not None:
+        target = ops._dev(target, torch.float32, "target")
+        if tuple(target.shape) != (B, N, 3):
+            raise ValueError("kabsch_stats_weighted: target is %s, expected %s" % (tuple(target.shape), (B, N, 3)))
+    out = torch.empty((B, 16), dtype=torch.float64, device=mask.device)
+    count = torch.empty((B,), dtype=torch.int32, device=mask.device)
+    check(_lib.lib().gdm_kabsch_stats_w_hip(cld.data_ptr(), cld.stride(0), 1, N, model_xyz.data_ptr(), best_idx.data_ptr(),
+                                            None if target is None else target.data_ptr(), weight.data_ptr(), mask.data_ptr(), B, N,
+                                            model_xyz.shape[0], out.data_ptr(), count.data_ptr(), ops._stream()),
+          "gdm_kabsch_stats_w_hip")
+    return out, count
+
+
+def solve_poses_weighted(res, cld_rgb_nrm, model_xyz, weight, target=None, min_points=5):
+    """The weighted least-squares fit: kabsch_stats_weighted, then the fit with n = sum w.  valid = at least min_points usable pairs
+    and sum w > 0, else the sentinel pose.  -> RT f32[B,3,4], valid bool[B].  Two launches, no host synchronisation."""
+    st, count = kabsch_stats_weighted(res, cld_rgb_nrm, model_xyz, weight, target)
+    B = st.shape[0]
+    RT = torch.empty((B, 3, 4), dtype=torch.float32, device=st.device)
+    valid = torch.empty((B,), dtype=torch.uint8, device=st.device)
+    check(_lib.lib().gdm_kabsch_solve_w_hip(st.data_ptr(), count.data_ptr(), B, int(min_points), RT.data_ptr(), valid.data_ptr(),
+                                            ops._stream()), "gdm_kabsch_solve_w_hip")
+    return RT, valid.bool()
+
+
+def kabsch_weighted_numpy(A, B, w):
+    """fp64 restatement of the weighted fit: A [n,3] model-side points, B [n,3] scene points, w [n] weights >= 0 -> RT [3,4] with
+    B ~ R A + t minimising sum w |R A + t - B|^2 (weighted centroids, SVD of sum w (A - cA)(B - cB)^T, reflection fix as
+    best_fit_transform)."""
+    A = np.asarray(A, dtype=np.float64)
+    B = np.asarray(B, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    sw = w.sum()
+    cA = (w[:, None] * A).sum(0) / sw
+    cB = (w[:, None] * B).sum(0) / sw
+    H = (w[:, None] * (A - cA)).T @ (B - cB)
+    U, _, Vt = np.linalg.svd(H)
+    R = Vt.T @ U.T
+    if np.linalg.det(R) < 0:
+        Vt[2, :] *= -1
+        R = Vt.T @ U.T
+    return np.concatenate([R, (cB - R @ cA)[:, None]], axis=1)
 
 
 def _mix32(x):
@@ -147,19 +216,21 @@ def refine_icp(RT, valid, cld_rgb_nrm, mask, model_xyz, iters=20, tolerance=0.00
 def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, pose_opts=None):
     """The pose stage of the pipeline: solve_poses with `pose_fit` ("kabsch" | "ransac"), then `icp_iters` ICP iterations when > 0.
     pose_opts (optional dict): ransac_iters, ransac_inlier_dist, ransac_fix_percent, seed, icp_tolerance, icp_reject_dist,
-    min_points.  -> dict(RT, valid[, icp_iters, icp_resid])."""
+    min_points, and for pose_fit="kabsch" weights ("none" | "conf") and targets ("vertex" | "soft") (solve_poses; RANSAC and ICP
+    keep the hard pairs).  -> dict(RT, valid[, icp_iters, icp_resid])."""
     o = dict(pose_opts or {})
     unknown = set(o) - {"ransac_iters", "ransac_inlier_dist", "ransac_fix_percent", "seed", "icp_tolerance", "icp_reject_dist",
-                        "min_points"}
+                        "min_points", "weights", "targets"}
     if unknown:
         raise ValueError("estimate_poses: unknown pose_opts %s" % sorted(unknown))
     min_points = o.get("min_points", 5)
     if pose_fit == "kabsch":
-        RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points)
+        RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, weights=o.get("weights", "none"),
+                                targets=o.get("targets", "vertex"))
     else:
         RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, method=pose_fit, ransac_iters=o.get("ransac_iters", 20),
                                 inlier_dist=o.get("ransac_inlier_dist", 0.015), fix_percent=o.get("ransac_fix_percent", 0.7),
-                                seed=o.get("seed", 0))
+                                seed=o.get("seed", 0), weights=o.get("weights", "none"), targets=o.get("targets", "vertex"))
     out = dict(RT=RT, valid=valid)
     if icp_iters > 0:
         out["RT"], out["icp_iters"], out["icp_resid"] = refine_icp(RT, valid, cld_rgb_nrm, res["mask"], model_xyz, icp_iters,

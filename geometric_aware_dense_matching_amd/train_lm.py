@@ -90,6 +90,12 @@ def build_parser():
     p.add_argument("--ransac-iters", dest="ransac_iters", type=int, default=20, help="test: RANSAC hypotheses per crop (max_iter)")
     p.add_argument("--ransac-inlier-dist", dest="ransac_inlier_dist", type=float, default=0.015,
                    help="test: RANSAC inlier distance in metres (match_err)")
+    p.add_argument("--match-gamma", dest="match_gamma", type=float, default=None,
+                   help="test: soft matching at this temperature (0 < G <= 40): per-point confidences, soft vertices and a csv score")
+    p.add_argument("--pose-weights", dest="pose_weights", type=str, default="none", choices=["none", "conf"],
+                   help="test, --pose-fit kabsch: weigh the pairs by the matching confidence (needs --match-gamma)")
+    p.add_argument("--pose-targets", dest="pose_targets", type=str, default="vertex", choices=["vertex", "soft"],
+                   help="test, --pose-fit kabsch: fit to the arg-max vertex or to the expected model coordinate (needs --match-gamma)")
     p.add_argument("--icp-iters", dest="icp_iters", type=int, default=0,
                    help="test: point-to-point ICP iterations after the fit (pvn3d_eval_utils_kpls.py:126-212); 0 = none")
     p.add_argument("--icp-tolerance", dest="icp_tolerance", type=float, default=0.001, help="test: ICP convergence tolerance (m)")
@@ -477,6 +483,16 @@ def test(args):
     pose_kw = dict(pose_fit=args.pose_fit, icp_iters=args.icp_iters,
                    pose_opts=dict(ransac_iters=args.ransac_iters, ransac_inlier_dist=args.ransac_inlier_dist,
                                   icp_tolerance=args.icp_tolerance))
+    match_gamma = getattr(args, "match_gamma", None)
+    soft_pose = (getattr(args, "pose_weights", "none"), getattr(args, "pose_targets", "vertex")) != ("none", "vertex")
+    if soft_pose and match_gamma is None:
+        raise SystemExit("train_lm test: --pose-weights conf / --pose-targets soft need --match-gamma")
+    if soft_pose and args.pose_fit != "kabsch":
+        raise SystemExit("train_lm test: --pose-weights conf / --pose-targets soft go with --pose-fit kabsch (RANSAC keeps the hard pairs)")
+    if soft_pose:
+        pose_kw["pose_opts"].update(weights=args.pose_weights, targets=args.pose_targets)
+    if match_gamma is not None:
+        pose_kw["match_gamma"] = match_gamma
     # evaluator.py:308-463: when the loader carries ground-truth poses (`RT`), every instance's ADD(-S) / re / te / re-projection error
     # is computed on the device per object group and the reference's recall table is printed at the end
     from . import evaluation
@@ -515,6 +531,8 @@ def test(args):
             torch.cuda.synchronize()
             results.append(dict(time=time.perf_counter() - t0, cls_id=cls, count=out["mask"].sum(dim=1).cpu(), best_idx=out["best_idx"].cpu(),
                                 best_sim=out["best_sim"].cpu(), mask=out["mask"].cpu(), RT=out["RT"].cpu(), valid=out["valid"].cpu()))
+            if "score" in out:
+                results[-1].update(score=out["score"].cpu(), conf=out["conf"].cpu())
             if "RT" in cu and cu["RT"].dim() == 3:
                 Kcam = cu["K"] if "K" in cu else torch.from_numpy(synthetic.LM_K).to(device)
                 for cid in sorted(set(cls)):
@@ -540,7 +558,8 @@ def test(args):
             bop_ids_seen = bop_ids_seen and has_ids
             if has_gt and has_ids:
                 for i, cid in enumerate(cls):
-                    bop.add("%06d/%06d" % (int(batch["scene_id"][i]), int(batch["im_id"][i])), cid, out["RT"][i, :, :3], out["RT"][i, :, 3])
+                    bop.add("%06d/%06d" % (int(batch["scene_id"][i]), int(batch["im_id"][i])), cid, out["RT"][i, :, :3], out["RT"][i, :, 3],
+                            score=float(out["score"][i]) if "score" in out else -1)
             if has_gt and "n_undetected" in batch:
                 for i, cid in enumerate(cls):
                     miss = int(batch["n_undetected"][i])

@@ -171,6 +171,26 @@ int gdm_match_packed_hip(const void* scene_rows, const void* model_rows, int R /
                          int32_t* best_idx, float* best_sim, float* sim,
                          void* partial, size_t partial_bytes, void* stream);
 
+/* Soft assignment on the same similarities (sim_ij = s_i . m_j in the kernel's own arithmetic), gamma a temperature:
+ *   lse_i      = log sum_j exp(gamma sim_ij)                      f32[R]
+ *   conf_i     = exp(gamma best_sim_i - lse_i)                    f32[R]     in (0, 1]: softmax probability of the arg-max vertex
+ *   soft_xyz_i = sum_j exp(gamma sim_ij - lse_i) model_xyz_j      f32[R,3]   expected model coordinate (model_xyz f32[M,3])
+ * over exactly the M real columns and for every row; best_idx / best_sim are those of gdm_match_packed_hip on the same rows, bit
+ * for bit.  No [R, M] tensor is written and no atomic is used: the kernel accumulates exp(gamma (sim - 1)) (cosines are <= 1, so
+ * the fixed shift 1 needs no running maximum, and gamma <= 40 keeps every term >= e^-80, a normal fp32), one partial per 256-column
+ * panel and row goes to `partial` (gdm_match_soft_partial_bytes(B, N), 16-byte aligned) and the panels are added in ascending
+ * order, so two runs are bit-identical.  0 < gamma <= GDM_MATCH_SOFT_MAX_GAMMA and 1 <= M <= GDM_MATCH_SOFT_MAX_M (the 64 panels
+ * the LDS-resident kernel form covers); anything else, a NaN gamma included, is refused with GDM_EINVAL before any launch. */
+#define GDM_MATCH_SOFT_MAX_GAMMA 40.0f
+#define GDM_MATCH_SOFT_MAX_M     16384
+size_t gdm_match_soft_partial_bytes(int B, int N);
+int gdm_match_soft_packed_hip(const void* scene_rows, const void* model_rows, const float* model_xyz, int R /* B*N */, int M,
+                              int precision, float gamma, int32_t* best_idx, float* best_sim, float* lse, float* conf,
+                              float* soft_xyz, void* partial, size_t partial_bytes, void* stream);
+/* score f32[B] = the mean of conf f32[B,N] over the points with mask u8[B,N] != 0, 0 for a crop with none (fp64, fixed order): the
+ * number an estimate is ranked by (the `score` column of a BOP csv). */
+int gdm_match_score_hip(const float* conf, const uint8_t* mask, int B, int N, float* score, void* stream);
+
 /* seg f32[B,2,N] -> mask u8[B,N] = (argmax over the 2 classes == 1) (evaluator.py:79-83),
  * count i32[B] of selected points (zeroed inside).                                        */
 int gdm_seg_mask_hip(const float* seg, int B, int N, uint8_t* mask, int32_t* count, void* stream);
@@ -372,6 +392,17 @@ int gdm_kabsch_stats_hip(const float* scene_xyz, long scene_bstride, int pt_stri
  * reference's sentinel pose [I | (0,0,-1000)] (evaluator.py:94-96).  The optimal proper rotation is obtained as Horn's unit
  * quaternion (largest eigenvector of a symmetric 4x4, cyclic Jacobi, f64) -- the same R as SVD + reflection fix. */
 int gdm_kabsch_solve_hip(const double* stats, int B, int min_points, float* RT, uint8_t* valid, void* stream);
+
+/* The weighted fit.  gdm_kabsch_stats_w_hip: out[b] = { sum w, sum w A (3), sum w B (3), sum w A_i B_j (9) } as f64 over the points
+ * with mask != 0 and a finite weight > 0 (weight f32[B,N]; NaN, infinite, zero and negative weights are skipped), count i32[B] = the
+ * number of such points.  A = target[b, i] (f32[B,N,3], e.g. soft_xyz of gdm_match_soft_packed_hip) when target is non-NULL, else
+ * model_xyz[best_idx] as gdm_kabsch_stats_hip (model_xyz / best_idx may then not be NULL; with a target they are ignored).
+ * gdm_kabsch_solve_w_hip: the fit of gdm_kabsch_solve_hip with n = sum w (it is scale-free in n: weights c w give the pose of
+ * weights w); valid = count >= min_points and sum w > 0, else the sentinel pose. */
+int gdm_kabsch_stats_w_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* model_xyz,
+                           const int32_t* best_idx, const float* target, const float* weight, const uint8_t* mask, int B, int N,
+                           int M, double* out, int32_t* count, void* stream);
+int gdm_kabsch_solve_w_hip(const double* stats, const int32_t* count, int B, int min_points, float* RT, uint8_t* valid, void* stream);
 
 /* Robust fit: the reference's RANSAC (utils/pvn3d_eval_utils_kpls.py:79-124 best_fit_transform_with_RANSAC, used next to
  * best_fit_transform by evaluator.py:21) for a whole batch, every hypothesis evaluated at once.  Same correspondences as
