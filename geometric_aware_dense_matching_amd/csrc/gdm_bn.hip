@@ -5,12 +5,16 @@
 // 150 MIOpen launches + the activation launches, 15 of 65 ms.  MIOpen's spatial kernels move these maps at 1.2 (forward) to
 // 2.5 TB/s (backward); the passes here are plain streaming reductions / maps:
 //   forward   bn_reduce<0>   per-channel sum x, sum x^2                          (1 read)
-//             bn_fwd_apply   y = act(a x + b), a, b formed inline from the sums  (1 read, 1 write)  + running statistics, saved mean / rstd
-//   backward  bn_reduce<1>   per-channel sum g', sum g' x,  g' = grad * act'(a x + b)            (2 reads)
-//             bn_bwd_apply   gx = A g' + B x + C, coefficients inline from the sums              (2 reads, 1 write)  + grad weight / bias
-// The activation is folded into both directions (its mask is recomputed from a x + b), so the separate activation forward / backward
-// passes disappear as well.  Per-thread partial sums are fp32 over <= a few hundred values in four independent lanes, everything
-// above that (wave, workgroup, grid) is accumulated in double, and mean / variance / coefficients are formed in double.  The grid-level
+//             bn_fwd_apply   y = act(a (x - m) + b), a, b formed inline from the sums  (1 read, 1 write)  + running statistics, saved mean / rstd
+//   backward  bn_reduce<1>   per-channel sum g', sum g' x,  g' = grad * act'(a (x - m) + b)      (2 reads)
+//             bn_bwd_apply   gx = A g' + B (x - m) + C, coefficients inline from the sums        (2 reads, 1 write)  + grad weight / bias
+// m is the batch mean rounded to fp32 and b = bias - (mean - m) a: x - m is exact where it matters (x within a factor 2 of m), while the
+// folded form a x + (bias - mean a) rounds its constant at |mean a| and so loses mean / std digits of the result in a low-variance channel.
+// The activation is folded into both directions (its mask is recomputed from a (x - m) + b), so the separate activation forward / backward
+// passes disappear as well.  Every sum is accumulated in double from the first element on (products x x and g' x formed in double,
+// where they are exact), and mean / variance / coefficients are formed in double: var = E[x^2] - mean^2 and S2 = sum g' x - mean sum g'
+// cancel all but a fraction var / mean^2 of their terms, and a channel of a real step may hold mean / std of several hundred (a post-ReLU
+// global feature over 8 values), where fp32 squares left the variance with a relative error of 1e-2.  The passes stay HBM-bound.  The grid-level
 // step has no atomics and no memset: workgroup g of channel c stores its pair to sums[g][c], and the apply kernels add the G <= 32
 // pairs of their channel themselves (lane-parallel, a few hundred cycles per workgroup) -- deterministic, two launches per direction.
 // x f32[B, C, inner] contiguous, inner % 4 == 0.
@@ -36,12 +40,13 @@ __global__ __launch_bounds__(BN_T) void bn_reduce_kernel(const float4* __restric
 {
     __shared__ double part[BN_T / 64][2];
     const int c = blockIdx.y;
-    float a = 1.f, b = 0.f;
+    float a = 1.f, b = 0.f, mf = 0.f;
     if (MODE == 1) {
         a = saved[c];
         b = saved[C + c];
+        mf = saved[2 * C + c];
     }
-    float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
+    double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
     for (unsigned j = blockIdx.x * BN_T + threadIdx.x; j < total4; j += gridDim.x * BN_T) {
         const unsigned bi = j / inner4, i = j - bi * inner4;
         const long off = ((long)bi * C + c) * inner4 + i;
@@ -50,22 +55,24 @@ __global__ __launch_bounds__(BN_T) void bn_reduce_kernel(const float4* __restric
         if (MODE == 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                s0[k] += xv[k];
-                s1[k] = fmaf(xv[k], xv[k], s1[k]);
+                const double xd = (double)xv[k];
+                s0[k] += xd;
+                s1[k] = fma(xd, xd, s1[k]);
             }
         } else {
             const float4 g = go[off];
             const float gv[4] = {g.x, g.y, g.z, g.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float gm = act_mask(fmaf(xv[k], a, b), gv[k], act, slope);
-                s0[k] += gm;
-                s1[k] = fmaf(gm, xv[k], s1[k]);
+                const float gm = act_mask(fmaf(xv[k] - mf, a, b), gv[k], act, slope);
+                const double gd = (double)gm;
+                s0[k] += gd;
+                s1[k] = fma(gd, (double)xv[k], s1[k]);
             }
         }
     }
-    double d0 = ((double)s0[0] + (double)s0[1]) + ((double)s0[2] + (double)s0[3]);
-    double d1 = ((double)s1[0] + (double)s1[1]) + ((double)s1[2] + (double)s1[3]);
+    double d0 = (s0[0] + s0[1]) + (s0[2] + s0[3]);
+    double d1 = (s1[0] + s1[1]) + (s1[2] + s1[3]);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         d0 += __shfl_xor(d0, m, 64);
@@ -111,8 +118,8 @@ __device__ __forceinline__ void channel_sums(const double* __restrict__ sums, in
     t1 = b;
 }
 
-// y = act(a x + b) with a = w rstd, b = bias - mean a from the (possibly all-reduced) sums; the b = 0 planes also store
-// saved = (a | b | mean | rstd) for the backward and update the running statistics (momentum m, unbiased variance).
+// y = act(a (x - m) + b) with a = w rstd, m = (float)mean, b = bias - (mean - m) a from the (possibly all-reduced) sums; the b = 0 planes
+// also store saved = (a | b | m | rstd | mean - m) for the backward and update the running statistics (momentum, unbiased variance).
 __global__ __launch_bounds__(BN_T) void bn_fwd_apply_kernel(const float4* __restrict__ x, const double* __restrict__ sums, const float* __restrict__ weight,
                                                             const float* __restrict__ bias, int C, int G, long inner4, float eps, float momentum,
                                                             int act, float slope, float* __restrict__ saved, float* __restrict__ running_mean,
@@ -127,12 +134,14 @@ __global__ __launch_bounds__(BN_T) void bn_fwd_apply_kernel(const float4* __rest
     const double var = fmax(t1 / n - mean * mean, 0.0);
     const double rstd = 1.0 / sqrt(var + (double)eps);
     const double ad = (double)weight[c] * rstd;
-    const float a = (float)ad, b = (float)((double)bias[c] - mean * ad);
+    const float mf = (float)mean;
+    const float a = (float)ad, b = (float)((double)bias[c] - (mean - (double)mf) * ad);
     if (blockIdx.x == 0 && plane < C && threadIdx.x == 0) {
         saved[c] = a;
         saved[C + c] = b;
-        saved[2 * C + c] = (float)mean;
+        saved[2 * C + c] = mf;
         saved[3 * C + c] = (float)rstd;
+        saved[4 * C + c] = (float)(mean - (double)mf);
         if (running_mean) {
             running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
             running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * (n > 1.0 ? var * n / (n - 1.0) : var));
@@ -142,7 +151,7 @@ __global__ __launch_bounds__(BN_T) void bn_fwd_apply_kernel(const float4* __rest
     float4* yp = y + plane * inner4;
     for (long i = (long)blockIdx.x * BN_T + threadIdx.x; i < inner4; i += (long)gridDim.x * BN_T) {
         const float4 v = xp[i];
-        float o[4] = {fmaf(v.x, a, b), fmaf(v.y, a, b), fmaf(v.z, a, b), fmaf(v.w, a, b)};
+        float o[4] = {fmaf(v.x - mf, a, b), fmaf(v.y - mf, a, b), fmaf(v.z - mf, a, b), fmaf(v.w - mf, a, b)};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (act == 1) o[k] = fmaxf(o[k], 0.f);
@@ -152,7 +161,8 @@ __global__ __launch_bounds__(BN_T) void bn_fwd_apply_kernel(const float4* __rest
     }
 }
 
-// gx = A g' + B x + Cc with S1 = sum g', S2 = rstd (sum g' x - mean S1):  A = w rstd,  B = -w rstd^2 S2 / n,  Cc = -B mean - w rstd S1 / n;
+// gx = A g' + B (x - m) + Cc with S1 = sum g', S2 = rstd (sum g' x - mean S1), mean = m + its saved remainder (S2 keeps a fraction
+// std / mean of its terms: the fp32 mean alone costs it those digits):  A = w rstd,  B = -w rstd^2 S2 / n,  Cc = -B (mean - m) - w rstd S1 / n;
 // grad weight = S2, grad bias = S1 (stored by the b = 0 planes).
 __global__ __launch_bounds__(BN_T) void bn_bwd_apply_kernel(const float4* __restrict__ x, const float4* __restrict__ go, const double* __restrict__ sums,
                                                             const float* __restrict__ weight, const float* __restrict__ saved, int C, int G, long inner4,
@@ -162,14 +172,15 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_apply_kernel(const float4* __rest
     const long plane = blockIdx.y;
     const int c = (int)(plane % C);
     const float a = saved[c], b = saved[C + c];
-    const double mean = (double)saved[2 * C + c], rstd = (double)saved[3 * C + c];
+    const double mlo = (double)saved[4 * C + c];
+    const double mean = (double)saved[2 * C + c] + mlo, rstd = (double)saved[3 * C + c];
     const double n = sums[2L * C * G];
     double S1, S2x;
     channel_sums(sums, C, c, G, S1, S2x);
     const double S2 = rstd * (S2x - mean * S1);
     const double wr = (double)weight[c] * rstd;
     const double Bd = -wr * rstd * S2 / n;
-    const float A = (float)wr, Bc = (float)Bd, Cc = (float)(-Bd * mean - wr * S1 / n);
+    const float A = (float)wr, Bc = (float)Bd, Cc = (float)(-Bd * mlo - wr * S1 / n), mf = saved[2 * C + c];
     if (blockIdx.x == 0 && plane < C && threadIdx.x == 0) {
         gweight[c] = (float)S2;
         gbias[c] = (float)S1;
@@ -183,8 +194,8 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_apply_kernel(const float4* __rest
         float o[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float gm = act_mask(fmaf(xv[k], a, b), gv[k], act, slope);
-            o[k] = fmaf(A, gm, fmaf(Bc, xv[k], Cc));
+            const float gm = act_mask(fmaf(xv[k] - mf, a, b), gv[k], act, slope);
+            o[k] = fmaf(A, gm, fmaf(Bc, xv[k] - mf, Cc));
         }
         op[i] = make_float4(o[0], o[1], o[2], o[3]);
     }

@@ -951,7 +951,7 @@ class _BatchNormAct(torch.autograd.Function):
         inner = x.numel() // (B * C)
         L = _lib.lib()
         sums = torch.empty(L.gdm_bn_sums_len(B, C, inner), dtype=torch.float64, device=x.device)
-        saved = torch.empty(4 * C, dtype=torch.float32, device=x.device)
+        saved = torch.empty(5 * C, dtype=torch.float32, device=x.device)       # a | b | fp32 mean | rstd | mean - fp32 mean
         y = torch.empty_like(x)
         check(L.gdm_bn_stats_hip(x.data_ptr(), B, C, inner, sums.data_ptr(), _stream()), "gdm_bn_stats_hip")
         groups = 0
@@ -988,7 +988,7 @@ class _BatchNormAct(torch.autograd.Function):
         check(L.gdm_bn_bwd_apply_hip(x.data_ptr(), go.data_ptr(), sums.data_ptr(), groups, weight.data_ptr(), saved.data_ptr(), B, C, inner,
                                      ctx.act, ctx.slope, gw.data_ptr(), gb.data_ptr(), gx.data_ptr(), _stream()), "gdm_bn_bwd_apply_hip")
         if local is not None:
-            mean, rstd = saved[2 * C:3 * C].double(), saved[3 * C:].double()
+            mean, rstd = saved[2 * C:3 * C].double() + saved[4 * C:].double(), saved[3 * C:4 * C].double()
             gb = local[:, 0].float()
             gw = (rstd * (local[:, 1] - mean * local[:, 0])).float()
         return gx, gw, gb, None, None, None, None, None, None, None
@@ -1629,7 +1629,7 @@ def conv64_gather_add_final(x, wpk, t, idx, scale, shift, act, slope, final_weig
 
 def channel_sum(t):
     """t f32[B,C,...] -> f32[C] sums over batch and inner dimensions (bias gradients): the streaming reduction of the BatchNorm kernels
-    (fp32 lanes, double above) where its shape rules hold -- torch's generic reduce_kernel moves these maps at 0.7 TB/s."""
+    (accumulated in double) where its shape rules hold -- torch's generic reduce_kernel moves these maps at 0.7 TB/s."""
     B, C = t.shape[0], t.shape[1]
     inner = t.numel() // max(B * C, 1)
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and B * C <= 65535 and inner >= 4 and inner % 4 == 0

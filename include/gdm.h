@@ -808,7 +808,8 @@ int gdm_dzi_boxes_hip(const float* bbox, int B, float max_side, float pad_ratio,
  * count per channel and G; no atomics, no memset, the apply calls add the partials (`groups` = 0: the layout the reduce call of the
  * same shape wrote).  A data-parallel caller (SyncBatchNorm semantics, /root/reference/train_lm.py:412) folds the partials to one
  * pair per channel, all-reduces pairs and count, and passes that buffer -- double[2C+1]: pairs, count -- with `groups` = 1.
- * saved f32[4C] = folded scale | folded shift | mean | rstd, written by the forward apply, read by both backward calls.
+ * saved f32[5C] = a | b | m | rstd | mean - m with y = act(a (x - m) + b), m the batch mean rounded to fp32; written by the forward
+ * apply, read by both backward calls.
  * act: 0 none, 1 ReLU, 2 LeakyReLU(slope).  running_mean / running_var (both or neither) are updated with `momentum`. */
 long gdm_bn_sums_len(int B, int C, long inner);
 int gdm_bn_stats_hip(const float* x, int B, int C, long inner, double* sums, void* stream);

@@ -2,6 +2,7 @@
 geometric_aware_dense_matching_amd.ops).  Bit-exact for indices and pure data movement; fp32
 tolerances are written at each check."""
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -58,7 +59,7 @@ def test_knn_cell_list_search_equals_oracle(ops, case):
     box, K = 32, 16384 points, points at the origin among real ones (depth holes), and a support barely over the threshold with K
     close to the cell population."""
     from oracle import knn as oknn
-    rs = np.random.RandomState(abs(hash(case)) % (2 ** 31))
+    rs = np.random.RandomState(zlib.crc32(case.encode()) % (2 ** 31))
     B, S, Q, K = 2, 2048, 1500, 16
     qry = None
     if case == "cube":
@@ -108,7 +109,7 @@ def test_knn1_through_job_table_equals_oracle(ops, case):
     (Written for a cell-list form of the K = 1 search, round 4: exact, but one query per lane walking its own cells is latency-bound --
     147 us against the exhaustive kernel's 73 us per pyramid -- so the exhaustive kernel stays; the cases stay as its test.)"""
     from oracle import knn as oknn
-    rs = np.random.RandomState(abs(hash("k1" + case)) % (2 ** 31))
+    rs = np.random.RandomState(zlib.crc32(("k1" + case).encode()) % (2 ** 31))
     B, S, Q = 2, 512, 5000
     qry = None
     if case in ("s512", "s128", "s64", "s1024"):

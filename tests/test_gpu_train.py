@@ -311,6 +311,47 @@ def test_fused_batchnorm_act_training_matches_modules(shape, act):
     assert int(bn_a.num_batches_tracked) == 1
 
 
+@pytest.mark.parametrize("shape,act,ratio", [((2, 16, 4, 1), 1, 400.0), ((2, 16, 4, 1), 0, 3000.0), ((3, 8, 100), 2, 1000.0), ((2, 4, 64, 64), 1, 1000.0)])
+def test_fused_batchnorm_channels_with_a_variance_near_eps(shape, act, ratio):
+    """Channels whose batch mean is `ratio` standard deviations from zero and whose variance is about eps (RandLA's 1e-6) -- what the
+    post-ReLU global feature f32[2,1024,4,1] of a real step looks like (found by tests/test_gpu_train_replay.py): var = E[x^2] - mean^2
+    keeps a fraction 1 / ratio^2 of its terms, so the sums need exact products, and the affine map must not round its constant at
+    |mean a|.  Same comparison and tolerances as test_fused_batchnorm_act_training_matches_modules (8 values per channel in the first
+    two cases; fp32 squares gave the output an error of 5e-3 there)."""
+    from geometric_aware_dense_matching_amd import ops
+    torch.manual_seed(int(ratio) + act)
+    C = shape[1]
+    cls = torch.nn.BatchNorm2d if len(shape) == 4 else torch.nn.BatchNorm1d
+    bn_a, bn_b = cls(C, eps=1e-6, momentum=0.99).cuda().train(), cls(C, eps=1e-6, momentum=0.99).cuda().train()
+    with torch.no_grad():
+        bn_a.weight.copy_(torch.randn(C)); bn_a.bias.copy_(torch.randn(C))
+    bn_b.load_state_dict(bn_a.state_dict())
+    bn_b = bn_b.double()
+    view = (1, C) + (1,) * (len(shape) - 2)
+    centre = (torch.arange(C, device="cuda").float() % 5 + 1.0).view(view) * torch.where(torch.arange(C, device="cuda") % 2 == 0, 1.0, -1.0).view(view)
+    x = centre + centre.abs() / ratio * torch.randn(*shape, device="cuda")
+    x[:, 0] = x[:, 0] - centre.flatten()[0]                  # one ordinary channel next to them
+    w = torch.randn(*shape, device="cuda")
+    xa = x.clone().requires_grad_(True)
+    xb = x.double().requires_grad_(True)
+    assert ops.bn_train_supported(xa, bn_a)
+    ya = ops.batch_norm_act_train(xa, bn_a, act, 0.2)
+    pre = bn_b(xb)
+    side = (ya.detach() > 0).double()
+    yb = pre * side if act == 1 else pre * (side + (1 - side) * 0.2) if act == 2 else pre
+    (ya * w).sum().backward()
+    (yb * w.double()).sum().backward()
+    keep = (pre.detach().abs() > 1e-5)
+    tol = lambda t: 1e-5 * max(1.0, t.abs().max().item())
+    errs = dict(y=((ya.double() - yb).abs() * keep).max().item() / tol(yb), gx=((xa.grad.double() - xb.grad).abs() * keep).max().item() / tol(xb.grad),
+                gw=(bn_a.weight.grad.double() - bn_b.weight.grad).abs().max().item() / tol(bn_b.weight.grad),
+                gb=(bn_a.bias.grad.double() - bn_b.bias.grad).abs().max().item() / tol(bn_b.bias.grad))
+    print("low-variance BatchNorm %s act %d ratio %g: error / bound %s" % (shape, act, ratio, "  ".join("%s %.3f" % kv for kv in errs.items())))
+    assert all(v < 1.0 for v in errs.values()), errs
+    assert torch.allclose(bn_a.running_mean.double(), bn_b.running_mean, rtol=1e-5, atol=1e-6)
+    assert torch.allclose(bn_a.running_var.double(), bn_b.running_var, rtol=1e-5, atol=1e-6)
+
+
 def _syncbn_worker(rank, world, port, out):
     import os
     import torch.distributed as dist
@@ -453,7 +494,8 @@ def test_training_step_through_fused_paths_equals_module_paths():
     exact re-associations in fp32 (low-resolution up-convolution, split PSP bottleneck) 3e-3 each; the split-bf16 convolutions (1e-5
     per output) 8e-2; the fused BatchNorm (fp64 sums against MIOpen's fp32 sums) 5e-2; everything 1.1e-1, loss 8e-5.  So the exact
     paths are held to 3e-2, and the full set to a bound that only an O(1) error -- a dropped term, a wrong scale -- would break; the
-    per-operator tests above hold each kernel to 1e-4 .. 1e-5 against fp64."""
+    per-operator tests above hold each kernel to 1e-4 .. 1e-5 against fp64.  What holds each kernel tightly ON THE DATA OF SUCH A STEP is
+    the per-call replay of tests/test_gpu_train_replay.py: every autograd Function of the step against fp64 on its own recorded inputs."""
     from geometric_aware_dense_matching_amd import cnn, ops, train_lm
     from geometric_aware_dense_matching_amd.geoMatch import GeoMatch
     M, N, B = 512, 1024, 2
