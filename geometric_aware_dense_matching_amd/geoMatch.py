@@ -26,6 +26,13 @@ def pdist(A, B):
 
 
 class GeoMatch(nn.Module):
+    # The soft-assignment training losses (loss.SoftAssignLoss): opt-in, plain attributes (not part of the state dict).
+    # With both weights 0 ops.soft_coord_match is never called and a training step is launch for launch what it was.
+    soft_gamma = 16.0
+    soft_beta = 0.005
+    soft_xyz_weight = 0.0
+    soft_nll_weight = 0.0
+
     def __init__(self, cfg, cls_id, model_points=None, cache_mesh_in_eval=False):
         super().__init__()
         self.awl = AutomaticWeightedLoss(2)
@@ -53,15 +60,24 @@ class GeoMatch(nn.Module):
         return derived(self, "nbr", (xyz,), lambda: ops.circle_nbr_table(xyz.contiguous(), self.positive_r),
                        extra=(float(self.positive_r), xyz.device))
 
-    def pointwise_feature_matching(self, rgbd_feature, mesh_feature, x):
+    def pointwise_feature_matching(self, rgbd_feature, mesh_feature, x, parts=False):
         """geoMatch.py:102-157 for the whole batch at once: value and gradients of the reference's per-item loop (mean over the
         items with >= 3 selected points of the mean circle loss of their rows).  The [n_sel, M+1] similarity is never formed: unit
         rows go to ops.circle_match (MFMA similarity tiles, masked LSEs in registers, recomputation in the backward kernels).
         Non-symmetric objects: positives = visible vertices within positive_r of the ground-truth vertex (:55-83); symmetric
         objects (model_emb.sys_corr_idx set): the row's own match and the match of its symmetric counterpart (:86-100, indexing
         restated as the reference writes it).  settings.USE_FUSED_MATCH_LOSS = False: same batch formulation with the similarity
-        materialised by one GEMM (the form the fused kernels are tested against, besides oracle/loss_ref.py and the goldens)."""
+        materialised by one GEMM (the form the fused kernels are tested against, besides oracle/loss_ref.py and the goldens).
+        With soft_xyz_weight or soft_nll_weight set, the two soft-assignment losses of the same rows are added with those weights
+        (loss.soft_assign_terms); parts=True returns (match_loss, soft_xyz_loss, soft_nll_loss) instead of their weighted sum."""
         from . import ops, settings
+        from .loss import soft_assign_terms
+        soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0
+
+        def result(match_loss, lx=None, ln=None):
+            if not soft_on:
+                return (match_loss, None, None) if parts else match_loss
+            return (match_loss, lx, ln) if parts else match_loss + self.soft_xyz_weight * lx + self.soft_nll_weight * ln
         if not rgbd_feature.is_cuda:
             raise RuntimeError("GeoMatch training matching loss runs on the GPU (HIP kernels); there is no CPU fallback")
         B, D, N = rgbd_feature.shape
@@ -81,7 +97,8 @@ class GeoMatch(nn.Module):
         else:
             bi, pi = torch.nonzero(sel, as_tuple=True)             # row-major: item, then point order
             if bi.numel() == 0:
-                return torch.zeros((), device=mesh.device)
+                zero = torch.zeros((), device=mesh.device)
+                return result(zero, zero, zero)
         rows = F.normalize(rgbd_feature.transpose(1, 2)[bi, pi], p=2, dim=1)      # [R,128]
         match_all = x["match_idx"].long()
         if static_rows:
@@ -96,6 +113,7 @@ class GeoMatch(nn.Module):
             c2 = match_all[bi, sys_idx[pi]]
         else:
             c1, c2 = match_all[bi, pi], None
+        mesh_rows = None
         if settings.USE_FUSED_MATCH_LOSS:
             mesh_rows = F.normalize(mesh, p=2, dim=0).t().contiguous()             # [M,128]; the -1 padding column is analytic
             if symmetric:
@@ -115,13 +133,20 @@ class GeoMatch(nn.Module):
                 lrow = self.circle_loss.rows(sim, mask, 0.2)
             else:
                 lrow = ops.circle_rows(sim, c1, bi, self.model_emb.xyz.contiguous(), x["visible_flag"], self.positive_r, 16.0, 0.2)
+        lx = ln = None
+        if soft_on:
+            if mesh_rows is None:
+                mesh_rows = F.normalize(mesh, p=2, dim=0).t().contiguous()
+            lx, ln = soft_assign_terms(self, rows, mesh_rows, self.model_emb.xyz.contiguous(), c1, c2, bi, pi, counts, x,
+                                       static_shape=(B, N) if static_rows else None,
+                                       row_weight=sel.reshape(-1) if static_rows else None)
         if static_rows:
             per_item = (lrow.view(B, N) * sel.to(lrow.dtype)).sum(dim=1) / counts.clamp(min=1).to(torch.float32)
             ok = item_ok.to(torch.float32)
-            return (per_item * ok).sum() / ok.sum().clamp(min=1.0)
+            return result((per_item * ok).sum() / ok.sum().clamp(min=1.0), lx, ln)
         per_item = torch.zeros(B, dtype=torch.float32, device=mesh.device).index_add_(0, bi, lrow)
         per_item = per_item[item_ok] / counts[item_ok].to(torch.float32)
-        return per_item.mean()
+        return result(per_item.mean(), lx, ln)
 
     # ------------------------------------------------------------------ forward (geoMatch.py:159-200)
     def mesh_features(self):
@@ -207,11 +232,19 @@ class GeoMatch(nn.Module):
         mesh_features = mesh_features.unsqueeze(0)
 
         if self.training:
-            match_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs)
+            soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0
+            if soft_on:
+                match_loss, soft_xyz_loss, soft_nll_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs, parts=True)
+            else:
+                match_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs)
             seg_loss = self.seg_loss_func(seg_features, inputs["labels"].long())
             end_points["loss"] = self.awl(seg_loss, match_loss)
             end_points["seg_loss"] = seg_loss
             end_points["match_loss"] = match_loss
+            if soft_on:
+                end_points["loss"] = end_points["loss"] + self.soft_xyz_weight * soft_xyz_loss + self.soft_nll_weight * soft_nll_loss
+                end_points["soft_xyz_loss"] = soft_xyz_loss
+                end_points["soft_nll_loss"] = soft_nll_loss
 
         end_points["seg"] = seg_features
         if mesh_rows is not None:

@@ -17,6 +17,11 @@ class GeoMatch(nn.Module):
     train_path = "modules"           # "modules" | "fused": how both trunks run in TRAINING mode (dgcnn._DgcnnTrunk._embed /
                                      # ._embed_train_fused); not part of the state dict, read only when self.training
 
+    soft_gamma = 16.0                # the soft-assignment training losses (loss.SoftAssignLoss, geoMatch.GeoMatch): opt-in,
+    soft_beta = 0.005                # plain attributes; with both weights 0 nothing of them runs
+    soft_xyz_weight = 0.0
+    soft_nll_weight = 0.0
+
     def __init__(self, cfg, cls_id, model_points=None):
         super().__init__()
         self.awl = AutomaticWeightedLoss(2)
@@ -32,7 +37,7 @@ class GeoMatch(nn.Module):
                                        .conv1d(self.feat_dim, activation=None, bias=False))
         self.normalize_feature_layer = pt_conv1d(self.feat_dim, self.feat_dim, bn=True)
 
-    def pointwise_feature_matching(self, rgbd_feature, mesh_feature, x):
+    def pointwise_feature_matching(self, rgbd_feature, mesh_feature, x, parts=False):
         """The training matching loss of geoMatch_DGCNN.py:52-135 for the whole batch at once, WITHOUT the [B, N, M+1] similarity:
         value and gradients of the reference's per-item loop (mean over the items with >= 3 rows of `origin_labels == 1` of the
         mean circle loss of their rows).  What differs from the FFB6D variant (geoMatch.GeoMatch.pointwise_feature_matching):
@@ -40,7 +45,15 @@ class GeoMatch(nn.Module):
           * a vertex v is a positive of a row with ground-truth vertex g when it is visible in the row's item and
             pdist(g, v) < positive_r / 1000 * z_i(v), z_i(v) = depth of v posed by the item's RT (:62-67): the radius depends on the
             item AND the vertex, so the positive tables are built per item (ops.circle_nbr_items, one launch for the batch) and the
-            fused kernels index them by (item, g) -- ops.circle_match(..., pad="e0")."""
+            fused kernels index them by (item, g) -- ops.circle_match(..., pad="e0").
+        soft_xyz_weight / soft_nll_weight / parts: as in geoMatch.GeoMatch.pointwise_feature_matching."""
+        from .loss import soft_assign_terms
+        soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0
+
+        def result(match_loss, lx=None, ln=None):
+            if not soft_on:
+                return (match_loss, None, None) if parts else match_loss
+            return (match_loss, lx, ln) if parts else match_loss + self.soft_xyz_weight * lx + self.soft_nll_weight * ln
         if not rgbd_feature.is_cuda:
             raise RuntimeError("GeoMatch (DGCNN) training matching loss runs on the GPU (HIP kernels); there is no CPU fallback")
         B, D, N = rgbd_feature.shape
@@ -52,7 +65,8 @@ class GeoMatch(nn.Module):
         sel = sel & item_ok.unsqueeze(1)
         bi, pi = torch.nonzero(sel, as_tuple=True)                 # row-major: item, then point order
         if bi.numel() == 0:
-            return torch.zeros((), device=mesh.device)
+            zero = torch.zeros((), device=mesh.device)
+            return result(zero, zero, zero)
         rows = F.normalize(rgbd_feature.transpose(1, 2)[bi, pi], p=2, dim=1)          # [R,128] (normalising a row commutes with selecting it)
         mesh_rows = F.normalize(mesh, p=2, dim=0).t().contiguous()                   # [M,128]; the padding column stays e0 under the normalisation
         g = x["match_idx"].long()[bi, pi]
@@ -64,7 +78,10 @@ class GeoMatch(nn.Module):
                                 visb=ops.circle_visbits(x["visible_flag"]), gamma=16.0, m=0.2, pad="e0")
         per_item = torch.zeros(B, dtype=torch.float32, device=mesh.device).index_add_(0, bi, lrow)
         per_item = per_item[item_ok] / counts[item_ok].to(torch.float32)
-        return per_item.mean()
+        if not soft_on:
+            return result(per_item.mean())
+        lx, ln = soft_assign_terms(self, rows, mesh_rows, mesh_xyz, g, None, bi, pi, counts, x)
+        return result(per_item.mean(), lx, ln)
 
     def forward(self, inputs, end_points=None, fused=False, defer_seg=False):
         """fused: both trunks on the fused inference path (dgcnn._DgcnnTrunk._embed_fused; eval only; raises in training mode).  In
@@ -90,11 +107,19 @@ class GeoMatch(nn.Module):
         rgbd_emb = rgbd_emb + rgbd_normalized
         seg_features = self.seg_layer(rgbd_emb)
         if self.training:
-            match_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs)
+            soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0
+            if soft_on:
+                match_loss, soft_xyz_loss, soft_nll_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs, parts=True)
+            else:
+                match_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs)
             seg_loss = self.seg_loss_func(seg_features, inputs["labels"].long())
             end_points["loss"] = self.awl(seg_loss, match_loss)
             end_points["seg_loss"] = seg_loss
             end_points["match_loss"] = match_loss
+            if soft_on:
+                end_points["loss"] = end_points["loss"] + self.soft_xyz_weight * soft_xyz_loss + self.soft_nll_weight * soft_nll_loss
+                end_points["soft_xyz_loss"] = soft_xyz_loss
+                end_points["soft_nll_loss"] = soft_nll_loss
         end_points["seg"] = seg_features
         end_points["mesh"] = mesh_features
         end_points["rgbd"] = rgbd_features

@@ -69,3 +69,100 @@ class AutomaticWeightedLoss(nn.Module):
         for i, loss in enumerate(x):
             loss_sum = loss_sum + 0.5 / (self.params[i] ** 2) * loss + torch.log(1 + self.params[i] ** 2)
         return loss_sum
+
+
+def soft_coord_reference(x, y, xyz, gamma):
+    """The soft assignment of ops.soft_coord_match in plain torch, any dtype and device, WITH the [R, M] similarity materialised:
+    x [R,D] and y [M,D] unit rows, xyz [M,3] -> lse [R] = logsumexp_c(gamma <x_r, y_c>), soft [R,3] = softmax_c(gamma <x_r, y_c>) @ xyz.
+    What the fused operator is held to (tests) and the materialised leg of tools/soft_coord_profile.py."""
+    logits = float(gamma) * (x @ y.t())
+    lse = torch.logsumexp(logits, dim=1)
+    soft = torch.exp(logits - lse.unsqueeze(1)) @ xyz.to(logits.dtype)
+    return lse, soft
+
+
+class SoftAssignLoss(nn.Module):
+    """Two training losses on the differentiable soft assignment, per selected scene row r with ground-truth vertex g_r:
+      coordinate  sum_k smooth_l1(soft_rk - t_rk, beta)     metres; t_r = the row's model coordinate (given by the caller)
+      likelihood  lse_r - gamma s_{r,g_r}                    = -log softmax_c(gamma s_rc)[g_r]; symmetric objects (c2 given):
+                  lse_r - logaddexp(gamma s_{r,c1}, gamma s_{r,c2})
+    averaged as the circle loss is: the mean over the items with at least 3 selected rows of the mean over their selected rows.  A
+    row without a ground-truth vertex (g == M; symmetric: either column == M) has weight 0 in both terms and still counts in its
+    item's denominator.  The coordinate term is refused for symmetric objects: the expectation over two valid vertices is neither.
+    match = "kernel": ops.soft_coord_match (HIP, no [R, M] tensor, float32 on the GPU only); "reference": soft_coord_reference
+    (materialised; any dtype and device) -- an explicit choice, never a fall-back."""
+
+    def __init__(self, gamma=16.0, beta=0.005, match="kernel"):
+        super().__init__()
+        if match not in ("kernel", "reference"):
+            raise ValueError("SoftAssignLoss: match must be 'kernel' or 'reference', got %r" % (match,))
+        self.gamma, self.beta, self.match = float(gamma), float(beta), match
+
+    def assignment(self, rows, mesh_rows, xyz):
+        if self.match == "kernel":
+            from . import ops
+            return ops.soft_coord_match(rows, mesh_rows, xyz, self.gamma)
+        return soft_coord_reference(rows, mesh_rows, xyz, self.gamma)
+
+    def forward(self, rows, mesh_rows, xyz, g, item, counts, target=None, c2=None, row_weight=None, terms=("xyz", "nll"),
+                static_shape=None):
+        """rows [R,D] / mesh_rows [M,D] unit rows, xyz [M,3], g int[R] (M = none), item int[R] in [0, B), counts int[B] = selected
+        rows per item, target [R,3] (default xyz[g]), c2 int[R] (symmetric objects), row_weight [R] (1 = selected, 0 = not: the
+        static all-rows form; default all selected), static_shape = (B, N) when the rows are all B*N points in order (the per-item
+        sums are then plain row sums, no index_add).  -> (coordinate loss, likelihood loss); a term not in `terms` is None."""
+        M = mesh_rows.shape[0]
+        symmetric = c2 is not None
+        if symmetric and "xyz" in terms:
+            raise ValueError("SoftAssignLoss: the coordinate term is not defined for symmetric objects (the expected vertex of two "
+                             "valid vertices is neither of them); use the likelihood term alone")
+        g = g.long()
+        has = g < M
+        if symmetric:
+            c2 = c2.long()
+            has = has & (c2 < M) & (c2 >= 0)
+        w = has.to(rows.dtype)
+        if row_weight is not None:
+            w = w * row_weight.to(rows.dtype)
+        lse, soft = self.assignment(rows, mesh_rows, xyz)
+        gc = g.clamp(0, M - 1)
+        B = counts.shape[0]
+        ok = (counts >= 3).to(rows.dtype)
+        denom = counts.clamp(min=1).to(rows.dtype)
+
+        def averaged(per_row):
+            per_row = per_row * w
+            if static_shape is not None:
+                per_item = per_row.view(static_shape).sum(dim=1)
+            else:
+                per_item = torch.zeros(B, dtype=rows.dtype, device=rows.device).index_add_(0, item.long(), per_row)
+            return (per_item / denom * ok).sum() / ok.sum().clamp(min=1.0)
+
+        out_xyz = out_nll = None
+        if "xyz" in terms:
+            t = xyz[gc].to(rows.dtype) if target is None else target.to(rows.dtype)
+            out_xyz = averaged(F.smooth_l1_loss(soft, t, beta=self.beta, reduction="none").sum(dim=1))
+        if "nll" in terms:
+            s1 = self.gamma * (rows * mesh_rows[gc]).sum(dim=1)
+            if symmetric:
+                s2 = self.gamma * (rows * mesh_rows[c2.clamp(0, M - 1)]).sum(dim=1)
+                s1 = torch.logaddexp(s1, s2)
+            out_nll = averaged(lse - s1)
+        return out_xyz, out_nll
+
+
+def soft_assign_terms(model, rows, mesh_rows, xyz, c1, c2, bi, pi, counts, x, static_shape=None, row_weight=None):
+    """The shared wiring of SoftAssignLoss into both variants' pointwise_feature_matching: (soft_xyz_loss, soft_nll_loss) for the
+    selected rows (bi, pi) of the batch x, controlled by the model attributes soft_gamma / soft_xyz_weight / soft_nll_weight; a term
+    whose weight is 0 is not computed and comes back as a zero scalar.  Coordinate target: R_b^T (p_r - t_b), the scene point in
+    model coordinates, when the batch carries RT; else the ground-truth vertex xyz[match_idx_r].  A model attribute soft_match =
+    "reference" selects the materialised plain-torch assignment (tests on the CPU / in fp64); the default is the HIP operator."""
+    terms = tuple(t for t, wt in (("xyz", model.soft_xyz_weight), ("nll", model.soft_nll_weight)) if wt != 0)
+    target = None
+    if "xyz" in terms and "RT" in x:
+        RT = x["RT"].to(rows.dtype)
+        p = x["cld_rgb_nrm"][:, :3, :].transpose(1, 2)[bi, pi].to(rows.dtype)              # [R,3] scene points (m)
+        target = torch.einsum("rj,rjk->rk", p - RT[bi, :, 3], RT[bi, :, :3])               # R^T (p - t) as a row vector
+    fn = SoftAssignLoss(model.soft_gamma, model.soft_beta, match=getattr(model, "soft_match", "kernel"))
+    lx, ln = fn(rows, mesh_rows, xyz, c1, bi, counts, target=target, c2=c2, row_weight=row_weight, terms=terms, static_shape=static_shape)
+    zero = torch.zeros((), dtype=rows.dtype, device=rows.device)
+    return (zero if lx is None else lx), (zero if ln is None else ln)

@@ -795,6 +795,97 @@ def circle_match(x, y, g, item, nbr=None, visb=None, c2=None, gamma=16.0, m=0.2,
     return _CircleMatch.apply(x, y, g, c2, item, nbr, visb, float(gamma), float(m), pad == "e0")
 
 
+SOFT_COORD_MAX_GAMMA = 40.0
+
+
+# The differentiable soft assignment is registered through torch.library (custom_op + register_autograd), not as an autograd.Function
+# subclass: two operators, gdm::soft_coord_fwd and gdm::soft_coord_bwd, each a fixed sequence of launches on the current stream with
+# no host read and no allocation that depends on data, so a hipGraph capture records them like any other operator.
+@torch.library.custom_op("gdm::soft_coord_fwd", mutates_args=(), device_types="cuda")
+def _soft_coord_fwd(x: torch.Tensor, y: torch.Tensor, xyz: torch.Tensor,
+                    gamma: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    L = _lib.lib()
+    R, M = x.shape[0], y.shape[0]
+    xr, xt, _ = _cm_pack(x)
+    yr, yt, _ = _cm_pack(y)
+    lse = torch.empty(R, dtype=torch.float32, device=x.device)
+    soft = torch.empty((R, 3), dtype=torch.float32, device=x.device)
+    check(L.gdm_soft_coord_fwd_hip(xr.data_ptr(), xt.data_ptr(), yr.data_ptr(), yt.data_ptr(), xyz.data_ptr(), R, M, gamma,
+                                   lse.data_ptr(), soft.data_ptr(), _stream()), "gdm_soft_coord_fwd_hip")
+    return lse, soft, xr, xt, yr, yt
+
+
+@_soft_coord_fwd.register_fake
+def _(x, y, xyz, gamma):
+    def nb(n):
+        return (n + 127) // 128 * 128
+    R, M = x.shape[0], y.shape[0]
+    u8 = dict(dtype=torch.uint8, device=x.device)
+    return (x.new_empty(R), x.new_empty((R, 3)), torch.empty(nb(R) * 512, **u8), torch.empty(nb(R) * 512, **u8),
+            torch.empty(nb(M) * 512, **u8), torch.empty(nb(M) * 512, **u8))
+
+
+@torch.library.custom_op("gdm::soft_coord_bwd", mutates_args=(), device_types="cuda")
+def _soft_coord_bwd(xr: torch.Tensor, xt: torch.Tensor, yr: torch.Tensor, yt: torch.Tensor, xyz: torch.Tensor, lse: torch.Tensor,
+                    kb: torch.Tensor, M: int, gamma: float) -> tuple[torch.Tensor, torch.Tensor]:
+    L = _lib.lib()
+    R = lse.shape[0]
+    P = int(L.gdm_soft_coord_bwd_parts(R, M))
+    Mp = (M + 127) // 128 * 128
+    gx = torch.empty((R, 128), dtype=torch.float32, device=lse.device)
+    gy = torch.empty((M, 128), dtype=torch.float32, device=lse.device)
+    part = torch.empty((P, Mp, 128), dtype=torch.float32, device=lse.device)
+    check(L.gdm_soft_coord_bwd_hip(xr.data_ptr(), xt.data_ptr(), yr.data_ptr(), yt.data_ptr(), xyz.data_ptr(), R, M, gamma, lse.data_ptr(),
+                                   kb.data_ptr(), gx.data_ptr(), part.data_ptr(), gy.data_ptr(), _stream()), "gdm_soft_coord_bwd_hip")
+    return gx, gy
+
+
+@_soft_coord_bwd.register_fake
+def _(xr, xt, yr, yt, xyz, lse, kb, M, gamma):
+    return lse.new_empty((lse.shape[0], 128)), lse.new_empty((M, 128))
+
+
+def _soft_coord_setup(ctx, inputs, output):
+    x, y, xyz, gamma = inputs
+    lse, soft, xr, xt, yr, yt = output
+    ctx.save_for_backward(xr, xt, yr, yt, xyz, lse, soft)
+    ctx.gamma, ctx.M = gamma, y.shape[0]
+
+
+def _soft_coord_backward(ctx, g_lse, g_soft, *unused):
+    xr, xt, yr, yt, xyz, lse, soft = ctx.saved_tensors
+    a = g_lse.to(torch.float32)
+    b = g_soft.to(torch.float32)
+    k = a - (b * soft).sum(dim=1)                                  # k_r = a_r - b_r . soft_r
+    kb = torch.cat([k.unsqueeze(1), b], dim=1).contiguous()        # [R,4]
+    gx, gy = _soft_coord_bwd(xr, xt, yr, yt, xyz, lse, kb, ctx.M, ctx.gamma)
+    return gx, gy, None, None
+
+
+_soft_coord_fwd.register_autograd(_soft_coord_backward, setup_context=_soft_coord_setup)
+
+
+def soft_coord_match(x, y, xyz, gamma=16.0):
+    """The differentiable soft assignment of unit scene rows x f32[R,128] over the unit vertex rows y f32[M,128] with coordinates
+    xyz f32[M,3], WITHOUT the [R, M] similarity matrix (csrc/gdm_softcoord.hip, forward and backward on the matrix cores):
+        lse_r = log sum_c exp(gamma <x_r, y_c>)            f32[R]
+        soft_r = sum_c softmax_c(gamma <x_r, y_c>) xyz_c    f32[R,3]   the expected model coordinate
+    over exactly the M vertices; 0 < gamma <= 40.  Differentiable w.r.t. x and y (not xyz); normalisation stays with the caller's
+    autograd, as for circle_match.  loss.soft_coord_reference states the same in plain torch."""
+    gamma = float(gamma)
+    if not (0.0 < gamma <= SOFT_COORD_MAX_GAMMA):                  # NaN fails both comparisons; refused before any launch
+        raise ValueError("soft_coord_match: gamma=%r outside (0, %g]" % (gamma, SOFT_COORD_MAX_GAMMA))
+    x = _dev(x, torch.float32, "x")
+    y = _dev(y, torch.float32, "y")
+    xyz = _dev(xyz, torch.float32, "xyz")
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != 128 or y.shape[1] != 128 or x.shape[0] < 1 or y.shape[0] < 1:
+        raise ValueError("soft_coord_match: x [R,128] and y [M,128] with R, M >= 1, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    if tuple(xyz.shape) != (y.shape[0], 3):
+        raise ValueError("soft_coord_match: xyz must be [M,3] = [%d,3], got %s" % (y.shape[0], tuple(xyz.shape)))
+    lse, soft = _soft_coord_fwd(x, y, xyz.detach(), gamma)[:2]
+    return lse, soft
+
+
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 
 

@@ -117,7 +117,21 @@ def build_parser():
                    help="train: 'loader' = labels / match_idx / visible_flag come with the items; 'device' = computed on the GPU from the "
                         "items' RT and origin_labels (get_pose_gt_info, linemod_pbr.py:602-655; targets.pose_gt_info), invalid items "
                         "replaced by the batch's first valid one")
+    p.add_argument("--soft-gamma", dest="soft_gamma", type=float, default=16.0,
+                   help="train: temperature of the soft-assignment losses (0 < gamma <= 40; loss.SoftAssignLoss)")
+    p.add_argument("--soft-xyz-weight", dest="soft_xyz_weight", type=float, default=0.0,
+                   help="train: weight of the expected-vertex regression (smooth L1, metres) added to the loss; 0 = off")
+    p.add_argument("--soft-nll-weight", dest="soft_nll_weight", type=float, default=0.0,
+                   help="train: weight of the negative log-likelihood of the ground-truth vertex under the soft assignment; 0 = off")
     return p
+
+
+def _set_soft_losses(model, args):
+    """--soft-gamma / --soft-xyz-weight / --soft-nll-weight onto the model; with both weights 0 the class defaults stay untouched."""
+    wx, wn = float(getattr(args, "soft_xyz_weight", 0.0)), float(getattr(args, "soft_nll_weight", 0.0))
+    if wx != 0 or wn != 0:
+        model.soft_gamma, model.soft_xyz_weight, model.soft_nll_weight = float(getattr(args, "soft_gamma", 16.0)), wx, wn
+    return model
 
 
 class BNMomentumScheduler:
@@ -293,18 +307,20 @@ class Trainer:
                         out, _ = model_fn_dec(self.model, batch, self.device, self.gt_targets, self.replaced)
                     loss = out["loss"]
                     vals = torch.stack([loss.detach().float(), out["seg_loss"].detach().float(),
-                                        torch.as_tensor(out["match_loss"], device=loss.device).detach().float()])
+                                        torch.as_tensor(out["match_loss"], device=loss.device).detach().float()]
+                                       + [out[k].detach().float() for k in ("soft_xyz_loss", "soft_nll_loss") if k in out])
                     sums = vals if sums is None else sums + vals
                     dev_hist.append(vals)
                     if (it + 1) % self.log_every == 0:
                         self._flush_history(dev_hist)            # the one host read of this log window; frees the per-iteration scalars
+                        soft = " soft_xyz: {:.6f} soft_nll: {:.4f}" if sums.numel() == 5 else ""     # the soft-assignment losses, when on
                         if self.local_rank == 0 and self.replaced is not None:
                             rd = self._replaced_counter()
                             vals = torch.cat([sums / self.log_every, rd.to(sums.dtype)]).tolist()     # one read: sums and counter
-                            print("avg_loss:{:.4f} seg: {:.4f} match: {:.4f}  invalid items replaced: {:.0f} unreplaced: {:.0f}  "
-                                  "time cost:{:.1f} s".format(*vals, time.time() - t0))
+                            print(("avg_loss:{:.4f} seg: {:.4f} match: {:.4f}" + soft + "  invalid items replaced: {:.0f} unreplaced: {:.0f}  "
+                                   "time cost:{:.1f} s").format(*vals, time.time() - t0))
                         elif self.local_rank == 0:
-                            print("avg_loss:{:.4f} seg: {:.4f} match: {:.4f}  time cost:{:.1f} s".format(
+                            print(("avg_loss:{:.4f} seg: {:.4f} match: {:.4f}" + soft + "  time cost:{:.1f} s").format(
                                 *(sums / self.log_every).tolist(), time.time() - t0))
                         sums = None
                         t0 = time.time()
@@ -331,7 +347,7 @@ class Trainer:
             return self.graphed_step.replaced
         return self.replaced
 
-    HISTORY_CAP = 100000          # `history` keeps the most recent iterations' (loss, seg, match) triples
+    HISTORY_CAP = 100000          # `history` keeps the most recent iterations' (loss, seg, match[, soft_xyz, soft_nll]) tuples
 
     def _flush_history(self, dev_hist):
         if dev_hist:
@@ -370,9 +386,9 @@ def build_model(args, cls_id, cache_mesh_in_eval=False):
         from .geoMatch_DGCNN import GeoMatch as GeoMatchDGCNN
         model = GeoMatchDGCNN(make_dgcnn_cfg(n_mesh_node=args.n_mesh, dataset=args.dataset_name), cls_id, model_points=pts)
         model.train_path = getattr(args, "dgcnn_train_path", "modules")
-        return _set_mesh_train_path(model, args)
+        return _set_soft_losses(_set_mesh_train_path(model, args), args)
     cfg = make_model_cfg(n_mesh_node=args.n_mesh, num_points=args.n_points, dataset=args.dataset_name)
-    return _set_mesh_train_path(GeoMatch(cfg, cls_id, model_points=pts, cache_mesh_in_eval=cache_mesh_in_eval), args)
+    return _set_soft_losses(_set_mesh_train_path(GeoMatch(cfg, cls_id, model_points=pts, cache_mesh_in_eval=cache_mesh_in_eval), args), args)
 
 
 def _set_mesh_train_path(model, args):

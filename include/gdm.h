@@ -365,6 +365,28 @@ int gdm_circle_match_bwd2_hip(const void* xrows, const void* xtp, const float* x
 int gdm_circle_match_bwd_parts(int R, int M);
 
 /* ---------------------------------------------------------------------------------------
+ * Differentiable soft assignment without the similarity matrix (gdm_softcoord.hip): the training half of the soft matching above.
+ * Operands are the buffers gdm_circle_match_pack_hip writes for the UNIT rows x f32[R,128] (xrows, xtp) and y f32[M,128] (yrows,
+ * ytp); xyz f32[M,3].  With s_rc = x_r . y_c (split-bf16 products, fp32 accumulation), over exactly the M real columns:
+ *   fwd    Z_r = sum_c exp(gamma (s_rc - 1));  lse f32[R]: lse_r = gamma + log Z_r;
+ *          soft f32[R,3]: soft_r = sum_c exp(gamma (s_rc - 1)) xyz_c / Z_r
+ *   bwd    lse f32[R] of fwd, kb f32[R,4] = (k_r, b_r) with a_r = dL/dlse_r, b_r = dL/dsoft_r, k_r = a_r - b_r . soft_r;
+ *          p_rc = exp(gamma s_rc - lse_r), G_rc = dL/ds_rc = gamma p_rc (k_r + b_r . xyz_c);
+ *          gx f32[R,128]: gx_r = sum_c G_rc y_c;  gy f32[M,128]: gy_c = sum_r G_rc x_r (no gradient for xyz).
+ *          gy_part f32[P][Mp,128] is workspace, Mp = M rounded up to 128, P = parts(R, M): partial sums over slices of the rows,
+ *          added in ascending P.  No atomics: two runs are bit-identical.
+ *          gx or gy may be NULL (not both): that gradient's launches are skipped (gy_part is needed with gy only).
+ * Padded columns weigh nothing and padded rows add nothing, whatever lies beyond R in the caller's buffers (those are not read).
+ * 0 < gamma <= GDM_SOFT_COORD_MAX_GAMMA (every term >= e^-80, a normal fp32: the fixed shift 1 needs no running maximum);
+ * anything else, a NaN included, is refused with GDM_EINVAL before any launch. */
+#define GDM_SOFT_COORD_MAX_GAMMA 40.0f
+int gdm_soft_coord_fwd_hip(const void* xrows, const void* xtp, const void* yrows, const void* ytp, const float* xyz, int R, int M,
+                           float gamma, float* lse, float* soft, void* stream);
+int gdm_soft_coord_bwd_hip(const void* xrows, const void* xtp, const void* yrows, const void* ytp, const float* xyz, int R, int M,
+                           float gamma, const float* lse, const float* kb, float* gx, float* gy_part, float* gy, void* stream);
+int gdm_soft_coord_bwd_parts(int R, int M);
+
+/* ---------------------------------------------------------------------------------------
  * One attentive-pooling stage of RandLA-Net's local feature aggregation in a single launch (inference):
  * models/RandLA/RandLANet.py:700-718 Building_block.forward = two such stages; :720-727 relative_pos_encoding, :729-738
  * gather_neighbour, :747-754 Att_pooling.forward.  For every point i with neighbours idx[b,i,0..15]:
