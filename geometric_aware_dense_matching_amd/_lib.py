@@ -125,6 +125,8 @@ SIGNATURES = {
     "gdm_icp_transform_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _i, _i, _vp, _vp]),
     "gdm_icp_update_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, ctypes.c_double, _i, _vp, _vp, _vp, _vp,
                                 _vp]),
+    "gdm_icp_plane_update_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdm_targets_workspace_bytes": (_sz, [_i, _i, _i]),
     "gdm_hpr_visible_hip": (_i, [_vp, ctypes.c_long, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "gdm_pose_targets_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i, _i, ctypes.c_double, _vp, _sz,

@@ -11,6 +11,8 @@
 // ICP (pvn3d_eval_utils_kpls.py:126-212 icp) runs scene -> model: icp_transform_kernel maps the selected scene points into the model
 // frame, the exact kNN (K = 1) finds the nearest vertex, icp_update_kernel refits the absolute pose from (model[nn], scene) in fp64
 // and applies the reference's convergence rule per crop, freezing a crop on the device once it stops.
+// icp_plane_update_kernel is the opt-in point-to-plane refiner (no counterpart in the reference): the same transform and search, then one
+// Gauss-Newton step on n . (x - q) with optional normal gating and Huber weights, frozen and flagged when the crop is degenerate.
 #include "gdm_common.h"
 
 namespace {
@@ -306,6 +308,89 @@ __global__ __launch_bounds__(256) void icp_update_kernel(const float* __restrict
     err[b] = mean;
 }
 
+// One point-to-plane Gauss-Newton iteration of every active crop (include/gdm.h gdm_icp_plane_update_hip): x = query (the scene
+// point in the model frame), q / n = the nearest vertex and its unit normal, r = n . (x - q), J = [x cross n ; n].  Per thread 30 fp64
+// sums { A = sum w J J^T (upper triangle, 21), g = sum w J r (6), S = sum w, L2 = sum w |x|^2, E = sum |r| } and the pair count, reduced
+// in the fixed order of block_sum; thread 0 solves (gdm_icp_plane_solve.inc) and applies the stop rule of icp_update_kernel.
+__global__ __launch_bounds__(256) void icp_plane_update_kernel(const float* __restrict__ scene_nrm, long scene_bstride, int pt_stride,
+                                                               int ch_stride, const float* __restrict__ query,
+                                                               const float* __restrict__ model_xyz, const float* __restrict__ model_nrm,
+                                                               const int32_t* __restrict__ nn, const float* __restrict__ d2,
+                                                               const uint8_t* __restrict__ mask, int N, int M, float reject2,
+                                                               double normal_gate, double huber_delta, double tolerance, int min_points,
+                                                               double pivot_min, float* __restrict__ RT, uint8_t* __restrict__ active,
+                                                               int32_t* __restrict__ iters, double* __restrict__ err,
+                                                               int32_t* __restrict__ status, int32_t* __restrict__ n_kept)
+{
+    __shared__ double red[4][30];
+    __shared__ int cred[4];
+    const int b = blockIdx.x;
+    if (!active[b]) return;                                         // block-uniform
+    double rt[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) rt[e] = (double)RT[(long)b * 12 + e];
+    const float* sn = scene_nrm ? scene_nrm + (long)b * scene_bstride : nullptr;
+    double acc[30];
+#pragma unroll
+    for (int i = 0; i < 30; ++i) acc[i] = 0.0;
+    int cnt = 0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        if (!mask[(long)b * N + i]) continue;
+        const float dd = fmaxf(d2[(long)b * N + i], 0.f);
+        if (reject2 >= 0.f && !(dd <= reject2)) continue;
+        int j = nn[(long)b * N + i];
+        j = min(max(j, 0), M - 1);
+        const double nx = (double)model_nrm[3 * j], ny = (double)model_nrm[3 * j + 1], nz = (double)model_nrm[3 * j + 2];
+        if (sn) {                                                   // (R^T s) . n >= normal_gate keeps the pair
+            const double sx = (double)sn[(long)i * pt_stride], sy = (double)sn[(long)i * pt_stride + ch_stride],
+                         sz = (double)sn[(long)i * pt_stride + 2 * ch_stride];
+            const double mx = rt[0] * sx + rt[4] * sy + rt[8] * sz;
+            const double my = rt[1] * sx + rt[5] * sy + rt[9] * sz;
+            const double mz = rt[2] * sx + rt[6] * sy + rt[10] * sz;
+            if (!(mx * nx + my * ny + mz * nz >= normal_gate)) continue;
+        }
+        const float* xq = query + ((long)b * N + i) * 3;
+        const double x = (double)xq[0], y = (double)xq[1], z = (double)xq[2];
+        const double r = nx * (x - (double)model_xyz[3 * j]) + ny * (y - (double)model_xyz[3 * j + 1]) +
+                         nz * (z - (double)model_xyz[3 * j + 2]);
+        const double ar = fabs(r);
+        const double w = (huber_delta <= 0.0 || ar <= huber_delta) ? 1.0 : huber_delta / ar;
+        const double J[6] = {y * nz - z * ny, z * nx - x * nz, x * ny - y * nx, nx, ny, nz};
+        int e = 0;
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+            const double wj = w * J[p];
+#pragma unroll
+            for (int q = p; q < 6; ++q) acc[e++] += wj * J[q];
+            acc[21 + p] += wj * r;
+        }
+        acc[27] += w;
+        acc[28] += w * (x * x + y * y + z * z);
+        acc[29] += ar;
+        cnt += 1;
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = cnt;      // visible after block_sum's barrier
+    double tot[30];
+    block_sum<30>(acc, red, tot);
+    if (threadIdx.x != 0) return;
+    const int n_pairs = cred[0] + cred[1] + cred[2] + cred[3];
+    if (n_kept) n_kept[b] = n_pairs;
+    if (n_pairs < max(min_points, 6)) { active[b] = 0; status[b] = 2; return; }
+    const double* ps = tot;
+#include "gdm_icp_plane_solve.inc"
+    if (degenerate) { active[b] = 0; status[b] = 3; return; }
+    float* o = RT + (long)b * 12;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) o[4 * i + j] = (float)Rn[i][j];
+        o[4 * i + 3] = (float)tn[i];
+    }
+    iters[b] += 1;
+    const double mean = tot[29] / (double)n_pairs;
+    if (fabs(err[b] - mean) < tolerance) { active[b] = 0; status[b] = 1; }
+    err[b] = mean;
+}
+
 struct RansacWs {
     float* pts;
     float* hyp;
@@ -393,4 +478,28 @@ extern "C" int gdm_icp_update_hip(const float* scene_xyz, long scene_bstride, in
     hipLaunchKernelGGL(icp_update_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scene_xyz, scene_bstride, pt_stride, ch_stride,
                        model_xyz, nn, d2, mask, N, M, reject2, tolerance, min_points, RT, active, iters, err);
     return gdm_launch_status("icp_update_kernel");
+}
+
+extern "C" int gdm_icp_plane_update_hip(const float* scene_nrm, long scene_bstride, int pt_stride, int ch_stride, const float* query,
+                                        const float* model_xyz, const float* model_nrm, const int32_t* nn, const float* d2,
+                                        const uint8_t* mask, int B, int N, int M, float reject_dist, double normal_gate,
+                                        double huber_delta, double tolerance, int min_points, double pivot_min, float* RT,
+                                        uint8_t* active, int32_t* iters, double* err, int32_t* status, int32_t* n_pairs,
+                                        void* stream)
+{
+    GDM_CHECK_ARG(query && model_xyz && model_nrm && nn && d2 && mask && RT && active && iters && err && status,
+                  "gdm_icp_plane_update_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_icp_plane_update_hip: bad shape B=%d N=%d M=%d", B, N, M);
+    GDM_CHECK_ARG(!scene_nrm || (pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0), "gdm_icp_plane_update_hip: bad scene strides");
+    GDM_CHECK_ARG(!scene_nrm || (normal_gate >= -1.0 && normal_gate <= 1.0), "gdm_icp_plane_update_hip: normal_gate=%g not in [-1, 1]",
+                  normal_gate);
+    GDM_CHECK_ARG(tolerance >= 0.0, "gdm_icp_plane_update_hip: tolerance=%g must be >= 0", tolerance);
+    GDM_CHECK_ARG(min_points >= 1, "gdm_icp_plane_update_hip: min_points=%d must be >= 1", min_points);
+    GDM_CHECK_ARG(pivot_min > 0.0, "gdm_icp_plane_update_hip: pivot_min=%g must be > 0", pivot_min);
+    GDM_CHECK_ARG(huber_delta == huber_delta, "gdm_icp_plane_update_hip: huber_delta is NaN");
+    const float reject2 = reject_dist >= 0.f ? reject_dist * reject_dist : -1.f;
+    hipLaunchKernelGGL(icp_plane_update_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scene_nrm, scene_bstride, pt_stride,
+                       ch_stride, query, model_xyz, model_nrm, nn, d2, mask, N, M, reject2, normal_gate, huber_delta, tolerance,
+                       min_points, pivot_min, RT, active, iters, err, status, n_pairs);
+    return gdm_launch_status("icp_plane_update_kernel");
 }

@@ -12,12 +12,17 @@ from . import frontend, matching, ops, pose, pyramid, settings
 _PREC = {"bf16x3": ops.MATCH_BF16X3, "f32": ops.MATCH_F32, 0: 0, 1: 1}
 
 
+def _plane_normals(model, pose_opts):
+    """The model's unit normals when pose_opts asks for point-to-plane ICP (cached on the mesh branch: normalised once per model)."""
+    return model.model_emb.unit_normals() if (pose_opts or {}).get("icp_metric") == "plane" else None
+
+
 def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf16x3", pose_fit="kabsch", icp_iters=0, pose_opts=None,
                      match_gamma=None):
     """model_dict: {cls_id: GeoMatch (eval, on the GPU)}; inputs: dict of batched device tensors (loader keys, plus
     `dpt_xyz` when the neighbour pyramid is not already in it); cls_ids: int tensor/list [bs].  pose_fit / icp_iters / pose_opts:
     pose.estimate_poses (the defaults are the plain Kabsch fit).  match_gamma: soft matching at that temperature (pipeline_step).
-    Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, lse, conf, soft_xyz, score][, RT, valid[, icp_iters, icp_resid]])."""
+    Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, lse, conf, soft_xyz, score][, RT, valid[, icp_iters, icp_resid[, icp_status]]])."""
     cls = torch.as_tensor(cls_ids).cpu().tolist()
     bs = len(cls)
     out = {}
@@ -38,7 +43,8 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
             if soft is not None:
                 part.update(lse=res["lse"], conf=res["conf"], soft_xyz=res["soft_xyz"], score=ops.match_score(res["conf"], res["mask"]))
             if with_pose:
-                part.update(pose.estimate_poses(res, sub["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts))
+                part.update(pose.estimate_poses(res, sub["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts,
+                                                _plane_normals(model, pose_opts)))
             for k, v in part.items():
                 out.setdefault(k, []).append(v)
             order += sel
@@ -54,7 +60,7 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
     loader's index arrays) -> GeoMatch.forward (eval) -> seg mask + descriptor packs + N x M arg-max (evaluator.py:78-93) [-> pose].
     Everything is enqueued on the current stream (and, with settings.USE_SIDE_STREAMS, on side streams forked from and joined back to
     it) with no host synchronisation, so the call captures in a hipGraph as it is.  Returns dict(seg, rgbd, mesh, mask, count,
-    best_idx, best_sim[, RT, valid[, icp_iters, icp_resid]]) plus the 30 pyramid arrays when keep_pyramid.  The pose stage is
+    best_idx, best_sim[, RT, valid[, icp_iters, icp_resid[, icp_status]]]) plus the 30 pyramid arrays when keep_pyramid.  The pose stage is
     pose.estimate_poses(pose_fit, icp_iters, pose_opts): RANSAC and ICP run on the device too, with no host branching.
     match_gamma = None: the arg-max kernel, as ever.  With a temperature the soft kernel takes its place (same best_idx / best_sim)
     and the outputs gain lse, conf, soft_xyz (include/gdm.h gdm_match_soft_packed_hip) and score f32[B] = the mean of conf over the
@@ -80,7 +86,8 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
         out = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=mask, count=count, best_idx=bi, best_sim=bs, lse=lse,
                    conf=conf, soft_xyz=sxyz, score=ops.match_score(conf, mask))
     if with_pose:
-        out.update(pose.estimate_poses(out, d["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts))
+        out.update(pose.estimate_poses(out, d["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts,
+                                       _plane_normals(model, pose_opts)))
     if keep_pyramid and pyr is not None:
         out.update((k, v) for k, v in pyr.items() if torch.is_tensor(v))
     return out

@@ -9,6 +9,7 @@ The reference does this on `bs` host threads with numpy (ThreadPoolExecutor, eva
 Opt-in robust variants (csrc/gdm_pose_robust.hip), also on the device and capturable in a hipGraph:
   utils/pvn3d_eval_utils_kpls.py:79-124 best_fit_transform_with_RANSAC   solve_poses(method="ransac") / ransac_poses
   utils/pvn3d_eval_utils_kpls.py:126-212 icp (point to point)              refine_icp
+and, with no counterpart in the reference, point-to-plane ICP with normal gating and Huber weights: refine_icp_plane.
 """
 import numpy as np
 import torch
@@ -213,17 +214,222 @@ def refine_icp(RT, valid, cld_rgb_nrm, mask, model_xyz, iters=20, tolerance=0.00
     return RT, n_iter, err.float()
 
 
-def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, pose_opts=None):
+ICP_STATUS = {0: "running or never run", 1: "converged", 2: "starved", 3: "degenerate"}
+
+
+def refine_icp_plane(RT, valid, cld_rgb_nrm, mask, model_xyz, model_nrm, iters=10, tolerance=1e-4, reject_dist=None, normal_gate=None,
+                     huber=None, min_points=6, pivot_min=1e-6):
+    """Point-to-plane ICP from the poses RT f32[B,3,4] (include/gdm.h gdm_icp_plane_update_hip): refine_icp's transform
+    and exact K = 1 search, then one Gauss-Newton step per crop on n . (x - q) with the model's unit normals model_nrm f32[M,3].
+    reject_dist (m) drops far pairs, normal_gate (a cosine) drops pairs whose scene normal (rows 6..8 of cld_rgb_nrm, turned into the
+    model frame) and model normal agree less than that, huber (m) down-weights residuals above it; None turns each off.  Exactly
+    `iters` iterations are enqueued, with no host synchronisation (the step captures in a hipGraph).  A crop stops on the device when
+    it converges (|prev_mean - mean| < tolerance, status 1), has fewer than max(min_points, 6) pairs (2) or is degenerate (3: a
+    plane, a sphere, a body of revolution; the unit-free pivot test of DESIGN.md 6b) -- in the last two cases with its pose unchanged.
+    -> RT f32[B,3,4] (a new tensor), iterations run i32[B], final mean |n . (x - q)| f32[B], status i32[B]."""
+    B, N = mask.shape
+    dev = mask.device
+    cld, sb, ps, cs = _scene_args(cld_rgb_nrm)
+    model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
+    model_nrm = ops._dev(model_nrm, torch.float32, "model_nrm")
+    M = model_xyz.shape[0]
+    if tuple(model_nrm.shape) != (M, 3):
+        raise ValueError("refine_icp_plane: model_nrm is %s, expected %s" % (tuple(model_nrm.shape), (M, 3)))
+    if normal_gate is not None and cld.shape[1] < 9:
+        raise ValueError("refine_icp_plane: normal_gate needs the scene normals in rows 6..8 of cld_rgb_nrm")
+    mask = mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)
+    mask = ops._dev(mask, torch.uint8, "mask")
+    RT = ops._dev(RT, torch.float32, "RT").clone()
+    active = valid.to(torch.uint8).contiguous().clone()
+    n_iter = torch.zeros((B,), dtype=torch.int32, device=dev)
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    err = torch.zeros((B,), dtype=torch.float64, device=dev)
+    if int(iters) <= 0:
+        return RT, n_iter, err.float(), status
+    query = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    nn = torch.empty((B, N, 1), dtype=torch.int32, device=dev)
+    d2 = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
+    job = (_lib.KnnJob * 1)()
+    job[0].support, job[0].query, job[0].idx, job[0].d2 = model_xyz.data_ptr(), query.data_ptr(), nn.data_ptr(), d2.data_ptr()
+    job[0].support_bstride, job[0].query_bstride = 0, N * 3
+    job[0].S, job[0].Q, job[0].K, job[0].grid_w = M, N, 1, 0
+    L = _lib.lib()
+    reject = -1.0 if reject_dist is None else float(reject_dist)
+    snrm = None if normal_gate is None else cld.data_ptr() + 6 * cs * cld.element_size()
+    gate = 0.0 if normal_gate is None else float(normal_gate)
+    delta = 0.0 if huber is None else float(huber)
+    for _ in range(int(iters)):
+        check(L.gdm_icp_transform_hip(cld.data_ptr(), sb, ps, cs, RT.data_ptr(), B, N, query.data_ptr(), ops._stream()),
+              "gdm_icp_transform_hip")
+        check(L.gdm_knn_jobs_ws_hip(job, 1, B, None, 0, ops._stream()), "gdm_knn_jobs_ws_hip")
+        check(L.gdm_icp_plane_update_hip(snrm, sb, ps, cs, query.data_ptr(), model_xyz.data_ptr(), model_nrm.data_ptr(), nn.data_ptr(),
+                                         d2.data_ptr(), mask.data_ptr(), B, N, M, reject, gate, delta, float(tolerance), int(min_points),
+                                         float(pivot_min), RT.data_ptr(), active.data_ptr(), n_iter.data_ptr(), err.data_ptr(),
+                                         status.data_ptr(), None, ops._stream()), "gdm_icp_plane_update_hip")
+    return RT, n_iter, err.float(), status
+
+
+def _nearest_two(query, model, chunk=512):
+    """The two nearest model vertices of every query row by brute force, in chunks: the four best candidates by the expanded form
+    |q|^2 - 2 q.m + |m|^2 (one matrix product), then their distances as sqrt(sum (q - m)^2) in fp64, which decide.
+    -> nn i64[n], d1 f64[n], d2nd f64[n] (distances; inf without a second vertex)."""
+    n, M = len(query), len(model)
+    k = min(4, M)
+    nn = np.zeros(n, np.int64)
+    d1, d2nd = np.zeros(n), np.full(n, np.inf)
+    m2 = (model * model).sum(1)
+    for s in range(0, n, chunk):
+        q = query[s:s + chunk]
+        approx = (q * q).sum(1)[:, None] - 2.0 * (q @ model.T) + m2[None, :]
+        cand = np.argpartition(approx, k - 1, axis=1)[:, :k] if k < M else np.tile(np.arange(M), (len(q), 1))
+        cand.sort(axis=1)                                            # ties go to the lowest index
+        dd = np.sqrt(((q[:, None, :] - model[cand]) ** 2).sum(2))
+        order = np.argsort(dd, axis=1, kind="stable")
+        r = np.arange(len(q))
+        nn[s:s + chunk], d1[s:s + chunk] = cand[r, order[:, 0]], dd[r, order[:, 0]]
+        if k > 1:
+            d2nd[s:s + chunk] = dd[r, order[:, 1]]
+    return nn, d1, d2nd
+
+
+def icp_plane_solve_numpy(A, g, S, L2, R, t, pivot_min=1e-6):
+    """fp64 restatement of csrc/gdm_icp_plane_solve.inc: A [6,6], g [6], S = sum w, L2 = sum w |x|^2, pose (R [3,3], t [3]) ->
+    dict degenerate, min_pivot (smallest Cholesky pivot L_kk^2 of D A D / S reached), xi [6], R, t (new; the old ones when degenerate)."""
+    A, g = np.asarray(A, np.float64), np.asarray(g, np.float64)
+    R, t = np.asarray(R, np.float64), np.asarray(t, np.float64)
+    out = dict(degenerate=True, min_pivot=np.inf, xi=np.zeros(6), R=R.copy(), t=t.copy())
+    l2 = L2 / S if S != 0 else np.nan
+    if not l2 > 0.0:
+        return out
+    D = np.array([1.0 / np.sqrt(l2)] * 3 + [1.0] * 3)
+    Ah = A * D[:, None] * D[None, :] / S
+    L = np.zeros((6, 6))
+    for k in range(6):
+        p = Ah[k, k] - (L[k, :k] ** 2).sum()
+        out["min_pivot"] = min(out["min_pivot"], p)
+        if not p >= pivot_min:
+            return out
+        L[k, k] = np.sqrt(p)
+        for i in range(k + 1, 6):
+            L[i, k] = (Ah[i, k] - (L[i, :k] * L[k, :k]).sum()) / L[k, k]
+    y = np.linalg.solve(L.T, np.linalg.solve(L, -g * D / S))
+    xi = y * D
+    w, v = xi[:3], xi[3:]
+    th = np.linalg.norm(w)
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    Ri = np.eye(3) + K if th < 1e-8 else np.eye(3) + np.sin(th) / th * K + (1.0 - np.cos(th)) / (th * th) * (K @ K)
+    Rn = R @ Ri.T
+    out.update(degenerate=False, xi=xi, R=Rn, t=t - Rn @ v)
+    return out
+
+
+def icp_plane_step_numpy(scene, scene_nrm, model_xyz, model_nrm, RT, mask=None, reject_dist=None, normal_gate=None, huber=None,
+                         min_points=6, pivot_min=1e-6, nn=None, d2=None, margin=1e-6):
+    """One point-to-plane iteration (include/gdm.h gdm_icp_plane_update_hip) restated in fp64 numpy.  scene [N,3] and scene_nrm [N,3]
+    (None without a gate) in the camera frame, model_xyz / model_nrm [M,3], RT [3,4] (model -> camera), mask [N].  The pairs come from a
+    brute-force nearest-vertex search of x = R^T (s - t), or from nn [N] / d2 [N] (squared distances, compared in fp32 as the kernel
+    does) when given -- the device's search, so that a near tie between two vertices cannot part the two computations.
+    -> dict RT [3,4] (new; unchanged when status != 0), status (0, 2 starved, 3 degenerate), n (pairs kept), mean (mean |r|), xi,
+    min_pivot, keep bool[N], rows (sqrt(w) J [n,6]) and rhs (sqrt(w) r [n]) of the kept pairs, w, r, nn_ref / dist_ref (the brute-force
+    search), ties (masked queries whose two nearest vertices are within `margin`), near_reject / near_gate (masked pairs within
+    `margin` of the reject distance / gate cosine)."""
+    scene, model_xyz, model_nrm = (np.asarray(a, np.float64) for a in (scene, model_xyz, model_nrm))
+    RT = np.asarray(RT, np.float64)
+    R, t = RT[:, :3], RT[:, 3]
+    N, M = len(scene), len(model_xyz)
+    sel = np.ones(N, bool) if mask is None else np.asarray(mask) != 0
+    x = (scene - t) @ R
+    nn_ref, dist_ref, dist_2nd = _nearest_two(x, model_xyz)
+    ties = int((sel & (dist_2nd - dist_ref < margin)).sum())
+    if nn is None:
+        j, dist = nn_ref, dist_ref
+        far = np.zeros(N, bool) if reject_dist is None else dist * dist > float(reject_dist) ** 2
+    else:
+        j = np.clip(np.asarray(nn, np.int64).reshape(N), 0, M - 1)
+        dd = np.maximum(np.asarray(d2, np.float32).reshape(N), np.float32(0))
+        dist = np.sqrt(dd.astype(np.float64))
+        far = np.zeros(N, bool) if reject_dist is None else ~(dd <= np.float32(reject_dist) * np.float32(reject_dist))
+    near_reject = 0 if reject_dist is None else int((sel & (np.abs(dist - float(reject_dist)) < margin)).sum())
+    q, n = model_xyz[j], model_nrm[j]
+    keep = sel & ~far
+    near_gate = 0
+    if normal_gate is not None:
+        cosang = ((np.asarray(scene_nrm, np.float64) @ R) * n).sum(1)
+        near_gate = int((keep & (np.abs(cosang - float(normal_gate)) < margin)).sum())
+        keep &= cosang >= float(normal_gate)
+    x, q, n = x[keep], q[keep], n[keep]
+    r = (n * (x - q)).sum(1)
+    ar = np.abs(r)
+    w = np.ones_like(r)
+    if huber is not None and huber > 0:
+        big = ar > huber
+        w[big] = huber / ar[big]
+    J = np.concatenate([np.cross(x, n), n], axis=1)
+    out = dict(RT=RT.copy(), status=0, n=int(keep.sum()), mean=float(ar.mean()) if len(r) else 0.0, xi=np.zeros(6), min_pivot=np.inf,
+               keep=keep, rows=np.sqrt(w)[:, None] * J, rhs=np.sqrt(w) * r, w=w, r=r, nn_ref=nn_ref, dist_ref=dist_ref, ties=ties,
+               near_reject=near_reject, near_gate=near_gate)
+    if out["n"] < max(int(min_points), 6):
+        out["status"] = 2
+        return out
+    sol = icp_plane_solve_numpy((w[:, None] * J).T @ J, (w[:, None] * J).T @ r, w.sum(), (w * (x * x).sum(1)).sum(), R, t, pivot_min)
+    out["min_pivot"] = sol["min_pivot"]
+    if sol["degenerate"]:
+        out["status"] = 3
+        return out
+    out["xi"] = sol["xi"]
+    out["RT"] = np.concatenate([sol["R"], sol["t"][:, None]], axis=1)
+    return out
+
+
+def icp_plane_numpy(scene, scene_nrm, model_xyz, model_nrm, RT0, mask=None, iters=10, tolerance=1e-4, reject_dist=None,
+                    normal_gate=None, huber=None, min_points=6, pivot_min=1e-6, fp32_pose=True):
+    """refine_icp_plane for one crop, free-running, in fp64 numpy: icp_plane_step_numpy with its own search, the pose rounded to fp32
+    after every update as the kernel stores it (fp32_pose), and the stop rule.  -> dict RT, iters, status (0 ran out of iterations,
+    1 converged, 2 starved, 3 degenerate), resid (mean |r| of the last iteration run), and per iteration run: n, mean, min_pivot, ties,
+    near_reject, near_gate, stop_margin (| |prev - mean| - tolerance |), RTs."""
+    RT = np.asarray(RT0, np.float64).copy()
+    out = dict(status=0, iters=0, resid=0.0, n=[], mean=[], min_pivot=[], ties=[], near_reject=[], near_gate=[], stop_margin=[], RTs=[])
+    prev = 0.0
+    for _ in range(int(iters)):
+        s = icp_plane_step_numpy(scene, scene_nrm, model_xyz, model_nrm, RT, mask, reject_dist, normal_gate, huber, min_points, pivot_min)
+        if s["status"] != 0:
+            out["status"] = s["status"]
+            break
+        RT = s["RT"].astype(np.float32).astype(np.float64) if fp32_pose else s["RT"]
+        out["iters"] += 1
+        out["resid"] = s["mean"]
+        for k in ("n", "mean", "min_pivot", "ties", "near_reject", "near_gate"):
+            out[k].append(s[k])
+        out["stop_margin"].append(abs(abs(prev - s["mean"]) - tolerance))
+        out["RTs"].append(RT)
+        if abs(prev - s["mean"]) < tolerance:
+            out["status"] = 1
+            break
+        prev = s["mean"]
+    out["RT"] = RT
+    return out
+
+
+def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, pose_opts=None, model_nrm=None):
     """The pose stage of the pipeline: solve_poses with `pose_fit` ("kabsch" | "ransac"), then `icp_iters` ICP iterations when > 0.
     pose_opts (optional dict): ransac_iters, ransac_inlier_dist, ransac_fix_percent, seed, icp_tolerance, icp_reject_dist,
     min_points, and for pose_fit="kabsch" weights ("none" | "conf") and targets ("vertex" | "soft") (solve_poses; RANSAC and ICP
-    keep the hard pairs).  -> dict(RT, valid[, icp_iters, icp_resid])."""
+    keep the hard pairs); icp_metric ("point" | "plane"): "plane" refines with refine_icp_plane instead of refine_icp, needs the
+    model's unit normals model_nrm f32[M,3], takes icp_huber and icp_normal_gate as well (icp_tolerance then defaults to 1e-4) and adds
+    icp_status.  -> dict(RT, valid[, icp_iters, icp_resid[, icp_status]])."""
     o = dict(pose_opts or {})
     unknown = set(o) - {"ransac_iters", "ransac_inlier_dist", "ransac_fix_percent", "seed", "icp_tolerance", "icp_reject_dist",
-                        "min_points", "weights", "targets"}
+                        "min_points", "weights", "targets", "icp_metric", "icp_huber", "icp_normal_gate"}
     if unknown:
         raise ValueError("estimate_poses: unknown pose_opts %s" % sorted(unknown))
     min_points = o.get("min_points", 5)
+    metric = o.get("icp_metric", "point")
+    if metric not in ("point", "plane"):
+        raise ValueError("estimate_poses: icp_metric must be 'point' or 'plane', got %r" % (metric,))
+    if metric == "plane" and model_nrm is None:
+        raise ValueError("estimate_poses: icp_metric='plane' needs model_nrm (the model's unit normals)")
+    if metric == "point" and (o.get("icp_huber") is not None or o.get("icp_normal_gate") is not None):
+        raise ValueError("estimate_poses: icp_huber / icp_normal_gate are for icp_metric='plane'")
     if pose_fit == "kabsch":
         RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, weights=o.get("weights", "none"),
                                 targets=o.get("targets", "vertex"))
@@ -232,7 +438,11 @@ def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, 
                                 inlier_dist=o.get("ransac_inlier_dist", 0.015), fix_percent=o.get("ransac_fix_percent", 0.7),
                                 seed=o.get("seed", 0), weights=o.get("weights", "none"), targets=o.get("targets", "vertex"))
     out = dict(RT=RT, valid=valid)
-    if icp_iters > 0:
+    if icp_iters > 0 and metric == "plane":
+        out["RT"], out["icp_iters"], out["icp_resid"], out["icp_status"] = refine_icp_plane(
+            RT, valid, cld_rgb_nrm, res["mask"], model_xyz, model_nrm, icp_iters, o.get("icp_tolerance", 1e-4), o.get("icp_reject_dist"),
+            o.get("icp_normal_gate"), o.get("icp_huber"), min_points)
+    elif icp_iters > 0:
         out["RT"], out["icp_iters"], out["icp_resid"] = refine_icp(RT, valid, cld_rgb_nrm, res["mask"], model_xyz, icp_iters,
                                                                    o.get("icp_tolerance", 0.001), o.get("icp_reject_dist"), min_points)
     return out

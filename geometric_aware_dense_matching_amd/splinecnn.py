@@ -451,6 +451,16 @@ class SplineCNN_Mesh(nn.Module):
             self.register_buffer("sys_idx", idx.to(self.xyz.device))
         self.sys_corr_idx = self.sys_idx
 
+    def unit_normals(self):
+        """The model's vertex normals (columns 6..8 of mesh_graph_x) scaled to unit length, f32[M,3]: what point-to-plane ICP
+        (pose.refine_icp_plane) pairs with `xyz`.  Computed once per model (a zero normal stays zero)."""
+        x = self.mesh_graph_x
+
+        def make():
+            n = x[:, 6:9].float()
+            return (n / n.norm(dim=1, keepdim=True).clamp_min(1e-20)).contiguous()
+        return derived(self, "unit_nrm", (x,), make)
+
     def set_symmetry_transform(self, R, t_mm):
         """sys_idx from a symmetry transform of the model frame (SplineCNN.py:163-169: `sym_transforms[1]` of
         misc.get_symmetry_transformations, t in mm): for every vertex the nearest vertex of the transformed model, by the HIP kNN."""

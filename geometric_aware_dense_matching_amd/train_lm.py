@@ -98,7 +98,15 @@ def build_parser():
                    help="test, --pose-fit kabsch: fit to the arg-max vertex or to the expected model coordinate (needs --match-gamma)")
     p.add_argument("--icp-iters", dest="icp_iters", type=int, default=0,
                    help="test: point-to-point ICP iterations after the fit (pvn3d_eval_utils_kpls.py:126-212); 0 = none")
-    p.add_argument("--icp-tolerance", dest="icp_tolerance", type=float, default=0.001, help="test: ICP convergence tolerance (m)")
+    p.add_argument("--icp-tolerance", dest="icp_tolerance", type=float, default=0.001,
+                   help="test: ICP convergence tolerance (m); --icp-metric plane settles below a millimetre, give it 0.0001")
+    p.add_argument("--icp-metric", dest="icp_metric", type=str, default="point", choices=["point", "plane"],
+                   help="test: the ICP residual -- the reference's point-to-point, or point-to-plane against the model normals "
+                        "(Gauss-Newton; degenerate crops are frozen and flagged in icp_status)")
+    p.add_argument("--icp-huber", dest="icp_huber", type=float, default=None, metavar="M",
+                   help="test, --icp-metric plane: Huber threshold on the point-to-plane residual in metres")
+    p.add_argument("--icp-normal-gate", dest="icp_normal_gate", type=float, default=None, metavar="C",
+                   help="test, --icp-metric plane: drop pairs whose scene and model normals have a cosine below C")
     p.add_argument("--objects-across-gpus", action="store_true",
                    help="train: the dataset's objects are independent jobs (train_ycb.sh:3-9 runs them one after the other): rank r of a "
                         "torch.distributed.run launch trains objects r, r + world, ... on its own GPU as single-process jobs -- no process "
@@ -499,6 +507,10 @@ def test(args):
     pose_kw = dict(pose_fit=args.pose_fit, icp_iters=args.icp_iters,
                    pose_opts=dict(ransac_iters=args.ransac_iters, ransac_inlier_dist=args.ransac_inlier_dist,
                                   icp_tolerance=args.icp_tolerance))
+    if getattr(args, "icp_metric", "point") == "plane":
+        pose_kw["pose_opts"].update(icp_metric="plane", icp_huber=args.icp_huber, icp_normal_gate=args.icp_normal_gate)
+    elif getattr(args, "icp_huber", None) is not None or getattr(args, "icp_normal_gate", None) is not None:
+        raise SystemExit("train_lm test: --icp-huber / --icp-normal-gate go with --icp-metric plane")
     match_gamma = getattr(args, "match_gamma", None)
     soft_pose = (getattr(args, "pose_weights", "none"), getattr(args, "pose_targets", "vertex")) != ("none", "vertex")
     if soft_pose and match_gamma is None:

@@ -466,6 +466,33 @@ int gdm_icp_update_hip(const float* scene_xyz, long scene_bstride, int pt_stride
                        const int32_t* nn, const float* d2, const uint8_t* mask, int B, int N, int M, float reject_dist,
                        double tolerance, int min_points, float* RT, uint8_t* active, int32_t* iters, double* err, void* stream);
 
+/* Point-to-plane ICP refinement, scene -> model (opt-in; no counterpart in the reference).  One iteration = gdm_icp_transform_hip,
+ * the same K = 1 search, gdm_icp_plane_update_hip: one Gauss-Newton step per crop on the point-to-plane residual, in the model frame.
+ * For a crop with active != 0 and pose (R, t) = RT[b] (fp32, widened to fp64):
+ *   Pairs.  For every point i with mask != 0: x = query[b,i] (the fp32 row gdm_icp_transform_hip wrote), j = clamp(nn[b,i], 0, M-1),
+ *     q = model_xyz[j], n = model_nrm[j] (f32[M,3], used as given: the caller supplies unit normals).  The pair is dropped when
+ *     reject_dist >= 0 and max(d2[b,i], 0) > reject_dist^2 (fp32, as gdm_icp_update_hip), or when scene_nrm != NULL and
+ *     (R^T s_i) . n < normal_gate (fp64; s_i = the scene normal of point i, element (b, i, c) at
+ *     scene_nrm[b*scene_bstride + i*pt_stride + c*ch_stride] -- rows 6..8 of cld_rgb_nrm; -1 <= normal_gate <= 1).
+ *     scene_nrm == NULL turns the gate off (the strides and normal_gate are then ignored).
+ *   Sums (fp64, fixed reduction order, no atomics).  r = n . (x - q); w = 1 when huber_delta <= 0 or |r| <= huber_delta, else
+ *     huber_delta / |r|; J = [x cross n ; n];  A = sum w J J^T, g = sum w J r, S = sum w, L2 = sum w |x|^2, E = sum |r|, n_pairs.
+ *   Starved.  n_pairs < max(min_points, 6): active = 0, status = 2, the crop is left unchanged.
+ *   Degenerate (unit-free).  l2 = L2 / S, D = diag(1/sqrt(l2) x3, 1 x3), A^ = D A D / S factored by Cholesky in that order without
+ *     pivoting; l2 <= 0 or a pivot L_kk^2 < pivot_min (> 0; 1e-6 is the package default): active = 0, status = 3, the crop is left
+ *     unchanged (a plane patch, a sphere about the origin, a body of revolution about an axis through it).
+ *   Update.  A xi = -g through that factor, xi = (omega, v); R_inc = exp([omega]x) by Rodrigues (I + [omega]x below |omega| = 1e-8);
+ *     R <- R R_inc^T, t <- t - R_new v, both stored as fp32.
+ *   Stop (as gdm_icp_update_hip).  iters += 1, mean = E / n_pairs; |err - mean| < tolerance sets active = 0 and status = 1; err = mean.
+ * status i32[B] is written only on those three events (start it at 0: 0 = still running or never run); active u8[B], iters i32[B],
+ * err f64[B] are read and written, so a fixed number of iterations runs without host synchronisation.  n_pairs i32[B] (may be
+ * NULL): the pairs kept in this call, written for every crop that was active on entry. */
+int gdm_icp_plane_update_hip(const float* scene_nrm, long scene_bstride, int pt_stride, int ch_stride, const float* query,
+                             const float* model_xyz, const float* model_nrm, const int32_t* nn, const float* d2, const uint8_t* mask,
+                             int B, int N, int M, float reject_dist, double normal_gate, double huber_delta, double tolerance,
+                             int min_points, double pivot_min, float* RT, uint8_t* active, int32_t* iters, double* err,
+                             int32_t* status, int32_t* n_pairs, void* stream);
+
 /* Ground-truth correspondence targets: the reference loader's get_pose_gt_info (datasets/lm/linemod_pbr.py:602-655) for a batch.
  * workspace: device memory, 16-byte aligned, of at least gdm_targets_workspace_bytes(B, N, M) bytes (any N >= 1 for
  * gdm_hpr_visible_hip alone); 0 for a bad shape.  M >= GDM_TARGETS_MIN_M, B <= 65535.
