@@ -1,210 +1,75 @@
-"""ctypes binding of libgdm_hip.so (the C ABI declared in include/gdm.h).
+"""ctypes binding of libgdm_hip.so, derived from the C ABI's own declaration: include/gdm.h is parsed at import into SIGNATURES,
+the job structures and the GDM_* constants, so an entry point is declared once, in the header.  `call()` is how the package calls one.
 
 The product path has no CPU fallback: if the shared library is missing or a call fails,
 this module raises.  `build()` compiles it in-tree with hipcc for gfx950.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libgdm_hip.so")
 CSRC = os.path.join(_PKG, "csrc")
 
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_f = ctypes.c_float
-_sz = ctypes.c_size_t
+HEADER = os.path.join(_PKG, "..", "include", "gdm.h")
 
-GDM_RANSAC_MAX_H = 4096                # include/gdm.h
-GDM_SAMPLE_MAX_N = 4096
-GDM_SAMPLE_MAX_S = 4096
-GDM_AUG_MIN_S = 32
-GDM_AUG_MAX_S = 4096
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double,
+            "uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
+_STRUCTS = {}          # C name -> ctypes.Structure of every `typedef struct` of the header
 
 
-class KnnJob(ctypes.Structure):
-    """struct gdm_knn_job (include/gdm.h)."""
-    _fields_ = [("support", _vp), ("query", _vp), ("idx", _vp), ("d2", _vp),
-                ("support_bstride", ctypes.c_int64), ("query_bstride", ctypes.c_int64),
-                ("S", ctypes.c_int32), ("Q", ctypes.c_int32), ("K", ctypes.c_int32), ("grid_w", ctypes.c_int32)]
+def _ctype(ctype, where):
+    """The ctypes class of one C type of the header; a data pointer is c_void_p whatever it points to.  An unknown word raises."""
+    t = re.sub(r"\bconst\b|\s", "", ctype)
+    if t in _SCALARS:
+        return _SCALARS[t]
+    if t == "void":
+        return None
+    if t == "char*":
+        return ctypes.c_char_p
+    if t[-1:] == "*" and t[:-1] in _STRUCTS:
+        return ctypes.POINTER(_STRUCTS[t[:-1]])
+    if t[-1:] == "*" and (t.rstrip("*") in _SCALARS or t.rstrip("*") in ("void", "uint8_t")):
+        return ctypes.c_void_p
+    raise RuntimeError("include/gdm.h: unknown type %r in `%s`" % (ctype.strip(), where))
 
 
-class PwSeg(ctypes.Structure):
-    """gdm_pw_seg (include/gdm.h)."""
-    _fields_ = [("x", _vp), ("idx", _vp), ("C", ctypes.c_int32), ("n_src", ctypes.c_int32)]
+def _parse(text):
+    """(constants, signatures, parameter names) of the text of gdm.h.  It defines the job structures into _STRUCTS on the way."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    consts = {}
+    for name, val in re.findall(r"^#define\s+(GDM_\w+)\s+\(?(-?[\d.]+)f?\)?\s*$", text, flags=re.M):
+        consts[name] = float(val) if "." in val else int(val)
+    text = re.sub(r"^\s*#[^\n]*", "", text, flags=re.M)
+    for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            ctype, first, rest = re.fullmatch(r"(.*?)(\w+)((?:\s*,\s*\w+)*)", decl, flags=re.S).groups()
+            fields += [(f, _ctype(ctype, "%s: %s" % (name, decl))) for f in [first] + re.findall(r"\w+", rest)]
+        cls = "".join(w.capitalize() for w in name.split("_")[1:])          # gdm_knn_job -> KnnJob
+        _STRUCTS[name] = type(cls, (ctypes.Structure,), {"_fields_": fields, "__doc__": "%s (include/gdm.h)." % name})
+    sigs, names = {}, {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(gdm_\w+)\s*\(([^)]*)\)\s*;", text):
+        where = "%s %s(%s)" % (ret.strip(), name, " ".join(params.split()))
+        params = [] if params.strip() == "void" else [re.fullmatch(r"(.*?)(\w+)", p.strip(), flags=re.S).groups() for p in params.split(",")]
+        sigs[name] = (_ctype(ret, where), [_ctype(t, where) for t, _ in params])
+        names[name] = tuple(n for _, n in params)
+    return consts, sigs, names
 
 
-class PwJob(ctypes.Structure):
-    """gdm_pw_job (include/gdm.h)."""
-    _fields_ = [("x", _vp), ("wt", _vp), ("out", _vp), ("n", ctypes.c_int32)]
-
-
-class CopyJob(ctypes.Structure):
-    """gdm_copy_job (include/gdm.h)."""
-    _fields_ = [("dst", _vp), ("src", _vp), ("sb", ctypes.c_int64), ("s1", ctypes.c_int64), ("s2", ctypes.c_int64),
-                ("B", ctypes.c_int32), ("R1", ctypes.c_int32), ("R2", ctypes.c_int32), ("E", ctypes.c_int32)]
-
-
-# name -> (restype, argtypes) of every symbol include/gdm.h declares, in its order
-SIGNATURES = {
-    "gdm_last_error": (ctypes.c_char_p, []),
-    "gdm_version": (_i, []),
-    "gdm_knn_batch": (None, [_vp, _sz, _sz, _sz, _vp, _sz, _sz, _vp]),
-    "gdm_knn_batch_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_knn_jobs_workspace_bytes": (_sz, [ctypes.POINTER(KnnJob), _i, _i]),
-    "gdm_knn_jobs_ws_hip": (_i, [ctypes.POINTER(KnnJob), _i, _i, _vp, _sz, _vp]),
-    "gdm_ballquery_hip": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
-    "gdm_furthestsampling_hip": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
-    "gdm_interpolation_forward_hip": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_interpolation_backward_hip": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_labelstat_ballrange_hip": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_labelstat_idx_hip": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "gdm_group_gather_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_group_gather_bwd2_hip": (_i, [_vp, ctypes.c_long, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_gather_max_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_gather_max_bwd_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_rel_pos_enc_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "gdm_att_pool_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_att_pool_bwd_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_match_workspace_bytes": (_sz, [_i, _i, _i]),
-    "gdm_match_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "gdm_match_rows_bytes": (_sz, [_i]),
-    "gdm_match_partial_bytes": (_sz, [_i, _i]),
-    "gdm_match_pack_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_match_pack2_hip": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
-    "gdm_match_packed_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "gdm_match_soft_partial_bytes": (_sz, [_i, _i]),
-    "gdm_match_soft_packed_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "gdm_match_score_hip": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
-    "gdm_seg_mask_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "gdm_spline_aggregate_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_spline_aggregate_bwd_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "gdm_spline_direct3_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "gdm_gemm_grouped_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_spline_pairs_aggregate3_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "gdm_spline_pairs_grad_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
-    "gdm_spline_segment_sum_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "gdm_spline_wgrad_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_upsample_bilinear_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_upsample_bilinear_bwd_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_topk_rows_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp]),
-    "gdm_topk_negdist_hip": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "gdm_edge_feature_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_edge_feature_bwd_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_feature_knn_workspace_bytes": (_sz, [_i, _i]),
-    "gdm_feature_knn_hip": (_i, [_vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
-    "gdm_edge_block_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _i, _i, _vp]),
-    "gdm_edge_train_groups": (ctypes.c_long, [_i, _i]),
-    "gdm_edge_stats_hip": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp]),
-    "gdm_edge_bwd_reduce_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "gdm_edge_bwd_mid_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_edge_bwd_scatter_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "gdm_circle_rows_fwd_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "gdm_circle_rows_bwd_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_circle_match_rows_bytes": (_sz, [_i]),
-    "gdm_circle_match_tp_bytes": (_sz, [_i]),
-    "gdm_circle_match_pack_hip": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
-    "gdm_circle_match_nbr_hip": (_i, [_vp, _i, _f, _vp, _vp]),
-    "gdm_circle_match_visbits_hip": (_i, [_vp, _i, _i, _vp, _vp]),
-    "gdm_circle_match_nbr_items_hip": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
-    "gdm_circle_match_fwd2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp]),
-    "gdm_circle_match_bwd2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_circle_match_bwd_parts": (_i, [_i, _i]),
-    "gdm_soft_coord_fwd_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
-    "gdm_soft_coord_bwd_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_soft_coord_bwd_parts": (_i, [_i, _i]),
-    "gdm_lfa_stage_hip": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "gdm_kabsch_stats_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "gdm_kabsch_solve_hip": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "gdm_kabsch_stats_w_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_kabsch_solve_w_hip": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
-    "gdm_ransac_workspace_bytes": (_sz, [_i, _i, _i]),
-    "gdm_ransac_pose_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, ctypes.c_double, ctypes.c_uint32, _i,
-                                 _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_icp_transform_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _i, _i, _vp, _vp]),
-    "gdm_icp_update_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, ctypes.c_double, _i, _vp, _vp, _vp, _vp,
-                                _vp]),
-    "gdm_icp_plane_update_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, ctypes.c_double,
-                                      ctypes.c_double, ctypes.c_double, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_targets_workspace_bytes": (_sz, [_i, _i, _i]),
-    "gdm_hpr_visible_hip": (_i, [_vp, ctypes.c_long, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
-    "gdm_pose_targets_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i, _i, ctypes.c_double, _vp, _sz,
-                                  _vp, _vp, _vp, _vp, _vp]),
-    "gdm_affine_act_maxk_hip": (_i, [_vp, _vp, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _i, _f, _vp, _vp]),
-    "gdm_prelu1_hip": (_i, [_vp, _vp, ctypes.c_long, _vp, _vp]),
-    "gdm_prelu1_bwd_hip": (_i, [_vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp]),
-    "gdm_affine_act_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _f, _vp, _vp]),
-    "gdm_upconv3x3_gather_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "gdm_upconv3x3_gather2_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
-    "gdm_upconv3x3_gather_bwd_hip": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_upconv_fused64_weight_bytes": (_sz, []),
-    "gdm_upconv_fused64_pack_weight_hip": (_i, [_vp, _vp, _vp]),
-    "gdm_upconv_fused64_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "gdm_psp_combine2_hip": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_gather_add_affine_act2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
-    "gdm_conv1x1_gather_add_act2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_long, _i, _f, _i, _vp, _vp]),
-    "gdm_conv64_gather_add_act_mfma2_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _i, _i, _vp, _vp, _i, _vp]),
-    "gdm_conv64_gather_add_final_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _vp, _vp, _vp, _vp]),
-    "gdm_conv3x3_act_bytes": (_sz, [_i, _i, _i, _i]),
-    "gdm_conv3x3_weight_bytes": (_sz, [_i, _i]),
-    "gdm_conv3x3_pack_weight_hip": (_i, [_vp, _i, _i, _vp, _vp]),
-    "gdm_conv3x3_pack_act_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_conv3x3_packed_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_conv3x3_strided_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_conv1x1_strided_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_conv1x1_gather_add_hip": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_affine_relu_maxpool_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_conv1x1_logsoftmax_hip": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_long, _vp, _vp]),
-    "gdm_pack_rows64_hip": (_i, [_vp, _i, _vp, _vp]),
-    "gdm_upconv_final_points_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_psp_pools_hip": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_psp_pools_bwd_hip": (_i, [_vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _vp, _vp]),
-    "gdm_conv1x1_weight_bytes": (_sz, [_i, _i]),
-    "gdm_conv1x1_pack_weight_hip": (_i, [_vp, _i, _i, _vp, _vp]),
-    "gdm_conv_pack_weight_dgrad_hip": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "gdm_conv1x1_packed_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_depth_to_xyz_hip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_depth_normals_hip": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_warp_crop_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_fill_depth_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "gdm_fill_depth_hip": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _sz, _vp, _vp, _vp]),
-    "gdm_sample_assemble_workspace_bytes": (_sz, [_i, _i]),
-    "gdm_sample_assemble_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "gdm_augment_workspace_bytes": (_sz, [_i, _i]),
-    "gdm_augment_crops_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "gdm_augment_force_all_stages": (None, [_i]),
-    "gdm_dzi_boxes_hip": (_i, [_vp, _i, _f, _f, _f, _f, _i, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
-    "gdm_bn_sums_len": (ctypes.c_long, [_i, _i, ctypes.c_long]),
-    "gdm_bn_stats_hip": (_i, [_vp, _i, _i, ctypes.c_long, _vp, _vp]),
-    "gdm_bn_fwd_apply_hip": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_long, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_bn_bwd_reduce_hip": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _vp, _vp]),
-    "gdm_bn_bwd_apply_hip": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_long, _i, _f, _vp, _vp, _vp, _vp]),
-    "gdm_point_heads2_hip": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
-    "gdm_pointwise2_hip": (_i, [ctypes.POINTER(PwSeg), _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _i, _vp]),
-    "gdm_pointwise_jobs_hip": (_i, [ctypes.POINTER(PwJob), _i, _i, _i, _i, _vp]),
-    "gdm_pointwise_chain2_hip": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_stem_weight_bytes": (_sz, []),
-    "gdm_stem_pack_weight_hip": (_i, [_vp, _vp, _vp]),
-    "gdm_stem_hip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_wgrad_x_bytes": (_sz, [_i, _i, _i, _i]),
-    "gdm_wgrad_go_bytes": (_sz, [_i, _i, _i, _i]),
-    "gdm_wgrad_pack_x_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_wgrad_pack_go_hip": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_wgrad_x1_bytes": (_sz, [_i, _i, _i]),
-    "gdm_wgrad_pack_x1_hip": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "gdm_mfma_probe_hip": (_i, [_i, _i, _i, _vp, _vp]),
-    "gdm_mfma_probe_lds_hip": (_i, [_i, _i, _i, _vp, _vp]),
-    "gdm_wgrad_direct_hip": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gdm_conv1x1_packed_wb_hip": (_i, [_vp, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp, _vp]),
-    "gdm_copy_jobs_hip": (_i, [ctypes.POINTER(CopyJob), _i, _vp]),
-    "gdm_mssd_mspd_hip": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gdm_render_depth_hip": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_double, _i, _vp, _vp]),
-    "gdm_vsd_counts_hip": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, ctypes.c_double, ctypes.POINTER(ctypes.c_double), _i,
-                                ctypes.c_double, _i, _vp, _vp, _vp]),
-}
+try:
+    with open(HEADER) as _header:
+        _consts, SIGNATURES, PARAMS = _parse(_header.read())
+except OSError as e:
+    raise RuntimeError("the package binds libgdm_hip.so from include/gdm.h and cannot read it (%s): %s" % (HEADER, e))
+# SIGNATURES: name -> (restype, argtypes) of every symbol the header declares, in its order; PARAMS: name -> parameter names
+globals().update(_consts)          # every numeric #define GDM_* of the header
+KnnJob, PwSeg, PwJob, CopyJob = (_STRUCTS["gdm_" + n] for n in ("knn_job", "pw_seg", "pw_job", "copy_job"))
 
 _lib = None
+_torch = None          # the torch module, once lib() has imported it: torch must not be loaded before lib() decides to
 
 
 def _objects_state():
@@ -265,7 +130,7 @@ def build_record():
 
 
 def lib():
-    global _lib
+    global _lib, _torch
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
@@ -274,7 +139,8 @@ def lib():
         # torch FIRST: PyTorch-ROCm ships its own HIP runtime (torch/lib/libamdhip64.so) and the process must hold exactly one.  Loaded
         # before torch, this library pulls in /opt/rocm's runtime instead, torch then brings its own, and the first launch from here
         # fails with "no ROCm-capable device is detected" (build() followed by smoke() in one process did exactly that).
-        import torch  # noqa: F401
+        import torch
+        _torch = torch
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(l, name)          # AttributeError if the library lacks a declared symbol
@@ -292,3 +158,31 @@ def check(rc, what):
     if rc != 0:
         msg = lib().gdm_last_error()
         raise GdmError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else "?"))
+
+
+def _stream():
+    return _torch.cuda.current_stream().cuda_stream
+
+
+_PLAIN = frozenset((int, float, type(None)))
+_entries = {}          # name -> (bound function, whether its last parameter is the stream, how many arguments the caller gives)
+
+
+def call(name, *args):
+    """Call entry point `name` of the library: tensors go as their data_ptr(), everything else (None, addresses, sizes, floats, job
+    arrays) as it is.  Every `*_hip` entry takes the HIP stream last and returns a status (the header's convention): torch's current
+    stream is appended for it at call time, and a status other than 0 raises GdmError.  The other entries return their value."""
+    try:
+        fn, hip, n = _entries[name]
+    except KeyError:
+        hip = PARAMS[name][-1:] == ("stream",)
+        fn, hip, n = _entries[name] = getattr(lib(), name), hip, len(PARAMS[name]) - hip
+    if len(args) != n:          # ctypes itself lets surplus arguments through, and the stream would follow them
+        raise TypeError("%s takes %d arguments%s, got %d" % (name, n, " and the stream" if hip else "", len(args)))
+    Tensor = _torch.Tensor          # (isinstance against it is slow for an int or a float: those are told by their type first)
+    argv = [a if type(a) in _PLAIN else a.data_ptr() if isinstance(a, Tensor) else a for a in args]
+    if not hip:
+        return fn(*argv)
+    rc = fn(*argv, _stream())
+    if rc != 0:
+        check(rc, name)

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops, pyramid
-from ._lib import check
+from ._lib import call
 
 
 def depth_to_xyz(depth, K, origin, S):
@@ -36,8 +36,7 @@ def depth_to_xyz(depth, K, origin, S):
     origin = ops._idx32(origin, "origin")
     B, H, W = depth.shape
     out = torch.empty((B, S, S, 3), dtype=torch.float32, device=depth.device)
-    check(_lib.lib().gdm_depth_to_xyz_hip(depth.data_ptr(), K.data_ptr(), origin.data_ptr(), B, H, W, S, out.data_ptr(), ops._stream()),
-          "gdm_depth_to_xyz_hip")
+    call("gdm_depth_to_xyz_hip", depth, K, origin, B, H, W, S, out)
     return out
 
 
@@ -92,7 +91,7 @@ def make_inputs(rgb_norm, depth, normals, K, origin, S, n_points, generator=None
 # --------------------------------------------------------------------------------------
 COLOR_MEAN = (0.485, 0.456, 0.406)                  # normalize_color (/root/reference/utils/ply.py:502-509), as csrc/gdm_frontend.hip
 COLOR_STD_CROP = (0.229, 0.224, 0.224)
-NORMALS_MAX_K = 64                                  # include/gdm.h GDM_NORMALS_MAX_K
+NORMALS_MAX_K = _lib.GDM_NORMALS_MAX_K
 
 
 def _depth_mm(depth):
@@ -224,8 +223,8 @@ def _cross(n):
 
 
 _DIAMOND_5 = [(dy, dx) for dy, dx in _full(5) if abs(dy) + abs(dx) <= 2]
-FILL_MODES = {"multiscale": 0, "fast": 1}                      # include/gdm.h GDM_FILL_MULTISCALE / GDM_FILL_FAST
-FILL_STAGES = 7                                                # include/gdm.h GDM_FILL_STAGES
+FILL_MODES = {"multiscale": _lib.GDM_FILL_MULTISCALE, "fast": _lib.GDM_FILL_FAST}
+FILL_STAGES = _lib.GDM_FILL_STAGES
 _FILL_STAGE_NAMES = ("s1_inverted_depths", "s2_dilated_depths", "s3_closed_depths", "s4_blurred_depths", "s5_combined_depths",
                      "s7_before_bilateral", "s7_blurred_depths")
 
@@ -653,9 +652,7 @@ def fill_depth(depth, mode="multiscale", max_depth=100.0, return_stages=False, e
             ws = _fill_workspace[depth.device] = torch.empty(need, dtype=torch.uint8, device=depth.device)
     out = torch.empty_like(depth)
     stages = torch.empty((FILL_STAGES, B, H, W), dtype=torch.float32, device=depth.device) if return_stages else None
-    check(lib.gdm_fill_depth_hip(depth.data_ptr(), B, H, W, m, float(max_depth), ws.data_ptr() if need else None,
-                                 ws.numel() if need else 0, out.data_ptr(), stages.data_ptr() if return_stages else None,
-                                 ops._stream()), "gdm_fill_depth_hip")
+    call("gdm_fill_depth_hip", depth, B, H, W, m, float(max_depth), ws if need else None, ws.numel() if need else 0, out, stages)
     if not return_stages:
         return out
     st = {name: stages[i] for i, name in enumerate(_FILL_STAGE_NAMES) if not (mode == "fast" and i == 3)}
@@ -675,8 +672,7 @@ def depth_normals(depth, K, k_size=5, distance_threshold=2000, difference_thresh
         raise ValueError("depth must be [B,H,W] and K [B,3,3], got %s and %s" % (tuple(depth.shape), tuple(K.shape)))
     B, H, W = depth.shape
     out = torch.empty((B, 3, H, W), dtype=torch.float32, device=depth.device)
-    check(_lib.lib().gdm_depth_normals_hip(depth.data_ptr(), K.data_ptr(), B, H, W, int(k_size), int(distance_threshold),
-                                           int(difference_threshold), out.data_ptr(), ops._stream()), "gdm_depth_normals_hip")
+    call("gdm_depth_normals_hip", depth, K, B, H, W, int(k_size), int(distance_threshold), int(difference_threshold), out)
     return out
 
 
@@ -744,9 +740,8 @@ def dzi_boxes(bbox_xyxy, im_hw, pad_ratio=1.5, scale_ratio=0.25, shift_ratio=0.2
         seed_val, seed_ptr = ops._seed_args(seed)
         center = torch.empty((B, 2), dtype=torch.float32, device=box.device)
         scale = torch.empty((B,), dtype=torch.float32, device=box.device)
-        check(_lib.lib().gdm_dzi_boxes_hip(box.data_ptr(), B, float(max(im_hw)), float(pad_ratio), float(scale_ratio), float(shift_ratio),
-                                           1 if train else 0, seed_val, seed_ptr, center.data_ptr(), scale.data_ptr(), ops._stream()),
-              "gdm_dzi_boxes_hip")
+        call("gdm_dzi_boxes_hip", box, B, float(max(im_hw)), float(pad_ratio), float(scale_ratio), float(shift_ratio), 1 if train else 0,
+             seed_val, seed_ptr, center, scale)
         return center, scale
     u = 2.0 * torch.rand((box.shape[0], 3), device=box.device, generator=generator) - 1.0 if train else None
     return _dzi_torch(box, im_hw, pad_ratio, scale_ratio, shift_ratio, u)
@@ -776,19 +771,15 @@ def crop_from_boxes(rgb_u8, depth, normals, K, center, scale, S, mask=None):
     out = dict(rgb=torch.empty((B, 3, S, S), dtype=torch.float32, device=dev),
                dpt_xyz=torch.empty((B, S, S, 3), dtype=torch.float32, device=dev),
                depth=torch.empty((B, S, S), dtype=torch.float32, device=dev))
-    mp = op = np_ = on = None
     if normals is not None:
         out["normals"] = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
-        np_, on = normals.data_ptr(), out["normals"].data_ptr()
     if mask is not None:
         mask = ops._dev(mask, torch.uint8, "mask")
         if tuple(mask.shape) != (B, H, W):
             raise ValueError("mask must be [B=%d,H=%d,W=%d], got %s" % (B, H, W, tuple(mask.shape)))
         out["mask"] = torch.empty((B, S, S), dtype=torch.uint8, device=dev)
-        mp, op = mask.data_ptr(), out["mask"].data_ptr()
-    check(_lib.lib().gdm_warp_crop_hip(rgb_u8.data_ptr(), depth.data_ptr(), np_, K.data_ptr(), mp, center.data_ptr(),
-                                       scale.data_ptr(), B, H, W, int(S), out["rgb"].data_ptr(), on,
-                                       out["dpt_xyz"].data_ptr(), out["depth"].data_ptr(), op, ops._stream()), "gdm_warp_crop_hip")
+    call("gdm_warp_crop_hip", rgb_u8, depth, normals, K, mask, center, scale, B, H, W, int(S), out["rgb"], out.get("normals"), out["dpt_xyz"],
+         out["depth"], out.get("mask"))
     return out
 
 

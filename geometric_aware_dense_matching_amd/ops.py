@@ -22,11 +22,11 @@ import os
 import torch
 
 from . import _lib, settings
-from ._lib import KnnJob, check
+from ._lib import KnnJob, call, check  # noqa: F401  (tests and tools reach check as ops.check)
 from .derived import derived
 
-MATCH_BF16X3 = 0
-MATCH_F32 = 1
+MATCH_BF16X3 = _lib.GDM_MATCH_BF16X3
+MATCH_F32 = _lib.GDM_MATCH_F32
 
 
 def _stream():
@@ -140,8 +140,7 @@ def knn_batch(support, query, K, return_d2=False):
     assert support.shape[2] == 3 and query.shape[2] == 3 and query.shape[0] == B
     idx = torch.empty((B, Q, K), dtype=torch.int32, device=support.device)
     d2 = torch.empty((B, Q, K), dtype=torch.float32, device=support.device) if return_d2 else None
-    check(_lib.lib().gdm_knn_batch_hip(support.data_ptr(), query.data_ptr(), B, S, Q, K, idx.data_ptr(),
-                                       d2.data_ptr() if return_d2 else None, _stream()), "gdm_knn_batch_hip")
+    call("gdm_knn_batch_hip", support, query, B, S, Q, K, idx, d2)
     return (idx, d2) if return_d2 else idx
 
 
@@ -207,7 +206,7 @@ def copy_views(views):
         arr[i] = _lib.CopyJob(out.data_ptr(), v.data_ptr(), v4.stride(0), v4.stride(1), v4.stride(2),
                               v4.shape[0], v4.shape[1], v4.shape[2], v4.shape[3])
         outs.append(out)
-    check(_lib.lib().gdm_copy_jobs_hip(arr, n, _stream()), "gdm_copy_jobs_hip")
+    call("gdm_copy_jobs_hip", arr, n)
     return outs
 
 
@@ -217,7 +216,7 @@ def _knn_launch(arr, n, B, device):
     L = _lib.lib()
     nbytes = int(L.gdm_knn_jobs_workspace_bytes(arr, n, B))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-    check(L.gdm_knn_jobs_ws_hip(arr, n, B, ws.data_ptr(), nbytes, _stream()), "gdm_knn_jobs_ws_hip")
+    call("gdm_knn_jobs_ws_hip", arr, n, B, ws, nbytes)
     return ws
 
 
@@ -228,8 +227,7 @@ def ballquery(radius, nsample, xyz, new_xyz):
     B, n, _ = xyz.shape
     m = new_xyz.shape[1]
     idx = torch.zeros((B, m, nsample), dtype=torch.int32, device=xyz.device)
-    check(_lib.lib().gdm_ballquery_hip(B, n, m, float(radius), nsample, new_xyz.data_ptr(), xyz.data_ptr(),
-                                       idx.data_ptr(), _stream()), "gdm_ballquery_hip")
+    call("gdm_ballquery_hip", B, n, m, float(radius), nsample, new_xyz, xyz, idx)
     return idx
 
 
@@ -239,8 +237,7 @@ def furthestsampling(xyz, m):
     B, n, _ = xyz.shape
     idx = torch.empty((B, m), dtype=torch.int32, device=xyz.device)
     temp = torch.empty((B, n), dtype=torch.float32, device=xyz.device)
-    check(_lib.lib().gdm_furthestsampling_hip(B, n, m, xyz.data_ptr(), temp.data_ptr(), idx.data_ptr(), _stream()),
-          "gdm_furthestsampling_hip")
+    call("gdm_furthestsampling_hip", B, n, m, xyz, temp, idx)
     return idx
 
 
@@ -261,8 +258,7 @@ class _GroupGather(torch.autograd.Function):
         B, C, n = feat.shape
         m, K = idx.shape[1], idx.shape[2]
         out = torch.empty((B, C, m, K), dtype=torch.float32, device=feat.device)
-        check(_lib.lib().gdm_group_gather_hip(feat.data_ptr(), idx.data_ptr(), B, C, n, m, K, out.data_ptr(), _stream()),
-              "gdm_group_gather_hip")
+        call("gdm_group_gather_hip", feat, idx, B, C, n, m, K, out)
         ctx.save_for_backward(idx)
         ctx.n = n
         return out
@@ -275,8 +271,7 @@ class _GroupGather(torch.autograd.Function):
         if not (go.dtype == torch.float32 and go.stride(3) == 1 and go.stride(2) == K and go.stride(1) == m * K and go.stride(0) >= C * m * K):
             go = go.contiguous()
         g = torch.zeros((B, C, ctx.n), dtype=torch.float32, device=go.device)
-        check(_lib.lib().gdm_group_gather_bwd2_hip(go.data_ptr(), go.stride(0), idx.data_ptr(), B, C, ctx.n, m, K, g.data_ptr(), _stream()),
-              "gdm_group_gather_bwd2_hip")
+        call("gdm_group_gather_bwd2_hip", go, go.stride(0), idx, B, C, ctx.n, m, K, g)
         return g, None
 
 
@@ -305,8 +300,7 @@ class _GatherMax(torch.autograd.Function):
         out = torch.empty((B, C, m), dtype=torch.float32, device=feat.device)
         need_arg = ctx.needs_input_grad[0]               # (not feat.requires_grad: _dev may have made a contiguous copy under no_grad)
         arg = torch.empty((B, C, m), dtype=torch.int32, device=feat.device) if need_arg else None
-        check(_lib.lib().gdm_gather_max_hip(feat.data_ptr(), idx.data_ptr(), B, C, n, m, K, out.data_ptr(),
-                                            arg.data_ptr() if need_arg else None, _stream()), "gdm_gather_max_hip")
+        call("gdm_gather_max_hip", feat, idx, B, C, n, m, K, out, arg)
         if need_arg:
             ctx.save_for_backward(arg)
         ctx.n = n
@@ -318,8 +312,7 @@ class _GatherMax(torch.autograd.Function):
         go = go.contiguous()
         B, C, m = go.shape
         g = torch.zeros((B, C, ctx.n), dtype=torch.float32, device=go.device)
-        check(_lib.lib().gdm_gather_max_bwd_hip(go.data_ptr(), arg.data_ptr(), B, C, ctx.n, m, g.data_ptr(), _stream()),
-              "gdm_gather_max_bwd_hip")
+        call("gdm_gather_max_bwd_hip", go, arg, B, C, ctx.n, m, g)
         return g, None
 
 
@@ -338,8 +331,7 @@ def rel_pos_enc(xyz, idx):
     K = idx.shape[2]
     assert idx.shape[0] == B and idx.shape[1] == n
     out = torch.empty((B, 10, n, K), dtype=torch.float32, device=xyz.device)
-    check(_lib.lib().gdm_rel_pos_enc_hip(xyz.data_ptr(), idx.data_ptr(), B, n, K, out.data_ptr(), _stream()),
-          "gdm_rel_pos_enc_hip")
+    call("gdm_rel_pos_enc_hip", xyz, idx, B, n, K, out)
     return out
 
 
@@ -351,8 +343,7 @@ class _AttPool(torch.autograd.Function):
         B, C, n, K = att.shape
         assert feat.shape == att.shape
         out = torch.empty((B, C, n), dtype=torch.float32, device=att.device)
-        check(_lib.lib().gdm_att_pool_hip(att.data_ptr(), feat.data_ptr(), B, C, n, K, out.data_ptr(), _stream()),
-              "gdm_att_pool_hip")
+        call("gdm_att_pool_hip", att, feat, B, C, n, K, out)
         ctx.save_for_backward(att, feat)
         return out
 
@@ -363,8 +354,7 @@ class _AttPool(torch.autograd.Function):
         B, C, n, K = att.shape
         ga = torch.empty_like(att)
         gf = torch.empty_like(feat)
-        check(_lib.lib().gdm_att_pool_bwd_hip(att.data_ptr(), feat.data_ptr(), go.data_ptr(), B, C, n, K,
-                                              ga.data_ptr(), gf.data_ptr(), _stream()), "gdm_att_pool_bwd_hip")
+        call("gdm_att_pool_bwd_hip", att, feat, go, B, C, n, K, ga, gf)
         return ga, gf
 
 
@@ -381,8 +371,7 @@ def topk_rows(score, k, return_values=False):
     rows = score.numel() // n
     idx = torch.empty(score.shape[:-1] + (k,), dtype=torch.int32, device=score.device)
     val = torch.empty(score.shape[:-1] + (k,), dtype=torch.float32, device=score.device) if return_values else None
-    check(_lib.lib().gdm_topk_rows_hip(score.data_ptr(), rows, n, k, idx.data_ptr(), val.data_ptr() if return_values else None,
-                                       _stream()), "gdm_topk_rows_hip")
+    call("gdm_topk_rows_hip", score, rows, n, k, idx, val)
     return (idx, val) if return_values else idx
 
 
@@ -393,7 +382,7 @@ def topk_negdist(gram, xx, k):
     xx = _dev(xx, torch.float32, "xx")
     B, n, _ = gram.shape
     idx = torch.empty((B, n, k), dtype=torch.int32, device=gram.device)
-    check(_lib.lib().gdm_topk_negdist_hip(gram.data_ptr(), xx.data_ptr(), B, n, k, idx.data_ptr(), _stream()), "gdm_topk_negdist_hip")
+    call("gdm_topk_negdist_hip", gram, xx, B, n, k, idx)
     return idx
 
 
@@ -418,8 +407,7 @@ def feature_knn(x, k, return_values=False, splits=0):
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)          # xx f32[B,n] + one flag per 32 rows
     idx = torch.empty((B, n, k), dtype=torch.int32, device=x.device)
     val = torch.empty((B, n, k), dtype=torch.float32, device=x.device) if return_values else None
-    check(_lib.lib().gdm_feature_knn_hip(x.data_ptr(), bstride, B, C, n, k, int(splits), ws.data_ptr(), nbytes, idx.data_ptr(),
-                                         val.data_ptr() if return_values else None, _stream()), "gdm_feature_knn_hip")
+    call("gdm_feature_knn_hip", x, bstride, B, C, n, k, int(splits), ws, nbytes, idx, val)
     return (idx, val) if return_values else idx
 
 
@@ -450,9 +438,7 @@ def edge_block(pq, idx, scale1, shift1, w2=None, scale2=None, shift2=None, slope
     elif (not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 3 or out.shape[0] != B
           or out.shape[2] != n):
         raise ValueError("edge_block: out must be a contiguous f32 [B,outC,%d] tensor" % n)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    check(_lib.lib().gdm_edge_block_hip(pq.data_ptr(), idx.data_ptr(), scale1.data_ptr(), shift1.data_ptr(), ptr(w2), ptr(scale2), ptr(shift2),
-                                        float(slope), B, n, K, out.data_ptr(), out.shape[1], int(out_c0), _stream()), "gdm_edge_block_hip")
+    call("gdm_edge_block_hip", pq, idx, scale1, shift1, w2, scale2, shift2, float(slope), B, n, K, out, out.shape[1], int(out_c0))
     return out
 
 
@@ -495,13 +481,12 @@ class _EdgeBlockTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pq, idx, w1, b1, w2, g2, b2, slope, bn1_args, bn2_args, group):
-        L = _lib.lib()
         B, n, _ = pq.shape
         K = idx.shape[2]
         two = w2 is not None
         count = float(B * n * K)
         buf = _edge_sums_buffer(B, n, K, pq.device)
-        check(L.gdm_edge_stats_hip(pq.data_ptr(), idx.data_ptr(), None, None, float(slope), B, n, K, buf.data_ptr(), _stream()), "gdm_edge_stats_hip")
+        call("gdm_edge_stats_hip", pq, idx, None, None, float(slope), B, n, K, buf)
         _, tot, E = _edge_fold(buf, group)
         E = count if E is None else E
         st1 = _edge_bn_fold(tot, E, w1, b1, *bn1_args)
@@ -509,8 +494,7 @@ class _EdgeBlockTrain(torch.autograd.Function):
         if two:
             ctx.w2_shape = w2.shape
             w2 = _dev(w2.detach().reshape(64, 64), torch.float32, "w2")
-            check(L.gdm_edge_stats_hip(pq.data_ptr(), idx.data_ptr(), st1.data_ptr(), w2.data_ptr(), float(slope), B, n, K, buf.data_ptr(), _stream()),
-                  "gdm_edge_stats_hip")
+            call("gdm_edge_stats_hip", pq, idx, st1, w2, float(slope), B, n, K, buf)
             _, tot, _ = _edge_fold(buf, group)
             st2 = _edge_bn_fold(tot, E, g2, b2, *bn2_args)
         out = edge_block(pq, idx, st1[0], st1[1], w2, st2[0] if two else None, st2[1] if two else None, slope)
@@ -523,16 +507,13 @@ class _EdgeBlockTrain(torch.autograd.Function):
         pq, idx, st1, w2, st2, E = ctx.saved_tensors
         E = ctx.count if E is None else E
         go = _dev(go, torch.float32, "grad")
-        L = _lib.lib()
         B, n, _ = pq.shape
         K = idx.shape[2]
         two = w2 is not None
         slope, group = ctx.slope, ctx.group
-        ptr = lambda t: t.data_ptr() if t is not None else None
         amax = torch.empty((B, n, 64), dtype=torch.uint8, device=pq.device)
         buf = _edge_sums_buffer(B, n, K, pq.device)
-        check(L.gdm_edge_bwd_reduce_hip(pq.data_ptr(), idx.data_ptr(), st1.data_ptr(), ptr(w2), ptr(st2), slope, B, n, K, go.data_ptr(), amax.data_ptr(),
-                                        buf.data_ptr(), _stream()), "gdm_edge_bwd_reduce_hip")
+        call("gdm_edge_bwd_reduce_hip", pq, idx, st1, w2, st2, slope, B, n, K, go, amax, buf)
         # grad gamma / beta (and dW2) stay LOCAL sums, as in _BatchNormAct: DDP averages parameter gradients over the ranks
         local, tot, _ = _edge_fold(buf, group)
         cf_last = (tot / E).t().contiguous().float()                        # [2,64] = dbeta / E | dgamma / E
@@ -540,8 +521,7 @@ class _EdgeBlockTrain(torch.autograd.Function):
         if two:
             gb2, gg2, cf2 = local[:, 0].float(), local[:, 1].float(), cf_last
             slabs = torch.empty((buf.numel() - 2) // 128, 64, 64, dtype=torch.float32, device=pq.device)
-            check(L.gdm_edge_bwd_mid_hip(pq.data_ptr(), idx.data_ptr(), st1.data_ptr(), w2.data_ptr(), st2.data_ptr(), cf2.data_ptr(), slope, B, n, K,
-                                         go.data_ptr(), amax.data_ptr(), buf.data_ptr(), slabs.data_ptr(), _stream()), "gdm_edge_bwd_mid_hip")
+            call("gdm_edge_bwd_mid_hip", pq, idx, st1, w2, st2, cf2, slope, B, n, K, go, amax, buf, slabs)
             gw2 = slabs.sum(0).reshape(ctx.w2_shape)
             local, tot, _ = _edge_fold(buf, group)
             cf1 = (tot / E).t().contiguous().float()
@@ -549,8 +529,7 @@ class _EdgeBlockTrain(torch.autograd.Function):
             cf1 = cf_last
         gb1, gg1 = local[:, 0].float(), local[:, 1].float()
         gpq = torch.zeros_like(pq)                                          # the P half is accumulated by atomicAdd
-        check(L.gdm_edge_bwd_scatter_hip(pq.data_ptr(), idx.data_ptr(), st1.data_ptr(), cf1.data_ptr(), ptr(w2), ptr(st2), ptr(cf2), slope, B, n, K,
-                                         go.data_ptr(), amax.data_ptr(), gpq.data_ptr(), _stream()), "gdm_edge_bwd_scatter_hip")
+        call("gdm_edge_bwd_scatter_hip", pq, idx, st1, cf1, w2, st2, cf2, slope, B, n, K, go, amax, gpq)
         return gpq, None, gg1, gb1, gw2, gg2, gb2, None, None, None, None
 
 
@@ -597,8 +576,7 @@ def affine_act_maxk(x, scale, shift, act=0, slope=0.0):
     x = _dev(x, torch.float32, "x")
     B, C, n, K = x.shape
     out = torch.empty((B, C, n), dtype=torch.float32, device=x.device)
-    check(_lib.lib().gdm_affine_act_maxk_hip(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), B * C, C, n, K, act, float(slope),
-                                             out.data_ptr(), _stream()), "gdm_affine_act_maxk_hip")
+    call("gdm_affine_act_maxk_hip", x, scale, shift, B * C, C, n, K, act, float(slope), out)
     return out
 
 
@@ -609,8 +587,7 @@ class _EdgeFeature(torch.autograd.Function):
         B, C, n = x.shape
         K = idx.shape[2]
         out = torch.empty((B, 2 * C, n, K), dtype=torch.float32, device=x.device)
-        check(_lib.lib().gdm_edge_feature_hip(x.data_ptr(), idx.data_ptr(), B, C, n, K, out.data_ptr(), _stream()),
-              "gdm_edge_feature_hip")
+        call("gdm_edge_feature_hip", x, idx, B, C, n, K, out)
         ctx.save_for_backward(idx)
         return out
 
@@ -620,8 +597,7 @@ class _EdgeFeature(torch.autograd.Function):
         go = go.contiguous()
         B, C2, n, K = go.shape
         g = torch.zeros((B, C2 // 2, n), dtype=torch.float32, device=go.device)
-        check(_lib.lib().gdm_edge_feature_bwd_hip(go.data_ptr(), idx.data_ptr(), B, C2 // 2, n, K, g.data_ptr(), _stream()),
-              "gdm_edge_feature_bwd_hip")
+        call("gdm_edge_feature_bwd_hip", go, idx, B, C2 // 2, n, K, g)
         return g, None
 
 
@@ -639,9 +615,7 @@ class _CircleRows(torch.autograd.Function):
         lse_p = torch.empty(R, dtype=torch.float32, device=sim.device)
         lse_n = torch.empty_like(lse_p)
         loss = torch.empty_like(lse_p)
-        check(_lib.lib().gdm_circle_rows_fwd_hip(sim.data_ptr(), R, Mp, match.data_ptr(), item.data_ptr(), xyz.data_ptr(),
-                                                 vis.data_ptr(), radius, gamma, m, lse_p.data_ptr(), lse_n.data_ptr(),
-                                                 loss.data_ptr(), _stream()), "gdm_circle_rows_fwd_hip")
+        call("gdm_circle_rows_fwd_hip", sim, R, Mp, match, item, xyz, vis, radius, gamma, m, lse_p, lse_n, loss)
         ctx.save_for_backward(sim, match, item, xyz, vis, lse_p, lse_n)
         ctx.consts = (radius, gamma, m)
         return loss
@@ -653,9 +627,7 @@ class _CircleRows(torch.autograd.Function):
         g = g.contiguous()
         R, Mp = sim.shape
         dsim = torch.empty_like(sim)
-        check(_lib.lib().gdm_circle_rows_bwd_hip(sim.data_ptr(), R, Mp, match.data_ptr(), item.data_ptr(), xyz.data_ptr(),
-                                                 vis.data_ptr(), radius, gamma, m, lse_p.data_ptr(), lse_n.data_ptr(),
-                                                 g.data_ptr(), dsim.data_ptr(), _stream()), "gdm_circle_rows_bwd_hip")
+        call("gdm_circle_rows_bwd_hip", sim, R, Mp, match, item, xyz, vis, radius, gamma, m, lse_p, lse_n, g, dsim)
         return dsim, None, None, None, None, None, None, None
 
 
@@ -680,7 +652,7 @@ def circle_nbr_table(xyz, radius):
     xyz = _dev(xyz, torch.float32, "xyz")
     M = xyz.shape[0]
     nbr = torch.empty((M, (M + 31) // 32), dtype=torch.int32, device=xyz.device)
-    check(_lib.lib().gdm_circle_match_nbr_hip(xyz.data_ptr(), M, float(radius), nbr.data_ptr(), _stream()), "gdm_circle_match_nbr_hip")
+    call("gdm_circle_match_nbr_hip", xyz, M, float(radius), nbr)
     return nbr
 
 
@@ -692,8 +664,7 @@ def circle_nbr_items(xyz, rad):
     B, M = rad.shape
     assert xyz.shape == (M, 3)
     nbr = torch.empty((B, M, (M + 31) // 32), dtype=torch.int32, device=xyz.device)
-    check(_lib.lib().gdm_circle_match_nbr_items_hip(xyz.data_ptr(), M, rad.data_ptr(), B, nbr.data_ptr(), _stream()),
-          "gdm_circle_match_nbr_items_hip")
+    call("gdm_circle_match_nbr_items_hip", xyz, M, rad, B, nbr)
     return nbr
 
 
@@ -704,7 +675,7 @@ def circle_visbits(vis):
     v8 = (vis != 0).to(torch.uint8).contiguous()
     B, M = v8.shape
     bits = torch.empty((B, (M + 31) // 32), dtype=torch.int32, device=vis.device)
-    check(_lib.lib().gdm_circle_match_visbits_hip(v8.data_ptr(), B, M, bits.data_ptr(), _stream()), "gdm_circle_match_visbits_hip")
+    call("gdm_circle_match_visbits_hip", v8, B, M, bits)
     return bits
 
 
@@ -715,7 +686,7 @@ def _cm_pack(x):
     rows = torch.empty(L.gdm_circle_match_rows_bytes(n), dtype=torch.uint8, device=x.device)
     tp = torch.empty(L.gdm_circle_match_tp_bytes(n), dtype=torch.uint8, device=x.device)
     rsum = torch.empty(npad, dtype=torch.float32, device=x.device)
-    check(L.gdm_circle_match_pack_hip(x.data_ptr(), n, rows.data_ptr(), tp.data_ptr(), rsum.data_ptr(), _stream()), "gdm_circle_match_pack_hip")
+    call("gdm_circle_match_pack_hip", x, n, rows, tp, rsum)
     return rows, tp, rsum
 
 
@@ -746,11 +717,8 @@ class _CircleMatch(torch.autograd.Function):
         lp = torch.empty(Rp, dtype=torch.float32, device=x.device)
         ln = torch.empty_like(lp)
         loss = torch.empty_like(lp)
-        check(_lib.lib().gdm_circle_match_fwd2_hip(xr.data_ptr(), xt.data_ptr(), xs.data_ptr(), yr.data_ptr(), yt.data_ptr(), R, M,
-                                                   gp.data_ptr(), c2p.data_ptr() if c2p is not None else None, ip.data_ptr(),
-                                                   nbr.data_ptr() if nbr is not None else None, int(per_item),
-                                                   visb.data_ptr() if visb is not None else None, int(bool(pad_e0)),
-                                                   gamma, m, lp.data_ptr(), ln.data_ptr(), loss.data_ptr(), _stream()), "gdm_circle_match_fwd2_hip")
+        call("gdm_circle_match_fwd2_hip", xr, xt, xs, yr, yt, R, M, gp, c2p, ip, nbr, int(per_item), visb, int(bool(pad_e0)), gamma, m, lp,
+             ln, loss)
         ctx.save_for_backward(xr, xt, xs, yr, yt, gp, ip, lp, ln)
         ctx.extra = (c2p, nbr, visb, gamma, m, R, M, per_item, bool(pad_e0))
         return loss[:R]
@@ -768,12 +736,8 @@ class _CircleMatch(torch.autograd.Function):
         P = int(L.gdm_circle_match_bwd_parts(R, M))
         gx = torch.empty((Rp, 128), dtype=torch.float32, device=lp.device)
         gyp = torch.empty((P, Mp, 128), dtype=torch.float32, device=lp.device)
-        check(L.gdm_circle_match_bwd2_hip(xr.data_ptr(), xt.data_ptr(), xs.data_ptr(), yr.data_ptr(), yt.data_ptr(), R, M, gp.data_ptr(),
-                                          c2p.data_ptr() if c2p is not None else None, ip.data_ptr(),
-                                          nbr.data_ptr() if nbr is not None else None, int(per_item),
-                                          visb.data_ptr() if visb is not None else None, int(pad_e0),
-                                          gamma, m, lp.data_ptr(), ln.data_ptr(), coef.data_ptr(), gx.data_ptr(), gyp.data_ptr(), _stream()),
-              "gdm_circle_match_bwd2_hip")
+        call("gdm_circle_match_bwd2_hip", xr, xt, xs, yr, yt, R, M, gp, c2p, ip, nbr, int(per_item), visb, int(pad_e0), gamma, m, lp, ln,
+             coef, gx, gyp)
         return gx[:R], gyp.sum(dim=0)[:M], None, None, None, None, None, None, None, None
 
 
@@ -795,7 +759,7 @@ def circle_match(x, y, g, item, nbr=None, visb=None, c2=None, gamma=16.0, m=0.2,
     return _CircleMatch.apply(x, y, g, c2, item, nbr, visb, float(gamma), float(m), pad == "e0")
 
 
-SOFT_COORD_MAX_GAMMA = 40.0
+SOFT_COORD_MAX_GAMMA = _lib.GDM_SOFT_COORD_MAX_GAMMA
 
 
 # The differentiable soft assignment is registered through torch.library (custom_op + register_autograd), not as an autograd.Function
@@ -804,14 +768,12 @@ SOFT_COORD_MAX_GAMMA = 40.0
 @torch.library.custom_op("gdm::soft_coord_fwd", mutates_args=(), device_types="cuda")
 def _soft_coord_fwd(x: torch.Tensor, y: torch.Tensor, xyz: torch.Tensor,
                     gamma: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    L = _lib.lib()
     R, M = x.shape[0], y.shape[0]
     xr, xt, _ = _cm_pack(x)
     yr, yt, _ = _cm_pack(y)
     lse = torch.empty(R, dtype=torch.float32, device=x.device)
     soft = torch.empty((R, 3), dtype=torch.float32, device=x.device)
-    check(L.gdm_soft_coord_fwd_hip(xr.data_ptr(), xt.data_ptr(), yr.data_ptr(), yt.data_ptr(), xyz.data_ptr(), R, M, gamma,
-                                   lse.data_ptr(), soft.data_ptr(), _stream()), "gdm_soft_coord_fwd_hip")
+    call("gdm_soft_coord_fwd_hip", xr, xt, yr, yt, xyz, R, M, gamma, lse, soft)
     return lse, soft, xr, xt, yr, yt
 
 
@@ -835,8 +797,7 @@ def _soft_coord_bwd(xr: torch.Tensor, xt: torch.Tensor, yr: torch.Tensor, yt: to
     gx = torch.empty((R, 128), dtype=torch.float32, device=lse.device)
     gy = torch.empty((M, 128), dtype=torch.float32, device=lse.device)
     part = torch.empty((P, Mp, 128), dtype=torch.float32, device=lse.device)
-    check(L.gdm_soft_coord_bwd_hip(xr.data_ptr(), xt.data_ptr(), yr.data_ptr(), yt.data_ptr(), xyz.data_ptr(), R, M, gamma, lse.data_ptr(),
-                                   kb.data_ptr(), gx.data_ptr(), part.data_ptr(), gy.data_ptr(), _stream()), "gdm_soft_coord_bwd_hip")
+    call("gdm_soft_coord_bwd_hip", xr, xt, yr, yt, xyz, R, M, gamma, lse, kb, gx, part, gy)
     return gx, gy
 
 
@@ -909,11 +870,7 @@ def affine_act(x, scale, shift, act=ACT_NONE, slope=0.0, res=None, res_scale=Non
         res = _dev(res, torch.float32, "res")
         assert res.shape == x.shape
     y = x if inplace else torch.empty_like(x)
-    check(_lib.lib().gdm_affine_act_hip(x.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                        res.data_ptr() if res is not None else None,
-                                        res_scale.data_ptr() if res_scale is not None else None,
-                                        res_shift.data_ptr() if res_shift is not None else None,
-                                        B * C, C, inner, act, float(slope), y.data_ptr(), _stream()), "gdm_affine_act_hip")
+    call("gdm_affine_act_hip", x, scale, shift, res, res_scale, res_shift, B * C, C, inner, act, float(slope), y)
     return y
 
 
@@ -974,9 +931,8 @@ def pointwise(segs, wt, scale=None, shift=None, act=ACT_NONE, slope=0.0, point_m
         outC = out.shape[2] if point_major else out.shape[1]
         if not out.is_contiguous() or out.dtype != torch.float32 or out.shape[0] != B or (out.shape[1] if point_major else out.shape[2]) != n:
             raise ValueError("pointwise: out must be a contiguous f32 [B,%s] tensor" % ("n,outC" if point_major else "outC,n"))
-    check(_lib.lib().gdm_pointwise2_hip(arr, len(segs), wt.data_ptr(), 1 if w_rowmajor else 0, scale.data_ptr() if scale is not None else None,
-                                        shift.data_ptr() if shift is not None else None, B, n, Cout, int(act), float(slope),
-                                        out.data_ptr(), outC, int(out_c0), 1 if point_major else 0, _stream()), "gdm_pointwise2_hip")
+    call("gdm_pointwise2_hip", arr, len(segs), wt, 1 if w_rowmajor else 0, scale, shift, B, n, Cout, int(act), float(slope), out, outC,
+         int(out_c0), 1 if point_major else 0)
     return out
 
 
@@ -991,10 +947,7 @@ def pointwise_chain2(x, p0, p1):
         raise ValueError("pointwise_chain2: weights %s, %s do not chain from %d channels" % (tuple(w0.shape), tuple(w1.shape), C0))
     y0 = torch.empty((B, C1, n), dtype=torch.float32, device=x.device)
     y1 = torch.empty((B, C2, n), dtype=torch.float32, device=x.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    check(_lib.lib().gdm_pointwise_chain2_hip(x.data_ptr(), w0.data_ptr(), ptr(s0), ptr(b0), int(a0), float(sl0), w1.data_ptr(), ptr(s1), ptr(b1),
-                                              int(a1), float(sl1), B, n, C0, C1, C2, y0.data_ptr(), y1.data_ptr(), _stream()),
-          "gdm_pointwise_chain2_hip")
+    call("gdm_pointwise_chain2_hip", x, w0, s0, b0, int(a0), float(sl0), w1, s1, b1, int(a1), float(sl1), B, n, C0, C1, C2, y0, y1)
     return y0, y1
 
 
@@ -1017,7 +970,7 @@ def pointwise_jobs(xs, wts):
         arr[j] = _lib.PwJob(x.data_ptr(), wt.data_ptr(), out.data_ptr(), x.shape[2])
         keep += [x, wt]
         outs.append(out)
-    check(_lib.lib().gdm_pointwise_jobs_hip(arr, len(xs), B, K, Cout, _stream()), "gdm_pointwise_jobs_hip")
+    call("gdm_pointwise_jobs_hip", arr, len(xs), B, K, Cout)
     return outs
 
 
@@ -1044,14 +997,12 @@ class _BatchNormAct(torch.autograd.Function):
         sums = torch.empty(L.gdm_bn_sums_len(B, C, inner), dtype=torch.float64, device=x.device)
         saved = torch.empty(5 * C, dtype=torch.float32, device=x.device)       # a | b | fp32 mean | rstd | mean - fp32 mean
         y = torch.empty_like(x)
-        check(L.gdm_bn_stats_hip(x.data_ptr(), B, C, inner, sums.data_ptr(), _stream()), "gdm_bn_stats_hip")
+        call("gdm_bn_stats_hip", x, B, C, inner, sums)
         groups = 0
         if group is not None:                               # SyncBatchNorm: statistics over the whole data-parallel batch
             sums, groups = _fold_and_all_reduce(sums, C, group), 1
-        check(L.gdm_bn_fwd_apply_hip(x.data_ptr(), sums.data_ptr(), groups, weight.data_ptr(), bias.data_ptr(), B, C, inner, float(eps),
-                                     float(momentum), act, float(slope), saved.data_ptr(),
-                                     running_mean.data_ptr() if running_mean is not None else None,
-                                     running_var.data_ptr() if running_var is not None else None, y.data_ptr(), _stream()), "gdm_bn_fwd_apply_hip")
+        call("gdm_bn_fwd_apply_hip", x, sums, groups, weight, bias, B, C, inner, float(eps), float(momentum), act, float(slope), saved,
+             running_mean, running_var, y)
         ctx.save_for_backward(x, weight, saved)
         ctx.act, ctx.slope, ctx.group = act, float(slope), group
         return y
@@ -1067,8 +1018,7 @@ class _BatchNormAct(torch.autograd.Function):
         gw = torch.empty(C, dtype=torch.float32, device=x.device)
         gb = torch.empty(C, dtype=torch.float32, device=x.device)
         gx = torch.empty_like(x)
-        check(L.gdm_bn_bwd_reduce_hip(x.data_ptr(), go.data_ptr(), saved.data_ptr(), B, C, inner, ctx.act, ctx.slope, sums.data_ptr(), _stream()),
-              "gdm_bn_bwd_reduce_hip")
+        call("gdm_bn_bwd_reduce_hip", x, go, saved, B, C, inner, ctx.act, ctx.slope, sums)
         groups = 0
         local = None
         if ctx.group is not None:
@@ -1076,8 +1026,7 @@ class _BatchNormAct(torch.autograd.Function):
             # the ranks afterwards, as with nn.SyncBatchNorm)
             local = sums[:-2].view(-1, C, 2).sum(0)
             sums, groups = _fold_and_all_reduce(sums, C, ctx.group), 1
-        check(L.gdm_bn_bwd_apply_hip(x.data_ptr(), go.data_ptr(), sums.data_ptr(), groups, weight.data_ptr(), saved.data_ptr(), B, C, inner,
-                                     ctx.act, ctx.slope, gw.data_ptr(), gb.data_ptr(), gx.data_ptr(), _stream()), "gdm_bn_bwd_apply_hip")
+        call("gdm_bn_bwd_apply_hip", x, go, sums, groups, weight, saved, B, C, inner, ctx.act, ctx.slope, gw, gb, gx)
         if local is not None:
             mean, rstd = saved[2 * C:3 * C].double() + saved[4 * C:].double(), saved[3 * C:4 * C].double()
             gb = local[:, 0].float()
@@ -1155,12 +1104,10 @@ def upconv3x3_gather(z, scale, shift, cout, out_size, act=ACT_NONE, slope=0.0, p
     if (packed and (cout == 64 or cout % 128 == 0) and OW % 32 == 0 and (B * OH * OW) % 256 == 0 and B * cout // 8 <= 65535
             and (OH, OW) == (2 * H, 2 * W)):
         opk = PackedAct(_packed_buffer(B, cout, OH, OW, z.device), (B, cout, OH, OW))
-        check(_lib.lib().gdm_upconv3x3_gather2_hip(z.data_ptr(), scale.data_ptr(), shift.data_ptr(), B, cout, H, W, OH, OW, act,
-                                                   float(slope), out.data_ptr(), opk.buf.data_ptr(), _stream()), "gdm_upconv3x3_gather2_hip")
+        call("gdm_upconv3x3_gather2_hip", z, scale, shift, B, cout, H, W, OH, OW, act, float(slope), out, opk.buf)
         out._gdm_packed = opk
         return out
-    check(_lib.lib().gdm_upconv3x3_gather_hip(z.data_ptr(), scale.data_ptr(), shift.data_ptr(), B, cout, H, W, OH, OW, act,
-                                              float(slope), out.data_ptr(), _stream()), "gdm_upconv3x3_gather_hip")
+    call("gdm_upconv3x3_gather_hip", z, scale, shift, B, cout, H, W, OH, OW, act, float(slope), out)
     return out
 
 
@@ -1171,7 +1118,7 @@ def upconv_fused64_pack_weight(weight):
         raise ValueError("upconv_fused64_pack_weight: weight must be [64,64,3,3], got %s" % (tuple(w.shape),))
     L = _lib.lib()
     wpk = torch.empty(L.gdm_upconv_fused64_weight_bytes(), dtype=torch.uint8, device=w.device)
-    check(L.gdm_upconv_fused64_pack_weight_hip(w.data_ptr(), wpk.data_ptr(), _stream()), "gdm_upconv_fused64_pack_weight_hip")
+    call("gdm_upconv_fused64_pack_weight_hip", w, wpk)
     return wpk
 
 
@@ -1181,8 +1128,7 @@ def upconv_fused64(x, wpk, scale, shift, out_size, act=0, slope=0.0):
     B, C, H, W = x.shape
     OH, OW = int(out_size[0]), int(out_size[1])
     out = torch.empty((B, C, OH, OW), dtype=torch.float32, device=x.device)
-    check(_lib.lib().gdm_upconv_fused64_hip(x.data_ptr(), wpk.data_ptr(), scale.data_ptr(), shift.data_ptr(), B, C, H, W, OH, OW, act,
-                                            float(slope), out.data_ptr(), _stream()), "gdm_upconv_fused64_hip")
+    call("gdm_upconv_fused64_hip", x, wpk, scale, shift, B, C, H, W, OH, OW, act, float(slope), out)
     return out
 
 
@@ -1196,8 +1142,7 @@ class _UpconvGather(torch.autograd.Function):
         ones = torch.ones(cout, dtype=torch.float32, device=z.device)
         shift = bias.detach().contiguous() if bias is not None else torch.zeros(cout, dtype=torch.float32, device=z.device)
         out = torch.empty((B, cout, OH, OW), dtype=torch.float32, device=z.device)
-        check(_lib.lib().gdm_upconv3x3_gather_hip(z.data_ptr(), ones.data_ptr(), shift.data_ptr(), B, cout, H, W, OH, OW, ACT_NONE, 0.0,
-                                                  out.data_ptr(), _stream()), "gdm_upconv3x3_gather_hip")
+        call("gdm_upconv3x3_gather_hip", z, ones, shift, B, cout, H, W, OH, OW, ACT_NONE, 0.0, out)
         ctx.shape = (B, cout, H, W, OH, OW)
         ctx.has_bias = bias is not None
         return out
@@ -1207,8 +1152,7 @@ class _UpconvGather(torch.autograd.Function):
         B, cout, H, W, OH, OW = ctx.shape
         go = go.contiguous()
         gz = torch.empty((B, 9 * cout, H, W), dtype=torch.float32, device=go.device)
-        check(_lib.lib().gdm_upconv3x3_gather_bwd_hip(go.data_ptr(), B, cout, H, W, OH, OW, gz.data_ptr(), _stream()),
-              "gdm_upconv3x3_gather_bwd_hip")
+        call("gdm_upconv3x3_gather_bwd_hip", go, B, cout, H, W, OH, OW, gz)
         return gz, (channel_sum(go) if ctx.has_bias else None), None, None, None
 
 
@@ -1257,15 +1201,14 @@ def gemm_wgrad(x3, go3):
         raise ValueError("gemm_wgrad: unsupported shape x %s grad_out %s" % (tuple(x3.shape), tuple(go3.shape)))
     xpk = torch.empty(nx, dtype=torch.uint8, device=x3.device)
     gpk = torch.empty(ng, dtype=torch.uint8, device=x3.device)
-    check(L.gdm_wgrad_pack_x1_hip(x3.data_ptr(), B, Cin, P, xpk.data_ptr(), _stream()), "gdm_wgrad_pack_x1_hip")
-    check(L.gdm_wgrad_pack_go_hip(go3.data_ptr(), B, Cout, P // 32, 32, gpk.data_ptr(), _stream()), "gdm_wgrad_pack_go_hip")
+    call("gdm_wgrad_pack_x1_hip", x3, B, Cin, P, xpk)
+    call("gdm_wgrad_pack_go_hip", go3, B, Cout, P // 32, 32, gpk)
     nchunk = B * P // 128
     parts = _wgrad_parts(nchunk, (Cin // 256) * ((Cout + 127) // 128))
     n = nchunk // parts
     coutp = (Cout + 127) // 128 * 128
     out = torch.empty((parts, Cout, Cin), dtype=torch.float32, device=x3.device)
-    check(L.gdm_conv1x1_packed_wb_hip(xpk.data_ptr(), gpk.data_ptr(), n * coutp * 512, parts, 128 * n, Cout, 1, Cin, out.data_ptr(), _stream()),
-          "gdm_conv1x1_packed_wb_hip")
+    call("gdm_conv1x1_packed_wb_hip", xpk, gpk, n * coutp * 512, parts, 128 * n, Cout, 1, Cin, out)
     return out[0] if parts == 1 else out.sum(0)
 
 
@@ -1299,8 +1242,7 @@ def wgrad_direct(x3, go3, bias=False):
     nsplit = max(1, min(nsteps // (8 * slices), 512 // blocks))           # >= 8 steps per wave, two workgroups per CU = one resident round
     part = torch.empty((nsplit, Cout, Cin), dtype=torch.float32, device=x3.device)
     bpart = torch.empty((nsplit, Cout), dtype=torch.float32, device=x3.device) if bias else None
-    check(_lib.lib().gdm_wgrad_direct_hip(go3.data_ptr(), go3.stride(0), x3.data_ptr(), x3.stride(0), B, Cout, Cin, P, nsplit,
-                                          part.data_ptr(), bpart.data_ptr() if bias else None, _stream()), "gdm_wgrad_direct_hip")
+    call("gdm_wgrad_direct_hip", go3, go3.stride(0), x3, x3.stride(0), B, Cout, Cin, P, nsplit, part, bpart)
     return part.sum(0), (bpart.sum(0) if bias else None)
 
 
@@ -1455,10 +1397,8 @@ def psp_combine(g, ys, bias, packed=False):
     opk = None
     if packed and (C == 64 or C % 128 == 0) and W % 32 == 0 and (B * H * W) % 256 == 0 and B * C // 8 <= 65535:
         opk = PackedAct(_packed_buffer(B, C, H, W, g.device), (B, C, H, W))
-    check(_lib.lib().gdm_psp_combine2_hip(g.data_ptr(), ys[0].data_ptr(), ys[0].shape[2], ys[1].data_ptr(), ys[1].shape[2],
-                                          ys[2].data_ptr(), ys[2].shape[2], ys[3].data_ptr(), ys[3].shape[2],
-                                          bias.data_ptr() if bias is not None else None, B, C, H, W, g.data_ptr(),
-                                          opk.buf.data_ptr() if opk is not None else None, _stream()), "gdm_psp_combine2_hip")
+    call("gdm_psp_combine2_hip", g, ys[0], ys[0].shape[2], ys[1], ys[1].shape[2], ys[2], ys[2].shape[2], ys[3], ys[3].shape[2], bias, B, C,
+         H, W, g, opk.buf if opk is not None else None)
     if opk is not None:
         g._gdm_packed = opk
     return g
@@ -1491,11 +1431,8 @@ def gather_add_affine_act(x, t, idx, scale, shift, act=ACT_NONE, slope=0.0, hw=N
         opk = PackedAct(_packed_buffer(B, C, hw[0], hw[1], x.device), (B, C, hw[0], hw[1]))
     if not f32_out and opk is None:
         raise ValueError("gather_add_affine_act: f32_out=False needs a map the packed operand is built for, got x %s hw %s" % (tuple(x.shape), hw))
-    check(_lib.lib().gdm_gather_add_affine_act2_hip(x.data_ptr(), t.data_ptr(), idx.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                    B, C, n, m, act, float(slope), x.data_ptr() if f32_out else None,
-                                                    opk.buf.data_ptr() if opk is not None else None,
-                                                    hw[1] if opk is not None else 0, _stream()),
-          "gdm_gather_add_affine_act2_hip")
+    call("gdm_gather_add_affine_act2_hip", x, t, idx, scale, shift, B, C, n, m, act, float(slope), x if f32_out else None,
+         opk.buf if opk is not None else None, hw[1] if opk is not None else 0)
     if not f32_out:
         return opk
     return (x, opk) if hw is not None else x
@@ -1511,11 +1448,9 @@ def lfa_stage(xyz, idx, feat, w1t, s1, b1, w2t, s2, b2, wft, wmt, sm, bm, slope=
     H = feat.shape[1]
     D, OUT = 2 * H, wmt.shape[1]
     out = torch.empty((B, OUT, n), dtype=torch.float32, device=feat.device)
-    z = 0
-    check(_lib.lib().gdm_lfa_stage_hip(xyz.data_ptr(), idx.data_ptr(), feat.data_ptr(), w1t.data_ptr(), s1.data_ptr(), b1.data_ptr(),
-                                       w2t.data_ptr() if w2t is not None else z, s2.data_ptr() if w2t is not None else z,
-                                       b2.data_ptr() if w2t is not None else z, wft.data_ptr(), wmt.data_ptr(), sm.data_ptr(),
-                                       bm.data_ptr(), B, n, K, D, OUT, float(slope), out.data_ptr(), _stream()), "gdm_lfa_stage_hip")
+    if w2t is None:
+        s2 = b2 = None
+    call("gdm_lfa_stage_hip", xyz, idx, feat, w1t, s1, b1, w2t, s2, b2, wft, wmt, sm, bm, B, n, K, D, OUT, float(slope), out)
     return out
 
 
@@ -1538,10 +1473,8 @@ def conv64_gather_add_act_mfma(x, wpk, t, idx, scale, shift, act=ACT_NONE, slope
     opk = None
     if hw is not None and not pixel_major and hw[0] * hw[1] == m and hw[1] % 32 == 0 and (B * m) % 256 == 0:
         opk = PackedAct(_packed_buffer(B, C, hw[0], hw[1], x.device), (B, C, hw[0], hw[1]))
-    check(_lib.lib().gdm_conv64_gather_add_act_mfma2_hip(x.data_ptr(), wpk.data_ptr(), t.data_ptr(), idx.data_ptr(), scale.data_ptr(),
-                                                         shift.data_ptr(), B, n, m, act, float(slope), int(bool(pixel_major)),
-                                                         int(bool(t_point_major)), y.data_ptr(), opk.buf.data_ptr() if opk is not None else None,
-                                                         int(hw[1]) if opk is not None else 0, _stream()), "gdm_conv64_gather_add_act_mfma2_hip")
+    call("gdm_conv64_gather_add_act_mfma2_hip", x, wpk, t, idx, scale, shift, B, n, m, act, float(slope), int(bool(pixel_major)),
+         int(bool(t_point_major)), y, opk.buf if opk is not None else None, int(hw[1]) if opk is not None else 0)
     if opk is not None:
         y._gdm_packed = opk
     return y
@@ -1559,9 +1492,7 @@ def conv1x1_gather_add_act(x, wt, t, idx, scale, shift, act=ACT_NONE, slope=0.0,
     if C != 64 or tuple(wt.shape) != (64, 64) or t.shape[1] != 64:
         raise ValueError("conv1x1_gather_add_act: built for 64 -> 64 channels, got x %s wt %s t %s" % (tuple(x.shape), tuple(wt.shape), tuple(t.shape)))
     y = torch.empty((B, m, C), dtype=torch.float32, device=x.device) if pixel_major else torch.empty_like(x)
-    check(_lib.lib().gdm_conv1x1_gather_add_act2_hip(x.data_ptr(), wt.data_ptr(), t.data_ptr(), idx.data_ptr(), scale.data_ptr(),
-                                                     shift.data_ptr(), B, C, t.shape[2], m, act, float(slope), int(bool(pixel_major)),
-                                                     y.data_ptr(), _stream()), "gdm_conv1x1_gather_add_act2_hip")
+    call("gdm_conv1x1_gather_add_act2_hip", x, wt, t, idx, scale, shift, B, C, t.shape[2], m, act, float(slope), int(bool(pixel_major)), y)
     return y
 
 
@@ -1597,13 +1528,8 @@ def point_heads(a, b, layers, last, feat_layer, res_layer, residual=None):
         rb = _dev(residual[1], torch.float32, "residual") if residual[1] is not None else None
         if ra.shape[0] != B or ra.shape[2] != N or ra.shape[1] + (rb.shape[1] if rb is not None else 0) != 128:
             raise ValueError("point_heads: the residual source must make 128 channels of the same points")
-    check(_lib.lib().gdm_point_heads2_hip(a.data_ptr(), b.data_ptr() if b is not None else None, Ca,
-                                          ra.data_ptr() if ra is not None else None, rb.data_ptr() if rb is not None else None,
-                                          ra.shape[1] if ra is not None else 0, B, N, n, w_arr, sc_arr, sh_arr, act_arr,
-                                          int(feat_layer), int(res_layer), wl.data_ptr() if wl is not None else None,
-                                          bl.data_ptr() if bl is not None else None, int(c_last),
-                                          out_feat.data_ptr() if out_feat is not None else None,
-                                          out_last.data_ptr() if out_last is not None else None, _stream()), "gdm_point_heads2_hip")
+    call("gdm_point_heads2_hip", a, b, Ca, ra, rb, ra.shape[1] if ra is not None else 0, B, N, n, w_arr, sc_arr, sh_arr, act_arr,
+         int(feat_layer), int(res_layer), wl, bl, int(c_last), out_feat, out_last)
     return out_feat, out_last
 
 
@@ -1613,7 +1539,7 @@ def pack_rows64(w2d):
     if w.dim() != 2 or w.shape[1] != 64:
         raise ValueError("pack_rows64: expected [R,64], got %s" % (tuple(w.shape),))
     out = torch.empty(w.shape[0] * 256, dtype=torch.uint8, device=w.device)
-    check(_lib.lib().gdm_pack_rows64_hip(w.data_ptr(), w.shape[0], out.data_ptr(), _stream()), "gdm_pack_rows64_hip")
+    call("gdm_pack_rows64_hip", w, w.shape[0], out)
     return out
 
 
@@ -1631,9 +1557,7 @@ def upconv_final_points(x_pm, hw, choose, wpk, scale, shift, act, slope, wf_pk, 
     N = choose.shape[1]
     OH, OW = int(out_size[0]), int(out_size[1])
     out = torch.empty((B, 64, N), dtype=torch.float32, device=x_pm.device)
-    check(_lib.lib().gdm_upconv_final_points_hip(x_pm.data_ptr(), choose.data_ptr(), wpk.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                 act, float(slope), wf_pk.data_ptr(), fbias.data_ptr() if fbias is not None else None,
-                                                 B, H, W, OH, OW, N, out.data_ptr(), _stream()), "gdm_upconv_final_points_hip")
+    call("gdm_upconv_final_points_hip", x_pm, choose, wpk, scale, shift, act, float(slope), wf_pk, fbias, B, H, W, OH, OW, N, out)
     return out
 
 
@@ -1646,7 +1570,7 @@ def stem_pack_weight(weight):
         raise ValueError("stem_pack_weight: the stem kernel is built for a [64,3,7,7] filter, got %s" % (tuple(w.shape),))
     L = _lib.lib()
     wpk = torch.empty(L.gdm_stem_weight_bytes(), dtype=torch.uint8, device=w.device)
-    check(L.gdm_stem_pack_weight_hip(w.data_ptr(), wpk.data_ptr(), _stream()), "gdm_stem_pack_weight_hip")
+    call("gdm_stem_pack_weight_hip", w, wpk)
     return wpk
 
 
@@ -1662,8 +1586,7 @@ def stem(x, wpk, scale, shift, packed=True):
     opk = None
     if packed and (B * PH * PW) % 256 == 0 and PW % 16 == 0:
         opk = PackedAct(_packed_buffer(B, 64, PH, PW, x.device), (B, 64, PH, PW))
-    check(_lib.lib().gdm_stem_hip(x.data_ptr(), wpk.data_ptr(), scale.data_ptr(), shift.data_ptr(), B, H, W, out.data_ptr(),
-                                  opk.buf.data_ptr() if opk is not None else None, _stream()), "gdm_stem_hip")
+    call("gdm_stem_hip", x, wpk, scale, shift, B, H, W, out, opk.buf if opk is not None else None)
     if opk is not None:
         out._gdm_packed = opk
     return out
@@ -1674,8 +1597,7 @@ def affine_relu_maxpool(x, scale, shift):
     x = _dev(x, torch.float32, "x")
     B, C, H, W = x.shape
     y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-    check(_lib.lib().gdm_affine_relu_maxpool_hip(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), B, C, H, W, y.data_ptr(), _stream()),
-          "gdm_affine_relu_maxpool_hip")
+    call("gdm_affine_relu_maxpool_hip", x, scale, shift, B, C, H, W, y)
     return y
 
 
@@ -1693,8 +1615,7 @@ def conv1x1_logsoftmax(x, weight, bias):
     B, C, H, W = x.shape
     w = _final_weight_t(weight)
     out = torch.empty_like(x)
-    check(_lib.lib().gdm_conv1x1_logsoftmax_hip(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                B, C, H * W, out.data_ptr(), _stream()), "gdm_conv1x1_logsoftmax_hip")
+    call("gdm_conv1x1_logsoftmax_hip", x, w, bias, B, C, H * W, out)
     return out
 
 
@@ -1711,10 +1632,7 @@ def conv64_gather_add_final(x, wpk, t, idx, scale, shift, act, slope, final_weig
                          % (tuple(x.shape), tuple(t.shape), tuple(final_weight.shape)))
     wft = _final_weight_t(final_weight)
     out = torch.empty_like(x)
-    check(_lib.lib().gdm_conv64_gather_add_final_hip(x.data_ptr(), wpk.data_ptr(), t.data_ptr(), idx.data_ptr(), scale.data_ptr(),
-                                                     shift.data_ptr(), B, t.shape[1], m, act, float(slope), wft.data_ptr(),
-                                                     final_bias.data_ptr() if final_bias is not None else None, out.data_ptr(),
-                                                     _stream()), "gdm_conv64_gather_add_final_hip")
+    call("gdm_conv64_gather_add_final_hip", x, wpk, t, idx, scale, shift, B, t.shape[1], m, act, float(slope), wft, final_bias, out)
     return out
 
 
@@ -1728,7 +1646,7 @@ def channel_sum(t):
         return t.sum(dim=[0] + list(range(2, t.dim())))
     L = _lib.lib()
     sums = torch.empty(L.gdm_bn_sums_len(B, C, inner), dtype=torch.float64, device=t.device)
-    check(L.gdm_bn_stats_hip(t.data_ptr(), B, C, inner, sums.data_ptr(), _stream()), "gdm_bn_stats_hip")
+    call("gdm_bn_stats_hip", t, B, C, inner, sums)
     return sums[:-2].view(-1, C, 2)[:, :, 0].sum(0).float()
 
 
@@ -1738,8 +1656,7 @@ class _PspPools(torch.autograd.Function):
         x = _dev(x, torch.float32, "x")
         B, C, H, W = x.shape
         outs = [torch.empty((B, C, s_, s_), dtype=torch.float32, device=x.device) for s_ in (1, 2, 3, 6)]
-        check(_lib.lib().gdm_psp_pools_hip(x.data_ptr(), B * C, H, W, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
-                                           outs[3].data_ptr(), _stream()), "gdm_psp_pools_hip")
+        call("gdm_psp_pools_hip", x, B * C, H, W, outs[0], outs[1], outs[2], outs[3])
         ctx.shape = (B, C, H, W)
         return tuple(outs)
 
@@ -1748,8 +1665,7 @@ class _PspPools(torch.autograd.Function):
         B, C, H, W = ctx.shape
         gs = [_dev(g, torch.float32, "grad") for g in (g1, g2, g3, g6)]
         gx = torch.empty((B, C, H, W), dtype=torch.float32, device=gs[0].device)
-        check(_lib.lib().gdm_psp_pools_bwd_hip(gs[0].data_ptr(), gs[1].data_ptr(), gs[2].data_ptr(), gs[3].data_ptr(), B * C, H, W,
-                                               gx.data_ptr(), _stream()), "gdm_psp_pools_bwd_hip")
+        call("gdm_psp_pools_bwd_hip", gs[0], gs[1], gs[2], gs[3], B * C, H, W, gx)
         return gx
 
 
@@ -1771,10 +1687,8 @@ class _PspCombine(torch.autograd.Function):
         ys = [_dev(y, torch.float32, "y") for y in (y1, y2, y3, y4)]
         B, C, H, W = g.shape
         out = torch.empty_like(g)
-        check(_lib.lib().gdm_psp_combine2_hip(g.data_ptr(), ys[0].data_ptr(), ys[0].shape[2], ys[1].data_ptr(), ys[1].shape[2],
-                                              ys[2].data_ptr(), ys[2].shape[2], ys[3].data_ptr(), ys[3].shape[2],
-                                              bias.data_ptr() if bias is not None else None, B, C, H, W, out.data_ptr(), None, _stream()),
-              "gdm_psp_combine2_hip")
+        call("gdm_psp_combine2_hip", g, ys[0], ys[0].shape[2], ys[1], ys[1].shape[2], ys[2], ys[2].shape[2], ys[3], ys[3].shape[2], bias,
+             B, C, H, W, out, None)
         ctx.save_for_backward(out)
         ctx.sizes = [y.shape[2] for y in ys]
         ctx.has_bias = bias is not None
@@ -1786,10 +1700,9 @@ class _PspCombine(torch.autograd.Function):
         B, C, H, W = out.shape
         gpre = torch.where(out > 0, go, torch.zeros((), dtype=go.dtype, device=go.device)).contiguous()
         gys = []
-        L = _lib.lib()
         for s_ in ctx.sizes:
             gy = torch.empty((B, C, s_, s_), dtype=torch.float32, device=go.device)
-            check(L.gdm_upsample_bilinear_bwd_hip(gpre.data_ptr(), B * C, s_, s_, H, W, gy.data_ptr(), _stream()), "gdm_upsample_bilinear_bwd_hip")
+            call("gdm_upsample_bilinear_bwd_hip", gpre, B * C, s_, s_, H, W, gy)
             gys.append(gy)
         gb = channel_sum(gpre) if ctx.has_bias else None
         return gpre, gb, gys[0], gys[1], gys[2], gys[3]
@@ -1871,8 +1784,8 @@ def conv3x3_wgrad(x, go, parts=None):
         raise ValueError("conv3x3_wgrad: unsupported shape x %s grad_out %s" % (tuple(x.shape), tuple(go.shape)))
     xpk = torch.empty(nx, dtype=torch.uint8, device=x.device)
     gpk = torch.empty(ng, dtype=torch.uint8, device=x.device)
-    check(L.gdm_wgrad_pack_x_hip(x.data_ptr(), B, Cin, H, W, xpk.data_ptr(), _stream()), "gdm_wgrad_pack_x_hip")
-    check(L.gdm_wgrad_pack_go_hip(go.data_ptr(), B, Cout, H, W, gpk.data_ptr(), _stream()), "gdm_wgrad_pack_go_hip")
+    call("gdm_wgrad_pack_x_hip", x, B, Cin, H, W, xpk)
+    call("gdm_wgrad_pack_go_hip", go, B, Cout, H, W, gpk)
     nchunk = B * H * W // 128
     if parts is None:
         # parts: the largest divisor of the chunk count that keeps the launch at about one round of workgroups (a part has
@@ -1887,8 +1800,7 @@ def conv3x3_wgrad(x, go, parts=None):
     n = nchunk // parts
     coutp = (Cout + 127) // 128 * 128
     out = torch.empty((parts, Cout, 9, Cin), dtype=torch.float32, device=x.device)
-    check(L.gdm_conv1x1_packed_wb_hip(xpk.data_ptr(), gpk.data_ptr(), n * coutp * 512, parts, 128 * n, Cout, 9, Cin, out.data_ptr(), _stream()),
-          "gdm_conv1x1_packed_wb_hip")
+    call("gdm_conv1x1_packed_wb_hip", xpk, gpk, n * coutp * 512, parts, 128 * n, Cout, 9, Cin, out)
     dw = out[0] if parts == 1 else out.sum(0)
     return dw.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
 
@@ -1914,7 +1826,7 @@ def conv_pack_weight_dgrad(weight):
     L = _lib.lib()
     nbytes = L.gdm_conv3x3_weight_bytes(Cin, Cout) if taps == 9 else L.gdm_conv1x1_weight_bytes(Cin, Cout)
     wpk = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    check(L.gdm_conv_pack_weight_dgrad_hip(weight.data_ptr(), Cout, Cin, taps, wpk.data_ptr(), _stream()), "gdm_conv_pack_weight_dgrad_hip")
+    call("gdm_conv_pack_weight_dgrad_hip", weight, Cout, Cin, taps, wpk)
     return wpk
 
 
@@ -1924,7 +1836,7 @@ def conv3x3_pack_weight(weight):
     Cout, Cin = weight.shape[0], weight.shape[1]
     L = _lib.lib()
     wpk = torch.empty(L.gdm_conv3x3_weight_bytes(Cout, Cin), dtype=torch.uint8, device=weight.device)
-    check(L.gdm_conv3x3_pack_weight_hip(weight.data_ptr(), Cout, Cin, wpk.data_ptr(), _stream()), "gdm_conv3x3_pack_weight_hip")
+    call("gdm_conv3x3_pack_weight_hip", weight, Cout, Cin, wpk)
     return wpk
 
 
@@ -1958,7 +1870,7 @@ def conv3x3_pack_act(x):
     x = _dev(x, torch.float32, "x")
     B, C, H, W = x.shape
     buf = _packed_buffer(B, C, H, W, x.device)
-    check(_lib.lib().gdm_conv3x3_pack_act_hip(x.data_ptr(), B, C, H, W, buf.data_ptr(), _stream()), "gdm_conv3x3_pack_act_hip")
+    call("gdm_conv3x3_pack_act_hip", x, B, C, H, W, buf)
     return PackedAct(buf, (B, C, H, W))
 
 
@@ -1972,7 +1884,6 @@ def conv3x3_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, res=None,
         if stride != 2 or H % 2 or W % 2:
             raise ValueError("conv3x3_bf16x3: stride %r on a %dx%d map" % (stride, H, W))
         H, W = H // 2, W // 2
-    L = _lib.lib()
     dev = xp.buf.device
     out = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev) if out_f32 else None
     opk = None
@@ -1983,10 +1894,8 @@ def conv3x3_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, res=None,
     if res is not None:
         res = _dev(res, torch.float32, "res")
         assert tuple(res.shape) == (B, cout, H, W)
-    check(L.gdm_conv3x3_strided_hip(xp.buf.data_ptr(), wpk.data_ptr(), scale.data_ptr() if scale is not None else None,
-                                    shift.data_ptr() if shift is not None else None, res.data_ptr() if res is not None else None,
-                                    B, Cin, cout, H, W, int(stride), act, out.data_ptr() if out is not None else None,
-                                    opk.buf.data_ptr() if opk is not None else None, _stream()), "gdm_conv3x3_strided_hip")
+    call("gdm_conv3x3_strided_hip", xp.buf, wpk, scale, shift, res, B, Cin, cout, H, W, int(stride), act, out,
+         opk.buf if opk is not None else None)
     return (out, opk) if out_packed else out
 
 
@@ -2063,10 +1972,8 @@ def conv1x1_packed_gather_add_act(x, wpk, cout, t, idx, scale, shift, act=ACT_NO
     opk = None
     if packed_out_supported(B, cout, H, W):
         opk = PackedAct(_packed_buffer(B, cout, H, W, dev, avoid=xp.buf), (B, cout, H, W))
-    check(_lib.lib().gdm_conv1x1_gather_add_hip(xp.buf.data_ptr(), wpk.data_ptr(), idx.data_ptr(), t.data_ptr(), t.shape[2],
-                                                scale.data_ptr(), shift.data_ptr(), B, Cin, cout, H, W, act,
-                                                y.data_ptr() if y is not None else None,
-                                                opk.buf.data_ptr() if opk is not None else None, _stream()), "gdm_conv1x1_gather_add_hip")
+    call("gdm_conv1x1_gather_add_hip", xp.buf, wpk, idx, t, t.shape[2], scale, shift, B, Cin, cout, H, W, act, y,
+         opk.buf if opk is not None else None)
     return (y, opk) if f32_out else opk
 
 
@@ -2078,9 +1985,7 @@ def conv1x1_packed2d(xp, wpk, cout, scale=None, shift=None, act=ACT_NONE, stride
         raise ValueError("conv1x1_packed2d: stride %r on a %dx%d map" % (stride, H, W))
     H, W = H // stride, W // stride
     out = torch.empty((B, cout, H, W), dtype=torch.float32, device=xp.buf.device)
-    check(_lib.lib().gdm_conv1x1_strided_hip(xp.buf.data_ptr(), wpk.data_ptr(), scale.data_ptr() if scale is not None else None,
-                                             shift.data_ptr() if shift is not None else None, B, Cin, cout, H, W, int(stride), act,
-                                             out.data_ptr(), _stream()), "gdm_conv1x1_strided_hip")
+    call("gdm_conv1x1_strided_hip", xp.buf, wpk, scale, shift, B, Cin, cout, H, W, int(stride), act, out)
     return out
 
 
@@ -2124,7 +2029,7 @@ def gemm_pack_weight(weight2d):
     Cout, Cin = w.shape
     L = _lib.lib()
     wpk = torch.empty(L.gdm_conv1x1_weight_bytes(Cout, Cin), dtype=torch.uint8, device=w.device)
-    check(L.gdm_conv1x1_pack_weight_hip(w.data_ptr(), Cout, Cin, wpk.data_ptr(), _stream()), "gdm_conv1x1_pack_weight_hip")
+    call("gdm_conv1x1_pack_weight_hip", w, Cout, Cin, wpk)
     return wpk
 
 
@@ -2133,13 +2038,10 @@ def gemm_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, pixel_major=
     f32[B,cout,n], or f32[B*n, cout] when pixel_major.  Inference only."""
     x = _dev(x, torch.float32, "x")
     B, Cin, n = x.shape
-    L = _lib.lib()
     xpk = _packed_buffer(B, Cin, 1, n, x.device)
-    check(L.gdm_conv3x3_pack_act_hip(x.data_ptr(), B, Cin, 1, n, xpk.data_ptr(), _stream()), "gdm_conv3x3_pack_act_hip")
+    call("gdm_conv3x3_pack_act_hip", x, B, Cin, 1, n, xpk)
     out = torch.empty((B * n, cout) if pixel_major else (B, cout, n), dtype=torch.float32, device=x.device)
-    check(L.gdm_conv1x1_packed_hip(xpk.data_ptr(), wpk.data_ptr(), scale.data_ptr() if scale is not None else None,
-                                   shift.data_ptr() if shift is not None else None, B, Cin, cout, 1, n, act,
-                                   1 if pixel_major else 0, out.data_ptr(), _stream()), "gdm_conv1x1_packed_hip")
+    call("gdm_conv1x1_packed_hip", xpk, wpk, scale, shift, B, Cin, cout, 1, n, act, 1 if pixel_major else 0, out)
     return out
 
 
@@ -2155,13 +2057,11 @@ def gemm_grouped(x_cm, wpk, rowidx, tile_co0, cout_total, xpk=None):
     x_cm = _dev(x_cm, torch.float32, "x")
     _, Cin, M = x_cm.shape
     R = rowidx.shape[0]
-    L = _lib.lib()
     if xpk is None:
         xpk = _packed_buffer(1, Cin, 1, M, x_cm.device)
-        check(L.gdm_conv3x3_pack_act_hip(x_cm.data_ptr(), 1, Cin, 1, M, xpk.data_ptr(), _stream()), "gdm_conv3x3_pack_act_hip")
+        call("gdm_conv3x3_pack_act_hip", x_cm, 1, Cin, 1, M, xpk)
     Y = torch.empty((R, 128), dtype=torch.float32, device=x_cm.device)
-    check(L.gdm_gemm_grouped_hip(xpk.data_ptr(), wpk.data_ptr(), rowidx.data_ptr(), tile_co0.data_ptr(), R, M, Cin, cout_total,
-                                 Y.data_ptr(), _stream()), "gdm_gemm_grouped_hip")
+    call("gdm_gemm_grouped_hip", xpk, wpk, rowidx, tile_co0, R, M, Cin, cout_total, Y)
     return Y
 
 
@@ -2171,8 +2071,7 @@ class _UpsampleBilinear(torch.autograd.Function):
         x = _dev(x, torch.float32, "x")
         B, C, H, W = x.shape
         out = torch.empty((B, C, OH, OW), dtype=torch.float32, device=x.device)
-        check(_lib.lib().gdm_upsample_bilinear_hip(x.data_ptr(), B * C, H, W, OH, OW, out.data_ptr(), _stream()),
-              "gdm_upsample_bilinear_hip")
+        call("gdm_upsample_bilinear_hip", x, B * C, H, W, OH, OW, out)
         ctx.hw = (H, W)
         return out
 
@@ -2182,8 +2081,7 @@ class _UpsampleBilinear(torch.autograd.Function):
         B, C, OH, OW = go.shape
         H, W = ctx.hw
         g = torch.empty((B, C, H, W), dtype=torch.float32, device=go.device)
-        check(_lib.lib().gdm_upsample_bilinear_bwd_hip(go.data_ptr(), B * C, H, W, OH, OW, g.data_ptr(), _stream()),
-              "gdm_upsample_bilinear_bwd_hip")
+        call("gdm_upsample_bilinear_bwd_hip", go, B * C, H, W, OH, OW, g)
         return g, None, None
 
 
@@ -2192,7 +2090,7 @@ class _PReLU1(torch.autograd.Function):
     def forward(ctx, x, slope):
         x = x.contiguous()
         y = torch.empty_like(x)
-        check(_lib.lib().gdm_prelu1_hip(x.data_ptr(), slope.data_ptr(), x.numel(), y.data_ptr(), _stream()), "gdm_prelu1_hip")
+        call("gdm_prelu1_hip", x, slope, x.numel(), y)
         ctx.save_for_backward(x, slope)
         return y
 
@@ -2202,8 +2100,7 @@ class _PReLU1(torch.autograd.Function):
         go = go.contiguous()
         gx = torch.empty_like(x)
         gs = torch.zeros_like(slope)
-        check(_lib.lib().gdm_prelu1_bwd_hip(x.data_ptr(), go.data_ptr(), slope.data_ptr(), x.numel(), gx.data_ptr(), gs.data_ptr(), _stream()),
-              "gdm_prelu1_bwd_hip")
+        call("gdm_prelu1_bwd_hip", x, go, slope, x.numel(), gx, gs)
         return gx, gs
 
 
@@ -2249,9 +2146,7 @@ def match(scene, model, precision=MATCH_BF16X3, return_sim=False):
     best_idx = torch.empty((B, N), dtype=torch.int32, device=scene.device)
     best_sim = torch.empty((B, N), dtype=torch.float32, device=scene.device)
     sim = torch.empty((B, N, M), dtype=torch.float32, device=scene.device) if return_sim else None
-    check(L.gdm_match_hip(scene.data_ptr(), model.data_ptr(), B, D, N, M, precision, best_idx.data_ptr(),
-                          best_sim.data_ptr(), sim.data_ptr() if return_sim else None, ws.data_ptr(), ws.numel(),
-                          _stream()), "gdm_match_hip")
+    call("gdm_match_hip", scene, model, B, D, N, M, precision, best_idx, best_sim, sim, ws, ws.numel())
     return (best_idx, best_sim, sim) if return_sim else (best_idx, best_sim)
 
 
@@ -2264,7 +2159,7 @@ def match_pack(x, precision=MATCH_BF16X3, out=None):
     L = _lib.lib()
     if out is None:
         out = torch.empty((L.gdm_match_rows_bytes(R * n),), dtype=torch.uint8, device=x.device)
-    check(L.gdm_match_pack_hip(x.data_ptr(), R, D, n, precision, out.data_ptr(), _stream()), "gdm_match_pack_hip")
+    call("gdm_match_pack_hip", x, R, D, n, precision, out)
     return out
 
 
@@ -2280,8 +2175,7 @@ def match_pack2(x1, x2, precision=MATCH_BF16X3):
     L = _lib.lib()
     o1 = torch.empty((L.gdm_match_rows_bytes(R1 * n1),), dtype=torch.uint8, device=x1.device)
     o2 = torch.empty((L.gdm_match_rows_bytes(R2 * n2),), dtype=torch.uint8, device=x1.device)
-    check(L.gdm_match_pack2_hip(x1.data_ptr(), R1, n1, o1.data_ptr(), x2.data_ptr(), R2, n2, o2.data_ptr(), D, precision, _stream()),
-          "gdm_match_pack2_hip")
+    call("gdm_match_pack2_hip", x1, R1, n1, o1, x2, R2, n2, o2, D, precision)
     return o1, o2
 
 
@@ -2295,14 +2189,13 @@ def match_packed(scene_rows, model_rows, B, N, M, precision=MATCH_BF16X3, return
     sim = None
     if return_sim:
         sim = sim_out if sim_out is not None else torch.empty((B, N, M), dtype=torch.float32, device=dev)
-    check(L.gdm_match_packed_hip(scene_rows.data_ptr(), model_rows.data_ptr(), B * N, M, precision, best_idx.data_ptr(),
-                                 best_sim.data_ptr(), sim.data_ptr() if return_sim else None, part.data_ptr(), part.numel(),
-                                 _stream()), "gdm_match_packed_hip")
+    call("gdm_match_packed_hip", scene_rows, model_rows, B * N, M, precision, best_idx, best_sim, sim,
+         part, part.numel())
     return (best_idx, best_sim, sim) if return_sim else (best_idx, best_sim)
 
 
-MATCH_SOFT_MAX_GAMMA = 40.0            # include/gdm.h GDM_MATCH_SOFT_MAX_GAMMA
-MATCH_SOFT_MAX_M = 16384               # include/gdm.h GDM_MATCH_SOFT_MAX_M
+MATCH_SOFT_MAX_GAMMA = _lib.GDM_MATCH_SOFT_MAX_GAMMA
+MATCH_SOFT_MAX_M = _lib.GDM_MATCH_SOFT_MAX_M
 
 
 def match_soft_packed(scene_rows, model_rows, model_xyz, B, N, M, precision=MATCH_BF16X3, gamma=16.0):
@@ -2320,9 +2213,8 @@ def match_soft_packed(scene_rows, model_rows, model_xyz, B, N, M, precision=MATC
     lse = torch.empty((B, N), dtype=torch.float32, device=dev)
     conf = torch.empty((B, N), dtype=torch.float32, device=dev)
     soft_xyz = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-    check(L.gdm_match_soft_packed_hip(scene_rows.data_ptr(), model_rows.data_ptr(), model_xyz.data_ptr(), B * N, M, precision,
-                                      float(gamma), best_idx.data_ptr(), best_sim.data_ptr(), lse.data_ptr(), conf.data_ptr(),
-                                      soft_xyz.data_ptr(), part.data_ptr(), part.numel(), _stream()), "gdm_match_soft_packed_hip")
+    call("gdm_match_soft_packed_hip", scene_rows, model_rows, model_xyz, B * N, M, precision, float(gamma), best_idx, best_sim, lse, conf,
+         soft_xyz, part, part.numel())
     return best_idx, best_sim, lse, conf, soft_xyz
 
 
@@ -2346,7 +2238,7 @@ def match_score(conf, mask):
     mask = _dev(mask, torch.uint8, "mask")
     B, N = conf.shape
     score = torch.empty((B,), dtype=torch.float32, device=conf.device)
-    check(_lib.lib().gdm_match_score_hip(conf.data_ptr(), mask.data_ptr(), B, N, score.data_ptr(), _stream()), "gdm_match_score_hip")
+    call("gdm_match_score_hip", conf, mask, B, N, score)
     return score
 
 
@@ -2357,8 +2249,7 @@ def seg_mask(seg):
     assert two == 2
     mask = torch.empty((B, N), dtype=torch.uint8, device=seg.device)
     count = torch.empty((B,), dtype=torch.int32, device=seg.device)
-    check(_lib.lib().gdm_seg_mask_hip(seg.data_ptr(), B, N, mask.data_ptr(), count.data_ptr(), _stream()),
-          "gdm_seg_mask_hip")
+    call("gdm_seg_mask_hip", seg, B, N, mask, count)
     return mask, count
 
 
@@ -2384,20 +2275,13 @@ def sample_assemble(valid_depth, dpt_xyz, rgb, normals, n_points, mask=None, see
     if not 1 <= N <= _lib.GDM_SAMPLE_MAX_N:
         raise ValueError("n_points=%d not in [1, %d]" % (N, _lib.GDM_SAMPLE_MAX_N))
     dev = valid_depth.device
-    seed_ptr, seed_val = None, 0
-    if torch.is_tensor(seed):
-        if not seed.is_cuda or seed.dtype != torch.int32 or seed.numel() != 1:
-            raise ValueError("a tensor seed must be a one-element int32 device tensor")
-        seed_ptr = seed.data_ptr()
-    else:
-        seed_val = int(seed) & 0xffffffff
-    labels = mp = lp = None
+    seed_val, seed_ptr = _seed_args(seed)
+    labels = None
     if mask is not None:
         mask = _dev(mask, torch.uint8, "mask")
         if tuple(mask.shape) != (B, S, S):
             raise ValueError("mask must be [B=%d,S=%d,S=%d], got %s" % (B, S, S, tuple(mask.shape)))
         labels = torch.empty((B, N), dtype=torch.uint8, device=dev)
-        mp, lp = mask.data_ptr(), labels.data_ptr()
     L = _lib.lib()
     need = L.gdm_sample_assemble_workspace_bytes(B, S)
     if need == 0:
@@ -2406,9 +2290,8 @@ def sample_assemble(valid_depth, dpt_xyz, rgb, normals, n_points, mask=None, see
     choose = torch.empty((B, N), dtype=torch.int32, device=dev)
     cld_rgb_nrm = torch.empty((B, 9, N), dtype=torch.float32, device=dev)
     n_valid = torch.empty((B,), dtype=torch.int32, device=dev)
-    check(L.gdm_sample_assemble_hip(valid_depth.data_ptr(), dpt_xyz.data_ptr(), rgb.data_ptr(), normals.data_ptr(), mp, B, S, N,
-                                    seed_val, seed_ptr, choose.data_ptr(), cld_rgb_nrm.data_ptr(), lp, n_valid.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), _stream()), "gdm_sample_assemble_hip")
+    call("gdm_sample_assemble_hip", valid_depth, dpt_xyz, rgb, normals, mask, B, S, N, seed_val, seed_ptr, choose, cld_rgb_nrm, labels,
+         n_valid, ws, ws.numel())
     return choose, cld_rgb_nrm, labels, n_valid
 
 
@@ -2436,18 +2319,15 @@ def augment_crops(rgb, depth, mask=None, background=None, enable=None, seed=0):
         raise ValueError("rgb must be %s, got %s" % ([B, 3, S, S], tuple(rgb.shape)))
     if not _lib.GDM_AUG_MIN_S <= S <= _lib.GDM_AUG_MAX_S:
         raise ValueError("augment_crops: S=%d not in [%d, %d] (a blur reaches 15 pixels)" % (S, _lib.GDM_AUG_MIN_S, _lib.GDM_AUG_MAX_S))
-    mp = ep = None
     if mask is not None:
         mask = _dev(mask, torch.uint8, "mask")
         if tuple(mask.shape) != (B, S, S):
             raise ValueError("mask must be [B=%d,S=%d,S=%d], got %s" % (B, S, S, tuple(mask.shape)))
-        mp = mask.data_ptr()
     if enable is not None:
         enable = _dev(enable, torch.uint8, "enable")
         if tuple(enable.shape) != (B,):
             raise ValueError("enable must be [B=%d], got %s" % (B, tuple(enable.shape)))
-        ep = enable.data_ptr()
-    bp, Nb, Hb, Wb = (None, None, None), 0, 0, 0
+    bg_rgb, bg_depth, bg_mask, Nb, Hb, Wb = None, None, None, 0, 0, 0
     if background is not None:
         if mask is None:
             raise ValueError("augment_crops: the background paste needs the crop's mask")
@@ -2461,14 +2341,12 @@ def augment_crops(rgb, depth, mask=None, background=None, enable=None, seed=0):
             raise ValueError("bg_depth and bg_mask must be %s, got %s and %s" % ([Nb, Hb, Wb], tuple(bg_depth.shape), tuple(bg_mask.shape)))
         if Nb < 1 or Hb < S + 2 or Wb < S + 2:
             raise ValueError("the bank's frames must be at least S + 2 = %d a side, got %d x %d (Nb = %d)" % (S + 2, Hb, Wb, Nb))
-        bp = (bg_rgb.data_ptr(), bg_depth.data_ptr(), bg_mask.data_ptr())
     seed_val, seed_ptr = _seed_args(seed)
     L = _lib.lib()
     ws = _workspace(L.gdm_augment_workspace_bytes(B, S), rgb.device)
     out_rgb, out_depth = torch.empty_like(rgb), torch.empty_like(depth)
-    check(L.gdm_augment_crops_hip(rgb.data_ptr(), depth.data_ptr(), mp, bp[0], bp[1], bp[2], ep, B, S, Nb, Hb, Wb, seed_val, seed_ptr,
-                                  out_rgb.data_ptr(), out_depth.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-          "gdm_augment_crops_hip")
+    call("gdm_augment_crops_hip", rgb, depth, mask, bg_rgb, bg_depth, bg_mask, enable, B, S, Nb, Hb, Wb, seed_val, seed_ptr, out_rgb,
+         out_depth, ws, ws.numel())
     return out_rgb, out_depth
 
 
@@ -2512,9 +2390,7 @@ def mssd_mspd(RT_est, RT_gt, pts, sym_R, sym_t, K):
     err = torch.empty((2, n, S), dtype=torch.float64, device=dev)
     out = torch.empty((2, n), dtype=torch.float64, device=dev)
     best = torch.empty((2, n), dtype=torch.int32, device=dev)
-    check(_lib.lib().gdm_mssd_mspd_hip(RT_est.data_ptr(), RT_gt.data_ptr(), pts.data_ptr(), sym_R.data_ptr(), sym_t.data_ptr(),
-                                       K.data_ptr(), kpi, n, pts.shape[0], S, err.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
-                                       best[0].data_ptr(), best[1].data_ptr(), _stream()), "gdm_mssd_mspd_hip")
+    call("gdm_mssd_mspd_hip", RT_est, RT_gt, pts, sym_R, sym_t, K, kpi, n, pts.shape[0], S, err, out[0], out[1], best[0], best[1])
     return out[0], out[1], best[0], best[1]
 
 
@@ -2537,9 +2413,8 @@ def render_depth(verts, faces, RT, K, H, W, near, keep_inf=False):
     n, H, W = RT.shape[0], int(H), int(W)
     K, kpi = _k64(K, n, "K")
     depth = torch.empty((n, H, W), dtype=torch.float32, device=RT.device)
-    check(_lib.lib().gdm_render_depth_hip(verts.data_ptr(), int(verts.dtype == torch.float64), faces.data_ptr(), RT.data_ptr(),
-                                          K.data_ptr(), kpi, n, verts.shape[0], faces.shape[0], H, W, float(near), int(bool(keep_inf)),
-                                          depth.data_ptr(), _stream()), "gdm_render_depth_hip")
+    call("gdm_render_depth_hip", verts, int(verts.dtype == torch.float64), faces, RT, K, kpi, n, verts.shape[0], faces.shape[0], H, W,
+         float(near), int(bool(keep_inf)), depth)
     return depth
 
 
@@ -2569,10 +2444,8 @@ def vsd_counts(depth_est, depth_gt, depth_test, K, delta, taus, diameter=None, t
     dev = depth_est.device
     counts = torch.empty((n, 2 + T), dtype=torch.int32, device=dev)
     tl = torch.empty((n, T), dtype=torch.float64, device=dev) if tlinear else None
-    check(_lib.lib().gdm_vsd_counts_hip(depth_est.data_ptr(), depth_gt.data_ptr(), depth_test.data_ptr(), tpi, K.data_ptr(), kpi, n, H, W,
-                                        float(delta), (ctypes.c_double * T)(*taus), T, float(diameter) if diameter else 0.0,
-                                        int(bool(inf_is_empty)), counts.data_ptr(), tl.data_ptr() if tlinear else None, _stream()),
-          "gdm_vsd_counts_hip")
+    call("gdm_vsd_counts_hip", depth_est, depth_gt, depth_test, tpi, K, kpi, n, H, W, float(delta), (ctypes.c_double * T)(*taus), T,
+         float(diameter) if diameter else 0.0, int(bool(inf_is_empty)), counts, tl)
     if tlinear:
         return counts[:, 0], counts[:, 1], counts[:, 2:], tl
     return counts[:, 0], counts[:, 1], counts[:, 2:]

@@ -26,8 +26,8 @@ from typing import Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import check
+from . import ops
+from ._lib import call
 
 
 def furthestsampling(xyz: torch.Tensor, m: int) -> torch.Tensor:
@@ -56,8 +56,7 @@ class _Interpolation(torch.autograd.Function):
         n = idx.shape[1]
         assert idx.shape == (b, n, 3) and weight.shape == (b, n, 3)
         out = torch.empty((b, c, n), dtype=torch.float32, device=features.device)
-        check(_lib.lib().gdm_interpolation_forward_hip(b, c, m, n, features.data_ptr(), idx.data_ptr(), weight.data_ptr(), out.data_ptr(),
-                                                       ops._stream()), "gdm_interpolation_forward_hip")
+        call("gdm_interpolation_forward_hip", b, c, m, n, features, idx, weight, out)
         ctx.save_for_backward(idx, weight)
         ctx.m = m
         return out
@@ -68,8 +67,7 @@ class _Interpolation(torch.autograd.Function):
         grad_out = grad_out.contiguous().float()
         b, c, n = grad_out.shape
         g = torch.zeros((b, c, ctx.m), dtype=torch.float32, device=grad_out.device)
-        check(_lib.lib().gdm_interpolation_backward_hip(b, c, n, ctx.m, grad_out.data_ptr(), idx.data_ptr(), weight.data_ptr(), g.data_ptr(),
-                                                        ops._stream()), "gdm_interpolation_backward_hip")
+        call("gdm_interpolation_backward_hip", b, c, n, ctx.m, grad_out, idx, weight, g)
         return g, None, None
 
 
@@ -125,8 +123,7 @@ def labelstat_ballrange(radius: float, xyz: torch.Tensor, new_xyz: torch.Tensor,
     b, n, nclass = ls.shape
     m = new_xyz.shape[1]
     out = torch.empty((b, m, nclass), dtype=torch.int32, device=xyz.device)
-    check(_lib.lib().gdm_labelstat_ballrange_hip(b, n, m, float(radius), nclass, new_xyz.data_ptr(), xyz.data_ptr(), ls.data_ptr(),
-                                                 out.data_ptr(), ops._stream()), "gdm_labelstat_ballrange_hip")
+    call("gdm_labelstat_ballrange_hip", b, n, m, float(radius), nclass, new_xyz, xyz, ls, out)
     return out
 
 
@@ -138,8 +135,7 @@ def labelstat_idx(nsample: int, label_stat: torch.Tensor, idx: torch.Tensor) -> 
     m = idx.shape[1]
     assert idx.shape[2] == nsample
     out = torch.empty((b, m, nclass), dtype=torch.int32, device=ls.device)
-    check(_lib.lib().gdm_labelstat_idx_hip(b, n, m, nsample, nclass, ls.data_ptr(), idx.data_ptr(), out.data_ptr(), ops._stream()),
-          "gdm_labelstat_idx_hip")
+    call("gdm_labelstat_idx_hip", b, n, m, nsample, nclass, ls, idx, out)
     return out
 
 

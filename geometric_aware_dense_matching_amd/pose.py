@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import check
+from ._lib import call
 
 
 def kabsch_stats(res, cld_rgb_nrm, model_xyz):
@@ -25,9 +25,7 @@ def kabsch_stats(res, cld_rgb_nrm, model_xyz):
     cld = ops._dev(cld_rgb_nrm, torch.float32, "cld_rgb_nrm")
     model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
     out = torch.empty((B, 16), dtype=torch.float64, device=mask.device)
-    check(_lib.lib().gdm_kabsch_stats_hip(cld.data_ptr(), cld.stride(0), 1, N, model_xyz.data_ptr(), best_idx.data_ptr(),
-                                          mask.data_ptr(), B, N, model_xyz.shape[0], out.data_ptr(), ops._stream()),
-          "gdm_kabsch_stats_hip")
+    call("gdm_kabsch_stats_hip", cld, cld.stride(0), 1, N, model_xyz, best_idx, mask, B, N, model_xyz.shape[0], out)
     return out
 
 
@@ -59,8 +57,7 @@ def solve_poses(res, cld_rgb_nrm, model_xyz, min_points=5, method="kabsch", rans
     B = st.shape[0]
     RT = torch.empty((B, 3, 4), dtype=torch.float32, device=st.device)
     valid = torch.empty((B,), dtype=torch.uint8, device=st.device)
-    check(_lib.lib().gdm_kabsch_solve_hip(st.data_ptr(), B, int(min_points), RT.data_ptr(), valid.data_ptr(), ops._stream()),
-          "gdm_kabsch_solve_hip")
+    call("gdm_kabsch_solve_hip", st, B, int(min_points), RT, valid)
     return RT, valid.bool()
 
 
@@ -81,10 +78,8 @@ def kabsch_stats_weighted(res, cld_rgb_nrm, model_xyz, weight, target=None):
             raise ValueError("kabsch_stats_weighted: target is %s, expected %s" % (tuple(target.shape), (B, N, 3)))
     out = torch.empty((B, 16), dtype=torch.float64, device=mask.device)
     count = torch.empty((B,), dtype=torch.int32, device=mask.device)
-    check(_lib.lib().gdm_kabsch_stats_w_hip(cld.data_ptr(), cld.stride(0), 1, N, model_xyz.data_ptr(), best_idx.data_ptr(),
-                                            None if target is None else target.data_ptr(), weight.data_ptr(), mask.data_ptr(), B, N,
-                                            model_xyz.shape[0], out.data_ptr(), count.data_ptr(), ops._stream()),
-          "gdm_kabsch_stats_w_hip")
+    call("gdm_kabsch_stats_w_hip", cld, cld.stride(0), 1, N, model_xyz, best_idx, target, weight, mask, B, N, model_xyz.shape[0], out,
+         count)
     return out, count
 
 
@@ -95,8 +90,7 @@ def solve_poses_weighted(res, cld_rgb_nrm, model_xyz, weight, target=None, min_p
     B = st.shape[0]
     RT = torch.empty((B, 3, 4), dtype=torch.float32, device=st.device)
     valid = torch.empty((B,), dtype=torch.uint8, device=st.device)
-    check(_lib.lib().gdm_kabsch_solve_w_hip(st.data_ptr(), count.data_ptr(), B, int(min_points), RT.data_ptr(), valid.data_ptr(),
-                                            ops._stream()), "gdm_kabsch_solve_w_hip")
+    call("gdm_kabsch_solve_w_hip", st, count, B, int(min_points), RT, valid)
     return RT, valid.bool()
 
 
@@ -167,11 +161,38 @@ def ransac_poses(res, cld_rgb_nrm, model_xyz, iters=20, inlier_dist=0.015, fix_p
     valid = torch.empty((B,), dtype=torch.uint8, device=mask.device)
     counts = torch.empty((B, H), dtype=torch.int32, device=mask.device)
     winner = torch.empty((B,), dtype=torch.int32, device=mask.device)
-    check(L.gdm_ransac_pose_hip(cld.data_ptr(), sb, ps, cs, model_xyz.data_ptr(), best_idx.data_ptr(), mask.data_ptr(), st.data_ptr(),
-                                B, N, model_xyz.shape[0], H, float(inlier_dist), float(fix_percent), int(seed) & 0xffffffff,
-                                int(min_points), ws.data_ptr(), nbytes, RT.data_ptr(), valid.data_ptr(), counts.data_ptr(),
-                                winner.data_ptr(), ops._stream()), "gdm_ransac_pose_hip")
+    call("gdm_ransac_pose_hip", cld, sb, ps, cs, model_xyz, best_idx, mask, st, B, N, model_xyz.shape[0], H, float(inlier_dist),
+         float(fix_percent), int(seed) & 0xffffffff, int(min_points), ws, nbytes, RT, valid, counts, winner)
     return RT, valid.bool(), counts, winner
+
+
+def _icp_setup(RT, valid, cld_rgb_nrm, mask, model_xyz):
+    """What the two ICP forms share: the checked inputs (RT and the active flags as new tensors), the K = 1 result buffers nn i32[B,N,1]
+    and d2 f32[B,N,1], and search(), which enqueues one iteration's transform of the scene points into the model frame and their exact
+    nearest-vertex search, and returns the transformed points f32[B,N,3].
+    -> (cld, batch stride, point stride, channel stride), model_xyz, mask, RT, active, nn, d2, search."""
+    B, N = mask.shape
+    dev = mask.device
+    scene = _scene_args(cld_rgb_nrm)
+    model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
+    mask = mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)
+    mask = ops._dev(mask, torch.uint8, "mask")
+    RT = ops._dev(RT, torch.float32, "RT").clone()
+    active = valid.to(torch.uint8).contiguous().clone()
+    query = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    nn = torch.empty((B, N, 1), dtype=torch.int32, device=dev)
+    d2 = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
+    job = (_lib.KnnJob * 1)()
+    job[0].support, job[0].query, job[0].idx, job[0].d2 = model_xyz.data_ptr(), query.data_ptr(), nn.data_ptr(), d2.data_ptr()
+    job[0].support_bstride, job[0].query_bstride = 0, N * 3
+    job[0].S, job[0].Q, job[0].K, job[0].grid_w = model_xyz.shape[0], N, 1, 0
+
+    def search():
+        call("gdm_icp_transform_hip", *scene, RT, B, N, query)
+        call("gdm_knn_jobs_ws_hip", job, 1, B, None, 0)
+        return query
+
+    return scene, model_xyz, mask, RT, active, nn, d2, search
 
 
 def refine_icp(RT, valid, cld_rgb_nrm, mask, model_xyz, iters=20, tolerance=0.001, reject_dist=None, min_points=5):
@@ -182,35 +203,15 @@ def refine_icp(RT, valid, cld_rgb_nrm, mask, model_xyz, iters=20, tolerance=0.00
     device by the reference's rule (|prev_error - mean| < tolerance, prev_error starting at 0), or when it is invalid or has fewer
     than min_points pairs.  -> RT f32[B,3,4] (a new tensor), iterations run i32[B], final mean residual f32[B] (the mean pair
     distance of the last iteration run; 0 for a crop that ran none)."""
+    scene, model_xyz, mask, RT, active, nn, d2, search = _icp_setup(RT, valid, cld_rgb_nrm, mask, model_xyz)
     B, N = mask.shape
-    dev = mask.device
-    cld, sb, ps, cs = _scene_args(cld_rgb_nrm)
-    model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
-    M = model_xyz.shape[0]
-    mask = mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)
-    mask = ops._dev(mask, torch.uint8, "mask")
-    RT = ops._dev(RT, torch.float32, "RT").clone()
-    active = valid.to(torch.uint8).contiguous().clone()
-    n_iter = torch.zeros((B,), dtype=torch.int32, device=dev)
-    err = torch.zeros((B,), dtype=torch.float64, device=dev)
-    if int(iters) <= 0:
-        return RT, n_iter, err.float()
-    query = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-    nn = torch.empty((B, N, 1), dtype=torch.int32, device=dev)
-    d2 = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
-    job = (_lib.KnnJob * 1)()
-    job[0].support, job[0].query, job[0].idx, job[0].d2 = model_xyz.data_ptr(), query.data_ptr(), nn.data_ptr(), d2.data_ptr()
-    job[0].support_bstride, job[0].query_bstride = 0, N * 3
-    job[0].S, job[0].Q, job[0].K, job[0].grid_w = M, N, 1, 0
-    L = _lib.lib()
+    n_iter = torch.zeros((B,), dtype=torch.int32, device=mask.device)
+    err = torch.zeros((B,), dtype=torch.float64, device=mask.device)
     reject = -1.0 if reject_dist is None else float(reject_dist)
     for _ in range(int(iters)):
-        check(L.gdm_icp_transform_hip(cld.data_ptr(), sb, ps, cs, RT.data_ptr(), B, N, query.data_ptr(), ops._stream()),
-              "gdm_icp_transform_hip")
-        check(L.gdm_knn_jobs_ws_hip(job, 1, B, None, 0, ops._stream()), "gdm_knn_jobs_ws_hip")
-        check(L.gdm_icp_update_hip(cld.data_ptr(), sb, ps, cs, model_xyz.data_ptr(), nn.data_ptr(), d2.data_ptr(), mask.data_ptr(), B, N,
-                                   M, reject, float(tolerance), int(min_points), RT.data_ptr(), active.data_ptr(), n_iter.data_ptr(),
-                                   err.data_ptr(), ops._stream()), "gdm_icp_update_hip")
+        search()
+        call("gdm_icp_update_hip", *scene, model_xyz, nn, d2, mask, B, N, model_xyz.shape[0], reject, float(tolerance), int(min_points), RT,
+             active, n_iter, err)
     return RT, n_iter, err.float()
 
 
@@ -227,45 +228,26 @@ def refine_icp_plane(RT, valid, cld_rgb_nrm, mask, model_xyz, model_nrm, iters=1
     it converges (|prev_mean - mean| < tolerance, status 1), has fewer than max(min_points, 6) pairs (2) or is degenerate (3: a
     plane, a sphere, a body of revolution; the unit-free pivot test of DESIGN.md 6b) -- in the last two cases with its pose unchanged.
     -> RT f32[B,3,4] (a new tensor), iterations run i32[B], final mean |n . (x - q)| f32[B], status i32[B]."""
+    scene, model_xyz, mask, RT, active, nn, d2, search = _icp_setup(RT, valid, cld_rgb_nrm, mask, model_xyz)
+    cld, _, _, cs = scene
     B, N = mask.shape
-    dev = mask.device
-    cld, sb, ps, cs = _scene_args(cld_rgb_nrm)
-    model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
-    model_nrm = ops._dev(model_nrm, torch.float32, "model_nrm")
     M = model_xyz.shape[0]
+    model_nrm = ops._dev(model_nrm, torch.float32, "model_nrm")
     if tuple(model_nrm.shape) != (M, 3):
         raise ValueError("refine_icp_plane: model_nrm is %s, expected %s" % (tuple(model_nrm.shape), (M, 3)))
     if normal_gate is not None and cld.shape[1] < 9:
         raise ValueError("refine_icp_plane: normal_gate needs the scene normals in rows 6..8 of cld_rgb_nrm")
-    mask = mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)
-    mask = ops._dev(mask, torch.uint8, "mask")
-    RT = ops._dev(RT, torch.float32, "RT").clone()
-    active = valid.to(torch.uint8).contiguous().clone()
-    n_iter = torch.zeros((B,), dtype=torch.int32, device=dev)
-    status = torch.zeros((B,), dtype=torch.int32, device=dev)
-    err = torch.zeros((B,), dtype=torch.float64, device=dev)
-    if int(iters) <= 0:
-        return RT, n_iter, err.float(), status
-    query = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-    nn = torch.empty((B, N, 1), dtype=torch.int32, device=dev)
-    d2 = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
-    job = (_lib.KnnJob * 1)()
-    job[0].support, job[0].query, job[0].idx, job[0].d2 = model_xyz.data_ptr(), query.data_ptr(), nn.data_ptr(), d2.data_ptr()
-    job[0].support_bstride, job[0].query_bstride = 0, N * 3
-    job[0].S, job[0].Q, job[0].K, job[0].grid_w = M, N, 1, 0
-    L = _lib.lib()
+    n_iter = torch.zeros((B,), dtype=torch.int32, device=mask.device)
+    status = torch.zeros((B,), dtype=torch.int32, device=mask.device)
+    err = torch.zeros((B,), dtype=torch.float64, device=mask.device)
     reject = -1.0 if reject_dist is None else float(reject_dist)
     snrm = None if normal_gate is None else cld.data_ptr() + 6 * cs * cld.element_size()
     gate = 0.0 if normal_gate is None else float(normal_gate)
     delta = 0.0 if huber is None else float(huber)
     for _ in range(int(iters)):
-        check(L.gdm_icp_transform_hip(cld.data_ptr(), sb, ps, cs, RT.data_ptr(), B, N, query.data_ptr(), ops._stream()),
-              "gdm_icp_transform_hip")
-        check(L.gdm_knn_jobs_ws_hip(job, 1, B, None, 0, ops._stream()), "gdm_knn_jobs_ws_hip")
-        check(L.gdm_icp_plane_update_hip(snrm, sb, ps, cs, query.data_ptr(), model_xyz.data_ptr(), model_nrm.data_ptr(), nn.data_ptr(),
-                                         d2.data_ptr(), mask.data_ptr(), B, N, M, reject, gate, delta, float(tolerance), int(min_points),
-                                         float(pivot_min), RT.data_ptr(), active.data_ptr(), n_iter.data_ptr(), err.data_ptr(),
-                                         status.data_ptr(), None, ops._stream()), "gdm_icp_plane_update_hip")
+        query = search()
+        call("gdm_icp_plane_update_hip", snrm, *scene[1:], query, model_xyz, model_nrm, nn, d2, mask, B, N, M, reject, gate, delta,
+             float(tolerance), int(min_points), float(pivot_min), RT, active, n_iter, err, status, None)
     return RT, n_iter, err.float(), status
 
 

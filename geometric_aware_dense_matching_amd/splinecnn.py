@@ -26,8 +26,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _lib, ops, settings
-from ._lib import check
+from . import ops, settings
+from ._lib import call
 from .derived import derived
 from .layers import cached_gemm_weight
 from .synthetic import COLOR_MEAN, COLOR_STD_MESH
@@ -40,9 +40,7 @@ class _SplineAggregate(torch.autograd.Function):
     def forward(ctx, xw, root, bias, rowptr, src, attr, relu):
         M, nk, C = xw.shape
         out = torch.empty((M, C), dtype=torch.float32, device=xw.device)
-        check(_lib.lib().gdm_spline_aggregate_hip(xw.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
-                                                  root.data_ptr(), bias.data_ptr(), M, C, KERNEL_SIZE, int(relu),
-                                                  out.data_ptr(), ops._stream()), "gdm_spline_aggregate_hip")
+        call("gdm_spline_aggregate_hip", xw, rowptr, src, attr, root, bias, M, C, KERNEL_SIZE, int(relu), out)
         ctx.save_for_backward(rowptr, src, attr, out)
         ctx.relu = relu
         ctx.nk = nk
@@ -56,9 +54,7 @@ class _SplineAggregate(torch.autograd.Function):
             go = go * (out > 0).to(go.dtype)
         M, C = go.shape
         gxw = torch.zeros((M, ctx.nk, C), dtype=torch.float32, device=go.device)
-        check(_lib.lib().gdm_spline_aggregate_bwd_hip(go.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
-                                                      M, C, KERNEL_SIZE, gxw.data_ptr(), ops._stream()),
-              "gdm_spline_aggregate_bwd_hip")
+        call("gdm_spline_aggregate_bwd_hip", go, rowptr, src, attr, M, C, KERNEL_SIZE, gxw)
         return gxw, go, go.sum(dim=0), None, None, None, None
 
 
@@ -68,10 +64,8 @@ def _pairs_grad(go, out, pairs, relu, want_packed):
     R = pairs["rowidx"].shape[0]
     gy = torch.empty((R, C), dtype=torch.float32, device=go.device)
     pk = ops.spline_packed_buffer(C, R, go.device) if want_packed else None
-    check(_lib.lib().gdm_spline_pairs_grad_hip(go.data_ptr(), out.data_ptr() if relu else None, pairs["pair_ptr"].data_ptr(),
-                                               pairs["pair_ec"].data_ptr(), pairs["basis"].data_ptr(), pairs["tgt"].data_ptr(),
-                                               pairs["inv_deg"].data_ptr(), R, C, gy.data_ptr(), pk.data_ptr() if pk is not None else None,
-                                               ops._stream()), "gdm_spline_pairs_grad_hip")
+    call("gdm_spline_pairs_grad_hip", go, out if relu else None, pairs["pair_ptr"], pairs["pair_ec"], pairs["basis"],
+         pairs["tgt"], pairs["inv_deg"], R, C, gy, pk)
     return gy, pk
 
 
@@ -82,9 +76,8 @@ def _spline_wgrad(x, gy, pairs, cin, cout):
     R = pairs["rowidx"].shape[0]
     dw = torch.empty((nk, cin, cout), dtype=torch.float32, device=x.device)
     part = torch.empty((R // 256, cin, cout), dtype=torch.float32, device=x.device)          # per-tile partial products
-    check(_lib.lib().gdm_spline_wgrad_hip(x.data_ptr(), pairs["rowidx"].data_ptr(), gy.data_ptr(), pairs["tile_co0"].data_ptr(),
-                                          pairs["blk_start"].data_ptr(), pairs["blk_rows"].data_ptr(), nk, R, cin, cout, part.data_ptr(),
-                                          dw.data_ptr(), ops._stream()), "gdm_spline_wgrad_hip")
+    call("gdm_spline_wgrad_hip", x, pairs["rowidx"], gy, pairs["tile_co0"], pairs["blk_start"], pairs["blk_rows"], nk, R, cin, cout, part,
+         dw)
     return dw
 
 
@@ -116,9 +109,8 @@ class _SplineDirectTrain(torch.autograd.Function):
         M = x.shape[0]
         out = torch.empty((M, conv.cout), dtype=torch.float32, device=x.device)
         root_t = _train_root_t(conv, lin_weight)
-        check(_lib.lib().gdm_spline_direct3_hip(x.data_ptr(), weight.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
-                                                root_t.data_ptr(), bias.data_ptr(), M, conv.cin, conv.cout, KERNEL_SIZE, int(relu),
-                                                out.data_ptr(), None, None, ops._stream()), "gdm_spline_direct3_hip")
+        call("gdm_spline_direct3_hip", x, weight, rowptr, src, attr, root_t, bias, M, conv.cin, conv.cout, KERNEL_SIZE, int(relu), out,
+             None, None)
         ctx.save_for_backward(x, out)
         ctx.pairs, ctx.relu, ctx.dims = pairs, relu, (conv.cin, conv.cout)
         return out
@@ -153,9 +145,8 @@ class _SplineGroupedTrain(torch.autograd.Function):
         else:
             root = x @ lin_weight.t()
         out = torch.empty((M, conv.cout), dtype=torch.float32, device=x.device)
-        check(_lib.lib().gdm_spline_pairs_aggregate3_hip(Y.data_ptr(), rowptr.data_ptr(), pairs["pos"].data_ptr(), pairs["basis"].data_ptr(),
-                                                         root.data_ptr(), bias.data_ptr(), M, conv.cout, int(relu), out.data_ptr(),
-                                                         None, None, ops._stream()), "gdm_spline_pairs_aggregate3_hip")
+        call("gdm_spline_pairs_aggregate3_hip", Y, rowptr, pairs["pos"], pairs["basis"], root, bias, M, conv.cout, int(relu), out, None,
+             None)
         ctx.save_for_backward(x, out, weight, lin_weight)
         ctx.conv, ctx.pairs, ctx.relu = conv, pairs, relu
         return out
@@ -176,13 +167,10 @@ class _SplineGroupedTrain(torch.autograd.Function):
             # Z[r, :] = gY[r, :] . W[k(r)]^T: rows of weight.reshape(125*cin, cout) are (k, ci); cin == cout, so tile_co0 = k*cin as it stands
             wpk = _train_gemm_weight(conv, "dgrad", weight, lambda w: w.reshape(nk * conv.cin, conv.cout))
             Z = torch.empty((R, conv.cin), dtype=torch.float32, device=x.device)
-            L = _lib.lib()
-            check(L.gdm_gemm_grouped_hip(pk.data_ptr(), wpk.data_ptr(), pairs["rowid"].data_ptr(), pairs["tile_co0"].data_ptr(), R, R, conv.cout,
-                                         nk * conv.cin, Z.data_ptr(), ops._stream()), "gdm_gemm_grouped_hip")
+            call("gdm_gemm_grouped_hip", pk, wpk, pairs["rowid"], pairs["tile_co0"], R, R, conv.cout, nk * conv.cin, Z)
             add = g @ lin_weight
             dx = torch.empty((M, conv.cin), dtype=torch.float32, device=x.device)
-            check(L.gdm_spline_segment_sum_hip(Z.data_ptr(), pairs["src_ptr"].data_ptr(), pairs["src_rows"].data_ptr(), add.data_ptr(), M,
-                                               conv.cin, dx.data_ptr(), ops._stream()), "gdm_spline_segment_sum_hip")
+            call("gdm_spline_segment_sum_hip", Z, pairs["src_ptr"], pairs["src_rows"], add, M, conv.cin, dx)
         dw = _spline_wgrad(x, gy, pairs, conv.cin, conv.cout)
         return dx, dw, g.t() @ x, g.sum(dim=0), None, None, None, None
 
@@ -222,10 +210,8 @@ class SplineConv(nn.Module):
         out_t = torch.empty((1, self.cout, M), dtype=torch.float32, device=x.device)
         pk = ops.spline_packed_buffer(self.cout, M, x.device) if want_packed and self.cout % 128 == 0 and self.cout <= 512 else None
         xc = x.contiguous()
-        check(_lib.lib().gdm_spline_direct3_hip(xc.data_ptr(), self.weight.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
-                                                self._root_t().data_ptr(), self.bias.data_ptr(), M, self.cin, self.cout, KERNEL_SIZE, int(relu),
-                                                None, out_t.data_ptr(), pk.data_ptr() if pk is not None else None, ops._stream()),
-              "gdm_spline_direct3_hip")
+        call("gdm_spline_direct3_hip", xc, self.weight, rowptr, src, attr, self._root_t(), self.bias, M, self.cin, self.cout, KERNEL_SIZE,
+             int(relu), None, out_t, pk)
         return out_t, pk
 
     def forward_grouped_cm(self, xt, rowptr, pairs, relu, xpk=None, want_packed=False):
@@ -238,10 +224,8 @@ class SplineConv(nn.Module):
         root = ops.pointwise([xt], self._root_t(), point_major=True)                       # [1, M, cout] = x @ W_root^T
         out_t = torch.empty((1, self.cout, M), dtype=torch.float32, device=xt.device)
         pk = ops.spline_packed_buffer(self.cout, M, xt.device, avoid=xpk) if want_packed and self.cout % 128 == 0 and self.cout <= 512 else None
-        check(_lib.lib().gdm_spline_pairs_aggregate3_hip(Y.data_ptr(), rowptr.data_ptr(), pairs["pos"].data_ptr(), pairs["basis"].data_ptr(),
-                                                         root.data_ptr(), self.bias.data_ptr(), M, self.cout, int(relu), None,
-                                                         out_t.data_ptr(), pk.data_ptr() if pk is not None else None, ops._stream()),
-              "gdm_spline_pairs_aggregate3_hip")
+        call("gdm_spline_pairs_aggregate3_hip", Y, rowptr, pairs["pos"], pairs["basis"], root, self.bias, M, self.cout, int(relu), None,
+             out_t, pk)
         return out_t, pk
 
     def train_grouped_ok(self, x, pairs):
@@ -268,9 +252,8 @@ class SplineConv(nn.Module):
             # few input channels (first layer, 9 -> 128): messages formed directly, no [M, 125*out] table (524 MB at M = 8192)
             out = torch.empty((M, self.cout), dtype=torch.float32, device=x.device)
             xc = x.contiguous()
-            check(_lib.lib().gdm_spline_direct3_hip(xc.data_ptr(), self.weight.data_ptr(), rowptr.data_ptr(), src.data_ptr(), attr.data_ptr(),
-                                                    self._root_t().data_ptr(), self.bias.data_ptr(), M, self.cin, self.cout, KERNEL_SIZE, int(relu),
-                                                    out.data_ptr(), None, None, ops._stream()), "gdm_spline_direct3_hip")
+            call("gdm_spline_direct3_hip", xc, self.weight, rowptr, src, attr, self._root_t(), self.bias, M, self.cin, self.cout,
+                 KERNEL_SIZE, int(relu), out, None, None)
             return out
         if (settings.USE_MFMA_GEMM and settings.USE_GROUPED_SPLINE and pairs is not None and not torch.is_grad_enabled() and x.is_cuda
                 and self.cin % 128 == 0 and self.cout == 128):
@@ -285,9 +268,8 @@ class SplineConv(nn.Module):
             else:
                 root = self.lin(x)
             out = torch.empty((M, self.cout), dtype=torch.float32, device=x.device)
-            check(_lib.lib().gdm_spline_pairs_aggregate3_hip(Y.data_ptr(), rowptr.data_ptr(), pairs["pos"].data_ptr(), pairs["basis"].data_ptr(),
-                                                             root.data_ptr(), self.bias.data_ptr(), M, self.cout, int(relu), out.data_ptr(),
-                                                             None, None, ops._stream()), "gdm_spline_pairs_aggregate3_hip")
+            call("gdm_spline_pairs_aggregate3_hip", Y, rowptr, pairs["pos"], pairs["basis"], root, self.bias, M, self.cout, int(relu), out,
+                 None, None)
             return out
         if (settings.USE_MFMA_GEMM and not torch.is_grad_enabled() and x.is_cuda
                 and ops.gemm_supported(self.cin, nk * self.cout, M)):

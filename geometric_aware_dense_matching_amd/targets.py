@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import check
+from ._lib import call
 
 HPR_PARAM = float(np.power(10.0, np.pi))            # compute_visibility.py:131 sphericalFlip(pts, c, math.pi)
 
@@ -74,9 +74,7 @@ def _hpr(model, mb, M, RT, cam_center, ws, nbytes):
         cam = ops._dev(cam_center, torch.float32, "cam_center").reshape(B, 3).contiguous()
     flipped = torch.empty((B, M, 3), dtype=torch.float64, device=RT.device)
     visible = torch.empty((B, M), dtype=torch.uint8, device=RT.device)
-    check(_lib.lib().gdm_hpr_visible_hip(model.data_ptr(), mb, RT.data_ptr(), None if cam is None else cam.data_ptr(), B, M,
-                                         ws.data_ptr(), nbytes, flipped.data_ptr(), visible.data_ptr(), ops._stream()),
-          "gdm_hpr_visible_hip")
+    call("gdm_hpr_visible_hip", model, mb, RT, cam, B, M, ws, nbytes, flipped, visible)
     return visible, flipped
 
 
@@ -124,10 +122,8 @@ def pose_gt_info(cld, labels, RT, model_xyz, dist_thresh=0.01, cam_center=None):
     match_idx = torch.empty((B, N), dtype=torch.int32, device=RT.device)
     visible_flag = torch.empty((B, M), dtype=torch.uint8, device=RT.device)
     valid = torch.empty((B,), dtype=torch.uint8, device=RT.device)
-    check(_lib.lib().gdm_pose_targets_hip(c.data_ptr(), cb, ps, cs, lab.data_ptr(), RT.data_ptr(), model.data_ptr(), mb,
-                                          visible.data_ptr(), B, N, M, float(dist_thresh), ws.data_ptr(), nbytes, labels_out.data_ptr(),
-                                          match_idx.data_ptr(), visible_flag.data_ptr(), valid.data_ptr(), ops._stream()),
-          "gdm_pose_targets_hip")
+    call("gdm_pose_targets_hip", c, cb, ps, cs, lab, RT, model, mb, visible, B, N, M, float(dist_thresh), ws, nbytes, labels_out,
+         match_idx, visible_flag, valid)
     # the kernels mark the labelled points that lost their label (filtered_pt_labels[...] = 0, :651); every other value is the input's
     lost = (lab != 0) & (labels_out == 0)
     labels_out = torch.where(lost, torch.zeros_like(labels), labels)

@@ -1,5 +1,6 @@
 """CPU: the C-ABI shared library builds for gfx950, loads, and exports every symbol include/gdm.h
-declares (no compute calls without a GPU); host-side argument checking fails loudly."""
+declares (no compute calls without a GPU); host-side argument checking fails loudly; the ctypes binding
+derived from the header has the types the C++ compiler sees in it."""
 import ctypes
 import os
 import re
@@ -115,3 +116,111 @@ def test_library_loads_behind_torch_hip_runtime():
     out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-500:]
     assert out.stdout.split()[-2:] == ["False", "True"]
+
+
+# ------------------------------------------------------------------------------------------
+# the binding is derived from include/gdm.h: the compiler, not a hand-typed table, says what the header's types are
+# ------------------------------------------------------------------------------------------
+_STRUCT_NAMES = {"gdm_knn_job": "KnnJob", "gdm_pw_seg": "PwSeg", "gdm_pw_job": "PwJob", "gdm_copy_job": "CopyJob"}
+
+_CXX_PRELUDE = """
+#include "gdm.h"
+#include <cstddef>
+#include <tuple>
+#include <type_traits>
+template <class F> struct sig;
+template <class R, class... A> struct sig<R (*)(A...)> {
+    using ret = R;
+    static constexpr int arity = sizeof...(A);
+    template <int i> using arg = std::tuple_element_t<i, std::tuple<A...>>;
+};
+template <class T> constexpr bool is_void = std::is_void_v<T>;
+template <class T> constexpr bool is_ptr = std::is_pointer_v<T>;
+template <class T, int size, bool sgn> constexpr bool is_int = std::is_integral_v<T> && sizeof(T) == size && std::is_signed_v<T> == sgn;
+template <class T, int size> constexpr bool is_flt = std::is_floating_point_v<T> && sizeof(T) == size;
+"""
+
+
+def _cxx_category(c):
+    """The C++ predicate (a template of the prelude, still missing its type argument) that a ctypes class stands for."""
+    if c is None:
+        return "is_void<%s>"
+    if c in (ctypes.c_void_p, ctypes.c_char_p) or _is_ptr(c):
+        return "is_ptr<%s>"
+    if c in (ctypes.c_float, ctypes.c_double):
+        return "is_flt<%%s, %d>" % ctypes.sizeof(c)
+    assert isinstance(c(0).value, int), c
+    return "is_int<%%s, %d, %s>" % (ctypes.sizeof(c), "true" if c(-1).value < 0 else "false")
+
+
+def test_compiler_agrees_with_the_parsed_header(tmp_path):
+    """Every return type, parameter type and arity of SIGNATURES, and the size and every field offset / type of the four job
+    structures, as static_asserts against decltype(&gdm_x) and offsetof in a C++ file that includes gdm.h: pointer, integer of a
+    size and signedness, floating type of a size.  A row that says int where the header says long does not compile."""
+    import subprocess
+    from geometric_aware_dense_matching_amd import _lib
+    lines = [_CXX_PRELUDE]
+    for name, (res, args) in _lib.SIGNATURES.items():
+        s = "sig<decltype(&%s)>" % name
+        lines.append('static_assert(%s::arity == %d, "%s: arity");' % (s, len(args), name))
+        lines.append('static_assert(%s, "%s: return type");' % (_cxx_category(res) % (s + "::ret"), name))
+        for i, a in enumerate(args):
+            lines.append('static_assert(%s, "%s: parameter %d (%s)");' % (_cxx_category(a) % ("%s::arg<%d>" % (s, i)), name, i,
+                                                                          _lib.PARAMS[name][i]))
+    for cname, pyname in _STRUCT_NAMES.items():
+        cls = getattr(_lib, pyname)
+        lines.append('static_assert(sizeof(%s) == %d, "%s: size");' % (cname, ctypes.sizeof(cls), cname))
+        for field, ftype in cls._fields_:
+            lines.append('static_assert(offsetof(%s, %s) == %d, "%s.%s: offset");' % (cname, field, getattr(cls, field).offset, cname, field))
+            lines.append('static_assert(%s, "%s.%s: type");' % (_cxx_category(ftype) % ("decltype(%s::%s)" % (cname, field)), cname, field))
+    assert len(_lib.SIGNATURES) >= 149 and len(lines) > 1500
+    src = tmp_path / "gdm_types.cpp"
+    src.write_text("\n".join(lines) + "\n")
+    out = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
+                         capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-3000:]
+
+
+def test_header_constants_and_their_aliases():
+    from geometric_aware_dense_matching_amd import _lib, frontend, ops
+    defines = re.findall(r"^#define\s+(GDM_\w+)\s+\(?(-?[0-9.]+)f?\)?\s*(?:/\*.*)?$", open(os.path.join(ROOT, "include", "gdm.h")).read(),
+                         flags=re.M)
+    assert len(defines) == 20
+    for name, text in defines:
+        val = getattr(_lib, name)
+        assert type(val) is (float if "." in text else int) and val == float(text), name
+    for mod, alias, name in ((ops, "MATCH_BF16X3", "GDM_MATCH_BF16X3"), (ops, "MATCH_F32", "GDM_MATCH_F32"),
+                             (ops, "MATCH_SOFT_MAX_GAMMA", "GDM_MATCH_SOFT_MAX_GAMMA"), (ops, "MATCH_SOFT_MAX_M", "GDM_MATCH_SOFT_MAX_M"),
+                             (ops, "SOFT_COORD_MAX_GAMMA", "GDM_SOFT_COORD_MAX_GAMMA"), (frontend, "NORMALS_MAX_K", "GDM_NORMALS_MAX_K"),
+                             (frontend, "FILL_STAGES", "GDM_FILL_STAGES")):
+        assert getattr(mod, alias) is getattr(_lib, name), alias
+    assert frontend.FILL_MODES == {"multiscale": _lib.GDM_FILL_MULTISCALE, "fast": _lib.GDM_FILL_FAST}
+
+
+def test_parser_refuses_an_unknown_type():
+    from geometric_aware_dense_matching_amd import _lib
+    with pytest.raises(RuntimeError, match="short.*gdm_made_up_hip"):
+        _lib._parse("int gdm_made_up_hip(const float* x, short n, void* stream);")
+    with pytest.raises(RuntimeError, match="gdm_made_up_hip"):
+        _lib._parse("int gdm_made_up_hip(const short* x, int n, void* stream);")
+    consts, sigs, names = _lib._parse("#define GDM_MADE_UP 3\nlong gdm_made_up(const float* x, size_t n);")
+    assert consts == {"GDM_MADE_UP": 3} and names == {"gdm_made_up": ("x", "n")}
+    assert sigs == {"gdm_made_up": (ctypes.c_long, [ctypes.c_void_p, ctypes.c_size_t])}
+
+
+def test_call_needs_no_gpu_for_host_side_refusals(lib, monkeypatch):
+    """_lib.call: tensors go as pointers, the stream is appended where the header's last parameter is the stream, a status raises
+    GdmError in check()'s format, a value comes back as it is.  The library refuses these arguments before any HIP call."""
+    from geometric_aware_dense_matching_amd import _lib
+    monkeypatch.setattr(_lib, "_stream", lambda: None)
+    conf, mask, score = torch.zeros(2, 8), torch.zeros(2, 8, dtype=torch.uint8), torch.nn.Parameter(torch.zeros(2))
+    with pytest.raises(_lib.GdmError, match=r"^gdm_match_score_hip failed \(rc=-1\): .*bad shape"):
+        _lib.call("gdm_match_score_hip", conf, mask, 0, 0, score)
+    with pytest.raises(_lib.GdmError, match=r"gdm_match_score_hip.*NULL"):
+        _lib.call("gdm_match_score_hip", None, None, 0, 0, None)
+    n = _lib.call("gdm_match_rows_bytes", 3)
+    assert type(n) is int and n == lib.gdm_match_rows_bytes(3) > 0
+    with pytest.raises(TypeError):
+        _lib.call("gdm_match_score_hip", conf, mask, 0, 0)
+    with pytest.raises(TypeError):
+        _lib.call("gdm_match_rows_bytes", 3, 4)

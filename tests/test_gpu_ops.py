@@ -1211,3 +1211,21 @@ def test_point_heads_in_two_launches_equals_one(ops):
     none2, seg2 = ops.point_heads(feat2, None, layers[4:], last, -1, 0, residual=(a, b))
     assert none2 is None
     assert torch.equal(feat1, feat2) and torch.equal(seg1, seg2)
+
+
+def test_call_helper_reads_the_stream_at_call_time(ops):
+    """ops.match_score (one kernel, through _lib.call) captured under torch.cuda.graph and replayed == the eager result.  Capture
+    runs on a stream of its own: a helper that had read the stream earlier would launch outside the capture, which raises."""
+    rs = np.random.RandomState(11)
+    B, N = 2, 70
+    conf = torch.from_numpy(rs.rand(B, N).astype(np.float32)).cuda()
+    mask = torch.from_numpy((rs.rand(B, N) < 0.6).astype(np.uint8)).cuda()
+    eager = ops.match_score(conf, mask)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = ops.match_score(conf, mask)
+    out.zero_()                                     # what capture left in the buffer is not the result
+    g.replay()
+    torch.cuda.synchronize()
+    assert float(eager.abs().min()) > 0 and torch.equal(out, eager)
