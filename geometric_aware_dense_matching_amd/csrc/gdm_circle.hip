@@ -27,43 +27,14 @@
 //                     gX^T[d, r] += Y^T[d, c] G[c, r] (24 MFMAs) with G taken STRAIGHT from the accumulator registers as the B
 //                     operand: the stream's d-major copy is packed in the k-order the accumulator layout dictates (cm_pack_kernel)
 //   MODE 2  grad y    owner = vertices, stream = scene rows (a slice of them per workgroup; partial sums reduced by the caller)
-// Products are split-bf16 (hi*hi + hi*lo + lo*hi, fp32 accumulate), as in the inference matching kernel.
-#include "gdm_common.h"
+// Products are split-bf16 (hi*hi + hi*lo + lo*hi, fp32 accumulate), as in the inference matching kernel.  The skeleton's tile code --
+// operand load, stage fills, both products, the output store -- is gdm_owner_stream.h, shared with soft_coord_kernel (gdm_softcoord.hip).
+#include "gdm_owner_stream.h"
 #include <math.h>
 
 namespace {
 
-
-constexpr int ROWB = 512;                       // packed row: 128 bf16 hi | 128 bf16 lo
-constexpr int CM_THREADS = 256;                 // 4 waves
-constexpr int CM_OWN = 128;                     // owner items per workgroup (32 per wave)
-constexpr int CM_ST = 64;                       // streamed items per LDS stage (two 32-item sub-tiles)
-constexpr int TP_G = 128 * 64;                  // bytes of one plane of a d-major 32-item sub-tile in global memory
-constexpr int TP_LSTRIDE = 80;                  // LDS bytes per d row of it (64 + 16 pad: conflict-free ds_read_b128)
-constexpr int TP_L = 128 * TP_LSTRIDE;
-constexpr int LDS_ROWS = CM_ST * ROWB;                       // 32 KiB
-constexpr int LDS_TP = (CM_ST / 32) * 2 * TP_L;              // 40 KiB
-constexpr int LDS_RD = 4 * CM_ST * 16;                       // MODE 2: per-wave row data
-
-__device__ __forceinline__ unsigned pack2(float a, float b)
-{
-    // plain casts: v_cvt_pk_bf16_f32 (round to nearest even, NaN stays NaN)
-    const __bf16 x = (__bf16)a, y = (__bf16)b;
-    return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
-}
-__device__ __forceinline__ float hi_of(float a) { return (float)(__bf16)a; }
-
-__device__ __forceinline__ void split8(const float* v, gdm_u32x4& hi, gdm_u32x4& lo)
-{
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        hi[j] = pack2(v[2 * j], v[2 * j + 1]);
-        lo[j] = pack2(v[2 * j] - hi_of(v[2 * j]), v[2 * j + 1] - hi_of(v[2 * j + 1]));
-    }
-}
-
-// accumulator register q (0..7) of k-step ks, lane half h  ->  streamed index inside a 32-item sub-tile
-__host__ __device__ __forceinline__ int acc_row(int ks, int h, int q) { return (q & 3) + 8 * (2 * ks + (q >> 2)) + 4 * h; }
+constexpr int LDS_RD = 4 * OS_ST * 16;                       // MODE 2: per-wave row data
 
 // x f32[n,128] (unit rows) -> rows[npad] (512-B split-bf16 rows, zero beyond n), tp[npad/32][2 planes][128 d][4 x 16 B] (the same
 // values d-major, the 8 values of a 16-B piece in accumulator order: piece (ks, h) holds items acc_row(ks, h, 0..7)), rowsum[npad].
@@ -205,7 +176,7 @@ __device__ __forceinline__ unsigned pos_word(const CmArgs& a, int g, int c2, int
 }
 
 template <int MODE, bool SYM>
-__global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a)
+__global__ __launch_bounds__(OS_THREADS, 2) void circle_mm_kernel(const CmArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* lrows = smem;
@@ -215,25 +186,18 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const bool own_is_x = MODE != 2;
-    const int nown_blocks = (own_is_x ? a.Rp : a.Mp) / CM_OWN;
+    const int nown_blocks = (own_is_x ? a.Rp : a.Mp) / OS_OWN;
     const int ob = blockIdx.x % nown_blocks;            // owner block
     const int part = blockIdx.x / nown_blocks;          // MODE 2: slice of the stream
-    const int own0 = ob * CM_OWN + wave * 32;           // this wave's first owner item
+    const int own0 = ob * OS_OWN + wave * 32;           // this wave's first owner item
     const unsigned char* orows = own_is_x ? a.xrows : a.yrows;
     const unsigned char* srows = own_is_x ? a.yrows : a.xrows;
     const unsigned char* stp = own_is_x ? a.ytp : a.xtp;
-    const int nstage = (own_is_x ? a.Mp : a.Rp) / CM_ST;
+    const int nstage = (own_is_x ? a.Mp : a.Rp) / OS_ST;
 
     // owner operand: 8 k-steps x (hi, lo)
     gdm_u32x4 ohi[8], olo[8];
-    {
-        const unsigned char* r = orows + (long)(own0 + j) * ROWB + h * 16;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            ohi[s] = *reinterpret_cast<const gdm_u32x4*>(r + s * 32);
-            olo[s] = *reinterpret_cast<const gdm_u32x4*>(r + 256 + s * 32);
-        }
-    }
+    os_load_owner(orows, own0 + j, h, ohi, olo);
     // per-lane constants of the owner row (MODE 0 / 1)
     int rg = 0, rc2 = -1, ritem = 0;
     float rlp = 0.f, rln = 0.f, rcoef = 0.f;
@@ -261,46 +225,23 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
     for (int st = (MODE == 2 ? part : 0); st < nstage; st += (MODE == 2 ? a.P : 1)) {
         __syncthreads();                                            // the previous stage's readers are done
         {
-            const unsigned char* src = srows + (long)st * CM_ST * ROWB;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int gch = i * CM_THREADS + tid;               // 2048 chunks of 16 B
-                *reinterpret_cast<gdm_u32x4*>(lrows + gdm_swz<ROWB>(gch >> 5, gch & 31)) = *reinterpret_cast<const gdm_u32x4*>(src + (long)gch * 16);
-            }
-            if (MODE != 0) {
-                const unsigned char* tsrc = stp + (long)st * (CM_ST / 32) * 2 * TP_G;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int gch = i * CM_THREADS + tid;           // (sub*2 + plane) * 512 + d * 4 + piece
-                    const int sp = gch >> 9, d = (gch >> 2) & 127, pc = gch & 3;
-                    *reinterpret_cast<gdm_u32x4*>(ltp + sp * TP_L + d * TP_LSTRIDE + pc * 16) = *reinterpret_cast<const gdm_u32x4*>(tsrc + (long)gch * 16);
-                }
-            }
+            os_fill_rows(srows, st, lrows, tid);
+            if (MODE != 0) os_fill_tp(stp, st, ltp, tid);
             if (MODE == 2) {                                        // per streamed scene row: lse_p, lse_n, coef, positives word
-                const int r = st * CM_ST + lane;                    //   of this wave's vertex tile
+                const int r = st * OS_ST + lane;                    //   of this wave's vertex tile
                 const unsigned w = pos_word<SYM>(a, a.g[r], (SYM && a.c2) ? a.c2[r] : -1, a.item[r], own0 >> 5);
-                lrd[wave * CM_ST + lane] = make_float4(a.lse_p[r], a.lse_n[r], a.coef[r], __uint_as_float(w));
+                lrd[wave * OS_ST + lane] = make_float4(a.lse_p[r], a.lse_n[r], a.coef[r], __uint_as_float(w));
             }
         }
         __syncthreads();
 
 #pragma unroll 1
-        for (int sub = 0; sub < CM_ST / 32; ++sub) {
-            const int t32 = st * (CM_ST / 32) + sub;                // index of this 32-item sub-tile in the stream
+        for (int sub = 0; sub < OS_ST / 32; ++sub) {
+            const int t32 = st * (OS_ST / 32) + sub;                // index of this 32-item sub-tile in the stream
             unsigned word = 0;
             if (own_is_x) word = pos_word<SYM>(a, rg, rc2, ritem, t32);
             // ---- S tile: acc[i][j] = <stream_i, owner_j> ----
-            gdm_f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const gdm_bf16x8 sh = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(lrows + gdm_swz<ROWB>(sub * 32 + j, 2 * s + h)));
-                const gdm_bf16x8 sl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(lrows + gdm_swz<ROWB>(sub * 32 + j, 16 + 2 * s + h)));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sh, __builtin_bit_cast(gdm_bf16x8, olo[s]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sl, __builtin_bit_cast(gdm_bf16x8, ohi[s]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sh, __builtin_bit_cast(gdm_bf16x8, ohi[s]), acc, 0, 0, 0);
-            }
+            const gdm_f32x16 acc = os_s_tile(lrows, sub * 32 + j, h, ohi, olo);
             // ---- element-wise: register r <-> streamed item i = acc_row(r >> 3, h, r & 7), lane <-> owner item j ----
             const int cbase = t32 * 32;                             // MODE 0/1: first vertex of the sub-tile
             float G[16];
@@ -315,7 +256,7 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
                     valid = cbase + i < a.M;
                     lp = rlp; ln = rln; cf = rcoef;
                 } else {
-                    const float4 rd = lrd[wave * CM_ST + sub * 32 + i];
+                    const float4 rd = lrd[wave * OS_ST + sub * 32 + i];
                     in = (__float_as_uint(rd.w) >> j) & 1u;
                     valid = true;                                   // padding rows carry coef = 0, padding vertices are dropped
                     lp = rd.x; ln = rd.y; cf = rd.z;
@@ -333,22 +274,7 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
                 }
             }
             if (MODE == 0) continue;
-            // ---- out^T[d][j] += sum_i stream^T[d][i] G[i][j]: G from the accumulator registers as the B operand ----
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                gdm_u32x4 gh, gl;
-                split8(&G[8 * ks], gh, gl);
-                const gdm_bf16x8 bgh = __builtin_bit_cast(gdm_bf16x8, gh), bgl = __builtin_bit_cast(gdm_bf16x8, gl);
-#pragma unroll
-                for (int db = 0; db < 4; ++db) {
-                    const unsigned char* p = ltp + (sub * 2) * TP_L + (db * 32 + j) * TP_LSTRIDE + (ks * 2 + h) * 16;
-                    const gdm_bf16x8 th = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(p));
-                    const gdm_bf16x8 tl = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(p + TP_L));
-                    outacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(th, bgl, outacc[db], 0, 0, 0);
-                    outacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tl, bgh, outacc[db], 0, 0, 0);
-                    outacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(th, bgh, outacc[db], 0, 0, 0);
-                }
-            }
+            os_second_product(ltp, sub, j, h, G, outacc);
         }
     }
 
@@ -385,28 +311,19 @@ __global__ __launch_bounds__(CM_THREADS, 2) void circle_mm_kernel(const CmArgs a
         else padg = rcoef != 0.f ? -w * inv_sqrt_d : 0.f;
     }
     float* ob_out = a.gout + (MODE == 2 ? (long)part * a.Mp * 128 : 0L) + (long)(own0 + j) * 128;
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const int d = db * 32 + 8 * q4 + 4 * h;                 // registers 4 q4 .. 4 q4 + 3 = four consecutive channels
-            *reinterpret_cast<float4*>(ob_out + d) = make_float4(outacc[db][4 * q4] + padg + (d == 0 ? padg0 : 0.f), outacc[db][4 * q4 + 1] + padg,
-                                                                 outacc[db][4 * q4 + 2] + padg, outacc[db][4 * q4 + 3] + padg);
-        }
+    os_store_out<true>(ob_out, h, outacc, padg, padg0);
 }
 
 template <int MODE>
 int launch_mode(const CmArgs& a, bool sym, hipStream_t stream)
 {
     const int lds = LDS_ROWS + (MODE != 0 ? LDS_TP : 0) + (MODE == 2 ? LDS_RD : 0);
-    const int grid = MODE == 2 ? (a.Mp / CM_OWN) * a.P : a.Rp / CM_OWN;
-    if (sym) {
-        GDM_HIP(hipFuncSetAttribute((const void*)circle_mm_kernel<MODE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        hipLaunchKernelGGL((circle_mm_kernel<MODE, true>), dim3(grid), dim3(CM_THREADS), lds, stream, a);
-    } else {
-        GDM_HIP(hipFuncSetAttribute((const void*)circle_mm_kernel<MODE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        hipLaunchKernelGGL((circle_mm_kernel<MODE, false>), dim3(grid), dim3(CM_THREADS), lds, stream, a);
-    }
+    const int grid = MODE == 2 ? (a.Mp / OS_OWN) * a.P : a.Rp / OS_OWN;
+    gdm_dispatch_bool(sym, [&](auto SYM) {
+        constexpr auto kernel = circle_mm_kernel<MODE, decltype(SYM)::value>;
+        gdm_allow_lds<kernel>(lds);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(OS_THREADS), lds, stream, a);
+    });
     return gdm_launch_status("circle_mm_kernel");
 }
 
@@ -485,11 +402,7 @@ extern "C" int gdm_circle_match_fwd2_hip(const void* xrows, const void* xtp, con
 
 extern "C" int gdm_circle_match_bwd_parts(int R, int M)
 {
-    if (R < 1 || M < 1) return 0;
-    const int vb = (M + 127) / 128, nst = (R + 127) / 128 * 128 / CM_ST;
-    int P = (768 + vb - 1) / vb;                                   // ~3 workgroups per CU in flight
-    if (P > nst) P = nst;
-    return P < 1 ? 1 : P;
+    return os_bwd_parts(R, M);
 }
 
 // Backward: gx f32[Rp,128] and gy_part f32[P][Mp,128] (P = gdm_circle_match_bwd_parts; the caller sums over P).

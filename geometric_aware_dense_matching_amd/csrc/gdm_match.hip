@@ -113,12 +113,77 @@ __global__ __launch_bounds__(256) void pack_rows2_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------
 // match
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int lds_chunk_off(int col, int ch)
+// accumulator register reg (0..15) of a 32 x 32 MFMA result, lane half h -> its row, in a block that starts at row0 (the column is lane & 31)
+__device__ __forceinline__ int acc_row(int row0, int reg, int h) { return row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+// the scene operand of one lane: its row's 16 chunks (clamped to the last row), resident in registers
+template <int PREC>
+__device__ __forceinline__ void load_a_rows(const unsigned char* __restrict__ apk, int row, int R, int h, gdm_u32x4 (&a)[16])
 {
-    // 512-B rows; XOR the low four bits of the 16-B chunk index with the column, so that the 16
-    // lanes of every ds_read_b128 group (distinct columns mod 16, same logical chunk) fall on 16
-    // different 16-B slots of the 256-B bank row.
-    return col * ROW_BYTES + (((ch & 16) | ((ch ^ col) & 15)) << 4);
+    const unsigned char* arow = apk + (long)min(row, R - 1) * ROW_BYTES;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        int ch;
+        if (PREC == GDM_MATCH_BF16X3) ch = (i < 8) ? (2 * i + h) : (16 + 2 * (i - 8) + h);   // hi[0..7], lo[0..7]
+        else ch = 16 * h + i;                                                                // k = 64h + 4i..4i+3
+        a[i] = *reinterpret_cast<const gdm_u32x4*>(arow + ch * 16);
+    }
+}
+
+// acc[b][reg] of lane (lr, h) = <scene row acc_row(0, reg, h) of the wave (areg, as load_a_rows leaves it), model column c0 + 32 b> over
+// the whole K = 128, the columns read from the swizzled image that starts base_off bytes into the dynamic LDS (c0 includes lr):
+//   BF16X3: v_mfma_f32_32x32x16_bf16, three per k-step in the order hi*lo, lo*hi, hi*hi;  F32: v_mfma_f32_32x32x2_f32
+// With NB = 2 the blocks alternate MFMA by MFMA, so that no MFMA waits for the one before it.  (The image is named by its offset:
+// given a pointer, match_kernel comes out with other register counts.)
+template <int PREC, int NB>
+__device__ __forceinline__ void tile_product(int base_off, int c0, int h, const gdm_u32x4 (&areg)[16], gdm_f32x16 (&acc)[NB])
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const unsigned char* base = smem + base_off;
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
+    if (PREC == GDM_MATCH_BF16X3) {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            gdm_bf16x8 bh[NB], bl[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                bh[b] = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(base + gdm_swz<ROW_BYTES>(c0 + 32 * b, 2 * s + h)));
+                bl[b] = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(base + gdm_swz<ROW_BYTES>(c0 + 32 * b, 16 + 2 * s + h)));
+            }
+            const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
+            const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[b], acc[b], 0, 0, 0);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[b], acc[b], 0, 0, 0);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[b], acc[b], 0, 0, 0);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            gdm_u32x4 bv[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) bv[b] = *reinterpret_cast<const gdm_u32x4*>(base + gdm_swz<ROW_BYTES>(c0 + 32 * b, 16 * h + i));
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i][e]), __uint_as_float(bv[b][e]), acc[b], 0, 0, 0);
+        }
+    }
+}
+
+// running (max, first arg-max) of one row: columns arrive in ascending order, so strict '>' keeps the first maximum
+__device__ __forceinline__ void running_max(float v, int col, bool ok, float& best, int& bidx)
+{
+    if (ok && v > best) {
+        best = v;
+        bidx = col;
+    }
 }
 
 template <int PREC, bool WRITE_SIM>
@@ -145,16 +210,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
 
     // ---- A operand: this lane's 16 chunks, resident for the whole kernel ----
     gdm_u32x4 areg[16];
-    {
-        const unsigned char* arow = apk + (long)min(row0 + lr, R - 1) * ROW_BYTES;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            int ch;
-            if (PREC == GDM_MATCH_BF16X3) ch = (i < 8) ? (2 * i + h) : (16 + 2 * (i - 8) + h);   // hi[0..7], lo[0..7]
-            else ch = 16 * h + i;                                                                // k = 64h + 4i..4i+3
-            areg[i] = *reinterpret_cast<const gdm_u32x4*>(arow + ch * 16);
-        }
-    }
+    load_a_rows<PREC>(apk, row0 + lr, R, h, areg);
 
     float best[16];
     int bidx[16];
@@ -182,7 +238,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
         for (int i = 0; i < 8; ++i) {
             const int g = i * 256 + tid;
             const int col = g >> 5, ch = g & 31;
-            *reinterpret_cast<gdm_u32x4*>(base + lds_chunk_off(col, ch)) = stage[i];
+            *reinterpret_cast<gdm_u32x4*>(base + gdm_swz<ROW_BYTES>(col, ch)) = stage[i];
         }
     };
 
@@ -197,44 +253,20 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
         const bool has_next = tile + 1 < ntiles;
         if (has_next) stage_load(tile + 1);                 // global loads in flight under the MFMAs
 
-        const unsigned char* base = smem + buf * TILE_BYTES;
         const int tcol0 = col_begin + tile * MT_COLS;
 
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
-            gdm_f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            gdm_f32x16 acc[1];
             const int col = cb * 32 + lr;
-            if (PREC == GDM_MATCH_BF16X3) {
-#pragma unroll
-                for (int s = 0; s < 8; ++s) {
-                    const gdm_u32x4 bh = *reinterpret_cast<const gdm_u32x4*>(base + lds_chunk_off(col, 2 * s + h));
-                    const gdm_u32x4 bl = *reinterpret_cast<const gdm_u32x4*>(base + lds_chunk_off(col, 16 + 2 * s + h));
-                    const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
-                    const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
-                    const gdm_bf16x8 vbh = __builtin_bit_cast(gdm_bf16x8, bh);
-                    const gdm_bf16x8 vbl = __builtin_bit_cast(gdm_bf16x8, bl);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, vbl, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, vbh, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, vbh, acc, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const gdm_u32x4 bv = *reinterpret_cast<const gdm_u32x4*>(base + lds_chunk_off(col, 16 * h + i));
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(bv.x), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(bv.y), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].z), __uint_as_float(bv.z), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].w), __uint_as_float(bv.w), acc, 0, 0, 0);
-                }
-            }
-            // ---- epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) ----
+            tile_product<PREC, 1>(buf * TILE_BYTES, col, h, areg, acc);
+            // ---- epilogue ----
             const int gcol = tcol0 + col;
             const bool col_ok = gcol < col_end;
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const float v = acc[reg];
+                const float v = acc[0][reg];
+                // running_max and acc_row restated: through the helpers match_kernel<*, true> comes out with other register counts
                 if (col_ok && v > best[reg]) {              // strict: first maximum per lane (ascending columns)
                     best[reg] = v;
                     bidx[reg] = gcol;
@@ -265,7 +297,7 @@ __global__ __launch_bounds__(256) void match_kernel(const unsigned char* __restr
             }
         }
         if (lr == 0) {
-            const int grow = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            const int grow = acc_row(row0, reg, h);
             if (grow < R) {
                 pval[(long)split * R + grow] = v;
                 pidx[(long)split * R + grow] = ix;
@@ -290,16 +322,77 @@ constexpr int PANEL_BYTES = PANEL_COLS * ROW_BYTES;     // 128 KiB
 constexpr int V2_THREADS = 512;
 constexpr int V2_ROWS = 256;                            // scene rows per workgroup iteration
 
-template <int PREC>
-__device__ __forceinline__ void load_a_rows(const unsigned char* __restrict__ apk, int row, int R, int h, gdm_u32x4 (&a)[16])
+// one-time panel fill at the start of the dynamic LDS: 256 columns x 32 chunks, 16 chunks per thread, coalesced 16-B loads; the columns
+// of a partial last panel are clamped to M - 1
+__device__ __forceinline__ void fill_panel(const unsigned char* bpk, int col0, int M, int tid)
 {
-    const unsigned char* arow = apk + (long)min(row, R - 1) * ROW_BYTES;
-#pragma unroll
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#pragma unroll 4
     for (int i = 0; i < 16; ++i) {
-        int ch;
-        if (PREC == GDM_MATCH_BF16X3) ch = (i < 8) ? (2 * i + h) : (16 + 2 * (i - 8) + h);
-        else ch = 16 * h + i;
-        a[i] = *reinterpret_cast<const gdm_u32x4*>(arow + ch * 16);
+        const int gi = i * V2_THREADS + tid;
+        const int col = gi >> 5, ch = gi & 31;
+        const int gc = min(col0 + col, M - 1);
+        const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)gc * ROW_BYTES + ch * 16);
+        *reinterpret_cast<gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(col, ch)) = v;
+    }
+}
+
+// k-step s of a BF16X3 scene row that exists (no clamp): its hi and its lo chunk, reloaded inside the pipelined kernels' steps
+__device__ __forceinline__ void load_a_step(const unsigned char* arow, int s, int h, gdm_u32x4 (&a)[16])
+{
+    a[s] = *reinterpret_cast<const gdm_u32x4*>(arow + (2 * s + h) * 16);
+    a[8 + s] = *reinterpret_cast<const gdm_u32x4*>(arow + (16 + 2 * s + h) * 16);
+}
+
+// one halving step of the row butterfly for (max, lowest arg): the lane keeps the upper (up) or lower n of its 2n rows and merges
+// the partner's values of them
+template <int n>
+__device__ __forceinline__ void halve_max(const float (&v)[2 * n], const int (&ix)[2 * n], float (&ov)[n], int (&oi)[n], bool up, int mask)
+{
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+        const float sv = up ? v[i] : v[i + n];
+        const int si = up ? ix[i] : ix[i + n];
+        const float pv = __shfl_xor(sv, mask, 64);
+        const int pi = __shfl_xor(si, mask, 64);
+        const float mv = up ? v[i + n] : v[i];
+        const int mi = up ? ix[i + n] : ix[i];
+        const bool take = pv > mv || (pv == mv && pi < mi);
+        ov[i] = take ? pv : mv;
+        oi[i] = take ? pi : mi;
+    }
+}
+
+// lane bits 0..3 chose the upper half of the remaining row set at steps 1..4 of the butterfly: the register (row acc_row(row0, reg, h))
+// whose result the lanes with (lane & 16) == 0 hold afterwards, reg = 8*b0 + 4*b1 + 2*b2 + b3
+__device__ __forceinline__ int survivor_reg(int lane) { return ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3); }
+
+// (max, lowest arg) across the 32 lanes of each half-wave, halving the row set every step: after step t each lane carries 16>>(t+1)
+// rows, so 16+8+4+2 (+2) shuffles instead of 160; one lane per row writes.  GUARD: rows past R are not written (the pipelined
+// kernels run only with R a multiple of the row block and need no guard)
+template <bool GUARD = false>
+__device__ __forceinline__ void finalize_rows(const float (&best)[16], const int (&bidx)[16], int lane, int h, int row0, int R,
+                                              int panel, float* __restrict__ pval, int32_t* __restrict__ pidx)
+{
+    float v8[8], v4[4], v2[2], w1[1];
+    int i8[8], i4[4], i2[2], j1[1];
+    halve_max<8>(best, bidx, v8, i8, lane & 1, 1);
+    halve_max<4>(v8, i8, v4, i4, lane & 2, 2);
+    halve_max<2>(v4, i4, v2, i2, lane & 4, 4);
+    halve_max<1>(v2, i2, w1, j1, lane & 8, 8);
+    float v1 = w1[0];                                   // scalars from here on: left in the arrays, two registers of
+    int i1 = j1[0];                                     // match_pipe_sim_kernel swap their names
+    const float ov = __shfl_xor(v1, 16, 64);
+    const int oi = __shfl_xor(i1, 16, 64);
+    if (ov > v1 || (ov == v1 && oi < i1)) {
+        v1 = ov;
+        i1 = oi;
+    }
+    if ((lane & 16) == 0) {
+        const int grow = acc_row(row0, survivor_reg(lane), h);
+        if (GUARD && grow >= R) return;
+        pval[(long)panel * R + grow] = v1;
+        pidx[(long)panel * R + grow] = i1;
     }
 }
 
@@ -323,15 +416,7 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_kernel(const unsigned 
     const int col0 = panel * PANEL_COLS;
     const int ncols = min(PANEL_COLS, M - col0);
 
-    // ---- one-time panel fill: 256 columns x 32 chunks, 16 chunks per thread, coalesced 16-B loads ----
-#pragma unroll 4
-    for (int i = 0; i < 16; ++i) {
-        const int gi = i * V2_THREADS + tid;
-        const int col = gi >> 5, ch = gi & 31;
-        const int gc = min(col0 + col, M - 1);
-        const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)gc * ROW_BYTES + ch * 16);
-        *reinterpret_cast<gdm_u32x4*>(smem + lds_chunk_off(col, ch)) = v;
-    }
+    fill_panel(bpk, col0, M, tid);
     __syncthreads();
 
     const int nrb = (R + V2_ROWS - 1) / V2_ROWS;
@@ -355,59 +440,18 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_kernel(const unsigned 
 
 #pragma unroll 1
         for (int cp = 0; cp < PANEL_COLS / 64; ++cp) {
-            gdm_f32x16 acc0, acc1;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                acc0[i] = 0.f;
-                acc1[i] = 0.f;
-            }
+            gdm_f32x16 acc[2];
             const int c0 = cp * 64 + lr, c1 = c0 + 32;
-            if (PREC == GDM_MATCH_BF16X3) {
-#pragma unroll
-                for (int s = 0; s < 8; ++s) {
-                    const gdm_bf16x8 bh0 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 2 * s + h)));
-                    const gdm_bf16x8 bl0 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 + 2 * s + h)));
-                    const gdm_bf16x8 bh1 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 2 * s + h)));
-                    const gdm_bf16x8 bl1 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 16 + 2 * s + h)));
-                    const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
-                    const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl1, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh1, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh1, acc1, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const gdm_u32x4 b0 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 * h + i));
-                    const gdm_u32x4 b1 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 16 * h + i));
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(b0.x), acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(b1.x), acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(b0.y), acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(b1.y), acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].z), __uint_as_float(b0.z), acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].z), __uint_as_float(b1.z), acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].w), __uint_as_float(b0.w), acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].w), __uint_as_float(b1.w), acc1, 0, 0, 0);
-                }
-            }
+            tile_product<PREC, 2>(0, c0, h, areg, acc);
             const int gc0 = col0 + c0, gc1 = col0 + c1;
             const bool ok0 = c0 < ncols, ok1 = c1 < ncols;
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const float v0 = acc0[reg], v1 = acc1[reg];
-                if (ok0 && v0 > best[reg]) {
-                    best[reg] = v0;
-                    bidx[reg] = gc0;
-                }
-                if (ok1 && v1 > best[reg]) {
-                    best[reg] = v1;
-                    bidx[reg] = gc1;
-                }
+                const float v0 = acc[0][reg], v1 = acc[1][reg];
+                running_max(v0, gc0, ok0, best[reg], bidx[reg]);
+                running_max(v1, gc1, ok1, best[reg], bidx[reg]);
                 if (WRITE_SIM) {
-                    const int grow = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+                    const int grow = acc_row(row0, reg, h);
                     if (grow < R) {
                         float* o = sim + (long)grow * M;
                         if (ok0) __builtin_nontemporal_store(v0, o + gc0);
@@ -417,87 +461,7 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_kernel(const unsigned 
             }
         }
 
-        // ---- (max, lowest arg) across the 32 lanes of each half-wave, halving the row set every step:
-        //      after step t each lane carries 16>>(t+1) rows, so 16+8+4+2 (+2) shuffles instead of 160 ----
-        float v8[8];  int i8[8];
-        {
-            const bool up = lane & 1;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float sv = up ? best[i] : best[i + 8];
-                const int si = up ? bidx[i] : bidx[i + 8];
-                const float ov = __shfl_xor(sv, 1, 64);
-                const int oi = __shfl_xor(si, 1, 64);
-                const float mv = up ? best[i + 8] : best[i];
-                const int mi = up ? bidx[i + 8] : bidx[i];
-                const bool take = ov > mv || (ov == mv && oi < mi);
-                v8[i] = take ? ov : mv;
-                i8[i] = take ? oi : mi;
-            }
-        }
-        float v4[4];  int i4[4];
-        {
-            const bool up = lane & 2;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float sv = up ? v8[i] : v8[i + 4];
-                const int si = up ? i8[i] : i8[i + 4];
-                const float ov = __shfl_xor(sv, 2, 64);
-                const int oi = __shfl_xor(si, 2, 64);
-                const float mv = up ? v8[i + 4] : v8[i];
-                const int mi = up ? i8[i + 4] : i8[i];
-                const bool take = ov > mv || (ov == mv && oi < mi);
-                v4[i] = take ? ov : mv;
-                i4[i] = take ? oi : mi;
-            }
-        }
-        float v2[2];  int i2[2];
-        {
-            const bool up = lane & 4;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float sv = up ? v4[i] : v4[i + 2];
-                const int si = up ? i4[i] : i4[i + 2];
-                const float ov = __shfl_xor(sv, 4, 64);
-                const int oi = __shfl_xor(si, 4, 64);
-                const float mv = up ? v4[i + 2] : v4[i];
-                const int mi = up ? i4[i + 2] : i4[i];
-                const bool take = ov > mv || (ov == mv && oi < mi);
-                v2[i] = take ? ov : mv;
-                i2[i] = take ? oi : mi;
-            }
-        }
-        float v1;  int i1;
-        {
-            const bool up = lane & 8;
-            const float sv = up ? v2[0] : v2[1];
-            const int si = up ? i2[0] : i2[1];
-            const float ov = __shfl_xor(sv, 8, 64);
-            const int oi = __shfl_xor(si, 8, 64);
-            const float mv = up ? v2[1] : v2[0];
-            const int mi = up ? i2[1] : i2[0];
-            const bool take = ov > mv || (ov == mv && oi < mi);
-            v1 = take ? ov : mv;
-            i1 = take ? oi : mi;
-        }
-        {
-            const float ov = __shfl_xor(v1, 16, 64);
-            const int oi = __shfl_xor(i1, 16, 64);
-            if (ov > v1 || (ov == v1 && oi < i1)) {
-                v1 = ov;
-                i1 = oi;
-            }
-        }
-        // lane bits 0..3 chose the upper half of the remaining row set at steps 1..4:
-        // register index reg = 8*b0 + 4*b1 + 2*b2 + b3
-        if ((lane & 16) == 0) {
-            const int reg = ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3);
-            const int grow = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            if (grow < R) {
-                pval[(long)panel * R + grow] = v1;
-                pidx[(long)panel * R + grow] = i1;
-            }
-        }
+        finalize_rows<true>(best, bidx, lane, h, row0, R, panel, pval, pidx);
     }
 }
 
@@ -523,10 +487,10 @@ struct BFrag { gdm_u32x4 h0, l0, h1, l1; };
 __device__ __forceinline__ BFrag read_bfrag(const unsigned char* smem, int c0, int s, int h)
 {
     BFrag f;
-    f.h0 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 2 * s + h));
-    f.l0 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 + 2 * s + h));
-    f.h1 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0 + 32, 2 * s + h));
-    f.l1 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0 + 32, 16 + 2 * s + h));
+    f.h0 = *reinterpret_cast<const gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(c0, 2 * s + h));
+    f.l0 = *reinterpret_cast<const gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(c0, 16 + 2 * s + h));
+    f.h1 = *reinterpret_cast<const gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(c0 + 32, 2 * s + h));
+    f.l1 = *reinterpret_cast<const gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(c0 + 32, 16 + 2 * s + h));
     return f;
 }
 
@@ -592,10 +556,7 @@ __device__ __forceinline__ void pipe_step(const unsigned char* smem, int lr, int
         n1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh1, al, n1, 0, 0, 0);
         n0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh0, ah, n0, 0, 0, 0);
         n1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh1, ah, n1, 0, 0, 0);
-        if (PREFETCH) {
-            areg[s] = *reinterpret_cast<const gdm_u32x4*>(arow_next + (2 * s + h) * 16);
-            areg[8 + s] = *reinterpret_cast<const gdm_u32x4*>(arow_next + (16 + 2 * s + h) * 16);
-        }
+        if (PREFETCH) load_a_step(arow_next, s, h, areg);
         fr = nx;
     }
     if (DRAIN) {
@@ -635,12 +596,14 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_kernel(const unsigned c
     const int panel = blockIdx.x / G;
     const int col0 = panel * PANEL_COLS;
 
+    // fill_panel (without the clamp) and load_a_step restated here and below: through the helpers match_pipe_kernel, which the
+    // headline step runs, comes out with its instructions in another order
 #pragma unroll 4
     for (int i = 0; i < 16; ++i) {
         const int gi = i * V2_THREADS + tid;
         const int col = gi >> 5, ch = gi & 31;
         const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)(col0 + col) * ROW_BYTES + ch * 16);
-        *reinterpret_cast<gdm_u32x4*>(smem + lds_chunk_off(col, ch)) = v;
+        *reinterpret_cast<gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(col, ch)) = v;
     }
     __syncthreads();
 
@@ -706,90 +669,6 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_kernel(const unsigned c
     }
 }
 
-// GUARD: rows past R are not written (the pipelined kernels run only with R a multiple of the row block and need no guard)
-template <bool GUARD = false>
-__device__ __forceinline__ void finalize_rows(const float (&best)[16], const int (&bidx)[16], int lane, int h, int row0, int R,
-                                              int panel, float* __restrict__ pval, int32_t* __restrict__ pidx)
-{
-    // (max, lowest arg) across the 32 lanes of each half-wave, halving the row set every step (as v2)
-    float v8[8];  int i8[8];
-    {
-        const bool up = lane & 1;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float sv = up ? best[i] : best[i + 8];
-            const int si = up ? bidx[i] : bidx[i + 8];
-            const float ov = __shfl_xor(sv, 1, 64);
-            const int oi = __shfl_xor(si, 1, 64);
-            const float mv = up ? best[i + 8] : best[i];
-            const int mi = up ? bidx[i + 8] : bidx[i];
-            const bool take = ov > mv || (ov == mv && oi < mi);
-            v8[i] = take ? ov : mv;
-            i8[i] = take ? oi : mi;
-        }
-    }
-    float v4[4];  int i4[4];
-    {
-        const bool up = lane & 2;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float sv = up ? v8[i] : v8[i + 4];
-            const int si = up ? i8[i] : i8[i + 4];
-            const float ov = __shfl_xor(sv, 2, 64);
-            const int oi = __shfl_xor(si, 2, 64);
-            const float mv = up ? v8[i + 4] : v8[i];
-            const int mi = up ? i8[i + 4] : i8[i];
-            const bool take = ov > mv || (ov == mv && oi < mi);
-            v4[i] = take ? ov : mv;
-            i4[i] = take ? oi : mi;
-        }
-    }
-    float v2[2];  int i2[2];
-    {
-        const bool up = lane & 4;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const float sv = up ? v4[i] : v4[i + 2];
-            const int si = up ? i4[i] : i4[i + 2];
-            const float ov = __shfl_xor(sv, 4, 64);
-            const int oi = __shfl_xor(si, 4, 64);
-            const float mv = up ? v4[i + 2] : v4[i];
-            const int mi = up ? i4[i + 2] : i4[i];
-            const bool take = ov > mv || (ov == mv && oi < mi);
-            v2[i] = take ? ov : mv;
-            i2[i] = take ? oi : mi;
-        }
-    }
-    float v1;  int i1;
-    {
-        const bool up = lane & 8;
-        const float sv = up ? v2[0] : v2[1];
-        const int si = up ? i2[0] : i2[1];
-        const float ov = __shfl_xor(sv, 8, 64);
-        const int oi = __shfl_xor(si, 8, 64);
-        const float mv = up ? v2[1] : v2[0];
-        const int mi = up ? i2[1] : i2[0];
-        const bool take = ov > mv || (ov == mv && oi < mi);
-        v1 = take ? ov : mv;
-        i1 = take ? oi : mi;
-    }
-    {
-        const float ov = __shfl_xor(v1, 16, 64);
-        const int oi = __shfl_xor(i1, 16, 64);
-        if (ov > v1 || (ov == v1 && oi < i1)) {
-            v1 = ov;
-            i1 = oi;
-        }
-    }
-    if ((lane & 16) == 0) {
-        const int reg = ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3);
-        const int grow = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        if (GUARD && grow >= R) return;
-        pval[(long)panel * R + grow] = v1;
-        pidx[(long)panel * R + grow] = i1;
-    }
-}
-
 // Materialised form of v3: original operand roles (lane = column, register = row), so one dword store instruction covers
 // 2 rows x 128 contiguous bytes and may stay non-temporal; the swapped layout's 16-byte pieces need write-back merging in L2
 // and lose under load (347 vs 256 us).  Running (max, arg) per register, v2's butterfly per row block.
@@ -799,8 +678,8 @@ struct BFrag1 { gdm_u32x4 h, l; };
 __device__ __forceinline__ BFrag1 read_bfrag1(const unsigned char* smem, int c, int s, int h)
 {
     BFrag1 f;
-    f.h = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c, 2 * s + h));
-    f.l = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c, 16 + 2 * s + h));
+    f.h = *reinterpret_cast<const gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(c, 2 * s + h));
+    f.l = *reinterpret_cast<const gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(c, 16 + 2 * s + h));
     return f;
 }
 
@@ -823,20 +702,19 @@ __device__ __forceinline__ void pipe_step_sim(const unsigned char* smem, int lr,
         n = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, n, 0, 0, 0);
         n = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, n, 0, 0, 0);
         n = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, n, 0, 0, 0);
-        if (RELOAD) {
-            areg[s] = *reinterpret_cast<const gdm_u32x4*>(arow_next + (2 * s + h) * 16);
-            areg[8 + s] = *reinterpret_cast<const gdm_u32x4*>(arow_next + (16 + 2 * s + h) * 16);
-        }
+        if (RELOAD) load_a_step(arow_next, s, h, areg);
         fr = nx;
     }
     if (DRAIN) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const float v = p[reg];
+            // running_max restated (here and in the kernel's last drain) as selects: through the helper's branch match_pipe_sim_kernel,
+            // which the headline step runs when the matrix is asked for, comes out with other instructions
             const bool t = v > best[reg];
             best[reg] = t ? v : best[reg];
             bidx[reg] = t ? pgc : bidx[reg];
-            float* o = pbase + (long)((reg & 3) + 8 * (reg >> 2)) * M + PCP * 32;     // uniform row base, per-lane 32-bit offset
+            float* o = pbase + (long)acc_row(0, reg, 0) * M + PCP * 32;     // uniform row base, per-lane 32-bit offset
             __builtin_nontemporal_store(v, o + pvoff);
         }
     }
@@ -868,12 +746,13 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_sim_kernel(const unsign
     const int panel = blockIdx.x / G;
     const int col0 = panel * PANEL_COLS;
 
+    // panel fill and first operand load restated, as in match_pipe_kernel: this kernel's instructions are to stay as they are
 #pragma unroll 4
     for (int i = 0; i < 16; ++i) {
         const int gi = i * V2_THREADS + tid;
         const int col = gi >> 5, ch = gi & 31;
         const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)(col0 + col) * ROW_BYTES + ch * 16);
-        *reinterpret_cast<gdm_u32x4*>(smem + lds_chunk_off(col, ch)) = v;
+        *reinterpret_cast<gdm_u32x4*>(smem + gdm_swz<ROW_BYTES>(col, ch)) = v;
     }
     __syncthreads();
 
@@ -927,7 +806,7 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_sim_kernel(const unsign
                 const bool t = v > best[reg];
                 best[reg] = t ? v : best[reg];
                 bidx[reg] = t ? gc + 224 : bidx[reg];
-                float* o = pbase + (long)((reg & 3) + 8 * (reg >> 2)) * Ml + 224;
+                float* o = pbase + (long)acc_row(0, reg, 0) * Ml + 224;
                 __builtin_nontemporal_store(v, o + pvoff);
             }
         }
@@ -946,19 +825,15 @@ __global__ __launch_bounds__(V2_THREADS) void match_pipe_sim_kernel(const unsign
 // Per scene row i, over the M real columns j (include/gdm.h gdm_match_soft_packed_hip):
 //   Z_i = sum_j exp(gamma (sim_ij - 1)),  S_i = sum_j exp(gamma (sim_ij - 1)) xyz_j;   lse = gamma + log Z, soft_xyz = S / Z.
 // Cosines are <= 1 and gamma <= 40, so with the fixed shift 1 every term lies in [e^-80, ~1]: no running maximum, no rescaling, and
-// the partial sums of the panels merge by addition.  Same operand loads, same MFMA sequence and same arg-max scan as
-// match_panel_kernel, so best_idx / best_sim are the hard path's bit for bit; that kernel's code is deliberately left untouched (its
-// instances compile to the same instructions as before), so the product block is restated here.
+// the partial sums of the panels merge by addition.  The panel fill, the operand load, the product block (tile_product), the
+// arg-max scan (running_max) and the row butterfly (finalize_rows) are match_panel_kernel's own, so best_idx / best_sim are the hard
+// path's bit for bit (profiles/tile_helpers.md: what sharing them changed in either kernel's code, and that it cost no time).
 // Layout as v2: lane = column, 16 rows per lane.  The four accumulators take 64 VGPRs per lane; they are paid for with v2's
 // next-row-block operand prefetch (64 VGPRs), whose latency the SIMD's partner wave covers.  The panel's xyz (3 KiB) sits in LDS
 // behind the descriptor panel.  Per row block a wave sums its 16 x 4 accumulators across the 32 lanes of each half-wave by the
 // same halving butterfly as the arg-max (a fixed order: two launches are bit-identical) and writes one (Z, Sx, Sy, Sz) per
 // (panel, row); soft_merge_kernel adds the panels in ascending order.  No atomics.
 constexpr int SOFT_LDS_BYTES = PANEL_BYTES + PANEL_COLS * 3 * (int)sizeof(float);
-
-// Packed fp32 arithmetic must not read a register in the two wait states behind the wait that retires its LDS read (ADVICE.md
-// item 1, tools/scan_lds_pk_hazard.py): retire the reads and spend the two states here, once per 64-column block / butterfly step.
-#define GDM_LDS_SETTLE(...) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 1" : __VA_ARGS__)
 
 // one halving step of the row butterfly for sums: the lane keeps the upper (up) or lower n of its 2n rows and adds the partner's
 template <int n>
@@ -967,10 +842,10 @@ __device__ __forceinline__ void halve_sum(const float (&in)[2 * n], float (&out)
     float ov[n];
 #pragma unroll
     for (int i = 0; i < n; ++i) ov[i] = __shfl_xor(up ? in[i] : in[i + n], mask, 64);
-    if constexpr (n == 8) GDM_LDS_SETTLE("+v"(ov[0]), "+v"(ov[1]), "+v"(ov[2]), "+v"(ov[3]), "+v"(ov[4]), "+v"(ov[5]), "+v"(ov[6]), "+v"(ov[7]));
-    else if constexpr (n == 4) GDM_LDS_SETTLE("+v"(ov[0]), "+v"(ov[1]), "+v"(ov[2]), "+v"(ov[3]));
-    else if constexpr (n == 2) GDM_LDS_SETTLE("+v"(ov[0]), "+v"(ov[1]));
-    else GDM_LDS_SETTLE("+v"(ov[0]));
+    if constexpr (n == 8) GDM_SETTLE_LDS("+v"(ov[0]), "+v"(ov[1]), "+v"(ov[2]), "+v"(ov[3]), "+v"(ov[4]), "+v"(ov[5]), "+v"(ov[6]), "+v"(ov[7]));
+    else if constexpr (n == 4) GDM_SETTLE_LDS("+v"(ov[0]), "+v"(ov[1]), "+v"(ov[2]), "+v"(ov[3]));
+    else if constexpr (n == 2) GDM_SETTLE_LDS("+v"(ov[0]), "+v"(ov[1]));
+    else GDM_SETTLE_LDS("+v"(ov[0]));
 #pragma unroll
     for (int i = 0; i < n; ++i) out[i] = (up ? in[i + n] : in[i]) + ov[i];
 }
@@ -985,7 +860,7 @@ __device__ __forceinline__ float row_sum16(const float (&a)[16], int lane)
     halve_sum<2>(a4, a2, lane & 4, 4);
     halve_sum<1>(a2, a1, lane & 8, 8);
     float o = __shfl_xor(a1[0], 16, 64);
-    GDM_LDS_SETTLE("+v"(o));
+    GDM_SETTLE_LDS("+v"(o));
     return a1[0] + o;
 }
 
@@ -1011,14 +886,7 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_soft_kernel(const unsi
     const int col0 = panel * PANEL_COLS;
     const int ncols = min(PANEL_COLS, M - col0);
 
-#pragma unroll 4
-    for (int i = 0; i < 16; ++i) {
-        const int gi = i * V2_THREADS + tid;
-        const int col = gi >> 5, ch = gi & 31;
-        const int gc = min(col0 + col, M - 1);
-        const gdm_u32x4 v = *reinterpret_cast<const gdm_u32x4*>(bpk + (long)gc * ROW_BYTES + ch * 16);
-        *reinterpret_cast<gdm_u32x4*>(smem + lds_chunk_off(col, ch)) = v;
-    }
+    fill_panel(bpk, col0, M, tid);
     for (int i = tid; i < 3 * PANEL_COLS; i += V2_THREADS) {
         const int col = i / 3;
         xs[i] = xyz[(long)min(col0 + col, M - 1) * 3 + (i - 3 * col)];
@@ -1042,60 +910,19 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_soft_kernel(const unsi
 
 #pragma unroll 1
         for (int cp = 0; cp < PANEL_COLS / 64; ++cp) {
-            gdm_f32x16 acc0, acc1;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                acc0[i] = 0.f;
-                acc1[i] = 0.f;
-            }
+            gdm_f32x16 acc[2];
             const int c0 = cp * 64 + lr, c1 = c0 + 32;
-            if (PREC == GDM_MATCH_BF16X3) {
-#pragma unroll
-                for (int s = 0; s < 8; ++s) {
-                    const gdm_bf16x8 bh0 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 2 * s + h)));
-                    const gdm_bf16x8 bl0 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 + 2 * s + h)));
-                    const gdm_bf16x8 bh1 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 2 * s + h)));
-                    const gdm_bf16x8 bl1 = __builtin_bit_cast(gdm_bf16x8, *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 16 + 2 * s + h)));
-                    const gdm_bf16x8 ah = __builtin_bit_cast(gdm_bf16x8, areg[s]);
-                    const gdm_bf16x8 al = __builtin_bit_cast(gdm_bf16x8, areg[8 + s]);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl1, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh1, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh1, acc1, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const gdm_u32x4 b0 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c0, 16 * h + i));
-                    const gdm_u32x4 b1 = *reinterpret_cast<const gdm_u32x4*>(smem + lds_chunk_off(c1, 16 * h + i));
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(b0.x), acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].x), __uint_as_float(b1.x), acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(b0.y), acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].y), __uint_as_float(b1.y), acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].z), __uint_as_float(b0.z), acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].z), __uint_as_float(b1.z), acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].w), __uint_as_float(b0.w), acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(areg[i].w), __uint_as_float(b1.w), acc1, 0, 0, 0);
-                }
-            }
+            tile_product<PREC, 2>(0, c0, h, areg, acc);
             const int gc0 = col0 + c0, gc1 = col0 + c1;
             const bool ok0 = c0 < ncols, ok1 = c1 < ncols;
             float x0 = xs[3 * c0], y0 = xs[3 * c0 + 1], z0 = xs[3 * c0 + 2];
             float x1 = xs[3 * c1], y1 = xs[3 * c1 + 1], z1 = xs[3 * c1 + 2];
-            GDM_LDS_SETTLE("+v"(x0), "+v"(y0), "+v"(z0), "+v"(x1), "+v"(y1), "+v"(z1));
+            GDM_SETTLE_LDS("+v"(x0), "+v"(y0), "+v"(z0), "+v"(x1), "+v"(y1), "+v"(z1));
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const float v0 = acc0[reg], v1 = acc1[reg];
-                if (ok0 && v0 > best[reg]) {
-                    best[reg] = v0;
-                    bidx[reg] = gc0;
-                }
-                if (ok1 && v1 > best[reg]) {
-                    best[reg] = v1;
-                    bidx[reg] = gc1;
-                }
+                const float v0 = acc[0][reg], v1 = acc[1][reg];
+                running_max(v0, gc0, ok0, best[reg], bidx[reg]);
+                running_max(v1, gc1, ok1, best[reg], bidx[reg]);
                 // a padding column of the last panel weighs nothing
                 const float w0 = ok0 ? __builtin_amdgcn_exp2f(__builtin_fmaf(v0, k2, -k2)) : 0.f;
                 const float w1 = ok1 ? __builtin_amdgcn_exp2f(__builtin_fmaf(v1, k2, -k2)) : 0.f;
@@ -1109,8 +936,7 @@ __global__ __launch_bounds__(V2_THREADS) void match_panel_soft_kernel(const unsi
         finalize_rows<true>(best, bidx, lane, h, row0, R, panel, pval, pidx);
         const float rz = row_sum16(z, lane), rx = row_sum16(sx, lane), ry = row_sum16(sy, lane), rw = row_sum16(sz, lane);
         if ((lane & 16) == 0) {
-            const int reg = ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3);
-            const int grow = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            const int grow = acc_row(row0, survivor_reg(lane), h);
             if (grow < R) psum[(long)panel * R + grow] = make_float4(rz, rx, ry, rw);
         }
     }

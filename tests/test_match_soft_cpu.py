@@ -196,11 +196,14 @@ def test_bop_csv_writes_the_given_scores():
 
 
 # ---- hazard scan ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("unit, marks, n_new", [("gdm_match.hip", ("soft",), 3), ("gdm_pose.hip", ("kabsch_stats_w", "kabsch_solve_w"), 2)])
+@pytest.mark.parametrize("unit, marks, n_new", [("gdm_match.hip", ("soft",), 3), ("gdm_pose.hip", ("kabsch_stats_w", "kabsch_solve_w"), 2),
+                                                ("gdm_match.hip", ("match_kernel", "match_panel_kernel"), 8),
+                                                ("gdm_circle.hip", ("circle_mm",), 6)])
 def test_new_kernels_have_no_exposed_packed_fp32_consumer(tmp_path, unit, marks, n_new):
     """hipcc -S of the translation units that hold the new kernels, with the Makefile's flags, then tools/scan_lds_pk_hazard.py: in
-    no soft instance and in neither weighted pose kernel does a packed-fp32 instruction read a register fewer than two wait states
-    after the wait that retires its LDS read."""
+    no soft instance, in neither weighted pose kernel and in none of the kernels that share the tile helpers (match_kernel,
+    match_panel_kernel, circle_mm_kernel: sharing re-orders their instructions) does a packed-fp32 instruction read a register fewer
+    than two wait states after the wait that retires its LDS read."""
     csrc = os.path.join(ROOT, "geometric_aware_dense_matching_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
     var = dict(re.findall(r"^(\w+)\s*[:?]?=\s*(.*)$", mk, flags=re.M))
