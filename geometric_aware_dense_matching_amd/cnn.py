@@ -254,6 +254,9 @@ class Upsample2x(nn.Module):
         return ops.upsample_bilinear(x, (x.shape[2] * 2, x.shape[3] * 2))
 
 
+FUSED64, TAP_GEMM_MFMA, TAP_GEMM_BLAS = "FUSED64", "TAP_GEMM_MFMA", "TAP_GEMM_BLAS"      # PSPUpsample._eval_path
+
+
 class PSPUpsample(nn.Module):
     def __init__(self, cin, cout):
         super().__init__()
@@ -264,44 +267,50 @@ class PSPUpsample(nn.Module):
         w = self.conv[1].weight
         return derived(self, "wt", (w,), lambda: w.permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1]).contiguous())
 
-    def reads_packed_only(self, shape):
-        """True when forward() on a GPU map of this shape takes the tap GEMM on the map's packed operand (`gemm_bf16x3_map`) and reads
-        nothing else of it: its producer may then hand over the ops.PackedAct alone.  Mirrors the branch conditions of forward()."""
+    def _eval_path(self, shape):
+        """The inference form forward() takes on a map of this shape: FUSED64, TAP_GEMM_MFMA, TAP_GEMM_BLAS, or None for the modules."""
         conv = self.conv[1]
         Bx, Cin, Hx, Wx = shape
-        if self.training or torch.is_grad_enabled() or act_code(self.conv[3]) is None or Cin != conv.in_channels:
-            return False
-        if not (Bx * conv.out_channels <= 65535 and conv.in_channels >= settings.UPCONV_MIN_CIN):
-            return False
+        if act_code(self.conv[3]) is None or not (Bx * conv.out_channels <= 65535 and conv.in_channels >= settings.UPCONV_MIN_CIN):
+            return None
         if settings.USE_FUSED_UPCONV and Cin == 64 and conv.out_channels == 64 and Hx >= 2 and Wx >= 2 and Bx <= 65535:
+            return FUSED64
+        if settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, 9 * conv.out_channels, Hx * Wx):
+            return TAP_GEMM_MFMA
+        return TAP_GEMM_BLAS
+
+    def reads_packed_only(self, shape):
+        """True when forward() on a GPU map of this shape takes the tap GEMM on the map's packed operand (`gemm_bf16x3_map`) and reads
+        nothing else of it: its producer may then hand over the ops.PackedAct alone."""
+        if self.training or torch.is_grad_enabled() or shape[1] != self.conv[1].in_channels:
             return False
-        return settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, 9 * conv.out_channels, Hx * Wx) and Wx % 32 == 0
+        return self._eval_path(shape) is TAP_GEMM_MFMA and shape[3] % 32 == 0
 
     def forward(self, x):
         packed_in = isinstance(x, ops.PackedAct)
         if packed_in and not self.reads_packed_only(x.shape):
             raise RuntimeError("PSPUpsample: a packed-only map of shape %s does not fit the path this stage takes" % (x.shape,))
-        if packed_in or fused_eval(x, self):
+        path = self._eval_path(x.shape) if packed_in or fused_eval(x, self) else None
+        if path is not None:
+            # conv3x3(up(x)) = 9-tap bilinear gather of a LOW-resolution 1x1 convolution (4x fewer FLOPs, no
+            # 2x-resolution intermediate), BN (with the conv bias) + PReLU folded into the gather's epilogue
             code = act_code(self.conv[3])
             conv = self.conv[1]
-            if code is not None and x.shape[0] * conv.out_channels <= 65535 and conv.in_channels >= settings.UPCONV_MIN_CIN:
-                # conv3x3(up(x)) = 9-tap bilinear gather of a LOW-resolution 1x1 convolution (4x fewer FLOPs, no
-                # 2x-resolution intermediate), BN (with the conv bias) + PReLU folded into the gather's epilogue
-                Bx, Cin, Hx, Wx = x.shape
-                if settings.USE_FUSED_UPCONV and Cin == 64 and conv.out_channels == 64 and Hx >= 2 and Wx >= 2 and Bx <= 65535:
-                    # 64 -> 64 (last up stage): channel mix on the matrix cores into LDS + gather in ONE kernel, no 9*64-channel tensor
-                    wpk = derived(self, "fused64", (conv.weight,), lambda: ops.upconv_fused64_pack_weight(conv.weight))
-                    scale, shift = folded_bn(self.conv[2], conv.bias)
-                    return ops.upconv_fused64(x, wpk, scale, shift, (Hx * 2, Wx * 2), code[0], code[1])
-                if settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, 9 * conv.out_channels, Hx * Wx):
-                    wpk, c9 = cached_gemm_weight(self, "tap", self._tap_major_weight, (conv.weight,))
-                    z = ops.gemm_bf16x3_map(x, wpk, c9)            # split-bf16 MFMA; reads the packed operand its producer wrote, if any
-                else:
-                    z = ops.wx(self._tap_major_weight(), x.reshape(Bx, Cin, Hx * Wx)).view(Bx, -1, Hx, Wx)   # hipBLASLt GEMM
+            Bx, Cin, Hx, Wx = x.shape
+            if path is FUSED64:
+                # 64 -> 64 (last up stage): channel mix on the matrix cores into LDS + gather in ONE kernel, no 9*64-channel tensor
+                wpk = derived(self, "fused64", (conv.weight,), lambda: ops.upconv_fused64_pack_weight(conv.weight))
                 scale, shift = folded_bn(self.conv[2], conv.bias)
-                # >= 128 channels: the next reader is a GEMM over the map (the p2r fusion's pixel half), so the gather writes its operand
-                return ops.upconv3x3_gather(z, scale, shift, conv.out_channels, (x.shape[2] * 2, x.shape[3] * 2), code[0], code[1],
-                                            packed=settings.USE_MFMA_GEMM and settings.USE_PACKED_PRODUCERS and conv.out_channels % 128 == 0)
+                return ops.upconv_fused64(x, wpk, scale, shift, (Hx * 2, Wx * 2), code[0], code[1])
+            if path is TAP_GEMM_MFMA:
+                wpk, c9 = cached_gemm_weight(self, "tap", self._tap_major_weight, (conv.weight,))
+                z = ops.gemm_bf16x3_map(x, wpk, c9)            # split-bf16 MFMA; reads the packed operand its producer wrote, if any
+            else:
+                z = ops.wx(self._tap_major_weight(), x.reshape(Bx, Cin, Hx * Wx)).view(Bx, -1, Hx, Wx)   # hipBLASLt GEMM
+            scale, shift = folded_bn(self.conv[2], conv.bias)
+            # >= 128 channels: the next reader is a GEMM over the map (the p2r fusion's pixel half), so the gather writes its operand
+            return ops.upconv3x3_gather(z, scale, shift, conv.out_channels, (x.shape[2] * 2, x.shape[3] * 2), code[0], code[1],
+                                        packed=settings.USE_MFMA_GEMM and settings.USE_PACKED_PRODUCERS and conv.out_channels % 128 == 0)
         act = self.conv[3]
         if x.is_cuda and isinstance(act, nn.PReLU) and act.weight.numel() == 1 and x.dtype == torch.float32:
             conv = self.conv[1]

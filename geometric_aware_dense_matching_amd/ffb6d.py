@@ -9,14 +9,77 @@ HIP operators replace the reference's gather chains:
   choose gather (:278-281)          -> ops.gather_nn
 Neighbour indices are consumed as int32 (int64 accepted and narrowed).
 """
+import collections
+import contextlib
+
 import torch
 import torch.nn as nn
 
-from . import ops, settings
-from .cnn import PSPNet, bn_act
+from . import ops, pyramid, settings
+from .cnn import FinalStage, PSPNet, PSPUpsample, bn_act
 from .derived import derived
 from .layers import act_code, cached_gemm_weight, folded_bn, fused_eval, pt_conv2d, rl_conv1d, rl_conv2d
 from .randla import DilatedResBlock
+
+
+# The forms a point-to-pixel (p2r) fusion site takes.  point_major: the layout of the point term the form reads -- [B, n', C] (True),
+# [B, C, n'] (False), no separate term (None); _p2r_point_term produces what this says and the form's executor reads it.
+# pixel_major: the form can write its map as [B, H*W, C].
+_P2RPath = collections.namedtuple("_P2RPath", "name point_major pixel_major")
+MFMA64 = _P2RPath("MFMA64", True, True)         # 64 -> 64 channels on the matrix cores; also the packed output and the fused `final`
+FMA64 = _P2RPath("FMA64", False, True)          # the same shapes in exact fp32 FMAs (settings.USE_MFMA_GEMM off)
+GEMM = _P2RPath("GEMM", False, False)           # every other channel count: a GEMM, then (or with, as its epilogue) the gather
+MODULES = _P2RPath("MODULES", None, False)      # gather, torch.cat and the layer itself: training, and any activation the kernels do not know
+
+
+def _p2r_path(fuse_layer, c, fused):
+    """The form the p2r fusion through `fuse_layer` takes on a c-channel map; fused = fused_eval(...) of the forward.  The ONE place
+    this is decided: the point-term producer, _p2r_fuse, _fused_final_stage and _sparse_final_ok all read the returned value."""
+    if not fused or act_code(getattr(fuse_layer, "activation", None)) is None:
+        return MODULES
+    if c == 64 and fuse_layer.conv.weight.shape[0] == 64:
+        return MFMA64 if settings.USE_MFMA_GEMM else FMA64
+    return GEMM
+
+
+class _Lanes:
+    """The two lanes of FFB6DEmb.forward's stage loop.  The image lane is the current stream; the point lane is side stream 0 when
+    `two`, and otherwise the image lane itself -- then exchange() does nothing and point() scopes nothing."""
+
+    def __init__(self, inputs, two):
+        dev = inputs["rgb"].device
+        self.inputs, self.two = inputs, bool(two)
+        self.image = torch.cuda.current_stream(dev) if two else None
+        self.side = ops.side_stream(dev, 0) if two else None
+
+    def point(self):
+        """with lanes.point(): the body is enqueued on the point lane."""
+        return torch.cuda.stream(self.side) if self.two else contextlib.nullcontext()
+
+    def exchange(self, to_point=(), to_image=(), ready=False):
+        """Hand `to_point` (made on the image lane) to the point lane and `to_image` the other way.  An event is recorded on each
+        producing lane BEFORE either lane waits, so neither event carries the other lane's work; then each consuming lane waits for
+        its event, and every tensor that crosses is recorded on the stream that did not allocate it.  ready: both lanes also wait
+        for the whole neighbour pyramid (pyramid.wait_ready) before their first use of the indices a RandLA block does not read."""
+        if not self.two:
+            return
+        ev_image = self.image.record_event() if to_point else None
+        ev_point = self.side.record_event() if to_image else None
+        if to_point:
+            self.side.wait_event(ev_image)
+            self._keep(to_point, self.side)
+        if ready:
+            pyramid.wait_ready(self.inputs, self.side)
+            pyramid.wait_ready(self.inputs, self.image)
+        if to_image:
+            self.image.wait_event(ev_point)
+            self._keep(to_image, self.image)
+
+    @staticmethod
+    def _keep(tensors, lane):
+        for t in tensors:
+            if torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(lane)
 
 
 class FFB6DEmb(nn.Module):
@@ -113,103 +176,96 @@ class FFB6DEmb(nn.Module):
         """wa transposed ([ci][co], contiguous), cached beside the split weights."""
         return derived(layer, "w%s_t" % tag, (wa,), lambda: wa.t().contiguous())
 
-    def _p2r_point_term(self, pre_layer, fuse_layer, c, p_emb0):
-        """The point half of the p2r fusion, W_b . pre(p_emb0), at the points -- exactly what _p2r_fuse computes first (same branch
-        conditions); the two-stream pipeline forms it on the POINT stream so that the image stream only waits for the finished term.
-        None when _p2r_fuse would not take a path with a separate point term."""
-        if not fused_eval(p_emb0, self) or act_code(getattr(fuse_layer, "activation", None)) is None or not settings.USE_POINTWISE:
+    def _p2r_point_term(self, path, pre_layer, fuse_layer, split, p_emb0):
+        """The point half of the p2r fusion, W_b . pre(p_emb0), at the points (a 1x1 conv commutes with the gather), in the layout
+        `path` reads: [B, n', 64] where path.point_major, else [B, Cout, n']; None for MODULES, which has no separate term.  The one
+        producer of the term: the stage loop forms it on the point lane, so the image lane only waits for the finished term.
+        split = _split_fuse_weight(fuse_layer, c), which the stage loop looks up once for this and for _p2r_fuse."""
+        if path is MODULES:
             return None
-        bs = p_emb0.shape[0]
-        wa, wb = self._split_fuse_weight(fuse_layer, c)
-        pp = pre_layer(p_emb0).reshape(bs, wb.shape[1], -1)
-        if c == 64 and wa.shape[0] == 64 and settings.USE_MFMA_GEMM:
-            return ops.pointwise([pp], self._fuse_weight_t(fuse_layer, wb, "b"), point_major=True)       # [B, n', 64]
-        return ops.pointwise([pp], self._fuse_weight_t(fuse_layer, wb, "b"))                             # [B, Cout, n']
+        wb = split[1]
+        pp = pre_layer(p_emb0).reshape(p_emb0.shape[0], wb.shape[1], -1)
+        if settings.USE_POINTWISE:
+            return ops.pointwise([pp], self._fuse_weight_t(fuse_layer, wb, "b"), point_major=path.point_major)
+        return torch.matmul(pp.transpose(1, 2), wb.t()) if path.point_major else ops.wx(wb, pp)
 
-    def _p2r_fuse(self, pre_layer, fuse_layer, rgb_emb0, p_emb0, idx, pixel_major=False, point_term=None, want_packed=False,
+    def _p2r_fuse(self, path, pre_layer, fuse_layer, split, rgb_emb0, p_emb0, term, idx, pixel_major=False, want_packed=False,
                   packed_only=False, final=None):
-        """fuse(cat(rgb_emb0, nearest_interp(pre(p_emb0)))) (ffb6d.py:216-222,252-258).  Eval: the point half of the
-        1x1 fuse convolution runs at the points (a 1x1 conv commutes with the gather), the pixel half is a GEMM with half
-        the K, and gather + add + BN + ReLU is one HIP launch; no concat, no full-resolution point features.
+        """fuse(cat(rgb_emb0, nearest_interp(pre(p_emb0)))) (ffb6d.py:216-222,252-258) in the form `path` names (_p2r_path), with
+        `term` from _p2r_point_term(path, ...) and the same `split` (W_a, W_b).  Eval: the pixel half of the 1x1 fuse convolution is a
+        GEMM with half the K, and gather + add + BN + ReLU is one HIP launch; no concat, no full-resolution point features.
         packed_only (the caller's promise, _packed_only_consumer): the next image stage reads the packed operand and nothing else, so
-        the generic path returns the ops.PackedAct alone and the fp32 map is never stored.  final (_fused_final_stage): the FinalStage
-        that is the fused map's only reader; the 64-channel path then returns final(fused map) from one launch, the map never stored."""
+        GEMM returns the ops.PackedAct alone and the fp32 map is never stored.  final (_fused_final_stage): the FinalStage that is the
+        fused map's only reader; MFMA64 then returns final(fused map) from one launch, the map never stored."""
+        if (pixel_major and not path.pixel_major) or (final is not None and path is not MFMA64):
+            raise RuntimeError("pixel-major output is the 64-channel kernels', the fused `final` MFMA64's, and this fusion takes %s; "
+                               "_sparse_final_ok() and _fused_final_stage() guard the caller" % path.name)
+        if path is MODULES:
+            bs, _, hr, wr = rgb_emb0.shape
+            p2r_emb = self.nearest_interpolation(pre_layer(p_emb0), idx).view(bs, -1, hr, wr)
+            return fuse_layer(torch.cat((rgb_emb0, p2r_emb), dim=1))
+        code = act_code(getattr(fuse_layer, "activation", None))
+        if path is MFMA64:
+            return self._fuse_mfma64(fuse_layer, split[0], rgb_emb0, term, idx, code, pixel_major, want_packed, final)
+        if path is FMA64:
+            return self._fuse_fma64(fuse_layer, split[0], rgb_emb0, term, idx, code, pixel_major)
+        return self._fuse_gemm(fuse_layer, split[0], rgb_emb0, term, idx, code, packed_only)
+
+    def _fuse_mfma64(self, fuse_layer, wa, rgb_emb0, t_pm, idx, code, pixel_major, want_packed, final):
+        """K = 64: channel mix on the matrix cores (split-bf16 x3) + gather + add + BN + ReLU in ONE pass over the pixels, bound by the
+        map's read + write; the point term is point-major ([B, n', 64]: one contiguous row per gathered point)."""
         bs, c, hr, wr = rgb_emb0.shape
-        if fused_eval(rgb_emb0, self):
-            code = act_code(getattr(fuse_layer, "activation", None))
-            if code is not None:
-                wa, wb = self._split_fuse_weight(fuse_layer, c)
-                if c == 64 and wa.shape[0] == 64 and settings.USE_MFMA_GEMM:
-                    # K = 64: channel mix on the matrix cores (split-bf16 x3) + gather + add + BN + ReLU in ONE pass over the pixels,
-                    # bound by the map's read + write; the point term is formed point-major ([B, n', 64]: one contiguous row per
-                    # gathered point) by the same library GEMM with its operands swapped
-                    scale, shift = folded_bn(fuse_layer.normlayer.bn)
-                    if point_term is not None:
-                        t_pm = point_term
-                    else:
-                        pp = pre_layer(p_emb0).reshape(bs, wb.shape[1], -1)
-                        if settings.USE_POINTWISE:
-                            t_pm = ops.pointwise([pp], self._fuse_weight_t(fuse_layer, wb, "b"), point_major=True)   # [B, n', 64]
-                        else:
-                            t_pm = torch.matmul(pp.transpose(1, 2), wb.t())
-                    wa_pk = derived(fuse_layer, "wa_pk", (wa,), lambda: ops.pack_rows64(wa))
-                    if final is not None:
-                        fconv = final[0]
-                        return ops.conv64_gather_add_final(rgb_emb0.reshape(bs, c, hr * wr), wa_pk, t_pm, idx.reshape(bs, -1), scale, shift,
-                                                           code[0], code[1], fconv.weight, fconv.bias).view(bs, -1, hr, wr)
-                    y = ops.conv64_gather_add_act_mfma(rgb_emb0.reshape(bs, c, hr * wr), wa_pk, t_pm, idx.reshape(bs, -1), scale, shift,
-                                                       code[0], code[1], pixel_major=pixel_major, t_point_major=True,
-                                                       hw=(hr, wr) if (want_packed and settings.USE_PACKED_PRODUCERS and not pixel_major) else None)
-                    if pixel_major:
-                        return y
-                    out = y.view(bs, -1, hr, wr)
-                    if getattr(y, "_gdm_packed", None) is not None:
-                        out._gdm_packed = y._gdm_packed         # the next stage's first convolution reads this: no pack launch
-                    return out
-                if point_term is not None:
-                    t = point_term
-                else:
-                    pp = pre_layer(p_emb0).reshape(bs, wb.shape[1], -1)
-                    if settings.USE_POINTWISE:
-                        t = ops.pointwise([pp], self._fuse_weight_t(fuse_layer, wb, "b"))   # [B,Cout,n'] at the points
-                    else:
-                        t = ops.wx(wb, pp)
-                if c == 64 and wa.shape[0] == 64:
-                    # K = 64: GEMM + gather + add + BN + ReLU in ONE pass over the pixels (exact fp32 FMAs)
-                    scale, shift = folded_bn(fuse_layer.normlayer.bn)
-                    y = ops.conv1x1_gather_add_act(rgb_emb0.reshape(bs, c, hr * wr), self._fuse_weight_t(fuse_layer, wa), t,
-                                                   idx.reshape(bs, -1), scale, shift, code[0], code[1], pixel_major=pixel_major)
-                    return y if pixel_major else y.view(bs, -1, hr, wr)  # pixel-major: [B, H*W, 64] for _final_at_choose
-                if pixel_major:
-                    raise RuntimeError("pixel-major fusion output is the 64-channel kernel's; _sparse_final_ok() guards the caller")
-                if settings.USE_MFMA_GEMM and ops.gemm_supported(c, wa.shape[0], hr * wr):
-                    wpk, co = cached_gemm_weight(fuse_layer, "wa", wa, (fuse_layer.conv.weight,))
-                    only = packed_only and ops.packed_out_supported(bs, co, hr, wr)
-                    if ops.conv1x1_gather_add_supported(rgb_emb0, co, code[0], f32_out=not only):
-                        # the GEMM runs inside gather_add_affine_act's launch (ops.conv1x1_packed_gather_add_act): gather, add, BN and
-                        # activation are its epilogue, the fp32 map between the two is never written
-                        x = ops.GemmMap(rgb_emb0, wpk, co)
-                    else:
-                        x = ops.gemm_bf16x3_map(rgb_emb0, wpk, co).view(bs, co, hr * wr)   # split-bf16 MFMA; reads the stage's packed output
-                else:
-                    x = ops.wx(wa, rgb_emb0.reshape(bs, c, hr * wr))                    # [B,Cout,HW]
-                scale, shift = folded_bn(fuse_layer.normlayer.bn)
-                if packed_only and ops.packed_out_supported(bs, x.shape[1], hr, wr):
-                    return ops.gather_add_affine_act(x, t, idx.reshape(bs, -1), scale, shift, code[0], code[1], hw=(hr, wr), f32_out=False)
-                y, ypk = ops.gather_add_affine_act(x, t, idx.reshape(bs, -1), scale, shift, code[0], code[1], hw=(hr, wr))
-                y = y.view(bs, -1, hr, wr)
-                if ypk is not None:
-                    y._gdm_packed = ypk             # the next image stage's first convolution / GEMM reads this: no pack launch
-                return y
+        scale, shift = folded_bn(fuse_layer.normlayer.bn)
+        wa_pk = derived(fuse_layer, "wa_pk", (wa,), lambda: ops.pack_rows64(wa))
+        if final is not None:
+            fconv = final[0]
+            return ops.conv64_gather_add_final(rgb_emb0.reshape(bs, c, hr * wr), wa_pk, t_pm, idx.reshape(bs, -1), scale, shift,
+                                               code[0], code[1], fconv.weight, fconv.bias).view(bs, -1, hr, wr)
+        y = ops.conv64_gather_add_act_mfma(rgb_emb0.reshape(bs, c, hr * wr), wa_pk, t_pm, idx.reshape(bs, -1), scale, shift,
+                                           code[0], code[1], pixel_major=pixel_major, t_point_major=MFMA64.point_major,
+                                           hw=(hr, wr) if (want_packed and settings.USE_PACKED_PRODUCERS and not pixel_major) else None)
         if pixel_major:
-            raise RuntimeError("pixel-major fusion output is the eval kernel's; _sparse_final_ok() guards the caller")
-        p2r_emb = self.nearest_interpolation(pre_layer(p_emb0), idx).view(bs, -1, hr, wr)
-        return fuse_layer(torch.cat((rgb_emb0, p2r_emb), dim=1))
+            return y                                    # [B, H*W, 64] for _final_at_choose
+        out = y.view(bs, -1, hr, wr)
+        if getattr(y, "_gdm_packed", None) is not None:
+            out._gdm_packed = y._gdm_packed             # the next stage's first convolution reads this: no pack launch
+        return out
+
+    def _fuse_fma64(self, fuse_layer, wa, rgb_emb0, t, idx, code, pixel_major):
+        """K = 64: GEMM + gather + add + BN + ReLU in ONE pass over the pixels (exact fp32 FMAs); channel-major point term."""
+        bs, c, hr, wr = rgb_emb0.shape
+        scale, shift = folded_bn(fuse_layer.normlayer.bn)
+        y = ops.conv1x1_gather_add_act(rgb_emb0.reshape(bs, c, hr * wr), self._fuse_weight_t(fuse_layer, wa), t,
+                                       idx.reshape(bs, -1), scale, shift, code[0], code[1], pixel_major=pixel_major)
+        return y if pixel_major else y.view(bs, -1, hr, wr)  # pixel-major: [B, H*W, 64] for _final_at_choose
+
+    def _fuse_gemm(self, fuse_layer, wa, rgb_emb0, t, idx, code, packed_only):
+        """Every other channel count: the pixel half as a GEMM, then gather + add + BN + activation (channel-major point term).  Which
+        GEMM depends on the operand the map carries at run time, so that choice is made here."""
+        bs, c, hr, wr = rgb_emb0.shape
+        if settings.USE_MFMA_GEMM and ops.gemm_supported(c, wa.shape[0], hr * wr):
+            wpk, co = cached_gemm_weight(fuse_layer, "wa", wa, (fuse_layer.conv.weight,))
+            only = packed_only and ops.packed_out_supported(bs, co, hr, wr)
+            if ops.conv1x1_gather_add_supported(rgb_emb0, co, code[0], f32_out=not only):
+                # the GEMM runs inside gather_add_affine_act's launch (ops.conv1x1_packed_gather_add_act): gather, add, BN and
+                # activation are its epilogue, the fp32 map between the two is never written
+                x = ops.GemmMap(rgb_emb0, wpk, co)
+            else:
+                x = ops.gemm_bf16x3_map(rgb_emb0, wpk, co).view(bs, co, hr * wr)   # split-bf16 MFMA; reads the stage's packed output
+        else:
+            x = ops.wx(wa, rgb_emb0.reshape(bs, c, hr * wr))                    # [B,Cout,HW]
+        scale, shift = folded_bn(fuse_layer.normlayer.bn)
+        if packed_only and ops.packed_out_supported(bs, x.shape[1], hr, wr):
+            return ops.gather_add_affine_act(x, t, idx.reshape(bs, -1), scale, shift, code[0], code[1], hw=(hr, wr), f32_out=False)
+        y, ypk = ops.gather_add_affine_act(x, t, idx.reshape(bs, -1), scale, shift, code[0], code[1], hw=(hr, wr))
+        y = y.view(bs, -1, hr, wr)
+        if ypk is not None:
+            y._gdm_packed = ypk             # the next image stage's first convolution / GEMM reads this: no pack launch
+        return y
 
     def _packed_only_consumer(self, stage, shape):
         """True when image stage `stage`, given a GPU map of this shape, reads its packed operand and nothing else: Sequential(PSPUpsample,
         dropout) in eval (the dropout is the identity) whose up-sampling stage takes its tap GEMM on the packed operand."""
-        from .cnn import PSPUpsample
         return (isinstance(stage, nn.Sequential) and len(stage) == 2 and isinstance(stage[0], PSPUpsample)
                 and isinstance(stage[1], (nn.Dropout, nn.Dropout2d)) and not stage[1].training and stage[0].reads_packed_only(shape))
 
@@ -218,17 +274,11 @@ class FFB6DEmb(nn.Module):
         """stage(x); a packed-only map (see _packed_only_consumer) goes straight to the up-sampling stage, past the identity dropout."""
         return stage[0](x) if isinstance(x, ops.PackedAct) else stage(x)
 
-    def _fused_final_stage(self, i_up, rgb_emb0, pixel_major):
-        """The FinalStage that _p2r_fuse of up stage i_up may apply in the same launch, or None: the fusion takes the 64-channel MFMA
-        kernel (the conditions of _p2r_fuse) in NCHW form, and the next image stage is `final` alone, 64 -> 64, so the fused map has
-        no other reader (the r2p gather of that stage reads rgb_emb0, the following stage reads final's output)."""
-        from .cnn import FinalStage
-        if pixel_major or i_up + 1 >= len(self.rndla_up_stages) - 1 or not fused_eval(rgb_emb0, self):
-            return None
-        fuse = self.up_fuse_p2r_fuse_layers[i_up]
-        w = fuse.conv.weight
-        if not (act_code(getattr(fuse, "activation", None)) is not None and settings.USE_MFMA_GEMM and rgb_emb0.shape[1] == 64
-                and w.shape[0] == 64 and w.shape[1] == 128 and rgb_emb0.shape[0] <= 65535):
+    def _fused_final_stage(self, i_up, path, batch, pixel_major):
+        """The FinalStage that _p2r_fuse of up stage i_up may apply in the same launch, or None: the fusion is MFMA64 in NCHW form, and
+        the next image stage is `final` alone, 64 -> 64, so the fused map has no other reader (the r2p gather of that stage reads
+        rgb_emb0, the following stage reads final's output)."""
+        if pixel_major or i_up + 1 >= len(self.rndla_up_stages) - 1 or path is not MFMA64 or batch > 65535:
             return None
         nxt = self.cnn_up_stages[i_up + 1]
         if not (isinstance(nxt, nn.Sequential) and len(nxt) == 1 and isinstance(nxt[0], FinalStage) and not nxt[0].training):
@@ -240,8 +290,18 @@ class FFB6DEmb(nn.Module):
 
     def forward(self, inputs, end_points=None, parts=False):
         """-> f32[B,128,N] (ffb6d.py:285: cat of the 64 image channels at the chosen pixels and the 64 point channels); parts=True
-        returns the two halves un-concatenated, for a consumer that reads them in place (the fused per-point heads)."""
-        if fused_eval(inputs["rgb"], self):
+        returns the two halves un-concatenated, for a consumer that reads them in place (the fused per-point heads).
+
+        The seven stages run against two lanes (_Lanes): the IMAGE lane (the current stream) runs the trunk / up stages and the
+        point-to-pixel fusions, the POINT lane the RandLA blocks, the decoder layers, the point terms and the pixel-to-point fusions.
+        Inference with settings.USE_SIDE_STREAMS and "point" in SIDE_PARTS puts the point lane on side stream 0: per stage each stream
+        waits ONCE for the other's product (the point stream for the image stage's map `rgb_emb0`, read by the r2p gather; the image
+        stream for `p_emb0` and the point term, read by the p2r fusion) and otherwise they run ahead independently -- the r2p chain of
+        stage i and the RandLA block of stage i + 1 sit in the shadow of the convolutions of stage i + 1.  Everything else (training
+        too) runs the same loop with both lanes on the current stream: the same kernels on the same operands in the same enqueue
+        order, bit-identical (tests/test_gpu_headline.py::test_timed_configuration_bit_exact_across_launch_forms)."""
+        fused = fused_eval(inputs["rgb"], self)
+        if fused:
             pre = self.cnn_pre_stages                                         # conv1, bn1, relu, maxpool
             s0, b0 = folded_bn(pre[1])
             mp = pre[3]
@@ -262,88 +322,76 @@ class FFB6DEmb(nn.Module):
         else:
             pre = self.cnn_pre_stages
             rgb_emb = pre[3](bn_act(pre[1], pre[0](inputs["rgb"]), pre[2]))
-        # Inference, settings.USE_SIDE_STREAMS (off by default): the point branch of every encoder stage (RandLA block + pooling) is
-        # forked onto side stream 0 beside the image branch's convolutions; they meet at the fusion.  An overlapped neighbour-pyramid
-        # build (pyramid.build_pyramid(..., overlap=True)) is waited for by EACH consuming stream before its first index use.
-        from . import pyramid as _pyr
-        overlap = settings.USE_SIDE_STREAMS and "point" in settings.SIDE_PARTS and fused_eval(inputs["rgb"], self)
-        if overlap and settings.USE_TWO_STREAM_PIPELINE:
-            return self._forward_two_streams(inputs, rgb_emb, parts)
-        if not overlap:
-            _pyr.wait_ready(inputs)
-        p_emb, f_pc0 = self._stem_and_mlp1(inputs["cld_rgb_nrm"])             # [B,8,N,1] (+ the first block's mlp1 of it)
+        # An overlapped neighbour-pyramid build (pyramid.build_pyramid(..., overlap=True)) is waited for by EACH consuming stream before
+        # its first index use: here by the point lane for the cloud's searches (all of it when there is one lane), the rest in stage 0
+        lanes = _Lanes(inputs, fused and settings.USE_SIDE_STREAMS and "point" in settings.SIDE_PARTS)
+        lanes.exchange(to_point=(inputs["cld_rgb_nrm"],))
+        with lanes.point():
+            pyramid.wait_ready(inputs, cloud_only=lanes.two)
+            p_emb, f_pc0 = self._stem_and_mlp1(inputs["cld_rgb_nrm"])         # [B,8,N,1] (+ the first block's mlp1 of it)
 
         ds_emb = []
         for i_ds in range(4):
-            if overlap:
-                xyz_i, nei_i, sub_i = inputs["cld_xyz%d" % i_ds], inputs["cld_nei_idx%d" % i_ds], inputs["cld_sub_idx%d" % i_ds]
-                with ops.fork(inputs["rgb"].device, 0) as f:
-                    if i_ds == 0:
-                        _pyr.wait_ready(inputs)                               # the side stream's own wait
-                    f.use(p_emb, xyz_i, nei_i, sub_i)
-                    f_encoder_i = self.rndla_ds_stages[i_ds](p_emb, xyz_i, nei_i, f_pc=f_pc0 if i_ds == 0 else None)
-                    p_emb0 = self.random_sample(f_encoder_i, sub_i)
-                rgb_emb0 = self.cnn_ds_stages[i_ds](rgb_emb)
-                if i_ds == 0:
-                    _pyr.wait_ready(inputs)                                   # the main stream's own wait, before its first index use
-                f.join(f_encoder_i, p_emb0)
-            else:
-                rgb_emb0 = self.cnn_ds_stages[i_ds](rgb_emb)
+            pre, fuse = self.ds_fuse_p2r_pre_layers[i_ds], self.ds_fuse_p2r_fuse_layers[i_ds]
+            rgb_emb0 = self.cnn_ds_stages[i_ds](rgb_emb)
+            bs, c, hr, wr = rgb_emb0.size()
+            path = _p2r_path(fuse, c, fused)
+            split = self._split_fuse_weight(fuse, c) if path is not MODULES else None
+            with lanes.point():
                 f_encoder_i = self.rndla_ds_stages[i_ds](p_emb, inputs["cld_xyz%d" % i_ds], inputs["cld_nei_idx%d" % i_ds],
                                                          f_pc=f_pc0 if i_ds == 0 else None)
                 p_emb0 = self.random_sample(f_encoder_i, inputs["cld_sub_idx%d" % i_ds])
-            bs, c, hr, wr = rgb_emb0.size()
-            if i_ds == 0:
-                ds_emb.append(f_encoder_i)
-
-            rgb_emb = self._p2r_fuse(self.ds_fuse_p2r_pre_layers[i_ds], self.ds_fuse_p2r_fuse_layers[i_ds], rgb_emb0, p_emb0,
-                                     inputs["p2r_ds_nei_idx%d" % i_ds], want_packed=True,
+                term = self._p2r_point_term(path, pre, fuse, split, p_emb0)
+            lanes.exchange(to_point=(rgb_emb0,), to_image=(p_emb0, term), ready=i_ds == 0)
+            with lanes.point():
+                r2p_emb = self.random_sample(rgb_emb0.reshape(bs, c, hr * wr), inputs["r2p_ds_nei_idx%d" % i_ds])
+                r2p_emb = self.ds_fuse_r2p_pre_layers[i_ds](r2p_emb)
+                p_emb = self.ds_fuse_r2p_fuse_layers[i_ds].forward_segs([p_emb0, r2p_emb])       # over cat(p_emb0, r2p_emb), never formed
+            ds_emb += [f_encoder_i, p_emb] if i_ds == 0 else [p_emb]
+            rgb_emb = self._p2r_fuse(path, pre, fuse, split, rgb_emb0, p_emb0, term, inputs["p2r_ds_nei_idx%d" % i_ds], want_packed=True,
                                      packed_only=i_ds == 3 and self._packed_only_consumer(self.cnn_up_stages[0], rgb_emb0.shape))
 
-            r2p_emb = self.random_sample(rgb_emb0.reshape(bs, c, hr * wr), inputs["r2p_ds_nei_idx%d" % i_ds])
-            r2p_emb = self.ds_fuse_r2p_pre_layers[i_ds](r2p_emb)
-            p_emb = self.ds_fuse_r2p_fuse_layers[i_ds].forward_segs([p_emb0, r2p_emb])       # over cat(p_emb0, r2p_emb), never formed
-            ds_emb.append(p_emb)
-
         n_up = len(self.rndla_up_stages)
-        sparse_final = self._sparse_final_ok(inputs["rgb"])
-        final_done = False
+        pm = final_done = False
         for i_up in range(n_up - 1):
+            pre, fuse = self.up_fuse_p2r_pre_layers[i_up], self.up_fuse_p2r_fuse_layers[i_up]
             rgb_emb0 = rgb_emb if final_done else self._image_stage(self.cnn_up_stages[i_up], rgb_emb)   # `final` ran inside the last fusion
             bs, c, hr, wr = rgb_emb0.size()
-            pm = sparse_final and i_up == n_up - 2
-            final = self._fused_final_stage(i_up, rgb_emb0, pm)
+            path = _p2r_path(fuse, c, fused)
+            split = self._split_fuse_weight(fuse, c) if path is not MODULES else None
+            pm = i_up == n_up - 2 and self._sparse_final_ok(path, bs)         # the last fusion writes pixel-major for _final_at_choose
+            final = self._fused_final_stage(i_up, path, bs, pm)
             final_done = final is not None
-
-            # decoder layer over cat(skip, nearest_interpolation(p_emb)): the interpolation is the second segment's index
-            p_emb0 = self.rndla_up_stages[i_up].forward_segs([ds_emb[-i_up - 2], (p_emb, inputs["cld_interp_idx%d" % (n_up - i_up - 1)])])
-
-            rgb_emb = self._p2r_fuse(self.up_fuse_p2r_pre_layers[i_up], self.up_fuse_p2r_fuse_layers[i_up], rgb_emb0, p_emb0,
-                                     inputs["p2r_up_nei_idx%d" % i_up], pixel_major=pm, final=final,
+            with lanes.point():
+                # decoder layer over cat(skip, nearest_interpolation(p_emb)): the interpolation is the second segment's index
+                p_emb0 = self.rndla_up_stages[i_up].forward_segs([ds_emb[-i_up - 2], (p_emb, inputs["cld_interp_idx%d" % (n_up - i_up - 1)])])
+                term = self._p2r_point_term(path, pre, fuse, split, p_emb0)
+            lanes.exchange(to_point=(rgb_emb0,), to_image=(p_emb0, term))
+            with lanes.point():
+                r2p_emb = self.random_sample(rgb_emb0.reshape(bs, c, hr * wr), inputs["r2p_up_nei_idx%d" % i_up])
+                r2p_emb = self.up_fuse_r2p_pre_layers[i_up](r2p_emb)
+                p_emb = self.up_fuse_r2p_fuse_layers[i_up].forward_segs([p_emb0, r2p_emb])
+            rgb_emb = self._p2r_fuse(path, pre, fuse, split, rgb_emb0, p_emb0, term, inputs["p2r_up_nei_idx%d" % i_up], pixel_major=pm, final=final,
                                      packed_only=i_up + 1 < n_up - 1 and self._packed_only_consumer(self.cnn_up_stages[i_up + 1], rgb_emb0.shape))
 
-            r2p_emb = self.random_sample(rgb_emb0.reshape(bs, c, hr * wr), inputs["r2p_up_nei_idx%d" % i_up])
-            r2p_emb = self.up_fuse_r2p_pre_layers[i_up](r2p_emb)
-            p_emb = self.up_fuse_r2p_fuse_layers[i_up].forward_segs([p_emb0, r2p_emb])
-
-        p_emb = self.rndla_up_stages[n_up - 1].forward_segs([ds_emb[0], (p_emb, inputs["cld_interp_idx0"])]).squeeze(-1)
-        if sparse_final:
+        with lanes.point():
+            p_emb = self.rndla_up_stages[n_up - 1].forward_segs([ds_emb[0], (p_emb, inputs["cld_interp_idx0"])]).squeeze(-1)
+        last = self.cnn_up_stages[n_up - 1]
+        if pm:
             # the last stage (up_3 + final) is a per-pixel function of a 3x3 neighbourhood and only the N `choose` pixels of its
             # full-resolution output are kept (reference ffb6d.py:266-285): evaluate it there, on the pixel-major fused map
             rgb_emb_c = self._final_at_choose(rgb_emb, (hr, wr), inputs["choose"])
-        elif self._gathered_final_ok():
-            # training (and unfused inference): up_3 needs the whole map (its BatchNorm statistics), but FinalStage -- 1x1 convolution +
-            # LogSoftmax over channels -- is a per-pixel function, so it commutes with the `choose` gather (reference ffb6d.py:266-285
-            # applies it to all H*W pixels and keeps N): gather first, and forward and backward of the stage touch N pixels, not H*W
-            last = self.cnn_up_stages[n_up - 1]
-            rgb_emb = last[0](rgb_emb)
-            bs, di, _, _ = rgb_emb.size()
-            rgb_emb_c = ops.gather_nn(rgb_emb.view(bs, di, -1), inputs["choose"].reshape(bs, -1, 1))
-            rgb_emb_c = last[1](rgb_emb_c.unsqueeze(-1)).squeeze(-1)
         else:
-            rgb_emb = self.cnn_up_stages[n_up - 1](rgb_emb)
+            # up_3 needs the whole map (in training: its BatchNorm statistics), but FinalStage -- 1x1 convolution + LogSoftmax over
+            # channels -- is a per-pixel function, so it commutes with the `choose` gather (reference ffb6d.py:266-285 applies it to all
+            # H*W pixels and keeps N): gathered first, forward and backward of the stage touch N pixels, not H*W
+            gathered = self._gathered_final_ok()
+            rgb_emb = last[0](rgb_emb) if gathered else last(rgb_emb)
             bs, di, _, _ = rgb_emb.size()
             rgb_emb_c = ops.gather_nn(rgb_emb.view(bs, di, -1), inputs["choose"].reshape(bs, -1, 1))
+            if gathered:
+                rgb_emb_c = last[1](rgb_emb_c.unsqueeze(-1)).squeeze(-1)
+        lanes.exchange(to_image=(p_emb,))
         if parts:
             return rgb_emb_c, p_emb
         return torch.cat([rgb_emb_c, p_emb], dim=1)
@@ -360,130 +408,30 @@ class FFB6DEmb(nn.Module):
                 return y0.unsqueeze(3), y1.unsqueeze(3)
         return self.rndla_pre_stages(x).unsqueeze(3), None
 
-    def _forward_two_streams(self, inputs, rgb_emb, parts):
-        """The inference forward as a two-stream pipeline (settings.USE_SIDE_STREAMS): the IMAGE stream (the current one) runs the
-        trunk / up stages and the point-to-pixel fusions, the POINT stream (side stream 0) the RandLA blocks, the decoder layers and the
-        pixel-to-point fusions.  Per stage each stream waits ONCE for the other's product (an event): the point stream for the image
-        stage's map (`rgb_emb0`, read by the r2p gather), the image stream for the pooled / decoded point features (`p_emb0`, read by
-        the p2r fusion); otherwise they run ahead independently -- the r2p chain of stage i and the RandLA block of stage i + 1 sit in
-        the shadow of the convolutions of stage i + 1.  Same kernels on the same operands as the single-stream order: bit-identical
-        (tests/test_gpu_headline.py::test_timed_configuration_bit_exact_across_launch_forms).  Every tensor that crosses is recorded
-        on the stream that did not allocate it."""
-        from . import pyramid as _pyr
-        dev = inputs["rgb"].device
-        M = torch.cuda.current_stream(dev)
-        S = ops.side_stream(dev, 0)
-
-        def to(stream, *ts):
-            for t in ts:
-                if torch.is_tensor(t) and t.is_cuda:
-                    t.record_stream(stream)
-
-        def event(stream):
-            e = torch.cuda.Event()
-            e.record(stream)
-            return e
-
-        S.wait_stream(M)
-        to(S, inputs["cld_rgb_nrm"])
-        with torch.cuda.stream(S):
-            _pyr.wait_ready(inputs, cloud_only=True)                          # the point stream's own wait: the cloud's searches only
-            p_emb, f_pc0 = self._stem_and_mlp1(inputs["cld_rgb_nrm"])         # [B,8,N,1] (+ the first block's mlp1 of it)
-        ds_emb = []
-        for i_ds in range(4):
-            rgb_emb0 = self.cnn_ds_stages[i_ds](rgb_emb)
-            ev_rgb0 = event(M)
-            bs, c, hr, wr = rgb_emb0.size()
-            with torch.cuda.stream(S):
-                f_encoder_i = self.rndla_ds_stages[i_ds](p_emb, inputs["cld_xyz%d" % i_ds], inputs["cld_nei_idx%d" % i_ds],
-                                                         f_pc=f_pc0 if i_ds == 0 else None)
-                p_emb0 = self.random_sample(f_encoder_i, inputs["cld_sub_idx%d" % i_ds])
-                pt = self._p2r_point_term(self.ds_fuse_p2r_pre_layers[i_ds], self.ds_fuse_p2r_fuse_layers[i_ds], c, p_emb0)
-                ev_p0 = event(S)
-                S.wait_event(ev_rgb0)
-                to(S, rgb_emb0)
-                if i_ds == 0:
-                    _pyr.wait_ready(inputs)                                   # the rest of the pyramid: the r2p / interpolation indices
-                r2p_emb = self.random_sample(rgb_emb0.reshape(bs, c, hr * wr), inputs["r2p_ds_nei_idx%d" % i_ds])
-                r2p_emb = self.ds_fuse_r2p_pre_layers[i_ds](r2p_emb)
-                p_emb = self.ds_fuse_r2p_fuse_layers[i_ds].forward_segs([p_emb0, r2p_emb])
-            if i_ds == 0:
-                ds_emb.append(f_encoder_i)
-            ds_emb.append(p_emb)
-            if i_ds == 0:
-                _pyr.wait_ready(inputs)                                       # the image stream's own wait: its first index use is this fusion
-            M.wait_event(ev_p0)
-            to(M, p_emb0, pt)
-            rgb_emb = self._p2r_fuse(self.ds_fuse_p2r_pre_layers[i_ds], self.ds_fuse_p2r_fuse_layers[i_ds], rgb_emb0, p_emb0,
-                                     inputs["p2r_ds_nei_idx%d" % i_ds], point_term=pt, want_packed=True,
-                                     packed_only=i_ds == 3 and self._packed_only_consumer(self.cnn_up_stages[0], rgb_emb0.shape))
-        n_up = len(self.rndla_up_stages)
-        sparse_final = self._sparse_final_ok(inputs["rgb"])
-        final_done = False
-        for i_up in range(n_up - 1):
-            rgb_emb0 = rgb_emb if final_done else self._image_stage(self.cnn_up_stages[i_up], rgb_emb)   # `final` ran inside the last fusion
-            ev_rgb0 = event(M)
-            bs, c, hr, wr = rgb_emb0.size()
-            pm = sparse_final and i_up == n_up - 2
-            final = self._fused_final_stage(i_up, rgb_emb0, pm)
-            final_done = final is not None
-            with torch.cuda.stream(S):
-                p_emb0 = self.rndla_up_stages[i_up].forward_segs([ds_emb[-i_up - 2], (p_emb, inputs["cld_interp_idx%d" % (n_up - i_up - 1)])])
-                pt = self._p2r_point_term(self.up_fuse_p2r_pre_layers[i_up], self.up_fuse_p2r_fuse_layers[i_up], c, p_emb0)
-                ev_p0 = event(S)
-                S.wait_event(ev_rgb0)
-                to(S, rgb_emb0)
-                r2p_emb = self.random_sample(rgb_emb0.reshape(bs, c, hr * wr), inputs["r2p_up_nei_idx%d" % i_up])
-                r2p_emb = self.up_fuse_r2p_pre_layers[i_up](r2p_emb)
-                p_emb = self.up_fuse_r2p_fuse_layers[i_up].forward_segs([p_emb0, r2p_emb])
-            M.wait_event(ev_p0)
-            to(M, p_emb0, pt)
-            rgb_emb = self._p2r_fuse(self.up_fuse_p2r_pre_layers[i_up], self.up_fuse_p2r_fuse_layers[i_up], rgb_emb0, p_emb0,
-                                     inputs["p2r_up_nei_idx%d" % i_up], pixel_major=pm, point_term=pt, final=final,
-                                     packed_only=i_up + 1 < n_up - 1 and self._packed_only_consumer(self.cnn_up_stages[i_up + 1], rgb_emb0.shape))
-        with torch.cuda.stream(S):
-            p_emb = self.rndla_up_stages[n_up - 1].forward_segs([ds_emb[0], (p_emb, inputs["cld_interp_idx0"])]).squeeze(-1)
-        if sparse_final:
-            rgb_emb_c = self._final_at_choose(rgb_emb, (hr, wr), inputs["choose"])
-        else:
-            rgb_emb = self.cnn_up_stages[n_up - 1](rgb_emb)
-            bs, di, _, _ = rgb_emb.size()
-            rgb_emb_c = ops.gather_nn(rgb_emb.view(bs, di, -1), inputs["choose"].reshape(bs, -1, 1))
-        M.wait_stream(S)
-        to(M, p_emb)
-        if parts:
-            return rgb_emb_c, p_emb
-        return torch.cat([rgb_emb_c, p_emb], dim=1)
-
     def _gathered_final_ok(self):
-        from .cnn import FinalStage
         last = self.cnn_up_stages[len(self.rndla_up_stages) - 1]
         return settings.USE_GATHERED_FINAL and len(last) == 2 and isinstance(last[1], FinalStage)
 
-    def _sparse_final_ok(self, rgb):
-        """Inference with folded BatchNorm, the last stage = PSPUpsample(64 -> 64) + FinalStage(64 -> 64) and the last fusion on the
-        64-channel kernel: then the stage runs at the chosen pixels only."""
-        from .cnn import FinalStage, PSPUpsample
+    def _sparse_final_ok(self, path, batch):
+        """Inference with folded BatchNorm, the last stage = PSPUpsample(64 -> 64) + FinalStage(64 -> 64) and the last fusion (`path`)
+        on a 64-channel kernel: then the stage runs at the chosen pixels only."""
         last = self.cnn_up_stages[len(self.rndla_up_stages) - 1]
-        if not (settings.USE_SPARSE_FINAL and settings.USE_FUSED_UPCONV and fused_eval(rgb, self) and len(last) == 2):
+        if not (settings.USE_SPARSE_FINAL and settings.USE_FUSED_UPCONV and path in (MFMA64, FMA64) and len(last) == 2):
             return False
         up, fin = last[0], last[1]
         if not (isinstance(up, PSPUpsample) and isinstance(fin, FinalStage)):
             return False
         conv, fconv = up.conv[1], fin[0]
-        fuse = self.up_fuse_p2r_fuse_layers[len(self.rndla_up_stages) - 2]
         return (conv.in_channels == 64 and conv.out_channels == 64 and fconv.in_channels == 64 and fconv.out_channels == 64
-                and act_code(up.conv[3]) is not None and act_code(getattr(fuse, "activation", None)) is not None
-                and fuse.conv.weight.shape[0] == 64 and fuse.conv.weight.shape[1] == 128 and rgb.shape[0] <= 65535)
+                and act_code(up.conv[3]) is not None and batch <= 65535)
 
     def _final_at_choose(self, x_pm, hw, choose):
-        from .layers import folded_bn as _fbn
         last = self.cnn_up_stages[len(self.rndla_up_stages) - 1]
         up, fin = last[0], last[1]
         conv, fconv = up.conv[1], fin[0]
         wpk, fpk = derived(self, "final_pk", (conv.weight, fconv.weight),
                            lambda: (ops.upconv_fused64_pack_weight(conv.weight), ops.pack_rows64(fconv.weight.reshape(64, 64))))
-        scale, shift = _fbn(up.conv[2], conv.bias)
+        scale, shift = folded_bn(up.conv[2], conv.bias)
         code = act_code(up.conv[3])
         return ops.upconv_final_points(x_pm, hw, choose, wpk, scale, shift, code[0], code[1], fpk, fconv.bias,
                                        (hw[0] * 2, hw[1] * 2))

@@ -16,8 +16,9 @@ the initial values.
     USE_FUSED_BN_TRAIN         GDM_FUSED_BN_TRAIN         training BatchNorm + activation on the torch modules
     USE_FUSED_SYNCBN           GDM_FUSED_SYNCBN           nn.SyncBatchNorm on torch's implementation
     USE_FUSED_MATCH_LOSS       GDM_FUSED_MATCH_LOSS       training similarity materialised by hipBLASLt, rows kernel for the circle loss
-    USE_SIDE_STREAMS           GDM_SIDE_STREAMS=1         (default OFF: everything on the caller's stream) inference forks the mesh branch, the
-                                                          neighbour pyramid and the point branch of each encoder stage onto side streams
+    USE_SIDE_STREAMS           GDM_SIDE_STREAMS=1         (default OFF: everything on the caller's stream) inference forks the mesh branch and the
+                                                          neighbour pyramid onto side streams and runs the embedding's point lane on one:
+                                                          image / point streams run ahead of each other, one event per stage and direction
                                                           (worth ~3 % of the step; see DESIGN.md "Side streams")
     UPCONV_MIN_CIN             GDM_UPCONV_MIN_CIN         (int) smallest Cin for the low-resolution form of conv3x3(upsample(x))
     USE_SPARSE_FINAL           GDM_SPARSE_FINAL           the last image stage (up_3 + final) on the full 2x map, then the gather with `choose`
@@ -73,7 +74,6 @@ USE_POINTWISE_TRAIN = _flag("GDM_POINTWISE_TRAIN")       # training: forward / i
 USE_POINT_CHAIN = _flag("GDM_POINT_CHAIN")               # the RandLA stem fc0 and the first block's mlp1 as one launch (gdm_pointwise_chain2_hip)
 USE_PSP_JOBS = _flag("GDM_PSP_JOBS")                     # the four prior products of the pyramid-pooling module in one launch (gdm_pointwise_jobs_hip)
 USE_PACKED_PRODUCERS = _flag("GDM_PACKED_PRODUCERS")     # psp_combine / the up-conv gather write the next GEMM's packed operand themselves
-USE_TWO_STREAM_PIPELINE = _flag("GDM_TWO_STREAM_PIPELINE")     # with USE_SIDE_STREAMS: image / point streams run ahead of each other, one event per stage and direction
 MESH_FORK_LATE = os.environ.get("GDM_MESH_FORK_LATE", "1") != "0"       # with USE_SIDE_STREAMS: the mesh fork is enqueued behind the embedding
 PACK_MESH_ROWS = os.environ.get("GDM_PACK_MESH_ROWS", "1") != "0"         # with USE_SIDE_STREAMS: the model descriptors' matching rows are packed inside the mesh fork
 SIDE_PARTS = os.environ.get("GDM_SIDE_PARTS", "mesh,point,pyr").split(",")     # development: which branches are forked

@@ -152,7 +152,12 @@ def test_embedding_forward_same_bits_with_and_without_the_new_paths(ops, emb_cas
     emb, d = emb_case
     saved = (settings.USE_SIDE_STREAMS, list(settings.SIDE_PARTS))
     calls = {"final": 0, "packed": 0}
-    real_final, real_gaa = ops.conv64_gather_add_final, ops.gather_add_affine_act
+    real_final, real_gaa, real_gmax = ops.conv64_gather_add_final, ops.gather_add_affine_act, ops.gather_max
+    on_side = []
+
+    def watch_gmax(feature, idx):
+        on_side.append(torch.cuda.current_stream(feature.device) == ops.side_stream(feature.device, 0))
+        return real_gmax(feature, idx)
 
     def count_final(*a, **k):
         calls["final"] += 1
@@ -177,13 +182,14 @@ def test_embedding_forward_same_bits_with_and_without_the_new_paths(ops, emb_cas
         settings.USE_SIDE_STREAMS = two_stream
         if two_stream:
             settings.SIDE_PARTS = ["point"]
-            assert settings.USE_TWO_STREAM_PIPELINE
         with torch.no_grad():
+            monkeypatch.setattr(ops, "gather_max", watch_gmax)
             monkeypatch.setattr(ops, "conv64_gather_add_final", count_final)
             monkeypatch.setattr(ops, "gather_add_affine_act", count_gaa)
             new = [v.clone() for v in emb(dict(d), parts=True)]
             torch.cuda.synchronize()
             assert calls == {"final": 1, "packed": 2}, calls           # the step really takes the three new paths
+            assert on_side and any(on_side) == two_stream, on_side      # the point lane is side stream 0 exactly when asked for
             calls.update(final=0, packed=0)
             monkeypatch.setattr(ops, "conv64_gather_add_final", old_final)
             monkeypatch.setattr(ops, "gather_add_affine_act", old_gaa)
@@ -194,6 +200,35 @@ def test_embedding_forward_same_bits_with_and_without_the_new_paths(ops, emb_cas
         settings.USE_SIDE_STREAMS, settings.SIDE_PARTS = saved
     assert torch.isfinite(old[0]).all() and torch.isfinite(old[1]).all()
     assert torch.equal(new[0], old[0]) and torch.equal(new[1], old[1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("off", [None, "USE_MFMA_GEMM", "USE_POINTWISE", "USE_PACKED_PRODUCERS", "USE_SPARSE_FINAL", "USE_FUSED_UPCONV"])
+def test_embedding_forward_same_bits_on_one_lane_and_on_two(emb_case, off):
+    """The stage loop of FFB6DEmb.forward with its point lane on the current stream and on side stream 0: the same kernels on the same
+    operands, so torch.equal on both returned halves -- under the defaults and with each switch off that moves a fusion site to
+    another form (USE_POINTWISE off: the point term is a library GEMM, formed on the point lane as well)."""
+    from geometric_aware_dense_matching_amd import settings
+    emb, d = emb_case
+    saved = (settings.USE_SIDE_STREAMS, list(settings.SIDE_PARTS), off and getattr(settings, off))
+    out = {}
+    try:
+        if off:
+            setattr(settings, off, False)
+        settings.SIDE_PARTS = ["point"]
+        for two in (False, True):
+            settings.USE_SIDE_STREAMS = two
+            with torch.no_grad():
+                out[two] = [v.clone() for v in emb(dict(d), parts=True)]
+            torch.cuda.synchronize()
+    finally:
+        settings.USE_SIDE_STREAMS, settings.SIDE_PARTS = saved[:2]
+        if off:
+            setattr(settings, off, saved[2])
+    for one, two in zip(out[False], out[True]):
+        assert torch.isfinite(one).all() and torch.isfinite(two).all()
+        assert torch.equal(one, two), "%s off: %d of %d entries differ, max |d| = %g" % (
+            off, int((one != two).sum()), one.numel(), (one - two).abs().max().item())
 
 
 def test_entry_points_refuse_degenerate_arguments():
