@@ -59,7 +59,8 @@ class BasicBlock(nn.Module):
         """Training: forward and input gradient of the 32x32-resolution 3x3 convolutions on the split-bf16 MFMA kernel (MIOpen's fp32
         Winograd runs them 3x slower); the weight gradient stays with MIOpen."""
         if (settings.USE_MFMA_CONV_TRAIN and conv.bias is None and tuple(conv.stride) == (1, 1)
-                and ops.conv3x3_supported(x, conv.weight, conv.stride, conv.padding, conv.dilation)):
+                and ops.conv3x3_supported(x, conv.weight, conv.stride, conv.padding, conv.dilation)
+                and ops.conv3x3_train_supported(x, conv.weight)):
             return ops.conv3x3_train(x, conv.weight)
         return conv(x)
 
@@ -86,7 +87,7 @@ class BasicBlock(nn.Module):
             dconv = self.downsample[0] if self.downsample is not None else None
             own_ds = (settings.USE_MFMA_STRIDED and dconv is not None and isinstance(dconv, nn.Conv2d) and dconv.kernel_size == (1, 1) and dconv.bias is None
                       and dconv.stride == self.conv1.stride and dconv.padding == (0, 0)
-                      and ops.gemm_supported(dconv.in_channels, dconv.out_channels, 64))
+                      and ops.gemm_supported(dconv.in_channels, dconv.out_channels, 64, 1))      # (reads conv1's operand: _mfma_ok weighed it)
             if own_ds and not isinstance(xin, ops.PackedAct):
                 xin = ops.conv3x3_pack_act(x)                      # one packed operand feeds conv1 and the downsample branch
             chain = (x.shape[0] * (x.shape[2] // stride) * (x.shape[3] // stride)) % 256 == 0
@@ -192,7 +193,7 @@ class PSPModule(nn.Module):
             ms, wf = self._split_weights()
             B, Cin = feats.shape[0], feats.shape[1]
             def full_res():
-                if settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, wf.shape[0], h * w):
+                if settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, wf.shape[0], h * w, B):
                     wpk, co = cached_gemm_weight(self, "wf", wf, (self.bottleneck.weight,))
                     return ops.gemm_bf16x3_map(feats, wpk, co)               # reads layer4's packed output when it is there
                 return ops.wx(wf, feats.reshape(B, Cin, h * w)).view(B, -1, h, w)
@@ -275,7 +276,7 @@ class PSPUpsample(nn.Module):
             return None
         if settings.USE_FUSED_UPCONV and Cin == 64 and conv.out_channels == 64 and Hx >= 2 and Wx >= 2 and Bx <= 65535:
             return FUSED64
-        if settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, 9 * conv.out_channels, Hx * Wx):
+        if settings.USE_MFMA_GEMM and ops.gemm_supported(Cin, 9 * conv.out_channels, Hx * Wx, Bx):
             return TAP_GEMM_MFMA
         return TAP_GEMM_BLAS
 

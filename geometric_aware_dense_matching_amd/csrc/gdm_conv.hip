@@ -17,6 +17,7 @@
 // MFMAs, registers -> LDS after them, ONE barrier per panel), 9 * Cin/128 panels accumulate into four 32x32 tiles.
 #include "gdm_common.h"
 #include <math.h>
+#include <limits.h>
 #include <stdlib.h>
 
 namespace {
@@ -195,7 +196,8 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
     // (plane kg of a k-step + the lane's pixel), everything that changes per panel / tap / k-step in the SCALAR offset.  The flat
     // form recomputed a 64-bit per-lane address for every load (v_mad_u64 / v_lshl_add_u64 / v_mul_lo clumps of ~45 vector
     // instructions at the head of each half panel, issued by both waves of a SIMD at once right behind the barrier: MFMA pipe idle).
-    // The host checks that both packed buffers are below 2 GiB.
+    // conv_launch, the only way to this kernel, refuses packed buffers of 2 GiB or more: every offset below is a byte offset INSIDE one
+    // of the two buffers, so it fits an int.
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(xpk), (short)0, 0x7ffffff0, 0x00020000);
     int avoff[NPH];                                                 // fragment ph: 16 consecutive pixels of one image row (W % 16 == 0)
 #pragma unroll
@@ -507,18 +509,43 @@ struct ConvArgs {
     const int32_t* gidx = nullptr;
     const float* gt = nullptr;
     int gn = 0, gt_lds = 0;
+    const char* who = "conv_mfma16_kernel";         // the entry point, for the messages of conv_launch
 };
+
+// a * b for byte counts, saturating: a refusal must not depend on a product that wrapped
+static long mul_sat(long a, long b)
+{
+    long r;
+    return (a < 0 || b < 0 || __builtin_mul_overflow(a, b, &r)) ? LONG_MAX : r;
+}
 
 // The one place conv_mfma16_kernel is launched from.  smem is what the SITE wants (it decides how many workgroups share a CU); what the
 // instance is allowed is set here, once, so an instance cannot be launched without it.
+// The kernel addresses both packed operands through buffer descriptors with 32-bit byte offsets, so each must stay below 2 GiB: checked
+// here too, before the first HIP call, from what the kernel itself derives its offsets from -- the activations are the zero-bordered
+// (H stride) x (W stride) input map of B images (the grouped form: ONE 1 x W map, B counts gathered rows), the weights TAPS panels per
+// 128-channel chunk, behind (B - 1) * wbstride bytes where every image has its own.  Nonzero: refused, gdm_last_error() says why.
+// (The alignment of the two pointers is checked behind the limit, so a caller -- a test without a GPU, say -- can see that a shape passed
+// the limit without launching it.)
 template <int ACT, bool RES, int TAPS, bool PM, int NKS, int NCB, int WV, bool GADD>
-void conv_launch(dim3 grid, int smem, hipStream_t s, const ConvArgs& a)
+int conv_launch(dim3 grid, int smem, hipStream_t s, const ConvArgs& a)
 {
+    const long chunks = (a.Cin + 127) / 128;
+    const long xbytes = mul_sat(mul_sat(a.rowidx ? 1 : a.B, mul_sat((long)a.H * a.stride + 2, (long)a.W * a.stride + 2)), chunks * ROWB);
+    const long wpanels = mul_sat(TAPS * chunks, (((long)a.Cout + 127) & ~127L) * ROWB);
+    const long wlead = a.wbstride ? mul_sat(a.B - 1, a.wbstride) : 0;
+    const long wbytes = wlead > LONG_MAX - wpanels ? LONG_MAX : wlead + wpanels;
+    GDM_CHECK_ARG(xbytes < (1L << 31) && wbytes < (1L << 31),
+                  "%s: packed operands must stay below 2 GiB (activations %ld bytes, weights %ld bytes)", a.who, xbytes, wbytes);
+    // every operand load is 16 bytes wide, and so is every store of the pack kernels that write these buffers
+    GDM_CHECK_ARG((((uintptr_t)a.xpk | (uintptr_t)a.wpk) & 15) == 0,
+                  "%s: the packed operands must be 16-byte aligned (xpk %p, wpk %p)", a.who, a.xpk, a.wpk);
     constexpr auto kernel = conv_mfma16_kernel<ACT, RES, TAPS, PM, NKS, NCB, WV, GADD>;
     gdm_allow_lds<kernel>(GADD ? LDS_MAX : conv_lds_bytes(NCB));
     hipLaunchKernelGGL(kernel, grid, dim3(WV * 64), smem, s, (const unsigned char*)a.xpk, (const unsigned char*)a.wpk, a.scale, a.shift, a.res,
                        a.B, a.Cin, a.Cout, a.H, a.W, a.out, a.rowidx, a.tile_co0, (unsigned char*)a.outpk, a.stride, a.wbstride, a.gidx, a.gt,
                        a.gn, a.gt_lds);
+    return 0;
 }
 
 } // namespace
@@ -694,19 +721,21 @@ static int conv3x3_launch(const void* xpk, const void* wpk, const float* scale, 
     const dim3 grid4h(gdm_cdiv(ptot, CV_PIX / 2), grid4.y);
     hipStream_t s = (hipStream_t)stream;
     ConvArgs a{xpk, wpk, scale, shift, res, B, Cin, Cout, H, W, out};
-    a.outpk = outpk; a.stride = stride;
+    a.outpk = outpk; a.stride = stride; a.who = who;
+    int refused = 0;
     gdm_dispatch_int<2>(act, [&](auto A) {
         gdm_dispatch_bool(res != nullptr, [&](auto R) {
             constexpr int ACT = decltype(A)::value;
             constexpr bool RES = decltype(R)::value;
-            if (half) return conv_launch<ACT, RES, 9, false, 8, 4, MF_WAVES / 2, false>(grid4h, conv_lds_bytes(4), s, a);
+            if (half) { refused = conv_launch<ACT, RES, 9, false, 8, 4, MF_WAVES / 2, false>(grid4h, conv_lds_bytes(4), s, a); return; }
             gdm_dispatch_bool(Cin == 64, [&](auto K4) {         // one half-filled chunk: only its four non-zero k-steps are run
                 constexpr int NKS = decltype(K4)::value ? 4 : 8;
-                if (narrow) conv_launch<ACT, RES, 9, false, NKS, 4, MF_WAVES, false>(grid4, conv_lds_bytes(4), s, a);
-                else conv_launch<ACT, RES, 9, false, NKS, 8, MF_WAVES, false>(grid, conv_lds_bytes(8), s, a);
+                if (narrow) refused = conv_launch<ACT, RES, 9, false, NKS, 4, MF_WAVES, false>(grid4, conv_lds_bytes(4), s, a);
+                else refused = conv_launch<ACT, RES, 9, false, NKS, 8, MF_WAVES, false>(grid, conv_lds_bytes(8), s, a);
             });
         });
     });
+    if (refused) return refused;
     return gdm_launch_status(half ? "conv_mfma16_kernel (3x3, 64-channel tiles, 128 pixels)"
                              : narrow ? "conv_mfma16_kernel (3x3, 64-channel tiles)" : "conv_mfma16_kernel (3x3)");
 }
@@ -734,8 +763,9 @@ extern "C" int gdm_gemm_grouped_hip(const void* xpk, const void* wpk, const int3
                   "gdm_gemm_grouped_hip: R=%d (multiple of 256) M=%d Cin=%d Cout_total=%d (multiples of 128)", R, M, Cin, Cout_total);
     // the kernel sees B = R "pixels" of a 1 x 1 map for the row bookkeeping and H = 1, W = M for the packed source
     ConvArgs a{xpk, wpk, nullptr, nullptr, nullptr, R, Cin, Cout_total, 1, M, out, rowidx, tile_co0};
+    a.who = "gdm_gemm_grouped_hip";
     // 2 * CV_PANEL, below conv_lds_bytes(8): no packed output, so the waves' output tiles are never in LDS
-    conv_launch<0, false, 1, true, 8, 8, MF_WAVES, false>(dim3(R / CV_PIX, 1), 2 * CV_PANEL, (hipStream_t)stream, a);
+    if (int refused = conv_launch<0, false, 1, true, 8, 8, MF_WAVES, false>(dim3(R / CV_PIX, 1), 2 * CV_PANEL, (hipStream_t)stream, a)) return refused;
     return gdm_launch_status("gemm_grouped_kernel");
 }
 
@@ -751,8 +781,9 @@ extern "C" int gdm_conv1x1_packed_wb_hip(const void* xpk, const void* wpk, long 
     const long ptot = (long)B * H * W;
     const dim3 grid(gdm_cdiv(ptot, CV_PIX), gdm_cdiv(Cout, CV_CO));
     ConvArgs a{xpk, wpk, nullptr, nullptr, nullptr, B, Cin, Cout, H, W, out};
-    a.wbstride = w_bstride;
-    conv_launch<0, false, 1, false, 8, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, (hipStream_t)stream, a);     // no packed output: panels only
+    a.wbstride = w_bstride; a.who = "gdm_conv1x1_packed_wb_hip";
+    // no packed output: panels only
+    if (int refused = conv_launch<0, false, 1, false, 8, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, (hipStream_t)stream, a)) return refused;
     return gdm_launch_status("conv1x1_bf16x3_kernel (per-image weights)");
 }
 
@@ -773,7 +804,8 @@ static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, 
     const unsigned ptiles = gdm_cdiv(ptot, CV_PIX);
     hipStream_t s = (hipStream_t)stream;
     ConvArgs a{xpk, wpk, scale, shift, nullptr, B, Cin, Cout, H, W, out};
-    a.stride = stride;
+    a.stride = stride; a.who = who;
+    int refused = 0;
     // 144-channel tiles (nine 16-channel blocks) where they divide Cout and fill the chip's rounds better than 128-channel ones: the
     // tap GEMMs of PSPUpsample have 9 * Cout' outputs -- 2304 at 64 pixel tiles = 1152 tiles of 128 (4.5 rounds of 256 CUs, paid as
     // 5) or 1024 tiles of 144 (4 rounds); 576 at 256 pixel tiles = 1280 tiles of 128, the last of every five half empty, or 1024 of 144
@@ -782,8 +814,9 @@ static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, 
         if (r144 < r128) {
             const dim3 grid9(ptiles, Cout / 144);
             gdm_dispatch_int<2>(act, [&](auto A) {
-                conv_launch<decltype(A)::value, false, 1, false, 8, 9, MF_WAVES, false>(grid9, conv_lds_bytes(9), s, a);
+                refused = conv_launch<decltype(A)::value, false, 1, false, 8, 9, MF_WAVES, false>(grid9, conv_lds_bytes(9), s, a);
             });
+            if (refused) return refused;
             return gdm_launch_status("conv1x1_bf16x3_kernel (144-channel tiles)");
         }
     }
@@ -797,14 +830,15 @@ static int conv1x1_launch(const void* xpk, const void* wpk, const float* scale, 
     gdm_dispatch_int<2>(act, [&](auto A) {
         constexpr int ACT = decltype(A)::value;
         if (Cin == 64)                                              // one half-filled chunk: only its four non-zero k-steps are run
-            conv_launch<ACT, false, 1, false, 4, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, s, a);
+            refused = conv_launch<ACT, false, 1, false, 4, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, s, a);
         else if (narrow)
-            conv_launch<ACT, false, 1, false, 8, 4, MF_WAVES, false>(grid, 2 * 64 * ROWB, s, a);
+            refused = conv_launch<ACT, false, 1, false, 8, 4, MF_WAVES, false>(grid, 2 * 64 * ROWB, s, a);
         else
             gdm_dispatch_bool(pixel_major != 0, [&](auto P) {
-                conv_launch<ACT, false, 1, decltype(P)::value, 8, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, s, a);
+                refused = conv_launch<ACT, false, 1, decltype(P)::value, 8, 8, MF_WAVES, false>(grid, 2 * CV_PANEL, s, a);
             });
     });
+    if (refused) return refused;
     return gdm_launch_status(narrow ? "conv1x1_bf16x3_kernel (64-channel tiles)" : "conv1x1_bf16x3_kernel");
 }
 
@@ -838,11 +872,6 @@ extern "C" int gdm_conv1x1_gather_add_hip(const void* xpk, const void* wpk, cons
     GDM_CHECK_ARG(act == 0 || act == 1, "%s: act=%d (none or ReLU)", who, act);
     GDM_CHECK_ARG(!outpk || (Cout % 8 == 0 && ((long)B * H * W) % CV_PIX == 0),
                   "%s: packed output needs Cout %% 8 == 0 and B*H*W %% 256 == 0 (got Cout=%d, B*H*W=%ld)", who, Cout, (long)B * H * W);
-    // the kernel addresses the packed activations and the packed weights through buffer descriptors with 32-bit byte offsets
-    const long xbytes = (long)B * (H + 2) * (W + 2) * ((Cin + 127) / 128) * ROWB;
-    const long wbytes = (long)((Cin + 127) / 128) * ((Cout + 127) & ~127) * ROWB;
-    GDM_CHECK_ARG(xbytes < (1L << 31) && wbytes < (1L << 31),
-                  "%s: packed operands must stay below 2 GiB (activations %ld bytes, weights %ld bytes)", who, xbytes, wbytes);
     GDM_CHECK_ARG(((uintptr_t)gidx & 15) == 0, "%s: gidx must be 16-byte aligned (the epilogue loads four indices at once)", who);
     const long ptot = (long)B * H * W;
     const unsigned ptiles = gdm_cdiv(ptot, CV_PIX);
@@ -857,12 +886,14 @@ extern "C" int gdm_conv1x1_gather_add_hip(const void* xpk, const void* wpk, cons
     const long smem = tiles + trows;
     const bool stage_t = (H * W) % CV_PIX == 0 && smem <= (narrow && (long)grid.x * grid.y > 256 ? LDS_MAX / 2 : LDS_MAX);
     ConvArgs a{xpk, wpk, scale, shift, nullptr, B, Cin, Cout, H, W, out};
-    a.outpk = outpk; a.gidx = gidx; a.gt = gt; a.gn = gn; a.gt_lds = stage_t ? tiles : 0;
+    a.outpk = outpk; a.gidx = gidx; a.gt = gt; a.gn = gn; a.gt_lds = stage_t ? tiles : 0; a.who = who;
     const int SM = stage_t ? (int)smem : tiles;
+    int refused = 0;                                                // packed operands of 2 GiB or more
     gdm_dispatch_int<2>(act, [&](auto A) {
         gdm_dispatch_bool(narrow, [&](auto N4) {
-            conv_launch<decltype(A)::value, false, 1, false, 8, decltype(N4)::value ? 4 : 8, MF_WAVES, true>(grid, SM, (hipStream_t)stream, a);
+            refused = conv_launch<decltype(A)::value, false, 1, false, 8, decltype(N4)::value ? 4 : 8, MF_WAVES, true>(grid, SM, (hipStream_t)stream, a);
         });
     });
+    if (refused) return refused;
     return gdm_launch_status(narrow ? "conv1x1_gather_add_kernel (64-channel tiles)" : "conv1x1_gather_add_kernel");
 }

@@ -243,7 +243,7 @@ class FFB6DEmb(nn.Module):
         """Every other channel count: the pixel half as a GEMM, then gather + add + BN + activation (channel-major point term).  Which
         GEMM depends on the operand the map carries at run time, so that choice is made here."""
         bs, c, hr, wr = rgb_emb0.shape
-        if settings.USE_MFMA_GEMM and ops.gemm_supported(c, wa.shape[0], hr * wr):
+        if settings.USE_MFMA_GEMM and ops.gemm_supported(c, wa.shape[0], hr * wr, bs):
             wpk, co = cached_gemm_weight(fuse_layer, "wa", wa, (fuse_layer.conv.weight,))
             only = packed_only and ops.packed_out_supported(bs, co, hr, wr)
             if ops.conv1x1_gather_add_supported(rgb_emb0, co, code[0], f32_out=not only):

@@ -1172,6 +1172,31 @@ def wx(w2d, x3):
     return torch.bmm(w2d.unsqueeze(0).expand(x3.shape[0], -1, -1), x3)
 
 
+OPERAND_LIMIT = 1 << 31
+
+
+def operands_fit(*nbytes):
+    """The convolution / GEMM kernel (csrc/gdm_conv.hip conv_mfma16_kernel) addresses its packed activations and its packed weights with
+    32-bit byte offsets: each operand must stay below 2 GiB, and the library refuses a launch that does not.  nbytes: what the library's
+    own size functions give for the operands of one launch (0 = a shape they do not take).  Every wrapper below asks this before it
+    allocates anything, and every *_supported predicate asks it so that the modules take their torch path past the limit."""
+    return all(0 < n < OPERAND_LIMIT for n in nbytes)
+
+
+def _require_fit(who, what, args, act_bytes, weight_bytes=None):
+    """ValueError unless the operands of a launch fit (weight_bytes None: a pack launch, which has the activations only).  `what % args`
+    describes the shapes; it is formatted only for the message."""
+    if not operands_fit(act_bytes, *(() if weight_bytes is None else (weight_bytes,))):
+        raise ValueError("%s: %s needs packed activations of %d bytes%s; a packed operand must be above 0 and below 2 GiB (%d bytes)"
+                         % (who, what % args, act_bytes, "" if weight_bytes is None else " and packed weights of %d bytes" % weight_bytes,
+                            OPERAND_LIMIT))
+
+
+def _map_bytes(B, C, H, W):
+    """Bytes of the packed operand of a [B,C,H,W] map (0: not a map the pack kernel takes)."""
+    return _lib.lib().gdm_conv3x3_act_bytes(B, C, H, W)
+
+
 def _wgrad_parts(nchunk, tiles):
     """K split of a pixel-contraction GEMM: the largest divisor of the chunk count that keeps the launch near one round of
     workgroups (a part has `tiles` of them) and at least four chunks per part."""
@@ -1184,21 +1209,24 @@ def _wgrad_parts(nchunk, tiles):
 
 def gemm_wgrad_supported(x3, go3):
     B, Cin, P = x3.shape
+    L = _lib.lib()
     return (settings.USE_MFMA_GEMM_TRAIN and x3.is_cuda and x3.dtype == torch.float32 and P % 128 == 0 and Cin % 256 == 0
-            and go3.shape[1] >= 64 and 2.0 * B * P * Cin * go3.shape[1] >= 2e9)
+            and go3.shape[1] >= 64 and 2.0 * B * P * Cin * go3.shape[1] >= 2e9
+            and operands_fit(L.gdm_wgrad_x1_bytes(B, Cin, P), L.gdm_wgrad_go_bytes(B, go3.shape[1], P // 32, 32)))
 
 
 def gemm_wgrad(x3, go3):
     """dW f32[Cout,Cin] = sum_b go3[b] . x3[b]^T (x3 f32[B,Cin,P], go3 f32[B,Cout,P]) on the split-bf16 MFMA GEMM with the pixels as the
     contraction axis (include/gdm.h gdm_wgrad_pack_x1_hip): the weight gradient of a 1x1 convolution / of `wx`."""
-    x3 = _dev(x3, torch.float32, "x")
-    go3 = _dev(go3, torch.float32, "grad_out")
     B, Cin, P = x3.shape
     Cout = go3.shape[1]
     L = _lib.lib()
     nx, ng = L.gdm_wgrad_x1_bytes(B, Cin, P), L.gdm_wgrad_go_bytes(B, Cout, P // 32, 32)
     if nx == 0 or ng == 0 or Cin % 256 != 0:
         raise ValueError("gemm_wgrad: unsupported shape x %s grad_out %s" % (tuple(x3.shape), tuple(go3.shape)))
+    _require_fit("gemm_wgrad", "x %s grad_out %s", (tuple(x3.shape), tuple(go3.shape)), nx, ng)
+    x3 = _dev(x3, torch.float32, "x")
+    go3 = _dev(go3, torch.float32, "grad_out")
     xpk = torch.empty(nx, dtype=torch.uint8, device=x3.device)
     gpk = torch.empty(ng, dtype=torch.uint8, device=x3.device)
     call("gdm_wgrad_pack_x1_hip", x3, B, Cin, P, xpk)
@@ -1247,7 +1275,7 @@ def wgrad_direct(x3, go3, bias=False):
 
 
 def _gemm_fwd_mfma_ok(cin, cout, n, B):
-    return settings.USE_MFMA_GEMM_TRAIN and gemm_supported(cin, cout, n) and 2.0 * B * n * cin * cout >= 2e9
+    return settings.USE_MFMA_GEMM_TRAIN and gemm_supported(cin, cout, n, B) and 2.0 * B * n * cin * cout >= 2e9
 
 
 class _WxTrain(torch.autograd.Function):
@@ -1336,9 +1364,24 @@ class _Conv1x1Train(torch.autograd.Function):
         return gx, gw, gb
 
 
+def _gemm_train_fits(cin, cout, n, B):
+    """False when one of the three products of a 1x1 layer's training step -- W . x, W^T . grad_out, grad_out . x^T -- is one the split-bf16
+    GEMM takes by its shape, with an operand of 2 GiB or more."""
+    L = _lib.lib()
+    big = settings.USE_MFMA_GEMM_TRAIN and 2.0 * B * n * cin * cout >= 2e9
+    for ci, co in ((cin, cout), (cout, cin)):        # forward on x; input gradient on grad_out
+        if big and gemm_shape_supported(ci, co, n) and not operands_fit(_map_bytes(B, ci, 1, n), L.gdm_conv1x1_weight_bytes(co, ci)):
+            return False
+    if big and n % 128 == 0 and cin % 256 == 0 and cout >= 64:
+        return operands_fit(L.gdm_wgrad_x1_bytes(B, cin, n), L.gdm_wgrad_go_bytes(B, cout, n // 32, 32))
+    return True
+
+
 def conv1x1_train_supported(conv, x):
+    """Past the operand limit of the split-bf16 GEMM (operands_fit; the backward's operands count too) the module runs its torch path."""
     return (settings.USE_GEMM_CONV1X1_TRAIN and x.is_cuda and x.dtype == torch.float32 and all(k == 1 for k in conv.kernel_size)
-            and all(st == 1 for st in conv.stride) and all(p == 0 for p in conv.padding) and conv.groups == 1 and x.dim() in (3, 4))
+            and all(st == 1 for st in conv.stride) and all(p == 0 for p in conv.padding) and conv.groups == 1 and x.dim() in (3, 4)
+            and _gemm_train_fits(x.shape[1], conv.weight.shape[0], x.numel() // max(1, x.shape[0] * x.shape[1]), x.shape[0]))
 
 
 def conv1x1_train(conv, x):
@@ -1767,21 +1810,23 @@ def conv3x3_wgrad_supported(x, go):
     whole 256-row tiles per part) -- the 32 x 32 half of the trunk, where torch's path (MIOpen fp32 implicit GEMM) is 2.5x slower."""
     B, Cin, H, W = x.shape
     return (settings.USE_MFMA_WGRAD and x.is_cuda and x.dtype == torch.float32 and go.shape[0] == B and tuple(go.shape[2:]) == (H, W)
-            and W in (32, 64) and (H * W) % 128 == 0 and Cin % 256 == 0 and go.shape[1] % 8 == 0)
+            and W in (32, 64) and (H * W) % 128 == 0 and Cin % 256 == 0 and go.shape[1] % 8 == 0
+            and operands_fit(_lib.lib().gdm_wgrad_x_bytes(B, Cin, H, W), _lib.lib().gdm_wgrad_go_bytes(B, go.shape[1], H, W)))
 
 
 def conv3x3_wgrad(x, go, parts=None):
     """dW f32[Cout,Cin,3,3] of a 3x3 / stride 1 / pad 1 convolution from its input x f32[B,Cin,H,W] and output gradient go
     f32[B,Cout,H,W], on the split-bf16 MFMA GEMM (include/gdm.h gdm_wgrad_*): the contraction runs over the B*H*W pixels, split
     into `parts` equal parts (one launch), whose [Cout,9,Cin] partial products are added here in a fixed order (deterministic)."""
-    x = _dev(x, torch.float32, "x")
-    go = _dev(go, torch.float32, "grad_out")
     B, Cin, H, W = x.shape
     Cout = go.shape[1]
     L = _lib.lib()
     nx, ng = L.gdm_wgrad_x_bytes(B, Cin, H, W), L.gdm_wgrad_go_bytes(B, Cout, H, W)
     if nx == 0 or ng == 0 or (9 * Cin) % 256 != 0:
         raise ValueError("conv3x3_wgrad: unsupported shape x %s grad_out %s" % (tuple(x.shape), tuple(go.shape)))
+    _require_fit("conv3x3_wgrad", "x %s grad_out %s", (tuple(x.shape), tuple(go.shape)), nx, ng)
+    x = _dev(x, torch.float32, "x")
+    go = _dev(go, torch.float32, "grad_out")
     xpk = torch.empty(nx, dtype=torch.uint8, device=x.device)
     gpk = torch.empty(ng, dtype=torch.uint8, device=x.device)
     call("gdm_wgrad_pack_x_hip", x, B, Cin, H, W, xpk)
@@ -1806,7 +1851,8 @@ def conv3x3_wgrad(x, go, parts=None):
 
 
 def conv3x3_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1)):
-    """3x3 / pad 1 / no dilation, stride 1 or 2 (output width a multiple of 32), Cin 64 or a multiple of 128."""
+    """3x3 / pad 1 / no dilation, stride 1 or 2 (output width a multiple of 32), Cin 64 or a multiple of 128, both packed operands
+    below 2 GiB (operands_fit)."""
     cin = weight.shape[1]
     st = tuple(stride)
     if st not in ((1, 1), (2, 2)):
@@ -1814,7 +1860,16 @@ def conv3x3_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1))
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)
             and tuple(padding) == (1, 1) and tuple(dilation) == (1, 1)
             and x.shape[2] % st[0] == 0 and x.shape[3] % st[1] == 0 and (x.shape[3] // st[1]) % 32 == 0
-            and (cin == 64 or cin % 128 == 0) and weight.shape[0] % 8 == 0 and x.shape[0] <= 65535)
+            and (cin == 64 or cin % 128 == 0) and weight.shape[0] % 8 == 0 and x.shape[0] <= 65535
+            and operands_fit(_map_bytes(x.shape[0], cin, x.shape[2], x.shape[3]), _lib.lib().gdm_conv3x3_weight_bytes(weight.shape[0], cin)))
+
+
+def conv3x3_train_supported(x, weight):
+    """conv3x3_train(x, weight): conv3x3_supported at stride 1, and the backward's launch too -- the input gradient is the same convolution
+    of grad_out f32[B,Cout,H,W] with the flipped, transposed filter, whose operands can be over the limit when the forward's are not."""
+    cout, cin = weight.shape[0], weight.shape[1]
+    return (conv3x3_supported(x, weight)
+            and operands_fit(_map_bytes(x.shape[0], cout, x.shape[2], x.shape[3]), _lib.lib().gdm_conv3x3_weight_bytes(cin, cout)))
 
 
 def conv_pack_weight_dgrad(weight):
@@ -1867,8 +1922,9 @@ def _packed_buffer(B, C, H, W, device, avoid=None):
 
 def conv3x3_pack_act(x):
     """x f32[B,C,H,W] -> PackedAct (one launch)."""
-    x = _dev(x, torch.float32, "x")
     B, C, H, W = x.shape
+    _require_fit("conv3x3_pack_act", "x %s", (tuple(x.shape),), _map_bytes(B, C, H, W))       # (in front of _dev, which may copy x)
+    x = _dev(x, torch.float32, "x")
     buf = _packed_buffer(B, C, H, W, x.device)
     call("gdm_conv3x3_pack_act_hip", x, B, C, H, W, buf)
     return PackedAct(buf, (B, C, H, W))
@@ -1878,6 +1934,7 @@ def conv3x3_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, res=None,
     """3x3/p1 convolution (stride 1 or 2) of x f32[B,Cin,H,W] (or a PackedAct) with packed weights on split-bf16 MFMA (+ per-channel
     scale/shift, optional residual, optional ReLU).  Returns the fp32 map, or -- out_packed -- (fp32 map or None, PackedAct of the
     result): the epilogue writes the next convolution's operand itself.  Inference only."""
+    _require_fit("conv3x3_bf16x3", "x %s -> %d channels", (tuple(x.shape), cout), _map_bytes(*x.shape), wpk.numel())
     xp = x if isinstance(x, PackedAct) else conv3x3_pack_act(x)
     B, Cin, H, W = xp.shape
     if stride != 1:
@@ -1933,7 +1990,9 @@ def conv1x1_gather_add_supported(x, cout, act, f32_out=True):
     if xp is None or act not in (ACT_NONE, ACT_RELU):
         return False
     B, cin, H, W = xp.shape
-    if cin % 128 != 0 or not gemm_supported(cin, cout, H * W) or cout % 8 != 0 or (B * H * W) % 256 != 0:
+    if cin % 128 != 0 or not gemm_shape_supported(cin, cout, H * W) or cout % 8 != 0 or (B * H * W) % 256 != 0:
+        return False
+    if not operands_fit(_map_bytes(B, cin, H, W), _lib.lib().gdm_conv1x1_weight_bytes(cout, cin)):
         return False
     return bool(f32_out) or packed_out_supported(B, cout, H, W)
 
@@ -1959,6 +2018,7 @@ def conv1x1_packed_gather_add_act(x, wpk, cout, t, idx, scale, shift, act=ACT_NO
                          % (tuple(x.shape), cout, act, f32_out))
     xp = _packed_operand(x)
     B, Cin, H, W = xp.shape
+    _require_fit("conv1x1_packed_gather_add_act", "x %s -> %d channels", (xp.shape, cout), _map_bytes(B, Cin, H, W), wpk.numel())
     if hw is not None and tuple(hw) != (H, W):
         raise ValueError("conv1x1_packed_gather_add_act: hw %s of a %dx%d map" % (tuple(hw), H, W))
     t = _dev(t, torch.float32, "t")
@@ -1981,6 +2041,7 @@ def conv1x1_packed2d(xp, wpk, cout, scale=None, shift=None, act=ACT_NONE, stride
     """1x1 convolution (stride 1 or 2) of a PackedAct map with gemm_pack_weight'ed weights -> f32[B,cout,H/stride,W/stride]: the
     downsample branch of a residual block on the packed operand its 3x3 convolution already reads.  Inference only."""
     B, Cin, H, W = xp.shape
+    _require_fit("conv1x1_packed2d", "x %s -> %d channels", (xp.shape, cout), _map_bytes(B, Cin, H, W), wpk.numel())
     if stride not in (1, 2) or H % stride or W % stride:
         raise ValueError("conv1x1_packed2d: stride %r on a %dx%d map" % (stride, H, W))
     H, W = H // stride, W // stride
@@ -2017,10 +2078,18 @@ def conv3x3_train(x, weight):
     return _Conv3x3Train.apply(x, weight)
 
 
-def gemm_supported(cin, cout, npix):
+def gemm_shape_supported(cin, cout, npix):
     """K in whole 128-channel chunks (or exactly 64); output channels are padded to 128 inside the kernel (zero weight rows, masked stores), which
     pays once the padding wastes at most a third of the MFMA work."""
     return (cin % 128 == 0 or cin == 64) and (cout % 128 == 0 or cout >= 192) and npix % 32 == 0
+
+
+def gemm_supported(cin, cout, npix, batch):
+    """gemm_bf16x3 on x f32[batch,cin,npix] -> cout channels: a shape the kernel takes (gemm_shape_supported) whose packed operands
+    stay below 2 GiB (operands_fit).  The activations count as gemm_bf16x3 packs them, a map of one row per image: three rows of
+    npix + 2 with the zero border, which is also an upper bound for the same pixels packed as a two-dimensional map."""
+    return (gemm_shape_supported(cin, cout, npix)
+            and operands_fit(_map_bytes(batch, cin, 1, npix), _lib.lib().gdm_conv1x1_weight_bytes(cout, cin)))
 
 
 def gemm_pack_weight(weight2d):
@@ -2036,8 +2105,9 @@ def gemm_pack_weight(weight2d):
 def gemm_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, pixel_major=False):
     """out[b] = act(scale * (W @ x[b]) + shift) on split-bf16 MFMA.  x f32[B,Cin,n] (channel-major, n % 32 == 0) ->
     f32[B,cout,n], or f32[B*n, cout] when pixel_major.  Inference only."""
-    x = _dev(x, torch.float32, "x")
     B, Cin, n = x.shape
+    _require_fit("gemm_bf16x3", "x %s -> %d channels", (tuple(x.shape), cout), _map_bytes(B, Cin, 1, n), wpk.numel())
+    x = _dev(x, torch.float32, "x")
     xpk = _packed_buffer(B, Cin, 1, n, x.device)
     call("gdm_conv3x3_pack_act_hip", x, B, Cin, 1, n, xpk)
     out = torch.empty((B * n, cout) if pixel_major else (B, cout, n), dtype=torch.float32, device=x.device)
@@ -2054,9 +2124,10 @@ def gemm_grouped(x_cm, wpk, rowidx, tile_co0, cout_total, xpk=None):
     """Grouped, gathered GEMM on the split-bf16 MFMA kernel (include/gdm.h gdm_gemm_grouped_hip): x_cm f32[1,Cin,M] (channel-major),
     wpk = gemm_pack_weight of a [cout_total, Cin] matrix, rowidx i32[R] (R % 256 == 0), tile_co0 i32[R/256] -> Y f32[R,128].
     xpk: the packed operand of x_cm when its producer wrote it (gdm_spline_*3_hip); otherwise one pack launch makes it here."""
-    x_cm = _dev(x_cm, torch.float32, "x")
     _, Cin, M = x_cm.shape
     R = rowidx.shape[0]
+    _require_fit("gemm_grouped", "x %s, %d rows -> %d channels", (tuple(x_cm.shape), R, cout_total), _map_bytes(1, Cin, 1, M), wpk.numel())
+    x_cm = _dev(x_cm, torch.float32, "x")
     if xpk is None:
         xpk = _packed_buffer(1, Cin, 1, M, x_cm.device)
         call("gdm_conv3x3_pack_act_hip", x_cm, 1, Cin, 1, M, xpk)

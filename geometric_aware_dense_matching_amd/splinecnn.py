@@ -272,7 +272,7 @@ class SplineConv(nn.Module):
                  None, None)
             return out
         if (settings.USE_MFMA_GEMM and not torch.is_grad_enabled() and x.is_cuda
-                and ops.gemm_supported(self.cin, nk * self.cout, M)):
+                and ops.gemm_supported(self.cin, nk * self.cout, M, 1)):
             # dense part on the split-bf16 MFMA GEMM, written node-major ([M, 125*out]) as the aggregation kernel reads it
             wpk, _ = cached_gemm_weight(self, "dense", lambda: self.weight.permute(0, 2, 1).reshape(nk * self.cout, self.cin),
                                         (self.weight,))

@@ -223,6 +223,8 @@ int gdm_spline_direct3_hip(const float* x, const float* weight, const int32_t* r
  * 4x fewer FLOPs than the dense form and no [M, 125*C] table.  gdm_gemm_grouped_hip: Y[r, 0:128] = Wpk[tile_co0[r/256] + 0:128, :] .
  * X[rowidx[r], :] for R % 256 == 0 rows (pairs sorted by kernel index, groups padded to 256 rows with rowidx = 0), X packed by
  * gdm_conv3x3_pack_act_hip(x^T, 1, Cin, 1, M), weights by gdm_conv1x1_pack_weight_hip (125*C rows, row = wi*C + co).
+ * The packed X, gdm_conv3x3_act_bytes(1, Cin, 1, M) bytes, and the packed weights must each stay below 2 GiB (the operand limit, at
+ * gdm_conv3x3_packed_hip below): refused on the host otherwise.
  * gdm_spline_pairs_aggregate3_hip: out_i = mean_e sum_s basis[e,s] * Y[pos[e,s]] + root_i + bias; root f32[M,C] and bias f32[C] may
  * be NULL. */
 int gdm_gemm_grouped_hip(const void* xpk, const void* wpk, const int32_t* rowidx, const int32_t* tile_co0, int R, int M,
@@ -611,7 +613,13 @@ int gdm_conv64_gather_add_final_hip(const float* x, const void* wpk, const float
  *   pack_weight: w f32[Cout,Cin,3,3] -> wpk (gdm_conv3x3_weight_bytes), once per weight change
  *   pack_act   : x f32[B,Cin,H,W]    -> xpk (gdm_conv3x3_act_bytes; pixel-major rows with a one-pixel ZERO border: the
  *                caller provides a zero-filled buffer, only interior rows are written)
- *   packed     : out f32[B,Cout,H,W] = act(scale[co] * conv + shift[co] (+ res)), act 0 none / 1 ReLU; scale/shift/res may be NULL */
+ *   packed     : out f32[B,Cout,H,W] = act(scale[co] * conv + shift[co] (+ res)), act 0 none / 1 ReLU; scale/shift/res may be NULL
+ * THE OPERAND LIMIT of every entry point that launches this kernel -- gdm_conv3x3_packed_hip, gdm_conv3x3_strided_hip,
+ * gdm_conv1x1_packed_hip, gdm_conv1x1_strided_hip, gdm_conv1x1_gather_add_hip, gdm_gemm_grouped_hip, gdm_conv1x1_packed_wb_hip: the kernel
+ * addresses xpk and wpk with 32-bit byte offsets, so each must stay below 2 GiB (2^31 bytes).  xpk counts as the packed INPUT map,
+ * gdm_conv3x3_act_bytes(B, Cin, H*stride, W*stride); wpk as gdm_conv3x3_weight_bytes / gdm_conv1x1_weight_bytes, behind (B - 1) *
+ * w_bstride bytes where every image has its own weights.  A call past the limit is refused on the host before any HIP call (nonzero,
+ * gdm_last_error() names the entry point and both byte counts); nothing is launched. */
 size_t gdm_conv3x3_act_bytes(int B, int Cin, int H, int W);
 size_t gdm_conv3x3_weight_bytes(int Cout, int Cin);
 int gdm_conv3x3_pack_weight_hip(const float* w, int Cout, int Cin, void* wpk, void* stream);
@@ -632,7 +640,7 @@ int gdm_conv1x1_strided_hip(const void* xpk, const void* wpk, const float* scale
  * out[b,co,j] = act(scale[co] * (sum_ci W[co,ci] x[b,ci,j] + gt[b,co,clamp(gidx[b,j], 0, gn-1)]) + shift[co]).
  * gidx int32[B,H*W] (16-byte aligned), gt f32[B,Cout,gn], gn >= 1; Cin a multiple of 128; act 0 (none) or 1 (ReLU).  out f32[B,Cout,H,W]
  * and / or outpk (the packed operand of the next convolution, as gdm_conv3x3_strided_hip writes it: Cout % 8 == 0, B*H*W % 256 == 0);
- * either may be NULL, not both.  The packed activations and the packed weights must each stay below 2 GiB. */
+ * either may be NULL, not both.  The packed activations and the packed weights must each stay below 2 GiB (the operand limit above). */
 int gdm_conv1x1_gather_add_hip(const void* xpk, const void* wpk, const int32_t* gidx, const float* gt, int gn, const float* scale,
                                const float* shift, int B, int Cin, int Cout, int H, int W, int act, float* out, void* outpk, void* stream);
 
@@ -661,7 +669,8 @@ int gdm_psp_pools_bwd_hip(const float* g1, const float* g2, const float* g3, con
 /* 1x1 convolution / GEMM on the same split-bf16 MFMA kernel (one tap): x packed by gdm_conv3x3_pack_act_hip, weights
  * f32[Cout,Cin] packed by gdm_conv1x1_pack_weight_hip.  out = act(scale*(W x)+shift) as f32[B,Cout,H,W], or, with
  * pixel_major != 0, as f32[B*H*W, Cout] (used for the dense part of SplineConv: nodes x (125*128)).  Cin % 128 == 0; Cout is
- * arbitrary: the packed weights carry zero rows up to the next multiple of 128 and the extra outputs are never stored. */
+ * arbitrary: the packed weights carry zero rows up to the next multiple of 128 and the extra outputs are never stored.  The operand
+ * limit above holds: a [B, Cin, n] product packed as a map of one row per image has B * 3 * (n + 2) * ceil(Cin / 128) * 512 bytes. */
 size_t gdm_conv1x1_weight_bytes(int Cout, int Cin);
 int gdm_conv1x1_pack_weight_hip(const float* w, int Cout, int Cin, void* wpk, void* stream);
 /* training: the packed weights of the INPUT-GRADIENT convolution (the flipped, transposed filter) straight from the forward weight
@@ -976,7 +985,9 @@ int gdm_mfma_probe_lds_hip(int blocks, int iters, int rpu, float* sink, void* st
  * The caller adds the nsplit partials. */
 int gdm_wgrad_direct_hip(const float* go, long go_bstride, const float* x, long x_bstride, int B, int Cout, int Cin, int P,
                          int nsplit, float* partial, float* bias_partial, void* stream);
-/* gdm_conv1x1_packed_hip without epilogue, NCHW output, with the weights of image b at wpk + b*w_bstride (H*W % 256 == 0). */
+/* gdm_conv1x1_packed_hip without epilogue, NCHW output, with the weights of image b at wpk + b*w_bstride (H*W % 256 == 0).  The operand
+ * limit (at gdm_conv3x3_packed_hip) counts all B weight sets: for the weight-gradient GEMMs above, gdm_wgrad_x_bytes / gdm_wgrad_x1_bytes
+ * and gdm_wgrad_go_bytes must each stay below 2 GiB, or the call is refused on the host. */
 int gdm_conv1x1_packed_wb_hip(const void* xpk, const void* wpk, long w_bstride, int B, int Cin, int Cout, int H, int W, float* out,
                               void* stream);
 

@@ -33,7 +33,7 @@ for it in range(40):
 # gemm
 for it in range(30):
     B, Cin, Cout, n = rs.randint(1, 3), int(rs.choice([64, 128, 256, 384])), rs.randint(1, 700), 32 * rs.randint(1, 40)
-    if not ops.gemm_supported(Cin, Cout, n): continue
+    if not ops.gemm_supported(Cin, Cout, n, B): continue
     x = torch.randn(B, Cin, n, device="cuda"); w = torch.randn(Cout, Cin, device="cuda") / Cin ** 0.5
     got = ops.gemm_bf16x3(x, ops.gemm_pack_weight(w), Cout)
     ref = torch.matmul(w.double(), x.double())
@@ -72,7 +72,7 @@ for it in range(12):
     got = ops.conv3x3_bf16x3(xp, ops.conv3x3_pack_weight(w), Cout, stride=2)
     ref = torch.nn.functional.conv2d(x.double(), w.double(), stride=2, padding=1)
     chk("conv3x3 s2", (got.double() - ref).abs().max().item() < 3e-5 * max(1.0, ref.abs().max().item()), (B, Cin, Cout, Ho, Wo))
-    if ops.gemm_supported(Cin, Cout, 64):
+    if ops.gemm_supported(Cin, Cout, 64, 1):
         w1 = torch.randn(Cout, Cin, device="cuda") / Cin ** 0.5
         got1 = ops.conv1x1_packed2d(xp, ops.gemm_pack_weight(w1), Cout, stride=2)
         ref1 = torch.nn.functional.conv2d(x.double(), w1.double()[:, :, None, None], stride=2)
