@@ -335,6 +335,7 @@ extern "C" size_t gdm_circle_match_tp_bytes(int n) { return n < 1 ? 0 : (size_t)
 extern "C" int gdm_circle_match_pack_hip(const float* x, int n, void* rows, void* tp, float* rowsum, void* stream)
 {
     GDM_CHECK_ARG(x && rows && tp && rowsum && n >= 1, "gdm_circle_match_pack_hip: NULL pointer or n=%d", n);
+    GDM_CHECK_ARG((((uintptr_t)rows | (uintptr_t)tp) & 15) == 0, "gdm_circle_match_pack_hip: rows and tp must be 16-byte aligned");
     const int np = (n + 127) / 128 * 128;
     hipLaunchKernelGGL(cm_pack_kernel, dim3(np / 32), dim3(256), 0, (hipStream_t)stream, x, n, (unsigned char*)rows, (unsigned char*)tp, rowsum);
     return gdm_launch_status("cm_pack_kernel");
@@ -370,6 +371,7 @@ static int fill_args(CmArgs& a, const void* xrows, const void* xtp, const float*
 {
     GDM_CHECK_ARG(xrows && xtp && xsum && yrows && ytp && g && item, "%s: NULL pointer", who);
     GDM_CHECK_ARG(R >= 1 && M >= 1, "%s: R=%d M=%d", who, R, M);
+    GDM_CHECK_ARG((((uintptr_t)xrows | (uintptr_t)xtp | (uintptr_t)yrows | (uintptr_t)ytp) & 15) == 0, "%s: the packed rows must be 16-byte aligned", who);
     GDM_CHECK_ARG(c2 || (nbr && visb), "%s: either the symmetric columns (c2) or the neighbour / visibility bit tables are needed", who);
     GDM_CHECK_ARG(gamma > 0.f && m >= 0.f && m < 1.f && gamma * (2.f + m) * (2.f - m) < 150.f, "%s: gamma=%g m=%g outside the fp32 exp range", who, gamma, m);
     a.xrows = (const unsigned char*)xrows; a.xtp = (const unsigned char*)xtp; a.xsum = xsum;

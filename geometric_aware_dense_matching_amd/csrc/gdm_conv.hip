@@ -540,6 +540,9 @@ int conv_launch(dim3 grid, int smem, hipStream_t s, const ConvArgs& a)
     // every operand load is 16 bytes wide, and so is every store of the pack kernels that write these buffers
     GDM_CHECK_ARG((((uintptr_t)a.xpk | (uintptr_t)a.wpk) & 15) == 0,
                   "%s: the packed operands must be 16-byte aligned (xpk %p, wpk %p)", a.who, a.xpk, a.wpk);
+    // the epilogue adds the residual and stores the result four pixels (or four channels) at a time
+    GDM_CHECK_ARG((((uintptr_t)a.res | (uintptr_t)a.out) & 15) == 0, "%s: res and out must be 16-byte aligned (res %p, out %p)", a.who,
+                  (const void*)a.res, (const void*)a.out);
     constexpr auto kernel = conv_mfma16_kernel<ACT, RES, TAPS, PM, NKS, NCB, WV, GADD>;
     gdm_allow_lds<kernel>(GADD ? LDS_MAX : conv_lds_bytes(NCB));
     hipLaunchKernelGGL(kernel, grid, dim3(WV * 64), smem, s, (const unsigned char*)a.xpk, (const unsigned char*)a.wpk, a.scale, a.shift, a.res,

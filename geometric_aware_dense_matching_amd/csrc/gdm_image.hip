@@ -1265,7 +1265,7 @@ extern "C" int gdm_psp_combine2_hip(const float* g, const float* y1, int s1, con
     if (gx > 16) gx = 16;
     if (outpk) {
         GDM_CHECK_ARG(C % 8 == 0 && W % 4 == 0 && ((uintptr_t)outpk & 15) == 0 && (C == 64 || C % 128 == 0),
-                      "gdm_psp_combine2_hip: packed output needs C = 64 or a multiple of 128 and W %% 4 == 0 (C=%d W=%d)", C, W);
+                      "gdm_psp_combine2_hip: packed output needs C = 64 or a multiple of 128, W %% 4 == 0 and a 16-byte aligned buffer (C=%d W=%d)", C, W);
         hipLaunchKernelGGL(psp_combine8_kernel, dim3(gx, B * C / 8), dim3(256), 0, (hipStream_t)stream, g, maps, bias, C, H, W, out,
                            (unsigned char*)outpk);
         return gdm_launch_status("psp_combine8_kernel");
@@ -1300,6 +1300,7 @@ extern "C" int gdm_conv1x1_gather_add_act2_hip(const float* x, const float* wt, 
     GDM_CHECK_ARG(x && wt && t && idx && scale && shift && y, "gdm_conv1x1_gather_add_act2_hip: NULL pointer");
     GDM_CHECK_ARG(C == 64, "gdm_conv1x1_gather_add_act2_hip: C=%d, only the 64-channel fusion levels are built", C);
     GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && act >= 0 && act <= 2, "gdm_conv1x1_gather_add_act2_hip: bad shape");
+    GDM_CHECK_ARG(!pixel_major || ((uintptr_t)y & 15) == 0, "gdm_conv1x1_gather_add_act2_hip: a pixel-major y must be 16-byte aligned (its rows are stored four channels at a time)");
     dim3 grid(gdm_cdiv(m, 256), B);
     hipStream_t s = (hipStream_t)stream;
     gdm_dispatch_int<3>(act, [&](auto A) {

@@ -1110,6 +1110,7 @@ extern "C" int gdm_match_packed_hip(const void* scene_rows, const void* model_ro
     GDM_CHECK_ARG(scene_rows && model_rows && best_idx && best_sim && partial, "gdm_match_packed_hip: NULL pointer");
     GDM_CHECK_ARG(R >= 1 && M >= 1, "gdm_match_packed_hip: bad shape R=%d M=%d", R, M);
     GDM_CHECK_ARG(precision == GDM_MATCH_BF16X3 || precision == GDM_MATCH_F32, "gdm_match_packed_hip: precision=%d", precision);
+    GDM_CHECK_ARG((((uintptr_t)scene_rows | (uintptr_t)model_rows) & 15) == 0, "gdm_match_packed_hip: the packed rows must be 16-byte aligned");
     const size_t half = align256(64 * (size_t)R * sizeof(float));
     if (partial_bytes < 2 * half) {
         gdm_set_error("gdm_match_packed_hip: partial workspace %zu < %zu bytes", partial_bytes, 2 * half);
@@ -1194,6 +1195,7 @@ extern "C" int gdm_match_soft_packed_hip(const void* scene_rows, const void* mod
     GDM_CHECK_ARG(gamma > 0.f && gamma <= GDM_MATCH_SOFT_MAX_GAMMA, "gdm_match_soft_packed_hip: gamma=%g not in (0, %g]", (double)gamma,
                   (double)GDM_MATCH_SOFT_MAX_GAMMA);                       // a NaN fails both comparisons
     GDM_CHECK_ARG(((uintptr_t)partial & 15) == 0, "gdm_match_soft_packed_hip: partial must be 16-byte aligned");
+    GDM_CHECK_ARG((((uintptr_t)scene_rows | (uintptr_t)model_rows) & 15) == 0, "gdm_match_soft_packed_hip: the packed rows must be 16-byte aligned");
     const size_t half = align256(64 * (size_t)R * sizeof(float));
     const size_t need = 2 * half + align256(64 * (size_t)R * sizeof(float4));
     if (partial_bytes < need) {

@@ -238,6 +238,7 @@ int fill_args(ScArgs& a, const void* xrows, const void* xtp, const void* yrows, 
     GDM_CHECK_ARG(R >= 1 && M >= 1, "%s: R=%d M=%d", who, R, M);
     GDM_CHECK_ARG(R <= (1 << 30) && M <= (1 << 30), "%s: R=%d M=%d beyond 2^30", who, R, M);
     GDM_CHECK_ARG(gamma > 0.f && gamma <= GDM_SOFT_COORD_MAX_GAMMA, "%s: gamma=%g outside (0, %g]", who, (double)gamma, (double)GDM_SOFT_COORD_MAX_GAMMA);
+    GDM_CHECK_ARG((((uintptr_t)xrows | (uintptr_t)xtp | (uintptr_t)yrows | (uintptr_t)ytp) & 15) == 0, "%s: the packed rows must be 16-byte aligned", who);
     a.xrows = (const unsigned char*)xrows; a.xtp = (const unsigned char*)xtp;
     a.yrows = (const unsigned char*)yrows; a.ytp = (const unsigned char*)ytp;
     a.xyz = xyz;
@@ -273,6 +274,7 @@ extern "C" int gdm_soft_coord_bwd_hip(const void* xrows, const void* xtp, const 
     if (rc) return rc;
     GDM_CHECK_ARG(lse && kb && (gx || gy), "gdm_soft_coord_bwd_hip: NULL pointer");
     GDM_CHECK_ARG(!gy || gy_part, "gdm_soft_coord_bwd_hip: gy needs the gy_part workspace");
+    GDM_CHECK_ARG((((uintptr_t)kb | (uintptr_t)gy_part | (uintptr_t)gy) & 15) == 0, "gdm_soft_coord_bwd_hip: kb, gy_part and gy must be 16-byte aligned");
     a.lse = const_cast<float*>(lse); a.kb = kb;
     if (gx) {                                                       // either gradient may be left out (NULL): its launches are skipped
         a.gout = gx;

@@ -764,7 +764,9 @@ extern "C" int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* w
     GDM_CHECK_ARG(x && wpk && t && idx && scale && shift && y, "gdm_conv64_gather_add_act_mfma2_hip: NULL pointer");
     GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && m <= 0x7fffffffL && act >= 0 && act <= 2, "gdm_conv64_gather_add_act_mfma2_hip: bad shape");
     GDM_CHECK_ARG(!ypk || (!pixel_major && W >= 1 && m % W == 0 && ((uintptr_t)ypk & 15) == 0),
-                  "gdm_conv64_gather_add_act_mfma2_hip: packed output goes with the NCHW form of an [m / W, W] map (m=%ld W=%d)", m, W);
+                  "gdm_conv64_gather_add_act_mfma2_hip: packed output goes with the NCHW form of an [m / W, W] map and a 16-byte aligned buffer (m=%ld W=%d)", m, W);
+    GDM_CHECK_ARG((!t_point_major || ((uintptr_t)t & 15) == 0) && (!pixel_major || ((uintptr_t)y & 15) == 0),
+                  "gdm_conv64_gather_add_act_mfma2_hip: a point-major t and a pixel-major y must be 16-byte aligned (read / written four channels at a time)");
     unsigned char* ypk8 = (unsigned char*)ypk;
     dim3 grid(gdm_cdiv(m, CG_P), B);
     hipStream_t s = (hipStream_t)stream;
@@ -785,6 +787,7 @@ extern "C" int gdm_conv64_gather_add_final_hip(const float* x, const void* wpk, 
 {
     GDM_CHECK_ARG(x && wpk && t && idx && scale && shift && wft && out, "gdm_conv64_gather_add_final_hip: NULL pointer");
     GDM_CHECK_ARG(B >= 1 && B <= 65535 && n >= 1 && m >= 1 && m <= 0x7fffffffL && act >= 0 && act <= 2, "gdm_conv64_gather_add_final_hip: bad shape");
+    GDM_CHECK_ARG(((uintptr_t)t & 15) == 0, "gdm_conv64_gather_add_final_hip: t must be 16-byte aligned (its rows are read four channels at a time)");
     dim3 grid(gdm_cdiv(m, CG_P), B);
     hipStream_t s = (hipStream_t)stream;
     gdm_dispatch_int<3>(act, [&](auto A) {

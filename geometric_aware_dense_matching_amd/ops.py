@@ -868,6 +868,8 @@ def affine_act(x, scale, shift, act=ACT_NONE, slope=0.0, res=None, res_scale=Non
         return y
     if res is not None:
         res = _dev(res, torch.float32, "res")
+        if res.data_ptr() % 16:
+            res = res.clone()                        # the kernel reads it four elements at a time
         assert res.shape == x.shape
     y = x if inplace else torch.empty_like(x)
     call("gdm_affine_act_hip", x, scale, shift, res, res_scale, res_shift, B * C, C, inner, act, float(slope), y)
@@ -1510,6 +1512,8 @@ def conv64_gather_add_act_mfma(x, wpk, t, idx, scale, shift, act=ACT_NONE, slope
     idx = _idx32(idx, "idx")
     B, C, m = x.shape
     n = t.shape[1] if t_point_major else t.shape[2]
+    if t_point_major and t.data_ptr() % 16:
+        t = t.clone()                                # the kernel reads a point's row four channels at a time
     if C != 64 or t.shape[2 if t_point_major else 1] != 64 or wpk.numel() != 64 * 256:
         raise ValueError("conv64_gather_add_act_mfma: built for 64 -> 64 channels, got x %s t %s" % (tuple(x.shape), tuple(t.shape)))
     y = torch.empty((B, m, C), dtype=torch.float32, device=x.device) if pixel_major else torch.empty_like(x)
@@ -1674,6 +1678,8 @@ def conv64_gather_add_final(x, wpk, t, idx, scale, shift, act, slope, final_weig
         raise ValueError("conv64_gather_add_final: built for 64 -> 64 -> 64 channels, got x %s t %s final %s"
                          % (tuple(x.shape), tuple(t.shape), tuple(final_weight.shape)))
     wft = _final_weight_t(final_weight)
+    if t.data_ptr() % 16:
+        t = t.clone()                                # the kernel reads a point's row four channels at a time
     out = torch.empty_like(x)
     call("gdm_conv64_gather_add_final_hip", x, wpk, t, idx, scale, shift, B, t.shape[1], m, act, float(slope), wft, final_bias, out)
     return out
@@ -1950,6 +1956,8 @@ def conv3x3_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, res=None,
         opk = PackedAct(_packed_buffer(B, cout, H, W, dev, avoid=xp.buf), (B, cout, H, W))
     if res is not None:
         res = _dev(res, torch.float32, "res")
+        if res.data_ptr() % 16:
+            res = res.clone()                        # the epilogue reads the residual four pixels at a time
         assert tuple(res.shape) == (B, cout, H, W)
     call("gdm_conv3x3_strided_hip", xp.buf, wpk, scale, shift, res, B, Cin, cout, H, W, int(stride), act, out,
          opk.buf if opk is not None else None)

@@ -167,6 +167,7 @@ int gdm_match_pack_hip(const float* x, int R, int D, int n, int precision, void*
  * gdm_match_pack_hip(x1, R1, D, n1, ..., rows1) + gdm_match_pack_hip(x2, R2, D, n2, ..., rows2) */
 int gdm_match_pack2_hip(const float* x1, int R1, int n1, void* rows1, const float* x2, int R2, int n2, void* rows2,
                         int D, int precision, void* stream);
+/* scene_rows, model_rows and partial must be 16-byte aligned (also for gdm_match_soft_packed_hip). */
 int gdm_match_packed_hip(const void* scene_rows, const void* model_rows, int R /* B*N */, int M, int precision,
                          int32_t* best_idx, float* best_sim, float* sim,
                          void* partial, size_t partial_bytes, void* stream);
@@ -352,6 +353,7 @@ int gdm_circle_rows_bwd_hip(const float* sim, int R, int Mp, const int32_t* matc
  * and `xpad` holds x[r][0].                                                                                                       */
 size_t gdm_circle_match_rows_bytes(int n);
 size_t gdm_circle_match_tp_bytes(int n);
+/* rows / tp (and xrows, xtp, yrows, ytp below) must be 16-byte aligned. */
 int gdm_circle_match_pack_hip(const float* x, int n, void* rows, void* tp, float* rowsum, void* stream);
 int gdm_circle_match_nbr_hip(const float* xyz, int M, float radius, uint32_t* nbr, void* stream);
 int gdm_circle_match_visbits_hip(const uint8_t* vis, int B, int M, uint32_t* bits, void* stream);
@@ -380,7 +382,8 @@ int gdm_circle_match_bwd_parts(int R, int M);
  *          gx or gy may be NULL (not both): that gradient's launches are skipped (gy_part is needed with gy only).
  * Padded columns weigh nothing and padded rows add nothing, whatever lies beyond R in the caller's buffers (those are not read).
  * 0 < gamma <= GDM_SOFT_COORD_MAX_GAMMA (every term >= e^-80, a normal fp32: the fixed shift 1 needs no running maximum);
- * anything else, a NaN included, is refused with GDM_EINVAL before any launch. */
+ * anything else, a NaN included, is refused with GDM_EINVAL before any launch, and so are packed rows, kb, gy_part or gy off a
+ * 16-byte boundary. */
 #define GDM_SOFT_COORD_MAX_GAMMA 40.0f
 int gdm_soft_coord_fwd_hip(const void* xrows, const void* xtp, const void* yrows, const void* ytp, const float* xyz, int R, int M,
                            float gamma, float* lse, float* soft, void* stream);
@@ -586,7 +589,7 @@ int gdm_gather_add_affine_act2_hip(const float* x, const float* t, const int32_t
                                    int B, int C, int n, int m, int act, float slope, float* y, void* y_packed, int W, void* stream);
 /* The same tail with the pixel half of the 1x1 convolution inside, for the 64-channel levels (C == 64):
  * y[b,co,j] = act(scale[co]*(sum_ci W[co,ci] x[b,ci,j] + t[b,co,idx[b,j]]) + shift[co]); wt f32[C,C] = W transposed ([ci][co]).
- * pixel_major = 0 writes y f32[B, C, m]; != 0 writes y f32[B, m, C] (one 256-byte row per pixel). */
+ * pixel_major = 0 writes y f32[B, C, m]; != 0 writes y f32[B, m, C] (one 256-byte row per pixel, y 16-byte aligned). */
 int gdm_conv1x1_gather_add_act2_hip(const float* x, const float* wt, const float* t, const int32_t* idx, const float* scale,
                                     const float* shift, int B, int C, int n, long m, int act, float slope, int pixel_major,
                                     float* y, void* stream);
@@ -594,14 +597,15 @@ int gdm_conv1x1_gather_add_act2_hip(const float* x, const float* wt, const float
  * output channel) packed by gdm_pack_rows64_hip; t_point_major != 0: t is f32[B, n, 64] (the gathered term is then one contiguous
  * 256-byte row per pixel instead of 64 scattered floats); pixel_major and the other arguments as above.  With ypk != NULL (NCHW form
  * only) the result is ALSO written as the packed split-bf16 operand of the next convolution over the [B, 64, m / W, W] map
- * (gdm_conv3x3_act_bytes(B, 64, m / W, W) bytes, zero border kept by the caller).  W is read only with ypk. */
+ * (gdm_conv3x3_act_bytes(B, 64, m / W, W) bytes, zero border kept by the caller).  W is read only with ypk.  A point-major t, a
+ * pixel-major y and ypk must be 16-byte aligned (GDM_EINVAL otherwise). */
 int gdm_conv64_gather_add_act_mfma2_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
                                         const float* shift, int B, int n, long m, int act, float slope, int pixel_major,
                                         int t_point_major, float* y, void* ypk, int W, void* stream);
 /* That fusion (NCHW form, point-major t f32[B, n, 64]) and the `final` stage behind it in one launch, for a fused map only `final`
  * reads: out f32[B, 64, m] = log_softmax_c(Wf . y + fbias) with y the map gdm_conv64_gather_add_act_mfma2_hip would write; the same
  * bits as that call followed by gdm_conv1x1_logsoftmax_hip, without the map between them.  wft f32[64, 64] = the `final` weight
- * transposed ([ci][co]), fbias f32[64] or NULL. */
+ * transposed ([ci][co]), fbias f32[64] or NULL.  t must be 16-byte aligned. */
 int gdm_conv64_gather_add_final_hip(const float* x, const void* wpk, const float* t, const int32_t* idx, const float* scale,
                                     const float* shift, int B, int n, long m, int act, float slope, const float* wft,
                                     const float* fbias, float* out, void* stream);
@@ -624,6 +628,7 @@ size_t gdm_conv3x3_act_bytes(int B, int Cin, int H, int W);
 size_t gdm_conv3x3_weight_bytes(int Cout, int Cin);
 int gdm_conv3x3_pack_weight_hip(const float* w, int Cout, int Cin, void* wpk, void* stream);
 int gdm_conv3x3_pack_act_hip(const float* x, int B, int Cin, int H, int W, void* xpk, void* stream);
+/* Every convolution / GEMM entry below refuses (GDM_EINVAL) packed operands, a residual or an output off a 16-byte boundary. */
 int gdm_conv3x3_packed_hip(const void* xpk, const void* wpk, const float* scale, const float* shift, const float* res,
                            int B, int Cin, int Cout, int H, int W, int act, float* out, void* stream);
 /* Strided forms (stride 1 or 2; the first block of ResNet-18 layer2, extractors.py:151-177): H, W are the OUTPUT size, xpk is the
