@@ -340,7 +340,8 @@ def test_training_step_fused_path_equals_module_path(monkeypatch):
     """One whole training step of the variant (N = 512, M = 384, k = 16 / 20, B = 2): `train_path = "fused"` against the module path
     with the fused path's six graphs injected (feature-space graphs differ at fp32 near-ties otherwise: a property of the kNN) --
     loss, running variances, relative L2 distance d over all parameter gradients, against the distance `noise` of the module path
-    from itself on an input moved by one fp32 rounding."""
+    from itself on an input moved by one fp32 rounding.  The tight check is
+    tests/test_gpu_step_compare.py::test_dgcnn_step_on_the_fused_path_equals_the_module_path_per_parameter: the same A/B per parameter."""
     from geometric_aware_dense_matching_amd import dgcnn, train_lm
     M, N, B = 384, 512, 2
     dev = torch.device("cuda", 0)

@@ -417,7 +417,7 @@ def test_fused_syncbatchnorm_two_ranks_equals_whole_batch_batchnorm():
     assert out.get() == "ok"
 
 
-def _rccl_group_of_one_worker(port, out):
+def _rccl_group_of_one_worker(rank, world, port, out):
     import os
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
@@ -453,27 +453,81 @@ def _rccl_group_of_one_worker(port, out):
         l1, g1 = run(ddp)
         den = sum((v ** 2).sum().item() for v in g0.values()) ** 0.5
         d = sum(((g1[k] - g0[k]) ** 2).sum().item() for k in g0) ** 0.5 / den
-        out.put((l0, l1, d, n_sync, len(g0), set(g0) == set(g1), dist.get_backend()))
+        # the same comparison per parameter on a conditioned step (tests/step_compare.py): BatchNorm eps 1e-2 in both arms, the
+        # neighbour pyramid built once; yardstick = the module path of the plain model against itself on inputs moved by 2^-23
+        import step_compare as sc
+        torch.manual_seed(0)
+        plain = GeoMatch(make_model_cfg(n_mesh_node=M, num_points=N), 1, model_points=synthetic.make_model_points(1, M)).to(dev).train()
+        sc.condition(plain, 1e-2)
+        sc.condition(sync, 1e-2)
+        state2 = {k: v.clone() for k, v in plain.state_dict().items()}
+        ds4 = train_lm.SyntheticCrops(4, N, M, seed=5)                # four items: twice the values per BatchNorm channel
+        fixed = sc.freeze_pyramid(torch.utils.data.default_collate([ds4[i] for i in range(4)]), dev)
+        _, nz = sc.noise(plain, fixed, dev, state=state2, delta=sc.DELTA_SAME, buffers=("model_emb.mesh_graph_x",))
+        step0 = sc.run_step(plain, fixed, dev, state=state2)
+        step1 = sc.run_step(ddp, fixed, dev, state=state2)
+        rep = sc.compare(step1, step0, nz, what="DDP + SyncBatchNorm in an RCCL group of one against the plain step")
+        # a summary, not the table: the report names at most 25 failing tensors, so what goes through the pipe stays a few KiB
+        table = dict(text=str(rep), ok=rep.ok, worst=rep.worst, resolution=sc.resolution(nz), coarse=sc.resolution(nz, below=sc.COARSE),
+                     n_grads=len(step1.grads))
+        out.put((l0, l1, d, n_sync, len(g0), set(g0) == set(g1), dist.get_backend(), table))
     finally:
         settings.SYNCBN_MIN_WORLD = 2
         dist.destroy_process_group()
+
+
+def _run_workers(target, world, limit=600):
+    """Start `world` spawned processes target(rank, world, port, out), take rank 0's result from the queue BEFORE joining (a child
+    blocked in a full pipe never exits), and leave no process behind: whatever is still alive afterwards is terminated."""
+    import socket
+    import time
+    import torch.multiprocessing as mp
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    ctx = mp.get_context("spawn")
+    out = ctx.SimpleQueue()
+    procs = [ctx.Process(target=target, args=(r, world, port, out)) for r in range(world)]
+    for p in procs:
+        p.start()
+    result, deadline = None, time.monotonic() + limit
+    try:
+        while result is None and time.monotonic() < deadline and all(p.exitcode in (None, 0) for p in procs):
+            if not out.empty():
+                result = out.get()
+            elif all(p.exitcode == 0 for p in procs):
+                break
+            else:
+                procs[0].join(0.05)
+        for p in procs:
+            p.join(max(0.0, min(60.0, deadline - time.monotonic())))
+    finally:
+        codes = [p.exitcode for p in procs]
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+                p.join(10)
+    assert codes == [0] * world and result is not None, (codes, result is not None)
+    return result
+
+
+_RCCL_GROUP_OF_ONE = []
+
+
+def _rccl_group_of_one_result():
+    """What the worker returns; the process is started by whichever of the two tests below runs first, once."""
+    if not _RCCL_GROUP_OF_ONE:
+        _RCCL_GROUP_OF_ONE.append(_run_workers(_rccl_group_of_one_worker, 1))
+    return _RCCL_GROUP_OF_ONE[0]
 
 
 def test_training_step_under_ddp_and_syncbn_in_an_rccl_group_of_one():
     """RCCL on the card at hand: one rank joins an `nccl` process group, the model is converted to SyncBatchNorm and wrapped in
     DistributedDataParallel as parallel.wrap_for_training does for N ranks (/root/reference/train_lm.py:412,436-439), and -- with
     settings.SYNCBN_MIN_WORLD = 1 -- every fused BatchNorm sends its fp64 statistics through `dist.all_reduce` on the device in both
-    directions.  A group of one changes no number: loss and gradients equal the plain single-process step (same dropout seed)."""
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    ctx = mp.get_context("spawn")
-    out = ctx.SimpleQueue()
-    p = ctx.Process(target=_rccl_group_of_one_worker, args=(port, out))
-    p.start()
-    p.join(600)
-    assert p.exitcode == 0
-    l0, l1, d, n_sync, n_grads, same_keys, backend = out.get()
+    directions.  A group of one changes no number: loss and gradients equal the plain single-process step (same dropout seed).
+
+    The global distance below is the loose form.  The tight check is the next test, from the same worker: every parameter on a conditioned
+    step (tests/step_compare.py, profiles/step_compare.md)."""
+    l0, l1, d, n_sync, n_grads, same_keys, backend, _ = _rccl_group_of_one_result()
     print("RCCL group of one: loss %.6f vs %.6f, gradient distance %.3e, %d SyncBatchNorm layers, %d gradients" % (l0, l1, d, n_sync, n_grads))
     assert backend == "nccl" and n_sync > 80 and n_grads > 300 and same_keys
     # What "no number changes" can mean here: a randomly initialised network on a batch of 2 has channels whose batch variance is ~eps, and
@@ -482,6 +536,82 @@ def test_training_step_under_ddp_and_syncbn_in_an_rccl_group_of_one():
     # the order of a few fp64 partial sums and in whatever the allocator's alignment does to kernel selection: seen 4e-5 alone in a
     # process, 9e-2 inside the whole suite.  A wrong statistic (a missing or doubled reduction, a wrong count) is an O(1) error.
     assert abs(l1 - l0) < 1e-3 * abs(l0) and d < 0.35, (l0, l1, d)
+
+
+def test_training_step_under_ddp_and_syncbn_in_an_rccl_group_of_one_per_parameter():
+    """The tight form of the test above, from the same worker: on a conditioned step (BatchNorm eps 1e-2) every parameter gradient, every
+    running statistic and the loss of the DDP + SyncBatchNorm step are within 10 x the 2^-23 yardstick of the plain step.  What a
+    group of one can show: the route through the collectives (SyncBatchNorm conversion, fp64 statistics through RCCL and back, DDP's
+    hooks and buckets) loses or rewires no tensor.  What it cannot: with one rank an all-reduce is the identity and every count is the
+    local one, so a bucket reduced twice or a wrong cross-rank count changes no number here -- that is the two-rank test below."""
+    table = _rccl_group_of_one_result()[7]
+    print("RCCL group of one per parameter: worst distance / bound %.3f at %s; %d gradients; yardstick resolution %.3f, share below 0.5 %.3f"
+          % (table["worst"] + (table["n_grads"], table["resolution"], table["coarse"])))
+    assert table["n_grads"] > 300 and table["coarse"] >= 0.95
+    assert table["ok"], table["text"]
+
+
+def _two_rank_worker(rank, world, port, out):
+    import os
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import step_compare as sc
+        from geometric_aware_dense_matching_amd import parallel, train_lm
+        from geometric_aware_dense_matching_amd.geoMatch import GeoMatch
+        M, N, B = 512, 1024, 4
+
+        def make():
+            torch.manual_seed(0)
+            m = GeoMatch(make_model_cfg(n_mesh_node=M, num_points=N), 1, model_points=synthetic.make_model_points(1, M)).to(dev).train()
+            m.model_emb.dropout = 0.0                 # no dropout in either arm: a half batch would draw other masks than the whole
+            for mod in m.modules():                   # (the image trunk's Dropout2d masks are per item and channel)
+                if isinstance(mod, torch.nn.modules.dropout._DropoutNd):
+                    mod.p = 0.0
+            sc.condition(m, 1e-2)
+            return m
+
+        ds = train_lm.SyntheticCrops(B, N, M, seed=5)
+        whole = sc.freeze_pyramid(torch.utils.data.default_collate([ds[i] for i in range(B)]), dev)
+        assert int((whole["labels"] == 1).sum(1).min()) >= 3      # no item is skipped: the loss is a plain mean over the items
+        lo, hi = rank * B // world, (rank + 1) * B // world
+        half = {k: (v[lo:hi] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for k, v in whole.items()}
+        plain = make()
+        state = {k: v.clone() for k, v in plain.state_dict().items()}
+        ddp = parallel.wrap_for_training(make(), local_rank=0)    # SyncBatchNorm + DDP, as the trainer wraps a model for N ranks
+        n_sync = sum(isinstance(mod, torch.nn.SyncBatchNorm) for mod in ddp.modules())
+        got = sc.run_step(ddp, half, dev, state=state)            # half the batch here, statistics and gradients over both ranks
+        loss = torch.tensor([got.loss], dtype=torch.float64)
+        dist.all_reduce(loss)
+        got.loss = float(loss) / world
+        if rank == 0:
+            _, nz = sc.noise(plain, whole, dev, state=state, delta=sc.DELTA_SAME, buffers=("model_emb.mesh_graph_x",))
+            ref = sc.run_step(plain, whole, dev, state=state)     # one process, the whole batch, plain BatchNorm
+            # The mesh branch is no function of the batch (both ranks run the same M vertices), but it holds no BatchNorm, so no
+            # statistic is taken over its rows twice: every running statistic of the step is comparable as it stands.
+            assert not any(k.startswith("model_emb.") for k in ref.stats)
+            rep = sc.compare(got, ref, nz, what="two ranks with half the batch each against one process on the whole batch")
+            out.put(dict(text=str(rep), ok=rep.ok, worst=rep.worst, n_grads=len(got.grads), n_stats=len(got.stats), n_sync=n_sync,
+                         coarse=sc.resolution(nz, below=sc.COARSE)))
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_training_step_on_two_ranks_with_half_the_batch_each_equals_one_process_per_parameter():
+    """Two gloo ranks on this card, two of the four items each, through parallel.wrap_for_training (SyncBatchNorm + DDP) against one
+    process on all four items with plain BatchNorm, on the conditioned step (eps 1e-2, no dropout): every parameter gradient, running
+    statistic and the loss within 10 x the 2^-23 yardstick.  Here the collectives are not the identity: a gradient bucket reduced
+    twice doubles every gradient, a wrong element count in a SyncBatchNorm reduction moves that layer's statistics and everything
+    behind it."""
+    r = _run_workers(_two_rank_worker, 2)
+    print("two ranks per parameter: worst distance / bound %.3f at %s; %d gradients, %d running statistics, %d SyncBatchNorm layers; "
+          "share of bounds below 0.5 %.3f" % (r["worst"] + (r["n_grads"], r["n_stats"], r["n_sync"], r["coarse"])))
+    assert r["n_grads"] > 300 and r["n_stats"] > 160 and r["n_sync"] > 80 and r["coarse"] >= 0.95
+    assert r["ok"], r["text"]
 
 
 def test_training_step_through_fused_paths_equals_module_paths():
@@ -495,7 +625,9 @@ def test_training_step_through_fused_paths_equals_module_paths():
     per output) 8e-2; the fused BatchNorm (fp64 sums against MIOpen's fp32 sums) 5e-2; everything 1.1e-1, loss 8e-5.  So the exact
     paths are held to 3e-2, and the full set to a bound that only an O(1) error -- a dropped term, a wrong scale -- would break; the
     per-operator tests above hold each kernel to 1e-4 .. 1e-5 against fp64.  What holds each kernel tightly ON THE DATA OF SUCH A STEP is
-    the per-call replay of tests/test_gpu_train_replay.py: every autograd Function of the step against fp64 on its own recorded inputs."""
+    the per-call replay of tests/test_gpu_train_replay.py: every autograd Function of the step against fp64 on its own recorded inputs.
+    What holds the GLUE between those calls is tests/test_gpu_step_compare.py: the same A/B per parameter on a conditioned step, where a
+    dropped, doubled or mis-wired gradient of any single tensor is rejected (one L2 over 300 gradients at 0.35 accepts all of those)."""
     from geometric_aware_dense_matching_amd import cnn, ops, train_lm
     from geometric_aware_dense_matching_amd.geoMatch import GeoMatch
     M, N, B = 512, 1024, 2

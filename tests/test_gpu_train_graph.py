@@ -73,7 +73,9 @@ def test_graphed_training_iterations_equal_the_eager_loop():
     3 replays) against the plain loop model_fn_dec -> backward -> Adam.step -> zero_grad.  Same kernels in the same order on both
     sides; what differs is the summation order of the atomics, which train-mode BatchNorm on a small batch amplifies (see
     test_training_step_through_fused_paths_equals_module_paths), so the loss trajectory is held to 10x what the eager loop differs from ITSELF run twice, and the
-    parameters to the size of the Adam steps taken.  A cyclic learning rate is stepped between iterations on both sides (the capture reads it from the device)."""
+    parameters to the size of the Adam steps taken.  A cyclic learning rate is stepped between iterations on both sides (the capture reads it from the device).
+    The tight check is test_graphed_training_iterations_equal_the_eager_loop_per_tensor below: parameters, Adam's exp_avg and running
+    statistics per tensor, on a conditioned step."""
     from geometric_aware_dense_matching_amd import train_lm
     from geometric_aware_dense_matching_amd.train_graph import GraphedTrainStep
     M, N, B, steps = 512, 1024, 4, 6
@@ -143,3 +145,85 @@ def test_bn_momentum_change_recaptures():
     assert stepper.captures == 2 and np.isfinite(float(out["loss"]))
     with pytest.raises(ValueError):
         stepper.step({k: v[:1] for k, v in batch.items()})       # a short last batch is rejected, not silently mis-run
+
+
+def test_graphed_training_iterations_equal_the_eager_loop_per_tensor():
+    """The tight form of test_graphed_training_iterations_equal_the_eager_loop, on a conditioned step (BatchNorm eps 1e-2, set BEFORE
+    the stepper is built: a capture bakes eps in).  Six optimiser steps, cyclic learning rate; after them, per tensor
+    (tests/step_compare.py): Adam's exp_avg (the gradient history), the parameters' displacement from their initial values, the
+    running statistics, and the loss of every step -- each within 10 x the larger of two reference-only yardsticks: the eager loop
+    against itself, and against itself on images moved by a relative 2^-23 per pixel (four sign patterns; the clouds are left alone so
+    that every run builds the same neighbour pyramid).  That a stale input in the capture is rejected is shown at the end, on a
+    seeded one.
+
+    The displacement has one more term in its bound.  Adam's first steps are lr * sign(gradient) per element, so an element whose
+    gradient is at noise level at some step goes the other way there in one run and not in the next: a discontinuity that averages out
+    over a large tensor and does not over a one-element one (a PReLU slope went 13 x beyond the largest of three repetitions in one run
+    of the whole suite, with its exp_avg at 0.2 of the bound).  One element reversed at every step, 2 * sum(lr_t), is therefore
+    allowed on top of no yardstick at all: the bound is the larger of the two, which for a scalar is what the older test allows and for a
+    tensor of n elements about 2 / sqrt(n) of its displacement."""
+    import step_compare as sc
+    from geometric_aware_dense_matching_amd import train_lm
+    from geometric_aware_dense_matching_amd.train_graph import GraphedTrainStep
+    M, N, B, steps = 512, 1024, 4, 6
+    dev = torch.device("cuda", 0)
+    ds = train_lm.SyntheticCrops(B * steps, N, M, seed=3)
+    batches = [torch.utils.data.default_collate([ds[s * B + i] for i in range(B)]) for s in range(steps)]
+    init = {k: v.detach().double().clone() for k, v in _model(M, N, seed=7).named_parameters()}
+
+    def run(graphed, pattern=None, stale=None):
+        model = _model(M, N, seed=7)
+        sc.condition(model, 1e-2)
+        opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+        stepper = GraphedTrainStep(model, opt, dev) if graphed else None
+        sched = torch.optim.lr_scheduler.CyclicLR(opt, base_lr=1e-7, max_lr=1e-5, cycle_momentum=False, step_size_up=4, step_size_down=4)
+        losses, lrs = [], []
+        for s, b in enumerate(batches):
+            lrs.append(float(opt.param_groups[0]["lr"]))
+            if pattern is not None:
+                b = sc.perturbed(b, ("rgb",), sc.DELTA_SAME, 10 * pattern + s)
+            if s == stale:
+                b = batches[s - 1]                                # the seeded fault: this step sees the previous step's batch again
+            if graphed:
+                out = stepper.step(b)
+            else:
+                out, _ = train_lm.model_fn_dec(model, b, dev)
+                out["loss"].backward()
+                opt.step()
+                opt.zero_grad()
+            losses.append(float(torch.as_tensor(out["loss"]).detach()))
+            sched.step()
+        assert stepper is None or (stepper.captures == 1 and stepper.calls == steps)
+        names = {id(p): k for k, p in model.named_parameters()}
+        avg = {names[id(p)]: st["exp_avg"].detach().double().clone() for p, st in opt.state.items()}
+        moved = {k: p.detach().double() - init[k] for k, p in model.named_parameters() if k in avg}
+        stats = {k: v.detach().double().clone() for k, v in model.state_dict().items() if k.endswith(("running_mean", "running_var"))}
+        return sc.Step(losses[-1], avg, stats), sc.Step(losses[-1], moved, {}), np.array(losses), lrs
+
+    e_avg, e_moved, e_loss, lrs = run(False)
+    others = [run(False)] + [run(False, pattern=p) for p in range(4)]
+    g_avg, g_moved, g_loss, _ = run(True)
+    assert len(e_avg.grads) > 300 and min(v.norm().item() for v in e_moved.grads.values()) > 0      # the optimiser stepped every tensor it holds
+    yard = {}
+    for what, got, ref, k in (("exp_avg", g_avg, e_avg, 0), ("displacement", g_moved, e_moved, 1)):
+        nz = yard[what] = sc.noise_from(ref, [o[k] for o in others])
+        if what == "displacement":
+            for name, v in ref.grads.items():
+                nz.grads[name] = max(nz.grads[name], 2.0 * sum(lrs) / v.norm().item() / sc.MARGIN)
+        rep = sc.compare(got, ref, nz, what="graphed against eager, %s and running statistics" % what)
+        print("graphed against eager, %-12s: worst distance / bound %.3f at %s; yardstick resolution %.3f, share below 0.5 %.3f"
+              % ((what,) + rep.worst + (sc.resolution(nz), sc.resolution(nz, below=sc.COARSE))))
+        assert rep.ok, str(rep)
+    noise = np.max([np.abs(o[2] - e_loss) for o in others], axis=0) / np.abs(e_loss)
+    diff = np.abs(g_loss - e_loss) / np.abs(e_loss)
+    print("loss per step: graph-vs-eager %s; yardstick %s" % (" ".join("%.1e" % v for v in diff), " ".join("%.1e" % v for v in noise)))
+    assert (diff <= sc.MARGIN * np.maximum(noise, sc.NOISE_FLOOR)).all(), (diff, noise)
+    # The test has teeth: a captured loop whose fifth step (a replay) reads the fourth step's batch again is rejected, by the loss
+    # of that step and by exp_avg per tensor.
+    s_avg, _, s_loss, _ = run(True, stale=4)
+    rep = sc.compare(s_avg, e_avg, yard["exp_avg"], what="one stale batch in the captured loop, exp_avg")
+    s_diff = np.abs(s_loss - e_loss) / np.abs(e_loss)
+    print("seeded stale batch: %d of %d tensors beyond their bound, worst distance / bound %.1f at %s; loss of that step off by %.1e (bound %.1e)"
+          % ((len(rep.failures), len(rep.rows)) + rep.worst + (s_diff[4], sc.MARGIN * max(noise[4], sc.NOISE_FLOOR))))
+    assert s_diff[4] > sc.MARGIN * max(noise[4], sc.NOISE_FLOOR)
+    assert not rep.ok and len(rep.failures) >= 10
