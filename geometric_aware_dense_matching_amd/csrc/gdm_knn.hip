@@ -37,7 +37,7 @@
 //     support index (the reference orders them by KD-tree traversal, which is not reproducible).
 #include "gdm_common.h"
 #include <math.h>
-#include <stdlib.h>
+#include <algorithm>
 #include <vector>
 
 namespace {
@@ -56,16 +56,42 @@ struct KnnJobDev {
     int S, Q, K, logT;
     int blocks_per_b;                   // blocks that cover the Q queries of one batch item
     int block_begin;                    // first blockIdx.x of this job
-    const float4* packed;               // K > 1 only: the support set as hashed float4 tiles [B][ntiles][npad] (workspace), or null
-    const float* ranges;                // organised supports: per crop [col_lo W][col_hi W][row_lo H][row_hi H][bad, hole, -, -] (workspace)
-    int grid_w, grid_h;
+    union {                             // the support's layout in the workspace, by the kernel that searches it (K > 1 only)
+        const float4* packed;           // knn_wave_kernel: hashed float4 tiles [B][ntiles][npad], or null: gather from the [S,3] array
+        const float4* sorted;           // knn_cells_kernel: [B][S] (x, y, z, index) in cell order
+    };
+    union {
+        const unsigned* ranges;         // knn_grid_kernel: per crop [col_lo W][col_hi W][row_lo H][row_hi H][bad, hole per 16 rows] as ordered keys
+        const int* cells;               // knn_cells_kernel: [B][KC_META] cell starts and box
+    };
+    int grid_w, grid_h;                 // knn_grid_kernel only
 };
 
-struct KnnTable {
+struct KnnTable {                       // passed by value: 32 x 96 + 8 = 3080 of the 4096 bytes a kernel's arguments may take
     KnnJobDev jobs[GDM_KNN_MAX_JOBS];
     int njobs;
     int B;
 };
+static_assert(sizeof(KnnTable) == 3080, "KnnTable must not grow");
+
+// One search block: which job, which batch item, which block of that item's queries (all wave-uniform).
+struct KnnBlock {
+    const KnnJobDev& job;
+    int b, qb;
+    __device__ __forceinline__ int query(int per_block, int slot) const { return per_block * qb + slot; }
+    __device__ __forceinline__ const float* support() const { return job.support + (long long)b * job.support_bstride; }
+    __device__ __forceinline__ const float* query_point(int q) const { return job.query + (long long)b * job.query_bstride + (long long)q * 3; }
+};
+
+__device__ __forceinline__ KnnBlock decode_block(const KnnTable& tab, int bid)
+{
+    int j = 0;
+    while (j + 1 < tab.njobs && bid >= tab.jobs[j + 1].block_begin) ++j;
+    const KnnJobDev& job = tab.jobs[j];
+    const int local = bid - job.block_begin;
+    const int b = local / job.blocks_per_b;
+    return {job, b, local - b * job.blocks_per_b};
+}
 
 __device__ __forceinline__ float dist2_ref(float qx, float qy, float qz, float px, float py, float pz)
 {
@@ -86,26 +112,20 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_kernel(const KnnTable tab)
 {
     __shared__ float4 tile[KNN_TILE];
 
-    // ---- which job / batch item / query block (all wave-uniform) ----
-    const int bid = blockIdx.x;
-    int j = 0;
-    while (j + 1 < tab.njobs && bid >= tab.jobs[j + 1].block_begin) ++j;
-    const KnnJobDev& job = tab.jobs[j];
-    const int local = bid - job.block_begin;
-    const int b = local / job.blocks_per_b;
-    const int qb = local - b * job.blocks_per_b;
-    const int logT = job.logT;
+    const KnnBlock blk = decode_block(tab, blockIdx.x);
+    const KnnJobDev& job = blk.job;
+    const int b = blk.b, logT = job.logT;
     const int T = 1 << logT;
     const int S = job.S, Q = job.Q, K = job.K;
 
     const int tid = threadIdx.x;
     const int t = tid & (T - 1);
-    const int q = qb * (KNN_BLOCK >> logT) + (tid >> logT);
+    const int q = blk.query(KNN_BLOCK >> logT, tid >> logT);
     const bool valid = q < Q;
     const int qc = valid ? q : Q - 1;
 
-    const float* sup = job.support + (long long)b * job.support_bstride;
-    const float* qry = job.query + (long long)b * job.query_bstride + (long long)qc * 3;
+    const float* sup = blk.support();
+    const float* qry = blk.query_point(qc);
     const float qx = qry[0], qy = qry[1], qz = qry[2];
 
     float dl[KMAX];
@@ -260,6 +280,95 @@ __device__ __forceinline__ void wave_sort64(u64& key, int lane)
     sort_merge<64, 32>(key, lane);
 }
 
+#ifdef GDM_KNN_STATS
+__device__ unsigned long long gdm_knn_stats_dev[8];      // queries, rings, row batches, extra steps (cell lists); compactions, admitted (every K > 1 kernel); -, -
+#define KSTAT(i, v) do { if (lane == 0) atomicAdd(&gdm_knn_stats_dev[i], (unsigned long long)(v)); } while (0)
+#else
+#define KSTAT(i, v) do { } while (0)
+#endif
+
+// The K best (d2, index) keys of ONE WAVE'S query, for all three K > 1 kernels: a 64-slot candidate buffer in LDS (`buf`), the
+// admission bound (td, ti) = the current K-th key, and cnt = buffered candidates (wave-uniform).  The exactness of every K > 1
+// search rests on this code: ties by index, the strict / inclusive bound, the wavefront fences around the buffer.
+struct KnnSelection {
+    u64* const buf;                                      // constructed as {the wave's LDS row, lane, K}
+    const int lane, K;
+    float td = INFINITY;                                 // (inf, IDX_EMPTY) while fewer than K are known
+    int ti = IDX_EMPTY;
+    int cnt = 0;
+
+    // keep the K smallest of the buffer (sorted, in slots 0..K-1) and tighten the bound; returns this lane's key
+    __device__ __forceinline__ u64 compact()
+    {
+        KSTAT(4, 1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        u64 key = lane < cnt ? buf[lane] : KEY_EMPTY;
+        wave_sort64(key, lane);
+        if (lane < K) buf[lane] = key;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        cnt = min(cnt, K);
+        td = __int_as_float(__shfl((int)(unsigned)(key >> 32), K - 1, 64));
+        ti = __shfl((int)(unsigned)key, K - 1, 64);
+        return key;
+    }
+
+    // is (d, di) inside the bound?  INCL (compile time) adds the form in which, where `incl` holds, the bound itself passes
+    template <bool INCL>
+    __device__ __forceinline__ bool inside(float d, int di, bool incl) const
+    {
+        return lex_less(d, di, td, ti) || (INCL && incl && d == td && di == ti);
+    }
+
+    // append the lanes that `pass` (ballot + mbcnt slot); a full buffer is compacted first and the lanes re-tested
+    template <bool INCL>
+    __device__ __forceinline__ void append(float d, int di, bool pass, bool incl)
+    {
+        unsigned long long bal = __ballot(pass);
+        while (bal) {                                    // wave-uniform
+            const int n = __builtin_popcountll(bal);
+            if (cnt + n > 64 && cnt > K) {               // no room: select, tighten, re-test
+                compact();
+                pass = pass && inside<INCL>(d, di, incl);
+                bal = __ballot(pass);
+                continue;
+            }
+            const int room = 64 - cnt;                   // >= 32 after a compaction (K <= 32)
+            const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+            const bool now = pass && pos < room;
+            if (now) buf[cnt + pos] = make_key(d, di);
+            KSTAT(5, min(n, room));
+            cnt += min(n, room);
+            pass = pass && !now;
+            bal = __ballot(pass);
+        }
+    }
+
+    // admission of one step's 64 candidates (d2 in d, support index in di), strict bound: knn_wave_kernel, knn_cells_kernel
+    __device__ __forceinline__ void admit(float d, int di)
+    {
+        if (__ballot(d <= td) == 0ull) return;           // the common case: nobody is inside the bound
+        append<false>(d, di, inside<false>(d, di, false), false);
+    }
+
+    // knn_grid_kernel: only `live` lanes hold a candidate; `incl`: the bound itself passes (second phase, after the buffer was
+    // emptied).  No early return here.
+    __device__ __forceinline__ void admit_live(float d, int di, bool live, bool incl)
+    {
+        append<true>(d, di, live && inside<true>(d, di, incl), incl);
+    }
+
+    // the closing write of compact()'s key: lane k holds the k-th neighbour
+    __device__ __forceinline__ void store(const KnnJobDev& job, int b, int q, u64 key) const
+    {
+        if (lane >= K) return;
+        const long long o = ((long long)b * job.Q + q) * K + lane;
+        const int si = (int)(unsigned)key;
+        const float sd = __int_as_float((int)(unsigned)(key >> 32));
+        job.idx[o] = si == IDX_EMPTY ? 0 : si;
+        if (job.d2) job.d2[o] = isinf(sd) ? 3.402823466e+38f : sd;
+    }
+};
+
 struct PackEntry {
     const float* support;
     float4* packed;
@@ -318,42 +427,19 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_wave_kernel(const KnnTable tab)
     __shared__ float4 tile[KW_TILE];
     __shared__ u64 cand[KW_WAVES][64];
 
-    const int bid = blockIdx.x;
-    int j = 0;
-    while (j + 1 < tab.njobs && bid >= tab.jobs[j + 1].block_begin) ++j;
-    const KnnJobDev& job = tab.jobs[j];
-    const int local = bid - job.block_begin;
-    const int b = local / job.blocks_per_b;
-    const int qb = local - b * job.blocks_per_b;
-    const int S = job.S, Q = job.Q, K = job.K;
+    const KnnBlock blk = decode_block(tab, blockIdx.x);
+    const KnnJobDev& job = blk.job;
+    const int b = blk.b, S = job.S, Q = job.Q, K = job.K;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int q = qb * KW_WAVES + wave;
+    const int q = blk.query(KW_WAVES, wave);
     const bool valid = q < Q;                            // wave-uniform
-    const int qc = valid ? q : Q - 1;
-    const float* sup = job.support + (long long)b * job.support_bstride;
-    const float* qry = job.query + (long long)b * job.query_bstride + (long long)qc * 3;
+    const float* sup = blk.support();
+    const float* qry = blk.query_point(valid ? q : Q - 1);
     const float qx = qry[0], qy = qry[1], qz = qry[2];
-    u64* buf = cand[wave];
-
-    float td = INFINITY;                                 // current K-th (d2, index): admission bound
-    int ti = IDX_EMPTY;
-    int cnt = 0;                                         // buffered candidates (wave-uniform)
-
-    // keep the K smallest of the buffer (sorted, in slots 0..K-1) and tighten the bound
-    auto compact = [&]() -> u64 {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        u64 key = lane < cnt ? buf[lane] : KEY_EMPTY;
-        wave_sort64(key, lane);
-        if (lane < K) buf[lane] = key;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        cnt = min(cnt, K);
-        td = __int_as_float(__shfl((int)(unsigned)(key >> 32), K - 1, 64));   // (inf, IDX_EMPTY) while fewer than K are known
-        ti = __shfl((int)(unsigned)key, K - 1, 64);
-        return key;
-    };
+    KnnSelection sel{cand[wave], lane, K};
 
     int ntiles, npad;
     tile_geometry(S, ntiles, npad);
@@ -368,28 +454,6 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_wave_kernel(const KnnTable tab)
         }
         __syncthreads();
         if (!valid) continue;
-        // admission of one step's 64 candidates (d2 in d, support index in di)
-        auto admit = [&](float d, int di) {
-            if (__ballot(d <= td) == 0ull) return;       // the common case: nobody is inside the bound
-            bool pass = lex_less(d, di, td, ti);
-            unsigned long long bal = __ballot(pass);
-            while (bal) {                                // wave-uniform
-                const int n = __builtin_popcountll(bal);
-                if (cnt + n > 64 && cnt > K) {           // no room: select, tighten, re-test
-                    compact();
-                    pass = pass && lex_less(d, di, td, ti);
-                    bal = __ballot(pass);
-                    continue;
-                }
-                const int room = 64 - cnt;               // >= 32 after a compaction (K <= 32)
-                const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                const bool now = pass && pos < room;
-                if (now) buf[cnt + pos] = make_key(d, di);
-                cnt += min(n, room);
-                pass = pass && !now;
-                bal = __ballot(pass);
-            }
-        };
         const float4* tl = tile + lane;
         int s = 0;
         for (; s + 4 <= steps; s += 4) {                 // four steps' reads and distances in flight before the first test
@@ -400,22 +464,15 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_wave_kernel(const KnnTable tab)
 #pragma unroll
             for (int u = 0; u < 4; ++u) d4[u] = dist2_ref(qx, qy, qz, v4[u].x, v4[u].y, v4[u].z);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) admit(d4[u], __float_as_int(v4[u].w));
+            for (int u = 0; u < 4; ++u) sel.admit(d4[u], __float_as_int(v4[u].w));
         }
         for (; s < steps; ++s) {                         // steps = 1 or 2 (supports of <= 128 points per tile)
             const float4 v = tl[s << 6];
-            admit(dist2_ref(qx, qy, qz, v.x, v.y, v.z), __float_as_int(v.w));
+            sel.admit(dist2_ref(qx, qy, qz, v.x, v.y, v.z), __float_as_int(v.w));
         }
     }
     if (!valid) return;
-    const u64 key = compact();
-    if (lane < K) {
-        const long long o = ((long long)b * Q + q) * K + lane;
-        const int si = (int)(unsigned)key;
-        const float sd = __int_as_float((int)(unsigned)(key >> 32));
-        job.idx[o] = si == IDX_EMPTY ? 0 : si;
-        if (job.d2) job.d2[o] = isinf(sd) ? 3.402823466e+38f : sd;
-    }
+    sel.store(job, b, q, sel.compact());
 }
 
 // ---- K > 1, organised support ---------------------------------------------------------------------------------------------
@@ -423,7 +480,7 @@ constexpr int KG_MAXDIM = 256;          // grid width / height handled (4 column
 
 struct RangeEntry {
     const float* support;
-    float* ranges;
+    unsigned* ranges;                   // ordered keys (ord_key)
     long long support_bstride;
     int W, H;
     int nblocks;                        // B * ceil(H / 16)
@@ -467,7 +524,7 @@ __global__ __launch_bounds__(256) void knn_grid_ranges_kernel(const RangeTable t
     const int chunks = (H + KG_ROWS - 1) / KG_ROWS;
     const int b = blk / chunks, v0 = (blk - b * chunks) * KG_ROWS;
     const float* sup = e.support + (long long)b * e.support_bstride;
-    unsigned* out = reinterpret_cast<unsigned*>(e.ranges) + (long long)b * range_floats(W, H);
+    unsigned* out = e.ranges + (long long)b * range_floats(W, H);
     const int tid = threadIdx.x;
     unsigned flags = 0;
     // rows v0 .. v0 + 15: 16 lanes per row
@@ -556,65 +613,24 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_grid_kernel(const KnnTable tab)
 {
     __shared__ u64 cand[KW_WAVES][64];
 
-    const int bid = blockIdx.x;
-    int j = 0;
-    while (j + 1 < tab.njobs && bid >= tab.jobs[j + 1].block_begin) ++j;
-    const KnnJobDev& job = tab.jobs[j];
-    const int local = bid - job.block_begin;
-    const int b = local / job.blocks_per_b;
-    const int qb = local - b * job.blocks_per_b;
-    const int Q = job.Q, K = job.K, W = job.grid_w, H = job.grid_h;
+    const KnnBlock blk = decode_block(tab, blockIdx.x);
+    const KnnJobDev& job = blk.job;
+    const int b = blk.b, Q = job.Q, K = job.K, W = job.grid_w, H = job.grid_h;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int q = qb * KW_WAVES + wave;
+    const int q = blk.query(KW_WAVES, wave);
     if (q >= Q) return;                                   // wave-uniform; no block-level barrier in this kernel
-    const float* sup = job.support + (long long)b * job.support_bstride;
-    const float* qry = job.query + (long long)b * job.query_bstride + (long long)q * 3;
+    const float* sup = blk.support();
+    const float* qry = blk.query_point(q);
     const float qx = qry[0], qy = qry[1], qz = qry[2];
-    const unsigned* rk = reinterpret_cast<const unsigned*>(job.ranges) + (long long)b * range_floats(W, H);
-    u64* buf = cand[wave];
-
-    float td = INFINITY;
-    int ti = IDX_EMPTY;
-    int cnt = 0;
-    auto compact = [&]() -> u64 {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        u64 key = lane < cnt ? buf[lane] : KEY_EMPTY;
-        wave_sort64(key, lane);
-        if (lane < K) buf[lane] = key;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        cnt = min(cnt, K);
-        td = __int_as_float(__shfl((int)(unsigned)(key >> 32), K - 1, 64));
-        ti = __shfl((int)(unsigned)key, K - 1, 64);
-        return key;
-    };
-    // admission of one step's candidates; `incl`: the bound itself passes (second phase, after the buffer was emptied)
-    auto admit = [&](float d, int di, bool live, bool incl) {
-        bool pass = live && (lex_less(d, di, td, ti) || (incl && d == td && di == ti));
-        unsigned long long bal = __ballot(pass);
-        while (bal) {
-            const int n = __builtin_popcountll(bal);
-            if (cnt + n > 64 && cnt > K) {
-                compact();
-                pass = pass && (lex_less(d, di, td, ti) || (incl && d == td && di == ti));
-                bal = __ballot(pass);
-                continue;
-            }
-            const int room = 64 - cnt;
-            const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-            const bool now = pass && pos < room;
-            if (now) buf[cnt + pos] = make_key(d, di);
-            cnt += min(n, room);
-            pass = pass && !now;
-            bal = __ballot(pass);
-        }
-    };
+    const unsigned* rk = job.ranges + (long long)b * range_floats(W, H);
+    KnnSelection sel{cand[wave], lane, K};
     auto eval = [&](int r, int c, bool live, bool incl) {  // grid cell (r, c) as a candidate
         const int gi = live ? r * W + c : 0;
         const float* p = sup + (long long)gi * 3;
-        admit(dist2_ref(qx, qy, qz, p[0], p[1], p[2]), gi, live, incl);
+        sel.admit_live(dist2_ref(qx, qy, qz, p[0], p[1], p[2]), gi, live, incl);
     };
 
     unsigned any_bad = 0u, any_hole = 0u;                                      // the table's flag words, one pair per 16 rows
@@ -652,7 +668,7 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_grid_kernel(const KnnTable tab)
         // phase 1: the 8 x 8 cells around the centre -> a first K-th distance
         const int uc = min(max(arg_min(lbc) - 4, 0), W - 8), vc = min(max(arg_min(lbr) - 4, 0), H - 8);
         eval(vc + (lane >> 3), uc + (lane & 7), true, false);
-        compact();
+        sel.compact();
         // phase 2: only columns / rows whose bound (less a rounding allowance, scale-free) can still be below the K-th distance
         const float slack = 2e-6f * sqrtf(q2);
         int cl = W, ch = -1, rl = H, rh = -1;
@@ -660,8 +676,8 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_grid_kernel(const KnnTable tab)
         for (int i = 0; i < KG_MAXDIM / 64; ++i) {
             const int u = lane + 64 * i;
             const float sc = sqrtf(lbc[i]) - slack, sr = sqrtf(lbr[i]) - slack;
-            const bool kc = u < W && (sc <= 0.f || sc * sc * 0.999f <= td);
-            const bool kr = u < H && (sr <= 0.f || sr * sr * 0.999f <= td);
+            const bool kc = u < W && (sc <= 0.f || sc * sc * 0.999f <= sel.td);
+            const bool kr = u < H && (sr <= 0.f || sr * sr * 0.999f <= sel.td);
             if (kc) { cl = min(cl, u); ch = max(ch, u); }
             if (kr) { rl = min(rl, u); rh = max(rh, u); }
         }
@@ -669,9 +685,9 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_grid_kernel(const KnnTable tab)
             cl = min(cl, __shfl_xor(cl, m, 64)); ch = max(ch, __shfl_xor(ch, m, 64));
             rl = min(rl, __shfl_xor(rl, m, 64)); rh = max(rh, __shfl_xor(rh, m, 64));
         }
-        const bool holes_matter = has_hole && q2 * 0.999f <= td;   // points at the origin lie outside every plane bound
+        const bool holes_matter = has_hole && q2 * 0.999f <= sel.td;   // points at the origin lie outside every plane bound
         if (!holes_matter && ch >= cl && rh >= rl) { c0 = cl; c1 = ch; r0 = rl; r1 = rh; }
-        cnt = 0;                                          // the window holds the K best again: start over, bound inclusive
+        sel.cnt = 0;                                      // the window holds the K best again: start over, bound inclusive
     }
     const bool incl = structured && W >= 8 && H >= 8;
     const int wc = c1 - c0 + 1, total = wc * (r1 - r0 + 1);
@@ -684,14 +700,7 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_grid_kernel(const KnnTable tab)
         const int c = e - r * wc;
         eval(r0 + r, c0 + c, e < total, incl);
     }
-    const u64 key = compact();
-    if (lane < K) {
-        const long long o = ((long long)b * Q + q) * K + lane;
-        const int si = (int)(unsigned)key;
-        const float sd = __int_as_float((int)(unsigned)(key >> 32));
-        job.idx[o] = si == IDX_EMPTY ? 0 : si;
-        if (job.d2) job.d2[o] = isinf(sd) ? 3.402823466e+38f : sd;
-    }
+    sel.store(job, b, q, sel.compact());
 }
 
 // ---- K > 1, large unorganised support: uniform (x, y) cell lists ---------------------------------------------------------------
@@ -807,77 +816,28 @@ __global__ __launch_bounds__(KC_BIN_THREADS) void knn_cells_bin_kernel(const Cel
     }
 }
 
-#ifdef GDM_KNN_STATS
-__device__ unsigned long long gdm_knn_stats_dev[8];      // queries, rings, row batches, extra steps, compactions, admitted, -, -
-#define KSTAT(i, v) do { if (lane == 0) atomicAdd(&gdm_knn_stats_dev[i], (unsigned long long)(v)); } while (0)
-#else
-#define KSTAT(i, v) do { } while (0)
-#endif
-
 __global__ __launch_bounds__(KW_BLOCK) void knn_cells_kernel(const KnnTable tab)
 {
     __shared__ int cstart[KC_CELLS_MAX + 1];
     __shared__ u64 cand[KW_WAVES][64];
 
-    const int bid = blockIdx.x;
-    int j = 0;
-    while (j + 1 < tab.njobs && bid >= tab.jobs[j + 1].block_begin) ++j;
-    const KnnJobDev& job = tab.jobs[j];
-    const int local = bid - job.block_begin;
-    const int b = local / job.blocks_per_b;
-    const int qb = local - b * job.blocks_per_b;
-    const int S = job.S, Q = job.Q, K = job.K;
+    const KnnBlock blk = decode_block(tab, blockIdx.x);
+    const KnnJobDev& job = blk.job;
+    const int b = blk.b, S = job.S, Q = job.Q, K = job.K;
     const int G = kc_grid(S);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int* meta = reinterpret_cast<const int*>(job.ranges) + (long long)b * KC_META;
-    const float4* sorted = job.packed + (long long)b * S;
+    const int* meta = job.cells + (long long)b * KC_META;
+    const float4* sorted = job.sorted + (long long)b * S;
     for (int i = tid; i <= G * G; i += KW_BLOCK) cstart[i] = meta[i];
     __syncthreads();
-    const int q = qb * KW_WAVES + wave;
+    const int q = blk.query(KW_WAVES, wave);
     if (q >= Q) return;                                  // wave-uniform; no barrier below
     const float* fm = reinterpret_cast<const float*>(meta + KC_FOFF);
     const float bx0 = fm[0], by0 = fm[1], cw = fm[2], ch = fm[3], icw = fm[4], ich = fm[5];
-    const float* qry = job.query + (long long)b * job.query_bstride + (long long)q * 3;
+    const float* qry = blk.query_point(q);
     const float qx = qry[0], qy = qry[1], qz = qry[2];
-    u64* buf = cand[wave];
-
-    float td = INFINITY;
-    int ti = IDX_EMPTY;
-    int cnt = 0;
-    auto compact = [&]() -> u64 {
-        KSTAT(4, 1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        u64 key = lane < cnt ? buf[lane] : KEY_EMPTY;
-        wave_sort64(key, lane);
-        if (lane < K) buf[lane] = key;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        cnt = min(cnt, K);
-        td = __int_as_float(__shfl((int)(unsigned)(key >> 32), K - 1, 64));
-        ti = __shfl((int)(unsigned)key, K - 1, 64);
-        return key;
-    };
-    auto admit = [&](float d, int di) {
-        if (__ballot(d <= td) == 0ull) return;
-        bool pass = lex_less(d, di, td, ti);
-        unsigned long long bal = __ballot(pass);
-        while (bal) {
-            const int n = __builtin_popcountll(bal);
-            if (cnt + n > 64 && cnt > K) {
-                compact();
-                pass = pass && lex_less(d, di, td, ti);
-                bal = __ballot(pass);
-                continue;
-            }
-            const int room = 64 - cnt;
-            const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-            const bool now = pass && pos < room;
-            if (now) buf[cnt + pos] = make_key(d, di);
-            cnt += min(n, room);
-            pass = pass && !now;
-            bal = __ballot(pass);
-        }
-    };
+    KnnSelection sel{cand[wave], lane, K};
     // Rows of the window, FOUR at a time: a row's new cells are sorted[l0, l1) and sorted[r0, r1) (its two flanks, or its whole width);
     // the first 64 points of each of the four rows are loaded together (four independent L2 round trips in flight instead of one
     // after the other -- the search is latency-bound), then admitted row by row; a row with more than 64 new points continues alone.
@@ -910,13 +870,13 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_cells_kernel(const KnnTable tab)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const bool live = lane < tot[i];
-            admit(live ? dist2_ref(qx, qy, qz, v[i].x, v[i].y, v[i].z) : INFINITY, live ? __float_as_int(v[i].w) : IDX_EMPTY);
+            sel.admit(live ? dist2_ref(qx, qy, qz, v[i].x, v[i].y, v[i].z) : INFINITY, live ? __float_as_int(v[i].w) : IDX_EMPTY);
             for (int e0 = 64; e0 < tot[i]; e0 += 64) {
                 KSTAT(3, 1);
                 const int e = e0 + lane;
                 const bool lv = e < tot[i];
                 const float4 w = sorted[lv ? (e < nl[i] ? l0[i] + e : r0[i] + (e - nl[i])) : 0];
-                admit(lv ? dist2_ref(qx, qy, qz, w.x, w.y, w.z) : INFINITY, lv ? __float_as_int(w.w) : IDX_EMPTY);
+                sel.admit(lv ? dist2_ref(qx, qy, qz, w.x, w.y, w.z) : INFINITY, lv ? __float_as_int(w.w) : IDX_EMPTY);
             }
         }
     };
@@ -930,7 +890,7 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_cells_kernel(const KnnTable tab)
         KSTAT(1, 1);
         const int nx0 = max(qcx - r, 0), nx1 = min(qcx + r, G - 1), ny0 = max(qcy - r, 0), ny1 = min(qcy + r, G - 1);
         for (int y = ny0; y <= ny1; y += 4) { KSTAT(2, 1); rows4(y, ny1, nx0, nx1, ox0, ox1, oy0, oy1); }
-        key = compact();
+        key = sel.compact();
         ox0 = nx0; ox1 = nx1; oy0 = ny0; oy1 = ny1;
         if (nx0 == 0 && nx1 == G - 1 && ny0 == 0 && ny1 == G - 1) break;                 // the whole grid
         // distance from the query to the nearest edge of the window that still has cells beyond it
@@ -939,20 +899,14 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_cells_kernel(const KnnTable tab)
         const float eyl = ny0 == 0 ? INFINITY : qy - (by0 + (float)ny0 * ch);
         const float eyh = ny1 == G - 1 ? INFINITY : (by0 + (float)(ny1 + 1) * ch) - qy;
         const float m = fminf(fminf(exl, exh), fminf(eyl, eyh));
-        if (m > 0.f && m * m * 0.999f > td) break;                                       // (td = inf while fewer than K are known)
+        if (m > 0.f && m * m * 0.999f > sel.td) break;                                      // (td = inf while fewer than K are known)
         // next ring: far enough for the current K-th distance where it is known, else twice as far
         const float cmin = fminf(cw > 0.f ? cw : INFINITY, ch > 0.f ? ch : INFINITY);
         int want = r * 2;
-        if (td < INFINITY && cmin < INFINITY) want = (int)fminf((float)G, ceilf(sqrtf(td) / cmin)) + 1;
+        if (sel.td < INFINITY && cmin < INFINITY) want = (int)fminf((float)G, ceilf(sqrtf(sel.td) / cmin)) + 1;
         r = min(G, max(r + 1, want));
     }
-    if (lane < K) {
-        const long long o = ((long long)b * Q + q) * K + lane;
-        const int si = (int)(unsigned)key;
-        const float sd = __int_as_float((int)(unsigned)(key >> 32));
-        job.idx[o] = si == IDX_EMPTY ? 0 : si;
-        if (job.d2) job.d2[o] = isinf(sd) ? 3.402823466e+38f : sd;
-    }
+    sel.store(job, b, q, key);
 }
 
 int pick_logT(int S)
@@ -963,41 +917,54 @@ int pick_logT(int S)
     return logT;
 }
 
-void fill_job(KnnJobDev& d, const gdm_knn_job& j)
+// A search table and the blocks of its launch.  add(): job j as the table's next entry, `per_block` queries per block, no workspace layout yet.
+struct KnnLaunch {
+    KnnTable tab;
+    int nblocks = 0;
+    explicit KnnLaunch(int B)
+    {
+        tab.njobs = 0;
+        tab.B = B;
+    }
+    KnnJobDev& add(const gdm_knn_job& j, int logT, int per_block)
+    {
+        KnnJobDev& d = tab.jobs[tab.njobs++];
+        d.support = j.support;
+        d.query = j.query;
+        d.idx = j.idx;
+        d.d2 = j.d2;
+        d.support_bstride = j.support_bstride;
+        d.query_bstride = j.query_bstride;
+        d.S = j.S;
+        d.Q = j.Q;
+        d.K = j.K;
+        d.logT = logT;
+        d.blocks_per_b = gdm_cdiv(d.Q, per_block);
+        d.block_begin = nblocks;
+        nblocks += d.blocks_per_b * tab.B;
+        d.packed = nullptr;
+        d.ranges = nullptr;
+        d.grid_w = d.grid_h = 0;
+        return d;
+    }
+};
+
+// one kernel over one table; a table without entries has no blocks and is not launched
+template <class Table>
+int launch(void (*kernel)(const Table), const char* name, int nblocks, int threads, const Table& tab, hipStream_t stream)
 {
-    d.support = j.support;
-    d.query = j.query;
-    d.idx = j.idx;
-    d.d2 = j.d2;
-    d.support_bstride = j.support_bstride;
-    d.query_bstride = j.query_bstride;
-    d.S = j.S;
-    d.Q = j.Q;
-    d.K = j.K;
-    d.packed = nullptr;
-    d.ranges = nullptr;
-    d.grid_w = d.grid_h = 0;
+    if (nblocks == 0) return 0;
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(threads), 0, stream, tab);
+    return gdm_launch_status(name);
 }
 
 // K == 1 jobs: per-lane best + shuffle merge
 int launch_k1(const gdm_knn_job* jobs, int njobs, int B, hipStream_t stream)
 {
-    KnnTable tab;
-    tab.njobs = 0;
-    tab.B = B;
-    int nblocks = 0;
-    for (int i = 0; i < njobs; ++i) {
-        if (jobs[i].K != 1) continue;
-        KnnJobDev& d = tab.jobs[tab.njobs++];
-        fill_job(d, jobs[i]);
-        d.logT = pick_logT(d.S);
-        d.blocks_per_b = gdm_cdiv(d.Q, KNN_BLOCK >> d.logT);
-        d.block_begin = nblocks;
-        nblocks += d.blocks_per_b * B;
-    }
-    if (tab.njobs == 0) return 0;
-    hipLaunchKernelGGL(knn_kernel<1>, dim3(nblocks), dim3(KNN_BLOCK), 0, stream, tab);
-    return gdm_launch_status("knn_kernel<1>");
+    KnnLaunch k1(B);
+    for (int i = 0; i < njobs; ++i)
+        if (jobs[i].K == 1) k1.add(jobs[i], pick_logT(jobs[i].S), KNN_BLOCK >> pick_logT(jobs[i].S));
+    return launch(knn_kernel<1>, "knn_kernel<1>", k1.nblocks, KNN_BLOCK, k1.tab, stream);
 }
 
 size_t packed_bytes(int S, int B)
@@ -1024,160 +991,114 @@ bool same_support(const gdm_knn_job& a, const gdm_knn_job& b)
     return a.support == b.support && a.S == b.S && a.support_bstride == b.support_bstride;
 }
 
-// K in [2, 32] jobs: one query per wave.  Large jobs first, so that the tail of the launch is made of short blocks.
-// With a workspace every distinct unorganised support set is re-laid out once (knn_pack_kernel) and shared by the jobs that search
-// it, and the searches against organised supports (grid_w > 0) run as window searches (knn_grid_ranges_kernel + knn_grid_kernel).
-int launch_wave(const gdm_knn_job* jobs, int njobs, int B, void* workspace, size_t workspace_bytes, hipStream_t stream)
-{
-    KnnTable tab, gtab, ctab;                            // wave / organised / cell lists
-    tab.njobs = gtab.njobs = ctab.njobs = 0;
-    tab.B = gtab.B = ctab.B = B;
+// The plan of the K in [2, 32] jobs of one call: which kernel searches each job, and where every distinct support set lies in the
+// workspace, laid out once (grid ranges, cell list or hashed tiles) and shared by the jobs that search it.
+enum { LAY_RANGES, LAY_CELLS, LAY_TILES, LAY_COUNT };
+struct KnnPlan {
+    KnnLaunch wave, grid, cells;                         // the three search tables
+    RangeTable rt;                                       // the three preparation tables
     CellTable ct;
-    ct.n = 0;
-    ct.B = B;
-    const gdm_knn_job* ct_job[GDM_KNN_MAX_JOBS];
-    int cblocks = 0;
+    PackTable pk;
+    int range_blocks = 0, pack_blocks = 0;
+    const gdm_knn_job* owner[LAY_COUNT][GDM_KNN_MAX_JOBS];   // the job that reserved each entry of rt / ct / pk
+    size_t used = 0;                                     // bytes of the workspace reserved
+    explicit KnnPlan(int B) : wave(B), grid(B), cells(B)
+    {
+        rt.n = ct.n = pk.n = 0;
+        rt.B = ct.B = pk.B = B;
+    }
+};
+
+// The entry that holds jb's support in ONE layout (n entries, owned by owner[0..n)): the one an earlier job reserved, else a new one
+// of `need` bytes, rounded up to 16, if that still fits into `capacity`.  -> its index (n: new, at the offset `used` had; the caller
+// fills it), or -1: no room, the job goes down the ladder.
+int find_or_reserve(const gdm_knn_job** owner, int n, const gdm_knn_job& jb, size_t need, size_t capacity, size_t& used)
+{
+    int e = 0;
+    while (e < n && !same_support(*owner[e], jb)) ++e;
+    if (e < n) return e;
+    need = (need + 15) & ~(size_t)15;
+    if (need > capacity || used > capacity - need) return -1;
+    owner[n] = &jb;
+    used += need;
+    return n;
+}
+
+// Large jobs first (by S descending, equal S in table order), so that the tail of each launch is made of short blocks.  Every job takes the first layout of its ladder that
+// is or can be reserved: organised supports (grid_w > 0) the ratio ranges (knn_grid_ranges_kernel + knn_grid_kernel), large unorganised
+// ones the cell lists, then the hashed tiles (knn_pack_kernel); with none, its blocks fill their tiles from the [S][3] array.
+// base == nullptr with an unlimited capacity only sizes the workspace (p.used).
+void plan_jobs(KnnPlan& p, const gdm_knn_job* jobs, int njobs, int B, char* base, size_t capacity)
+{
     int order[GDM_KNN_MAX_JOBS], n = 0;
     for (int i = 0; i < njobs; ++i)
         if (jobs[i].K > 1) order[n++] = i;
-    if (n == 0) return 0;
-    for (int a = 1; a < n; ++a)                          // insertion sort by support size, descending (stable)
-        for (int c = a; c > 0 && jobs[order[c]].S > jobs[order[c - 1]].S; --c) {
-            const int tmp = order[c];
-            order[c] = order[c - 1];
-            order[c - 1] = tmp;
-        }
-    PackTable pk;
-    pk.n = 0;
-    pk.B = B;
-    RangeTable rt;
-    rt.n = 0;
-    rt.B = B;
-    const gdm_knn_job* rt_job[GDM_KNN_MAX_JOBS];
-    const gdm_knn_job* pk_job[GDM_KNN_MAX_JOBS];
-    int pack_blocks = 0, range_blocks = 0;
-    size_t used = 0;
-    int nblocks = 0, gblocks = 0;
+    std::sort(order, order + n, [&](int x, int y) { return jobs[x].S != jobs[y].S ? jobs[x].S > jobs[y].S : x < y; });
     for (int a = 0; a < n; ++a) {
         const gdm_knn_job& jb = jobs[order[a]];
-        if (workspace && is_grid_job(jb)) {               // organised support: window search
-            int e = 0;
-            while (e < rt.n && !same_support(*rt_job[e], jb)) ++e;
-            bool ok = e < rt.n;
-            if (!ok) {
-                const size_t need = (ranges_bytes(jb, B) + 15) & ~(size_t)15;
-                if (used + need <= workspace_bytes) {
-                    RangeEntry& re = rt.e[rt.n];
-                    re.support = jb.support;
-                    re.support_bstride = jb.support_bstride;
-                    re.W = jb.grid_w;
-                    re.H = jb.S / jb.grid_w;
-                    re.ranges = (float*)((char*)workspace + used);
-                    re.nblocks = B * gdm_cdiv(re.H, KG_ROWS);
-                    range_blocks += re.nblocks;
-                    rt_job[rt.n++] = &jb;
-                    used += need;
-                    ok = true;
-                }
+        char* const at = base ? base + p.used : nullptr; // where a new entry would lie
+        int e;
+        if (is_grid_job(jb) && (e = find_or_reserve(p.owner[LAY_RANGES], p.rt.n, jb, ranges_bytes(jb, B), capacity, p.used)) >= 0) {
+            if (e == p.rt.n) {
+                RangeEntry& re = p.rt.e[p.rt.n++];
+                re.support = jb.support;
+                re.support_bstride = jb.support_bstride;
+                re.W = jb.grid_w;
+                re.H = jb.S / jb.grid_w;
+                re.ranges = (unsigned*)at;
+                re.nblocks = B * range_chunks(re.H);
+                p.range_blocks += re.nblocks;
             }
-            if (ok) {
-                KnnJobDev& d = gtab.jobs[gtab.njobs++];
-                fill_job(d, jb);
-                d.logT = 0;
-                d.grid_w = jb.grid_w;
-                d.grid_h = jb.S / jb.grid_w;
-                d.ranges = rt.e[e].ranges;
-                d.blocks_per_b = gdm_cdiv(d.Q, KW_WAVES);
-                d.block_begin = gblocks;
-                gblocks += d.blocks_per_b * B;
-                continue;
-            }
+            KnnJobDev& d = p.grid.add(jb, 0, KW_WAVES);
+            d.grid_w = jb.grid_w;
+            d.grid_h = jb.S / jb.grid_w;
+            d.ranges = p.rt.e[e].ranges;
+            continue;
         }
-        if (workspace && is_cell_job(jb)) {               // large unorganised support: cell lists
-            int e = 0;
-            while (e < ct.n && !same_support(*ct_job[e], jb)) ++e;
-            bool ok = e < ct.n;
-            if (!ok) {
-                const size_t need = cells_bytes(jb.S, B);
-                if (used + need <= workspace_bytes) {
-                    CellEntry& ce = ct.e[ct.n];
-                    ce.support = jb.support;
-                    ce.support_bstride = jb.support_bstride;
-                    ce.S = jb.S;
-                    ce.sorted = (float4*)((char*)workspace + used);
-                    ce.meta = (int*)((char*)workspace + used + (size_t)B * jb.S * sizeof(float4));
-                    ct_job[ct.n++] = &jb;
-                    used += need;
-                    ok = true;
-                }
+        if (is_cell_job(jb) && (e = find_or_reserve(p.owner[LAY_CELLS], p.ct.n, jb, cells_bytes(jb.S, B), capacity, p.used)) >= 0) {
+            if (e == p.ct.n) {
+                CellEntry& ce = p.ct.e[p.ct.n++];
+                ce.support = jb.support;
+                ce.support_bstride = jb.support_bstride;
+                ce.S = jb.S;
+                ce.sorted = (float4*)at;
+                ce.meta = (int*)(at ? at + (size_t)B * jb.S * sizeof(float4) : nullptr);
             }
-            if (ok) {
-                KnnTable& tt = ctab;
-                int& nb = cblocks;
-                KnnJobDev& d = tt.jobs[tt.njobs++];
-                fill_job(d, jb);
-                d.logT = 0;
-                d.packed = ct.e[e].sorted;
-                d.ranges = reinterpret_cast<const float*>(ct.e[e].meta);
-                d.grid_w = kc_grid(jb.S);
-                d.blocks_per_b = gdm_cdiv(d.Q, KW_WAVES);
-                d.block_begin = nb;
-                nb += d.blocks_per_b * B;
-                continue;
-            }
+            KnnJobDev& d = p.cells.add(jb, 0, KW_WAVES);
+            d.sorted = p.ct.e[e].sorted;
+            d.cells = p.ct.e[e].meta;
+            continue;
         }
-        KnnJobDev& d = tab.jobs[tab.njobs++];
-        fill_job(d, jb);
-        d.logT = 0;
-        d.blocks_per_b = gdm_cdiv(d.Q, KW_WAVES);
-        d.block_begin = nblocks;
-        nblocks += d.blocks_per_b * B;
-        if (!workspace) continue;
-        int e = 0;                                        // a support set already packed for an earlier job?
-        while (e < pk.n && !same_support(*pk_job[e], jb)) ++e;
-        if (e == pk.n) {
-            const size_t need = packed_bytes(jb.S, B);
-            if (used + need > workspace_bytes) continue;  // does not fit: this job fills its tiles from the [S][3] array
-            PackEntry& pe = pk.e[pk.n];
+        KnnJobDev& d = p.wave.add(jb, 0, KW_WAVES);
+        if ((e = find_or_reserve(p.owner[LAY_TILES], p.pk.n, jb, packed_bytes(jb.S, B), capacity, p.used)) < 0) continue;
+        if (e == p.pk.n) {
+            PackEntry& pe = p.pk.e[p.pk.n++];
             pe.support = jb.support;
             pe.support_bstride = jb.support_bstride;
             pe.S = jb.S;
             tile_geometry(jb.S, pe.ntiles, pe.npad);
-            pe.packed = (float4*)((char*)workspace + used);
-            pe.block_begin = pack_blocks;
-            pack_blocks += (int)gdm_cdiv((long)B * pe.ntiles * pe.npad, 256);
-            pk_job[pk.n++] = &jb;
-            used += need;
+            pe.packed = (float4*)at;
+            pe.block_begin = p.pack_blocks;
+            p.pack_blocks += (int)gdm_cdiv((long)B * pe.ntiles * pe.npad, 256);
         }
-        d.packed = pk.e[e].packed;
+        d.packed = p.pk.e[e].packed;
     }
+}
+
+// K in [2, 32] jobs: one query per wave.  Plan, then up to six launches.  Without a workspace nothing can be reserved: every job
+// goes to knn_wave_kernel and gathers.
+int launch_wave(const gdm_knn_job* jobs, int njobs, int B, void* workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    KnnPlan p(B);
+    plan_jobs(p, jobs, njobs, B, (char*)workspace, workspace ? workspace_bytes : 0);
     int rc;
-    if (rt.n) {
-        // every word of the range tables is written by the kernel itself: no zero fill
-        hipLaunchKernelGGL(knn_grid_ranges_kernel, dim3(range_blocks), dim3(256), 0, stream, rt);
-        if ((rc = gdm_launch_status("knn_grid_ranges_kernel"))) return rc;
-    }
-    if (ct.n) {
-        hipLaunchKernelGGL(knn_cells_bin_kernel, dim3(ct.n * B), dim3(KC_BIN_THREADS), 0, stream, ct);
-        if ((rc = gdm_launch_status("knn_cells_bin_kernel"))) return rc;
-    }
-    if (pk.n) {
-        hipLaunchKernelGGL(knn_pack_kernel, dim3(pack_blocks), dim3(256), 0, stream, pk);
-        if ((rc = gdm_launch_status("knn_pack_kernel"))) return rc;
-    }
-    if (ctab.njobs) {
-        hipLaunchKernelGGL(knn_cells_kernel, dim3(cblocks), dim3(KW_BLOCK), 0, stream, ctab);
-        if ((rc = gdm_launch_status("knn_cells_kernel"))) return rc;
-    }
-    if (tab.njobs) {
-        hipLaunchKernelGGL(knn_wave_kernel, dim3(nblocks), dim3(KW_BLOCK), 0, stream, tab);
-        if ((rc = gdm_launch_status("knn_wave_kernel"))) return rc;
-    }
-    if (gtab.njobs) {
-        hipLaunchKernelGGL(knn_grid_kernel, dim3(gblocks), dim3(KW_BLOCK), 0, stream, gtab);
-        if ((rc = gdm_launch_status("knn_grid_kernel"))) return rc;
-    }
-    return 0;
+    // every word of the range tables is written by the kernel itself: no zero fill
+    if ((rc = launch(knn_grid_ranges_kernel, "knn_grid_ranges_kernel", p.range_blocks, 256, p.rt, stream))) return rc;
+    if ((rc = launch(knn_cells_bin_kernel, "knn_cells_bin_kernel", p.ct.n * B, KC_BIN_THREADS, p.ct, stream))) return rc;
+    if ((rc = launch(knn_pack_kernel, "knn_pack_kernel", p.pack_blocks, 256, p.pk, stream))) return rc;
+    if ((rc = launch(knn_cells_kernel, "knn_cells_kernel", p.cells.nblocks, KW_BLOCK, p.cells.tab, stream))) return rc;
+    if ((rc = launch(knn_wave_kernel, "knn_wave_kernel", p.wave.nblocks, KW_BLOCK, p.wave.tab, stream))) return rc;
+    return launch(knn_grid_kernel, "knn_grid_kernel", p.grid.nblocks, KW_BLOCK, p.grid.tab, stream);
 }
 
 } // namespace
@@ -1213,18 +1134,9 @@ extern "C" int gdm_knn_stats_read(unsigned long long* out8, int reset)
 extern "C" size_t gdm_knn_jobs_workspace_bytes(const gdm_knn_job* jobs, int njobs, int B)
 {
     if (!jobs || njobs < 0 || njobs > GDM_KNN_MAX_JOBS || B < 1) return 0;
-    size_t total = 0;
-    for (int i = 0; i < njobs; ++i) {
-        if (jobs[i].K <= 1) continue;
-        bool seen = false;
-        for (int e = 0; e < i && !seen; ++e)
-            seen = jobs[e].K > 1 && same_support(jobs[e], jobs[i]) && is_grid_job(jobs[e]) == is_grid_job(jobs[i]);
-        if (seen) continue;
-        // (a cell job is sized for both layouts: it falls back to the hashed tiles when the cell lists no longer fit)
-        total += is_grid_job(jobs[i]) ? ((ranges_bytes(jobs[i], B) + 15) & ~(size_t)15)
-                                      : (is_cell_job(jobs[i]) ? cells_bytes(jobs[i].S, B) : packed_bytes(jobs[i].S, B));
-    }
-    return total;
+    KnnPlan p(B);                                        // the launch's own plan with room for everything: what it reserves is the size
+    plan_jobs(p, jobs, njobs, B, nullptr, ~(size_t)0);
+    return p.used;
 }
 
 static int run_jobs(const gdm_knn_job* jobs, int njobs, int B, void* workspace, size_t workspace_bytes, hipStream_t stream, const char* who)
@@ -1246,17 +1158,7 @@ extern "C" int gdm_knn_jobs_ws_hip(const gdm_knn_job* jobs, int njobs, int B, vo
 extern "C" int gdm_knn_batch_hip(const float* support, const float* query, int B, int S, int Q, int K,
                                  int32_t* idx, float* d2, void* stream)
 {
-    gdm_knn_job j;
-    j.support = support;
-    j.query = query;
-    j.idx = idx;
-    j.d2 = d2;
-    j.support_bstride = (int64_t)S * 3;
-    j.query_bstride = (int64_t)Q * 3;
-    j.S = S;
-    j.Q = Q;
-    j.K = K;
-    j.grid_w = 0;
+    const gdm_knn_job j = {support, query, idx, d2, (int64_t)S * 3, (int64_t)Q * 3, S, Q, K, 0};   // dense strides, no grid
     return run_jobs(&j, 1, B, nullptr, 0, (hipStream_t)stream, "gdm_knn_batch_hip");
 }
 

@@ -211,8 +211,9 @@ def copy_views(views):
 
 
 def _knn_launch(arr, n, B, device):
-    """gdm_knn_jobs_ws_hip with a workspace from torch's caching allocator (graph-capture safe): the K > 1 jobs' support sets are
-    re-laid out once per launch as hashed float4 tiles."""
+    """gdm_knn_jobs_ws_hip with a workspace from torch's caching allocator (graph-capture safe): every distinct support set of the
+    K > 1 jobs is re-laid out once per launch -- ratio ranges for an organised map, a cell list from 1024 points, hashed float4 tiles
+    otherwise (include/gdm.h, gdm_knn_jobs_workspace_bytes)."""
     L = _lib.lib()
     nbytes = int(L.gdm_knn_jobs_workspace_bytes(arr, n, B))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)

@@ -69,7 +69,14 @@ typedef struct gdm_knn_job {
  * set of the K > 1 jobs is re-laid out once: small unorganised supports as hashed float4 tiles that the search blocks stream with
  * coalesced loads, unorganised supports of >= 1024 points as (x, y) cell lists (a counting sort per crop; a query then visits cells
  * ring by ring instead of every point), organised supports (grid_w) as per-column / per-row ratio ranges.  workspace NULL with
- * workspace_bytes 0: each block gathers its tiles from the [S,3] array.  Results are identical in every form, for any data.      */
+ * workspace_bytes 0: each block gathers its tiles from the [S,3] array.  Results are identical in every form, for any data.
+ * Bytes per distinct (support, S, support_bstride, layout), each rounded up to 16, reserved in the order of the jobs by descending S:
+ *   ranges (W = grid_w and H = S / grid_w both in [8, 256]):  B * (2 W + 2 H + 2 ceil(H / 16)) * 4
+ *   cell list (no ranges, S >= 1024):                         B * S * 16 + B * 1036 * 4
+ *   hashed tiles (every other K > 1 job):                     B * ntiles * npad * 16, ntiles = ceil(S / 1024), npad = the power of two
+ *                                                             >= max(64, ceil(S / ntiles))
+ * gdm_knn_jobs_workspace_bytes is their sum.  With fewer bytes a job whose entry no longer fits takes the next layout of
+ * ranges -> cell list (S >= 1024) -> hashed tiles -> gather from the [S,3] array; the results do not change.                     */
 size_t gdm_knn_jobs_workspace_bytes(const gdm_knn_job* jobs, int njobs, int B);
 int gdm_knn_jobs_ws_hip(const gdm_knn_job* jobs, int njobs, int B, void* workspace, size_t workspace_bytes, void* stream);
 

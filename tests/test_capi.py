@@ -224,3 +224,54 @@ def test_call_needs_no_gpu_for_host_side_refusals(lib, monkeypatch):
         _lib.call("gdm_match_score_hip", conf, mask, 0, 0)
     with pytest.raises(TypeError):
         _lib.call("gdm_match_rows_bytes", 3, 4)
+
+
+_KNN_WS_TABLES = {                                     # entries: (support id, S, K, grid_w); Q = 33, dense strides
+    "cloud": [(1, 2048, 16, 0), (2, 512, 16, 0), (3, 128, 16, 0), (4, 32, 16, 0)],
+    "k1": [(1, 2048, 1, 0), (2, 512, 1, 0)],
+    "one": [(1, 77, 16, 0)],
+    "mixed": [(1, 16384, 16, 128), (1, 16384, 16, 0), (1, 16384, 1, 0), (1, 16384, 16, 128), (2, 960, 5, 40), (2, 960, 5, 0),
+              (3, 64, 16, 4), (3, 64, 16, 0), (4, 1023, 2, 0), (5, 1024, 2, 0), (6, 8192, 32, 0)],
+}
+_KNN_WS_BYTES = {"cloud": (48176, 144528, 770816), "k1": (0, 0, 0), "one": (2048, 6144, 32768), "mixed": (458464, 1375392, 7335424)}
+
+
+def _knn_ws_table(entries):
+    """A job table over fake, distinct, 16-byte-aligned addresses per support id (nothing is dereferenced by the size function)."""
+    from geometric_aware_dense_matching_amd import _lib
+    Q = 33
+    arr = (_lib.KnnJob * max(len(entries), 1))()
+    for a, (sid, S, K, grid_w) in zip(arr, entries):
+        a.support = 0x10000000 * sid
+        a.query = 0x7000000000 + 0x10000 * sid
+        a.idx = 0x7100000000
+        a.d2 = None
+        a.support_bstride, a.query_bstride = S * 3, Q * 3
+        a.S, a.Q, a.K, a.grid_w = S, Q, K, grid_w
+    return arr
+
+
+@pytest.mark.parametrize("name", sorted(_KNN_WS_TABLES))
+def test_knn_workspace_bytes(lib, name):
+    """gdm_knn_jobs_workspace_bytes is what the launch's own plan reserves.  Per distinct (support, layout), each rounded up to 16 bytes:
+    organised (grid_w >= 8, S / grid_w >= 8, both <= 256): B * (2 W + 2 H + 2 ceil(H / 16)) * 4; unorganised with S >= 1024: B * (16 S +
+    4144) (sorted float4 points + KC_META = 1036 words per crop); else hashed tiles B * ntiles * npad * 16 with ntiles = ceil(S / 1024),
+    npad = the power of two >= max(64, ceil(S / ntiles)); K = 1 jobs take nothing.  E.g. "cloud", B = 1: 36912 + 8192 + 2048 + 1024;
+    "mixed", B = 1: 2112 + 266288 + 528 + 16384 + 1024 (support 3 once: grid_w = 4 is no grid) + 16384 + 20528 + 135216."""
+    entries = _KNN_WS_TABLES[name]
+    arr = _knn_ws_table(entries)
+    for B, want in zip((1, 3, 16), _KNN_WS_BYTES[name]):
+        assert lib.gdm_knn_jobs_workspace_bytes(arr, len(entries), B) == want, (name, B)
+
+
+def test_knn_workspace_bytes_ignores_the_order_of_the_table_and_refuses_bad_tables(lib):
+    import random
+    rng = random.Random(7)
+    entries = list(_KNN_WS_TABLES["mixed"])
+    for _ in range(200):
+        rng.shuffle(entries)
+        assert lib.gdm_knn_jobs_workspace_bytes(_knn_ws_table(entries), len(entries), 3) == _KNN_WS_BYTES["mixed"][1], entries
+    arr = _knn_ws_table(_KNN_WS_TABLES["cloud"])
+    assert lib.gdm_knn_jobs_workspace_bytes(arr, 33, 1) == 0
+    assert lib.gdm_knn_jobs_workspace_bytes(arr, 4, 0) == 0
+    assert lib.gdm_knn_jobs_workspace_bytes(None, 4, 1) == 0

@@ -240,6 +240,44 @@ def test_knn_organised_hint_on_unstructured_data_is_still_exact(ops):
         assert np.array_equal(np.stack([oknn.d2_of(sup[b], qry[b], got[b]) for b in range(B)]), want_d2)
 
 
+def test_knn_undersized_workspace_takes_the_next_layout_with_the_same_result(ops, monkeypatch):
+    """Every rung of the ladder an undersized workspace sends a job down (ranges -> cell list -> hashed tiles -> gather from [S,3]):
+    one table with a cell-list support searched by two jobs, an organised 16 x 8 support with holes, a one-tile support and a K = 1
+    job -- the smallest shapes that reach every layout -- run with 0 bytes, the full size, 16 bytes less (the tiles of the last
+    support no longer fit), room for the first reservation only and for the first two, and room for just the hashed tiles of the
+    cell-list support.  The sizes come from the formulas of include/gdm.h.  Indices equal ops.knn_batch on dense copies, bit for bit."""
+    rs = np.random.RandomState(41)
+    B, H, W = 2, 16, 8
+    cell_sup = torch.from_numpy(_cloud(rs, B, 1024)).cuda()
+    grid_sup = torch.from_numpy(_depth_grid(rs, B, H, W, holes=0.08, step_edge=False)).cuda()
+    assert int((grid_sup[..., 2] == 0).sum()) >= 2                       # a few holes at the origin
+    tile_sup = torch.from_numpy(_cloud(rs, B, 77)).cuda()
+    q33a, q20, q33b, q33c, q33d = (torch.from_numpy(_cloud(rs, B, n)).cuda() for n in (33, 20, 33, 33, 33))
+    q33b = (q33b - 0.5) * 0.2 + torch.tensor([0.0, 0.0, 0.8], device="cuda")          # around the depth surface
+    jobs = [(cell_sup, q33a, 5), (cell_sup, q20, 3), (grid_sup, q33b, 5, W), (tile_sup, q33c, 16), (tile_sup, q33d, 1)]
+    want = [ops.knn_batch(j[0].contiguous(), j[1].contiguous(), j[2]) for j in jobs]
+    cells = B * 1024 * 16 + B * 1036 * 4                                  # reserved first (largest S)
+    ranges = (B * (2 * W + 2 * H + 2 * ((H + 15) // 16)) * 4 + 15) // 16 * 16
+    tiles = B * 1 * 128 * 16                                              # S = 77: one tile of 128 slots
+    full = cells + ranges + tiles
+    from geometric_aware_dense_matching_amd import _lib
+    for nbytes in (0, full, full - 16, cells, cells + ranges, B * 1 * 1024 * 16):
+        seen = []
+
+        def launch(arr, n, B, device, nbytes=nbytes):
+            seen.append(int(_lib.lib().gdm_knn_jobs_workspace_bytes(arr, n, B)))
+            ws = torch.empty(full, dtype=torch.uint8, device=device)
+            ops.call("gdm_knn_jobs_ws_hip", arr, n, B, ws, nbytes)
+            return ws
+
+        monkeypatch.setattr(ops, "_knn_launch", launch)
+        got = ops.knn_jobs(jobs, B)
+        torch.cuda.synchronize()
+        assert seen == [full]                                             # the formulas above are the library's
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert torch.equal(g, w), (nbytes, i)
+
+
 def _feat_idx(rs, B, C, n, m, K):
     feat = torch.from_numpy(rs.randn(B, C, n).astype(np.float32))
     idx = torch.from_numpy(rs.randint(0, n, size=(B, m, K)).astype(np.int64))
