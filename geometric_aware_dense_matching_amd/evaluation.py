@@ -466,10 +466,11 @@ def vsd_from_poses(verts, faces, RT_est, RT_gt, depth_test, K, delta, taus, diam
     return (errors, counts) if return_counts else errors
 
 
-def load_ply(path):
+def load_ply(path, attributes=False):
     """The triangle meshes BOP ships, in pure numpy: ascii or binary_little_endian PLY with a `vertex` element whose properties include
     x, y, z (further ones -- normals, colours, texture coordinates -- are skipped) and a `face` element that is one list property of
-    uchar / int (or uint) triples -> verts f64[V,3] (the file's unit: mm in BOP), faces i32[F,3]."""
+    uchar / int (or uint) triples -> verts f64[V,3] (the file's unit: mm in BOP), faces i32[F,3].  attributes=True: also normals
+    f32[V,3] from nx, ny, nz and colors u8[V,3] from red, green, blue, each None when the file lacks one of its three properties."""
     np_type = {"char": "i1", "uchar": "u1", "short": "i2", "ushort": "u2", "int": "i4", "uint": "u4", "float": "f4", "double": "f8",
                "int8": "i1", "uint8": "u1", "int16": "i2", "uint16": "u2", "int32": "i4", "uint32": "u4", "float32": "f4", "float64": "f8"}
     with open(path, "rb") as f:
@@ -493,7 +494,7 @@ def load_ply(path):
                 break
         if fmt not in ("ascii", "binary_little_endian"):
             raise ValueError("%s: PLY format %r is not supported (ascii, binary_little_endian)" % (path, fmt))
-        verts = faces = None
+        verts = faces = normals = colors = None
         for name, count, props in elements:
             is_list = [p[0] == "list" for p in props]
             if any(is_list) and (name != "face" or len(props) != 1):
@@ -523,9 +524,13 @@ def load_ply(path):
                     cols = {nm: rec[nm] for nm in names}
                 if name == "vertex":
                     verts = np.stack([cols["x"], cols["y"], cols["z"]], axis=1).astype(np.float64)
+                    if attributes and all(k in cols for k in ("nx", "ny", "nz")):
+                        normals = np.stack([cols["nx"], cols["ny"], cols["nz"]], axis=1).astype(np.float32)
+                    if attributes and all(k in cols for k in ("red", "green", "blue")):
+                        colors = np.stack([cols["red"], cols["green"], cols["blue"]], axis=1).astype(np.uint8)
     if verts is None or faces is None:
         raise ValueError("%s: PLY without a vertex and a face element" % path)
-    return verts, faces
+    return (verts, faces, normals, colors) if attributes else (verts, faces)
 
 
 class BopScores:

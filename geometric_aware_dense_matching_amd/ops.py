@@ -15,6 +15,8 @@ Operator <-> reference map (file:line under /root/reference):
   att_pool               models/RandLA/RandLANet.py:749-752
   match / seg_mask       evaluator.py:79-93
   ballquery / furthestsampling   lib/pointops/functions/pointops.py:205-219, 40-50
+  surface_sample / furthestsampling_wide / point_diameter   the producer of obj_%06d_fps.npy, which the reference names
+                         (ref/ycbv.py:106) and does not ship: model_prep.py, DESIGN.md 6n
 """
 import ctypes
 import os
@@ -240,6 +242,60 @@ def furthestsampling(xyz, m):
     temp = torch.empty((B, n), dtype=torch.float32, device=xyz.device)
     call("gdm_furthestsampling_hip", B, n, m, xyz, temp, idx)
     return idx
+
+
+def furthestsampling_wide(xyz, m, groups=0):
+    """furthestsampling for many candidates: the same idx i32[B,m], bit for bit, from m small launches that spread the candidates
+    over the whole device (include/gdm.h gdm_fps_wide_hip).  groups: workgroups per cloud, 1..1024, or 0 = the launcher's choice."""
+    xyz = _dev(xyz, torch.float32, "xyz")
+    B, n, _ = xyz.shape
+    g = int(groups) or int(call("gdm_fps_wide_groups", n))
+    idx = torch.empty((B, m), dtype=torch.int32, device=xyz.device)
+    dist = torch.empty((B, n), dtype=torch.float32, device=xyz.device)
+    partial = torch.empty((B, 2, max(g, 1)), dtype=torch.int64, device=xyz.device)
+    call("gdm_fps_wide_hip", B, n, m, int(groups), xyz, dist, partial, idx)
+    return idx
+
+
+def surface_sample(verts, faces, vnrm, vrgb, cdf, S, seed=0):
+    """S points on a triangle mesh by the sample rule of include/gdm.h (gdm_surface_sample_hip): verts, vnrm f32[V,3], vrgb u8 or
+    f32[V,3] (integer levels), faces i32[F,3], cdf i64[F] = inclusive cumulative integer face weights -> f32[S,9] = xyz, rgb, normal.
+    What the device cannot see is refused here: a face index outside [0, V) and a cdf that ends in 0 or decreases."""
+    verts = _dev(verts, torch.float32, "verts")
+    vnrm = _dev(vnrm, torch.float32, "vnrm")
+    if isinstance(vrgb, torch.Tensor) and vrgb.dtype == torch.uint8:
+        vrgb = vrgb.float()
+    vrgb = _dev(vrgb, torch.float32, "vrgb")
+    faces = _dev(faces, torch.int32, "faces")
+    cdf = _dev(cdf, torch.int64, "cdf")
+    V, F, S = verts.shape[0], faces.shape[0], int(S)
+    if verts.shape != (V, 3) or vnrm.shape != (V, 3) or vrgb.shape != (V, 3) or faces.shape != (F, 3) or cdf.shape != (F,):
+        raise ValueError("surface_sample: verts / vnrm / vrgb must be [V,3], faces [F,3] and cdf [F]")
+    if V >= 1 and F >= 1:
+        lo, hi, last, step = (int(v) for v in torch.stack([faces.min().long(), faces.max().long(), cdf[-1],
+                                                           (cdf - torch.cat([cdf.new_zeros(1), cdf[:-1]])).min()]).tolist())
+        if lo < 0 or hi >= V:
+            raise ValueError("surface_sample: face indices %d..%d outside the %d vertices" % (lo, hi, V))
+        if last <= 0 or step < 0:
+            raise ValueError("surface_sample: cdf must be a cumulative sum of non-negative weights that ends above 0 (cdf[F-1]=%d)" % last)
+    if not 1 <= S < 1 << 31:
+        raise ValueError("surface_sample: S=%d not in [1, 2^31)" % S)
+    out = torch.empty((S, 9), dtype=torch.float32, device=verts.device)
+    call("gdm_surface_sample_hip", verts, faces, vnrm, vrgb, cdf, V, F, S, int(seed) & 0xffffffff, out)
+    return out
+
+
+def point_diameter(xyz):
+    """The exact farthest pair of xyz f32[V,3] (include/gdm.h gdm_point_diameter_hip): (pair i32[2] with i < j, d2 f32[1]), the
+    lowest i and then the lowest j among equal fp32 squared distances."""
+    xyz = _dev(xyz, torch.float32, "xyz")
+    V = xyz.shape[0]
+    nbytes = int(call("gdm_point_diameter_workspace_bytes", V))
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=xyz.device)
+    pair = torch.empty(2, dtype=torch.int32, device=xyz.device)
+    d2 = torch.empty(1, dtype=torch.float32, device=xyz.device)
+    call("gdm_point_diameter_hip", xyz, V, ws, nbytes, pair, d2)
+    return pair, d2
 
 
 # --------------------------------------------------------------------------------------

@@ -131,6 +131,9 @@ def build_parser():
                    help="train: weight of the expected-vertex regression (smooth L1, metres) added to the loss; 0 = off")
     p.add_argument("--soft-nll-weight", dest="soft_nll_weight", type=float, default=0.0,
                    help="train: weight of the negative log-likelihood of the ground-truth vertex under the soft assignment; 0 = off")
+    p.add_argument("--models-dir", dest="models_dir", type=str, default=None, metavar="DIR",
+                   help="a BOP models directory: when the dataset has no obj_%%06d_fps.npy for an object and DIR/obj_%%06d.ply exists, "
+                        "the model table is built from that mesh on the GPU (model_prep.build_model_points) instead of a synthetic one")
     return p
 
 
@@ -381,6 +384,10 @@ def _model_points(args, ds, cls_id):
     path = os.path.join(ds["model_pth"], "obj_%06d_fps.npy" % cls_id)
     if os.path.exists(path):
         return np.load(path)
+    ply = os.path.join(getattr(args, "models_dir", None) or "", "obj_%06d.ply" % cls_id)
+    if getattr(args, "models_dir", None) and os.path.exists(ply):          # --models-dir: the table built from the BOP mesh, in memory
+        from . import model_prep
+        return model_prep.build_model_points(ply, args.n_mesh)
     return synthetic.make_model_points(cls_id, args.n_mesh, ds["diameters"][cls_id])       # KeyError: not an object of this dataset
 
 

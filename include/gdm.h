@@ -1057,6 +1057,52 @@ int gdm_vsd_counts_hip(const float* depth_est, const float* depth_gt, const floa
                        int k_per_instance, int n, int H, int W, double delta, const double* taus /* host array */, int T,
                        double diameter, int inf_is_empty, int32_t* counts, double* tl_sums, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Object model preparation: from a triangle mesh to the table obj_%06d_fps.npy holds ([M,9] = xyz in mm, rgb 0..255, unit normal,
+ * rows in farthest-point order; read by datasets/lm/linemod_pbr.py:89-97, evaluator.py:34-40, models/SplineCNN.py:116).  The script
+ * that wrote the reference's files is not part of it, so each entry is defined by the rule written here, which model_prep.py
+ * restates in numpy (surface_sample_numpy, fps_numpy, point_diameter_numpy) bit for bit; DESIGN.md 6n.  All fp32 arithmetic below
+ * is single operations rounded to nearest, never fused, the division and the square root included.
+ *
+ * gdm_surface_sample_hip: S points on the mesh, faces drawn in proportion to integer weights, attributes interpolated.
+ * verts, vnrm, vrgb f32[V,3] (vrgb holds integer levels 0..255); faces i32[F,3], every index in [0, V) (the CALLER checks that);
+ * cdf i64[F] = the inclusive cumulative sum of non-negative integer face weights with cdf[F-1] > 0 (the caller checks that too: it
+ * cannot be seen from the host here); out f32[S,9] = xyz, rgb, normal.  THE SAMPLE RULE for sample s, all words uint32:
+ *   words     base = mix32(mix32(seed ^ 0x9e3779b9) ^ s), h_j = mix32(base ^ ((j + 1) * 0x9e3779b9 mod 2^32)) for j = 0..3, mix32 the
+ *             lowbias32 of gdm_sample_assemble_hip
+ *   face      target = floor(((h_0 << 32 | h_1) * cdf[F-1]) / 2^64) (__umul64hi); f = the first face with cdf[f] > target -- a face
+ *             of weight 0 is never drawn
+ *   weights   ui = h_2 >> 8, vi = h_3 >> 8; when ui + vi > 2^24 (u + v > 1, decided on the integers): ui = 2^24 - ui, vi = 2^24 - vi;
+ *             u = ui * 2^-24, v = vi * 2^-24, w0 = (1 - u) - v -- all three exact and >= 0
+ *   channels  x = ((w0 * A) + (u * B)) + (v * C) for each of the nine, A, B, C the values at the face's three vertices in its order
+ *   colour    min(max(floor(x + 0.5), 0), 255)
+ *   normal    l = sqrt(((nx * nx) + (ny * ny)) + (nz * nz)); each component divided by l when l > 0, a zero normal stays zero
+ * One thread per sample, no atomics: the result does not depend on the launch shape.  1 <= S < 2^31, V >= 1, F >= 1. */
+int gdm_surface_sample_hip(const float* verts, const int32_t* faces, const float* vnrm, const float* vrgb, const int64_t* cdf,
+                           int V, int F, long S, uint32_t seed, float* out, void* stream);
+/* gdm_fps_wide_hip: furthest point sampling for many candidates, spread over the whole device.  idx i32[B,m] equals what
+ * gdm_furthestsampling_hip returns for the same xyz f32[B,n,3], bit for bit.  THE RULE both follow: pick 0 is index 0; dist starts
+ * at 1e10; after pick p every candidate takes dist = fminf(dist, d2), d2 = ((dx * dx) + (dy * dy)) + (dz * dz) to p; the next pick
+ * is the candidate of largest dist, the lowest index among equals.
+ * The entry enqueues m launches of one small kernel and returns without synchronising.  In launch i (1..m) every workgroup reduces
+ * the `groups` partial results launch i-1 left -- a partial is (float bits of dist) << 32 | (0xffffffff - index), so the unsigned
+ * 64-bit maximum is the largest dist and then the lowest index; a workgroup with an empty slice leaves 0 --, takes the winner as
+ * pick i-1 (workgroup 0 stores idx[i-1]; launch 1 reads nothing and takes index 0), updates dist over its own slice of
+ * ceil(n / groups) candidates and writes its partial into half (i & 1) of partial.  Launch m only stores the last pick.  No workgroup
+ * waits for another inside a kernel (no cooperative launch, no grid barrier, no flag): the order comes from the stream alone.
+ * dist f32[B,n] is scratch (initialised inside, left unwritten when m == 1); partial: [B, 2, groups] 64-bit words, 8-byte aligned,
+ * scratch.  groups: 1..1024, or 0 = gdm_fps_wide_groups(n) (one workgroup per 1024 candidates, at most 1024), which then sizes
+ * partial.  B <= 65535, 1 <= m <= n. */
+int gdm_fps_wide_groups(int n);
+int gdm_fps_wide_hip(int B, int n, int m, int groups, const float* xyz, float* dist, void* partial, int32_t* idx, void* stream);
+/* gdm_point_diameter_hip: the exact farthest pair of xyz f32[V,3]: pair i32[2] = the (i < j) of the largest
+ * d2 = ((dx * dx) + (dy * dy)) + (dz * dz), the lowest i and then the lowest j among equals; d2 f32[1] is that value.  Row tiles of
+ * 256 points in registers against column tiles in LDS over the upper triangle; every workgroup writes one packed partial into
+ * workspace (gdm_point_diameter_workspace_bytes(V) bytes, 8-byte aligned; 0 for an unsupported V) and a second launch reduces
+ * them.  No atomics: every run gives the same answer.  2 <= V <= 2^24. */
+size_t gdm_point_diameter_workspace_bytes(int V);
+int gdm_point_diameter_hip(const float* xyz, int V, int64_t* workspace, size_t workspace_bytes, int32_t* pair, float* d2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
