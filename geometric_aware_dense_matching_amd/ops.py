@@ -18,7 +18,9 @@ Operator <-> reference map (file:line under /root/reference):
   surface_sample / furthestsampling_wide / point_diameter   the producer of obj_%06d_fps.npy, which the reference names
                          (ref/ycbv.py:106) and does not ship: model_prep.py, DESIGN.md 6n
 """
+import collections
 import ctypes
+import functools
 import os
 
 import torch
@@ -1225,7 +1227,7 @@ def upconv3x3_gather_train(z, bias, cout, out_size):
 def wx(w2d, x3):
     """W f32[Cout,Cin] . x f32[B,Cin,n] -> f32[B,Cout,n] as ONE batched GEMM on the shared weight.  torch.matmul(2-D, 3-D) folds the
     batch into GEMM rows instead and pays a transposing copy of the product (and of its gradient) to get back to [B,Cout,n]:
-    2 ms of an 83 ms training step on the 9*Cout-channel tap tensors of PSPUpsample."""
+    2 ms of an 83 ms training step on the 9*Cout-channel tap tensors of PSPUpsample.  Under autograd: _WxTrain (train_plan)."""
     if torch.is_grad_enabled() and (w2d.requires_grad or x3.requires_grad) and x3.is_cuda and x3.dtype == torch.float32:
         return _WxTrain.apply(x3.contiguous(), w2d.contiguous())
     return torch.bmm(w2d.unsqueeze(0).expand(x3.shape[0], -1, -1), x3)
@@ -1266,50 +1268,44 @@ def _wgrad_parts(nchunk, tiles):
     return parts
 
 
-def gemm_wgrad_supported(x3, go3):
-    B, Cin, P = x3.shape
+def _wgrad_packed(who, x, go, taps, parts=None):
+    """The weight-gradient launch of the split-bf16 MFMA GEMM with the pixels as the contraction axis, for a 1x1 product (taps 1:
+    x f32[B,Cin,P], go f32[B,Cout,P]) or a 3x3 / stride 1 / pad 1 convolution (taps 9: x f32[B,Cin,H,W], go f32[B,Cout,H,W])
+    -> f32[Cout,taps,Cin].  Sizes, fit check, two packs, one launch over `parts` equal parts of the contraction (_wgrad_parts unless
+    given), whose partial products are added in a fixed order (deterministic).  Every ValueError comes from the shapes alone."""
+    B, Cin, Cout = x.shape[0], x.shape[1], go.shape[1]
+    H, W = (x.shape[2] // 32, 32) if taps == 1 else (x.shape[2], x.shape[3])      # a 1x1 product packs grad_out as rows of 32 pixels
+    P = x.shape[2] if taps == 1 else H * W
     L = _lib.lib()
-    return (settings.USE_MFMA_GEMM_TRAIN and x3.is_cuda and x3.dtype == torch.float32 and P % 128 == 0 and Cin % 256 == 0
-            and go3.shape[1] >= 64 and 2.0 * B * P * Cin * go3.shape[1] >= 2e9
-            and operands_fit(L.gdm_wgrad_x1_bytes(B, Cin, P), L.gdm_wgrad_go_bytes(B, go3.shape[1], P // 32, 32)))
+    nx = L.gdm_wgrad_x1_bytes(B, Cin, P) if taps == 1 else L.gdm_wgrad_x_bytes(B, Cin, H, W)
+    ng = L.gdm_wgrad_go_bytes(B, Cout, H, W)
+    if nx == 0 or ng == 0 or (taps * Cin) % 256 != 0:
+        raise ValueError("%s: unsupported shape x %s grad_out %s" % (who, tuple(x.shape), tuple(go.shape)))
+    _require_fit(who, "x %s grad_out %s", (tuple(x.shape), tuple(go.shape)), nx, ng)
+    nchunk = B * P // 128
+    if parts is None:
+        parts = _wgrad_parts(nchunk, (taps * Cin // 256) * ((Cout + 127) // 128))
+    if nchunk % parts != 0:
+        raise ValueError("%s: %d parts do not divide the %d chunks of the contraction" % (who, parts, nchunk))
+    x, go = _dev(x, torch.float32, "x"), _dev(go, torch.float32, "grad_out")
+    xpk, gpk = torch.empty(nx, dtype=torch.uint8, device=x.device), torch.empty(ng, dtype=torch.uint8, device=x.device)
+    if taps == 1:
+        call("gdm_wgrad_pack_x1_hip", x, B, Cin, P, xpk)
+    else:
+        call("gdm_wgrad_pack_x_hip", x, B, Cin, H, W, xpk)
+    call("gdm_wgrad_pack_go_hip", go, B, Cout, H, W, gpk)
+    n = nchunk // parts
+    coutp = (Cout + 127) // 128 * 128
+    out = torch.empty((parts, Cout, taps, Cin), dtype=torch.float32, device=x.device)
+    call("gdm_conv1x1_packed_wb_hip", xpk, gpk, n * coutp * 512, parts, 128 * n, Cout, taps, Cin, out)
+    return out[0] if parts == 1 else out.sum(0)
 
 
 def gemm_wgrad(x3, go3):
     """dW f32[Cout,Cin] = sum_b go3[b] . x3[b]^T (x3 f32[B,Cin,P], go3 f32[B,Cout,P]) on the split-bf16 MFMA GEMM with the pixels as the
     contraction axis (include/gdm.h gdm_wgrad_pack_x1_hip): the weight gradient of a 1x1 convolution / of `wx`."""
     B, Cin, P = x3.shape
-    Cout = go3.shape[1]
-    L = _lib.lib()
-    nx, ng = L.gdm_wgrad_x1_bytes(B, Cin, P), L.gdm_wgrad_go_bytes(B, Cout, P // 32, 32)
-    if nx == 0 or ng == 0 or Cin % 256 != 0:
-        raise ValueError("gemm_wgrad: unsupported shape x %s grad_out %s" % (tuple(x3.shape), tuple(go3.shape)))
-    _require_fit("gemm_wgrad", "x %s grad_out %s", (tuple(x3.shape), tuple(go3.shape)), nx, ng)
-    x3 = _dev(x3, torch.float32, "x")
-    go3 = _dev(go3, torch.float32, "grad_out")
-    xpk = torch.empty(nx, dtype=torch.uint8, device=x3.device)
-    gpk = torch.empty(ng, dtype=torch.uint8, device=x3.device)
-    call("gdm_wgrad_pack_x1_hip", x3, B, Cin, P, xpk)
-    call("gdm_wgrad_pack_go_hip", go3, B, Cout, P // 32, 32, gpk)
-    nchunk = B * P // 128
-    parts = _wgrad_parts(nchunk, (Cin // 256) * ((Cout + 127) // 128))
-    n = nchunk // parts
-    coutp = (Cout + 127) // 128 * 128
-    out = torch.empty((parts, Cout, Cin), dtype=torch.float32, device=x3.device)
-    call("gdm_conv1x1_packed_wb_hip", xpk, gpk, n * coutp * 512, parts, 128 * n, Cout, 1, Cin, out)
-    return out[0] if parts == 1 else out.sum(0)
-
-
-def wgrad_direct_supported(x3, go3, bias=False):
-    """Small-channel, many-pixel products: the HBM-bound form that reads the fp32 rows once (include/gdm.h gdm_wgrad_direct_hip).
-    Kernel times at batch 24 (tools/bench_wgrad_direct.py under rocprofv3, own vs the fp32 batched GEMM; + 6-12 us for the sum of the
-    partials on both sides): 32x32 @ 65536 px 90 vs 320 us, 16x32 48 vs 166, 64x32 135 vs 167, 64x64 @ 16384 px 52 vs 57,
-    32x64 @ 4096 12 vs 23, 128x64 @ 16384 112 vs 103, 128x128 @ 4096 48 vs 41 -- so up to 64 x 64 channels, and up to 128 x 128 when the
-    bias gradient rides along (its separate reduction costs 34-490 us)."""
-    B, Cin, P = x3.shape
-    Cout = go3.shape[1]
-    lim = 128 if bias else 64
-    return (settings.USE_DIRECT_WGRAD and x3.is_cuda and x3.dtype == torch.float32 and go3.dtype == torch.float32 and P % 32 == 0
-            and Cin <= lim and Cout <= lim and B * P >= 16384 and _rows_ok(x3) and _rows_ok(go3))
+    return _wgrad_packed("gemm_wgrad", x3, go3, 1).view(go3.shape[1], Cin)
 
 
 def _rows_ok(t):
@@ -1333,55 +1329,118 @@ def wgrad_direct(x3, go3, bias=False):
     return part.sum(0), (bpart.sum(0) if bias else None)
 
 
-def _gemm_fwd_mfma_ok(cin, cout, n, B):
-    return settings.USE_MFMA_GEMM_TRAIN and gemm_supported(cin, cout, n, B) and 2.0 * B * n * cin * cout >= 2e9
+TrainPlan = collections.namedtuple("TrainPlan", "function fwd dgrad wgrad asks_mfma fits")
+
+
+def train_plan(entry, B, cin, cout, n, cuda=True, bias_grad=False):
+    """Which engine makes each product of one training step of a 1x1 layer x f32[B,cin,n] -> cout channels, from what is known before a
+    tensor is touched.  entry: "wx", "conv1x1_train" or "conv1x1_train_w"; cuda: the operands are fp32 tensors on the GPU (anything else
+    goes to torch); bias_grad: the layer has a bias whose gradient is wanted.  -> TrainPlan (cached: layer shapes repeat every step):
+      function   the autograd Function the entry point applies, "_WxTrain" or "_Conv1x1Train"
+      fwd dgrad  the engine of W . x and of W^T . go: "gemm_bf16x3" (>= 2 GFLOP) before "pointwise" before "torch.bmm"
+      wgrad      the engines of sum_b go . x^T in order of preference: "gemm_wgrad" (>= 2 GFLOP), "wgrad_direct", "torch.bmm".  Row layout
+                 is the one run-time condition (wgrad_direct wants _rows_ok of x and go; go exists only in the backward): _train_wgrad
+      asks_mfma  False: no product is offered to the split-bf16 MFMA GEMM;  fits: False when a product that GEMM takes by shape and
+                 size has an operand of 2 GiB or more (conv1x1_train_supported)"""
+    return _train_plan(entry, int(B), int(cin), int(cout), int(n), bool(cuda), bool(bias_grad),
+                       settings.USE_MFMA_GEMM_TRAIN, settings.USE_POINTWISE_TRAIN, settings.USE_DIRECT_WGRAD)
+
+
+@functools.lru_cache(maxsize=4096)
+def _train_plan(entry, B, cin, cout, n, cuda, bias_grad, use_mfma, use_pointwise, use_direct):
+    L = _lib.lib()
+    big = use_mfma and cuda and 2.0 * B * n * cin * cout >= 2e9
+    # per product (the MFMA GEMM takes it by shape and size, its operands fit): W . x on x, W^T . go on go, go . x^T
+    mfma = [(big and gemm_shape_supported(ci, co, n), operands_fit(_map_bytes(B, ci, 1, n), L.gdm_conv1x1_weight_bytes(co, ci)))
+            for ci, co in ((cin, cout), (cout, cin))]
+    mfma.append((big and n % 128 == 0 and cin % 256 == 0 and cout >= 64,
+                 operands_fit(L.gdm_wgrad_x1_bytes(B, cin, n), L.gdm_wgrad_go_bytes(B, cout, n // 32, 32))))
+    fwd_mfma, dgrad_mfma, wgrad_mfma = (takes and fits for takes, fits in mfma)
+    function = "_WxTrain" if entry == "wx" or (entry == "conv1x1_train" and (fwd_mfma or dgrad_mfma)) else "_Conv1x1Train"
+    # INHERITED, NOT DESIGNED: _Conv1x1Train (always applied by conv1x1_train_w) never asked the MFMA GEMM for anything.  conv1x1_train
+    # chooses it exactly when neither W . x nor W^T . go is a product that GEMM takes, so there the flag decides the weight gradient alone:
+    # Cin % 256 == 0, Cout in [64, 192) other than 64 and 128, n % 128 == 0, >= 2 GFLOP goes to gemm_wgrad through wx, to torch.bmm through
+    # conv1x1_train.  True everywhere needs a GPU measurement of gemm_wgrad against torch.bmm / wgrad_direct in that class first.
+    asks_mfma = function == "_WxTrain"
+    other = "pointwise" if use_pointwise and cuda else "torch.bmm"
+    # wgrad_direct: up to 64 x 64 channels, 128 x 128 when the bias gradient rides along in the call (measurements: DESIGN.md 6o)
+    lim = 128 if bias_grad and not asks_mfma else 64
+    direct = use_direct and cuda and n % 32 == 0 and cin <= lim and cout <= lim and B * n >= 16384
+    return TrainPlan(function, "gemm_bf16x3" if asks_mfma and fwd_mfma else other, "gemm_bf16x3" if asks_mfma and dgrad_mfma else other,
+                     (("gemm_wgrad",) if asks_mfma and wgrad_mfma else ()) + (("wgrad_direct",) if direct else ()) + ("torch.bmm",),
+                     asks_mfma, not any(takes and not fits for takes, fits in mfma))
+
+
+def gemm_wgrad_supported(x3, go3):
+    """gemm_wgrad is what a Function that asks the MFMA GEMM (the wx route) takes for this weight gradient."""
+    B, Cin, P = x3.shape
+    return "gemm_wgrad" in train_plan("wx", B, Cin, go3.shape[1], P, cuda=x3.is_cuda and x3.dtype == torch.float32).wgrad
+
+
+def wgrad_direct_supported(x3, go3, bias=False):
+    """Small-channel, many-pixel products in rows wgrad_direct can read (the shape rule and its measurements: train_plan)."""
+    B, Cin, P = x3.shape
+    plan = train_plan("conv1x1_train_w", B, Cin, go3.shape[1], P, cuda=x3.is_cuda and x3.dtype == go3.dtype == torch.float32, bias_grad=bias)
+    return "wgrad_direct" in plan.wgrad and _rows_ok(x3) and _rows_ok(go3)
+
+
+def _train_fwd(plan, x3, w2, bias=None, out=None):
+    """W . x3 (+ bias) on plan.fwd, into `out` f32[B,Cout,n] where given."""
+    if plan.fwd == "gemm_bf16x3":
+        assert bias is None and out is None                    # (only _WxTrain asks this engine: its bias is added outside)
+        return gemm_bf16x3(x3, gemm_pack_weight(w2), w2.shape[0])
+    if plan.fwd == "pointwise":                                # the module's [Cout, Cin] weight read in place, the bias in the epilogue
+        return pointwise([x3], w2, None, bias, ACT_NONE, 0.0, out=out, w_rowmajor=True)
+    y = torch.bmm(w2.unsqueeze(0).expand(x3.shape[0], -1, -1), x3, out=out)
+    if bias is not None:
+        y += bias.view(1, -1, 1)
+    return y
+
+
+def _train_dgrad(plan, go3, w2):
+    """W^T . go3 on plan.dgrad -> f32[B,Cin,n]."""
+    if plan.dgrad == "gemm_bf16x3":
+        return gemm_bf16x3(go3, conv_pack_weight_dgrad(w2), w2.shape[1])
+    if plan.dgrad == "pointwise":
+        return pointwise([go3.contiguous()], w2)                # the same weight read as [K = Cout][Cin]
+    return torch.bmm(w2.t().unsqueeze(0).expand(go3.shape[0], -1, -1), go3)
+
+
+def _train_wgrad(plan, x3, go3, bias_grad=False):
+    """(sum_b go3[b] . x3[b]^T, db or None) on the first engine of plan.wgrad whose run-time condition holds; db only from wgrad_direct."""
+    for engine in plan.wgrad:
+        if engine == "gemm_wgrad":
+            return gemm_wgrad(x3, go3), None
+        if engine == "wgrad_direct" and _rows_ok(x3) and _rows_ok(go3):
+            return wgrad_direct(x3, go3, bias=bias_grad)
+    return torch.bmm(go3, x3.transpose(1, 2)).sum(0), None        # [B, Cout, Cin] partials: <= 25 MB for every layer but one
 
 
 class _WxTrain(torch.autograd.Function):
-    """y[b] = W . x[b] under autograd with the three products on the split-bf16 MFMA GEMM where they are large (>= 2 GFLOP: the tap
-    GEMMs of PSPUpsample, the PSP bottleneck, the 512 / 1024-channel fusion convolutions), on hipBLASLt fp32 batched GEMMs otherwise:
-    forward W . x, input gradient W^T . go, weight gradient sum_b go[b] . x[b]^T (pixels as the contraction axis)."""
+    """y[b] = W . x[b] under autograd, every product offered to the split-bf16 MFMA GEMM first (train_plan; >= 2 GFLOP: the tap GEMMs of
+    PSPUpsample, the PSP bottleneck, the 512 / 1024-channel fusion convolutions).  No bias: a caller adds it outside, and its gradient
+    is autograd's own sum."""
 
     @staticmethod
     def forward(ctx, x3, w2):
         ctx.save_for_backward(x3, w2)
-        B, Cin, n = x3.shape
-        Cout = w2.shape[0]
-        if x3.is_cuda and _gemm_fwd_mfma_ok(Cin, Cout, n, B):
-            return gemm_bf16x3(x3, gemm_pack_weight(w2), Cout)
-        if settings.USE_POINTWISE_TRAIN and x3.is_cuda:
-            return pointwise([x3], w2, w_rowmajor=True)
-        return torch.bmm(w2.unsqueeze(0).expand(B, -1, -1), x3)
+        ctx.plan = train_plan("wx", x3.shape[0], x3.shape[1], w2.shape[0], x3.shape[2], cuda=x3.is_cuda and x3.dtype == torch.float32)
+        return _train_fwd(ctx.plan, x3, w2)
 
     @staticmethod
     def backward(ctx, go):
         x3, w2 = ctx.saved_tensors
-        B, Cin, n = x3.shape
-        Cout = w2.shape[0]
         go = go.contiguous()
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            if x3.is_cuda and _gemm_fwd_mfma_ok(Cout, Cin, n, B):
-                gx = gemm_bf16x3(go, conv_pack_weight_dgrad(w2), Cin)
-            elif settings.USE_POINTWISE_TRAIN and x3.is_cuda:
-                gx = pointwise([go], w2)
-            else:
-                gx = torch.bmm(w2.t().unsqueeze(0).expand(B, -1, -1), go)
-        if ctx.needs_input_grad[1]:
-            if gemm_wgrad_supported(x3, go):
-                gw = gemm_wgrad(x3, go)
-            elif wgrad_direct_supported(x3, go):
-                gw = wgrad_direct(x3, go)[0]
-            else:
-                gw = torch.bmm(go, x3.transpose(1, 2)).sum(0)
+        gx = _train_dgrad(ctx.plan, go, w2) if ctx.needs_input_grad[0] else None
+        gw = _train_wgrad(ctx.plan, x3, go)[0] if ctx.needs_input_grad[1] else None
         return gx, gw
 
 
 class _Conv1x1Train(torch.autograd.Function):
-    """y[b] = W . x[b] (+ bias) for a 1x1 convolution, with all three products as batched GEMMs on the NCHW tensors as they lie:
-    forward W . x, input gradient W^T . go, weight gradient sum_b go[b] . x[b]^T.  torch's convolution backward sends a 1x1
-    convolution to MIOpen's implicit-GEMM wgrad / bwd-data kernels, which want NHWC and pay a transposing copy of every operand
-    (181 `batched_transpose` launches, 2.7 ms of a 56 ms training step) around fp32 kernels slower than the GEMM library's."""
+    """y[b] = W . x[b] (+ bias) for a 1x1 convolution, with all three products as batched GEMMs on the NCHW tensors as they lie and none
+    of them on the split-bf16 MFMA GEMM (train_plan, asks_mfma).  torch's convolution backward sends a 1x1 convolution to MIOpen's
+    implicit-GEMM wgrad / bwd-data kernels, which want NHWC and pay a transposing copy of every operand (181 `batched_transpose`
+    launches, 2.7 ms of a 56 ms training step) around fp32 kernels slower than the GEMM library's."""
 
     @staticmethod
     def forward(ctx, x, w2, bias):
@@ -1389,77 +1448,47 @@ class _Conv1x1Train(torch.autograd.Function):
         x3 = x.reshape(B, Cin, -1)
         ctx.save_for_backward(x3, w2)
         ctx.xshape = x.shape
-        ctx.has_bias = bias is not None
+        ctx.bias_grad = bias is not None and ctx.needs_input_grad[2]
+        ctx.plan = train_plan("conv1x1_train_w", B, Cin, w2.shape[0], x3.shape[2], x.is_cuda and x.dtype == torch.float32, ctx.bias_grad)
         y = torch.empty((B, w2.shape[0]) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)   # returned as it is (not a view: the
-        y3 = y.view(B, w2.shape[0], -1)                                                            # modules' in-place activations follow)
-        if settings.USE_POINTWISE_TRAIN and x3.is_cuda and x3.is_contiguous():
-            # own exact-fp32 MFMA kernel, the module's [Cout, Cin] weight read in place, the bias in its epilogue
-            pointwise([x3], w2, None, bias, ACT_NONE, 0.0, out=y3, w_rowmajor=True)
-            return y
-        torch.bmm(w2.unsqueeze(0).expand(B, -1, -1), x3, out=y3)
-        if bias is not None:
-            y3 += bias.view(1, -1, 1)
+        _train_fwd(ctx.plan, x3, w2, bias, out=y.view(B, w2.shape[0], -1))                          # modules' in-place activations follow)
         return y
 
     @staticmethod
     def backward(ctx, go):
         x3, w2 = ctx.saved_tensors
-        B = x3.shape[0]
-        go3 = go.reshape(B, w2.shape[0], -1)
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            if settings.USE_POINTWISE_TRAIN and go3.is_cuda:
-                gx = pointwise([go3.contiguous()], w2).view(ctx.xshape)     # W^T . go: the same weight read as [K = Cout][Cin]
-            else:
-                gx = torch.bmm(w2.t().unsqueeze(0).expand(B, -1, -1), go3).view(ctx.xshape)
-        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] and wgrad_direct_supported(x3, go3, bias=want_gb):
-            gw, gb = wgrad_direct(x3, go3, bias=want_gb)             # weight and bias gradient from one read of go
-            return gx, gw, gb
-        if ctx.needs_input_grad[1]:
-            gw = torch.bmm(go3, x3.transpose(1, 2)).sum(0)            # [B, Cout, Cin] partials: <= 25 MB for every layer but one
-        if want_gb:
+        go3 = go.reshape(x3.shape[0], w2.shape[0], -1)
+        gx = _train_dgrad(ctx.plan, go3, w2).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        gw, gb = _train_wgrad(ctx.plan, x3, go3, ctx.bias_grad) if ctx.needs_input_grad[1] else (None, None)
+        if ctx.bias_grad and gb is None:
             gb = go3.sum((0, 2))
         return gx, gw, gb
 
 
-def _gemm_train_fits(cin, cout, n, B):
-    """False when one of the three products of a 1x1 layer's training step -- W . x, W^T . grad_out, grad_out . x^T -- is one the split-bf16
-    GEMM takes by its shape, with an operand of 2 GiB or more."""
-    L = _lib.lib()
-    big = settings.USE_MFMA_GEMM_TRAIN and 2.0 * B * n * cin * cout >= 2e9
-    for ci, co in ((cin, cout), (cout, cin)):        # forward on x; input gradient on grad_out
-        if big and gemm_shape_supported(ci, co, n) and not operands_fit(_map_bytes(B, ci, 1, n), L.gdm_conv1x1_weight_bytes(co, ci)):
-            return False
-    if big and n % 128 == 0 and cin % 256 == 0 and cout >= 64:
-        return operands_fit(L.gdm_wgrad_x1_bytes(B, cin, n), L.gdm_wgrad_go_bytes(B, cout, n // 32, 32))
-    return True
-
-
 def conv1x1_train_supported(conv, x):
-    """Past the operand limit of the split-bf16 GEMM (operands_fit; the backward's operands count too) the module runs its torch path."""
+    """Past the operand limit of the split-bf16 GEMM (train_plan's fits; the backward's operands count too) the module runs its torch path."""
     return (settings.USE_GEMM_CONV1X1_TRAIN and x.is_cuda and x.dtype == torch.float32 and all(k == 1 for k in conv.kernel_size)
             and all(st == 1 for st in conv.stride) and all(p == 0 for p in conv.padding) and conv.groups == 1 and x.dim() in (3, 4)
-            and _gemm_train_fits(x.shape[1], conv.weight.shape[0], x.numel() // max(1, x.shape[0] * x.shape[1]), x.shape[0]))
+            and train_plan("conv1x1_train", x.shape[0], x.shape[1], conv.weight.shape[0], x.numel() // max(1, x.shape[0] * x.shape[1])).fits)
 
 
 def conv1x1_train(conv, x):
-    """Differentiable 1x1 convolution of an nn.Conv1d / nn.Conv2d module as batched GEMMs (see _Conv1x1Train); large layers take the
-    split-bf16 MFMA GEMM for all three products (_WxTrain)."""
+    """Differentiable 1x1 convolution of an nn.Conv1d / nn.Conv2d module.  Where the split-bf16 MFMA GEMM takes the forward or the input
+    gradient (train_plan) the layer goes through _WxTrain with the bias added here; every other layer through _Conv1x1Train."""
     w = conv.weight
-    B, Cin = x.shape[0], x.shape[1]
+    B, Cin, Cout = x.shape[0], x.shape[1], w.shape[0]
     n = x.numel() // (B * Cin)
-    Cout = w.shape[0]
-    if x.is_cuda and (_gemm_fwd_mfma_ok(Cin, Cout, n, B) or _gemm_fwd_mfma_ok(Cout, Cin, n, B)):
+    if train_plan("conv1x1_train", B, Cin, Cout, n, cuda=x.is_cuda and x.dtype == torch.float32).function == "_WxTrain":
         y = _WxTrain.apply(x.reshape(B, Cin, n).contiguous(), w.reshape(Cout, Cin).contiguous())
         if conv.bias is not None:
             y = y + conv.bias.view(1, -1, 1)
         return y.view(B, Cout, *x.shape[2:])
-    return _Conv1x1Train.apply(x.contiguous(), w.reshape(w.shape[0], w.shape[1]), conv.bias)
+    return _Conv1x1Train.apply(x.contiguous(), w.reshape(Cout, Cin), conv.bias)
 
 
 def conv1x1_train_w(x, w2, bias=None):
-    """`conv1x1_train` for a weight TENSOR f32[Cout,Cin] (a slice of a module's weight, say) instead of a module: x f32[B,Cin,n]."""
+    """`conv1x1_train` for a weight TENSOR f32[Cout,Cin] (a slice of a module's weight, say) instead of a module: x f32[B,Cin,n].
+    Always _Conv1x1Train."""
     return _Conv1x1Train.apply(x.contiguous(), w2, bias)
 
 
@@ -1866,8 +1895,6 @@ def _capturing_unscoped():
     return False
 
 
-
-
 def conv3x3_wgrad_supported(x, go):
     """The split-bf16 MFMA weight-gradient path: 32- or 64-wide maps, Cin a multiple of 256 (the per-part weights of the GEMM want
     whole 256-row tiles per part) -- the 32 x 32 half of the trunk, where torch's path (MIOpen fp32 implicit GEMM) is 2.5x slower."""
@@ -1880,37 +1907,9 @@ def conv3x3_wgrad_supported(x, go):
 def conv3x3_wgrad(x, go, parts=None):
     """dW f32[Cout,Cin,3,3] of a 3x3 / stride 1 / pad 1 convolution from its input x f32[B,Cin,H,W] and output gradient go
     f32[B,Cout,H,W], on the split-bf16 MFMA GEMM (include/gdm.h gdm_wgrad_*): the contraction runs over the B*H*W pixels, split
-    into `parts` equal parts (one launch), whose [Cout,9,Cin] partial products are added here in a fixed order (deterministic)."""
+    into `parts` equal parts (one launch, _wgrad_packed), whose [Cout,9,Cin] partial products are added in a fixed order."""
     B, Cin, H, W = x.shape
-    Cout = go.shape[1]
-    L = _lib.lib()
-    nx, ng = L.gdm_wgrad_x_bytes(B, Cin, H, W), L.gdm_wgrad_go_bytes(B, Cout, H, W)
-    if nx == 0 or ng == 0 or (9 * Cin) % 256 != 0:
-        raise ValueError("conv3x3_wgrad: unsupported shape x %s grad_out %s" % (tuple(x.shape), tuple(go.shape)))
-    _require_fit("conv3x3_wgrad", "x %s grad_out %s", (tuple(x.shape), tuple(go.shape)), nx, ng)
-    x = _dev(x, torch.float32, "x")
-    go = _dev(go, torch.float32, "grad_out")
-    xpk = torch.empty(nx, dtype=torch.uint8, device=x.device)
-    gpk = torch.empty(ng, dtype=torch.uint8, device=x.device)
-    call("gdm_wgrad_pack_x_hip", x, B, Cin, H, W, xpk)
-    call("gdm_wgrad_pack_go_hip", go, B, Cout, H, W, gpk)
-    nchunk = B * H * W // 128
-    if parts is None:
-        # parts: the largest divisor of the chunk count that keeps the launch at about one round of workgroups (a part has
-        # 9 Cin / 256 x ceil(Cout / 128) of them) and at least four chunks per part
-        tiles = (9 * Cin // 256) * ((Cout + 127) // 128)
-        parts = 1
-        for d in range(1, nchunk + 1):
-            if nchunk % d == 0 and d * tiles <= 320 and nchunk // d >= 4:
-                parts = d
-    if nchunk % parts != 0:
-        raise ValueError("conv3x3_wgrad: %d parts do not divide the %d chunks of the contraction" % (parts, nchunk))
-    n = nchunk // parts
-    coutp = (Cout + 127) // 128 * 128
-    out = torch.empty((parts, Cout, 9, Cin), dtype=torch.float32, device=x.device)
-    call("gdm_conv1x1_packed_wb_hip", xpk, gpk, n * coutp * 512, parts, 128 * n, Cout, 9, Cin, out)
-    dw = out[0] if parts == 1 else out.sum(0)
-    return dw.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
+    return _wgrad_packed("conv3x3_wgrad", x, go, 9, parts).view(go.shape[1], 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
 
 
 def conv3x3_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1)):

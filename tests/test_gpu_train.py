@@ -785,3 +785,79 @@ def test_direct_weight_and_bias_gradient_of_small_channel_layers_equals_fp64(B, 
     assert (got_w.double() - want_w).norm().item() < 3e-5 * want_w.norm().item()
     assert (got_w.double() - want_w).abs().max().item() < 1e-4 * want_w.abs().max().item()
     assert (got_b.double() - want_b).abs().max().item() < 1e-4 * max(1.0, want_b.abs().max().item())
+
+
+@pytest.mark.parametrize("off", ["", "USE_MFMA_GEMM_TRAIN", "USE_POINTWISE_TRAIN", "USE_DIRECT_WGRAD"])
+def test_every_1x1_training_product_runs_on_the_engine_recorded_for_it(off):
+    """The recorder of tests/train_products.py (the engines replaced by stubs that note their name: nothing is computed) on ops.wx,
+    ops.conv1x1_train and ops.conv1x1_train_w gives tests/golden/train_products.json row for row: the engine of each product of every
+    shape, layout and switch setting is the one the routing chose before ops.train_plan decided it in one place."""
+    import train_products as tp
+    from geometric_aware_dense_matching_amd import ops
+    rows = tp.load("train_products.json")["rows"][off]
+    assert len(rows) >= 700
+    with tp.switched_off(settings, off):
+        bad = [(k, got, row) for k, row in rows.items()
+               for got in [tp.record_shape(ops, tp.shape_of(k), tp.LAYOUTS if not off else tp.LAYOUTS[:1])] if got != row]
+    assert not bad, "%d of %d rows differ, first: %s" % (len(bad), len(rows), bad[:3])
+
+
+# (entry, x shape, Cout, bias, the letters of tests/train_products.py the case must reach).  Each the smallest shape that reaches its
+# engines past the 2 GFLOP gate.  (2, 256, 72, 16384) has the shape of the inherited asymmetry of ops.train_plan but 1.2 GFLOP: both
+# routes agree on it; (2, 256, 136, 16384), 2.3 GFLOP, is the smallest shape on which they differ.  (2, 64, 64, 576) as a 24 x 24 map
+# has B * P = 1152 < 16384 and does not reach wgrad_direct: the map is 64 x 128 = 8192 pixels instead.
+PRODUCT_CASES = [("conv1x1_train", (2, 256, 4096), 512, True, "GGWA"), ("wx", (2, 512, 4096), 256, False, "GGW-"),
+                 ("wx", (2, 256, 16384), 72, False, "PPB-"), ("conv1x1_train", (2, 256, 16384), 72, False, "PPB-"),
+                 ("wx", (2, 256, 16384), 136, False, "PPW-"), ("conv1x1_train", (2, 256, 16384), 136, False, "PPB-"),
+                 ("conv1x1_train", (2, 64, 64, 128), 64, True, "PPDD"), ("conv1x1_train", (3, 16, 50), 24, True, "PPBF")]
+
+
+@pytest.mark.parametrize("entry,shape,cout,bias,letters", PRODUCT_CASES)
+def test_each_1x1_training_product_equals_its_planned_engine_called_alone(entry, shape, cout, bias, letters):
+    """Forward, input gradient, weight gradient and bias gradient as the autograd Functions return them == what the engine ops.train_plan
+    names gives when called alone through its public op, bit for bit; where the engine is torch.bmm (or the bias gradient a sum),
+    1e-4 of the scale of the fp64 product, as the neighbouring tests hold it."""
+    import train_products as tp
+    from geometric_aware_dense_matching_amd import ops
+    B, cin = shape[:2]
+    n = int(np.prod(shape[2:]))
+    plan = ops.train_plan(entry, B, cin, cout, n, cuda=True, bias_grad=bias)
+    in_function = plan.function == "_Conv1x1Train"
+    assert tp.LETTER[plan.fwd] + tp.LETTER[plan.dgrad] + tp.LETTER[plan.wgrad[0]] == letters[:3], plan
+    assert tp.load("train_products.json")["rows"][""][tp.key((B, cin, cout, n))].split()[tp.columns().index((entry, bias, "contiguous"))] == letters
+    torch.manual_seed(cin + cout + n)
+    conv = (torch.nn.Conv1d if len(shape) == 3 else torch.nn.Conv2d)(cin, cout, 1, bias=bias).cuda()
+    x = torch.randn(*shape, device="cuda", requires_grad=True)
+    go = torch.randn(B, cout, *shape[2:], device="cuda")
+    y = ops.wx(conv.weight.view(cout, cin), x) if entry == "wx" else ops.conv1x1_train(conv, x)
+    assert y.shape == go.shape
+    y.backward(go)
+    w2, b = conv.weight.detach().view(cout, cin), (conv.bias.detach() if bias else None)
+    x3, go3 = x.detach().view(B, cin, n), go.view(B, cout, n)
+
+    def close(got, want):
+        assert (got.double() - want).abs().max().item() < 1e-4 * max(1.0, want.abs().max().item())
+
+    # forward: the bias in the pointwise epilogue inside _Conv1x1Train, added to the product outside _WxTrain
+    if plan.fwd == "torch.bmm":
+        close(y.detach().view(B, cout, n), torch.matmul(w2.double(), x3.double()) + (b.double().view(1, -1, 1) if bias else 0.0))
+    else:
+        want = (ops.gemm_bf16x3(x3, ops.gemm_pack_weight(w2), cout) if plan.fwd == "gemm_bf16x3"
+                else ops.pointwise([x3], w2, None, b if in_function else None, w_rowmajor=True))
+        assert torch.equal(y.detach().view(B, cout, n), want + b.view(1, -1, 1) if bias and not in_function else want)
+    if plan.dgrad == "torch.bmm":
+        close(x.grad.view(B, cin, n), torch.matmul(w2.double().t(), go3.double()))
+    else:
+        want = ops.gemm_bf16x3(go3, ops.conv_pack_weight_dgrad(w2), cin) if plan.dgrad == "gemm_bf16x3" else ops.pointwise([go3], w2)
+        assert torch.equal(x.grad.view(B, cin, n), want)
+    gw, gb = conv.weight.grad.view(cout, cin), (conv.bias.grad if bias else None)
+    if plan.wgrad[0] == "torch.bmm":
+        close(gw, torch.bmm(go3.double(), x3.double().transpose(1, 2)).sum(0))
+    elif plan.wgrad[0] == "gemm_wgrad":
+        assert torch.equal(gw, ops.gemm_wgrad(x3, go3))
+    else:
+        want_w, want_b = ops.wgrad_direct(x3, go3, bias=bias and in_function)
+        assert torch.equal(gw, want_w) and (want_b is None or torch.equal(gb, want_b))
+    if bias and letters[3] != "D":
+        close(gb, go3.double().sum((0, 2)))
+    assert (letters[3] == "D") == (bias and in_function and plan.wgrad[0] == "wgrad_direct")
