@@ -7,14 +7,16 @@
 //                          (tile, symmetry) on the bit pattern of the non-negative double (ordered like the value; a NaN stays on top).
 //                          The only temporary is err[2][n][S].
 //   sym_min_kernel         one wave per (error, instance): the minimum over the symmetries, the first one on a tie.
-//   raster_kernel          one thread per (instance, triangle) by the pixel rule of include/gdm.h; a triangle whose clamped box holds
-//                          more than kSmallBox pixels is drawn by its whole wave striding over the box.  Unsigned atomicMin on the fp32
-//                          bit pattern: positive floats order like their bits and a minimum does not depend on arrival order.
+//   raster_kernel          one thread per (instance, triangle) by the pixel rule of include/gdm.h (gdm_raster.h holds its code, shared
+//                          with gdm_render.hip); a triangle whose clamped box holds more than kSmallBox pixels is drawn by its whole
+//                          wave striding over the box.  Unsigned atomicMin on the fp32 bit pattern: positive floats order like their
+//                          bits and a minimum does not depend on arrival order.
 //   vsd_counts_kernel      distance images, visibility masks and the pixel costs in one pass over the three depth images; counts are
 //                          summed per thread, per wave, per workgroup, then one integer atomicAdd per workgroup and counter.
 // No allocation and no host read in any entry point: they capture in a hipGraph.  Accumulators are cleared by fill_u32_kernel, not by
 // hipMemsetAsync: replayed from a captured graph, the runtime's memset node left a 16-byte non-zero pattern in the VSD counters.
 #include "gdm_common.h"
+#include "gdm_raster.h"
 
 namespace {
 
@@ -22,7 +24,6 @@ constexpr int kThreads = 256;
 constexpr int kPPT = 2;                                                    // model points a thread keeps in registers
 constexpr int kTile = kThreads * kPPT;
 constexpr int kSymChunk = 64;                                              // symmetric ground truths formed in LDS at a time
-constexpr int kSmallBox = 64;                                              // pixels a single thread may walk for one triangle
 constexpr unsigned kInfBits = 0x7f800000u;
 
 typedef unsigned long long u64;
@@ -155,46 +156,11 @@ __global__ __launch_bounds__(64) void sym_min_kernel(const double* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // rasteriser
 
-struct TriSetup {
-    int x0, y0, x1, y1, x2, y2;                                            // snapped vertices (1/256 px), normalised winding
-    double iz0, iz1, iz2;                                                  // 1 / z of the vertices
-    int px0, px1, py0, py1;                                                // clamped pixel box, inclusive
-};
-
-__device__ __forceinline__ long long edge_fn(int ax, int ay, int bx, int by, long long X, long long Y)
-{
-    return (long long)(bx - ax) * (Y - ay) - (long long)(by - ay) * (X - ax);
-}
-
-__device__ __forceinline__ bool edge_in(long long w, int dx, int dy) { return w > 0 || (w == 0 && (dy < 0 || (dy == 0 && dx > 0))); }
-
 __device__ __forceinline__ void shade(const TriSetup& s, int px, int py, unsigned* __restrict__ zb, int W)
 {
-    const long long X = (long long)px * 256, Y = (long long)py * 256;
-    const long long w0 = edge_fn(s.x1, s.y1, s.x2, s.y2, X, Y);           // opposite vertex 0
-    const long long w1 = edge_fn(s.x2, s.y2, s.x0, s.y0, X, Y);
-    const long long w2 = edge_fn(s.x0, s.y0, s.x1, s.y1, X, Y);
-    if (!(edge_in(w0, s.x2 - s.x1, s.y2 - s.y1) && edge_in(w1, s.x0 - s.x2, s.y0 - s.y2) && edge_in(w2, s.x1 - s.x0, s.y1 - s.y0)))
-        return;
-    const double A = (double)((w0 + w1) + w2);
-    const double iz = (((double)w0 * s.iz0 + (double)w1 * s.iz1) + (double)w2 * s.iz2) / A;
-    const float d = (float)(1.0 / iz);
-    atomicMin(&zb[(long)py * W + px], __float_as_uint(d));
-}
-
-__device__ __forceinline__ bool project_vertex(const double* __restrict__ rt, double fx, double fy, double cx, double cy, double near,
-                                               double x, double y, double z, int& xs, int& ys, double& iz)
-{
-    const double X = ((rt[0] * x + rt[1] * y) + rt[2] * z) + rt[3];
-    const double Y = ((rt[4] * x + rt[5] * y) + rt[6] * z) + rt[7];
-    const double Z = ((rt[8] * x + rt[9] * y) + rt[10] * z) + rt[11];
-    if (!(Z > near)) return false;
-    const double u = fx * (X / Z) + cx, v = fy * (Y / Z) + cy;
-    if (!(fabs(u) <= 65536.0) || !(fabs(v) <= 65536.0)) return false;
-    xs = (int)(long long)floor(u * 256.0 + 0.5);
-    ys = (int)(long long)floor(v * 256.0 + 0.5);
-    iz = 1.0 / Z;
-    return true;
+    long long w0, w1, w2;
+    if (!edge_values(s, px, py, w0, w1, w2)) return;
+    atomicMin(&zb[(long)py * W + px], __float_as_uint(pixel_depth(s, w0, w1, w2)));
 }
 
 template <typename VT>
@@ -211,36 +177,9 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(const VT* __restrict__
     if (valid) {
         b = (int)(gid / F);
         const int f = (int)(gid % F);
-        const int i0 = faces[(long)f * 3], i1 = faces[(long)f * 3 + 1], i2 = faces[(long)f * 3 + 2];
-        valid = i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V;
-        if (valid) {
-            const double* rt = RT + (long)b * 12;
-            const double* kk = Kmat + (k_per_instance ? (long)b * 9 : 0);
-            const double fx = kk[0], fy = kk[4], cx = kk[2], cy = kk[5];
-            valid = project_vertex(rt, fx, fy, cx, cy, near, (double)verts[(long)i0 * 3], (double)verts[(long)i0 * 3 + 1],
-                                   (double)verts[(long)i0 * 3 + 2], s.x0, s.y0, s.iz0);
-            valid = project_vertex(rt, fx, fy, cx, cy, near, (double)verts[(long)i1 * 3], (double)verts[(long)i1 * 3 + 1],
-                                   (double)verts[(long)i1 * 3 + 2], s.x1, s.y1, s.iz1) && valid;
-            valid = project_vertex(rt, fx, fy, cx, cy, near, (double)verts[(long)i2 * 3], (double)verts[(long)i2 * 3 + 1],
-                                   (double)verts[(long)i2 * 3 + 2], s.x2, s.y2, s.iz2) && valid;
-        }
-        if (valid) {
-            const long long A2 = (long long)(s.x1 - s.x0) * (s.y2 - s.y0) - (long long)(s.x2 - s.x0) * (s.y1 - s.y0);
-            if (A2 == 0) valid = false;
-            if (A2 < 0) {                                                  // normalise the winding: both are drawn
-                const int tx = s.x1, ty = s.y1;
-                const double tz = s.iz1;
-                s.x1 = s.x2; s.y1 = s.y2; s.iz1 = s.iz2;
-                s.x2 = tx; s.y2 = ty; s.iz2 = tz;
-            }
-            const int xmin = min(s.x0, min(s.x1, s.x2)), xmax = max(s.x0, max(s.x1, s.x2));
-            const int ymin = min(s.y0, min(s.y1, s.y2)), ymax = max(s.y0, max(s.y1, s.y2));
-            s.px0 = max((xmin + 255) >> 8, 0);
-            s.px1 = min(xmax >> 8, W - 1);
-            s.py0 = max((ymin + 255) >> 8, 0);
-            s.py1 = min(ymax >> 8, H - 1);
-            if (s.px0 > s.px1 || s.py0 > s.py1) valid = false;
-        }
+        bool swapped;
+        valid = tri_setup(verts, V, faces[(long)f * 3], faces[(long)f * 3 + 1], faces[(long)f * 3 + 2], RT + (long)b * 12,
+                          Kmat + (k_per_instance ? (long)b * 9 : 0), near, H, W, s, swapped);
     }
     const long box = valid ? (long)(s.px1 - s.px0 + 1) * (s.py1 - s.py0 + 1) : 0;
     if (valid && box <= kSmallBox) {
@@ -253,13 +192,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(const VT* __restrict__
     while (big) {
         const int src = __ffsll((long long)big) - 1;
         big &= big - 1;
-        TriSetup c;
-        c.x0 = __shfl(s.x0, src, 64); c.y0 = __shfl(s.y0, src, 64);
-        c.x1 = __shfl(s.x1, src, 64); c.y1 = __shfl(s.y1, src, 64);
-        c.x2 = __shfl(s.x2, src, 64); c.y2 = __shfl(s.y2, src, 64);
-        c.iz0 = __shfl(s.iz0, src, 64); c.iz1 = __shfl(s.iz1, src, 64); c.iz2 = __shfl(s.iz2, src, 64);
-        c.px0 = __shfl(s.px0, src, 64); c.px1 = __shfl(s.px1, src, 64);
-        c.py0 = __shfl(s.py0, src, 64); c.py1 = __shfl(s.py1, src, 64);
+        const TriSetup c = tri_from_lane(s, src);
         const int cb = __shfl(b, src, 64);
         unsigned* zb = zbuf + (long)cb * H * W;
         const int bw = c.px1 - c.px0 + 1;

@@ -2584,3 +2584,60 @@ def vsd_counts(depth_est, depth_gt, depth_test, K, delta, taus, diameter=None, t
     if tlinear:
         return counts[:, 0], counts[:, 1], counts[:, 2:], tl
     return counts[:, 0], counts[:, 1], counts[:, 2:]
+
+
+RENDER_MAX_SLOTS = 8          # GDM_RENDER_MAX_SLOTS / GDM_RENDER_MAX_OBJECTS of include/gdm.h (an enum there; the library refuses beyond)
+RENDER_MAX_OBJECTS = 256
+
+
+def render_frames(verts, vcol, vnrm, faces, obj_face0, slot_obj, RT, K, light, H, W, ambient, near):
+    """Colour, depth, instance mask, face ids and per-slot statistics of n frames of S posed objects by the rule of include/gdm.h
+    (gdm_render_frames_hip): verts f32|f64[Vt,3], vcol u8[Vt,3], vnrm f32[Vt,3], faces i32[Ft,3] on the device; obj_face0 a HOST
+    sequence of O+1 ascending face offsets; slot_obj i32[n,S] (-1: empty), RT f64[n,S,3,4], K f64[3,3] or f64[n,3,3], light f64[n,3]
+    -> rgb u8[n,H,W,3], depth f32[n,H,W], inst u8[n,H,W], face i32[n,H,W], stats i32[n,S,6] = (px_all, px_vis, xmin, ymin, xmax,
+    ymax).  render.render_frames is the interface with defaults and the derived outputs."""
+    if not isinstance(verts, torch.Tensor) or verts.dtype not in (torch.float32, torch.float64):
+        _dev(verts, torch.float32, "verts")
+        raise TypeError("verts must be float32 or float64")
+    verts = _dev(verts, verts.dtype, "verts")
+    vcol = _dev(vcol, torch.uint8, "vcol")
+    vnrm = _dev(vnrm, torch.float32, "vnrm")
+    faces = _dev(faces, torch.int32, "faces")
+    slot_obj = _dev(slot_obj, torch.int32, "slot_obj")
+    RT = _dev(RT, torch.float64, "RT")
+    light = _dev(light, torch.float64, "light")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError("verts must be [Vt,3], got %s" % (tuple(verts.shape),))
+    Vt = verts.shape[0]
+    if tuple(vcol.shape) != (Vt, 3) or tuple(vnrm.shape) != (Vt, 3):
+        raise ValueError("vcol and vnrm must be [Vt=%d,3], got %s and %s" % (Vt, tuple(vcol.shape), tuple(vnrm.shape)))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError("faces must be [Ft,3], got %s" % (tuple(faces.shape),))
+    if RT.dim() != 4 or tuple(RT.shape[2:]) != (3, 4) or RT.shape[0] < 1 or RT.shape[1] < 1:
+        raise ValueError("RT must be [n,S,3,4], got %s" % (tuple(RT.shape),))
+    n, S = RT.shape[:2]
+    if S > RENDER_MAX_SLOTS:
+        raise ValueError("S=%d slots, at most %d" % (S, RENDER_MAX_SLOTS))
+    if tuple(slot_obj.shape) != (n, S):
+        raise ValueError("slot_obj must be [n=%d,S=%d], got %s" % (n, S, tuple(slot_obj.shape)))
+    if tuple(light.shape) != (n, 3):
+        raise ValueError("light must be [n=%d,3], got %s" % (n, tuple(light.shape)))
+    table = [int(v) for v in obj_face0]
+    O = len(table) - 1
+    if not 1 <= O <= RENDER_MAX_OBJECTS:
+        raise ValueError("obj_face0 must hold O+1 offsets for 1 <= O <= %d objects, got %d values" % (RENDER_MAX_OBJECTS, len(table)))
+    K, kpi = _k64(K, n, "K")
+    H, W = int(H), int(W)
+    dev = RT.device
+    nbytes = call("gdm_render_frames_workspace_bytes", n, S, H, W)
+    if nbytes == 0:
+        raise ValueError("render_frames: n=%d S=%d H=%d W=%d outside what gdm_render_frames_hip addresses" % (n, S, H, W))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    rgb = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+    depth = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+    inst = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+    face = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+    stats = torch.empty((n, S, 6), dtype=torch.int32, device=dev)
+    call("gdm_render_frames_hip", verts, int(verts.dtype == torch.float64), vcol, vnrm, faces, (ctypes.c_int32 * (O + 1))(*table), slot_obj,
+         RT, K, kpi, light, float(ambient), float(near), n, S, O, Vt, faces.shape[0], H, W, ws, nbytes, rgb, depth, inst, face, stats)
+    return rgb, depth, inst, face, stats

@@ -19,7 +19,8 @@ Three things differ by design:
     batch GROUPED per object (infer.run_multi_object) instead of one batch-1 forward per instance (:298-314), with the
     input-independent mesh descriptors cached per object;
   * BOP dataset loaders are out of scope: `-data synthetic` (default) feeds generated crops
-    with the loader's item layout, a real loader can be plugged through `--dataset-factory module:function`.
+    with the loader's item layout, `-data rendered` feeds RGB-D frames of the object's mesh drawn on the GPU (render.py), a real
+    loader can be plugged through `--dataset-factory module:function`.
 """
 import argparse
 import importlib
@@ -62,7 +63,10 @@ def build_parser():
     p.add_argument("--gpu", type=str, default=None)
     p.add_argument("--deterministic", action="store_true")
     # additions (not in the reference)
-    p.add_argument("-data", type=str, default="synthetic")
+    p.add_argument("-data", type=str, default="synthetic", choices=["synthetic", "rendered"],
+                   help="synthetic = generated crops (random surfaces, nothing to learn); rendered = RGB-D frames of the object's mesh "
+                        "drawn on the GPU (render.RenderedFrames) -- the meshes of --models-dir, or render.demo_mesh without it; implies "
+                        "--gt-targets device and, with -state=test, --single-object on held-out frames (another seed)")
     p.add_argument("--dataset-factory", type=str, default=None, help="module:function(cfg, split) -> torch Dataset")
     p.add_argument("--model-variant", type=str, default="ffb6d", choices=["ffb6d", "dgcnn"],
                    help="ffb6d = models/geoMatch.py (CNN + RandLA + SplineCNN); dgcnn = models/geoMatch_DGCNN.py")
@@ -368,6 +372,46 @@ class Trainer:
                 del self.history[:len(self.history) - self.HISTORY_CAP]
 
 
+RENDERED_DISTRACTORS = 3          # -data rendered --models-dir: at most this many other meshes of DIR are drawn beside the object
+
+
+def _rendered_meshes(args, cls_id):
+    """-data rendered: ([mesh dicts in the model file's unit (mm)], index of object cls_id).  With --models-dir the object's
+    obj_%06d.ply and up to RENDERED_DISTRACTORS other meshes of DIR; without it render.demo_mesh(seed=cls_id) and a second demo mesh."""
+    from . import model_prep, render
+    models_dir = getattr(args, "models_dir", None)
+    if not models_dir:
+        out = []
+        for seed in (cls_id, cls_id + 1000):
+            m = render.demo_mesh(level=3, seed=seed)
+            out.append(dict(m, verts=m["verts"] * 1000.0))
+        return out, 0
+    ply = os.path.join(models_dir, "obj_%06d.ply" % cls_id)
+    if not os.path.exists(ply):
+        raise SystemExit("-data rendered: %s does not exist" % ply)
+    others = sorted(f for f in os.listdir(models_dir) if f.startswith("obj_") and f.endswith(".ply") and f != os.path.basename(ply))
+    out = []
+    for path in [ply] + [os.path.join(models_dir, f) for f in others[:RENDERED_DISTRACTORS]]:
+        v, f, nr, c = model_prep.load_ply(path)
+        out.append(dict(verts=v, faces=f, normals=nr, colors=c))
+    return out, 0
+
+
+def make_rendered(args, split, cls_id, batch_size, device):
+    """-data rendered: render.RenderedFrames over the object's mesh (metres), other meshes as distractors and a backdrop plane;
+    --synthetic-items frames per epoch; the test split draws from another seed and carries no box jitter."""
+    from . import render
+    meshes, target = _rendered_meshes(args, cls_id)
+    packed = [(m["verts"], m["faces"], m.get("colors"), m.get("normals")) for m in meshes]
+    packed.append(render._as_mesh(render.backdrop_mesh(synthetic.LM_K, 480, 640, z=1500.0)))
+    scene = render.SceneMeshes(packed, device=device, scale=0.001)
+    ds = dataset_config(args.dataset_name)
+    model_xyz = _model_points(args, ds, cls_id)[:, :3] / 1000.0
+    return render.RenderedFrames(scene, target, model_xyz, batch_size, args.n_points, seed=0 if split == "train" else 1,
+                                 n_batches=max(1, args.synthetic_items // batch_size), backdrop_obj=len(packed) - 1,
+                                 train=split == "train", cls_id=cls_id)
+
+
 def make_dataset(args, split, cls_ids=None):
     if args.dataset_factory:
         mod, fn = args.dataset_factory.split(":")
@@ -381,6 +425,9 @@ def make_dataset(args, split, cls_ids=None):
 
 
 def _model_points(args, ds, cls_id):
+    if getattr(args, "data", "synthetic") == "rendered":                    # the table of the mesh that is drawn, never another one
+        from . import model_prep
+        return model_prep.build_model_points(_rendered_meshes(args, cls_id)[0][0], args.n_mesh)
     path = os.path.join(ds["model_pth"], "obj_%06d_fps.npy" % cls_id)
     if os.path.exists(path):
         return np.load(path)
@@ -458,10 +505,18 @@ def train(args):
         rank, local_rank, world = 0, args.local_rank, 1       # one object per rank: no process group (--objects-across-gpus)
     else:
         rank, local_rank, world = init_distributed("nccl", device)
-    train_ds = make_dataset(args, "train")
-    sampler = torch.utils.data.distributed.DistributedSampler(train_ds) if world > 1 else None
-    loader = torch.utils.data.DataLoader(train_ds, batch_size=batch_size, shuffle=sampler is None, drop_last=True,
-                                         num_workers=4, sampler=sampler)
+    if getattr(args, "data", "synthetic") == "rendered":       # batches come from the device as they are: no DataLoader, no sampler
+        if world > 1:
+            raise SystemExit("-data rendered draws its frames on one device; run it as a single process")
+        args.gt_targets = "device"
+        loader, sampler = make_rendered(args, "train", args.cls_id, batch_size, device), None
+        n_items = len(loader) * batch_size
+    else:
+        train_ds = make_dataset(args, "train")
+        sampler = torch.utils.data.distributed.DistributedSampler(train_ds) if world > 1 else None
+        loader = torch.utils.data.DataLoader(train_ds, batch_size=batch_size, shuffle=sampler is None, drop_last=True,
+                                             num_workers=4, sampler=sampler)
+        n_items = len(train_ds)
     model = build_model(args, args.cls_id).to(device)
     # same update rule as the reference's Adam (train_lm.py:414-416); `fused`: one multi-tensor kernel per step instead of ~25 foreach launches
     optimizer = torch.optim.Adam(model.parameters(), lr=0.0001, weight_decay=args.weight_decay, fused=settings.USE_FUSED_ADAM)
@@ -479,7 +534,7 @@ def train(args):
         from .train_graph import GraphedTrainStep
         graphed = GraphedTrainStep(model, optimizer, device,      # before the schedulers: they then drive the device-side lr
                                    gt_targets=getattr(args, "gt_targets", "loader"))
-    steps = max(1, args.epochs * len(train_ds) // batch_size // 6 // max(world, 1))
+    steps = max(1, args.epochs * n_items // batch_size // 6 // max(world, 1))
     lr_scheduler = torch.optim.lr_scheduler.CyclicLR(optimizer, base_lr=1e-6, max_lr=1e-3, cycle_momentum=False,
                                                      step_size_up=steps, step_size_down=steps, mode="triangular")
     bnm = BNMomentumScheduler(model, lambda i: max(args.bn_momentum * args.bn_decay ** int(i * batch_size / args.decay_step),
@@ -499,7 +554,8 @@ def test(args):
     batch_size = args.batch_size or ds["val_batch_size"]
     device = torch.device("cuda", args.local_rank)
     torch.cuda.set_device(device)
-    ids = [args.cls_id] if args.single_object else sorted(ds["objs"])
+    rendered = getattr(args, "data", "synthetic") == "rendered"
+    ids = [args.cls_id] if args.single_object or rendered else sorted(ds["objs"])
     ckpt_root = args.checkpoint or ds["checkpoints"]
     model_dict = {}
     for cid in ids:
@@ -508,7 +564,10 @@ def test(args):
         if os.path.exists(stem + ".pth.tar"):                 # the reference also skips objects without a checkpoint (:336)
             load_checkpoint(model, None, stem, device=device, strict=ds["load_strict"])
         model_dict[cid] = model.eval()
-    loader = torch.utils.data.DataLoader(make_dataset(args, "test", cls_ids=ids), batch_size=batch_size, shuffle=False, num_workers=2)
+    if rendered:
+        loader = make_rendered(args, "test", args.cls_id, batch_size, device)
+    else:
+        loader = torch.utils.data.DataLoader(make_dataset(args, "test", cls_ids=ids), batch_size=batch_size, shuffle=False, num_workers=2)
     graphs = {}
     results = []
     pose_kw = dict(pose_fit=args.pose_fit, icp_iters=args.icp_iters,

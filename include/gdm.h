@@ -1058,6 +1058,46 @@ int gdm_vsd_counts_hip(const float* depth_est, const float* depth_gt, const floa
                        double diameter, int inf_is_empty, int32_t* counts, double* tl_sums, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training frames from meshes: colour, depth, instance mask, face ids and per-slot visibility statistics of n frames of S posed
+ * objects each (render.render_frames_numpy restates the rule bit for bit).  Parity with BOP's renderers or with
+ * BlenderProc's PBR frames is NOT claimed: the image is defined by the rule written here.
+ *
+ * THE SCENE  O meshes concatenated: verts f32[Vt,3] (verts_f64 0) or f64[Vt,3] (1), vcol u8[Vt,3], vnrm f32[Vt,3] (object frame);
+ * faces i32[Ft,3] index the concatenated vertices; obj_face0: HOST array i32[O+1], object o owns the faces obj_face0[o] ..
+ * obj_face0[o+1]-1 (strictly ascending, from >= 0 to <= Ft; refused otherwise).  slot_obj i32[n,S]: the object of each slot, -1 for
+ * an empty one -- DEVICE data the entry cannot look at: the kernel treats every value outside [0, O) as an empty slot and never
+ * indexes with it.  RT f64[n,S,3,4]; K f64[3,3] (k_per_instance 0) or f64[n,3,3] (1); light f64[n,3], a unit vector in the camera
+ * frame pointing from the surface towards the light; ambient in [0, 1]; near >= 0.
+ *
+ * THE RULE  Coverage and depth of every triangle are THE PIXEL RULE of gdm_render_depth_hip above, unchanged (one copy of the code
+ * serves both entries).
+ *   layers      per (frame, slot, pixel) the minimum over the object's covering faces of the 64-bit key (fp32 depth bits << 32) |
+ *               global face id: the nearest face, the lower id among equal depths.  Order-independent, hence reproducible.
+ *   winner      per pixel the slot with the smallest depth bits, the lower slot on a tie
+ *   attributes  the winning face is set up again; when the winding normalisation swapped vertices 1 and 2 their attributes swap too.
+ *               With w_i the edge values at the pixel: q_i = (double) w_i * (1 / z_i), Q = (q0 + q1) + q2, and every attribute is
+ *               ((q0 a0 + q1 a1) + q2 a2) / Q in fp64 -- the colour channels as levels 0..255, the normal's three components
+ *   shading     the interpolated normal o is rotated by the slot's R, n_i = (R_i0 ox + R_i1 oy) + R_i2 oz;
+ *               len = sqrt((nx nx + ny ny) + nz nz); cos = len > 0 ? max(((nx lx + ny ly) + nz lz) / len, 0) : 0;
+ *               k = ambient + (1 - ambient) cos; channel = (u8) min(255, floor(c k + 0.5))
+ * OUTPUTS  rgb u8[n,H,W,3]; depth f32[n,H,W] (the winner's, 0 where empty); inst u8[n,H,W] (slot + 1, 0 where empty); face
+ * i32[n,H,W] (-1 where empty); stats i32[n,S,6] = (px_all, px_vis, xmin, ymin, xmax, ymax): px_all = the non-empty pixels of the
+ * slot's own layer (BOP's px_count_all, clipped to the image), px_vis = the pixels the slot wins, the box that of the won pixels,
+ * (W, H, -1, -1) when there are none.
+ * workspace: gdm_render_frames_workspace_bytes(n, S, H, W) = n S H W 8 bytes (the layers; 0 for arguments the entry refuses),
+ * 8-byte aligned.  No allocation and no host read: the call captures in a hipGraph.
+ * LIMITS (what the index arithmetic addresses; refused beyond): S <= GDM_RENDER_MAX_SLOTS, O <= GDM_RENDER_MAX_OBJECTS (the face
+ * ranges travel by value in the kernel arguments), n <= 65535, H, W <= 16384, n S Fmax <= 2^30 with Fmax the largest object's face
+ * count. */
+enum { GDM_RENDER_MAX_SLOTS = 8, GDM_RENDER_MAX_OBJECTS = 256 };
+size_t gdm_render_frames_workspace_bytes(int n, int S, int H, int W);
+int gdm_render_frames_hip(const void* verts, int verts_f64, const uint8_t* vcol, const float* vnrm, const int32_t* faces,
+                          const int32_t* obj_face0 /* host array */, const int32_t* slot_obj, const double* RT, const double* K,
+                          int k_per_instance, const double* light, double ambient, double near, int n, int S, int O, int Vt, int Ft,
+                          int H, int W, void* workspace, size_t workspace_bytes, uint8_t* rgb, float* depth, uint8_t* inst,
+                          int32_t* face, int32_t* stats, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Object model preparation: from a triangle mesh to the table obj_%06d_fps.npy holds ([M,9] = xyz in mm, rgb 0..255, unit normal,
  * rows in farthest-point order; read by datasets/lm/linemod_pbr.py:89-97, evaluator.py:34-40, models/SplineCNN.py:116).  The script
  * that wrote the reference's files is not part of it, so each entry is defined by the rule written here, which model_prep.py
