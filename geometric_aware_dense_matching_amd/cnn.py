@@ -76,14 +76,12 @@ class BasicBlock(nn.Module):
             # 64 x 64 and 32 x 32 stages: both 3x3 convolutions on the split-bf16 MFMA implicit-GEMM kernel with BN, ReLU and the
             # residual add in its epilogue (MIOpen's fp32 path here is a vector-ALU Winograd kernel, 2.7x slower).  The epilogue
             # also writes the NEXT convolution's operand (bf16 hi / lo planes): conv1 -> conv2 needs no fp32 map at all, and a block
-            # hands its packed output to the next block on the tensor it returns (`_gdm_packed`), so one pack launch feeds a whole
+            # hands its packed output to the next block on the tensor it returns (ops.carry_packed), so one pack launch feeds a whole
             # chain of blocks.
             s1, b1 = folded_bn(self.bn1)
             planes = self.conv1.weight.shape[0]
             stride = self.conv1.stride[0]
-            xin = getattr(x, "_gdm_packed", None)
-            if xin is None or xin.shape != tuple(x.shape):
-                xin = x
+            xin = ops.packed_of(x) or x
             dconv = self.downsample[0] if self.downsample is not None else None
             own_ds = (settings.USE_MFMA_STRIDED and dconv is not None and isinstance(dconv, nn.Conv2d) and dconv.kernel_size == (1, 1) and dconv.bias is None
                       and dconv.stride == self.conv1.stride and dconv.padding == (0, 0)
@@ -108,8 +106,7 @@ class BasicBlock(nn.Module):
             if not chain:
                 return ops.conv3x3_bf16x3(mid, self._packed_weight(self.conv2), planes, s2, b2, ops.ACT_RELU, res)
             out, opk = ops.conv3x3_bf16x3(mid, self._packed_weight(self.conv2), planes, s2, b2, ops.ACT_RELU, res, out_packed=True)
-            out._gdm_packed = opk
-            return out
+            return ops.carry_packed(out, opk)
         if fused_eval(x, self):
             # eval: conv -> [BN+ReLU] -> conv -> [BN + (BN'd) residual + ReLU], each bracket one HIP launch
             s1, b1 = folded_bn(self.bn1)

@@ -9,13 +9,14 @@
 //   out[b,co,y,x] = act( scale[co] * sum_{tap,ci} W[co,ci,tap] * in[b,ci,y+ky-1,x+kx-1] + shift[co] (+ res) )
 //
 // Data layout: activations are re-packed once per layer (pack kernel below) into bf16 hi / lo planes of 8 channels with a
-// one-pixel zero border (fragment-planar, see conv_pack_act_kernel), so a tap is just a pixel offset, the zero padding is
+// one-pixel zero border (fragment-planar: gdm_packed_act.h defines the format), so a tap is just a pixel offset, the zero padding is
 // real zeros and every operand load of a wave is two contiguous 512-B runs.  Weights are packed once per weight change into
 // rows (tap, chunk, co) of the same 512-B format.  Then the kernel is the matching kernel's shape: a wave keeps
 // 32 pixels x 128 channels of one (tap, chunk) in 64 VGPRs as the MFMA A operand, 128 output channels of that
 // (tap, chunk) sit in a double-buffered, XOR-swizzled LDS panel as the B operand (global -> registers before the
 // MFMAs, registers -> LDS after them, ONE barrier per panel), 9 * Cin/128 panels accumulate into four 32x32 tiles.
 #include "gdm_common.h"
+#include "gdm_packed_act.h"
 #include <math.h>
 #include <limits.h>
 #include <stdlib.h>
@@ -23,6 +24,7 @@
 namespace {
 
 constexpr int ROWB = 512;                 // bytes per packed row (128 channels, hi | lo)
+static_assert(ROWB == GDM_PK_PLANES * GDM_PK_GRANULE, "a pixel's 128 channels are a row's worth of granules");
 constexpr int CV_PIX = 256;               // pixels per workgroup (32 per wave)
 constexpr int CV_CO = 128;                // output channels per workgroup
 constexpr int CV_PANEL = CV_CO * ROWB;    // 64 KiB
@@ -30,26 +32,16 @@ constexpr int CV_PANEL = CV_CO * ROWB;    // 64 KiB
 #define GDM_CONV16_PF 2
 #endif
 
-__device__ __forceinline__ void split8(const float* v, unsigned (&hi)[4], unsigned (&lo)[4])
-{
-#pragma unroll
-    for (int j = 0; j < 4; ++j) gdm_split2(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
-}
-
-// x f32[B,C,H,W] -> packed activations, PLANAR by 16-byte MFMA fragment: for every (b, 128-channel chunk) 32 planes of the
-// zero-bordered pixel grid, plane q < 16 = bf16 "hi" of channels [8q, 8q+8), plane 16+q = their "lo"; element (yy, xx) of a
-// plane is 16 B at ((b*nchunk + chunk)*32 + plane) * (H+2)(W+2) + yy*(W+2) + xx.  A wave's operand load (lane = pixel, one
-// fragment) is then two contiguous 512-B runs for ANY tap shift, instead of 32 scattered 32-B pieces of pixel-major rows.
+// x f32[B,C,H,W] -> packed activations (the layout: gdm_packed_act.h)
 // one block: 64 consecutive pixels of one image x one 128-channel chunk
 __global__ __launch_bounds__(256) void conv_pack_act_kernel(const float* __restrict__ x, int C, int H, int W,
                                                             unsigned char* __restrict__ out)
 {
     __shared__ float t[128][65];
     const int b = blockIdx.z, chunk = blockIdx.y;
-    const int nchunk = (C + 127) / 128;
+    const gdm_packed_map pm{C, H, W};
     const int cvalid = min(128, C - chunk * 128);          // a trailing partial chunk: the missing channels' planes stay zero
     const int hw = H * W;
-    const long plane = (long)(H + 2) * (W + 2);
     const int p0 = blockIdx.x * 64;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int p = min(p0 + lane, hw - 1);
@@ -59,15 +51,12 @@ __global__ __launch_bounds__(256) void conv_pack_act_kernel(const float* __restr
     const int pp = p0 + lane;
     if (pp >= hw) return;
     const int y = pp / W, xx = pp - y * W;
-    unsigned char* o = out + (((long)(b * nchunk + chunk) * 32) * plane + (long)(y + 1) * (W + 2) + xx + 1) * 16;
+    unsigned char* o = out + pm.pixel(b, chunk, y, xx);
     for (int q = w; q * 8 < cvalid; q += 4) {            // consecutive lanes = consecutive pixels: 1-KiB contiguous stores
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = t[q * 8 + j][lane];
-        unsigned hi[4], lo[4];
-        split8(v, hi, lo);
-        *reinterpret_cast<uint4*>(o + (long)q * plane * 16) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-        *reinterpret_cast<uint4*>(o + (long)(16 + q) * plane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+        gdm_packed_store8(o, pm.group(q), pm.group(GDM_PK_LO + q), v);
     }
 }
 
@@ -96,11 +85,11 @@ __global__ __launch_bounds__(256) void conv_pack_w_kernel(const float* __restric
         const bool in = co < Cout && ci < Cin;
         v[j] = !in ? 0.f : dgrad ? w[((long)ci * Cout + co) * taps + (taps - 1 - tap)] : w[((long)co * Cin + ci) * taps + tap];
     }
-    unsigned hi[4], lo[4];
-    split8(v, hi, lo);
+    gdm_u32x4 hi, lo;
+    gdm_split8(v, hi, lo);
     unsigned char* r = out + row * ROWB;
-    *reinterpret_cast<uint4*>(r + ch * 16) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-    *reinterpret_cast<uint4*>(r + 256 + ch * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    *reinterpret_cast<gdm_u32x4*>(r + ch * 16) = hi;
+    *reinterpret_cast<gdm_u32x4*>(r + 256 + ch * 16) = lo;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -190,8 +179,9 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
     const int b = (int)(pc / hw);                                   // one image per wave (hw % MF_WPIX == 0)
     const int prem = (int)(pc - (long)b * hw);
     const int Wi = W * stride;
-    const long plane = (long)(H * stride + 2) * (Wi + 2);           // input planes (operand loads)
-    const long oplane = (long)(H + 2) * (W + 2);                    // output planes (packed epilogue)
+    // input planes (operand loads): gdm_packed_map{Cin, H stride, Wi}.plane(); the reader keeps its own arithmetic (from the members,
+    const long plane = (long)(H * stride + 2) * (Wi + 2);           // the same values compile to other scalar code in every instance)
+    const gdm_packed_map om{Cout, H, W};                            // the packed output (packed epilogue)
     // Operand loads are BUFFER loads: descriptor over the packed activations, per-lane byte offset fixed for the whole kernel
     // (plane kg of a k-step + the lane's pixel), everything that changes per panel / tap / k-step in the SCALAR offset.  The flat
     // form recomputed a 64-bit per-lane address for every load (v_mad_u64 / v_lshl_add_u64 / v_mul_lo clumps of ~45 vector
@@ -205,7 +195,7 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
         const int pr = prem + 16 * ph;
         const int yy = pr / W, xx = pr - yy * W;
         const long pixbase = rowidx ? (long)max(rowidx[pc + l16 + 16 * ph], 0) : (long)(yy * stride) * (Wi + 2) + (long)(xx + l16) * stride;
-        avoff[ph] = (int)(((long)kg * plane + pixbase) * 16);
+        avoff[ph] = (int)(((long)kg * plane + pixbase) * GDM_PK_GRANULE);
     }
 
     gdm_u32x4 ahi[NS][NPH], alo[NS][NPH];                               // fragments of k-step S, pixel fragment ph
@@ -217,11 +207,11 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
         if (++p.kx == 3) { p.kx = 0; if (++p.ky == 3) { p.ky = 0; ++p.chunk; } }
         return p;
     };
-    const int a_base = (int)(((long)(rowidx ? 0 : b) * nchunk * 32) * plane * 16);
-    const int a_chunk = (int)(32 * plane * 16), a_rowb = (Wi + 2) * 16;
-    auto pan_a = [&](Pan p) -> int { return a_base + p.chunk * a_chunk + p.ky * a_rowb + p.kx * 16; };
-    const int sstride = (int)(4 * plane * 16);                      // plane 4 S + kg -> 4 (S + 1) + kg
-    const int lostride = (int)(16 * plane * 16);                    // hi plane q -> lo plane 16 + q
+    const int a_base = (int)(((long)(rowidx ? 0 : b) * nchunk * GDM_PK_PLANES) * plane * GDM_PK_GRANULE);
+    const int a_chunk = (int)(GDM_PK_PLANES * plane * GDM_PK_GRANULE), a_rowb = (Wi + 2) * GDM_PK_GRANULE;
+    auto pan_a = [&](Pan p) -> int { return a_base + p.chunk * a_chunk + p.ky * a_rowb + p.kx * GDM_PK_GRANULE; };
+    const int sstride = (int)(4 * plane * GDM_PK_GRANULE);          // plane 4 S + kg -> 4 (S + 1) + kg
+    const int lostride = (int)(GDM_PK_LO * plane * GDM_PK_GRANULE); // hi plane q -> lo plane 16 + q
     auto load_a = [&](int r, int S) {
 #pragma unroll
         for (int ph = 0; ph < NPH; ++ph) {
@@ -471,13 +461,12 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
     if (outpk) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         const int lr = lane & 31, h = lane >> 5;
-        const int ochunks = (Cout + 127) / 128;
         const int ochunk = co0 / 128;
 #pragma unroll
         for (int half = 0; half < MF_WPIX / 32; ++half) {
             const int pp = prem + 32 * half + lr;                    // this lane's pixel of the wave's tile
             const int yy = pp / W, xx = pp - yy * W;
-            unsigned char* ob = outpk + (((long)(b * ochunks + ochunk) * 32) * oplane + (long)(yy + 1) * (W + 2) + xx + 1) * 16;
+            unsigned char* ob = outpk + om.pixel(b, ochunk, yy, xx);
             const float* row = tl + (32 * half + lr) * TST;
 #pragma unroll
             for (int it = 0; it < NCB; ++it) {
@@ -487,10 +476,7 @@ __global__ __launch_bounds__(MF_THREADS) void conv_mfma16_kernel(const unsigned 
                 const float4 a0 = *reinterpret_cast<const float4*>(row + ql * 8);
                 const float4 a1 = *reinterpret_cast<const float4*>(row + ql * 8 + 4);
                 const float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                unsigned hi[4], lo[4];
-                split8(v, hi, lo);
-                *reinterpret_cast<uint4*>(ob + (long)q * oplane * 16) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-                *reinterpret_cast<uint4*>(ob + (long)(16 + q) * oplane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+                gdm_packed_store8(ob, om.group(q), om.group(GDM_PK_LO + q), v);
             }
         }
     }
@@ -635,7 +621,7 @@ extern "C" int gdm_mfma_probe_hip(int blocks, int iters, int chain, float* sink,
     return gdm_launch_status("mfma_probe_kernel");
 }
 
-static bool cin_ok(int Cin) { return Cin == 64 || (Cin >= 128 && Cin % 128 == 0); }
+static bool cin_ok(int Cin) { return gdm_packed_channels_ok(Cin); }
 
 // 64-channel output tiles instead of 128-channel ones: when the 128-channel tiling gives fewer workgroups than the chip has CUs, or
 // the layer has only 64 output channels
@@ -647,7 +633,7 @@ static bool narrow_tiles(unsigned pixel_tiles, int Cout)
 extern "C" size_t gdm_conv3x3_act_bytes(int B, int Cin, int H, int W)
 {
     if (B < 1 || !cin_ok(Cin) || H < 1 || W < 1) return 0;
-    return (size_t)B * (H + 2) * (W + 2) * ((Cin + 127) / 128) * ROWB;
+    return gdm_packed_map{Cin, H, W}.bytes(B);
 }
 
 extern "C" size_t gdm_conv3x3_weight_bytes(int Cout, int Cin)

@@ -10,6 +10,7 @@
 // Index / weight arithmetic is the same as ATen's (scale = (in-1)/(out-1) in fp32,
 // src = scale*dst, i0 = (int)src, lambda = src - i0, i1 = i0 + (i0 < in-1)).
 #include "gdm_common.h"
+#include "gdm_packed_act.h"
 
 namespace {
 
@@ -614,7 +615,7 @@ __global__ __launch_bounds__(256) void upconv3x3_gather_lds_kernel(const float* 
 
 // EIGHT output channels per workgroup (Cout % 8 == 0): a 32 x 8 output tile, thread = one output pixel, the interpolation
 // coefficients of a pixel computed once for its eight channels (the one-channel form above is VALU-bound on exactly those), and the
-// result ALSO written as the packed split-bf16 operand of the next GEMM over the map (conv_pack_act_kernel's layout: the eight channels
+// result ALSO written as the packed split-bf16 operand of the next GEMM over the map (gdm_packed_act.h: the eight channels
 // of a pixel = one 16-byte group in the hi plane and one in the lo plane): the pack launch that followed (36 us in front of the p2r GEMM
 // of the first up stage, on the image branch's critical path) is gone.  Same taps, same blend expression, same order: same bits.
 constexpr int U8_W = 32, U8_H = 8, U8_PH = 8, U8_PW = 20;
@@ -697,14 +698,8 @@ __global__ __launch_bounds__(256) void upconv3x3_gather8_kernel(const float* __r
         out[(((long)b * Cout + c0 + ch) * OH + oy) * OW + ox] = o;
     }
     if (ypk) {
-        const long pplane = (long)(OH + 2) * (OW + 2);
-        const int nchunk = (Cout + 127) / 128, chunk = c0 / 128, q = (c0 % 128) / 8;
-        unsigned char* o = ypk + ((((long)b * nchunk + chunk) * 32 + q) * pplane + (long)(oy + 1) * (OW + 2) + ox + 1) * 16;
-        unsigned hi[4], lo[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) gdm_split2(v[2 * i], v[2 * i + 1], hi[i], lo[i]);
-        *reinterpret_cast<uint4*>(o) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-        *reinterpret_cast<uint4*>(o + 16 * pplane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+        const gdm_packed_map pm{Cout, OH, OW};
+        gdm_packed_store8(ypk + pm.granule(b, c0 / GDM_PK_CHUNK, (c0 % GDM_PK_CHUNK) / 8, oy, ox), 0, pm.lo(), v);
     }
 }
 
@@ -766,7 +761,7 @@ __global__ __launch_bounds__(256) void psp_combine_kernel(const float* __restric
 }
 
 // The same for EIGHT planes per workgroup (C % 8 == 0, W % 4 == 0): the interpolation coordinates of a pixel are computed once for its
-// eight channels, and the result is ALSO written as the packed split-bf16 operand of the next GEMM over the map (conv_pack_act_kernel's
+// eight channels, and the result is ALSO written as the packed split-bf16 operand of the next GEMM over the map (gdm_packed_act.h's
 // layout: the eight channels of a pixel are one 16-byte group in the hi plane and one in the lo plane) -- the pack launch that followed
 // this kernel (33 us on the image branch's critical path) is gone.
 __global__ __launch_bounds__(256) void psp_combine8_kernel(const float* __restrict__ g, PspMaps maps, const float* __restrict__ bias,
@@ -785,8 +780,7 @@ __global__ __launch_bounds__(256) void psp_combine8_kernel(const float* __restri
     float bc[8];
 #pragma unroll
     for (int ch = 0; ch < 8; ++ch) bc[ch] = bias ? bias[c0 + ch] : 0.f;
-    const long pplane = (long)(H + 2) * (W + 2);
-    const int nchunk = (C + 127) / 128, chunk = c0 / 128, q = (c0 % 128) / 8;
+    const gdm_packed_map pk{C, H, W};
     for (int i0 = (blockIdx.x * 256 + threadIdx.x) * 4; i0 < hw; i0 += gridDim.x * 1024) {
         const int oy = i0 / W, ox0 = i0 - oy * W;                      // four pixels of one row (W % 4 == 0)
         float v[8][4];
@@ -820,14 +814,11 @@ __global__ __launch_bounds__(256) void psp_combine8_kernel(const float* __restri
             *reinterpret_cast<float4*>(out + (plane0 + ch) * hw + i0) = make_float4(v[ch][0], v[ch][1], v[ch][2], v[ch][3]);
         }
         if (ypk) {
-            unsigned char* o = ypk + ((((long)b * nchunk + chunk) * 32 + q) * pplane + (long)(oy + 1) * (W + 2) + ox0 + 1) * 16;
+            unsigned char* o = ypk + pk.granule(b, c0 / GDM_PK_CHUNK, (c0 % GDM_PK_CHUNK) / 8, oy, ox0);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                unsigned hi[4], lo[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) gdm_split2(v[2 * i][e], v[2 * i + 1][e], hi[i], lo[i]);
-                *reinterpret_cast<uint4*>(o + e * 16) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-                *reinterpret_cast<uint4*>(o + e * 16 + 16 * pplane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+                const float ve[8] = {v[0][e], v[1][e], v[2][e], v[3][e], v[4][e], v[5][e], v[6][e], v[7][e]};
+                gdm_packed_store8(o, e * GDM_PK_GRANULE, e * GDM_PK_GRANULE + pk.lo(), ve);
             }
         }
     }
@@ -843,8 +834,8 @@ __global__ __launch_bounds__(256) void gather_add_affine_act_kernel(const float*
                                                                     const float* __restrict__ shift, int C, int n, int m, float slope,
                                                                     float* __restrict__ y,
                                                                     // optional: the result ALSO as the packed split-bf16 operand of the next
-                                                                    // convolution / GEMM over the [B, C, m / W, W] map (gdm_conv.hip
-                                                                    // conv_pack_act_kernel's layout): a block's 8 channels are one 16-byte
+                                                                    // convolution / GEMM over the [B, C, m / W, W] map (the layout of
+                                                                    // gdm_packed_act.h): a block's 8 channels are one 16-byte
                                                                     // operand group, so the pack launch that would follow is free here
                                                                     unsigned char* __restrict__ ypk, int W)
 {
@@ -870,15 +861,9 @@ __global__ __launch_bounds__(256) void gather_add_affine_act_kernel(const float*
         v[i] = o;
     }
     if (ypk) {
-        const int H = m / W, yy = j / W, xx = j - yy * W;
-        const long plane = (long)(H + 2) * (W + 2);
-        const int nchunk = (C + 127) / 128, chunk = c0 / 128, q = (c0 % 128) / 8;
-        unsigned char* o = ypk + ((((long)b * nchunk + chunk) * 32 + q) * plane + (long)(yy + 1) * (W + 2) + xx + 1) * 16;
-        unsigned hi[4], lo[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) gdm_split2(v[2 * i], v[2 * i + 1], hi[i], lo[i]);
-        *reinterpret_cast<uint4*>(o) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-        *reinterpret_cast<uint4*>(o + 16 * plane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+        const gdm_packed_map pm{C, m / W, W};
+        const int yy = j / W, xx = j - yy * W;
+        gdm_packed_store8(ypk + pm.granule(b, c0 / GDM_PK_CHUNK, (c0 % GDM_PK_CHUNK) / 8, yy, xx), 0, pm.lo(), v);
     }
 }
 
@@ -1183,10 +1168,10 @@ extern "C" int gdm_upconv3x3_gather2_hip(const float* z, const float* scale, con
                                          int OH, int OW, int act, float slope, float* out, void* outpk, void* stream)
 {
     GDM_CHECK_ARG(z && scale && shift && out && outpk, "gdm_upconv3x3_gather2_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && Cout >= 8 && Cout % 8 == 0 && (Cout == 64 || Cout % 128 == 0) && (long)B * (Cout / 8) <= 65535 && H >= 1 && W >= 1
-                  && OH >= 1 && OW >= 1, "gdm_upconv3x3_gather2_hip: bad shape B=%d Cout=%d %dx%d -> %dx%d (Cout = 64 or a multiple of 128)",
-                  B, Cout, H, W, OH, OW);
-    GDM_CHECK_ARG(act >= 0 && act <= 2 && ((uintptr_t)outpk & 15) == 0, "gdm_upconv3x3_gather2_hip: act=%d / unaligned packed output", act);
+    GDM_CHECK_ARG(B >= 1 && Cout >= 8 && (long)B * (Cout / 8) <= 65535 && H >= 1 && W >= 1 && OH >= 1 && OW >= 1,
+                  "gdm_upconv3x3_gather2_hip: bad shape B=%d Cout=%d %dx%d -> %dx%d", B, Cout, H, W, OH, OW);
+    GDM_CHECK_ARG(act >= 0 && act <= 2 && gdm_packed_out_ok(Cout, outpk),
+                  "gdm_upconv3x3_gather2_hip: act=%d / packed output needs Cout = 64 or a multiple of 128 and a 16-byte aligned buffer (Cout=%d)", act, Cout);
     const float rh = scale_ac(H, OH), rw = scale_ac(W, OW);
     GDM_CHECK_ARG((int)(rh * (U8_H + 1)) + 3 <= U8_PH && (int)(rw * (U8_W + 1)) + 3 <= U8_PW,
                   "gdm_upconv3x3_gather2_hip: scale factors %g x %g too large for the LDS tile (the x2 stages of PSPUpsample fit)", rh, rw);
@@ -1264,7 +1249,7 @@ extern "C" int gdm_psp_combine2_hip(const float* g, const float* y1, int s1, con
     int gx = gdm_cdiv((long)H * W, 1024);
     if (gx > 16) gx = 16;
     if (outpk) {
-        GDM_CHECK_ARG(C % 8 == 0 && W % 4 == 0 && ((uintptr_t)outpk & 15) == 0 && (C == 64 || C % 128 == 0),
+        GDM_CHECK_ARG(W % 4 == 0 && gdm_packed_out_ok(C, outpk),
                       "gdm_psp_combine2_hip: packed output needs C = 64 or a multiple of 128, W %% 4 == 0 and a 16-byte aligned buffer (C=%d W=%d)", C, W);
         hipLaunchKernelGGL(psp_combine8_kernel, dim3(gx, B * C / 8), dim3(256), 0, (hipStream_t)stream, g, maps, bias, C, H, W, out,
                            (unsigned char*)outpk);
@@ -1280,7 +1265,7 @@ extern "C" int gdm_gather_add_affine_act2_hip(const float* x, const float* t, co
     unsigned char* ypk = (unsigned char*)y_packed;
     GDM_CHECK_ARG(x && t && idx && scale && shift && (y || ypk), "gdm_gather_add_affine_act2_hip: NULL pointer");
     GDM_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && n >= 1 && m >= 1 && act >= 0 && act <= 2, "gdm_gather_add_affine_act2_hip: bad shape");
-    GDM_CHECK_ARG(!ypk || (W >= 1 && m % W == 0 && C % 8 == 0 && (C == 64 || C % 128 == 0) && ((uintptr_t)ypk & 15) == 0),
+    GDM_CHECK_ARG(!ypk || (W >= 1 && m % W == 0 && gdm_packed_out_ok(C, ypk)),
                   "gdm_gather_add_affine_act2_hip: packed output needs m %% W == 0, C = 64 or a multiple of 128, a 16-byte aligned buffer");
     dim3 grid(gdm_cdiv(m, 256), gdm_cdiv(C, 8), B);
     hipStream_t s = (hipStream_t)stream;

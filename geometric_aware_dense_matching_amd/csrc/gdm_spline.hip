@@ -16,6 +16,7 @@
 // add root term and bias, optional ReLU.  Edges are in CSR form sorted by target, so the mean needs
 // no atomics and is bitwise reproducible.
 #include "gdm_common.h"
+#include "gdm_packed_act.h"
 #include <math.h>
 
 namespace {
@@ -175,18 +176,12 @@ __global__ __launch_bounds__(128) void spline_direct_kernel(const float* __restr
 }
 
 // The four channels [o, o+4) of vertex i as their half of a 16-byte group of the packed split-bf16 operand the next layer's grouped GEMM
-// reads (conv_pack_act_kernel's layout for a [1, C, 1, M] map: planes of 3 x (M + 2) zero-bordered pixels, hi plane q / lo plane 16 + q of
-// every 128-channel chunk, 8 channels = 16 bytes per pixel): the pack launch between two SplineConv layers is then not needed.
+// reads (gdm_packed_act.h, a [1, C, 1, M] map: vertex i is pixel (0, i)): the pack launch between two SplineConv layers is then not needed.
 __device__ __forceinline__ void spline_store_packed(unsigned char* __restrict__ out_pk, int M, int i, int o, const float4 r)
 {
-    const long plane = 3L * (M + 2);
-    const int chunk = o >> 7, q = (o & 127) >> 3, half = (o & 7) >> 2;
-    unsigned hi0, lo0, hi1, lo1;
-    gdm_split2(r.x, r.y, hi0, lo0);
-    gdm_split2(r.z, r.w, hi1, lo1);
-    unsigned char* p = out_pk + (((long)chunk * 32 + q) * plane + (M + 2) + i + 1) * 16 + half * 8;
-    *reinterpret_cast<uint2*>(p) = make_uint2(hi0, hi1);
-    *reinterpret_cast<uint2*>(p + 16 * plane * 16) = make_uint2(lo0, lo1);
+    const gdm_packed_map pm{GDM_PK_CHUNK, 1, M};                  // (the channel count only sets the chunks per image, and there is one image)
+    const float v[4] = {r.x, r.y, r.z, r.w};
+    gdm_packed_store4(out_pk + pm.granule(0, o >> 7, (o & 127) >> 3, 0, i), 0, pm.lo(), (o & 7) >> 2, v);
 }
 
 // The same with FOUR output channels per thread (C % 4 == 0): the kernel is bound by its weight loads (4 edges x 8 corners x Cin rows

@@ -13,6 +13,7 @@
 // LDS; a lane builds its A fragment with four 8-byte LDS reads + the hi / lo split; the B fragments (weights, pre-packed in fragment
 // order by stem_pack_w_kernel: 48 KB) come straight from global memory / L2 into registers, one k-step ahead.
 #include "gdm_common.h"
+#include "gdm_packed_act.h"
 
 namespace {
 
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
     const int pxl = tid & 15, pyl = (tid >> 4) & 3;
     const int py = py0 + pyl, px = px0 + pxl;
     const bool store = py < PH && px < PW;
-    const long plane = (long)(PH + 2) * (PW + 2);
+    const gdm_packed_map pm{64, PH, PW};
     // which of this lane's 4 MPW convolution pixels lie inside the tile and inside the map (the same for every channel and pass)
     unsigned inmap = 0, intile = 0;
 #pragma unroll
@@ -213,15 +214,9 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
             for (int i = 0; i < 8; ++i) out[(((long)b * 64 + c0 + i) * PH + py) * PW + px] = pooled[i];
         }
         if (outpk) {
-            // packed operand of the next 3x3 convolution (gdm_conv.hip conv_pack_act_kernel's layout, one 64-channel chunk): plane
-            // q < 8 = bf16 hi of channels [8q, 8q + 8), plane 16 + q = their lo; element (py + 1, px + 1) of the zero-bordered grid
+            // packed operand of the next 3x3 convolution (gdm_packed_act.h: one 64-channel chunk per image)
             const int q = c0 / 8;
-            unsigned char* ob = outpk + (((long)b * 32) * plane + (long)(py + 1) * (PW + 2) + px + 1) * 16;
-            unsigned hi[4], lo[4];
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) gdm_split2(pooled[2 * jj], pooled[2 * jj + 1], hi[jj], lo[jj]);
-            *reinterpret_cast<uint4*>(ob + (long)q * plane * 16) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-            *reinterpret_cast<uint4*>(ob + (long)(16 + q) * plane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+            gdm_packed_store8(outpk + pm.pixel(b, 0, py, px), pm.group(q), pm.group(GDM_PK_LO + q), pooled);
         }
     }
 }

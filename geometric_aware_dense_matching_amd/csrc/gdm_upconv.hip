@@ -3,6 +3,7 @@
 // of the last image stage (`upconv_final_points_kernel`) and the 64-channel fusion tail (`conv64_gather_add_act_mfma_kernel`).  All use
 // split-bf16 products (hi*hi + hi*lo + lo*hi, fp32 accumulate: the scheme of the matching / convolution kernels).
 #include "gdm_common.h"
+#include "gdm_packed_act.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -521,15 +522,10 @@ __global__ __launch_bounds__(256, 4) void conv64_gather_add_act_mfma_kernel(cons
 #pragma unroll
             for (int r = 0; r < 4; ++r) p4[r] = __shfl_xor(o[r], 16);
             if (j < m && !(kg & 1)) {
-                const int H = m / W, yy = j / W, xx = j - yy * W;
-                const long plane = (long)(H + 2) * (W + 2);
-                const int q = 2 * wave + (kg >> 1);
-                unsigned char* op = ypk + ((((long)b * 32) + q) * plane + (long)(yy + 1) * (W + 2) + xx + 1) * 16;
-                unsigned hi[4], lo[4];
-                gdm_split2(o[0], o[1], hi[0], lo[0]); gdm_split2(o[2], o[3], hi[1], lo[1]);
-                gdm_split2(p4[0], p4[1], hi[2], lo[2]); gdm_split2(p4[2], p4[3], hi[3], lo[3]);
-                *reinterpret_cast<uint4*>(op) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-                *reinterpret_cast<uint4*>(op + 16 * plane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+                const int yy = j / W, xx = j - yy * W;
+                const gdm_packed_map pm{UF_C, m / W, W};
+                const float v[8] = {o[0], o[1], o[2], o[3], p4[0], p4[1], p4[2], p4[3]};
+                gdm_packed_store8(ypk + pm.granule(b, 0, 2 * wave + (kg >> 1), yy, xx), 0, pm.lo(), v);
             }
         }
         if (j >= m) continue;

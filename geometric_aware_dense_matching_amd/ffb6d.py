@@ -226,10 +226,8 @@ class FFB6DEmb(nn.Module):
                                            hw=(hr, wr) if (want_packed and settings.USE_PACKED_PRODUCERS and not pixel_major) else None)
         if pixel_major:
             return y                                    # [B, H*W, 64] for _final_at_choose
-        out = y.view(bs, -1, hr, wr)
-        if getattr(y, "_gdm_packed", None) is not None:
-            out._gdm_packed = y._gdm_packed             # the next stage's first convolution reads this: no pack launch
-        return out
+        # the next stage's first convolution reads the operand the kernel wrote (of the [B, 64, H, W] map): no pack launch
+        return ops.carry_packed(y.view(bs, -1, hr, wr), ops.packed_of(y, (bs, c, hr, wr)))
 
     def _fuse_fma64(self, fuse_layer, wa, rgb_emb0, t, idx, code, pixel_major):
         """K = 64: GEMM + gather + add + BN + ReLU in ONE pass over the pixels (exact fp32 FMAs); channel-major point term."""
@@ -258,10 +256,7 @@ class FFB6DEmb(nn.Module):
         if packed_only and ops.packed_out_supported(bs, x.shape[1], hr, wr):
             return ops.gather_add_affine_act(x, t, idx.reshape(bs, -1), scale, shift, code[0], code[1], hw=(hr, wr), f32_out=False)
         y, ypk = ops.gather_add_affine_act(x, t, idx.reshape(bs, -1), scale, shift, code[0], code[1], hw=(hr, wr))
-        y = y.view(bs, -1, hr, wr)
-        if ypk is not None:
-            y._gdm_packed = ypk             # the next image stage's first convolution / GEMM reads this: no pack launch
-        return y
+        return ops.carry_packed(y.view(bs, -1, hr, wr), ypk)   # the next image stage's first convolution / GEMM reads this: no pack launch
 
     def _packed_only_consumer(self, stage, shape):
         """True when image stage `stage`, given a GPU map of this shape, reads its packed operand and nothing else: Sequential(PSPUpsample,

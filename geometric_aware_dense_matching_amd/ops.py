@@ -1162,12 +1162,10 @@ def upconv3x3_gather(z, scale, shift, cout, out_size, act=ACT_NONE, slope=0.0, p
     assert c9 == 9 * cout
     OH, OW = int(out_size[0]), int(out_size[1])
     out = torch.empty((B, cout, OH, OW), dtype=torch.float32, device=z.device)
-    if (packed and (cout == 64 or cout % 128 == 0) and OW % 32 == 0 and (B * OH * OW) % 256 == 0 and B * cout // 8 <= 65535
-            and (OH, OW) == (2 * H, 2 * W)):
-        opk = PackedAct(_packed_buffer(B, cout, OH, OW, z.device), (B, cout, OH, OW))
+    if packed and packed_out_supported(B, cout, OH, OW, grid_groups=True) and (OH, OW) == (2 * H, 2 * W):   # (blockIdx.z = group; x2: its LDS tile)
+        opk = _packed_out(B, cout, OH, OW, z.device)
         call("gdm_upconv3x3_gather2_hip", z, scale, shift, B, cout, H, W, OH, OW, act, float(slope), out, opk.buf)
-        out._gdm_packed = opk
-        return out
+        return carry_packed(out, opk)
     call("gdm_upconv3x3_gather_hip", z, scale, shift, B, cout, H, W, OH, OW, act, float(slope), out)
     return out
 
@@ -1525,19 +1523,18 @@ def psp_combine(g, ys, bias, packed=False):
     B, C, H, W = g.shape
     ys = [_dev(y, torch.float32, "y") for y in ys]
     assert len(ys) == 4
-    opk = None
-    if packed and (C == 64 or C % 128 == 0) and W % 32 == 0 and (B * H * W) % 256 == 0 and B * C // 8 <= 65535:
-        opk = PackedAct(_packed_buffer(B, C, H, W, g.device), (B, C, H, W))
+    opk = _packed_out(B, C, H, W, g.device) if packed and packed_out_supported(B, C, H, W, grid_groups=True) else None   # (blockIdx.y = group)
     call("gdm_psp_combine2_hip", g, ys[0], ys[0].shape[2], ys[1], ys[1].shape[2], ys[2], ys[2].shape[2], ys[3], ys[3].shape[2], bias, B, C,
          H, W, g, opk.buf if opk is not None else None)
-    if opk is not None:
-        g._gdm_packed = opk
-    return g
+    return carry_packed(g, opk)
 
 
-def packed_out_supported(B, C, H, W):
-    """The shapes for which gather_add_affine_act writes the packed operand of the [B,C,H,W] map."""
-    return (C == 64 or C % 128 == 0) and W % 32 == 0 and (B * H * W) % 256 == 0
+def packed_out_supported(B, C, H, W, row=32, grid_groups=False):
+    """The shapes for which a producer (gather_add_affine_act with the defaults) writes the packed operand of its [B,C,H,W] map: a
+    channel count of the format, whole 256-pixel workgroup tiles of the reader, image rows in whole runs of `row` pixels (32: the
+    reader may be the 1x1 GEMM, gemm_bf16x3_map; 16: a 3x3 convolution, whose 16-pixel operand fragment lies inside one image row).
+    grid_groups: the producer launches one grid row per (image, 8-channel group), which must fit a grid dimension."""
+    return (C == 64 or C % 128 == 0) and W % row == 0 and (B * H * W) % 256 == 0 and (not grid_groups or B * C // 8 <= 65535)
 
 
 def gather_add_affine_act(x, t, idx, scale, shift, act=ACT_NONE, slope=0.0, hw=None, f32_out=True):
@@ -1557,9 +1554,7 @@ def gather_add_affine_act(x, t, idx, scale, shift, act=ACT_NONE, slope=0.0, hw=N
     idx = _idx32(idx, "idx")
     B, C, m = x.shape
     n = t.shape[2]
-    opk = None
-    if hw is not None and hw[0] * hw[1] == m and packed_out_supported(B, C, hw[0], hw[1]):
-        opk = PackedAct(_packed_buffer(B, C, hw[0], hw[1], x.device), (B, C, hw[0], hw[1]))
+    opk = _packed_out(B, C, hw[0], hw[1], x.device) if hw is not None and hw[0] * hw[1] == m and packed_out_supported(B, C, hw[0], hw[1]) else None
     if not f32_out and opk is None:
         raise ValueError("gather_add_affine_act: f32_out=False needs a map the packed operand is built for, got x %s hw %s" % (tuple(x.shape), hw))
     call("gdm_gather_add_affine_act2_hip", x, t, idx, scale, shift, B, C, n, m, act, float(slope), x if f32_out else None,
@@ -1603,14 +1598,11 @@ def conv64_gather_add_act_mfma(x, wpk, t, idx, scale, shift, act=ACT_NONE, slope
     if C != 64 or t.shape[2 if t_point_major else 1] != 64 or wpk.numel() != 64 * 256:
         raise ValueError("conv64_gather_add_act_mfma: built for 64 -> 64 channels, got x %s t %s" % (tuple(x.shape), tuple(t.shape)))
     y = torch.empty((B, m, C), dtype=torch.float32, device=x.device) if pixel_major else torch.empty_like(x)
-    opk = None
-    if hw is not None and not pixel_major and hw[0] * hw[1] == m and hw[1] % 32 == 0 and (B * m) % 256 == 0:
-        opk = PackedAct(_packed_buffer(B, C, hw[0], hw[1], x.device), (B, C, hw[0], hw[1]))
+    want = hw is not None and not pixel_major and hw[0] * hw[1] == m and packed_out_supported(B, C, hw[0], hw[1])
+    opk = _packed_out(B, C, hw[0], hw[1], x.device) if want else None
     call("gdm_conv64_gather_add_act_mfma2_hip", x, wpk, t, idx, scale, shift, B, n, m, act, float(slope), int(bool(pixel_major)),
          int(bool(t_point_major)), y, opk.buf if opk is not None else None, int(hw[1]) if opk is not None else 0)
-    if opk is not None:
-        y._gdm_packed = opk
-    return y
+    return carry_packed(y, opk)
 
 
 def conv1x1_gather_add_act(x, wt, t, idx, scale, shift, act=ACT_NONE, slope=0.0, pixel_major=False):
@@ -1716,13 +1708,9 @@ def stem(x, wpk, scale, shift, packed=True):
         raise ValueError("stem: 3 input channels, got %d" % C)
     PH, PW = ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1
     out = torch.empty((B, 64, PH, PW), dtype=torch.float32, device=x.device)
-    opk = None
-    if packed and (B * PH * PW) % 256 == 0 and PW % 16 == 0:
-        opk = PackedAct(_packed_buffer(B, 64, PH, PW, x.device), (B, 64, PH, PW))
+    opk = _packed_out(B, 64, PH, PW, x.device) if packed and packed_out_supported(B, 64, PH, PW, row=16) else None   # (read by a 3x3 convolution)
     call("gdm_stem_hip", x, wpk, scale, shift, B, H, W, out, opk.buf if opk is not None else None)
-    if opk is not None:
-        out._gdm_packed = opk
-    return out
+    return carry_packed(out, opk)
 
 
 def affine_relu_maxpool(x, scale, shift):
@@ -1966,6 +1954,26 @@ class PackedAct:
         self.buf, self.shape = buf, tuple(shape)
 
 
+def carry_packed(t, opk):
+    """Hangs the packed operand opk (a PackedAct, or None) on the fp32 map t of the same producer, for the next reader (packed_of)."""
+    if opk is not None:
+        t._gdm_packed = opk
+    return t
+
+
+def packed_of(x, shape=None):
+    """The PackedAct that x is, or carries (carry_packed) for a map of its own shape (or `shape`: x is a view of that map); else None."""
+    if isinstance(x, PackedAct):
+        return x
+    xp = getattr(x, "_gdm_packed", None)
+    return xp if isinstance(xp, PackedAct) and xp.shape == tuple(x.shape if shape is None else shape) else None
+
+
+def _packed_out(B, C, H, W, device, avoid=None):
+    """A PackedAct of a [B,C,H,W] map for a producer to write: a zero-bordered buffer of the pool (_packed_buffer) and its shape."""
+    return PackedAct(_packed_buffer(B, C, H, W, device, avoid=avoid), (B, C, H, W))
+
+
 def _packed_buffer(B, C, H, W, device, avoid=None):
     """Zero-bordered operand buffer for [B,C,H,W] from the current BufferPool (two per shape and stream: a layer reads one and
     writes the other).  Only interior pixels are ever written, so the border stays zero."""
@@ -1987,9 +1995,9 @@ def conv3x3_pack_act(x):
     B, C, H, W = x.shape
     _require_fit("conv3x3_pack_act", "x %s", (tuple(x.shape),), _map_bytes(B, C, H, W))       # (in front of _dev, which may copy x)
     x = _dev(x, torch.float32, "x")
-    buf = _packed_buffer(B, C, H, W, x.device)
-    call("gdm_conv3x3_pack_act_hip", x, B, C, H, W, buf)
-    return PackedAct(buf, (B, C, H, W))
+    xp = _packed_out(B, C, H, W, x.device)
+    call("gdm_conv3x3_pack_act_hip", x, B, C, H, W, xp.buf)
+    return xp
 
 
 def conv3x3_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, res=None, out_f32=True, out_packed=False, stride=1):
@@ -2009,7 +2017,7 @@ def conv3x3_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, res=None,
     if out_packed:
         if (B * H * W) % 256 != 0 or cout % 8 != 0:
             raise ValueError("conv3x3_bf16x3: packed output needs B*H*W %% 256 == 0 and Cout %% 8 == 0")
-        opk = PackedAct(_packed_buffer(B, cout, H, W, dev, avoid=xp.buf), (B, cout, H, W))
+        opk = _packed_out(B, cout, H, W, dev, avoid=xp.buf)
     if res is not None:
         res = _dev(res, torch.float32, "res")
         if res.data_ptr() % 16:
@@ -2025,25 +2033,19 @@ def gemm_bf16x3_map(x, wpk, cout):
     producer wrote (`_gdm_packed`, the trunk's residual blocks), or is that PackedAct itself, the GEMM reads that and no pack launch
     is needed."""
     B, Cin, H, W = x.shape
-    if isinstance(x, PackedAct):                     # a map that exists as the packed operand only
-        if W % 32 != 0:
-            raise ValueError("gemm_bf16x3_map: a packed-only map needs W %% 32 == 0, got %s" % (x.shape,))
-        return conv1x1_packed2d(x, wpk, cout)
-    xp = getattr(x, "_gdm_packed", None)
-    if isinstance(xp, PackedAct) and xp.shape == (B, Cin, H, W) and W % 32 == 0:
+    xp = _packed_operand(x)
+    if xp is not None:
         return conv1x1_packed2d(xp, wpk, cout)
+    if isinstance(x, PackedAct):                     # a map that exists as the packed operand only
+        raise ValueError("gemm_bf16x3_map: a packed-only map needs W %% 32 == 0, got %s" % (x.shape,))
     return gemm_bf16x3(x.reshape(B, Cin, H * W), wpk, cout).view(B, cout, H, W)
 
 
 def _packed_operand(x):
     """The packed operand gemm_bf16x3_map would read for the map x (a PackedAct, or a tensor that carries its producer's `_gdm_packed`),
     or None where it would pack x itself."""
-    if isinstance(x, PackedAct):
-        return x if x.shape[3] % 32 == 0 else None
-    xp = getattr(x, "_gdm_packed", None)
-    if isinstance(xp, PackedAct) and len(x.shape) == 4 and xp.shape == tuple(x.shape) and x.shape[3] % 32 == 0:
-        return xp
-    return None
+    xp = packed_of(x)
+    return xp if xp is not None and xp.shape[3] % 32 == 0 else None
 
 
 def conv1x1_gather_add_supported(x, cout, act, f32_out=True):
@@ -2093,9 +2095,7 @@ def conv1x1_packed_gather_add_act(x, wpk, cout, t, idx, scale, shift, act=ACT_NO
         idx = idx.clone()                            # the epilogue loads four indices at once
     dev = xp.buf.device
     y = torch.empty((B, cout, H * W), dtype=torch.float32, device=dev) if f32_out else None
-    opk = None
-    if packed_out_supported(B, cout, H, W):
-        opk = PackedAct(_packed_buffer(B, cout, H, W, dev, avoid=xp.buf), (B, cout, H, W))
+    opk = _packed_out(B, cout, H, W, dev, avoid=xp.buf) if packed_out_supported(B, cout, H, W) else None
     call("gdm_conv1x1_gather_add_hip", xp.buf, wpk, idx, t, t.shape[2], scale, shift, B, Cin, cout, H, W, act, y,
          opk.buf if opk is not None else None)
     return (y, opk) if f32_out else opk
@@ -2182,6 +2182,11 @@ def gemm_bf16x3(x, wpk, cout, scale=None, shift=None, act=ACT_NONE, pixel_major=
 def spline_packed_buffer(C, M, device, avoid=None):
     """The zero-bordered operand buffer a SplineConv layer's kernels write for the NEXT layer's grouped GEMM (a [1, C, 1, M] map)."""
     return _packed_buffer(1, C, 1, M, device, avoid=avoid)
+
+
+def spline_packed_supported(C):
+    """The layer widths whose SplineConv kernels write that buffer: whole 128-channel chunks, a vertex's channels within one workgroup."""
+    return C % 128 == 0 and C <= 512
 
 
 def gemm_grouped(x_cm, wpk, rowidx, tile_co0, cout_total, xpk=None):

@@ -208,7 +208,7 @@ class SplineConv(nn.Module):
         pack launch between the layers).  Returns (out_t, packed buffer or None)."""
         M = x.shape[0]
         out_t = torch.empty((1, self.cout, M), dtype=torch.float32, device=x.device)
-        pk = ops.spline_packed_buffer(self.cout, M, x.device) if want_packed and self.cout % 128 == 0 and self.cout <= 512 else None
+        pk = ops.spline_packed_buffer(self.cout, M, x.device) if want_packed and ops.spline_packed_supported(self.cout) else None
         xc = x.contiguous()
         call("gdm_spline_direct3_hip", xc, self.weight, rowptr, src, attr, self._root_t(), self.bias, M, self.cin, self.cout, KERNEL_SIZE,
              int(relu), None, out_t, pk)
@@ -223,7 +223,7 @@ class SplineConv(nn.Module):
         Y = ops.gemm_grouped(xt, wpk, pairs["rowidx"], pairs["tile_co0"], nk * self.cout, xpk=xpk)
         root = ops.pointwise([xt], self._root_t(), point_major=True)                       # [1, M, cout] = x @ W_root^T
         out_t = torch.empty((1, self.cout, M), dtype=torch.float32, device=xt.device)
-        pk = ops.spline_packed_buffer(self.cout, M, xt.device, avoid=xpk) if want_packed and self.cout % 128 == 0 and self.cout <= 512 else None
+        pk = ops.spline_packed_buffer(self.cout, M, xt.device, avoid=xpk) if want_packed and ops.spline_packed_supported(self.cout) else None
         call("gdm_spline_pairs_aggregate3_hip", Y, rowptr, pairs["pos"], pairs["basis"], root, self.bias, M, self.cout, int(relu), None,
              out_t, pk)
         return out_t, pk

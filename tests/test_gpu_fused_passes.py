@@ -113,6 +113,30 @@ def test_packed_only_gather_add_affine_act_writes_the_same_operand(ops, C, H, W,
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("act", [0, 1, 2])
+def test_gather_add_affine_act_operand_of_two_images_of_two_chunks(ops, act):
+    """B = 2 images of C = 256 channels (two 128-channel chunks): the smallest map on which image b's chunks start at b * nchunk, not
+    at b.  The operand of both forms is byte-identical to what the pack kernel makes of the fp32 result."""
+    B, C, H, W, n = 2, 256, 8, 32, 50
+    g = torch.Generator().manual_seed(40 + act)
+    x = torch.randn(B, C, H * W, generator=g).cuda()
+    t = torch.randn(B, C, n, generator=g).cuda()
+    idx = torch.randint(-2, n + 2, (B, H * W), generator=g, dtype=torch.int32).cuda()
+    sc = (torch.rand(C, generator=g) + 0.5).cuda()
+    sh = torch.randn(C, generator=g).cuda()
+    assert ops.packed_out_supported(B, C, H, W)
+    y, pk = ops.gather_add_affine_act(x.clone(), t, idx, sc, sh, act, 0.2, hw=(H, W))
+    assert pk is not None and pk.shape == (B, C, H, W)
+    mine = pk.buf.clone()                               # the pool may hand the same buffer to the launches below
+    pk.buf.zero_()
+    only = ops.gather_add_affine_act(x, t, idx, sc, sh, act, 0.2, hw=(H, W), f32_out=False)
+    assert torch.equal(only.buf, mine)
+    mine2 = only.buf.clone()
+    only.buf.zero_()
+    assert torch.equal(ops.conv3x3_pack_act(y.view(B, C, H, W).clone()).buf, mine2)
+
+
+@pytest.mark.gpu
 def test_packed_only_needs_a_map_the_operand_is_built_for(ops):
     x = torch.zeros(1, 24, 40, device="cuda")
     t = torch.zeros(1, 24, 3, device="cuda")

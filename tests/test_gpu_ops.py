@@ -738,7 +738,8 @@ def test_conv3x3_bf16x3_small_channel_counts(ops, B, Cin, Cout, H, W):
     assert (got.double() - ref).abs().max().item() < 2e-5 * max(1.0, ref.abs().max().item())
 
 
-@pytest.mark.parametrize("B,C1,C2,C3,H,W", [(2, 128, 256, 256, 32, 32), (1, 64, 64, 64, 64, 64), (1, 128, 64, 72, 8, 32), (2, 256, 128, 200, 4, 32)])
+@pytest.mark.parametrize("B,C1,C2,C3,H,W", [(2, 128, 256, 256, 32, 32), (1, 64, 64, 64, 64, 64), (1, 128, 64, 72, 8, 32), (2, 256, 128, 200, 4, 32),
+                                            (2, 128, 256, 128, 8, 32)])
 def test_conv3x3_packed_output_feeds_the_next_convolution(ops, B, C1, C2, C3, H, W):
     """The epilogue's packed output (bf16 hi / lo planes written straight from the accumulators) == packing the fp32 result with
     the pack kernel, bit for bit, so conv -> conv through it equals conv -> pack -> conv exactly; with and without the fp32 map."""
@@ -762,6 +763,29 @@ def test_conv3x3_packed_output_feeds_the_next_convolution(ops, B, C1, C2, C3, H,
     for _ in range(3):
         _, pk = ops.conv3x3_bf16x3(x, p1, C2, sc, sh, ops.ACT_RELU, res, out_f32=False, out_packed=True)
         assert torch.equal(ops.conv3x3_bf16x3(pk, p2, C3), want)
+    mine = pk.buf.clone()                                         # the pool may hand the same buffer to the pack launch below
+    assert torch.equal(ops.conv3x3_pack_act(mid).buf, mine)
+
+
+@pytest.mark.parametrize("B,C,H,W", [(2, 136, 3, 16), (1, 64, 2, 32)])
+def test_pack_kernel_against_the_layout_restated_in_numpy(ops, B, C, H, W):
+    """conv3x3_pack_act, the kernel every producer's packed bytes are compared with, against tests/packed_layout.py: the documented
+    address of every granule and gdm_split2's round-to-nearest-even hi / lo split, byte for byte (border and unused planes zero).
+    The library packs maps of 64 or a multiple of 128 channels; the 136-channel map -- a partial second chunk -- goes in with its
+    missing channels as zeros, which by the layout's definition are the same bytes: a plane nobody writes is zero, and so are the hi
+    and lo parts of 0.0."""
+    import packed_layout as P
+    rs = np.random.RandomState(B * 1000 + C)
+    x = rs.randn(B, C, H, W).astype(np.float32)
+    x[0, 0, 0, :4] = [0.0, -0.0, 1.0 + 2.0 ** -8, 3.0e38]         # zeros, a rounding tie, the top of the range
+    want = P.pack(x)
+    Cp = C if C == 64 else (C + 127) // 128 * 128
+    xp = np.zeros((B, Cp, H, W), np.float32)
+    xp[:, :C] = x
+    assert want.size == P.packed_bytes(B, Cp, H, W)
+    got = ops.conv3x3_pack_act(torch.from_numpy(xp).cuda())
+    assert got.shape == (B, Cp, H, W) and got.buf.numel() == want.size
+    assert np.array_equal(got.buf.cpu().numpy(), want)
 
 
 def test_final_stage_and_psp_pools(ops):
