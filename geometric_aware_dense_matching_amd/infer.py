@@ -17,11 +17,38 @@ def _plane_normals(model, pose_opts):
     return model.model_emb.unit_normals() if (pose_opts or {}).get("icp_metric") == "plane" else None
 
 
+def _pose_stage(model, res, cld_rgb_nrm, pose_fit, icp_iters, pose_opts, verify):
+    """pose.estimate_poses, or with a `verify` dict pose.estimate_poses_verified, whose winner comes back as RT / valid beside
+    verify_score f64[B], verify_which i32[B], verify_counts i32[B,C,6] and verify_cand_RT f32[B,C,3,4] (every candidate, in order)."""
+    if verify is None:
+        return pose.estimate_poses(res, cld_rgb_nrm, model.model_emb.xyz, pose_fit, icp_iters, pose_opts, _plane_normals(model, pose_opts))
+    v = dict(verify)
+    kw = {k: v.pop(k) for k in ("candidates", "icp_iters") if k in v}
+    sel = pose.estimate_poses_verified(res, cld_rgb_nrm, model.model_emb.xyz, v, pose_opts=pose_opts,
+                                       model_nrm=_plane_normals(model, pose_opts), **kw)
+    return dict(RT=sel["RT"], valid=sel["valid"], verify_score=sel["score"], verify_which=sel["which"], verify_counts=sel["counts"],
+                verify_cand_RT=sel["cand_RT"])
+
+
+def _verify_rows(verify, cid, idx, bs):
+    """The verify dict of class cid ({cls_id: dict} or one dict for all), its per-instance depth / K / window cut down to rows idx."""
+    if verify is None:
+        return None
+    v = dict(verify if "verts" in verify else verify[cid])
+    for k, dims in (("depth", 3), ("K", 3), ("window", 2)):
+        if torch.is_tensor(v.get(k)) and v[k].dim() == dims and v[k].shape[0] == bs:
+            v[k] = v[k].index_select(0, idx)
+    return v
+
+
 def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf16x3", pose_fit="kabsch", icp_iters=0, pose_opts=None,
-                     match_gamma=None):
+                     match_gamma=None, verify=None):
     """model_dict: {cls_id: GeoMatch (eval, on the GPU)}; inputs: dict of batched device tensors (loader keys, plus
     `dpt_xyz` when the neighbour pyramid is not already in it); cls_ids: int tensor/list [bs].  pose_fit / icp_iters / pose_opts:
     pose.estimate_poses (the defaults are the plain Kabsch fit).  match_gamma: soft matching at that temperature (pipeline_step).
+    verify (with_pose only): the dict pose.estimate_poses_verified takes (verts, faces, depth, K[, window, delta, ...], optionally
+    candidates and icp_iters), one for all classes or {cls_id: dict}; depth / K / window with a leading batch dimension are cut down to
+    each class's rows.  The pose is then the verified selection and verify_score, verify_which, verify_counts join the outputs.
     Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, lse, conf, soft_xyz, score][, RT, valid[, icp_iters, icp_resid[, icp_status]]])."""
     cls = torch.as_tensor(cls_ids).cpu().tolist()
     bs = len(cls)
@@ -43,8 +70,7 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
             if soft is not None:
                 part.update(lse=res["lse"], conf=res["conf"], soft_xyz=res["soft_xyz"], score=ops.match_score(res["conf"], res["mask"]))
             if with_pose:
-                part.update(pose.estimate_poses(res, sub["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts,
-                                                _plane_normals(model, pose_opts)))
+                part.update(_pose_stage(model, res, sub["cld_rgb_nrm"], pose_fit, icp_iters, pose_opts, _verify_rows(verify, cid, idx, bs)))
             for k, v in part.items():
                 out.setdefault(k, []).append(v)
             order += sel
@@ -55,7 +81,7 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
 
 
 def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyramid=False, pose_fit="kabsch", icp_iters=0, pose_opts=None,
-                  match_gamma=None):
+                  match_gamma=None, verify=None):
     """ONE pass of the hot path over a batch of crops resident on the device: neighbour pyramid (unless `inputs` already carries the
     loader's index arrays) -> GeoMatch.forward (eval) -> seg mask + descriptor packs + N x M arg-max (evaluator.py:78-93) [-> pose].
     Everything is enqueued on the current stream (and, with settings.USE_SIDE_STREAMS, on side streams forked from and joined back to
@@ -64,7 +90,10 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
     pose.estimate_poses(pose_fit, icp_iters, pose_opts): RANSAC and ICP run on the device too, with no host branching.
     match_gamma = None: the arg-max kernel, as ever.  With a temperature the soft kernel takes its place (same best_idx / best_sim)
     and the outputs gain lse, conf, soft_xyz (include/gdm.h gdm_match_soft_packed_hip) and score f32[B] = the mean of conf over the
-    masked points (0 where none); pose_opts' weights / targets can then use them."""
+    masked points (0 where none); pose_opts' weights / targets can then use them.
+    verify = None: the pose stage as ever.  With with_pose and a verify dict (pose.estimate_poses_verified: verts, faces, depth, K[,
+    window, delta, ...], optionally candidates and icp_iters) RT / valid are the candidate the observed depth agrees with best and
+    the outputs gain verify_score, verify_which and verify_counts; still no host synchronisation."""
     prec = _PREC[precision]
     d = dict(inputs)
     pyr = None
@@ -86,8 +115,7 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
         out = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=mask, count=count, best_idx=bi, best_sim=bs, lse=lse,
                    conf=conf, soft_xyz=sxyz, score=ops.match_score(conf, mask))
     if with_pose:
-        out.update(pose.estimate_poses(out, d["cld_rgb_nrm"], model.model_emb.xyz, pose_fit, icp_iters, pose_opts,
-                                       _plane_normals(model, pose_opts)))
+        out.update(_pose_stage(model, out, d["cld_rgb_nrm"], pose_fit, icp_iters, pose_opts, verify))
     if keep_pyramid and pyr is not None:
         out.update((k, v) for k, v in pyr.items() if torch.is_tensor(v))
     return out

@@ -10,6 +10,8 @@ Opt-in robust variants (csrc/gdm_pose_robust.hip), also on the device and captur
   utils/pvn3d_eval_utils_kpls.py:79-124 best_fit_transform_with_RANSAC   solve_poses(method="ransac") / ransac_poses
   utils/pvn3d_eval_utils_kpls.py:126-212 icp (point to point)              refine_icp
 and, with no counterpart in the reference, point-to-plane ICP with normal gating and Huber weights: refine_icp_plane.
+Verification of pose candidates against the observed depth frame (csrc/gdm_verify.hip), also without one:
+  verify_poses / verify_poses_numpy, boxes_to_windows, select_verified, estimate_poses_verified.
 """
 import numpy as np
 import torch
@@ -419,7 +421,13 @@ def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, 
         RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, method=pose_fit, ransac_iters=o.get("ransac_iters", 20),
                                 inlier_dist=o.get("ransac_inlier_dist", 0.015), fix_percent=o.get("ransac_fix_percent", 0.7),
                                 seed=o.get("seed", 0), weights=o.get("weights", "none"), targets=o.get("targets", "vertex"))
-    out = dict(RT=RT, valid=valid)
+    return _icp_stage(dict(RT=RT, valid=valid), res, cld_rgb_nrm, model_xyz, icp_iters, o, model_nrm)
+
+
+def _icp_stage(out, res, cld_rgb_nrm, model_xyz, icp_iters, o, model_nrm):
+    """The ICP of estimate_poses on the fit out = dict(RT, valid) under the (checked) options o; `out` comes back, refined."""
+    RT, valid = out["RT"], out["valid"]
+    min_points, metric = o.get("min_points", 5), o.get("icp_metric", "point")
     if icp_iters > 0 and metric == "plane":
         out["RT"], out["icp_iters"], out["icp_resid"], out["icp_status"] = refine_icp_plane(
             RT, valid, cld_rgb_nrm, res["mask"], model_xyz, model_nrm, icp_iters, o.get("icp_tolerance", 1e-4), o.get("icp_reject_dist"),
@@ -445,3 +453,215 @@ def adi_metric(RT_est, RT_gt, model_xyz):
     pe, pg = transform(model_xyz, RT_est).contiguous(), transform(model_xyz, RT_gt).contiguous()
     _, d2 = ops.knn_batch(pe, pg, 1, return_d2=True)
     return d2[:, :, 0].clamp(min=0).sqrt().mean(dim=1)
+
+
+# ---- verification against the observed depth (csrc/gdm_verify.hip; include/gdm.h THE VERIFICATION RULE) ---------------
+VERIFY_TILE = 64               # kTile of csrc/gdm_verify.hip: the side of the LDS tile a window is cut into
+VERIFY_Q = 256                 # quantisation steps of |z_o - z_r| / delta over an agreeing pixel
+VERIFY_Q_DEN = 512.0           # score = (n_agree - q_agree / 512) / ...: a pixel at the tolerance edge counts 0.5
+VERIFY_COUNTS = ("n_model", "n_agree", "n_front", "n_behind", "n_nodepth", "q_agree")
+VERIFY_CANDIDATES = ("kabsch", "ransac", "kabsch+icp", "ransac+icp")
+
+
+def verify_poses(verts, faces, RT, depth, K, window=None, delta=0.01, near=0.0, front_weight=0.25, min_px=16, cand_valid=None):
+    """C candidate poses of one mesh for each of n instances against the observed depth, in one fused launch (gdm_pose_verify_hip):
+    every candidate is rasterised by the pixel rule of include/gdm.h into LDS tiles of the instance's window and compared there with
+    the depth frame; no [n C, H, W] image exists.  verts f32|f64[V,3] (passed on in that dtype, as evaluation.render_depth does) and
+    faces i32[F,3] (device tensors or arrays); RT [n,C,3,4], a device tensor of any float dtype; depth f32[H,W] or [n,H,W]; K [3,3]
+    or [n,3,3]; window i32[n,4] = (x0, y0, x1, y1) inclusive in frame pixels (boxes_to_windows), None = the whole frame; cand_valid
+    bool[n,C] or None.  delta: the agreement tolerance in the unit of depth.  front_weight and min_px are the defaults of a
+    definition, not tuned values.  -> dict(counts i32[n,C,6] = VERIFY_COUNTS, score f64[n,C], best i32[n]: the eligible candidate
+    with the largest score, the lowest index on a tie, -1 when there is none).  No host synchronisation."""
+    if not torch.is_tensor(RT) or RT.dim() != 4 or tuple(RT.shape[2:]) != (3, 4) or RT.shape[0] < 1 or RT.shape[1] < 1:
+        raise ValueError("verify_poses: RT must be a tensor [n,C,3,4], got %s" % (tuple(RT.shape) if torch.is_tensor(RT) else type(RT),))
+    dev = RT.device
+    n, C = RT.shape[:2]
+    RT = ops._dev(RT.to(torch.float64), torch.float64, "RT")
+    verts = torch.as_tensor(verts).to(dev)
+    if verts.dtype not in (torch.float32, torch.float64):
+        verts = verts.double()
+    verts = ops._dev(verts, verts.dtype, "verts")
+    faces = ops._dev(torch.as_tensor(faces).to(device=dev, dtype=torch.int32), torch.int32, "faces")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError("verify_poses: verts must be [V,3], got %s" % (tuple(verts.shape),))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError("verify_poses: faces must be [F,3], got %s" % (tuple(faces.shape),))
+    depth = ops._dev(torch.as_tensor(depth).to(device=dev, dtype=torch.float32), torch.float32, "depth")
+    if depth.dim() == 2:
+        opi = 0
+    elif depth.dim() == 3 and depth.shape[0] == n:
+        opi = 1
+    else:
+        raise ValueError("verify_poses: depth must be [H,W] or [n=%d,H,W], got %s" % (n, tuple(depth.shape)))
+    H, W = depth.shape[-2:]
+    K, kpi = ops._k64(torch.as_tensor(K).to(device=dev, dtype=torch.float64), n, "K")
+    if window is not None:
+        window = ops._dev(torch.as_tensor(window).to(device=dev, dtype=torch.int32), torch.int32, "window")
+        if tuple(window.shape) != (n, 4):
+            raise ValueError("verify_poses: window must be [n=%d,4], got %s" % (n, tuple(window.shape)))
+    if cand_valid is not None:
+        cand_valid = ops._dev(torch.as_tensor(cand_valid).to(device=dev, dtype=torch.uint8), torch.uint8, "cand_valid")
+        if tuple(cand_valid.shape) != (n, C):
+            raise ValueError("verify_poses: cand_valid must be [n=%d,C=%d], got %s" % (n, C, tuple(cand_valid.shape)))
+    counts = torch.empty((n, C, 6), dtype=torch.int32, device=dev)
+    score = torch.empty((n, C), dtype=torch.float64, device=dev)
+    best = torch.empty((n,), dtype=torch.int32, device=dev)
+    call("gdm_pose_verify_hip", verts, int(verts.dtype == torch.float64), faces, RT, K, kpi, depth, opi, window, cand_valid, n, C,
+         verts.shape[0], faces.shape[0], H, W, float(near), float(delta), float(front_weight), int(min_px), counts, score, best)
+    return dict(counts=counts, score=score, best=best)
+
+
+def verify_select_numpy(counts, front_weight=0.25, min_px=16, cand_valid=None):
+    """THE SELECTION of include/gdm.h on counts i[n,C,6] in fp64 -> score f64[n,C], best i32[n]."""
+    k = np.asarray(counts).astype(np.float64)
+    n, C = k.shape[:2]
+    den = (k[..., 1] + k[..., 3]) + np.float64(front_weight) * k[..., 2]
+    score = (k[..., 1] - k[..., 5] / VERIFY_Q_DEN) / np.maximum(1.0, den)
+    ok = np.asarray(counts)[..., 0] >= int(min_px)
+    if cand_valid is not None:
+        ok &= np.asarray(cand_valid).reshape(n, C) != 0
+    best = np.full(n, -1, dtype=np.int32)
+    for i in range(n):
+        for c in range(C):
+            if ok[i, c] and (best[i] < 0 or score[i, c] > score[i, best[i]]):
+                best[i] = c
+    return score, best
+
+
+def verify_poses_numpy(verts, faces, RT, depth, K, window=None, delta=0.01, near=0.0, front_weight=0.25, min_px=16, cand_valid=None):
+    """verify_poses on the host, the definition the kernel is tested against: evaluation.render_depth_numpy draws every candidate,
+    np.float32 arithmetic restates THE VERIFICATION RULE of include/gdm.h and fp64 the selection.  Same arguments (arrays or
+    tensors), same dict, as numpy arrays."""
+    from . import evaluation
+
+    def host(a):
+        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+    RT = host(RT).astype(np.float64)
+    n, C = RT.shape[:2]
+    depth = host(depth).astype(np.float32)
+    H, W = depth.shape[-2:]
+    depth = np.broadcast_to(depth, (n, H, W))
+    K = np.broadcast_to(host(K).astype(np.float64), (n, 3, 3))
+    verts = host(verts)
+    rendered = evaluation.render_depth_numpy(verts, faces, RT.reshape(n * C, 3, 4), np.repeat(K, C, axis=0), H, W, near)
+    rendered = rendered.reshape(n, C, H, W)
+    D, Q = np.float32(delta), np.float32(256.0 / float(delta))
+    counts = np.zeros((n, C, 6), dtype=np.int32)
+    for i in range(n):
+        x0, y0, x1, y1 = (0, 0, W - 1, H - 1) if window is None else (int(v) for v in host(window)[i])
+        x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, W - 1), min(y1, H - 1)
+        if x0 > x1 or y0 > y1:
+            continue
+        z_o = depth[i, y0:y1 + 1, x0:x1 + 1]
+        for c in range(C):
+            z_r = rendered[i, c, y0:y1 + 1, x0:x1 + 1]
+            model = z_r > 0                                                 # render_depth_numpy leaves 0 where nothing is drawn
+            with np.errstate(invalid="ignore"):
+                seen = z_o > 0
+                d = (z_o - z_r).astype(np.float32)
+                a = np.abs(d)
+                agree = model & seen & (a <= D)
+                front = model & seen & ~(a <= D) & (d < -D)
+                behind = model & seen & ~(a <= D) & ~(d < -D)
+                q = np.floor((a * Q).astype(np.float32))[agree].astype(np.int64).sum()
+            nodepth = model & ~seen
+            counts[i, c] = [model.sum(), agree.sum(), front.sum(), behind.sum(), nodepth.sum(), q]
+    score, best = verify_select_numpy(counts, front_weight, min_px, None if cand_valid is None else host(cand_valid))
+    return dict(counts=counts, score=score, best=best)
+
+
+def boxes_to_windows(bbox_xyxy, H, W, pad=1.25):
+    """Detection boxes f[n,4] = (x0, y0, x1, y1) -> the windows verify_poses takes, i32[n,4] on the boxes' device: the box scaled
+    about its centre by `pad`, floor / ceil to whole pixels, cut to the frame.  A box that misses the frame gives an empty window
+    (x0 > x1 or y0 > y1: all-zero counts, never eligible)."""
+    b = torch.as_tensor(bbox_xyxy).to(torch.float64)
+    if b.dim() != 2 or b.shape[1] != 4:
+        raise ValueError("boxes_to_windows: boxes must be [n,4], got %s" % (tuple(b.shape),))
+    cx, cy = (b[:, 0] + b[:, 2]) * 0.5, (b[:, 1] + b[:, 3]) * 0.5
+    hx, hy = (b[:, 2] - b[:, 0]) * 0.5 * float(pad), (b[:, 3] - b[:, 1]) * 0.5 * float(pad)
+    lo = torch.stack([torch.floor(cx - hx).nan_to_num(nan=float(W)).clamp(0, W), torch.floor(cy - hy).nan_to_num(nan=float(H)).clamp(0, H)], 1)
+    hi = torch.stack([torch.ceil(cx + hx).nan_to_num(nan=-1.0).clamp(-1, W - 1), torch.ceil(cy + hy).nan_to_num(nan=-1.0).clamp(-1, H - 1)], 1)
+    return torch.cat([lo, hi], dim=1).to(torch.int32)
+
+
+_VERIFY_KEYS = {"verts", "faces", "depth", "K", "window", "delta", "near", "front_weight", "min_px"}
+
+
+def select_verified(candidates, verify):
+    """candidates: an ordered dict name -> (RT f32[n,3,4], valid bool[n]); verify: dict(verts, faces, depth, K[, window, delta, near,
+    front_weight, min_px]) -- verify_poses' arguments.  The candidates are stacked in the dict's order, verified with their valid
+    flags as cand_valid, and the winner is gathered on the device (no host synchronisation).  -> dict(RT f32[n,3,4], valid bool[n] =
+    best >= 0 -- an invalid item keeps candidate 0's RT and score --, which i32[n] = best, score f64[n], scores f64[n,C], counts
+    i32[n,C,6], names, cand_RT f32[n,C,3,4], cand_valid bool[n,C])."""
+    if not candidates:
+        raise ValueError("select_verified: no candidates")
+    unknown = set(verify) - _VERIFY_KEYS
+    missing = {"verts", "faces", "depth", "K"} - set(verify)
+    if unknown or missing:
+        raise ValueError("select_verified: verify has unknown keys %s / lacks %s" % (sorted(unknown), sorted(missing)))
+    names = tuple(candidates)
+    cand_RT = torch.stack([candidates[k][0] for k in names], dim=1).contiguous()
+    cand_valid = torch.stack([candidates[k][1].bool() for k in names], dim=1)
+    v = verify_poses(verify["verts"], verify["faces"], cand_RT, verify["depth"], verify["K"], cand_valid=cand_valid,
+                     **{k: verify[k] for k in ("window", "delta", "near", "front_weight", "min_px") if k in verify})
+    pick = v["best"].clamp_min(0).long()
+    RT = torch.gather(cand_RT, 1, pick[:, None, None, None].expand(-1, 1, 3, 4))[:, 0]
+    score = torch.gather(v["score"], 1, pick[:, None])[:, 0]
+    return dict(RT=RT, valid=v["best"] >= 0, which=v["best"], score=score, scores=v["score"], counts=v["counts"], names=names,
+                cand_RT=cand_RT, cand_valid=cand_valid)
+
+
+def estimate_poses_verified(res, cld_rgb_nrm, model_xyz, verify, candidates=VERIFY_CANDIDATES, icp_iters=10, pose_opts=None,
+                            model_nrm=None):
+    """Several pose estimates of every crop, judged against the depth frame the crop came from: each name of `candidates` -- "kabsch"
+    or "ransac", with "+icp" for `icp_iters` ICP iterations on it (the base fit is made once and shared) -- goes through
+    estimate_poses' stages with pose_opts, then select_verified(verify) keeps, per crop, the one the observed depth agrees with best.
+    -> select_verified's dict."""
+    names = tuple(candidates)
+    bad = [k for k in names if k.split("+")[0] not in ("kabsch", "ransac") or k.split("+")[1:] not in ([], ["icp"])]
+    if bad or not names or len(set(names)) != len(names):
+        raise ValueError("estimate_poses_verified: candidates must be distinct names out of kabsch, ransac, kabsch+icp, ransac+icp; "
+                         "got %r" % (names,))
+    o = dict(pose_opts or {})
+    base, fits = {}, {}
+    for k in names:
+        fit = k.split("+")[0]
+        if fit not in base:
+            base[fit] = estimate_poses(res, cld_rgb_nrm, model_xyz, fit, 0, o, model_nrm)
+        out = base[fit] if k == fit else _icp_stage(dict(base[fit]), res, cld_rgb_nrm, model_xyz, int(icp_iters), o, model_nrm)
+        fits[k] = (out["RT"], out["valid"])
+    return select_verified(fits, verify)
+
+
+def verify_counts_composed(verts, faces, RT, depth, K, window=None, delta=0.01, near=0.0):
+    """The counts of verify_poses composed from what the package offered before the fused kernel: evaluation.render_depth into an
+    [n C, H, W] z-buffer, then torch comparisons.  The yardstick of tools/pose_verify_profile.py and of the test that ties the LDS
+    path to raster_kernel; it reads and writes n C H W floats several times over and is not meant for use.  -> counts i32[n,C,6]."""
+    from . import evaluation
+    n, C = RT.shape[:2]
+    dev = RT.device
+    depth = torch.as_tensor(depth).to(device=dev, dtype=torch.float32)
+    H, W = depth.shape[-2:]
+    K = torch.as_tensor(K).to(device=dev, dtype=torch.float64)
+    z_r = evaluation.render_depth(verts, faces, RT.reshape(n * C, 3, 4), K if K.dim() == 2 else K.repeat_interleave(C, dim=0), H, W, near,
+                                  keep_inf=True).view(n, C, H, W)
+    model = torch.isfinite(z_r)
+    if window is not None:
+        w = torch.as_tensor(window).to(dev).long()
+        xs, ys = torch.arange(W, device=dev), torch.arange(H, device=dev)
+        inside = ((ys[None, :, None] >= w[:, 1, None, None]) & (ys[None, :, None] <= w[:, 3, None, None])
+                  & (xs[None, None, :] >= w[:, 0, None, None]) & (xs[None, None, :] <= w[:, 2, None, None]))
+        model = model & inside[:, None]
+    z_o = depth.view(-1, 1, H, W).expand(n, C, H, W)
+    D = torch.tensor(np.float32(delta), device=dev)
+    Q = torch.tensor(np.float32(256.0 / float(delta)), device=dev)
+    seen = z_o > 0
+    d = z_o - z_r
+    a = d.abs()
+    agree = model & seen & (a <= D)
+    front = model & seen & ~(a <= D) & (d < -D)
+    behind = model & seen & ~(a <= D) & ~(d < -D)
+    nodepth = model & ~seen
+    q = torch.where(agree, torch.floor(a * Q), torch.zeros_like(a)).to(torch.int64)
+    return torch.stack([m.sum(dim=(2, 3)) for m in (model, agree, front, behind, nodepth, q)], dim=-1).to(torch.int32)

@@ -389,11 +389,12 @@ class RenderedFrames:
     origin_labels = 0 on the device, which is what device_targets replaces by the batch's first valid item: no host read.
     model_xyz f32[M,3] (metres) gives the radius the distractors are placed by.  train=False (held-out frames for -state=test):
     no box jitter, and the batch carries scene_id / im_id.  build_pyramid=False leaves the neighbour pyramid (which wants n_points >=
-    1024) to the consumer, as make_inputs_from_boxes does."""
+    1024) to the consumer, as make_inputs_from_boxes does.  keep_frames=True: a batch also carries frame_depth f32[B,H,W] (the rendered
+    depth frame) and bbox f32[B,4] (the target's visible box), what pose.verify_poses wants; the default leaves the batch as it is."""
 
     def __init__(self, scene, target_obj, model_xyz, batch, n_points, S_crop=256, seed=0, n_batches=64, K=None, H=480, W=640, S=4,
                  z_range=(0.4, 1.0), distractor_objs=None, backdrop_obj=None, min_px_vis=64, min_valid=200, train=True, cls_id=None,
-                 light=None, ambient=AMBIENT, near=NEAR, build_pyramid=True):
+                 light=None, ambient=AMBIENT, near=NEAR, build_pyramid=True, keep_frames=False):
         from . import synthetic
         self.scene, self.target_obj, self.batch, self.n_points, self.S_crop = scene, int(target_obj), int(batch), int(n_points), int(S_crop)
         self.seed, self.n_batches, self.H, self.W, self.S = int(seed), int(n_batches), int(H), int(W), int(S)
@@ -405,6 +406,7 @@ class RenderedFrames:
         self.distractor_objs = tuple(others if distractor_objs is None else distractor_objs)
         self.min_px_vis, self.min_valid, self.train, self.cls_id = int(min_px_vis), int(min_valid), bool(train), cls_id
         self.light, self.ambient, self.near, self.build_pyramid = light, ambient, near, bool(build_pyramid)
+        self.keep_frames = bool(keep_frames)
         dev = scene.device
         self._K32 = torch.from_numpy(self.K.astype(np.float32)).to(dev).expand(self.batch, 3, 3).contiguous()
         self._K64 = torch.from_numpy(self.K).to(dev)
@@ -439,6 +441,8 @@ class RenderedFrames:
         if not self.train:
             item["scene_id"] = torch.full((self.batch,), 1 + self.seed, dtype=torch.int32)
             item["im_id"] = torch.arange(i * self.batch, (i + 1) * self.batch, dtype=torch.int32)
+        if self.keep_frames:
+            item["frame_depth"], item["bbox"] = fr["depth"], bbox
         return item
 
     def __iter__(self):

@@ -111,6 +111,15 @@ def build_parser():
                    help="test, --icp-metric plane: Huber threshold on the point-to-plane residual in metres")
     p.add_argument("--icp-normal-gate", dest="icp_normal_gate", type=float, default=None, metavar="C",
                    help="test, --icp-metric plane: drop pairs whose scene and model normals have a cosine below C")
+    p.add_argument("--pose-verify", dest="pose_verify", action="store_true",
+                   help="test, -data rendered: fit every pose of --verify-candidates, verify each against the depth frame "
+                        "(pose.estimate_poses_verified) and keep the best; prints the recall table of every candidate and of the "
+                        "selection, and the verification score becomes the csv score")
+    p.add_argument("--verify-delta", dest="verify_delta", type=float, default=0.01, metavar="D",
+                   help="test, --pose-verify: the depth agreement tolerance in metres")
+    p.add_argument("--verify-candidates", dest="verify_candidates", type=str, default="kabsch,ransac,kabsch+icp,ransac+icp",
+                   help="test, --pose-verify: comma-separated candidates out of kabsch, ransac, kabsch+icp, ransac+icp "
+                        "(+icp runs --icp-iters iterations, 10 when that is 0)")
     p.add_argument("--objects-across-gpus", action="store_true",
                    help="train: the dataset's objects are independent jobs (train_ycb.sh:3-9 runs them one after the other): rank r of a "
                         "torch.distributed.run launch trains objects r, r + world, ... on its own GPU as single-process jobs -- no process "
@@ -397,9 +406,10 @@ def _rendered_meshes(args, cls_id):
     return out, 0
 
 
-def make_rendered(args, split, cls_id, batch_size, device):
+def make_rendered(args, split, cls_id, batch_size, device, keep_frames=False):
     """-data rendered: render.RenderedFrames over the object's mesh (metres), other meshes as distractors and a backdrop plane;
-    --synthetic-items frames per epoch; the test split draws from another seed and carries no box jitter."""
+    --synthetic-items frames per epoch; the test split draws from another seed and carries no box jitter.  keep_frames: the batches
+    also carry the depth frame and the target's box (--pose-verify)."""
     from . import render
     meshes, target = _rendered_meshes(args, cls_id)
     packed = [(m["verts"], m["faces"], m.get("colors"), m.get("normals")) for m in meshes]
@@ -409,7 +419,7 @@ def make_rendered(args, split, cls_id, batch_size, device):
     model_xyz = _model_points(args, ds, cls_id)[:, :3] / 1000.0
     return render.RenderedFrames(scene, target, model_xyz, batch_size, args.n_points, seed=0 if split == "train" else 1,
                                  n_batches=max(1, args.synthetic_items // batch_size), backdrop_obj=len(packed) - 1,
-                                 train=split == "train", cls_id=cls_id)
+                                 train=split == "train", cls_id=cls_id, keep_frames=keep_frames)
 
 
 def make_dataset(args, split, cls_ids=None):
@@ -550,11 +560,22 @@ def test(args):
     """train_lm.py:317-373 without the BOP evaluator: ONE MODEL PER OBJECT of the dataset (:331-340), every batch dispatched per
     instance by its `cls_id` (:298-314) -- grouped per object into true batches here -- then dense matching and the batched GPU
     pose solve (evaluator.py:78-100).  Returns per-batch results in the loader's instance order."""
+    rendered = getattr(args, "data", "synthetic") == "rendered"
+    verify_names = None
+    if getattr(args, "pose_verify", False):
+        if not rendered:
+            raise SystemExit("train_lm test: --pose-verify needs -data rendered: the other batches carry no depth frame and no mesh "
+                             "faces (use pose.verify_poses from Python)")
+        verify_names = tuple(k for k in args.verify_candidates.split(",") if k)
+        if not verify_names or set(verify_names) - set(pose.VERIFY_CANDIDATES) or len(set(verify_names)) != len(verify_names):
+            raise SystemExit("train_lm test: --verify-candidates takes distinct names out of %s, got %r" %
+                             (", ".join(pose.VERIFY_CANDIDATES), args.verify_candidates))
+        if args.graph_batch1:
+            raise SystemExit("train_lm test: --pose-verify does not go with --graph-batch1")
     ds = dataset_config(args.dataset_name)
     batch_size = args.batch_size or ds["val_batch_size"]
     device = torch.device("cuda", args.local_rank)
     torch.cuda.set_device(device)
-    rendered = getattr(args, "data", "synthetic") == "rendered"
     ids = [args.cls_id] if args.single_object or rendered else sorted(ds["objs"])
     ckpt_root = args.checkpoint or ds["checkpoints"]
     model_dict = {}
@@ -565,7 +586,7 @@ def test(args):
             load_checkpoint(model, None, stem, device=device, strict=ds["load_strict"])
         model_dict[cid] = model.eval()
     if rendered:
-        loader = make_rendered(args, "test", args.cls_id, batch_size, device)
+        loader = make_rendered(args, "test", args.cls_id, batch_size, device, keep_frames=verify_names is not None)
     else:
         loader = torch.utils.data.DataLoader(make_dataset(args, "test", cls_ids=ids), batch_size=batch_size, shuffle=False, num_workers=2)
     graphs = {}
@@ -606,6 +627,14 @@ def test(args):
         for cid in ids:
             R, t = evaluation.symmetry_transformations(info.get(cid, {}), scale=0.001)
             syms[cid] = (torch.from_numpy(R).to(device), torch.from_numpy(t).to(device))
+    # --pose-verify: the mesh _rendered_meshes drew (metres), the depth frame and the padded box of every item; one recall table per
+    # candidate beside the selection's
+    verify_mesh, cand_tables = None, {}
+    if verify_names is not None:
+        mesh = _rendered_meshes(args, args.cls_id)[0][0]
+        verify_mesh = (torch.from_numpy(np.asarray(mesh["verts"], dtype=np.float64) / 1000.0).to(device),
+                       torch.from_numpy(np.ascontiguousarray(mesh["faces"]).astype(np.int32)).to(device))
+        cand_tables = {k: evaluation.RecallTable() for k in verify_names}
     n_seen = 0
     bop_ids_seen = True                                      # every batch so far carried scene_id / im_id
     sym_names = set(ds.get("sym_objs", ()))                 # config/*_cfg.py SYM_OBJS: object NAMES
@@ -620,12 +649,21 @@ def test(args):
                 if cid not in graphs:
                     graphs[cid] = infer.GraphedPipeline(model_dict[cid], one, **pose_kw)
                 out = {k: v.clone() for k, v in graphs[cid](one).items()}
+            elif verify_names is not None:
+                fd = cu["frame_depth"]
+                verify = dict(verts=verify_mesh[0], faces=verify_mesh[1], depth=fd, K=cu["K"], delta=args.verify_delta,
+                              window=pose.boxes_to_windows(cu["bbox"], fd.shape[-2], fd.shape[-1]), candidates=verify_names,
+                              icp_iters=args.icp_iters or 10)
+                out = infer.run_multi_object(model_dict, cu, cls, **dict(pose_kw, verify=verify))
+                out["score"] = out["verify_score"].float()                 # the csv score
             else:
                 out = infer.run_multi_object(model_dict, cu, cls, **pose_kw)
             torch.cuda.synchronize()
             results.append(dict(time=time.perf_counter() - t0, cls_id=cls, count=out["mask"].sum(dim=1).cpu(), best_idx=out["best_idx"].cpu(),
                                 best_sim=out["best_sim"].cpu(), mask=out["mask"].cpu(), RT=out["RT"].cpu(), valid=out["valid"].cpu()))
-            if "score" in out:
+            if verify_names is not None:
+                results[-1].update(score=out["score"].cpu(), verify_which=out["verify_which"].cpu(), verify_counts=out["verify_counts"].cpu())
+            elif "score" in out:
                 results[-1].update(score=out["score"].cpu(), conf=out["conf"].cpu())
             if "RT" in cu and cu["RT"].dim() == 3:
                 Kcam = cu["K"] if "K" in cu else torch.from_numpy(synthetic.LM_K).to(device)
@@ -636,6 +674,11 @@ def test(args):
                                                  sym_rots=getattr(model_dict[cid].model_emb, "sym_rots", None))
                     table.update(obj_name_of(ds, cid), err, ds["diameters"][cid] / 1000.0)
                     prec_table.update(obj_name_of(ds, cid), err, ds["diameters"][cid] / 1000.0)
+                    for c, name in enumerate(verify_names or ()):
+                        cand_tables[name].update(obj_name_of(ds, cid), evaluation.pose_errors(
+                            out["verify_cand_RT"][rows][:, c], cu["RT"][rows][:, :3], model_dict[cid].model_emb.xyz,
+                            Kcam[rows] if Kcam.dim() == 3 else Kcam, symmetric=obj_name_of(ds, cid) in sym_names,
+                            sym_rots=getattr(model_dict[cid].model_emb, "sym_rots", None)), ds["diameters"][cid] / 1000.0)
                     if bop_scores is not None:
                         mssd, mspd, _, _ = evaluation.mssd_mspd(out["RT"][rows], cu["RT"][rows][:, :3], model_dict[cid].model_emb.xyz,
                                                                 syms[cid][0], syms[cid][1], Kcam[rows] if Kcam.dim() == 3 else Kcam)
@@ -665,7 +708,13 @@ def test(args):
             n_seen += len(cls)
     if table.recalls:
         test.last_table = table
+        test.last_candidate_tables = cand_tables
         if args.local_rank == 0:
+            for name, t in cand_tables.items():
+                print("--pose-verify candidate %s:" % name)
+                print(t.format())
+            if cand_tables:
+                print("--pose-verify selection (delta %g m):" % args.verify_delta)
             print(table.format())
     if bop_scores is not None and bop_scores.correct:
         test.last_bop_scores = bop_scores

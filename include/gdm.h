@@ -1056,6 +1056,32 @@ int gdm_render_depth_hip(const void* verts, int verts_f64, const int32_t* faces,
 int gdm_vsd_counts_hip(const float* depth_est, const float* depth_gt, const float* depth_test, int test_per_instance, const double* K,
                        int k_per_instance, int n, int H, int W, double delta, const double* taus /* host array */, int T,
                        double diameter, int inf_is_empty, int32_t* counts, double* tl_sums, void* stream);
+/* Pose candidates verified against the observed depth (pose.verify_poses_numpy restates it bit for bit): C candidate
+ * poses of one mesh for each of n instances are rasterised by THE PIXEL RULE above into tiles of the instance's window held in LDS,
+ * compared there with the observed depth, and summed into six integers per candidate; no depth image is written.  Parity with any
+ * other verifier is NOT claimed.  verts, faces as for gdm_render_depth_hip; RT f64[n,C,3,4]; depth_obs f32[n,H,W]
+ * (obs_per_instance 1) or one shared f32[H,W] (0); window i32[n,4] = (x0, y0, x1, y1), inclusive, in frame pixels -- DEVICE data the
+ * entry does not read: the kernel clamps it to the frame, an empty one gives all-zero counts -- or NULL for the whole frame;
+ * cand_valid u8[n,C] or NULL (every candidate valid).  THE VERIFICATION RULE for a pixel p of the clamped window whose rendered depth
+ * z_r is drawn (the z-buffer minimum of the candidate, below +inf), with z_o = depth_obs[p]; all fp32, single operations:
+ *   NODEPTH     z_o is not > 0 (zero, negative, NaN)
+ *   otherwise   d = z_o - z_r, a = |d|, D = (float) delta
+ *   AGREE       a <= D; q += (int) floor(a * Q) with Q = (float)(256.0 / delta) formed on the host: 0 for a perfect pixel, 256 at the edge
+ *   FRONT       d < -D: something stands in front of the model (occlusion, neutral)
+ *   BEHIND      d > D: the camera sees through the model (a contradiction)
+ * counts i32[n,C,6] = (n_model, n_agree, n_front, n_behind, n_nodepth, q_agree), n_model the sum of the four classes; integer atomic
+ * adds, cleared by the entry: reproducible bit for bit.
+ * THE SELECTION, fp64, candidates in index order:
+ *   score[i,c] = (n_agree - q_agree / 512.0) / max(1.0, (n_agree + n_behind) + front_weight * n_front), written for every candidate;
+ *   candidate c is eligible when cand_valid[i,c] != 0 and n_model >= min_px; best[i] = the eligible candidate with the largest score,
+ *   the lowest index on a tie, -1 when none is eligible.
+ * LIMITS (refused beyond): n, C <= 65535, H, W <= 16384, H W <= 2^22 (q_agree stays inside an int32), tiles n C <= 2^23 with
+ * tiles = ceil(W / 64) ceil(H / 64); near >= 0, delta > 0 with delta and 256 / delta finite in fp32, front_weight >= 0, min_px >= 0.
+ * No workspace, no allocation and no host read: the call captures in a hipGraph. */
+int gdm_pose_verify_hip(const void* verts, int verts_f64, const int32_t* faces, const double* RT, const double* K, int k_per_instance,
+                        const float* depth_obs, int obs_per_instance, const int32_t* window, const uint8_t* cand_valid, int n, int C,
+                        int V, int F, int H, int W, double near, double delta, double front_weight, int min_px, int32_t* counts,
+                        double* score, int32_t* best, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Training frames from meshes: colour, depth, instance mask, face ids and per-slot visibility statistics of n frames of S posed
