@@ -19,15 +19,19 @@ def _plane_normals(model, pose_opts):
 
 def _pose_stage(model, res, cld_rgb_nrm, pose_fit, icp_iters, pose_opts, verify):
     """pose.estimate_poses, or with a `verify` dict pose.estimate_poses_verified, whose winner comes back as RT / valid beside
-    verify_score f64[B], verify_which i32[B], verify_counts i32[B,C,6] and verify_cand_RT f32[B,C,3,4] (every candidate, in order)."""
+    verify_score f64[B], verify_which i32[B], verify_counts i32[B,C,6] and verify_cand_RT f32[B,C,3,4] (every candidate, in order);
+    the dict's candidates, icp_iters, depth_iters and depth_opts are estimate_poses_verified's arguments, the rest its `verify`."""
     if verify is None:
         return pose.estimate_poses(res, cld_rgb_nrm, model.model_emb.xyz, pose_fit, icp_iters, pose_opts, _plane_normals(model, pose_opts))
     v = dict(verify)
-    kw = {k: v.pop(k) for k in ("candidates", "icp_iters") if k in v}
+    kw = {k: v.pop(k) for k in ("candidates", "icp_iters", "depth_iters", "depth_opts") if k in v}
     sel = pose.estimate_poses_verified(res, cld_rgb_nrm, model.model_emb.xyz, v, pose_opts=pose_opts,
                                        model_nrm=_plane_normals(model, pose_opts), **kw)
-    return dict(RT=sel["RT"], valid=sel["valid"], verify_score=sel["score"], verify_which=sel["which"], verify_counts=sel["counts"],
-                verify_cand_RT=sel["cand_RT"])
+    out = dict(RT=sel["RT"], valid=sel["valid"], verify_score=sel["score"], verify_which=sel["which"], verify_counts=sel["counts"],
+               verify_cand_RT=sel["cand_RT"])
+    if "depth_status" in sel:                                              # only with a "+depth" candidate
+        out["verify_depth_status"] = sel["depth_status"]
+    return out
 
 
 def _verify_rows(verify, cid, idx, bs):
@@ -47,8 +51,8 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
     `dpt_xyz` when the neighbour pyramid is not already in it); cls_ids: int tensor/list [bs].  pose_fit / icp_iters / pose_opts:
     pose.estimate_poses (the defaults are the plain Kabsch fit).  match_gamma: soft matching at that temperature (pipeline_step).
     verify (with_pose only): the dict pose.estimate_poses_verified takes (verts, faces, depth, K[, window, delta, ...], optionally
-    candidates and icp_iters), one for all classes or {cls_id: dict}; depth / K / window with a leading batch dimension are cut down to
-    each class's rows.  The pose is then the verified selection and verify_score, verify_which, verify_counts join the outputs.
+    candidates, icp_iters, depth_iters and depth_opts; a "+depth" candidate adds verify_depth_status), one for all classes or
+    {cls_id: dict}; depth / K / window with a leading batch dimension are cut down to each class's rows.  The pose is then the verified selection and verify_score, verify_which, verify_counts join the outputs.
     Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, lse, conf, soft_xyz, score][, RT, valid[, icp_iters, icp_resid[, icp_status]]])."""
     cls = torch.as_tensor(cls_ids).cpu().tolist()
     bs = len(cls)
@@ -92,8 +96,9 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
     and the outputs gain lse, conf, soft_xyz (include/gdm.h gdm_match_soft_packed_hip) and score f32[B] = the mean of conf over the
     masked points (0 where none); pose_opts' weights / targets can then use them.
     verify = None: the pose stage as ever.  With with_pose and a verify dict (pose.estimate_poses_verified: verts, faces, depth, K[,
-    window, delta, ...], optionally candidates and icp_iters) RT / valid are the candidate the observed depth agrees with best and
-    the outputs gain verify_score, verify_which and verify_counts; still no host synchronisation."""
+    window, delta, ...], optionally candidates, icp_iters, depth_iters and depth_opts) RT / valid are the candidate the observed depth
+    agrees with best and the outputs gain verify_score, verify_which and verify_counts (verify_depth_status i32[B,C] with a "+depth"
+    candidate, which pose.refine_poses_depth refines against the frame); still no host synchronisation."""
     prec = _PREC[precision]
     d = dict(inputs)
     pyr = None

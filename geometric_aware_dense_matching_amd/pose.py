@@ -12,6 +12,8 @@ Opt-in robust variants (csrc/gdm_pose_robust.hip), also on the device and captur
 and, with no counterpart in the reference, point-to-plane ICP with normal gating and Huber weights: refine_icp_plane.
 Verification of pose candidates against the observed depth frame (csrc/gdm_verify.hip), also without one:
   verify_poses / verify_poses_numpy, boxes_to_windows, select_verified, estimate_poses_verified.
+Refinement of pose candidates against that frame by render-and-compare (csrc/gdm_refine.hip), likewise:
+  refine_poses_depth / refine_poses_depth_numpy, and the "+depth" candidates of estimate_poses_verified.
 """
 import numpy as np
 import torch
@@ -463,17 +465,10 @@ VERIFY_COUNTS = ("n_model", "n_agree", "n_front", "n_behind", "n_nodepth", "q_ag
 VERIFY_CANDIDATES = ("kabsch", "ransac", "kabsch+icp", "ransac+icp")
 
 
-def verify_poses(verts, faces, RT, depth, K, window=None, delta=0.01, near=0.0, front_weight=0.25, min_px=16, cand_valid=None):
-    """C candidate poses of one mesh for each of n instances against the observed depth, in one fused launch (gdm_pose_verify_hip):
-    every candidate is rasterised by the pixel rule of include/gdm.h into LDS tiles of the instance's window and compared there with
-    the depth frame; no [n C, H, W] image exists.  verts f32|f64[V,3] (passed on in that dtype, as evaluation.render_depth does) and
-    faces i32[F,3] (device tensors or arrays); RT [n,C,3,4], a device tensor of any float dtype; depth f32[H,W] or [n,H,W]; K [3,3]
-    or [n,3,3]; window i32[n,4] = (x0, y0, x1, y1) inclusive in frame pixels (boxes_to_windows), None = the whole frame; cand_valid
-    bool[n,C] or None.  delta: the agreement tolerance in the unit of depth.  front_weight and min_px are the defaults of a
-    definition, not tuned values.  -> dict(counts i32[n,C,6] = VERIFY_COUNTS, score f64[n,C], best i32[n]: the eligible candidate
-    with the largest score, the lowest index on a tie, -1 when there is none).  No host synchronisation."""
+def _verify_like_args(who, verts, faces, RT, depth, K, window, cand_valid):
+    """The argument handling verify_poses and refine_poses_depth share: everything on RT's device in the dtype the entries take."""
     if not torch.is_tensor(RT) or RT.dim() != 4 or tuple(RT.shape[2:]) != (3, 4) or RT.shape[0] < 1 or RT.shape[1] < 1:
-        raise ValueError("verify_poses: RT must be a tensor [n,C,3,4], got %s" % (tuple(RT.shape) if torch.is_tensor(RT) else type(RT),))
+        raise ValueError("%s: RT must be a tensor [n,C,3,4], got %s" % (who, tuple(RT.shape) if torch.is_tensor(RT) else type(RT)))
     dev = RT.device
     n, C = RT.shape[:2]
     RT = ops._dev(RT.to(torch.float64), torch.float64, "RT")
@@ -483,26 +478,42 @@ def verify_poses(verts, faces, RT, depth, K, window=None, delta=0.01, near=0.0, 
     verts = ops._dev(verts, verts.dtype, "verts")
     faces = ops._dev(torch.as_tensor(faces).to(device=dev, dtype=torch.int32), torch.int32, "faces")
     if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
-        raise ValueError("verify_poses: verts must be [V,3], got %s" % (tuple(verts.shape),))
+        raise ValueError("%s: verts must be [V,3], got %s" % (who, tuple(verts.shape)))
     if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-        raise ValueError("verify_poses: faces must be [F,3], got %s" % (tuple(faces.shape),))
+        raise ValueError("%s: faces must be [F,3], got %s" % (who, tuple(faces.shape)))
     depth = ops._dev(torch.as_tensor(depth).to(device=dev, dtype=torch.float32), torch.float32, "depth")
     if depth.dim() == 2:
         opi = 0
     elif depth.dim() == 3 and depth.shape[0] == n:
         opi = 1
     else:
-        raise ValueError("verify_poses: depth must be [H,W] or [n=%d,H,W], got %s" % (n, tuple(depth.shape)))
-    H, W = depth.shape[-2:]
+        raise ValueError("%s: depth must be [H,W] or [n=%d,H,W], got %s" % (who, n, tuple(depth.shape)))
     K, kpi = ops._k64(torch.as_tensor(K).to(device=dev, dtype=torch.float64), n, "K")
     if window is not None:
         window = ops._dev(torch.as_tensor(window).to(device=dev, dtype=torch.int32), torch.int32, "window")
         if tuple(window.shape) != (n, 4):
-            raise ValueError("verify_poses: window must be [n=%d,4], got %s" % (n, tuple(window.shape)))
+            raise ValueError("%s: window must be [n=%d,4], got %s" % (who, n, tuple(window.shape)))
     if cand_valid is not None:
         cand_valid = ops._dev(torch.as_tensor(cand_valid).to(device=dev, dtype=torch.uint8), torch.uint8, "cand_valid")
         if tuple(cand_valid.shape) != (n, C):
-            raise ValueError("verify_poses: cand_valid must be [n=%d,C=%d], got %s" % (n, C, tuple(cand_valid.shape)))
+            raise ValueError("%s: cand_valid must be [n=%d,C=%d], got %s" % (who, n, C, tuple(cand_valid.shape)))
+    return verts, faces, RT, depth, opi, K, kpi, window, cand_valid
+
+
+def verify_poses(verts, faces, RT, depth, K, window=None, delta=0.01, near=0.0, front_weight=0.25, min_px=16, cand_valid=None):
+    """C candidate poses of one mesh for each of n instances against the observed depth, in one fused launch (gdm_pose_verify_hip):
+    every candidate is rasterised by the pixel rule of include/gdm.h into LDS tiles of the instance's window and compared there with
+    the depth frame; no [n C, H, W] image exists.  verts f32|f64[V,3] (passed on in that dtype, as evaluation.render_depth does) and
+    faces i32[F,3] (device tensors or arrays); RT [n,C,3,4], a device tensor of any float dtype; depth f32[H,W] or [n,H,W]; K [3,3]
+    or [n,3,3]; window i32[n,4] = (x0, y0, x1, y1) inclusive in frame pixels (boxes_to_windows), None = the whole frame; cand_valid
+    bool[n,C] or None.  delta: the agreement tolerance in the unit of depth.  front_weight and min_px are the defaults of a
+    definition, not tuned values.  -> dict(counts i32[n,C,6] = VERIFY_COUNTS, score f64[n,C], best i32[n]: the eligible candidate
+    with the largest score, the lowest index on a tie, -1 when there is none).  No host synchronisation."""
+    verts, faces, RT, depth, opi, K, kpi, window, cand_valid = _verify_like_args("verify_poses", verts, faces, RT, depth, K, window,
+                                                                                 cand_valid)
+    dev = RT.device
+    n, C = RT.shape[:2]
+    H, W = depth.shape[-2:]
     counts = torch.empty((n, C, 6), dtype=torch.int32, device=dev)
     score = torch.empty((n, C), dtype=torch.float64, device=dev)
     best = torch.empty((n,), dtype=torch.int32, device=dev)
@@ -571,6 +582,241 @@ def verify_poses_numpy(verts, faces, RT, depth, K, window=None, delta=0.01, near
     return dict(counts=counts, score=score, best=best)
 
 
+# ---- refinement against the observed depth (csrc/gdm_refine.hip; include/gdm.h THE DEPTH REFINEMENT RULE) --------------
+REFINE_STATUS = {0: "active", 1: "converged", 2: "starved", 3: "degenerate", 4: "invalid on entry"}
+REFINE_SUMS = 30               # A upper triangle (21), g (6), S, L2, E: the doubles of a partial row before the pair count
+
+
+def refine_poses_depth(verts, faces, RT, depth, K, window=None, iters=5, reject=0.01, huber=None, min_cos=0.0, near=0.0, min_px=16,
+                       tolerance=0.0, pivot_min=1e-6, cand_valid=None):
+    """C candidate poses of one mesh for each of n instances moved towards the observed depth by render-and-compare
+    (gdm_pose_refine_depth_hip; include/gdm.h THE DEPTH REFINEMENT RULE): per iteration every active candidate is rasterised into LDS
+    tiles of its window, every drawn pixel whose observed depth lies within `reject` of the rendered one pairs with the face drawn
+    there, and one point-to-plane Gauss-Newton step is solved from the fp64 sums; the pose stays fp64 throughout.  Arguments as for
+    verify_poses; huber None or 0 = no robust weights, min_cos 0 = no grazing gate.  reject, huber and min_cos are the defaults of a
+    definition, not tuned values.  -> dict(RT f64[n,C,3,4], status i32[n,C] (REFINE_STATUS), iters i32[n,C], err f64[n,C] = mean |r|
+    of the last applied iteration, pairs i32[n,C]).  A candidate with status 2, 3 or 4 keeps the pose it had.  Reproducible bit for
+    bit; no host synchronisation; the only temporary is the planner's workspace."""
+    verts, faces, RT, depth, opi, K, kpi, window, cand_valid = _verify_like_args("refine_poses_depth", verts, faces, RT, depth, K, window,
+                                                                                 cand_valid)
+    dev = RT.device
+    n, C = RT.shape[:2]
+    H, W = depth.shape[-2:]
+    nbytes = call("gdm_pose_refine_depth_workspace_bytes", n, C, H, W)
+    if nbytes == 0:
+        raise ValueError("refine_poses_depth: n=%d C=%d H=%d W=%d is beyond the entry's limits (include/gdm.h)" % (n, C, H, W))
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    out = torch.empty((n, C, 3, 4), dtype=torch.float64, device=dev)
+    status = torch.empty((n, C), dtype=torch.int32, device=dev)
+    its = torch.empty((n, C), dtype=torch.int32, device=dev)
+    err = torch.empty((n, C), dtype=torch.float64, device=dev)
+    pairs = torch.empty((n, C), dtype=torch.int32, device=dev)
+    call("gdm_pose_refine_depth_hip", verts, int(verts.dtype == torch.float64), faces, RT, K, kpi, depth, opi, window, cand_valid, n, C,
+         verts.shape[0], faces.shape[0], H, W, float(near), int(iters), float(reject), float(huber or 0.0), float(min_cos), int(min_px),
+         float(tolerance), float(pivot_min), ws, nbytes, out, status, its, err, pairs)
+    return dict(RT=out, status=status, iters=its, err=err, pairs=pairs)
+
+
+def raster_depth_face_numpy(verts, faces, rt, K, H, W, near):
+    """One pose by the pixel rule of include/gdm.h (evaluation.render_depth_numpy), keeping the face too: depth f32[H,W] (+inf where
+    nothing is drawn) and face i64[H,W] (-1 there) -- per pixel the minimum depth, the lowest face index among equal depths."""
+    verts, rt, K = np.asarray(verts, dtype=np.float64), np.asarray(rt, dtype=np.float64), np.asarray(K, dtype=np.float64)
+    faces = np.asarray(faces).astype(np.int64)
+    zbuf = np.full((H, W), np.inf, dtype=np.float32)
+    fbuf = np.full((H, W), -1, dtype=np.int64)
+    x, y, z = verts[:, 0], verts[:, 1], verts[:, 2]
+    R, t = rt[:, :3], rt[:, 3]
+    with np.errstate(all="ignore"):
+        X = ((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0]
+        Y = ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1]
+        Z = ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]
+        u = K[0, 0] * (X / Z) + K[0, 2]
+        v = K[1, 1] * (Y / Z) + K[1, 2]
+        ok = (Z > near) & (np.abs(u) <= 65536.0) & (np.abs(v) <= 65536.0)
+        xs = np.floor(np.where(ok, u, 0.0) * 256.0 + 0.5).astype(np.int64)
+        ys = np.floor(np.where(ok, v, 0.0) * 256.0 + 0.5).astype(np.int64)
+        iz = 1.0 / Z
+    V = len(verts)
+    for fi, f in enumerate(faces):
+        if not ((f >= 0) & (f < V)).all() or not ok[f].all():
+            continue
+        i0, i1, i2 = f
+        A2 = (xs[i1] - xs[i0]) * (ys[i2] - ys[i0]) - (xs[i2] - xs[i0]) * (ys[i1] - ys[i0])
+        if A2 == 0:
+            continue
+        if A2 < 0:
+            i1, i2 = i2, i1
+        px0, px1 = max((min(xs[i0], xs[i1], xs[i2]) + 255) >> 8, 0), min(max(xs[i0], xs[i1], xs[i2]) >> 8, W - 1)
+        py0, py1 = max((min(ys[i0], ys[i1], ys[i2]) + 255) >> 8, 0), min(max(ys[i0], ys[i1], ys[i2]) >> 8, H - 1)
+        if px0 > px1 or py0 > py1:
+            continue
+        PX, PY = np.meshgrid(np.arange(px0, px1 + 1, dtype=np.int64) * 256, np.arange(py0, py1 + 1, dtype=np.int64) * 256)
+        inside, w = np.ones(PX.shape, dtype=bool), []
+        for a, c in ((i1, i2), (i2, i0), (i0, i1)):                    # the edge opposite vertex 0, 1, 2
+            dx, dy = xs[c] - xs[a], ys[c] - ys[a]
+            e = dx * (PY - ys[a]) - dy * (PX - xs[a])
+            inside &= (e > 0) | ((e == 0) & bool(dy < 0 or (dy == 0 and dx > 0)))
+            w.append(e)
+        if not inside.any():
+            continue
+        A = ((w[0] + w[1]) + w[2]).astype(np.float64)
+        with np.errstate(all="ignore"):
+            izp = ((w[0].astype(np.float64) * iz[i0] + w[1].astype(np.float64) * iz[i1]) + w[2].astype(np.float64) * iz[i2]) / A
+            d = (1.0 / izp).astype(np.float32)
+        zt, ft = zbuf[py0:py1 + 1, px0:px1 + 1], fbuf[py0:py1 + 1, px0:px1 + 1]
+        # the unsigned order of the depth bits: positive floats in their own order, NaN and negative values above +inf (never kept);
+        # faces come in ascending order, so a strict < keeps the lowest index among equal depths
+        with np.errstate(invalid="ignore"):
+            take = inside & (d >= 0) & (d < zt)
+        zt[take] = d[take]
+        ft[take] = fi
+    return zbuf, fbuf
+
+
+def refine_depth_sums_numpy(verts, faces, rt, depth, K, window=None, reject=0.01, huber=None, min_cos=0.0, near=0.0, terms=False):
+    """The pairs and sums of ONE iteration of THE DEPTH REFINEMENT RULE for one pose rt f64[3,4] against depth f32[H,W]: the same fp64
+    single operations as the kernel, the sums in numpy's order.  -> dict(sums f64[30] = A upper triangle (21), g (6), S, L2, E;
+    pairs; with terms=True also J f64[P,6], r, w f64[P], the pixel coordinates uv i64[P,2] and the margins |r| - huber and
+    |cos| - min_cos of every pair that reached the gate in question)."""
+    verts_in = np.asarray(verts)
+    verts64 = verts_in.astype(np.float64)                                  # fp32 vertices widen exactly
+    faces = np.asarray(faces).astype(np.int64)
+    rt = np.asarray(rt, dtype=np.float64)
+    K = np.asarray(K, dtype=np.float64)
+    depth = np.asarray(depth, dtype=np.float32)
+    H, W = depth.shape
+    x0, y0, x1, y1 = (0, 0, W - 1, H - 1) if window is None else (int(v) for v in np.asarray(window))
+    x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, W - 1), min(y1, H - 1)
+    out = dict(sums=np.zeros(REFINE_SUMS), pairs=0)
+    huber = float(huber or 0.0)
+    empty = np.zeros(0)
+    if terms:
+        out.update(J=np.zeros((0, 6)), r=empty, w=empty, uv=np.zeros((0, 2), dtype=np.int64), huber_margin=empty, cos_margin=empty)
+    if x0 > x1 or y0 > y1:
+        return out
+    zbuf, fbuf = raster_depth_face_numpy(verts64, faces, rt, K, H, W, near)
+    inside = np.zeros((H, W), dtype=bool)
+    inside[y0:y1 + 1, x0:x1 + 1] = True
+    with np.errstate(invalid="ignore"):
+        pair = inside & (fbuf >= 0) & np.isfinite(zbuf) & (depth > 0)
+        pair &= np.abs((depth - zbuf).astype(np.float32)) <= np.float32(reject)
+    v, u = np.nonzero(pair)                                                # row-major pixel order
+    if len(u) == 0:
+        return out
+    f = faces[fbuf[v, u]]
+    a, b, c = verts64[f[:, 0]], verts64[f[:, 1]], verts64[f[:, 2]]
+    e1, e2 = b - a, c - a
+    mx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    my = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    mz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    mm = (mx * mx + my * my) + mz * mz
+    keep = mm > 0.0
+    with np.errstate(all="ignore"):
+        ln = np.sqrt(mm)
+        nx, ny, nz = mx / ln, my / ln, mz / ln
+    zo = depth[v, u].astype(np.float64)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    ox, oy, oz = (zo * (u.astype(np.float64) - cx)) / fx, (zo * (v.astype(np.float64) - cy)) / fy, zo
+    R, t = rt[:, :3], rt[:, 3]
+    cos_margin = empty
+    if min_cos > 0.0:
+        qx = (R[0, 0] * nx + R[0, 1] * ny) + R[0, 2] * nz
+        qy = (R[1, 0] * nx + R[1, 1] * ny) + R[1, 2] * nz
+        qz = (R[2, 0] * nx + R[2, 1] * ny) + R[2, 2] * nz
+        dot = np.abs((qx * ox + qy * oy) + qz * oz)
+        lim = np.float64(min_cos) * np.sqrt((ox * ox + oy * oy) + oz * oz)
+        cos_margin = (dot - lim)[keep]
+        with np.errstate(invalid="ignore"):
+            keep = keep & ~(dot < lim)
+    dx, dy, dz = ox - t[0], oy - t[1], oz - t[2]
+    X = (R[0, 0] * dx + R[1, 0] * dy) + R[2, 0] * dz
+    Y = (R[0, 1] * dx + R[1, 1] * dy) + R[2, 1] * dz
+    Z = (R[0, 2] * dx + R[1, 2] * dy) + R[2, 2] * dz
+    r = (nx * (X - a[:, 0]) + ny * (Y - a[:, 1])) + nz * (Z - a[:, 2])
+    sel = np.nonzero(keep)[0]
+    X, Y, Z, nx, ny, nz, r, u, v = (q[sel] for q in (X, Y, Z, nx, ny, nz, r, u, v))
+    ar = np.abs(r)
+    w = np.ones(len(r))
+    if huber > 0.0:
+        with np.errstate(all="ignore"):
+            w = np.where(ar <= huber, 1.0, huber / ar)
+    J = np.stack([Y * nz - Z * ny, Z * nx - X * nz, X * ny - Y * nx, nx, ny, nz], axis=1)
+    sums = np.zeros(REFINE_SUMS)
+    e = 0
+    for p in range(6):
+        wj = w * J[:, p]
+        for q in range(p, 6):
+            sums[e] = (wj * J[:, q]).sum()
+            e += 1
+        sums[21 + p] = (wj * r).sum()
+    sums[27] = w.sum()
+    sums[28] = (w * ((X * X + Y * Y) + Z * Z)).sum()
+    sums[29] = ar.sum()
+    out.update(sums=sums, pairs=len(r))
+    if terms:
+        out.update(J=J, r=r, w=w, uv=np.stack([u, v], axis=1), huber_margin=ar - huber, cos_margin=cos_margin)
+    return out
+
+
+def refine_poses_depth_numpy(verts, faces, RT, depth, K, window=None, iters=5, reject=0.01, huber=None, min_cos=0.0, near=0.0, min_px=16,
+                             tolerance=0.0, pivot_min=1e-6, cand_valid=None, trace=False):
+    """refine_poses_depth on the host, the definition the kernels are tested against: raster_depth_face_numpy draws every active
+    candidate, refine_depth_sums_numpy forms the pairs and sums, icp_plane_solve_numpy (the restatement of gdm_icp_plane_solve.inc)
+    solves and composes, and the stop rule follows the header statement for statement.  Same arguments (arrays or tensors), the same
+    dict as numpy arrays.  trace=True adds `trace`: per (instance, candidate) a list with one dict per iteration evaluated --
+    sums f64[30], pairs, min_pivot (None when starved), mean, stop_margin = | |err - mean| - tolerance |, RT (the pose after it)."""
+    def host(a):
+        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+    RT = host(RT).astype(np.float64).copy()
+    n, C = RT.shape[:2]
+    depth = host(depth).astype(np.float32)
+    H, W = depth.shape[-2:]
+    depth = np.broadcast_to(depth, (n, H, W))
+    K = np.broadcast_to(host(K).astype(np.float64), (n, 3, 3))
+    verts, faces = host(verts), host(faces)
+    status = np.zeros((n, C), dtype=np.int32)
+    if cand_valid is not None:
+        status[host(cand_valid).reshape(n, C) == 0] = 4
+    its = np.zeros((n, C), dtype=np.int32)
+    err = np.zeros((n, C), dtype=np.float64)
+    pairs = np.zeros((n, C), dtype=np.int32)
+    log = [[[] for _ in range(C)] for _ in range(n)]
+    for _ in range(int(iters)):
+        for i in range(n):
+            win = None if window is None else host(window)[i]
+            for c in range(C):
+                if status[i, c] != 0:
+                    continue
+                s = refine_depth_sums_numpy(verts, faces, RT[i, c], depth[i], K[i], win, reject, huber, min_cos, near)
+                pairs[i, c] = s["pairs"]
+                rec = dict(sums=s["sums"], pairs=s["pairs"], min_pivot=None, mean=None, stop_margin=None, RT=RT[i, c].copy())
+                log[i][c].append(rec)
+                if s["pairs"] < max(int(min_px), 6):
+                    status[i, c] = 2
+                    continue
+                A = np.zeros((6, 6))
+                A[np.triu_indices(6)] = s["sums"][:21]
+                A = A + np.triu(A, 1).T
+                with np.errstate(all="ignore"):
+                    sol = icp_plane_solve_numpy(A, s["sums"][21:27], s["sums"][27], s["sums"][28], RT[i, c, :, :3], RT[i, c, :, 3], pivot_min)
+                rec["min_pivot"] = sol["min_pivot"]
+                if sol["degenerate"]:
+                    status[i, c] = 3
+                    continue
+                RT[i, c, :, :3], RT[i, c, :, 3] = sol["R"], sol["t"]
+                its[i, c] += 1
+                mean = s["sums"][29] / np.float64(s["pairs"])
+                rec.update(mean=mean, stop_margin=abs(abs(err[i, c] - mean) - tolerance), RT=RT[i, c].copy())
+                if abs(err[i, c] - mean) < tolerance:
+                    status[i, c] = 1
+                err[i, c] = mean
+    out = dict(RT=RT, status=status, iters=its, err=err, pairs=pairs)
+    if trace:
+        out["trace"] = log
+    return out
+
+
 def boxes_to_windows(bbox_xyxy, H, W, pad=1.25):
     """Detection boxes f[n,4] = (x0, y0, x1, y1) -> the windows verify_poses takes, i32[n,4] on the boxes' device: the box scaled
     about its centre by `pad`, floor / ceil to whole pixels, cut to the frame.  A box that misses the frame gives an empty window
@@ -612,26 +858,58 @@ def select_verified(candidates, verify):
                 cand_RT=cand_RT, cand_valid=cand_valid)
 
 
+_DEPTH_OPTS = {"reject", "huber", "min_cos", "min_px", "tolerance", "pivot_min"}
+
+
 def estimate_poses_verified(res, cld_rgb_nrm, model_xyz, verify, candidates=VERIFY_CANDIDATES, icp_iters=10, pose_opts=None,
-                            model_nrm=None):
+                            model_nrm=None, depth_iters=5, depth_opts=None):
     """Several pose estimates of every crop, judged against the depth frame the crop came from: each name of `candidates` -- "kabsch"
-    or "ransac", with "+icp" for `icp_iters` ICP iterations on it (the base fit is made once and shared) -- goes through
-    estimate_poses' stages with pose_opts, then select_verified(verify) keeps, per crop, the one the observed depth agrees with best.
-    -> select_verified's dict."""
+    or "ransac", with "+icp" for `icp_iters` ICP iterations on it, and after that "+depth" for `depth_iters` iterations of
+    refine_poses_depth on its parent (the name without "+depth") against the verify dict's verts, faces, depth, K, window and near with
+    depth_opts (reject, huber, min_cos, min_px, tolerance, pivot_min) -- goes through estimate_poses' stages with pose_opts, every
+    parent made once and shared; then select_verified(verify) keeps, per crop, the one the observed depth agrees with best.  A
+    "+depth" candidate is its refined pose rounded to f32, valid when the parent was and the refinement's status is 0 or 1.
+    -> select_verified's dict; with a "+depth" name also depth_status i32[n,C]: the refinement's status, -1 for the other candidates."""
     names = tuple(candidates)
-    bad = [k for k in names if k.split("+")[0] not in ("kabsch", "ransac") or k.split("+")[1:] not in ([], ["icp"])]
+    bad = [k for k in names if k.split("+")[0] not in ("kabsch", "ransac")
+           or k.split("+")[1:] not in ([], ["icp"], ["depth"], ["icp", "depth"])]
     if bad or not names or len(set(names)) != len(names):
-        raise ValueError("estimate_poses_verified: candidates must be distinct names out of kabsch, ransac, kabsch+icp, ransac+icp; "
-                         "got %r" % (names,))
+        raise ValueError("estimate_poses_verified: candidates must be distinct names out of kabsch, ransac, kabsch+icp, ransac+icp, "
+                         "each optionally followed by +depth; got %r" % (names,))
     o = dict(pose_opts or {})
-    base, fits = {}, {}
+    dopts = dict(depth_opts or {})
+    if set(dopts) - _DEPTH_OPTS:
+        raise ValueError("estimate_poses_verified: unknown depth_opts %s" % sorted(set(dopts) - _DEPTH_OPTS))
+    made = {}
+
+    def stage(k):
+        if k not in made:
+            fit = k.split("+")[0]
+            if k == fit:
+                made[k] = estimate_poses(res, cld_rgb_nrm, model_xyz, fit, 0, o, model_nrm)
+            else:
+                made[k] = _icp_stage(dict(stage(fit)), res, cld_rgb_nrm, model_xyz, int(icp_iters), o, model_nrm)
+        return made[k]
+
+    fits, depth_status = {}, {}
     for k in names:
-        fit = k.split("+")[0]
-        if fit not in base:
-            base[fit] = estimate_poses(res, cld_rgb_nrm, model_xyz, fit, 0, o, model_nrm)
-        out = base[fit] if k == fit else _icp_stage(dict(base[fit]), res, cld_rgb_nrm, model_xyz, int(icp_iters), o, model_nrm)
-        fits[k] = (out["RT"], out["valid"])
-    return select_verified(fits, verify)
+        parent = stage(k[:-len("+depth")] if k.endswith("+depth") else k)
+        if k.endswith("+depth"):
+            missing = {"verts", "faces", "depth", "K"} - set(verify)
+            if missing:
+                raise ValueError("estimate_poses_verified: verify lacks %s" % sorted(missing))
+            r = refine_poses_depth(verify["verts"], verify["faces"], parent["RT"][:, None], verify["depth"], verify["K"],
+                                   window=verify.get("window"), iters=int(depth_iters), near=verify.get("near", 0.0),
+                                   cand_valid=parent["valid"][:, None], **dopts)
+            depth_status[k] = r["status"][:, 0]
+            fits[k] = (r["RT"][:, 0].to(torch.float32), parent["valid"].bool() & (r["status"][:, 0] <= 1))
+        else:
+            fits[k] = (parent["RT"], parent["valid"])
+    sel = select_verified(fits, verify)
+    if depth_status:
+        none = torch.full_like(next(iter(depth_status.values())), -1)
+        sel["depth_status"] = torch.stack([depth_status.get(k, none) for k in names], dim=1)
+    return sel
 
 
 def verify_counts_composed(verts, faces, RT, depth, K, window=None, delta=0.01, near=0.0):
@@ -665,3 +943,63 @@ def verify_counts_composed(verts, faces, RT, depth, K, window=None, delta=0.01, 
     nodepth = model & ~seen
     q = torch.where(agree, torch.floor(a * Q), torch.zeros_like(a)).to(torch.int64)
     return torch.stack([m.sum(dim=(2, 3)) for m in (model, agree, front, behind, nodepth, q)], dim=-1).to(torch.int32)
+
+
+def refine_sums_composed(verts, faces, RT, depth, K, window=None, reject=0.01, huber=None, min_cos=0.0, near=0.0):
+    """The pairs and sums of one iteration of refine_poses_depth composed from what the package offered before the fused kernel:
+    render.render_frames' kernel into [n C, H, W] depth and face images, then torch gathers and fp64 sums over whole images.  The
+    yardstick of tools/pose_depth_refine_profile.py and of the test that ties the 64-bit LDS path to raster_kernel; not meant for use.
+    -> dict(pairs i32[n,C], sums f64[n,C,30] in the kernel's layout, torch's summation order)."""
+    n, C = RT.shape[:2]
+    dev = RT.device
+    verts = torch.as_tensor(verts).to(dev)
+    verts = verts if verts.dtype in (torch.float32, torch.float64) else verts.double()
+    faces = torch.as_tensor(faces).to(device=dev, dtype=torch.int32).contiguous()
+    depth = torch.as_tensor(depth).to(device=dev, dtype=torch.float32)
+    H, W = depth.shape[-2:]
+    K = torch.as_tensor(K).to(device=dev, dtype=torch.float64)
+    Kc = K.expand(n, 3, 3).repeat_interleave(C, dim=0).contiguous()
+    V, F = verts.shape[0], faces.shape[0]
+    RTc = RT.to(torch.float64).reshape(n * C, 1, 3, 4).contiguous()
+    light = torch.tensor([0.0, 0.0, -1.0], dtype=torch.float64, device=dev).expand(n * C, 3).contiguous()
+    _, z_r, _, face, _ = ops.render_frames(verts.contiguous(), torch.zeros((V, 3), dtype=torch.uint8, device=dev),
+                                           torch.zeros((V, 3), dtype=torch.float32, device=dev), faces, [0, F],
+                                           torch.zeros((n * C, 1), dtype=torch.int32, device=dev), RTc, Kc, light, H, W, 0.5, near)
+    z_r, face = z_r.view(n, C, H, W), face.view(n, C, H, W).long()
+    pair = face >= 0
+    xs, ys = torch.arange(W, device=dev), torch.arange(H, device=dev)
+    if window is not None:
+        w = torch.as_tensor(window).to(dev).long()
+        inside = ((ys[None, :, None] >= w[:, 1, None, None]) & (ys[None, :, None] <= w[:, 3, None, None])
+                  & (xs[None, None, :] >= w[:, 0, None, None]) & (xs[None, None, :] <= w[:, 2, None, None]))
+        pair = pair & inside[:, None]
+    z_o = depth.view(-1, 1, H, W).expand(n, C, H, W)
+    pair = pair & (z_o > 0) & ((z_o - z_r).abs() <= torch.tensor(np.float32(reject), device=dev))
+    vd = verts.double()
+    tri = vd[faces.long()[face.clamp_min(0)]]                              # [n,C,H,W,3,3]
+    a, e1, e2 = tri[..., 0, :], tri[..., 1, :] - tri[..., 0, :], tri[..., 2, :] - tri[..., 0, :]
+    m = torch.cross(e1, e2, dim=-1)
+    mm = (m * m).sum(-1)
+    pair = pair & (mm > 0)
+    nrm = m / mm.clamp_min(1e-300).sqrt()[..., None]
+    zo = torch.where(pair, z_o, torch.zeros_like(z_o)).double()
+    Kn = K.expand(n, 3, 3)
+    fx, fy, cx, cy = (Kn[:, i, j].view(n, 1, 1, 1) for i, j in ((0, 0), (1, 1), (0, 2), (1, 2)))
+    o = torch.stack([zo * (xs.double().view(1, 1, 1, W) - cx) / fx, zo * (ys.double().view(1, 1, H, 1) - cy) / fy, zo], dim=-1)
+    R, t = RT[..., :3].double(), RT[..., 3].double()
+    if min_cos > 0.0:
+        q = torch.einsum("ncij,nchwj->nchwi", R, nrm)
+        pair = pair & ~((q * o).sum(-1).abs() < float(min_cos) * (o * o).sum(-1).sqrt())
+    x = torch.einsum("ncji,nchwj->nchwi", R, o - t[:, :, None, None, :])
+    r = (nrm * (x - a)).sum(-1)
+    ar = r.abs()
+    h = float(huber or 0.0)
+    wt = torch.where(ar <= h, torch.ones_like(ar), h / ar.clamp_min(1e-300)) if h > 0.0 else torch.ones_like(ar)
+    wt = torch.where(pair, wt, torch.zeros_like(wt))
+    J = torch.cat([torch.cross(x, nrm, dim=-1), nrm], dim=-1)
+    sums = []
+    for p in range(6):
+        sums += [(wt * J[..., p] * J[..., q]).sum(dim=(2, 3)) for q in range(p, 6)]
+    sums += [(wt * J[..., p] * r).sum(dim=(2, 3)) for p in range(6)]
+    sums += [wt.sum(dim=(2, 3)), (wt * (x * x).sum(-1)).sum(dim=(2, 3)), torch.where(pair, ar, torch.zeros_like(ar)).sum(dim=(2, 3))]
+    return dict(pairs=pair.sum(dim=(2, 3)).to(torch.int32), sums=torch.stack(sums, dim=-1))

@@ -119,7 +119,12 @@ def build_parser():
                    help="test, --pose-verify: the depth agreement tolerance in metres")
     p.add_argument("--verify-candidates", dest="verify_candidates", type=str, default="kabsch,ransac,kabsch+icp,ransac+icp",
                    help="test, --pose-verify: comma-separated candidates out of kabsch, ransac, kabsch+icp, ransac+icp "
-                        "(+icp runs --icp-iters iterations, 10 when that is 0)")
+                        "(+icp runs --icp-iters iterations, 10 when that is 0), each optionally followed by +depth: the candidate "
+                        "refined against the depth frame by render-and-compare (pose.refine_poses_depth), e.g. kabsch+depth")
+    p.add_argument("--depth-refine-iters", dest="depth_refine_iters", type=int, default=5, metavar="K",
+                   help="test, --pose-verify: Gauss-Newton iterations of a +depth candidate")
+    p.add_argument("--depth-refine-reject", dest="depth_refine_reject", type=float, default=0.01, metavar="M",
+                   help="test, --pose-verify: a +depth candidate pairs a pixel whose observed depth lies within M metres of the rendered one")
     p.add_argument("--objects-across-gpus", action="store_true",
                    help="train: the dataset's objects are independent jobs (train_ycb.sh:3-9 runs them one after the other): rank r of a "
                         "torch.distributed.run launch trains objects r, r + world, ... on its own GPU as single-process jobs -- no process "
@@ -567,9 +572,10 @@ def test(args):
             raise SystemExit("train_lm test: --pose-verify needs -data rendered: the other batches carry no depth frame and no mesh "
                              "faces (use pose.verify_poses from Python)")
         verify_names = tuple(k for k in args.verify_candidates.split(",") if k)
-        if not verify_names or set(verify_names) - set(pose.VERIFY_CANDIDATES) or len(set(verify_names)) != len(verify_names):
-            raise SystemExit("train_lm test: --verify-candidates takes distinct names out of %s, got %r" %
-                             (", ".join(pose.VERIFY_CANDIDATES), args.verify_candidates))
+        allowed = pose.VERIFY_CANDIDATES + tuple(k + "+depth" for k in pose.VERIFY_CANDIDATES)
+        if not verify_names or set(verify_names) - set(allowed) or len(set(verify_names)) != len(verify_names):
+            raise SystemExit("train_lm test: --verify-candidates takes distinct names out of %s, each optionally followed by +depth, "
+                             "got %r" % (", ".join(pose.VERIFY_CANDIDATES), args.verify_candidates))
         if args.graph_batch1:
             raise SystemExit("train_lm test: --pose-verify does not go with --graph-batch1")
     ds = dataset_config(args.dataset_name)
@@ -653,7 +659,8 @@ def test(args):
                 fd = cu["frame_depth"]
                 verify = dict(verts=verify_mesh[0], faces=verify_mesh[1], depth=fd, K=cu["K"], delta=args.verify_delta,
                               window=pose.boxes_to_windows(cu["bbox"], fd.shape[-2], fd.shape[-1]), candidates=verify_names,
-                              icp_iters=args.icp_iters or 10)
+                              icp_iters=args.icp_iters or 10, depth_iters=getattr(args, "depth_refine_iters", 5),
+                              depth_opts=dict(reject=getattr(args, "depth_refine_reject", 0.01)))
                 out = infer.run_multi_object(model_dict, cu, cls, **dict(pose_kw, verify=verify))
                 out["score"] = out["verify_score"].float()                 # the csv score
             else:

@@ -1082,6 +1082,49 @@ int gdm_pose_verify_hip(const void* verts, int verts_f64, const int32_t* faces, 
                         const float* depth_obs, int obs_per_instance, const int32_t* window, const uint8_t* cand_valid, int n, int C,
                         int V, int F, int H, int W, double near, double delta, double front_weight, int min_px, int32_t* counts,
                         double* score, int32_t* best, void* stream);
+/* Pose candidates refined against the observed depth by render-and-compare (pose.refine_poses_depth_numpy restates it
+ * operation for operation).  Where verification only counts, this entry moves a pose towards the frame: `iters` Gauss-Newton
+ * iterations on the point-to-plane residual between every agreeing depth pixel and the mesh face drawn at it.  Parity with any other
+ * depth refiner is NOT claimed; reject, huber and min_cos are the defaults of a definition, not tuned values.  verts, faces, K,
+ * depth_obs, window, cand_valid, n, C, V, F, H, W, near as for gdm_pose_verify_hip; RT_in f64[n,C,3,4] (object to camera).
+ * THE DEPTH REFINEMENT RULE, one iteration of candidate c of instance i whose status is 0, with pose [R | t] (fp64):
+ *   rasterise   the mesh under [R | t] by THE PIXEL RULE above (set-up with the frame's H, W) into the window clamped to the frame;
+ *               per pixel the minimum of the 64-bit key (fp32 depth bits << 32) | face index: the nearest face, the lowest face index
+ *               among equal depth bits (the key of gdm_render_frames_hip, here in LDS).  z_r = the key's depth.
+ *   pair        a drawn pixel (col u, row v) with z_o = depth_obs[v, u] pairs when, in fp32 single operations, z_o > 0 and
+ *               |z_o - z_r| <= (float) reject.  (What verification calls FRONT, BEHIND or NODEPTH pulls on nothing.)
+ *   terms       fp64, the library is built with -ffp-contract=off; zo = (double) z_o:
+ *               o = ((zo (u - cx)) / fx, (zo (v - cy)) / fy, zo);  d = o - t;  x_j = (R_0j d_0 + R_1j d_1) + R_2j d_2  (x = R^T (o - t))
+ *               v0, v1, v2 = the face's vertices in stored order, widened from fp32 where the mesh is fp32; e1 = v1 - v0, e2 = v2 - v0;
+ *               m = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x);  mm = (mx mx + my my) + mz mz; no pair unless mm > 0;
+ *               n = m / sqrt(mm) (the sign of n cancels in every sum: no orientation step)
+ *               grazing gate, only with min_cos > 0: q_i = (R_i0 nx + R_i1 ny) + R_i2 nz; the pair is dropped when
+ *               |(q0 ox + q1 oy) + q2 oz| < min_cos sqrt((ox ox + oy oy) + oz oz)
+ *               r = (nx (x0 - v0x) + ny (x1 - v0y)) + nz (x2 - v0z);  w = 1, or huber / |r| when huber > 0 and |r| > huber
+ *               J = (x1 nz - x2 ny, x2 nx - x0 nz, x0 ny - x1 nx, nx, ny, nz)
+ *   sums        the 29 sums of gdm_icp_plane_update_hip -- A += (w J_p) J_q for p <= q (21), g_p += (w J_p) r (6), S += w,
+ *               L2 += w ((x0 x0 + x1 x1) + x2 x2) --, E += |r| and the integer pair count, per (tile of the window) in a fixed order,
+ *               then over the window's tiles in tile index order.  No floating-point atomics: reproducible bit for bit.
+ *   solve       pairs < max(min_px, 6): status 2.  Otherwise the solve, the degeneracy test (a scaled pivot below pivot_min: status 3)
+ *               and the composition R <- R exp([omega]x)^T, t <- t - R_new v of gdm_icp_plane_update_hip, the same statements.
+ *   stop        iters += 1; mean = E / pairs; |err - mean| < tolerance: status 1; err <- mean  (err starts at 0).
+ * The pose stays fp64 from iteration to iteration.  status i32[n,C]: 0 still active after `iters` iterations, 1 converged by the stop
+ * rule, 2 starved, 3 degenerate, 4 cand_valid == 0 on entry; 2, 3 and 4 leave the pose of that moment as it is (bit-identical to
+ * RT_in when they arise in the first iteration), and a candidate whose status is not 0 is not touched again.  OUTPUTS RT f64[n,C,3,4],
+ * status, iters_out i32[n,C] (iterations applied), err f64[n,C] (mean |r| of the last applied iteration, 0 before one),
+ * pairs i32[n,C] (of the last iteration evaluated).
+ * workspace: gdm_pose_refine_depth_workspace_bytes(n, C, H, W) = n C ceil(W / 64) ceil(H / 64) 32 doubles (one row of 30 sums, the
+ * pair count and a zero per tile a window can have; 0 for arguments the entry refuses), 8-byte aligned.  1 + 2 iters launches; no
+ * allocation, no host read, no memset node: the call captures in a hipGraph.
+ * LIMITS (refused beyond, before any HIP call): those of gdm_pose_verify_hip; iters in [1, 64]; reject > 0 and finite in fp32;
+ * huber >= 0 (0: off); 0 <= min_cos < 1 (0: off); min_px >= 0; tolerance >= 0; pivot_min > 0. */
+size_t gdm_pose_refine_depth_workspace_bytes(int n, int C, int H, int W);
+int gdm_pose_refine_depth_hip(const void* verts, int verts_f64, const int32_t* faces, const double* RT_in, const double* K,
+                              int k_per_instance, const float* depth_obs, int obs_per_instance, const int32_t* window,
+                              const uint8_t* cand_valid, int n, int C, int V, int F, int H, int W, double near, int iters, double reject,
+                              double huber, double min_cos, int min_px, double tolerance, double pivot_min, void* workspace,
+                              size_t workspace_bytes, double* RT, int32_t* status, int32_t* iters_out, double* err, int32_t* pairs,
+                              void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Training frames from meshes: colour, depth, instance mask, face ids and per-slot visibility statistics of n frames of S posed
