@@ -7,10 +7,12 @@
 //                          (tile, symmetry) on the bit pattern of the non-negative double (ordered like the value; a NaN stays on top).
 //                          The only temporary is err[2][n][S].
 //   sym_min_kernel         one wave per (error, instance): the minimum over the symmetries, the first one on a tie.
-//   raster_kernel          one thread per (instance, triangle) by the pixel rule of include/gdm.h (gdm_raster.h holds its code, shared
-//                          with gdm_render.hip); a triangle whose clamped box holds more than kSmallBox pixels is drawn by its whole
-//                          wave striding over the box.  Unsigned atomicMin on the fp32 bit pattern: positive floats order like their
-//                          bits and a minimum does not depend on arrival order.
+//   raster_kernel          one thread per (instance, triangle) by the pixel rule of include/gdm.h.  gdm_raster.h holds its code and the
+//                          drawing loop (draw_wave_triangles: a triangle whose clamped box holds more than kSmallBox pixels is drawn
+//                          by its whole wave striding over the box; the instance index travels with it) for every rasteriser of the
+//                          library; pixel_rule.py restates the rule for evaluation.render_depth_numpy.  Unsigned atomicMin on the
+//                          fp32 bit pattern (shade): positive floats order like their bits and a minimum does not depend on arrival
+//                          order.
 //   vsd_counts_kernel      distance images, visibility masks and the pixel costs in one pass over the three depth images; counts are
 //                          summed per thread, per wave, per workgroup, then one integer atomicAdd per workgroup and counter.
 // No allocation and no host read in any entry point: they capture in a hipGraph.  Accumulators are cleared by fill_u32_kernel, not by
@@ -156,13 +158,6 @@ __global__ __launch_bounds__(64) void sym_min_kernel(const double* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // rasteriser
 
-__device__ __forceinline__ void shade(const TriSetup& s, int px, int py, unsigned* __restrict__ zb, int W)
-{
-    long long w0, w1, w2;
-    if (!edge_values(s, px, py, w0, w1, w2)) return;
-    atomicMin(&zb[(long)py * W + px], __float_as_uint(pixel_depth(s, w0, w1, w2)));
-}
-
 template <typename VT>
 __global__ __launch_bounds__(kThreads) void raster_kernel(const VT* __restrict__ verts, const int32_t* __restrict__ faces,
                                                           const double* __restrict__ RT, const double* __restrict__ Kmat,
@@ -170,7 +165,6 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(const VT* __restrict__
                                                           unsigned* __restrict__ zbuf)
 {
     const long gid = (long)blockIdx.x * kThreads + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     TriSetup s = {};
     bool valid = gid < (long)n * F;
     int b = 0;
@@ -181,24 +175,9 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(const VT* __restrict__
         valid = tri_setup(verts, V, faces[(long)f * 3], faces[(long)f * 3 + 1], faces[(long)f * 3 + 2], RT + (long)b * 12,
                           Kmat + (k_per_instance ? (long)b * 9 : 0), near, H, W, s, swapped);
     }
-    const long box = valid ? (long)(s.px1 - s.px0 + 1) * (s.py1 - s.py0 + 1) : 0;
-    if (valid && box <= kSmallBox) {
-        unsigned* zb = zbuf + (long)b * H * W;
-        for (int py = s.py0; py <= s.py1; ++py)
-            for (int px = s.px0; px <= s.px1; ++px) shade(s, px, py, zb, W);
-    }
-    // the large triangles of the wave, one after the other, by all 64 lanes (every lane of the wave reaches this point)
-    u64 big = __ballot(valid && box > kSmallBox);
-    while (big) {
-        const int src = __ffsll((long long)big) - 1;
-        big &= big - 1;
-        const TriSetup c = tri_from_lane(s, src);
-        const int cb = __shfl(b, src, 64);
-        unsigned* zb = zbuf + (long)cb * H * W;
-        const int bw = c.px1 - c.px0 + 1;
-        const long cnt = (long)bw * (c.py1 - c.py0 + 1);
-        for (long i = lane; i < cnt; i += 64) shade(c, c.px0 + (int)(i % bw), c.py0 + (int)(i / bw), zb, W);
-    }
+    draw_wave_triangles(s, valid, b, [=](int cb, int px, int py, unsigned bits) {
+        shade(&zbuf[(long)cb * H * W + (long)py * W + px], bits, 0u);
+    });
 }
 
 __global__ __launch_bounds__(kThreads) void fill_u32_kernel(unsigned* __restrict__ p, long count, unsigned v)

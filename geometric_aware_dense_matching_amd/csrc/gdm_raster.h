@@ -1,6 +1,9 @@
-// The one copy of the pixel rule of include/gdm.h (gdm_render_depth_hip), shared by the depth rasteriser of
-// gdm_bop.hip and the frame renderer of gdm_render.hip: fp64 vertex transform and projection, discard, snapping to 1/256 px, int64
-// edge functions with the top-left rule, the winding normalised by the sign of the snapped area, the pixel box clamped to the image.
+// The one copy of the pixel rule of include/gdm.h (gdm_render_depth_hip) and of the wave's drawing loop, shared by the
+// depth rasteriser of gdm_bop.hip, the frame renderer of gdm_render.hip and, through gdm_raster_tile.h, the LDS tiles of gdm_verify.hip
+// and gdm_refine.hip: fp64 vertex transform and projection, discard, snapping to 1/256 px, int64 edge functions with the top-left
+// rule, the winding normalised by the sign of the snapped area, the pixel box clamped to the image (tri_setup); then
+// draw_wave_triangles, which walks a small box with the owning lane and draws a larger one with all 64 lanes, and shade, the
+// atomicMin of the depth key that every z-buffer of the family keeps, in LDS or in memory.
 #pragma once
 #include "gdm_common.h"
 
@@ -98,4 +101,67 @@ __device__ __forceinline__ TriSetup tri_from_lane(const TriSetup& s, int src)
     c.px0 = __shfl(s.px0, src, 64); c.px1 = __shfl(s.px1, src, 64);
     c.py0 = __shfl(s.py0, src, 64); c.py1 = __shfl(s.py1, src, 64);
     return c;
+}
+
+// A small plain-data payload of lane `src`, for the whole wave: one __shfl per 32-bit word.
+struct NoPayload {};
+
+template <typename P>
+__device__ __forceinline__ P payload_from_lane(const P& p, int src)
+{
+    if constexpr (std::is_empty<P>::value) {
+        return p;
+    } else {
+        static_assert(std::is_trivially_copyable<P>::value && sizeof(P) % sizeof(int) == 0, "a payload is whole words of plain data");
+        int w[sizeof(P) / sizeof(int)];
+        __builtin_memcpy(w, &p, sizeof(P));
+#pragma unroll
+        for (unsigned k = 0; k < sizeof(P) / sizeof(int); ++k) w[k] = __shfl(w[k], src, 64);
+        P c;
+        __builtin_memcpy(&c, w, sizeof(P));
+        return c;
+    }
+}
+
+// The drawing loop of a wave.  Every lane of the wave must call it (it ballots), each with the set-up of its own triangle, `valid`
+// false where it has none, and the payload its sink needs to find the buffer and name the face.  A box of at most kSmallBox pixels is
+// walked by the owning lane; the larger ones are drawn one after the other by all 64 lanes, set-up and payload broadcast from the
+// source lane once per triangle.  sink(payload, px, py, bits) gets every covered pixel and the fp32 bits of its depth.  A clamped box
+// holds at most 16384^2 = 2^28 pixels (the entries refuse a larger H or W): int counts it.
+template <typename P, typename Sink>
+__device__ __forceinline__ void draw_wave_triangles(const TriSetup& s, bool valid, const P& payload, Sink sink)
+{
+    const int lane = threadIdx.x & 63;
+    const int box = valid ? (s.px1 - s.px0 + 1) * (s.py1 - s.py0 + 1) : 0;
+    long long w0, w1, w2;
+    if (valid && box <= kSmallBox) {
+        for (int py = s.py0; py <= s.py1; ++py)
+            for (int px = s.px0; px <= s.px1; ++px)
+                if (edge_values(s, px, py, w0, w1, w2)) sink(payload, px, py, __float_as_uint(pixel_depth(s, w0, w1, w2)));
+    }
+    unsigned long long big = __ballot(valid && box > kSmallBox);
+    while (big) {
+        const int src = __ffsll((long long)big) - 1;
+        big &= big - 1;
+        const TriSetup c = tri_from_lane(s, src);
+        const P cp = payload_from_lane(payload, src);
+        const int bw = c.px1 - c.px0 + 1;
+        const int cnt = bw * (c.py1 - c.py0 + 1);
+        for (int k = lane; k < cnt; k += 64) {
+            const int px = c.px0 + k % bw, py = c.py0 + k / bw;
+            if (edge_values(c, px, py, w0, w1, w2)) sink(cp, px, py, __float_as_uint(pixel_depth(c, w0, w1, w2)));
+        }
+    }
+}
+
+// The z-buffer's one operation: the unsigned minimum of the key at p, in LDS or in memory.  A 32-bit key is the fp32 depth bits
+// (positive floats order like their bits); a 64-bit key is bits << 32 | face, so equal depths go to the lower face.  A minimum over
+// integers does not depend on arrival order.
+template <typename K>
+__device__ __forceinline__ void shade(K* p, unsigned bits, unsigned face)
+{
+    if constexpr (sizeof(K) == sizeof(unsigned))
+        atomicMin(p, bits);
+    else
+        atomicMin(p, ((K)bits << 32) | face);
 }

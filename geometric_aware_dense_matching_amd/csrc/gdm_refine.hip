@@ -1,57 +1,34 @@
 // Pose refinement against the observed depth by render-and-compare, gfx950 (gdm_pose_refine_depth_hip; include/gdm.h THE DEPTH
-// REFINEMENT RULE; pose.refine_poses_depth_numpy restates it operation for operation).  Coverage and depth are the
-// pixel rule of gdm_render_depth_hip from its one copy in gdm_raster.h; the solve is gdm_icp_plane_solve.inc, unchanged.
+// REFINEMENT RULE; pose.refine_poses_depth_numpy restates it operation for operation, drawing with pixel_rule.py).
+// Coverage and depth are the pixel rule of gdm_render_depth_hip from its one copy in gdm_raster.h; the window clamp, the tile of a
+// workgroup and the tile's z-buffer are gdm_raster_tile.h, shared with gdm_verify.hip; the solve is gdm_icp_plane_solve.inc.
 //   depth_refine_init_kernel    one thread per (instance, candidate): the pose copied to the output, status 0 or 4 (cand_valid == 0),
 //                               iters, err and pairs cleared -- a kernel, not a memset node (see gdm_bop.hip).
 //   depth_refine_accum_kernel   one workgroup per (instance, candidate, tile of the instance's window), built like pose_verify_kernel:
-//                               clear the LDS tile, walk all F faces 256 at a time (small boxes by the owning lane, larger ones by the
-//                               whole wave).  The tile holds 64-bit keys (fp32 depth bits << 32 | face), 32 KiB, one LDS atomicMin
-//                               per covered pixel: the nearest face, the lower index among equal depths, as gdm_render.hip keeps it in
-//                               memory.  After the barrier every thread forms the fp64 terms of its pixels; the 30 sums and the pair
-//                               count are reduced in a fixed order (butterfly in each wave, then waves 0..3) and 32 threads store the
-//                               row partial[i, c, tile, 0..31] (the sums, the count, a zero).  No floating-point atomic anywhere: the
+//                               draw_tile clears the LDS tile and walks all F faces into it 256 at a time.  The tile holds 64-bit
+//                               keys (fp32 depth bits << 32 | face), 32 KiB, one LDS atomicMin per covered pixel: the nearest face,
+//                               the lower index among equal depths, as gdm_render.hip keeps it in memory.  After the barrier every
+//                               thread forms the fp64 terms of its pixels; the 30 sums and the pair count are reduced in a fixed
+//                               order (butterfly in each wave, then waves 0..3) and 32 threads store the row
+//                               partial[i, c, tile, 0..31] (the sums, the count, a zero).  No floating-point atomic anywhere: the
 //                               result does not depend on arrival order.
-//   depth_refine_solve_kernel   one thread per (instance, candidate): clamps the window the same way, adds the rows of exactly the
-//                               tiles that window has in tile index order (a row no workgroup wrote is never read), applies the
-//                               starved / degenerate / stop logic and writes pose, status, iters, err, pairs.  The pose stays fp64.
+//   depth_refine_solve_kernel   one thread per (instance, candidate): clamps the window with the same clamped_window, adds the
+//                               rows of exactly the tiles that window has in tile index order (a row no workgroup wrote is never
+//                               read), applies the starved / degenerate / stop logic and writes pose, status, iters, err, pairs.
+//                               The pose stays fp64.
 // The entry enqueues the init kernel and `iters` pairs of the other two.  A candidate whose status is no longer 0 costs its
 // workgroups one load: they return before touching LDS.  No allocation, no host read: the call captures in a hipGraph.
 #include "gdm_common.h"
-#include "gdm_raster.h"
+#include "gdm_raster_tile.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kTile = 64;                                                  // pixels per tile side; kTile^2 keys of LDS
 constexpr unsigned kInfBits = 0x7f800000u;
 constexpr int kSums = 30;                                                  // A (21), g (6), S, L2, E
 constexpr int kRow = 32;                                                   // doubles per partial row: the sums, the pair count, a 0
 
 typedef unsigned long long u64;
-
-struct TileBox { int x0, y0, x1, y1; };                                    // inclusive, frame pixels
-
-struct Win { int x0, y0, x1, y1; };
-
-__device__ __forceinline__ Win clamped_window(const int32_t* __restrict__ window, int i, int H, int W)
-{
-    Win w = {0, 0, W - 1, H - 1};
-    if (window) {
-        w.x0 = max(window[(long)i * 4], 0);
-        w.y0 = max(window[(long)i * 4 + 1], 0);
-        w.x1 = min(window[(long)i * 4 + 2], W - 1);
-        w.y1 = min(window[(long)i * 4 + 3], H - 1);
-    }
-    return w;
-}
-
-__device__ __forceinline__ void shade_key(const TriSetup& s, int px, int py, const TileBox& t, unsigned face, u64* zt)
-{
-    long long w0, w1, w2;
-    if (!edge_values(s, px, py, w0, w1, w2)) return;
-    const u64 key = ((u64)__float_as_uint(pixel_depth(s, w0, w1, w2)) << 32) | face;
-    atomicMin(&zt[(py - t.y0) * kTile + (px - t.x0)], key);
-}
 
 __global__ __launch_bounds__(kThreads) void depth_refine_init_kernel(const double* __restrict__ RT_in, const uint8_t* __restrict__ cand_valid,
                                                                      long count, double* __restrict__ RT, int32_t* __restrict__ status,
@@ -81,53 +58,12 @@ __global__ __launch_bounds__(kThreads) void depth_refine_accum_kernel(const VT* 
     __shared__ int cred[4];
     const int i = blockIdx.z, c = blockIdx.y;
     if (status[(long)i * C + c] != 0) return;                              // frozen: block-uniform, before any LDS access
-    const int tiles_x = (W + kTile - 1) / kTile;
-    const int tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
-    const Win w = clamped_window(window, i, H, W);
-    if (w.x0 > w.x1 || w.y0 > w.y1) return;
     TileBox t;
-    t.x0 = w.x0 + tile_x * kTile;                                          // w.x0 < W <= 16384: no overflow
-    t.y0 = w.y0 + tile_y * kTile;
-    if (t.x0 > w.x1 || t.y0 > w.y1) return;
-    t.x1 = min(t.x0 + kTile - 1, w.x1);
-    t.y1 = min(t.y0 + kTile - 1, w.y1);
-
-    for (int k = threadIdx.x; k < kTile * kTile; k += kThreads) zt[k] = ~0ull;
-    __syncthreads();
-
+    if (!tile_of_block(clamped_window(window, i, H, W), blockIdx.x, W, t)) return;
     const int lane = threadIdx.x & 63;
     const double* rt = RT + ((long)i * C + c) * 12;
     const double* kk = Kmat + (k_per_instance ? (long)i * 9 : 0);
-    for (int base = 0; base < F; base += kThreads) {                       // uniform trip count: every lane reaches the ballot
-        const int f = base + (int)threadIdx.x;
-        TriSetup s = {};
-        bool valid = f < F;
-        if (valid) {
-            bool swapped;
-            valid = tri_setup(verts, V, faces[(long)f * 3], faces[(long)f * 3 + 1], faces[(long)f * 3 + 2], rt, kk, near, H, W, s, swapped);
-        }
-        if (valid) {
-            s.px0 = max(s.px0, t.x0); s.px1 = min(s.px1, t.x1);
-            s.py0 = max(s.py0, t.y0); s.py1 = min(s.py1, t.y1);
-            valid = s.px0 <= s.px1 && s.py0 <= s.py1;
-        }
-        const int box = valid ? (s.px1 - s.px0 + 1) * (s.py1 - s.py0 + 1) : 0;      // at most kTile^2
-        if (valid && box <= kSmallBox) {
-            for (int py = s.py0; py <= s.py1; ++py)
-                for (int px = s.px0; px <= s.px1; ++px) shade_key(s, px, py, t, (unsigned)f, zt);
-        }
-        u64 big = __ballot(valid && box > kSmallBox);
-        while (big) {
-            const int src = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const TriSetup b = tri_from_lane(s, src);
-            const unsigned bf = (unsigned)(base + (int)(threadIdx.x & ~63u) + src);
-            const int bw = b.px1 - b.px0 + 1;
-            const int cnt = bw * (b.py1 - b.py0 + 1);
-            for (int k = lane; k < cnt; k += 64) shade_key(b, b.px0 + k % bw, b.py0 + k / bw, t, bf, zt);
-        }
-    }
-    __syncthreads();
+    draw_tile<kThreads>(zt, t, verts, faces, V, F, rt, kk, near, H, W);
 
     // THE DEPTH REFINEMENT RULE: the gate in fp32, the terms in fp64
     const float* obs = depth_obs + (obs_per_instance ? (long)i * H * W : 0L);
@@ -209,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void depth_refine_accum_kernel(const VT* 
     }
     __syncthreads();
     if (threadIdx.x < kRow) {
-        const int tiles = tiles_x * ((H + kTile - 1) / kTile);
+        const int tiles = ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile);
         double* row = partial + (((long)i * C + c) * tiles + blockIdx.x) * kRow;
         const int a = threadIdx.x;
         row[a] = a < kSums ? ((red[0][a] + red[1][a]) + red[2][a]) + red[3][a] : a == kSums ? (double)(((cred[0] + cred[1]) + cred[2]) + cred[3]) : 0.0;
@@ -256,18 +192,12 @@ __global__ __launch_bounds__(kThreads) void depth_refine_solve_kernel(const doub
     err[k] = mean;
 }
 
-bool refine_shape_ok(int n, int C, int H, int W)
-{
-    if (n < 1 || n > 65535 || C < 1 || C > 65535 || H < 1 || H > 16384 || W < 1 || W > 16384) return false;
-    if ((long)H * W > (1L << 22)) return false;
-    return (long)gdm_cdiv(W, kTile) * gdm_cdiv(H, kTile) * n * C <= (1L << 23);
-}
-
 } // namespace
 
 extern "C" size_t gdm_pose_refine_depth_workspace_bytes(int n, int C, int H, int W)
 {
-    if (!refine_shape_ok(n, C, H, W)) return 0;
+    // the shape limits alone: the other arguments stand in with values that pass
+    if (tile_entry_check("gdm_pose_refine_depth_workspace_bytes", "", n, C, 1, 1, H, W, 0.0, 0, 0, 0)) return 0;
     return (size_t)gdm_cdiv(W, kTile) * gdm_cdiv(H, kTile) * n * C * kRow * sizeof(double);
 }
 
@@ -280,13 +210,8 @@ extern "C" int gdm_pose_refine_depth_hip(const void* verts, int verts_f64, const
 {
     const char* me = "gdm_pose_refine_depth_hip";
     GDM_CHECK_ARG(verts && faces && RT_in && K && depth_obs && workspace && RT && status && iters_out && err && pairs, "%s: NULL pointer", me);
-    GDM_CHECK_ARG(n >= 1 && n <= 65535 && C >= 1 && C <= 65535, "%s: n=%d C=%d not in [1, 65535]", me, n, C);
-    GDM_CHECK_ARG(V >= 1 && F >= 1, "%s: V=%d F=%d must be positive", me, V, F);
-    GDM_CHECK_ARG(H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "%s: H=%d W=%d not in [1, 16384]", me, H, W);
-    GDM_CHECK_ARG((long)H * W <= (1L << 22), "%s: H=%d W=%d: more than 2^22 pixels", me, H, W);
-    const long tiles = (long)gdm_cdiv(W, kTile) * gdm_cdiv(H, kTile);       // at most 256 * 256
-    GDM_CHECK_ARG(tiles * n * C <= (1L << 23), "%s: n=%d C=%d too large for H=%d W=%d (tiles n C <= 2^23)", me, n, C, H, W);
-    GDM_CHECK_ARG(near >= 0.0, "%s: near=%g must be >= 0", me, near);
+    int rc = tile_entry_check(me, "", n, C, V, F, H, W, near, k_per_instance, obs_per_instance, verts_f64);
+    if (rc) return rc;
     GDM_CHECK_ARG(iters >= 1 && iters <= 64, "%s: iters=%d not in [1, 64]", me, iters);
     GDM_CHECK_ARG(reject > 0.0 && reject <= 3.0e38 && (float)reject > 0.f, "%s: reject=%g must be positive and finite in fp32", me, reject);
     GDM_CHECK_ARG(huber >= 0.0, "%s: huber=%g must be >= 0 (0: off)", me, huber);
@@ -294,9 +219,6 @@ extern "C" int gdm_pose_refine_depth_hip(const void* verts, int verts_f64, const
     GDM_CHECK_ARG(min_px >= 0, "%s: min_px=%d must be >= 0", me, min_px);
     GDM_CHECK_ARG(tolerance >= 0.0, "%s: tolerance=%g must be >= 0", me, tolerance);
     GDM_CHECK_ARG(pivot_min > 0.0, "%s: pivot_min=%g must be positive", me, pivot_min);
-    GDM_CHECK_ARG(k_per_instance == 0 || k_per_instance == 1, "%s: k_per_instance=%d must be 0 or 1", me, k_per_instance);
-    GDM_CHECK_ARG(obs_per_instance == 0 || obs_per_instance == 1, "%s: obs_per_instance=%d must be 0 or 1", me, obs_per_instance);
-    GDM_CHECK_ARG(verts_f64 == 0 || verts_f64 == 1, "%s: verts_f64=%d must be 0 or 1", me, verts_f64);
     const size_t need = gdm_pose_refine_depth_workspace_bytes(n, C, H, W);
     GDM_CHECK_ARG(workspace_bytes >= need, "%s: workspace_bytes=%zu < %zu (gdm_pose_refine_depth_workspace_bytes)", me, workspace_bytes, need);
     GDM_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", me);
@@ -304,9 +226,9 @@ extern "C" int gdm_pose_refine_depth_hip(const void* verts, int verts_f64, const
     const long count = (long)n * C;
     const dim3 per_cand((unsigned)gdm_cdiv(count, kThreads));
     hipLaunchKernelGGL(depth_refine_init_kernel, per_cand, dim3(kThreads), 0, s, RT_in, cand_valid, count, RT, status, iters_out, err, pairs);
-    int rc = gdm_launch_status("depth_refine_init_kernel");
+    rc = gdm_launch_status("depth_refine_init_kernel");
     if (rc) return rc;
-    const dim3 grid((unsigned)tiles, C, n);
+    const dim3 grid((unsigned)(gdm_cdiv(W, kTile) * gdm_cdiv(H, kTile)), C, n);
     const float reject_f = (float)reject;
     double* partial = (double*)workspace;
     for (int it = 0; it < iters; ++it) {

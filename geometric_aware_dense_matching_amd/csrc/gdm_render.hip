@@ -1,11 +1,12 @@
 // Training frames from triangle meshes on the device, gfx950: colour, depth, instance mask, face ids and the per-slot visibility
 // statistics of n frames of up to GDM_RENDER_MAX_SLOTS posed objects each, by the written rule of include/gdm.h
-// (gdm_render_frames_hip; render.render_frames_numpy restates it bit for bit).  Coverage and depth are the pixel rule
-// of gdm_render_depth_hip, from its one copy in gdm_raster.h.
+// (gdm_render_frames_hip; render.render_frames_numpy restates it bit for bit, drawing with pixel_rule.py).  Coverage
+// and depth are the pixel rule of gdm_render_depth_hip, from its one copy in gdm_raster.h, and so is the wave's drawing loop.
 //   clear_kernel     the slot layers to all-ones and the statistics to (0, 0, W, H, -1, -1).  A kernel, not hipMemsetAsync: see the
 //                    header comment of gdm_bop.hip for what the runtime's memset node did under graph replay.
-//   vis_kernel       one thread per (frame, slot, face of the slot's object); a triangle whose clamped box holds more than kSmallBox
-//                    pixels is drawn by its whole wave, as raster_kernel does.  Every covered pixel does ONE 64-bit unsigned atomicMin
+//   vis_kernel       one thread per (frame, slot, face of the slot's object), drawn by draw_wave_triangles of gdm_raster.h with the
+//                    payload (slot, face): a triangle whose clamped box holds more than kSmallBox pixels is drawn by its whole wave,
+//                    as raster_kernel does.  Every covered pixel does ONE 64-bit unsigned atomicMin
 //                    (global_atomic_umin_x2, no compare-and-swap loop) of (fp32 depth bits << 32 | global face id) into its slot's
 //                    layer: a minimum over integers does not depend on arrival order, and equal depths go to the lower face id.
 //   resolve_kernel   one thread per pixel: the winning slot (smallest depth bits, the lower slot on a tie), the set-up of the winning
@@ -35,12 +36,7 @@ __global__ __launch_bounds__(kThreads) void clear_kernel(u64* __restrict__ keys,
     }
 }
 
-__device__ __forceinline__ void shade_key(const TriSetup& s, int px, int py, u64* __restrict__ layer, int W, unsigned f)
-{
-    long long w0, w1, w2;
-    if (!edge_values(s, px, py, w0, w1, w2)) return;
-    atomicMin(&layer[(long)py * W + px], ((u64)__float_as_uint(pixel_depth(s, w0, w1, w2)) << 32) | f);
-}
+struct SlotFace { int slot, face; };                                       // b * S + s and the global face id
 
 template <typename VT>
 __global__ __launch_bounds__(kThreads) void vis_kernel(const VT* __restrict__ verts, const int32_t* __restrict__ faces,
@@ -49,7 +45,6 @@ __global__ __launch_bounds__(kThreads) void vis_kernel(const VT* __restrict__ ve
                                                        int n, int S, int Vt, int Fmax, int H, int W, double near, u64* __restrict__ keys)
 {
     const long gid = (long)blockIdx.x * kThreads + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     TriSetup s = {};
     bool valid = gid < (long)n * S * Fmax;
     long slot = 0;                                                         // b * S + s
@@ -70,25 +65,9 @@ __global__ __launch_bounds__(kThreads) void vis_kernel(const VT* __restrict__ ve
                               Kmat + (k_per_instance ? (long)b * 9 : 0), near, H, W, s, swapped);
         }
     }
-    const long box = valid ? (long)(s.px1 - s.px0 + 1) * (s.py1 - s.py0 + 1) : 0;
-    if (valid && box <= kSmallBox) {
-        u64* layer = keys + slot * H * W;
-        for (int py = s.py0; py <= s.py1; ++py)
-            for (int px = s.px0; px <= s.px1; ++px) shade_key(s, px, py, layer, W, (unsigned)f);
-    }
-    // the large triangles of the wave, one after the other, by all 64 lanes (every lane of the wave reaches this point)
-    u64 big = __ballot(valid && box > kSmallBox);
-    while (big) {
-        const int src = __ffsll((long long)big) - 1;
-        big &= big - 1;
-        const TriSetup c = tri_from_lane(s, src);
-        const long cslot = __shfl(slot, src, 64);
-        const unsigned cf = (unsigned)__shfl(f, src, 64);
-        u64* layer = keys + cslot * H * W;
-        const int bw = c.px1 - c.px0 + 1;
-        const long cnt = (long)bw * (c.py1 - c.py0 + 1);
-        for (long i = lane; i < cnt; i += 64) shade_key(c, c.px0 + (int)(i % bw), c.py0 + (int)(i / bw), layer, W, cf);
-    }
+    draw_wave_triangles(s, valid, SlotFace{(int)slot, f}, [=](SlotFace c, int px, int py, unsigned bits) {       // slot < n S <= 2^30
+        shade(&keys[(long)c.slot * H * W + (long)py * W + px], bits, (unsigned)c.face);
+    });
 }
 
 __device__ __forceinline__ int wave_min_i32(int v)

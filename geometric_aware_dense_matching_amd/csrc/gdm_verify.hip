@@ -1,27 +1,23 @@
 // Pose verification against the observed depth, gfx950 (gdm_pose_verify_hip; include/gdm.h THE VERIFICATION RULE; DESIGN.md 6q;
-// pose.verify_poses_numpy restates it bit for bit).  Coverage and depth are the pixel rule of gdm_render_depth_hip, from its one
-// copy in gdm_raster.h.
+// pose.verify_poses_numpy restates it bit for bit on evaluation.render_depth_numpy, which draws with pixel_rule.py).  Coverage and
+// depth are the pixel rule of gdm_render_depth_hip, from its one copy in gdm_raster.h; the window clamp, the tile of a workgroup, the
+// tile's z-buffer and the refusals shared with gdm_refine.hip are gdm_raster_tile.h.
 //   pose_verify_kernel     one workgroup per (instance, candidate, tile of the instance's window).  A tile is kTile x kTile pixels
-//                          counted from the window's clamped corner, and its z-buffer lives in LDS: kTile = 64 is 16 KiB, so nine
-//                          workgroups fit the 160 KiB of a CU beside each other and a 128 x 128 window is four tiles.  (32 would
-//                          quadruple the tiles, each of which walks all F faces; 128 is 64 KiB and one workgroup for the whole
-//                          window, which leaves most CUs idle at 16 x 8 candidates.)  The workgroup clears the tile, walks all F
-//                          faces -- set-up with the frame's H, W, the pixel box then clamped to tile, window and frame; small boxes
-//                          by the owning lane, larger ones by the whole wave, as raster_kernel does -- with LDS atomicMin on the
-//                          fp32 bit pattern, then classifies the tile's pixels against the observed depth and adds six integers
-//                          per wave to counts.  Integer sums commute: the counts do not depend on arrival order.  No depth image
-//                          reaches memory.
+//                          counted from the window's clamped corner, and its z-buffer lives in LDS: 16 KiB of fp32 depth bits, so
+//                          nine workgroups fit the 160 KiB of a CU beside each other.  draw_tile clears the tile and walks all F
+//                          faces into it with LDS atomicMin; the kernel then classifies the tile's pixels against the observed
+//                          depth and adds six integers per wave to counts.  Integer sums commute: the counts do not depend on
+//                          arrival order.  No depth image reaches memory.
 //   verify_select_kernel   one thread per instance: the fp64 score of every candidate in index order, the best eligible one.
 // The grid covers every tile a window can have (cdiv(W, kTile) x cdiv(H, kTile)): the windows are device data the launcher does
 // not read, and a workgroup whose tile lies outside its window returns before it touches LDS.  counts is cleared by a fill kernel,
 // not a memset node (see gdm_bop.hip).  No allocation and no host read: the call captures in a hipGraph.
 #include "gdm_common.h"
-#include "gdm_raster.h"
+#include "gdm_raster_tile.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kTile = 64;                                                  // pixels per tile side; kTile^2 words of LDS
 constexpr unsigned kInfBits = 0x7f800000u;
 constexpr int kCounters = 6;                                               // n_model, n_agree, n_front, n_behind, n_nodepth, q_agree
 
@@ -34,15 +30,6 @@ __device__ __forceinline__ int wave_sum_i32(int v)
     return v;
 }
 
-struct TileBox { int x0, y0, x1, y1; };                                    // inclusive, frame pixels
-
-__device__ __forceinline__ void shade_lds(const TriSetup& s, int px, int py, const TileBox& t, unsigned* zt)
-{
-    long long w0, w1, w2;
-    if (!edge_values(s, px, py, w0, w1, w2)) return;
-    atomicMin(&zt[(py - t.y0) * kTile + (px - t.x0)], __float_as_uint(pixel_depth(s, w0, w1, w2)));
-}
-
 template <typename VT>
 __global__ __launch_bounds__(kThreads) void pose_verify_kernel(const VT* __restrict__ verts, const int32_t* __restrict__ faces,
                                                                const double* __restrict__ RT, const double* __restrict__ Kmat,
@@ -53,59 +40,10 @@ __global__ __launch_bounds__(kThreads) void pose_verify_kernel(const VT* __restr
 {
     __shared__ unsigned zt[kTile * kTile];
     const int i = blockIdx.z, c = blockIdx.y;
-    const int tiles_x = (W + kTile - 1) / kTile;
-    const int tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
-    // the window clamped to the frame, then this workgroup's tile of it (the same for every thread: the early return is uniform)
-    int wx0 = 0, wy0 = 0, wx1 = W - 1, wy1 = H - 1;
-    if (window) {
-        wx0 = max(window[(long)i * 4], 0);
-        wy0 = max(window[(long)i * 4 + 1], 0);
-        wx1 = min(window[(long)i * 4 + 2], W - 1);
-        wy1 = min(window[(long)i * 4 + 3], H - 1);
-    }
-    if (wx0 > wx1 || wy0 > wy1) return;
     TileBox t;
-    t.x0 = wx0 + tile_x * kTile;                                           // wx0 < W <= 16384: no overflow
-    t.y0 = wy0 + tile_y * kTile;
-    if (t.x0 > wx1 || t.y0 > wy1) return;
-    t.x1 = min(t.x0 + kTile - 1, wx1);
-    t.y1 = min(t.y0 + kTile - 1, wy1);
-
-    for (int k = threadIdx.x; k < kTile * kTile; k += kThreads) zt[k] = kInfBits;
-    __syncthreads();
-
+    if (!tile_of_block(clamped_window(window, i, H, W), blockIdx.x, W, t)) return;
     const int lane = threadIdx.x & 63;
-    const double* rt = RT + ((long)i * C + c) * 12;
-    const double* kk = Kmat + (k_per_instance ? (long)i * 9 : 0);
-    for (int base = 0; base < F; base += kThreads) {                       // uniform trip count: every lane reaches the ballot
-        const int f = base + (int)threadIdx.x;
-        TriSetup s = {};
-        bool valid = f < F;
-        if (valid) {
-            bool swapped;
-            valid = tri_setup(verts, V, faces[(long)f * 3], faces[(long)f * 3 + 1], faces[(long)f * 3 + 2], rt, kk, near, H, W, s, swapped);
-        }
-        if (valid) {
-            s.px0 = max(s.px0, t.x0); s.px1 = min(s.px1, t.x1);
-            s.py0 = max(s.py0, t.y0); s.py1 = min(s.py1, t.y1);
-            valid = s.px0 <= s.px1 && s.py0 <= s.py1;
-        }
-        const int box = valid ? (s.px1 - s.px0 + 1) * (s.py1 - s.py0 + 1) : 0;      // at most kTile^2
-        if (valid && box <= kSmallBox) {
-            for (int py = s.py0; py <= s.py1; ++py)
-                for (int px = s.px0; px <= s.px1; ++px) shade_lds(s, px, py, t, zt);
-        }
-        u64 big = __ballot(valid && box > kSmallBox);
-        while (big) {
-            const int src = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const TriSetup b = tri_from_lane(s, src);
-            const int bw = b.px1 - b.px0 + 1;
-            const int cnt = bw * (b.py1 - b.py0 + 1);
-            for (int k = lane; k < cnt; k += 64) shade_lds(b, b.px0 + k % bw, b.py0 + k / bw, t, zt);
-        }
-    }
-    __syncthreads();
+    draw_tile<kThreads>(zt, t, verts, faces, V, F, RT + ((long)i * C + c) * 12, Kmat + (k_per_instance ? (long)i * 9 : 0), near, H, W);
 
     // THE VERIFICATION RULE, fp32
     const float* obs = depth_obs + (obs_per_instance ? (long)i * H * W : 0L);
@@ -174,31 +112,23 @@ extern "C" int gdm_pose_verify_hip(const void* verts, int verts_f64, const int32
                                    double front_weight, int min_px, int32_t* counts, double* score, int32_t* best, void* stream)
 {
     GDM_CHECK_ARG(verts && faces && RT && K && depth_obs && counts && score && best, "gdm_pose_verify_hip: NULL pointer");
-    GDM_CHECK_ARG(n >= 1 && n <= 65535 && C >= 1 && C <= 65535, "gdm_pose_verify_hip: n=%d C=%d not in [1, 65535]", n, C);
-    GDM_CHECK_ARG(V >= 1 && F >= 1, "gdm_pose_verify_hip: V=%d F=%d must be positive", V, F);
-    GDM_CHECK_ARG(H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "gdm_pose_verify_hip: H=%d W=%d not in [1, 16384]", H, W);
     // q_agree adds up to 256 per pixel (a rounding above it included: 257) into an int32
-    GDM_CHECK_ARG((long)H * W <= (1L << 22), "gdm_pose_verify_hip: H=%d W=%d: more than 2^22 pixels would overflow q_agree", H, W);
-    const long tiles = (long)gdm_cdiv(W, kTile) * gdm_cdiv(H, kTile);       // at most 256 * 256
-    GDM_CHECK_ARG(tiles * n * C <= (1L << 23), "gdm_pose_verify_hip: n=%d C=%d too large for H=%d W=%d (tiles n C <= 2^23)", n, C, H, W);
-    GDM_CHECK_ARG(near >= 0.0, "gdm_pose_verify_hip: near=%g must be >= 0", near);
+    int rc = tile_entry_check("gdm_pose_verify_hip", " would overflow q_agree", n, C, V, F, H, W, near, k_per_instance, obs_per_instance,
+                              verts_f64);
+    if (rc) return rc;
     GDM_CHECK_ARG(delta > 0.0 && delta <= 3.0e38, "gdm_pose_verify_hip: delta=%g must be positive and finite in fp32", delta);
     const float delta_f = (float)delta, inv_delta_q = (float)(256.0 / delta);
     GDM_CHECK_ARG(delta_f > 0.f && inv_delta_q > 0.f && inv_delta_q <= 3.0e38f,
                   "gdm_pose_verify_hip: delta=%g: delta or 256 / delta is not a positive finite fp32 number", delta);
     GDM_CHECK_ARG(front_weight >= 0.0, "gdm_pose_verify_hip: front_weight=%g must be >= 0", front_weight);
     GDM_CHECK_ARG(min_px >= 0, "gdm_pose_verify_hip: min_px=%d must be >= 0", min_px);
-    GDM_CHECK_ARG(k_per_instance == 0 || k_per_instance == 1, "gdm_pose_verify_hip: k_per_instance=%d must be 0 or 1", k_per_instance);
-    GDM_CHECK_ARG(obs_per_instance == 0 || obs_per_instance == 1, "gdm_pose_verify_hip: obs_per_instance=%d must be 0 or 1",
-                  obs_per_instance);
-    GDM_CHECK_ARG(verts_f64 == 0 || verts_f64 == 1, "gdm_pose_verify_hip: verts_f64=%d must be 0 or 1", verts_f64);
     const hipStream_t s = (hipStream_t)stream;
     const long words = (long)n * C * kCounters;
     const int fill_blocks = gdm_cdiv(words, kThreads) < 2048 ? gdm_cdiv(words, kThreads) : 2048;
     hipLaunchKernelGGL(zero_i32_kernel, dim3(fill_blocks), dim3(kThreads), 0, s, counts, words);
-    int rc = gdm_launch_status("zero_i32_kernel");
+    rc = gdm_launch_status("zero_i32_kernel");
     if (rc) return rc;
-    const dim3 grid((unsigned)tiles, C, n);
+    const dim3 grid((unsigned)(gdm_cdiv(W, kTile) * gdm_cdiv(H, kTile)), C, n);
     if (verts_f64)
         hipLaunchKernelGGL(pose_verify_kernel<double>, grid, dim3(kThreads), 0, s, (const double*)verts, faces, RT, K, k_per_instance,
                            depth_obs, obs_per_instance, window, C, V, F, H, W, near, delta_f, inv_delta_q, counts);

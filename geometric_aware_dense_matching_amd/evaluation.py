@@ -11,7 +11,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import pose
+from . import pixel_rule, pose
 
 METRICS = ["ad_2", "ad_5", "ad_10", "ad_0.1", "rete_2", "rete_5", "rete_10", "re_2", "re_5", "re_10", "te_2", "te_5", "te_10",
            "proj_2", "proj_5", "proj_10"]                           # evaluator.py:323-340
@@ -307,54 +307,19 @@ def render_depth_numpy(verts, faces, RT, K, H, W, near):
     """The pixel rule of include/gdm.h (gdm_render_depth_hip) on the host, the definition the kernel is tested against:
     fp64 vertex transform ((R_i0 x + R_i1 y) + R_i2 z) + t_i, u = fx (X / Z) + cx (skew ignored, pixel centres at integers), snapping
     to 1/256 px, int64 edge functions with the top-left rule on the winding normalised by the sign of the area, perspective-correct
-    depth, minimum over the triangles -> f32[n,H,W], 0 where nothing is drawn."""
+    depth, minimum over the triangles in the unsigned order of the depth bits -> f32[n,H,W], 0 where nothing is drawn.  The rule
+    itself is pixel_rule.project and pixel_rule.covered; this function keeps the z-buffer."""
     verts, RT, K = _np64(verts), _np64(RT), _np64(K)
     faces = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)).astype(np.int64)
     n = RT.shape[0]
     K = np.broadcast_to(K, (n, 3, 3))
-    out = np.full((n, H, W), np.inf, dtype=np.float32)
-    x, y, z = verts[:, 0], verts[:, 1], verts[:, 2]
+    out = np.full((n, H, W), pixel_rule.INF_BITS, dtype=np.uint32)
     for b in range(n):
-        R, t = RT[b, :, :3], RT[b, :, 3]
-        X = ((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0]
-        Y = ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1]
-        Z = ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]
-        with np.errstate(all="ignore"):
-            u = K[b, 0, 0] * (X / Z) + K[b, 0, 2]
-            v = K[b, 1, 1] * (Y / Z) + K[b, 1, 2]
-            ok = (Z > near) & (np.abs(u) <= 65536.0) & (np.abs(v) <= 65536.0)
-            xs = np.floor(np.where(ok, u, 0.0) * 256.0 + 0.5).astype(np.int64)
-            ys = np.floor(np.where(ok, v, 0.0) * 256.0 + 0.5).astype(np.int64)
-            iz = 1.0 / Z
-        for f in faces:
-            if not ok[f].all():
-                continue
-            i0, i1, i2 = f
-            A2 = (xs[i1] - xs[i0]) * (ys[i2] - ys[i0]) - (xs[i2] - xs[i0]) * (ys[i1] - ys[i0])
-            if A2 == 0:
-                continue
-            if A2 < 0:
-                i1, i2 = i2, i1
-            px0, px1 = max((min(xs[i0], xs[i1], xs[i2]) + 255) >> 8, 0), min(max(xs[i0], xs[i1], xs[i2]) >> 8, W - 1)
-            py0, py1 = max((min(ys[i0], ys[i1], ys[i2]) + 255) >> 8, 0), min(max(ys[i0], ys[i1], ys[i2]) >> 8, H - 1)
-            if px0 > px1 or py0 > py1:
-                continue
-            PX, PY = np.meshgrid(np.arange(px0, px1 + 1, dtype=np.int64) * 256, np.arange(py0, py1 + 1, dtype=np.int64) * 256)
-            inside, w = np.ones(PX.shape, dtype=bool), []
-            for a, c in ((i1, i2), (i2, i0), (i0, i1)):                # the edge opposite vertex 0, 1, 2
-                dx, dy = xs[c] - xs[a], ys[c] - ys[a]
-                e = dx * (PY - ys[a]) - dy * (PX - xs[a])
-                inside &= (e > 0) | ((e == 0) & bool(dy < 0 or (dy == 0 and dx > 0)))
-                w.append(e)
-            if not inside.any():
-                continue
-            A = ((w[0] + w[1]) + w[2]).astype(np.float64)
-            izp = ((w[0].astype(np.float64) * iz[i0] + w[1].astype(np.float64) * iz[i1]) + w[2].astype(np.float64) * iz[i2]) / A
-            d = (1.0 / izp).astype(np.float32)
+        for _, (px0, py0, px1, py1), inside, d in pixel_rule.covered(faces, *pixel_rule.project(verts, RT[b], K[b], near), H, W):
             tile = out[b, py0:py1 + 1, px0:px1 + 1]
-            tile[inside] = np.minimum(tile[inside], d[inside])
-    out[np.isinf(out)] = 0.0
-    return out
+            tile[inside] = np.minimum(tile[inside], pixel_rule.depth_keys(d)[inside])
+    out[out >= pixel_rule.INF_BITS] = 0
+    return out.view(np.float32)
 
 
 def render_depth(verts, faces, RT, K, H, W, near, keep_inf=False):

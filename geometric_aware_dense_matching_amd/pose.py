@@ -18,7 +18,7 @@ Refinement of pose candidates against that frame by render-and-compare (csrc/gdm
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, pixel_rule
 from ._lib import call
 
 
@@ -465,6 +465,11 @@ VERIFY_COUNTS = ("n_model", "n_agree", "n_front", "n_behind", "n_nodepth", "q_ag
 VERIFY_CANDIDATES = ("kabsch", "ransac", "kabsch+icp", "ransac+icp")
 
 
+def _host(a):
+    """A tensor or an array as a numpy array on the host."""
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
 def _verify_like_args(who, verts, faces, RT, depth, K, window, cand_valid):
     """The argument handling verify_poses and refine_poses_depth share: everything on RT's device in the dtype the entries take."""
     if not torch.is_tensor(RT) or RT.dim() != 4 or tuple(RT.shape[2:]) != (3, 4) or RT.shape[0] < 1 or RT.shape[1] < 1:
@@ -544,23 +549,19 @@ def verify_poses_numpy(verts, faces, RT, depth, K, window=None, delta=0.01, near
     np.float32 arithmetic restates THE VERIFICATION RULE of include/gdm.h and fp64 the selection.  Same arguments (arrays or
     tensors), same dict, as numpy arrays."""
     from . import evaluation
-
-    def host(a):
-        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-    RT = host(RT).astype(np.float64)
+    RT = _host(RT).astype(np.float64)
     n, C = RT.shape[:2]
-    depth = host(depth).astype(np.float32)
+    depth = _host(depth).astype(np.float32)
     H, W = depth.shape[-2:]
     depth = np.broadcast_to(depth, (n, H, W))
-    K = np.broadcast_to(host(K).astype(np.float64), (n, 3, 3))
-    verts = host(verts)
+    K = np.broadcast_to(_host(K).astype(np.float64), (n, 3, 3))
+    verts = _host(verts)
     rendered = evaluation.render_depth_numpy(verts, faces, RT.reshape(n * C, 3, 4), np.repeat(K, C, axis=0), H, W, near)
     rendered = rendered.reshape(n, C, H, W)
     D, Q = np.float32(delta), np.float32(256.0 / float(delta))
     counts = np.zeros((n, C, 6), dtype=np.int32)
     for i in range(n):
-        x0, y0, x1, y1 = (0, 0, W - 1, H - 1) if window is None else (int(v) for v in host(window)[i])
+        x0, y0, x1, y1 = (0, 0, W - 1, H - 1) if window is None else (int(v) for v in _host(window)[i])
         x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, W - 1), min(y1, H - 1)
         if x0 > x1 or y0 > y1:
             continue
@@ -578,7 +579,7 @@ def verify_poses_numpy(verts, faces, RT, depth, K, window=None, delta=0.01, near
                 q = np.floor((a * Q).astype(np.float32))[agree].astype(np.int64).sum()
             nodepth = model & ~seen
             counts[i, c] = [model.sum(), agree.sum(), front.sum(), behind.sum(), nodepth.sum(), q]
-    score, best = verify_select_numpy(counts, front_weight, min_px, None if cand_valid is None else host(cand_valid))
+    score, best = verify_select_numpy(counts, front_weight, min_px, None if cand_valid is None else _host(cand_valid))
     return dict(counts=counts, score=score, best=best)
 
 
@@ -618,58 +619,19 @@ def refine_poses_depth(verts, faces, RT, depth, K, window=None, iters=5, reject=
 
 
 def raster_depth_face_numpy(verts, faces, rt, K, H, W, near):
-    """One pose by the pixel rule of include/gdm.h (evaluation.render_depth_numpy), keeping the face too: depth f32[H,W] (+inf where
-    nothing is drawn) and face i64[H,W] (-1 there) -- per pixel the minimum depth, the lowest face index among equal depths."""
+    """One pose by the pixel rule of include/gdm.h (pixel_rule.covered, as evaluation.render_depth_numpy), keeping the face too: depth
+    f32[H,W] (+inf where nothing is drawn) and face i64[H,W] (-1 there) -- per pixel the unsigned minimum of depth bits << 32 | face,
+    as the kernel's tile keeps it: the minimum depth, the lowest face index among equal depths."""
     verts, rt, K = np.asarray(verts, dtype=np.float64), np.asarray(rt, dtype=np.float64), np.asarray(K, dtype=np.float64)
     faces = np.asarray(faces).astype(np.int64)
-    zbuf = np.full((H, W), np.inf, dtype=np.float32)
-    fbuf = np.full((H, W), -1, dtype=np.int64)
-    x, y, z = verts[:, 0], verts[:, 1], verts[:, 2]
-    R, t = rt[:, :3], rt[:, 3]
-    with np.errstate(all="ignore"):
-        X = ((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0]
-        Y = ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1]
-        Z = ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]
-        u = K[0, 0] * (X / Z) + K[0, 2]
-        v = K[1, 1] * (Y / Z) + K[1, 2]
-        ok = (Z > near) & (np.abs(u) <= 65536.0) & (np.abs(v) <= 65536.0)
-        xs = np.floor(np.where(ok, u, 0.0) * 256.0 + 0.5).astype(np.int64)
-        ys = np.floor(np.where(ok, v, 0.0) * 256.0 + 0.5).astype(np.int64)
-        iz = 1.0 / Z
-    V = len(verts)
-    for fi, f in enumerate(faces):
-        if not ((f >= 0) & (f < V)).all() or not ok[f].all():
-            continue
-        i0, i1, i2 = f
-        A2 = (xs[i1] - xs[i0]) * (ys[i2] - ys[i0]) - (xs[i2] - xs[i0]) * (ys[i1] - ys[i0])
-        if A2 == 0:
-            continue
-        if A2 < 0:
-            i1, i2 = i2, i1
-        px0, px1 = max((min(xs[i0], xs[i1], xs[i2]) + 255) >> 8, 0), min(max(xs[i0], xs[i1], xs[i2]) >> 8, W - 1)
-        py0, py1 = max((min(ys[i0], ys[i1], ys[i2]) + 255) >> 8, 0), min(max(ys[i0], ys[i1], ys[i2]) >> 8, H - 1)
-        if px0 > px1 or py0 > py1:
-            continue
-        PX, PY = np.meshgrid(np.arange(px0, px1 + 1, dtype=np.int64) * 256, np.arange(py0, py1 + 1, dtype=np.int64) * 256)
-        inside, w = np.ones(PX.shape, dtype=bool), []
-        for a, c in ((i1, i2), (i2, i0), (i0, i1)):                    # the edge opposite vertex 0, 1, 2
-            dx, dy = xs[c] - xs[a], ys[c] - ys[a]
-            e = dx * (PY - ys[a]) - dy * (PX - xs[a])
-            inside &= (e > 0) | ((e == 0) & bool(dy < 0 or (dy == 0 and dx > 0)))
-            w.append(e)
-        if not inside.any():
-            continue
-        A = ((w[0] + w[1]) + w[2]).astype(np.float64)
-        with np.errstate(all="ignore"):
-            izp = ((w[0].astype(np.float64) * iz[i0] + w[1].astype(np.float64) * iz[i1]) + w[2].astype(np.float64) * iz[i2]) / A
-            d = (1.0 / izp).astype(np.float32)
-        zt, ft = zbuf[py0:py1 + 1, px0:px1 + 1], fbuf[py0:py1 + 1, px0:px1 + 1]
-        # the unsigned order of the depth bits: positive floats in their own order, NaN and negative values above +inf (never kept);
-        # faces come in ascending order, so a strict < keeps the lowest index among equal depths
-        with np.errstate(invalid="ignore"):
-            take = inside & (d >= 0) & (d < zt)
-        zt[take] = d[take]
-        ft[take] = fi
+    keys = np.full((H, W), np.uint64(0xFFFFFFFFFFFFFFFF), dtype=np.uint64)
+    for f, (px0, py0, px1, py1), inside, d in pixel_rule.covered(faces, *pixel_rule.project(verts, rt, K, near), H, W):
+        tile = keys[py0:py1 + 1, px0:px1 + 1]
+        tile[inside] = np.minimum(tile[inside], pixel_rule.depth_keys(d, f)[inside])
+    bits = (keys >> np.uint64(32)).astype(np.uint32)
+    drawn = bits < pixel_rule.INF_BITS
+    zbuf = np.where(drawn, bits, np.uint32(pixel_rule.INF_BITS)).view(np.float32)
+    fbuf = np.where(drawn, (keys & np.uint64(0xFFFFFFFF)).astype(np.int64), -1)
     return zbuf, fbuf
 
 
@@ -765,26 +727,23 @@ def refine_poses_depth_numpy(verts, faces, RT, depth, K, window=None, iters=5, r
     solves and composes, and the stop rule follows the header statement for statement.  Same arguments (arrays or tensors), the same
     dict as numpy arrays.  trace=True adds `trace`: per (instance, candidate) a list with one dict per iteration evaluated --
     sums f64[30], pairs, min_pivot (None when starved), mean, stop_margin = | |err - mean| - tolerance |, RT (the pose after it)."""
-    def host(a):
-        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-    RT = host(RT).astype(np.float64).copy()
+    RT = _host(RT).astype(np.float64).copy()
     n, C = RT.shape[:2]
-    depth = host(depth).astype(np.float32)
+    depth = _host(depth).astype(np.float32)
     H, W = depth.shape[-2:]
     depth = np.broadcast_to(depth, (n, H, W))
-    K = np.broadcast_to(host(K).astype(np.float64), (n, 3, 3))
-    verts, faces = host(verts), host(faces)
+    K = np.broadcast_to(_host(K).astype(np.float64), (n, 3, 3))
+    verts, faces = _host(verts), _host(faces)
     status = np.zeros((n, C), dtype=np.int32)
     if cand_valid is not None:
-        status[host(cand_valid).reshape(n, C) == 0] = 4
+        status[_host(cand_valid).reshape(n, C) == 0] = 4
     its = np.zeros((n, C), dtype=np.int32)
     err = np.zeros((n, C), dtype=np.float64)
     pairs = np.zeros((n, C), dtype=np.int32)
     log = [[[] for _ in range(C)] for _ in range(n)]
     for _ in range(int(iters)):
         for i in range(n):
-            win = None if window is None else host(window)[i]
+            win = None if window is None else _host(window)[i]
             for c in range(C):
                 if status[i, c] != 0:
                     continue

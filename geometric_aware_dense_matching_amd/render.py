@@ -16,6 +16,8 @@ BlenderProc's PBR frames is not claimed: the frame is defined by the written rul
 import numpy as np
 import torch
 
+from . import pixel_rule
+
 NEAR = 0.01
 AMBIENT = 0.4
 _EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -128,7 +130,7 @@ def render_frames(scene, slot_obj, RT, K, H, W, light=None, ambient=AMBIENT, nea
 
 def render_frames_numpy(scene, slot_obj, RT, K, H, W, light=None, ambient=AMBIENT, near=NEAR):
     """The rule of gdm_render_frames_hip (include/gdm.h) on the host, operation for operation in fp64: the dict of
-    render_frames as numpy arrays plus `ambiguous` bool[n,H,W]: the pixels whose two best candidate depths, over all faces and
+    render_frames as numpy arrays (coverage and depth from pixel_rule.covered) plus `ambiguous` bool[n,H,W]: the pixels whose two best candidate depths, over all faces and
     slots, lie within 2 fp32 ulp of each other -- where the winner is not robust against the last bit of a division."""
     verts = scene.verts_np.astype(np.float64)
     vcol, vnrm = scene.vcol_np.astype(np.float64), scene.vnrm_np.astype(np.float64)
@@ -141,54 +143,16 @@ def render_frames_numpy(scene, slot_obj, RT, K, H, W, light=None, ambient=AMBIEN
     keys = np.full((n, S, H, W), _EMPTY, dtype=np.uint64)
     d1 = np.full((n, H, W), np.inf, dtype=np.float32)                      # the two best candidate depths of every pixel
     d2 = np.full((n, H, W), np.inf, dtype=np.float32)
-    x, y, z = verts[:, 0], verts[:, 1], verts[:, 2]
     proj = {}
     for b in range(n):
         for s in range(S):
             o = int(slot_obj[b, s])
             if not 0 <= o < O:
                 continue
-            R, t = RT[b, s, :, :3], RT[b, s, :, 3]
-            X = ((R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z) + t[0]
-            Y = ((R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z) + t[1]
-            Z = ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + t[2]
-            with np.errstate(all="ignore"):
-                u = K[b, 0, 0] * (X / Z) + K[b, 0, 2]
-                v = K[b, 1, 1] * (Y / Z) + K[b, 1, 2]
-                ok = (Z > near) & (np.abs(u) <= 65536.0) & (np.abs(v) <= 65536.0)
-                xs = np.floor(np.where(ok, u, 0.0) * 256.0 + 0.5).astype(np.int64)
-                ys = np.floor(np.where(ok, v, 0.0) * 256.0 + 0.5).astype(np.int64)
-                iz = 1.0 / Z
-            proj[b, s] = (xs, ys, iz)
-            for f in range(face0[o], face0[o + 1]):
-                i0, i1, i2 = faces[f]
-                if not (ok[i0] and ok[i1] and ok[i2]):
-                    continue
-                A2 = (xs[i1] - xs[i0]) * (ys[i2] - ys[i0]) - (xs[i2] - xs[i0]) * (ys[i1] - ys[i0])
-                if A2 == 0:
-                    continue
-                if A2 < 0:
-                    i1, i2 = i2, i1
-                px0, px1 = max((min(xs[i0], xs[i1], xs[i2]) + 255) >> 8, 0), min(max(xs[i0], xs[i1], xs[i2]) >> 8, W - 1)
-                py0, py1 = max((min(ys[i0], ys[i1], ys[i2]) + 255) >> 8, 0), min(max(ys[i0], ys[i1], ys[i2]) >> 8, H - 1)
-                if px0 > px1 or py0 > py1:
-                    continue
-                PX, PY = np.meshgrid(np.arange(px0, px1 + 1, dtype=np.int64) * 256, np.arange(py0, py1 + 1, dtype=np.int64) * 256)
-                inside, w = np.ones(PX.shape, dtype=bool), []
-                for a, c in ((i1, i2), (i2, i0), (i0, i1)):                # the edge opposite vertex 0, 1, 2
-                    dx, dy = xs[c] - xs[a], ys[c] - ys[a]
-                    e = dx * (PY - ys[a]) - dy * (PX - xs[a])
-                    inside &= (e > 0) | ((e == 0) & bool(dy < 0 or (dy == 0 and dx > 0)))
-                    w.append(e)
-                if not inside.any():
-                    continue
-                A = ((w[0] + w[1]) + w[2]).astype(np.float64)
-                with np.errstate(all="ignore"):
-                    izp = ((w[0].astype(np.float64) * iz[i0] + w[1].astype(np.float64) * iz[i1]) + w[2].astype(np.float64) * iz[i2]) / A
-                    d = (1.0 / izp).astype(np.float32)
-                key = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.uint64(f)
+            ok, xs, ys, iz = proj[b, s] = pixel_rule.project(verts, RT[b, s], K[b], near)
+            for f, (px0, py0, px1, py1), inside, d in pixel_rule.covered(faces, ok, xs, ys, iz, H, W, face0[o], face0[o + 1]):
                 tile = keys[b, s, py0:py1 + 1, px0:px1 + 1]
-                tile[inside] = np.minimum(tile[inside], key[inside])
+                tile[inside] = np.minimum(tile[inside], pixel_rule.depth_keys(d, f)[inside])
                 t1, t2 = d1[b, py0:py1 + 1, px0:px1 + 1], d2[b, py0:py1 + 1, px0:px1 + 1]
                 t2[inside] = np.minimum(t2[inside], np.maximum(t1[inside], d[inside]))
                 t1[inside] = np.minimum(t1[inside], d[inside])
@@ -209,15 +173,14 @@ def render_frames_numpy(scene, slot_obj, RT, K, H, W, light=None, ambient=AMBIEN
                            cols.max() if len(rows) else -1, rows.max() if len(rows) else -1)
             if not len(rows):
                 continue
-            xs, ys, iz = proj[b, s]
+            _, xs, ys, iz = proj[b, s]
             i0, i1, i2 = faces[face[b, rows, cols]].T
             A2 = (xs[i1] - xs[i0]) * (ys[i2] - ys[i0]) - (xs[i2] - xs[i0]) * (ys[i1] - ys[i0])
             i1, i2 = np.where(A2 < 0, i2, i1), np.where(A2 < 0, i1, i2)   # the attributes follow the winding
             PX, PY = cols.astype(np.int64) * 256, rows.astype(np.int64) * 256
             q = []
             for a, c, opp in ((i1, i2, i0), (i2, i0, i1), (i0, i1, i2)):
-                e = (xs[c] - xs[a]) * (PY - ys[a]) - (ys[c] - ys[a]) * (PX - xs[a])
-                q.append(e.astype(np.float64) * iz[opp])
+                q.append(pixel_rule.edge(xs, ys, a, c, PX, PY).astype(np.float64) * iz[opp])
             Q = (q[0] + q[1]) + q[2]
 
             def interp(attr):

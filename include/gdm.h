@@ -1030,12 +1030,13 @@ int gdm_mssd_mspd_hip(const double* RT_est, const double* RT_gt, const double* p
                       const double* K, int k_per_instance, int n, int M, int S, double* err, double* mssd, double* mspd,
                       int32_t* best_sym_mssd, int32_t* best_sym_mspd, void* stream);
 /* Depth images of one triangle mesh in n poses (what pose_error.py:59-64 asks of its `renderer`): depth f32[n,H,W], 0 where nothing
- * is drawn.  verts f32[V,3] (verts_f64 0) or f64[V,3] (1); faces i32[F,3]; RT f64[n,3,4].  THE PIXEL RULE (evaluation.render_depth_numpy
- * restates it):
+ * is drawn.  verts f32[V,3] (verts_f64 0) or f64[V,3] (1); faces i32[F,3]; RT f64[n,3,4].  THE PIXEL RULE (pixel_rule.py restates
+ * it for evaluation.render_depth_numpy; csrc/gdm_raster.h holds its device code):
  *   vertex      P = R v + t in fp64, each component ((R_i0 x + R_i1 y) + R_i2 z) + t_i
  *   projection  u = fx (X / Z) + cx, v = fy (Y / Z) + cy with fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]; skew is ignored.
  *               Pixel centres sit at integer coordinates.
- *   discard     the whole triangle when a vertex has Z <= near, or |u| or |v| above 2^16, or its snapped area is 0
+ *   discard     the whole triangle when a vertex index lies outside [0, V), a vertex has Z <= near, or |u| or |v| above 2^16, or its
+ *               snapped area is 0
  *   snapping    Xs = (int64) floor(u * 256 + 0.5), Ys likewise
  *   coverage    int64 edge functions at (256 px, 256 py), the winding normalised by the sign of the area (no culling); a pixel is
  *               covered when all three are >= 0, a zero counting only on a top or left edge (dy < 0, or dy == 0 and dx > 0, of the

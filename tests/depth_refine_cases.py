@@ -103,13 +103,13 @@ def _observed(verts, faces, RT0, K, seed, h, w):
 
 
 SWEEP = ("n3 C5 f32 K,depth per instance", "n3 C5 f64 K,depth shared", "n1 C1 f32 whole frame", "n1 C5 f64 whole frame huber cos",
-         "n3 C1 f32 huber cos", "n1 C5 f32 four tiles")
+         "n3 C1 f32 huber cos", "n1 C5 f32 four tiles", vc.BIG_LATE)
 
 
 @functools.lru_cache(maxsize=None)
 def sweep_case(name):
     """One sweep scene as the keyword arguments of refine_poses_depth / refine_poses_depth_numpy (iters is the caller's)."""
-    verts, faces = vc.mixed_mesh()
+    verts, faces = vc.mixed_mesh(2 if name == vc.BIG_LATE else 1)
     h, w, K, opts = H, W, K0, dict(huber=None, min_cos=0.0)
     if name == "n3 C5 f32 K,depth per instance":
         n, C, dtype, kper, dper = 3, 5, np.float32, True, True
@@ -132,6 +132,8 @@ def sweep_case(name):
         n, C, dtype, kper, dper, h, w = 1, 5, np.float32, False, True, 144, 160
         K = np.array([[250.0, 0.0, 79.3], [0.0, 247.0, 71.6], [0.0, 0.0, 1.0]])
         window = np.array([[20, 10, 140, 130]], dtype=np.int32)
+    elif name == vc.BIG_LATE:
+        n, C, dtype, kper, dper, window = 1, 5, np.float32, False, True, None
     else:
         raise KeyError(name)
     RT = _near_candidates(n, C, seed=len(name))

@@ -60,7 +60,13 @@ def tilted_quad():
     return dict(meshes=[quad_mesh(0.5)], slot_obj=np.zeros((1, 1), dtype=np.int32), RT=RT, K=bi.K, light=unit((0.2, 0.1, -1.0))[None])
 
 
-SCENES = {"two objects": two_objects, "tilted quad": tilted_quad}          # the scenes the GPU file compares with the restatement
+def tilted_quad_twice():
+    """The tilted quad in slots 0 and 1 of one frame, the second 0.1 farther along z: four large triangles of two slots in one wave."""
+    RT = np.stack([pose(bi.rot(0.5, (1, 1, 0)), (0.0, 0.0, 0.25 + 0.1 * s)) for s in range(2)])[None]
+    return dict(meshes=[quad_mesh(0.5)], slot_obj=np.zeros((1, 2), dtype=np.int32), RT=RT, K=bi.K, light=unit((0.2, 0.1, -1.0))[None])
+
+
+SCENES = {"two objects": two_objects, "tilted quad": tilted_quad, "tilted quad twice": tilted_quad_twice}          # the scenes the GPU file compares with the restatement
 
 
 def render_args(case):

@@ -86,6 +86,10 @@ def test_render_depth_large_triangles_take_the_cooperative_path():
     RT = np.hstack([bi.rot(0.5, (1, 1, 0)), np.array([[0.0], [0.0], [0.25]])])[None]
     check_image(ev.render_depth(verts, faces, dev(RT), bi.K, bi.H, bi.W, bi.NEAR),
                 ev.render_depth_numpy(verts, faces, RT, bi.K, bi.H, bi.W, bi.NEAR), "tilted quad")
+    both = np.concatenate([bi.identity_pose(), RT])                      # n = 2: large triangles of two instances in one wave
+    want = ev.render_depth_numpy(verts, faces, both, bi.K, bi.H, bi.W, bi.NEAR)
+    assert (want[0] > 0).sum() == 2745 and (want[1] > 0).sum() == 744
+    check_image(ev.render_depth(verts, faces, dev(both), bi.K, bi.H, bi.W, bi.NEAR), want, "identity and tilted together")
     one = ev.render_depth(verts, faces[:1], dev(RT), bi.K, bi.H, bi.W, bi.NEAR)                           # F = 1
     check_image(one, ev.render_depth_numpy(verts, faces[:1], RT, bi.K, bi.H, bi.W, bi.NEAR), "F = 1")
 

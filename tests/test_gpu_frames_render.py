@@ -83,6 +83,13 @@ def test_large_triangles_take_the_cooperative_path(wanted):
         got = _check(render.render_frames(render.SceneMeshes(case["meshes"], verts_dtype=dtype), *args, **kw), wanted["tilted quad", dtype],
                      "tilted quad, %s" % np.dtype(dtype).name)
     assert got["px_vis"][0, 0] > 500 and len(np.unique(got["depth"])) > 100      # two triangles, each far above the per-thread limit
+    # the quad in two slots: the wave draws large triangles of both, so slot and face travel with the source lane
+    case = rc.tilted_quad_twice()
+    args, kw = rc.render_args(case)
+    for dtype in (np.float64, np.float32):
+        got = _check(render.render_frames(render.SceneMeshes(case["meshes"], verts_dtype=dtype), *args, **kw),
+                     wanted["tilted quad twice", dtype], "tilted quad twice, %s" % np.dtype(dtype).name)
+        assert got["px_all"][0].tolist() == [744, 748] and got["px_vis"][0].tolist() == [744, 8]
 
 
 def test_equal_depths_go_to_the_lower_face_id():

@@ -25,11 +25,12 @@ def pose(R, t):
 
 
 @functools.lru_cache(maxsize=None)
-def mixed_mesh():
-    """demo_mesh(level=1) (80 faces) in the object frame plus, expressed in the same frame so that one pose moves all of it: a
+def mixed_mesh(level=1):
+    """demo_mesh(level) (80 faces at level 1, 320 at level 2) in the object frame plus, expressed in the same frame so that one pose moves all of it: a
     triangle 0.7 across behind the object (under the poses below it covers all four tiles of the frame: the cooperative path), a
-    triangle whose third vertex lies 0.5 in front (behind `near` once posed at z = 0.45) and a degenerate triangle."""
-    m = render.demo_mesh(level=1, seed=4)
+    triangle whose third vertex lies 0.5 in front (behind `near` once posed at z = 0.45) and a degenerate triangle.  At level 2 the
+    large triangle is face 320: the second trip of a 256-thread face loop, thread 64, so wave 1."""
+    m = render.demo_mesh(level=level, seed=4)
     v, f = m["verts"], m["faces"]
     extra = np.array([[-0.45, -0.3, 0.12], [0.45, -0.28, 0.15], [0.02, 0.42, 0.1],            # the large one
                       [0.03, 0.03, 0.0], [0.05, 0.03, 0.0], [0.04, 0.05, -0.5],                # reaches behind near
@@ -67,9 +68,12 @@ def _observed(verts, faces, RT0, K, seed):
     return d
 
 
+BIG_LATE = "n1 C5 f32, 323 faces"    # mixed_mesh(2): the large triangle on a later trip of the face loop, in a wave other than 0
+
+
 def mixed_case(name):
     """One of the mixed scenes, as the keyword arguments of verify_poses / verify_poses_numpy."""
-    verts, faces = mixed_mesh()
+    verts, faces = mixed_mesh(2 if name == BIG_LATE else 1)
     if name == "n3 C5 f32 K,depth per instance":
         n, C, dtype, kper, dper = 3, 5, np.float32, True, True
         window = np.array([[3, 5, 72, 49], [0, 0, 95, 79], [44, 36, 44, 36]], dtype=np.int32)
@@ -80,6 +84,8 @@ def mixed_case(name):
         n, C, dtype, kper, dper, window = 1, 1, np.float32, False, True, None
     elif name == "n1 C5 f64 whole frame":
         n, C, dtype, kper, dper, window = 1, 5, np.float64, True, False, None
+    elif name == BIG_LATE:
+        n, C, dtype, kper, dper, window = 1, 5, np.float32, False, True, None
     else:
         raise KeyError(name)
     RT = _candidates(n, C, seed=len(name))
@@ -92,7 +98,7 @@ def mixed_case(name):
                 near=NEAR, front_weight=0.25, min_px=16, cand_valid=cand_valid)
 
 
-MIXED = ("n3 C5 f32 K,depth per instance", "n3 C5 f64 K,depth shared", "n1 C1 f32 whole frame", "n1 C5 f64 whole frame")
+MIXED = ("n3 C5 f32 K,depth per instance", "n3 C5 f64 K,depth shared", "n1 C1 f32 whole frame", "n1 C5 f64 whole frame", BIG_LATE)
 
 # ---- the exact edges of the rule ------------------------------------------------------------------------------------------------
 EDGE_VALUES = np.array([1.0, 1.0 + DELTA_EDGE, np.nextafter(np.float32(1.0 + DELTA_EDGE), np.float32(2)),
