@@ -69,7 +69,8 @@ static inline void gdm_allow_lds(int bytes)
 #endif
 
 #ifdef __HIPCC__
-// Split-bf16 operands (the matching, convolution, up-convolution and circle-loss kernels): v = hi + lo + O(2^-17 |v|), both parts
+// Split-bf16 operands (the matching, convolution, up-convolution and circle-loss kernels): |v - hi - lo| <= 2^-16 |v| (a bf16 half-ulp
+// is 2^-8 relative: |lo| <= 2^-8 |v|, and lo's own rounding is 2^-8 of that), both parts
 // rounded to nearest even by the hardware conversion (v_cvt_pk_bf16_f32): a NaN stays a NaN in hi (so it reaches the output, as it
 // would through an fp32 product) and an overflow rounds to infinity.  hi / lo come back packed two to a dword (element 0 low).
 typedef __attribute__((ext_vector_type(2))) float gdm_f32x2;

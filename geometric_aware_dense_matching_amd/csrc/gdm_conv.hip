@@ -3,8 +3,9 @@
 // For the 32x32-resolution half of the ResNet-18 trunk (layer3 / layer4 of
 // /root/reference/models/cnn/extractors.py:36-58,151-177: 128..512 -> 256..512 channels), where MIOpen's
 // fp32 path is an ASM Winograd F(2,3) kernel on the vector ALUs (~118 TF/s direct-equivalent).  fp32 products are
-// replaced by three bf16 MFMAs (hi*hi + hi*lo + lo*hi, fp32 accumulate; |err| <= 3*2^-18 per product, the same
-// scheme as the descriptor matching kernel), which is ~5x the f32-MFMA rate.
+// replaced by three bf16 MFMAs (hi*hi + hi*lo + lo*hi, fp32 accumulate; |err| <= 3*2^-16 |w x| per product: a bf16 half-ulp is
+// 2^-8 relative, so |lo| <= 2^-8 |v|, |v - hi - lo| <= 2^-16 |v|, and the dropped lo*lo and the two residual terms are 2^-16 each;
+// the same scheme as the descriptor matching kernel), which is ~5x the f32-MFMA rate.
 //
 //   out[b,co,y,x] = act( scale[co] * sum_{tap,ci} W[co,ci,tap] * in[b,ci,y+ky-1,x+kx-1] + shift[co] (+ res) )
 //

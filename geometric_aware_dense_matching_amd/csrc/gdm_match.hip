@@ -8,7 +8,7 @@
 // Two kernels:
 //   1. pack_rows_kernel   [R, D=128, n] channel-major fp32  ->  R*n packed rows of 512 B:
 //        L2-normalise over D (x / max(|x|, 1e-12), F.normalize semantics) and store either
-//          BF16X3: 128 bf16 "hi" | 128 bf16 "lo"   (x = hi + lo + O(2^-18 |x|))
+//          BF16X3: 128 bf16 "hi" | 128 bf16 "lo"   (|x - hi - lo| <= 2^-16 |x|)
 //          F32   : 128 fp32
 //        Transposes through LDS so that global reads are contiguous along n and global writes
 //        are contiguous 512-B rows.

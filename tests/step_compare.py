@@ -29,7 +29,7 @@ import torch
 TRAIN_FLAGS = ("USE_LOWRES_UPCONV_TRAIN", "USE_SPLIT_PSP_TRAIN", "USE_MFMA_CONV_TRAIN", "USE_FUSED_BN_TRAIN")
 EXACT_FLAGS = TRAIN_FLAGS[:2]                  # fp32 re-associations of the same arithmetic
 DELTA_SAME = 2.0 ** -23                        # same arithmetic, other order or route: one fp32 rounding of the inputs
-DELTA_OTHER = 2.0 ** -17                       # other arithmetic: split-bf16 products (3 * 2^-18 per output), fp64 against fp32 sums
+DELTA_OTHER = 2.0 ** -17                       # other arithmetic: split-bf16 products (<= 3 * 2^-16 per product: |lo| <= 2^-8 |v|, residual <= 2^-16 |v|), fp64 against fp32 sums
 MARGIN = 10.0                                  # the project's standing factor for "number of re-associated sums"
 ZERO_CLASS = 1e-6                              # ||ref_k|| below this share of the median gradient norm: an analytically zero gradient
 # Two fp32 evaluations of one tensor differ by at least a rounding of its elements whatever the inputs do: no yardstick is below it.

@@ -705,8 +705,8 @@ def test_spline_scalar_kernels_for_odd_channel_counts(ops):
 
 @pytest.mark.parametrize("B,Cin,Cout,H,W", [(2, 128, 128, 32, 32), (1, 256, 512, 32, 32), (3, 512, 128, 8, 32), (2, 128, 256, 5, 64)])
 def test_conv3x3_bf16x3_vs_fp32_conv(ops, B, Cin, Cout, H, W):
-    """Split-bf16 MFMA implicit GEMM vs the fp64 convolution on the CPU; error bound 3*2^-18 * sum|w x| per output
-    (measured ~1e-6 relative to the output scale), far inside the network tolerance used against the golden vectors."""
+    """Split-bf16 MFMA implicit GEMM vs the fp64 convolution on the CPU; error bound 3*2^-16 * sum|w x| per output
+    (a bf16 half-ulp is 2^-8 relative: |lo| <= 2^-8 |v|, residual <= 2^-16 |v|, three such terms per product; measured ~1e-6 relative to the output scale), far inside the network tolerance used against the golden vectors."""
     rs = np.random.RandomState(Cin + Cout + H)
     x = torch.from_numpy(rs.randn(B, Cin, H, W).astype(np.float32))
     w = torch.from_numpy((rs.randn(Cout, Cin, 3, 3) / np.sqrt(Cin * 9)).astype(np.float32))
@@ -1164,7 +1164,7 @@ def test_pointwise_jobs_mixed_k_splits_and_bad_shapes(ops):
 @pytest.mark.parametrize("B,H,W", [(2, 256, 256), (1, 100, 70), (3, 64, 128), (1, 7, 9)])
 def test_stem_kernel_vs_torch_fp64(ops, B, H, W):
     """gdm_stem_hip == maxpool3x3/2/p1(relu(bn(conv7x7/2/p3(x)))) (extractors.py:112-116,181-185) in fp64 torch: split-bf16 products
-    (|err| <= 3 * 2^-18 per product over 147 terms): 2e-5 relative to the output scale.  The packed operand it also writes is
+    (|err| <= 3 * 2^-16 |w x| per product -- |lo| <= 2^-8 |v|, residual <= 2^-16 |v| -- over 147 terms): 2e-5 relative to the output scale.  The packed operand it also writes is
     byte-identical to what the pack kernel makes of its fp32 output."""
     from geometric_aware_dense_matching_amd import _lib
     g = torch.Generator(device="cpu").manual_seed(H * 7 + W)
