@@ -10,6 +10,7 @@
 //   gdm_point_diameter_hip   the exact farthest pair: row tile i in registers, column tiles through LDS, one packed partial per
 //                            workgroup, a second launch reduces them.  No atomics.
 #include "gdm_common.h"
+#include "gdm_texture.h"
 
 namespace {
 
@@ -22,9 +23,22 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x)
 
 constexpr int kSampleT = 256;
 
+// The textured sampler's extra arguments (gdm_surface_sample_tex_hip): the face corners' (u, v), the texel buffer and the object's
+// table row, validated by the entry.
+struct SampleTex {
+    const float* fuv;
+    const uint32_t* tex;
+    TexObj obj;
+    int flip_v;
+};
+struct SampleNoTex {};
+
+// TEX: the same draws, xyz and normal; the colour is the texture's level 0 at the interpolated (u, v) instead of the vertex colours'.
+template <bool TEX>
 __global__ __launch_bounds__(kSampleT) void surface_sample_kernel(
     const float* __restrict__ verts, const int32_t* __restrict__ faces, const float* __restrict__ vnrm, const float* __restrict__ vrgb,
-    const int64_t* __restrict__ cdf, int F, int S, uint32_t seed, float* __restrict__ out)
+    const int64_t* __restrict__ cdf, int F, int S, uint32_t seed, float* __restrict__ out,
+    const std::conditional_t<TEX, SampleTex, SampleNoTex> st)
 {
     const long s = (long)blockIdx.x * kSampleT + threadIdx.x;
     if (s >= S) return;
@@ -54,8 +68,16 @@ __global__ __launch_bounds__(kSampleT) void surface_sample_kernel(
         ch[3 + k] = __fadd_rn(__fadd_rn(__fmul_rn(w0, vrgb[a * 3 + k]), __fmul_rn(u, vrgb[b * 3 + k])), __fmul_rn(v, vrgb[c * 3 + k]));
         ch[6 + k] = __fadd_rn(__fadd_rn(__fmul_rn(w0, vnrm[a * 3 + k]), __fmul_rn(u, vnrm[b * 3 + k])), __fmul_rn(v, vnrm[c * 3 + k]));
     }
+    if constexpr (TEX) {
+        const float* uv = st.fuv + (long)lo * 6;
+        const float tu = __fadd_rn(__fadd_rn(__fmul_rn(w0, uv[0]), __fmul_rn(u, uv[2])), __fmul_rn(v, uv[4]));
+        const float tv = __fadd_rn(__fadd_rn(__fmul_rn(w0, uv[1]), __fmul_rn(u, uv[3])), __fmul_rn(v, uv[5]));
+        const uint32_t c = tex_fetch(st.tex, st.obj, 0, (double)tu, (double)tv, st.flip_v);
+        ch[3] = (float)(c & 255u); ch[4] = (float)((c >> 8) & 255u); ch[5] = (float)((c >> 16) & 255u);
+    } else {
 #pragma unroll
-    for (int k = 3; k < 6; ++k) ch[k] = fminf(fmaxf(floorf(__fadd_rn(ch[k], 0.5f)), 0.f), 255.f);
+        for (int k = 3; k < 6; ++k) ch[k] = fminf(fmaxf(floorf(__fadd_rn(ch[k], 0.5f)), 0.f), 255.f);
+    }
     // sqrtf, not __fsqrt_rn: the compiler's header maps that one to the native square root (1 ulp), sqrtf is correctly rounded
     const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ch[6], ch[6]), __fmul_rn(ch[7], ch[7])), __fmul_rn(ch[8], ch[8])));
     if (len > 0.f) {
@@ -240,8 +262,34 @@ extern "C" int gdm_surface_sample_hip(const float* verts, const int32_t* faces, 
     GDM_CHECK_ARG(verts && faces && vnrm && vrgb && cdf && out, "gdm_surface_sample_hip: NULL pointer");
     GDM_CHECK_ARG(V >= 1 && F >= 1, "gdm_surface_sample_hip: V=%d F=%d must both be at least 1", V, F);
     GDM_CHECK_ARG(S >= 1 && S < (1l << 31), "gdm_surface_sample_hip: S=%ld not in [1, 2^31)", S);
-    hipLaunchKernelGGL(surface_sample_kernel, dim3(gdm_cdiv(S, kSampleT)), dim3(kSampleT), 0, (hipStream_t)stream, verts, faces, vnrm,
-                       vrgb, cdf, F, (int)S, seed, out);
+    hipLaunchKernelGGL(surface_sample_kernel<false>, dim3(gdm_cdiv(S, kSampleT)), dim3(kSampleT), 0, (hipStream_t)stream, verts, faces,
+                       vnrm, vrgb, cdf, F, (int)S, seed, out, SampleNoTex{});
+    return gdm_launch_status("surface_sample_kernel");
+}
+
+extern "C" int gdm_surface_sample_tex_hip(const float* verts, const int32_t* faces, const float* vnrm, const float* vrgb,
+                                          const int64_t* cdf, const float* fuv, const void* tex, int64_t tex_off, int64_t tex_w,
+                                          int64_t tex_h, int64_t tex_levels, long tex_texels, int flip_v, int V, int F, long S,
+                                          uint32_t seed, float* out, void* stream)
+{
+    GDM_CHECK_ARG(verts && faces && vnrm && vrgb && cdf && fuv && tex && out, "gdm_surface_sample_tex_hip: NULL pointer");
+    GDM_CHECK_ARG(V >= 1 && F >= 1, "gdm_surface_sample_tex_hip: V=%d F=%d must both be at least 1", V, F);
+    GDM_CHECK_ARG(S >= 1 && S < (1l << 31), "gdm_surface_sample_tex_hip: S=%ld not in [1, 2^31)", S);
+    GDM_CHECK_ARG(tex_texels >= 1 && tex_texels < (1l << 31), "gdm_surface_sample_tex_hip: tex_texels=%ld not in [1, 2^31)", tex_texels);
+    GDM_CHECK_ARG(((uintptr_t)tex & 3) == 0, "gdm_surface_sample_tex_hip: tex must be 4-byte aligned");
+    GDM_CHECK_ARG(flip_v == 0 || flip_v == 1, "gdm_surface_sample_tex_hip: flip_v=%d must be 0 or 1", flip_v);
+    const dim3 grid(gdm_cdiv(S, kSampleT));
+    if (tex_w == 0) {                                                      // no texture: the vertex colours, as gdm_surface_sample_hip
+        hipLaunchKernelGGL(surface_sample_kernel<false>, grid, dim3(kSampleT), 0, (hipStream_t)stream, verts, faces, vnrm, vrgb, cdf, F,
+                           (int)S, seed, out, SampleNoTex{});
+        return gdm_launch_status("surface_sample_kernel");
+    }
+    SampleTex st = {fuv, (const uint32_t*)tex, {}, flip_v};
+    GDM_CHECK_ARG(tex_row_valid(tex_off, tex_w, tex_h, tex_levels, tex_texels, st.obj),
+                  "gdm_surface_sample_tex_hip: the row (offset %lld, %lld x %lld, %lld levels) does not lie inside %ld texels",
+                  (long long)tex_off, (long long)tex_w, (long long)tex_h, (long long)tex_levels, tex_texels);
+    hipLaunchKernelGGL(surface_sample_kernel<true>, grid, dim3(kSampleT), 0, (hipStream_t)stream, verts, faces, vnrm, vrgb, cdf, F, (int)S,
+                       seed, out, st);
     return gdm_launch_status("surface_sample_kernel");
 }
 

@@ -12,10 +12,15 @@
 //   resolve_kernel   one thread per pixel: the winning slot (smallest depth bits, the lower slot on a tie), the set-up of the winning
 //                    face once more, perspective-correct colour and normal in fp64, the diffuse term, and the statistics -- counted by
 //                    ballot and reduced by shuffles per wave, then one integer atomic per wave and counter that has something to say
-//                    (integer adds, minima and maxima are order-independent).
-// No allocation and no host read in the entry point: it captures in a hipGraph.
+//                    (integer adds, minima and maxima are order-independent).  Its second instance, resolve_kernel<VT, true>
+//                    (gdm_render_frames_tex_hip), colours the pixels whose winner's object has a valid row in the
+//                    texture table from that object's pyramid by THE TEXTURE RULE (gdm_texture.h): the corner (u, v) interpolated
+//                    like every attribute, once more at (px + 1, py) and (px, py + 1) for the level, then four dword loads and an
+//                    integer blend.  The branch is compiled out of the first instance, which stays what it was.
+// No allocation and no host read in the entry points: they capture in a hipGraph.
 #include "gdm_common.h"
 #include "gdm_raster.h"
+#include "gdm_texture.h"
 
 namespace {
 
@@ -90,14 +95,26 @@ __device__ __forceinline__ double interp(double q0, double q1, double q2, double
     return ((q0 * a0 + q1 * a1) + q2 * a2) / Q;
 }
 
-template <typename VT>
+// What the textured resolve needs beyond the untextured one (gdm_render_frames_tex_hip); NoTex for the instance without the branch.
+struct TexArgs {
+    const float* fuv;                                                      // f32[Ft,3,2]: a (u, v) per face corner
+    const uint32_t* tex;                                                   // every object's pyramid, tex_texels texels
+    const int64_t* tab;                                                    // i64[O,4] = (offset, W0, H0, L): device data, validated per use
+    const int32_t* slot_obj;
+    long tex_texels;
+    int O, flip_v;
+};
+struct NoTex {};
+
+template <typename VT, bool TEX>
 __global__ __launch_bounds__(kThreads) void resolve_kernel(const VT* __restrict__ verts, const uint8_t* __restrict__ vcol,
                                                            const float* __restrict__ vnrm, const int32_t* __restrict__ faces,
                                                            const double* __restrict__ RT, const double* __restrict__ Kmat,
                                                            int k_per_instance, const double* __restrict__ light, double ambient, double near,
                                                            int S, int Vt, int Ft, int H, int W, const u64* __restrict__ keys,
                                                            uint8_t* __restrict__ rgb, float* __restrict__ depth, uint8_t* __restrict__ inst,
-                                                           int32_t* __restrict__ face, int32_t* __restrict__ stats)
+                                                           int32_t* __restrict__ face, int32_t* __restrict__ stats,
+                                                           const std::conditional_t<TEX, TexArgs, NoTex> ta)
 {
     const int b = blockIdx.y;
     const long P = (long)H * W;
@@ -151,9 +168,50 @@ __global__ __launch_bounds__(kThreads) void resolve_kernel(const VT* __restrict_
                 const double* l = light + (long)b * 3;
                 const double cs = len > 0.0 ? fmax(((nx * l[0] + ny * l[1]) + nz * l[2]) / len, 0.0) : 0.0;
                 const double k = ambient + (1.0 - ambient) * cs;
-                r = (int)fmin(255.0, floor(interp(q0, q1, q2, Q, (double)c0[0], (double)c1[0], (double)c2[0]) * k + 0.5));
-                g = (int)fmin(255.0, floor(interp(q0, q1, q2, Q, (double)c0[1], (double)c1[1], (double)c2[1]) * k + 0.5));
-                bl = (int)fmin(255.0, floor(interp(q0, q1, q2, Q, (double)c0[2], (double)c1[2], (double)c2[2]) * k + 0.5));
+                // the winner's object decides the branch: whole waves take one side wherever a wave's pixels show one object
+                TexObj to = {};
+                bool textured = false;
+                if constexpr (TEX) {
+                    const int o = ta.slot_obj[(long)b * S + win];
+                    if (o >= 0 && o < ta.O) {
+                        const int64_t* row = ta.tab + (long)o * 4;
+                        textured = tex_row_valid(row[0], row[1], row[2], row[3], ta.tex_texels, to);
+                    }
+                }
+                if (textured) {
+                    if constexpr (TEX) {
+                        const float* uv = ta.fuv + (long)f * 6;            // the corners follow the winding like the vertices
+                        const int k1 = swapped ? 2 : 1, k2 = swapped ? 1 : 2;
+                        const double u0 = (double)uv[0], v0 = (double)uv[1], u1 = (double)uv[k1 * 2], v1 = (double)uv[k1 * 2 + 1],
+                                     u2 = (double)uv[k2 * 2], v2 = (double)uv[k2 * 2 + 1];
+                        const double u = interp(q0, q1, q2, Q, u0, u1, u2), v = interp(q0, q1, q2, Q, v0, v1, v2);
+                        // the same face at (px + 1, py) and (px, py + 1), covered or not: the edge functions are evaluated there
+                        const long long X = (long long)px * 256, Y = (long long)py * 256;
+                        double dU[2], dV[2];
+                        bool fine = true;
+#pragma unroll
+                        for (int d = 0; d < 2; ++d) {
+                            const long long Xn = X + (d == 0 ? 256 : 0), Yn = Y + (d == 0 ? 0 : 256);
+                            const double p0 = (double)edge_fn(t.x1, t.y1, t.x2, t.y2, Xn, Yn) * t.iz0;
+                            const double p1 = (double)edge_fn(t.x2, t.y2, t.x0, t.y0, Xn, Yn) * t.iz1;
+                            const double p2 = (double)edge_fn(t.x0, t.y0, t.x1, t.y1, Xn, Yn) * t.iz2;
+                            const double Qn = (p0 + p1) + p2;
+                            fine = fine && Qn > 0.0;
+                            dU[d] = interp(p0, p1, p2, Qn, u0, u1, u2) * (double)to.W0 - u * (double)to.W0;
+                            dV[d] = interp(p0, p1, p2, Qn, v0, v1, v2) * (double)to.H0 - v * (double)to.H0;
+                        }
+                        const double ra = dU[0] * dU[0] + dV[0] * dV[0], rb = dU[1] * dU[1] + dV[1] * dV[1];
+                        const int level = fine ? tex_level(ra >= rb ? ra : (rb > ra ? rb : ra + rb), to.L) : to.L - 1;        // the larger; NaN if either is
+                        const uint32_t c = tex_fetch(ta.tex, to, level, u, v, ta.flip_v);
+                        r = (int)fmin(255.0, floor((double)(c & 255u) * k + 0.5));
+                        g = (int)fmin(255.0, floor((double)((c >> 8) & 255u) * k + 0.5));
+                        bl = (int)fmin(255.0, floor((double)((c >> 16) & 255u) * k + 0.5));
+                    }
+                } else {
+                    r = (int)fmin(255.0, floor(interp(q0, q1, q2, Q, (double)c0[0], (double)c1[0], (double)c2[0]) * k + 0.5));
+                    g = (int)fmin(255.0, floor(interp(q0, q1, q2, Q, (double)c0[1], (double)c1[1], (double)c2[1]) * k + 0.5));
+                    bl = (int)fmin(255.0, floor(interp(q0, q1, q2, Q, (double)c0[2], (double)c1[2], (double)c2[2]) * k + 0.5));
+                }
             }
         }
         const long o = (long)b * P + p;
@@ -189,39 +247,49 @@ extern "C" size_t gdm_render_frames_workspace_bytes(int n, int S, int H, int W)
     return (size_t)n * S * H * W * sizeof(u64);
 }
 
-extern "C" int gdm_render_frames_hip(const void* verts, int verts_f64, const uint8_t* vcol, const float* vnrm, const int32_t* faces,
-                                     const int32_t* obj_face0, const int32_t* slot_obj, const double* RT, const double* K,
-                                     int k_per_instance, const double* light, double ambient, double near, int n, int S, int O, int Vt,
-                                     int Ft, int H, int W, void* workspace, size_t workspace_bytes, uint8_t* rgb, float* depth,
-                                     uint8_t* inst, int32_t* face, int32_t* stats, void* stream)
+namespace {
+
+// Both entries: the checks, the clear and visibility passes, and the resolve pass with (ta != nullptr) or without the texture branch.
+// `who` names the entry in a refusal.
+int render_frames(const char* who, const void* verts, int verts_f64, const uint8_t* vcol, const float* vnrm, const int32_t* faces,
+                  const int32_t* obj_face0, const int32_t* slot_obj, const double* RT, const double* K, int k_per_instance,
+                  const double* light, double ambient, double near, int n, int S, int O, int Vt, int Ft, int H, int W, void* workspace,
+                  size_t workspace_bytes, uint8_t* rgb, float* depth, uint8_t* inst, int32_t* face, int32_t* stats, const TexArgs* ta,
+                  void* stream)
 {
     GDM_CHECK_ARG(verts && vcol && vnrm && faces && obj_face0 && slot_obj && RT && K && light && workspace && rgb && depth && inst && face &&
                       stats,
-                  "gdm_render_frames_hip: NULL pointer");
-    GDM_CHECK_ARG(n >= 1 && n <= 65535, "gdm_render_frames_hip: n=%d not in [1, 65535]", n);
-    GDM_CHECK_ARG(S >= 1 && S <= GDM_RENDER_MAX_SLOTS, "gdm_render_frames_hip: S=%d not in [1, %d]", S, (int)GDM_RENDER_MAX_SLOTS);
-    GDM_CHECK_ARG(O >= 1 && O <= GDM_RENDER_MAX_OBJECTS, "gdm_render_frames_hip: O=%d not in [1, %d]", O, (int)GDM_RENDER_MAX_OBJECTS);
-    GDM_CHECK_ARG(Vt >= 1 && Ft >= 1, "gdm_render_frames_hip: Vt=%d Ft=%d must be positive", Vt, Ft);
-    GDM_CHECK_ARG(H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "gdm_render_frames_hip: H=%d W=%d not in [1, 16384]", H, W);
-    GDM_CHECK_ARG(near >= 0.0, "gdm_render_frames_hip: near=%g must be >= 0", near);
-    GDM_CHECK_ARG(ambient >= 0.0 && ambient <= 1.0, "gdm_render_frames_hip: ambient=%g not in [0, 1]", ambient);
-    GDM_CHECK_ARG(k_per_instance == 0 || k_per_instance == 1, "gdm_render_frames_hip: k_per_instance=%d must be 0 or 1", k_per_instance);
-    GDM_CHECK_ARG(verts_f64 == 0 || verts_f64 == 1, "gdm_render_frames_hip: verts_f64=%d must be 0 or 1", verts_f64);
+                  "%s: NULL pointer", who);
+    GDM_CHECK_ARG(n >= 1 && n <= 65535, "%s: n=%d not in [1, 65535]", who, n);
+    GDM_CHECK_ARG(S >= 1 && S <= GDM_RENDER_MAX_SLOTS, "%s: S=%d not in [1, %d]", who, S, (int)GDM_RENDER_MAX_SLOTS);
+    GDM_CHECK_ARG(O >= 1 && O <= GDM_RENDER_MAX_OBJECTS, "%s: O=%d not in [1, %d]", who, O, (int)GDM_RENDER_MAX_OBJECTS);
+    GDM_CHECK_ARG(Vt >= 1 && Ft >= 1, "%s: Vt=%d Ft=%d must be positive", who, Vt, Ft);
+    GDM_CHECK_ARG(H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "%s: H=%d W=%d not in [1, 16384]", who, H, W);
+    GDM_CHECK_ARG(near >= 0.0, "%s: near=%g must be >= 0", who, near);
+    GDM_CHECK_ARG(ambient >= 0.0 && ambient <= 1.0, "%s: ambient=%g not in [0, 1]", who, ambient);
+    GDM_CHECK_ARG(k_per_instance == 0 || k_per_instance == 1, "%s: k_per_instance=%d must be 0 or 1", who, k_per_instance);
+    GDM_CHECK_ARG(verts_f64 == 0 || verts_f64 == 1, "%s: verts_f64=%d must be 0 or 1", who, verts_f64);
+    if (ta) {
+        GDM_CHECK_ARG(ta->fuv && ta->tex && ta->tab, "%s: NULL pointer", who);
+        GDM_CHECK_ARG(ta->tex_texels >= 1 && ta->tex_texels < (1l << 31), "%s: tex_texels=%ld not in [1, 2^31)", who, ta->tex_texels);
+        GDM_CHECK_ARG(((uintptr_t)ta->tex & 3) == 0, "%s: tex must be 4-byte aligned", who);
+        GDM_CHECK_ARG(((uintptr_t)ta->tab & 7) == 0, "%s: tex_tab must be 8-byte aligned", who);
+        GDM_CHECK_ARG(ta->flip_v == 0 || ta->flip_v == 1, "%s: flip_v=%d must be 0 or 1", who, ta->flip_v);
+    }
     ObjTable tab = {};
     int Fmax = 0;
-    GDM_CHECK_ARG(obj_face0[0] >= 0, "gdm_render_frames_hip: obj_face0[0]=%d must be >= 0", obj_face0[0]);
+    GDM_CHECK_ARG(obj_face0[0] >= 0, "%s: obj_face0[0]=%d must be >= 0", who, obj_face0[0]);
     for (int o = 0; o < O; ++o) {
-        GDM_CHECK_ARG(obj_face0[o + 1] > obj_face0[o], "gdm_render_frames_hip: obj_face0 is not ascending at object %d (%d, then %d)", o,
-                      obj_face0[o], obj_face0[o + 1]);
+        GDM_CHECK_ARG(obj_face0[o + 1] > obj_face0[o], "%s: obj_face0 is not ascending at object %d (%d, then %d)", who, o, obj_face0[o],
+                      obj_face0[o + 1]);
         Fmax = obj_face0[o + 1] - obj_face0[o] > Fmax ? obj_face0[o + 1] - obj_face0[o] : Fmax;
     }
-    GDM_CHECK_ARG(obj_face0[O] <= Ft, "gdm_render_frames_hip: obj_face0[O]=%d exceeds Ft=%d", obj_face0[O], Ft);
+    GDM_CHECK_ARG(obj_face0[O] <= Ft, "%s: obj_face0[O]=%d exceeds Ft=%d", who, obj_face0[O], Ft);
     for (int o = 0; o <= O; ++o) tab.face0[o] = obj_face0[o];
-    GDM_CHECK_ARG((long)n * S * Fmax <= (1L << 30), "gdm_render_frames_hip: n=%d S=%d too large for an object of %d faces (n S F <= 2^30)",
-                  n, S, Fmax);
+    GDM_CHECK_ARG((long)n * S * Fmax <= (1L << 30), "%s: n=%d S=%d too large for an object of %d faces (n S F <= 2^30)", who, n, S, Fmax);
     const size_t need = gdm_render_frames_workspace_bytes(n, S, H, W);
-    GDM_CHECK_ARG(workspace_bytes >= need, "gdm_render_frames_hip: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    GDM_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "gdm_render_frames_hip: workspace must be 8-byte aligned");
+    GDM_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    GDM_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
     const hipStream_t s = (hipStream_t)stream;
     u64* keys = (u64*)workspace;
     const long count = (long)n * S * H * W;
@@ -231,20 +299,43 @@ extern "C" int gdm_render_frames_hip(const void* verts, int verts_f64, const uin
     if (rc) return rc;
     const dim3 vgrid(gdm_cdiv((long)n * S * Fmax, kThreads));
     const dim3 rgrid(gdm_cdiv((long)H * W, kThreads), n);
-    if (verts_f64) {
-        hipLaunchKernelGGL(vis_kernel<double>, vgrid, dim3(kThreads), 0, s, (const double*)verts, faces, slot_obj, tab, O, RT, K,
-                           k_per_instance, n, S, Vt, Fmax, H, W, near, keys);
+    gdm_dispatch_bool(verts_f64 != 0, [&](auto f64) {
+        using VT = std::conditional_t<decltype(f64)::value, double, float>;
+        hipLaunchKernelGGL((vis_kernel<VT>), vgrid, dim3(kThreads), 0, s, (const VT*)verts, faces, slot_obj, tab, O, RT, K, k_per_instance,
+                           n, S, Vt, Fmax, H, W, near, keys);
         rc = gdm_launch_status("vis_kernel");
-        if (rc) return rc;
-        hipLaunchKernelGGL(resolve_kernel<double>, rgrid, dim3(kThreads), 0, s, (const double*)verts, vcol, vnrm, faces, RT, K,
-                           k_per_instance, light, ambient, near, S, Vt, Ft, H, W, keys, rgb, depth, inst, face, stats);
-    } else {
-        hipLaunchKernelGGL(vis_kernel<float>, vgrid, dim3(kThreads), 0, s, (const float*)verts, faces, slot_obj, tab, O, RT, K,
-                           k_per_instance, n, S, Vt, Fmax, H, W, near, keys);
-        rc = gdm_launch_status("vis_kernel");
-        if (rc) return rc;
-        hipLaunchKernelGGL(resolve_kernel<float>, rgrid, dim3(kThreads), 0, s, (const float*)verts, vcol, vnrm, faces, RT, K,
-                           k_per_instance, light, ambient, near, S, Vt, Ft, H, W, keys, rgb, depth, inst, face, stats);
-    }
-    return gdm_launch_status("resolve_kernel");
+        if (rc) return;
+        if (ta)
+            hipLaunchKernelGGL((resolve_kernel<VT, true>), rgrid, dim3(kThreads), 0, s, (const VT*)verts, vcol, vnrm, faces, RT, K,
+                               k_per_instance, light, ambient, near, S, Vt, Ft, H, W, keys, rgb, depth, inst, face, stats, *ta);
+        else
+            hipLaunchKernelGGL((resolve_kernel<VT, false>), rgrid, dim3(kThreads), 0, s, (const VT*)verts, vcol, vnrm, faces, RT, K,
+                               k_per_instance, light, ambient, near, S, Vt, Ft, H, W, keys, rgb, depth, inst, face, stats, NoTex{});
+        rc = gdm_launch_status("resolve_kernel");
+    });
+    return rc;
+}
+
+} // namespace
+
+extern "C" int gdm_render_frames_hip(const void* verts, int verts_f64, const uint8_t* vcol, const float* vnrm, const int32_t* faces,
+                                     const int32_t* obj_face0, const int32_t* slot_obj, const double* RT, const double* K,
+                                     int k_per_instance, const double* light, double ambient, double near, int n, int S, int O, int Vt,
+                                     int Ft, int H, int W, void* workspace, size_t workspace_bytes, uint8_t* rgb, float* depth,
+                                     uint8_t* inst, int32_t* face, int32_t* stats, void* stream)
+{
+    return render_frames("gdm_render_frames_hip", verts, verts_f64, vcol, vnrm, faces, obj_face0, slot_obj, RT, K, k_per_instance, light,
+                         ambient, near, n, S, O, Vt, Ft, H, W, workspace, workspace_bytes, rgb, depth, inst, face, stats, nullptr, stream);
+}
+
+extern "C" int gdm_render_frames_tex_hip(const void* verts, int verts_f64, const uint8_t* vcol, const float* vnrm, const int32_t* faces,
+                                         const int32_t* obj_face0, const int32_t* slot_obj, const double* RT, const double* K,
+                                         int k_per_instance, const double* light, double ambient, double near, int n, int S, int O, int Vt,
+                                         int Ft, int H, int W, void* workspace, size_t workspace_bytes, uint8_t* rgb, float* depth,
+                                         uint8_t* inst, int32_t* face, int32_t* stats, const float* fuv, const void* tex,
+                                         const int64_t* tex_tab, long tex_texels, int flip_v, void* stream)
+{
+    const TexArgs ta = {fuv, (const uint32_t*)tex, tex_tab, slot_obj, tex_texels, O, flip_v};
+    return render_frames("gdm_render_frames_tex_hip", verts, verts_f64, vcol, vnrm, faces, obj_face0, slot_obj, RT, K, k_per_instance,
+                         light, ambient, near, n, S, O, Vt, Ft, H, W, workspace, workspace_bytes, rgb, depth, inst, face, stats, &ta, stream);
 }

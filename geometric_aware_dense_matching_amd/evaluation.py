@@ -431,22 +431,87 @@ def vsd_from_poses(verts, faces, RT_est, RT_gt, depth_test, K, delta, taus, diam
     return (errors, counts) if return_counts else errors
 
 
-def load_ply(path, attributes=False):
+def _ply_faces(f, path, fmt, count, props, np_type, texcoords):
+    """The `face` element: (faces i32[count,3], face texcoords f32[count,3,2] or None).  One list property of vertex indices; beside
+    it scalar properties (skipped) and a list property `texcoord` (MeshLab's six floats per face; read only with `texcoords`, and then
+    accepted only when every face has 3 indices and 6 coordinates)."""
+    lists = [p for p in props if p[0] == "list"]
+    index = [p for p in lists if p[3] in ("vertex_indices", "vertex_index")] or lists[:1]
+    other = [p for p in lists if p is not index[0] and p[3] != "texcoord"]
+    if len(index) != 1 or other:
+        raise ValueError("%s: element 'face' with list properties %s is not supported" % (path, [p[3] for p in lists]))
+    want = {id(index[0]): 3}
+    want.update({id(p): 6 for p in lists if p[3] == "texcoord"})
+    got = {}
+    if fmt == "ascii" and len(props) == 1:
+        rows = np.array([f.readline().split() for _ in range(count)], dtype=np.int64).reshape(count, -1)
+        if rows.shape[1] != 4:
+            raise ValueError("%s: faces must be triangles" % path)
+        got[id(index[0])] = (rows[:, 0], rows[:, 1:4])
+    elif fmt == "ascii":
+        cols = {id(p): ([], []) for p in lists}
+        for _ in range(count):
+            tok, at = f.readline().split(), 0
+            for p in props:
+                if p[0] != "list":
+                    at += 1
+                    continue
+                k = int(tok[at])
+                cols[id(p)][0].append(k)
+                cols[id(p)][1].append(tok[at + 1:at + 1 + k])
+                at += 1 + k
+        for p in lists:
+            cnt = np.asarray(cols[id(p)][0], dtype=np.int64)
+            ok = bool((cnt == want[id(p)]).all())
+            got[id(p)] = (cnt, np.asarray(cols[id(p)][1], dtype=np.float64).reshape(count, want[id(p)]) if ok else None)
+    else:                                                                  # binary: a fixed record, which the counts then confirm
+        fields = []
+        for k, p in enumerate(props):
+            if p[0] == "list":
+                fields += [("n%d" % k, "<" + np_type[p[1]]), ("v%d" % k, "<" + np_type[p[2]], (want[id(p)],))]
+            else:
+                fields.append(("s%d" % k, "<" + np_type[p[0]]))
+        dt = np.dtype(fields)
+        rec = np.frombuffer(f.read(count * dt.itemsize), dtype=dt, count=count)
+        for k, p in enumerate(props):
+            if p[0] == "list":
+                got[id(p)] = (rec["n%d" % k], rec["v%d" % k])
+    cnt, idx = got[id(index[0])]
+    if count and not (np.asarray(cnt) == 3).all():
+        raise ValueError("%s: faces must be triangles" % path)
+    faces = np.ascontiguousarray(idx).astype(np.int32).reshape(count, 3)
+    fuv = None
+    for p in lists:
+        if p[3] == "texcoord" and (texcoords or fmt != "ascii"):           # a binary record was read on the strength of these counts
+            cnt, val = got[id(p)]
+            if count and not (np.asarray(cnt) == 6).all():
+                raise ValueError("%s: the face property `texcoord` must hold 6 coordinates for every face (3 corners), found counts %s"
+                                 % (path, sorted(set(int(c) for c in np.asarray(cnt)))[:4]))
+            fuv = np.ascontiguousarray(val).astype(np.float32).reshape(count, 3, 2)
+    return faces, fuv
+
+
+def load_ply(path, attributes=False, texcoords=False):
     """The triangle meshes BOP ships, in pure numpy: ascii or binary_little_endian PLY with a `vertex` element whose properties include
-    x, y, z (further ones -- normals, colours, texture coordinates -- are skipped) and a `face` element that is one list property of
-    uchar / int (or uint) triples -> verts f64[V,3] (the file's unit: mm in BOP), faces i32[F,3].  attributes=True: also normals
-    f32[V,3] from nx, ny, nz and colors u8[V,3] from red, green, blue, each None when the file lacks one of its three properties."""
+    x, y, z and a `face` element with one list property of uchar / int (or uint) triples -> verts f64[V,3] (the file's unit: mm in
+    BOP), faces i32[F,3].  attributes=True: also normals f32[V,3] from nx, ny, nz and colors u8[V,3] from red, green, blue, each None
+    when the file lacks one of its three properties.  texcoords=True: also, at the end of the tuple, uv f32[F,3,2] -- one (u, v) per
+    face corner, from the vertex properties texture_u / texture_v (BOP's form; also u / v or s / t) gathered through the faces, or from
+    a face list property `texcoord` of six floats (MeshLab's form, which can hold a seam without doubled vertices) -- or None, and
+    texture_file, the name after `comment TextureFile`, or None.  The image itself is not read here (texture.load_texture)."""
     np_type = {"char": "i1", "uchar": "u1", "short": "i2", "ushort": "u2", "int": "i4", "uint": "u4", "float": "f4", "double": "f8",
                "int8": "i1", "uint8": "u1", "int16": "i2", "uint16": "u2", "int32": "i4", "uint32": "u4", "float32": "f4", "float64": "f8"}
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError("%s is not a PLY file" % path)
-        fmt, elements = None, []
+        fmt, elements, texture_file = None, [], None
         while True:
             line = f.readline()
             if not line:
                 raise ValueError("%s: PLY header without end_header" % path)
             tok = line.decode("ascii", "replace").split()
+            if len(tok) >= 3 and tok[0] == "comment" and tok[1] == "TextureFile" and texture_file is None:
+                texture_file = " ".join(tok[2:])
             if not tok or tok[0] in ("comment", "obj_info"):
                 continue
             if tok[0] == "format":
@@ -459,25 +524,13 @@ def load_ply(path, attributes=False):
                 break
         if fmt not in ("ascii", "binary_little_endian"):
             raise ValueError("%s: PLY format %r is not supported (ascii, binary_little_endian)" % (path, fmt))
-        verts = faces = normals = colors = None
+        verts = faces = normals = colors = vuv = fuv = None
         for name, count, props in elements:
             is_list = [p[0] == "list" for p in props]
-            if any(is_list) and (name != "face" or len(props) != 1):
+            if any(is_list) and name != "face":
                 raise ValueError("%s: element %r with list properties is not supported" % (path, name))
             if name == "face":
-                ct, it = np_type[props[0][1]], np_type[props[0][2]]
-                if fmt == "ascii":
-                    rows = np.array([f.readline().split() for _ in range(count)], dtype=np.int64).reshape(count, -1)
-                    cnt, idx = rows[:, 0], rows[:, 1:4]
-                    if rows.shape[1] != 4:
-                        raise ValueError("%s: faces must be triangles" % path)
-                else:
-                    rec = np.frombuffer(f.read(count * (np.dtype(ct).itemsize + 3 * np.dtype(it).itemsize)),
-                                        dtype=np.dtype([("n", "<" + ct), ("v", "<" + it, (3,))]), count=count)
-                    cnt, idx = rec["n"], rec["v"]
-                if count and not (cnt == 3).all():
-                    raise ValueError("%s: faces must be triangles" % path)
-                faces = np.ascontiguousarray(idx).astype(np.int32).reshape(count, 3)
+                faces, fuv = _ply_faces(f, path, fmt, count, props, np_type, texcoords)
             else:
                 names = [p[1] for p in props]
                 if fmt == "ascii":
@@ -493,9 +546,19 @@ def load_ply(path, attributes=False):
                         normals = np.stack([cols["nx"], cols["ny"], cols["nz"]], axis=1).astype(np.float32)
                     if attributes and all(k in cols for k in ("red", "green", "blue")):
                         colors = np.stack([cols["red"], cols["green"], cols["blue"]], axis=1).astype(np.uint8)
+                    for ku, kv in (("texture_u", "texture_v"), ("u", "v"), ("s", "t")):
+                        if texcoords and vuv is None and ku in cols and kv in cols:
+                            vuv = np.stack([cols[ku], cols[kv]], axis=1).astype(np.float32)
     if verts is None or faces is None:
         raise ValueError("%s: PLY without a vertex and a face element" % path)
-    return (verts, faces, normals, colors) if attributes else (verts, faces)
+    out = (verts, faces, normals, colors) if attributes else (verts, faces)
+    if not texcoords:
+        return out
+    if fuv is None and vuv is not None:
+        if len(faces) and (faces.min() < 0 or faces.max() >= len(vuv)):
+            raise ValueError("%s: a face index lies outside [0, %d)" % (path, len(vuv)))
+        fuv = np.ascontiguousarray(vuv[faces.astype(np.int64)])
+    return out + (fuv, texture_file)
 
 
 class BopScores:

@@ -6,7 +6,8 @@ farthest-point subset for every n.
            [--n-points 8192] [--candidates S] [--seed 0] [--source surface|vertices]
 
 The work runs on the GPU through three entries of include/gdm.h, each defined by a rule written there:
-  ops.surface_sample          area-weighted points on the triangles with interpolated colour and normal
+  ops.surface_sample          area-weighted points on the triangles with interpolated colour and normal (ops.surface_sample_tex for a
+                              mesh with texture coordinates and a texture image: the colour is fetched from the image)
   ops.furthestsampling_wide   the farthest-point order over all candidates (ops.furthestsampling below FPS_WIDE_MIN_N candidates)
   ops.point_diameter          the exact farthest pair, whose fp64 length is the `diameter` of models_info.json
 surface_sample_numpy, fps_numpy and point_diameter_numpy restate the three rules on the CPU, bit for bit; the tests hold the
@@ -40,6 +41,25 @@ def load_ply(path, attributes=True):
     """evaluation.load_ply with the vertex attributes: (verts f64[V,3], faces i32[F,3], normals f32[V,3] or None, colors u8[V,3] or
     None); attributes=False gives (verts, faces) alone."""
     return _load_ply(path, attributes=attributes)
+
+
+def load_mesh(path, verbose=False):
+    """A PLY file as the mesh dict build_model_points and render.SceneMeshes take: verts, faces, normals, colors (each of the last two
+    None when the file has none) and, for a file that carries texture coordinates and names an image (`comment TextureFile`) that
+    lies beside it, uv f32[F,3,2] and texture u8[H,W,3], with texture_file the path that was read.  An image that is named but
+    missing is said aloud (a warning) and the mesh stays untextured; a missing PIL is an error (texture.load_texture)."""
+    from . import texture
+    verts, faces, normals, colors, uv, name = _load_ply(path, attributes=True, texcoords=True)
+    mesh = dict(verts=verts, faces=faces, normals=normals, colors=colors)
+    if uv is not None and name:
+        image = os.path.join(os.path.dirname(os.path.abspath(path)), name)
+        if os.path.exists(image):
+            mesh.update(uv=uv, texture=texture.load_texture(image), texture_file=image)
+            if verbose:
+                print("%s: texture %s (%d x %d)" % (os.path.basename(path), image, mesh["texture"].shape[1], mesh["texture"].shape[0]))
+        else:
+            warnings.warn("%s names the texture %s, which does not exist: the mesh is read without it" % (path, image))
+    return mesh
 
 
 def vertex_normals_numpy(verts, faces):
@@ -77,8 +97,9 @@ def _mix32(x):
     return x ^ (x >> np.uint64(16))
 
 
-def surface_sample_numpy(verts, faces, vnrm, vrgb, cdf, S, seed=0):
-    """THE SAMPLE RULE of gdm_surface_sample_hip (include/gdm.h): f32[S,9] = xyz, rgb, normal, bit-equal to the kernel."""
+def surface_sample_numpy(verts, faces, vnrm, vrgb, cdf, S, seed=0, _draws=False):
+    """THE SAMPLE RULE of gdm_surface_sample_hip (include/gdm.h): f32[S,9] = xyz, rgb, normal, bit-equal to the kernel.  (_draws: also
+    the drawn faces and the fp32 weights w0, u, v as [S,1] columns, for surface_sample_tex_numpy.)"""
     verts, vnrm, vrgb = (np.ascontiguousarray(a, dtype=np.float32) for a in (verts, vnrm, vrgb))
     faces, cdf = np.asarray(faces, dtype=np.int64), np.asarray(cdf, dtype=np.int64)
     S = int(S)
@@ -108,6 +129,25 @@ def surface_sample_numpy(verts, faces, vnrm, vrgb, cdf, S, seed=0):
     n = out[:, 6:9]
     length = np.sqrt(((n[:, 0] * n[:, 0]) + (n[:, 1] * n[:, 1])) + (n[:, 2] * n[:, 2]))[:, None]
     out[:, 6:9] = np.divide(n, length, out=n.copy(), where=length > 0)
+    return (out, (f, w0, u, v)) if _draws else out
+
+
+def surface_sample_tex_numpy(verts, faces, vnrm, vrgb, cdf, fuv, tex, row, S, seed=0, flip_v=True):
+    """THE SAMPLE RULE of gdm_surface_sample_tex_hip (include/gdm.h): surface_sample_numpy's draws, xyz and normal; rgb = the texture's
+    level 0 at the (u, v) interpolated in fp32 from the face corners' fuv f32[F,3,2].  tex u8[T,4], row = (offset, W0, H0, L)."""
+    from . import texture
+    out, (f, w0, u, v) = surface_sample_numpy(verts, faces, vnrm, vrgb, cdf, S, seed, _draws=True)
+    off, W0, H0, L = (int(x) for x in row)
+    if W0 == 0:
+        return out
+    tex = np.asarray(tex)
+    if not texture.valid_row(row, len(tex)):
+        raise ValueError("surface_sample_tex_numpy: the row %s does not lie inside %d texels" % ((off, W0, H0, L), len(tex)))
+    fuv = np.ascontiguousarray(fuv, dtype=np.float32)
+    if fuv.shape != (len(faces), 3, 2):
+        raise ValueError("surface_sample_tex_numpy: fuv must be [F=%d,3,2], got %s" % (len(faces), fuv.shape))
+    t = ((w0 * fuv[f, 0]) + (u * fuv[f, 1])) + (v * fuv[f, 2])            # fp32 [S,2]
+    out[:, 3:6] = texture.fetch_numpy(tex, H0, W0, 0, t[:, 0].astype(np.float64), t[:, 1].astype(np.float64), flip_v, offset=off)
     return out
 
 
@@ -162,6 +202,14 @@ class _DeviceOps:
         return ops.surface_sample(cls._t(verts), cls._t(faces), cls._t(vnrm), cls._t(vrgb), cls._t(cdf), S, seed).cpu().numpy()
 
     @classmethod
+    def surface_sample_tex(cls, verts, faces, vnrm, vrgb, cdf, fuv, image, S, seed):
+        from . import ops, texture
+        tex = texture.build_mips(cls._t(image))
+        row = (0, image.shape[1], image.shape[0], texture.full_levels(*image.shape[:2]))
+        return ops.surface_sample_tex(cls._t(verts), cls._t(faces), cls._t(vnrm), cls._t(vrgb), cls._t(cdf), cls._t(fuv), tex, row, S, seed,
+                                      texture.FLIP_V).cpu().numpy()
+
+    @classmethod
     def fps(cls, xyz, m):
         from . import ops
         op = ops.furthestsampling_wide if len(xyz) >= FPS_WIDE_MIN_N else ops.furthestsampling
@@ -177,6 +225,12 @@ class _DeviceOps:
 class _NumpyOps:
     """The same three steps on the restatements (the tests' stand-in, and the reference the GPU pipeline is compared with)."""
     surface_sample = staticmethod(surface_sample_numpy)
+
+    @staticmethod
+    def surface_sample_tex(verts, faces, vnrm, vrgb, cdf, fuv, image, S, seed):
+        from . import texture
+        row = (0, image.shape[1], image.shape[0], texture.full_levels(*image.shape[:2]))
+        return surface_sample_tex_numpy(verts, faces, vnrm, vrgb, cdf, fuv, texture.build_mips_numpy(image), row, S, seed, texture.FLIP_V)
     fps = staticmethod(fps_numpy)
     point_diameter = staticmethod(point_diameter_numpy)
 
@@ -185,10 +239,13 @@ _impl = _DeviceOps          # the one hook: what runs the three steps
 
 
 def _mesh_arrays(mesh):
-    if isinstance(mesh, dict):
-        verts, faces, normals, colors = mesh["verts"], mesh["faces"], mesh.get("normals"), mesh.get("colors")
-    else:
-        verts, faces, normals, colors = load_ply(mesh)
+    """-> verts f64, faces i32, normals f32, colors f32 (levels), uv f32[F,3,2] or None, texture u8[H,W,3] or None.  With a texture
+    the colours are not read (zeros when the mesh has none): no grey, no warning."""
+    from . import texture as _texture
+    if not isinstance(mesh, dict):
+        mesh = load_mesh(mesh)
+    verts, faces, normals, colors = mesh["verts"], mesh["faces"], mesh.get("normals"), mesh.get("colors")
+    uv, image = mesh.get("uv"), mesh.get("texture")
     verts, faces = np.asarray(verts, dtype=np.float64), np.asarray(faces, dtype=np.int32)
     if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3 or not len(verts) or not len(faces):
         raise ValueError("a mesh needs verts [V,3] and faces [F,3], got %s and %s" % (verts.shape, faces.shape))
@@ -196,26 +253,47 @@ def _mesh_arrays(mesh):
         raise ValueError("face indices %d..%d outside the %d vertices" % (faces.min(), faces.max(), len(verts)))
     if normals is None:
         normals = vertex_normals_numpy(verts, faces)
+    if image is not None:
+        if uv is None:
+            raise ValueError("a mesh with a texture needs uv")
+        uv, image = np.asarray(uv, dtype=np.float32), _texture._image(image)
+        if uv.shape == (len(verts), 2):
+            uv = uv[faces]
+        if uv.shape != (len(faces), 3, 2):
+            raise ValueError("uv must be [F=%d,3,2] or [V=%d,2], got %s" % (len(faces), len(verts), uv.shape))
+        _texture.level_shapes(image.shape[0], image.shape[1])
+        if colors is None:
+            colors = np.zeros((len(verts), 3), dtype=np.uint8)
+    else:
+        uv = None
     if colors is None:
         warnings.warn("the mesh has no vertex colours: every rgb channel of the model file becomes 128")
         colors = np.full((len(verts), 3), 128, dtype=np.uint8)
-    return verts, faces, np.asarray(normals, dtype=np.float32), np.asarray(colors).astype(np.float32)
+    return verts, faces, np.asarray(normals, dtype=np.float32), np.asarray(colors).astype(np.float32), uv, image
 
 
 def build_model_points(mesh, n_points, candidates=None, seed=0, source="surface"):
     """The model table of a mesh: f32[n_points,9] = xyz (the mesh's unit: mm in BOP), rgb 0..255, unit normal, rows in
     farthest-point order from candidate 0 -- so the first k rows are the table of n_points = k FOR THE SAME CANDIDATES.
-    mesh: a PLY path, or {"verts", "faces"[, "normals", "colors"]}.  source "surface": `candidates` (default 32 * n_points) points
-    drawn on the triangles by area; "vertices": the mesh's own vertices with their attributes (V >= n_points)."""
+    mesh: a PLY path, or {"verts", "faces"[, "normals", "colors", "uv", "texture"]}.  source "surface": `candidates` (default
+    32 * n_points) points drawn on the triangles by area; "vertices": the mesh's own vertices with their attributes (V >= n_points).
+    A mesh with "uv" (f32[F,3,2] per face corner, or [V,2]) and "texture" (u8[H,W,3]) -- a PLY that names a TextureFile beside it --
+    takes its rgb from the texture (ops.surface_sample_tex); that needs source "surface": a per-corner uv has no single value at a
+    vertex."""
     n_points = int(n_points)
-    verts, faces, normals, colors = _mesh_arrays(mesh)
+    verts, faces, normals, colors, uv, image = _mesh_arrays(mesh)
+    if image is not None and source == "vertices":
+        raise ValueError("source='vertices' cannot colour a textured mesh (a per-corner uv has no single vertex value): use 'surface'")
     if n_points < 1:
         raise ValueError("n_points=%d must be at least 1" % n_points)
     if source == "surface":
         S = 32 * n_points if candidates is None else int(candidates)
         if S < n_points:
             raise ValueError("candidates=%d is fewer than n_points=%d" % (S, n_points))
-        cand = _impl.surface_sample(verts.astype(np.float32), faces, normals, colors, face_cdf(verts, faces), S, seed)
+        if image is not None:
+            cand = _impl.surface_sample_tex(verts.astype(np.float32), faces, normals, colors, face_cdf(verts, faces), uv, image, S, seed)
+        else:
+            cand = _impl.surface_sample(verts.astype(np.float32), faces, normals, colors, face_cdf(verts, faces), S, seed)
     elif source == "vertices":
         if len(verts) < n_points:
             raise ValueError("source='vertices' needs at least n_points=%d vertices, the mesh has %d" % (n_points, len(verts)))
@@ -258,9 +336,9 @@ def main(argv=None):
             info = {int(k): v for k, v in json.load(f).items()}
     os.makedirs(args.out_dir, exist_ok=True)
     for obj in ids:
-        verts, faces, normals, colors = load_ply(os.path.join(args.models_dir, "obj_%06d.ply" % obj))
-        table = build_model_points({"verts": verts, "faces": faces, "normals": normals, "colors": colors}, args.n_points,
-                                   candidates=args.candidates, seed=args.seed, source=args.source)
+        mesh = load_mesh(os.path.join(args.models_dir, "obj_%06d.ply" % obj))
+        verts, faces = mesh["verts"], mesh["faces"]
+        table = build_model_points(mesh, args.n_points, candidates=args.candidates, seed=args.seed, source=args.source)
         out = os.path.join(args.out_dir, "obj_%06d_fps.npy" % obj)
         np.save(out, table)
         diameter = model_diameter(verts)
@@ -268,6 +346,8 @@ def main(argv=None):
         if "diameter" in info.get(obj, {}):
             rec = float(info[obj]["diameter"])
             line += " (models_info.json: %.6f, relative difference %.3e)" % (rec, abs(diameter - rec) / rec)
+        if mesh.get("texture_file"):
+            line += ", rgb from the texture %s" % mesh["texture_file"]
         print(line)
     return 0
 

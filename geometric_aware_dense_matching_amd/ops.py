@@ -17,6 +17,8 @@ Operator <-> reference map (file:line under /root/reference):
   ballquery / furthestsampling   lib/pointops/functions/pointops.py:205-219, 40-50
   surface_sample / furthestsampling_wide / point_diameter   the producer of obj_%06d_fps.npy, which the reference names
                          (ref/ycbv.py:106) and does not ship: model_prep.py, DESIGN.md 6n
+  texture_mips / render_frames(textures=...) / surface_sample_tex   no counterpart in the reference: texture maps by the written
+                         rule of include/gdm.h (texture.py)
 """
 import collections
 import ctypes
@@ -263,6 +265,12 @@ def surface_sample(verts, faces, vnrm, vrgb, cdf, S, seed=0):
     """S points on a triangle mesh by the sample rule of include/gdm.h (gdm_surface_sample_hip): verts, vnrm f32[V,3], vrgb u8 or
     f32[V,3] (integer levels), faces i32[F,3], cdf i64[F] = inclusive cumulative integer face weights -> f32[S,9] = xyz, rgb, normal.
     What the device cannot see is refused here: a face index outside [0, V) and a cdf that ends in 0 or decreases."""
+    return _surface_sample(verts, faces, vnrm, vrgb, cdf, S, seed, None)
+
+
+def _surface_sample(verts, faces, vnrm, vrgb, cdf, S, seed, textured):
+    """surface_sample and surface_sample_tex: the checks they share, then the entry; `textured` is None or the textured entry's extra
+    arguments in its order."""
     verts = _dev(verts, torch.float32, "verts")
     vnrm = _dev(vnrm, torch.float32, "vnrm")
     if isinstance(vrgb, torch.Tensor) and vrgb.dtype == torch.uint8:
@@ -283,8 +291,25 @@ def surface_sample(verts, faces, vnrm, vrgb, cdf, S, seed=0):
     if not 1 <= S < 1 << 31:
         raise ValueError("surface_sample: S=%d not in [1, 2^31)" % S)
     out = torch.empty((S, 9), dtype=torch.float32, device=verts.device)
-    call("gdm_surface_sample_hip", verts, faces, vnrm, vrgb, cdf, V, F, S, int(seed) & 0xffffffff, out)
+    if textured is None:
+        call("gdm_surface_sample_hip", verts, faces, vnrm, vrgb, cdf, V, F, S, int(seed) & 0xffffffff, out)
+    else:
+        call("gdm_surface_sample_tex_hip", verts, faces, vnrm, vrgb, cdf, *textured, V, F, S, int(seed) & 0xffffffff, out)
     return out
+
+
+def surface_sample_tex(verts, faces, vnrm, vrgb, cdf, fuv, tex, row, S, seed=0, flip_v=True):
+    """surface_sample for a textured mesh (gdm_surface_sample_tex_hip): fuv f32[F,3,2], tex u8[T,4] on the device, row = the object's
+    (offset, W0, H0, L) as host integers.  The same draws, xyz and normals; rgb is the texture's level 0 at the interpolated (u, v)."""
+    fuv = _dev(fuv, torch.float32, "fuv")
+    tex = _dev(tex, torch.uint8, "tex")
+    F = faces.shape[0]
+    if tuple(fuv.shape) != (F, 3, 2):
+        raise ValueError("surface_sample_tex: fuv must be [F=%d,3,2], got %s" % (F, tuple(fuv.shape)))
+    if tex.dim() != 2 or tex.shape[1] != 4 or not 1 <= tex.shape[0] < 1 << 31:
+        raise ValueError("surface_sample_tex: tex must be u8[T,4] with 1 <= T < 2^31, got %s" % (tuple(tex.shape),))
+    off, W0, H0, L = (int(v) for v in row)
+    return _surface_sample(verts, faces, vnrm, vrgb, cdf, S, seed, (fuv, tex, off, W0, H0, L, tex.shape[0], int(bool(flip_v))))
 
 
 def point_diameter(xyz):
@@ -2595,12 +2620,13 @@ RENDER_MAX_SLOTS = 8          # GDM_RENDER_MAX_SLOTS / GDM_RENDER_MAX_OBJECTS of
 RENDER_MAX_OBJECTS = 256
 
 
-def render_frames(verts, vcol, vnrm, faces, obj_face0, slot_obj, RT, K, light, H, W, ambient, near):
+def render_frames(verts, vcol, vnrm, faces, obj_face0, slot_obj, RT, K, light, H, W, ambient, near, textures=None):
     """Colour, depth, instance mask, face ids and per-slot statistics of n frames of S posed objects by the rule of include/gdm.h
     (gdm_render_frames_hip): verts f32|f64[Vt,3], vcol u8[Vt,3], vnrm f32[Vt,3], faces i32[Ft,3] on the device; obj_face0 a HOST
     sequence of O+1 ascending face offsets; slot_obj i32[n,S] (-1: empty), RT f64[n,S,3,4], K f64[3,3] or f64[n,3,3], light f64[n,3]
     -> rgb u8[n,H,W,3], depth f32[n,H,W], inst u8[n,H,W], face i32[n,H,W], stats i32[n,S,6] = (px_all, px_vis, xmin, ymin, xmax,
-    ymax).  render.render_frames is the interface with defaults and the derived outputs."""
+    ymax).  render.render_frames is the interface with defaults and the derived outputs.  textures = (fuv f32[Ft,3,2], tex u8[T,4],
+    tex_tab i64[O,4], flip_v), all three tensors on the device: the textured entry (gdm_render_frames_tex_hip) instead."""
     if not isinstance(verts, torch.Tensor) or verts.dtype not in (torch.float32, torch.float64):
         _dev(verts, torch.float32, "verts")
         raise TypeError("verts must be float32 or float64")
@@ -2643,6 +2669,36 @@ def render_frames(verts, vcol, vnrm, faces, obj_face0, slot_obj, RT, K, light, H
     inst = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
     face = torch.empty((n, H, W), dtype=torch.int32, device=dev)
     stats = torch.empty((n, S, 6), dtype=torch.int32, device=dev)
-    call("gdm_render_frames_hip", verts, int(verts.dtype == torch.float64), vcol, vnrm, faces, (ctypes.c_int32 * (O + 1))(*table), slot_obj,
-         RT, K, kpi, light, float(ambient), float(near), n, S, O, Vt, faces.shape[0], H, W, ws, nbytes, rgb, depth, inst, face, stats)
+    args = (verts, int(verts.dtype == torch.float64), vcol, vnrm, faces, (ctypes.c_int32 * (O + 1))(*table), slot_obj, RT, K, kpi, light,
+            float(ambient), float(near), n, S, O, Vt, faces.shape[0], H, W, ws, nbytes, rgb, depth, inst, face, stats)
+    if textures is None:
+        call("gdm_render_frames_hip", *args)
+    else:
+        fuv, tex, tex_tab, flip_v = textures
+        fuv = _dev(fuv, torch.float32, "fuv")
+        tex = _dev(tex, torch.uint8, "tex")
+        tex_tab = _dev(tex_tab, torch.int64, "tex_tab")
+        if tuple(fuv.shape) != (faces.shape[0], 3, 2):
+            raise ValueError("fuv must be [Ft=%d,3,2], got %s" % (faces.shape[0], tuple(fuv.shape)))
+        if tex.dim() != 2 or tex.shape[1] != 4 or not 1 <= tex.shape[0] < 1 << 31:
+            raise ValueError("tex must be u8[T,4] with 1 <= T < 2^31, got %s" % (tuple(tex.shape),))
+        if tuple(tex_tab.shape) != (O, 4):
+            raise ValueError("tex_tab must be [O=%d,4], got %s" % (O, tuple(tex_tab.shape)))
+        call("gdm_render_frames_tex_hip", *args, fuv, tex, tex_tab, tex.shape[0], int(bool(flip_v)))
     return rgb, depth, inst, face, stats
+
+
+def texture_mips(image, L=None):
+    """The texture pyramid of image u8[H,W,3] (device) by THE TEXTURE RULE of include/gdm.h (gdm_texture_mips_hip): u8[T,4], level 0
+    the image, every further level the 2 x 2 mean of the one before; L levels, default all 1 + floor(log2(max(W, H)))."""
+    image = _dev(image, torch.uint8, "image")
+    if image.dim() != 3 or image.shape[2] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError("image must be u8[H,W,3], got %s" % (tuple(image.shape),))
+    H, W = image.shape[:2]
+    L = max(H, W).bit_length() if L is None else int(L)
+    T = call("gdm_texture_pyramid_texels", H, W, L)
+    if T == 0:
+        raise ValueError("texture_mips: H=%d W=%d L=%d outside what gdm_texture_mips_hip builds" % (H, W, L))
+    pyr = torch.empty((T, 4), dtype=torch.uint8, device=image.device)
+    call("gdm_texture_mips_hip", image, H, W, L, pyr, T)
+    return pyr

@@ -1,10 +1,12 @@
 """RGB-D training frames from triangle meshes on the GPU (gdm_render_frames_hip), and training batches made of them.
 
-  SceneMeshes            O meshes packed into one vertex / face table (on the device, and on the host for the restatement)
+  SceneMeshes            O meshes packed into one vertex / face table (on the device, and on the host for the restatement); a mesh
+                         may carry uv per face corner and a texture image (texture.py; gdm_render_frames_tex_hip)
   render_frames          n frames of S posed objects -> rgb, depth, inst, face, px_all, px_vis, bbox_vis, visib_fract (two kernels)
   render_frames_numpy    the written rule of include/gdm.h on the host, bit for bit, plus `ambiguous` (where the rule's minimum is
                          decided by less than 2 fp32 ulp of depth, so a one-ulp difference in a division could change the winner)
   demo_mesh              a bumpy, coloured subdivided icosahedron, about 0.1 across: an object to train on without any file
+                         (textured=True: the same solid with a seamed spherical uv and a hash-drawn image instead of vertex colours)
   backdrop_mesh          a coloured vertex-grid plane behind the objects, so that a frame has valid depth everywhere
   sample_scene_poses     counter-based pose draws on the host: the target in slot 0, distractors (some in front of it) in the others
   RenderedFrames         an iterable of training batches: poses -> render -> frontend.make_inputs_from_boxes -> + RT; the labels,
@@ -30,13 +32,19 @@ class SceneMeshes:
     `model_prep.load_ply(path)` is (verts, faces, normals, colours): use `SceneMeshes.from_ply` for files --, concatenated:
     verts f32 (or f64 with verts_dtype) [Vt,3], vcol u8[Vt,3], vnrm f32[Vt,3], faces i32[Ft,3] indexing the concatenated vertices,
     obj_face0 = the O+1 face offsets.  Missing normals are model_prep.vertex_normals_numpy's, missing colours grey (128).  `scale`
-    multiplies the vertices (0.001: a BOP mesh in mm -> metres).  device=None keeps the host arrays only (the restatement's input)."""
+    multiplies the vertices (0.001: a BOP mesh in mm -> metres).  device=None keeps the host arrays only (the restatement's input).
+    A mesh tuple may carry a 5th and a 6th item, uv f32[F,3,2] (one (u, v) per face corner; or per vertex, [V,2], gathered through
+    the faces) and texture u8[H,W,3]: the object is then coloured from the texture by THE TEXTURE RULE of include/gdm.h (texture.py)
+    and its vertex colours are not read.  The scene packs fuv f32[Ft,3,2] (zeros for the other objects), every pyramid into one
+    texel buffer tex u8[T,4] and tex_tab i64[O,4] = (offset, W0, H0, L), all zero for an object without a texture; has_texture says
+    whether any object has one, flip_v (texture.FLIP_V) is the scene's reading of v."""
 
-    def __init__(self, meshes, device="cuda", verts_dtype=np.float32, scale=1.0):
-        from . import model_prep
+    def __init__(self, meshes, device="cuda", verts_dtype=np.float32, scale=1.0, flip_v=None):
+        from . import model_prep, texture
         if not meshes:
             raise ValueError("SceneMeshes needs at least one mesh")
         verts, faces, cols, nrms, face0, v0 = [], [], [], [], [0], 0
+        fuvs, textures = [], []
         for k, m in enumerate(meshes):
             v, f = np.asarray(m[0], dtype=np.float64) * float(scale), np.asarray(m[1]).astype(np.int64)
             c = m[2] if len(m) > 2 else None
@@ -49,6 +57,20 @@ class SceneMeshes:
             c = np.full((len(v), 3), 128, dtype=np.uint8) if c is None else np.asarray(c)
             if c.shape != v.shape or nr.shape != v.shape:
                 raise ValueError("mesh %d: colours and normals must be [V=%d,3]" % (k, len(v)))
+            uv = m[4] if len(m) > 4 else None
+            tx = m[5] if len(m) > 5 else None
+            if tx is not None:
+                if uv is None:
+                    raise ValueError("mesh %d: a texture needs uv" % k)
+                uv = np.asarray(uv, dtype=np.float32)
+                if uv.shape == (len(v), 2):
+                    uv = uv[f]
+                if uv.shape != (len(f), 3, 2):
+                    raise ValueError("mesh %d: uv must be [F=%d,3,2] or [V=%d,2], got %s" % (k, len(f), len(v), uv.shape))
+                tx = texture._image(tx)
+                texture.level_shapes(tx.shape[0], tx.shape[1])          # refuses a side outside [1, 16384]
+            fuvs.append(np.zeros((len(f), 3, 2), dtype=np.float32) if tx is None else uv)
+            textures.append(tx)
             verts.append(v)
             faces.append(f + v0)
             cols.append(np.clip(np.floor(c.astype(np.float64) + 0.5), 0, 255).astype(np.uint8))
@@ -61,24 +83,29 @@ class SceneMeshes:
         self.faces_np = np.ascontiguousarray(np.concatenate(faces).astype(np.int32))
         self.obj_face0 = face0
         self.n_objects = len(meshes)
+        self.has_texture = any(t is not None for t in textures)
+        self.flip_v = texture.FLIP_V if flip_v is None else bool(flip_v)
+        self.fuv_np = np.ascontiguousarray(np.concatenate(fuvs))
+        self.tex_np, self.tex_tab_np = texture.pack_table(textures)
         self.device = None if device is None else torch.device(device)
         if self.device is not None:
             self.verts, self.vcol, self.vnrm, self.faces = (torch.from_numpy(a).to(self.device) for a in
                                                             (self.verts_np, self.vcol_np, self.vnrm_np, self.faces_np))
+            if self.has_texture:                                           # the pyramids are built on the device, image by image
+                self.fuv, self.tex_tab = torch.from_numpy(self.fuv_np).to(self.device), torch.from_numpy(self.tex_tab_np).to(self.device)
+                self.tex = torch.cat([texture.build_mips(torch.from_numpy(t).to(self.device)) for t in textures if t is not None])
 
     @classmethod
     def from_ply(cls, paths, **kw):
+        """The meshes of PLY files; a file that names a texture (`comment TextureFile`) and carries uv is drawn with the image of that
+        name beside it (model_prep.load_mesh)."""
         from . import model_prep
-        meshes = []
-        for p in paths:
-            v, f, nr, c = model_prep.load_ply(p)
-            meshes.append((v, f, c, nr))
-        return cls(meshes, **kw)
+        return cls([_as_mesh(model_prep.load_mesh(p)) for p in paths], **kw)
 
 
 def _as_mesh(m):
-    """A demo_mesh / backdrop_mesh dict as the tuple SceneMeshes takes."""
-    return (m["verts"], m["faces"], m["colors"], m["normals"])
+    """A mesh dict (demo_mesh, backdrop_mesh, model_prep.load_mesh) as the tuple SceneMeshes takes."""
+    return (m["verts"], m["faces"], m.get("colors"), m.get("normals"), m.get("uv"), m.get("texture"))
 
 
 def _np(a, dtype):
@@ -123,15 +150,19 @@ def render_frames(scene, slot_obj, RT, K, H, W, light=None, ambient=AMBIENT, nea
     if light is None or not torch.is_tensor(light):
         light = torch.from_numpy(_light(light, n))
     light = light.to(device=dev, dtype=torch.float64).expand(n, 3).contiguous()
+    textures = (scene.fuv, scene.tex, scene.tex_tab, scene.flip_v) if scene.has_texture else None
     rgb, depth, inst, face, stats = ops.render_frames(scene.verts, scene.vcol, scene.vnrm, scene.faces, scene.obj_face0, slot_obj,
-                                                      RT.contiguous(), K.contiguous(), light, H, W, ambient, near)
+                                                      RT.contiguous(), K.contiguous(), light, H, W, ambient, near, textures=textures)
     return _outputs(rgb, depth, inst, face, stats, torch)
 
 
 def render_frames_numpy(scene, slot_obj, RT, K, H, W, light=None, ambient=AMBIENT, near=NEAR):
     """The rule of gdm_render_frames_hip (include/gdm.h) on the host, operation for operation in fp64: the dict of
     render_frames as numpy arrays (coverage and depth from pixel_rule.covered) plus `ambiguous` bool[n,H,W]: the pixels whose two best candidate depths, over all faces and
-    slots, lie within 2 fp32 ulp of each other -- where the winner is not robust against the last bit of a division."""
+    slots, lie within 2 fp32 ulp of each other -- where the winner is not robust against the last bit of a division.  A scene with a
+    texture is coloured by THE TEXTURE RULE (texture.py) where the winner's object has one, and then also returns `tex_level`
+    i8[n,H,W]: the pyramid level every such pixel fetched from, -1 elsewhere."""
+    from . import texture
     verts = scene.verts_np.astype(np.float64)
     vcol, vnrm = scene.vcol_np.astype(np.float64), scene.vnrm_np.astype(np.float64)
     faces, face0, O = scene.faces_np.astype(np.int64), scene.obj_face0, scene.n_objects
@@ -166,6 +197,7 @@ def render_frames_numpy(scene, slot_obj, RT, K, H, W, light=None, ambient=AMBIEN
     depth = np.where(empty, 0, best_bits).astype(np.uint32).view(np.float32)
     stats = np.zeros((n, S, 6), dtype=np.int32)
     rgb = np.zeros((n, H, W, 3), dtype=np.uint8)
+    tex_level = np.full((n, H, W), -1, dtype=np.int8)
     for b in range(n):
         for s in range(S):
             rows, cols = np.nonzero(inst[b] == s + 1)
@@ -195,12 +227,52 @@ def render_frames_numpy(scene, slot_obj, RT, K, H, W, light=None, ambient=AMBIEN
             with np.errstate(all="ignore"):
                 cs = np.where(length > 0, np.maximum(((nx * light[b, 0] + ny * light[b, 1]) + nz * light[b, 2]) / length, 0.0), 0.0)
             k = ambient + (1.0 - ambient) * cs
+            row = scene.tex_tab_np[int(slot_obj[b, s])] if scene.has_texture else None
+            if row is not None and texture.valid_row(row, len(scene.tex_np)):
+                texel, tex_level[b, rows, cols] = _textured_levels(scene, row, q, Q, (i0, i1, i2), A2 < 0, face[b, rows, cols], xs, ys,
+                                                                   iz, PX, PY)
+                for ch in range(3):
+                    rgb[b, rows, cols, ch] = np.minimum(255.0, np.floor(texel[:, ch].astype(np.float64) * k + 0.5)).astype(np.uint8)
+                continue
             for ch in range(3):
                 rgb[b, rows, cols, ch] = np.minimum(255.0, np.floor(interp(vcol[:, ch]) * k + 0.5)).astype(np.uint8)
     out = _outputs(rgb, depth, inst, face, stats, np)
     gap = d2.view(np.int32).astype(np.int64) - d1.view(np.int32).astype(np.int64)
     out["ambiguous"] = np.isfinite(d2) & (gap <= 2)
+    if scene.has_texture:
+        out["tex_level"] = tex_level
     return out
+
+
+def _textured_levels(scene, row, q, Q, tri, swapped, fidx, xs, ys, iz, PX, PY):
+    """The textured branch of the resolve pass for the pixels of one slot: q, Q the pixel's perspective weights, tri = (i0, i1, i2)
+    with the winding's swap applied, swapped where it was, fidx the winning faces, (PX, PY) the pixels in 1/256 px -> the fetched
+    colour levels u8[P,3] before shading, and the pyramid level i64[P] of each.  Operation for operation what resolve_kernel<VT, true> does."""
+    from . import texture
+    off, W0, H0, L = (int(x) for x in row)
+    i0, i1, i2 = tri
+    uv = scene.fuv_np.astype(np.float64)[fidx]                             # [P,3,2]: the corners follow the winding
+    c0, c1, c2 = uv[:, 0], np.where(swapped[:, None], uv[:, 2], uv[:, 1]), np.where(swapped[:, None], uv[:, 1], uv[:, 2])
+
+    def at(qq, QQ, ch):
+        return ((qq[0] * c0[:, ch] + qq[1] * c1[:, ch]) + qq[2] * c2[:, ch]) / QQ
+
+    u, v = at(q, Q, 0), at(q, Q, 1)
+    fine, d = np.ones(len(u), dtype=bool), []
+    with np.errstate(all="ignore"):
+        for dx, dy in ((256, 0), (0, 256)):
+            qn = [pixel_rule.edge(xs, ys, a, c, PX + dx, PY + dy).astype(np.float64) * iz[opp]
+                  for a, c, opp in ((i1, i2, i0), (i2, i0, i1), (i0, i1, i2))]
+            Qn = (qn[0] + qn[1]) + qn[2]
+            fine &= Qn > 0.0
+            d.append((at(qn, Qn, 0) * float(W0), at(qn, Qn, 1) * float(H0)))
+        U, V = u * float(W0), v * float(H0)
+        level = texture.mip_level_numpy(U, V, d[0][0], d[0][1], d[1][0], d[1][1], L, fine)
+    out = np.zeros((len(u), 3), dtype=np.uint8)
+    for l in np.unique(level):
+        m = level == l
+        out[m] = texture.fetch_numpy(scene.tex_np, H0, W0, int(l), u[m], v[m], scene.flip_v, offset=off)
+    return out, level
 
 
 # ---- built-in meshes ---------------------------------------------------------------------------------------------------------------
@@ -215,11 +287,12 @@ def _uniform(seed, index, j):
     return _mix32(base ^ np.uint32(((j + 1) * 0x9E3779B9) & 0xFFFFFFFF)).astype(np.float64) / 4294967296.0
 
 
-def demo_mesh(level=3, seed=0):
+def demo_mesh(level=3, seed=0, textured=False, tex_size=64):
     """A bumpy subdivided icosahedron with hash-drawn vertex colours: 20 * 4**level faces, diameter about 0.1 (metres), no symmetry.
     The colours are drawn per vertex of the once-subdivided solid (42 of them) and averaged onto the finer vertices, so that they
     vary over the surface more slowly than the sampling does.  -> dict(verts f64[V,3], faces i32[F,3], normals f32[V,3], colors
-    u8[V,3]), the mesh dict model_prep.build_model_points takes."""
+    u8[V,3]), the mesh dict model_prep.build_model_points takes.  textured=True: the same solid as a textured object without any
+    file -- colors None, uv f32[F,3,2] and texture u8[tex_size, 2 tex_size, 3] (_demo_texture)."""
     from . import model_prep
     level = int(level)
     if not 0 <= level <= 7:
@@ -260,7 +333,35 @@ def demo_mesh(level=3, seed=0):
     verts = d * bump[:, None] * np.array([0.05, 0.042, 0.034])
     faces = np.asarray(f, dtype=np.int32)
     normals = model_prep.vertex_normals_numpy(verts, faces).astype(np.float32)
+    if textured:
+        uv, image = _demo_texture(d, faces, seed, int(tex_size))
+        return dict(verts=verts, faces=faces, normals=normals, colors=None, uv=uv, texture=image)
     return dict(verts=verts, faces=faces, normals=normals, colors=np.floor(np.asarray(col) + 0.5).astype(np.uint8))
+
+
+def _demo_texture(d, faces, seed, size):
+    """A seamed spherical parametrisation of the unit directions d f64[V,3] per face CORNER, and a hash-drawn image for it.  The
+    longitude of a vertex is one number, so a face that straddles longitude +-pi gets 1 added at its corners on the low side: the seam
+    lives in the corners and no vertex is doubled.  Fetches clamp to the edge and never wrap, so the longitude is mapped to u in [0, 1/2)
+    (up to 3/4 on a seam face) and the image's right half repeats its left half.  v = colatitude / pi; a pole corner takes the mean u of
+    the face's other corners.  The image: size x 2 size texels, a colour drawn per block of 4 x 4 texels plus a per-texel grain."""
+    if size < 8 or size > 4096 or size % 4:
+        raise ValueError("tex_size=%d must be a multiple of 4 in [8, 4096]" % size)
+    lon = np.arctan2(d[:, 1], d[:, 0]) / (2.0 * np.pi) + 0.5               # [0, 1]
+    lat = np.arccos(np.clip(d[:, 2], -1.0, 1.0)) / np.pi
+    pole = np.abs(d[:, 2]) > 1.0 - 1e-12
+    fu, fv, fp = lon[faces], lat[faces], pole[faces]                       # [F,3]
+    span = np.where(fp, np.nan, fu)
+    wrap = (np.nanmax(span, axis=1) - np.nanmin(span, axis=1)) > 0.5
+    fu = np.where(wrap[:, None] & (fu < 0.5), fu + 1.0, fu)
+    mean = np.nanmean(np.where(fp, np.nan, fu), axis=1)
+    fu = np.where(fp, mean[:, None], fu)
+    uv = np.stack([fu * 0.5, fv], axis=-1).astype(np.float32)
+    by, bx = np.meshgrid(np.arange(size) // 4, np.arange(size) // 4, indexing="ij")
+    ty, tx = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
+    half = np.stack([np.floor(40.0 + 150.0 * _uniform(seed, (by * 1024 + bx).ravel() + 20000, ch)
+                              + 60.0 * _uniform(seed, (ty * 4096 + tx).ravel() + 9000000, ch)).reshape(size, size) for ch in range(3)], axis=-1)
+    return uv, np.ascontiguousarray(np.concatenate([half, half], axis=1).astype(np.uint8))
 
 
 def backdrop_mesh(K, H, W, z=1.5, grid=(4, 3), margin=8.0, seed=0):

@@ -406,8 +406,7 @@ def _rendered_meshes(args, cls_id):
     others = sorted(f for f in os.listdir(models_dir) if f.startswith("obj_") and f.endswith(".ply") and f != os.path.basename(ply))
     out = []
     for path in [ply] + [os.path.join(models_dir, f) for f in others[:RENDERED_DISTRACTORS]]:
-        v, f, nr, c = model_prep.load_ply(path)
-        out.append(dict(verts=v, faces=f, normals=nr, colors=c))
+        out.append(model_prep.load_mesh(path, verbose=True))               # with its texture, when the file names one beside it
     return out, 0
 
 
@@ -417,7 +416,7 @@ def make_rendered(args, split, cls_id, batch_size, device, keep_frames=False):
     also carry the depth frame and the target's box (--pose-verify)."""
     from . import render
     meshes, target = _rendered_meshes(args, cls_id)
-    packed = [(m["verts"], m["faces"], m.get("colors"), m.get("normals")) for m in meshes]
+    packed = [render._as_mesh(m) for m in meshes]
     packed.append(render._as_mesh(render.backdrop_mesh(synthetic.LM_K, 480, 640, z=1500.0)))
     scene = render.SceneMeshes(packed, device=device, scale=0.001)
     ds = dataset_config(args.dataset_name)

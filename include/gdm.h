@@ -1168,6 +1168,55 @@ int gdm_render_frames_hip(const void* verts, int verts_f64, const uint8_t* vcol,
                           int32_t* face, int32_t* stats, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Textures: the appearance of a mesh that carries (u, v) per face corner and an image instead of vertex colours (BOP's YCB-V, HB,
+ * TUD-L models; texture.py restates the rule in numpy bit for bit).  Parity with BOP's GL renderers is NOT claimed: the
+ * level choice is isotropic, one level per pixel without a trilinear blend, and blurs at grazing angles.
+ *
+ * THE TEXTURE RULE
+ *   storage   an object's texture is a pyramid of texels u8[T,4] = (r, g, b, 0), one dword each.  Level 0 is the image, W0 x H0, row
+ *             major, row 0 the image's top row; level l has W_l x H_l = max(1, W0 >> l) x max(1, H0 >> l) texels and follows level
+ *             l - 1 without a gap; 1 <= L <= 1 + floor(log2(max(W0, H0))) levels.  All objects' pyramids lie in one buffer of
+ *             tex_texels texels, 1 <= tex_texels < 2^31, 4-byte aligned.
+ *   table     tex_tab i64[O,4] = (offset in texels, W0, H0, L) per object; W0 = 0: no texture, the vertex colours.  DEVICE data the
+ *             entry cannot look at: a kernel uses a row only when W0, H0 in [1, 16384], L in [1, 1 + floor(log2(max(W0, H0)))],
+ *             offset >= 0 and offset + (the texels of the L levels) <= tex_texels; every other row counts as "no texture", and no
+ *             address outside the buffer is ever formed.
+ *   mips      texel (x, y) of level l = per channel (a + b + c + d + 2) >> 2 over the texels (2x, 2y), (2x+1, 2y), (2x, 2y+1),
+ *             (2x+1, 2y+1) of level l - 1, each index clamped to that level.
+ *   fetch     Fetch(l, u, v), fp64: x = u W_l - 0.5, y = (flip_v ? 1 - v : v) H_l - 0.5 (flip_v = 1, the default of a definition,
+ *             makes v = 0 the image's bottom row); x0 = floor(x), fx = (int) floor((x - x0) 256), likewise y0, fy; the texels
+ *             c00 = (x0, y0), c10 = (x0 + 1, y0), c01 = (x0, y0 + 1), c11 = (x0 + 1, y0 + 1) with every index clamped to the level
+ *             (clamp to edge); per channel ((c00 (256 - fx) + c10 fx) (256 - fy) + (c01 (256 - fx) + c11 fx) fy + 32768) >> 16.
+ *             A u or v that is not finite fetches texel (0, 0) of the level.
+ *   level     no transcendental.  With (U, V) = (u W0, v H0) at the pixel and at its neighbours (px + 1, py) and (px, py + 1):
+ *             dUx = Ux - U, dVx = Vx - V, dUy, dVy likewise; a = dUx dUx + dVx dVx, b = dUy dUy + dVy dVy; rho2 = the larger of a
+ *             and b, NaN when either is; the level is the smallest l with rho2 <= 4^l, capped at L - 1 (a NaN ends there too).
+ *
+ * gdm_texture_pyramid_texels(H, W, L): the texels of the L levels of an H x W image; 0 for what gdm_texture_mips_hip refuses.
+ * gdm_texture_mips_hip: image u8[H,W,3] -> pyr, pyr_texels >= gdm_texture_pyramid_texels(H, W, L) texels (4-byte aligned, below
+ * 2^31): level 0 packed, levels 1 .. L-1 built, one launch per level.  No memset node, no allocation, no host read. */
+long gdm_texture_pyramid_texels(int H, int W, int L);
+int gdm_texture_mips_hip(const uint8_t* image, int H, int W, int L, void* pyr, long pyr_texels, void* stream);
+/* gdm_render_frames_tex_hip: gdm_render_frames_hip with textures.  fuv f32[Ft,3,2]: a (u, v) for every corner of every face of the
+ * scene (those of untextured objects are not read); tex, tex_tab, tex_texels as above, one row per object of obj_face0; flip_v 0 or 1.
+ * The clear and visibility passes are those of gdm_render_frames_hip; so is everything the resolve pass writes but rgb at the pixels
+ * whose winning slot holds an object with a valid table row.  There:
+ *   corners     the face's three (u, v) in stored order; when the winding normalisation swapped vertices 1 and 2, corners 1 and 2 swap
+ *   uv          u and v by ((q0 a0 + q1 a1) + q2 a2) / Q, fp64, like every attribute
+ *   neighbours  the same with the face's edge values at (px + 1, py) and at (px, py + 1), whether or not the face covers them;
+ *               a neighbour whose Q is not > 0 sends the pixel to level L - 1
+ *   colour      c = Fetch(level, u, v) by THE TEXTURE RULE, then the shading of gdm_render_frames_hip per channel:
+ *               (u8) min(255, floor(c k + 0.5))
+ * A slot whose object has no valid row is coloured from vcol, bit for bit as gdm_render_frames_hip does; with no valid row at all
+ * the two entries write the same bytes.  Captures in a hipGraph. */
+int gdm_render_frames_tex_hip(const void* verts, int verts_f64, const uint8_t* vcol, const float* vnrm, const int32_t* faces,
+                              const int32_t* obj_face0 /* host array */, const int32_t* slot_obj, const double* RT, const double* K,
+                              int k_per_instance, const double* light, double ambient, double near, int n, int S, int O, int Vt, int Ft,
+                              int H, int W, void* workspace, size_t workspace_bytes, uint8_t* rgb, float* depth, uint8_t* inst,
+                              int32_t* face, int32_t* stats, const float* fuv, const void* tex, const int64_t* tex_tab, long tex_texels,
+                              int flip_v, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Object model preparation: from a triangle mesh to the table obj_%06d_fps.npy holds ([M,9] = xyz in mm, rgb 0..255, unit normal,
  * rows in farthest-point order; read by datasets/lm/linemod_pbr.py:89-97, evaluator.py:34-40, models/SplineCNN.py:116).  The script
  * that wrote the reference's files is not part of it, so each entry is defined by the rule written here, which model_prep.py
@@ -1190,6 +1239,15 @@ int gdm_render_frames_hip(const void* verts, int verts_f64, const uint8_t* vcol,
  * One thread per sample, no atomics: the result does not depend on the launch shape.  1 <= S < 2^31, V >= 1, F >= 1. */
 int gdm_surface_sample_hip(const float* verts, const int32_t* faces, const float* vnrm, const float* vrgb, const int64_t* cdf,
                            int V, int F, long S, uint32_t seed, float* out, void* stream);
+/* gdm_surface_sample_tex_hip: gdm_surface_sample_hip for a textured mesh.  fuv f32[F,3,2] (a (u, v) per face corner), tex and
+ * tex_texels as for gdm_render_frames_tex_hip, the object's table row BY VALUE (tex_off, tex_w, tex_h, tex_levels) and flip_v.  The
+ * row is host data here: one that THE TEXTURE RULE calls invalid is refused, and tex_w = 0 (no texture) gives gdm_surface_sample_hip's
+ * output.  Otherwise the same draws, and xyz and normal bit-equal to gdm_surface_sample_hip's for the same seed;
+ *   colour    tu = ((w0 * u_A) + (u * u_B)) + (v * u_C), tv likewise, fp32 single operations like every channel; rgb = the three
+ *             integers of Fetch(0, (double) tu, (double) tv): level 0, the samples are not pixels and have no footprint. */
+int gdm_surface_sample_tex_hip(const float* verts, const int32_t* faces, const float* vnrm, const float* vrgb, const int64_t* cdf,
+                               const float* fuv, const void* tex, int64_t tex_off, int64_t tex_w, int64_t tex_h, int64_t tex_levels,
+                               long tex_texels, int flip_v, int V, int F, long S, uint32_t seed, float* out, void* stream);
 /* gdm_fps_wide_hip: furthest point sampling for many candidates, spread over the whole device.  idx i32[B,m] equals what
  * gdm_furthestsampling_hip returns for the same xyz f32[B,n,3], bit for bit.  THE RULE both follow: pick 0 is index 0; dist starts
  * at 1e10; after pick p every candidate takes dist = fminf(dist, d2), d2 = ((dx * dx) + (dy * dy)) + (dz * dz) to p; the next pick
