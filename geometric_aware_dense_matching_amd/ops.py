@@ -2516,6 +2516,51 @@ def augment_crops(rgb, depth, mask=None, background=None, enable=None, seed=0):
 
 
 # --------------------------------------------------------------------------------------
+# a structured-light depth sensor on a depth frame (gdm_sensor.hip; sensor.py is the interface with names and defaults)
+# --------------------------------------------------------------------------------------
+def _header_enums(prefix):
+    """{name: value} of the `enum { NAME = int, ... };` constants of include/gdm.h whose names start with `prefix` (the header keeps
+    some limits as enumerators; _lib reads the #defines)."""
+    import re
+    with open(_lib.HEADER) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    found = {}
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for name, val in re.findall(r"\b(%s\w+)\s*=\s*(-?\d+)" % re.escape(prefix), body):
+            found[name] = int(val)
+    return found
+
+
+SENSOR = _header_enums("GDM_SENSOR_")          # the stage bits, GDM_SENSOR_MAX_DISP, GDM_SENSOR_TILE_W / _H, GDM_SENSOR_MAX_K
+
+
+def depth_sensor(depth, K, baseline, z_min, z_max, sigma_d, subpixel, cos_min, cos_soft, p_shift, stages, seed=0, out=None):
+    """THE SENSOR RULE of include/gdm.h (gdm_depth_sensor_hip), one launch: depth f32[n,H,W] on the device (metres), K a HOST
+    float32 tensor [3,3] or [n,3,3] (the library checks the shadow window from it before the launch), the rule's scalars, stages the
+    sum of the GDM_SENSOR_* stage bits, seed as for sample_assemble -> (out_depth f32[n,H,W], cause u8[n,H,W]).  out = (out_depth,
+    cause) to write into given tensors.  What the rule does not allow the library refuses (GdmError)."""
+    depth = _dev(depth, torch.float32, "depth")
+    if depth.dim() != 3:
+        raise ValueError("depth must be [n,H,W], got %s" % (tuple(depth.shape),))
+    n, H, W = depth.shape
+    if not isinstance(K, torch.Tensor) or K.is_cuda or K.dtype != torch.float32:
+        raise TypeError("K must be a float32 tensor on the host (the shadow window is checked before the launch)")
+    if tuple(K.shape) not in ((3, 3), (n, 3, 3)):
+        raise ValueError("K must be [3,3] or [n=%d,3,3], got %s" % (n, tuple(K.shape)))
+    K = K.contiguous()
+    seed_val, seed_ptr = _seed_args(seed)
+    if out is None:
+        out_depth, cause = torch.empty_like(depth), torch.empty((n, H, W), dtype=torch.uint8, device=depth.device)
+    else:
+        out_depth, cause = _dev(out[0], torch.float32, "out_depth"), _dev(out[1], torch.uint8, "cause")
+        if tuple(out_depth.shape) != (n, H, W) or tuple(cause.shape) != (n, H, W):
+            raise ValueError("out_depth and cause must be %s" % ([n, H, W],))
+    call("gdm_depth_sensor_hip", depth, K, int(K.dim() == 3), n, H, W, float(baseline), float(z_min), float(z_max), float(sigma_d),
+         float(subpixel), float(cos_min), float(cos_soft), float(p_shift), int(stages), seed_val, seed_ptr, out_depth, cause)
+    return out_depth, cause
+
+
+# --------------------------------------------------------------------------------------
 # BOP pose errors (lib/pysixd/pose_error.py:22-179): gdm_bop.hip
 
 

@@ -454,11 +454,15 @@ class RenderedFrames:
     model_xyz f32[M,3] (metres) gives the radius the distractors are placed by.  train=False (held-out frames for -state=test):
     no box jitter, and the batch carries scene_id / im_id.  build_pyramid=False leaves the neighbour pyramid (which wants n_points >=
     1024) to the consumer, as make_inputs_from_boxes does.  keep_frames=True: a batch also carries frame_depth f32[B,H,W] (the rendered
-    depth frame) and bbox f32[B,4] (the target's visible box), what pose.verify_poses wants; the default leaves the batch as it is."""
+    depth frame) and bbox f32[B,4] (the target's visible box), what pose.verify_poses wants; the default leaves the batch as it is.
+    depth_sensor: a sensor.DepthSensor, or None (the default: every tensor of the batch is what it was without the argument).  With one,
+    the rendered depth passes through sensor.simulate_depth_sensor (seed sensor_seed(i)) before make_inputs_from_boxes, so the crop, its
+    normals and cld_rgb_nrm are a camera's; the mask, the box, RT and the statistics stay the renderer's.  With keep_frames the batch's
+    frame_depth is then the SENSED frame, and it also carries frame_depth_clean f32[B,H,W] and depth_cause u8[B,H,W]."""
 
     def __init__(self, scene, target_obj, model_xyz, batch, n_points, S_crop=256, seed=0, n_batches=64, K=None, H=480, W=640, S=4,
                  z_range=(0.4, 1.0), distractor_objs=None, backdrop_obj=None, min_px_vis=64, min_valid=200, train=True, cls_id=None,
-                 light=None, ambient=AMBIENT, near=NEAR, build_pyramid=True, keep_frames=False):
+                 light=None, ambient=AMBIENT, near=NEAR, build_pyramid=True, keep_frames=False, depth_sensor=None):
         from . import synthetic
         self.scene, self.target_obj, self.batch, self.n_points, self.S_crop = scene, int(target_obj), int(batch), int(n_points), int(S_crop)
         self.seed, self.n_batches, self.H, self.W, self.S = int(seed), int(n_batches), int(H), int(W), int(S)
@@ -471,6 +475,7 @@ class RenderedFrames:
         self.min_px_vis, self.min_valid, self.train, self.cls_id = int(min_px_vis), int(min_valid), bool(train), cls_id
         self.light, self.ambient, self.near, self.build_pyramid = light, ambient, near, bool(build_pyramid)
         self.keep_frames = bool(keep_frames)
+        self.depth_sensor = depth_sensor
         dev = scene.device
         self._K32 = torch.from_numpy(self.K.astype(np.float32)).to(dev).expand(self.batch, 3, 3).contiguous()
         self._K64 = torch.from_numpy(self.K).to(dev)
@@ -484,14 +489,26 @@ class RenderedFrames:
                                           self.distractor_objs, self.backdrop_obj, self.radius, first=i * self.batch)
         return slot_obj, RT, render_frames(self.scene, slot_obj, RT, self._K64, self.H, self.W, self.light, self.ambient, self.near)
 
+    def item_seed(self, i):
+        return (self.seed * 1000003 + i * 7919 + 1) & 0x7FFFFFFF
+
+    def sensor_seed(self, i):
+        """The seed of batch i's depth sensor call, derived from its item seed."""
+        return (self.item_seed(i) ^ 0x5BD1E995) & 0xFFFFFFFF
+
     def batch_at(self, i):
         from . import frontend
         _, RT, fr = self.frames(i)
         dev = self.scene.device
         mask = (fr["inst"] == 1).to(torch.uint8) * 255
         bbox = fr["bbox_vis"][:, 0].to(torch.float32)
-        item_seed = (self.seed * 1000003 + i * 7919 + 1) & 0x7FFFFFFF
-        item = frontend.make_inputs_from_boxes(fr["rgb"], fr["depth"], self._K32, bbox, self.S_crop, self.n_points, mask=mask,
+        item_seed = self.item_seed(i)
+        depth, sensed = fr["depth"], None
+        if self.depth_sensor is not None:
+            from . import sensor
+            sensed = sensor.simulate_depth_sensor(depth, self.K.astype(np.float32), self.depth_sensor, seed=self.sensor_seed(i))
+            depth = sensed["depth"]
+        item = frontend.make_inputs_from_boxes(fr["rgb"], depth, self._K32, bbox, self.S_crop, self.n_points, mask=mask,
                                                train=self.train, sampler="hash", jitter="hash", seed=item_seed,
                                                build_pyramid=self.build_pyramid)
         keep = (fr["px_vis"][:, 0] >= self.min_px_vis) & (item["n_valid"] >= self.min_valid)
@@ -506,7 +523,9 @@ class RenderedFrames:
             item["scene_id"] = torch.full((self.batch,), 1 + self.seed, dtype=torch.int32)
             item["im_id"] = torch.arange(i * self.batch, (i + 1) * self.batch, dtype=torch.int32)
         if self.keep_frames:
-            item["frame_depth"], item["bbox"] = fr["depth"], bbox
+            item["frame_depth"], item["bbox"] = depth, bbox
+            if sensed is not None:
+                item["frame_depth_clean"], item["depth_cause"] = fr["depth"], sensed["cause"]
         return item
 
     def __iter__(self):

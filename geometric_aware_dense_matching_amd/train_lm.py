@@ -125,6 +125,19 @@ def build_parser():
                    help="test, --pose-verify: Gauss-Newton iterations of a +depth candidate")
     p.add_argument("--depth-refine-reject", dest="depth_refine_reject", type=float, default=0.01, metavar="M",
                    help="test, --pose-verify: a +depth candidate pairs a pixel whose observed depth lies within M metres of the rendered one")
+    p.add_argument("--render-depth-sensor", dest="render_depth_sensor", action="store_true",
+                   help="-data rendered, train and test: pass every rendered depth frame through the structured-light sensor model "
+                        "(sensor.DepthSensor: range, projector shadow, grazing drop-outs, jitter, disparity noise and quantisation) "
+                        "before the crop; off by default.  The --sensor-* options override its defaults")
+    for _name, _help in (("baseline", "signed projector offset in metres"), ("z-min", "nearest measured depth in metres"),
+                         ("z-max", "farthest measured depth in metres"), ("sigma-d", "disparity noise in pixels"),
+                         ("subpixel", "disparity steps per pixel"), ("cos-min", "incidence cosine below which a pixel always drops"),
+                         ("cos-soft", "incidence cosine above which a pixel never drops"),
+                         ("p-shift", "probability per axis that a pixel reads its neighbour")):
+        p.add_argument("--sensor-" + _name, dest="sensor_" + _name.replace("-", "_"), type=float, default=None, metavar="X",
+                       help="--render-depth-sensor: " + _help)
+    p.add_argument("--sensor-stages", dest="sensor_stages", type=str, default="all",
+                   help="--render-depth-sensor: 'all' or a comma-separated subset of range, shadow, grazing, jitter, noise")
     p.add_argument("--objects-across-gpus", action="store_true",
                    help="train: the dataset's objects are independent jobs (train_ycb.sh:3-9 runs them one after the other): rank r of a "
                         "torch.distributed.run launch trains objects r, r + world, ... on its own GPU as single-process jobs -- no process "
@@ -410,10 +423,22 @@ def _rendered_meshes(args, cls_id):
     return out, 0
 
 
+def depth_sensor_from_args(args):
+    """--render-depth-sensor and the --sensor-* overrides -> a sensor.DepthSensor, or None with the option off."""
+    if not getattr(args, "render_depth_sensor", False):
+        return None
+    from . import sensor
+    over = {k: getattr(args, "sensor_" + k, None) for k in ("baseline", "z_min", "z_max", "sigma_d", "subpixel", "cos_min", "cos_soft",
+                                                            "p_shift")}
+    stages = getattr(args, "sensor_stages", "all") or "all"
+    return sensor.DepthSensor(stages="all" if stages == "all" else [s.strip() for s in stages.split(",") if s.strip()],
+                              **{k: v for k, v in over.items() if v is not None})
+
+
 def make_rendered(args, split, cls_id, batch_size, device, keep_frames=False):
     """-data rendered: render.RenderedFrames over the object's mesh (metres), other meshes as distractors and a backdrop plane;
     --synthetic-items frames per epoch; the test split draws from another seed and carries no box jitter.  keep_frames: the batches
-    also carry the depth frame and the target's box (--pose-verify)."""
+    also carry the depth frame and the target's box (--pose-verify).  --render-depth-sensor: both splits see sensed depth."""
     from . import render
     meshes, target = _rendered_meshes(args, cls_id)
     packed = [render._as_mesh(m) for m in meshes]
@@ -423,7 +448,8 @@ def make_rendered(args, split, cls_id, batch_size, device, keep_frames=False):
     model_xyz = _model_points(args, ds, cls_id)[:, :3] / 1000.0
     return render.RenderedFrames(scene, target, model_xyz, batch_size, args.n_points, seed=0 if split == "train" else 1,
                                  n_batches=max(1, args.synthetic_items // batch_size), backdrop_obj=len(packed) - 1,
-                                 train=split == "train", cls_id=cls_id, keep_frames=keep_frames)
+                                 train=split == "train", cls_id=cls_id, keep_frames=keep_frames,
+                                 depth_sensor=depth_sensor_from_args(args))
 
 
 def make_dataset(args, split, cls_ids=None):

@@ -1217,6 +1217,67 @@ int gdm_render_frames_tex_hip(const void* verts, int verts_f64, const uint8_t* v
                               int flip_v, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A structured-light depth sensor on a metric depth frame (sensor.simulate_depth_sensor_numpy restates the rule and
+ * the kernel equals it bit for bit).  A function of the depth frame alone: what gdm_render_frames_hip or gdm_render_depth_hip drew,
+ * or any other depth in metres.  Parity with a real device, with BlenSor or with simkinect is NOT claimed: the rule is the definition.
+ *
+ * INPUTS  depth f32[n,H,W] in metres (0, negative or NaN: no depth);  K: a HOST array f32[n,3,3] (k_per_frame 1) or f32[3,3]
+ * (k_per_frame 0), fx = K[0], cx = K[2], fy = K[4], cy = K[5] -- host data, because the shadow window below is checked before the
+ * launch; the intrinsics travel by value in the kernel arguments, so k_per_frame 1 wants n <= GDM_SENSOR_MAX_K;  baseline (metres,
+ * signed and not 0: the projector sits at camera x = +baseline), z_min, z_max, sigma_d (pixels of disparity), subpixel (disparity
+ * steps per pixel), cos_min <= cos_soft, p_shift;  stages: the sum of GDM_SENSOR_RANGE 1, GDM_SENSOR_SHADOW 2, GDM_SENSOR_GRAZING 4,
+ * GDM_SENSOR_JITTER 8, GDM_SENSOR_NOISE 16 -- a stage whose bit is clear is skipped;  seed, and seed_dev as for
+ * gdm_sample_assemble_hip.
+ * OUTPUTS  out_depth f32[n,H,W], 0 where the sensor returns nothing;  cause u8[n,H,W]: 0 measured, 1 empty in the input, 2 out of
+ * range, 3 projector shadow, 4 grazing, 5 jittered onto a pixel outside the frame.  Neither output may overlap the input.
+ *
+ * THE SENSOR RULE.  All arithmetic is fp32, one rounding per operation in the order written (the library is built with
+ * -ffp-contract=off), but for fb.  No transcendental and no square root anywhere.  Pixel (x, y) of frame b, p = y W + x, z = depth.
+ *   draws     mix = lowbias32 as above;  hb = mix(mix(seed ^ 0x27d4eb2f) ^ b);  the pixel word of stream s is mix(mix(hb ^ s) ^ p),
+ *             s = 1 grazing, 2 jitter, 3 noise
+ *   fb        (float) ((double) fx (double) |baseline|): fp64, rounded once;  D(z) = fb / z, the disparity in pixels
+ *   valid     z > 0 (false for NaN); otherwise cause 1
+ *   1 range   a valid pixel with !(z >= z_min && z <= z_max) gets cause 2.  The pixels that are valid and not dropped here SURVIVE;
+ *             with the stage off every valid pixel survives.  A pixel out of range casts no shadow and is no neighbour in stage 3
+ *             either: a simplification -- a real surface nearer than z_min still blocks the projector.
+ *   2 shadow  Wd = (int) ceilf(fb / z_min), the widest disparity a survivor can have.
+ *             baseline > 0:  g(x) = (float) x - D;  a survivor x is shadowed (cause 3) iff some survivor x' of its row has
+ *                            0 < x' - x <= Wd and g(x') <= g(x)
+ *             baseline < 0:  g(x) = (float) x + D;  shadowed iff some survivor x' of its row has 0 < x - x' <= Wd and g(x') >= g(x)
+ *             (the shadow lies left of an occluder for a positive baseline, right of it for a negative one, and is D_near - D_far
+ *             wide).  A windowed minimum of identical fp32 values: any scan order gives the same bits.  A shadowed pixel still casts.
+ *   3 grazing for a survivor that stage 2 kept:  P(x, y) = (z u, z v, z) with u = ((float) x - cx) / fx, v = ((float) y - cy) / fy.
+ *             tx = P(x+1, y) - P(x-1, y) when both neighbours survive, else P(x+1, y) - P(x, y), else P(x, y) - P(x-1, y), by which
+ *             neighbour survives (a pixel outside the frame does not); ty likewise with y.  No tangent in a direction: cause 4.
+ *             nrm = tx x ty, each component a b - c d as two products and one subtraction, in the order
+ *             (tx.y ty.z - tx.z ty.y, tx.z ty.x - tx.x ty.z, tx.x ty.y - tx.y ty.x);  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;
+ *             c2 = (dot(nrm, P) dot(nrm, P)) / (dot(nrm, nrm) dot(P, P))   (the squared cosine of the incidence angle)
+ *             cmin2 = cos_min cos_min, csoft2 = cos_soft cos_soft.  !(c2 >= cmin2): cause 4 (a NaN c2 too).  Otherwise, when
+ *             c2 < csoft2:  r = (csoft2 - c2) / (csoft2 - cmin2);  T = (uint32) (r 16777216.0f) (truncated, 0 .. 2^24);
+ *             cause 4 iff (word of stream 1 >> 8) < T.  At a silhouette the difference runs across the depth step, so the rim
+ *             frays: intended.
+ *   4 jitter  T = (uint32) (p_shift 32768.0f);  w = the word of stream 2;  for h = w & 0xffff: jx = h < T ? -1 : (h >= 65536 - T ?
+ *             1 : 0);  jy the same from h = w >> 16.  Output pixel p reads source pixel q = (x + jx, y + jy); with the stage off
+ *             q = p.  q outside the frame: cause 5.  q with a cause from stages 1 - 3 (or empty): p takes that cause.
+ *   5 noise   zeta = (sum of the four bytes of the word of stream 3 at p) - 510 (Irwin-Hall, as in the augmentation rule);
+ *             e = (float) zeta 0.0067658751f (= 1 / sqrt(21845): unit variance);  D' = D(z(q)) + sigma_d e;
+ *             Dq = rintf(D' subpixel) / subpixel;  !(Dq > 0): cause 2;  otherwise out = fb / Dq, cause 0.
+ *             With the stage off out = z(q), the input's bits.
+ * THE CALL  one launch whatever n, one workgroup per (frame, GDM_SENSOR_TILE_W x GDM_SENSOR_TILE_H tile).  The tile keeps its pixels'
+ * surviving depth with a ring of 2 (stage 4 reads stage-3 results one pixel away, which read stage-1 depth one pixel further) and Wd
+ * further columns on the projector side in LDS, recomputes the halo, and takes the windowed minimum by log-step doubling in LDS
+ * (ceil(log2 Wd) passes, not Wd steps per pixel).  No workspace, no atomics, no allocation, no host read: it captures in a hipGraph
+ * and redraws from seed_dev on replay.
+ * LIMITS (refused beyond, before any HIP call): 1 <= n <= 65535, 1 <= H, W <= 16384; finite fx, fy > 0; baseline finite, not 0;
+ * z_min > 0, z_max > z_min; sigma_d >= 0; subpixel >= 1; 0 <= cos_min <= cos_soft <= 1; 0 <= p_shift <= 1; stages in [0, 31];
+ * 1 <= Wd <= GDM_SENSOR_MAX_DISP for every frame (checked whether or not stage 2 is on). */
+enum { GDM_SENSOR_RANGE = 1, GDM_SENSOR_SHADOW = 2, GDM_SENSOR_GRAZING = 4, GDM_SENSOR_JITTER = 8, GDM_SENSOR_NOISE = 16 };
+enum { GDM_SENSOR_MAX_DISP = 255, GDM_SENSOR_TILE_W = 128, GDM_SENSOR_TILE_H = 8, GDM_SENSOR_MAX_K = 64 };
+int gdm_depth_sensor_hip(const float* depth, const float* K /* host array */, int k_per_frame, int n, int H, int W, float baseline,
+                         float z_min, float z_max, float sigma_d, float subpixel, float cos_min, float cos_soft, float p_shift,
+                         int stages, uint32_t seed, const uint32_t* seed_dev, float* out_depth, uint8_t* cause, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Object model preparation: from a triangle mesh to the table obj_%06d_fps.npy holds ([M,9] = xyz in mm, rgb 0..255, unit normal,
  * rows in farthest-point order; read by datasets/lm/linemod_pbr.py:89-97, evaluator.py:34-40, models/SplineCNN.py:116).  The script
  * that wrote the reference's files is not part of it, so each entry is defined by the rule written here, which model_prep.py
