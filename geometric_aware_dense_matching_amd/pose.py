@@ -10,6 +10,8 @@ Opt-in robust variants (csrc/gdm_pose_robust.hip), also on the device and captur
   utils/pvn3d_eval_utils_kpls.py:79-124 best_fit_transform_with_RANSAC   solve_poses(method="ransac") / ransac_poses
   utils/pvn3d_eval_utils_kpls.py:126-212 icp (point to point)              refine_icp
 and, with no counterpart in the reference, point-to-plane ICP with normal gating and Huber weights: refine_icp_plane.
+Consensus fit from pairwise-compatible correspondences (csrc/gdm_consensus.hip; include/gdm.h THE CONSENSUS RULE),
+likewise without one: consensus_poses / consensus_poses_numpy, solve_poses(method="consensus").
 Verification of pose candidates against the observed depth frame (csrc/gdm_verify.hip), also without one:
   verify_poses / verify_poses_numpy, boxes_to_windows, select_verified, estimate_poses_verified.
 Refinement of pose candidates against that frame by render-and-compare (csrc/gdm_refine.hip), likewise:
@@ -34,10 +36,11 @@ def kabsch_stats(res, cld_rgb_nrm, model_xyz):
 
 
 def solve_poses(res, cld_rgb_nrm, model_xyz, min_points=5, method="kabsch", ransac_iters=20, inlier_dist=0.015, fix_percent=0.7,
-                seed=0, weights="none", targets="vertex"):
+                seed=0, weights="none", targets="vertex", consensus_tau=0.005, consensus_seeds=8):
     """-> RT f32[B,3,4] mapping model coordinates to the camera frame, valid bool[B].  Two launches (statistics, fit), no
     host synchronisation.  method="ransac": the reference's RANSAC (ransac_poses) with max_iter = ransac_iters hypotheses,
-    match_err = inlier_dist (m) and fix_percent; `seed` selects the hashed samples.
+    match_err = inlier_dist (m) and fix_percent; `seed` selects the hashed samples.  method="consensus": the consensus fit
+    (consensus_poses) with consensus_tau, consensus_seeds and inlier_dist.
     method="kabsch" only: weights="conf" weighs every pair by res["conf"], targets="soft" pairs the scene point with
     res["soft_xyz"] instead of its arg-max vertex (both from soft matching, matching.match_frames(soft=...)); either takes the
     weighted entries (solve_poses_weighted).  The defaults are the unweighted launches."""
@@ -49,8 +52,14 @@ def solve_poses(res, cld_rgb_nrm, model_xyz, min_points=5, method="kabsch", rans
             raise ValueError("solve_poses: weights=%r / targets=%r are for method='kabsch'; RANSAC keeps the hard pairs" % (weights, targets))
         RT, valid, _, _ = ransac_poses(res, cld_rgb_nrm, model_xyz, ransac_iters, inlier_dist, fix_percent, seed, min_points)
         return RT, valid
+    if method == "consensus":
+        if soft:
+            raise ValueError("solve_poses: weights=%r / targets=%r are for method='kabsch'; the consensus fit keeps the hard pairs"
+                             % (weights, targets))
+        out = consensus_poses(res, cld_rgb_nrm, model_xyz, consensus_tau, consensus_seeds, inlier_dist, min_points)
+        return out["RT"], out["valid"]
     if method != "kabsch":
-        raise ValueError("solve_poses: method must be 'kabsch' or 'ransac', got %r" % (method,))
+        raise ValueError("solve_poses: method must be 'kabsch', 'ransac' or 'consensus', got %r" % (method,))
     if soft:
         need = [k for k, on in (("conf", weights == "conf"), ("soft_xyz", targets == "soft")) if on and k not in res]
         if need:
@@ -168,6 +177,123 @@ def ransac_poses(res, cld_rgb_nrm, model_xyz, iters=20, inlier_dist=0.015, fix_p
     call("gdm_ransac_pose_hip", cld, sb, ps, cs, model_xyz, best_idx, mask, st, B, N, model_xyz.shape[0], H, float(inlier_dist),
          float(fix_percent), int(seed) & 0xffffffff, int(min_points), ws, nbytes, RT, valid, counts, winner)
     return RT, valid.bool(), counts, winner
+
+
+CONSENSUS_MAX_POINTS = 4096    # N of gdm_consensus_pose_hip: a bit row is held one 64-bit word per lane
+CONSENSUS_MAX_SEEDS = 64
+
+
+def consensus_poses(res, cld_rgb_nrm, model_xyz, tau=0.005, seeds=8, inlier_dist=0.015, min_points=5):
+    """The consensus fit (include/gdm.h THE CONSENSUS RULE, gdm_consensus_pose_hip) over the same correspondences as
+    solve_poses: pairs whose scene and model distances agree within tau (m) are compatible; the pairs with the most second-order
+    support seed `seeds` weighted fits, the one with the most pairs within inlier_dist (m) wins and is refit on them.  tau, seeds and
+    inlier_dist are the defaults of a definition, not tuned values.  -> dict(RT f32[B,3,4], valid bool[B], score / degree i32[B,N]
+    (per point, -1 where unselected), seed_idx i32[B,seeds] (point indices, -1 unused), hyp_RT f32[B,seeds,3,4], counts i32[B,seeds]
+    (-1 for a skipped hypothesis), winner i32[B]).  Six launches, no host synchronisation; the only temporary is the planner's
+    workspace, which holds an n x n bit matrix per crop (512 KiB at N = 2048) and no n x n float tensor."""
+    S = int(seeds)
+    mask, best_idx = res["mask"], res["best_idx"]
+    B, N = mask.shape
+    if not 1 <= S <= CONSENSUS_MAX_SEEDS:
+        raise ValueError("consensus_poses: seeds=%d not in [1, %d]" % (S, CONSENSUS_MAX_SEEDS))
+    if N > CONSENSUS_MAX_POINTS:
+        raise ValueError("consensus_poses: N=%d > %d points per crop" % (N, CONSENSUS_MAX_POINTS))
+    if int(min_points) < 3:
+        raise ValueError("consensus_poses: min_points=%d must be >= 3" % int(min_points))
+    cld, sb, ps, cs = _scene_args(cld_rgb_nrm)
+    model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
+    dev = mask.device
+    nbytes = call("gdm_consensus_workspace_bytes", B, N, S)
+    if nbytes == 0:
+        raise ValueError("consensus_poses: B=%d N=%d seeds=%d is beyond the entry's limits (include/gdm.h)" % (B, N, S))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    out = dict(RT=torch.empty((B, 3, 4), dtype=torch.float32, device=dev), valid=torch.empty((B,), dtype=torch.uint8, device=dev),
+               score=torch.empty((B, N), dtype=torch.int32, device=dev), degree=torch.empty((B, N), dtype=torch.int32, device=dev),
+               seed_idx=torch.empty((B, S), dtype=torch.int32, device=dev),
+               hyp_RT=torch.empty((B, S, 3, 4), dtype=torch.float32, device=dev),
+               counts=torch.empty((B, S), dtype=torch.int32, device=dev), winner=torch.empty((B,), dtype=torch.int32, device=dev))
+    call("gdm_consensus_pose_hip", cld, sb, ps, cs, model_xyz, best_idx, mask, B, N, model_xyz.shape[0], S, float(tau),
+         float(inlier_dist), int(min_points), ws, nbytes, out["RT"], out["valid"], out["score"], out["degree"], out["seed_idx"],
+         out["hyp_RT"], out["counts"], out["winner"])
+    out["valid"] = out["valid"].bool()
+    return out
+
+
+def consensus_bits_numpy(p, q, tau):
+    """Step 1 of THE CONSENSUS RULE in np.float32 operations in the written order: p, q [n,3] -> C bool[n,n]."""
+    p, q = np.asarray(p, np.float32), np.asarray(q, np.float32)
+
+    def dist2(x):
+        d = x[:, None, :] - x[None, :, :]
+        return ((d[..., 0] * d[..., 0]) + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+    a2, b2 = dist2(p), dist2(q)
+    u = (a2 + b2) - np.float32(tau) * np.float32(tau)
+    with np.errstate(over="ignore", invalid="ignore"):
+        C = (u <= np.float32(0)) | (u * u <= (np.float32(4) * a2) * b2)
+    np.fill_diagonal(C, False)
+    return C
+
+
+SENTINEL_RT = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, -1000]], np.float64)
+
+
+def consensus_poses_numpy(scene, model_pts, mask, tau=0.005, seeds=8, inlier_dist=0.015, min_points=5, near_margin=1e-5):
+    """consensus_poses for ONE crop on the host, the definition the kernels are tested against.  scene [N,3] and model_pts [N,3] (the
+    matched vertex of every point, already clamped and gathered) as fp32, mask [N].  The bits come from consensus_bits_numpy; the
+    intersections from a float64 product of 0/1 matrices, which is exact; the fits from kabsch_weighted_numpy and the residuals in fp64.
+    -> dict(RT f64[3,4], valid, score / degree i64[N] (-1 unselected), seed_idx i64[S], hyp_RT f64[S,3,4], counts i64[S], winner;
+    and for the tests: sel i64[n], C bool[n,n], weights f64[S,n] (compacted order, 0 = not in the fit), near i64[S] (pairs within
+    near_margin of inlier_dist under hypothesis t), inliers bool[n] of the winner)."""
+    scene, model_pts = np.asarray(scene, np.float32), np.asarray(model_pts, np.float32)
+    N, S = len(scene), int(seeds)
+    sel = np.nonzero(np.asarray(mask).reshape(-1) != 0)[0]
+    n = len(sel)
+    p, q = scene[sel], model_pts[sel]
+    C = consensus_bits_numpy(p, q, tau)
+    Cf = C.astype(np.float64)
+    common = Cf @ Cf                                                       # |row_i & row_j|: sums of at most n ones, exact
+    deg = C.sum(1).astype(np.int64)
+    s = np.rint((common * Cf).sum(1)).astype(np.int64)
+    score, degree = np.full(N, -1, np.int64), np.full(N, -1, np.int64)
+    score[sel], degree[sel] = s, deg
+    covered = np.zeros(n, bool)
+    seedk = np.full(S, -1, np.int64)
+    for t in range(S):
+        cand = np.where(~covered & (s > 0), s, 0)
+        if n == 0 or cand.max() <= 0:
+            break
+        g = int(np.argmax(cand))                                           # the first maximum: the smallest k on a tie
+        seedk[t] = g
+        covered |= C[g]
+        covered[g] = True
+    p64, q64 = p.astype(np.float64), q.astype(np.float64)
+    hyp = np.tile(SENTINEL_RT, (S, 1, 1))
+    counts, near = np.full(S, -1, np.int64), np.zeros(S, np.int64)
+    weights = np.zeros((S, n))
+    resid = np.zeros((S, n))
+    for t in range(S):
+        g = seedk[t]
+        if g < 0:
+            continue
+        w = np.rint(common[g] * Cf[g])
+        w[g] = deg[g]
+        pos = w > 0
+        if pos.sum() < 3:
+            continue
+        weights[t] = w
+        hyp[t] = kabsch_weighted_numpy(q64[pos], p64[pos], w[pos])
+        resid[t] = np.linalg.norm(q64 @ hyp[t][:, :3].T + hyp[t][:, 3] - p64, axis=1)
+        counts[t] = int((resid[t] <= inlier_dist).sum())
+        near[t] = int((np.abs(resid[t] - inlier_dist) < near_margin).sum())
+    seed_idx = np.where(seedk >= 0, sel[np.clip(seedk, 0, max(n - 1, 0))] if n else -1, -1)
+    out = dict(RT=SENTINEL_RT.copy(), valid=False, score=score, degree=degree, seed_idx=seed_idx, hyp_RT=hyp, counts=counts, winner=-1,
+               sel=sel, C=C, weights=weights, near=near, inliers=np.zeros(n, bool))
+    win = int(np.argmax(counts)) if S else -1
+    if n >= min_points and win >= 0 and counts[win] >= min_points:
+        inl = resid[win] <= inlier_dist
+        out.update(RT=kabsch_weighted_numpy(q64[inl], p64[inl], np.ones(int(inl.sum()))), valid=True, winner=win, inliers=inl)
+    return out
 
 
 def _icp_setup(RT, valid, cld_rgb_nrm, mask, model_xyz):
@@ -397,15 +523,17 @@ def icp_plane_numpy(scene, scene_nrm, model_xyz, model_nrm, RT0, mask=None, iter
 
 
 def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, pose_opts=None, model_nrm=None):
-    """The pose stage of the pipeline: solve_poses with `pose_fit` ("kabsch" | "ransac"), then `icp_iters` ICP iterations when > 0.
-    pose_opts (optional dict): ransac_iters, ransac_inlier_dist, ransac_fix_percent, seed, icp_tolerance, icp_reject_dist,
+    """The pose stage of the pipeline: solve_poses with `pose_fit` ("kabsch" | "ransac" | "consensus"), then `icp_iters` ICP iterations
+    when > 0.  pose_opts (optional dict): ransac_iters, ransac_inlier_dist, ransac_fix_percent, seed, consensus_tau, consensus_seeds,
+    consensus_inlier_dist (pose_fit="consensus": consensus_poses' tau, seeds and inlier_dist), icp_tolerance, icp_reject_dist,
     min_points, and for pose_fit="kabsch" weights ("none" | "conf") and targets ("vertex" | "soft") (solve_poses; RANSAC and ICP
     keep the hard pairs); icp_metric ("point" | "plane"): "plane" refines with refine_icp_plane instead of refine_icp, needs the
     model's unit normals model_nrm f32[M,3], takes icp_huber and icp_normal_gate as well (icp_tolerance then defaults to 1e-4) and adds
     icp_status.  -> dict(RT, valid[, icp_iters, icp_resid[, icp_status]])."""
     o = dict(pose_opts or {})
     unknown = set(o) - {"ransac_iters", "ransac_inlier_dist", "ransac_fix_percent", "seed", "icp_tolerance", "icp_reject_dist",
-                        "min_points", "weights", "targets", "icp_metric", "icp_huber", "icp_normal_gate"}
+                        "min_points", "weights", "targets", "icp_metric", "icp_huber", "icp_normal_gate", "consensus_tau", "consensus_seeds",
+                        "consensus_inlier_dist"}
     if unknown:
         raise ValueError("estimate_poses: unknown pose_opts %s" % sorted(unknown))
     min_points = o.get("min_points", 5)
@@ -419,6 +547,10 @@ def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, 
     if pose_fit == "kabsch":
         RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, weights=o.get("weights", "none"),
                                 targets=o.get("targets", "vertex"))
+    elif pose_fit == "consensus":
+        RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, method=pose_fit, inlier_dist=o.get("consensus_inlier_dist", 0.015),
+                                weights=o.get("weights", "none"), targets=o.get("targets", "vertex"),
+                                consensus_tau=o.get("consensus_tau", 0.005), consensus_seeds=o.get("consensus_seeds", 8))
     else:
         RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, method=pose_fit, ransac_iters=o.get("ransac_iters", 20),
                                 inlier_dist=o.get("ransac_inlier_dist", 0.015), fix_percent=o.get("ransac_fix_percent", 0.7),
@@ -822,19 +954,19 @@ _DEPTH_OPTS = {"reject", "huber", "min_cos", "min_px", "tolerance", "pivot_min"}
 
 def estimate_poses_verified(res, cld_rgb_nrm, model_xyz, verify, candidates=VERIFY_CANDIDATES, icp_iters=10, pose_opts=None,
                             model_nrm=None, depth_iters=5, depth_opts=None):
-    """Several pose estimates of every crop, judged against the depth frame the crop came from: each name of `candidates` -- "kabsch"
-    or "ransac", with "+icp" for `icp_iters` ICP iterations on it, and after that "+depth" for `depth_iters` iterations of
+    """Several pose estimates of every crop, judged against the depth frame the crop came from: each name of `candidates` -- "kabsch",
+    "ransac" or "consensus", with "+icp" for `icp_iters` ICP iterations on it, and after that "+depth" for `depth_iters` iterations of
     refine_poses_depth on its parent (the name without "+depth") against the verify dict's verts, faces, depth, K, window and near with
     depth_opts (reject, huber, min_cos, min_px, tolerance, pivot_min) -- goes through estimate_poses' stages with pose_opts, every
     parent made once and shared; then select_verified(verify) keeps, per crop, the one the observed depth agrees with best.  A
     "+depth" candidate is its refined pose rounded to f32, valid when the parent was and the refinement's status is 0 or 1.
     -> select_verified's dict; with a "+depth" name also depth_status i32[n,C]: the refinement's status, -1 for the other candidates."""
     names = tuple(candidates)
-    bad = [k for k in names if k.split("+")[0] not in ("kabsch", "ransac")
+    bad = [k for k in names if k.split("+")[0] not in ("kabsch", "ransac", "consensus")
            or k.split("+")[1:] not in ([], ["icp"], ["depth"], ["icp", "depth"])]
     if bad or not names or len(set(names)) != len(names):
-        raise ValueError("estimate_poses_verified: candidates must be distinct names out of kabsch, ransac, kabsch+icp, ransac+icp, "
-                         "each optionally followed by +depth; got %r" % (names,))
+        raise ValueError("estimate_poses_verified: candidates must be distinct names out of kabsch, ransac, consensus, kabsch+icp, "
+                         "ransac+icp, consensus+icp, each optionally followed by +depth; got %r" % (names,))
     o = dict(pose_opts or {})
     dopts = dict(depth_opts or {})
     if set(dopts) - _DEPTH_OPTS:

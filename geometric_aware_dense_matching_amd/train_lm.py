@@ -88,12 +88,20 @@ def build_parser():
                    help="test, with --bop-scores: the dataset's models_info.json (object symmetries); without it only the identity")
     p.add_argument("--graph-batch1", action="store_true",
                    help="test: per-object hipGraph replay for single-instance groups (a batch-1 eager step is launch-bound)")
-    p.add_argument("--pose-fit", dest="pose_fit", type=str, default="kabsch", choices=["kabsch", "ransac"],
-                   help="test: pose fit from the correspondences -- least squares over all of them (evaluator.py:97) or the reference's "
-                        "RANSAC (pvn3d_eval_utils_kpls.py:79-124), both on the GPU")
+    p.add_argument("--pose-fit", dest="pose_fit", type=str, default="kabsch", choices=["kabsch", "ransac", "consensus"],
+                   help="test: pose fit from the correspondences -- least squares over all of them (evaluator.py:97), the reference's "
+                        "RANSAC (pvn3d_eval_utils_kpls.py:79-124) or the consensus fit from pairwise-compatible pairs "
+                        "(pose.consensus_poses), all on the GPU")
     p.add_argument("--ransac-iters", dest="ransac_iters", type=int, default=20, help="test: RANSAC hypotheses per crop (max_iter)")
     p.add_argument("--ransac-inlier-dist", dest="ransac_inlier_dist", type=float, default=0.015,
                    help="test: RANSAC inlier distance in metres (match_err)")
+    p.add_argument("--consensus-tau", dest="consensus_tau", type=float, default=0.005, metavar="T",
+                   help="test, --pose-fit consensus: two pairs are compatible when their scene and model distances agree within T metres "
+                        "(the default of a definition, not a tuned value)")
+    p.add_argument("--consensus-seeds", dest="consensus_seeds", type=int, default=8, metavar="S",
+                   help="test, --pose-fit consensus: hypotheses per crop")
+    p.add_argument("--consensus-inlier-dist", dest="consensus_inlier_dist", type=float, default=0.015, metavar="D",
+                   help="test, --pose-fit consensus: inlier distance in metres of the hypothesis count and the refit")
     p.add_argument("--match-gamma", dest="match_gamma", type=float, default=None,
                    help="test: soft matching at this temperature (0 < G <= 40): per-point confidences, soft vertices and a csv score")
     p.add_argument("--pose-weights", dest="pose_weights", type=str, default="none", choices=["none", "conf"],
@@ -118,7 +126,8 @@ def build_parser():
     p.add_argument("--verify-delta", dest="verify_delta", type=float, default=0.01, metavar="D",
                    help="test, --pose-verify: the depth agreement tolerance in metres")
     p.add_argument("--verify-candidates", dest="verify_candidates", type=str, default="kabsch,ransac,kabsch+icp,ransac+icp",
-                   help="test, --pose-verify: comma-separated candidates out of kabsch, ransac, kabsch+icp, ransac+icp "
+                   help="test, --pose-verify: comma-separated candidates out of kabsch, ransac, consensus, kabsch+icp, ransac+icp, "
+                        "consensus+icp "
                         "(+icp runs --icp-iters iterations, 10 when that is 0), each optionally followed by +depth: the candidate "
                         "refined against the depth frame by render-and-compare (pose.refine_poses_depth), e.g. kabsch+depth")
     p.add_argument("--depth-refine-iters", dest="depth_refine_iters", type=int, default=5, metavar="K",
@@ -597,10 +606,11 @@ def test(args):
             raise SystemExit("train_lm test: --pose-verify needs -data rendered: the other batches carry no depth frame and no mesh "
                              "faces (use pose.verify_poses from Python)")
         verify_names = tuple(k for k in args.verify_candidates.split(",") if k)
-        allowed = pose.VERIFY_CANDIDATES + tuple(k + "+depth" for k in pose.VERIFY_CANDIDATES)
+        bases = pose.VERIFY_CANDIDATES + ("consensus", "consensus+icp")
+        allowed = bases + tuple(k + "+depth" for k in bases)
         if not verify_names or set(verify_names) - set(allowed) or len(set(verify_names)) != len(verify_names):
             raise SystemExit("train_lm test: --verify-candidates takes distinct names out of %s, each optionally followed by +depth, "
-                             "got %r" % (", ".join(pose.VERIFY_CANDIDATES), args.verify_candidates))
+                             "got %r" % (", ".join(bases), args.verify_candidates))
         if args.graph_batch1:
             raise SystemExit("train_lm test: --pose-verify does not go with --graph-batch1")
     ds = dataset_config(args.dataset_name)
@@ -624,6 +634,8 @@ def test(args):
     results = []
     pose_kw = dict(pose_fit=args.pose_fit, icp_iters=args.icp_iters,
                    pose_opts=dict(ransac_iters=args.ransac_iters, ransac_inlier_dist=args.ransac_inlier_dist,
+                                  consensus_tau=getattr(args, "consensus_tau", 0.005), consensus_seeds=getattr(args, "consensus_seeds", 8),
+                                  consensus_inlier_dist=getattr(args, "consensus_inlier_dist", 0.015),
                                   icp_tolerance=args.icp_tolerance))
     if getattr(args, "icp_metric", "point") == "plane":
         pose_kw["pose_opts"].update(icp_metric="plane", icp_huber=args.icp_huber, icp_normal_gate=args.icp_normal_gate)

@@ -463,6 +463,43 @@ int gdm_ransac_pose_hip(const float* scene_xyz, long scene_bstride, int pt_strid
                         float match_err, double fix_percent, uint32_t seed, int min_points, void* workspace, size_t workspace_bytes,
                         float* RT, uint8_t* valid, int32_t* counts, int32_t* winner, void* stream);
 
+/* Consensus fit from pairwise-compatible correspondences (no counterpart in the reference; the idea of spectral matching and of
+ * SC^2-PCR's second-order spatial compatibility, parity with either is not claimed): two correct matches of a rigid object keep their
+ * distance, so counting which pairs agree with which finds the consistent set without a draw.  Deterministic, a fixed set of
+ * launches, no host synchronisation.  Same correspondences and scene addressing as gdm_kabsch_stats_hip.
+ *
+ * THE CONSENSUS RULE, per crop b.  The selected pairs are the points with mask != 0 in point order, compacted to k = 0..n-1; pair k
+ * holds two fp32 points: the scene point p_k and the model point q_k = model_xyz[clamp(best_idx, 0, M-1)].
+ *   1. Compatibility bit.  fp32 throughout, every product and sum rounded once (no contraction), no square root.  With d = p_i - p_j:
+ *        a2 = ((dx dx) + dy dy) + dz dz,  b2 the same for q,  u = (a2 + b2) - tau tau  (tau tau one fp32 product),
+ *        C_ij = (i != j) and (u <= 0 or u u <= (4 a2) b2)
+ *      -- in real arithmetic | |p_i - p_j| - |q_i - q_j| | <= tau.  C is symmetric by construction.
+ *   2. Degree and score, integers.  row_i = { j : C_ij },  deg_i = |row_i|,  s_i = sum_{j in row_i} |row_i & row_j|  (<= n^2, int32).
+ *   3. Seeds, sequential, integers only.  covered = {}.  For t = 0..seeds-1: g_t = the uncovered pair with the largest s, the smallest
+ *      k on a tie; when no uncovered pair has s > 0, this seed and every later one is -1.  Then covered gains row_g and g itself.
+ *   4. Hypothesis t: a weighted least-squares fit.  Every j in row_g has w_j = |row_g & row_j|, the seed itself w_g = deg_g (exact
+ *      integers); the 16 weighted statistics of gdm_kabsch_stats_w_hip over the pairs with w > 0, accumulated in fp64 in a fixed order,
+ *      solved as gdm_kabsch_solve_w_hip solves them.  Fewer than 3 pairs with w > 0 (or no seed): the hypothesis is skipped, its
+ *      count is -1 and its pose the sentinel.
+ *   5. Count.  c_t = #{ selected pairs with |R_t q + t_t - p|^2 <= inlier_dist^2 }, the fp32 residual of gdm_ransac_pose_hip,
+ *      integer counts (no float atomics).
+ *   6. Winner.  The largest c_t wins, the smallest t on a tie, and RT is the unweighted Kabsch refit on its inliers (fp64 sums in a
+ *      fixed order).  valid = n >= min_points and c_winner >= min_points; otherwise the sentinel [I | (0,0,-1000)], valid = 0,
+ *      winner = -1.  Steps 1-5 do not look at min_points.
+ * The final score is an inlier count, as RANSAC's is: a clump of wrong pairs collapsed onto one vertex and one scene spot that
+ * outnumbers the true inliers wins.  Judging candidates by the depth frame is gdm_pose_verify_hip's part.
+ * Outputs: RT f32[B,3,4], valid u8[B], score / degree i32[B,N] (s and deg per POINT, -1 where mask == 0), seed_idx i32[B,seeds]
+ * (point indices, -1 = unused), hyp_RT f32[B,seeds,3,4], counts i32[B,seeds], winner i32[B] (the t that won).
+ * 1 <= N <= 4096 (a bit row is held one 64-bit word per lane), 1 <= seeds <= 64, tau > 0, inlier_dist > 0, min_points >= 3,
+ * B <= 65535.  workspace: device memory aligned for uint64_t, of at least gdm_consensus_workspace_bytes(B, N, seeds) bytes (0 for
+ * shapes beyond these limits): the compacted pairs, per-pair integers and an n x n BIT matrix per crop, ceil(N/64) words a row --
+ * 512 KiB per crop at N = 2048, 2 MiB at 4096.  No n x n float tensor is formed. */
+size_t gdm_consensus_workspace_bytes(int B, int N, int seeds);
+int gdm_consensus_pose_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* model_xyz,
+                           const int32_t* best_idx, const uint8_t* mask, int B, int N, int M, int seeds, float tau, float inlier_dist,
+                           int min_points, void* workspace, size_t workspace_bytes, float* RT, uint8_t* valid, int32_t* score,
+                           int32_t* degree, int32_t* seed_idx, float* hyp_RT, int32_t* counts, int32_t* winner, void* stream);
+
 /* Point-to-point ICP refinement, scene -> model (utils/pvn3d_eval_utils_kpls.py:126-212 icp, run as icp(scene, model, RT^-1)).
  * One iteration = gdm_icp_transform_hip, an exact K = 1 search of the query among the model vertices (gdm_knn_jobs_ws_hip, support
  * batch stride 0, with d2), gdm_icp_update_hip.
