@@ -25,14 +25,15 @@
 //
 // Roofline: materialised form moves 4D(BN+M) + 4BNM bytes; fused form 4D(BN+M)+8BN.
 #include "gdm_common.h"
+#include "gdm_match_rows.h"
 #include <math.h>
 #include <stdlib.h>
 
 namespace {
 
 
-constexpr int D = 128;                 // descriptor length (config/lmo_cfg.py:125 feat_dim)
-constexpr int ROW_BYTES = 512;         // one packed row
+constexpr int D = GDM_ROWS_D;          // descriptor length (config/lmo_cfg.py:125 feat_dim)
+constexpr int ROW_BYTES = GDM_ROWS_BYTES;   // one packed row
 constexpr int MT_ROWS = 128;           // scene rows per workgroup
 constexpr int MT_COLS = 64;            // model columns per LDS tile
 constexpr int TILE_BYTES = MT_COLS * ROW_BYTES;   // 32 KiB
@@ -50,39 +51,13 @@ __device__ __forceinline__ void pack_rows_tile(const float* __restrict__ x, int 
     const int w = threadIdx.x >> 6;
     const int p = min(p0 + lane, n - 1);
     const float* xr = x + (long)r * D * n;
-    float ss = 0.f;
-    for (int c = w; c < D; c += 4) {
+    part[w][lane] = gdm_rows_sumsq(w, [&](int c) {
         const float v = xr[(long)c * n + p];
         t[c][lane] = v;
-        ss += v * v;
-    }
-    part[w][lane] = ss;
+        return v;
+    }, [](float (&)[8]) {});
     __syncthreads();
-    // every thread recomputes the norm of the points it will write
-    for (int it = 0; it < 4; ++it) {
-        const int item = it * 256 + threadIdx.x;       // 64 points x 16 chunks of 8 channels
-        const int ch = item & 15;
-        const int pl = item >> 4;
-        if (p0 + pl >= n) continue;
-        const float nrm = sqrtf((part[0][pl] + part[1][pl]) + (part[2][pl] + part[3][pl]));
-        const float inv_den = fmaxf(nrm, 1e-12f);
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = t[ch * 8 + j][pl] / inv_den;
-        unsigned char* row = out + ((long)r * n + p0 + pl) * ROW_BYTES;
-        if (PREC == GDM_MATCH_BF16X3) {
-            unsigned hi[4], lo[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                gdm_split2(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
-            }
-            *reinterpret_cast<uint4*>(row + ch * 16) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-            *reinterpret_cast<uint4*>(row + 256 + ch * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-        } else {
-            *reinterpret_cast<float4*>(row + ch * 32) = make_float4(v[0], v[1], v[2], v[3]);
-            *reinterpret_cast<float4*>(row + ch * 32 + 16) = make_float4(v[4], v[5], v[6], v[7]);
-        }
-    }
+    gdm_rows_store<PREC>(part, n - p0, out + ((long)r * n + p0) * ROW_BYTES, [&](int c, int pl) { return t[c][pl]; });
 }
 
 template <int PREC>

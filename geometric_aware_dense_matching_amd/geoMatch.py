@@ -191,6 +191,7 @@ class GeoMatch(nn.Module):
         rgb = inputs["rgb"]
         late_join = None
         mesh_rows = None
+        scene_rows = None
         heads = self._fused_heads(rgb)
         # the fused heads read the two halves of the embedding in place: no concat launch
         emb = (lambda x: self.pcd_emb(x, parts=True)) if (heads is not None and isinstance(self.pcd_emb, FFB6DEmb)) else self.pcd_emb
@@ -221,7 +222,11 @@ class GeoMatch(nn.Module):
         if heads is not None:
             # feature_encoding_layer, normalize_feature_layer, the residual add and seg_layer: nine per-point 1x1 convolutions, one launch
             a, b = rgbd_emb if isinstance(rgbd_emb, tuple) else (rgbd_emb, None)
-            rgbd_features, seg_features = ops.point_heads(a, b, heads[0], heads[1], feat_layer=3, res_layer=4)
+            if settings.HEADS_MATCH_ROWS and not self.training:
+                # ... and the matching kernel's operand rows of rgbd_features (no pack launch between the heads and the arg-max)
+                rgbd_features, seg_features, scene_rows = ops.point_heads(a, b, heads[0], heads[1], feat_layer=3, res_layer=4, rows=True)
+            else:
+                rgbd_features, seg_features = ops.point_heads(a, b, heads[0], heads[1], feat_layer=3, res_layer=4)
             if late_join is not None:
                 late_join.join(mesh_features, mesh_rows)
         else:
@@ -249,6 +254,8 @@ class GeoMatch(nn.Module):
         end_points["seg"] = seg_features
         if mesh_rows is not None:
             end_points["mesh_rows"] = mesh_rows          # u8 packed rows for ops.match_packed (matching.match_tail reads them)
+        if scene_rows is not None:
+            end_points["scene_rows"] = scene_rows        # the same for rgbd_features, written by the heads kernel (bf16x3 rows)
         end_points["mesh"] = mesh_features
         end_points["rgbd"] = rgbd_features
         return end_points

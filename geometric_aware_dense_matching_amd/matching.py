@@ -52,7 +52,8 @@ def match_tail(end_points, B, N, M, precision=ops.MATCH_BF16X3, soft=None):
     """The step's tail on packed rows (evaluator.py:78-93): seg mask, descriptor packs, N x M arg-max -> (mask, count, best_idx, best_sim).
     With settings.USE_SIDE_STREAMS the mask -- which the arg-max does not read -- is formed on a side stream beside the matching
     kernel, and the model's descriptor rows are taken from `end_points["mesh_rows"]` when GeoMatch.forward packed them inside its
-    mesh fork (same kernels, same operands: same bits).  soft = dict(gamma=..., model_xyz=...): the soft kernel in place of the
+    mesh fork (same kernels, same operands: same bits); the scene's rows likewise from `end_points["scene_rows"]` when the fused heads
+    wrote them (bf16x3 only: the pack kernel's own code on the same values, same bytes).  soft = dict(gamma=..., model_xyz=...): the soft kernel in place of the
     arg-max kernel, and (lse, conf, soft_xyz) appended to the result."""
     from . import settings
     seg, rgbd, mesh = end_points["seg"], end_points["rgbd"], end_points["mesh"]
@@ -65,10 +66,13 @@ def match_tail(end_points, B, N, M, precision=ops.MATCH_BF16X3, soft=None):
 
     forked = settings.USE_SIDE_STREAMS and seg.is_cuda and not torch.is_grad_enabled()
     mrows = end_points.get("mesh_rows") if precision == ops.MATCH_BF16X3 else None
-    if mrows is None:
+    srows = end_points.get("scene_rows") if precision == ops.MATCH_BF16X3 else None
+    if mrows is None and srows is None:
         srows, mrows = ops.match_pack2(rgbd, mesh[0] if mesh.dim() == 3 else mesh, precision)      # both packs, one launch
-    else:
+    elif srows is None:
         srows = ops.match_pack(rgbd, precision)
+    elif mrows is None:
+        mrows = ops.match_pack(mesh[0] if mesh.dim() == 3 else mesh, precision)
     if forked:
         with ops.fork(seg.device, 0) as f:                   # side stream 0: behind the segmentation layers, if they are pending there
             f.use(seg)

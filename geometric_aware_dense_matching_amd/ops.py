@@ -1646,11 +1646,27 @@ def conv1x1_gather_add_act(x, wt, t, idx, scale, shift, act=ACT_NONE, slope=0.0,
     return y
 
 
-def point_heads(a, b, layers, last, feat_layer, res_layer, residual=None):
+def heads_rows_buffer(R, device):
+    """u8[R * 512]: where point_heads(rows=True) writes the matching rows of R points.  It belongs to the current BufferPool (one per
+    row count), so a captured step allocates nothing for it; its contents hold until the next point_heads(rows=True) of the same
+    pool and row count."""
+    nbytes = _lib.lib().gdm_match_rows_bytes(R)
+    if _capturing_unscoped():
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    key = ("heads_rows", device.index, R)
+    buf = _pool.workspace.get(key)
+    if buf is None:
+        buf = _pool.workspace[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return buf
+
+
+def point_heads(a, b, layers, last, feat_layer, res_layer, residual=None, rows=False):
     """The per-point 1x1-convolution chain of GeoMatch.forward in one launch (inference).  a f32[B,Ca,N] (+ b f32[B,128-Ca,N] or None);
     layers = [(wpk, scale|None, shift|None, act)] of 128 -> 128 layers (wpk from gemm_pack_weight, act ACT_NONE / ACT_RELU);
     last = (wpk, bias|None, c_last) or None (the chain ends with its hidden layers).  residual = (ra, rb|None): the tensor added at
-    res_layer (default: the input).  -> (out_feat f32[B,128,N] = output of layer feat_layer or None, out_last f32[B,c_last,N] or None)."""
+    res_layer (default: the input).  -> (out_feat f32[B,128,N] = output of layer feat_layer or None, out_last f32[B,c_last,N] or None).
+    rows=True (with feat_layer >= 0): the kernel also writes the matching rows of out_feat, the bytes match_pack(out_feat, MATCH_BF16X3)
+    would (gdm_point_heads3_hip), into heads_rows_buffer(B * N) -> (out_feat, out_last, rows u8[B*N*512])."""
     import ctypes
     a = _dev(a, torch.float32, "a")
     B, Ca, N = a.shape
@@ -1678,6 +1694,13 @@ def point_heads(a, b, layers, last, feat_layer, res_layer, residual=None):
         rb = _dev(residual[1], torch.float32, "residual") if residual[1] is not None else None
         if ra.shape[0] != B or ra.shape[2] != N or ra.shape[1] + (rb.shape[1] if rb is not None else 0) != 128:
             raise ValueError("point_heads: the residual source must make 128 channels of the same points")
+    if rows:
+        if feat_layer < 0:
+            raise ValueError("point_heads: rows are the matching rows of out_feat and need feat_layer >= 0")
+        out_rows = heads_rows_buffer(B * N, a.device)
+        call("gdm_point_heads3_hip", a, b, Ca, ra, rb, ra.shape[1] if ra is not None else 0, B, N, n, w_arr, sc_arr, sh_arr, act_arr,
+             int(feat_layer), int(res_layer), wl, bl, int(c_last), out_feat, out_last, out_rows)
+        return out_feat, out_last, out_rows
     call("gdm_point_heads2_hip", a, b, Ca, ra, rb, ra.shape[1] if ra is not None else 0, B, N, n, w_arr, sc_arr, sh_arr, act_arr,
          int(feat_layer), int(res_layer), wl, bl, int(c_last), out_feat, out_last)
     return out_feat, out_last

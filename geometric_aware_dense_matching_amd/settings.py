@@ -37,6 +37,8 @@ the initial values.
     USE_POINTWISE_TRAIN        GDM_POINTWISE_TRAIN        training: forward / input gradient of the small 1x1 layers as hipBLASLt fp32 batched GEMMs
     USE_POINT_CHAIN            GDM_POINT_CHAIN            the RandLA stem layer and the first block's mlp1 as two launches of the per-point kernel
     USE_PSP_JOBS               GDM_PSP_JOBS               the four prior products of the pyramid-pooling module as four launches of the per-point kernel
+    SPLINE_LDS_WEIGHTS         GDM_SPLINE_LDS_WEIGHTS     the first mesh layer (9 -> 128) fetches every weight row from L2 (spline_direct_vec_kernel)
+    HEADS_MATCH_ROWS           GDM_HEADS_MATCH_ROWS       the scene descriptors' matching rows by a pack launch behind the fused heads
     STATIC_MATCH_ROWS          GDM_STATIC_MATCH_ROWS=1    (default off) matching loss over all B*N rows with zero weight on the unselected
                                                           ones instead of compacting them: no host read; always on under graph capture
 """
@@ -76,6 +78,8 @@ USE_PSP_JOBS = _flag("GDM_PSP_JOBS")                     # the four prior produc
 USE_PACKED_PRODUCERS = _flag("GDM_PACKED_PRODUCERS")     # psp_combine / the up-conv gather write the next GEMM's packed operand themselves
 MESH_FORK_LATE = os.environ.get("GDM_MESH_FORK_LATE", "1") != "0"       # with USE_SIDE_STREAMS: the mesh fork is enqueued behind the embedding
 PACK_MESH_ROWS = os.environ.get("GDM_PACK_MESH_ROWS", "1") != "0"         # with USE_SIDE_STREAMS: the model descriptors' matching rows are packed inside the mesh fork
+SPLINE_LDS_WEIGHTS = os.environ.get("GDM_SPLINE_LDS_WEIGHTS", "1") != "0"   # the first mesh layer (9 -> 128) reads its weight slice from LDS (off: every weight row from L2)
+HEADS_MATCH_ROWS = os.environ.get("GDM_HEADS_MATCH_ROWS", "1") != "0"       # the fused heads write the scene descriptors' matching rows themselves (off: a pack launch behind them)
 SIDE_PARTS = os.environ.get("GDM_SIDE_PARTS", "mesh,point,pyr").split(",")     # development: which branches are forked
 STATIC_MATCH_ROWS = _flag("GDM_STATIC_MATCH_ROWS", "0")
 UPCONV_MIN_CIN = int(os.environ.get("GDM_UPCONV_MIN_CIN", "0"))

@@ -110,7 +110,7 @@ class _SplineDirectTrain(torch.autograd.Function):
         out = torch.empty((M, conv.cout), dtype=torch.float32, device=x.device)
         root_t = _train_root_t(conv, lin_weight)
         call("gdm_spline_direct3_hip", x, weight, rowptr, src, attr, root_t, bias, M, conv.cin, conv.cout, KERNEL_SIZE, int(relu), out,
-             None, None)
+             None, None, int(settings.SPLINE_LDS_WEIGHTS))
         ctx.save_for_backward(x, out)
         ctx.pairs, ctx.relu, ctx.dims = pairs, relu, (conv.cin, conv.cout)
         return out
@@ -211,7 +211,7 @@ class SplineConv(nn.Module):
         pk = ops.spline_packed_buffer(self.cout, M, x.device) if want_packed and ops.spline_packed_supported(self.cout) else None
         xc = x.contiguous()
         call("gdm_spline_direct3_hip", xc, self.weight, rowptr, src, attr, self._root_t(), self.bias, M, self.cin, self.cout, KERNEL_SIZE,
-             int(relu), None, out_t, pk)
+             int(relu), None, out_t, pk, int(settings.SPLINE_LDS_WEIGHTS))
         return out_t, pk
 
     def forward_grouped_cm(self, xt, rowptr, pairs, relu, xpk=None, want_packed=False):
@@ -253,7 +253,7 @@ class SplineConv(nn.Module):
             out = torch.empty((M, self.cout), dtype=torch.float32, device=x.device)
             xc = x.contiguous()
             call("gdm_spline_direct3_hip", xc, self.weight, rowptr, src, attr, self._root_t(), self.bias, M, self.cin, self.cout,
-                 KERNEL_SIZE, int(relu), out, None, None)
+                 KERNEL_SIZE, int(relu), out, None, None, int(settings.SPLINE_LDS_WEIGHTS))
             return out
         if (settings.USE_MFMA_GEMM and settings.USE_GROUPED_SPLINE and pairs is not None and not torch.is_grad_enabled() and x.is_cuda
                 and self.cin % 128 == 0 and self.cout == 128):

@@ -223,10 +223,13 @@ int gdm_spline_aggregate_bwd_hip(const float* grad_out, const int32_t* rowptr, c
  * split-bf16 operand planes of the next layer's grouped GEMM (gdm_conv3x3_act_bytes(1, C, 1, M) bytes, the layout
  * gdm_conv3x3_pack_act_hip(x_cm, 1, C, 1, M) writes; zero border in place, C = 128, 256 or 512), so that the pack launch between two
  * SplineConv layers (SplineCNN.py:238-239) is not needed.  Each may be NULL, but not both out and out_t; out_t and out_packed need
- * C % 4 == 0, 512 % C == 0 and 16-byte aligned buffers. */
+ * C % 4 == 0, 512 % C == 0 and 16-byte aligned buffers.
+ * weights_in_lds != 0: where it applies (C = 128, kernel_size = 5, the 16-byte path) a workgroup owns 16 output channels and a run of
+ * vertices and reads its slice of the weight table, [125][Cin][16] (72,000 B at Cin = 9), from LDS instead of fetching every weight row
+ * from L2 once per (edge, corner); 0: always the kernel that reads the table in global memory.  Same arithmetic, same bits. */
 int gdm_spline_direct3_hip(const float* x, const float* weight, const int32_t* rowptr, const int32_t* src, const float* attr,
                            const float* root_t, const float* bias, int M, int Cin, int C, int kernel_size, int relu,
-                           float* out, float* out_t, void* out_packed, void* stream);
+                           float* out, float* out_t, void* out_packed, int weights_in_lds, void* stream);
 /* Edge-grouped form of the 128-channel layers: only the (source vertex, kernel index) pairs that some edge needs are multiplied,
  * 4x fewer FLOPs than the dense form and no [M, 125*C] table.  gdm_gemm_grouped_hip: Y[r, 0:128] = Wpk[tile_co0[r/256] + 0:128, :] .
  * X[rowidx[r], :] for R % 256 == 0 rows (pairs sorted by kernel index, groups padded to 256 rows with rowidx = 0), X packed by
@@ -944,6 +947,15 @@ int gdm_point_heads2_hip(const float* a, const float* b, int Ca, const float* ra
                          const void* const* w, const float* const* scale, const float* const* shift, const int* act, int feat_layer,
                          int res_layer, const void* w_last, const float* shift_last, int c_last, float* out_feat, float* out_last,
                          void* stream);
+/* The same with one more output: out_rows u8[B*N, 512] (may be NULL), the matching kernel's split-bf16 operand rows of out_feat -- byte
+ * for byte what gdm_match_pack_hip(out_feat, B, 128, N, GDM_MATCH_BF16X3, out_rows) writes, formed from the kernel's own accumulators
+ * (the norm and the row write are the pack kernel's code, csrc/gdm_match_rows.h), so that no pack launch stands between the heads and
+ * gdm_match_packed_hip.  It needs feat_layer >= 0 and a 16-byte aligned buffer of gdm_match_rows_bytes(B * N) bytes.  out_feat and
+ * out_last do not depend on whether the rows are asked for. */
+int gdm_point_heads3_hip(const float* a, const float* b, int Ca, const float* ra, const float* rb, int rCa, int B, int N, int nlayer,
+                         const void* const* w, const float* const* scale, const float* const* shift, const int* act, int feat_layer,
+                         int res_layer, const void* w_last, const float* shift_last, int c_last, float* out_feat, float* out_last,
+                         void* out_rows, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * One per-point (1x1) layer in a single launch (inference): concat-free, BatchNorm / bias / activation / residual branch folded in.
