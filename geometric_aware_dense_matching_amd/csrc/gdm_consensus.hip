@@ -4,8 +4,8 @@
 // pair of a crop, how many others agree with it (first and second order), pick seeds from those integer scores, fit one weighted
 // hypothesis per seed and keep the one with the most inliers -- no draws, a fixed set of launches:
 //   consensus_compact_kernel  one workgroup per crop: the selected correspondences (mask != 0) in point order as six fp32 planes
-//                             (A = matched model vertex, B = scene point), the compaction of ransac_compact_kernel
-//                             (gdm_pose_robust.hip), plus sel[k] = the point index of compacted k; score / degree start at -1
+//                             (A = matched model vertex, B = scene point), the compact_pairs of gdm_pose_fit.h that
+//                             ransac_compact_kernel runs, plus sel[k] = the point index of compacted k; score / degree start at -1
 //   consensus_pairs_kernel    a 64-row tile of a crop's n x n compatibility BIT matrix: one lane per column, __ballot makes the word
 //   consensus_score_kernel    deg_i = |row_i| and s_i = sum_{j in row_i} |row_i & row_j|: one lane per 64-bit word of a row (that is
 //                             the N <= 4096 limit), 64 rows j staged in LDS once for the 16 rows i of a workgroup
@@ -14,8 +14,9 @@
 //                             of block_sum, the fit of gdm_kabsch_fit.inc, and that hypothesis' inlier count (ballot + popcount)
 //   consensus_select_kernel   one workgroup per crop: the largest count (lowest t on ties) and the fp64 refit on its inliers
 // No n x n float tensor exists: the workspace holds n x n bits per crop (512 KiB at N = 2048, 2 MiB at 4096).  No floating-point
-// atomics; every sum has one order, so two launches give the same bytes.
-#include "gdm_common.h"
+// atomics; every sum has one order, so two launches give the same bytes.  The fit, the residual, the statistics and block_sum are
+// the ones RANSAC and Kabsch use (gdm_pose_fit.h).
+#include "gdm_pose_fit.h"
 
 namespace {
 
@@ -27,62 +28,6 @@ constexpr int SCORE_ROWS_PER_WAVE = 4;  // consensus_score_kernel: the rows i a 
 constexpr int SCORE_ROWS = 4 * SCORE_ROWS_PER_WAVE;
 constexpr int SCORE_SLOTS = 64 * (MAX_N / 64) / 256;                // words of a full 64-row tile per thread
 
-__device__ __forceinline__ void sentinel_pose(float* o)
-{
-    o[0] = 1.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
-    o[4] = 0.f; o[5] = 1.f; o[6] = 0.f; o[7] = 0.f;
-    o[8] = 0.f; o[9] = 0.f; o[10] = 1.f; o[11] = -1000.f;
-}
-
-// [R | t] from the 16 statistics { n, sum A, sum B, sum A_i B_j }, n > 0 (the same math as kabsch_solve_kernel).
-__device__ __forceinline__ void kabsch_fit(const double* st, float* o)
-{
-    const double n = st[0];
-#include "gdm_kabsch_fit.inc"
-}
-
-// Squared residual |R a + t - b|^2 in fp32: the form of gdm_pose_robust.hip, operation for operation.
-__device__ __forceinline__ float residual2(const float* rt, float ax, float ay, float az, float bx, float by, float bz)
-{
-    const float ex = rt[0] * ax + rt[1] * ay + rt[2] * az + rt[3] - bx;
-    const float ey = rt[4] * ax + rt[5] * ay + rt[6] * az + rt[7] - by;
-    const float ez = rt[8] * ax + rt[9] * ay + rt[10] * az + rt[11] - bz;
-    return ex * ex + ey * ey + ez * ez;
-}
-
-__device__ __forceinline__ void acc_pair_w(double* acc, double w, double ax, double ay, double az, double bx, double by, double bz)
-{
-    const double wx = w * ax, wy = w * ay, wz = w * az;
-    acc[0] += w;
-    acc[1] += wx; acc[2] += wy; acc[3] += wz;
-    acc[4] += w * bx; acc[5] += w * by; acc[6] += w * bz;
-    acc[7] += wx * bx; acc[8] += wx * by; acc[9] += wx * bz;
-    acc[10] += wy * bx; acc[11] += wy * by; acc[12] += wy * bz;
-    acc[13] += wz * bx; acc[14] += wz * by; acc[15] += wz * bz;
-}
-
-// Sum of 16 per-thread accumulators over a 256-thread block in a fixed order (butterfly in each wave, then waves 0..3);
-// every thread gets the totals in tot[].
-__device__ __forceinline__ void block_sum16(double* acc, double (*red)[16], double* tot)
-{
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        double v = acc[i];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        acc[i] = v;
-    }
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < 16; ++i) red[threadIdx.x >> 6][i] = acc[i];
-    __syncthreads();
-    for (int i = 0; i < 16; ++i) tot[i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // pts f32[B][6][N]: planes ax, ay, az, bx, by, bz of the selected pairs in point order; nsel i32[B] their number; sel i32[B][N] the
 // point index of compacted k (k < nsel).  score / degree i32[B][N] are set to -1 here; consensus_score_kernel fills the selected ones.
 __global__ __launch_bounds__(256) void consensus_compact_kernel(const float* __restrict__ scene_xyz, long scene_bstride, int pt_stride,
@@ -92,38 +37,7 @@ __global__ __launch_bounds__(256) void consensus_compact_kernel(const float* __r
                                                                 int32_t* __restrict__ sel, int32_t* __restrict__ score,
                                                                 int32_t* __restrict__ degree)
 {
-    __shared__ int wtot[4];
-    const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* sp = scene_xyz + (long)b * scene_bstride;
-    float* P = pts + (long)b * 6 * N;
-    int run = 0;
-    for (int c0 = 0; c0 < N; c0 += 256) {
-        const int i = c0 + threadIdx.x;
-        const bool on = i < N && mask[(long)b * N + i];
-        const u64 bal = __ballot(on);
-        const int below = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[wave] = __popcll(bal);
-        __syncthreads();
-        int off = run;
-        for (int w = 0; w < wave; ++w) off += wtot[w];
-        if (i < N) { score[(long)b * N + i] = -1; degree[(long)b * N + i] = -1; }
-        if (on) {
-            int j = best_idx[(long)b * N + i];
-            j = min(max(j, 0), M - 1);
-            const int k = off + below;
-            P[k] = model_xyz[3 * j];
-            P[N + k] = model_xyz[3 * j + 1];
-            P[2 * N + k] = model_xyz[3 * j + 2];
-            P[3 * N + k] = sp[(long)i * pt_stride];
-            P[4 * N + k] = sp[(long)i * pt_stride + ch_stride];
-            P[5 * N + k] = sp[(long)i * pt_stride + 2 * ch_stride];
-            sel[(long)b * N + k] = i;
-        }
-        run += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) nsel[b] = run;
+    compact_pairs<true>(scene_xyz, scene_bstride, pt_stride, ch_stride, model_xyz, best_idx, mask, N, M, pts, nsel, sel, score, degree);
 }
 
 // bits u64[B][N][W], W = ceil(N / 64): bit (j & 63) of word j >> 6 of row i is C_ij (THE CONSENSUS RULE, step 1), for i, j < n; the
@@ -346,9 +260,9 @@ __global__ __launch_bounds__(256) void consensus_fit_kernel(const float* __restr
         }
     }
     cnt = wave_sum(cnt);
-    if (lane == 0) cred[wave] = cnt;                                // visible after block_sum16's barrier
+    if (lane == 0) cred[wave] = cnt;                                // visible after block_sum's barrier
     double tot[16];
-    block_sum16(acc, red, tot);
+    block_sum<16>(acc, red, tot);
     const int n_pos = cred[0] + cred[1] + cred[2] + cred[3];
     if (n_pos < 3) {                                                // block-uniform
         if (threadIdx.x == 0) { sentinel_pose(o); counts[(long)b * S + t] = -1; }
@@ -393,21 +307,7 @@ __global__ __launch_bounds__(256) void consensus_select_kernel(const float* __re
     }
     float rt[12];
     for (int e = 0; e < 12; ++e) rt[e] = hyp[((long)b * S + bt) * 12 + e];
-    const float* P = pts + (long)b * 6 * N;
-    double acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float ax = P[i], ay = P[N + i], az = P[2 * N + i], bx = P[3 * N + i], by = P[4 * N + i], bz = P[5 * N + i];
-        if (residual2(rt, ax, ay, az, bx, by, bz) <= thr2) acc_pair_w(acc, 1.0, ax, ay, az, bx, by, bz);
-    }
-    double tot[16];
-    block_sum16(acc, red, tot);
-    if (threadIdx.x == 0) {
-        kabsch_fit(tot, o);
-        valid[b] = 1;
-        winner[b] = bt;
-    }
+    refit_winner(pts + (long)b * 6 * N, N, n, rt, thr2, red, b, bt, o, valid, winner);
 }
 
 struct ConsensusWs {
@@ -420,23 +320,17 @@ struct ConsensusWs {
 // Every piece is a multiple of 16 bytes, the bit matrix (the only 8-byte type) first after the planes.
 ConsensusWs consensus_ws(void* base, int B, int N, int S)
 {
-    const auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t W = (size_t)(N + 63) / 64;
-    const size_t pts = up((size_t)B * 6 * N * sizeof(float));
-    const size_t bits = up((size_t)B * N * W * sizeof(u64));
-    const size_t bn = up((size_t)B * N * sizeof(int32_t));
-    const size_t nsel = up((size_t)B * sizeof(int32_t));
-    const size_t seedk = up((size_t)B * S * sizeof(int32_t));
+    const size_t bn = (size_t)B * N * sizeof(int32_t);
     ConsensusWs w;
-    char* p = (char*)base;
-    w.pts = (float*)p; p += pts;
-    w.bits = (u64*)p; p += bits;
-    w.sel = (int32_t*)p; p += bn;
-    w.sc = (int32_t*)p; p += bn;
-    w.dg = (int32_t*)p; p += bn;
-    w.nsel = (int32_t*)p; p += nsel;
-    w.seedk = (int32_t*)p; p += seedk;
-    w.bytes = pts + bits + 3 * bn + nsel + seedk;
+    w.bytes = 0;
+    w.pts = carve<float>(base, w.bytes, (size_t)B * 6 * N * sizeof(float), 16);
+    w.bits = carve<u64>(base, w.bytes, (size_t)B * N * W * sizeof(u64), 16);
+    w.sel = carve<int32_t>(base, w.bytes, bn, 16);
+    w.sc = carve<int32_t>(base, w.bytes, bn, 16);
+    w.dg = carve<int32_t>(base, w.bytes, bn, 16);
+    w.nsel = carve<int32_t>(base, w.bytes, (size_t)B * sizeof(int32_t), 16);
+    w.seedk = carve<int32_t>(base, w.bytes, (size_t)B * S * sizeof(int32_t), 16);
     return w;
 }
 
@@ -454,12 +348,11 @@ extern "C" int gdm_consensus_pose_hip(const float* scene_xyz, long scene_bstride
                                       uint8_t* valid, int32_t* score, int32_t* degree, int32_t* seed_idx, float* hyp_RT, int32_t* counts,
                                       int32_t* winner, void* stream)
 {
-    GDM_CHECK_ARG(scene_xyz && model_xyz && best_idx && mask && workspace && RT && valid && score && degree && seed_idx && hyp_RT &&
-                      counts && winner,
-                  "gdm_consensus_pose_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_consensus_pose_hip: bad shape B=%d N=%d M=%d", B, N, M);
-    GDM_CHECK_ARG(pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0, "gdm_consensus_pose_hip: bad scene strides");
-    GDM_CHECK_ARG(B <= 65535, "gdm_consensus_pose_hip: B=%d > 65535", B);
+    int rc = pair_entry_check("gdm_consensus_pose_hip",
+                              scene_xyz && model_xyz && best_idx && mask && workspace && RT && valid && score && degree && seed_idx &&
+                                  hyp_RT && counts && winner,
+                              B, N, M, true, scene_bstride, pt_stride, ch_stride, true);
+    if (rc) return rc;
     GDM_CHECK_ARG(N <= MAX_N, "gdm_consensus_pose_hip: N=%d > %d (one lane per 64-bit word of a bit row)", N, MAX_N);
     GDM_CHECK_ARG(seeds >= 1 && seeds <= MAX_SEEDS, "gdm_consensus_pose_hip: seeds=%d not in [1,%d]", seeds, MAX_SEEDS);
     GDM_CHECK_ARG(tau > 0.f && tau < 1e18f, "gdm_consensus_pose_hip: tau=%g must be > 0", (double)tau);
@@ -472,8 +365,7 @@ extern "C" int gdm_consensus_pose_hip(const float* scene_xyz, long scene_bstride
     const float tau2 = tau * tau, thr2 = inlier_dist * inlier_dist;
     hipLaunchKernelGGL(consensus_compact_kernel, dim3(B), dim3(256), 0, s, scene_xyz, scene_bstride, pt_stride, ch_stride, model_xyz,
                        best_idx, mask, N, M, w.pts, w.nsel, w.sel, score, degree);
-    int rc = gdm_launch_status("consensus_compact_kernel");
-    if (rc) return rc;
+    if ((rc = gdm_launch_status("consensus_compact_kernel"))) return rc;
     hipLaunchKernelGGL(consensus_pairs_kernel, dim3(tiles, B), dim3(256), 0, s, w.pts, w.nsel, N, W, tau2, w.bits);
     if ((rc = gdm_launch_status("consensus_pairs_kernel"))) return rc;
     hipLaunchKernelGGL(consensus_score_kernel, dim3(gdm_cdiv(N, SCORE_ROWS), B), dim3(256), (size_t)65 * W * sizeof(u64), s, w.bits, w.nsel, w.sel, N, W, w.sc, w.dg, score, degree);

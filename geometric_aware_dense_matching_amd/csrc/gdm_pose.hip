@@ -8,7 +8,7 @@
 // A = model vertex matched to the point, B = scene point.  fp64 accumulation: H = sum A B^T - n cA cB^T cancels heavily.
 // kabsch_solve_kernel turns the 16 statistics into [R|t] on the device, one lane per crop (no library SVD, no host
 // synchronisation, so the whole step can be captured in a hipGraph).
-#include "gdm_common.h"
+#include "gdm_pose_fit.h"
 
 namespace {
 
@@ -27,28 +27,15 @@ __global__ __launch_bounds__(256) void kabsch_stats_kernel(const float* __restri
         if (!mask[(long)b * N + i]) continue;
         int j = best_idx[(long)b * N + i];
         j = min(max(j, 0), M - 1);
-        const double ax = model_xyz[3 * j], ay = model_xyz[3 * j + 1], az = model_xyz[3 * j + 2];
-        const double bx = sp[(long)i * pt_stride], by = sp[(long)i * pt_stride + ch_stride], bz = sp[(long)i * pt_stride + 2 * ch_stride];
-        acc[0] += 1.0;
-        acc[1] += ax; acc[2] += ay; acc[3] += az;
-        acc[4] += bx; acc[5] += by; acc[6] += bz;
-        acc[7] += ax * bx; acc[8] += ax * by; acc[9] += ax * bz;
-        acc[10] += ay * bx; acc[11] += ay * by; acc[12] += ay * bz;
-        acc[13] += az * bx; acc[14] += az * by; acc[15] += az * bz;
+        acc_pair(acc, model_xyz[3 * j], model_xyz[3 * j + 1], model_xyz[3 * j + 2], sp[(long)i * pt_stride],
+                 sp[(long)i * pt_stride + ch_stride], sp[(long)i * pt_stride + 2 * ch_stride]);
     }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        double v = acc[i];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        acc[i] = v;
-    }
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < 16; ++i) red[threadIdx.x >> 6][i] = acc[i];
-    __syncthreads();
+    wave_sums<16>(acc, red);
     if (threadIdx.x < 16) out[(long)b * 16 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// The fit itself (Horn's quaternion, fp64 Jacobi: gdm_kabsch_fit.inc), one lane per crop.
+// The fit itself (Horn's quaternion, fp64 Jacobi), one lane per crop.  The two solve kernels include the fragment gdm_kabsch_fit.inc
+// themselves and do not call kabsch_fit, its wrapper: through the wrapper the same statements compile to other instructions.
 __global__ __launch_bounds__(64) void kabsch_solve_kernel(const double* __restrict__ stats, int B, int min_points,
                                                           float* __restrict__ RT, uint8_t* __restrict__ valid)
 {
@@ -58,9 +45,7 @@ __global__ __launch_bounds__(64) void kabsch_solve_kernel(const double* __restri
     const double n = st[0];
     float* o = RT + (long)b * 12;
     if (!(n >= (double)min_points)) {                                   // evaluator.py:94-96 sentinel pose
-        o[0] = 1.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
-        o[4] = 0.f; o[5] = 1.f; o[6] = 0.f; o[7] = 0.f;
-        o[8] = 0.f; o[9] = 0.f; o[10] = 1.f; o[11] = -1000.f;
+        sentinel_pose(o);
         valid[b] = 0;
         return;
     }
@@ -88,7 +73,6 @@ __global__ __launch_bounds__(256) void kabsch_stats_w_kernel(const float* __rest
         if (!mask[(long)b * N + i]) continue;
         const float wf = weight[(long)b * N + i];
         if (!(wf > 0.f) || !(wf <= 3.402823466e38f)) continue;          // NaN, inf, zero and negative weights are skipped
-        const double w = wf;
         double ax, ay, az;
         if (target) {
             const float* t = target + ((long)b * N + i) * 3;
@@ -98,28 +82,12 @@ __global__ __launch_bounds__(256) void kabsch_stats_w_kernel(const float* __rest
             j = min(max(j, 0), M - 1);
             ax = model_xyz[3 * j]; ay = model_xyz[3 * j + 1]; az = model_xyz[3 * j + 2];
         }
-        const double bx = sp[(long)i * pt_stride], by = sp[(long)i * pt_stride + ch_stride], bz = sp[(long)i * pt_stride + 2 * ch_stride];
-        const double wax = w * ax, way = w * ay, waz = w * az;
         cnt += 1;
-        acc[0] += w;
-        acc[1] += wax; acc[2] += way; acc[3] += waz;
-        acc[4] += w * bx; acc[5] += w * by; acc[6] += w * bz;
-        acc[7] += wax * bx; acc[8] += wax * by; acc[9] += wax * bz;
-        acc[10] += way * bx; acc[11] += way * by; acc[12] += way * bz;
-        acc[13] += waz * bx; acc[14] += waz * by; acc[15] += waz * bz;
+        acc_pair_w(acc, wf, ax, ay, az, sp[(long)i * pt_stride], sp[(long)i * pt_stride + ch_stride], sp[(long)i * pt_stride + 2 * ch_stride]);
     }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        double v = acc[i];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        acc[i] = v;
-    }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if ((threadIdx.x & 63) == 0) {
-        for (int i = 0; i < 16; ++i) red[threadIdx.x >> 6][i] = acc[i];
-        cred[threadIdx.x >> 6] = cnt;
-    }
-    __syncthreads();
+    cnt = wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = cnt;          // visible after wave_sums' barrier
+    wave_sums<16>(acc, red);
     if (threadIdx.x < 16) out[(long)b * 16 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
     if (threadIdx.x == 16) count[b] = cred[0] + cred[1] + cred[2] + cred[3];
 }
@@ -134,9 +102,7 @@ __global__ __launch_bounds__(64) void kabsch_solve_w_kernel(const double* __rest
     const double n = st[0];
     float* o = RT + (long)b * 12;
     if (!(count[b] >= min_points) || !(n > 0.0)) {
-        o[0] = 1.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
-        o[4] = 0.f; o[5] = 1.f; o[6] = 0.f; o[7] = 0.f;
-        o[8] = 0.f; o[9] = 0.f; o[10] = 1.f; o[11] = -1000.f;
+        sentinel_pose(o);
         valid[b] = 0;
         return;
     }

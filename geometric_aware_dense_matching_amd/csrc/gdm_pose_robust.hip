@@ -13,26 +13,13 @@
 // and applies the reference's convergence rule per crop, freezing a crop on the device once it stops.
 // icp_plane_update_kernel is the opt-in point-to-plane refiner (no counterpart in the reference): the same transform and search, then one
 // Gauss-Newton step on n . (x - q) with optional normal gating and Huber weights, frozen and flagged when the crop is degenerate.
-#include "gdm_common.h"
+// The fit, the residual, the statistics, the reductions, the compaction and the two per-pair steps of ICP are gdm_pose_fit.h.
+#include "gdm_pose_fit.h"
 
 namespace {
 
 constexpr int SCORE_HYP_PER_WAVE = 4;
 constexpr int SCORE_HYP_PER_BLOCK = 4 * SCORE_HYP_PER_WAVE;        // 256 threads = 4 waves
-
-__device__ __forceinline__ void sentinel_pose(float* o)
-{
-    o[0] = 1.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
-    o[4] = 0.f; o[5] = 1.f; o[6] = 0.f; o[7] = 0.f;
-    o[8] = 0.f; o[9] = 0.f; o[10] = 1.f; o[11] = -1000.f;
-}
-
-// [R | t] from the 16 statistics { n, sum A, sum B, sum A_i B_j }, n >= 1 (the same math as kabsch_solve_kernel).
-__device__ __forceinline__ void kabsch_fit(const double* st, float* o)
-{
-    const double n = st[0];
-#include "gdm_kabsch_fit.inc"
-}
 
 // lowbias32 (include/gdm.h, GDM_RANSAC sampling)
 __device__ __forceinline__ uint32_t mix32(uint32_t x)
@@ -41,78 +28,13 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x)
     return x;
 }
 
-// Squared residual |R a + t - b|^2 in fp32, evaluated in one fixed order (scoring and refit must agree on every inlier).
-__device__ __forceinline__ float residual2(const float* rt, float ax, float ay, float az, float bx, float by, float bz)
-{
-    const float ex = rt[0] * ax + rt[1] * ay + rt[2] * az + rt[3] - bx;
-    const float ey = rt[4] * ax + rt[5] * ay + rt[6] * az + rt[7] - by;
-    const float ez = rt[8] * ax + rt[9] * ay + rt[10] * az + rt[11] - bz;
-    return ex * ex + ey * ey + ez * ez;
-}
-
-__device__ __forceinline__ void acc_pair(double* acc, double ax, double ay, double az, double bx, double by, double bz)
-{
-    acc[0] += 1.0;
-    acc[1] += ax; acc[2] += ay; acc[3] += az;
-    acc[4] += bx; acc[5] += by; acc[6] += bz;
-    acc[7] += ax * bx; acc[8] += ax * by; acc[9] += ax * bz;
-    acc[10] += ay * bx; acc[11] += ay * by; acc[12] += ay * bz;
-    acc[13] += az * bx; acc[14] += az * by; acc[15] += az * bz;
-}
-
-// Sum of NA per-thread accumulators over a 256-thread block in a fixed order (butterfly in each wave, then waves 0..3);
-// every thread gets the totals in tot[].
-template <int NA>
-__device__ __forceinline__ void block_sum(double* acc, double (*red)[NA], double* tot)
-{
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        double v = acc[i];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        acc[i] = v;
-    }
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < NA; ++i) red[threadIdx.x >> 6][i] = acc[i];
-    __syncthreads();
-    for (int i = 0; i < NA; ++i) tot[i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
-}
-
 // pts f32[B][6][N]: planes ax, ay, az, bx, by, bz of the selected pairs in point order; nsel i32[B] their number.
 __global__ __launch_bounds__(256) void ransac_compact_kernel(const float* __restrict__ scene_xyz, long scene_bstride, int pt_stride,
                                                              int ch_stride, const float* __restrict__ model_xyz,
                                                              const int32_t* __restrict__ best_idx, const uint8_t* __restrict__ mask,
                                                              int N, int M, float* __restrict__ pts, int32_t* __restrict__ nsel)
 {
-    __shared__ int wtot[4];
-    const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* sp = scene_xyz + (long)b * scene_bstride;
-    float* P = pts + (long)b * 6 * N;
-    int run = 0;
-    for (int c0 = 0; c0 < N; c0 += 256) {
-        const int i = c0 + threadIdx.x;
-        const bool sel = i < N && mask[(long)b * N + i];
-        const unsigned long long bal = __ballot(sel);
-        const int below = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[wave] = __popcll(bal);
-        __syncthreads();
-        int off = run;
-        for (int w = 0; w < wave; ++w) off += wtot[w];
-        if (sel) {
-            int j = best_idx[(long)b * N + i];
-            j = min(max(j, 0), M - 1);
-            const int k = off + below;
-            P[k] = model_xyz[3 * j];
-            P[N + k] = model_xyz[3 * j + 1];
-            P[2 * N + k] = model_xyz[3 * j + 2];
-            P[3 * N + k] = sp[(long)i * pt_stride];
-            P[4 * N + k] = sp[(long)i * pt_stride + ch_stride];
-            P[5 * N + k] = sp[(long)i * pt_stride + 2 * ch_stride];
-        }
-        run += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) nsel[b] = run;
+    compact_pairs<false>(scene_xyz, scene_bstride, pt_stride, ch_stride, model_xyz, best_idx, mask, N, M, pts, nsel, nullptr, nullptr, nullptr);
 }
 
 // hyp f32[B][H][12]: hypothesis poses.  Crops with n < min_points get the identity (never scored).
@@ -126,9 +48,8 @@ __global__ __launch_bounds__(64) void ransac_hyp_kernel(const float* __restrict_
     float* o = hyp + ((long)b * H + h) * 12;
     const int n = nsel[b];
     if (n < min_points) {
-        o[0] = 1.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
-        o[4] = 0.f; o[5] = 1.f; o[6] = 0.f; o[7] = 0.f;
-        o[8] = 0.f; o[9] = 0.f; o[10] = 1.f; o[11] = 0.f;
+        sentinel_pose(o);
+        o[11] = 0.f;                                                // deliberate: [I | 0], not the sentinel, in these unscored rows
         return;
     }
     if (h == 0) {                                                   // pvn3d_eval_utils_kpls.py:95 curr_RT = best_fit_transform(A, B)
@@ -236,21 +157,7 @@ __global__ __launch_bounds__(256) void ransac_select_kernel(const float* __restr
     __syncthreads();
     float rt[12];
     for (int e = 0; e < 12; ++e) rt[e] = s_rt[e];
-    const float* P = pts + (long)b * 6 * N;
-    double acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) {                    // :108 best_fit_transform(A[match_idx], B[match_idx])
-        const float ax = P[i], ay = P[N + i], az = P[2 * N + i], bx = P[3 * N + i], by = P[4 * N + i], bz = P[5 * N + i];
-        if (residual2(rt, ax, ay, az, bx, by, bz) <= thr2) acc_pair(acc, ax, ay, az, bx, by, bz);
-    }
-    double tot[16];
-    block_sum<16>(acc, red, tot);
-    if (threadIdx.x == 0) {
-        kabsch_fit(tot, o);
-        valid[b] = 1;
-        winner[b] = first;
-    }
+    refit_winner(pts + (long)b * 6 * N, N, n, rt, thr2, red, b, first, o, valid, winner);
 }
 
 // query f32[B,N,3] = R^T (b - t): the scene points in the model frame of the current pose.
@@ -287,16 +194,11 @@ __global__ __launch_bounds__(256) void icp_update_kernel(const float* __restrict
     double acc[17];
 #pragma unroll
     for (int i = 0; i < 17; ++i) acc[i] = 0.0;
-    for (int i = threadIdx.x; i < N; i += 256) {
-        if (!mask[(long)b * N + i]) continue;
-        const float dd = fmaxf(d2[(long)b * N + i], 0.f);
-        if (reject2 >= 0.f && !(dd <= reject2)) continue;
-        int j = nn[(long)b * N + i];
-        j = min(max(j, 0), M - 1);
+    for_icp_pairs(mask, d2, nn, b, N, M, reject2, [&](int i, int j, float dd) {
         acc_pair(acc, model_xyz[3 * j], model_xyz[3 * j + 1], model_xyz[3 * j + 2], sp[(long)i * pt_stride],
                  sp[(long)i * pt_stride + ch_stride], sp[(long)i * pt_stride + 2 * ch_stride]);
         acc[16] += sqrt((double)dd);
-    }
+    });
     double tot[17];
     block_sum<17>(acc, red, tot);
     if (threadIdx.x != 0) return;
@@ -309,9 +211,8 @@ __global__ __launch_bounds__(256) void icp_update_kernel(const float* __restrict
 }
 
 // One point-to-plane Gauss-Newton iteration of every active crop (include/gdm.h gdm_icp_plane_update_hip): x = query (the scene
-// point in the model frame), q / n = the nearest vertex and its unit normal, r = n . (x - q), J = [x cross n ; n].  Per thread 30 fp64
-// sums { A = sum w J J^T (upper triangle, 21), g = sum w J r (6), S = sum w, L2 = sum w |x|^2, E = sum |r| } and the pair count, reduced
-// in the fixed order of block_sum; thread 0 solves (gdm_icp_plane_solve.inc) and applies the stop rule of icp_update_kernel.
+// point in the model frame), q / n = the nearest vertex and its unit normal.  Per thread the 30 fp64 sums of acc_plane_pair and the pair
+// count, reduced in the fixed order of block_sum; thread 0 solves (gdm_icp_plane_solve.inc) and applies the stop rule of icp_update_kernel.
 __global__ __launch_bounds__(256) void icp_plane_update_kernel(const float* __restrict__ scene_nrm, long scene_bstride, int pt_stride,
                                                                int ch_stride, const float* __restrict__ query,
                                                                const float* __restrict__ model_xyz, const float* __restrict__ model_nrm,
@@ -334,12 +235,7 @@ __global__ __launch_bounds__(256) void icp_plane_update_kernel(const float* __re
 #pragma unroll
     for (int i = 0; i < 30; ++i) acc[i] = 0.0;
     int cnt = 0;
-    for (int i = threadIdx.x; i < N; i += 256) {
-        if (!mask[(long)b * N + i]) continue;
-        const float dd = fmaxf(d2[(long)b * N + i], 0.f);
-        if (reject2 >= 0.f && !(dd <= reject2)) continue;
-        int j = nn[(long)b * N + i];
-        j = min(max(j, 0), M - 1);
+    for_icp_pairs(mask, d2, nn, b, N, M, reject2, [&](int i, int j, float) {
         const double nx = (double)model_nrm[3 * j], ny = (double)model_nrm[3 * j + 1], nz = (double)model_nrm[3 * j + 2];
         if (sn) {                                                   // (R^T s) . n >= normal_gate keeps the pair
             const double sx = (double)sn[(long)i * pt_stride], sy = (double)sn[(long)i * pt_stride + ch_stride],
@@ -347,29 +243,14 @@ __global__ __launch_bounds__(256) void icp_plane_update_kernel(const float* __re
             const double mx = rt[0] * sx + rt[4] * sy + rt[8] * sz;
             const double my = rt[1] * sx + rt[5] * sy + rt[9] * sz;
             const double mz = rt[2] * sx + rt[6] * sy + rt[10] * sz;
-            if (!(mx * nx + my * ny + mz * nz >= normal_gate)) continue;
+            if (!(mx * nx + my * ny + mz * nz >= normal_gate)) return;
         }
         const float* xq = query + ((long)b * N + i) * 3;
-        const double x = (double)xq[0], y = (double)xq[1], z = (double)xq[2];
-        const double r = nx * (x - (double)model_xyz[3 * j]) + ny * (y - (double)model_xyz[3 * j + 1]) +
-                         nz * (z - (double)model_xyz[3 * j + 2]);
-        const double ar = fabs(r);
-        const double w = (huber_delta <= 0.0 || ar <= huber_delta) ? 1.0 : huber_delta / ar;
-        const double J[6] = {y * nz - z * ny, z * nx - x * nz, x * ny - y * nx, nx, ny, nz};
-        int e = 0;
-#pragma unroll
-        for (int p = 0; p < 6; ++p) {
-            const double wj = w * J[p];
-#pragma unroll
-            for (int q = p; q < 6; ++q) acc[e++] += wj * J[q];
-            acc[21 + p] += wj * r;
-        }
-        acc[27] += w;
-        acc[28] += w * (x * x + y * y + z * z);
-        acc[29] += ar;
+        acc_plane_pair(acc, (double)xq[0], (double)xq[1], (double)xq[2], nx, ny, nz, (double)model_xyz[3 * j],
+                       (double)model_xyz[3 * j + 1], (double)model_xyz[3 * j + 2], huber_delta);
         cnt += 1;
-    }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    });
+    cnt = wave_sum(cnt);
     if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = cnt;      // visible after block_sum's barrier
     double tot[30];
     block_sum<30>(acc, red, tot);
@@ -401,14 +282,10 @@ struct RansacWs {
 RansacWs ransac_ws(void* base, int B, int N, int H)
 {
     RansacWs w;
-    const size_t pts = ((size_t)B * 6 * N * sizeof(float) + 255) & ~(size_t)255;
-    const size_t hyp = ((size_t)B * H * 12 * sizeof(float) + 255) & ~(size_t)255;
-    const size_t nsel = ((size_t)B * sizeof(int32_t) + 255) & ~(size_t)255;
-    char* p = (char*)base;
-    w.pts = (float*)p;
-    w.hyp = (float*)(p + pts);
-    w.nsel = (int32_t*)(p + pts + hyp);
-    w.bytes = pts + hyp + nsel;
+    w.bytes = 0;
+    w.pts = carve<float>(base, w.bytes, (size_t)B * 6 * N * sizeof(float), 256);
+    w.hyp = carve<float>(base, w.bytes, (size_t)B * H * 12 * sizeof(float), 256);
+    w.nsel = carve<int32_t>(base, w.bytes, (size_t)B * sizeof(int32_t), 256);
     return w;
 }
 
@@ -425,11 +302,10 @@ extern "C" int gdm_ransac_pose_hip(const float* scene_xyz, long scene_bstride, i
                                    float match_err, double fix_percent, uint32_t seed, int min_points, void* workspace,
                                    size_t workspace_bytes, float* RT, uint8_t* valid, int32_t* counts, int32_t* winner, void* stream)
 {
-    GDM_CHECK_ARG(scene_xyz && model_xyz && best_idx && mask && stats && workspace && RT && valid && counts && winner,
-                  "gdm_ransac_pose_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_ransac_pose_hip: bad shape B=%d N=%d M=%d", B, N, M);
-    GDM_CHECK_ARG(pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0, "gdm_ransac_pose_hip: bad scene strides");
-    GDM_CHECK_ARG(B <= 65535, "gdm_ransac_pose_hip: B=%d > 65535", B);
+    int rc = pair_entry_check("gdm_ransac_pose_hip",
+                              scene_xyz && model_xyz && best_idx && mask && stats && workspace && RT && valid && counts && winner, B, N, M,
+                              true, scene_bstride, pt_stride, ch_stride, true);
+    if (rc) return rc;
     GDM_CHECK_ARG(H >= 1 && H <= GDM_RANSAC_MAX_H, "gdm_ransac_pose_hip: H=%d not in [1,%d]", H, GDM_RANSAC_MAX_H);
     GDM_CHECK_ARG(match_err > 0.f && match_err < 1e18f, "gdm_ransac_pose_hip: match_err=%g must be > 0", (double)match_err);
     GDM_CHECK_ARG(fix_percent > 0.0 && fix_percent <= 1.0, "gdm_ransac_pose_hip: fix_percent=%g not in (0, 1]", fix_percent);
@@ -441,8 +317,7 @@ extern "C" int gdm_ransac_pose_hip(const float* scene_xyz, long scene_bstride, i
     const float thr2 = match_err * match_err;
     hipLaunchKernelGGL(ransac_compact_kernel, dim3(B), dim3(256), 0, s, scene_xyz, scene_bstride, pt_stride, ch_stride, model_xyz,
                        best_idx, mask, N, M, w.pts, w.nsel);
-    int rc = gdm_launch_status("ransac_compact_kernel");
-    if (rc) return rc;
+    if ((rc = gdm_launch_status("ransac_compact_kernel"))) return rc;
     hipLaunchKernelGGL(ransac_hyp_kernel, dim3(gdm_cdiv(H, 64), B), dim3(64), 0, s, w.pts, w.nsel, stats, N, H, min_points, seed, w.hyp);
     if ((rc = gdm_launch_status("ransac_hyp_kernel"))) return rc;
     hipLaunchKernelGGL(ransac_score_kernel, dim3(gdm_cdiv(H, SCORE_HYP_PER_BLOCK), B), dim3(256), 0, s, w.pts, w.nsel, w.hyp, N, H,
@@ -456,10 +331,8 @@ extern "C" int gdm_ransac_pose_hip(const float* scene_xyz, long scene_bstride, i
 extern "C" int gdm_icp_transform_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* RT, int B,
                                      int N, float* query, void* stream)
 {
-    GDM_CHECK_ARG(scene_xyz && RT && query, "gdm_icp_transform_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && N >= 1, "gdm_icp_transform_hip: bad shape B=%d N=%d", B, N);
-    GDM_CHECK_ARG(pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0, "gdm_icp_transform_hip: bad scene strides");
-    GDM_CHECK_ARG(B <= 65535, "gdm_icp_transform_hip: B=%d > 65535", B);
+    const int rc = pair_entry_check("gdm_icp_transform_hip", scene_xyz && RT && query, B, N, -1, true, scene_bstride, pt_stride, ch_stride, true);
+    if (rc) return rc;
     hipLaunchKernelGGL(icp_transform_kernel, dim3(gdm_cdiv(N, 256), B), dim3(256), 0, (hipStream_t)stream, scene_xyz, scene_bstride,
                        pt_stride, ch_stride, RT, N, query);
     return gdm_launch_status("icp_transform_kernel");
@@ -469,9 +342,9 @@ extern "C" int gdm_icp_update_hip(const float* scene_xyz, long scene_bstride, in
                                   const int32_t* nn, const float* d2, const uint8_t* mask, int B, int N, int M, float reject_dist,
                                   double tolerance, int min_points, float* RT, uint8_t* active, int32_t* iters, double* err, void* stream)
 {
-    GDM_CHECK_ARG(scene_xyz && model_xyz && nn && d2 && mask && RT && active && iters && err, "gdm_icp_update_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_icp_update_hip: bad shape B=%d N=%d M=%d", B, N, M);
-    GDM_CHECK_ARG(pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0, "gdm_icp_update_hip: bad scene strides");
+    const int rc = pair_entry_check("gdm_icp_update_hip", scene_xyz && model_xyz && nn && d2 && mask && RT && active && iters && err, B, N, M,
+                                    true, scene_bstride, pt_stride, ch_stride, false);
+    if (rc) return rc;
     GDM_CHECK_ARG(tolerance >= 0.0, "gdm_icp_update_hip: tolerance=%g must be >= 0", tolerance);
     GDM_CHECK_ARG(min_points >= 1, "gdm_icp_update_hip: min_points=%d must be >= 1", min_points);
     const float reject2 = reject_dist >= 0.f ? reject_dist * reject_dist : -1.f;
@@ -487,10 +360,10 @@ extern "C" int gdm_icp_plane_update_hip(const float* scene_nrm, long scene_bstri
                                         uint8_t* active, int32_t* iters, double* err, int32_t* status, int32_t* n_pairs,
                                         void* stream)
 {
-    GDM_CHECK_ARG(query && model_xyz && model_nrm && nn && d2 && mask && RT && active && iters && err && status,
-                  "gdm_icp_plane_update_hip: NULL pointer");
-    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_icp_plane_update_hip: bad shape B=%d N=%d M=%d", B, N, M);
-    GDM_CHECK_ARG(!scene_nrm || (pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0), "gdm_icp_plane_update_hip: bad scene strides");
+    const int rc = pair_entry_check("gdm_icp_plane_update_hip",
+                                    query && model_xyz && model_nrm && nn && d2 && mask && RT && active && iters && err && status, B, N, M,
+                                    scene_nrm != nullptr, scene_bstride, pt_stride, ch_stride, false);
+    if (rc) return rc;
     GDM_CHECK_ARG(!scene_nrm || (normal_gate >= -1.0 && normal_gate <= 1.0), "gdm_icp_plane_update_hip: normal_gate=%g not in [-1, 1]",
                   normal_gate);
     GDM_CHECK_ARG(tolerance >= 0.0, "gdm_icp_plane_update_hip: tolerance=%g must be >= 0", tolerance);

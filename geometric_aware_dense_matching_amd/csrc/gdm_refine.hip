@@ -8,8 +8,8 @@
 //                               draw_tile clears the LDS tile and walks all F faces into it 256 at a time.  The tile holds 64-bit
 //                               keys (fp32 depth bits << 32 | face), 32 KiB, one LDS atomicMin per covered pixel: the nearest face,
 //                               the lower index among equal depths, as gdm_render.hip keeps it in memory.  After the barrier every
-//                               thread forms the fp64 terms of its pixels; the 30 sums and the pair count are reduced in a fixed
-//                               order (butterfly in each wave, then waves 0..3) and 32 threads store the row
+//                               thread forms the fp64 terms of its pixels (acc_plane_pair, the step of icp_plane_update_kernel); the
+//                               30 sums and the pair count are reduced in block_sum's order (gdm_pose_fit.h) and 32 threads store the row
 //                               partial[i, c, tile, 0..31] (the sums, the count, a zero).  No floating-point atomic anywhere: the
 //                               result does not depend on arrival order.
 //   depth_refine_solve_kernel   one thread per (instance, candidate): clamps the window with the same clamped_window, adds the
@@ -18,7 +18,7 @@
 //                               The pose stays fp64.
 // The entry enqueues the init kernel and `iters` pairs of the other two.  A candidate whose status is no longer 0 costs its
 // workgroups one load: they return before touching LDS.  No allocation, no host read: the call captures in a hipGraph.
-#include "gdm_common.h"
+#include "gdm_pose_fit.h"
 #include "gdm_raster_tile.h"
 
 namespace {
@@ -114,36 +114,13 @@ __global__ __launch_bounds__(kThreads) void depth_refine_accum_kernel(const VT* 
         const double x = (R[0] * dx + R[3] * dy) + R[6] * dz;
         const double y = (R[1] * dx + R[4] * dy) + R[7] * dz;
         const double z = (R[2] * dx + R[5] * dy) + R[8] * dz;
-        const double r = (nx * (x - ax) + ny * (y - ay)) + nz * (z - az);
-        const double ar = fabs(r);
-        const double wt = (huber <= 0.0 || ar <= huber) ? 1.0 : huber / ar;
-        const double J[6] = {y * nz - z * ny, z * nx - x * nz, x * ny - y * nx, nx, ny, nz};
-        int e = 0;
-#pragma unroll
-        for (int p = 0; p < 6; ++p) {
-            const double wj = wt * J[p];
-#pragma unroll
-            for (int q = p; q < 6; ++q) acc[e++] += wj * J[q];
-            acc[21 + p] += wj * r;
-        }
-        acc[27] += wt;
-        acc[28] += wt * ((x * x + y * y) + z * z);
-        acc[29] += ar;
+        acc_plane_pair(acc, x, y, z, nx, ny, nz, ax, ay, az, huber);
         cnt += 1;
     }
-    // fixed order: butterfly in each wave, then waves 0..3 (block_sum of gdm_pose_robust.hip)
-#pragma unroll
-    for (int a = 0; a < kSums; ++a) {
-        double s = acc[a];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        acc[a] = s;
-    }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if (lane == 0) {
-        for (int a = 0; a < kSums; ++a) red[threadIdx.x >> 6][a] = acc[a];
-        cred[threadIdx.x >> 6] = cnt;
-    }
-    __syncthreads();
+    // fixed order: butterfly in each wave (wave_sums), then waves 0..3 as block_sum adds them
+    cnt = wave_sum(cnt);
+    if (lane == 0) cred[threadIdx.x >> 6] = cnt;                           // visible after wave_sums' barrier
+    wave_sums<kSums>(acc, red);
     if (threadIdx.x < kRow) {
         const int tiles = ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile);
         double* row = partial + (((long)i * C + c) * tiles + blockIdx.x) * kRow;

@@ -24,14 +24,25 @@ from . import _lib, ops, pixel_rule
 from ._lib import call
 
 
+def _scene_args(cld_rgb_nrm):
+    """The (pointer, batch stride, point stride, channel stride) of the xyz rows of cld_rgb_nrm f32[B,9,N]."""
+    cld = ops._dev(cld_rgb_nrm, torch.float32, "cld_rgb_nrm")
+    return cld, cld.stride(0), 1, cld.shape[2]
+
+
+def _pose_outputs(B, device):
+    """The outputs every fit writes: RT f32[B,3,4] and valid u8[B], uninitialised."""
+    return torch.empty((B, 3, 4), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.uint8, device=device)
+
+
 def kabsch_stats(res, cld_rgb_nrm, model_xyz):
     """res: matching.match_frames output; cld_rgb_nrm f32[B,9,N] (rows 0-2 = xyz); model_xyz f32[M,3] -> f64[B,16]."""
     mask, best_idx = res["mask"], res["best_idx"]
     B, N = mask.shape
-    cld = ops._dev(cld_rgb_nrm, torch.float32, "cld_rgb_nrm")
+    scene = _scene_args(cld_rgb_nrm)
     model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
     out = torch.empty((B, 16), dtype=torch.float64, device=mask.device)
-    call("gdm_kabsch_stats_hip", cld, cld.stride(0), 1, N, model_xyz, best_idx, mask, B, N, model_xyz.shape[0], out)
+    call("gdm_kabsch_stats_hip", *scene, model_xyz, best_idx, mask, B, N, model_xyz.shape[0], out)
     return out
 
 
@@ -68,8 +79,7 @@ def solve_poses(res, cld_rgb_nrm, model_xyz, min_points=5, method="kabsch", rans
         return solve_poses_weighted(res, cld_rgb_nrm, model_xyz, w, res["soft_xyz"] if targets == "soft" else None, min_points)
     st = kabsch_stats(res, cld_rgb_nrm, model_xyz)
     B = st.shape[0]
-    RT = torch.empty((B, 3, 4), dtype=torch.float32, device=st.device)
-    valid = torch.empty((B,), dtype=torch.uint8, device=st.device)
+    RT, valid = _pose_outputs(B, st.device)
     call("gdm_kabsch_solve_hip", st, B, int(min_points), RT, valid)
     return RT, valid.bool()
 
@@ -80,7 +90,7 @@ def kabsch_stats_weighted(res, cld_rgb_nrm, model_xyz, weight, target=None):
     weight > 0; the others are skipped)."""
     mask, best_idx = res["mask"], res["best_idx"]
     B, N = mask.shape
-    cld = ops._dev(cld_rgb_nrm, torch.float32, "cld_rgb_nrm")
+    scene = _scene_args(cld_rgb_nrm)
     model_xyz = ops._dev(model_xyz, torch.float32, "model_xyz")
     weight = ops._dev(weight, torch.float32, "weight")
     if tuple(weight.shape) != (B, N):
@@ -91,8 +101,7 @@ def kabsch_stats_weighted(res, cld_rgb_nrm, model_xyz, weight, target=None):
             raise ValueError("kabsch_stats_weighted: target is %s, expected %s" % (tuple(target.shape), (B, N, 3)))
     out = torch.empty((B, 16), dtype=torch.float64, device=mask.device)
     count = torch.empty((B,), dtype=torch.int32, device=mask.device)
-    call("gdm_kabsch_stats_w_hip", cld, cld.stride(0), 1, N, model_xyz, best_idx, target, weight, mask, B, N, model_xyz.shape[0], out,
-         count)
+    call("gdm_kabsch_stats_w_hip", *scene, model_xyz, best_idx, target, weight, mask, B, N, model_xyz.shape[0], out, count)
     return out, count
 
 
@@ -101,8 +110,7 @@ def solve_poses_weighted(res, cld_rgb_nrm, model_xyz, weight, target=None, min_p
     and sum w > 0, else the sentinel pose.  -> RT f32[B,3,4], valid bool[B].  Two launches, no host synchronisation."""
     st, count = kabsch_stats_weighted(res, cld_rgb_nrm, model_xyz, weight, target)
     B = st.shape[0]
-    RT = torch.empty((B, 3, 4), dtype=torch.float32, device=st.device)
-    valid = torch.empty((B,), dtype=torch.uint8, device=st.device)
+    RT, valid = _pose_outputs(B, st.device)
     call("gdm_kabsch_solve_w_hip", st, count, B, int(min_points), RT, valid)
     return RT, valid.bool()
 
@@ -149,12 +157,6 @@ def ransac_sample_indices(counts, H, seed=0):
     return idx
 
 
-def _scene_args(cld_rgb_nrm):
-    """The (pointer, batch stride, point stride, channel stride) of the xyz rows of cld_rgb_nrm f32[B,9,N]."""
-    cld = ops._dev(cld_rgb_nrm, torch.float32, "cld_rgb_nrm")
-    return cld, cld.stride(0), 1, cld.shape[2]
-
-
 def ransac_poses(res, cld_rgb_nrm, model_xyz, iters=20, inlier_dist=0.015, fix_percent=0.7, seed=0, min_points=5):
     """Batched best_fit_transform_with_RANSAC (pvn3d_eval_utils_kpls.py:79-124; include/gdm.h gdm_ransac_pose_hip) over the same
     correspondences as solve_poses.  -> RT f32[B,3,4], valid bool[B], counts i32[B,iters] (inliers of every hypothesis), winner
@@ -170,8 +172,7 @@ def ransac_poses(res, cld_rgb_nrm, model_xyz, iters=20, inlier_dist=0.015, fix_p
     L = _lib.lib()
     nbytes = int(L.gdm_ransac_workspace_bytes(B, N, H))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
-    RT = torch.empty((B, 3, 4), dtype=torch.float32, device=mask.device)
-    valid = torch.empty((B,), dtype=torch.uint8, device=mask.device)
+    RT, valid = _pose_outputs(B, mask.device)
     counts = torch.empty((B, H), dtype=torch.int32, device=mask.device)
     winner = torch.empty((B,), dtype=torch.int32, device=mask.device)
     call("gdm_ransac_pose_hip", cld, sb, ps, cs, model_xyz, best_idx, mask, st, B, N, model_xyz.shape[0], H, float(inlier_dist),
@@ -207,7 +208,8 @@ def consensus_poses(res, cld_rgb_nrm, model_xyz, tau=0.005, seeds=8, inlier_dist
     if nbytes == 0:
         raise ValueError("consensus_poses: B=%d N=%d seeds=%d is beyond the entry's limits (include/gdm.h)" % (B, N, S))
     ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
-    out = dict(RT=torch.empty((B, 3, 4), dtype=torch.float32, device=dev), valid=torch.empty((B,), dtype=torch.uint8, device=dev),
+    RT, valid = _pose_outputs(B, dev)
+    out = dict(RT=RT, valid=valid,
                score=torch.empty((B, N), dtype=torch.int32, device=dev), degree=torch.empty((B, N), dtype=torch.int32, device=dev),
                seed_idx=torch.empty((B, S), dtype=torch.int32, device=dev),
                hyp_RT=torch.empty((B, S, 3, 4), dtype=torch.float32, device=dev),
