@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void kabsch_stats_w_kernel(const float* __rest
     for (int i = threadIdx.x; i < N; i += 256) {
         if (!mask[(long)b * N + i]) continue;
         const float wf = weight[(long)b * N + i];
-        if (!(wf > 0.f) || !(wf <= 3.402823466e38f)) continue;          // NaN, inf, zero and negative weights are skipped
+        if (!weight_usable(wf)) continue;                               // NaN, inf, zero and negative weights are skipped
         double ax, ay, az;
         if (target) {
             const float* t = target + ((long)b * N + i) * 3;

@@ -45,6 +45,10 @@ __device__ __forceinline__ void acc_pair_w(double* acc, double w, double ax, dou
     acc[13] += wz * bx; acc[14] += wz * by; acc[15] += wz * bz;
 }
 
+// The weights a weighted fit takes: finite and > 0.  NaN, infinite, zero and negative weights are skipped, here and in the backward of
+// the pose loss, which must skip exactly the points the statistics skipped.
+__device__ __forceinline__ bool weight_usable(float wf) { return (wf > 0.f) && (wf <= 3.402823466e38f); }
+
 // The unweighted pair: 1.0 * a is a exactly and nothing is contracted (-ffp-contract=off), so this is the plain sum.
 __device__ __forceinline__ void acc_pair(double* acc, double ax, double ay, double az, double bx, double by, double bz)
 {

@@ -32,6 +32,11 @@ class GeoMatch(nn.Module):
     soft_beta = 0.005
     soft_xyz_weight = 0.0
     soft_nll_weight = 0.0
+    # The pose-fit loss (loss.PoseFitLoss): opt-in likewise; with the weight 0 nothing of it runs.  Its targets are the
+    # soft vertices at soft_gamma, its error is over the first pose_loss_points model points, pose_loss_weights = "uniform" | "prob".
+    pose_loss_weight = 0.0
+    pose_loss_points = 256
+    pose_loss_weights = "uniform"
 
     def __init__(self, cfg, cls_id, model_points=None, cache_mesh_in_eval=False):
         super().__init__()
@@ -69,14 +74,20 @@ class GeoMatch(nn.Module):
         restated as the reference writes it).  settings.USE_FUSED_MATCH_LOSS = False: same batch formulation with the similarity
         materialised by one GEMM (the form the fused kernels are tested against, besides oracle/loss_ref.py and the goldens).
         With soft_xyz_weight or soft_nll_weight set, the two soft-assignment losses of the same rows are added with those weights
-        (loss.soft_assign_terms); parts=True returns (match_loss, soft_xyz_loss, soft_nll_loss) instead of their weighted sum."""
+        (loss.soft_assign_terms); parts=True returns (match_loss, soft_xyz_loss, soft_nll_loss) instead of their weighted sum.
+        With pose_loss_weight set the pose-fit loss of the same soft assignment is added too (a fourth part); it needs x["RT"] and a
+        model that is not symmetric."""
         from . import ops, settings
         from .loss import soft_assign_terms
-        soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0
+        pose_on = self.pose_loss_weight != 0
+        soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0 or pose_on
 
-        def result(match_loss, lx=None, ln=None):
+        def result(match_loss, lx=None, ln=None, lp=None):
             if not soft_on:
                 return (match_loss, None, None) if parts else match_loss
+            if pose_on:                  # the pose-fit loss rides as a fourth part
+                return (match_loss, lx, ln, lp) if parts else (match_loss + self.soft_xyz_weight * lx + self.soft_nll_weight * ln
+                                                               + self.pose_loss_weight * lp)
             return (match_loss, lx, ln) if parts else match_loss + self.soft_xyz_weight * lx + self.soft_nll_weight * ln
         if not rgbd_feature.is_cuda:
             raise RuntimeError("GeoMatch training matching loss runs on the GPU (HIP kernels); there is no CPU fallback")
@@ -98,7 +109,7 @@ class GeoMatch(nn.Module):
             bi, pi = torch.nonzero(sel, as_tuple=True)             # row-major: item, then point order
             if bi.numel() == 0:
                 zero = torch.zeros((), device=mesh.device)
-                return result(zero, zero, zero)
+                return result(zero, zero, zero, zero)
         rows = F.normalize(rgbd_feature.transpose(1, 2)[bi, pi], p=2, dim=1)      # [R,128]
         match_all = x["match_idx"].long()
         if static_rows:
@@ -134,19 +145,20 @@ class GeoMatch(nn.Module):
             else:
                 lrow = ops.circle_rows(sim, c1, bi, self.model_emb.xyz.contiguous(), x["visible_flag"], self.positive_r, 16.0, 0.2)
         lx = ln = None
+        lp = ()
         if soft_on:
             if mesh_rows is None:
                 mesh_rows = F.normalize(mesh, p=2, dim=0).t().contiguous()
-            lx, ln = soft_assign_terms(self, rows, mesh_rows, self.model_emb.xyz.contiguous(), c1, c2, bi, pi, counts, x,
-                                       static_shape=(B, N) if static_rows else None,
-                                       row_weight=sel.reshape(-1) if static_rows else None)
+            lx, ln, *lp = soft_assign_terms(self, rows, mesh_rows, self.model_emb.xyz.contiguous(), c1, c2, bi, pi, counts, x,
+                                            static_shape=(B, N) if static_rows else None,
+                                            row_weight=sel.reshape(-1) if static_rows else None)
         if static_rows:
             per_item = (lrow.view(B, N) * sel.to(lrow.dtype)).sum(dim=1) / counts.clamp(min=1).to(torch.float32)
             ok = item_ok.to(torch.float32)
-            return result((per_item * ok).sum() / ok.sum().clamp(min=1.0), lx, ln)
+            return result((per_item * ok).sum() / ok.sum().clamp(min=1.0), lx, ln, *lp)
         per_item = torch.zeros(B, dtype=torch.float32, device=mesh.device).index_add_(0, bi, lrow)
         per_item = per_item[item_ok] / counts[item_ok].to(torch.float32)
-        return result(per_item.mean(), lx, ln)
+        return result(per_item.mean(), lx, ln, *lp)
 
     # ------------------------------------------------------------------ forward (geoMatch.py:159-200)
     def mesh_features(self):
@@ -237,19 +249,24 @@ class GeoMatch(nn.Module):
         mesh_features = mesh_features.unsqueeze(0)
 
         if self.training:
-            soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0
+            pose_on = self.pose_loss_weight != 0
+            soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0 or pose_on
             if soft_on:
-                match_loss, soft_xyz_loss, soft_nll_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs, parts=True)
+                match_loss, soft_xyz_loss, soft_nll_loss, *pose_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs,
+                                                                                                     parts=True)
             else:
                 match_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs)
             seg_loss = self.seg_loss_func(seg_features, inputs["labels"].long())
             end_points["loss"] = self.awl(seg_loss, match_loss)
             end_points["seg_loss"] = seg_loss
             end_points["match_loss"] = match_loss
-            if soft_on:
+            if self.soft_xyz_weight != 0 or self.soft_nll_weight != 0:
                 end_points["loss"] = end_points["loss"] + self.soft_xyz_weight * soft_xyz_loss + self.soft_nll_weight * soft_nll_loss
                 end_points["soft_xyz_loss"] = soft_xyz_loss
                 end_points["soft_nll_loss"] = soft_nll_loss
+            if pose_on:
+                end_points["loss"] = end_points["loss"] + self.pose_loss_weight * pose_loss[0]
+                end_points["pose_loss"] = pose_loss[0]
 
         end_points["seg"] = seg_features
         if mesh_rows is not None:

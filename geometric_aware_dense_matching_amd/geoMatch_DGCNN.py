@@ -21,6 +21,9 @@ class GeoMatch(nn.Module):
     soft_beta = 0.005                # plain attributes; with both weights 0 nothing of them runs
     soft_xyz_weight = 0.0
     soft_nll_weight = 0.0
+    pose_loss_weight = 0.0           # the pose-fit loss (loss.PoseFitLoss), as in geoMatch.GeoMatch: opt-in, off at 0
+    pose_loss_points = 256
+    pose_loss_weights = "uniform"
 
     def __init__(self, cfg, cls_id, model_points=None):
         super().__init__()
@@ -46,13 +49,17 @@ class GeoMatch(nn.Module):
             pdist(g, v) < positive_r / 1000 * z_i(v), z_i(v) = depth of v posed by the item's RT (:62-67): the radius depends on the
             item AND the vertex, so the positive tables are built per item (ops.circle_nbr_items, one launch for the batch) and the
             fused kernels index them by (item, g) -- ops.circle_match(..., pad="e0").
-        soft_xyz_weight / soft_nll_weight / parts: as in geoMatch.GeoMatch.pointwise_feature_matching."""
+        soft_xyz_weight / soft_nll_weight / pose_loss_weight / parts: as in geoMatch.GeoMatch.pointwise_feature_matching."""
         from .loss import soft_assign_terms
-        soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0
+        pose_on = self.pose_loss_weight != 0
+        soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0 or pose_on
 
-        def result(match_loss, lx=None, ln=None):
+        def result(match_loss, lx=None, ln=None, lp=None):
             if not soft_on:
                 return (match_loss, None, None) if parts else match_loss
+            if pose_on:                  # the pose-fit loss rides as a fourth part
+                return (match_loss, lx, ln, lp) if parts else (match_loss + self.soft_xyz_weight * lx + self.soft_nll_weight * ln
+                                                               + self.pose_loss_weight * lp)
             return (match_loss, lx, ln) if parts else match_loss + self.soft_xyz_weight * lx + self.soft_nll_weight * ln
         if not rgbd_feature.is_cuda:
             raise RuntimeError("GeoMatch (DGCNN) training matching loss runs on the GPU (HIP kernels); there is no CPU fallback")
@@ -66,7 +73,7 @@ class GeoMatch(nn.Module):
         bi, pi = torch.nonzero(sel, as_tuple=True)                 # row-major: item, then point order
         if bi.numel() == 0:
             zero = torch.zeros((), device=mesh.device)
-            return result(zero, zero, zero)
+            return result(zero, zero, zero, zero)
         rows = F.normalize(rgbd_feature.transpose(1, 2)[bi, pi], p=2, dim=1)          # [R,128] (normalising a row commutes with selecting it)
         mesh_rows = F.normalize(mesh, p=2, dim=0).t().contiguous()                   # [M,128]; the padding column stays e0 under the normalisation
         g = x["match_idx"].long()[bi, pi]
@@ -80,8 +87,8 @@ class GeoMatch(nn.Module):
         per_item = per_item[item_ok] / counts[item_ok].to(torch.float32)
         if not soft_on:
             return result(per_item.mean())
-        lx, ln = soft_assign_terms(self, rows, mesh_rows, mesh_xyz, g, None, bi, pi, counts, x)
-        return result(per_item.mean(), lx, ln)
+        lx, ln, *lp = soft_assign_terms(self, rows, mesh_rows, mesh_xyz, g, None, bi, pi, counts, x)
+        return result(per_item.mean(), lx, ln, *lp)
 
     def forward(self, inputs, end_points=None, fused=False, defer_seg=False):
         """fused: both trunks on the fused inference path (dgcnn._DgcnnTrunk._embed_fused; eval only; raises in training mode).  In
@@ -107,19 +114,24 @@ class GeoMatch(nn.Module):
         rgbd_emb = rgbd_emb + rgbd_normalized
         seg_features = self.seg_layer(rgbd_emb)
         if self.training:
-            soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0
+            pose_on = self.pose_loss_weight != 0
+            soft_on = self.soft_xyz_weight != 0 or self.soft_nll_weight != 0 or pose_on
             if soft_on:
-                match_loss, soft_xyz_loss, soft_nll_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs, parts=True)
+                match_loss, soft_xyz_loss, soft_nll_loss, *pose_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs,
+                                                                                                     parts=True)
             else:
                 match_loss = self.pointwise_feature_matching(rgbd_features, mesh_features, inputs)
             seg_loss = self.seg_loss_func(seg_features, inputs["labels"].long())
             end_points["loss"] = self.awl(seg_loss, match_loss)
             end_points["seg_loss"] = seg_loss
             end_points["match_loss"] = match_loss
-            if soft_on:
+            if self.soft_xyz_weight != 0 or self.soft_nll_weight != 0:
                 end_points["loss"] = end_points["loss"] + self.soft_xyz_weight * soft_xyz_loss + self.soft_nll_weight * soft_nll_loss
                 end_points["soft_xyz_loss"] = soft_xyz_loss
                 end_points["soft_nll_loss"] = soft_nll_loss
+            if pose_on:
+                end_points["loss"] = end_points["loss"] + self.pose_loss_weight * pose_loss[0]
+                end_points["pose_loss"] = pose_loss[0]
         end_points["seg"] = seg_features
         end_points["mesh"] = mesh_features
         end_points["rgbd"] = rgbd_features

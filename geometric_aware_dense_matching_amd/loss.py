@@ -105,13 +105,19 @@ class SoftAssignLoss(nn.Module):
         return soft_coord_reference(rows, mesh_rows, xyz, self.gamma)
 
     def forward(self, rows, mesh_rows, xyz, g, item, counts, target=None, c2=None, row_weight=None, terms=("xyz", "nll"),
-                static_shape=None):
+                static_shape=None, pose=None):
         """rows [R,D] / mesh_rows [M,D] unit rows, xyz [M,3], g int[R] (M = none), item int[R] in [0, B), counts int[B] = selected
         rows per item, target [R,3] (default xyz[g]), c2 int[R] (symmetric objects), row_weight [R] (1 = selected, 0 = not: the
         static all-rows form; default all selected), static_shape = (B, N) when the rows are all B*N points in order (the per-item
-        sums are then plain row sums, no index_add).  -> (coordinate loss, likelihood loss); a term not in `terms` is None."""
+        sums are then plain row sums, no index_add).  -> (coordinate loss, likelihood loss); a term not in `terms` is None.
+        "pose" in terms adds the pose-fit loss of the same assignment (one soft_coord_match for all three) as a third value:
+        pose = dict(fn=PoseFitLoss, scene=cld_rgb_nrm [B,C,N] or [B,N,3], RT=[B,3,4], point=int[R] the point index of every row,
+        shape=(B, N)); the soft vertices are the targets, scattered into [B,N] (the static form is a view)."""
         M = mesh_rows.shape[0]
         symmetric = c2 is not None
+        if symmetric and "pose" in terms:
+            raise ValueError("SoftAssignLoss: the pose-fit term is not defined for symmetric objects (the expected vertex of two valid "
+                             "vertices is neither of them); pose.kabsch_pose_loss takes symmetry transforms for hard targets")
         if symmetric and "xyz" in terms:
             raise ValueError("SoftAssignLoss: the coordinate term is not defined for symmetric objects (the expected vertex of two "
                              "valid vertices is neither of them); use the likelihood term alone")
@@ -147,7 +153,58 @@ class SoftAssignLoss(nn.Module):
                 s2 = self.gamma * (rows * mesh_rows[c2.clamp(0, M - 1)]).sum(dim=1)
                 s1 = torch.logaddexp(s1, s2)
             out_nll = averaged(lse - s1)
-        return out_xyz, out_nll
+        if "pose" not in terms:
+            return out_xyz, out_nll
+        fn = pose["fn"]
+        wrow = fn.row_weight(w, self.gamma * (rows * mesh_rows[gc]).sum(dim=1) if fn.weights == "prob" else None, lse)
+        B, N = pose["shape"]
+        if static_shape is not None:
+            tgt, wgt = soft.view(B, N, 3), wrow.view(B, N)
+        else:
+            at = (item.long(), pose["point"].long())
+            tgt = torch.zeros((B, N, 3), dtype=soft.dtype, device=soft.device).index_put(at, soft)
+            wgt = torch.zeros((B, N), dtype=soft.dtype, device=soft.device).index_put(at, wrow)
+        return out_xyz, out_nll, fn(pose["scene"], tgt, wgt, pose["RT"], xyz)
+
+
+class PoseFitLoss(nn.Module):
+    """The pose-fit training loss (include/gdm.h THE POSE LOSS RULE): the mean, over the crops whose fit is well
+    conditioned (state 0; clamp(min=1) on their number, as SoftAssignLoss averages), of the mean distance of the first `points` model
+    points between the weighted Kabsch fit of the targets and the ground-truth pose -- what the evaluator's ADD measures, with a
+    gradient for the targets and the weights.  weights: what the caller's rows weigh (row_weight): "uniform" the 0/1 row selection,
+    "prob" the soft assignment's probability of the ground-truth vertex, exp(gamma s_{r,g_r} - lse_r), 0 for a row without one.
+    match = "kernel": pose.kabsch_pose_loss (HIP, float32 on the GPU only); "reference": pose.kabsch_pose_loss_reference (plain torch,
+    torch.linalg.svd and autograd; any dtype and device) -- an explicit choice, never a fall-back.  cond_min = 1e-3 is the default of a
+    definition, not a tuned value."""
+
+    def __init__(self, points=256, weights="uniform", cond_min=1e-3, match="kernel"):
+        super().__init__()
+        if weights not in ("uniform", "prob"):
+            raise ValueError("PoseFitLoss: weights must be 'uniform' or 'prob', got %r" % (weights,))
+        if match not in ("kernel", "reference"):
+            raise ValueError("PoseFitLoss: match must be 'kernel' or 'reference', got %r" % (match,))
+        if int(points) < 1:
+            raise ValueError("PoseFitLoss: points=%r must be >= 1" % (points,))
+        self.points, self.weights, self.cond_min, self.match = int(points), weights, float(cond_min), match
+
+    def row_weight(self, selected, logit_g=None, lse=None):
+        """The fit weight of every row: selected (0/1, 0 for a row without a ground-truth vertex), times exp(logit_g - lse) for "prob"."""
+        if self.weights == "uniform":
+            return selected
+        return torch.exp(logit_g - lse) * selected
+
+    def per_crop(self, scene, target, weight, RT_gt, model_xyz, sym=None, mask=None, min_points=5):
+        """-> (loss [B], RT f32[B,3,4], state u8[B], sym_idx i32[B]) of the first `points` rows of model_xyz [M,3]."""
+        from . import pose
+        pts = model_xyz[:self.points].detach().contiguous()
+        if self.match == "kernel":
+            return pose.kabsch_pose_loss(scene, target, weight, RT_gt.detach(), pts, sym, mask, min_points, self.cond_min)
+        return pose.kabsch_pose_loss_reference(scene, target, weight, RT_gt.detach(), pts, sym, mask, min_points, self.cond_min)
+
+    def forward(self, scene, target, weight, RT_gt, model_xyz, sym=None, mask=None, min_points=5):
+        loss_b, _, state, _ = self.per_crop(scene, target, weight, RT_gt, model_xyz, sym, mask, min_points)
+        ok = (state == 0).to(loss_b.dtype)
+        return (loss_b * ok).sum() / ok.sum().clamp(min=1.0)
 
 
 def soft_assign_terms(model, rows, mesh_rows, xyz, c1, c2, bi, pi, counts, x, static_shape=None, row_weight=None):
@@ -155,14 +212,34 @@ def soft_assign_terms(model, rows, mesh_rows, xyz, c1, c2, bi, pi, counts, x, st
     selected rows (bi, pi) of the batch x, controlled by the model attributes soft_gamma / soft_xyz_weight / soft_nll_weight; a term
     whose weight is 0 is not computed and comes back as a zero scalar.  Coordinate target: R_b^T (p_r - t_b), the scene point in
     model coordinates, when the batch carries RT; else the ground-truth vertex xyz[match_idx_r].  A model attribute soft_match =
-    "reference" selects the materialised plain-torch assignment (tests on the CPU / in fp64); the default is the HIP operator."""
+    "reference" selects the materialised plain-torch assignment (tests on the CPU / in fp64); the default is the HIP operator.
+    With the model attribute pose_loss_weight != 0 the pose-fit loss (PoseFitLoss on pose_loss_points model points with pose_loss_weights
+    row weights; targets = the soft vertices at soft_gamma, from the same single soft_coord_match) is a third value: it needs the
+    batch's RT and a model that is not symmetric, and raises ValueError otherwise.  soft_match selects its reference as well."""
     terms = tuple(t for t, wt in (("xyz", model.soft_xyz_weight), ("nll", model.soft_nll_weight)) if wt != 0)
+    pose = None
+    if getattr(model, "pose_loss_weight", 0.0) != 0:
+        if "RT" not in x:
+            raise ValueError("pose_loss_weight != 0 needs the ground-truth pose x['RT'] in the batch")
+        if c2 is not None:
+            raise ValueError("pose_loss_weight != 0: the pose-fit loss is not defined for symmetric objects (an expectation over two "
+                             "valid vertices is neither); pose.kabsch_pose_loss takes symmetry transforms for hard targets")
+        terms += ("pose",)
+        fit = PoseFitLoss(getattr(model, "pose_loss_points", 256), getattr(model, "pose_loss_weights", "uniform"),
+                          match=getattr(model, "soft_match", "kernel"))
+        cld = x["cld_rgb_nrm"]
+        pose = dict(fn=fit, scene=cld.detach() if cld.dtype == rows.dtype else cld[:, :3, :].detach().to(rows.dtype), RT=x["RT"][:, :3, :].to(rows.dtype),
+                    point=pi, shape=static_shape if static_shape is not None else (counts.shape[0], cld.shape[2]))
     target = None
     if "xyz" in terms and "RT" in x:
         RT = x["RT"].to(rows.dtype)
         p = x["cld_rgb_nrm"][:, :3, :].transpose(1, 2)[bi, pi].to(rows.dtype)              # [R,3] scene points (m)
         target = torch.einsum("rj,rjk->rk", p - RT[bi, :, 3], RT[bi, :, :3])               # R^T (p - t) as a row vector
     fn = SoftAssignLoss(model.soft_gamma, model.soft_beta, match=getattr(model, "soft_match", "kernel"))
-    lx, ln = fn(rows, mesh_rows, xyz, c1, bi, counts, target=target, c2=c2, row_weight=row_weight, terms=terms, static_shape=static_shape)
     zero = torch.zeros((), dtype=rows.dtype, device=rows.device)
+    if pose is not None:
+        lx, ln, lp = fn(rows, mesh_rows, xyz, c1, bi, counts, target=target, c2=c2, row_weight=row_weight, terms=terms,
+                        static_shape=static_shape, pose=pose)
+        return (zero if lx is None else lx), (zero if ln is None else ln), lp
+    lx, ln = fn(rows, mesh_rows, xyz, c1, bi, counts, target=target, c2=c2, row_weight=row_weight, terms=terms, static_shape=static_shape)
     return (zero if lx is None else lx), (zero if ln is None else ln)

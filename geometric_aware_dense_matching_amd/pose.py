@@ -134,6 +134,212 @@ def kabsch_weighted_numpy(A, B, w):
     return np.concatenate([R, (cB - R @ cA)[:, None]], axis=1)
 
 
+# ---- the differentiable pose-fit loss (csrc/gdm_poseloss.hip; include/gdm.h THE POSE LOSS RULE) ------------------------
+POSE_LOSS = ops._header_enums("GDM_POSE_LOSS_")          # GDM_POSE_LOSS_MAX_S, GDM_POSE_LOSS_REC
+POSE_LOSS_STATE = {0: "fitted", 1: "too few usable points (or a ground-truth pose that is not finite)", 2: "ill-conditioned"}
+
+
+# Registered through torch.library (custom_op + register_autograd) as ops.soft_coord_match is, not as an autograd.Function subclass:
+# gdm::pose_loss_fwd is two launches and gdm::pose_loss_bwd one, on the current stream, with no host read and no allocation that
+# depends on data, so a hipGraph capture records them like any other operator.  `scene` is the tensor the strides address (rows 0-2 of
+# cld_rgb_nrm f32[B,C,N], or f32[B,N,3]); sb / ps / cs are the strides of _scene_args.  sym with S == 0 rows stands for "none".
+@torch.library.custom_op("gdm::pose_loss_fwd", mutates_args=(), device_types="cuda")
+def _pose_loss_fwd(scene: torch.Tensor, sb: int, ps: int, cs: int, target: torch.Tensor, weight: torch.Tensor, mask: torch.Tensor,
+                   RT_gt: torch.Tensor, model_pts: torch.Tensor, sym: torch.Tensor, min_points: int,
+                   cond_min: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    B, N = weight.shape
+    dev = weight.device
+    nbytes = call("gdm_pose_loss_record_bytes", B)
+    record = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    loss = torch.empty((B,), dtype=torch.float64, device=dev)
+    RT = torch.empty((B, 3, 4), dtype=torch.float32, device=dev)
+    state = torch.empty((B,), dtype=torch.uint8, device=dev)
+    sym_idx = torch.empty((B,), dtype=torch.int32, device=dev)
+    S = sym.shape[0]
+    call("gdm_pose_loss_fwd_hip", scene, sb, ps, cs, target, weight, mask, RT_gt, model_pts, sym if S else None, B, N, model_pts.shape[0],
+         max(S, 1), min_points, cond_min, record, nbytes, loss, RT, state, sym_idx)
+    return loss, RT, state, sym_idx, record
+
+
+@_pose_loss_fwd.register_fake
+def _(scene, sb, ps, cs, target, weight, mask, RT_gt, model_pts, sym, min_points, cond_min):
+    B = weight.shape[0]
+    return (weight.new_empty((B,), dtype=torch.float64), weight.new_empty((B, 3, 4)), weight.new_empty((B,), dtype=torch.uint8),
+            weight.new_empty((B,), dtype=torch.int32), weight.new_empty((B * (16 + POSE_LOSS["GDM_POSE_LOSS_REC"]) + (B + 1) // 2,),
+                                                                        dtype=torch.float64))
+
+
+@torch.library.custom_op("gdm::pose_loss_bwd", mutates_args=(), device_types="cuda")
+def _pose_loss_bwd(scene: torch.Tensor, sb: int, ps: int, cs: int, target: torch.Tensor, weight: torch.Tensor, mask: torch.Tensor,
+                   record: torch.Tensor, grad_loss: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    B, N = weight.shape
+    grad_target = torch.empty((B, N, 3), dtype=torch.float32, device=weight.device)
+    grad_weight = torch.empty((B, N), dtype=torch.float32, device=weight.device)
+    call("gdm_pose_loss_bwd_hip", scene, sb, ps, cs, target, weight, mask, record, record.numel() * 8, grad_loss, B, N, grad_target,
+         grad_weight)
+    return grad_target, grad_weight
+
+
+@_pose_loss_bwd.register_fake
+def _(scene, sb, ps, cs, target, weight, mask, record, grad_loss):
+    return weight.new_empty(tuple(weight.shape) + (3,)), weight.new_empty(tuple(weight.shape))
+
+
+def _pose_loss_setup(ctx, inputs, output):
+    scene, sb, ps, cs, target, weight, mask = inputs[:7]
+    ctx.save_for_backward(scene, target, weight, mask, output[4])
+    ctx.strides = (sb, ps, cs)
+    ctx.set_materialize_grads(False)
+
+
+def _pose_loss_backward(ctx, g_loss, *unused):
+    scene, target, weight, mask, record = ctx.saved_tensors
+    if g_loss is None:
+        return (None,) * 12
+    gt, gw = _pose_loss_bwd(scene, *ctx.strides, target, weight, mask, record, g_loss.to(torch.float64).contiguous())
+    return None, None, None, None, gt, gw, None, None, None, None, None, None
+
+
+_pose_loss_fwd.register_autograd(_pose_loss_backward, setup_context=_pose_loss_setup)
+
+
+def _pose_loss_scene(scene, B, N, who):
+    """The scene of the pose loss as [B,N,3]-addressable: rows 0-2 of f32[B,C>=3,N] (cld_rgb_nrm, no copy) or f32[B,N,3].  A [B,N,3]
+    tensor with N == 3 is read as points.  -> (tensor, batch stride, point stride, channel stride, is_rows)."""
+    if scene.dim() != 3 or scene.shape[0] != B:
+        raise ValueError("%s: the scene must be [B=%d,C>=3,N=%d] or [B,N,3], got %s" % (who, B, N, tuple(scene.shape)))
+    if tuple(scene.shape[1:]) == (N, 3):
+        return scene, N * 3, 3, 1, False
+    if scene.shape[1] >= 3 and scene.shape[2] == N:
+        return scene, scene.shape[1] * N, 1, N, True
+    raise ValueError("%s: the scene must be [B=%d,C>=3,N=%d] or [B,N,3], got %s" % (who, B, N, tuple(scene.shape)))
+
+
+def _pose_loss_args(who, scene, target, weight, RT_gt, model_pts, sym, mask):
+    """The shape checks the operator and its reference share.  -> B, N, K, S."""
+    if target.dim() != 3 or target.shape[2] != 3 or target.shape[0] < 1 or target.shape[1] < 1:
+        raise ValueError("%s: target must be [B,N,3], got %s" % (who, tuple(target.shape)))
+    B, N = target.shape[:2]
+    if tuple(weight.shape) != (B, N):
+        raise ValueError("%s: weight is %s, expected %s" % (who, tuple(weight.shape), (B, N)))
+    if tuple(RT_gt.shape) != (B, 3, 4):
+        raise ValueError("%s: RT_gt is %s, expected %s" % (who, tuple(RT_gt.shape), (B, 3, 4)))
+    if model_pts.dim() != 2 or model_pts.shape[1] != 3 or model_pts.shape[0] < 1:
+        raise ValueError("%s: model_pts must be [K,3] with K >= 1, got %s" % (who, tuple(model_pts.shape)))
+    S = 1
+    if sym is not None:
+        if sym.dim() != 3 or tuple(sym.shape[1:]) != (3, 4) or not 1 <= sym.shape[0] <= POSE_LOSS["GDM_POSE_LOSS_MAX_S"]:
+            raise ValueError("%s: sym must be [S,3,4] with 1 <= S <= %d, got %s" % (who, POSE_LOSS["GDM_POSE_LOSS_MAX_S"], tuple(sym.shape)))
+        S = sym.shape[0]
+    if mask is not None and tuple(mask.shape) != (B, N):
+        raise ValueError("%s: mask is %s, expected %s" % (who, tuple(mask.shape), (B, N)))
+    for name, t in (("the scene", scene), ("RT_gt", RT_gt), ("model_pts", model_pts), ("sym", sym)):
+        if t is not None and t.requires_grad:
+            raise ValueError("%s: a gradient with respect to %s is not offered (detach it); the loss is differentiable in target and "
+                             "weight" % (who, name))
+    return B, N, model_pts.shape[0], S
+
+
+def sym_transforms(syms, device=None, dtype=torch.float32):
+    """evaluation.symmetry_transformations' list of {"R": [3,3], "t": [3,1]} (call it with scale=0.001: metres) -> [S,3,4]."""
+    out = np.stack([np.concatenate([np.asarray(s["R"], np.float64).reshape(3, 3), np.asarray(s["t"], np.float64).reshape(3, 1)], axis=1)
+                    for s in syms])
+    return torch.as_tensor(out, dtype=dtype, device=device)
+
+
+def kabsch_pose_loss(cld_rgb_nrm_or_scene, target, weight, RT_gt, model_pts, sym=None, mask=None, min_points=5, cond_min=1e-3,
+                     loss_dtype=torch.float32):
+    """The differentiable pose-fit loss (include/gdm.h THE POSE LOSS RULE; csrc/gdm_poseloss.hip): per crop, the weighted Kabsch fit of
+    the scene points onto target f32[B,N,3] (model side, e.g. the soft vertices of ops.soft_coord_match) under weight f32[B,N], and
+    the mean distance of the K model points model_pts f32[K,3] between that pose and RT_gt f32[B,3,4] -- the minimum over the symmetry
+    transforms sym f32[S,3,4] (sym_transforms; None = the identity alone).  The scene is cld_rgb_nrm f32[B,C>=3,N] (rows 0-2, no copy)
+    or f32[B,N,3]; mask u8/bool[B,N] (None = every point).  Points with mask 0 or a weight that is NaN, infinite, zero or negative are
+    skipped.  -> loss [B] (loss_dtype; the kernels' own f64 rounded once), RT f32[B,3,4] (solve_poses_weighted's, bit for bit), state
+    u8[B] (POSE_LOSS_STATE; a crop that is not 0 has loss 0 and no gradient), sym_idx i32[B] (the winning transform, -1 when not
+    fitted).  loss is differentiable in target and weight (own kernels, no SVD); the rest is detached.  A gradient with respect to
+    the scene, RT_gt, model_pts or sym is not offered: a tensor that requires one raises.  Two launches forward and one backward, no
+    host synchronisation."""
+    who = "kabsch_pose_loss"
+    B, N, K, S = _pose_loss_args(who, cld_rgb_nrm_or_scene, target, weight, RT_gt, model_pts, sym, mask)
+    target = ops._dev(target, torch.float32, "target")
+    weight = ops._dev(weight, torch.float32, "weight")
+    scene, sb, ps, cs, _ = _pose_loss_scene(ops._dev(cld_rgb_nrm_or_scene, torch.float32, "scene"), B, N, who)
+    RT_gt = ops._dev(RT_gt, torch.float32, "RT_gt")
+    model_pts = ops._dev(model_pts, torch.float32, "model_pts")
+    sym = torch.empty((0, 3, 4), dtype=torch.float32, device=target.device) if sym is None else ops._dev(sym, torch.float32, "sym")
+    if mask is None:
+        mask = torch.ones((B, N), dtype=torch.uint8, device=target.device)
+    else:
+        mask = ops._dev(mask if mask.dtype == torch.uint8 else mask.to(torch.uint8), torch.uint8, "mask")
+    if not 0.0 <= float(cond_min) < 1.0:
+        raise ValueError("%s: cond_min=%r not in [0, 1)" % (who, cond_min))
+    loss, RT, state, sym_idx, _ = _pose_loss_fwd(scene, sb, ps, cs, target, weight, mask, RT_gt, model_pts, sym, int(min_points),
+                                                 float(cond_min))
+    return loss.to(loss_dtype), RT.detach(), state.detach(), sym_idx.detach()
+
+
+def kabsch_pose_loss_reference(cld_rgb_nrm_or_scene, target, weight, RT_gt, model_pts, sym=None, mask=None, min_points=5, cond_min=1e-3):
+    """THE POSE LOSS RULE in plain torch, any dtype (target's) and device: torch.linalg.svd with the reflection fix of
+    kabsch_weighted_numpy, and autograd supplies the gradient.  Same arguments, skip rule, states and outputs as kabsch_pose_loss
+    (loss in target's dtype).  What the kernels are held to; an explicit choice (loss.PoseFitLoss(match="reference")), never a
+    fall-back."""
+    who = "kabsch_pose_loss_reference"
+    B, N, K, S = _pose_loss_args(who, cld_rgb_nrm_or_scene, target, weight, RT_gt, model_pts, sym, mask)
+    dt, dev = target.dtype, target.device
+    scene, _, _, _, rows = _pose_loss_scene(cld_rgb_nrm_or_scene, B, N, who)
+    scene = (scene[:, :3, :].transpose(1, 2) if rows else scene).to(dt)
+    weight = weight.to(dt)
+    gt = RT_gt.to(dt)
+    X = model_pts.to(dt)
+    sym = torch.eye(3, 4, dtype=dt, device=dev)[None] if sym is None else sym.to(dt)
+    usable = torch.isfinite(weight) & (weight > 0)
+    if mask is not None:
+        usable = usable & (mask != 0)
+    losses, RTs = [], []
+    state = torch.zeros(B, dtype=torch.uint8, device=dev)
+    sym_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    sentinel = torch.as_tensor(SENTINEL_RT, dtype=torch.float32, device=dev)
+    for b in range(B):
+        u = usable[b]
+        w = weight[b][u]
+        W = w.sum()
+        if int(u.sum()) < int(min_points) or not float(W.detach()) > 0:
+            state[b] = 1
+            losses.append(torch.zeros((), dtype=dt, device=dev))
+            RTs.append(sentinel)
+            continue
+        A, Bp = target[b][u], scene[b][u]
+        cA = (w[:, None] * A).sum(0) / W
+        cB = (w[:, None] * Bp).sum(0) / W
+        H = (w[:, None] * (A - cA)).t() @ (Bp - cB)
+        U, sv, Vt = torch.linalg.svd(H)
+        sign = 1.0
+        if float(torch.linalg.det((Vt.t() @ U.t()).detach())) < 0:                  # the reflection fix: the last row of V^T negated
+            Vt = Vt * torch.tensor([1.0, 1.0, -1.0], dtype=dt, device=dev)[:, None]
+            sign = -1.0
+        R = Vt.t() @ U.t()
+        t = cB - R @ cA
+        RTs.append(torch.cat([R, t[:, None]], dim=1).detach().float())
+        s1, s2, s3 = (float(v) for v in sv.detach())
+        if not bool(torch.isfinite(gt[b]).all()):
+            state[b] = 1
+        elif not (s2 + sign * s3) > float(cond_min) * s1:                # the eigenvalues of sym(R H) are s1, s2, sign * s3
+            state[b] = 2
+        if int(state[b]) != 0:
+            losses.append(torch.zeros((), dtype=dt, device=dev))
+            continue
+        pred = X @ R.t() + t
+        best = None
+        for s in range(sym.shape[0]):
+            want = (X @ sym[s, :, :3].t() + sym[s, :, 3]) @ gt[b, :, :3].t() + gt[b, :, 3]
+            D = torch.linalg.norm(pred - want, dim=1).mean()
+            if best is None or float(D.detach()) < float(best.detach()):                 # the lowest s wins a tie
+                best = D
+                sym_idx[b] = s
+        losses.append(best)
+    return torch.stack(losses), torch.stack(RTs), state, sym_idx
+
+
 def _mix32(x):
     x = x ^ (x >> np.uint32(16))
     x = x * np.uint32(0x7feb352d)

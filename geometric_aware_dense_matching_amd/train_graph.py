@@ -36,8 +36,8 @@ def _bn_momenta(model):
 
 
 class GraphedTrainStep:
-    """step(batch) -> {"loss", "seg_loss", "match_loss"} (plus "soft_xyz_loss" / "soft_nll_loss" when the model's soft-assignment
-    losses are on; device scalars owned by the capture; read or clone before the next step).
+    """step(batch) -> {"loss", "seg_loss", "match_loss"} (plus "soft_xyz_loss" / "soft_nll_loss" / "pose_loss" when the model's soft-assignment
+    or pose-fit losses are on; device scalars owned by the capture; read or clone before the next step).
 
     model: the (unwrapped, single-process) training module; optimizer: its Adam.  The first call warms up `warmup` eager iterations
     on a side stream (MIOpen picks its algorithms, the allocator reaches steady state, Adam's state exists), then captures.  Those
@@ -70,7 +70,7 @@ class GraphedTrainStep:
         if self.gt_targets == "device":
             self.static_targets = {k: cu[k] for k in ("labels", "match_idx", "visible_flag")}
         self.optimizer.step()
-        keys = ("loss", "seg_loss", "match_loss") + tuple(k for k in ("soft_xyz_loss", "soft_nll_loss") if k in out)
+        keys = ("loss", "seg_loss", "match_loss") + tuple(k for k in ("soft_xyz_loss", "soft_nll_loss", "pose_loss") if k in out)
         return {k: torch.as_tensor(out[k], device=self.device).detach().float() for k in keys}
 
     def _load(self, batch):

@@ -171,6 +171,14 @@ def build_parser():
                    help="train: weight of the expected-vertex regression (smooth L1, metres) added to the loss; 0 = off")
     p.add_argument("--soft-nll-weight", dest="soft_nll_weight", type=float, default=0.0,
                    help="train: weight of the negative log-likelihood of the ground-truth vertex under the soft assignment; 0 = off")
+    p.add_argument("--pose-loss-weight", dest="pose_loss_weight", type=float, default=0.0,
+                   help="train: weight of the pose-fit loss (loss.PoseFitLoss: the ADD-style error of the weighted Kabsch fit of the soft "
+                        "vertices at --soft-gamma against the item's RT, differentiable through own kernels); 0 = off")
+    p.add_argument("--pose-loss-points", dest="pose_loss_points", type=int, default=256, metavar="K",
+                   help="train: the pose-fit loss measures the first K model points (a farthest-point subset by the model file's contract)")
+    p.add_argument("--pose-loss-weights", dest="pose_loss_weights", type=str, default="uniform", choices=["uniform", "prob"],
+                   help="train: fit weights of the pose-fit loss: 'uniform' = the selected rows, 'prob' = the soft assignment's probability "
+                        "of the ground-truth vertex")
     p.add_argument("--models-dir", dest="models_dir", type=str, default=None, metavar="DIR",
                    help="a BOP models directory: when the dataset has no obj_%%06d_fps.npy for an object and DIR/obj_%%06d.ply exists, "
                         "the model table is built from that mesh on the GPU (model_prep.build_model_points) instead of a synthetic one")
@@ -182,6 +190,10 @@ def _set_soft_losses(model, args):
     wx, wn = float(getattr(args, "soft_xyz_weight", 0.0)), float(getattr(args, "soft_nll_weight", 0.0))
     if wx != 0 or wn != 0:
         model.soft_gamma, model.soft_xyz_weight, model.soft_nll_weight = float(getattr(args, "soft_gamma", 16.0)), wx, wn
+    wp = float(getattr(args, "pose_loss_weight", 0.0))
+    if wp != 0:          # --pose-loss-weight / --pose-loss-points / --pose-loss-weights; its targets are the soft vertices at --soft-gamma
+        model.soft_gamma, model.pose_loss_weight = float(getattr(args, "soft_gamma", 16.0)), wp
+        model.pose_loss_points, model.pose_loss_weights = int(getattr(args, "pose_loss_points", 256)), getattr(args, "pose_loss_weights", "uniform")
     return model
 
 
@@ -359,12 +371,13 @@ class Trainer:
                     loss = out["loss"]
                     vals = torch.stack([loss.detach().float(), out["seg_loss"].detach().float(),
                                         torch.as_tensor(out["match_loss"], device=loss.device).detach().float()]
-                                       + [out[k].detach().float() for k in ("soft_xyz_loss", "soft_nll_loss") if k in out])
+                                       + [out[k].detach().float() for k in ("soft_xyz_loss", "soft_nll_loss", "pose_loss") if k in out])
                     sums = vals if sums is None else sums + vals
                     dev_hist.append(vals)
                     if (it + 1) % self.log_every == 0:
                         self._flush_history(dev_hist)            # the one host read of this log window; frees the per-iteration scalars
-                        soft = " soft_xyz: {:.6f} soft_nll: {:.4f}" if sums.numel() == 5 else ""     # the soft-assignment losses, when on
+                        soft = " soft_xyz: {:.6f} soft_nll: {:.4f}" if "soft_xyz_loss" in out else ""     # the soft-assignment losses, when on
+                        soft += " pose: {:.6f}" if "pose_loss" in out else ""                           # the pose-fit loss (metres), when on
                         if self.local_rank == 0 and self.replaced is not None:
                             rd = self._replaced_counter()
                             vals = torch.cat([sums / self.log_every, rd.to(sums.dtype)]).tolist()     # one read: sums and counter
@@ -398,7 +411,7 @@ class Trainer:
             return self.graphed_step.replaced
         return self.replaced
 
-    HISTORY_CAP = 100000          # `history` keeps the most recent iterations' (loss, seg, match[, soft_xyz, soft_nll]) tuples
+    HISTORY_CAP = 100000          # `history` keeps the most recent iterations' (loss, seg, match[, soft_xyz, soft_nll][, pose]) tuples
 
     def _flush_history(self, dev_hist):
         if dev_hist:

@@ -441,6 +441,50 @@ int gdm_kabsch_stats_w_hip(const float* scene_xyz, long scene_bstride, int pt_st
                            int M, double* out, int32_t* count, void* stream);
 int gdm_kabsch_solve_w_hip(const double* stats, const int32_t* count, int B, int min_points, float* RT, uint8_t* valid, void* stream);
 
+/* The differentiable pose-fit loss (opt-in, training; no counterpart in the reference): the mean model-point distance between the
+ * weighted fit of soft targets and the ground-truth pose, with its gradient with respect to the targets and the weights -- the
+ * ADD-style error the evaluator reports, seen by training.  Forward and backward are own kernels: no library SVD, no host read, a
+ * fixed number of launches (two forward, one backward), so the step captures in a hipGraph.
+ *
+ * THE POSE LOSS RULE, per crop b.  Inputs: scene points B_i (f32, the addressing of gdm_kabsch_stats_hip; they carry no gradient),
+ * targets A_i = target[b,i] (f32[B,N,3], model side), weights w_i = weight[b,i] (f32[B,N]), mask u8[B,N], the ground-truth pose
+ * (Rg | tg) = RT_gt[b] (f32[B,3,4]), K model points X_k = model_pts (f32[K,3], shared by the crops; the first K rows of the model file,
+ * a farthest-point subset by that file's contract) and S symmetry transforms (Rs | ts) = sym (f32[S,3,4], metres, shared; NULL = the
+ * identity alone, S = 1).
+ *   1. Statistics.  Exactly those of gdm_kabsch_stats_w_hip (that launch itself): the usable points (mask != 0 and a finite weight
+ *      > 0), the skipped ones and the order of the sums are its own.  W = sum w, cA, cB, S = sum w (A - cA)(B - cB)^T.
+ *   2. Fit.  The fp64 rotation R of the shared fragment (gdm_kabsch_fit.inc) before it is rounded, t = cB - R cA in fp64.  The f32 RT
+ *      output is the fragment's own: gdm_kabsch_solve_w_hip's bit for bit.
+ *   3. State, u8.  1 = too few: fewer than min_points usable points or W <= 0 (RT is the sentinel pose, as gdm_kabsch_solve_w_hip
+ *      writes it), or a ground-truth pose that is not finite (RT is still the fit).  2 = ill-conditioned: with l1 >= l2 >= l3 the
+ *      eigenvalues of P = (R S + (R S)^T) / 2, l2 + l3 <= cond_min l1 (the fit is not unique at l2 + l3 = 0: collinear points, or a
+ *      plane whose mirror image fits as well).  0 = fitted.  A crop whose state is not 0 has loss 0, sym_idx -1 and every gradient 0.
+ *   4. Loss.  e_sk = (R X_k + t) - (Rg (Rs X_k + ts) + tg) in fp64, D_s = (1/K) sum_k |e_sk| summed in one fixed order (lanes stride
+ *      k, one butterfly per wave, waves left to right), loss = min_s D_s, the lowest s on a tie; sym_idx = that s.
+ *   5. Pose gradient, over the winner only, e^ = e / |e| (0 where |e| = 0): G = dloss/dR = (1/K) sum_k e^_k X_k^T, g = dloss/dt =
+ *      (1/K) sum_k e^_k.
+ *   6. Fit adjoint.  G' = G - g cA^T, Z = G' R^T, Za = (Z - Z^T) / 2; the antisymmetric Omega with Omega P + P Omega = Za, i.e.
+ *      (tr(P) I - P) omega = axial(Za), whose eigenvalues l_i + l_j state 2 keeps away from 0; Gamma = dloss/dS = -2 R^T Omega,
+ *      dloss/dcA = -R^T g, dloss/dcB = g.
+ *   7. Per usable point: dloss/dA_i = w_i [Gamma (B_i - cB) - R^T g / W],
+ *      dloss/dw_i = (A_i - cA)^T Gamma (B_i - cB) - (A_i - cA) . R^T g / W + (B_i - cB) . g / W; both 0 for a skipped point; both
+ *      times grad_loss[b], rounded once to f32.  No point's gradient is a sum over other points: no atomics, and eager, repeated and
+ *      replayed runs give the same bits.
+ * gdm_pose_loss_fwd_hip -> loss f64[B], RT f32[B,3,4], state u8[B], sym_idx i32[B] and the record: device memory aligned to 8 bytes of
+ * at least gdm_pose_loss_record_bytes(B) bytes (the 16 statistics, GDM_POSE_LOSS_REC doubles and the usable-point count per crop), the
+ * only workspace; it is what the backward reads instead of refitting.  gdm_pose_loss_bwd_hip: the same scene, target, weight and mask,
+ * that record, grad_loss f64[B] -> grad_target f32[B,N,3], grad_weight f32[B,N], every element written.
+ * 1 <= S <= GDM_POSE_LOSS_MAX_S, 0 <= cond_min < 1, B <= 65535; cond_min = 1e-3 is the default of a definition, not a tuned value. */
+enum { GDM_POSE_LOSS_MAX_S = 64, GDM_POSE_LOSS_REC = 32 };
+size_t gdm_pose_loss_record_bytes(int B);
+int gdm_pose_loss_fwd_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* target,
+                          const float* weight, const uint8_t* mask, const float* RT_gt, const float* model_pts, const float* sym, int B,
+                          int N, int K, int S, int min_points, double cond_min, void* record, size_t record_bytes, double* loss,
+                          float* RT, uint8_t* state, int32_t* sym_idx, void* stream);
+int gdm_pose_loss_bwd_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const float* target,
+                          const float* weight, const uint8_t* mask, const void* record, size_t record_bytes, const double* grad_loss,
+                          int B, int N, float* grad_target, float* grad_weight, void* stream);
+
 /* Robust fit: the reference's RANSAC (utils/pvn3d_eval_utils_kpls.py:79-124 best_fit_transform_with_RANSAC, used next to
  * best_fit_transform by evaluator.py:21) for a whole batch, every hypothesis evaluated at once.  Same correspondences as
  * gdm_kabsch_stats_hip (same arguments), plus `stats` = its output for them.  H = max_iter hypotheses per crop:
