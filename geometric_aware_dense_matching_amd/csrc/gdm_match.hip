@@ -1025,6 +1025,206 @@ __global__ __launch_bounds__(256) void match_score_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// two-way matching: v2's panel kernel with the masked column arg-max of every crop taken from the same accumulators
+// ------------------------------------------------------------------------------------------
+// include/gdm.h THE TWO-WAY RULE.  The panel fill, the operand load, the product block, the row scan and the row butterfly are
+// match_panel_kernel's own (best_idx / best_sim are the hard path's bit for bit); like the soft kernel this one gives up v2's operand
+// prefetch.  The reverse direction, per 64-column step and per crop c that the wave's 32 rows touch (one, or two at a crop boundary;
+// more only when N < 32):
+//   1. in-lane: a scan of the lane's 16 registers (ascending rows, strict '>': the lowest row on ties) under the bits of the rows
+//      that are masked and belong to c;
+//   2. the two half-waves by one shuffle (rows interleave in fours, so the row decides ties);
+//   3. the 8 waves: a 64-bit unsigned atomic maximum of the key into the workgroup's column buffer in LDS, one slot of 256 keys per
+//      crop of the row block (the compiler folds this and the direct form of step 4 into one flat_atomic_umax_x2);
+//   4. the row blocks (and the crops past the TW_SLOTS a row block has slots for, which skip step 3): global_atomic_umax_x2 of the
+//      key into keys[crop][column], from the buffer after a barrier, 2 KiB contiguous per slot.
+// key = order-preserving image of the similarity << 32 | ~(row in the crop): an integer maximum picks the larger similarity, then the
+// lower row, whatever the arrival order; 0 (below every real key) means no candidate.  twoway_cols_kernel decodes.
+constexpr int TW_SLOTS = 2;                             // crops of one row block that merge in LDS: all of them when N >= 255
+constexpr int TWOWAY_LDS_BYTES = PANEL_BYTES + TW_SLOTS * PANEL_COLS * (int)sizeof(unsigned long long);
+
+__device__ __forceinline__ unsigned long long col_key(float v, int row)
+{
+    unsigned u = __float_as_uint(v + 0.f);              // -0 -> +0: the two compare equal and must share a key
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)u << 32) | (unsigned)~row;
+}
+
+// bit reg is set iff row acc_row(0, reg, 0) of the lane is masked (mbits) and lies in [lo, lo + n)
+__device__ __forceinline__ unsigned crop_rows(unsigned mbits, int lo, int n)
+{
+    unsigned b = 0;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) b |= (unsigned)(acc_row(0, reg, 0) - lo) < (unsigned)n ? 1u << reg : 0u;
+    return b & mbits;
+}
+
+// steps 1 to 3 (or 4) for one column of the lane: a = its 16 similarities, bits = the rows that count, rbase = the row in the crop
+// of the lane's register 0; the key goes to lds (the column's key in the workgroup's buffer) if in_lds, else to gkey directly
+__device__ __forceinline__ void col_reduce(const gdm_f32x16& a, unsigned bits, int rbase, bool ok, int h, bool in_lds,
+                                           unsigned long long* lds, unsigned long long* gkey)
+{
+    float bv = -INFINITY;
+    int row = -1;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) running_max(a[reg], rbase + acc_row(0, reg, 0), (bits >> reg) & 1u, bv, row);
+    const float ov = __shfl_xor(bv, 32, 64);
+    const int orow = __shfl_xor(row, 32, 64);
+    if (ov > bv || (ov == bv && (unsigned)orow < (unsigned)row)) {      // no candidate is row -1: the largest unsigned
+        bv = ov;
+        row = orow;
+    }
+    if (h == 0 && ok && row >= 0) {
+        const unsigned long long key = col_key(bv, row);
+        if (in_lds) atomicMax(lds, key);
+        else atomicMax(gkey, key);
+    }
+}
+
+template <int PREC>
+__global__ __launch_bounds__(V2_THREADS) void match_panel_twoway_kernel(const unsigned char* __restrict__ apk,
+                                                                         const unsigned char* __restrict__ bpk,
+                                                                         const uint8_t* __restrict__ mask,       // [R]
+                                                                         int R, int N, int M, int G,
+                                                                         float* __restrict__ pval,               // [panels, R]
+                                                                         int32_t* __restrict__ pidx,
+                                                                         unsigned long long* __restrict__ keys)  // [R / N, M]
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // TWOWAY_LDS_BYTES
+    unsigned long long* cbuf = reinterpret_cast<unsigned long long*>(smem + PANEL_BYTES);   // [TW_SLOTS][PANEL_COLS]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int lr = lane & 31;
+    const int h = lane >> 5;
+    const int g = blockIdx.x % G;
+    const int panel = blockIdx.x / G;
+    const int col0 = panel * PANEL_COLS;
+    const int ncols = min(PANEL_COLS, M - col0);
+
+    fill_panel(bpk, col0, M, tid);
+    static_assert(TW_SLOTS * PANEL_COLS == V2_THREADS, "one key of the column buffer per thread");
+    cbuf[tid] = 0ull;
+    __syncthreads();
+
+    const int nrb = (R + V2_ROWS - 1) / V2_ROWS;
+    for (int rb = g; rb < nrb; rb += G) {
+        gdm_u32x4 areg[16];
+        const int row0 = rb * V2_ROWS + wave * 32;
+        load_a_rows<PREC>(apk, row0 + lr, R, h, areg);
+
+        // the lane's 16 rows: which are real and masked; the crops the wave's rows touch, and the first crop of the row block
+        unsigned mbits = 0;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int grow = acc_row(row0, reg, h);
+            if (grow < R && mask[grow]) mbits |= 1u << reg;
+        }
+        const int lrow0 = row0 + 4 * h;                                    // the lane's register 0
+        const int cfirst = (rb * V2_ROWS) / N;
+        const int cb0 = row0 / N;
+        const int cb1 = row0 < R ? min(row0 + 31, R - 1) / N : cb0 - 1;     // a wave past the last row has no crop
+        const unsigned bits0 = crop_rows(mbits, cb0 * N - lrow0, N);
+
+        float best[16];
+        int bidx[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            best[i] = -INFINITY;
+            bidx[i] = 0;
+        }
+
+#pragma unroll 1
+        for (int cp = 0; cp < PANEL_COLS / 64; ++cp) {
+            gdm_f32x16 acc[2];
+            const int c0 = cp * 64 + lr, c1 = c0 + 32;
+            tile_product<PREC, 2>(0, c0, h, areg, acc);
+            const int gc0 = col0 + c0, gc1 = col0 + c1;
+            const bool ok0 = c0 < ncols, ok1 = c1 < ncols;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                running_max(acc[0][reg], gc0, ok0, best[reg], bidx[reg]);
+                running_max(acc[1][reg], gc1, ok1, best[reg], bidx[reg]);
+            }
+#pragma unroll 1
+            for (int c = cb0; c <= cb1; ++c) {
+                const int rbase = lrow0 - c * N;
+                const unsigned bits = c == cb0 ? bits0 : crop_rows(mbits, -rbase, N);
+                const bool in_lds = c - cfirst < TW_SLOTS;
+                unsigned long long* slot = cbuf + (in_lds ? c - cfirst : 0) * PANEL_COLS;
+                unsigned long long* gk = keys + (long)c * M + col0;
+                col_reduce(acc[0], bits, rbase, ok0, h, in_lds, slot + c0, gk + c0);
+                col_reduce(acc[1], bits, rbase, ok1, h, in_lds, slot + c1, gk + c1);
+            }
+        }
+
+        finalize_rows<true>(best, bidx, lane, h, row0, R, panel, pval, pidx);
+
+        // step 4: the row block's keys leave the buffer (one thread per key) and the buffer is empty again for the next row block
+        __syncthreads();
+        {
+            const int c = cfirst + tid / PANEL_COLS, col = tid % PANEL_COLS;
+            const unsigned long long key = cbuf[tid];
+            if (key != 0ull) {                                             // only columns < ncols of crops < R / N were ever written
+                atomicMax(keys + (long)c * M + col0 + col, key);
+                cbuf[tid] = 0ull;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// key -> (col_idx, col_sim); 0 -> (-1, -inf)
+__global__ __launch_bounds__(256) void twoway_cols_kernel(const unsigned long long* __restrict__ keys, long n, int32_t* __restrict__ col_idx,
+                                                          float* __restrict__ col_sim)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = keys[i];
+    const unsigned u = (unsigned)(key >> 32);
+    col_idx[i] = key ? (int32_t)~(unsigned)key : -1;
+    col_sim[i] = key ? __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u) : -INFINITY;
+}
+
+// include/gdm.h THE CYCLE RULE: one workgroup per crop, one pass over its points, an integer count
+__global__ __launch_bounds__(256) void match_cycle_kernel(const float* __restrict__ scene_xyz, long scene_bstride, int pt_stride, int ch_stride,
+                                                          const int32_t* __restrict__ best_idx, const int32_t* __restrict__ col_idx,
+                                                          const uint8_t* __restrict__ mask, int N, int M, float r2,
+                                                          uint8_t* __restrict__ pair_mask, int32_t* __restrict__ pair_count,
+                                                          float* __restrict__ cycle_d2)
+{
+    __shared__ int cred[4];
+    const int b = blockIdx.x;
+    const float* sp = scene_xyz + (long)b * scene_bstride;
+    int c = 0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        float d2 = INFINITY;
+        bool keep = false;
+        if (mask[(long)b * N + i]) {
+            const int j = best_idx[(long)b * N + i];
+            const int k = (j >= 0 && j < M) ? col_idx[(long)b * M + j] : -1;
+            if (k >= 0 && k < N) {
+                const float* pi = sp + (long)i * pt_stride;
+                const float* pk = sp + (long)k * pt_stride;
+                const float dx = __fsub_rn(pi[0], pk[0]);
+                const float dy = __fsub_rn(pi[ch_stride], pk[ch_stride]);
+                const float dz = __fsub_rn(pi[2L * ch_stride], pk[2L * ch_stride]);
+                d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                keep = d2 <= r2;                                           // false for a NaN
+            }
+        }
+        pair_mask[(long)b * N + i] = keep ? 1 : 0;
+        cycle_d2[(long)b * N + i] = d2;
+        c += keep ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) pair_count[b] = cred[0] + cred[1] + cred[2] + cred[3];
+}
+
 } // namespace
 
 extern "C" size_t gdm_match_rows_bytes(int rows)
@@ -1207,6 +1407,81 @@ extern "C" int gdm_match_score_hip(const float* conf, const uint8_t* mask, int B
     GDM_CHECK_ARG(B >= 1 && N >= 1, "gdm_match_score_hip: bad shape B=%d N=%d", B, N);
     hipLaunchKernelGGL(match_score_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, conf, mask, N, score);
     return gdm_launch_status("match_score_kernel");
+}
+
+extern "C" size_t gdm_match_twoway_partial_bytes(int B, int N, int M)
+{
+    if (B < 1 || N < 1 || M < 1) return 0;
+    return gdm_match_partial_bytes(B, N) + align256((size_t)B * M * sizeof(unsigned long long));
+}
+
+extern "C" int gdm_match_twoway_packed_hip(const void* scene_rows, const void* model_rows, const uint8_t* mask, int B, int N, int M,
+                                           int precision, int32_t* best_idx, float* best_sim, int32_t* col_idx, float* col_sim,
+                                           void* partial, size_t partial_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    GDM_CHECK_ARG(scene_rows && model_rows && mask && best_idx && best_sim && col_idx && col_sim && partial,
+                  "gdm_match_twoway_packed_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_match_twoway_packed_hip: bad shape B=%d N=%d M=%d", B, N, M);
+    GDM_CHECK_ARG((long)B * N < (1L << 22), "gdm_match_twoway_packed_hip: B*N too large");
+    GDM_CHECK_ARG(M <= GDM_MATCH_SOFT_MAX_M, "gdm_match_twoway_packed_hip: M=%d, the two-way kernel covers M <= %d", M, GDM_MATCH_SOFT_MAX_M);
+    GDM_CHECK_ARG(precision == GDM_MATCH_BF16X3 || precision == GDM_MATCH_F32, "gdm_match_twoway_packed_hip: precision=%d", precision);
+    GDM_CHECK_ARG(((uintptr_t)partial & 15) == 0, "gdm_match_twoway_packed_hip: partial must be 16-byte aligned");
+    GDM_CHECK_ARG((((uintptr_t)scene_rows | (uintptr_t)model_rows) & 15) == 0, "gdm_match_twoway_packed_hip: the packed rows must be 16-byte aligned");
+    const int R = B * N;
+    const size_t half = align256(64 * (size_t)R * sizeof(float));
+    const size_t nkeys = (size_t)B * M;
+    const size_t need = 2 * half + align256(nkeys * sizeof(unsigned long long));
+    if (partial_bytes < need) {
+        gdm_set_error("gdm_match_twoway_packed_hip: partial workspace %zu < %zu bytes", partial_bytes, need);
+        return GDM_ENOMEM;
+    }
+    float* pval = (float*)partial;
+    int32_t* pidx = (int32_t*)((unsigned char*)partial + half);
+    unsigned long long* keys = (unsigned long long*)((unsigned char*)partial + 2 * half);
+    const int panels = gdm_cdiv(M, PANEL_COLS);
+    const int nrb = gdm_cdiv(R, V2_ROWS);
+    int G = 512 / panels;                                       // as v2: one workgroup per CU, two rounds
+    if (G < 1) G = 1;
+    if (G > nrb) G = nrb;
+    if (G >= 8) G &= ~7;
+    const dim3 kgrid((unsigned)((nkeys + 255) / 256));
+    const hipError_t me = hipMemsetAsync(keys, 0, nkeys * sizeof(unsigned long long), stream);      // key 0 = no candidate
+    if (me != hipSuccess) {
+        gdm_set_error("gdm_match_twoway_packed_hip: hipMemsetAsync of the keys failed: %s", hipGetErrorString(me));
+        return (int)me;
+    }
+    int rc;
+    float* ov = panels == 1 ? best_sim : pval;
+    int32_t* oi = panels == 1 ? best_idx : pidx;
+    gdm_dispatch_int<2>(precision, [&](auto P) {
+        constexpr auto kernel = match_panel_twoway_kernel<decltype(P)::value>;
+        gdm_allow_lds<kernel>(TWOWAY_LDS_BYTES);
+        hipLaunchKernelGGL(kernel, dim3(panels * G), dim3(V2_THREADS), TWOWAY_LDS_BYTES, stream, (const unsigned char*)scene_rows,
+                           (const unsigned char*)model_rows, mask, R, N, M, G, ov, oi, keys);
+    });
+    rc = gdm_launch_status("match_panel_twoway_kernel");
+    if (rc) return rc;
+    if (panels > 1) {
+        hipLaunchKernelGGL(merge_splits_kernel, dim3(gdm_cdiv(R, 256)), dim3(256), 0, stream, pval, pidx, panels, R, best_sim, best_idx);
+        rc = gdm_launch_status("merge_splits_kernel");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(twoway_cols_kernel, kgrid, dim3(256), 0, stream, keys, (long)nkeys, col_idx, col_sim);
+    return gdm_launch_status("twoway_cols_kernel");
+}
+
+extern "C" int gdm_match_cycle_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const int32_t* best_idx,
+                                   const int32_t* col_idx, const uint8_t* mask, int B, int N, int M, float radius, uint8_t* pair_mask,
+                                   int32_t* pair_count, float* cycle_d2, void* stream)
+{
+    GDM_CHECK_ARG(scene_xyz && best_idx && col_idx && mask && pair_mask && pair_count && cycle_d2, "gdm_match_cycle_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_match_cycle_hip: bad shape B=%d N=%d M=%d", B, N, M);
+    GDM_CHECK_ARG(pt_stride >= 1 && ch_stride >= 1 && scene_bstride >= 0, "gdm_match_cycle_hip: bad scene strides");
+    GDM_CHECK_ARG(radius >= 0.f && radius < INFINITY, "gdm_match_cycle_hip: radius=%g must be finite and >= 0", (double)radius);   // a NaN fails
+    hipLaunchKernelGGL(match_cycle_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scene_xyz, scene_bstride, pt_stride, ch_stride,
+                       best_idx, col_idx, mask, N, M, radius * radius, pair_mask, pair_count, cycle_d2);
+    return gdm_launch_status("match_cycle_kernel");
 }
 
 extern "C" int gdm_match_hip(const float* scene, const float* model, int B, int Dd, int N, int M, int precision,

@@ -27,15 +27,28 @@ def _soft_args(soft, who):
     return float(soft["gamma"]), soft["model_xyz"]
 
 
-def match_frames(end_points, precision="bf16x3", return_sim=False, soft=None):
+def _no_soft_twoway(sa, twoway, who):
+    if twoway and sa is not None:
+        raise ValueError("%s: twoway and soft exclude each other (there is no soft two-way kernel)" % who)
+
+
+def match_frames(end_points, precision="bf16x3", return_sim=False, soft=None, twoway=False):
     """end_points: GeoMatch.forward output (seg [B,2,N], rgbd [B,128,N], mesh [1,128,M]).
     Returns dict(mask u8[B,N], count i32[B], best_idx i32[B,N], best_sim f32[B,N] [, sim f32[B,N,M]]).
     soft = dict(gamma=..., model_xyz=f32[M,3]) takes the soft kernel instead (ops.match_soft: the same best_idx / best_sim) and adds
-    lse f32[B,N], conf f32[B,N], soft_xyz f32[B,N,3]."""
+    lse f32[B,N], conf f32[B,N], soft_xyz f32[B,N,3].
+    twoway takes the two-way kernel instead (ops.match_twoway under the mask: the same best_idx / best_sim) and adds col_idx i32[B,M],
+    col_sim f32[B,M]: per vertex the masked point that matches it best (include/gdm.h THE TWO-WAY RULE)."""
     seg, rgbd, mesh = end_points["seg"], end_points["rgbd"], end_points["mesh"]
     sa = _soft_args(soft, "match_frames")
+    _no_soft_twoway(sa, twoway, "match_frames")
     mask, count = ops.seg_mask(seg)
     mesh = mesh[0] if mesh.dim() == 3 else mesh
+    if twoway:
+        if return_sim:
+            raise ValueError("match_frames: return_sim and twoway exclude each other (the two-way kernel writes no matrix)")
+        bi, bs, ci, cs = ops.match_twoway(rgbd, mesh, mask, _PREC[precision])
+        return dict(mask=mask, count=count, best_idx=bi, best_sim=bs, col_idx=ci, col_sim=cs)
     if sa is None:
         out = ops.match(rgbd, mesh, precision=_PREC[precision], return_sim=return_sim)
         res = dict(mask=mask, count=count, best_idx=out[0], best_sim=out[1])
@@ -48,23 +61,28 @@ def match_frames(end_points, precision="bf16x3", return_sim=False, soft=None):
     return dict(mask=mask, count=count, best_idx=bi, best_sim=bs, lse=lse, conf=conf, soft_xyz=sxyz)
 
 
-def match_tail(end_points, B, N, M, precision=ops.MATCH_BF16X3, soft=None):
+def match_tail(end_points, B, N, M, precision=ops.MATCH_BF16X3, soft=None, twoway=False):
     """The step's tail on packed rows (evaluator.py:78-93): seg mask, descriptor packs, N x M arg-max -> (mask, count, best_idx, best_sim).
     With settings.USE_SIDE_STREAMS the mask -- which the arg-max does not read -- is formed on a side stream beside the matching
     kernel, and the model's descriptor rows are taken from `end_points["mesh_rows"]` when GeoMatch.forward packed them inside its
     mesh fork (same kernels, same operands: same bits); the scene's rows likewise from `end_points["scene_rows"]` when the fused heads
     wrote them (bf16x3 only: the pack kernel's own code on the same values, same bytes).  soft = dict(gamma=..., model_xyz=...): the soft kernel in place of the
-    arg-max kernel, and (lse, conf, soft_xyz) appended to the result."""
+    arg-max kernel, and (lse, conf, soft_xyz) appended to the result.  twoway: the two-way kernel in its place, and (col_idx, col_sim)
+    appended; that kernel reads the mask, so the mask is formed in front of it on the same stream and its side-stream fork is not
+    taken."""
     from . import settings
     seg, rgbd, mesh = end_points["seg"], end_points["rgbd"], end_points["mesh"]
     sa = _soft_args(soft, "match_tail")
+    _no_soft_twoway(sa, twoway, "match_tail")
 
-    def run(srows, mrows):
+    def run(srows, mrows, mask=None):
+        if twoway:
+            return ops.match_twoway_packed(srows, mrows, mask, B, N, M, precision)
         if sa is None:
             return ops.match_packed(srows, mrows, B, N, M, precision)
         return ops.match_soft_packed(srows, mrows, sa[1], B, N, M, precision, sa[0])
 
-    forked = settings.USE_SIDE_STREAMS and seg.is_cuda and not torch.is_grad_enabled()
+    forked = settings.USE_SIDE_STREAMS and seg.is_cuda and not torch.is_grad_enabled() and not twoway
     mrows = end_points.get("mesh_rows") if precision == ops.MATCH_BF16X3 else None
     srows = end_points.get("scene_rows") if precision == ops.MATCH_BF16X3 else None
     if mrows is None and srows is None:
@@ -81,7 +99,7 @@ def match_tail(end_points, B, N, M, precision=ops.MATCH_BF16X3, soft=None):
         f.join(mask, count, seg)
     else:
         mask, count = ops.seg_mask(seg)
-        m = run(srows, mrows)
+        m = run(srows, mrows, mask)
     return (mask, count) + tuple(m)
 
 
@@ -106,6 +124,38 @@ def match_soft_numpy(scene, model, model_xyz, gamma):
     Z = e.sum(axis=1)
     lse = g * best_sim + np.log(Z)
     return dict(best_idx=best_idx, best_sim=best_sim, lse=lse, conf=1.0 / Z, soft_xyz=(e @ xyz) / Z[:, None])
+
+
+def match_twoway_numpy(scene, model, mask):
+    """THE TWO-WAY RULE of include/gdm.h restated in fp64 (numpy) for one crop.  scene f32[N,128] raw descriptors (one per row) and
+    model f32[128,M], normalised as in match_soft_numpy -- or scene = a similarity matrix [N,M] (of any float type, compared as it
+    is) and model = None; mask [N], nonzero = the point counts for the columns.  -> dict(best_idx i64[N], best_sim [N]: the row
+    arg-max over all columns for every row, first maximum on ties; col_idx i64[M], col_sim [M]: per column, from (-1, -inf), a masked
+    row takes over iff its similarity is greater -- so the first of equal maxima stays and a NaN never wins)."""
+    if model is None:
+        sim = np.asarray(scene)
+        sim = sim if sim.dtype.kind == "f" else sim.astype(np.float64)
+    else:
+        a = np.asarray(scene, dtype=np.float64)
+        b = np.asarray(model, dtype=np.float64)
+        a = a / np.maximum(np.linalg.norm(a, axis=1, keepdims=True), 1e-12)
+        b = b / np.maximum(np.linalg.norm(b, axis=0, keepdims=True), 1e-12)
+        sim = a @ b
+    N, M = sim.shape
+    keep = np.asarray(mask).reshape(N) != 0
+    best_idx = np.zeros(N, dtype=np.int64)
+    best_sim = np.full(N, -np.inf, dtype=sim.dtype)
+    for j in range(M):                                        # ascending columns, strict '>': the first maximum (running_max)
+        take = sim[:, j] > best_sim
+        best_idx[take] = j
+        best_sim[take] = sim[take, j]
+    col_idx = np.full(M, -1, dtype=np.int64)
+    col_sim = np.full(M, -np.inf, dtype=sim.dtype)
+    for i in np.flatnonzero(keep):                            # ascending rows, strict '>': the lowest row on ties
+        take = sim[i] > col_sim
+        col_idx[take] = i
+        col_sim[take] = sim[i, take]
+    return dict(best_idx=best_idx, best_sim=best_sim, col_idx=col_idx, col_sim=col_sim)
 
 
 def selected(res, b):

@@ -2430,6 +2430,59 @@ def match_score(conf, mask):
     return score
 
 
+def match_twoway_packed(scene_rows, model_rows, mask, B, N, M, precision=MATCH_BF16X3):
+    """match_packed plus the reverse direction under mask u8[B,N] (include/gdm.h THE TWO-WAY RULE): -> best_idx i32[B,N], best_sim
+    f32[B,N] (the bits of match_packed), col_idx i32[B,M] = per crop and vertex the masked point with the largest similarity (the
+    lowest on ties, -1 where there is none), col_sim f32[B,M] (-inf there).  No [N, M] tensor; M <= 16384, refused otherwise."""
+    L = _lib.lib()
+    mask = _dev(mask, torch.uint8, "mask")
+    if tuple(mask.shape) != (B, N):
+        raise ValueError("match_twoway_packed: mask is %s, expected (%d, %d)" % (tuple(mask.shape), B, N))
+    dev = scene_rows.device
+    part = _workspace(L.gdm_match_twoway_partial_bytes(B, N, M), dev)
+    best_idx = torch.empty((B, N), dtype=torch.int32, device=dev)
+    best_sim = torch.empty((B, N), dtype=torch.float32, device=dev)
+    col_idx = torch.empty((B, M), dtype=torch.int32, device=dev)
+    col_sim = torch.empty((B, M), dtype=torch.float32, device=dev)
+    call("gdm_match_twoway_packed_hip", scene_rows, model_rows, mask, B, N, M, precision, best_idx, best_sim, col_idx, col_sim, part,
+         part.numel())
+    return best_idx, best_sim, col_idx, col_sim
+
+
+def match_twoway(scene, model, mask, precision=MATCH_BF16X3):
+    """scene f32[B,128,N], model f32[128,M], mask u8[B,N] -> (best_idx, best_sim, col_idx, col_sim): both packs, then
+    match_twoway_packed."""
+    scene = _dev(scene, torch.float32, "scene")
+    model = _dev(model, torch.float32, "model")
+    if model.dim() == 3:
+        assert model.shape[0] == 1
+        model = model[0]
+    B, D, N = scene.shape
+    assert model.shape[0] == D
+    srows, mrows = match_pack2(scene, model, precision)
+    return match_twoway_packed(srows, mrows, mask, B, N, model.shape[1], precision)
+
+
+def match_cycle(cld_rgb_nrm, best_idx, col_idx, mask, radius):
+    """The cycle-consistency filter (include/gdm.h THE CYCLE RULE): cld_rgb_nrm f32[B,9,N] (rows 0-2 = xyz), best_idx i32[B,N], col_idx
+    i32[B,M], mask u8[B,N]; a masked point is kept iff the point its vertex picks back lies within `radius` of it (radius = 0: the
+    mutual best pairs).  -> pair_mask u8[B,N], pair_count i32[B], cycle_d2 f32[B,N] (+inf where no distance was formed)."""
+    cld = _dev(cld_rgb_nrm, torch.float32, "cld_rgb_nrm")
+    best_idx = _dev(best_idx, torch.int32, "best_idx")
+    col_idx = _dev(col_idx, torch.int32, "col_idx")
+    mask = _dev(mask, torch.uint8, "mask")
+    B, N = mask.shape
+    if cld.dim() != 3 or cld.shape[0] != B or cld.shape[1] < 3 or cld.shape[2] != N or best_idx.shape != mask.shape or col_idx.shape[0] != B:
+        raise ValueError("match_cycle: cld_rgb_nrm %s, best_idx %s, col_idx %s do not go with mask %s" %
+                         (tuple(cld.shape), tuple(best_idx.shape), tuple(col_idx.shape), (B, N)))
+    pair_mask = torch.empty((B, N), dtype=torch.uint8, device=mask.device)
+    pair_count = torch.empty((B,), dtype=torch.int32, device=mask.device)
+    cycle_d2 = torch.empty((B, N), dtype=torch.float32, device=mask.device)
+    call("gdm_match_cycle_hip", cld, cld.stride(0), 1, cld.shape[2], best_idx, col_idx, mask, B, N, col_idx.shape[1], float(radius),
+         pair_mask, pair_count, cycle_d2)
+    return pair_mask, pair_count, cycle_d2
+
+
 def seg_mask(seg):
     """seg f32[B,2,N] -> (mask u8[B,N] = argmax==1, count i32[B])."""
     seg = _dev(seg, torch.float32, "seg")

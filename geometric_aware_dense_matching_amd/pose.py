@@ -730,6 +730,63 @@ def icp_plane_numpy(scene, scene_nrm, model_xyz, model_nrm, RT0, mask=None, iter
     return out
 
 
+CYCLE_RADIUS = 0.005          # m: the default of the cycle filter's definition, not a tuned value
+
+
+def cycle_filter(res, cld_rgb_nrm, radius=CYCLE_RADIUS):
+    """The cycle-consistency pair filter (include/gdm.h THE CYCLE RULE) on a two-way match res (matching.match_frames(twoway=True):
+    mask, best_idx, col_idx): a masked point stays iff the point its matched vertex picks back lies within `radius` of it.
+    -> (pair_mask u8[B,N], pair_count i32[B], cycle_d2 f32[B,N]).  One launch, no host synchronisation."""
+    if "col_idx" not in res:
+        raise ValueError("cycle_filter: res has no col_idx (match with twoway=True)")
+    return ops.match_cycle(cld_rgb_nrm, res["best_idx"], res["col_idx"], res["mask"], radius)
+
+
+def cycle_filter_numpy(xyz, best_idx, col_idx, mask, radius=CYCLE_RADIUS):
+    """THE CYCLE RULE restated in fp32, operation for operation, for one crop: xyz f32[N,3], best_idx [N], col_idx [M], mask [N].
+    -> (pair_mask u8[N], pair_count int, cycle_d2 f32[N])."""
+    f = np.float32
+    p = np.asarray(xyz, dtype=f)
+    bi, ci, mk = np.asarray(best_idx), np.asarray(col_idx), np.asarray(mask)
+    N, M = p.shape[0], ci.shape[0]
+    r = f(radius)
+    if not (np.isfinite(r) and r >= 0):
+        raise ValueError("cycle_filter_numpy: radius=%r must be finite and >= 0" % (radius,))
+    with np.errstate(over="ignore", invalid="ignore"):
+        r2 = r * r
+        pair = np.zeros(N, dtype=np.uint8)
+        d2 = np.full(N, np.inf, dtype=f)
+        for i in range(N):
+            if not mk[i]:
+                continue
+            j = int(bi[i])
+            k = int(ci[j]) if 0 <= j < M else -1
+            if not 0 <= k < N:
+                continue
+            dx, dy, dz = f(p[i, 0] - p[k, 0]), f(p[i, 1] - p[k, 1]), f(p[i, 2] - p[k, 2])
+            d2[i] = f(f(f(dx * dx) + f(dy * dy)) + f(dz * dz))
+            pair[i] = 1 if d2[i] <= r2 else 0
+    return pair, int(pair.sum()), d2
+
+
+def _pair_filter(o, res, cld_rgb_nrm, who):
+    """pose_opts' pair_filter / cycle_radius -> (the res the fit sees, the outputs the filter adds)."""
+    kind = o.get("pair_filter", "none")
+    if kind not in ("none", "cycle"):
+        raise ValueError("%s: pair_filter must be 'none' or 'cycle', got %r" % (who, kind))
+    if kind == "none":
+        if "cycle_radius" in o:
+            raise ValueError("%s: cycle_radius is for pair_filter='cycle'" % who)
+        return res, {}
+    radius = float(o.get("cycle_radius", CYCLE_RADIUS))
+    if not (np.isfinite(radius) and radius >= 0):
+        raise ValueError("%s: cycle_radius=%r must be finite and >= 0" % (who, radius))
+    if "col_idx" not in res:
+        raise ValueError("%s: pair_filter='cycle' needs col_idx in res (match with twoway=True)" % who)
+    pair_mask, pair_count, _ = cycle_filter(res, cld_rgb_nrm, radius)
+    return dict(res, mask=pair_mask), dict(pair_mask=pair_mask, pair_count=pair_count)
+
+
 def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, pose_opts=None, model_nrm=None):
     """The pose stage of the pipeline: solve_poses with `pose_fit` ("kabsch" | "ransac" | "consensus"), then `icp_iters` ICP iterations
     when > 0.  pose_opts (optional dict): ransac_iters, ransac_inlier_dist, ransac_fix_percent, seed, consensus_tau, consensus_seeds,
@@ -737,11 +794,14 @@ def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, 
     min_points, and for pose_fit="kabsch" weights ("none" | "conf") and targets ("vertex" | "soft") (solve_poses; RANSAC and ICP
     keep the hard pairs); icp_metric ("point" | "plane"): "plane" refines with refine_icp_plane instead of refine_icp, needs the
     model's unit normals model_nrm f32[M,3], takes icp_huber and icp_normal_gate as well (icp_tolerance then defaults to 1e-4) and adds
-    icp_status.  -> dict(RT, valid[, icp_iters, icp_resid[, icp_status]])."""
+    icp_status; pair_filter ("none" | "cycle"): "cycle" needs a two-way match (col_idx in res), passes the pairs through cycle_filter
+    at cycle_radius (default CYCLE_RADIUS) and gives the fit -- any pose_fit, weighted or not -- dict(res, mask=pair_mask), while ICP
+    keeps the segmentation mask; the result gains pair_mask and pair_count.
+    -> dict(RT, valid[, pair_mask, pair_count][, icp_iters, icp_resid[, icp_status]])."""
     o = dict(pose_opts or {})
     unknown = set(o) - {"ransac_iters", "ransac_inlier_dist", "ransac_fix_percent", "seed", "icp_tolerance", "icp_reject_dist",
                         "min_points", "weights", "targets", "icp_metric", "icp_huber", "icp_normal_gate", "consensus_tau", "consensus_seeds",
-                        "consensus_inlier_dist"}
+                        "consensus_inlier_dist", "pair_filter", "cycle_radius"}
     if unknown:
         raise ValueError("estimate_poses: unknown pose_opts %s" % sorted(unknown))
     min_points = o.get("min_points", 5)
@@ -752,6 +812,8 @@ def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, 
         raise ValueError("estimate_poses: icp_metric='plane' needs model_nrm (the model's unit normals)")
     if metric == "point" and (o.get("icp_huber") is not None or o.get("icp_normal_gate") is not None):
         raise ValueError("estimate_poses: icp_huber / icp_normal_gate are for icp_metric='plane'")
+    seg_res = res
+    res, extra = _pair_filter(o, res, cld_rgb_nrm, "estimate_poses")
     if pose_fit == "kabsch":
         RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, weights=o.get("weights", "none"),
                                 targets=o.get("targets", "vertex"))
@@ -763,7 +825,7 @@ def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, 
         RT, valid = solve_poses(res, cld_rgb_nrm, model_xyz, min_points, method=pose_fit, ransac_iters=o.get("ransac_iters", 20),
                                 inlier_dist=o.get("ransac_inlier_dist", 0.015), fix_percent=o.get("ransac_fix_percent", 0.7),
                                 seed=o.get("seed", 0), weights=o.get("weights", "none"), targets=o.get("targets", "vertex"))
-    return _icp_stage(dict(RT=RT, valid=valid), res, cld_rgb_nrm, model_xyz, icp_iters, o, model_nrm)
+    return _icp_stage(dict(RT=RT, valid=valid, **extra), seg_res, cld_rgb_nrm, model_xyz, icp_iters, o, model_nrm)
 
 
 def _icp_stage(out, res, cld_rgb_nrm, model_xyz, icp_iters, o, model_nrm):
@@ -1168,7 +1230,8 @@ def estimate_poses_verified(res, cld_rgb_nrm, model_xyz, verify, candidates=VERI
     depth_opts (reject, huber, min_cos, min_px, tolerance, pivot_min) -- goes through estimate_poses' stages with pose_opts, every
     parent made once and shared; then select_verified(verify) keeps, per crop, the one the observed depth agrees with best.  A
     "+depth" candidate is its refined pose rounded to f32, valid when the parent was and the refinement's status is 0 or 1.
-    -> select_verified's dict; with a "+depth" name also depth_status i32[n,C]: the refinement's status, -1 for the other candidates."""
+    -> select_verified's dict; with a "+depth" name also depth_status i32[n,C]: the refinement's status, -1 for the other candidates;
+    with pose_opts' pair_filter="cycle" (every fit then sees the filtered pairs, estimate_poses) also pair_mask and pair_count."""
     names = tuple(candidates)
     bad = [k for k in names if k.split("+")[0] not in ("kabsch", "ransac", "consensus")
            or k.split("+")[1:] not in ([], ["icp"], ["depth"], ["icp", "depth"])]
@@ -1179,13 +1242,16 @@ def estimate_poses_verified(res, cld_rgb_nrm, model_xyz, verify, candidates=VERI
     dopts = dict(depth_opts or {})
     if set(dopts) - _DEPTH_OPTS:
         raise ValueError("estimate_poses_verified: unknown depth_opts %s" % sorted(set(dopts) - _DEPTH_OPTS))
+    # pose_opts' pair_filter runs once: every fit sees the same filtered pairs, ICP (below) the segmentation mask
+    fit_res, pair_out = _pair_filter(o, res, cld_rgb_nrm, "estimate_poses_verified")
+    fit_opts = {k: v for k, v in o.items() if k not in ("pair_filter", "cycle_radius")}
     made = {}
 
     def stage(k):
         if k not in made:
             fit = k.split("+")[0]
             if k == fit:
-                made[k] = estimate_poses(res, cld_rgb_nrm, model_xyz, fit, 0, o, model_nrm)
+                made[k] = estimate_poses(fit_res, cld_rgb_nrm, model_xyz, fit, 0, fit_opts, model_nrm)
             else:
                 made[k] = _icp_stage(dict(stage(fit)), res, cld_rgb_nrm, model_xyz, int(icp_iters), o, model_nrm)
         return made[k]
@@ -1205,6 +1271,7 @@ def estimate_poses_verified(res, cld_rgb_nrm, model_xyz, verify, candidates=VERI
         else:
             fits[k] = (parent["RT"], parent["valid"])
     sel = select_verified(fits, verify)
+    sel.update(pair_out)
     if depth_status:
         none = torch.full_like(next(iter(depth_status.values())), -1)
         sel["depth_status"] = torch.stack([depth_status.get(k, none) for k in names], dim=1)

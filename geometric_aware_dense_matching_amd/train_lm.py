@@ -108,6 +108,11 @@ def build_parser():
                    help="test, --pose-fit kabsch: weigh the pairs by the matching confidence (needs --match-gamma)")
     p.add_argument("--pose-targets", dest="pose_targets", type=str, default="vertex", choices=["vertex", "soft"],
                    help="test, --pose-fit kabsch: fit to the arg-max vertex or to the expected model coordinate (needs --match-gamma)")
+    p.add_argument("--pair-filter", dest="pair_filter", type=str, default="none", choices=["none", "cycle"],
+                   help="test: cycle = two-way matching and the cycle-consistency pair filter in front of the fit (pose.cycle_filter); the "
+                        "kept fraction of the masked points is printed per object under the recall table")
+    p.add_argument("--cycle-radius", dest="cycle_radius", type=float, default=None, metavar="R",
+                   help="test, --pair-filter cycle: the filter's radius in metres (default pose.CYCLE_RADIUS; 0 = mutual best pairs only)")
     p.add_argument("--icp-iters", dest="icp_iters", type=int, default=0,
                    help="test: point-to-point ICP iterations after the fit (pvn3d_eval_utils_kpls.py:126-212); 0 = none")
     p.add_argument("--icp-tolerance", dest="icp_tolerance", type=float, default=0.001,
@@ -664,6 +669,15 @@ def test(args):
         pose_kw["pose_opts"].update(weights=args.pose_weights, targets=args.pose_targets)
     if match_gamma is not None:
         pose_kw["match_gamma"] = match_gamma
+    pair_filter = getattr(args, "pair_filter", "none")
+    if pair_filter == "cycle":
+        if match_gamma is not None:
+            raise SystemExit("train_lm test: --pair-filter cycle does not go with --match-gamma (there is no soft two-way kernel)")
+        pose_kw["pose_opts"].update(pair_filter="cycle", cycle_radius=pose.CYCLE_RADIUS if getattr(args, "cycle_radius", None) is None
+                                    else args.cycle_radius)
+    elif getattr(args, "cycle_radius", None) is not None:
+        raise SystemExit("train_lm test: --cycle-radius goes with --pair-filter cycle")
+    kept = {}                                                # object name -> [kept pairs, masked points] over the run
     # evaluator.py:308-463: when the loader carries ground-truth poses (`RT`), every instance's ADD(-S) / re / te / re-projection error
     # is computed on the device per object group and the reference's recall table is printed at the end
     from . import evaluation
@@ -722,6 +736,12 @@ def test(args):
                 results[-1].update(score=out["score"].cpu(), verify_which=out["verify_which"].cpu(), verify_counts=out["verify_counts"].cpu())
             elif "score" in out:
                 results[-1].update(score=out["score"].cpu(), conf=out["conf"].cpu())
+            if "pair_count" in out:
+                results[-1].update(pair_mask=out["pair_mask"].cpu(), pair_count=out["pair_count"].cpu())
+                for i, cid in enumerate(cls):
+                    k = kept.setdefault(obj_name_of(ds, cid), [0, 0])
+                    k[0] += int(results[-1]["pair_count"][i])
+                    k[1] += int(results[-1]["count"][i])
             if "RT" in cu and cu["RT"].dim() == 3:
                 Kcam = cu["K"] if "K" in cu else torch.from_numpy(synthetic.LM_K).to(device)
                 for cid in sorted(set(cls)):
@@ -773,6 +793,12 @@ def test(args):
             if cand_tables:
                 print("--pose-verify selection (delta %g m):" % args.verify_delta)
             print(table.format())
+    if kept:
+        test.last_kept = kept
+        if args.local_rank == 0:
+            print("--pair-filter cycle (radius %g m): kept fraction of the masked points" % pose_kw["pose_opts"]["cycle_radius"])
+            for name in sorted(kept):
+                print("  %-16s %8d / %8d = %.3f" % (name, kept[name][0], kept[name][1], kept[name][0] / max(kept[name][1], 1)))
     if bop_scores is not None and bop_scores.correct:
         test.last_bop_scores = bop_scores
         if args.local_rank == 0:

@@ -199,6 +199,38 @@ int gdm_match_soft_packed_hip(const void* scene_rows, const void* model_rows, co
  * number an estimate is ranked by (the `score` column of a BOP csv). */
 int gdm_match_score_hip(const float* conf, const uint8_t* mask, int B, int N, float* score, void* stream);
 
+/* THE TWO-WAY RULE.  Matching in both directions from one pass over the similarities.  scene_rows: B*N packed rows (crop b owns rows
+ * b*N .. b*N+N-1), model_rows: M packed rows, mask u8[B,N]; sim_ij is the kernel's own similarity (the arithmetic of
+ * gdm_match_packed_hip at that precision).
+ *   best_idx i32[B,N], best_sim f32[B,N]   those of gdm_match_packed_hip on the same rows, bit for bit, for every row, masked or not
+ *   col_idx i32[B,M], col_sim f32[B,M]     per crop b and vertex j: start from (idx, sim) = (-1, -inf) and let a point i of the crop
+ *                                          with mask[b,i] != 0 take over iff sim_ij > sim (the comparison of the row arg-max: a NaN
+ *                                          never wins), the lowest such i on exact ties; i counts inside the crop, 0 .. N-1
+ * so a crop with no masked point, or a column whose masked similarities are all NaN, gives col_idx = -1 and col_sim = -inf.  A
+ * winning similarity of -0 is reported as +0 (the two compare equal).
+ * No [R, M] tensor and no floating-point atomic: a lane reduces its column over its 16 rows, the two half-waves merge by shuffle,
+ * and the waves, the row blocks and the crops a row block spans merge through an integer maximum of the 64-bit key
+ * (order-preserving image of sim << 32 | ~i), which is exact and commutes: two launches give the same bytes.  The keys live in
+ * `partial` (gdm_match_twoway_partial_bytes(B, N, M), 16-byte aligned) behind the row partials and are reset inside the call, so the
+ * result does not depend on what `partial` held.  1 <= M <= GDM_MATCH_SOFT_MAX_M (the 64 panels of the LDS-resident kernel form);
+ * that, a NULL argument, a non-positive size, a bad precision or rows off a 16-byte boundary is refused with GDM_EINVAL before any
+ * launch. */
+size_t gdm_match_twoway_partial_bytes(int B, int N, int M);
+int gdm_match_twoway_packed_hip(const void* scene_rows, const void* model_rows, const uint8_t* mask, int B, int N, int M, int precision,
+                                int32_t* best_idx, float* best_sim, int32_t* col_idx, float* col_sim, void* partial,
+                                size_t partial_bytes, void* stream);
+/* THE CYCLE RULE.  Scene xyz addressed as in gdm_kabsch_stats_hip; best_idx i32[B,N], col_idx i32[B,M], mask u8[B,N]; radius finite
+ * and >= 0 (else GDM_EINVAL).  For a point i of crop b with mask != 0: j = best_idx[b,i], k = col_idx[b,j], d = p_i - p_k (fp32,
+ * component by component), d2 = ((dx*dx) + dy*dy) + dz*dz in fp32, every product and sum rounded on its own (no contraction); the
+ * point is kept iff d2 <= radius*radius (the product in fp32).  k == i gives d2 = 0, so radius = 0 keeps exactly the mutual best
+ * pairs (and the points that coincide with their vertex's point).  j outside [0,M), k outside [0,N) or a NaN d2 drops the point.
+ *   pair_mask u8[B,N]; pair_count i32[B] = the kept points of the crop (written, not accumulated);
+ *   cycle_d2 f32[B,N] = d2 where one was formed (a NaN included, of whatever sign and payload the arithmetic gives it), +inf where
+ *   the point is unmasked or dropped without one. */
+int gdm_match_cycle_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const int32_t* best_idx,
+                        const int32_t* col_idx, const uint8_t* mask, int B, int N, int M, float radius, uint8_t* pair_mask,
+                        int32_t* pair_count, float* cycle_d2, void* stream);
+
 /* seg f32[B,2,N] -> mask u8[B,N] = (argmax over the 2 classes == 1) (evaluator.py:79-83),
  * count i32[B] of selected points (zeroed inside).                                        */
 int gdm_seg_mask_hip(const float* seg, int B, int N, uint8_t* mask, int32_t* count, void* stream);
