@@ -30,7 +30,12 @@
 //     then takes its first 64 candidates around the column / row whose range holds its own ratio, and afterwards only scans
 //     the window of columns and rows whose lower bound is below its K-th distance: ~100 candidates instead of 16384, results
 //     identical to the exhaustive search (depth holes -- points at the origin -- are covered by a |q|^2 test that widens the
-//     window to the whole grid).
+//     window to the whole grid).  What the two margins of the keep test  (sqrt(bound) - slack)^2 * 0.999f <= td  cover: a plane bound is at
+//     most |q|^2 (the planes hold the origin) and its error is ABSOLUTE -- a few ulps of |q| in p - lo * z, where the two terms cancel --
+//     so slack = 2e-6 |q| (33 ulps of |q|) comes off its root; the factor covers the relative error of the squares and the division.
+//     A point at the origin is on every plane, so no bound speaks for it (a column of holes has an empty range and bound +inf): hence the
+//     |q|^2 test.  Restated in float32 in tests/knn_prune_model.py; its test shows that slack 0, a factor of 1.02 or no hole test each
+//     lose neighbours on the cases of tests/knn_adversarial_cases.py, and the kernel is held to brute force on them.
 //   * distances are ((dx*dx)+dy*dy)+dz*dz with every operation rounded to fp32 (no FMA
 //     contraction: __fmul_rn/__fadd_rn and -ffp-contract=off), exactly the reference's
 //     arithmetic, so indices are bit-exact on tie-free inputs; ties are ordered by ascending
@@ -669,7 +674,7 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_grid_kernel(const KnnTable tab)
         const int uc = min(max(arg_min(lbc) - 4, 0), W - 8), vc = min(max(arg_min(lbr) - 4, 0), H - 8);
         eval(vc + (lane >> 3), uc + (lane & 7), true, false);
         sel.compact();
-        // phase 2: only columns / rows whose bound (less a rounding allowance, scale-free) can still be below the K-th distance
+        // phase 2: only columns / rows whose bound (less a rounding allowance, scale-free: see the head of this file) can still be below the K-th distance
         const float slack = 2e-6f * sqrtf(q2);
         int cl = W, ch = -1, rl = H, rh = -1;
 #pragma unroll
@@ -708,9 +713,21 @@ __global__ __launch_bounds__(KW_BLOCK) void knn_grid_kernel(const KnnTable tab)
 // admitted candidates and 3-4 sorts per query on top of 32 scan steps.  Here the support of a crop is binned ONCE into G x G cells (kc_grid)
 // of its (x, y) bounding box (knn_cells_bin_kernel: counting sort in LDS, one workgroup per crop) and a query visits the cells ring
 // by ring around its own -- 3 x 3 first, one wave step per cell row -- until the nearest edge of the visited window lies farther than
-// the current K-th distance: dx (or dy) alone already exceeds it for every unvisited point.  Exact for any data (same (d2, index)
-// keys, the window just grows to the whole grid in the worst case); the bound carries a 0.1 % allowance on d2 for the rounding of the
-// cell assignment.
+// the current K-th distance: dx (or dy) alone already exceeds it for every unvisited point.  Exact for any finite data (same (d2, index)
+// keys, the window just grows to the whole grid in the worst case).  Why the fp32 exit test  m * m * 0.999f > td  never skips a neighbour:
+// an unvisited point v beyond the edge E(n) = fl(lo + fl(n * cw)) was binned with cell(v) = trunc(fl(fl(v - lo) * inv)) >= n, so in exact
+// arithmetic v >= lo + n * cw.  Two roundings stand between that and  v - q >= m:
+//   * ABSOLUTE: lo + n * cw is rounded to the float grid at |lo|, which may be coarser than a cell (a crop far from the origin).  v lies on
+//     the same grid and rounding to nearest is monotone: v >= e implies v = fl(v) >= fl(e).  The rounded edge is never beyond a point that
+//     is beyond the exact one, whatever |lo| / extent is; no margin is needed for it.  Where the grid is coarser than a cell m comes out as
+//     0 (no exit: m > 0 is required) or as whole ulps (exact).
+//   * RELATIVE: fl(v - lo), the product with inv = fl(1 / cw), cw = fl(extent / G) and fl(n * cw) carry half an ulp each: the boundary the
+//     binning drew lies within ~4 * 2^-24 * G = 8e-6 cells of lo + n * cw.  m is at least one cell less that (the window holds the query's
+//     cell and its neighbours; a query outside the box is clamped to a border cell, farther from the inner edge), so the error is below
+//     1e-5 of m, 2e-5 of m * m.  THAT is what the factor 0.999 covers, fifty times over.
+// tests/knn_prune_model.py restates the rule operation by operation in float32; tests/test_knn_prune_model_cpu.py holds it, and
+// tests/test_gpu_knn_adversarial.py this kernel, to brute force on supports up to 2^20 extents from the origin, points on and next to
+// the edges, and K-th neighbours that race a point one float beyond an edge.
 constexpr int KC_MIN_S = 1024;          // supports below this stay on knn_wave_kernel
 constexpr int KC_GMAX = 32;             // cells per axis: 16 below 8192 points, 32 from there (kc_grid).  Measured on the pyramid's 2048-point clouds
                                         // (tools/knn_cells_stats.py): 16 -> 1.8 rings, 2.6 row batches, 2.7 sorts per query, 64 us per batch of

@@ -62,14 +62,15 @@ typedef struct gdm_knn_job {
     int32_t S, Q, K;
     int32_t grid_w;           /* 0, or: the support is an ORGANISED map (e.g. the xyz of a depth crop) of S / grid_w rows x grid_w columns
                                * in row-major pixel order -- a hint that lets K > 1 searches with a workspace prune by pixel columns / rows;
-                               * results are identical with and without it, for any data                                            */
+                               * results are identical with and without it, for any finite data                                     */
 } gdm_knn_job;
 #define GDM_KNN_MAX_JOBS 32
 /* jobs is a HOST array.  workspace: device memory (16-byte aligned, >= gdm_knn_jobs_workspace_bytes) in which every distinct support
  * set of the K > 1 jobs is re-laid out once: small unorganised supports as hashed float4 tiles that the search blocks stream with
  * coalesced loads, unorganised supports of >= 1024 points as (x, y) cell lists (a counting sort per crop; a query then visits cells
  * ring by ring instead of every point), organised supports (grid_w) as per-column / per-row ratio ranges.  workspace NULL with
- * workspace_bytes 0: each block gathers its tiles from the [S,3] array.  Results are identical in every form, for any data.
+ * workspace_bytes 0: each block gathers its tiles from the [S,3] array.  Results are identical in every form, for any data with
+ * finite coordinates (the order of NaN and infinite coordinates is not defined and may differ between the forms).
  * Bytes per distinct (support, S, support_bstride, layout), each rounded up to 16, reserved in the order of the jobs by descending S:
  *   ranges (W = grid_w and H = S / grid_w both in [8, 256]):  B * (2 W + 2 H + 2 ceil(H / 16)) * 4
  *   cell list (no ranges, S >= 1024):                         B * S * 16 + B * 1036 * 4
