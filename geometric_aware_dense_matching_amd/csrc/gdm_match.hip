@@ -1082,6 +1082,20 @@ __device__ __forceinline__ void col_reduce(const gdm_f32x16& a, unsigned bits, i
     }
 }
 
+// col_reduce's steps 2 and 3 alone, for the dual kernel, which takes step 1 inside its own loop over the registers (its accumulators
+// do not outlive that loop): (bv, row) = what step 1 left in the lane, row -1 where no row counted; the key goes to lds.  The same
+// comparisons and the same key: written twice so that col_reduce, and with it the two-way kernel's code, stays as it was
+__device__ __forceinline__ void col_merge(float bv, int row, bool ok, int h, unsigned long long* lds)
+{
+    const float ov = __shfl_xor(bv, 32, 64);
+    const int orow = __shfl_xor(row, 32, 64);
+    if (ov > bv || (ov == bv && (unsigned)orow < (unsigned)row)) {
+        bv = ov;
+        row = orow;
+    }
+    if (h == 0 && ok && row >= 0) atomicMax(lds, col_key(bv, row));
+}
+
 template <int PREC>
 __global__ __launch_bounds__(V2_THREADS) void match_panel_twoway_kernel(const unsigned char* __restrict__ apk,
                                                                          const unsigned char* __restrict__ bpk,
@@ -1223,6 +1237,204 @@ __global__ __launch_bounds__(256) void match_cycle_kernel(const float* __restric
     if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) pair_count[b] = cred[0] + cred[1] + cred[2] + cred[3];
+}
+
+// ------------------------------------------------------------------------------------------
+// dual-softmax matching: the soft kernel's row softmax, the two-way kernel's column arg-max and the column sum of the soft weights
+// ------------------------------------------------------------------------------------------
+// include/gdm.h THE DUAL RULE.  One pass of MFMAs gives all three.  The panel fill, the operand load, the product block, the row scan,
+// the row butterflies (finalize_rows, row_sum16) and the weight w = exp2(fma(sim, k2, -k2)) are match_panel_soft_kernel's own, the
+// column key scan (col_reduce's comparisons and key) is match_panel_twoway_kernel's: the row outputs are the soft launch's bit for bit and col_idx /
+// col_sim the two-way launch's.  Unlike those two kernels this one cuts the rows into blocks that never span a crop: ceil(N / 256)
+// blocks of 256 rows per crop, the rows past the crop's end unreal (loaded clamped, never written, never counted).  One crop per row
+// block means one key slot and one sum slot in LDS and no crop loop.  The helpers are addressed crop by crop: the crop's rows as a
+// launch of N rows, the partials through pointers moved so that finalize_rows' [panel * N + row] lands on [panel * R + c * N + row].
+// A step is ONE 32-column accumulator block (tile_product<PREC, 1>), where those kernels take two: 16 accumulator VGPRs less, which
+// is what lets all three results fit in 256 VGPRs without scratch (241 / 249, profiles/match_dual.md).  z + w and fma(w, x, s) run
+// over the same columns in the same order as the soft kernel's (z + w0) + w1 and nested fmas: the same bits.
+// The column sum, per step and for the lane's column, reuses the w of the row sums (no further exponential):
+//   1. in-lane: the lane's 16 rows in ascending register order, under the bits of the rows that are real and masked;
+//   2. the other half-wave by one shuffle (a + b = b + a: both halves hold the same bits);
+//   3. the 8 waves: each writes its partial to wsum[wave][column] in LDS (every wave writes every column of every row block, so the
+//      buffer needs no reset); after the barrier the key flush has anyway one thread per column adds them in ascending wave order
+//      and writes cpart[row block][column];
+//   4. the row blocks of a crop: dual_cols_kernel adds them in ascending order.
+// A fixed order throughout and no floating-point atomic: two launches give the same bytes.
+constexpr int DUAL_KEY_OFF = SOFT_LDS_BYTES;                                            // [PANEL_COLS] keys of the row block's crop
+constexpr int DUAL_SUM_OFF = DUAL_KEY_OFF + PANEL_COLS * (int)sizeof(unsigned long long);   // [8 waves][PANEL_COLS] column sums
+constexpr int DUAL_LDS_BYTES = DUAL_SUM_OFF + (V2_THREADS / 64) * PANEL_COLS * (int)sizeof(float);
+static_assert(DUAL_KEY_OFF % 8 == 0 && DUAL_LDS_BYTES <= 160 * 1024, "the dual kernel's LDS: 128 KiB panel + 3 KiB xyz + 2 KiB keys + 8 KiB sums");
+
+template <int PREC>
+__global__ __launch_bounds__(V2_THREADS) void match_panel_dual_kernel(const unsigned char* __restrict__ apk,
+                                                                       const unsigned char* __restrict__ bpk,
+                                                                       const float* __restrict__ xyz,          // [M, 3]
+                                                                       const uint8_t* __restrict__ mask,       // [B, N]
+                                                                       int B, int N, int M, int G, float k2,
+                                                                       float* __restrict__ pval,               // [panels, R]
+                                                                       int32_t* __restrict__ pidx,
+                                                                       float4* __restrict__ psum,              // [panels, R]
+                                                                       unsigned long long* __restrict__ keys,  // [B, M]
+                                                                       float* __restrict__ cpart)              // [B * nrbc, M]
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // DUAL_LDS_BYTES
+    float* xs = reinterpret_cast<float*>(smem + PANEL_BYTES);              // [PANEL_COLS][3]
+    unsigned long long* cbuf = reinterpret_cast<unsigned long long*>(smem + DUAL_KEY_OFF);
+    float* wsum = reinterpret_cast<float*>(smem + DUAL_SUM_OFF);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);         // uniform: what derives from it stays out of the VGPRs
+    const int lr = lane & 31;
+    const int h = lane >> 5;
+    const int g = blockIdx.x % G;
+    const int panel = blockIdx.x / G;
+    const int col0 = panel * PANEL_COLS;
+    const int ncols = min(PANEL_COLS, M - col0);
+    const int R = B * N;
+
+    fill_panel(bpk, col0, M, tid);
+    for (int i = tid; i < 3 * PANEL_COLS; i += V2_THREADS) {
+        const int col = i / 3;
+        xs[i] = xyz[(long)min(col0 + col, M - 1) * 3 + (i - 3 * col)];
+    }
+    if (tid < PANEL_COLS) cbuf[tid] = 0ull;
+    __syncthreads();
+
+    const int nrbc = (N + V2_ROWS - 1) / V2_ROWS;                          // row blocks per crop
+    const int nq = B * nrbc;
+    for (int q = g; q < nq; q += G) {
+        gdm_u32x4 areg[16];
+        const int c = q / nrbc;
+        const long crow = (long)c * N;                                     // the crop's first row
+        const int row0 = (q - c * nrbc) * V2_ROWS + wave * 32;             // counted inside the crop
+        load_a_rows<PREC>(apk + crow * ROW_BYTES, row0 + lr, N, h, areg);
+
+        unsigned mbits = 0;                                                // the lane's 16 rows: which are real and masked
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int lrow = acc_row(row0, reg, h);
+            if (lrow < N && mask[crow + lrow]) mbits |= 1u << reg;
+        }
+
+        float best[16], z[16], sx[16], sy[16], sz[16];
+        int bidx[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            best[i] = -INFINITY;
+            bidx[i] = 0;
+            z[i] = sx[i] = sy[i] = sz[i] = 0.f;
+        }
+
+#pragma unroll 1
+        for (int cb = 0; cb < PANEL_COLS / 32; ++cb) {
+            gdm_f32x16 acc[1];
+            const int c0 = cb * 32 + lr;
+            tile_product<PREC, 1>(0, c0, h, areg, acc);
+            // the step's column bookkeeping is formed from the lane behind the products, step by step, not held across them (the
+            // tail below says why)
+            int lc = lane;
+            asm volatile("" : "+v"(lc));
+            const int cc = cb * 32 + (lc & 31), hc = lc >> 5;              // = c0, h
+            const int gc0 = col0 + cc;
+            const bool ok0 = cc < ncols;
+            float x0 = xs[3 * cc], y0 = xs[3 * cc + 1], z0 = xs[3 * cc + 2];
+            GDM_SETTLE_LDS("+v"(x0), "+v"(y0), "+v"(z0));
+            float cs0 = 0.f, kv0 = -INFINITY;
+            int kr0 = -1;
+            const int krow = row0 + 4 * hc;                                // the lane's register 0, counted inside the crop
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const float v0 = acc[0][reg];
+                running_max(v0, gc0, ok0, best[reg], bidx[reg]);
+                // a padding column of the last panel weighs nothing
+                const float w0 = ok0 ? __builtin_amdgcn_exp2f(__builtin_fmaf(v0, k2, -k2)) : 0.f;
+                z[reg] = z[reg] + w0;
+                sx[reg] = __builtin_fmaf(w0, x0, sx[reg]);
+                sy[reg] = __builtin_fmaf(w0, y0, sy[reg]);
+                sz[reg] = __builtin_fmaf(w0, z0, sz[reg]);
+                const bool on = (mbits >> reg) & 1u;                       // step 1 of the column sum and of the column arg-max
+                cs0 += on ? w0 : 0.f;
+                running_max(v0, krow + acc_row(0, reg, 0), on, kv0, kr0);
+            }
+            cs0 += __shfl_xor(cs0, 32, 64);                                // step 2
+            if (hc == 0) wsum[wave * PANEL_COLS + cc] = cs0;               // step 3: this wave's partial of the row block
+            col_merge(kv0, kr0, ok0, hc, cbuf + cc);
+        }
+
+        // what the tail derives from the lane is formed here, row block by row block: hoisted out of the loop it would sit in
+        // registers through the products, which have none to spare
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int hn = ln >> 5;
+        const long poff = crow + (long)panel * (R - N);                    // [panel * N + row] from here = [panel * R + crow + row]
+        finalize_rows<true>(best, bidx, ln, hn, row0, N, panel, pval + poff, pidx + poff);
+        const float rz = row_sum16(z, ln), rx = row_sum16(sx, ln), ry = row_sum16(sy, ln), rw = row_sum16(sz, ln);
+        if ((ln & 16) == 0) {
+            const int lrow = acc_row(row0, survivor_reg(ln), hn);
+            if (lrow < N) psum[(long)panel * R + crow + lrow] = make_float4(rz, rx, ry, rw);
+        }
+
+        // the row block's keys and sums leave LDS, one thread per column; the key buffer is empty again for the next row block
+        __syncthreads();
+        const int col = wave * 64 + ln;
+        if (col < PANEL_COLS) {
+            const unsigned long long key = cbuf[col];
+            if (key != 0ull) {                                             // only columns < ncols were ever written
+                atomicMax(keys + (long)c * M + col0 + col, key);
+                cbuf[col] = 0ull;
+            }
+            if (col < ncols) {
+                float s = wsum[col];
+#pragma unroll
+                for (int w = 1; w < V2_THREADS / 64; ++w) s += wsum[w * PANEL_COLS + col];      // ascending waves
+                cpart[(long)q * M + col0 + col] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// per (crop, vertex): Zc = the row blocks' partials in ascending order; the key decoded as twoway_cols_kernel does it; col_lse with
+// the logarithm in fp64 as soft_merge_kernel; col_conf = the w of col_sim, recomputed by the same two instructions, over Zc.  That w is
+// one of Zc's terms and fp32 addition of non-negative terms is monotone, so col_conf lies in (0, 1].
+__global__ __launch_bounds__(256) void dual_cols_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ cpart, long n,
+                                                        int nrbc, int M, float gamma, float k2, int32_t* __restrict__ col_idx,
+                                                        float* __restrict__ col_sim, float* __restrict__ col_lse, float* __restrict__ col_conf,
+                                                        float* __restrict__ zc)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long b = i / M;
+    const int j = (int)(i - b * M);
+    const float* p = cpart + b * nrbc * M + j;
+    float s = p[0];
+    for (int k = 1; k < nrbc; ++k) s += p[(long)k * M];
+    const unsigned long long key = keys[i];
+    const unsigned u = (unsigned)(key >> 32);
+    const float sim = key ? __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u) : -INFINITY;
+    col_idx[i] = key ? (int32_t)~(unsigned)key : -1;
+    col_sim[i] = sim;
+    zc[i] = s;
+    col_lse[i] = (float)((double)gamma + log((double)s));                  // log 0 = -inf: a crop with no masked point
+    col_conf[i] = key ? (float)((double)__builtin_amdgcn_exp2f(__builtin_fmaf(sim, k2, -k2)) / (double)s) : 0.f;
+}
+
+// dual[i] = conf[i] * (w_ij / Zc[b, j]) at j = best_idx[i] for a masked point, the quotient and the product in fp64 and one rounding;
+// 0 for an unmasked point.  The point is one of Zc's terms, so the quotient is <= 1 and dual <= conf.
+__global__ __launch_bounds__(256) void dual_rows_kernel(const int32_t* __restrict__ best_idx, const float* __restrict__ best_sim,
+                                                        const float* __restrict__ conf, const uint8_t* __restrict__ mask,
+                                                        const float* __restrict__ zc, int R, int N, int M, float k2, float* __restrict__ dual)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    float d = 0.f;
+    if (mask[r]) {
+        const int j = min(max(best_idx[r], 0), M - 1);
+        const double w = (double)__builtin_amdgcn_exp2f(__builtin_fmaf(best_sim[r], k2, -k2));
+        d = (float)((double)conf[r] * (w / (double)zc[(long)(r / N) * M + j]));
+    }
+    dual[r] = d;
 }
 
 } // namespace
@@ -1482,6 +1694,84 @@ extern "C" int gdm_match_cycle_hip(const float* scene_xyz, long scene_bstride, i
     hipLaunchKernelGGL(match_cycle_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scene_xyz, scene_bstride, pt_stride, ch_stride,
                        best_idx, col_idx, mask, N, M, radius * radius, pair_mask, pair_count, cycle_d2);
     return gdm_launch_status("match_cycle_kernel");
+}
+
+// the dual launch's workspace: the soft launch's (row partials, row sums), then the keys u64[B,M], the column partials
+// f32[B * ceil(N / 256), M] and Zc f32[B,M]
+extern "C" size_t gdm_match_dual_partial_bytes(int B, int N, int M)
+{
+    if (B < 1 || N < 1 || M < 1) return 0;
+    const size_t cols = (size_t)B * M;
+    return gdm_match_soft_partial_bytes(B, N) + align256(cols * sizeof(unsigned long long)) +
+           align256(cols * gdm_cdiv(N, V2_ROWS) * sizeof(float)) + align256(cols * sizeof(float));
+}
+
+extern "C" int gdm_match_dual_packed_hip(const void* scene_rows, const void* model_rows, const float* model_xyz, const uint8_t* mask, int B,
+                                         int N, int M, int precision, float gamma, int32_t* best_idx, float* best_sim, float* lse,
+                                         float* conf, float* soft_xyz, int32_t* col_idx, float* col_sim, float* col_lse, float* col_conf,
+                                         float* dual, void* partial, size_t partial_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    GDM_CHECK_ARG(scene_rows && model_rows && model_xyz && mask && best_idx && best_sim && lse && conf && soft_xyz && col_idx && col_sim &&
+                      col_lse && col_conf && dual && partial,
+                  "gdm_match_dual_packed_hip: NULL pointer");
+    GDM_CHECK_ARG(B >= 1 && N >= 1 && M >= 1, "gdm_match_dual_packed_hip: bad shape B=%d N=%d M=%d", B, N, M);
+    GDM_CHECK_ARG((long)B * N < (1L << 22), "gdm_match_dual_packed_hip: B*N too large");
+    GDM_CHECK_ARG(M <= GDM_MATCH_SOFT_MAX_M, "gdm_match_dual_packed_hip: M=%d, the dual kernel covers M <= %d", M, GDM_MATCH_SOFT_MAX_M);
+    GDM_CHECK_ARG(precision == GDM_MATCH_BF16X3 || precision == GDM_MATCH_F32, "gdm_match_dual_packed_hip: precision=%d", precision);
+    GDM_CHECK_ARG(gamma > 0.f && gamma <= GDM_MATCH_SOFT_MAX_GAMMA, "gdm_match_dual_packed_hip: gamma=%g not in (0, %g]", (double)gamma,
+                  (double)GDM_MATCH_SOFT_MAX_GAMMA);                       // a NaN fails both comparisons
+    GDM_CHECK_ARG(((uintptr_t)partial & 15) == 0, "gdm_match_dual_packed_hip: partial must be 16-byte aligned");
+    GDM_CHECK_ARG((((uintptr_t)scene_rows | (uintptr_t)model_rows) & 15) == 0, "gdm_match_dual_packed_hip: the packed rows must be 16-byte aligned");
+    const int R = B * N;
+    const int nrbc = gdm_cdiv(N, V2_ROWS);
+    const size_t ncols = (size_t)B * M;
+    const size_t half = align256(64 * (size_t)R * sizeof(float));
+    const size_t sums = align256(64 * (size_t)R * sizeof(float4));
+    const size_t kbytes = align256(ncols * sizeof(unsigned long long));
+    const size_t cbytes = align256(ncols * nrbc * sizeof(float));
+    const size_t need = 2 * half + sums + kbytes + cbytes + align256(ncols * sizeof(float));
+    if (partial_bytes < need) {
+        gdm_set_error("gdm_match_dual_packed_hip: partial workspace %zu < %zu bytes", partial_bytes, need);
+        return GDM_ENOMEM;
+    }
+    unsigned char* base = (unsigned char*)partial;
+    float* pval = (float*)base;
+    int32_t* pidx = (int32_t*)(base + half);
+    float4* psum = (float4*)(base + 2 * half);
+    unsigned long long* keys = (unsigned long long*)(base + 2 * half + sums);
+    float* cpart = (float*)(base + 2 * half + sums + kbytes);
+    float* zc = (float*)(base + 2 * half + sums + kbytes + cbytes);
+    const int panels = gdm_cdiv(M, PANEL_COLS);
+    const int nq = B * nrbc;                                    // row blocks: none spans a crop
+    int G = 512 / panels;                                       // as v2: one workgroup per CU, two rounds
+    if (G < 1) G = 1;
+    if (G > nq) G = nq;
+    if (G >= 8) G &= ~7;
+    const float k2 = gamma * 1.44269504088896340736f;
+    const hipError_t me = hipMemsetAsync(keys, 0, ncols * sizeof(unsigned long long), stream);      // key 0 = no candidate
+    if (me != hipSuccess) {
+        gdm_set_error("gdm_match_dual_packed_hip: hipMemsetAsync of the keys failed: %s", hipGetErrorString(me));
+        return (int)me;
+    }
+    gdm_dispatch_int<2>(precision, [&](auto P) {
+        constexpr auto kernel = match_panel_dual_kernel<decltype(P)::value>;
+        gdm_allow_lds<kernel>(DUAL_LDS_BYTES);
+        hipLaunchKernelGGL(kernel, dim3(panels * G), dim3(V2_THREADS), DUAL_LDS_BYTES, stream, (const unsigned char*)scene_rows,
+                           (const unsigned char*)model_rows, model_xyz, mask, B, N, M, G, k2, pval, pidx, psum, keys, cpart);
+    });
+    int rc = gdm_launch_status("match_panel_dual_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(soft_merge_kernel, dim3(gdm_cdiv(R, 256)), dim3(256), 0, stream, pval, pidx, psum, panels, R, gamma, k2, best_sim,
+                       best_idx, lse, conf, soft_xyz);
+    rc = gdm_launch_status("soft_merge_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(dual_cols_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, stream, keys, cpart, (long)ncols, nrbc, M, gamma,
+                       k2, col_idx, col_sim, col_lse, col_conf, zc);
+    rc = gdm_launch_status("dual_cols_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(dual_rows_kernel, dim3(gdm_cdiv(R, 256)), dim3(256), 0, stream, best_idx, best_sim, conf, mask, zc, R, N, M, k2, dual);
+    return gdm_launch_status("dual_rows_kernel");
 }
 
 extern "C" int gdm_match_hip(const float* scene, const float* model, int B, int Dd, int N, int M, int precision,

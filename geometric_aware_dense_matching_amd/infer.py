@@ -17,8 +17,15 @@ def _plane_normals(model, pose_opts):
     return model.model_emb.unit_normals() if (pose_opts or {}).get("icp_metric") == "plane" else None
 
 
-def _twoway(match_twoway, pose_opts, match_gamma):
-    """The two-way kernel is taken when asked for, and when pose_opts' pair_filter needs its col_idx; not together with soft matching."""
+def _twoway(match_twoway, pose_opts, match_gamma, match_dual=False):
+    """The two-way kernel is taken when asked for, and when pose_opts' pair_filter needs its col_idx; not together with soft matching.
+    match_dual (which needs match_gamma) is the soft form of both: the dual kernel's col_idx serves the filter and this returns False."""
+    if match_dual:
+        if match_gamma is None:
+            raise ValueError("match_dual needs match_gamma (the dual softmax has a temperature)")
+        if match_twoway:
+            raise ValueError("match_dual already returns col_idx / col_sim; do not pass match_twoway with it")
+        return False
     on = bool(match_twoway) or (pose_opts or {}).get("pair_filter", "none") == "cycle"
     if on and match_gamma is not None:
         raise ValueError("match_twoway (or pair_filter='cycle') and match_gamma: twoway and soft exclude each other (there is no soft "
@@ -56,7 +63,7 @@ def _verify_rows(verify, cid, idx, bs):
 
 
 def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf16x3", pose_fit="kabsch", icp_iters=0, pose_opts=None,
-                     match_gamma=None, verify=None, match_twoway=False):
+                     match_gamma=None, verify=None, match_twoway=False, match_dual=False):
     """model_dict: {cls_id: GeoMatch (eval, on the GPU)}; inputs: dict of batched device tensors (loader keys, plus
     `dpt_xyz` when the neighbour pyramid is not already in it); cls_ids: int tensor/list [bs].  pose_fit / icp_iters / pose_opts:
     pose.estimate_poses (the defaults are the plain Kabsch fit).  match_gamma: soft matching at that temperature (pipeline_step).
@@ -64,9 +71,10 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
     candidates, icp_iters, depth_iters and depth_opts; a "+depth" candidate adds verify_depth_status), one for all classes or
     {cls_id: dict}; depth / K / window with a leading batch dimension are cut down to each class's rows.  The pose is then the verified selection and verify_score, verify_which, verify_counts join the outputs.
     match_twoway (or pair_filter="cycle" in pose_opts): two-way matching, as in pipeline_step; col_idx, col_sim (and pair_mask,
-    pair_count) join the outputs.
+    pair_count) join the outputs.  match_dual (with match_gamma): dual-softmax matching, as in pipeline_step; col_idx, col_sim,
+    col_lse, col_conf, dual join the soft outputs and pair_filter="cycle" is accepted.
     Returns dict(seg, rgbd, mesh, mask, best_idx, best_sim[, lse, conf, soft_xyz, score][, RT, valid[, icp_iters, icp_resid[, icp_status]]])."""
-    twoway = _twoway(match_twoway, pose_opts, match_gamma)
+    twoway = _twoway(match_twoway, pose_opts, match_gamma, match_dual)
     cls = torch.as_tensor(cls_ids).cpu().tolist()
     bs = len(cls)
     out = {}
@@ -81,11 +89,13 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
                 sub.update(pyramid.build_pyramid(pyramid.cloud_from_inputs(sub["cld_rgb_nrm"]), sub["dpt_xyz"]))
             ep = model(sub)
             soft = None if match_gamma is None else dict(gamma=match_gamma, model_xyz=model.model_emb.xyz)
-            res = matching.match_frames(ep, precision=precision, soft=soft, twoway=twoway)
+            res = matching.match_frames(ep, precision=precision, soft=soft, twoway=twoway, dual=match_dual)
             part = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"].expand(len(sel), -1, -1), mask=res["mask"],
                         best_idx=res["best_idx"], best_sim=res["best_sim"])
             if "col_idx" in res:
                 part.update(col_idx=res["col_idx"], col_sim=res["col_sim"])
+            if "dual" in res:
+                part.update(col_lse=res["col_lse"], col_conf=res["col_conf"], dual=res["dual"])
             if soft is not None:
                 part.update(lse=res["lse"], conf=res["conf"], soft_xyz=res["soft_xyz"], score=ops.match_score(res["conf"], res["mask"]))
             if with_pose:
@@ -100,7 +110,7 @@ def run_multi_object(model_dict, inputs, cls_ids, with_pose=True, precision="bf1
 
 
 def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyramid=False, pose_fit="kabsch", icp_iters=0, pose_opts=None,
-                  match_gamma=None, verify=None, match_twoway=False):
+                  match_gamma=None, verify=None, match_twoway=False, match_dual=False):
     """ONE pass of the hot path over a batch of crops resident on the device: neighbour pyramid (unless `inputs` already carries the
     loader's index arrays) -> GeoMatch.forward (eval) -> seg mask + descriptor packs + N x M arg-max (evaluator.py:78-93) [-> pose].
     Everything is enqueued on the current stream (and, with settings.USE_SIDE_STREAMS, on side streams forked from and joined back to
@@ -116,9 +126,12 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
     candidate, which pose.refine_poses_depth refines against the frame); still no host synchronisation.
     match_twoway = False: as ever.  With it (or with pair_filter="cycle" in pose_opts, which needs it) the two-way kernel takes the
     arg-max kernel's place behind the mask (same best_idx / best_sim; not together with match_gamma) and the outputs gain col_idx
-    i32[B,M], col_sim f32[B,M] (include/gdm.h THE TWO-WAY RULE); the pose stage then adds pair_mask, pair_count when it filters."""
+    i32[B,M], col_sim f32[B,M] (include/gdm.h THE TWO-WAY RULE); the pose stage then adds pair_mask, pair_count when it filters.
+    match_dual = False: as ever.  With it (it needs match_gamma) the dual kernel takes the soft kernel's place behind the mask (the
+    same soft outputs, the two-way kernel's col_idx / col_sim) and the outputs gain col_lse f32[B,M], col_conf f32[B,M] and dual
+    f32[B,N] (include/gdm.h THE DUAL RULE); pose_opts' weights="dual" and pair_filter="cycle" can then use them."""
     prec = _PREC[precision]
-    twoway = _twoway(match_twoway, pose_opts, match_gamma)          # refuses before anything is enqueued
+    twoway = _twoway(match_twoway, pose_opts, match_gamma, match_dual)          # refuses before anything is enqueued
     d = dict(inputs)
     pyr = None
     if not getattr(model, "needs_pyramid", True):
@@ -134,6 +147,10 @@ def pipeline_step(model, inputs, precision="bf16x3", with_pose=False, keep_pyram
         mask, count, bi, bs, ci, cs = matching.match_tail(ep, B, N, M, prec, twoway=True)
         out = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=mask, count=count, best_idx=bi, best_sim=bs, col_idx=ci,
                    col_sim=cs)
+    elif match_dual:
+        t = matching.match_tail(ep, B, N, M, prec, soft=dict(gamma=match_gamma, model_xyz=model.model_emb.xyz), dual=True)
+        out = dict(zip(ops.DUAL_KEYS, t[2:]), seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=t[0], count=t[1],
+                   score=ops.match_score(t[5], t[0]))
     elif match_gamma is None:
         mask, count, bi, bs = matching.match_tail(ep, B, N, M, prec)
         out = dict(seg=ep["seg"], rgbd=ep["rgbd"], mesh=ep["mesh"], mask=mask, count=count, best_idx=bi, best_sim=bs)
@@ -153,7 +170,7 @@ FRAME_KEYS = ("rgb_u8", "depth", "K", "bbox_xyxy", "mask")           # what a `f
 
 
 def frame_step(model, frames, S, n_points, seed=0, depth_fill=None, precision="bf16x3", with_pose=False, keep_pyramid=False,
-               pose_fit="kabsch", icp_iters=0, pose_opts=None, match_gamma=None, match_twoway=False):
+               pose_fit="kabsch", icp_iters=0, pose_opts=None, match_gamma=None, match_twoway=False, match_dual=False):
     """From raw frames and detection boxes to the step's outputs: frames = dict(rgb_u8 u8[B,H,W,3], depth f32[B,H,W], K f32[B,3,3],
     bbox_xyxy f32[B,4][, mask u8[B,H,W]]) -> frontend.make_inputs_from_boxes(sampler="hash", build_pyramid=False, train=False) ->
     pipeline_step (which builds the pyramid a model needs).  seed: an int or a one-element int32 device tensor (ops.sample_assemble).
@@ -163,7 +180,7 @@ def frame_step(model, frames, S, n_points, seed=0, depth_fill=None, precision="b
                                            mask=frames.get("mask"), train=False, depth_fill=depth_fill, sampler="hash", seed=seed,
                                            build_pyramid=False)
     out = pipeline_step(model, item, precision, with_pose, keep_pyramid, pose_fit, icp_iters, pose_opts, match_gamma,
-                        match_twoway=match_twoway)
+                        match_twoway=match_twoway, match_dual=match_dual)
     out.update((k, item[k]) for k in ("choose", "cld_rgb_nrm", "n_valid", "center", "scale", "origin_labels") if k in item)
     return out
 
@@ -194,9 +211,9 @@ class GraphedPipeline:
 
     def __init__(self, model, example_inputs, precision="bf16x3", with_pose=True, warmup=3, forked="auto", burst=8,
                  keep_pyramid=False, capture_error_mode=None, keep_both=False, pose_fit="kabsch", icp_iters=0, pose_opts=None,
-                 match_gamma=None, match_twoway=False):
+                 match_gamma=None, match_twoway=False, match_dual=False):
         self.model = model.eval()
-        self.match_gamma, self.match_twoway = match_gamma, match_twoway
+        self.match_gamma, self.match_twoway, self.match_dual = match_gamma, match_twoway, match_dual
         self.precision, self.with_pose, self.keep_pyramid = precision, with_pose, keep_pyramid
         self.pose_fit, self.icp_iters, self.pose_opts = pose_fit, icp_iters, dict(pose_opts or {})
         self.static_in = {k: v.clone() for k, v in example_inputs.items() if torch.is_tensor(v)}
@@ -242,7 +259,7 @@ class GraphedPipeline:
     # -- construction helpers ---------------------------------------------------------------------------------------------
     def _step(self):
         return pipeline_step(self.model, self.static_in, self.precision, self.with_pose, self.keep_pyramid, self.pose_fit, self.icp_iters,
-                             self.pose_opts, self.match_gamma, match_twoway=self.match_twoway)
+                             self.pose_opts, self.match_gamma, match_twoway=self.match_twoway, match_dual=self.match_dual)
 
     def _eager_reference(self, warmup):
         """Eager single-stream steps on the example inputs (they also fill the per-module caches); the last one's outputs, cloned."""
@@ -319,7 +336,7 @@ class GraphedFramePipeline(GraphedPipeline):
 
     def _step(self):
         return frame_step(self.model, self.static_in, self.S, self.n_points, self.seed, self.depth_fill, self.precision, self.with_pose,
-                          self.keep_pyramid, self.pose_fit, self.icp_iters, self.pose_opts, self.match_gamma, self.match_twoway)
+                          self.keep_pyramid, self.pose_fit, self.icp_iters, self.pose_opts, self.match_gamma, self.match_twoway, self.match_dual)
 
     def __call__(self, frames, seed=None):
         """Copies `frames` (and, when given, the seed) into the static buffers, replays the graph, returns the static outputs (valid

@@ -2463,6 +2463,47 @@ def match_twoway(scene, model, mask, precision=MATCH_BF16X3):
     return match_twoway_packed(srows, mrows, mask, B, N, model.shape[1], precision)
 
 
+DUAL_KEYS = ("best_idx", "best_sim", "lse", "conf", "soft_xyz", "col_idx", "col_sim", "col_lse", "col_conf", "dual")
+
+
+def match_dual_packed(scene_rows, model_rows, model_xyz, mask, B, N, M, precision=MATCH_BF16X3, gamma=16.0):
+    """Soft matching in both directions from one pass (include/gdm.h THE DUAL RULE): match_soft_packed's five outputs and
+    match_twoway_packed's col_idx / col_sim, bit for bit, plus col_lse f32[B,M] (the log-sum-exp of a vertex's column over the masked
+    points of the crop, -inf where there is none), col_conf f32[B,M] (the share of that column its best point holds, 0 where
+    col_idx = -1) and dual f32[B,N] (conf times the share of the arg-max vertex's column that the point holds; 0 for an unmasked
+    point; 0 <= dual <= conf).  -> the ten tensors in the order of DUAL_KEYS.  No [N, M] tensor; 0 < gamma <= 40 and M <= 16384,
+    refused otherwise."""
+    L = _lib.lib()
+    model_xyz = _dev(model_xyz, torch.float32, "model_xyz")
+    mask = _dev(mask, torch.uint8, "mask")
+    if tuple(model_xyz.shape) != (M, 3):
+        raise ValueError("match_dual_packed: model_xyz is %s, expected (%d, 3)" % (tuple(model_xyz.shape), M))
+    if tuple(mask.shape) != (B, N):
+        raise ValueError("match_dual_packed: mask is %s, expected (%d, %d)" % (tuple(mask.shape), B, N))
+    dev = scene_rows.device
+    part = _workspace(L.gdm_match_dual_partial_bytes(B, N, M), dev)
+    f32, i32 = torch.float32, torch.int32
+    out = [torch.empty(shape, dtype=dt, device=dev) for shape, dt in
+           (((B, N), i32), ((B, N), f32), ((B, N), f32), ((B, N), f32), ((B, N, 3), f32),
+            ((B, M), i32), ((B, M), f32), ((B, M), f32), ((B, M), f32), ((B, N), f32))]
+    call("gdm_match_dual_packed_hip", scene_rows, model_rows, model_xyz, mask, B, N, M, precision, float(gamma), *out, part, part.numel())
+    return tuple(out)
+
+
+def match_dual(scene, model, model_xyz, mask, precision=MATCH_BF16X3, gamma=16.0):
+    """scene f32[B,128,N], model f32[128,M], model_xyz f32[M,3], mask u8[B,N] -> the ten tensors of match_dual_packed: both packs,
+    then match_dual_packed."""
+    scene = _dev(scene, torch.float32, "scene")
+    model = _dev(model, torch.float32, "model")
+    if model.dim() == 3:
+        assert model.shape[0] == 1
+        model = model[0]
+    B, D, N = scene.shape
+    assert model.shape[0] == D
+    srows, mrows = match_pack2(scene, model, precision)
+    return match_dual_packed(srows, mrows, model_xyz, mask, B, N, model.shape[1], precision, gamma)
+
+
 def match_cycle(cld_rgb_nrm, best_idx, col_idx, mask, radius):
     """The cycle-consistency filter (include/gdm.h THE CYCLE RULE): cld_rgb_nrm f32[B,9,N] (rows 0-2 = xyz), best_idx i32[B,N], col_idx
     i32[B,M], mask u8[B,N]; a masked point is kept iff the point its vertex picks back lies within `radius` of it (radius = 0: the

@@ -53,10 +53,12 @@ def solve_poses(res, cld_rgb_nrm, model_xyz, min_points=5, method="kabsch", rans
     match_err = inlier_dist (m) and fix_percent; `seed` selects the hashed samples.  method="consensus": the consensus fit
     (consensus_poses) with consensus_tau, consensus_seeds and inlier_dist.
     method="kabsch" only: weights="conf" weighs every pair by res["conf"], targets="soft" pairs the scene point with
-    res["soft_xyz"] instead of its arg-max vertex (both from soft matching, matching.match_frames(soft=...)); either takes the
-    weighted entries (solve_poses_weighted).  The defaults are the unweighted launches."""
-    if weights not in ("none", "conf") or targets not in ("vertex", "soft"):
-        raise ValueError("solve_poses: weights must be 'none' or 'conf' and targets 'vertex' or 'soft', got %r, %r" % (weights, targets))
+    res["soft_xyz"] instead of its arg-max vertex (both from soft matching, matching.match_frames(soft=...)); weights="dual" weighs
+    every pair by res["dual"], the dual-softmax confidence (matching.match_frames(soft=..., dual=True)); each takes the weighted
+    entries (solve_poses_weighted).  The defaults are the unweighted launches."""
+    if weights not in ("none", "conf", "dual") or targets not in ("vertex", "soft"):
+        raise ValueError("solve_poses: weights must be 'none', 'conf' or 'dual' and targets 'vertex' or 'soft', got %r, %r"
+                         % (weights, targets))
     soft = weights != "none" or targets != "vertex"
     if method == "ransac":
         if soft:
@@ -72,10 +74,11 @@ def solve_poses(res, cld_rgb_nrm, model_xyz, min_points=5, method="kabsch", rans
     if method != "kabsch":
         raise ValueError("solve_poses: method must be 'kabsch', 'ransac' or 'consensus', got %r" % (method,))
     if soft:
-        need = [k for k, on in (("conf", weights == "conf"), ("soft_xyz", targets == "soft")) if on and k not in res]
+        need = [k for k, on in (("conf", weights == "conf"), ("dual", weights == "dual"), ("soft_xyz", targets == "soft"))
+                if on and k not in res]
         if need:
             raise ValueError("solve_poses: weights=%r / targets=%r need the soft matching outputs %s in res" % (weights, targets, need))
-        w = res["conf"] if weights == "conf" else torch.ones(res["mask"].shape, dtype=torch.float32, device=res["mask"].device)
+        w = res[weights] if weights != "none" else torch.ones(res["mask"].shape, dtype=torch.float32, device=res["mask"].device)
         return solve_poses_weighted(res, cld_rgb_nrm, model_xyz, w, res["soft_xyz"] if targets == "soft" else None, min_points)
     st = kabsch_stats(res, cld_rgb_nrm, model_xyz)
     B = st.shape[0]
@@ -738,7 +741,7 @@ def cycle_filter(res, cld_rgb_nrm, radius=CYCLE_RADIUS):
     mask, best_idx, col_idx): a masked point stays iff the point its matched vertex picks back lies within `radius` of it.
     -> (pair_mask u8[B,N], pair_count i32[B], cycle_d2 f32[B,N]).  One launch, no host synchronisation."""
     if "col_idx" not in res:
-        raise ValueError("cycle_filter: res has no col_idx (match with twoway=True)")
+        raise ValueError("cycle_filter: res has no col_idx (match with twoway=True, or with soft and dual=True)")
     return ops.match_cycle(cld_rgb_nrm, res["best_idx"], res["col_idx"], res["mask"], radius)
 
 
@@ -782,7 +785,7 @@ def _pair_filter(o, res, cld_rgb_nrm, who):
     if not (np.isfinite(radius) and radius >= 0):
         raise ValueError("%s: cycle_radius=%r must be finite and >= 0" % (who, radius))
     if "col_idx" not in res:
-        raise ValueError("%s: pair_filter='cycle' needs col_idx in res (match with twoway=True)" % who)
+        raise ValueError("%s: pair_filter='cycle' needs col_idx in res (match with twoway=True, or with soft and dual=True)" % who)
     pair_mask, pair_count, _ = cycle_filter(res, cld_rgb_nrm, radius)
     return dict(res, mask=pair_mask), dict(pair_mask=pair_mask, pair_count=pair_count)
 
@@ -791,7 +794,7 @@ def estimate_poses(res, cld_rgb_nrm, model_xyz, pose_fit="kabsch", icp_iters=0, 
     """The pose stage of the pipeline: solve_poses with `pose_fit` ("kabsch" | "ransac" | "consensus"), then `icp_iters` ICP iterations
     when > 0.  pose_opts (optional dict): ransac_iters, ransac_inlier_dist, ransac_fix_percent, seed, consensus_tau, consensus_seeds,
     consensus_inlier_dist (pose_fit="consensus": consensus_poses' tau, seeds and inlier_dist), icp_tolerance, icp_reject_dist,
-    min_points, and for pose_fit="kabsch" weights ("none" | "conf") and targets ("vertex" | "soft") (solve_poses; RANSAC and ICP
+    min_points, and for pose_fit="kabsch" weights ("none" | "conf" | "dual") and targets ("vertex" | "soft") (solve_poses; RANSAC and ICP
     keep the hard pairs); icp_metric ("point" | "plane"): "plane" refines with refine_icp_plane instead of refine_icp, needs the
     model's unit normals model_nrm f32[M,3], takes icp_huber and icp_normal_gate as well (icp_tolerance then defaults to 1e-4) and adds
     icp_status; pair_filter ("none" | "cycle"): "cycle" needs a two-way match (col_idx in res), passes the pairs through cycle_filter

@@ -104,8 +104,14 @@ def build_parser():
                    help="test, --pose-fit consensus: inlier distance in metres of the hypothesis count and the refit")
     p.add_argument("--match-gamma", dest="match_gamma", type=float, default=None,
                    help="test: soft matching at this temperature (0 < G <= 40): per-point confidences, soft vertices and a csv score")
-    p.add_argument("--pose-weights", dest="pose_weights", type=str, default="none", choices=["none", "conf"],
-                   help="test, --pose-fit kabsch: weigh the pairs by the matching confidence (needs --match-gamma)")
+    p.add_argument("--match-dual", dest="match_dual", action="store_true",
+                   help="test, with --match-gamma: dual-softmax matching (include/gdm.h THE DUAL RULE): the soft outputs, each vertex's "
+                        "best masked point and the dual confidence from one pass; --pair-filter cycle then goes with --match-gamma")
+    p.add_argument("--match-score", dest="match_score", type=str, default="conf", choices=["conf", "dual"],
+                   help="test, --match-gamma: what the csv score averages over the masked points (dual needs --match-dual)")
+    p.add_argument("--pose-weights", dest="pose_weights", type=str, default="none", choices=["none", "conf", "dual"],
+                   help="test, --pose-fit kabsch: weigh the pairs by the matching confidence (needs --match-gamma) or by the dual-softmax "
+                        "confidence (needs --match-dual)")
     p.add_argument("--pose-targets", dest="pose_targets", type=str, default="vertex", choices=["vertex", "soft"],
                    help="test, --pose-fit kabsch: fit to the arg-max vertex or to the expected model coordinate (needs --match-gamma)")
     p.add_argument("--pair-filter", dest="pair_filter", type=str, default="none", choices=["none", "cycle"],
@@ -613,6 +619,18 @@ def train(args):
     return trainer
 
 
+def check_dual_flags(args):
+    """The -state=test flags of dual-softmax matching, checked against one another: -> whether --match-dual is on."""
+    dual = bool(getattr(args, "match_dual", False))
+    if dual and getattr(args, "match_gamma", None) is None:
+        raise SystemExit("train_lm test: --match-dual needs --match-gamma")
+    if getattr(args, "pose_weights", "none") == "dual" and not dual:
+        raise SystemExit("train_lm test: --pose-weights dual needs --match-dual")
+    if getattr(args, "match_score", "conf") == "dual" and not dual:
+        raise SystemExit("train_lm test: --match-score dual needs --match-dual")
+    return dual
+
+
 def test(args):
     """train_lm.py:317-373 without the BOP evaluator: ONE MODEL PER OBJECT of the dataset (:331-340), every batch dispatched per
     instance by its `cls_id` (:298-314) -- grouped per object into true batches here -- then dense matching and the batched GPU
@@ -660,6 +678,7 @@ def test(args):
     elif getattr(args, "icp_huber", None) is not None or getattr(args, "icp_normal_gate", None) is not None:
         raise SystemExit("train_lm test: --icp-huber / --icp-normal-gate go with --icp-metric plane")
     match_gamma = getattr(args, "match_gamma", None)
+    match_dual = check_dual_flags(args)
     soft_pose = (getattr(args, "pose_weights", "none"), getattr(args, "pose_targets", "vertex")) != ("none", "vertex")
     if soft_pose and match_gamma is None:
         raise SystemExit("train_lm test: --pose-weights conf / --pose-targets soft need --match-gamma")
@@ -669,10 +688,13 @@ def test(args):
         pose_kw["pose_opts"].update(weights=args.pose_weights, targets=args.pose_targets)
     if match_gamma is not None:
         pose_kw["match_gamma"] = match_gamma
+    if match_dual:
+        pose_kw["match_dual"] = True
     pair_filter = getattr(args, "pair_filter", "none")
     if pair_filter == "cycle":
-        if match_gamma is not None:
-            raise SystemExit("train_lm test: --pair-filter cycle does not go with --match-gamma (there is no soft two-way kernel)")
+        if match_gamma is not None and not match_dual:
+            raise SystemExit("train_lm test: --pair-filter cycle does not go with --match-gamma (there is no soft two-way kernel) unless "
+                             "--match-dual is given")
         pose_kw["pose_opts"].update(pair_filter="cycle", cycle_radius=pose.CYCLE_RADIUS if getattr(args, "cycle_radius", None) is None
                                     else args.cycle_radius)
     elif getattr(args, "cycle_radius", None) is not None:
@@ -729,6 +751,8 @@ def test(args):
                 out["score"] = out["verify_score"].float()                 # the csv score
             else:
                 out = infer.run_multi_object(model_dict, cu, cls, **pose_kw)
+            if getattr(args, "match_score", "conf") == "dual" and verify_names is None:
+                out["score"] = ops.match_score(out["dual"], out["mask"])  # the csv score: the mean dual confidence of the masked points
             torch.cuda.synchronize()
             results.append(dict(time=time.perf_counter() - t0, cls_id=cls, count=out["mask"].sum(dim=1).cpu(), best_idx=out["best_idx"].cpu(),
                                 best_sim=out["best_sim"].cpu(), mask=out["mask"].cpu(), RT=out["RT"].cpu(), valid=out["valid"].cpu()))
@@ -736,6 +760,8 @@ def test(args):
                 results[-1].update(score=out["score"].cpu(), verify_which=out["verify_which"].cpu(), verify_counts=out["verify_counts"].cpu())
             elif "score" in out:
                 results[-1].update(score=out["score"].cpu(), conf=out["conf"].cpu())
+            if "dual" in out:
+                results[-1].update(dual=out["dual"].cpu())
             if "pair_count" in out:
                 results[-1].update(pair_mask=out["pair_mask"].cpu(), pair_count=out["pair_count"].cpu())
                 for i, cid in enumerate(cls):

@@ -231,6 +231,32 @@ int gdm_match_twoway_packed_hip(const void* scene_rows, const void* model_rows, 
 int gdm_match_cycle_hip(const float* scene_xyz, long scene_bstride, int pt_stride, int ch_stride, const int32_t* best_idx,
                         const int32_t* col_idx, const uint8_t* mask, int B, int N, int M, float radius, uint8_t* pair_mask,
                         int32_t* pair_count, float* cycle_d2, void* stream);
+/* THE DUAL RULE.  Soft matching in both directions from one pass over the similarities: the row softmax of
+ * gdm_match_soft_packed_hip, the column arg-max of gdm_match_twoway_packed_hip and the column softmax under the mask, whose product
+ * with the row softmax is the dual-softmax confidence of a pair.  Inputs as those two entries take them: B*N packed scene rows, M
+ * packed model rows, model_xyz f32[M,3], mask u8[B,N], 0 < gamma <= GDM_MATCH_SOFT_MAX_GAMMA.  With k2 = gamma * log2(e) in fp32,
+ * w_ij = exp2(fma(sim_ij, k2, -k2)): the soft kernel's own two instructions on the same similarity bits.
+ *   best_idx, best_sim, lse, conf, soft_xyz   those of gdm_match_soft_packed_hip, bit for bit, for every row, masked or not
+ *   col_idx i32[B,M], col_sim f32[B,M]        those of gdm_match_twoway_packed_hip, bit for bit
+ *   Zc[b,j]  (in `partial`)                   the sum of w_ij over the points i of crop b with mask != 0, in fp32 and a fixed order
+ *   col_lse f32[B,M]  = gamma + log Zc        the logarithm in fp64; -inf where the crop has no masked point
+ *   col_conf f32[B,M] = w(col_sim) / Zc       w recomputed by the same two instructions, the quotient in fp64; 0 where col_idx = -1.
+ *                                             The share of the column that the vertex's best point holds, in (0, 1]
+ *   dual f32[B,N]     = conf_i * (w_ij / Zc[b,j]) at j = best_idx[i] for a point with mask != 0, from best_sim's and conf's fp32
+ *                                             values, quotient and product in fp64, rounded once; 0 for any other point
+ * Point i is one of Zc's terms and fp32 addition of non-negative terms is monotone, so w_ij <= Zc and 0 <= dual <= conf <= 1.
+ * The order of Zc: the rows are cut into blocks of 256 that start at each crop's first row (none spans a crop); inside a block a
+ * lane adds its 16 rows in ascending order, the two half-waves add by one shuffle, the 8 waves are added in ascending order, and
+ * the blocks of a crop in ascending order.  No [R, M] tensor, no floating-point atomic: two launches give the same bytes.  The
+ * workspace `partial` (gdm_match_dual_partial_bytes(B, N, M), 16-byte aligned) holds the soft launch's partials, the two-way
+ * launch's keys (reset inside the call), one column partial per row block and Zc; the result does not depend on what it held.
+ * Limits: those of both entries (B*N < 2^22, 1 <= M <= GDM_MATCH_SOFT_MAX_M); they, a NULL argument, a non-positive size, a bad
+ * precision, a gamma outside its range (a NaN included) or rows off a 16-byte boundary are refused with GDM_EINVAL before any launch. */
+size_t gdm_match_dual_partial_bytes(int B, int N, int M);
+int gdm_match_dual_packed_hip(const void* scene_rows, const void* model_rows, const float* model_xyz, const uint8_t* mask, int B, int N,
+                              int M, int precision, float gamma, int32_t* best_idx, float* best_sim, float* lse, float* conf,
+                              float* soft_xyz, int32_t* col_idx, float* col_sim, float* col_lse, float* col_conf, float* dual,
+                              void* partial, size_t partial_bytes, void* stream);
 
 /* seg f32[B,2,N] -> mask u8[B,N] = (argmax over the 2 classes == 1) (evaluator.py:79-83),
  * count i32[B] of selected points (zeroed inside).                                        */
